@@ -28,6 +28,9 @@ Besides the contract's keys the JSON line carries (rank 0, N = 1 only; none of i
                 of the five training sizes, evaluation forward on 8 x 75k nodes, kernel averages and byte fractions
   sir           the Monte-Carlo label generator on configs[2]'s shape (10 000 sims x T = 20)
 With --gpus N > 1 the line keeps `roofline` (rank 0's kernel) and adds every rank's elapsed time (`rank_elapsed_s`).
+
+--dump-outputs DIR writes what rank 0's last timed step returned (S, I, R; see `dump_outputs`) as DIR/<name>.npy, so that
+two builds can be compared output for output: graph, weights and samples come from fixed seeds.
 """
 import argparse
 import json
@@ -45,6 +48,7 @@ import numpy as np  # noqa: E402
 HBM_PEAK_GBS = 8000.0          # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 HBM_ACHIEVABLE_GBS = 6290.0    # measured float4 copy, same guide
 GATHER_CEILING_GBS = (7400.0, 7900.0)   # same guide, "Indexed rows": uniformly random rows of a 151 MB table, chip-wide
+DUMP_BUDGET_BYTES = 64 * 10**6          # all files of --dump-outputs together
 
 
 def step_bytes(n, nnz, H, projected_R=True):
@@ -612,6 +616,26 @@ def bench_sir(lib, dev, n, m, sims, T):
     return out, (g, rp, ci, seeds, 0.3, 0.2)
 
 
+def dump_outputs(outs, out_dir, n):
+    """The last timed step's S, I, R as its caller receives them (one [grid points, chunk * n] triple per chunk of
+    samples), concatenated over the chunks and written as DIR/{S,I,R}.npy, float32 [grid points, samples, nodes].  All
+    nodes when the three files fit DUMP_BUDGET_BYTES, else the same fixed seeded sample of node ids (sorted) in each."""
+    import torch
+    n_out = int(outs[0][0].shape[0])
+    B = sum(int(o[0].shape[1]) for o in outs) // n
+    k = min(n, max(1, (DUMP_BUDGET_BYTES - 3 * 4096) // (3 * n_out * B * 4)))    # 4096: room for the .npy headers
+    nodes = np.arange(n) if k == n else np.sort(np.random.default_rng(0).choice(n, size=k, replace=False))
+    idx = torch.from_numpy(nodes).to(outs[0][0].device)
+    os.makedirs(out_dir, exist_ok=True)
+    shapes = {}
+    for j, name in enumerate("SIR"):
+        a = torch.cat([o[j].reshape(n_out, -1, n).index_select(2, idx) for o in outs], 1).cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float32, copy=False))
+        shapes[name] = list(a.shape)
+    return {"dir": out_dir, "arrays": shapes, "dtype": "float32",
+            "nodes": "all" if k == n else f"{k} of {n}: sorted numpy default_rng(0).choice without replacement"}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -628,7 +652,13 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true", help="skip the train-step and Monte-Carlo legs")
     ap.add_argument("--cpu-steps", type=int, default=59, help="Euler steps of the bounded CPU-baseline sample")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write S, I, R of rank 0's last timed step as DIR/<name>.npy "
+                         "(float32, at most 64 MB in all: a fixed seeded node sample of larger outputs; "
+                         "bench_outputs/ is ignored by git)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -721,6 +751,7 @@ def main():
     S, I, R = outs[0]
     tot = (S + I + R)
     ok = bool(torch.isfinite(tot).all().item()) and abs(float(tot.mean().item()) - 1.0) < 1e-4
+    dumped = dump_outputs(outs, args.dump_outputs, n) if args.dump_outputs and rank == 0 else None
 
     units = world * B * n * n_steps * args.steps
     value = units / elapsed
@@ -769,6 +800,8 @@ def main():
     }
 
     result["rank_elapsed_s"] = {"min": min(rank_elapsed), "max": max(rank_elapsed), "per_rank": rank_elapsed}
+    if dumped is not None:
+        result["dumped_outputs"] = dumped
     if world > 1 and not args.no_secondary:
         # data-parallel training step on configs[1]'s shape, 8 samples per rank: local forward + adjoint backward, ONE flat
         # all-reduce of the 4 809-float gradient, identical Adam step on every rank; the all-reduce is timed on its own
