@@ -4,6 +4,23 @@
 
 #define BWD_NWG 768     // 3 workgroups per CU (52 KB of LDS each) on 256 CUs
 
+// lanes per row of the generic-H kernels: H/4 rounded up to a power of two, and the switch over it
+static inline int lpr_of(int H) {
+    int need = H / 4, l = 1;
+    while (l < need) l <<= 1;
+    return l;
+}
+
+#define BWD_DISPATCH(lpr, ...)                                   \
+    switch (lpr) {                                               \
+        case 1: { constexpr int LPR = 1; __VA_ARGS__; } break;   \
+        case 2: { constexpr int LPR = 2; __VA_ARGS__; } break;   \
+        case 4: { constexpr int LPR = 4; __VA_ARGS__; } break;   \
+        case 8: { constexpr int LPR = 8; __VA_ARGS__; } break;   \
+        case 16: { constexpr int LPR = 16; __VA_ARGS__; } break; \
+        default: { constexpr int LPR = 32; __VA_ARGS__; } break; \
+    }
+
 // partial-buffer layout per workgroup (floats)
 struct PartLayout {
     int H;
@@ -24,6 +41,22 @@ int gn_launch_tiny_bwd64(const gnode_graph_s* g, long rows, const float* x, cons
                          int n_steps, const int32_t* out_rows_host, int n_out, const float* sol, const float* gS,
                          const float* gI, const float* gR, float* part,
                          const float* keep /* the forward's kept activations, or null = recompute */, hipStream_t st);
+
+// Pieces of gnode_backward_f32's generic path, shared with the RK4 adjoint (gnode_rhs_vjp.hip).  Each raises *slots_used to
+// the partial slots it wrote.
+// head backward at one grid point: a[3 slabs] += its VJP, linear3 / linearS2 partials into slots of PartLayout{H}
+int gn_launch_head_bwd(long rows, int H, const float* Ysol, const float* gS, const float* gI, const float* gR,
+                       const gnode_params* p, float* a, float* part, int* slots_used, hipStream_t st);
+// encoder backward on a_0: linearS1 partials
+int gn_launch_enc_bwd(long rows, int H, const float* a, const float* sol0, const float* x, float* part, int* slots_used,
+                      hipStream_t st);
+// fixed-order sum of slots [0, nwg) of PartLayout{H} into the 8 gradients (overwritten)
+int gn_launch_reduce_all(const float* part, int nwg, int H, const gnode_params* grads, hipStream_t st);
+// the same for slots of [H*H gW | H gb] into dW, db
+int gn_launch_reduce_parts(const float* part, int nwg, int H, float* dW, float* db, hipStream_t st);
+// node MLP Z = sigmoid(X W^T + b) of nrows rows (gnode_ode.hip)
+int gn_launch_mlp_any(const gnode_graph_s* g, const float* X, const float* W, const float* b, float* Z, long nrows, int H,
+                      hipStream_t st);
 
 // H = 128: a += dt dpre W, gW, gb on the matrix cores (gnode_h128.hip); raises *slots_used to its grid size
 int gn_launch_bwd_mlp128(const gnode_graph_s* g, const float* dpre, const float* Ysol, const float* W, float dt, float* a, long rows,

@@ -1094,22 +1094,6 @@ __global__ __launch_bounds__(256) void k_reduce_parts(const float* __restrict__ 
 int gn_launch_mlp_any(const gnode_graph_s* g, const float* X, const float* W, const float* b, float* Z, long nrows, int H,
                       hipStream_t st);
 
-static int lpr_of(int H) {
-    int need = H / 4, l = 1;
-    while (l < need) l <<= 1;
-    return l;
-}
-
-#define BWD_DISPATCH(lpr, ...)                                   \
-    switch (lpr) {                                               \
-        case 1: { constexpr int LPR = 1; __VA_ARGS__; } break;   \
-        case 2: { constexpr int LPR = 2; __VA_ARGS__; } break;   \
-        case 4: { constexpr int LPR = 4; __VA_ARGS__; } break;   \
-        case 8: { constexpr int LPR = 8; __VA_ARGS__; } break;   \
-        case 16: { constexpr int LPR = 16; __VA_ARGS__; } break; \
-        default: { constexpr int LPR = 32; __VA_ARGS__; } break; \
-    }
-
 __global__ void k_extract_bg(const float* __restrict__ bgslab, long rows, int H, float* __restrict__ beta,
                              float* __restrict__ gamma) {
     const long r = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1457,5 +1441,57 @@ extern "C" int gnode_backward_status(int64_t rows, int32_t H, const void* worksp
 extern "C" int gnode_backward_phase_ticks(int64_t rows, int32_t H, const void* workspace, uint64_t* ticks8_host) {
     const PersCtl* ctl = (const PersCtl*)((const char*)workspace + backward_fixed_bytes(rows, H) - gn_pers64_ctl_bytes());
     GN_HIP(hipMemcpy(ticks8_host, ctl->prof, 8 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// --------------------------------------------------------------------------- pieces shared with the RK4 adjoint
+// (gnode_rhs_vjp.hip): the same kernels and launch shapes as gnode_backward_f32's `head` step, encoder step and final
+// reduction above.
+int gn_launch_head_bwd(long rows, int H, const float* Ysol, const float* gS, const float* gI, const float* gR,
+                       const gnode_params* p, float* a, float* part, int* slots_used, hipStream_t st) {
+    const int lpr = lpr_of(H), rpw = 256 / lpr;
+    const size_t lds = (size_t)rpw * (4 * H + 9) * sizeof(float);
+    const int hgrid = (int)std::min<long>(BWD_NWG, std::max<long>(1, (rows + rpw - 1) / rpw));
+    *slots_used = std::max(*slots_used, hgrid);
+    BWD_DISPATCH(lpr, hipLaunchKernelGGL(k_head_bwd<LPR>, dim3(hgrid), dim3(256), lds, st, Ysol, rows, H, gS, gI, gR,
+                                         p->linear3_weight, p->linear3_bias, p->linearS2_weight, p->linearS2_bias, a, part));
+    GN_LAUNCH_CHECK();
+    return 0;
+}
+
+int gn_launch_enc_bwd(long rows, int H, const float* a, const float* sol0, const float* x, float* part, int* slots_used,
+                      hipStream_t st) {
+    const int lpr = lpr_of(H), rpw = 256 / lpr;
+    const size_t lds = (size_t)rpw * 2 * H * sizeof(float);
+    const int egrid = (int)std::min<long>(BWD_NWG, std::max<long>(1, (rows + rpw - 1) / rpw));
+    *slots_used = std::max(*slots_used, egrid);
+    BWD_DISPATCH(lpr, hipLaunchKernelGGL(k_enc_bwd<LPR>, dim3(egrid), dim3(256), lds, st, a, sol0, x, rows, H, part));
+    GN_LAUNCH_CHECK();
+    return 0;
+}
+
+int gn_launch_reduce_all(const float* part, int nwg, int H, const gnode_params* grads, hipStream_t st) {
+    const PartLayout L{H};
+    GradDst gd;
+    gd.dst[0] = (float*)grads->odefunc_linear_weight; gd.dst[1] = (float*)grads->odefunc_linear_bias;
+    gd.dst[2] = (float*)grads->linear3_weight;        gd.dst[3] = (float*)grads->linear3_bias;
+    gd.dst[4] = (float*)grads->linearS2_weight;       gd.dst[5] = (float*)grads->linearS2_bias;
+    gd.dst[6] = (float*)grads->linearS1_weight;       gd.dst[7] = (float*)grads->linearS1_bias;
+    const int offs[9] = {L.oW(), L.ob(), L.ow3(), L.ob3(), L.ow2(), L.ob2(), L.ow1(), L.ob1(), L.total()};
+    for (int k = 0; k < 9; ++k) gd.off[k] = offs[k];
+    hipLaunchKernelGGL(k_reduce_parts, dim3((L.total() + 15) / 16), dim3(256), 0, st, part, nwg, L.total(), gd);
+    GN_LAUNCH_CHECK();
+    return 0;
+}
+
+int gn_launch_reduce_parts(const float* part, int nwg, int H, float* dW, float* db, hipStream_t st) {
+    const int total = H * H + H;                 // slots of [H*H gW | H gb]
+    GradDst gd;
+    for (int k = 0; k < 8; ++k) gd.dst[k] = nullptr;
+    gd.dst[0] = dW; gd.dst[1] = db;
+    gd.off[0] = 0; gd.off[1] = H * H;
+    for (int k = 2; k < 9; ++k) gd.off[k] = total;
+    hipLaunchKernelGGL(k_reduce_parts, dim3((total + 15) / 16), dim3(256), 0, st, part, nwg, total, gd);
+    GN_LAUNCH_CHECK();
     return 0;
 }

@@ -2,8 +2,10 @@
 
 Inference (no_grad, or nothing requires grad) calls the fused forward and never
 materialises the trajectory.  Training saves `sol` as torchdiffeq's
-odeint_adjoint does and runs the adjoint-Euler backward in
-libgnode_hip.so.
+odeint_adjoint does and runs its adjoint backward in libgnode_hip.so: the
+adjoint-Euler sweep (method='euler') or the RK4 (3/8 rule)
+adjoint (method='rk4').  `rhs` is ODEfunc.forward as an
+autograd node over the RHS and its vector-Jacobian product.
 """
 from __future__ import annotations
 
@@ -46,6 +48,34 @@ def forward_with_grad(graph, x2d, params, dts, method="euler", out_rows=None):
         return S, I, R
     keys = tuple(params.keys())
     return _GNODEForward.apply(graph, x2d, dts, method, out_rows, keys, *[params[k] for k in keys])
+
+
+class _RHSFunction(torch.autograd.Function):
+    """ODEfunc.forward (ode_nn_ngraph_sim.py:58-96) as an autograd node: the value from `ops.rhs`, the backward from ONE
+    `ops.rhs_vjp` pass -- what torchdiffeq's odeint_adjoint asks of the reference's ODEfunc (torch.autograd.grad of
+    func(t, y) with respect to y and the parameters)."""
+
+    @staticmethod
+    def forward(ctx, graph, x, W, b):
+        ctx.graph = graph
+        ctx.save_for_backward(x, W, b)
+        return ops.rhs(graph, x, W, b)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        x, W, b = ctx.saved_tensors
+        _, want_x, want_W, want_b = ctx.needs_input_grad
+        if not (want_x or want_W or want_b):
+            return None, None, None, None
+        _, dx, dW, db = ops.rhs_vjp(ctx.graph, x, W.detach(), b.detach(), g.contiguous(), want_f=False,
+                                    want_y=want_x, want_W=want_W, want_b=want_b)
+        return None, dx, dW, db
+
+
+def rhs(graph, x, W, b):
+    """Differentiable RHS: x [4*rows, H] -> dx; gradients flow to x, W and b as they require it."""
+    return _RHSFunction.apply(graph, x, W, b)
 
 
 class _L1LossSum(torch.autograd.Function):

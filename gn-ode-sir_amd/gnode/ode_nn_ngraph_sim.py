@@ -12,13 +12,17 @@ import numpy as np
 import torch
 import torch.nn as nn
 
+from . import autograd as _autograd
 from . import ops
 from .graph import DeviceGraph
 
 
 class ODEfunc(nn.Module):
-    def __init__(self, A, beta, gamma, hidden1, device):
+    def __init__(self, A, beta, gamma, hidden1, device, *, differentiable=False):
         super().__init__()
+        # extension: differentiable=True makes forward an autograd node (gnode.autograd.rhs) whenever grad is enabled, so a
+        # caller's own integrator (or torchdiffeq) can train through it; the default keeps the no_grad RHS
+        self.differentiable = differentiable
         self.A = A
         self.beta = beta          # unused by forward, as in the reference (:42-43)
         self.gamma = gamma
@@ -32,6 +36,8 @@ class ODEfunc(nn.Module):
 
     def forward(self, t, x):
         """x [4*B*n, H] -> dx (reference :58-96).  t is unused there too."""
+        if self.differentiable and torch.is_grad_enabled():
+            return _autograd.rhs(self.graph, x, self.linear.weight, self.linear.bias)
         with torch.no_grad():
             return ops.rhs(self.graph, x, self.linear.weight, self.linear.bias)
 

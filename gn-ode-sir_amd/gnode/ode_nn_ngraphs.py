@@ -20,13 +20,15 @@ import collections
 import torch
 import torch.nn as nn
 
+from . import autograd as _autograd
 from . import ops
 from .graph import DeviceGraph, concat_csr, csr_arrays
 
 
 class ODEfunc(nn.Module):
-    def __init__(self, A_list, hidden1, device):
+    def __init__(self, A_list, hidden1, device, *, differentiable=False):
         super().__init__()
+        self.differentiable = differentiable         # extension: see gnode.ode_nn_ngraph_sim.ODEfunc
         self.A_list = A_list
         self.ln = nn.LayerNorm(hidden1)             # unused in the reference forward; state_dict parity
         self.linear = nn.Linear(hidden1, hidden1)
@@ -63,6 +65,9 @@ class ODEfunc(nn.Module):
         g = self.graph_for(x[3, :, 2])
         if g.n != x.size(1):
             raise ValueError(f"markers describe {g.n} nodes but the state has {x.size(1)}")
+        if self.differentiable and torch.is_grad_enabled():
+            flat = x.reshape(4 * x.size(1), x.size(2))
+            return _autograd.rhs(g, flat, self.linear.weight, self.linear.bias).view_as(x)
         with torch.no_grad():
             flat = x.reshape(4 * x.size(1), x.size(2))
             return ops.rhs(g, flat, self.linear.weight, self.linear.bias).view_as(x)

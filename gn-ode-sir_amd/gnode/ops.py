@@ -78,6 +78,30 @@ def rhs(graph: DeviceGraph, x: torch.Tensor, W: torch.Tensor, b: torch.Tensor) -
     return dx
 
 
+def rhs_vjp(graph: DeviceGraph, y: torch.Tensor, W: torch.Tensor, b: torch.Tensor, v: torch.Tensor, want_f: bool = False,
+            want_y: bool = True, want_W: bool = True, want_b: bool = True):
+    """The RHS's vector-Jacobian product at y [4*rows, H] for the cotangent v (same shape): what torch autograd takes through
+    ODEfunc.forward (ode_nn_ngraph_sim.py:58-96).  Returns (f or None, dy or None, dW or None, db or None); f (want_f) is
+    the RHS itself, bit-identical to `rhs`."""
+    lib = _lib.load()
+    y, v, W, b = _f32c(y), _f32c(v), _f32c(W), _f32c(b)
+    graph.check_device(y)
+    if tuple(v.shape) != tuple(y.shape):
+        raise _lib.GnodeError(f"cotangent shape {tuple(v.shape)} != state shape {tuple(y.shape)}")
+    rows4, H = y.shape
+    if rows4 % 4:
+        raise _lib.GnodeError("state must have 4 slabs")
+    rows = rows4 // 4
+    f = torch.empty_like(y) if want_f else None
+    dy = torch.empty_like(y) if want_y else None
+    dW = torch.empty((H, H), dtype=torch.float32, device=y.device) if want_W else None
+    db = torch.empty((H,), dtype=torch.float32, device=y.device) if want_b else None
+    ws = _workspace(lib.gnode_rhs_vjp_workspace_bytes(graph.handle, rows, H), y.device)
+    _lib.check(lib.gnode_rhs_vjp_f32(graph.handle, _lib.ptr(y), _lib.ptr(W), _lib.ptr(b), _lib.ptr(v), _lib.ptr(f), _lib.ptr(dy),
+                                     _lib.ptr(dW), _lib.ptr(db), rows, H, _lib.ptr(ws), ws.numel(), _lib.stream_ptr()))
+    return f, dy, dW, db
+
+
 def forward(graph: DeviceGraph, x2d: torch.Tensor, params: dict, dts: np.ndarray, method: str = "euler",
             out_rows: np.ndarray | None = None, want_sol: bool = False, workspace: torch.Tensor | None = None,
             want_keep: bool | None = None, persist: bool | None = None):
@@ -154,11 +178,13 @@ def forward_status() -> int:
 
 def backward(graph: DeviceGraph, x2d: torch.Tensor, params: dict, dts: np.ndarray, method: str, out_rows, sol: torch.Tensor,
              gS: torch.Tensor, gI: torch.Tensor, gR: torch.Tensor, keep="auto", persist: bool | None = None) -> dict:
-    """Adjoint-Euler parameter gradients (torchdiffeq odeint_adjoint semantics)
+    """Adjoint parameter gradients (torchdiffeq odeint_adjoint semantics: Euler; rk4)
     given the saved trajectory `sol` and the upstream gradients of S, I, R ([n_out, rows]).
-    keep: the forward's kept activations ("auto": ``sol.gnode_keep`` when `forward` attached it; None: recompute)."""
+    keep: the forward's kept activations ("auto": ``sol.gnode_keep`` when `forward` attached it; None: recompute; Euler only)."""
+    if method == "rk4":
+        return _backward_rk4(graph, x2d, params, dts, out_rows, sol, gS, gI, gR)
     if method != "euler":
-        raise _lib.GnodeError("the adjoint backward is implemented for method='euler' (the reference's method)")
+        raise _lib.GnodeError(f"unknown method {method!r} (euler | rk4)")
     lib = _lib.load()
     x2d = _f32c(x2d)
     rows, H = x2d.shape[0], x2d.shape[1] - 3
@@ -188,6 +214,33 @@ def backward(graph: DeviceGraph, x2d: torch.Tensor, params: dict, dts: np.ndarra
         _lib.ptr(ws), ws.numel(), _lib.stream_ptr(), 0 if (PERSIST_DEFAULT if persist is None else persist) else FWD_PER_STEP,
         int(getattr(sol, "gnode_info", -1))))
     backward.last_workspace = (rows, H, ws)
+    return grads
+
+
+def _backward_rk4(graph: DeviceGraph, x2d, params: dict, dts, out_rows, sol, gS, gI, gR) -> dict:
+    """The RK4 (3/8 rule) adjoint of a method='rk4' forward: gnode_backward_rk4_f32."""
+    lib = _lib.load()
+    x2d = _f32c(x2d)
+    rows, H = x2d.shape[0], x2d.shape[1] - 3
+    dts = np.ascontiguousarray(dts, dtype=np.float32)
+    n_steps = int(dts.shape[0])
+    if out_rows is not None:
+        out_rows = np.ascontiguousarray(out_rows, dtype=np.int32)
+        n_out = int(out_rows.shape[0])
+    else:
+        n_out = n_steps + 1
+    for t in (gS, gI, gR):
+        if tuple(t.shape) != (n_out, rows):
+            raise _lib.GnodeError(f"upstream gradient shape {tuple(t.shape)} != {(n_out, rows)}")
+    grads = {k: torch.empty_like(params[k], memory_format=torch.contiguous_format) for k in PARAM_KEYS}
+    ws = _workspace(lib.gnode_backward_rk4_workspace_bytes(graph.handle, rows, H), x2d.device)
+    p, gp = pack_params({k: v.detach() for k, v in params.items()}), pack_params(grads)
+    _lib.check(lib.gnode_backward_rk4_f32(
+        graph.handle, _lib.ptr(x2d), C.byref(p), _lib.host_ptr(dts), n_steps,
+        _lib.host_ptr(out_rows) if out_rows is not None else None, n_out, _lib.ptr(_f32c(sol)),
+        _lib.ptr(_f32c(gS)), _lib.ptr(_f32c(gI)), _lib.ptr(_f32c(gR)), C.byref(gp), rows, H,
+        _lib.ptr(ws), ws.numel(), _lib.stream_ptr()))
+    backward.last_workspace = None               # (no persistent sweep on this path: nothing for backward_status to read)
     return grads
 
 

@@ -14,7 +14,7 @@
  *     past the call.  "host" pointers are ordinary memory, read before return.
  *   - `stream` is a hipStream_t passed as void* (NULL = the default stream).
  *     All work is enqueued on it.  gnode_rhs_f32, gnode_forward_f32,
- *     gnode_backward_f32 and gnode_l1_loss_f32 allocate nothing, synchronise nothing and keep nothing in
+ *     gnode_backward_f32, gnode_rhs_vjp_f32, gnode_backward_rk4_f32 and gnode_l1_loss_f32 allocate nothing, synchronise nothing and keep nothing in
  *     the graph handle: every byte of scratch (including the partial sums of long
  *     "hub" rows) is carved from the caller's workspace, so they can be captured
  *     into a hipGraph on first use and one handle may serve several streams (each
@@ -193,6 +193,36 @@ int gnode_backward_f32(gnode_graph_t g, const float* x, const gnode_params* p, c
                        const float* gS, const float* gI, const float* gR, const gnode_params* grads,
                        int64_t rows, int32_t H, void* workspace, size_t workspace_bytes, void* stream,
                        int32_t flags, int32_t sol_info);
+
+/* ---- RHS value and vector-Jacobian product -----------------------------------
+ * What torch autograd takes through ODEfunc.forward (ode_nn_ngraph_sim.py:58-96, multi: ode_nn_ngraphs.py:54-83) when
+ * torchdiffeq's adjoint calls torch.autograd.grad(func(t, y), (y, *params), v): for a cotangent v of the RHS output
+ *   y, v       device [4*rows, H], slabs S | I | R | beta-gamma (v's 4th slab is not read: that output is 0, :96)
+ *   f_out      NULL, or device [4*rows, H]: f(y), bit-identical to gnode_rhs_f32 on the same input
+ *   gy_out     NULL, or device [4*rows, H]: v^T df/dy (R slab 0: Z_R is dead in the reference, :62-66; beta-gamma slab:
+ *              column 0 d/dbeta, column 1 d/dgamma, the other columns 0)
+ *   gW_out     NULL, or device [H,H]: v^T df/dW     gb_out: NULL, or device [H]: v^T df/db   (overwritten)
+ * Each NULL output skips its work.  4 <= H <= 128, H % 4 == 0.  Deterministic (fixed-order reduction, no float atomics);
+ * allocates nothing and synchronises nothing (capturable).
+ *   workspace  device, >= gnode_rhs_vjp_workspace_bytes(g, rows, H) */
+size_t gnode_rhs_vjp_workspace_bytes(gnode_graph_t g, int64_t rows, int32_t H);
+int gnode_rhs_vjp_f32(gnode_graph_t g, const float* y, const float* W, const float* b, const float* v, float* f_out,
+                      float* gy_out, float* gW_out, float* gb_out, int64_t rows, int32_t H, void* workspace,
+                      size_t workspace_bytes, void* stream);
+
+/* ---- RK4 backward ------------------------------------------------------------
+ * The gradient of ODEBlock(method='rk4'): torchdiffeq 0.2.2's odeint_adjoint(..., method='rk4') (the 3/8 rule on the fixed
+ * grid; the reference's call site is ode_nn_ngraph_sim.py:168, which hard-codes 'euler') followed by autograd through the
+ * head and the encoder; the rule is restated in DESIGN.md section 7.  Arguments as gnode_backward_f32 without keep / flags /
+ * sol_info: `sol` is the trajectory of a gnode_forward_f32 call with method = 1 on THIS graph, same n_steps / out_rows;
+ * only its S, I, R slabs and grid point 0's 4th slab are read.  grads receive dL/dparam (overwritten).  Deterministic.
+ * Enqueue-only, one launch sequence per interval.
+ *   workspace  device, >= gnode_backward_rk4_workspace_bytes(g, rows, H) */
+size_t gnode_backward_rk4_workspace_bytes(gnode_graph_t g, int64_t rows, int32_t H);
+int gnode_backward_rk4_f32(gnode_graph_t g, const float* x, const gnode_params* p, const float* dt_host,
+                           int32_t n_steps, const int32_t* out_rows_host, int32_t n_out, const float* sol,
+                           const float* gS, const float* gI, const float* gR, const gnode_params* grads,
+                           int64_t rows, int32_t H, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- Monte-Carlo SIR labels ------------------------------------------------
  * sir_torch(G, seed_set, beta, gamma, sims, T): ode_nn.py:30-88.

@@ -1,0 +1,109 @@
+#!/usr/bin/env python3
+"""Golden vector-Jacobian products of the REFERENCE's ODEfunc (the RHS), float64.
+
+Runs only where the reference checkout is (import shims as in make_golden.py).  What is executed from the reference,
+unchanged: ``ODEfunc.forward`` of ode_nn_ngraph_sim.py:58-96 and of ode_nn_ngraphs.py:54-83; torch.autograd.grad of
+<v, f(t, x)> through it gives dx, dW, db -- what torchdiffeq's odeint_adjoint asks of it.  The classes run under
+torch.float64.
+
+  rhs_vjp_karate_B2_H64.npz      karate club, B = 2, H = 64
+  rhs_vjp_loops40_B3_H8.npz      the 40-node graph with self-loops, B = 3, H = 8
+  rhs_vjp_heavy_B1_H64.npz       synth.heavy_tail_csr(1500, 6000, seed=4): rows longer than the hub threshold (96)
+  rhs_vjp_karate_B1_H128.npz     karate club, B = 1, H = 128
+  rhs_vjp_multi_0-2-1_H8.npz     multi-graph batch of karate, er200, loops40 (picks 0, 2, 1), H = 8
+Each holds the seeds of its inputs (tests/rhs_vjp_restate.py rebuilds them), the edge list (or the generator's arguments),
+dx at the rows listed in "rows_kept" (indices into the [4*rows, H] state; all rows for the small cases), dW and db in full.
+"""
+import os
+import sys
+
+import numpy as np
+import networkx as nx
+import scipy.sparse as sp
+import torch
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(os.path.dirname(HERE))
+sys.path.insert(0, HERE)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, os.path.join(ROOT, "oracle"))
+sys.path.insert(0, os.path.join(ROOT, "gn-ode-sir_amd", "gnode"))
+import make_golden as MG  # noqa: E402
+import synth  # noqa: E402
+import rhs_vjp_restate as RV  # noqa: E402
+
+
+def _grads(f, x, v):
+    xt = torch.from_numpy(x).to(torch.float64).requires_grad_(True)
+    out = f.forward(torch.tensor(0.0), xt)
+    W, b = f.linear.weight, f.linear.bias
+    gx, gW, gb = torch.autograd.grad(out, (xt, W, b), torch.from_numpy(v).to(torch.float64))
+    return gx.numpy(), gW.numpy(), gb.numpy()
+
+
+def _set_linear(f, P):
+    with torch.no_grad():
+        f.linear.weight.copy_(torch.from_numpy(P["odefunc.linear.weight"]).to(torch.float64))
+        f.linear.bias.copy_(torch.from_numpy(P["odefunc.linear.bias"]).to(torch.float64))
+
+
+def main():
+    MG._install_import_shims()
+    sys.path.insert(0, MG.REF)
+    cwd = os.getcwd()
+    os.chdir("/tmp")
+    import ode_nn_ngraph_sim as single
+    import ode_nn_ngraphs as multi
+    os.chdir(cwd)
+    torch.set_default_dtype(torch.float64)
+    dev = torch.device("cpu")
+    graphs = MG._graphs()
+    cases = [("karate", 2, 64, 31), ("loops40", 3, 8, 32), ("heavy", 1, 64, 33), ("karate", 1, 128, 34)]
+    for gname, B, H, seed in cases:
+        d = dict(B=np.int32(B), H=np.int32(H), param_seed=np.int32(seed), input_seed=np.int32(seed + 100))
+        if gname == "heavy":
+            n, m, gseed = 1500, 6000, 4
+            rp, ci = synth.heavy_tail_csr(n, m, seed=gseed)
+            assert int(np.diff(rp).max()) > 96
+            A = sp.csr_matrix((np.ones(ci.shape[0], dtype=np.int64), ci, rp), shape=(n, n))
+            d.update(n=np.int32(n), m=np.int32(m), graph_seed=np.int32(gseed))
+        else:
+            G = graphs[gname]
+            A = nx.adjacency_matrix(G)
+            n = A.shape[0]
+            d.update(n=np.int32(n), edges=np.asarray(list(G.edges()), dtype=np.int32))
+        P = synth.linear_params(H, seed=seed)
+        f = single.ODEfunc(A, 0.2, 0.1, H, dev)
+        _set_linear(f, P)
+        y, v = RV.vjp_inputs(B * n, H, seed + 100, n)
+        gx, gW, gb = _grads(f, y, v)
+        rows = 4 * B * n
+        kept = np.arange(rows) if rows <= 2000 else np.sort(np.random.default_rng(seed).choice(rows, 1000, replace=False))
+        d.update(rows_kept=kept.astype(np.int32), gx=gx[kept], gW=gW, gb=gb)
+        tag = f"rhs_vjp_{gname}_B{B}_H{H}"
+        np.savez_compressed(os.path.join(HERE, tag + ".npz"), **d)
+        print("wrote", tag, "|gx|", float(np.abs(gx).max()), "|gW|", float(np.abs(gW).max()))
+
+    # multi-graph batch
+    names = ["karate", "loops40", "er200"]
+    A_list = [nx.adjacency_matrix(graphs[k]) for k in names]
+    picks, H, seed = [0, 2, 1], 8, 35
+    f = multi.ODEfunc(A_list, H, dev)
+    P = synth.linear_params(H, seed=seed)
+    _set_linear(f, P)
+    ns = [a.shape[0] for a in A_list]
+    y, v = RV.multi_inputs(ns, picks, H, seed + 100)
+    gx, gW, gb = _grads(f, y, v)
+    d = dict(H=np.int32(H), param_seed=np.int32(seed), input_seed=np.int32(seed + 100), picks=np.asarray(picks, dtype=np.int32),
+             gx=gx, gW=gW, gb=gb)
+    for j, k in enumerate(names):
+        d[f"edges{j}"] = np.asarray(list(graphs[k].edges()), dtype=np.int32)
+        d[f"n{j}"] = np.int32(ns[j])
+    tag = "rhs_vjp_multi_0-2-1_H8"
+    np.savez_compressed(os.path.join(HERE, tag + ".npz"), **d)
+    print("wrote", tag, "|gx|", float(np.abs(gx).max()))
+    torch.set_default_dtype(torch.float32)
+
+
+if __name__ == "__main__":
+    main()
