@@ -4,23 +4,6 @@
 
 #define BWD_NWG 768     // 3 workgroups per CU (52 KB of LDS each) on 256 CUs
 
-// lanes per row of the generic-H kernels: H/4 rounded up to a power of two, and the switch over it
-static inline int lpr_of(int H) {
-    int need = H / 4, l = 1;
-    while (l < need) l <<= 1;
-    return l;
-}
-
-#define BWD_DISPATCH(lpr, ...)                                   \
-    switch (lpr) {                                               \
-        case 1: { constexpr int LPR = 1; __VA_ARGS__; } break;   \
-        case 2: { constexpr int LPR = 2; __VA_ARGS__; } break;   \
-        case 4: { constexpr int LPR = 4; __VA_ARGS__; } break;   \
-        case 8: { constexpr int LPR = 8; __VA_ARGS__; } break;   \
-        case 16: { constexpr int LPR = 16; __VA_ARGS__; } break; \
-        default: { constexpr int LPR = 32; __VA_ARGS__; } break; \
-    }
-
 // partial-buffer layout per workgroup (floats)
 struct PartLayout {
     int H;

@@ -1091,9 +1091,6 @@ __global__ __launch_bounds__(256) void k_reduce_parts(const float* __restrict__ 
 }
 
 // --------------------------------------------------------------------------- host
-int gn_launch_mlp_any(const gnode_graph_s* g, const float* X, const float* W, const float* b, float* Z, long nrows, int H,
-                      hipStream_t st);
-
 __global__ void k_extract_bg(const float* __restrict__ bgslab, long rows, int H, float* __restrict__ beta,
                              float* __restrict__ gamma) {
     const long r = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1102,28 +1099,335 @@ __global__ void k_extract_bg(const float* __restrict__ bgslab, long rows, int H,
     gamma[r] = bgslab[(size_t)r * H + 1];
 }
 
-// one workspace slab: rows x H floats plus ONE MORE ROW (the q tables' zero row, which k_bwd_kept64's gather reads for absent
-// neighbours), rounded up
-static size_t bwd_slab_bytes(int64_t rows, int32_t H) { return gn_align(((size_t)rows + 1) * H * sizeof(float)); }
-
-static size_t backward_fixed_bytes(int64_t rows, int32_t H) {
-    const PartLayout L{H};
-    const size_t slab = bwd_slab_bytes(rows, H);
-    // a[3], Z[2], q[1], dpre[2] slabs + beta, gamma + partial buffer + reduced gradient vector
-    // (+ the control block of the persistent sweep, gnode_pers64_bwd.hip)
-    return 8 * slab + 2 * gn_align((size_t)rows * sizeof(float)) +
-           gn_align((size_t)BWD_NWG * L.total() * sizeof(float)) + gn_align((size_t)L.total() * sizeof(float)) +
-           gn_pers64_ctl_bytes();
+// The backward workspace as byte offsets, in order: a [3 slabs] | Z [2] | q [1] | dpre [2] | beta | gamma | the partial
+// gradient slots | one spare gradient vector | the control block of the persistent sweeps | `fixed`: the hub scratch
+// (gn_hub_scratch_bytes, two tables).  A slab is rows x H floats plus ONE MORE ROW (the q tables' zero row, which
+// k_bwd_kept64's gather reads for absent neighbours), rounded up.
+struct BwdLayout { size_t slab, a, Z, q, dpre, beta, gamma, part, ctl, fixed; };
+static BwdLayout backward_layout(int64_t rows, int32_t H) {
+    const size_t nparts = PartLayout{H}.total(), vec = gn_align((size_t)rows * sizeof(float));
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t at = off; off += bytes; return at; };
+    BwdLayout L;
+    L.slab = gn_align(((size_t)rows + 1) * H * sizeof(float));
+    L.a = take(3 * L.slab); L.Z = take(2 * L.slab); L.q = take(L.slab); L.dpre = take(2 * L.slab);
+    L.beta = take(vec); L.gamma = take(vec);
+    L.part = take(gn_align((size_t)BWD_NWG * nparts * sizeof(float)));
+    take(gn_align(nparts * sizeof(float)));
+    L.ctl = take(gn_pers64_ctl_bytes());
+    L.fixed = off;
+    return L;
 }
 
 extern "C" size_t gnode_backward_workspace_bytes(gnode_graph_t g, int64_t rows, int32_t H) {
     if (!g || rows <= 0 || H <= 0) return 0;
-    return backward_fixed_bytes(rows, H) + gn_hub_scratch_bytes(g, rows / g->n, H, 2);     // two tables per hub pass
+    return backward_layout(rows, H).fixed + gn_hub_scratch_bytes(g, rows / g->n, H, 2);     // two tables per hub pass
 }
 
 // dynamic LDS above 64 KB (the five-launch generic path at H > 100) needs the attribute once per device
 int gn_bwd_set_attributes() {
     GN_HIP(hipFuncSetAttribute((const void*)k_bwd_mlp<32>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    return 0;
+}
+
+// Which form the Euler adjoint sweep takes for a call.
+enum class BwdPath {
+    tiny,      // graphs that fit one workgroup, behind the one-workgroup forward: the whole sweep in one launch
+    h64,       // H = 64: one launch per interval, or the persistent sweep over the kept activations
+    small_h,   // H = 8 .. 32: one launch per interval, or (gpersist) the whole sweep in one persistent launch
+    generic,   // other H: five launches per interval
+};
+struct BwdPlan {
+    BwdPath path;
+    bool fwd_tiny;        // the forward took the one-workgroup path: sol's 4th slabs do not carry A Z_I
+    // h64
+    const float* keep;    // the kept activations the sweep reads, or null (recompute)
+    bool persist;         // intervals G-2 .. 1 (or G-1 .. 1 with `fold`) in ONE persistent launch (gnode_pers64_bwd.hip)
+    bool fold;            // ... starting at interval G-1, whose adjoint is zero
+    bool skip_last;       // one launch per interval over kept activations, interval G-1 (zero adjoint) skipped
+    PersPlan pers;
+    // small_h
+    bool gpersist;
+    PersgPlan persg;
+};
+
+static BwdPlan backward_plan(gnode_graph_s* g, long rows, int H, int n_steps, int n_emit, const int* slot, const float* keep,
+                             int sol_info, int flags) {
+    const int G = n_steps + 1;
+    const bool persist_ok = !(flags & GNODE_FWD_PER_STEP);
+    BwdPlan pl{};
+    // what the forward that produced `sol` / `keep` was (its sol_info says so; unchecked callers: the same question, same flags)
+    pl.fwd_tiny = sol_info >= 0 ? (sol_info & GNODE_SOL_TINY) != 0
+                                : gn_forward_plan(g, rows, H, 0, n_steps, n_emit, true, flags).path == FwdPath::tiny;
+    if (pl.fwd_tiny && gn_tiny_bwd64_ok(g, rows, H, n_steps)) {
+        pl.path = BwdPath::tiny;
+    } else if (H == 64 && n_steps >= 1) {
+        pl.path = BwdPath::h64;
+        // the 4th slabs (or the keep buffer's P_S) carry A Z_I unless the one-workgroup forward ran; the intervals below the
+        // last read Z_S(y_k), Z_I(y_k) back when the forward kept them as well
+        pl.keep = !pl.fwd_tiny && gnode_forward_keep_bytes(g, rows, H, n_steps, n_emit) > 0 ? keep : nullptr;
+        pl.persist = pl.keep && G >= 3 && persist_ok && gn_pers_bwd64_plan(g, rows / g->n, n_steps, &pl.pers);
+        // The last grid point emits nothing in the reference's use (get_sir_t_nodes_torch keeps the integer times, the grid ends
+        // half a step later): the adjoint is still ZERO through interval G-1 -- every product of that interval is zero -- and all
+        // it leaves is the head's VJP at grid point G-2 and the first q table.  The persistent sweep does that at its start
+        // (`fold`), and the two start-up launches (Z(y_{G-1}) + q, and the two-table interval kernel) do not run at all.
+        pl.fold = pl.persist && slot[G - 1] < 0;
+        // the same on the one-launch-per-interval path over kept activations (large graphs): instead of the two-table interval kernel
+        // on a zero adjoint (451 us at 75k x 4 against 282 for a kept interval) only the head's VJP at grid point G-2 and
+        // q = beta (a_I - a_S) Z_S(y_{G-2}) from the kept table run
+        pl.skip_last = !pl.persist && pl.keep && G >= 3 && slot[G - 1] < 0 && rows < (1L << 24) &&
+                       (long)(rows / g->n) * g->n_seg < (1L << 24);
+    } else if (H <= 32 && n_steps >= 1) {
+        pl.path = BwdPath::small_h;
+        // batches that fit one resident grid: the whole sweep INCLUDING its start-up is one persistent launch
+        pl.gpersist = persist_ok && gn_persg_plan(g, rows, H, n_steps, &pl.persg);
+    } else {
+        pl.path = BwdPath::generic;
+    }
+    return pl;
+}
+
+// One backward call as the path launchers see it.
+struct BwdCall {
+    gnode_graph_s* g;
+    const gnode_params* p;
+    const float* dt_host;
+    int G, H;
+    long rows;
+    size_t slab, slab_b;             // rows * H floats; the workspace's slab stride in bytes
+    const float *sol, *gS, *gI, *gR;
+    const int* slot;                 // [G]: output row of each grid point, or -1
+    float *a, *Z, *q, *dpre, *beta, *gamma, *part; char* ctl; void* hub_scratch;   // workspace (backward_layout)
+    hipStream_t st;
+    int slots_used;                  // highest workgroup slot any launch wrote, for the final reduction
+    const float* point(int gi) const { return sol + (size_t)gi * 4 * slab; }   // trajectory point gi
+    // grid point gi's row of an upstream gradient (gS, gI or gR), or null when gi is not emitted
+    const float* up(const float* U, int gi) const { return slot[gi] >= 0 ? U + (size_t)slot[gi] * rows : nullptr; }
+    // the head's VJP at grid point gi (when it is emitted)
+    int head(int gi) {
+        if (slot[gi] < 0) return 0;
+        return gn_launch_head_bwd(rows, H, point(gi), up(gS, gi), up(gI, gi), up(gR, gi), p, a, part, &slots_used, st);
+    }
+    // per interval i of a persistent sweep: the output row of grid point i-1 ([0]: of the last grid point)
+    std::vector<int> slot_prev() const {
+        std::vector<int> prev(G);
+        prev[0] = slot[G - 1];
+        for (int j = 1; j <= G - 1; ++j) prev[j] = slot[j - 1];
+        return prev;
+    }
+};
+
+// every start-up zero-fill in ONE launch: the adjoint state, the gradient slots, (H = 64) the q tables' zero rows and the
+// control block of the persistent sweeps (they then skip their own zero-fill launch; a call that runs none leaves the
+// give-up word at 0, which is what gnode_backward_status reads); then beta / gamma and the head's VJP at the last grid point,
+// unless the persistent small-H sweep does those itself
+static int backward_start(BwdCall& c, const BwdPlan& pl) {
+    GnZeroRegions zr;
+    zr.n = 0;
+    auto add = [&](void* ptr, size_t bytes) { zr.p[zr.n] = ptr; zr.bytes[zr.n] = bytes; ++zr.n; };
+    add(c.a, 3 * c.slab * sizeof(float));
+    add(c.part, (size_t)BWD_NWG * PartLayout{c.H}.total() * sizeof(float));
+    if (pl.path == BwdPath::h64) {
+        add(c.q + c.slab, (size_t)c.H * sizeof(float));
+        add(c.dpre + c.slab_b / sizeof(float) + c.slab, (size_t)c.H * sizeof(float));
+    }
+    if (c.H == 64 || c.H <= 32) add(c.ctl, gn_pers64_ctl_bytes());
+    if (int e = gn_zero_regions_async(zr, c.st)) return e;
+    if (pl.gpersist) return 0;
+    hipLaunchKernelGGL(k_extract_bg, dim3((unsigned)((c.rows + 255) / 256)), dim3(256), 0, c.st, c.sol + 3 * c.slab, c.rows, c.H,
+                       c.beta, c.gamma);
+    GN_LAUNCH_CHECK();
+    return c.head(c.G - 1);
+}
+
+// graphs that fit one workgroup: the whole sweep is one launch writing slot b for sample b (gnode_bwd_tiny.hip)
+static int backward_tiny(BwdCall& c, const float* x, const int32_t* out_rows_host, int n_out, int n_emit, const float* keep,
+                         size_t keep_bytes) {
+    const int n_steps = c.G - 1;
+    const size_t keep_need = gnode_forward_keep_bytes(c.g, c.rows, c.H, n_steps, n_emit);
+    if (keep && keep_need > 0 && keep_bytes < keep_need) {
+        gnode_set_error("gnode_backward_f32: keep buffer %zu < %zu", keep_bytes, keep_need);
+        return GNODE_ERR_WORKSPACE;
+    }
+    if (int e = gn_launch_tiny_bwd64(c.g, c.rows, x, c.p, c.dt_host, n_steps, out_rows_host, n_out, c.sol, c.gS, c.gI, c.gR, c.part,
+                                     keep_need > 0 ? keep : nullptr, c.st))
+        return e;
+    c.slots_used = (int)(c.rows / c.g->n);
+    PersCtl* ctl = (PersCtl*)c.ctl;       // (gnode_backward_status reads a defined word after this path too)
+    return gn_zero_async(ctl->error, sizeof(ctl->error), c.st);
+}
+
+// H = 64, one launch per interval: a[3] | Z_S | Z_I(0) | q(0) | Z_I(1) | q(1)  (Z_S is row-local, the gather tables ping-pong;
+// k_mlp64_q fills Z_S | Z_I element-contiguously; the q tables' zero rows, Qb[k] + slab, were zero-filled by the call's first
+// launch).  16-row tiles at 3 workgroups per CU (measured on the 75k graph, 4 samples: 32-row tiles at 3 / 2 per CU 481 / 548 us
+// per interval, the unfused three-launch form 563; 16-row tiles 451)
+struct Tables64 { float* ZIb[2]; float* Qb[2]; };
+static Tables64 tables64(const BwdCall& c) { return {{c.Z + c.slab, c.dpre}, {c.q, c.dpre + c.slab_b / sizeof(float)}}; }
+static int grid64(const BwdCall& c) {
+    const long total = (long)(c.rows / c.g->n) * ((c.g->n + 15) / 16);
+    return (int)std::min<long>(std::min<long>((long)GN_BWD_RPG1_OCC * c.g->num_cu, BWD_NWG), total);
+}
+
+// interval i (y_i -> y_{i-1}) in one launch: over the kept activations, or gathering one or (`two`) both tables
+static int backward64_interval(BwdCall& c, const BwdPlan& pl, int i) {
+    const gnode_graph_s* g = c.g;
+    const gnode_params* p = c.p;
+    const Tables64 T = tables64(c);
+    const float* keep = pl.keep;
+    const long rows = c.rows;
+    const int tps = (g->n + 15) / 16, grid = grid64(c);
+    const long total = (long)(rows / g->n) * tps;
+    const int cur = (c.G - 1 - i) & 1;
+    const bool ai_saved = !pl.fwd_tiny;
+    const bool two = !ai_saved || i == c.G - 1;          // A Z_I(y_{G-1}) was never needed by the forward
+    const float *AIhub = nullptr, *GQhub = nullptr;
+    const bool kept_launch = keep && !two && rows < (1L << 24) && (long)(rows / g->n) * g->n_seg < (1L << 24);   // 32-bit byte offsets of rows and hub partials
+    const float* HubP = nullptr;               // kept kernel: segment partials only, it adds them up itself
+    if (two) { if (int e = gn_hub_gather(g, rows / g->n, 64, T.ZIb[cur], T.Qb[cur], c.hub_scratch, &AIhub, &GQhub, c.st)) return e; }
+    else if (kept_launch) { if (int e = gn_hub_segments(g, rows / g->n, 64, T.Qb[cur], c.hub_scratch, &HubP, c.st)) return e; }
+    else if (int e = gn_hub_gather(g, rows / g->n, 64, T.Qb[cur], nullptr, c.hub_scratch, &GQhub, nullptr, c.st)) return e;
+    const float* gSs = c.up(c.gS, i - 1);
+    const bool sampled = gn_prof_begin(2, c.st);
+    if (kept_launch) {
+        // the head instance carries 25 more accumulators and the head's temporaries: two workgroups per CU there
+        constexpr int HOCC = GN_BWD_KEPT_HEAD_OCC;
+        const bool hubs = g->n_hub > 0;
+        auto kept_kernel = gSs ? (hubs ? k_bwd_kept64<HOCC, true, true> : k_bwd_kept64<HOCC, true, false>)
+                               : (hubs ? k_bwd_kept64<GN_BWD_RPG1_OCC, false, true> : k_bwd_kept64<GN_BWD_RPG1_OCC, false, false>);
+        const int kgrid = gSs ? (int)std::min<long>((long)HOCC * g->num_cu, grid) : grid;
+        hipLaunchKernelGGL(kept_kernel, dim3(kgrid), dim3(256), 0, c.st, g->rowhdr, g->col, g->n, rows, tps, total, T.Qb[cur],
+                           T.Qb[cur ^ 1], c.point(i), c.point(i - 1), gn_keep_ps(keep, rows, i), gn_keep_zi(keep, rows, i),
+                           gn_keep_zs(keep, rows, i - 1), p->odefunc_linear_weight, c.beta, c.gamma, c.dt_host[i - 1], c.a, c.part,
+                           gSs, c.up(c.gI, i - 1), c.up(c.gR, i - 1), p->linear3_weight, p->linear3_bias, p->linearS2_weight,
+                           p->linearS2_bias, g->hubidx, HubP, g->hub_seg_ptr, g->n_seg, i > 1 ? 1 : 0);
+    } else {
+        auto fused_kernel = two ? k_bwd_fused64<GN_BWD_RPG1_OCC, 1, true> : k_bwd_fused64<GN_BWD_RPG1_OCC, 1, false>;
+        hipLaunchKernelGGL(fused_kernel, dim3(grid), dim3(256), 0, c.st, g->rowptr, g->col, g->n, rows, tps, total, T.ZIb[cur],
+                           T.Qb[cur], ai_saved ? nullptr : T.ZIb[cur ^ 1], T.Qb[cur ^ 1], c.point(i), c.point(i - 1),
+                           p->odefunc_linear_weight, p->odefunc_linear_bias, c.beta, c.gamma, c.dt_host[i - 1], c.a, c.part, gSs,
+                           c.up(c.gI, i - 1), c.up(c.gR, i - 1), p->linear3_weight, p->linear3_bias, p->linearS2_weight,
+                           p->linearS2_bias, g->hubidx, AIhub, GQhub, g->n_hub, i > 1 ? 1 : 0, c.point(i) + 3 * c.slab);
+    }
+    if (sampled) gn_prof_end(2, c.st);
+    GN_LAUNCH_CHECK();
+    return 0;
+}
+
+static int backward_h64(BwdCall& c, const BwdPlan& pl, const float* keep, size_t keep_bytes, int n_emit, int sol_info) {
+    const gnode_params* p = c.p;
+    const int G = c.G;
+    const Tables64 T = tables64(c);
+    if (sol_info >= 0) {
+        // the forward said what it left in `sol` / `keep` (sol_info_host): a trajectory and a keep buffer belong together
+        if (keep) GN_CHECK_ARG(sol_info & GNODE_SOL_KEEP, "gnode_backward_f32: a keep buffer was passed with a trajectory whose "
+                               "forward call filled none (sol_info %d)", sol_info);
+        else if (!pl.fwd_tiny) GN_CHECK_ARG(sol_info & GNODE_SOL_AI, "gnode_backward_f32: this trajectory was produced WITH a keep buffer "
+                                            "(its 4th slabs are unwritten): pass that buffer (sol_info %d)", sol_info);
+    }
+    const size_t keep_need = gnode_forward_keep_bytes(c.g, c.rows, c.H, G - 1, n_emit);
+    if (pl.keep && keep_bytes < keep_need) {
+        gnode_set_error("gnode_backward_f32: keep buffer %zu < %zu", keep_bytes, keep_need);
+        return GNODE_ERR_WORKSPACE;
+    }
+    c.slots_used = std::max(c.slots_used, grid64(c));
+    if (pl.skip_last) {
+        if (int e = c.head(G - 2)) return e;
+        hipLaunchKernelGGL(k_bwd_q, dim3(2048), dim3(256), 0, c.st, c.a, gn_keep_zs(pl.keep, c.rows, G - 2), c.beta, T.Qb[1], c.rows, 64);
+        GN_LAUNCH_CHECK();
+    } else if (!pl.fold) {
+        const long mt = (2 * c.rows + TILE_ROWS - 1) / TILE_ROWS;
+        hipLaunchKernelGGL(k_mlp64_q, dim3((unsigned)std::min<long>(mt, 1024)), dim3(256), 0, c.st, c.point(G - 1),
+                           p->odefunc_linear_weight, p->odefunc_linear_bias, c.Z, c.a, c.beta, c.q, c.rows);
+        GN_LAUNCH_CHECK();
+    }
+    // intervals above `low` take one launch each; `low` .. 1 belong to the persistent sweep
+    const int low = !pl.persist ? 0 : pl.fold ? G - 1 : G - 2;
+    for (int i = pl.skip_last ? G - 2 : G - 1; i > low; --i)
+        if (int e = backward64_interval(c, pl, i)) return e;
+    if (!pl.persist) return 0;
+    const std::vector<int> prev = c.slot_prev();
+    int pslots = 0;
+    const bool sampled = gn_prof_begin(2, c.st);
+    if (int e = gn_launch_pers_bwd64(c.g, pl.pers, c.rows, G, T.Qb[0], T.Qb[1], c.sol, pl.keep, p->odefunc_linear_weight, c.beta,
+                                     c.gamma, c.a, c.part, c.gS, c.gI, c.gR, p, c.dt_host, prev.data(), c.ctl, true, pl.fold, &pslots,
+                                     c.st))
+        return e;
+    if (sampled) gn_prof_end(2, c.st);
+    c.slots_used = std::max(c.slots_used, pslots);
+    return 0;
+}
+
+// small hidden sizes: the one-launch-per-interval scheme of H = 64 on lane groups (k_bwd_fused_generic), or the whole sweep in
+// ONE persistent launch (gnode_persg.hip)
+static int backward_small_h(BwdCall& c, const BwdPlan& pl) {
+    const gnode_graph_s* g = c.g;
+    const gnode_params* p = c.p;
+    const long rows = c.rows;
+    const int H = c.H, G = c.G, lpr = gn_lpr(H), rpw = 256 / lpr;
+    float* ZIb[2] = {c.Z + c.slab, c.dpre};
+    float* Qb[2] = {c.q, c.dpre + c.slab};
+    if (pl.gpersist) {
+        const std::vector<int> prev = c.slot_prev();
+        const bool sampled = gn_prof_begin(2, c.st);
+        if (int e = gn_launch_persg_bwd(g, pl.persg, rows, H, G, ZIb[0], ZIb[1], Qb[0], Qb[1], c.Z, c.sol, c.beta, c.gamma, c.a,
+                                        c.part, c.gS, c.gI, c.gR, p, c.dt_host, prev.data(), c.ctl, true, c.st))
+            return e;
+        if (sampled) gn_prof_end(2, c.st);
+        c.slots_used = std::max(c.slots_used, pl.persg.wgs);
+        return 0;
+    }
+    if (int e = gn_launch_mlp_any(g, c.point(G - 1), p->odefunc_linear_weight, p->odefunc_linear_bias, c.Z, 2 * rows, H, c.st)) return e;
+    hipLaunchKernelGGL(k_bwd_q, dim3(2048), dim3(256), 0, c.st, c.a, c.Z, c.beta, c.q, rows, H);
+    GN_LAUNCH_CHECK();
+    const size_t fl = std::max((size_t)2 * H * H + (size_t)4 * rpw * H, (size_t)rpw * (4 * H + 12));
+    const int grid = (int)std::min<long>(BWD_NWG, std::max<long>(1, (rows + rpw - 1) / rpw));
+    c.slots_used = std::max(c.slots_used, grid);
+    for (int i = G - 1; i >= 1; --i) {
+        const int cur = (G - 1 - i) & 1;
+        const float *HubP0 = nullptr, *HubP1 = nullptr;        // segment partials; the interval kernel adds them up itself
+        if (int e = gn_hub_segments2(g, rows / g->n, H, ZIb[cur], Qb[cur], c.hub_scratch, &HubP0, &HubP1, c.st)) return e;
+        const bool sampled = gn_prof_begin(2, c.st);
+        GN_LPR_DISPATCH(32, lpr, hipLaunchKernelGGL(k_bwd_fused_generic<LPR>, dim3(grid), dim3(256), fl * sizeof(float), c.st, g->rowptr,
+                                                    g->col, g->n, rows, H, c.Z, ZIb[cur], Qb[cur], ZIb[cur ^ 1], Qb[cur ^ 1], c.point(i),
+                                                    c.point(i - 1), p->odefunc_linear_weight, p->odefunc_linear_bias, c.beta, c.gamma,
+                                                    c.dt_host[i - 1], c.a, c.part, c.up(c.gS, i - 1), c.up(c.gI, i - 1),
+                                                    c.up(c.gR, i - 1), p->linear3_weight, p->linear3_bias, p->linearS2_weight,
+                                                    p->linearS2_bias, g->hubidx, HubP0, HubP1, g->hub_seg_ptr, g->n_seg, i > 1 ? 1 : 0));
+        if (sampled) gn_prof_end(2, c.st);
+        GN_LAUNCH_CHECK();
+    }
+    return 0;
+}
+
+// other H: node MLP, q, gather, VJP of the node MLP and the head's VJP: five launches per interval
+static int backward_generic(BwdCall& c) {
+    const gnode_graph_s* g = c.g;
+    const gnode_params* p = c.p;
+    const long rows = c.rows;
+    const int H = c.H, lpr = gn_lpr(H), rpw = 256 / lpr;
+    const size_t mlp_lds = ((size_t)H * H + (size_t)4 * rpw * H) * sizeof(float);
+    for (int i = c.G - 1; i >= 1; --i) {
+        const float* yi = c.point(i);
+        const float dt = c.dt_host[i - 1];
+        if (int e = gn_launch_mlp_any(g, yi, p->odefunc_linear_weight, p->odefunc_linear_bias, c.Z, 2 * rows, H, c.st)) return e;
+        hipLaunchKernelGGL(k_bwd_q, dim3(2048), dim3(256), 0, c.st, c.a, c.Z, c.beta, c.q, rows, H);
+        GN_LAUNCH_CHECK();
+        dim3 ggrid((unsigned)((g->n + rpw - 1) / rpw), (unsigned)(rows / g->n));
+        const float *AIhub = nullptr, *GQhub = nullptr;
+        if (int e = gn_hub_gather(g, rows / g->n, H, c.Z + c.slab, c.q, c.hub_scratch, &AIhub, &GQhub, c.st)) return e;
+        GN_LPR_DISPATCH(32, lpr, hipLaunchKernelGGL(k_bwd_gather<LPR>, ggrid, dim3(256), 0, c.st, g->rowptr, g->col, g->n, rows, H,
+                                                    c.a, c.Z, c.q, c.beta, c.gamma, c.dpre, g->hubidx, AIhub, GQhub, g->n_hub));
+        GN_LAUNCH_CHECK();
+        if (H == 128) {
+            if (int e = gn_launch_bwd_mlp128(g, c.dpre, yi, p->odefunc_linear_weight, dt, c.a, rows, c.part, &c.slots_used, c.st)) return e;
+        } else {
+            c.slots_used = BWD_NWG;
+            GN_LPR_DISPATCH(32, lpr, hipLaunchKernelGGL(k_bwd_mlp<LPR>, dim3(BWD_NWG), dim3(256), mlp_lds, c.st, c.dpre, yi,
+                                                        p->odefunc_linear_weight, dt, c.a, rows, H, c.part));
+        }
+        GN_LAUNCH_CHECK();
+        if (int e = c.head(i - 1)) return e;
+    }
     return 0;
 }
 
@@ -1144,328 +1448,62 @@ extern "C" int gnode_backward_f32(gnode_graph_t g, const float* x, const gnode_p
         gnode_set_error("gnode_backward_f32: workspace %zu < %zu", workspace_bytes, gnode_backward_workspace_bytes(g, rows, H));
         return GNODE_ERR_WORKSPACE;
     }
-    const int G = n_steps + 1;
-    if (out_rows_host)
-        for (int i = 0; i < n_out; ++i)
-            GN_CHECK_ARG(out_rows_host[i] >= 0 && out_rows_host[i] < G && (i == 0 || out_rows_host[i] > out_rows_host[i - 1]),
-                         "gnode_backward_f32: out_rows must be ascending grid indices in [0,%d)", G);
-    hipStream_t st = (hipStream_t)stream;
-    const PartLayout L{H};
-    const size_t slab = (size_t)rows * H, slab_b = bwd_slab_bytes(rows, H);
-    const size_t vec_b = gn_align((size_t)rows * sizeof(float));
+    const int G = n_steps + 1, n_emit = out_rows_host ? n_out : G;
+    if (int e = gn_check_out_rows("gnode_backward_f32", out_rows_host, n_out, G)) return e;
+    const std::vector<int> slot = gn_out_slots(out_rows_host, n_out, G);
+    const BwdPlan pl = backward_plan(g, rows, H, n_steps, n_emit, slot.data(), keep, sol_info, flags);
+    const BwdLayout L = backward_layout(rows, H);
     char* ws = (char*)workspace;
-    float* a = (float*)ws;                               // 3 slabs (element-contiguous inside 3 aligned slabs)
-    float* Z = (float*)(ws + 3 * slab_b);                // 2 slabs
-    float* q = (float*)(ws + 5 * slab_b);                // 1 slab
-    float* dpre = (float*)(ws + 6 * slab_b);             // 2 slabs
-    float* beta = (float*)(ws + 8 * slab_b);
-    float* gamma = (float*)(ws + 8 * slab_b + vec_b);
-    float* part = (float*)(ws + 8 * slab_b + 2 * vec_b);
-    float* red = (float*)(ws + 8 * slab_b + 2 * vec_b + gn_align((size_t)BWD_NWG * L.total() * sizeof(float)));
-    void* hub_scratch = ws + backward_fixed_bytes(rows, H);
-    int slots_used = 1;                                  // highest workgroup slot any launch wrote, for the final reduction
-    // what the forward that produced `sol` / `keep` was (its sol_info says so; unchecked callers: the same question, same flags)
-    const int n_emit = out_rows_host ? n_out : n_steps + 1;
-    const bool fwd_tiny = sol_info >= 0 ? (sol_info & GNODE_SOL_TINY) != 0 : gn_forward_kind(g, rows, H, 0, n_steps, n_emit, true, flags, nullptr) == 1;
-    const bool tiny = fwd_tiny && gn_tiny_bwd64_ok(g, rows, H, n_steps);
-    if (tiny) {
-        // graphs that fit one workgroup: the whole sweep is one launch writing slot b for sample b (gnode_bwd_tiny.hip)
-        const size_t keep_need = gnode_forward_keep_bytes(g, rows, H, n_steps, out_rows_host ? n_out : n_steps + 1);
-        if (keep && keep_need > 0 && keep_bytes < keep_need) {
-            gnode_set_error("gnode_backward_f32: keep buffer %zu < %zu", keep_bytes, keep_need);
-            return GNODE_ERR_WORKSPACE;
-        }
-        if (int e = gn_launch_tiny_bwd64(g, rows, x, p, dt_host, n_steps, out_rows_host, n_out, sol, gS, gI, gR, part,
-                                         keep_need > 0 ? keep : nullptr, st))
-            return e;
-        slots_used = (int)(rows / g->n);
-        {   // (gnode_backward_status reads a defined word after this path too)
-            PersCtl* ctl = (PersCtl*)(ws + backward_fixed_bytes(rows, H) - gn_pers64_ctl_bytes());
-            if (int e = gn_zero_async(ctl->error, sizeof(ctl->error), st)) return e;
-        }
+    BwdCall c{g, p, dt_host, G, H, (long)rows, (size_t)rows * H, L.slab, sol, gS, gI, gR, slot.data(),
+              (float*)(ws + L.a), (float*)(ws + L.Z), (float*)(ws + L.q), (float*)(ws + L.dpre), (float*)(ws + L.beta),
+              (float*)(ws + L.gamma), (float*)(ws + L.part), ws + L.ctl, ws + L.fixed, (hipStream_t)stream, 1};
+    int e = 0;
+    if (pl.path == BwdPath::tiny) {
+        e = backward_tiny(c, x, out_rows_host, n_out, n_emit, keep, keep_bytes);
     } else {
-    // every start-up zero-fill in ONE launch: the adjoint state, the gradient slots, (H = 64) the q tables' zero rows and the
-    // control block of the persistent sweeps (they then skip their own zero-fill launch; a call that runs none leaves the
-    // give-up word at 0, which is what gnode_backward_status reads)
-    const bool has_ctl = H == 64 || H <= 32;
-    char* ctl_ptr = ws + backward_fixed_bytes(rows, H) - gn_pers64_ctl_bytes();
-    {
-        GnZeroRegions zr;
-        zr.n = 0;
-        auto add = [&](void* ptr, size_t bytes) { zr.p[zr.n] = ptr; zr.bytes[zr.n] = bytes; ++zr.n; };
-        add(a, 3 * slab * sizeof(float));
-        add(part, (size_t)BWD_NWG * L.total() * sizeof(float));
-        if (H == 64 && n_steps >= 1) {
-            add(q + slab, (size_t)H * sizeof(float));
-            add(dpre + slab_b / sizeof(float) + slab, (size_t)H * sizeof(float));
-        }
-        if (has_ctl) add(ctl_ptr, gn_pers64_ctl_bytes());
-        if (int e = gn_zero_regions_async(zr, st)) return e;
+        e = backward_start(c, pl);
+        if (!e && pl.path == BwdPath::h64) e = backward_h64(c, pl, keep, keep_bytes, n_emit, sol_info);
+        if (!e && pl.path == BwdPath::small_h) e = backward_small_h(c, pl);
+        if (!e && pl.path == BwdPath::generic) e = backward_generic(c);
+        if (!e) e = gn_launch_enc_bwd(c.rows, H, c.a, sol, x, c.part, &c.slots_used, c.st);
     }
-    // small hidden sizes, batches that fit one resident grid: the whole sweep INCLUDING its start-up is one persistent launch
-    PersgPlan gp;
-    const bool gpersist = H <= 32 && n_steps >= 1 && !(flags & GNODE_FWD_PER_STEP) && gn_persg_plan(g, rows, H, n_steps, &gp);
-    if (!gpersist) {
-    hipLaunchKernelGGL(k_extract_bg, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, sol + 3 * slab, (long)rows, H,
-                       beta, gamma);
-    GN_LAUNCH_CHECK();
-    }
-
-    const int lpr = lpr_of(H), rpw = 256 / lpr;
-    auto slot_of = [&](int gi) -> int {
-        if (!out_rows_host) return gi;
-        for (int i = 0; i < n_out; ++i) if (out_rows_host[i] == gi) return i;
-        return -1;
-    };
-    auto head = [&](int gi) -> int {
-        const int s = slot_of(gi);
-        if (s < 0) return 0;
-        const size_t lds = (size_t)rpw * (4 * H + 9) * sizeof(float);
-        const int hgrid = (int)std::min<long>(BWD_NWG, std::max<long>(1, (rows + rpw - 1) / rpw));
-        slots_used = std::max(slots_used, hgrid);
-        BWD_DISPATCH(lpr, hipLaunchKernelGGL(k_head_bwd<LPR>, dim3(hgrid), dim3(256), lds, st, sol + (size_t)gi * 4 * slab,
-                                             (long)rows, H, gS + (size_t)s * rows, gI + (size_t)s * rows, gR + (size_t)s * rows,
-                                             p->linear3_weight, p->linear3_bias, p->linearS2_weight, p->linearS2_bias, a, part));
-        GN_LAUNCH_CHECK();
-        return 0;
-    };
-    if (!gpersist)
-        if (int e = head(G - 1)) return e;
-    const size_t mlp_lds = ((size_t)H * H + (size_t)4 * rpw * H) * sizeof(float);
-    if (H == 64 && n_steps >= 1) {
-        // one launch per interval: a[3] | Z_S | Z_I(0) | q(0) | Z_I(1) | q(1)  (Z_S is row-local, the gather tables ping-pong)
-        float* ZS = Z; float* ZIb[2] = {Z + slab, dpre};     // (k_mlp64_q fills Z_S | Z_I element-contiguously)
-        float* Qb[2] = {q, dpre + slab_b / sizeof(float)};
-        // (the q tables' zero rows, Qb[k] + slab, were zero-filled by the call's first launch)
-        // 16-row tiles at 3 workgroups per CU (measured on the 75k graph, 4 samples: 32-row tiles at 3 / 2 per CU 481 / 548 us
-        // per interval, the unfused three-launch form 563; 16-row tiles 451)
-        // does this trajectory carry A Z_I(y_i) in its 4th slabs (gnode_forward_f32 wrote it: H = 64, not the one-launch path)?
-        const bool ai_saved = !fwd_tiny;               // the 4th slabs (or the keep buffer's P_S) carry A Z_I unless the one-workgroup forward ran
-        // ... and did the forward keep Z_S(y_k), Z_I(y_k) as well?  Then the intervals below the last read them back
-        const size_t keep_need = gnode_forward_keep_bytes(g, rows, H, n_steps, out_rows_host ? n_out : G);
-        if (sol_info >= 0) {
-            // the forward said what it left in `sol` / `keep` (sol_info_host): a trajectory and a keep buffer belong together
-            if (keep) GN_CHECK_ARG(sol_info & GNODE_SOL_KEEP, "gnode_backward_f32: a keep buffer was passed with a trajectory whose "
-                                   "forward call filled none (sol_info %d)", sol_info);
-            else if (ai_saved) GN_CHECK_ARG(sol_info & GNODE_SOL_AI, "gnode_backward_f32: this trajectory was produced WITH a keep buffer "
-                                            "(its 4th slabs are unwritten): pass that buffer (sol_info %d)", sol_info);
-        }
-        if (!(ai_saved && keep_need > 0)) keep = nullptr;
-        if (keep && keep_bytes < keep_need) {
-            gnode_set_error("gnode_backward_f32: keep buffer %zu < %zu", keep_bytes, keep_need);
-            return GNODE_ERR_WORKSPACE;
-        }
-        const int tps = (g->n + 15) / 16;
-        const long total = (long)(rows / g->n) * tps;
-        const int grid = (int)std::min<long>(std::min<long>((long)GN_BWD_RPG1_OCC * g->num_cu, BWD_NWG), total);
-        slots_used = std::max(slots_used, grid);
-        // mid-size graphs: intervals G-2 .. 1 over the kept activations in ONE persistent launch (gnode_pers64_bwd.hip)
-        PersPlan pplan;
-        const bool persist = keep && G >= 3 && !(flags & GNODE_FWD_PER_STEP) && gn_pers_bwd64_plan(g, rows / g->n, n_steps, &pplan);
-        // The last grid point emits nothing in the reference's use (get_sir_t_nodes_torch keeps the integer times, the grid ends
-        // half a step later): the adjoint is still ZERO through interval G-1 -- every product of that interval is zero -- and all
-        // it leaves is the head's VJP at grid point G-2 and the first q table.  The persistent sweep does that at its start
-        // (`fold`), and the two start-up launches (Z(y_{G-1}) + q, and the two-table interval kernel) do not run at all.
-        const bool fold = persist && slot_of(G - 1) < 0;
-        // the same on the one-launch-per-interval path over kept activations (large graphs): instead of the two-table interval kernel
-        // on a zero adjoint (451 us at 75k x 4 against 282 for a kept interval) only the head's VJP at grid point G-2 and
-        // q = beta (a_I - a_S) Z_S(y_{G-2}) from the kept table run
-        const bool skip_last = !persist && keep && G >= 3 && slot_of(G - 1) < 0 && rows < (1L << 24) &&
-                               (long)(rows / g->n) * g->n_seg < (1L << 24);
-        if (skip_last) {
-            if (int e = head(G - 2)) return e;
-            hipLaunchKernelGGL(k_bwd_q, dim3(2048), dim3(256), 0, st, a, gn_keep_zs(keep, rows, G - 2), beta, Qb[1], (long)rows, 64);
-            GN_LAUNCH_CHECK();
-        }
-        if (!fold && !skip_last) {
-            const long mt = (2 * rows + TILE_ROWS - 1) / TILE_ROWS;
-            hipLaunchKernelGGL(k_mlp64_q, dim3((unsigned)std::min<long>(mt, 1024)), dim3(256), 0, st, sol + (size_t)(G - 1) * 4 * slab,
-                               p->odefunc_linear_weight, p->odefunc_linear_bias, Z, a, beta, q, (long)rows);
-            GN_LAUNCH_CHECK();
-        }
-        for (int i = skip_last ? G - 2 : G - 1; i >= 1; --i) {
-            if (persist && (i == G - 2 || fold)) {
-                int slot_prev[128];
-                for (int j = 1; j <= G - 1; ++j) slot_prev[j] = slot_of(j - 1);
-                int pslots = 0;
-                const bool sampled = gn_prof_begin(2, st);
-                if (int e = gn_launch_pers_bwd64(g, pplan, rows, G, Qb[0], Qb[1], sol, keep, p->odefunc_linear_weight, beta, gamma, a, part,
-                                                 gS, gI, gR, p, dt_host, slot_prev, ctl_ptr, true, fold, &pslots, st))
-                    return e;
-                if (sampled) gn_prof_end(2, st);
-                slots_used = std::max(slots_used, pslots);
-                break;
-            }
-            const int cur = (G - 1 - i) & 1;
-            const bool two = !ai_saved || i == G - 1;          // A Z_I(y_{G-1}) was never needed by the forward
-            const float *AIhub = nullptr, *GQhub = nullptr;
-            const bool kept_launch = keep && !two && rows < (1L << 24) && (long)(rows / g->n) * g->n_seg < (1L << 24);   // 32-bit byte offsets of rows and hub partials
-            const float* HubP = nullptr;               // kept kernel: segment partials only, it adds them up itself
-            if (two) { if (int e = gn_hub_gather(g, rows / g->n, 64, ZIb[cur], Qb[cur], hub_scratch, &AIhub, &GQhub, st)) return e; }
-            else if (kept_launch) { if (int e = gn_hub_segments(g, rows / g->n, 64, Qb[cur], hub_scratch, &HubP, st)) return e; }
-            else if (int e = gn_hub_gather(g, rows / g->n, 64, Qb[cur], nullptr, hub_scratch, &GQhub, nullptr, st)) return e;
-            const int s = slot_of(i - 1);
-            const float* gSs = s >= 0 ? gS + (size_t)s * rows : nullptr;
-            const bool sampled = gn_prof_begin(2, st);
-            if (kept_launch) {
-                // the head instance carries 25 more accumulators and the head's temporaries: two workgroups per CU there
-                constexpr int HOCC = GN_BWD_KEPT_HEAD_OCC;
-                const bool hubs = g->n_hub > 0;
-                auto kept_kernel = gSs ? (hubs ? k_bwd_kept64<HOCC, true, true> : k_bwd_kept64<HOCC, true, false>)
-                                       : (hubs ? k_bwd_kept64<GN_BWD_RPG1_OCC, false, true> : k_bwd_kept64<GN_BWD_RPG1_OCC, false, false>);
-                const int kgrid = gSs ? (int)std::min<long>((long)HOCC * g->num_cu, grid) : grid;
-                hipLaunchKernelGGL(kept_kernel, dim3(kgrid), dim3(256), 0, st, g->rowhdr, g->col, g->n, (long)rows,
-                                   tps, total, Qb[cur], Qb[cur ^ 1], sol + (size_t)i * 4 * slab, sol + (size_t)(i - 1) * 4 * slab,
-                                   gn_keep_ps(keep, rows, i), gn_keep_zi(keep, rows, i), gn_keep_zs(keep, rows, i - 1),
-                                   p->odefunc_linear_weight, beta, gamma, dt_host[i - 1],
-                                   a, part, gSs, s >= 0 ? gI + (size_t)s * rows : nullptr,
-                                   s >= 0 ? gR + (size_t)s * rows : nullptr, p->linear3_weight, p->linear3_bias,
-                                   p->linearS2_weight, p->linearS2_bias, g->hubidx, HubP, g->hub_seg_ptr, g->n_seg, i > 1 ? 1 : 0);
-            } else {
-            auto fused_kernel = two ? k_bwd_fused64<GN_BWD_RPG1_OCC, 1, true> : k_bwd_fused64<GN_BWD_RPG1_OCC, 1, false>;
-            hipLaunchKernelGGL(fused_kernel, dim3(grid), dim3(256), 0, st, g->rowptr, g->col, g->n, (long)rows, tps, total,
-                               ZIb[cur], Qb[cur], ai_saved ? nullptr : ZIb[cur ^ 1], Qb[cur ^ 1], sol + (size_t)i * 4 * slab,
-                               sol + (size_t)(i - 1) * 4 * slab, p->odefunc_linear_weight, p->odefunc_linear_bias, beta, gamma,
-                               dt_host[i - 1], a, part, gSs, s >= 0 ? gI + (size_t)s * rows : nullptr,
-                               s >= 0 ? gR + (size_t)s * rows : nullptr, p->linear3_weight, p->linear3_bias,
-                               p->linearS2_weight, p->linearS2_bias, g->hubidx, AIhub, GQhub, g->n_hub, i > 1 ? 1 : 0,
-                               sol + (size_t)i * 4 * slab + 3 * slab);
-            }
-            if (sampled) gn_prof_end(2, st);
-            GN_LAUNCH_CHECK();
-        }
-    } else if (H <= 32 && n_steps >= 1) {
-        // small hidden sizes: the same one-launch-per-interval scheme on lane groups (k_bwd_fused_generic)
-        float* ZS = Z; float* ZIb[2] = {Z + slab, dpre};
-        float* Qb[2] = {q, dpre + slab};
-        const float* yl = sol + (size_t)(G - 1) * 4 * slab;
-        if (!gpersist) {
-            if (int e = gn_launch_mlp_any(g, yl, p->odefunc_linear_weight, p->odefunc_linear_bias, Z, 2 * rows, H, st)) return e;
-            hipLaunchKernelGGL(k_bwd_q, dim3(2048), dim3(256), 0, st, a, Z, beta, q, (long)rows, H);
-            GN_LAUNCH_CHECK();
-        }
-        const size_t fl = std::max((size_t)2 * H * H + (size_t)4 * rpw * H, (size_t)rpw * (4 * H + 12));
-        const int grid = (int)std::min<long>(BWD_NWG, std::max<long>(1, (rows + rpw - 1) / rpw));
-        // batches that fit one resident grid: every interval in ONE persistent launch (gnode_persg.hip)
-        if (gpersist) {
-            int slot_prev[128];
-            slot_prev[0] = slot_of(G - 1);
-            for (int j = 1; j <= G - 1; ++j) slot_prev[j] = slot_of(j - 1);
-            const bool sampled = gn_prof_begin(2, st);
-            if (int e = gn_launch_persg_bwd(g, gp, rows, H, G, ZIb[0], ZIb[1], Qb[0], Qb[1], ZS, sol, beta, gamma, a, part, gS, gI, gR, p,
-                                            dt_host, slot_prev, ctl_ptr, true, st))
-                return e;
-            if (sampled) gn_prof_end(2, st);
-            slots_used = std::max(slots_used, gp.wgs);
-        } else
-        slots_used = std::max(slots_used, grid);
-        for (int i = gpersist ? 0 : G - 1; i >= 1; --i) {
-            const int cur = (G - 1 - i) & 1;
-            const float *HubP0 = nullptr, *HubP1 = nullptr;        // segment partials; the interval kernel adds them up itself
-            if (int e = gn_hub_segments2(g, rows / g->n, H, ZIb[cur], Qb[cur], hub_scratch, &HubP0, &HubP1, st)) return e;
-            const int s = slot_of(i - 1);
-            const bool sampled = gn_prof_begin(2, st);
-            BWD_DISPATCH(lpr, hipLaunchKernelGGL(k_bwd_fused_generic<LPR>, dim3(grid), dim3(256), fl * sizeof(float), st, g->rowptr,
-                                                 g->col, g->n, (long)rows, H, ZS, ZIb[cur], Qb[cur], ZIb[cur ^ 1], Qb[cur ^ 1],
-                                                 sol + (size_t)i * 4 * slab, sol + (size_t)(i - 1) * 4 * slab,
-                                                 p->odefunc_linear_weight, p->odefunc_linear_bias, beta, gamma, dt_host[i - 1], a,
-                                                 part, s >= 0 ? gS + (size_t)s * rows : nullptr,
-                                                 s >= 0 ? gI + (size_t)s * rows : nullptr, s >= 0 ? gR + (size_t)s * rows : nullptr,
-                                                 p->linear3_weight, p->linear3_bias, p->linearS2_weight, p->linearS2_bias,
-                                                 g->hubidx, HubP0, HubP1, g->hub_seg_ptr, g->n_seg, i > 1 ? 1 : 0));
-            if (sampled) gn_prof_end(2, st);
-            GN_LAUNCH_CHECK();
-        }
-    } else
-    for (int i = G - 1; i >= 1; --i) {
-        const float* yi = sol + (size_t)i * 4 * slab;
-        const float dt = dt_host[i - 1];
-        {
-            if (int e = gn_launch_mlp_any(g, yi, p->odefunc_linear_weight, p->odefunc_linear_bias, Z, 2 * rows, H, st)) return e;
-            hipLaunchKernelGGL(k_bwd_q, dim3(2048), dim3(256), 0, st, a, Z, beta, q, (long)rows, H);
-            GN_LAUNCH_CHECK();
-            dim3 ggrid((unsigned)((g->n + rpw - 1) / rpw), (unsigned)(rows / g->n));
-            const float *AIhub = nullptr, *GQhub = nullptr;
-            if (int e = gn_hub_gather(g, rows / g->n, H, Z + slab, q, hub_scratch, &AIhub, &GQhub, st)) return e;
-            BWD_DISPATCH(lpr, hipLaunchKernelGGL(k_bwd_gather<LPR>, ggrid, dim3(256), 0, st, g->rowptr, g->col, g->n, (long)rows, H,
-                                                 a, Z, q, beta, gamma, dpre, g->hubidx, AIhub, GQhub, g->n_hub));
-            GN_LAUNCH_CHECK();
-            if (H == 128) {
-                if (int e = gn_launch_bwd_mlp128(g, dpre, yi, p->odefunc_linear_weight, dt, a, rows, part, &slots_used, st)) return e;
-            } else
-            BWD_DISPATCH(lpr, {
-                slots_used = BWD_NWG;
-                hipLaunchKernelGGL(k_bwd_mlp<LPR>, dim3(BWD_NWG), dim3(256), mlp_lds, st, dpre, yi, p->odefunc_linear_weight, dt,
-                                   a, (long)rows, H, part);
-            });
-            GN_LAUNCH_CHECK();
-        }
-        if (int e = head(i - 1)) return e;
-    }
-    {
-        const size_t lds = (size_t)rpw * 2 * H * sizeof(float);
-        const int egrid = (int)std::min<long>(BWD_NWG, std::max<long>(1, (rows + rpw - 1) / rpw));
-        slots_used = std::max(slots_used, egrid);
-        BWD_DISPATCH(lpr, hipLaunchKernelGGL(k_enc_bwd<LPR>, dim3(egrid), dim3(256), lds, st, a, sol, x, (long)rows, H, part));
-        GN_LAUNCH_CHECK();
-    }
-    }   // !tiny
-    // slot layout order == PartLayout order: W, b, w3, b3, w2, b2, w1, b1
-    GradDst gd;
-    gd.dst[0] = (float*)grads->odefunc_linear_weight; gd.dst[1] = (float*)grads->odefunc_linear_bias;
-    gd.dst[2] = (float*)grads->linear3_weight;        gd.dst[3] = (float*)grads->linear3_bias;
-    gd.dst[4] = (float*)grads->linearS2_weight;       gd.dst[5] = (float*)grads->linearS2_bias;
-    gd.dst[6] = (float*)grads->linearS1_weight;       gd.dst[7] = (float*)grads->linearS1_bias;
-    const int offs[9] = {L.oW(), L.ob(), L.ow3(), L.ob3(), L.ow2(), L.ob2(), L.ow1(), L.ob1(), L.total()};
-    for (int k = 0; k < 9; ++k) gd.off[k] = offs[k];
-    hipLaunchKernelGGL(k_reduce_parts, dim3((L.total() + 15) / 16), dim3(256), 0, st, part, slots_used, L.total(), gd);
-    GN_LAUNCH_CHECK();
-    return 0;
+    return e ? e : gn_launch_reduce_all(c.part, c.slots_used, H, grads, c.st);
 }
 
 // The persistent adjoint sweeps' give-up word (the control block at the end of the fixed part of the backward workspace).
 extern "C" int gnode_backward_status(int64_t rows, int32_t H, const void* workspace, void* stream, int32_t* code_host) {
     GN_CHECK_ARG(workspace && code_host && rows > 0, "gnode_backward_status: null pointer");
-    *code_host = 0;
-    if (H != 64 && H > 32) return 0;
-    unsigned err[2] = {0, 0};
-    const PersCtl* ctl = (const PersCtl*)((const char*)workspace + backward_fixed_bytes(rows, H) - gn_pers64_ctl_bytes());
-    GN_HIP(hipMemcpyAsync(err, ctl->error, sizeof(err), hipMemcpyDeviceToHost, (hipStream_t)stream));
-    GN_HIP(hipStreamSynchronize((hipStream_t)stream));
-    *code_host = (int32_t)err[0];
-    if (err[0]) gnode_set_error("persistent adjoint sweep: a workgroup gave up waiting for epoch %u of its group", err[1]);
-    return 0;
+    return gn_read_give_up((const char*)workspace + backward_layout(rows, H).ctl, H, stream, code_host, "persistent adjoint sweep");
 }
 
 // diagnostic build (GN_PERS_PROF): per-phase 100 MHz ticks of the last persistent adjoint sweep on this workspace
 extern "C" int gnode_backward_phase_ticks(int64_t rows, int32_t H, const void* workspace, uint64_t* ticks8_host) {
-    const PersCtl* ctl = (const PersCtl*)((const char*)workspace + backward_fixed_bytes(rows, H) - gn_pers64_ctl_bytes());
+    const PersCtl* ctl = (const PersCtl*)((const char*)workspace + backward_layout(rows, H).ctl);
     GN_HIP(hipMemcpy(ticks8_host, ctl->prof, 8 * sizeof(uint64_t), hipMemcpyDeviceToHost));
     return 0;
 }
 
 // --------------------------------------------------------------------------- pieces shared with the RK4 adjoint
-// (gnode_rhs_vjp.hip): the same kernels and launch shapes as gnode_backward_f32's `head` step, encoder step and final
-// reduction above.
+// (gnode_rhs_vjp.hip): the head step, encoder step and final reduction of gnode_backward_f32.
 int gn_launch_head_bwd(long rows, int H, const float* Ysol, const float* gS, const float* gI, const float* gR,
                        const gnode_params* p, float* a, float* part, int* slots_used, hipStream_t st) {
-    const int lpr = lpr_of(H), rpw = 256 / lpr;
+    const int lpr = gn_lpr(H), rpw = 256 / lpr;
     const size_t lds = (size_t)rpw * (4 * H + 9) * sizeof(float);
     const int hgrid = (int)std::min<long>(BWD_NWG, std::max<long>(1, (rows + rpw - 1) / rpw));
     *slots_used = std::max(*slots_used, hgrid);
-    BWD_DISPATCH(lpr, hipLaunchKernelGGL(k_head_bwd<LPR>, dim3(hgrid), dim3(256), lds, st, Ysol, rows, H, gS, gI, gR,
-                                         p->linear3_weight, p->linear3_bias, p->linearS2_weight, p->linearS2_bias, a, part));
+    GN_LPR_DISPATCH(32, lpr, hipLaunchKernelGGL(k_head_bwd<LPR>, dim3(hgrid), dim3(256), lds, st, Ysol, rows, H, gS, gI, gR,
+                                                p->linear3_weight, p->linear3_bias, p->linearS2_weight, p->linearS2_bias, a, part));
     GN_LAUNCH_CHECK();
     return 0;
 }
 
 int gn_launch_enc_bwd(long rows, int H, const float* a, const float* sol0, const float* x, float* part, int* slots_used,
                       hipStream_t st) {
-    const int lpr = lpr_of(H), rpw = 256 / lpr;
+    const int lpr = gn_lpr(H), rpw = 256 / lpr;
     const size_t lds = (size_t)rpw * 2 * H * sizeof(float);
     const int egrid = (int)std::min<long>(BWD_NWG, std::max<long>(1, (rows + rpw - 1) / rpw));
     *slots_used = std::max(*slots_used, egrid);
-    BWD_DISPATCH(lpr, hipLaunchKernelGGL(k_enc_bwd<LPR>, dim3(egrid), dim3(256), lds, st, a, sol0, x, rows, H, part));
+    GN_LPR_DISPATCH(32, lpr, hipLaunchKernelGGL(k_enc_bwd<LPR>, dim3(egrid), dim3(256), lds, st, a, sol0, x, rows, H, part));
     GN_LAUNCH_CHECK();
     return 0;
 }

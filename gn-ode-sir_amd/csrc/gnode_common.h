@@ -4,6 +4,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstdint>
+#include <vector>
 #include "gnode.h"
 
 struct gnode_graph_s {
@@ -121,3 +122,40 @@ void gn_prof_end(int kind, hipStream_t st);
 #define GN_LAUNCH_CHECK() GN_HIP(hipGetLastError())
 
 static inline size_t gn_align(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
+
+// lanes per row of the lane-group kernels: H/4 rounded up to a power of two
+static inline int gn_lpr(int H) {
+    int need = H / 4, l = 1;
+    while (l < need) l <<= 1;
+    return l;
+}
+
+// switch over it to a compile-time LPR; a file's largest instance is LMAX (32 or 64), which larger values also take
+#define GN_LPR_DISPATCH(LMAX, lpr, ...)                            \
+    switch (lpr) {                                                 \
+        case 1: { constexpr int LPR = 1; __VA_ARGS__; } break;     \
+        case 2: { constexpr int LPR = 2; __VA_ARGS__; } break;     \
+        case 4: { constexpr int LPR = 4; __VA_ARGS__; } break;     \
+        case 8: { constexpr int LPR = 8; __VA_ARGS__; } break;     \
+        case 16: { constexpr int LPR = 16; __VA_ARGS__; } break;   \
+        case 32: { constexpr int LPR = 32; __VA_ARGS__; } break;   \
+        default: { constexpr int LPR = LMAX; __VA_ARGS__; } break; \
+    }
+
+// out_rows (the grid points written to S / I / R; null = every one) must be ascending grid indices in [0, G)
+static inline int gn_check_out_rows(const char* fn, const int32_t* out_rows, int n_out, int G) {
+    if (out_rows)
+        for (int i = 0; i < n_out; ++i)
+            GN_CHECK_ARG(out_rows[i] >= 0 && out_rows[i] < G && (i == 0 || out_rows[i] > out_rows[i - 1]),
+                         "%s: out_rows must be ascending grid indices in [0,%d)", fn, G);
+    return 0;
+}
+// the output row of each of the G grid points, or -1 (out_rows checked)
+static inline std::vector<int> gn_out_slots(const int32_t* out_rows, int n_out, int G) {
+    std::vector<int> slot(G, -1);
+    for (int i = 0; i < (out_rows ? n_out : G); ++i) slot[out_rows ? out_rows[i] : i] = i;
+    return slot;
+}
+// the persistent launches' give-up word in the control block at `ctl` (forward and backward workspaces): *code_host = 0 or
+// the code, with the error message naming `who`; synchronises the stream
+int gn_read_give_up(const void* ctl, int H, void* stream, int32_t* code_host, const char* who);

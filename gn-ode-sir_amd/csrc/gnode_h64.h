@@ -1,6 +1,8 @@
 // H = 64 fast path launchers (gnode_h64.hip), used by the C-ABI host code in gnode_ode.hip.
 #pragma once
 #include "gnode_common.h"
+#include "gnode_pers64.h"
+#include "gnode_persg.h"
 
 struct Step64Out {
     float* S; float* I; float* R;   // this step's output rows [rows], or null
@@ -13,9 +15,24 @@ struct Step64Out {
 // True when gnode_forward_f32 (H = 64, trajectory kept) stores A Z_I(y_k) in the 4th slab of sol[k], 1 <= k <= n_steps - 1,
 // instead of the beta-gamma copy; gnode_backward_f32 asks the same question about the `sol` it is handed.
 bool gn_sol_carries_ai(const gnode_graph_s* g, long rows, int H, int n_steps, int n_out, int flags);
-// 2 = persistent launch, 1 = one workgroup per sample, 0 = one launch per step (gnode_ode.hip); plan may be null
-struct PersPlan;
-int gn_forward_kind(const gnode_graph_s* g, long rows, int H, int method, int n_steps, int n_out, bool with_sol, int flags, PersPlan* plan);
+
+// Which form gnode_forward_f32 takes for a call (gnode_forward_path() returns the number, include/gnode.h documents it).
+enum class FwdPath : int {
+    per_step = 0,   // one launch per step (Euler at any H, RK4)
+    tiny = 1,       // H = 64: one workgroup per sample (tiny graphs in batches too large for one resident grid)
+    pers64 = 2,     // H = 64: ONE persistent launch (gnode_pers64.hip)
+    persg = 3,      // H = 8 / 16 / 32: ONE persistent launch (gnode_persg.hip)
+};
+struct FwdPlan {
+    FwdPath path;
+    bool h64;         // H = 64 Euler: the fused step kernels of gnode_h64.hip on the per-step path
+    int n_emit;       // grid points written to S / I / R
+    PersPlan pers;    // path == pers64
+    PersgPlan persg;  // path == persg
+};
+// n_emit: emitted grid points; with_sol: a trajectory is requested.  The backward asks the same question (same arguments)
+// to know what `sol` / `keep` hold.
+FwdPlan gn_forward_plan(const gnode_graph_s* g, long rows, int H, int method, int n_steps, int n_emit, bool with_sol, int flags);
 
 int gn_h64_set_attributes();    // once per device, from gnode_graph_create
 int gn_launch_mlp64(const gnode_graph_s* g, const float* X, const float* W, const float* b, float* Z, long nrows, hipStream_t st);

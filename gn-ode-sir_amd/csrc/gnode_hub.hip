@@ -197,23 +197,6 @@ void gn_hub_free(gnode_graph_s* g) {
     if (g->hub_seg_ptr) (void)hipFree(g->hub_seg_ptr);
 }
 
-static int hub_lpr(int H) {
-    int need = H / 4, l = 1;
-    while (l < need) l <<= 1;
-    return l;
-}
-
-#define HUB_DISPATCH(lpr, ...)                                   \
-    switch (lpr) {                                               \
-        case 1: { constexpr int LPR = 1; __VA_ARGS__; } break;   \
-        case 2: { constexpr int LPR = 2; __VA_ARGS__; } break;   \
-        case 4: { constexpr int LPR = 4; __VA_ARGS__; } break;   \
-        case 8: { constexpr int LPR = 8; __VA_ARGS__; } break;   \
-        case 16: { constexpr int LPR = 16; __VA_ARGS__; } break; \
-        case 32: { constexpr int LPR = 32; __VA_ARGS__; } break; \
-        default: { constexpr int LPR = 64; __VA_ARGS__; } break; \
-    }
-
 size_t gn_hub_scratch_bytes(const gnode_graph_s* g, long B, int H, int ntables) {
     if (g->n_hub == 0) return 0;
     const size_t part_f = (size_t)B * g->n_seg * H, hub_f = (size_t)B * g->n_hub * H;
@@ -236,11 +219,11 @@ int gn_hub_segments2(const gnode_graph_s* g, long B, int H, const float* T0, con
     const size_t part_b = gn_align(sizeof(float) * (size_t)B * g->n_seg * H);
     float* P0 = (float*)scratch;
     float* P1 = T1 ? (float*)((char*)scratch + part_b) : nullptr;       // (inside the two-table scratch of gn_hub_scratch_bytes)
-    const int lpr = hub_lpr(H), gpw = 256 / lpr;
+    const int lpr = gn_lpr(H), gpw = 256 / lpr;
     for (long b0 = 0; b0 < B; b0 += 65535) {
         const unsigned nb = (unsigned)std::min<long>(65535, B - b0);
-        HUB_DISPATCH(lpr, hipLaunchKernelGGL(k_hub_seg<LPR>, dim3((unsigned)((g->n_seg + gpw - 1) / gpw), nb), dim3(256), 0, st,
-                                             g->seg_lo, g->seg_hi, g->col, g->n, g->n_seg, H, T0, T1, P0, P1, b0));
+        GN_LPR_DISPATCH(64, lpr, hipLaunchKernelGGL(k_hub_seg<LPR>, dim3((unsigned)((g->n_seg + gpw - 1) / gpw), nb), dim3(256), 0, st,
+                                                    g->seg_lo, g->seg_hi, g->col, g->n, g->n_seg, H, T0, T1, P0, P1, b0));
     }
     GN_LAUNCH_CHECK();
     *P0out = P0;
@@ -263,13 +246,13 @@ int gn_hub_gather(const gnode_graph_s* g, long B, int H, const float* T0, const 
     float* a0 = (float*)(base + part_b);
     float* P1 = (float*)(base + part_b + hub_b);
     float* a1 = (float*)(base + 2 * part_b + hub_b);
-    const int lpr = hub_lpr(H), gpw = 256 / lpr;
+    const int lpr = gn_lpr(H), gpw = 256 / lpr;
     GN_CHECK_ARG(B <= 65535, "hub sums: %ld samples per launch exceed the grid's y extent (split the batch)", B);
-    HUB_DISPATCH(lpr, hipLaunchKernelGGL(k_hub_seg<LPR>, dim3((unsigned)((g->n_seg + gpw - 1) / gpw), (unsigned)B), dim3(256), 0, st,
-                                         g->seg_lo, g->seg_hi, g->col, g->n, g->n_seg, H, T0, T1, P0, P1, 0L));
+    GN_LPR_DISPATCH(64, lpr, hipLaunchKernelGGL(k_hub_seg<LPR>, dim3((unsigned)((g->n_seg + gpw - 1) / gpw), (unsigned)B), dim3(256), 0, st,
+                                                g->seg_lo, g->seg_hi, g->col, g->n, g->n_seg, H, T0, T1, P0, P1, 0L));
     GN_LAUNCH_CHECK();
-    HUB_DISPATCH(lpr, hipLaunchKernelGGL(k_hub_reduce<LPR>, dim3((unsigned)((g->n_hub + gpw - 1) / gpw), (unsigned)B), dim3(256), 0,
-                                         st, g->hub_seg_ptr, g->n_hub, g->n_seg, H, P0, nt == 2 ? P1 : nullptr, a0, a1));
+    GN_LPR_DISPATCH(64, lpr, hipLaunchKernelGGL(k_hub_reduce<LPR>, dim3((unsigned)((g->n_hub + gpw - 1) / gpw), (unsigned)B), dim3(256), 0,
+                                                st, g->hub_seg_ptr, g->n_hub, g->n_seg, H, P0, nt == 2 ? P1 : nullptr, a0, a1));
     GN_LAUNCH_CHECK();
     *A0 = a0;
     if (A1) *A1 = nt == 2 ? a1 : nullptr;

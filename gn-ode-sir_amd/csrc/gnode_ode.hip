@@ -445,12 +445,6 @@ __global__ __launch_bounds__(256) void k_fill_bg(float* __restrict__ sol, size_t
 }
 
 // --------------------------------------------------------------------------- host side
-static int lpr_for(int H) {
-    int need = H / 4, l = 1;
-    while (l < need) l <<= 1;
-    return l;
-}
-
 static int check_H(int H) {
     if (H < 4 || H > 256 || (H % 4) != 0) {
         gnode_set_error("unsupported hidden size H=%d (need 4 <= H <= 256, H %% 4 == 0)", H);
@@ -458,17 +452,6 @@ static int check_H(int H) {
     }
     return 0;
 }
-
-#define DISPATCH_LPR(lpr, ...)                                   \
-    switch (lpr) {                                               \
-        case 1: { constexpr int LPR = 1; __VA_ARGS__; } break;   \
-        case 2: { constexpr int LPR = 2; __VA_ARGS__; } break;   \
-        case 4: { constexpr int LPR = 4; __VA_ARGS__; } break;   \
-        case 8: { constexpr int LPR = 8; __VA_ARGS__; } break;   \
-        case 16: { constexpr int LPR = 16; __VA_ARGS__; } break; \
-        case 32: { constexpr int LPR = 32; __VA_ARGS__; } break; \
-        default: { constexpr int LPR = 64; __VA_ARGS__; } break; \
-    }
 
 static int launch_mlp(const gnode_graph_s* g, const float* X, const float* W, const float* b, float* Z, long nrows, int H, hipStream_t st) {
     if (nrows == 0) return 0;
@@ -479,10 +462,10 @@ static int launch_mlp(const gnode_graph_s* g, const float* X, const float* W, co
         if (int e = gn_launch_mlp128(g, X, W, b, Z, nrows, st)) return e;    // matrix cores (gnode_h128.hip)
     } else {
         GN_CHECK_ARG(H <= 128, "generic node-MLP path supports H <= 128 (got %d)", H);
-        const int lpr = lpr_for(H);
+        const int lpr = gn_lpr(H);
         const int rpw = 256 / lpr;
         const size_t lds = ((size_t)H * H + (size_t)rpw * H) * sizeof(float);
-        DISPATCH_LPR(lpr, hipLaunchKernelGGL(k_mlp_generic<LPR>, dim3((unsigned)((nrows + rpw - 1) / rpw)), dim3(256), lds, st, X, W, b, Z, nrows, H));
+        GN_LPR_DISPATCH(64, lpr, hipLaunchKernelGGL(k_mlp_generic<LPR>, dim3((unsigned)((nrows + rpw - 1) / rpw)), dim3(256), lds, st, X, W, b, Z, nrows, H));
     }
     if (sampled) prof_mark(1, st);
     GN_LAUNCH_CHECK();
@@ -504,7 +487,7 @@ int gn_ode_set_attributes() {
 static int launch_gather(gnode_graph_t g, int mode, long rows, int H, float* Y, const float* Z, const float* beta,
                          const float* gamma, int bg_stride, float dt, float* dY, const gnode_params* p, StepOut out,
                          void* hub_scratch, hipStream_t st) {
-    const int lpr = lpr_for(H), rpw = 256 / lpr;
+    const int lpr = gn_lpr(H), rpw = 256 / lpr;
     const long B = rows / g->n;
     dim3 grid((unsigned)((g->n + rpw - 1) / rpw), (unsigned)B);
     const float *w3 = p ? p->linear3_weight : nullptr, *b3 = p ? p->linear3_bias : nullptr;
@@ -513,11 +496,11 @@ static int launch_gather(gnode_graph_t g, int mode, long rows, int H, float* Y, 
     if (int e = gn_hub_gather(g, B, H, Z + (size_t)rows * H, nullptr, hub_scratch, &AIhub, nullptr, st)) return e;
     const bool sampled = mode == 1 && prof_begin(0, st);
     if (mode == 0) {
-        DISPATCH_LPR(lpr, hipLaunchKernelGGL((k_gather<LPR, 0>), grid, dim3(256), 0, st, g->rowptr, g->col, g->n, rows, H,
-                                             Y, Z, beta, gamma, bg_stride, dt, dY, w3, b3, w2, b2, out, g->hubidx, AIhub, g->n_hub));
+        GN_LPR_DISPATCH(64, lpr, hipLaunchKernelGGL((k_gather<LPR, 0>), grid, dim3(256), 0, st, g->rowptr, g->col, g->n, rows, H,
+                                                    Y, Z, beta, gamma, bg_stride, dt, dY, w3, b3, w2, b2, out, g->hubidx, AIhub, g->n_hub));
     } else {
-        DISPATCH_LPR(lpr, hipLaunchKernelGGL((k_gather<LPR, 1>), grid, dim3(256), 0, st, g->rowptr, g->col, g->n, rows, H,
-                                             Y, Z, beta, gamma, bg_stride, dt, dY, w3, b3, w2, b2, out, g->hubidx, AIhub, g->n_hub));
+        GN_LPR_DISPATCH(64, lpr, hipLaunchKernelGGL((k_gather<LPR, 1>), grid, dim3(256), 0, st, g->rowptr, g->col, g->n, rows, H,
+                                                    Y, Z, beta, gamma, bg_stride, dt, dY, w3, b3, w2, b2, out, g->hubidx, AIhub, g->n_hub));
     }
     if (sampled) prof_mark(0, st);
     GN_LAUNCH_CHECK();
@@ -526,10 +509,10 @@ static int launch_gather(gnode_graph_t g, int mode, long rows, int H, float* Y, 
 
 static int launch_readout(const float* Y, long rows, int H, const gnode_params* p, float* S, float* I, float* R,
                           hipStream_t st) {
-    const int lpr = lpr_for(H), rpw = 256 / lpr;
-    DISPATCH_LPR(lpr, hipLaunchKernelGGL(k_readout<LPR>, dim3((unsigned)((rows + rpw - 1) / rpw)), dim3(256), 0, st, Y,
-                                         rows, H, p->linear3_weight, p->linear3_bias, p->linearS2_weight,
-                                         p->linearS2_bias, S, I, R));
+    const int lpr = gn_lpr(H), rpw = 256 / lpr;
+    GN_LPR_DISPATCH(64, lpr, hipLaunchKernelGGL(k_readout<LPR>, dim3((unsigned)((rows + rpw - 1) / rpw)), dim3(256), 0, st, Y,
+                                                rows, H, p->linear3_weight, p->linear3_bias, p->linearS2_weight,
+                                                p->linearS2_bias, S, I, R));
     GN_LAUNCH_CHECK();
     return 0;
 }
@@ -539,8 +522,6 @@ static int launch_readout(const float* Y, long rows, int H, const gnode_params* 
 // never inside a stream capture): dynamic-LDS attributes of every kernel that can ask for more than 64 KB, and the
 // device's CU count.  The only process-wide state besides the opt-in profiler: write-once per device, under a lock.
 #include <mutex>
-#include "gnode_pers64.h"
-#include "gnode_persg.h"
 static std::mutex g_dev_mu;
 static bool g_dev_done[64] = {};
 static int g_dev_cu[64] = {};
@@ -694,36 +675,216 @@ extern "C" int gnode_rhs_f32(gnode_graph_t g, const float* x, const float* W, co
 }
 
 // --------------------------------------------------------------------------- forward
-// Which form the H = 64 Euler forward takes for a batch: 2 = ONE persistent launch (gnode_pers64.hip; preferred wherever
-// its plan fits -- down to karate: it measured faster than the one-workgroup kernels, 0.11 vs 0.17 ms for 39 steps, and
-// its adjoint sweep 0.18 vs 0.35 ms), 1 = one workgroup per sample (tiny graphs in batches too large for one resident
-// grid), 0 = one launch per step.  The backward asks the same question (same arguments) to know what `sol` / `keep` hold.
-int gn_forward_kind(const gnode_graph_s* g, long rows, int H, int method, int n_steps, int n_out, bool with_sol, int flags, PersPlan* plan) {
-    if (method == 0 && H <= 32 && n_steps >= 1 && !(flags & GNODE_FWD_PER_STEP) && gn_persg_plan(g, rows, H, n_steps, nullptr)) return 3;
-    if (!(H == 64 && method == 0) || n_steps < 1) return 0;
-    PersPlan pl;
-    if (!(flags & GNODE_FWD_PER_STEP) && gn_pers64_plan(g, rows / g->n, n_steps, &pl)) { if (plan) *plan = pl; return 2; }
-    if (gn_tiny64_ok(g->n, n_steps, n_out, !with_sol)) return 1;
-    return 0;
+// Which form the forward takes (FwdPath): the H = 64 Euler forward prefers ONE persistent launch wherever its plan fits --
+// down to karate: it measured faster than the one-workgroup kernels, 0.11 vs 0.17 ms for 39 steps, and its adjoint sweep
+// 0.18 vs 0.35 ms -- then one workgroup per sample (tiny graphs in batches too large for one resident grid), then one launch
+// per step.  H = 8 / 16 / 32 take their persistent launch where the batch fits one resident grid.
+FwdPlan gn_forward_plan(const gnode_graph_s* g, long rows, int H, int method, int n_steps, int n_emit, bool with_sol, int flags) {
+    FwdPlan pl{};
+    pl.path = FwdPath::per_step;
+    pl.h64 = H == 64 && method == 0;
+    pl.n_emit = n_emit;
+    const bool persist = n_steps >= 1 && !(flags & GNODE_FWD_PER_STEP);
+    if (method == 0 && H <= 32 && persist && gn_persg_plan(g, rows, H, n_steps, &pl.persg)) pl.path = FwdPath::persg;
+    else if (pl.h64 && persist && gn_pers64_plan(g, rows / g->n, n_steps, &pl.pers)) pl.path = FwdPath::pers64;
+    else if (pl.h64 && n_steps >= 1 && gn_tiny64_ok(g->n, n_steps, n_emit, !with_sol)) pl.path = FwdPath::tiny;
+    return pl;
 }
 
-static size_t forward_fixed_bytes(int64_t rows, int32_t H, int32_t method) {
-    const size_t slab = gn_align((size_t)rows * H * sizeof(float));
-    size_t nslab = 5;                       // Y[3], Z[2]
-    if (method == 1) nslab += 3 * 5;        // k1..k4, ytmp (3 slabs each)
-    // + one 256-B ZERO ROW behind each of the two gather tables (H = 64 step kernel: rows shorter than the gather
-    //   width read it instead of branching per neighbour)
-    // + the control block of the persistent one-launch path (gnode_pers64.hip): tickets, barrier flags, give-up word
-    return nslab * slab + 512 + 2 * gn_align((size_t)rows * sizeof(float)) + gn_align((size_t)rows * 4 * sizeof(float)) +
-           gn_pers64_ctl_bytes();
-}
-static char* forward_ctl_ptr(void* workspace, int64_t rows, int32_t H, int32_t method) {
-    return (char*)workspace + forward_fixed_bytes(rows, H, method) - gn_pers64_ctl_bytes();
+// The forward workspace as byte offsets, in order: Y [3 slabs, element-contiguous] | Z [2 slabs; on the H = 64 path
+// [table 0][zero row][table 1][zero row]: rows shorter than the step kernel's gather width read a zero row instead of
+// branching per neighbour] | beta | gamma | projected R [rows][4] | (rk4) k1..k4, ytmp [3 slabs each] | the control block
+// of the persistent launches (tickets, barrier flags, give-up word) | `fixed`: the hub scratch (gn_hub_scratch_bytes).
+struct FwdLayout { size_t Y, Z, beta, gamma, pr, rk, ctl, fixed; };
+static FwdLayout forward_layout(int64_t rows, int32_t H, int32_t method) {
+    const size_t slab = gn_align((size_t)rows * H * sizeof(float)), vec = gn_align((size_t)rows * sizeof(float));
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t at = off; off += bytes; return at; };
+    FwdLayout L;
+    L.Y = take(3 * slab); L.Z = take(2 * slab + 512); L.beta = take(vec); L.gamma = take(vec);
+    L.pr = take(gn_align((size_t)rows * 4 * sizeof(float)));
+    L.rk = take(method == 1 ? 15 * slab : 0);
+    L.ctl = take(gn_pers64_ctl_bytes());
+    L.fixed = off;
+    return L;
 }
 
 extern "C" size_t gnode_forward_workspace_bytes(gnode_graph_t g, int64_t rows, int32_t H, int32_t method) {
     if (!g || rows <= 0 || H <= 0) return 0;
-    return forward_fixed_bytes(rows, H, method) + gn_hub_scratch_bytes(g, rows / g->n, H, 1);
+    return forward_layout(rows, H, method).fixed + gn_hub_scratch_bytes(g, rows / g->n, H, 1);
+}
+
+// One forward call as the path launchers see it.
+struct FwdCall {
+    gnode_graph_s* g;
+    const gnode_params* p;
+    const float* dt_host;
+    int n_steps, H;
+    long rows;
+    size_t slab;                        // rows * H floats
+    float *S, *I, *R, *sol, *keep;
+    const int* slot;                    // [n_steps + 1]: output row of each grid point, or -1
+    float *Y, *Z, *beta, *gamma, *rk; char* ctl; void* hub_scratch;   // workspace (forward_layout)
+    float* PR;                          // H = 64 inference (no trajectory): R's 4-float projection, else null
+    float *zi_cur, *zi_nxt;             // gather tables of the current and the next step
+    hipStream_t st;
+    // grid point gi's row of an output (S, I or R), or null when gi is not emitted
+    float* out(float* O, int gi) const { return slot[gi] >= 0 ? O + (size_t)slot[gi] * rows : nullptr; }
+};
+
+// sol[g][3rd slab] = sol[0][3rd slab] for g = 1 .. G-1 (the H = 64 paths keep A Z_I(y_k) there instead)
+static int fill_bg(const FwdCall& c) {
+    if (!c.sol || c.n_steps < 1) return 0;
+    const size_t slab4 = c.slab / 4;
+    hipLaunchKernelGGL(k_fill_bg, dim3((unsigned)std::min<size_t>((slab4 + 255) / 256, 2048)), dim3(256), 0, c.st, c.sol, slab4,
+                       c.n_steps + 1);
+    GN_LAUNCH_CHECK();
+    return 0;
+}
+
+// Grid point 0: the encoder, beta / gamma, trajectory point 0, the read-out and (Euler below H = 128) the first gather table
+// Z_I(y_0).  The persistent launches' control block is zeroed by the prologue's first workgroup: one launch less in front of them.
+static int forward_prologue(const FwdCall& c, const FwdPlan& pl, const float* x, int method) {
+    const gnode_params* p = c.p;
+    const int H = c.H, lpr = gn_lpr(H), rpw = 256 / lpr;
+    const dim3 grid((unsigned)((c.rows + rpw - 1) / rpw));
+    if (pl.h64 && c.n_steps > 0)        // encoder, beta/gamma, trajectory point 0, read-out, projected R and Z_I(y_0): one launch
+        return gn_launch_prologue64(x, p, c.Y, c.beta, c.gamma, c.sol, c.zi_cur, c.zi_nxt, c.PR, c.out(c.S, 0), c.out(c.I, 0),
+                                    c.out(c.R, 0), c.rows, pl.path == FwdPath::pers64 ? c.ctl : nullptr, gn_pers64_ctl_bytes(), c.st);
+    if (method == 0 && H < 128 && c.n_steps > 0) {     // generic H: encoder, read-out and Z_I(y_0) in one launch
+        uint32_t* ctl = pl.path == FwdPath::persg ? (uint32_t*)c.ctl : nullptr;
+        GN_LPR_DISPATCH(64, lpr, hipLaunchKernelGGL(k_prologue_generic<LPR>, grid, dim3(256), (size_t)H * H * sizeof(float), c.st, x,
+                                                    p->linearS1_weight, p->linearS1_bias, p->odefunc_linear_weight,
+                                                    p->odefunc_linear_bias, p->linear3_weight, p->linear3_bias, p->linearS2_weight,
+                                                    p->linearS2_bias, c.Y, c.beta, c.gamma, c.sol, c.zi_cur, c.out(c.S, 0),
+                                                    c.out(c.I, 0), c.out(c.R, 0), c.rows, H, ctl, (int)(gn_pers64_ctl_bytes() / 4)));
+        GN_LAUNCH_CHECK();
+        return 0;
+    }
+    // encoder, then the read-out (H = 128, rk4, no steps: the steps form their own node-MLP tables)
+    GN_LPR_DISPATCH(64, lpr, hipLaunchKernelGGL(k_encode<LPR>, grid, dim3(256), 0, c.st, x, p->linearS1_weight, p->linearS1_bias,
+                                                c.Y, c.beta, c.gamma, c.sol, c.rows, H));
+    GN_LAUNCH_CHECK();
+    if (c.slot[0] >= 0) return launch_readout(c.Y, c.rows, H, p, c.out(c.S, 0), c.out(c.I, 0), c.out(c.R, 0), c.st);
+    return 0;
+}
+
+// mid-size graphs, H = 64: ONE persistent launch, every workgroup keeps its rows in registers for all steps (gnode_pers64.hip)
+static int forward_pers64(const FwdCall& c, const FwdPlan& pl) {
+    const gnode_params* p = c.p;
+    const bool sampled = prof_begin(0, c.st);
+    if (int e = gn_launch_pers64(c.g, pl.pers, c.rows, c.Y, c.PR, c.zi_cur, c.zi_nxt, p->odefunc_linear_weight, p->odefunc_linear_bias,
+                                 c.beta, c.gamma, c.dt_host, c.slot + 1, c.n_steps, p, c.S, c.I, c.R, c.sol, c.keep, c.ctl, true, c.st))
+        return e;
+    if (sampled) prof_mark(0, c.st);
+    return 0;
+}
+
+// small hidden sizes, batches that fit one resident grid: ONE persistent launch (gnode_persg.hip)
+static int forward_persg(const FwdCall& c, const FwdPlan& pl) {
+    const bool sampled = prof_begin(0, c.st);
+    if (int e = gn_launch_persg(c.g, pl.persg, c.rows, c.H, c.Y, c.zi_cur, c.zi_nxt, c.beta, c.gamma, c.dt_host, c.slot + 1, c.n_steps,
+                                c.p, c.S, c.I, c.R, c.sol, c.ctl, true, c.st))
+        return e;
+    if (sampled) prof_mark(0, c.st);
+    return fill_bg(c);
+}
+
+// tiny graphs, H = 64: the whole integration in one launch (one workgroup per sample, state in LDS)
+static int forward_tiny(const FwdCall& c) {
+    const gnode_params* p = c.p;
+    if (int e = gn_launch_tiny64(c.g, c.rows, c.Y, c.zi_cur, c.PR, p->odefunc_linear_weight, p->odefunc_linear_bias, c.beta, c.gamma,
+                                 c.dt_host, c.slot + 1, c.n_steps, p, c.S, c.I, c.R, c.sol, c.keep, c.st))
+        return e;
+    return fill_bg(c);
+}
+
+// Euler, one launch per step: H = 64 fused (gnode_h64.hip), generic H fused, H = 128 node MLP + gather
+static int forward_euler_steps(FwdCall c, const FwdPlan& pl) {
+    const gnode_params* p = c.p;
+    const size_t slab = c.slab;
+    const long rows = c.rows;
+    const int H = c.H, lpr = gn_lpr(H), rpw = 256 / lpr;
+    for (int k = 0; k < c.n_steps; ++k) {
+        const float dt = c.dt_host[k];
+        float* sol_next = c.sol ? c.sol + (size_t)(k + 1) * 4 * slab : nullptr;
+        // with a trajectory the fused kernels read point k and write point k+1 (no separate state copy)
+        float* Ycur = c.sol ? c.sol + (size_t)k * 4 * slab : c.Y;
+        if (pl.h64) {
+            // training: the 4th slab of sol[k] (k >= 1; its odeint content is the constant beta-gamma slab of sol[0])
+            // receives A Z_I(y_k), which the adjoint backward would otherwise gather again
+            Step64Out out = {c.out(c.S, k + 1), c.out(c.I, k + 1), c.out(c.R, k + 1), sol_next,
+                             c.keep ? (k >= 1 ? gn_keep_ps(c.keep, rows, k) : nullptr)          // with `keep`: P_S(y_k) there instead
+                                    : ((c.sol && k >= 1) ? c.sol + (size_t)k * 4 * slab + 3 * slab : nullptr),
+                             c.keep ? gn_keep_zs(c.keep, rows, k) : nullptr};
+            const bool sampled = prof_begin(0, c.st);
+            if (int e = gn_launch_step64(c.g, rows, Ycur, c.zi_cur, c.zi_nxt, p->odefunc_linear_weight,
+                                         p->odefunc_linear_bias, c.beta, c.gamma, dt, p, c.PR, out, c.hub_scratch, c.st))
+                return e;
+            if (sampled) prof_mark(0, c.st);
+            if (c.keep) { c.zi_cur = c.zi_nxt; c.zi_nxt = gn_keep_zi(c.keep, rows, std::min(k + 2, c.n_steps)); }
+            else std::swap(c.zi_cur, c.zi_nxt);
+        } else if (H < 128) {
+            // generic H: one fused launch per step (gather + both node MLPs as lane-group mat-vecs); H = 128 takes the
+            // two-launch branch below, whose node MLP runs on the matrix cores (a VALU mat-vec is 12x off the bound there)
+            StepOut out = {c.out(c.S, k + 1), c.out(c.I, k + 1), c.out(c.R, k + 1), sol_next};
+            const float* HubP = nullptr;          // segment partials of the hub rows; the step kernel adds them up itself
+            if (int e = gn_hub_segments(c.g, rows / c.g->n, H, c.zi_cur, c.hub_scratch, &HubP, c.st)) return e;
+            dim3 grid((unsigned)((c.g->n + rpw - 1) / rpw), (unsigned)(rows / c.g->n));
+            const size_t lds = (size_t)H * H * sizeof(float);
+            const bool sampled = prof_begin(0, c.st);
+            // (H < 128 here: W^T is at most 61 KB of dynamic LDS, below the 64 KB that would need an attribute)
+            const bool hubs = c.g->n_hub > 0;
+            GN_LPR_DISPATCH(64, lpr, hipLaunchKernelGGL((hubs ? k_step_generic<LPR, true> : k_step_generic<LPR, false>), grid, dim3(256), lds,
+                                                        c.st, c.g->rowptr, c.g->col, c.g->n, rows, H, Ycur, c.zi_cur, c.zi_nxt,
+                                                        p->odefunc_linear_weight, p->odefunc_linear_bias, c.beta, c.gamma, dt,
+                                                        p->linear3_weight, p->linear3_bias, p->linearS2_weight, p->linearS2_bias, out,
+                                                        c.g->hubidx, HubP, c.g->hub_seg_ptr, c.g->n_seg));
+            if (sampled) prof_mark(0, c.st);
+            GN_LAUNCH_CHECK();
+            std::swap(c.zi_cur, c.zi_nxt);
+        } else {
+            if (int e = launch_mlp(c.g, c.Y, p->odefunc_linear_weight, p->odefunc_linear_bias, c.Z, 2 * rows, H, c.st)) return e;
+            StepOut out = {c.out(c.S, k + 1), c.out(c.I, k + 1), c.out(c.R, k + 1), sol_next};
+            if (int e = launch_gather(c.g, 1, rows, H, c.Y, c.Z, c.beta, c.gamma, 1, dt, nullptr, p, out, c.hub_scratch, c.st)) return e;
+        }
+    }
+    return pl.h64 ? 0 : fill_bg(c);        // (H = 64: those slabs hold A Z_I(y_k) instead, see above)
+}
+
+// torchdiffeq 'rk4' = 3/8 rule, one step at a time
+static int forward_rk4(const FwdCall& c) {
+    const gnode_params* p = c.p;
+    const size_t slab = c.slab;
+    const long rows = c.rows;
+    const int H = c.H;
+    float *Y = c.Y, *Z = c.Z;
+    float* k1 = c.rk; float* k2 = c.rk + 3 * slab; float* k3 = c.rk + 6 * slab; float* k4 = c.rk + 9 * slab;
+    float* yt = c.rk + 12 * slab;
+    const size_t n4 = 3 * slab / 4;
+    const int eg = (int)std::min<size_t>((n4 + 255) / 256, 2048);
+    StepOut none = {nullptr, nullptr, nullptr, nullptr};
+    auto f = [&](float* y, float* kout) -> int {
+        if (int e = launch_mlp(c.g, y, p->odefunc_linear_weight, p->odefunc_linear_bias, Z, 2 * rows, H, c.st)) return e;
+        return launch_gather(c.g, 0, rows, H, y, Z, c.beta, c.gamma, 1, 0.f, kout, nullptr, none, c.hub_scratch, c.st);
+    };
+    const float third = 1.0f / 3.0f;
+    for (int k = 0; k < c.n_steps; ++k) {
+        const float dt = c.dt_host[k];
+        if (int e = f(Y, k1)) return e;
+        hipLaunchKernelGGL(k_lincomb, dim3(eg), dim3(256), 0, c.st, yt, Y, dt, k1, third, nullptr, 0.f, nullptr, 0.f, nullptr, 0.f, n4);
+        if (int e = f(yt, k2)) return e;
+        hipLaunchKernelGGL(k_lincomb, dim3(eg), dim3(256), 0, c.st, yt, Y, dt, k1, -third, k2, 1.f, nullptr, 0.f, nullptr, 0.f, n4);
+        if (int e = f(yt, k3)) return e;
+        hipLaunchKernelGGL(k_lincomb, dim3(eg), dim3(256), 0, c.st, yt, Y, dt, k1, 1.f, k2, -1.f, k3, 1.f, nullptr, 0.f, n4);
+        if (int e = f(yt, k4)) return e;
+        hipLaunchKernelGGL(k_lincomb, dim3(eg), dim3(256), 0, c.st, Y, Y, dt, k1, 0.125f, k2, 0.375f, k3, 0.375f, k4, 0.125f, n4);
+        GN_LAUNCH_CHECK();
+        if (c.sol) GN_HIP(hipMemcpyAsync(c.sol + (size_t)(k + 1) * 4 * slab, Y, 3 * slab * sizeof(float), hipMemcpyDeviceToDevice, c.st));
+        if (c.slot[k + 1] >= 0)
+            if (int e = launch_readout(Y, rows, H, p, c.out(c.S, k + 1), c.out(c.I, k + 1), c.out(c.R, k + 1), c.st)) return e;
+    }
+    return fill_bg(c);
 }
 
 extern "C" int gnode_forward_f32(gnode_graph_t g, const float* x, const gnode_params* p, const float* dt_host,
@@ -746,241 +907,72 @@ extern "C" int gnode_forward_f32(gnode_graph_t g, const float* x, const gnode_pa
         return GNODE_ERR_WORKSPACE;
     }
     const int G = n_steps + 1;
-    if (out_rows_host) {
-        GN_CHECK_ARG(n_out >= 0, "gnode_forward_f32: n_out < 0");
-        for (int i = 0; i < n_out; ++i)
-            GN_CHECK_ARG(out_rows_host[i] >= 0 && out_rows_host[i] < G && (i == 0 || out_rows_host[i] > out_rows_host[i - 1]),
-                         "gnode_forward_f32: out_rows must be ascending grid indices in [0,%d)", G);
-    }
+    if (out_rows_host) GN_CHECK_ARG(n_out >= 0, "gnode_forward_f32: n_out < 0");
+    if (int e = gn_check_out_rows("gnode_forward_f32", out_rows_host, n_out, G)) return e;
+    const FwdPlan pl = gn_forward_plan(g, rows, H, method, n_steps, out_rows_host ? n_out : G, sol != nullptr, flags);
     // kept activations: only the fused H = 64 training path fills them (elsewhere the backward recomputes)
-    if (!(keep && sol && method == 0 && gnode_forward_keep_bytes(g, rows, H, n_steps, out_rows_host ? n_out : G) > 0)) keep = nullptr;
-    if (keep && keep_bytes < gnode_forward_keep_bytes(g, rows, H, n_steps, out_rows_host ? n_out : G)) {
-        gnode_set_error("gnode_forward_f32: keep buffer %zu < %zu", keep_bytes,
-                        gnode_forward_keep_bytes(g, rows, H, n_steps, out_rows_host ? n_out : G));
+    const size_t keep_need = gnode_forward_keep_bytes(g, rows, H, n_steps, pl.n_emit);
+    if (!(keep && sol && method == 0 && keep_need > 0)) keep = nullptr;
+    if (keep && keep_bytes < keep_need) {
+        gnode_set_error("gnode_forward_f32: keep buffer %zu < %zu", keep_bytes, keep_need);
         return GNODE_ERR_WORKSPACE;
     }
     if (sol_info_host) {                         // what this call leaves in `sol` / `keep`: gnode_backward_f32 checks it
-        const int n_emit = out_rows_host ? n_out : G;
-        const int kind = gn_forward_kind(g, rows, H, method, n_steps, n_emit, sol != nullptr, flags, nullptr);
-        *sol_info_host = !sol ? 0 : ((keep ? GNODE_SOL_KEEP : (H == 64 && method == 0 && n_steps >= 1 && kind != 1 ? GNODE_SOL_AI : 0)) |
-                                     (kind == 1 ? GNODE_SOL_TINY : 0));
+        const bool tiny = pl.path == FwdPath::tiny;
+        *sol_info_host = !sol ? 0 : ((keep ? GNODE_SOL_KEEP : (pl.h64 && n_steps >= 1 && !tiny ? GNODE_SOL_AI : 0)) |
+                                     (tiny ? GNODE_SOL_TINY : 0));
     }
-    hipStream_t st = (hipStream_t)stream;
-    const size_t slab = (size_t)rows * H, slab_b = gn_align(slab * sizeof(float));
+    const FwdLayout L = forward_layout(rows, H, method);
     char* ws = (char*)workspace;
-    float* Y = (float*)ws;                       // [3][rows][H] (contiguous: slab strides are elements, not aligned bytes)
-    // keep slabs element-contiguous: Y uses 3*slab floats inside 3 aligned slabs
-    float* Z = (float*)(ws + 3 * slab_b);
-    char* after_z = ws + 5 * slab_b + 512;     // Z: [table 0][zero row][table 1][zero row] on the H = 64 path
-    float* beta = (float*)after_z;
-    float* gamma = (float*)(after_z + gn_align((size_t)rows * sizeof(float)));
-    float* prbuf = (float*)(after_z + 2 * gn_align((size_t)rows * sizeof(float)));
-    float* rk = (float*)(after_z + 2 * gn_align((size_t)rows * sizeof(float)) + gn_align((size_t)rows * 4 * sizeof(float)));
-    void* hub_scratch = ws + forward_fixed_bytes(rows, H, method);      // segment partials + hub sums (graphs with hub rows)
-
-    const int lpr = lpr_for(H), rpw = 256 / lpr;
-    int next_out = 0;  // index into the output list
-    auto out_slot = [&](int gidx) -> int {   // which output row (or -1) grid point gidx is written to
-        if (!out_rows_host) return gidx;
-        if (next_out < n_out && out_rows_host[next_out] == gidx) return next_out++;
-        return -1;
-    };
-    int slot = out_slot(0);
-
-    // H = 64: fused step kernels (gnode_h64.hip)
-    const bool h64 = (H == 64 && method == 0);
-    float* zi_cur = Z;
-    float* zi_nxt = Z + slab + (h64 ? 64 : 0);           // H = 64: each table is followed by its zero row
-    if (keep) { zi_cur = gn_keep_zi(keep, rows, 0); zi_nxt = gn_keep_zi(keep, rows, 1); }   // step k gathers table k, fills k+1
-    // inference (no trajectory requested): R only feeds the read-out -> carry its 4-float projection
-    float* PR = (h64 && !sol) ? prbuf : nullptr;
-    bool pre_zeroed_ctl = false;
-    if (h64 && n_steps > 0) {
-        // encoder, beta/gamma, trajectory point 0, read-out at grid point 0, projected R and Z_I(y_0): one launch
-        // (the persistent launch's control block is zeroed by the prologue's first workgroup: one launch less in front of it)
-        pre_zeroed_ctl = gn_forward_kind(g, rows, H, method, n_steps, out_rows_host ? n_out : G, sol != nullptr, flags, nullptr) == 2;
-        if (int e = gn_launch_prologue64(x, p, Y, beta, gamma, sol, zi_cur, zi_nxt, PR, slot >= 0 ? S + (size_t)slot * rows : nullptr,
-                                         slot >= 0 ? I + (size_t)slot * rows : nullptr,
-                                         slot >= 0 ? R + (size_t)slot * rows : nullptr, rows,
-                                         pre_zeroed_ctl ? forward_ctl_ptr(workspace, rows, H, method) : nullptr, gn_pers64_ctl_bytes(), st))
-            return e;
-    } else if (method == 0 && H < 128 && n_steps > 0) {
-        // generic-H fused path: encoder, read-out at grid point 0 and Z_I(y_0) in one launch (+ the persistent launch's control block)
-        pre_zeroed_ctl = gn_forward_kind(g, rows, H, method, n_steps, out_rows_host ? n_out : G, sol != nullptr, flags, nullptr) == 3;
-        DISPATCH_LPR(lpr, hipLaunchKernelGGL(k_prologue_generic<LPR>, dim3((unsigned)((rows + rpw - 1) / rpw)), dim3(256),
-                                             (size_t)H * H * sizeof(float), st, x, p->linearS1_weight, p->linearS1_bias,
-                                             p->odefunc_linear_weight, p->odefunc_linear_bias, p->linear3_weight, p->linear3_bias,
-                                             p->linearS2_weight, p->linearS2_bias, Y, beta, gamma, sol, zi_cur,
-                                             slot >= 0 ? S + (size_t)slot * rows : nullptr, slot >= 0 ? I + (size_t)slot * rows : nullptr,
-                                             slot >= 0 ? R + (size_t)slot * rows : nullptr, (long)rows, H,
-                                             pre_zeroed_ctl ? (uint32_t*)forward_ctl_ptr(workspace, rows, H, method) : nullptr,
-                                             (int)(gn_pers64_ctl_bytes() / 4)));
-        GN_LAUNCH_CHECK();
-    } else {
-        DISPATCH_LPR(lpr, hipLaunchKernelGGL(k_encode<LPR>, dim3((unsigned)((rows + rpw - 1) / rpw)), dim3(256), 0, st, x,
-                                             p->linearS1_weight, p->linearS1_bias, Y, beta, gamma, sol, (long)rows, H));
-        GN_LAUNCH_CHECK();
-        if (slot >= 0)
-            if (int e = launch_readout(Y, rows, H, p, S + (size_t)slot * rows, I + (size_t)slot * rows, R + (size_t)slot * rows, st))
-                return e;
-        if (method == 0 && H < 128 && n_steps > 0)
-            if (int e = launch_mlp(g, Y + slab, p->odefunc_linear_weight, p->odefunc_linear_bias, zi_cur, rows, H, st)) return e;
+    const std::vector<int> slot = gn_out_slots(out_rows_host, n_out, G);
+    FwdCall c{g, p, dt_host, n_steps, H, (long)rows, (size_t)rows * H, S, I, R, sol, keep, slot.data(),
+              (float*)(ws + L.Y), (float*)(ws + L.Z), (float*)(ws + L.beta), (float*)(ws + L.gamma), (float*)(ws + L.rk),
+              ws + L.ctl, ws + L.fixed, (pl.h64 && !sol) ? (float*)(ws + L.pr) : nullptr, nullptr, nullptr, (hipStream_t)stream};
+    c.zi_cur = c.Z;
+    c.zi_nxt = c.Z + c.slab + (pl.h64 ? 64 : 0);           // H = 64: each table is followed by its zero row
+    if (keep) { c.zi_cur = gn_keep_zi(keep, rows, 0); c.zi_nxt = gn_keep_zi(keep, rows, 1); }   // step k gathers table k, fills k+1
+    if (int e = forward_prologue(c, pl, x, method)) return e;
+    switch (pl.path) {
+        case FwdPath::pers64: return forward_pers64(c, pl);
+        case FwdPath::persg: return forward_persg(c, pl);
+        case FwdPath::tiny: return forward_tiny(c);
+        default: return method == 0 ? forward_euler_steps(c, pl) : forward_rk4(c);
     }
-    PersPlan plan;
-    const int fkind = gn_forward_kind(g, rows, H, method, n_steps, out_rows_host ? n_out : G, sol != nullptr, flags, &plan);
-    if (fkind == 2) {
-        // mid-size graphs: ONE persistent launch, every workgroup keeps its rows in registers for all steps (gnode_pers64.hip)
-        int slots[128];
-        for (int k = 0; k < n_steps; ++k) slots[k] = out_slot(k + 1);
-        const bool sampled = prof_begin(0, st);
-        if (int e = gn_launch_pers64(g, plan, rows, Y, PR, zi_cur, zi_nxt, p->odefunc_linear_weight, p->odefunc_linear_bias, beta,
-                                     gamma, dt_host, slots, n_steps, p, S, I, R, sol, keep, forward_ctl_ptr(workspace, rows, H, method), pre_zeroed_ctl, st))
-            return e;
-        if (sampled) prof_mark(0, st);
-        return 0;
-    }
-
-    if (fkind == 3) {
-        // small hidden sizes, batches that fit one resident grid: ONE persistent launch (gnode_persg.hip)
-        PersgPlan gp;
-        gn_persg_plan(g, rows, H, n_steps, &gp);
-        int slots[128];
-        for (int k = 0; k < n_steps; ++k) slots[k] = out_slot(k + 1);
-        const bool sampled = prof_begin(0, st);
-        if (int e = gn_launch_persg(g, gp, rows, H, Y, zi_cur, zi_nxt, beta, gamma, dt_host, slots, n_steps, p, S, I, R, sol,
-                                    forward_ctl_ptr(workspace, rows, H, method), pre_zeroed_ctl, st))
-            return e;
-        if (sampled) prof_mark(0, st);
-        if (sol) {
-            const size_t slab4 = slab / 4;
-            hipLaunchKernelGGL(k_fill_bg, dim3((unsigned)std::min<size_t>((slab4 + 255) / 256, 2048)), dim3(256), 0, st, sol, slab4, G);
-            GN_LAUNCH_CHECK();
-        }
-        return 0;
-    }
-
-    if (fkind == 1) {
-        // tiny graphs: the whole integration in one launch (one workgroup per sample, state in LDS)
-        int slots[128];
-        for (int k = 0; k < n_steps; ++k) slots[k] = out_slot(k + 1);
-        if (int e = gn_launch_tiny64(g, rows, Y, zi_cur, PR, p->odefunc_linear_weight, p->odefunc_linear_bias, beta, gamma,
-                                     dt_host, slots, n_steps, p, S, I, R, sol, keep, st))
-            return e;
-        if (sol) {
-            const size_t slab4 = slab / 4;
-            hipLaunchKernelGGL(k_fill_bg, dim3((unsigned)std::min<size_t>((slab4 + 255) / 256, 2048)), dim3(256), 0, st, sol, slab4, G);
-            GN_LAUNCH_CHECK();
-        }
-        return 0;
-    }
-    for (int k = 0; k < n_steps; ++k) {
-        const float dt = dt_host[k];
-        slot = out_slot(k + 1);
-        float* sol_next = sol ? sol + (size_t)(k + 1) * 4 * slab : nullptr;
-        // with a trajectory the fused kernels read point k and write point k+1 (no separate state copy)
-        float* Ycur = (sol && (h64 || (method == 0 && H <= 128))) ? sol + (size_t)k * 4 * slab : Y;
-        if (h64) {
-            // training: the 4th slab of sol[k] (k >= 1; its odeint content is the constant beta-gamma slab of sol[0])
-            // receives A Z_I(y_k), which the adjoint backward would otherwise gather again
-            Step64Out out = {slot >= 0 ? S + (size_t)slot * rows : nullptr, slot >= 0 ? I + (size_t)slot * rows : nullptr,
-                             slot >= 0 ? R + (size_t)slot * rows : nullptr, sol_next,
-                             keep ? (k >= 1 ? gn_keep_ps(keep, rows, k) : nullptr)          // with `keep`: P_S(y_k) there instead
-                                  : ((sol && k >= 1) ? sol + (size_t)k * 4 * slab + 3 * slab : nullptr),
-                             keep ? gn_keep_zs(keep, rows, k) : nullptr};
-            const bool sampled = prof_begin(0, st);
-            if (int e = gn_launch_step64(g, rows, Ycur, zi_cur, zi_nxt, p->odefunc_linear_weight, p->odefunc_linear_bias, beta,
-                                         gamma, dt, p, PR, out, hub_scratch, st))
-                return e;
-            if (sampled) prof_mark(0, st);
-            if (keep) { zi_cur = zi_nxt; zi_nxt = gn_keep_zi(keep, rows, std::min(k + 2, n_steps)); }
-            else std::swap(zi_cur, zi_nxt);
-        } else if (method == 0 && H < 128) {
-            // generic H: one fused launch per step (gather + both node MLPs as lane-group mat-vecs); H = 128 takes the
-            // two-launch branch below, whose node MLP runs on the matrix cores (a VALU mat-vec is 12x off the bound there)
-            StepOut out = {slot >= 0 ? S + (size_t)slot * rows : nullptr, slot >= 0 ? I + (size_t)slot * rows : nullptr,
-                           slot >= 0 ? R + (size_t)slot * rows : nullptr, sol_next};
-            const float* HubP = nullptr;          // segment partials of the hub rows; the step kernel adds them up itself
-            if (int e = gn_hub_segments(g, rows / g->n, H, zi_cur, hub_scratch, &HubP, st)) return e;
-            dim3 grid((unsigned)((g->n + rpw - 1) / rpw), (unsigned)(rows / g->n));
-            const size_t lds = (size_t)H * H * sizeof(float);
-            const bool sampled = prof_begin(0, st);
-            // (H < 128 here: W^T is at most 61 KB of dynamic LDS, below the 64 KB that would need an attribute)
-            const bool hubs = g->n_hub > 0;
-            DISPATCH_LPR(lpr, hipLaunchKernelGGL((hubs ? k_step_generic<LPR, true> : k_step_generic<LPR, false>), grid, dim3(256), lds, st, g->rowptr, g->col, g->n, (long)rows, H,
-                                                 Ycur, zi_cur, zi_nxt, p->odefunc_linear_weight, p->odefunc_linear_bias, beta, gamma,
-                                                 dt, p->linear3_weight, p->linear3_bias, p->linearS2_weight, p->linearS2_bias, out,
-                                                 g->hubidx, HubP, g->hub_seg_ptr, g->n_seg));
-            if (sampled) prof_mark(0, st);
-            GN_LAUNCH_CHECK();
-            std::swap(zi_cur, zi_nxt);
-        } else if (method == 0) {
-            if (int e = launch_mlp(g, Y, p->odefunc_linear_weight, p->odefunc_linear_bias, Z, 2 * rows, H, st)) return e;
-            StepOut out = {slot >= 0 ? S + (size_t)slot * rows : nullptr, slot >= 0 ? I + (size_t)slot * rows : nullptr,
-                           slot >= 0 ? R + (size_t)slot * rows : nullptr, sol_next};
-            if (int e = launch_gather(g, 1, rows, H, Y, Z, beta, gamma, 1, dt, nullptr, p, out, hub_scratch, st)) return e;
-        } else {
-            // torchdiffeq 'rk4' = 3/8 rule
-            float* k1 = rk; float* k2 = rk + 3 * slab; float* k3 = rk + 6 * slab; float* k4 = rk + 9 * slab;
-            float* yt = rk + 12 * slab;
-            const size_t n4 = 3 * slab / 4;
-            const int eg = (int)std::min<size_t>((n4 + 255) / 256, 2048);
-            StepOut none = {nullptr, nullptr, nullptr, nullptr};
-            auto f = [&](float* y, float* kout) -> int {
-                if (int e = launch_mlp(g, y, p->odefunc_linear_weight, p->odefunc_linear_bias, Z, 2 * rows, H, st)) return e;
-                return launch_gather(g, 0, rows, H, y, Z, beta, gamma, 1, 0.f, kout, nullptr, none, hub_scratch, st);
-            };
-            const float third = 1.0f / 3.0f;
-            if (int e = f(Y, k1)) return e;
-            hipLaunchKernelGGL(k_lincomb, dim3(eg), dim3(256), 0, st, yt, Y, dt, k1, third, nullptr, 0.f, nullptr, 0.f, nullptr, 0.f, n4);
-            if (int e = f(yt, k2)) return e;
-            hipLaunchKernelGGL(k_lincomb, dim3(eg), dim3(256), 0, st, yt, Y, dt, k1, -third, k2, 1.f, nullptr, 0.f, nullptr, 0.f, n4);
-            if (int e = f(yt, k3)) return e;
-            hipLaunchKernelGGL(k_lincomb, dim3(eg), dim3(256), 0, st, yt, Y, dt, k1, 1.f, k2, -1.f, k3, 1.f, nullptr, 0.f, n4);
-            if (int e = f(yt, k4)) return e;
-            hipLaunchKernelGGL(k_lincomb, dim3(eg), dim3(256), 0, st, Y, Y, dt, k1, 0.125f, k2, 0.375f, k3, 0.375f, k4, 0.125f, n4);
-            GN_LAUNCH_CHECK();
-            if (sol_next) GN_HIP(hipMemcpyAsync(sol_next, Y, 3 * slab * sizeof(float), hipMemcpyDeviceToDevice, st));
-            if (slot >= 0)
-                if (int e = launch_readout(Y, rows, H, p, S + (size_t)slot * rows, I + (size_t)slot * rows,
-                                           R + (size_t)slot * rows, st))
-                    return e;
-        }
-    }
-    if (sol && n_steps > 0 && !h64) {        // (H = 64: those slabs hold A Z_I(y_k) instead, see above)
-        const size_t slab4 = slab / 4;
-        hipLaunchKernelGGL(k_fill_bg, dim3((unsigned)std::min<size_t>((slab4 + 255) / 256, 2048)), dim3(256), 0, st, sol, slab4, G);
-        GN_LAUNCH_CHECK();
-    }
-    return 0;
 }
 
 extern "C" int gnode_forward_path(gnode_graph_t g, int64_t rows, int32_t H, int32_t method, int32_t n_steps, int32_t n_out,
                                   int32_t with_sol, int32_t flags, int32_t* plan_host) {
     if (!g || rows <= 0 || rows % g->n) return -1;
-    PersPlan pl;
-    const int kind = gn_forward_kind(g, rows, H, method, n_steps, n_out, with_sol != 0, flags, &pl);
-    if (kind == 2 && plan_host) { plan_host[0] = pl.nt; plan_host[1] = pl.wgs; plan_host[2] = pl.span; plan_host[3] = pl.gpx; plan_host[4] = pl.concurrent; }
-    return kind;
+    const FwdPlan pl = gn_forward_plan(g, rows, H, method, n_steps, n_out, with_sol != 0, flags);
+    if (pl.path == FwdPath::pers64 && plan_host) {
+        const PersPlan& q = pl.pers;
+        plan_host[0] = q.nt; plan_host[1] = q.wgs; plan_host[2] = q.span; plan_host[3] = q.gpx; plan_host[4] = q.concurrent;
+    }
+    return (int)pl.path;
 }
 
 // diagnostic build (GN_PERS_PROF): per-phase 100 MHz ticks of the last persistent launch on this workspace
 extern "C" int gnode_forward_phase_ticks(int64_t rows, int32_t H, int32_t method, const void* workspace, uint64_t* ticks8_host) {
-    const PersCtl* ctl = (const PersCtl*)forward_ctl_ptr(const_cast<void*>(workspace), rows, H, method);
+    const PersCtl* ctl = (const PersCtl*)((const char*)workspace + forward_layout(rows, H, method).ctl);
     GN_HIP(hipMemcpy(ticks8_host, ctl->prof, 8 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int gn_read_give_up(const void* ctl_ptr, int H, void* stream, int32_t* code_host, const char* who) {
+    *code_host = 0;
+    if (H != 64 && H > 32) return 0;             // (no persistent launch at other hidden sizes)
+    unsigned err[2] = {0, 0};
+    const PersCtl* ctl = (const PersCtl*)ctl_ptr;
+    GN_HIP(hipMemcpyAsync(err, ctl->error, sizeof(err), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    GN_HIP(hipStreamSynchronize((hipStream_t)stream));
+    *code_host = (int32_t)err[0];
+    if (err[0]) gnode_set_error("%s: a workgroup gave up waiting for epoch %u of its group", who, err[1]);
     return 0;
 }
 
 extern "C" int gnode_forward_status(int64_t rows, int32_t H, int32_t method, const void* workspace, void* stream, int32_t* code_host) {
     GN_CHECK_ARG(workspace && code_host && rows > 0, "gnode_forward_status: null pointer");
-    *code_host = 0;
-    if (H != 64 && H > 32) return 0;
-    unsigned err[2] = {0, 0};
-    const PersCtl* ctl = (const PersCtl*)forward_ctl_ptr(const_cast<void*>(workspace), rows, H, method);
-    GN_HIP(hipMemcpyAsync(err, ctl->error, sizeof(err), hipMemcpyDeviceToHost, (hipStream_t)stream));
-    GN_HIP(hipStreamSynchronize((hipStream_t)stream));
-    *code_host = (int32_t)err[0];
-    if (err[0]) gnode_set_error("persistent forward: a workgroup gave up waiting for epoch %u of its group", err[1]);
-    return 0;
+    return gn_read_give_up((const char*)workspace + forward_layout(rows, H, method).ctl, H, stream, code_host, "persistent forward");
 }
 
 extern "C" size_t gnode_forward_keep_bytes(gnode_graph_t g, int64_t rows, int32_t H, int32_t n_steps, int32_t n_out) {
@@ -990,7 +982,7 @@ extern "C" size_t gnode_forward_keep_bytes(gnode_graph_t g, int64_t rows, int32_
 }
 
 bool gn_sol_carries_ai(const gnode_graph_s* g, long rows, int H, int n_steps, int n_out, int flags) {
-    return H == 64 && n_steps >= 1 && gn_forward_kind(g, rows, H, 0, n_steps, n_out, true, flags, nullptr) != 1;
+    return H == 64 && n_steps >= 1 && gn_forward_plan(g, rows, H, 0, n_steps, n_out, true, flags).path != FwdPath::tiny;
 }
 
 extern "C" int gnode_sol_carries_neighbour_sums(gnode_graph_t g, int64_t rows, int32_t H, int32_t n_steps, int32_t n_out, int32_t flags) {

@@ -280,12 +280,12 @@ __global__ __launch_bounds__(256) void k_rk4_stage(int mode, size_t n4, float dt
 // --------------------------------------------------------------------------- host
 // workgroups of pass 2 (= partial slots it writes): a fixed function of (rows, H)
 static int vjp_grid(long rows, int H) {
-    const int rpw = 256 / lpr_of(H);
+    const int rpw = 256 / gn_lpr(H);
     return (int)std::min<long>(BWD_NWG, std::max<long>(1, (rows + rpw - 1) / rpw));
 }
 
 static size_t vjp_lds_bytes(int H, bool gy) {
-    const int rpw = 256 / lpr_of(H);
+    const int rpw = 256 / gn_lpr(H);
     return ((gy ? (size_t)H * H : 0) + (size_t)4 * rpw * H) * sizeof(float);
 }
 
@@ -325,10 +325,10 @@ static int vjp_launch(const gnode_graph_s* g, long rows, int H, const float* y, 
     A.hubidx = g->hubidx; A.AIhub = AIhub; A.GQhub = GQhub; A.n_hub = g->n_hub;
     A.fSI = o.fSI; A.fR = o.fR; A.f4 = o.f4; A.gySI = o.gySI; A.gyR = o.gyR; A.gybg = o.gybg;
     A.part = o.part; A.part_stride = o.part_stride; A.w = o.w;
-    const int lpr = lpr_of(H);
+    const int lpr = gn_lpr(H);
     const size_t lds = vjp_lds_bytes(H, o.gySI != nullptr);
-    if (256 % H == 0) BWD_DISPATCH(lpr, hipLaunchKernelGGL((k_rhs_vjp<LPR, true>), dim3(vjp_grid(rows, H)), dim3(256), lds, st, A))
-    else BWD_DISPATCH(lpr, hipLaunchKernelGGL((k_rhs_vjp<LPR, false>), dim3(vjp_grid(rows, H)), dim3(256), lds, st, A))
+    if (256 % H == 0) GN_LPR_DISPATCH(32, lpr, hipLaunchKernelGGL((k_rhs_vjp<LPR, true>), dim3(vjp_grid(rows, H)), dim3(256), lds, st, A))
+    else GN_LPR_DISPATCH(32, lpr, hipLaunchKernelGGL((k_rhs_vjp<LPR, false>), dim3(vjp_grid(rows, H)), dim3(256), lds, st, A))
     GN_LAUNCH_CHECK();
     return 0;
 }
@@ -421,10 +421,8 @@ extern "C" int gnode_backward_rk4_f32(gnode_graph_t g, const float* x, const gno
         return GNODE_ERR_WORKSPACE;
     }
     const int G = n_steps + 1;
-    if (out_rows_host)
-        for (int i = 0; i < n_out; ++i)
-            GN_CHECK_ARG(out_rows_host[i] >= 0 && out_rows_host[i] < G && (i == 0 || out_rows_host[i] > out_rows_host[i - 1]),
-                         "gnode_backward_rk4_f32: out_rows must be ascending grid indices in [0,%d)", G);
+    if (int e = gn_check_out_rows("gnode_backward_rk4_f32", out_rows_host, n_out, G)) return e;
+    const std::vector<int> slot = gn_out_slots(out_rows_host, n_out, G);
     hipStream_t st = (hipStream_t)stream;
     const PartLayout L{H};
     const size_t slab = (size_t)rows * H, s2 = slabs_bytes(rows, H, 2);
@@ -448,13 +446,8 @@ extern "C" int gnode_backward_rk4_f32(gnode_graph_t g, const float* x, const gno
         if (int e = gn_zero_regions_async(zr, st)) return e;
     }
     int slots_used = 1;
-    auto slot_of = [&](int gi) -> int {
-        if (!out_rows_host) return gi;
-        for (int i = 0; i < n_out; ++i) if (out_rows_host[i] == gi) return i;
-        return -1;
-    };
     auto head = [&](int gi) -> int {
-        const int s = slot_of(gi);
+        const int s = slot[gi];
         if (s < 0) return 0;
         return gn_launch_head_bwd(rows, H, sol + (size_t)gi * 4 * slab, gS + (size_t)s * rows, gI + (size_t)s * rows,
                                   gR + (size_t)s * rows, p, a, part, &slots_used, st);

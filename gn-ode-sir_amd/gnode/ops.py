@@ -26,6 +26,11 @@ PERSIST_DEFAULT = os.environ.get("GNODE_PERSIST", "1") != "0"
 FWD_PER_STEP = 1
 
 
+def _fwd_flags(persist: bool | None) -> int:
+    """The `flags` argument of the forward / backward entries: GNODE_FWD_PER_STEP unless the persistent launch is allowed."""
+    return 0 if (PERSIST_DEFAULT if persist is None else persist) else FWD_PER_STEP
+
+
 def time_grid(maxTime, deltaT) -> np.ndarray:
     """float64 np.arange(0, maxTime, deltaT): reference ode_nn_ngraph_sim.py:110."""
     return np.arange(0, maxTime, deltaT)
@@ -144,7 +149,7 @@ def forward(graph: DeviceGraph, x2d: torch.Tensor, params: dict, dts: np.ndarray
         _lib.ptr(out[0]), _lib.ptr(out[1]), _lib.ptr(out[2]), _lib.ptr(sol) if sol is not None else None,
         _lib.ptr(keep) if keep is not None else None, keep.numel() * 4 if keep is not None else 0,
         rows, H, _lib.ptr(ws), ws.numel(), _lib.stream_ptr(),
-        0 if (PERSIST_DEFAULT if persist is None else persist) else FWD_PER_STEP, C.byref(info)))
+        _fwd_flags(persist), C.byref(info)))
     if sol is not None:
         sol.gnode_keep = keep
         sol.gnode_info = int(info.value)         # what the call left in sol / keep: the backward checks the pairing
@@ -159,7 +164,7 @@ def forward_path(graph: DeviceGraph, rows: int, H: int, n_steps: int, n_out: int
     plan = (tiles per workgroup, workgroups per sample, XCDs per sample, samples per XCD, samples alive at once)."""
     plan = (C.c_int32 * 8)()
     path = _lib.load().gnode_forward_path(graph.handle, rows, H, METHODS[method], n_steps, n_steps + 1 if n_out is None else n_out,
-                                          int(want_sol), 0 if (PERSIST_DEFAULT if persist is None else persist) else FWD_PER_STEP, plan)
+                                          int(want_sol), _fwd_flags(persist), plan)
     return int(path), tuple(int(v) for v in plan[:5])
 
 
@@ -211,7 +216,7 @@ def backward(graph: DeviceGraph, x2d: torch.Tensor, params: dict, dts: np.ndarra
         _lib.host_ptr(out_rows) if out_rows is not None else None, n_out, _lib.ptr(_f32c(sol)),
         _lib.ptr(keep) if keep is not None else None, keep.numel() * 4 if keep is not None else 0,
         _lib.ptr(_f32c(gS)), _lib.ptr(_f32c(gI)), _lib.ptr(_f32c(gR)), C.byref(gp), rows, H,
-        _lib.ptr(ws), ws.numel(), _lib.stream_ptr(), 0 if (PERSIST_DEFAULT if persist is None else persist) else FWD_PER_STEP,
+        _lib.ptr(ws), ws.numel(), _lib.stream_ptr(), _fwd_flags(persist),
         int(getattr(sol, "gnode_info", -1))))
     backward.last_workspace = (rows, H, ws)
     return grads
