@@ -27,22 +27,10 @@
 #include "gnode_h64.h"
 #include "gnode_gather.h"
 #include "gnode_mfma64.h"
-#include "gnode_head64.h"
 #include "gnode_pers64.h"
 #include "gnode_persg.h"
 #include <algorithm>
-
-__device__ __forceinline__ float4 ld4b(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4b(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
-__device__ __forceinline__ float4 z4() { return make_float4(0.f, 0.f, 0.f, 0.f); }
-__device__ __forceinline__ float dot4(float4 a, float4 b) { return fmaf(a.x, b.x, fmaf(a.y, b.y, fmaf(a.z, b.z, a.w * b.w))); }
-
-template <int LPR>
-__device__ __forceinline__ float gsum(float v) {
-#pragma unroll
-    for (int m = LPR / 2; m >= 1; m >>= 1) v += __shfl_xor(v, m, LPR);
-    return v;
-}
+#include <type_traits>
 
 // Deterministic in-workgroup reduction of per-group contributions staged in LDS:
 // red[group][NE] -> part[e] += sum_groups (fixed order).
@@ -72,21 +60,22 @@ __global__ __launch_bounds__(256) void k_head_bwd(const float* __restrict__ Ysol
     const size_t slab = (size_t)rows * H;
     float4 w3v[4];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) w3v[k] = active ? ld4b(w3 + (size_t)k * H + 4 * sub) : z4();
-    float4 dw3[4] = {z4(), z4(), z4(), z4()};
+    for (int k = 0; k < 4; ++k) w3v[k] = active ? ld4(w3 + (size_t)k * H + 4 * sub) : zero4();
+    float4 dw3[4] = {zero4(), zero4(), zero4(), zero4()};
     float db3[4] = {0.f, 0.f, 0.f, 0.f}, dw2[4] = {0.f, 0.f, 0.f, 0.f}, db2 = 0.f;
     for (long r = (long)blockIdx.x * G + grp; r < rows; r += (long)gridDim.x * G) {
         const size_t off = (size_t)r * H + 4 * sub;
         float4 y[3];
 #pragma unroll
-        for (int X = 0; X < 3; ++X) y[X] = active ? ld4b(Ysol + X * slab + off) : z4();
+        for (int X = 0; X < 3; ++X) y[X] = active ? ld4(Ysol + X * slab + off) : zero4();
+        // gn_head_vjp inline (XorSum<LPR>): the call reschedules this kernel
         float p3[3][4], q[3];
 #pragma unroll
         for (int X = 0; X < 3; ++X) {
             q[X] = b2[0];
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-                p3[X][k] = gsum<LPR>(dot4(w3v[k], y[X])) + b3[k];
+                p3[X][k] = group_sum<LPR>(dot4(w3v[k], y[X])) + b3[k];
                 q[X] = fmaf(w2[k], fmaxf(p3[X][k], 0.f), q[X]);
             }
         }
@@ -99,7 +88,7 @@ __global__ __launch_bounds__(256) void k_head_bwd(const float* __restrict__ Ysol
 #pragma unroll
         for (int X = 0; X < 3; ++X) {
             const float dq = p[X] * (g[X] - gp);
-            float4 dy = z4();
+            float4 dy = zero4();
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const float dp3 = p3[X][k] > 0.f ? dq * w2[k] : 0.f;
@@ -112,16 +101,16 @@ __global__ __launch_bounds__(256) void k_head_bwd(const float* __restrict__ Ysol
             }
             db2 += dq;
             if (active) {
-                float4 av = ld4b(a + X * slab + off);
+                float4 av = ld4(a + X * slab + off);
                 av.x += dy.x; av.y += dy.y; av.z += dy.z; av.w += dy.w;
-                st4b(a + X * slab + off, av);
+                st4(a + X * slab + off, av);
             }
         }
     }
     float* mine = red + (size_t)grp * ne;
     if (active)
 #pragma unroll
-        for (int k = 0; k < 4; ++k) st4b(mine + k * H + 4 * sub, dw3[k]);
+        for (int k = 0; k < 4; ++k) st4(mine + k * H + 4 * sub, dw3[k]);
     if (sub == 0) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) { mine[4 * H + k] = db3[k]; mine[4 * H + 4 + k] = dw2[k]; }
@@ -138,9 +127,8 @@ __global__ __launch_bounds__(256) void k_bwd_q(const float* __restrict__ a, cons
     const int h4 = H / 4;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
         const float bt = beta[i / h4];
-        const float4 aS = ld4b(a + 4 * i), aI = ld4b(a + slab + 4 * i), z = ld4b(ZS + 4 * i);
-        st4b(q + 4 * i, make_float4(bt * (aI.x - aS.x) * z.x, bt * (aI.y - aS.y) * z.y, bt * (aI.z - aS.z) * z.z,
-                                    bt * (aI.w - aS.w) * z.w));
+        const float4 aS = ld4(a + 4 * i), aI = ld4(a + slab + 4 * i), z = ld4(ZS + 4 * i);
+        st4(q + 4 * i, gn_q4(bt, aI, aS, z));
     }
 }
 
@@ -159,29 +147,22 @@ __global__ __launch_bounds__(256) void k_bwd_gather(const int* __restrict__ rowp
     const long base = (long)blockIdx.y * n, r = base + node;
     const size_t slab = (size_t)rows * H, off = (size_t)r * H + 4 * sub;
     const float* ZI = Z + slab;
-    float4 ai = z4(), gq = z4();
+    float4 ai = zero4(), gq = zero4();
     const int hub = hubidx ? hubidx[node] : -1;
     if (hub >= 0 && active) {
-        ai = ld4b(AIhub + ((size_t)blockIdx.y * n_hub + hub) * H + 4 * sub);
-        gq = ld4b(GQhub + ((size_t)blockIdx.y * n_hub + hub) * H + 4 * sub);
+        ai = ld4(AIhub + ((size_t)blockIdx.y * n_hub + hub) * H + 4 * sub);
+        gq = ld4(GQhub + ((size_t)blockIdx.y * n_hub + hub) * H + 4 * sub);
     }
     const int start = hub >= 0 ? 0 : rowptr[node], end = hub >= 0 ? 0 : rowptr[node + 1];
     gn_gather2<4>(col, start, end, ZI + (size_t)base * H, q + (size_t)base * H, H, sub, active, ai, gq);
     if (!active) return;
     const float bt = beta[r], gm = gamma[r];
-    const float4 aS = ld4b(a + off), aI = ld4b(a + slab + off), aR = ld4b(a + 2 * slab + off);
-    const float4 zs = ld4b(Z + off), zi = ld4b(ZI + off);
+    const float4 aS = ld4(a + off), aI = ld4(a + slab + off), aR = ld4(a + 2 * slab + off);
+    const float4 zs = ld4(Z + off), zi = ld4(ZI + off);
     float4 dS, dI;
-#define GN_DPRE(c)                                                         \
-    {                                                                      \
-        const float v = bt * (aI.c - aS.c);                                \
-        dS.c = (v * ai.c) * (zs.c * (1.0f - zs.c));                        \
-        dI.c = (gq.c + gm * (aR.c - aI.c)) * (zi.c * (1.0f - zi.c));       \
-    }
-    GN_DPRE(x) GN_DPRE(y) GN_DPRE(z) GN_DPRE(w)
-#undef GN_DPRE
-    st4b(dpre + off, dS);
-    st4b(dpre + slab + off, dI);
+    gn_dpre_row(bt, gm, aS, aI, aR, ai, gq, zs, zi, dS, dI);
+    st4(dpre + off, dS);
+    st4(dpre + slab + off, dI);
 }
 
 // --------------------------------------------------------------------------- a += dt dpre W ; partial gW, gb
@@ -214,25 +195,25 @@ __global__ __launch_bounds__(256) void k_bwd_mlp(const float* __restrict__ dpre,
 #pragma unroll
         for (int X = 0; X < 2; ++X) {
             if (!lane_ok) continue;            // idle lanes of a group (H/4 not a power of two) would write into the next row
-            st4b(Dt + ((size_t)X * G + grp) * H + 4 * sub, ok ? ld4b(dpre + X * slab + off) : z4());
-            st4b(Yt + ((size_t)X * G + grp) * H + 4 * sub, ok ? ld4b(Ysol + X * slab + off) : z4());
+            st4(Dt + ((size_t)X * G + grp) * H + 4 * sub, ok ? ld4(dpre + X * slab + off) : zero4());
+            st4(Yt + ((size_t)X * G + grp) * H + 4 * sub, ok ? ld4(Ysol + X * slab + off) : zero4());
         }
         __syncthreads();
         // g_Y = dpre W  (this lane: 4 columns of its own row, both slabs)
-        float4 gS = z4(), gI = z4();
+        float4 gS = zero4(), gI = zero4();
         const float* dS = Dt + (size_t)grp * H;
         const float* dI = Dt + ((size_t)G + grp) * H;
         for (int j = 0; j < H; ++j) {
-            const float4 w = lane_ok ? ld4b(Wl + (size_t)j * H + 4 * sub) : z4();
+            const float4 w = lane_ok ? ld4(Wl + (size_t)j * H + 4 * sub) : zero4();
             const float s = dS[j], i = dI[j];
             gS.x = fmaf(s, w.x, gS.x); gS.y = fmaf(s, w.y, gS.y); gS.z = fmaf(s, w.z, gS.z); gS.w = fmaf(s, w.w, gS.w);
             gI.x = fmaf(i, w.x, gI.x); gI.y = fmaf(i, w.y, gI.y); gI.z = fmaf(i, w.z, gI.z); gI.w = fmaf(i, w.w, gI.w);
         }
         if (ok) {
-            float4 aS = ld4b(a + off), aI = ld4b(a + slab + off);
+            float4 aS = ld4(a + off), aI = ld4(a + slab + off);
             aS.x += dt * gS.x; aS.y += dt * gS.y; aS.z += dt * gS.z; aS.w += dt * gS.w;
             aI.x += dt * gI.x; aI.y += dt * gI.y; aI.z += dt * gI.z; aI.w += dt * gI.w;
-            st4b(a + off, aS); st4b(a + slab + off, aI);
+            st4(a + off, aS); st4(a + slab + off, aI);
         }
         // gW[j][k] += sum_rows dpre[r][j] * y[r][k]   (thread owns entries e = tid + 256 m)
 #pragma unroll
@@ -290,7 +271,7 @@ __global__ __launch_bounds__(256) void k_mlp64_q(const float* __restrict__ X, co
 #pragma unroll
         for (int p = 0; p < 2; ++p) {
             r[p] = t * TILE_ROWS + lr[p];
-            *reinterpret_cast<float4*>(T + lr[p] * TS + 4 * sub) = r[p] < nrows ? ld4g(X + (size_t)r[p] * 64 + 4 * sub) : zero4();
+            *reinterpret_cast<float4*>(T + lr[p] * TS + 4 * sub) = r[p] < nrows ? ld4(X + (size_t)r[p] * 64 + 4 * sub) : zero4();
         }
         __syncthreads();
         mfma_tile<true>(T, Wl, T2, bias_l, w, lane);
@@ -300,12 +281,11 @@ __global__ __launch_bounds__(256) void k_mlp64_q(const float* __restrict__ X, co
             if (r[p] >= nrows) continue;
             const float4 z = *reinterpret_cast<const float4*>(T2 + lr[p] * TS + 4 * sub);
             const size_t off = (size_t)r[p] * 64 + 4 * sub;
-            st4g(Z + off, z);
+            st4(Z + off, z);
             if (r[p] < rows) {                                   // S slab: q rides along
                 const float bt = beta[r[p]];
-                const float4 aS = ld4g(a + off), aI = ld4g(a + slab + off);
-                st4g(q + off, make_float4(bt * (aI.x - aS.x) * z.x, bt * (aI.y - aS.y) * z.y, bt * (aI.z - aS.z) * z.z,
-                                          bt * (aI.w - aS.w) * z.w));
+                const float4 aS = ld4(a + off), aI = ld4(a + slab + off);
+                st4(q + off, gn_q4(bt, aI, aS, z));
             }
         }
         __syncthreads();
@@ -453,22 +433,22 @@ __global__ __launch_bounds__(256, OCC) void k_bwd_fused64(const int* __restrict_
             if (valid[p]) {
                 bt[p] = beta[base + node];
                 gmv[p] = gamma[base + node];
-                aS[p] = ld4g(a + off[p]); aI[p] = ld4g(a + slab + off[p]); aR[p] = ld4g(a + 2 * slab + off[p]);
-                ysr = ld4g(Ysol + off[p]); yir = ld4g(Ysol + slab + off[p]);
+                aS[p] = ld4(a + off[p]); aI[p] = ld4(a + slab + off[p]); aR[p] = ld4(a + 2 * slab + off[p]);
+                ysr = ld4(Ysol + off[p]); yir = ld4(Ysol + slab + off[p]);
             }
             *reinterpret_cast<float4*>(&Yt[0][lr[p] * TS + 4 * sub]) = ysr;
             *reinterpret_cast<float4*>(&Yt[1][lr[p] * TS + 4 * sub]) = yir;
             const int hub = (hubidx && valid[p]) ? hubidx[node] : -1;
             if (GATHER_AI) {
                 if (hub >= 0) {
-                    ai[p] = ld4g(AIhub + ((size_t)b * n_hub + hub) * 64 + 4 * sub);
-                    gq[p] = ld4g(GQhub + ((size_t)b * n_hub + hub) * 64 + 4 * sub);
+                    ai[p] = ld4(AIhub + ((size_t)b * n_hub + hub) * 64 + 4 * sub);
+                    gq[p] = ld4(GQhub + ((size_t)b * n_hub + hub) * 64 + 4 * sub);
                 } else {
                     gather2_row64<GN_BWD_NB>(rowptr, col, ZIc + (size_t)base * 64, Qc + (size_t)base * 64, node, valid[p], sub, ai[p], gq[p]);
                 }
             } else {
-                ai[p] = valid[p] ? ld4g(AIsaved + off[p]) : zero4();
-                if (hub >= 0) gq[p] = ld4g(GQhub + ((size_t)b * n_hub + hub) * 64 + 4 * sub);
+                ai[p] = valid[p] ? ld4(AIsaved + off[p]) : zero4();
+                if (hub >= 0) gq[p] = ld4(GQhub + ((size_t)b * n_hub + hub) * 64 + 4 * sub);
                 else gq[p] = gather1_row64<>(rowptr, col, Qc + (size_t)base * 64, node, valid[p], sub);
             }
         }
@@ -484,14 +464,7 @@ __global__ __launch_bounds__(256, OCC) void k_bwd_fused64(const int* __restrict_
                 const float4 zs = *reinterpret_cast<const float4*>(&Dt[0][lr[p] * TS + 4 * sub]);
                 const float4 zi = *reinterpret_cast<const float4*>(&Dt[1][lr[p] * TS + 4 * sub]);
                 const float gm = gmv[p];
-#define GN_DP(c)                                                               \
-                {                                                              \
-                    const float v = bt[p] * (aI[p].c - aS[p].c);               \
-                    dS.c = (v * ai[p].c) * (zs.c * (1.0f - zs.c));             \
-                    dI.c = (gq[p].c + gm * (aR[p].c - aI[p].c)) * (zi.c * (1.0f - zi.c)); \
-                }
-                GN_DP(x) GN_DP(y) GN_DP(z) GN_DP(w)
-#undef GN_DP
+                gn_dpre_row(bt[p], gm, aS[p], aI[p], aR[p], ai[p], gq[p], zs, zi, dS, dI);
             }
             *reinterpret_cast<float4*>(&Dt[0][lr[p] * TS + 4 * sub]) = dS;      // own row only: read above, rewritten here
             *reinterpret_cast<float4*>(&Dt[1][lr[p] * TS + 4 * sub]) = dI;
@@ -532,10 +505,10 @@ __global__ __launch_bounds__(256, OCC) void k_bwd_fused64(const int* __restrict_
                 const float4 uI = *reinterpret_cast<const float4*>(&Yt[1][lr[p] * TS + 4 * sub]);
                 aS[p].x += dt * uS.x; aS[p].y += dt * uS.y; aS[p].z += dt * uS.z; aS[p].w += dt * uS.w;
                 aI[p].x += dt * uI.x; aI[p].y += dt * uI.y; aI[p].z += dt * uI.z; aI[p].w += dt * uI.w;
-                if (head || do_next) y[0] = ld4g(Yprev + off[p]);
-                if (head || (do_next && ZIn)) y[1] = ld4g(Yprev + slab + off[p]);
+                if (head || do_next) y[0] = ld4(Yprev + off[p]);
+                if (head || (do_next && ZIn)) y[1] = ld4(Yprev + slab + off[p]);
                 if (head) {
-                    y[2] = ld4g(Yprev + 2 * slab + off[p]);
+                    y[2] = ld4(Yprev + 2 * slab + off[p]);
                     const size_t o = (size_t)(base + tile * TR + lr[p]);
                     gout[0] = gS[o]; gout[1] = gI[o]; gout[2] = gR[o];
                 }
@@ -547,11 +520,11 @@ __global__ __launch_bounds__(256, OCC) void k_bwd_fused64(const int* __restrict_
             if (head) {
                 float4 w3v[4];
 #pragma unroll
-                for (int k = 0; k < 4; ++k) w3v[k] = ld4g(w3 + k * 64 + 4 * sub);      // L1-resident
-                head_vjp64(y, gout, w3v, b3, w2, b2, aS[p], aI[p], aR[p], hacc);
-                if (valid[p]) st4g(a + 2 * slab + off[p], aR[p]);
+                for (int k = 0; k < 4; ++k) w3v[k] = ld4(w3 + k * 64 + 4 * sub);      // L1-resident
+                gn_head_vjp<DppSum16>(y, gout, w3v, b3, w2, b2, aS[p], aI[p], aR[p], hacc);
+                if (valid[p]) st4(a + 2 * slab + off[p], aR[p]);
             }
-            if (valid[p]) { st4g(a + off[p], aS[p]); st4g(a + slab + off[p], aI[p]); }
+            if (valid[p]) { st4(a + off[p], aS[p]); st4(a + slab + off[p], aI[p]); }
         }
         if (do_next) {
             // q = beta (a_I - a_S) * Z_S(y_{i-1}): the table the NEXT interval gathers (its own-row Z_S, Z_I are recomputed there)
@@ -566,10 +539,9 @@ __global__ __launch_bounds__(256, OCC) void k_bwd_fused64(const int* __restrict_
 #pragma unroll
             for (int p = 0; p < RPG; ++p) {
                 if (!valid[p]) continue;
-                if (ZIn) st4g(ZIn + off[p], *reinterpret_cast<const float4*>(&Dt[1][lr[p] * TS + 4 * sub]));
+                if (ZIn) st4(ZIn + off[p], *reinterpret_cast<const float4*>(&Dt[1][lr[p] * TS + 4 * sub]));
                 const float4 zs = *reinterpret_cast<const float4*>(&Dt[0][lr[p] * TS + 4 * sub]);
-                st4g(Qn + off[p], make_float4(bt[p] * (aI[p].x - aS[p].x) * zs.x, bt[p] * (aI[p].y - aS[p].y) * zs.y,
-                                              bt[p] * (aI[p].z - aS[p].z) * zs.z, bt[p] * (aI[p].w - aS[p].w) * zs.w));
+                st4(Qn + off[p], gn_q4(bt[p], aI[p], aS[p], zs));
             }
         }
     }
@@ -741,6 +713,7 @@ __global__ __launch_bounds__(256, OCC) void k_bwd_kept64(const int* __restrict__
         }
         {
             float4 dS, dI;
+            // gn_dpre_row_kept inline: the call reschedules this kernel
 #define GN_DP(c)                                                               \
             {                                                                  \
                 const float v = bt * (aI.c - aS.c);                            \
@@ -792,13 +765,14 @@ __global__ __launch_bounds__(256, OCC) void k_bwd_kept64(const int* __restrict__
         if (head) {
             float4 w3v[4];
 #pragma unroll
-            for (int k = 0; k < 4; ++k) w3v[k] = ld4g(w3 + k * 64 + 4 * sub);      // L1-resident
-            head_vjp64(y, gout, w3v, b3, w2, b2, aS, aI, aR, hacc);                 // padding rows: gout = 0 adds nothing
+            for (int k = 0; k < 4; ++k) w3v[k] = ld4(w3 + k * 64 + 4 * sub);      // L1-resident
+            gn_head_vjp<DppSum16>(y, gout, w3v, b3, w2, b2, aS, aI, aR, hacc);                 // padding rows: gout = 0 adds nothing
             if (valid) st4so<NT>(a + 2 * slab, off, aR);
         }
         if (valid) {
             st4so<NT>(a, off, aS); st4so<NT>(a + slab, off, aI);
             if (do_next)
+                // gn_q4 inline: the call reschedules this kernel
                 st4so<NT>(Qn, off, make_float4(bt * (aI.x - aS.x) * zsp.x, bt * (aI.y - aS.y) * zsp.y,
                                           bt * (aI.z - aS.z) * zsp.z, bt * (aI.w - aS.w) * zsp.w));
         }
@@ -846,14 +820,14 @@ __global__ __launch_bounds__(256, OCC) void k_bwd_kept64(const int* __restrict__
 // tiles as in k_bwd_mlp, and the head's VJP at grid point i-1 plus the next interval's Z / q tables are folded in.
 template <int LPR>
 __device__ __forceinline__ float4 group_lin(float4 x, const float* __restrict__ M, int sub, bool active, int H) {
-    float4 acc = z4();
+    float4 acc = zero4();
     const float xv[4] = {x.x, x.y, x.z, x.w};
     for (int kk = 0; 4 * kk < H; ++kk) {
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
             const float xk = __shfl(xv[c], kk, LPR);
             if (active) {
-                const float4 w = ld4b(M + (size_t)(4 * kk + c) * H + 4 * sub);
+                const float4 w = ld4(M + (size_t)(4 * kk + c) * H + 4 * sub);
                 acc.x = fmaf(xk, w.x, acc.x); acc.y = fmaf(xk, w.y, acc.y);
                 acc.z = fmaf(xk, w.z, acc.z); acc.w = fmaf(xk, w.w, acc.w);
             }
@@ -861,7 +835,6 @@ __device__ __forceinline__ float4 group_lin(float4 x, const float* __restrict__ 
     }
     return acc;
 }
-__device__ __forceinline__ float sig_b(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
 
 template <int LPR>
 __global__ __launch_bounds__(256) void k_bwd_fused_generic(
@@ -897,13 +870,13 @@ __global__ __launch_bounds__(256) void k_bwd_fused_generic(
     float accb = 0.f;
     const int M = (nE + 255) / 256;
     const bool head = gS != nullptr;
-    const float4 bias4 = lane_ok ? ld4b(bias + 4 * sub) : z4();
+    const float4 bias4 = lane_ok ? ld4(bias + 4 * sub) : zero4();
     float4 w3v[4];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) w3v[k] = lane_ok ? ld4b(w3 + (size_t)k * H + 4 * sub) : z4();
+    for (int k = 0; k < 4; ++k) w3v[k] = lane_ok ? ld4(w3 + (size_t)k * H + 4 * sub) : zero4();
     HeadAcc hacc;
 #pragma unroll
-    for (int k = 0; k < 4; ++k) { hacc.dw3[k] = z4(); hacc.db3[k] = 0.f; hacc.dw2[k] = 0.f; }
+    for (int k = 0; k < 4; ++k) { hacc.dw3[k] = zero4(); hacc.db3[k] = 0.f; hacc.dw2[k] = 0.f; }
     hacc.db2 = 0.f;
     for (long r0 = (long)blockIdx.x * G; r0 < rows; r0 += (long)gridDim.x * G) {
         const long r = r0 + grp;
@@ -913,15 +886,15 @@ __global__ __launch_bounds__(256) void k_bwd_fused_generic(
         const size_t off = (size_t)r * H + 4 * sub;
         // 1. own-row loads first (they travel under the gathers' dependent round trips), then both gathers (no
         //    cross-lane traffic inside, so the tail rows may skip them)
-        float4 aS = z4(), aI = z4(), aR = z4(), dS = z4(), dI = z4(), yS = z4(), yI = z4(), zs0 = z4(), zi0 = z4();
+        float4 aS = zero4(), aI = zero4(), aR = zero4(), dS = zero4(), dI = zero4(), yS = zero4(), yI = zero4(), zs0 = zero4(), zi0 = zero4();
         float bt = 0.f, gm = 0.f;
         if (ok) {
             bt = beta[r]; gm = gamma[r];
-            aS = ld4b(a + off); aI = ld4b(a + slab + off); aR = ld4b(a + 2 * slab + off);
-            zs0 = ld4b(ZS + off); zi0 = ld4b(ZIc + off);
-            yS = ld4b(Ysol + off); yI = ld4b(Ysol + slab + off);
+            aS = ld4(a + off); aI = ld4(a + slab + off); aR = ld4(a + 2 * slab + off);
+            zs0 = ld4(ZS + off); zi0 = ld4(ZIc + off);
+            yS = ld4(Ysol + off); yI = ld4(Ysol + slab + off);
         }
-        float4 ai = z4(), gq = z4();
+        float4 ai = zero4(), gq = zero4();
         if (inrow) {
             const int hub = hubidx ? hubidx[node] : -1;
             if (hub >= 0) {
@@ -933,8 +906,8 @@ __global__ __launch_bounds__(256) void k_bwd_fused_generic(
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
                         const bool on = lane_ok && sg + q < s1;
-                        u[q] = on ? ld4b(HubP0 + pb + (size_t)(sg + q) * H) : z4();
-                        v[q] = on ? ld4b(HubP1 + pb + (size_t)(sg + q) * H) : z4();
+                        u[q] = on ? ld4(HubP0 + pb + (size_t)(sg + q) * H) : zero4();
+                        v[q] = on ? ld4(HubP1 + pb + (size_t)(sg + q) * H) : zero4();
                     }
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
@@ -947,6 +920,7 @@ __global__ __launch_bounds__(256) void k_bwd_fused_generic(
             }
         }
         if (ok) {
+        // gn_dpre_row inline: the call reschedules this kernel
 #define GN_DPRE(c)                                                         \
             {                                                              \
                 const float v = bt * (aI.c - aS.c);                        \
@@ -958,33 +932,33 @@ __global__ __launch_bounds__(256) void k_bwd_fused_generic(
         }
         __syncthreads();                       // previous tile's gW pass is done with the tiles (also covers the W stage)
         if (lane_ok) {
-            st4b(Dt + (size_t)grp * H + 4 * sub, dS);       st4b(Dt + ((size_t)G + grp) * H + 4 * sub, dI);
-            st4b(Yt + (size_t)grp * H + 4 * sub, yS);       st4b(Yt + ((size_t)G + grp) * H + 4 * sub, yI);
+            st4(Dt + (size_t)grp * H + 4 * sub, dS);       st4(Dt + ((size_t)G + grp) * H + 4 * sub, dI);
+            st4(Yt + (size_t)grp * H + 4 * sub, yS);       st4(Yt + ((size_t)G + grp) * H + 4 * sub, yI);
         }
         // 2. g_Y = dpre W (row broadcast inside the lane group), a += dt g_Y
         const float4 uS = group_lin<LPR>(dS, Wl, sub, lane_ok, H), uI = group_lin<LPR>(dI, Wl, sub, lane_ok, H);
         aS.x += dt * uS.x; aS.y += dt * uS.y; aS.z += dt * uS.z; aS.w += dt * uS.w;
         aI.x += dt * uI.x; aI.y += dt * uI.y; aI.z += dt * uI.z; aI.w += dt * uI.w;
         // 3. dL/dsol[i-1] through the head (rows beyond the end carry y = 0, gout = 0)
-        float4 y[3] = {z4(), z4(), z4()};
+        float4 y[3] = {zero4(), zero4(), zero4()};
         float gout[3] = {0.f, 0.f, 0.f};
-        if (ok && (head || do_next)) { y[0] = ld4b(Yprev + off); y[1] = ld4b(Yprev + slab + off); }
+        if (ok && (head || do_next)) { y[0] = ld4(Yprev + off); y[1] = ld4(Yprev + slab + off); }
         if (head) {
-            if (ok) y[2] = ld4b(Yprev + 2 * slab + off);
+            if (ok) y[2] = ld4(Yprev + 2 * slab + off);
             if (inrow) { gout[0] = gS[r]; gout[1] = gI[r]; gout[2] = gR[r]; }
-            head_vjp64<LPR>(y, gout, w3v, b3, w2, b2, aS, aI, aR, hacc);
-            if (ok) st4b(a + 2 * slab + off, aR);
+            // a 16-lane group is one DPP row: it sums with row_sum16, like the H = 64 kernels; smaller groups shuffle
+            gn_head_vjp<std::conditional_t<LPR == 16, DppSum16, XorSum<LPR>>>(y, gout, w3v, b3, w2, b2, aS, aI, aR, hacc);
+            if (ok) st4(a + 2 * slab + off, aR);
         }
-        if (ok) { st4b(a + off, aS); st4b(a + slab + off, aI); }
+        if (ok) { st4(a + off, aS); st4(a + slab + off, aI); }
         // 4. Z(y_{i-1}) and q for the next interval
         if (do_next) {
             float4 zs = group_lin<LPR>(y[0], Wt, sub, lane_ok, H), zi = group_lin<LPR>(y[1], Wt, sub, lane_ok, H);
-            zs = make_float4(sig_b(zs.x + bias4.x), sig_b(zs.y + bias4.y), sig_b(zs.z + bias4.z), sig_b(zs.w + bias4.w));
-            zi = make_float4(sig_b(zi.x + bias4.x), sig_b(zi.y + bias4.y), sig_b(zi.z + bias4.z), sig_b(zi.w + bias4.w));
+            zs = make_float4(gn_sigmoid(zs.x + bias4.x), gn_sigmoid(zs.y + bias4.y), gn_sigmoid(zs.z + bias4.z), gn_sigmoid(zs.w + bias4.w));
+            zi = make_float4(gn_sigmoid(zi.x + bias4.x), gn_sigmoid(zi.y + bias4.y), gn_sigmoid(zi.z + bias4.z), gn_sigmoid(zi.w + bias4.w));
             if (ok) {
-                st4b(ZS + off, zs); st4b(ZIn + off, zi);
-                st4b(Qn + off, make_float4(bt * (aI.x - aS.x) * zs.x, bt * (aI.y - aS.y) * zs.y, bt * (aI.z - aS.z) * zs.z,
-                                           bt * (aI.w - aS.w) * zs.w));
+                st4(ZS + off, zs); st4(ZIn + off, zi);
+                st4(Qn + off, gn_q4(bt, aI, aS, zs));
             }
         }
         __syncthreads();                       // tiles complete
@@ -1022,7 +996,7 @@ __global__ __launch_bounds__(256) void k_bwd_fused_generic(
         float* mine = lds + (size_t)grp * ne;
         if (lane_ok)
 #pragma unroll
-            for (int k = 0; k < 4; ++k) st4b(mine + k * H + 4 * sub, hacc.dw3[k]);
+            for (int k = 0; k < 4; ++k) st4(mine + k * H + 4 * sub, hacc.dw3[k]);
         if (sub == 0) {
 #pragma unroll
             for (int k = 0; k < 4; ++k) { mine[4 * H + k] = hacc.db3[k]; mine[4 * H + 4 + k] = hacc.dw2[k]; }
@@ -1048,14 +1022,14 @@ __global__ __launch_bounds__(256) void k_enc_bwd(const float* __restrict__ a, co
     const int sub = threadIdx.x % LPR, grp = threadIdx.x / LPR;
     const bool active = 4 * sub < H;
     const size_t slab = (size_t)rows * H;
-    float4 dw = z4(), db = z4();
+    float4 dw = zero4(), db = zero4();
     for (long r = (long)blockIdx.x * G + grp; r < rows; r += (long)gridDim.x * G) {
         if (!active) continue;
         const size_t off = (size_t)r * H + 4 * sub;
 #pragma unroll
         for (int X = 0; X < 3; ++X) {
             const float s = x[(size_t)r * (3 + H) + X];
-            const float4 y = ld4b(sol0 + X * slab + off), av = ld4b(a + X * slab + off);
+            const float4 y = ld4(sol0 + X * slab + off), av = ld4(a + X * slab + off);
             const float4 mk = make_float4(y.x > 0.f ? av.x : 0.f, y.y > 0.f ? av.y : 0.f, y.z > 0.f ? av.z : 0.f,
                                           y.w > 0.f ? av.w : 0.f);
             dw.x = fmaf(mk.x, s, dw.x); dw.y = fmaf(mk.y, s, dw.y); dw.z = fmaf(mk.z, s, dw.z); dw.w = fmaf(mk.w, s, dw.w);
@@ -1063,7 +1037,7 @@ __global__ __launch_bounds__(256) void k_enc_bwd(const float* __restrict__ a, co
         }
     }
     float* mine = red + (size_t)grp * 2 * H;
-    if (active) { st4b(mine + 4 * sub, dw); st4b(mine + H + 4 * sub, db); }
+    if (active) { st4(mine + 4 * sub, dw); st4(mine + H + 4 * sub, db); }
     __syncthreads();
     flush_groups(red, G, 2 * H, part_all + (size_t)blockIdx.x * L.total() + L.ow1());
 }

@@ -16,7 +16,6 @@
 // the association of the dt factor differs (dt is folded into dpre once instead of into gW / g_Y afterwards).
 #include "gnode_bwd.h"
 #include "gnode_mfma64.h"
-#include "gnode_head64.h"
 #include <cstdlib>
 
 struct TinyBwdSched {
@@ -98,7 +97,7 @@ __global__ __launch_bounds__(512) void k_tiny_bwd64(const int* __restrict__ rowp
     }
     float4 w3v[4];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) w3v[k] = ld4g(w3 + k * 64 + 4 * sub);
+    for (int k = 0; k < 4; ++k) w3v[k] = ld4(w3 + k * 64 + 4 * sub);
 
     float4 aS[2] = {zero4(), zero4()}, aI[2] = {zero4(), zero4()}, aR[2] = {zero4(), zero4()};
     HeadAcc hacc;
@@ -126,10 +125,10 @@ __global__ __launch_bounds__(512) void k_tiny_bwd64(const int* __restrict__ rowp
             r.gout[p][0] = r.gout[p][1] = r.gout[p][2] = 0.f;
             r.zs[p] = r.zi[p] = zero4();
             if (!valid[p]) continue;
-            if (kept) { r.zs[p] = ld4g(gn_keep_zs(keep, rows, gi) + off[p]); r.zi[p] = ld4g(gn_keep_zi(keep, rows, gi) + off[p]); }
-            r.y[p][0] = ld4g(Yg + off[p]); r.y[p][1] = ld4g(Yg + slab + off[p]);
+            if (kept) { r.zs[p] = ld4(gn_keep_zs(keep, rows, gi) + off[p]); r.zi[p] = ld4(gn_keep_zi(keep, rows, gi) + off[p]); }
+            r.y[p][0] = ld4(Yg + off[p]); r.y[p][1] = ld4(Yg + slab + off[p]);
             if (s >= 0) {
-                r.y[p][2] = ld4g(Yg + 2 * slab + off[p]);
+                r.y[p][2] = ld4(Yg + 2 * slab + off[p]);
                 const size_t o = (size_t)s * rows + base + node[p];
                 r.gout[p][0] = gS[o]; r.gout[p][1] = gI[o]; r.gout[p][2] = gR[o];
             }
@@ -140,7 +139,7 @@ __global__ __launch_bounds__(512) void k_tiny_bwd64(const int* __restrict__ rowp
         if (sched.slot[gi] < 0) return;
 #pragma unroll
         for (int p = 0; p < 2; ++p)       // padding rows: gout = 0 -> adds nothing
-            head_vjp64(r.y[p], r.gout[p], w3v, b3, w2, b2, aS[p], aI[p], aR[p], hacc);
+            gn_head_vjp<DppSum16>(r.y[p], r.gout[p], w3v, b3, w2, b2, aS[p], aI[p], aR[p], hacc);
     };
 
     // a tile whose rows 16..31 are all padding (karate: n = 34 -> tile 1 holds 2 rows) runs half the MFMAs, and the
@@ -190,6 +189,7 @@ __global__ __launch_bounds__(512) void k_tiny_bwd64(const int* __restrict__ rowp
         // 3. q = beta (a_I - a_S) Z_S
 #pragma unroll
         for (int p = 0; p < 2; ++p) {
+            // gn_q4 inline: the call reschedules this kernel
             *reinterpret_cast<float4*>(Qm + lr[p] * TS + 4 * sub) =
                 make_float4(bt[p] * (aI[p].x - aS[p].x) * zs[p].x, bt[p] * (aI[p].y - aS[p].y) * zs[p].y,
                             bt[p] * (aI[p].z - aS[p].z) * zs[p].z, bt[p] * (aI[p].w - aS[p].w) * zs[p].w);
@@ -202,6 +202,7 @@ __global__ __launch_bounds__(512) void k_tiny_bwd64(const int* __restrict__ rowp
             gather2_row_lds(col, ZIt, Qt, e_lo[p], e_hi[p], first16[p], sub, ai, gq);
             float4 dS = zero4(), dI = zero4();
             if (valid[p]) {
+            // gn_dpre_row inline, times dt: the call reschedules this kernel
 #define GN_DP(c)                                                                              \
                 {                                                                             \
                     const float v = bt[p] * (aI[p].c - aS[p].c);                              \
@@ -262,7 +263,7 @@ __global__ __launch_bounds__(512) void k_tiny_bwd64(const int* __restrict__ rowp
 #pragma unroll
         for (int X = 0; X < 3; ++X) {
             const float s = x[(size_t)(base + node[p]) * (3 + 64) + X];
-            const float4 y = ld4g(sol + X * slab + off[p]);
+            const float4 y = ld4(sol + X * slab + off[p]);
             const float4 mk = make_float4(y.x > 0.f ? av[X]->x : 0.f, y.y > 0.f ? av[X]->y : 0.f, y.z > 0.f ? av[X]->z : 0.f,
                                           y.w > 0.f ? av[X]->w : 0.f);
             dw1.x = fmaf(mk.x, s, dw1.x); dw1.y = fmaf(mk.y, s, dw1.y); dw1.z = fmaf(mk.z, s, dw1.z); dw1.w = fmaf(mk.w, s, dw1.w);

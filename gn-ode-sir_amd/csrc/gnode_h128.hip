@@ -7,6 +7,7 @@
 // CU; wave w owns output columns [32w, 32w + 32) as two independent 16x16 accumulators over K = 128
 // (v_mfma_f32_16x16x4_f32, kappa = 32 (lane>>4) + 4m + c so that every fragment is one ds_read_b128).
 #include "gnode_bwd.h"
+#include "gnode_row.h"
 #include <algorithm>
 
 typedef float f32x4h __attribute__((ext_vector_type(4)));
@@ -65,8 +66,8 @@ __global__ __launch_bounds__(256) void k_mlp128(const float* __restrict__ X, con
         __syncthreads();                                              // every wave is done reading the X tile
 #pragma unroll
         for (int r = 0; r < 4; ++r) {                                 // D: row = 4 kq + r, col = i
-            T[(4 * kq + r) * TS128 + 32 * w + i] = __builtin_amdgcn_rcpf(1.0f + __expf(-acc0[r]));
-            T[(4 * kq + r) * TS128 + 32 * w + 16 + i] = __builtin_amdgcn_rcpf(1.0f + __expf(-acc1[r]));
+            T[(4 * kq + r) * TS128 + 32 * w + i] = gn_sigmoid(acc0[r]);
+            T[(4 * kq + r) * TS128 + 32 * w + 16 + i] = gn_sigmoid(acc1[r]);
         }
         __syncthreads();
         const long ra = t * 16 + r0, rb = ra + 8;

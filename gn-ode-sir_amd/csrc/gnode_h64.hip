@@ -40,8 +40,8 @@ __global__ __launch_bounds__(256) void k_mlp64(const float* __restrict__ X, cons
     float4 x0 = zero4(), x1 = zero4();
     if (t < ntiles) {
         const long r0 = t * TILE_ROWS + lr0, r1 = t * TILE_ROWS + lr1;
-        if (r0 < nrows) x0 = ld4g(X + (size_t)r0 * 64 + 4 * sub);
-        if (r1 < nrows) x1 = ld4g(X + (size_t)r1 * 64 + 4 * sub);
+        if (r0 < nrows) x0 = ld4(X + (size_t)r0 * 64 + 4 * sub);
+        if (r1 < nrows) x1 = ld4(X + (size_t)r1 * 64 + 4 * sub);
     }
     for (; t < ntiles; t += gridDim.x) {
         *reinterpret_cast<float4*>(T + lr0 * TS + 4 * sub) = x0;
@@ -50,15 +50,15 @@ __global__ __launch_bounds__(256) void k_mlp64(const float* __restrict__ X, cons
         x0 = zero4(); x1 = zero4();
         if (tn < ntiles) {
             const long r0 = tn * TILE_ROWS + lr0, r1 = tn * TILE_ROWS + lr1;
-            if (r0 < nrows) x0 = ld4g(X + (size_t)r0 * 64 + 4 * sub);
-            if (r1 < nrows) x1 = ld4g(X + (size_t)r1 * 64 + 4 * sub);
+            if (r0 < nrows) x0 = ld4(X + (size_t)r0 * 64 + 4 * sub);
+            if (r1 < nrows) x1 = ld4(X + (size_t)r1 * 64 + 4 * sub);
         }
         __syncthreads();
         mfma_tile<true>(T, Wl, T2, bias_l, w, lane);
         __syncthreads();
         const long r0 = t * TILE_ROWS + lr0, r1 = t * TILE_ROWS + lr1;
-        if (r0 < nrows) st4g(Z + (size_t)r0 * 64 + 4 * sub, *reinterpret_cast<const float4*>(T2 + lr0 * TS + 4 * sub));
-        if (r1 < nrows) st4g(Z + (size_t)r1 * 64 + 4 * sub, *reinterpret_cast<const float4*>(T2 + lr1 * TS + 4 * sub));
+        if (r0 < nrows) st4(Z + (size_t)r0 * 64 + 4 * sub, *reinterpret_cast<const float4*>(T2 + lr0 * TS + 4 * sub));
+        if (r1 < nrows) st4(Z + (size_t)r1 * 64 + 4 * sub, *reinterpret_cast<const float4*>(T2 + lr1 * TS + 4 * sub));
     }
 }
 
@@ -126,7 +126,7 @@ __global__ __launch_bounds__(256, LAT ? 2 : StepOcc<PRJ>::value) void k_step64(c
     //  against 360 us per launch on the 75k graph x 8.)
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, g = lane >> 4, sub = lane & 15;
     // training: ZI_next may be a fresh table of the kept-activation buffer (gn_keep_zi) -- give it its zero row
-    if (!PRJ && blockIdx.x == 0 && threadIdx.x < 16) st4g(ZI_next + (size_t)rows * 64 + 4 * threadIdx.x, zero4());
+    if (!PRJ && blockIdx.x == 0 && threadIdx.x < 16) st4(ZI_next + (size_t)rows * 64 + 4 * threadIdx.x, zero4());
     load_W_to_lds<false>(W, L + O_W);
     L[O_W3 + threadIdx.x] = w3[threadIdx.x];
     float bias_l = bias[16 * w + (lane & 15)];
@@ -300,7 +300,7 @@ __global__ __launch_bounds__(256, LAT ? 2 : StepOcc<PRJ>::value) void k_step64(c
             const unsigned off = cur.row * 256u + lane_b;
             const float4 zs = *reinterpret_cast<const float4*>(t2s);
             float4 ys = *reinterpret_cast<const float4*>(tB);          // this row's Y_S, staged one iteration ago
-            float4 dS, dI, dR;
+            float4 dS, dI, dR;         // gn_rhs_row, gn_euler4 and gn_kept_ps inline: the calls reschedule k_step64
             dS.x = nb * (acc.x * zs.x); dS.y = nb * (acc.y * zs.y); dS.z = nb * (acc.z * zs.z); dS.w = nb * (acc.w * zs.w);
             dR.x = gm * zi.x; dR.y = gm * zi.y; dR.z = gm * zi.z; dR.w = gm * zi.w;
             dI.x = -dS.x - dR.x; dI.y = -dS.y - dR.y; dI.z = -dS.z - dR.z; dI.w = -dS.w - dR.w;
@@ -460,11 +460,11 @@ __global__ __launch_bounds__(768) void k_tiny64(const int* __restrict__ rowptr, 
         lrow[p] = t * TILE_ROWS + w * 8 + 4 * p + g;
         valid[p] = lrow[p] < n;
         const size_t off = (size_t)(base + lrow[p]) * 64 + 4 * sub;
-        *reinterpret_cast<float4*>(YS + lrow[p] * TS + 4 * sub) = valid[p] ? ld4g(Y0 + off) : zero4();
-        *reinterpret_cast<float4*>(YI + lrow[p] * TS + 4 * sub) = valid[p] ? ld4g(Y0 + slab + off) : zero4();
-        *reinterpret_cast<float4*>(ZA + lrow[p] * TS + 4 * sub) = valid[p] ? ld4g(ZI0 + off) : zero4();
-        if (PRJ) { if (sub == 0) *reinterpret_cast<float4*>(YR + lrow[p] * 4) = valid[p] ? ld4g(PR0 + (size_t)(base + lrow[p]) * 4) : zero4(); }
-        else *reinterpret_cast<float4*>(YR + lrow[p] * TS + 4 * sub) = valid[p] ? ld4g(Y0 + 2 * slab + off) : zero4();
+        *reinterpret_cast<float4*>(YS + lrow[p] * TS + 4 * sub) = valid[p] ? ld4(Y0 + off) : zero4();
+        *reinterpret_cast<float4*>(YI + lrow[p] * TS + 4 * sub) = valid[p] ? ld4(Y0 + slab + off) : zero4();
+        *reinterpret_cast<float4*>(ZA + lrow[p] * TS + 4 * sub) = valid[p] ? ld4(ZI0 + off) : zero4();
+        if (PRJ) { if (sub == 0) *reinterpret_cast<float4*>(YR + lrow[p] * 4) = valid[p] ? ld4(PR0 + (size_t)(base + lrow[p]) * 4) : zero4(); }
+        else *reinterpret_cast<float4*>(YR + lrow[p] * TS + 4 * sub) = valid[p] ? ld4(Y0 + 2 * slab + off) : zero4();
     }
     float nb[2] = {0.f, 0.f}, gm[2] = {0.f, 0.f};
     int e_lo[2] = {0, 0}, e_hi[2] = {0, 0}, first16[2] = {0, 0};
@@ -508,31 +508,29 @@ __global__ __launch_bounds__(768) void k_tiny64(const int* __restrict__ rowptr, 
             const float4 zs = *reinterpret_cast<const float4*>(T2 + lr * TS + 4 * sub);
             const float4 zi = *reinterpret_cast<const float4*>(Zc + lrow[p] * TS + 4 * sub);
             float4 dS, dI, dR;
-            dS.x = nb[p] * (ai.x * zs.x); dS.y = nb[p] * (ai.y * zs.y); dS.z = nb[p] * (ai.z * zs.z); dS.w = nb[p] * (ai.w * zs.w);
-            dR.x = gm[p] * zi.x; dR.y = gm[p] * zi.y; dR.z = gm[p] * zi.z; dR.w = gm[p] * zi.w;
-            dI.x = -dS.x - dR.x; dI.y = -dS.y - dR.y; dI.z = -dS.z - dR.z; dI.w = -dS.w - dR.w;
-            ys[p].x += dt * dS.x; ys[p].y += dt * dS.y; ys[p].z += dt * dS.z; ys[p].w += dt * dS.w;
-            yi[p].x += dt * dI.x; yi[p].y += dt * dI.y; yi[p].z += dt * dI.z; yi[p].w += dt * dI.w;
+            gn_rhs_row(nb[p], gm[p], ai, zs, zi, dS, dI, dR);
+            ys[p] = gn_euler4(ys[p], dt, dS);
+            yi[p] = gn_euler4(yi[p], dt, dI);
             *reinterpret_cast<float4*>(YS + lrow[p] * TS + 4 * sub) = ys[p];
             *reinterpret_cast<float4*>(YI + lrow[p] * TS + 4 * sub) = yi[p];
             float prj[4] = {0.f, 0.f, 0.f, 0.f};
-            if (PRJ) {
+            if (PRJ) {                 // the projection step inline, operation for operation as in k_step64 and k_pers64
                 float4 w3r[4];
 #pragma unroll
-                for (int q = 0; q < 4; ++q) w3r[q] = ld4g(w3 + q * 64 + 4 * sub);
+                for (int q = 0; q < 4; ++q) w3r[q] = ld4(w3 + q * 64 + 4 * sub);
                 prj[0] = pr[p].x + dt * (gm[p] * row_sum16(fmaf(w3r[0].x, zi.x, fmaf(w3r[0].y, zi.y, fmaf(w3r[0].z, zi.z, w3r[0].w * zi.w)))));
                 prj[1] = pr[p].y + dt * (gm[p] * row_sum16(fmaf(w3r[1].x, zi.x, fmaf(w3r[1].y, zi.y, fmaf(w3r[1].z, zi.z, w3r[1].w * zi.w)))));
                 prj[2] = pr[p].z + dt * (gm[p] * row_sum16(fmaf(w3r[2].x, zi.x, fmaf(w3r[2].y, zi.y, fmaf(w3r[2].z, zi.z, w3r[2].w * zi.w)))));
                 prj[3] = pr[p].w + dt * (gm[p] * row_sum16(fmaf(w3r[3].x, zi.x, fmaf(w3r[3].y, zi.y, fmaf(w3r[3].z, zi.z, w3r[3].w * zi.w)))));
                 pr[p] = make_float4(prj[0], prj[1], prj[2], prj[3]);
             } else {
-                yr[p].x += dt * dR.x; yr[p].y += dt * dR.y; yr[p].z += dt * dR.z; yr[p].w += dt * dR.w;
+                yr[p] = gn_euler4(yr[p], dt, dR);
             }
             if (solk && valid[p]) {
                 const size_t off = (size_t)(base + lrow[p]) * 64 + 4 * sub;
-                st4g(solk + off, ys[p]); st4g(solk + slab + off, yi[p]); st4g(solk + 2 * slab + off, yr[p]);
+                st4(solk + off, ys[p]); st4(solk + slab + off, yi[p]); st4(solk + 2 * slab + off, yr[p]);
                 if (!PRJ && keep) {                // kept activations of grid point k (gn_keep_zs / gn_keep_zi): the adjoint sweep reads them back
-                    st4g(gn_keep_zs(keep, rows, k) + off, zs); st4g(gn_keep_zi(keep, rows, k) + off, zi);
+                    st4(gn_keep_zs(keep, rows, k) + off, zs); st4(gn_keep_zi(keep, rows, k) + off, zi);
                 }
             }
             if (slot >= 0) {
@@ -608,7 +606,7 @@ __global__ __launch_bounds__(256) void k_prologue64(const float* __restrict__ x,
         for (int i = threadIdx.x; i < n_zero_words; i += 256) zero_words[i] = 0u;
     if (blockIdx.x == 0 && threadIdx.x < 32) {            // the zero rows behind the two gather tables (k_step64)
         float* z = (threadIdx.x < 16 ? ZI : ZI_alt) + (size_t)rows * 64 + 4 * (threadIdx.x & 15);
-        st4g(z, zero4());
+        st4(z, zero4());
     }
     __shared__ __attribute__((aligned(16))) float Wl[64 * TS];
     __shared__ __attribute__((aligned(16))) float T[TILE_ROWS * TS];
@@ -616,7 +614,7 @@ __global__ __launch_bounds__(256) void k_prologue64(const float* __restrict__ x,
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, g = lane >> 4, sub = lane & 15;
     load_W_to_lds<false>(W, Wl);
     const float bias_l = bias[16 * w + (lane & 15)];
-    const float4 wv = ld4g(w1 + 4 * sub), bv = ld4g(b1 + 4 * sub);
+    const float4 wv = ld4(w1 + 4 * sub), bv = ld4(b1 + 4 * sub);
     const size_t slab = (size_t)rows * 64;
     const long ntiles = (rows + TILE_ROWS - 1) / TILE_ROWS;
     const int lr[2] = {w * 8 + g, w * 8 + 4 + g};
@@ -636,12 +634,12 @@ __global__ __launch_bounds__(256) void k_prologue64(const float* __restrict__ x,
                 };
                 yS = enc(s0); yI = enc(i0); yR = enc(r0);
                 const size_t off = (size_t)r[p] * 64 + 4 * sub;
-                st4g(Y + off, yS); st4g(Y + slab + off, yI); st4g(Y + 2 * slab + off, yR);
+                st4(Y + off, yS); st4(Y + slab + off, yI); st4(Y + 2 * slab + off, yR);
                 if (sub == 0) { beta[r[p]] = xr[3]; gamma[r[p]] = xr[4]; }
                 if (sol0) {
-                    st4g(sol0 + off, yS); st4g(sol0 + slab + off, yI); st4g(sol0 + 2 * slab + off, yR);
+                    st4(sol0 + off, yS); st4(sol0 + slab + off, yI); st4(sol0 + 2 * slab + off, yR);
                     const float* bg = xr + 3 + 4 * sub;
-                    st4g(sol0 + 3 * slab + off, make_float4(bg[0], bg[1], bg[2], bg[3]));
+                    st4(sol0 + 3 * slab + off, make_float4(bg[0], bg[1], bg[2], bg[3]));
                 }
             }
             *reinterpret_cast<float4*>(T + lr[p] * TS + 4 * sub) = yI;
@@ -649,10 +647,10 @@ __global__ __launch_bounds__(256) void k_prologue64(const float* __restrict__ x,
                 float v[4];
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
-                    const float4 c = ld4g(w3 + k * 64 + 4 * sub);
-                    v[k] = row_sum16(fmaf(c.x, yR.x, fmaf(c.y, yR.y, fmaf(c.z, yR.z, c.w * yR.w))));
+                    const float4 c = ld4(w3 + k * 64 + 4 * sub);
+                    v[k] = row_sum16(dot4(c, yR));
                 }
-                if (valid && sub == 0) st4g(PR + (size_t)r[p] * 4, make_float4(v[0], v[1], v[2], v[3]));
+                if (valid && sub == 0) st4(PR + (size_t)r[p] * 4, make_float4(v[0], v[1], v[2], v[3]));
             }
             if (S0) {
                 float pS, pI, pR;
@@ -666,7 +664,7 @@ __global__ __launch_bounds__(256) void k_prologue64(const float* __restrict__ x,
         __syncthreads();
 #pragma unroll
         for (int p = 0; p < 2; ++p)
-            if (r[p] < rows) st4g(ZI + (size_t)r[p] * 64 + 4 * sub, *reinterpret_cast<const float4*>(T2 + lr[p] * TS + 4 * sub));
+            if (r[p] < rows) st4(ZI + (size_t)r[p] * 64 + 4 * sub, *reinterpret_cast<const float4*>(T2 + lr[p] * TS + 4 * sub));
         __syncthreads();
     }
 }

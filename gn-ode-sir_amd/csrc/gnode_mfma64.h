@@ -1,19 +1,13 @@
 // Device-side building blocks of the H = 64 kernels (gnode_h64.hip, gnode_bwd.hip): LDS tile
 // geometry, 16-lane DPP row helpers and the fp32 MFMA tile engine.
 #pragma once
-#include <hip/hip_runtime.h>
+#include "gnode_row.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 #define TS 68            // LDS row stride in floats (272 B): 16-B aligned rows, spreads banks
 #define TILE_ROWS 32
 
-// v_exp_f32 + v_rcp_f32 (1 ulp each).  __frcp_rn would expand to the IEEE-exact division sequence (~10 VALU
-// instructions per value, 16 values per wave and tile) for nothing: the result is within 2e-7 either way.
-__device__ __forceinline__ float sigmoid_f(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
-__device__ __forceinline__ float4 ld4g(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4g(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
-__device__ __forceinline__ float4 zero4() { return make_float4(0.f, 0.f, 0.f, 0.f); }
 // uniform base pointer + 32-bit BYTE offset: the compiler emits `global_load/store v, v_off, s[base:base+1]`, one
 // 32-bit VALU op per address instead of a 64-bit shift-add pair (the step kernel is VALU-issue sensitive)
 __device__ __forceinline__ float4 ld4o(const float* b, unsigned off) {
@@ -27,12 +21,12 @@ typedef float v4f __attribute__((ext_vector_type(4)));
 template <bool NT>
 __device__ __forceinline__ float4 ld4s(const float* p) {
     if (NT) { const v4f v = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(p)); return make_float4(v.x, v.y, v.z, v.w); }
-    return ld4g(p);
+    return ld4(p);
 }
 template <bool NT>
 __device__ __forceinline__ void st4s(float* p, float4 v) {
     if (NT) { v4f t = {v.x, v.y, v.z, v.w}; __builtin_nontemporal_store(t, reinterpret_cast<v4f*>(p)); }
-    else st4g(p, v);
+    else st4(p, v);
 }
 
 // the same through a uniform base + 32-bit byte offset
@@ -43,20 +37,8 @@ __device__ __forceinline__ void st4so(float* b, unsigned off, float4 v) { st4s<N
 
 // ---- DPP helpers: a 16-lane group is exactly one DPP row -----------------------------
 template <int CTRL>
-__device__ __forceinline__ float dpp_f(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true));
-}
-template <int CTRL>
 __device__ __forceinline__ int dpp_i(int v) {
     return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, true);
-}
-// sum over the 16 lanes of a row, result in every lane: mirror, half-mirror, xor2, xor1
-__device__ __forceinline__ float row_sum16(float v) {
-    v += dpp_f<0x140>(v);   // row_mirror        i <-> 15-i
-    v += dpp_f<0x141>(v);   // row_half_mirror   i <-> 7-i within each half
-    v += dpp_f<0x4E>(v);    // quad_perm [2,3,0,1]
-    v += dpp_f<0xB1>(v);    // quad_perm [1,0,3,2]
-    return v;
 }
 // lane J of the row broadcast to the whole row
 template <int J>
@@ -96,8 +78,8 @@ __device__ __forceinline__ void mfma_tile(const float* __restrict__ Tin, const f
     }
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-        Tout[(4 * kq + r) * TS + 16 * w + i] = SIGMOID ? sigmoid_f(acc0[r]) : acc0[r];
-        Tout[(16 + 4 * kq + r) * TS + 16 * w + i] = SIGMOID ? sigmoid_f(acc1[r]) : acc1[r];
+        Tout[(4 * kq + r) * TS + 16 * w + i] = SIGMOID ? gn_sigmoid(acc0[r]) : acc0[r];
+        Tout[(16 + 4 * kq + r) * TS + 16 * w + i] = SIGMOID ? gn_sigmoid(acc1[r]) : acc1[r];
     }
 }
 
@@ -131,7 +113,7 @@ __device__ __forceinline__ void mfma_tile16(const float* __restrict__ Tin, const
         acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.w, b1.w, acc1, 0, 0, 0);
     }
 #pragma unroll
-    for (int r = 0; r < 4; ++r) Tout[(4 * kq + r) * TS + 16 * w + i] = SIGMOID ? sigmoid_f(acc0[r] + acc1[r]) : acc0[r] + acc1[r];
+    for (int r = 0; r < 4; ++r) Tout[(4 * kq + r) * TS + 16 * w + i] = SIGMOID ? gn_sigmoid(acc0[r] + acc1[r]) : acc0[r] + acc1[r];
 }
 
 // Wl[r][c] = W[r][c] (forward: out = X W^T), or TRANSPOSE: Wl[c][r] = W[r][c] (backward: out = X W)
@@ -142,7 +124,7 @@ __device__ __forceinline__ void load_W_to_lds(const float* __restrict__ W, float
     for (int q = 0; q < 4; ++q) {
         const int idx = q * 256 + threadIdx.x;      // float4 index
         const int r = idx >> 4, c4 = idx & 15;
-        const float4 v = ld4g(W + (size_t)idx * 4);
+        const float4 v = ld4(W + (size_t)idx * 4);
         if (TRANSPOSE) {
             Wl[(4 * c4 + 0) * TS + r] = v.x; Wl[(4 * c4 + 1) * TS + r] = v.y;
             Wl[(4 * c4 + 2) * TS + r] = v.z; Wl[(4 * c4 + 3) * TS + r] = v.w;

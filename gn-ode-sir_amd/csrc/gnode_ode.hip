@@ -217,7 +217,7 @@ __global__ __launch_bounds__(256) void k_prologue_generic(const float* __restric
     }
     if (S0) {
         float pS, pI, pR;
-        readout_row<LPR>(yS, yI, yR, active, sub, H, w3, b3, w2, b2, pS, pI, pR);
+        gn_readout<XorSum<LPR>>(yS, yI, yR, W3Rows{w3, H, sub, active}, b3, w2, b2[0], pS, pI, pR);
         if (sub == 0 && inrow) { S0[r] = pS; I0[r] = pI; R0[r] = pR; }
     }
     const float4 bias4 = active ? ld4(bias + 4 * sub) : z0;
@@ -301,9 +301,7 @@ __global__ __launch_bounds__(256) void k_gather(const int* __restrict__ rowptr, 
     if (active) { zs = ld4(ZS + off); zi = ld4(ZI + off); }
     const float nb = -beta[(size_t)r * bg_stride], gm = gamma[(size_t)r * bg_stride];
     float4 dS, dI, dR;
-    dS.x = nb * (ai.x * zs.x); dS.y = nb * (ai.y * zs.y); dS.z = nb * (ai.z * zs.z); dS.w = nb * (ai.w * zs.w);
-    dR.x = gm * zi.x; dR.y = gm * zi.y; dR.z = gm * zi.z; dR.w = gm * zi.w;
-    dI.x = -dS.x - dR.x; dI.y = -dS.y - dR.y; dI.z = -dS.z - dR.z; dI.w = -dS.w - dR.w;
+    gn_rhs_row(nb, gm, ai, zs, zi, dS, dI, dR);
     if (MODE == 0) {
         if (active) { st4(dY + off, dS); st4(dY + slab + off, dI); st4(dY + 2 * slab + off, dR); }
         return;
@@ -311,15 +309,15 @@ __global__ __launch_bounds__(256) void k_gather(const int* __restrict__ rowptr, 
     float4 yS = make_float4(0.f, 0.f, 0.f, 0.f), yI = yS, yR = yS;
     if (active) {
         yS = ld4(Y + off); yI = ld4(Y + slab + off); yR = ld4(Y + 2 * slab + off);
-        yS.x += dt * dS.x; yS.y += dt * dS.y; yS.z += dt * dS.z; yS.w += dt * dS.w;
-        yI.x += dt * dI.x; yI.y += dt * dI.y; yI.z += dt * dI.z; yI.w += dt * dI.w;
-        yR.x += dt * dR.x; yR.y += dt * dR.y; yR.z += dt * dR.z; yR.w += dt * dR.w;
+        yS = gn_euler4(yS, dt, dS);
+        yI = gn_euler4(yI, dt, dI);
+        yR = gn_euler4(yR, dt, dR);
         st4(Y + off, yS); st4(Y + slab + off, yI); st4(Y + 2 * slab + off, yR);
         if (out.sol) { st4(out.sol + off, yS); st4(out.sol + slab + off, yI); st4(out.sol + 2 * slab + off, yR); }
     }
     if (out.S) {
         float pS, pI, pR;
-        readout_row<LPR>(yS, yI, yR, active, sub, H, w3, b3, w2, b2, pS, pI, pR);
+        gn_readout<XorSum<LPR>>(yS, yI, yR, W3Rows{w3, H, sub, active}, b3, w2, b2[0], pS, pI, pR);
         if (sub == 0) { out.S[r] = pS; out.I[r] = pI; out.R[r] = pR; }
     }
 }
@@ -381,19 +379,17 @@ __global__ __launch_bounds__(256) void k_step_generic(const int* __restrict__ ro
     } else ai = gather_row<LPR>(rowptr, col, ZI + (size_t)base * H, node, sub, active, H);
     const float4 zs = group_mlp<LPR>(yS, Wt, bias4, sub, active, H);
     float4 dS, dI, dR;
-    dS.x = nb * (ai.x * zs.x); dS.y = nb * (ai.y * zs.y); dS.z = nb * (ai.z * zs.z); dS.w = nb * (ai.w * zs.w);
-    dR.x = gm * zi.x; dR.y = gm * zi.y; dR.z = gm * zi.z; dR.w = gm * zi.w;
-    dI.x = -dS.x - dR.x; dI.y = -dS.y - dR.y; dI.z = -dS.z - dR.z; dI.w = -dS.w - dR.w;
-    yS.x += dt * dS.x; yS.y += dt * dS.y; yS.z += dt * dS.z; yS.w += dt * dS.w;
-    yI.x += dt * dI.x; yI.y += dt * dI.y; yI.z += dt * dI.z; yI.w += dt * dI.w;
-    yR.x += dt * dR.x; yR.y += dt * dR.y; yR.z += dt * dR.z; yR.w += dt * dR.w;
+    gn_rhs_row(nb, gm, ai, zs, zi, dS, dI, dR);
+    yS = gn_euler4(yS, dt, dS);
+    yI = gn_euler4(yI, dt, dI);
+    yR = gn_euler4(yR, dt, dR);
     if (active) {                                 // in place, or trajectory point k -> k+1 (the trajectory is the state)
         float* Yo = out.sol ? out.sol : Y;
         st4(Yo + off, yS); st4(Yo + slab + off, yI); st4(Yo + 2 * slab + off, yR);
     }
     if (out.S) {
         float pS, pI, pR;
-        readout_row<LPR>(yS, yI, yR, active, sub, H, w3, b3, w2, b2, pS, pI, pR);
+        gn_readout<XorSum<LPR>>(yS, yI, yR, W3Rows{w3, H, sub, active}, b3, w2, b2[0], pS, pI, pR);
         if (sub == 0) { out.S[r] = pS; out.I[r] = pI; out.R[r] = pR; }
     }
     const float4 zn = group_mlp<LPR>(yI, Wt, bias4, sub, active, H);     // Z_I of the next step
@@ -414,7 +410,7 @@ __global__ __launch_bounds__(256) void k_readout(const float* __restrict__ Y, lo
     float4 yS = make_float4(0.f, 0.f, 0.f, 0.f), yI = yS, yR = yS;
     if (active) { yS = ld4(Y + off); yI = ld4(Y + slab + off); yR = ld4(Y + 2 * slab + off); }
     float pS, pI, pR;
-    readout_row<LPR>(yS, yI, yR, active, sub, H, w3, b3, w2, b2, pS, pI, pR);
+    gn_readout<XorSum<LPR>>(yS, yI, yR, W3Rows{w3, H, sub, active}, b3, w2, b2[0], pS, pI, pR);
     if (sub == 0) { S[r] = pS; I[r] = pI; R[r] = pR; }
 }
 

@@ -184,12 +184,10 @@ __global__ __launch_bounds__(256 * NT) void k_pers64(const PersArgs a) {
             }
             PS_STAMP(1)
             float4 dS, dI, dR;
-            dS.x = nb * (acc.x * zs.x); dS.y = nb * (acc.y * zs.y); dS.z = nb * (acc.z * zs.z); dS.w = nb * (acc.w * zs.w);
-            dR.x = gm * zi.x; dR.y = gm * zi.y; dR.z = gm * zi.z; dR.w = gm * zi.w;
-            dI.x = -dS.x - dR.x; dI.y = -dS.y - dR.y; dI.z = -dS.z - dR.z; dI.w = -dS.w - dR.w;
-            ys.x += dt * dS.x; ys.y += dt * dS.y; ys.z += dt * dS.z; ys.w += dt * dS.w;
-            yi.x += dt * dI.x; yi.y += dt * dI.y; yi.z += dt * dI.z; yi.w += dt * dI.w;
-            if (PRJ) {
+            gn_rhs_row(nb, gm, acc, zs, zi, dS, dI, dR);
+            ys = gn_euler4(ys, dt, dS);
+            yi = gn_euler4(yi, dt, dI);
+            if (PRJ) {                 // the projection step inline, operation for operation as in k_step64 and k_tiny64
                 float4 w3r[4];
 #pragma unroll
                 for (int q = 0; q < 4; ++q) w3r[q] = *reinterpret_cast<const float4*>(w3s + q * 64 + 4 * sub);
@@ -200,12 +198,11 @@ __global__ __launch_bounds__(256 * NT) void k_pers64(const PersArgs a) {
                 prj[3] = pr.w + dt * (gm * row_sum16(fmaf(w3r[3].x, zi.x, fmaf(w3r[3].y, zi.y, fmaf(w3r[3].z, zi.z, w3r[3].w * zi.w)))));
                 pr = make_float4(prj[0], prj[1], prj[2], prj[3]);
             } else {
-                yr.x += dt * dR.x; yr.y += dt * dR.y; yr.z += dt * dR.z; yr.w += dt * dR.w;
+                yr = gn_euler4(yr, dt, dR);
                 // kept for the backward: Z_S(y_k) and A Z_I(y_k) [* Z_S (1 - Z_S) with a keep buffer]
                 zs_k = zs;
                 ai_k = acc;
-                if (a.keep) ai_k = make_float4(acc.x * (zs.x * (1.0f - zs.x)), acc.y * (zs.y * (1.0f - zs.y)),
-                                               acc.z * (zs.z * (1.0f - zs.z)), acc.w * (zs.w * (1.0f - zs.w)));
+                if (a.keep) ai_k = gn_kept_ps(acc, zs);
             }
             *reinterpret_cast<float4*>(TA + ro) = yi;
             *reinterpret_cast<float4*>(TB + ro) = ys;

@@ -18,7 +18,6 @@
 #include "gnode_bwd.h"
 #include "gnode_h64.h"
 #include "gnode_mfma64.h"
-#include "gnode_head64.h"
 #include "gnode_pers64.h"
 #include "gnode_pers64_dev.h"
 #include <algorithm>
@@ -151,13 +150,12 @@ __global__ __launch_bounds__(256 * NT) void k_pers_bwd64(const PersBwdArgs a) {
             if (valid) { gout[0] = a.gS[(size_t)s * rows + row]; gout[1] = a.gI[(size_t)s * rows + row]; gout[2] = a.gR[(size_t)s * rows + row]; }
             float4 w3v[4];
 #pragma unroll
-            for (int q = 0; q < 4; ++q) w3v[q] = ld4g(a.w3 + q * 64 + 4 * sub);
-            head_vjp64(y, gout, w3v, a.b3, a.w2, a.b2, aS, aI, aR, hacc);
+            for (int q = 0; q < 4; ++q) w3v[q] = ld4(a.w3 + q * 64 + 4 * sub);
+            gn_head_vjp<DppSum16>(y, gout, w3v, a.b3, a.w2, a.b2, aS, aI, aR, hacc);
         }
         const float4 zsp = ld4so<true>(gn_keep_zs(a.keep, rows, G - 2), off);
         if (valid) pers_st<STAUX>(pers_rsrc(a.Q[1], tbytes), off,
-                                  make_float4(bt * (aI.x - aS.x) * zsp.x, bt * (aI.y - aS.y) * zsp.y,
-                                              bt * (aI.z - aS.z) * zsp.z, bt * (aI.w - aS.w) * zsp.w));
+                                  gn_q4(bt, aI, aS, zsp));
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         if (threadIdx.x == 0) __hip_atomic_store(flags + idx, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -183,14 +181,8 @@ __global__ __launch_bounds__(256 * NT) void k_pers_bwd64(const PersBwdArgs a) {
         const Pre p = pre;
         {
             float4 dS, dI;
-#define PB_DP(c)                                                                              \
-            {                                                                                 \
-                const float v = bt * (aI.c - aS.c);                                           \
-                dS.c = v * p.ps.c;                                                            \
-                dI.c = valid ? (gq.c + gm * (aR.c - aI.c)) * (p.zi.c * (1.0f - p.zi.c)) : 0.f; \
-            }
-            PB_DP(x) PB_DP(y) PB_DP(z) PB_DP(w)
-#undef PB_DP
+            gn_dpre_row_kept(bt, gm, aS, aI, aR, p.ps, gq, p.zi, dS, dI);
+            dI = valid ? dI : zero4();
             totb.x += dt * (dS.x + dI.x); totb.y += dt * (dS.y + dI.y); totb.z += dt * (dS.z + dI.z); totb.w += dt * (dS.w + dI.w);
             *reinterpret_cast<float4*>(Dt0 + ro) = dS; *reinterpret_cast<float4*>(Dt1 + ro) = dI;
             *reinterpret_cast<float4*>(Yt0 + ro) = p.ys; *reinterpret_cast<float4*>(Yt1 + ro) = p.yi;
@@ -208,13 +200,12 @@ __global__ __launch_bounds__(256 * NT) void k_pers_bwd64(const PersBwdArgs a) {
         if (a.slot[i] >= 0) {                                          // the head's VJP at grid point i-1 (uniform per interval)
             float4 w3v[4];
 #pragma unroll
-            for (int q = 0; q < 4; ++q) w3v[q] = ld4g(a.w3 + q * 64 + 4 * sub);
-            head_vjp64(p.y, p.gout, w3v, a.b3, a.w2, a.b2, aS, aI, aR, hacc);   // padding rows: gout = 0 adds nothing
+            for (int q = 0; q < 4; ++q) w3v[q] = ld4(a.w3 + q * 64 + 4 * sub);
+            gn_head_vjp<DppSum16>(p.y, p.gout, w3v, a.b3, a.w2, a.b2, aS, aI, aR, hacc);   // padding rows: gout = 0 adds nothing
         }
         if (i > 1) {
             if (valid) pers_st<STAUX>(pers_rsrc(a.Q[cur ^ 1], tbytes), off,
-                                      make_float4(bt * (aI.x - aS.x) * p.zsp.x, bt * (aI.y - aS.y) * p.zsp.y,
-                                                  bt * (aI.z - aS.z) * p.zsp.z, bt * (aI.w - aS.w) * p.zsp.w));
+                                      gn_q4(bt, aI, aS, p.zsp));
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __syncthreads();
             if (threadIdx.x == 0) __hip_atomic_store(flags + idx, (unsigned)k + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

@@ -27,7 +27,6 @@
 #include "gnode_bwd.h"
 #include "gnode_common.h"
 #include "gnode_generic.h"
-#include "gnode_head64.h"
 #include "gnode_pers64_dev.h"
 #include "gnode_persg.h"
 #include <algorithm>
@@ -243,12 +242,10 @@ __global__ __launch_bounds__(256) void k_persg(const PersgArgs a) {
         PS_STAMP(3)
         const float dt = a.sched.dt[k];
         float4 dS, dI, dR;
-        dS.x = nb * (ai.x * zs.x); dS.y = nb * (ai.y * zs.y); dS.z = nb * (ai.z * zs.z); dS.w = nb * (ai.w * zs.w);
-        dR.x = gm * zmine.x; dR.y = gm * zmine.y; dR.z = gm * zmine.z; dR.w = gm * zmine.w;
-        dI.x = -dS.x - dR.x; dI.y = -dS.y - dR.y; dI.z = -dS.z - dR.z; dI.w = -dS.w - dR.w;
-        yS.x += dt * dS.x; yS.y += dt * dS.y; yS.z += dt * dS.z; yS.w += dt * dS.w;
-        yI.x += dt * dI.x; yI.y += dt * dI.y; yI.z += dt * dI.z; yI.w += dt * dI.w;
-        yR.x += dt * dR.x; yR.y += dt * dR.y; yR.z += dt * dR.z; yR.w += dt * dR.w;
+        gn_rhs_row(nb, gm, ai, zs, zmine, dS, dI, dR);
+        yS = gn_euler4(yS, dt, dS);
+        yI = gn_euler4(yI, dt, dI);
+        yR = gn_euler4(yR, dt, dR);
         if (k + 1 < n_steps) {
             const float4 zn = group_mlp<LPR>(yI, L.Wt, bias4, sub, true, H);      // Z_I of the next step -> the other table
             if (row.inrow) pers_st<16>(tab[(k + 1) & 1], row.off_b, zn);
@@ -265,7 +262,7 @@ __global__ __launch_bounds__(256) void k_persg(const PersgArgs a) {
         const int slot = a.sched.slot[k];
         if (slot >= 0) {
             float pS, pI, pR;
-            readout_row_regs<LPR>(yS, yI, yR, w3r, b3r, w2r, b2r, pS, pI, pR);
+            gn_readout<XorSum<LPR>>(yS, yI, yR, w3r, b3r, w2r, b2r, pS, pI, pR);
             if (sub == 0 && row.inrow) { const size_t o = (size_t)slot * a.rows + row.r; a.S[o] = pS; a.I[o] = pI; a.R[o] = pR; }
         }
         PS_STAMP(6)
@@ -292,7 +289,6 @@ __device__ __forceinline__ float4 pg_lin(float4 x, const float* __restrict__ M, 
     }
     return acc;
 }
-__device__ __forceinline__ float pg_sig(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
 
 template <int LPR>
 __global__ __launch_bounds__(256) void k_persg_bwd(const PersgArgs a) {
@@ -339,14 +335,13 @@ __global__ __launch_bounds__(256) void k_persg_bwd(const PersgArgs a) {
                 gout[0] = a.S[o]; gout[1] = a.I[o]; gout[2] = a.R[o];
             }
         }
-        if (slot_last >= 0) head_vjp64<LPR>(y, gout, w3v, a.b3, a.w2, a.b2, aS, aI, aR, hacc);
+        if (slot_last >= 0) gn_head_vjp<XorSum<LPR>>(y, gout, w3v, a.b3, a.w2, a.b2, aS, aI, aR, hacc);
         yS = y[0]; yI = y[1];
         zs0 = group_mlp<LPR>(yS, L.Wt, bias4, sub, true, H);                       // (the start-up launch's arithmetic: bias first)
         zi0 = group_mlp<LPR>(yI, L.Wt, bias4, sub, true, H);
         if (row.inrow) {
             pers_st<16>(zt[0], row.off_b, zi0);
-            pers_st<16>(qt[0], row.off_b, make_float4(bt * (aI.x - aS.x) * zs0.x, bt * (aI.y - aS.y) * zs0.y,
-                                                      bt * (aI.z - aS.z) * zs0.z, bt * (aI.w - aS.w) * zs0.w));
+            pers_st<16>(qt[0], row.off_b, gn_q4(bt, aI, aS, zs0));
         }
         pg_publish(a.ctl, 1u);
     }
@@ -395,30 +390,22 @@ __global__ __launch_bounds__(256) void k_persg_bwd(const PersgArgs a) {
         pg_sum2<GN_PERSG_BNB>(ai, gq, zt[cur], qt[cur], L.IDS + row.estart, row.cnt, cmax, lane_b);
         PS_STAMP(3)
         float4 dS, dI;
-#define PG_DPRE(c)                                                         \
-        {                                                                  \
-            const float v = bt * (aI.c - aS.c);                            \
-            dS.c = (v * ai.c) * (zs0.c * (1.0f - zs0.c));                  \
-            dI.c = (gq.c + gm * (aR.c - aI.c)) * (zi0.c * (1.0f - zi0.c)); \
-        }
-        PG_DPRE(x) PG_DPRE(y) PG_DPRE(z) PG_DPRE(w)
-#undef PG_DPRE
+        gn_dpre_row(bt, gm, aS, aI, aR, ai, gq, zs0, zi0, dS, dI);
         // g_Y = dpre W, a += dt g_Y
         const float4 uS = pg_lin<LPR>(dS, L.Wl, sub), uI = pg_lin<LPR>(dI, L.Wl, sub);
         aS.x += dt * uS.x; aS.y += dt * uS.y; aS.z += dt * uS.z; aS.w += dt * uS.w;
         aI.x += dt * uI.x; aI.y += dt * uI.y; aI.z += dt * uI.z; aI.w += dt * uI.w;
         // dL/dsol[i-1] through the head
-        if (slot >= 0) head_vjp64<LPR>(y, gout, w3v, a.b3, a.w2, a.b2, aS, aI, aR, hacc);
+        if (slot >= 0) gn_head_vjp<XorSum<LPR>>(y, gout, w3v, a.b3, a.w2, a.b2, aS, aI, aR, hacc);
         // Z(y_{i-1}) and q: the tables the next interval gathers
         float4 zs = z0, zi = z0;
         if (i > 1) {
             zs = pg_lin<LPR>(y[0], L.Wt, sub); zi = pg_lin<LPR>(y[1], L.Wt, sub);
-            zs = make_float4(pg_sig(zs.x + bias4.x), pg_sig(zs.y + bias4.y), pg_sig(zs.z + bias4.z), pg_sig(zs.w + bias4.w));
-            zi = make_float4(pg_sig(zi.x + bias4.x), pg_sig(zi.y + bias4.y), pg_sig(zi.z + bias4.z), pg_sig(zi.w + bias4.w));
+            zs = make_float4(gn_sigmoid(zs.x + bias4.x), gn_sigmoid(zs.y + bias4.y), gn_sigmoid(zs.z + bias4.z), gn_sigmoid(zs.w + bias4.w));
+            zi = make_float4(gn_sigmoid(zi.x + bias4.x), gn_sigmoid(zi.y + bias4.y), gn_sigmoid(zi.z + bias4.z), gn_sigmoid(zi.w + bias4.w));
             if (row.inrow) {
                 pers_st<16>(zt[cur ^ 1], row.off_b, zi);
-                pers_st<16>(qt[cur ^ 1], row.off_b, make_float4(bt * (aI.x - aS.x) * zs.x, bt * (aI.y - aS.y) * zs.y,
-                                                                bt * (aI.z - aS.z) * zs.z, bt * (aI.w - aS.w) * zs.w));
+                pers_st<16>(qt[cur ^ 1], row.off_b, gn_q4(bt, aI, aS, zs));
             }
             PS_STAMP(4)
             pg_publish(a.ctl, (unsigned)(G - i + 1));

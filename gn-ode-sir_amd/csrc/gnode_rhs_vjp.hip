@@ -19,18 +19,8 @@
 #include "gnode_common.h"
 #include "gnode_bwd.h"
 #include "gnode_gather.h"
+#include "gnode_row.h"
 #include <algorithm>
-
-__device__ __forceinline__ float4 vld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void vst4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
-__device__ __forceinline__ float4 vz4() { return make_float4(0.f, 0.f, 0.f, 0.f); }
-
-template <int LPR>
-__device__ __forceinline__ float vgsum(float v) {
-#pragma unroll
-    for (int m = LPR / 2; m >= 1; m >>= 1) v += __shfl_xor(v, m, LPR);
-    return v;
-}
 
 // --------------------------------------------------------------------------- pass 1: q = beta (v_I - v_S) * Z_S
 __global__ __launch_bounds__(256) void k_vjp_q(const float* __restrict__ vSI, const float* __restrict__ ZS,
@@ -39,9 +29,8 @@ __global__ __launch_bounds__(256) void k_vjp_q(const float* __restrict__ vSI, co
     const int h4 = H / 4;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
         const float bt = bg[(i / h4) * H];
-        const float4 vS = vld4(vSI + 4 * i), vI = vld4(vSI + slab + 4 * i), z = vld4(ZS + 4 * i);
-        vst4(q + 4 * i, make_float4(bt * (vI.x - vS.x) * z.x, bt * (vI.y - vS.y) * z.y, bt * (vI.z - vS.z) * z.z,
-                                    bt * (vI.w - vS.w) * z.w));
+        const float4 vS = ld4(vSI + 4 * i), vI = ld4(vSI + slab + 4 * i), z = ld4(ZS + 4 * i);
+        st4(q + 4 * i, gn_q4(bt, vI, vS, z));
     }
 }
 
@@ -103,46 +92,45 @@ __global__ __launch_bounds__(256) void k_rhs_vjp(VjpArgs A) {
         const long b = row_ok ? r / A.n : 0;
         const int node = row_ok ? (int)(r - b * A.n) : 0;
         const size_t off = (size_t)r * H + 4 * sub;
-        float4 ai = vz4(), gq = vz4();
+        float4 ai = zero4(), gq = zero4();
         const int hub = (row_ok && A.hubidx) ? A.hubidx[node] : -1;
         if (hub >= 0 && lane_ok) {
-            ai = vld4(A.AIhub + ((size_t)b * A.n_hub + hub) * H + 4 * sub);
-            gq = vld4(A.GQhub + ((size_t)b * A.n_hub + hub) * H + 4 * sub);
+            ai = ld4(A.AIhub + ((size_t)b * A.n_hub + hub) * H + 4 * sub);
+            gq = ld4(A.GQhub + ((size_t)b * A.n_hub + hub) * H + 4 * sub);
         }
         const int start = (row_ok && hub < 0) ? A.rowptr[node] : 0, end = (row_ok && hub < 0) ? A.rowptr[node + 1] : 0;
         const size_t base = (size_t)b * A.n * H;
         gn_gather2<4>(A.col, start, end, ZI + base, A.q + base, H, sub, lane_ok, ai, gq);
-        float4 zs = vz4(), zi = vz4(), vS = vz4(), vI = vz4(), vR = vz4(), yS = vz4(), yI = vz4();
+        float4 zs = zero4(), zi = zero4(), vS = zero4(), vI = zero4(), vR = zero4(), yS = zero4(), yI = zero4();
         float bt = 0.f, gm = 0.f;
         if (ok) {
-            zs = vld4(A.Z + off); zi = vld4(ZI + off);
-            vS = vld4(A.vSI + off); vI = vld4(A.vSI + slab + off); vR = vld4(A.vR + off);
-            if (A.part) { yS = vld4(A.y + off); yI = vld4(A.y + slab + off); }
+            zs = ld4(A.Z + off); zi = ld4(ZI + off);
+            vS = ld4(A.vSI + off); vI = ld4(A.vSI + slab + off); vR = ld4(A.vR + off);
+            if (A.part) { yS = ld4(A.y + off); yI = ld4(A.y + slab + off); }
         }
         if (row_ok) { bt = A.bg[(size_t)r * H]; gm = A.bg[(size_t)r * H + 1]; }
         if (A.fSI && ok) {
             // gnode_rhs_f32's expressions (k_gather), operation for operation
             const float nb = -bt;
             float4 dS, dI, dR;
-            dS.x = nb * (ai.x * zs.x); dS.y = nb * (ai.y * zs.y); dS.z = nb * (ai.z * zs.z); dS.w = nb * (ai.w * zs.w);
-            dR.x = gm * zi.x; dR.y = gm * zi.y; dR.z = gm * zi.z; dR.w = gm * zi.w;
-            dI.x = -dS.x - dR.x; dI.y = -dS.y - dR.y; dI.z = -dS.z - dR.z; dI.w = -dS.w - dR.w;
-            vst4(A.fSI + off, dS); vst4(A.fSI + slab + off, dI);
-            if (A.fR) vst4(A.fR + off, dR);
+            gn_rhs_row(nb, gm, ai, zs, zi, dS, dI, dR);
+            st4(A.fSI + off, dS); st4(A.fSI + slab + off, dI);
+            if (A.fR) st4(A.fR + off, dR);
         }
-        if (A.f4 && ok) vst4(A.f4 + off, vz4());
-        if (A.gyR && ok) vst4(A.gyR + off, vz4());
+        if (A.f4 && ok) st4(A.f4 + off, zero4());
+        if (A.gyR && ok) st4(A.gyR + off, zero4());
         if (A.gybg) {
             // d/dbeta: sum_h (v_I - v_S) AI Z_S;  d/dgamma: sum_h (v_R - v_I) Z_I   (every lane of the group takes part)
             float c0 = (vI.x - vS.x) * ai.x * zs.x + (vI.y - vS.y) * ai.y * zs.y + (vI.z - vS.z) * ai.z * zs.z +
                        (vI.w - vS.w) * ai.w * zs.w;
             float c1 = (vR.x - vI.x) * zi.x + (vR.y - vI.y) * zi.y + (vR.z - vI.z) * zi.z + (vR.w - vI.w) * zi.w;
-            c0 = vgsum<LPR>(c0);
-            c1 = vgsum<LPR>(c1);
-            if (ok) vst4(A.gybg + off, sub == 0 ? make_float4(c0, c1, 0.f, 0.f) : vz4());
+            c0 = group_sum<LPR>(c0);
+            c1 = group_sum<LPR>(c1);
+            if (ok) st4(A.gybg + off, sub == 0 ? make_float4(c0, c1, 0.f, 0.f) : zero4());
         }
         if (!mat) continue;
         float4 dS, dI;
+        // gn_dpre_row inline: the call reschedules this kernel
 #define GN_VJP_DPRE(c)                                                     \
         {                                                                  \
             const float u = bt * (vI.c - vS.c);                            \
@@ -153,33 +141,33 @@ __global__ __launch_bounds__(256) void k_rhs_vjp(VjpArgs A) {
 #undef GN_VJP_DPRE
         __syncthreads();                       // previous tile fully consumed (also covers the W stage)
         if (lane_ok) {                         // idle lanes of a group (H/4 not a power of two) would write into the next row
-            vst4(Dt + (size_t)grp * H + 4 * sub, ok ? dS : vz4());
-            vst4(Dt + ((size_t)G + grp) * H + 4 * sub, ok ? dI : vz4());
+            st4(Dt + (size_t)grp * H + 4 * sub, ok ? dS : zero4());
+            st4(Dt + ((size_t)G + grp) * H + 4 * sub, ok ? dI : zero4());
             if (A.part) {
-                vst4(Yt + (size_t)grp * H + 4 * sub, yS);
-                vst4(Yt + ((size_t)G + grp) * H + 4 * sub, yI);
+                st4(Yt + (size_t)grp * H + 4 * sub, yS);
+                st4(Yt + ((size_t)G + grp) * H + 4 * sub, yI);
             }
         }
         __syncthreads();
         if (A.gySI) {
             // g_y = dpre W  (this lane: 4 columns of its own row, both slabs)
-            float4 gS = vz4(), gI = vz4();
+            float4 gS = zero4(), gI = zero4();
             const float* pS = Dt + (size_t)grp * H;
             const float* pI = Dt + ((size_t)G + grp) * H;
             for (int j = 0; j < H; ++j) {
-                const float4 wv = lane_ok ? vld4(Wl + (size_t)j * H + 4 * sub) : vz4();
+                const float4 wv = lane_ok ? ld4(Wl + (size_t)j * H + 4 * sub) : zero4();
                 const float s = pS[j], i = pI[j];
                 gS.x = fmaf(s, wv.x, gS.x); gS.y = fmaf(s, wv.y, gS.y); gS.z = fmaf(s, wv.z, gS.z); gS.w = fmaf(s, wv.w, gS.w);
                 gI.x = fmaf(i, wv.x, gI.x); gI.y = fmaf(i, wv.y, gI.y); gI.z = fmaf(i, wv.z, gI.z); gI.w = fmaf(i, wv.w, gI.w);
             }
-            if (ok) { vst4(A.gySI + off, gS); vst4(A.gySI + slab + off, gI); }
+            if (ok) { st4(A.gySI + off, gS); st4(A.gySI + slab + off, gI); }
         }
         if (A.part) {
             // gW[j][k] += sum_rows dpre[r][j] * y[r][k]   (thread owns entries e = tid + 256 m), gb[j] += sum_rows dpre[r][j]
             if (quad) {
 #pragma unroll 2
                 for (int rr = 0; rr < 2 * G; ++rr) {
-                    const float4 yq = vld4(Yt + (size_t)rr * H + 4 * qc);
+                    const float4 yq = ld4(Yt + (size_t)rr * H + 4 * qc);
                     const float* d = Dt + (size_t)rr * H;
 #pragma unroll
                     for (int a = 0; a < MAXA; ++a) {
@@ -248,32 +236,32 @@ __global__ __launch_bounds__(256) void k_rk4_stage(int mode, size_t n4, float dt
     const float third = 1.0f / 3.0f, h = -dt;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
         const size_t o = 4 * i;
-        const float4 av = vld4(a + o);
-        float4 yo = vz4(), ao;
+        const float4 av = ld4(a + o);
+        float4 yo = zero4(), ao;
         if (mode == 2) {
-            const float4 yv = vld4(y + o), c1 = vld4(k1 + o), u1 = vld4(V1 + o);
+            const float4 yv = ld4(y + o), c1 = ld4(k1 + o), u1 = ld4(V1 + o);
 #define S2(c) yo.c = yv.c + h * c1.c * third; ao.c = av.c + dt * u1.c * third;
             S2(x) S2(y) S2(z) S2(w)
 #undef S2
         } else if (mode == 3) {
-            const float4 yv = vld4(y + o), c1 = vld4(k1 + o), c2 = vld4(k2 + o), u1 = vld4(V1 + o), u2 = vld4(V2 + o);
+            const float4 yv = ld4(y + o), c1 = ld4(k1 + o), c2 = ld4(k2 + o), u1 = ld4(V1 + o), u2 = ld4(V2 + o);
 #define S3(c) yo.c = yv.c + h * (c2.c - c1.c * third); ao.c = av.c + dt * (u2.c - u1.c * third);
             S3(x) S3(y) S3(z) S3(w)
 #undef S3
         } else if (mode == 4) {
-            const float4 yv = vld4(y + o), c1 = vld4(k1 + o), c2 = vld4(k2 + o), c3 = vld4(k3 + o);
-            const float4 u1 = vld4(V1 + o), u2 = vld4(V2 + o), u3 = vld4(V3 + o);
+            const float4 yv = ld4(y + o), c1 = ld4(k1 + o), c2 = ld4(k2 + o), c3 = ld4(k3 + o);
+            const float4 u1 = ld4(V1 + o), u2 = ld4(V2 + o), u3 = ld4(V3 + o);
 #define S4(c) yo.c = yv.c + h * (c1.c - c2.c + c3.c); ao.c = av.c + dt * (u1.c - u2.c + u3.c);
             S4(x) S4(y) S4(z) S4(w)
 #undef S4
         } else {
-            const float4 u1 = vld4(V1 + o), u2 = vld4(V2 + o), u3 = vld4(V3 + o), u4 = vld4(V4 + o);
+            const float4 u1 = ld4(V1 + o), u2 = ld4(V2 + o), u3 = ld4(V3 + o), u4 = ld4(V4 + o);
 #define S5(c) ao.c = av.c + (u1.c + 3.0f * (u2.c + u3.c) + u4.c) * dt * 0.125f;
             S5(x) S5(y) S5(z) S5(w)
 #undef S5
         }
-        if (mode != 5) vst4(ys + o, yo);
-        vst4(as + o, ao);
+        if (mode != 5) st4(ys + o, yo);
+        st4(as + o, ao);
     }
 }
 

@@ -3,6 +3,7 @@
 #pragma once
 #include "gnode_mfma64.h"
 
+// The H = 64 forwards' read-out: gn_readout's operations with row_sum16 (one template for both reschedules these kernels).
 // PRJ: the R compartment arrives already projected (prj[k] = w3[k] . Y_R, see k_step64's PRJ mode)
 template <bool PRJ>
 __device__ __forceinline__ void readout64(float4 yS, float4 yI, float4 yR, const float (&prj)[4], int sub,
@@ -12,7 +13,7 @@ __device__ __forceinline__ void readout64(float4 yS, float4 yI, float4 yR, const
     float qS = b2[0], qI = qS, qR = qS;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-        const float4 wv = ld4g(w3 + k * 64 + 4 * sub);
+        const float4 wv = ld4(w3 + k * 64 + 4 * sub);
         float s = fmaf(wv.x, yS.x, fmaf(wv.y, yS.y, fmaf(wv.z, yS.z, wv.w * yS.w)));
         float i = fmaf(wv.x, yI.x, fmaf(wv.y, yI.y, fmaf(wv.z, yI.z, wv.w * yI.w)));
         float r;
@@ -58,8 +59,8 @@ __device__ __forceinline__ void mfma_dual16(const float* __restrict__ XA, const 
 #undef GN_MQ
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-        if (DO_A) OA[oo + r * TS] = sigmoid_f(a0[r] + a1[r]);
-        if (DO_B) OB[oo + r * TS] = sigmoid_f(c0[r] + c1[r]);
+        if (DO_A) OA[oo + r * TS] = gn_sigmoid(a0[r] + a1[r]);
+        if (DO_B) OB[oo + r * TS] = gn_sigmoid(c0[r] + c1[r]);
     }
 }
 
