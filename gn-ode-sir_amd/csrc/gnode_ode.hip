@@ -442,8 +442,8 @@ __global__ __launch_bounds__(256) void k_fill_bg(float* __restrict__ sol, size_t
 
 // --------------------------------------------------------------------------- host side
 static int check_H(int H) {
-    if (H < 4 || H > 256 || (H % 4) != 0) {
-        gnode_set_error("unsupported hidden size H=%d (need 4 <= H <= 256, H %% 4 == 0)", H);
+    if (H < 4 || H > 128 || (H % 4) != 0) {
+        gnode_set_error("unsupported hidden size H=%d (need 4 <= H <= 128, H %% 4 == 0)", H);
         return GNODE_ERR_ARG;
     }
     return 0;
@@ -642,7 +642,7 @@ extern "C" int gnode_graph_info(gnode_graph_t g, int32_t* n, int64_t* nnz, int32
 
 // --------------------------------------------------------------------------- RHS
 extern "C" size_t gnode_rhs_workspace_bytes(gnode_graph_t g, int64_t rows, int32_t H) {
-    if (!g || rows <= 0 || H <= 0) return 0;
+    if (!g || rows <= 0 || H < 4 || H > 128 || H % 4) return 0;
     return gn_align((size_t)2 * rows * H * sizeof(float)) + gn_hub_scratch_bytes(g, rows / g->n, H, 1);
 }
 
@@ -706,7 +706,7 @@ static FwdLayout forward_layout(int64_t rows, int32_t H, int32_t method) {
 }
 
 extern "C" size_t gnode_forward_workspace_bytes(gnode_graph_t g, int64_t rows, int32_t H, int32_t method) {
-    if (!g || rows <= 0 || H <= 0) return 0;
+    if (!g || rows <= 0 || H < 4 || H > 128 || H % 4) return 0;
     return forward_layout(rows, H, method).fixed + gn_hub_scratch_bytes(g, rows / g->n, H, 1);
 }
 

@@ -85,6 +85,7 @@ int gnode_graph_info(gnode_graph_t g, int32_t* n, int64_t* nnz, int32_t* max_deg
 /* ---- RHS -----------------------------------------------------------------
  * ODEfunc.forward(t, x): ode_nn_ngraph_sim.py:58-96 (multi: ode_nn_ngraphs.py:54-83).
  * x, dx: device [4*rows, H], slabs S | I | R | beta-gamma (col 0 beta, col 1 gamma).
+ * 4 <= H <= 128, H % 4 == 0 (else GNODE_ERR_ARG, and the workspace size is 0).
  * workspace: device, >= gnode_rhs_workspace_bytes(g, rows, H) (the size depends on the
  * graph: long rows are summed through scratch carved from the workspace). */
 size_t gnode_rhs_workspace_bytes(gnode_graph_t g, int64_t rows, int32_t H);
@@ -95,7 +96,8 @@ int gnode_rhs_f32(gnode_graph_t g, const float* x, const float* W, const float* 
  * ODEBlock.forward(x): ode_nn_ngraph_sim.py:148-188 (multi: ode_nn_ngraphs.py:124-152)
  * = encoder + odeint(method='euler' | 'rk4') over the grid + read-out + softmax,
  * optionally fused with get_sir_t_nodes_torch (ode_nn.py:249-261).
- *   x          device [rows, 3+H]
+ *   x          device [rows, 3+H]; 4 <= H <= 128, H % 4 == 0 (else GNODE_ERR_ARG, and the
+ *              workspace size is 0)
  *   dt_host    host  [n_steps] fp32 step sizes t[k+1]-t[k] (grid has n_steps+1 points)
  *   method     0 = euler, 1 = rk4 (torchdiffeq's 3/8 rule)
  *   out_rows_host  host [n_out] ascending grid indices to emit, or NULL = all

@@ -283,6 +283,49 @@ def test_backward_full_size_properties(dev):
         assert float((rs[k] - (r1[k] + r2[k])).abs().max()) <= 2e-4 * scale, k  # additivity, fp32 sums over 75k rows x 6 points
 
 
+@pytest.mark.parametrize("sub", [True, False], ids=["subsampled", "full"])
+def test_backward_full_size_vs_float64(sub, dev):
+    """bench.py's training shape (75k nodes x 2, H = 64, 5 intervals) against the float64 checker: one launch per interval
+    over the kept activations -- with the subsampled grid the last grid point emits nothing and its interval is skipped
+    (skip_last) -- and the recomputing sweep.  One oracle run serves both."""
+    import torch
+    import gnode_oracle as O
+    from gnode import ops
+    from gnode.graph import DeviceGraph
+    n, m, B, H, maxTime, deltaT = 75000, 500000, 2, 64, 3, 0.5
+    rp, ci, _ = O.er_graph(n, m, seed=0)
+    P = O.init_params(H, seed=0)
+    x = O.make_samples(n, B, H, seed=4)
+    grid = O.time_grid(maxTime, deltaT)
+    out_rows = ops.subsample_rows(maxTime, deltaT) if sub else None
+    n_out = len(grid) if out_rows is None else len(out_rows)
+    rng = np.random.default_rng(0)
+    gs = [rng.normal(size=(n_out, B * n)).astype(np.float32) for _ in range(3)]
+    want = O.adjoint_grads_torch(x, P, rp, ci, maxTime, deltaT, *gs, out_rows=out_rows, dtype="float64")
+    g = DeviceGraph(rp, ci)
+    params = {k: torch.from_numpy(v).to(dev) for k, v in P.items()}
+    x2d = torch.from_numpy(x).to(dev).reshape(B * n, 3 + H)
+    dts = ops.step_sizes(grid)
+    gst = [torch.from_numpy(a).to(dev) for a in gs]
+    _, _, _, sol = ops.forward(g, x2d, params, dts, "euler", out_rows, want_sol=True, want_keep=True)
+    assert sol.gnode_keep is not None
+    variants = {"kept": ops.backward(g, x2d, params, dts, "euler", out_rows, sol, *gst)}
+    del sol
+    _, _, _, sol = ops.forward(g, x2d, params, dts, "euler", out_rows, want_sol=True, want_keep=False)
+    variants["recomputed"] = ops.backward(g, x2d, params, dts, "euler", out_rows, sol, *gst)
+    scale = max(float(np.abs(w).max()) for w in want.values())
+    for name, got in variants.items():
+        for k in want:
+            if k == "linearS2.bias":                            # exact gradient 0 (softmax shift invariance)
+                assert abs(float(got[k].cpu())) <= 1e-4 * max(1.0, float(np.abs(want["linearS2.weight"]).max()))
+                continue
+            peak = float(np.abs(want[k]).max())
+            assert peak > 1e-3 * scale, f"{k}: degenerate in this case"     # the checked gradient is not ~0
+            err = float(np.max(np.abs(got[k].cpu().numpy().astype(np.float64) - want[k]))) / (max(peak, 1e-3 * scale) + 1e-30)
+            print(f"[headline sub={sub}] {name} {k}: rel err {err:.2e}")
+            assert err <= 2e-4, f"{name} {k}: rel err {err:.2e}"
+
+
 def test_kept_activations_are_the_forwards_and_optional(dev):
     """The `keep` buffer of gnode_forward_f32 (include/gnode.h): outputs and trajectory do not depend on whether it is given;
     its tables ARE sigmoid(W y_k + b) of the trajectory's S / I rows (checked against torch on the saved rows); and the
