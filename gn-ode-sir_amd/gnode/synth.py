@@ -25,8 +25,9 @@ def er_csr(n: int, m: int, seed: int = 0):
 
 
 def heavy_tail_csr(n: int, m: int, exponent: float = 0.5, seed: int = 0):
-    """A graph with the degree tail of the reference's real datasets (fb-social's longest row ~700 of 1 893 nodes,
-    wiki-vote's ~1 065 of 7 066: SURVEY section 7): m distinct undirected edges whose endpoints are drawn with probability
+    """A graph with a long degree tail like the reference's real datasets' (their largest components: fb-social's longest
+    row is 255 of 1 893 nodes with 30 rows above 96 edges, wiki-vote's 1 065 of 7 066 with 568; exponent 0.8 at fb-social's
+    counts gives a longer tail than fb-social's own, ~700): m distinct undirected edges whose endpoints are drawn with probability
     ~ (rank + 1)^-exponent (Chung-Lu), no self-loops; the big nodes come first, as in many real node numberings.
     Symmetrised CSR int32 with sorted columns -> (rowptr, col)."""
     rng = np.random.default_rng(seed)

@@ -20,9 +20,11 @@ Pinning status (see DESIGN.md "Oracle"):
     from torch's CPU generator, ode_nn.py:65,70); it is the spec for the
     production Monte-Carlo kernel and is checked statistically against
     ``sir_coins``.
-  * The reference's shipped label pickles (multi-graph-1/.../karate-*.pkl) and
-    graph pickles (real_graphs/*.pkl) are NOT used: the only loaders that
-    execute nothing (numpy.load(allow_pickle=False)) refuse them.
+  * The reference's shipped label pickles (multi-graph-1/.../karate-*.pkl) are
+    NOT used: the only loaders that execute nothing (numpy.load(allow_pickle=False))
+    refuse them.  Its graph pickles (real_graphs/*.pkl) are read only by the
+    fixture generator tests/golden/make_golden_realgraphs.py in the build
+    container; the tests read the CSR it committed (tests/golden/real_graphs.npz).
 
 All citations are file:line into the reference repository.
 """
@@ -507,7 +509,7 @@ def make_samples(n, B, H, seed=0, n_seeds=2):
 
 
 # --------------------------------------------------------------------------- adjoint backward (A7)
-def adjoint_grads_torch(x, P, rowptr, col, maxTime, deltaT, gS, gI, gR, out_rows=None, dtype="float32"):
+def adjoint_grads_torch(x, P, rowptr, col, maxTime, deltaT, gS, gI, gR, out_rows=None, dtype="float32", stop_at=1):
     """Parameter gradients of  L = <gS,S> + <gI,I> + <gR,R>  as torchdiffeq 0.2.2's
     ``odeint_adjoint(..., method='euler')`` produces them -- PARITY
     UNPINNED (third-party, absent); restated here with torch autograd supplying every
@@ -520,6 +522,8 @@ def adjoint_grads_torch(x, P, rowptr, col, maxTime, deltaT, gS, gI, gR, out_rows
       at the RIGHT endpoint y_i, then y is reset to the stored sol[i-1]);  a_0 flows into
       the encoder.  The head (Linear(H,4), relu, Linear(4,1), softmax) is ordinary autograd
       on ``sol``.   x [B,n,3+H]; gS,gI,gR [n_out, B*n].  Returns {state_dict key: grad}.
+      beta, gamma are read per row, so a multi-graph batch is x[None] over its concatenated CSR (adjoint_grads_multi).
+      stop_at > 1 ends the sweep early (intervals below stop_at are skipped): a deliberately wrong rule for sensitivity checks.
     """
     import torch
     dt_t = getattr(torch, dtype)
@@ -567,7 +571,7 @@ def adjoint_grads_torch(x, P, rowptr, col, maxTime, deltaT, gS, gI, gR, out_rows
     grads = {k: g for k, g in zip(head, gr[1:])}
     a = gsol[-1].clone()
     gW, gb = torch.zeros_like(W), torch.zeros_like(b)
-    for i in range(sol.shape[0] - 1, 0, -1):
+    for i in range(sol.shape[0] - 1, stop_at - 1, -1):
         yi = sol[i].clone().requires_grad_(True)
         f = func(yi, W, b)
         vy, vW, vb = torch.autograd.grad(f, (yi, W, b), a)
@@ -579,6 +583,16 @@ def adjoint_grads_torch(x, P, rowptr, col, maxTime, deltaT, gS, gI, gR, out_rows
     ge = torch.autograd.grad(y0, [Pt["linearS1.weight"], Pt["linearS1.bias"]], a)
     grads["linearS1.weight"], grads["linearS1.bias"] = ge
     return {k: v.detach().numpy() for k, v in grads.items()}
+
+
+def adjoint_grads_multi(x, P, graphs, maxTime, deltaT, gS, gI, gR, out_rows=None, dtype="float32", stop_at=1):
+    """adjoint_grads_torch for the multi-graph script (ode_nn_ngraphs.py:124-152, 198-224): x [sumN, 3+H] with the
+    graph markers in column 5 (:333), graphs a list of (rowptr, col); the batch runs over the block-diagonal CSR its
+    markers name (concat_csr), beta and gamma per sample.  gS, gI, gR [n_out, sumN]."""
+    x = np.asarray(x)
+    rp, ci, off = concat_csr(graphs, picks_from_marker(x[:, 3 + 2]))
+    assert off[-1] == x.shape[0], "marker/graph sizes do not tile the batch"
+    return adjoint_grads_torch(x[None], P, rp, ci, maxTime, deltaT, gS, gI, gR, out_rows=out_rows, dtype=dtype, stop_at=stop_at)
 
 
 def chung_lu_graph(n, m, exponent=0.8, seed=0):

@@ -20,7 +20,8 @@ def _setup(n, m, B, seed, dev, tail=0.0):
     import torch
     from gnode import ops, synth
     from gnode.graph import DeviceGraph
-    # tail > 0: Chung-Lu degrees with the reference datasets' tails (hub rows: longest ~740 at fb-social size, ~1 020 at wiki-vote size)
+    # tail > 0: Chung-Lu degrees with long hub rows (longest ~740 at fb-social size, ~1 020 at wiki-vote size; the real graphs' longest
+    # rows are 255 in fb-social, 1 065 in wiki-vote: test_gpu_real_graphs.py runs those)
     rp, ci = synth.heavy_tail_csr(n, m, tail, seed=seed) if tail else synth.er_csr(n, m, seed=seed)
     g = DeviceGraph(rp, ci)
     P = {k: torch.from_numpy(v).to(dev) for k, v in synth.linear_params(64, seed=seed + 1).items()}
