@@ -30,9 +30,9 @@ int gn_launch_tiny_bwd64(const gnode_graph_s* g, long rows, const float* x, cons
 // head backward at one grid point: a[3 slabs] += its VJP, linear3 / linearS2 partials into slots of PartLayout{H}
 int gn_launch_head_bwd(long rows, int H, const float* Ysol, const float* gS, const float* gI, const float* gR,
                        const gnode_params* p, float* a, float* part, int* slots_used, hipStream_t st);
-// encoder backward on a_0: linearS1 partials
+// encoder backward on a_0: linearS1 partials; with gx, also dL/d(S0, I0, R0) into its columns 0-2 (w1 = linearS1.weight)
 int gn_launch_enc_bwd(long rows, int H, const float* a, const float* sol0, const float* x, float* part, int* slots_used,
-                      hipStream_t st);
+                      hipStream_t st, float* gx = nullptr, const float* w1 = nullptr);
 // fixed-order sum of slots [0, nwg) of PartLayout{H} into the 8 gradients (overwritten)
 int gn_launch_reduce_all(const float* part, int nwg, int H, const gnode_params* grads, hipStream_t st);
 // the same for slots of [H*H gW | H gb] into dW, db

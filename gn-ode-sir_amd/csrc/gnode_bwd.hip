@@ -133,13 +133,15 @@ __global__ __launch_bounds__(256) void k_bwd_q(const float* __restrict__ a, cons
 }
 
 // --------------------------------------------------------------------------- gathers + dpre
-template <int LPR>
+// WANT_BG: also accumulate dt * (d/dbeta, d/dgamma) of each row into gx columns 3, 4 (gnode_backward_dx_f32)
+template <int LPR, bool WANT_BG = false>
 __global__ __launch_bounds__(256) void k_bwd_gather(const int* __restrict__ rowptr, const int* __restrict__ col, int n,
                                                     long rows, int H, const float* __restrict__ a,
                                                     const float* __restrict__ Z, const float* __restrict__ q,
                                                     const float* __restrict__ beta, const float* __restrict__ gamma,
                                                     float* __restrict__ dpre, const int* __restrict__ hubidx,
-                                                    const float* __restrict__ AIhub, const float* __restrict__ GQhub, int n_hub) {
+                                                    const float* __restrict__ AIhub, const float* __restrict__ GQhub, int n_hub,
+                                                    float* __restrict__ gx, float dt) {
     const int sub = threadIdx.x % LPR;
     const int node = blockIdx.x * (256 / LPR) + threadIdx.x / LPR;
     if (node >= n) return;
@@ -155,14 +157,30 @@ __global__ __launch_bounds__(256) void k_bwd_gather(const int* __restrict__ rowp
     }
     const int start = hub >= 0 ? 0 : rowptr[node], end = hub >= 0 ? 0 : rowptr[node + 1];
     gn_gather2<4>(col, start, end, ZI + (size_t)base * H, q + (size_t)base * H, H, sub, active, ai, gq);
-    if (!active) return;
-    const float bt = beta[r], gm = gamma[r];
-    const float4 aS = ld4(a + off), aI = ld4(a + slab + off), aR = ld4(a + 2 * slab + off);
-    const float4 zs = ld4(Z + off), zi = ld4(ZI + off);
-    float4 dS, dI;
-    gn_dpre_row(bt, gm, aS, aI, aR, ai, gq, zs, zi, dS, dI);
-    st4(dpre + off, dS);
-    st4(dpre + slab + off, dI);
+    if constexpr (!WANT_BG) {
+        if (!active) return;
+        const float bt = beta[r], gm = gamma[r];
+        const float4 aS = ld4(a + off), aI = ld4(a + slab + off), aR = ld4(a + 2 * slab + off);
+        const float4 zs = ld4(Z + off), zi = ld4(ZI + off);
+        float4 dS, dI;
+        gn_dpre_row(bt, gm, aS, aI, aR, ai, gq, zs, zi, dS, dI);
+        st4(dpre + off, dS);
+        st4(dpre + slab + off, dI);
+    } else {
+        // the same, with the idle lanes of the group (H/4 not a power of two) kept for the row sums: they add zeros
+        float4 aS = zero4(), aI = zero4(), aR = zero4(), zs = zero4(), zi = zero4();
+        if (active) {
+            const float bt = beta[r], gm = gamma[r];
+            aS = ld4(a + off); aI = ld4(a + slab + off); aR = ld4(a + 2 * slab + off);
+            zs = ld4(Z + off); zi = ld4(ZI + off);
+            float4 dS, dI;
+            gn_dpre_row(bt, gm, aS, aI, aR, ai, gq, zs, zi, dS, dI);
+            st4(dpre + off, dS);
+            st4(dpre + slab + off, dI);
+        }
+        const float2 c = gn_bg_row<XorSum<LPR>>(aS, aI, aR, ai, zs, zi);
+        if (sub == 0) gn_bg_accumulate(gx, (size_t)r, H, dt, c);
+    }
 }
 
 // --------------------------------------------------------------------------- a += dt dpre W ; partial gW, gb
@@ -367,7 +385,8 @@ __device__ __forceinline__ float4 gather1_row64(const int* __restrict__ rowptr, 
 static_assert(GN_BWD_RPG1_OCC * 256 <= BWD_NWG, "fused backward grid exceeds the partial-gradient slots");
 // GATHER_AI: gather A Z_I as well (the last grid point, and trajectories whose 4th slabs do not carry it); otherwise the
 // row's A Z_I(y_i) is read back from `AIsaved` (the forward kept it) and only A q is gathered: one table instead of two.
-template <int OCC, int RPG, bool GATHER_AI>
+// WANT_BG: also accumulate the beta-gamma slab's adjoint into gx columns 3, 4 (gnode_backward_dx_f32).
+template <int OCC, int RPG, bool GATHER_AI, bool WANT_BG = false>
 __global__ __launch_bounds__(256, OCC) void k_bwd_fused64(const int* __restrict__ rowptr, const int* __restrict__ col, int n,
                                                      long rows, int tiles_per_sample, long total_tiles,
                                                      const float* __restrict__ ZIc, const float* __restrict__ Qc,
@@ -383,7 +402,7 @@ __global__ __launch_bounds__(256, OCC) void k_bwd_fused64(const int* __restrict_
                                                      const float* __restrict__ w2, const float* __restrict__ b2,
                                                      const int* __restrict__ hubidx, const float* __restrict__ AIhub,
                                                      const float* __restrict__ GQhub, int n_hub, int do_next,
-                                                     const float* __restrict__ AIsaved) {
+                                                     const float* __restrict__ AIsaved, float* __restrict__ gx) {
     __shared__ __attribute__((aligned(16))) float Wl[64 * TS];
     constexpr int TR = 16 * RPG;                   // rows per tile (RPG rows per 16-lane group)
     __shared__ __attribute__((aligned(16))) float tiles[4][TR * TS];
@@ -465,6 +484,13 @@ __global__ __launch_bounds__(256, OCC) void k_bwd_fused64(const int* __restrict_
                 const float4 zi = *reinterpret_cast<const float4*>(&Dt[1][lr[p] * TS + 4 * sub]);
                 const float gm = gmv[p];
                 gn_dpre_row(bt[p], gm, aS[p], aI[p], aR[p], ai[p], gq[p], zs, zi, dS, dI);
+            }
+            if constexpr (WANT_BG) {
+                // a, AI and Z of the row before its update (padding rows: a = 0 adds 0); the 16 lanes sum in one DPP row
+                const float4 zs = *reinterpret_cast<const float4*>(&Dt[0][lr[p] * TS + 4 * sub]);
+                const float4 zi = *reinterpret_cast<const float4*>(&Dt[1][lr[p] * TS + 4 * sub]);
+                const float2 c = gn_bg_row<DppSum16>(aS[p], aI[p], aR[p], ai[p], zs, zi);
+                if (valid[p] && sub == 0) gn_bg_accumulate(gx, (size_t)(base + tile * TR + lr[p]), 64, dt, c);
             }
             *reinterpret_cast<float4*>(&Dt[0][lr[p] * TS + 4 * sub]) = dS;      // own row only: read above, rewritten here
             *reinterpret_cast<float4*>(&Dt[1][lr[p] * TS + 4 * sub]) = dI;
@@ -836,7 +862,8 @@ __device__ __forceinline__ float4 group_lin(float4 x, const float* __restrict__ 
     return acc;
 }
 
-template <int LPR>
+// WANT_BG: also accumulate dt * (d/dbeta, d/dgamma) of each row into gx columns 3, 4 (gnode_backward_dx_f32)
+template <int LPR, bool WANT_BG = false>
 __global__ __launch_bounds__(256) void k_bwd_fused_generic(
     const int* __restrict__ rowptr, const int* __restrict__ col, int n, long rows, int H, float* __restrict__ ZS,
     const float* __restrict__ ZIc, const float* __restrict__ Qc, float* __restrict__ ZIn, float* __restrict__ Qn,
@@ -846,7 +873,8 @@ __global__ __launch_bounds__(256) void k_bwd_fused_generic(
     const float* __restrict__ gR, const float* __restrict__ w3, const float* __restrict__ b3, const float* __restrict__ w2,
     const float* __restrict__ b2, const int* __restrict__ hubidx,
     const float* __restrict__ HubP0 /* hub rows: per-segment partial sums of A Z_I, [B][n_seg][H] */,
-    const float* __restrict__ HubP1 /* ... of A q */, const int* __restrict__ hub_seg_ptr, int n_seg, int do_next) {
+    const float* __restrict__ HubP1 /* ... of A q */, const int* __restrict__ hub_seg_ptr, int n_seg, int do_next,
+    float* __restrict__ gx) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     constexpr int G = 256 / LPR;
     const PartLayout L{H};
@@ -930,6 +958,11 @@ __global__ __launch_bounds__(256) void k_bwd_fused_generic(
             GN_DPRE(x) GN_DPRE(y) GN_DPRE(z) GN_DPRE(w)
 #undef GN_DPRE
         }
+        if constexpr (WANT_BG) {
+            // rows beyond the end and idle lanes hold zeros and add 0; a 16-lane group sums in one DPP row, as the head does
+            const float2 c = gn_bg_row<std::conditional_t<LPR == 16, DppSum16, XorSum<LPR>>>(aS, aI, aR, ai, zs0, zi0);
+            if (inrow && sub == 0) gn_bg_accumulate(gx, (size_t)r, H, dt, c);
+        }
         __syncthreads();                       // previous tile's gW pass is done with the tiles (also covers the W stage)
         if (lane_ok) {
             st4(Dt + (size_t)grp * H + 4 * sub, dS);       st4(Dt + ((size_t)G + grp) * H + 4 * sub, dI);
@@ -1012,10 +1045,12 @@ __global__ __launch_bounds__(256) void k_bwd_fused_generic(
 }
 
 // --------------------------------------------------------------------------- encoder backward
-template <int LPR>
+// WANT_X: also write dL/dS0, dL/dI0, dL/dR0 = sum_h (relu-masked a_X(t0)) linearS1.weight into gx columns 0, 1, 2
+template <int LPR, bool WANT_X = false>
 __global__ __launch_bounds__(256) void k_enc_bwd(const float* __restrict__ a, const float* __restrict__ sol0,
                                                  const float* __restrict__ x, long rows, int H,
-                                                 float* __restrict__ part_all) {
+                                                 float* __restrict__ part_all, float* __restrict__ gx,
+                                                 const float* __restrict__ w1) {
     extern __shared__ float red[];                       // [G][2H]
     constexpr int G = 256 / LPR;
     const PartLayout L{H};
@@ -1023,17 +1058,24 @@ __global__ __launch_bounds__(256) void k_enc_bwd(const float* __restrict__ a, co
     const bool active = 4 * sub < H;
     const size_t slab = (size_t)rows * H;
     float4 dw = zero4(), db = zero4();
+    const float4 w1v = (WANT_X && active) ? ld4(w1 + 4 * sub) : zero4();
     for (long r = (long)blockIdx.x * G + grp; r < rows; r += (long)gridDim.x * G) {
-        if (!active) continue;
+        if (!WANT_X && !active) continue;
         const size_t off = (size_t)r * H + 4 * sub;
 #pragma unroll
         for (int X = 0; X < 3; ++X) {
-            const float s = x[(size_t)r * (3 + H) + X];
-            const float4 y = ld4(sol0 + X * slab + off), av = ld4(a + X * slab + off);
-            const float4 mk = make_float4(y.x > 0.f ? av.x : 0.f, y.y > 0.f ? av.y : 0.f, y.z > 0.f ? av.z : 0.f,
-                                          y.w > 0.f ? av.w : 0.f);
-            dw.x = fmaf(mk.x, s, dw.x); dw.y = fmaf(mk.y, s, dw.y); dw.z = fmaf(mk.z, s, dw.z); dw.w = fmaf(mk.w, s, dw.w);
-            db.x += mk.x; db.y += mk.y; db.z += mk.z; db.w += mk.w;
+            float4 mk = zero4();
+            if (!WANT_X || active) {
+                const float s = x[(size_t)r * (3 + H) + X];
+                const float4 y = ld4(sol0 + X * slab + off), av = ld4(a + X * slab + off);
+                mk = make_float4(y.x > 0.f ? av.x : 0.f, y.y > 0.f ? av.y : 0.f, y.z > 0.f ? av.z : 0.f, y.w > 0.f ? av.w : 0.f);
+                dw.x = fmaf(mk.x, s, dw.x); dw.y = fmaf(mk.y, s, dw.y); dw.z = fmaf(mk.z, s, dw.z); dw.w = fmaf(mk.w, s, dw.w);
+                db.x += mk.x; db.y += mk.y; db.z += mk.z; db.w += mk.w;
+            }
+            if constexpr (WANT_X) {
+                const float gx0 = group_sum<LPR>(dot4(mk, w1v));      // idle lanes add 0
+                if (sub == 0) gx[(size_t)r * (3 + H) + X] = gx0;
+            }
         }
     }
     float* mine = red + (size_t)grp * 2 * H;
@@ -1125,15 +1167,18 @@ struct BwdPlan {
     PersgPlan persg;
 };
 
+// want_x (an input gradient is asked for, keep is then null): only the recomputing one-launch-per-interval forms, which
+// have a, A Z_I and Z of every row at hand -- k_bwd_fused64 (H = 64), k_bwd_fused_generic (H <= 32), the generic path
+// (k_bwd_gather) -- never the one-launch sweeps (k_tiny_bwd64, k_persg_bwd) nor the kept / persistent H = 64 sweeps.
 static BwdPlan backward_plan(gnode_graph_s* g, long rows, int H, int n_steps, int n_emit, const int* slot, const float* keep,
-                             int sol_info, int flags) {
+                             int sol_info, int flags, bool want_x = false) {
     const int G = n_steps + 1;
-    const bool persist_ok = !(flags & GNODE_FWD_PER_STEP);
+    const bool persist_ok = !(flags & GNODE_FWD_PER_STEP) && !want_x;
     BwdPlan pl{};
     // what the forward that produced `sol` / `keep` was (its sol_info says so; unchecked callers: the same question, same flags)
     pl.fwd_tiny = sol_info >= 0 ? (sol_info & GNODE_SOL_TINY) != 0
                                 : gn_forward_plan(g, rows, H, 0, n_steps, n_emit, true, flags).path == FwdPath::tiny;
-    if (pl.fwd_tiny && gn_tiny_bwd64_ok(g, rows, H, n_steps)) {
+    if (pl.fwd_tiny && !want_x && gn_tiny_bwd64_ok(g, rows, H, n_steps)) {
         pl.path = BwdPath::tiny;
     } else if (H == 64 && n_steps >= 1) {
         pl.path = BwdPath::h64;
@@ -1174,6 +1219,7 @@ struct BwdCall {
     float *a, *Z, *q, *dpre, *beta, *gamma, *part; char* ctl; void* hub_scratch;   // workspace (backward_layout)
     hipStream_t st;
     int slots_used;                  // highest workgroup slot any launch wrote, for the final reduction
+    float* gx;                       // the input gradient [rows, 3+H] (gnode_backward_dx_f32), or null
     const float* point(int gi) const { return sol + (size_t)gi * 4 * slab; }   // trajectory point gi
     // grid point gi's row of an upstream gradient (gS, gI or gR), or null when gi is not emitted
     const float* up(const float* U, int gi) const { return slot[gi] >= 0 ? U + (size_t)slot[gi] * rows : nullptr; }
@@ -1275,12 +1321,13 @@ static int backward64_interval(BwdCall& c, const BwdPlan& pl, int i) {
                            gSs, c.up(c.gI, i - 1), c.up(c.gR, i - 1), p->linear3_weight, p->linear3_bias, p->linearS2_weight,
                            p->linearS2_bias, g->hubidx, HubP, g->hub_seg_ptr, g->n_seg, i > 1 ? 1 : 0);
     } else {
-        auto fused_kernel = two ? k_bwd_fused64<GN_BWD_RPG1_OCC, 1, true> : k_bwd_fused64<GN_BWD_RPG1_OCC, 1, false>;
+        auto fused_kernel = c.gx ? (two ? k_bwd_fused64<GN_BWD_RPG1_OCC, 1, true, true> : k_bwd_fused64<GN_BWD_RPG1_OCC, 1, false, true>)
+                                 : (two ? k_bwd_fused64<GN_BWD_RPG1_OCC, 1, true> : k_bwd_fused64<GN_BWD_RPG1_OCC, 1, false>);
         hipLaunchKernelGGL(fused_kernel, dim3(grid), dim3(256), 0, c.st, g->rowptr, g->col, g->n, rows, tps, total, T.ZIb[cur],
                            T.Qb[cur], ai_saved ? nullptr : T.ZIb[cur ^ 1], T.Qb[cur ^ 1], c.point(i), c.point(i - 1),
                            p->odefunc_linear_weight, p->odefunc_linear_bias, c.beta, c.gamma, c.dt_host[i - 1], c.a, c.part, gSs,
                            c.up(c.gI, i - 1), c.up(c.gR, i - 1), p->linear3_weight, p->linear3_bias, p->linearS2_weight,
-                           p->linearS2_bias, g->hubidx, AIhub, GQhub, g->n_hub, i > 1 ? 1 : 0, c.point(i) + 3 * c.slab);
+                           p->linearS2_bias, g->hubidx, AIhub, GQhub, g->n_hub, i > 1 ? 1 : 0, c.point(i) + 3 * c.slab, c.gx);
     }
     if (sampled) gn_prof_end(2, c.st);
     GN_LAUNCH_CHECK();
@@ -1361,12 +1408,17 @@ static int backward_small_h(BwdCall& c, const BwdPlan& pl) {
         const float *HubP0 = nullptr, *HubP1 = nullptr;        // segment partials; the interval kernel adds them up itself
         if (int e = gn_hub_segments2(g, rows / g->n, H, ZIb[cur], Qb[cur], c.hub_scratch, &HubP0, &HubP1, c.st)) return e;
         const bool sampled = gn_prof_begin(2, c.st);
-        GN_LPR_DISPATCH(32, lpr, hipLaunchKernelGGL(k_bwd_fused_generic<LPR>, dim3(grid), dim3(256), fl * sizeof(float), c.st, g->rowptr,
-                                                    g->col, g->n, rows, H, c.Z, ZIb[cur], Qb[cur], ZIb[cur ^ 1], Qb[cur ^ 1], c.point(i),
-                                                    c.point(i - 1), p->odefunc_linear_weight, p->odefunc_linear_bias, c.beta, c.gamma,
-                                                    c.dt_host[i - 1], c.a, c.part, c.up(c.gS, i - 1), c.up(c.gI, i - 1),
-                                                    c.up(c.gR, i - 1), p->linear3_weight, p->linear3_bias, p->linearS2_weight,
-                                                    p->linearS2_bias, g->hubidx, HubP0, HubP1, g->hub_seg_ptr, g->n_seg, i > 1 ? 1 : 0));
+#define GN_FUSED_GENERIC(BG)                                                                                                        \
+        GN_LPR_DISPATCH(32, lpr, hipLaunchKernelGGL((k_bwd_fused_generic<LPR, BG>), dim3(grid), dim3(256), fl * sizeof(float), c.st,     \
+                                                    g->rowptr, g->col, g->n, rows, H, c.Z, ZIb[cur], Qb[cur], ZIb[cur ^ 1], Qb[cur ^ 1], \
+                                                    c.point(i), c.point(i - 1), p->odefunc_linear_weight, p->odefunc_linear_bias,       \
+                                                    c.beta, c.gamma, c.dt_host[i - 1], c.a, c.part, c.up(c.gS, i - 1),                 \
+                                                    c.up(c.gI, i - 1), c.up(c.gR, i - 1), p->linear3_weight, p->linear3_bias,          \
+                                                    p->linearS2_weight, p->linearS2_bias, g->hubidx, HubP0, HubP1, g->hub_seg_ptr,     \
+                                                    g->n_seg, i > 1 ? 1 : 0, c.gx))
+        if (c.gx) GN_FUSED_GENERIC(true)
+        else GN_FUSED_GENERIC(false)
+#undef GN_FUSED_GENERIC
         if (sampled) gn_prof_end(2, c.st);
         GN_LAUNCH_CHECK();
     }
@@ -1389,8 +1441,14 @@ static int backward_generic(BwdCall& c) {
         dim3 ggrid((unsigned)((g->n + rpw - 1) / rpw), (unsigned)(rows / g->n));
         const float *AIhub = nullptr, *GQhub = nullptr;
         if (int e = gn_hub_gather(g, rows / g->n, H, c.Z + c.slab, c.q, c.hub_scratch, &AIhub, &GQhub, c.st)) return e;
-        GN_LPR_DISPATCH(32, lpr, hipLaunchKernelGGL(k_bwd_gather<LPR>, ggrid, dim3(256), 0, c.st, g->rowptr, g->col, g->n, rows, H,
-                                                    c.a, c.Z, c.q, c.beta, c.gamma, c.dpre, g->hubidx, AIhub, GQhub, g->n_hub));
+        if (c.gx)
+            GN_LPR_DISPATCH(32, lpr, hipLaunchKernelGGL((k_bwd_gather<LPR, true>), ggrid, dim3(256), 0, c.st, g->rowptr, g->col, g->n, rows,
+                                                        H, c.a, c.Z, c.q, c.beta, c.gamma, c.dpre, g->hubidx, AIhub, GQhub, g->n_hub,
+                                                        c.gx, dt))
+        else
+            GN_LPR_DISPATCH(32, lpr, hipLaunchKernelGGL((k_bwd_gather<LPR, false>), ggrid, dim3(256), 0, c.st, g->rowptr, g->col, g->n, rows,
+                                                        H, c.a, c.Z, c.q, c.beta, c.gamma, c.dpre, g->hubidx, AIhub, GQhub, g->n_hub,
+                                                        nullptr, 0.f))
         GN_LAUNCH_CHECK();
         if (H == 128) {
             if (int e = gn_launch_bwd_mlp128(g, c.dpre, yi, p->odefunc_linear_weight, dt, c.a, rows, c.part, &c.slots_used, c.st)) return e;
@@ -1405,19 +1463,22 @@ static int backward_generic(BwdCall& c) {
     return 0;
 }
 
-extern "C" int gnode_backward_f32(gnode_graph_t g, const float* x, const gnode_params* p, const float* dt_host,
-                                  int32_t n_steps, const int32_t* out_rows_host, int32_t n_out, const float* sol,
-                                  const float* keep, size_t keep_bytes, const float* gS, const float* gI, const float* gR,
-                                  const gnode_params* grads, int64_t rows, int32_t H, void* workspace,
-                                  size_t workspace_bytes, void* stream, int32_t flags, int32_t sol_info) {
-    GN_CHECK_ARG(g && x && p && sol && gS && gI && gR && grads && workspace, "gnode_backward_f32: null pointer");
+extern "C" int gnode_backward_dx_f32(gnode_graph_t g, const float* x, const gnode_params* p, const float* dt_host,
+                                     int32_t n_steps, const int32_t* out_rows_host, int32_t n_out, const float* sol,
+                                     const float* keep, size_t keep_bytes, const float* gS, const float* gI, const float* gR,
+                                     const gnode_params* grads, int64_t rows, int32_t H, void* workspace,
+                                     size_t workspace_bytes, void* stream, int32_t flags, int32_t sol_info, float* gx) {
+    GN_CHECK_ARG(g && x && p && sol && gS && gI && gR && workspace, "gnode_backward_f32: null pointer");
+    GN_CHECK_ARG(grads || gx, "gnode_backward_dx_f32: neither grads nor gx requested");
+    GN_CHECK_ARG(!(gx && keep), "gnode_backward_dx_f32: a keep buffer cannot serve an input gradient (pass keep = NULL)");
+    GN_CHECK_ARG(!gx || p->linearS1_weight, "gnode_backward_dx_f32: null linearS1.weight");
     GN_CHECK_ARG(n_steps >= 0 && (n_steps == 0 || dt_host), "gnode_backward_f32: bad n_steps/dt");
     GN_CHECK_ARG(H >= 4 && H <= 128 && H % 4 == 0, "gnode_backward_f32: need 4 <= H <= 128, H %% 4 == 0 (got %d)", H);
     GN_CHECK_ARG(rows > 0 && rows % g->n == 0, "gnode_backward_f32: rows=%lld is not a multiple of graph n=%d",
                  (long long)rows, g->n);
-    GN_CHECK_ARG(grads->odefunc_linear_weight && grads->odefunc_linear_bias && grads->linearS1_weight &&
+    GN_CHECK_ARG(!grads || (grads->odefunc_linear_weight && grads->odefunc_linear_bias && grads->linearS1_weight &&
                      grads->linearS1_bias && grads->linear3_weight && grads->linear3_bias && grads->linearS2_weight &&
-                     grads->linearS2_bias, "gnode_backward_f32: null gradient pointer");
+                     grads->linearS2_bias), "gnode_backward_f32: null gradient pointer");
     if (workspace_bytes < gnode_backward_workspace_bytes(g, rows, H)) {
         gnode_set_error("gnode_backward_f32: workspace %zu < %zu", workspace_bytes, gnode_backward_workspace_bytes(g, rows, H));
         return GNODE_ERR_WORKSPACE;
@@ -1425,13 +1486,16 @@ extern "C" int gnode_backward_f32(gnode_graph_t g, const float* x, const gnode_p
     const int G = n_steps + 1, n_emit = out_rows_host ? n_out : G;
     if (int e = gn_check_out_rows("gnode_backward_f32", out_rows_host, n_out, G)) return e;
     const std::vector<int> slot = gn_out_slots(out_rows_host, n_out, G);
-    const BwdPlan pl = backward_plan(g, rows, H, n_steps, n_emit, slot.data(), keep, sol_info, flags);
+    const BwdPlan pl = backward_plan(g, rows, H, n_steps, n_emit, slot.data(), keep, sol_info, flags, gx != nullptr);
     const BwdLayout L = backward_layout(rows, H);
     char* ws = (char*)workspace;
     BwdCall c{g, p, dt_host, G, H, (long)rows, (size_t)rows * H, L.slab, sol, gS, gI, gR, slot.data(),
               (float*)(ws + L.a), (float*)(ws + L.Z), (float*)(ws + L.q), (float*)(ws + L.dpre), (float*)(ws + L.beta),
-              (float*)(ws + L.gamma), (float*)(ws + L.part), ws + L.ctl, ws + L.fixed, (hipStream_t)stream, 1};
+              (float*)(ws + L.gamma), (float*)(ws + L.part), ws + L.ctl, ws + L.fixed, (hipStream_t)stream, 1, gx};
     int e = 0;
+    // the interval kernels accumulate columns 3, 4 in place and the encoder writes 0-2: the rest stays 0
+    if (gx) e = gn_zero_async(gx, (size_t)rows * (3 + H) * sizeof(float), c.st);
+    if (e) return e;
     if (pl.path == BwdPath::tiny) {
         e = backward_tiny(c, x, out_rows_host, n_out, n_emit, keep, keep_bytes);
     } else {
@@ -1439,9 +1503,20 @@ extern "C" int gnode_backward_f32(gnode_graph_t g, const float* x, const gnode_p
         if (!e && pl.path == BwdPath::h64) e = backward_h64(c, pl, keep, keep_bytes, n_emit, sol_info);
         if (!e && pl.path == BwdPath::small_h) e = backward_small_h(c, pl);
         if (!e && pl.path == BwdPath::generic) e = backward_generic(c);
-        if (!e) e = gn_launch_enc_bwd(c.rows, H, c.a, sol, x, c.part, &c.slots_used, c.st);
+        if (!e) e = gn_launch_enc_bwd(c.rows, H, c.a, sol, x, c.part, &c.slots_used, c.st, gx, p->linearS1_weight);
     }
-    return e ? e : gn_launch_reduce_all(c.part, c.slots_used, H, grads, c.st);
+    if (e || !grads) return e;
+    return gn_launch_reduce_all(c.part, c.slots_used, H, grads, c.st);
+}
+
+extern "C" int gnode_backward_f32(gnode_graph_t g, const float* x, const gnode_params* p, const float* dt_host,
+                                  int32_t n_steps, const int32_t* out_rows_host, int32_t n_out, const float* sol,
+                                  const float* keep, size_t keep_bytes, const float* gS, const float* gI, const float* gR,
+                                  const gnode_params* grads, int64_t rows, int32_t H, void* workspace,
+                                  size_t workspace_bytes, void* stream, int32_t flags, int32_t sol_info) {
+    GN_CHECK_ARG(grads, "gnode_backward_f32: null pointer");
+    return gnode_backward_dx_f32(g, x, p, dt_host, n_steps, out_rows_host, n_out, sol, keep, keep_bytes, gS, gI, gR, grads, rows,
+                                 H, workspace, workspace_bytes, stream, flags, sol_info, nullptr);
 }
 
 // The persistent adjoint sweeps' give-up word (the control block at the end of the fixed part of the backward workspace).
@@ -1472,12 +1547,17 @@ int gn_launch_head_bwd(long rows, int H, const float* Ysol, const float* gS, con
 }
 
 int gn_launch_enc_bwd(long rows, int H, const float* a, const float* sol0, const float* x, float* part, int* slots_used,
-                      hipStream_t st) {
+                      hipStream_t st, float* gx, const float* w1) {
     const int lpr = gn_lpr(H), rpw = 256 / lpr;
     const size_t lds = (size_t)rpw * 2 * H * sizeof(float);
     const int egrid = (int)std::min<long>(BWD_NWG, std::max<long>(1, (rows + rpw - 1) / rpw));
     *slots_used = std::max(*slots_used, egrid);
-    GN_LPR_DISPATCH(32, lpr, hipLaunchKernelGGL(k_enc_bwd<LPR>, dim3(egrid), dim3(256), lds, st, a, sol0, x, rows, H, part));
+    if (gx)
+        GN_LPR_DISPATCH(32, lpr, hipLaunchKernelGGL((k_enc_bwd<LPR, true>), dim3(egrid), dim3(256), lds, st, a, sol0, x, rows, H, part,
+                                                    gx, w1))
+    else
+        GN_LPR_DISPATCH(32, lpr, hipLaunchKernelGGL((k_enc_bwd<LPR, false>), dim3(egrid), dim3(256), lds, st, a, sol0, x, rows, H, part,
+                                                    nullptr, nullptr))
     GN_LAUNCH_CHECK();
     return 0;
 }

@@ -54,9 +54,11 @@ struct VjpArgs {
     float* part;           // [grid][part_stride] gW at +0, gb at +H*H; or null
     int part_stride;
     float w;               // part += w * partial
+    float* gx;             // BGX instance: rows of 3+H floats, columns 3, 4 += w * (d/dbeta, d/dgamma)
 };
 
-template <int LPR, bool QUAD>
+// BGX: the beta-gamma column gradients are accumulated into A.gx (the RK4 adjoint's input gradient) instead of gybg
+template <int LPR, bool QUAD, bool BGX = false>
 __global__ __launch_bounds__(256) void k_rhs_vjp(VjpArgs A) {
     extern __shared__ float lds[];
     constexpr int G = 256 / LPR;
@@ -127,6 +129,10 @@ __global__ __launch_bounds__(256) void k_rhs_vjp(VjpArgs A) {
             c0 = group_sum<LPR>(c0);
             c1 = group_sum<LPR>(c1);
             if (ok) st4(A.gybg + off, sub == 0 ? make_float4(c0, c1, 0.f, 0.f) : zero4());
+        }
+        if constexpr (BGX) {
+            const float2 c = gn_bg_row<XorSum<LPR>>(vS, vI, vR, ai, zs, zi);       // idle lanes and rows hold zeros
+            if (row_ok && sub == 0) gn_bg_accumulate(A.gx, (size_t)r, H, A.w, c);
         }
         if (!mat) continue;
         float4 dS, dI;
@@ -281,6 +287,8 @@ static size_t vjp_lds_bytes(int H, bool gy) {
 int gn_rhs_vjp_set_attributes() {
     GN_HIP(hipFuncSetAttribute((const void*)k_rhs_vjp<32, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     GN_HIP(hipFuncSetAttribute((const void*)k_rhs_vjp<32, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    GN_HIP(hipFuncSetAttribute((const void*)k_rhs_vjp<32, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    GN_HIP(hipFuncSetAttribute((const void*)k_rhs_vjp<32, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     return 0;
 }
 
@@ -288,6 +296,7 @@ struct VjpOut {
     float* fSI = nullptr; float* fR = nullptr; float* f4 = nullptr;
     float* gySI = nullptr; float* gyR = nullptr; float* gybg = nullptr;
     float* part = nullptr; int part_stride = 0; float w = 1.f;
+    float* gx = nullptr;      // accumulate w * (d/dbeta, d/dgamma) into gx columns 3, 4 (rows of 3+H floats)
 };
 
 // f and the VJP of (vSI, vR) at (y = S | I slabs, bg): node MLP, q table, hub sums, pass 2.  Z: 2 slabs, q: 1 slab of
@@ -296,7 +305,7 @@ static int vjp_launch(const gnode_graph_s* g, long rows, int H, const float* y, 
                       const float* vR, const float* W, const float* b, float* Z, float* q, void* hub_scratch, const VjpOut& o,
                       hipStream_t st) {
     const bool need_q = o.gySI || o.part;
-    if (!(o.fSI || o.f4 || o.gySI || o.gyR || o.gybg || o.part)) return 0;
+    if (!(o.fSI || o.f4 || o.gySI || o.gyR || o.gybg || o.part || o.gx)) return 0;
     const size_t slab = (size_t)rows * H;
     if (int e = gn_launch_mlp_any(g, y, W, b, Z, 2 * rows, H, st)) return e;      // Z_S | Z_I (Z_R is dead work)
     if (need_q) {
@@ -312,11 +321,17 @@ static int vjp_launch(const gnode_graph_s* g, long rows, int H, const float* y, 
     A.y = y; A.bg = bg; A.Z = Z; A.q = qt; A.vSI = vSI; A.vR = vR; A.W = W;
     A.hubidx = g->hubidx; A.AIhub = AIhub; A.GQhub = GQhub; A.n_hub = g->n_hub;
     A.fSI = o.fSI; A.fR = o.fR; A.f4 = o.f4; A.gySI = o.gySI; A.gyR = o.gyR; A.gybg = o.gybg;
-    A.part = o.part; A.part_stride = o.part_stride; A.w = o.w;
+    A.part = o.part; A.part_stride = o.part_stride; A.w = o.w; A.gx = o.gx;
     const int lpr = gn_lpr(H);
     const size_t lds = vjp_lds_bytes(H, o.gySI != nullptr);
-    if (256 % H == 0) GN_LPR_DISPATCH(32, lpr, hipLaunchKernelGGL((k_rhs_vjp<LPR, true>), dim3(vjp_grid(rows, H)), dim3(256), lds, st, A))
-    else GN_LPR_DISPATCH(32, lpr, hipLaunchKernelGGL((k_rhs_vjp<LPR, false>), dim3(vjp_grid(rows, H)), dim3(256), lds, st, A))
+    const dim3 grid(vjp_grid(rows, H));
+    if (o.gx) {
+        if (256 % H == 0) GN_LPR_DISPATCH(32, lpr, hipLaunchKernelGGL((k_rhs_vjp<LPR, true, true>), grid, dim3(256), lds, st, A))
+        else GN_LPR_DISPATCH(32, lpr, hipLaunchKernelGGL((k_rhs_vjp<LPR, false, true>), grid, dim3(256), lds, st, A))
+    } else {
+        if (256 % H == 0) GN_LPR_DISPATCH(32, lpr, hipLaunchKernelGGL((k_rhs_vjp<LPR, true>), grid, dim3(256), lds, st, A))
+        else GN_LPR_DISPATCH(32, lpr, hipLaunchKernelGGL((k_rhs_vjp<LPR, false>), grid, dim3(256), lds, st, A))
+    }
     GN_LAUNCH_CHECK();
     return 0;
 }
@@ -389,11 +404,13 @@ extern "C" size_t gnode_backward_rk4_workspace_bytes(gnode_graph_t g, int64_t ro
     return rk4_fixed_bytes(rows, H) + gn_hub_scratch_bytes(g, rows / g->n, H, 2);
 }
 
-extern "C" int gnode_backward_rk4_f32(gnode_graph_t g, const float* x, const gnode_params* p, const float* dt_host,
-                                      int32_t n_steps, const int32_t* out_rows_host, int32_t n_out, const float* sol,
-                                      const float* gS, const float* gI, const float* gR, const gnode_params* grads,
-                                      int64_t rows, int32_t H, void* workspace, size_t workspace_bytes, void* stream) {
-    GN_CHECK_ARG(g && x && p && sol && gS && gI && gR && grads && workspace, "gnode_backward_rk4_f32: null pointer");
+extern "C" int gnode_backward_rk4_dx_f32(gnode_graph_t g, const float* x, const gnode_params* p, const float* dt_host,
+                                         int32_t n_steps, const int32_t* out_rows_host, int32_t n_out, const float* sol,
+                                         const float* gS, const float* gI, const float* gR, const gnode_params* grads,
+                                         int64_t rows, int32_t H, void* workspace, size_t workspace_bytes, void* stream,
+                                         float* gx) {
+    GN_CHECK_ARG(g && x && p && sol && gS && gI && gR && workspace, "gnode_backward_rk4_f32: null pointer");
+    GN_CHECK_ARG(grads || gx, "gnode_backward_rk4_dx_f32: neither grads nor gx requested");
     GN_CHECK_ARG(n_steps >= 0 && (n_steps == 0 || dt_host), "gnode_backward_rk4_f32: bad n_steps/dt");
     GN_CHECK_ARG(H >= 4 && H <= 128 && H % 4 == 0, "gnode_backward_rk4_f32: need 4 <= H <= 128, H %% 4 == 0 (got %d)", H);
     GN_CHECK_ARG(rows > 0 && rows % g->n == 0, "gnode_backward_rk4_f32: rows=%lld is not a multiple of graph n=%d",
@@ -401,9 +418,9 @@ extern "C" int gnode_backward_rk4_f32(gnode_graph_t g, const float* x, const gno
     GN_CHECK_ARG(p->odefunc_linear_weight && p->odefunc_linear_bias && p->linear3_weight && p->linear3_bias &&
                      p->linearS2_weight && p->linearS2_bias && p->linearS1_weight && p->linearS1_bias,
                  "gnode_backward_rk4_f32: null parameter pointer");
-    GN_CHECK_ARG(grads->odefunc_linear_weight && grads->odefunc_linear_bias && grads->linearS1_weight &&
+    GN_CHECK_ARG(!grads || (grads->odefunc_linear_weight && grads->odefunc_linear_bias && grads->linearS1_weight &&
                      grads->linearS1_bias && grads->linear3_weight && grads->linear3_bias && grads->linearS2_weight &&
-                     grads->linearS2_bias, "gnode_backward_rk4_f32: null gradient pointer");
+                     grads->linearS2_bias), "gnode_backward_rk4_f32: null gradient pointer");
     if (workspace_bytes < gnode_backward_rk4_workspace_bytes(g, rows, H)) {
         gnode_set_error("gnode_backward_rk4_f32: workspace %zu < %zu", workspace_bytes, gnode_backward_rk4_workspace_bytes(g, rows, H));
         return GNODE_ERR_WORKSPACE;
@@ -433,6 +450,9 @@ extern "C" int gnode_backward_rk4_f32(gnode_graph_t g, const float* x, const gno
         zr.p[1] = part; zr.bytes[1] = (size_t)BWD_NWG * L.total() * sizeof(float);
         if (int e = gn_zero_regions_async(zr, st)) return e;
     }
+    // the stage VJPs accumulate columns 3, 4 in place and the encoder writes 0-2: the rest stays 0
+    if (gx)
+        if (int e = gn_zero_async(gx, (size_t)rows * (3 + H) * sizeof(float), st)) return e;
     int slots_used = 1;
     auto head = [&](int gi) -> int {
         const int s = slot[gi];
@@ -456,6 +476,7 @@ extern "C" int gnode_backward_rk4_f32(gnode_graph_t g, const float* x, const gno
             if (s < 3) o.fSI = k[s];                  // k4 is never needed: y is reset to sol[i-1] after the step
             o.gySI = V[s];
             o.part = part; o.part_stride = L.total(); o.w = wts[s];
+            o.gx = gx;
             if (int e = vjp_launch(g, rows, H, s == 0 ? yi : ys, bg, s == 0 ? a : as, a + 2 * slab, W, bb, Z, q, hub_scratch,
                                    o, st))
                 return e;
@@ -466,6 +487,15 @@ extern "C" int gnode_backward_rk4_f32(gnode_graph_t g, const float* x, const gno
         slots_used = std::max(slots_used, nwg);
         if (int e = head(i - 1)) return e;
     }
-    if (int e = gn_launch_enc_bwd(rows, H, a, sol, x, part, &slots_used, st)) return e;
-    return gn_launch_reduce_all(part, slots_used, H, grads, st);
+    if (int e = gn_launch_enc_bwd(rows, H, a, sol, x, part, &slots_used, st, gx, p->linearS1_weight)) return e;
+    return grads ? gn_launch_reduce_all(part, slots_used, H, grads, st) : 0;
+}
+
+extern "C" int gnode_backward_rk4_f32(gnode_graph_t g, const float* x, const gnode_params* p, const float* dt_host,
+                                      int32_t n_steps, const int32_t* out_rows_host, int32_t n_out, const float* sol,
+                                      const float* gS, const float* gI, const float* gR, const gnode_params* grads,
+                                      int64_t rows, int32_t H, void* workspace, size_t workspace_bytes, void* stream) {
+    GN_CHECK_ARG(grads, "gnode_backward_rk4_f32: null pointer");
+    return gnode_backward_rk4_dx_f32(g, x, p, dt_host, n_steps, out_rows_host, n_out, sol, gS, gI, gR, grads, rows, H, workspace,
+                                     workspace_bytes, stream, nullptr);
 }

@@ -114,6 +114,27 @@ __device__ __forceinline__ void gn_dpre_row_kept(float bt, float gm, float4 uS, 
     GN_DPRE_ROW(x, v * ps.x) GN_DPRE_ROW(y, v * ps.y) GN_DPRE_ROW(z, v * ps.z) GN_DPRE_ROW(w, v * ps.w)
 }
 #undef GN_DPRE_ROW
+// the adjoint of the beta-gamma slab (ODEBlock input gradient): this lane's 4 columns of
+//   d/dbeta = sum_h (u_I - u_S) AI Z_S        d/dgamma = sum_h (u_R - u_I) Z_I
+__device__ __forceinline__ float2 gn_bg_part(float4 uS, float4 uI, float4 uR, float4 ai, float4 zs, float4 zi) {
+    const float c0 = (uI.x - uS.x) * ai.x * zs.x + (uI.y - uS.y) * ai.y * zs.y + (uI.z - uS.z) * ai.z * zs.z +
+                     (uI.w - uS.w) * ai.w * zs.w;
+    const float c1 = (uR.x - uI.x) * zi.x + (uR.y - uI.y) * zi.y + (uR.z - uI.z) * zi.z + (uR.w - uI.w) * zi.w;
+    return make_float2(c0, c1);
+}
+// ... summed over the lanes that hold the row (fixed order; every lane of the group must take part, idle lanes with zeros),
+// result in every lane
+template <class Sum>
+__device__ __forceinline__ float2 gn_bg_row(float4 uS, float4 uI, float4 uR, float4 ai, float4 zs, float4 zi) {
+    const float2 c = gn_bg_part(uS, uI, uR, ai, zs, zi);
+    return make_float2(Sum::sum(c.x), Sum::sum(c.y));
+}
+// gx[row][3], gx[row][4] += w * (d/dbeta, d/dgamma): one lane per row, rows of 3 + H floats (the layout of x)
+__device__ __forceinline__ void gn_bg_accumulate(float* __restrict__ gx, size_t row, int H, float w, float2 c) {
+    float* p = gx + row * (size_t)(3 + H) + 3;
+    p[0] += w * c.x;
+    p[1] += w * c.y;
+}
 
 // per-lane-group accumulators of the read-out head's parameter gradients
 struct HeadAcc {

@@ -14,15 +14,18 @@ import torch
 from . import ops
 
 
-def _needs_grad(params: dict) -> bool:
-    return torch.is_grad_enabled() and any(p.requires_grad for p in params.values())
+def _needs_grad(params: dict, x2d=None) -> bool:
+    return torch.is_grad_enabled() and (any(p.requires_grad for p in params.values()) or
+                                        (x2d is not None and x2d.requires_grad))
 
 
 class _GNODEForward(torch.autograd.Function):
     @staticmethod
     def forward(ctx, graph, x2d, dts, method, out_rows, keys, *tensors):
         params = dict(zip(keys, tensors))
-        S, I, R, sol = ops.forward(graph, x2d, params, dts, method, out_rows, want_sol=True)
+        # an input gradient needs the recomputing backward: no kept activations, the trajectory carries A Z_I instead
+        want_keep = False if ctx.needs_input_grad[1] else None
+        S, I, R, sol = ops.forward(graph, x2d.detach(), params, dts, method, out_rows, want_sol=True, want_keep=want_keep)
         ctx.graph, ctx.dts, ctx.method, ctx.out_rows, ctx.keys = graph, dts, method, out_rows, keys
         ctx.keep = sol.gnode_keep            # kept activations (a plain buffer nothing else references), or None
         ctx.save_for_backward(x2d, sol, *tensors)
@@ -34,15 +37,20 @@ class _GNODEForward(torch.autograd.Function):
         params = dict(zip(ctx.keys, tensors))
         ref = next(g for g in (gS, gI, gR) if g is not None)          # an output the loss did not use has no gradient
         gS, gI, gR = (torch.zeros_like(ref) if g is None else g for g in (gS, gI, gR))
-        grads = ops.backward(ctx.graph, x2d, params, ctx.dts, ctx.method, ctx.out_rows, sol,
-                             gS.contiguous(), gI.contiguous(), gR.contiguous(), keep=ctx.keep)
+        want_x = ctx.needs_input_grad[1]
+        want_params = any(ctx.needs_input_grad[6:])
+        grads = ops.backward(ctx.graph, x2d.detach(), params, ctx.dts, ctx.method, ctx.out_rows, sol,
+                             gS.contiguous(), gI.contiguous(), gR.contiguous(), keep=ctx.keep, want_x=want_x,
+                             want_params=want_params)
         # (ctx.keep stays: a second backward through this node -- retain_graph=True, two losses on one forward --
         #  needs it again; it is freed with ctx and sol)
-        return (None, None, None, None, None, None, *[grads[k] for k in ctx.keys])
+        gx = grads["x"].to(x2d.dtype) if want_x else None
+        return (None, gx, None, None, None, None,
+                *[grads[k] if need else None for k, need in zip(ctx.keys, ctx.needs_input_grad[6:])])
 
 
 def forward_with_grad(graph, x2d, params, dts, method="euler", out_rows=None):
-    if not _needs_grad(params):
+    if not _needs_grad(params, x2d):
         with torch.no_grad():
             S, I, R, _ = ops.forward(graph, x2d, {k: v.detach() for k, v in params.items()}, dts, method, out_rows)
         return S, I, R

@@ -181,13 +181,27 @@ def forward_status() -> int:
     return int(code.value)
 
 
+def _grad_buffers(params: dict, want_params: bool, want_x: bool, x2d: torch.Tensor):
+    """(grads dict, packed gradient pointers or None, gx or None): what a backward call writes."""
+    grads = {k: torch.empty_like(params[k], memory_format=torch.contiguous_format) for k in PARAM_KEYS} if want_params else {}
+    gx = torch.empty_like(x2d) if want_x else None
+    if gx is not None:
+        grads["x"] = gx
+    return grads, (pack_params({k: grads[k] for k in PARAM_KEYS}) if want_params else None), gx
+
+
 def backward(graph: DeviceGraph, x2d: torch.Tensor, params: dict, dts: np.ndarray, method: str, out_rows, sol: torch.Tensor,
-             gS: torch.Tensor, gI: torch.Tensor, gR: torch.Tensor, keep="auto", persist: bool | None = None) -> dict:
+             gS: torch.Tensor, gI: torch.Tensor, gR: torch.Tensor, keep="auto", persist: bool | None = None,
+             want_x: bool = False, want_params: bool = True) -> dict:
     """Adjoint parameter gradients (torchdiffeq odeint_adjoint semantics: Euler; rk4)
     given the saved trajectory `sol` and the upstream gradients of S, I, R ([n_out, rows]).
-    keep: the forward's kept activations ("auto": ``sol.gnode_keep`` when `forward` attached it; None: recompute; Euler only)."""
+    keep: the forward's kept activations ("auto": ``sol.gnode_keep`` when `forward` attached it; None: recompute; Euler only).
+    want_x: also dL/dx2d as key "x" ([rows, 3+H]; include/gnode.h gnode_backward_dx_f32; needs a trajectory produced
+    without keep); want_params=False: no parameter gradients (then want_x must be set)."""
+    if not (want_x or want_params):
+        raise _lib.GnodeError("backward: neither parameter nor input gradients requested")
     if method == "rk4":
-        return _backward_rk4(graph, x2d, params, dts, out_rows, sol, gS, gI, gR)
+        return _backward_rk4(graph, x2d, params, dts, out_rows, sol, gS, gI, gR, want_x=want_x, want_params=want_params)
     if method != "euler":
         raise _lib.GnodeError(f"unknown method {method!r} (euler | rk4)")
     lib = _lib.load()
@@ -203,27 +217,30 @@ def backward(graph: DeviceGraph, x2d: torch.Tensor, params: dict, dts: np.ndarra
     for t in (gS, gI, gR):
         if tuple(t.shape) != (n_out, rows):
             raise _lib.GnodeError(f"upstream gradient shape {tuple(t.shape)} != {(n_out, rows)}")
-    grads = {k: torch.empty_like(params[k], memory_format=torch.contiguous_format) for k in PARAM_KEYS}
+    grads, gp, gx = _grad_buffers(params, want_params, want_x, x2d)
     ws = _workspace(lib.gnode_backward_workspace_bytes(graph.handle, rows, H), x2d.device)
-    p, gp = pack_params({k: v.detach() for k, v in params.items()}), pack_params(grads)
+    p = pack_params({k: v.detach() for k, v in params.items()})
     if isinstance(keep, str):
         keep = getattr(sol, "gnode_keep", None)
     elif keep is None and getattr(sol, "gnode_keep", None) is not None and H == 64:
         # (a trajectory produced WITH kept activations does not carry A Z_I in its 4th slabs: include/gnode.h)
         raise _lib.GnodeError("this trajectory was produced with a keep buffer: pass it (keep='auto'), or run the forward with want_keep=False")
-    _lib.check(lib.gnode_backward_f32(
-        graph.handle, _lib.ptr(x2d), C.byref(p), _lib.host_ptr(dts), n_steps,
-        _lib.host_ptr(out_rows) if out_rows is not None else None, n_out, _lib.ptr(_f32c(sol)),
-        _lib.ptr(keep) if keep is not None else None, keep.numel() * 4 if keep is not None else 0,
-        _lib.ptr(_f32c(gS)), _lib.ptr(_f32c(gI)), _lib.ptr(_f32c(gR)), C.byref(gp), rows, H,
-        _lib.ptr(ws), ws.numel(), _lib.stream_ptr(), _fwd_flags(persist),
-        int(getattr(sol, "gnode_info", -1))))
+    args = (graph.handle, _lib.ptr(x2d), C.byref(p), _lib.host_ptr(dts), n_steps,
+            _lib.host_ptr(out_rows) if out_rows is not None else None, n_out, _lib.ptr(_f32c(sol)),
+            _lib.ptr(keep) if keep is not None else None, keep.numel() * 4 if keep is not None else 0,
+            _lib.ptr(_f32c(gS)), _lib.ptr(_f32c(gI)), _lib.ptr(_f32c(gR)), C.byref(gp) if gp is not None else None, rows, H,
+            _lib.ptr(ws), ws.numel(), _lib.stream_ptr(), _fwd_flags(persist), int(getattr(sol, "gnode_info", -1)))
+    if want_x:
+        _lib.check(lib.gnode_backward_dx_f32(*args, _lib.ptr(gx)))
+    else:
+        _lib.check(lib.gnode_backward_f32(*args))
     backward.last_workspace = (rows, H, ws)
     return grads
 
 
-def _backward_rk4(graph: DeviceGraph, x2d, params: dict, dts, out_rows, sol, gS, gI, gR) -> dict:
-    """The RK4 (3/8 rule) adjoint of a method='rk4' forward: gnode_backward_rk4_f32."""
+def _backward_rk4(graph: DeviceGraph, x2d, params: dict, dts, out_rows, sol, gS, gI, gR, want_x: bool = False,
+                  want_params: bool = True) -> dict:
+    """The RK4 (3/8 rule) adjoint of a method='rk4' forward: gnode_backward_rk4_f32 (want_x: gnode_backward_rk4_dx_f32)."""
     lib = _lib.load()
     x2d = _f32c(x2d)
     rows, H = x2d.shape[0], x2d.shape[1] - 3
@@ -237,14 +254,17 @@ def _backward_rk4(graph: DeviceGraph, x2d, params: dict, dts, out_rows, sol, gS,
     for t in (gS, gI, gR):
         if tuple(t.shape) != (n_out, rows):
             raise _lib.GnodeError(f"upstream gradient shape {tuple(t.shape)} != {(n_out, rows)}")
-    grads = {k: torch.empty_like(params[k], memory_format=torch.contiguous_format) for k in PARAM_KEYS}
+    grads, gp, gx = _grad_buffers(params, want_params, want_x, x2d)
     ws = _workspace(lib.gnode_backward_rk4_workspace_bytes(graph.handle, rows, H), x2d.device)
-    p, gp = pack_params({k: v.detach() for k, v in params.items()}), pack_params(grads)
-    _lib.check(lib.gnode_backward_rk4_f32(
-        graph.handle, _lib.ptr(x2d), C.byref(p), _lib.host_ptr(dts), n_steps,
-        _lib.host_ptr(out_rows) if out_rows is not None else None, n_out, _lib.ptr(_f32c(sol)),
-        _lib.ptr(_f32c(gS)), _lib.ptr(_f32c(gI)), _lib.ptr(_f32c(gR)), C.byref(gp), rows, H,
-        _lib.ptr(ws), ws.numel(), _lib.stream_ptr()))
+    p = pack_params({k: v.detach() for k, v in params.items()})
+    args = (graph.handle, _lib.ptr(x2d), C.byref(p), _lib.host_ptr(dts), n_steps,
+            _lib.host_ptr(out_rows) if out_rows is not None else None, n_out, _lib.ptr(_f32c(sol)),
+            _lib.ptr(_f32c(gS)), _lib.ptr(_f32c(gI)), _lib.ptr(_f32c(gR)), C.byref(gp) if gp is not None else None, rows, H,
+            _lib.ptr(ws), ws.numel(), _lib.stream_ptr())
+    if want_x:
+        _lib.check(lib.gnode_backward_rk4_dx_f32(*args, _lib.ptr(gx)))
+    else:
+        _lib.check(lib.gnode_backward_rk4_f32(*args))
     backward.last_workspace = None               # (no persistent sweep on this path: nothing for backward_status to read)
     return grads
 

@@ -14,7 +14,7 @@
  *     past the call.  "host" pointers are ordinary memory, read before return.
  *   - `stream` is a hipStream_t passed as void* (NULL = the default stream).
  *     All work is enqueued on it.  gnode_rhs_f32, gnode_forward_f32,
- *     gnode_backward_f32, gnode_rhs_vjp_f32, gnode_backward_rk4_f32 and gnode_l1_loss_f32 allocate nothing, synchronise nothing and keep nothing in
+ *     gnode_backward_f32, gnode_rhs_vjp_f32, gnode_backward_rk4_f32, their _dx forms and gnode_l1_loss_f32 allocate nothing, synchronise nothing and keep nothing in
  *     the graph handle: every byte of scratch (including the partial sums of long
  *     "hub" rows) is carved from the caller's workspace, so they can be captured
  *     into a hipGraph on first use and one handle may serve several streams (each
@@ -225,6 +225,37 @@ int gnode_backward_rk4_f32(gnode_graph_t g, const float* x, const gnode_params* 
                            int32_t n_steps, const int32_t* out_rows_host, int32_t n_out, const float* sol,
                            const float* gS, const float* gI, const float* gR, const gnode_params* grads,
                            int64_t rows, int32_t H, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- input gradient: backpropagation to the ODEBlock input x ---------------
+ * gnode_backward_f32 / gnode_backward_rk4_f32 with one more output: what odeint_adjoint returns for the initial state
+ * (ode_nn_ngraph_sim.py:148-168, multi: ode_nn_ngraphs.py:124-137) taken back through the encoder, i.e. dL/dx.
+ *   gx     NULL (then exactly the call without _dx), or device [rows, 3+H] fp32 in the layout of x, OVERWRITTEN:
+ *            columns 0, 1, 2  dL/dS0, dL/dI0, dL/dR0 = sum_h a_X(t0)[r,h] [sol0_X[r,h] > 0] linearS1.weight[h]
+ *                             (a(t0) includes the head's VJP at grid point 0 when that point is emitted)
+ *            column 3, 4      dL/dbeta, dL/dgamma: the beta-gamma slab's adjoint, over intervals i = G-1 .. 1 with the
+ *                             adjoint a_i before its update and the Jacobian at y_i, AI = A Z_I(y_i):
+ *                               beta  += dt_{i-1} sum_h (a_I - a_S) AI Z_S      gamma += dt_{i-1} sum_h (a_R - a_I) Z_I
+ *                             (RK4: the same two sums per stage at the stage state, weighted dt {1, 3, 3, 1} / 8)
+ *            columns 5 ..     0 (the slab's other columns, the multi-graph marker among them, feed nothing)
+ *   grads  as there, or NULL when gx is given: the parameter reduction is then skipped.  NULL grads and NULL gx: GNODE_ERR_ARG.
+ *   keep   (Euler) must be NULL when gx is given (GNODE_ERR_ARG otherwise): the kept activations hold AI Z_S (1 - Z_S), not
+ *          AI, so a gx call needs a trajectory produced WITHOUT keep.
+ * A gx call runs the recomputing one-launch-per-interval forms (H = 64: the fused interval kernel over one table when sol
+ * carries A Z_I, two otherwise; H <= 32: the small-H interval kernel; other H: the five-launch path), never the one-launch
+ * sweeps of tiny graphs / small H nor the kept or persistent H = 64 sweeps, whatever `flags` says: slower than the
+ * training backward on the shapes that take those.  Parameter gradients are bitwise those of the
+ * call without gx on the same path.  Same workspace as without gx; deterministic (the beta / gamma columns are
+ * read-modify-written by one lane per row per launch, launches stream-ordered; no atomics); enqueue-only (capturable). */
+int gnode_backward_dx_f32(gnode_graph_t g, const float* x, const gnode_params* p, const float* dt_host,
+                          int32_t n_steps, const int32_t* out_rows_host, int32_t n_out, const float* sol,
+                          const float* keep, size_t keep_bytes,
+                          const float* gS, const float* gI, const float* gR, const gnode_params* grads,
+                          int64_t rows, int32_t H, void* workspace, size_t workspace_bytes, void* stream,
+                          int32_t flags, int32_t sol_info, float* gx);
+int gnode_backward_rk4_dx_f32(gnode_graph_t g, const float* x, const gnode_params* p, const float* dt_host,
+                              int32_t n_steps, const int32_t* out_rows_host, int32_t n_out, const float* sol,
+                              const float* gS, const float* gI, const float* gR, const gnode_params* grads,
+                              int64_t rows, int32_t H, void* workspace, size_t workspace_bytes, void* stream, float* gx);
 
 /* ---- Monte-Carlo SIR labels ------------------------------------------------
  * sir_torch(G, seed_set, beta, gamma, sims, T): ode_nn.py:30-88.
