@@ -13,6 +13,8 @@
 //     encoder backward on a_0.
 // The Jacobians are evaluated at the RIGHT endpoint y_i (one Euler step of the augmented
 // system from t_i to t_{i-1}), which is what the reference's training gradients are.
+// gnode_backward_discrete_f32 runs the same sweep with every interval's Jacobian, parameter VJP and beta-gamma sums at the
+// LEFT endpoint y_{i-1} (BwdCall::jp, the kernels' EXACT flag): the exact gradient of the Euler loop.
 //
 // Launch structure: H = 64 and H <= 32 take ONE launch per interval (k_bwd_fused64 / k_bwd_fused_generic: the
 // interval's VJPs, the head's VJP at grid point i-1 and the NEXT interval's Z / q gather tables, double-buffered);
@@ -386,7 +388,9 @@ static_assert(GN_BWD_RPG1_OCC * 256 <= BWD_NWG, "fused backward grid exceeds the
 // GATHER_AI: gather A Z_I as well (the last grid point, and trajectories whose 4th slabs do not carry it); otherwise the
 // row's A Z_I(y_i) is read back from `AIsaved` (the forward kept it) and only A q is gathered: one table instead of two.
 // WANT_BG: also accumulate the beta-gamma slab's adjoint into gx columns 3, 4 (gnode_backward_dx_f32).
-template <int OCC, int RPG, bool GATHER_AI, bool WANT_BG = false>
+// EXACT: the discrete sweep (gnode_backward_discrete_f32): Ysol is y_{i-1}, at which the Jacobian AND the
+// head are evaluated, and Yprev is y_{i-2}, whose rows the next interval's Z_I / q tables are built from.
+template <int OCC, int RPG, bool GATHER_AI, bool WANT_BG = false, bool EXACT = false>
 __global__ __launch_bounds__(256, OCC) void k_bwd_fused64(const int* __restrict__ rowptr, const int* __restrict__ col, int n,
                                                      long rows, int tiles_per_sample, long total_tiles,
                                                      const float* __restrict__ ZIc, const float* __restrict__ Qc,
@@ -531,15 +535,24 @@ __global__ __launch_bounds__(256, OCC) void k_bwd_fused64(const int* __restrict_
                 const float4 uI = *reinterpret_cast<const float4*>(&Yt[1][lr[p] * TS + 4 * sub]);
                 aS[p].x += dt * uS.x; aS[p].y += dt * uS.y; aS[p].z += dt * uS.z; aS[p].w += dt * uS.w;
                 aI[p].x += dt * uI.x; aI[p].y += dt * uI.y; aI[p].z += dt * uI.z; aI[p].w += dt * uI.w;
-                if (head || do_next) y[0] = ld4(Yprev + off[p]);
-                if (head || (do_next && ZIn)) y[1] = ld4(Yprev + slab + off[p]);
+                if constexpr (EXACT) {
+                    // the head reads y_{i-1} (Ysol, L2-hot: staged above), the next tables y_{i-2}: park those rows now
+                    if (do_next) {
+                        *reinterpret_cast<float4*>(&Yt[0][lr[p] * TS + 4 * sub]) = ld4(Yprev + off[p]);
+                        if (ZIn) *reinterpret_cast<float4*>(&Yt[1][lr[p] * TS + 4 * sub]) = ld4(Yprev + slab + off[p]);
+                    }
+                    if (head) { y[0] = ld4(Ysol + off[p]); y[1] = ld4(Ysol + slab + off[p]); y[2] = ld4(Ysol + 2 * slab + off[p]); }
+                } else {
+                    if (head || do_next) y[0] = ld4(Yprev + off[p]);
+                    if (head || (do_next && ZIn)) y[1] = ld4(Yprev + slab + off[p]);
+                    if (head) y[2] = ld4(Yprev + 2 * slab + off[p]);
+                }
                 if (head) {
-                    y[2] = ld4(Yprev + 2 * slab + off[p]);
                     const size_t o = (size_t)(base + tile * TR + lr[p]);
                     gout[0] = gS[o]; gout[1] = gI[o]; gout[2] = gR[o];
                 }
             }
-            if (do_next) {
+            if (!EXACT && do_next) {
                 *reinterpret_cast<float4*>(&Yt[0][lr[p] * TS + 4 * sub]) = y[0];
                 if (ZIn) *reinterpret_cast<float4*>(&Yt[1][lr[p] * TS + 4 * sub]) = y[1];
             }
@@ -863,7 +876,8 @@ __device__ __forceinline__ float4 group_lin(float4 x, const float* __restrict__ 
 }
 
 // WANT_BG: also accumulate dt * (d/dbeta, d/dgamma) of each row into gx columns 3, 4 (gnode_backward_dx_f32)
-template <int LPR, bool WANT_BG = false>
+// EXACT: the discrete sweep: Ysol is y_{i-1} (Jacobian, gW and the head), Yprev y_{i-2} (next tables)
+template <int LPR, bool WANT_BG = false, bool EXACT = false>
 __global__ __launch_bounds__(256) void k_bwd_fused_generic(
     const int* __restrict__ rowptr, const int* __restrict__ col, int n, long rows, int H, float* __restrict__ ZS,
     const float* __restrict__ ZIc, const float* __restrict__ Qc, float* __restrict__ ZIn, float* __restrict__ Qn,
@@ -975,9 +989,13 @@ __global__ __launch_bounds__(256) void k_bwd_fused_generic(
         // 3. dL/dsol[i-1] through the head (rows beyond the end carry y = 0, gout = 0)
         float4 y[3] = {zero4(), zero4(), zero4()};
         float gout[3] = {0.f, 0.f, 0.f};
-        if (ok && (head || do_next)) { y[0] = ld4(Yprev + off); y[1] = ld4(Yprev + slab + off); }
+        if constexpr (EXACT) {
+            if (head) { y[0] = yS; y[1] = yI; }             // y_{i-1}: the rows loaded for gW (zero where !ok)
+        } else {
+            if (ok && (head || do_next)) { y[0] = ld4(Yprev + off); y[1] = ld4(Yprev + slab + off); }
+        }
         if (head) {
-            if (ok) y[2] = ld4(Yprev + 2 * slab + off);
+            if (ok) y[2] = ld4((EXACT ? Ysol : Yprev) + 2 * slab + off);
             if (inrow) { gout[0] = gS[r]; gout[1] = gI[r]; gout[2] = gR[r]; }
             // a 16-lane group is one DPP row: it sums with row_sum16, like the H = 64 kernels; smaller groups shuffle
             gn_head_vjp<std::conditional_t<LPR == 16, DppSum16, XorSum<LPR>>>(y, gout, w3v, b3, w2, b2, aS, aI, aR, hacc);
@@ -986,6 +1004,10 @@ __global__ __launch_bounds__(256) void k_bwd_fused_generic(
         if (ok) { st4(a + off, aS); st4(a + slab + off, aI); }
         // 4. Z(y_{i-1}) and q for the next interval
         if (do_next) {
+            if constexpr (EXACT) {                          // the next tables' rows are y_{i-2}
+                y[0] = zero4(); y[1] = zero4();
+                if (ok) { y[0] = ld4(Yprev + off); y[1] = ld4(Yprev + slab + off); }
+            }
             float4 zs = group_lin<LPR>(y[0], Wt, sub, lane_ok, H), zi = group_lin<LPR>(y[1], Wt, sub, lane_ok, H);
             zs = make_float4(gn_sigmoid(zs.x + bias4.x), gn_sigmoid(zs.y + bias4.y), gn_sigmoid(zs.z + bias4.z), gn_sigmoid(zs.w + bias4.w));
             zi = make_float4(gn_sigmoid(zi.x + bias4.x), gn_sigmoid(zi.y + bias4.y), gn_sigmoid(zi.z + bias4.z), gn_sigmoid(zi.w + bias4.w));
@@ -1220,7 +1242,13 @@ struct BwdCall {
     hipStream_t st;
     int slots_used;                  // highest workgroup slot any launch wrote, for the final reduction
     float* gx;                       // the input gradient [rows, 3+H] (gnode_backward_dx_f32), or null
+    bool exact = false;              // the discrete sweep (gnode_backward_discrete_f32): Jacobians at the LEFT endpoints
     const float* point(int gi) const { return sol + (size_t)gi * 4 * slab; }   // trajectory point gi
+    // the grid point at which interval i (y_i -> y_{i-1}) evaluates its Jacobian: y_i (adjoint), y_{i-1} (discrete)
+    int jp(int i) const { return exact ? i - 1 : i; }
+    // the rows the interval kernels read besides point(jp(i)): grid point jp(i) - 1 (the adjoint's head, the discrete sweep's
+    // next tables; nothing reads it when jp(i) = 0)
+    const float* before(int i) const { return point(std::max(jp(i) - 1, 0)); }
     // grid point gi's row of an upstream gradient (gS, gI or gR), or null when gi is not emitted
     const float* up(const float* U, int gi) const { return slot[gi] >= 0 ? U + (size_t)slot[gi] * rows : nullptr; }
     // the head's VJP at grid point gi (when it is emitted)
@@ -1299,7 +1327,9 @@ static int backward64_interval(BwdCall& c, const BwdPlan& pl, int i) {
     const long total = (long)(rows / g->n) * tps;
     const int cur = (c.G - 1 - i) & 1;
     const bool ai_saved = !pl.fwd_tiny;
-    const bool two = !ai_saved || i == c.G - 1;          // A Z_I(y_{G-1}) was never needed by the forward
+    // the forward left A Z_I(y_k) in the 4th slab of grid points 1 .. G-2 (A Z_I(y_{G-1}) was never needed by it)
+    auto two_at = [&](int j) { const int k = c.jp(j); return !ai_saved || k < 1 || k > c.G - 2; };
+    const bool two = two_at(i);
     const float *AIhub = nullptr, *GQhub = nullptr;
     const bool kept_launch = keep && !two && rows < (1L << 24) && (long)(rows / g->n) * g->n_seg < (1L << 24);   // 32-bit byte offsets of rows and hub partials
     const float* HubP = nullptr;               // kept kernel: segment partials only, it adds them up itself
@@ -1321,13 +1351,18 @@ static int backward64_interval(BwdCall& c, const BwdPlan& pl, int i) {
                            gSs, c.up(c.gI, i - 1), c.up(c.gR, i - 1), p->linear3_weight, p->linear3_bias, p->linearS2_weight,
                            p->linearS2_bias, g->hubidx, HubP, g->hub_seg_ptr, g->n_seg, i > 1 ? 1 : 0);
     } else {
-        auto fused_kernel = c.gx ? (two ? k_bwd_fused64<GN_BWD_RPG1_OCC, 1, true, true> : k_bwd_fused64<GN_BWD_RPG1_OCC, 1, false, true>)
-                                 : (two ? k_bwd_fused64<GN_BWD_RPG1_OCC, 1, true> : k_bwd_fused64<GN_BWD_RPG1_OCC, 1, false>);
+        constexpr int O = GN_BWD_RPG1_OCC;
+        auto fused_kernel = c.exact ? (c.gx ? (two ? k_bwd_fused64<O, 1, true, true, true> : k_bwd_fused64<O, 1, false, true, true>)
+                                            : (two ? k_bwd_fused64<O, 1, true, false, true> : k_bwd_fused64<O, 1, false, false, true>))
+                                    : (c.gx ? (two ? k_bwd_fused64<O, 1, true, true> : k_bwd_fused64<O, 1, false, true>)
+                                            : (two ? k_bwd_fused64<O, 1, true> : k_bwd_fused64<O, 1, false>));
+        // the next interval gathers A Z_I itself when its grid point's 4th slab does not carry it
+        float* ZIn = c.exact ? (two_at(i - 1) ? T.ZIb[cur ^ 1] : nullptr) : (ai_saved ? nullptr : T.ZIb[cur ^ 1]);
         hipLaunchKernelGGL(fused_kernel, dim3(grid), dim3(256), 0, c.st, g->rowptr, g->col, g->n, rows, tps, total, T.ZIb[cur],
-                           T.Qb[cur], ai_saved ? nullptr : T.ZIb[cur ^ 1], T.Qb[cur ^ 1], c.point(i), c.point(i - 1),
+                           T.Qb[cur], ZIn, T.Qb[cur ^ 1], c.point(c.jp(i)), c.before(i),
                            p->odefunc_linear_weight, p->odefunc_linear_bias, c.beta, c.gamma, c.dt_host[i - 1], c.a, c.part, gSs,
                            c.up(c.gI, i - 1), c.up(c.gR, i - 1), p->linear3_weight, p->linear3_bias, p->linearS2_weight,
-                           p->linearS2_bias, g->hubidx, AIhub, GQhub, g->n_hub, i > 1 ? 1 : 0, c.point(i) + 3 * c.slab, c.gx);
+                           p->linearS2_bias, g->hubidx, AIhub, GQhub, g->n_hub, i > 1 ? 1 : 0, c.point(c.jp(i)) + 3 * c.slab, c.gx);
     }
     if (sampled) gn_prof_end(2, c.st);
     GN_LAUNCH_CHECK();
@@ -1357,7 +1392,7 @@ static int backward_h64(BwdCall& c, const BwdPlan& pl, const float* keep, size_t
         GN_LAUNCH_CHECK();
     } else if (!pl.fold) {
         const long mt = (2 * c.rows + TILE_ROWS - 1) / TILE_ROWS;
-        hipLaunchKernelGGL(k_mlp64_q, dim3((unsigned)std::min<long>(mt, 1024)), dim3(256), 0, c.st, c.point(G - 1),
+        hipLaunchKernelGGL(k_mlp64_q, dim3((unsigned)std::min<long>(mt, 1024)), dim3(256), 0, c.st, c.point(c.jp(G - 1)),
                            p->odefunc_linear_weight, p->odefunc_linear_bias, c.Z, c.a, c.beta, c.q, c.rows);
         GN_LAUNCH_CHECK();
     }
@@ -1397,7 +1432,8 @@ static int backward_small_h(BwdCall& c, const BwdPlan& pl) {
         c.slots_used = std::max(c.slots_used, pl.persg.wgs);
         return 0;
     }
-    if (int e = gn_launch_mlp_any(g, c.point(G - 1), p->odefunc_linear_weight, p->odefunc_linear_bias, c.Z, 2 * rows, H, c.st)) return e;
+    if (int e = gn_launch_mlp_any(g, c.point(c.jp(G - 1)), p->odefunc_linear_weight, p->odefunc_linear_bias, c.Z, 2 * rows, H, c.st))
+        return e;
     hipLaunchKernelGGL(k_bwd_q, dim3(2048), dim3(256), 0, c.st, c.a, c.Z, c.beta, c.q, rows, H);
     GN_LAUNCH_CHECK();
     const size_t fl = std::max((size_t)2 * H * H + (size_t)4 * rpw * H, (size_t)rpw * (4 * H + 12));
@@ -1408,16 +1444,21 @@ static int backward_small_h(BwdCall& c, const BwdPlan& pl) {
         const float *HubP0 = nullptr, *HubP1 = nullptr;        // segment partials; the interval kernel adds them up itself
         if (int e = gn_hub_segments2(g, rows / g->n, H, ZIb[cur], Qb[cur], c.hub_scratch, &HubP0, &HubP1, c.st)) return e;
         const bool sampled = gn_prof_begin(2, c.st);
-#define GN_FUSED_GENERIC(BG)                                                                                                        \
-        GN_LPR_DISPATCH(32, lpr, hipLaunchKernelGGL((k_bwd_fused_generic<LPR, BG>), dim3(grid), dim3(256), fl * sizeof(float), c.st,     \
+#define GN_FUSED_GENERIC(BG, EX)                                                                                                    \
+        GN_LPR_DISPATCH(32, lpr, hipLaunchKernelGGL((k_bwd_fused_generic<LPR, BG, EX>), dim3(grid), dim3(256), fl * sizeof(float), c.st, \
                                                     g->rowptr, g->col, g->n, rows, H, c.Z, ZIb[cur], Qb[cur], ZIb[cur ^ 1], Qb[cur ^ 1], \
-                                                    c.point(i), c.point(i - 1), p->odefunc_linear_weight, p->odefunc_linear_bias,       \
+                                                    c.point(c.jp(i)), c.before(i), p->odefunc_linear_weight, p->odefunc_linear_bias,    \
                                                     c.beta, c.gamma, c.dt_host[i - 1], c.a, c.part, c.up(c.gS, i - 1),                 \
                                                     c.up(c.gI, i - 1), c.up(c.gR, i - 1), p->linear3_weight, p->linear3_bias,          \
                                                     p->linearS2_weight, p->linearS2_bias, g->hubidx, HubP0, HubP1, g->hub_seg_ptr,     \
                                                     g->n_seg, i > 1 ? 1 : 0, c.gx))
-        if (c.gx) GN_FUSED_GENERIC(true)
-        else GN_FUSED_GENERIC(false)
+        if (c.exact) {
+            if (c.gx) GN_FUSED_GENERIC(true, true)
+            else GN_FUSED_GENERIC(false, true)
+        } else {
+            if (c.gx) GN_FUSED_GENERIC(true, false)
+            else GN_FUSED_GENERIC(false, false)
+        }
 #undef GN_FUSED_GENERIC
         if (sampled) gn_prof_end(2, c.st);
         GN_LAUNCH_CHECK();
@@ -1433,7 +1474,7 @@ static int backward_generic(BwdCall& c) {
     const int H = c.H, lpr = gn_lpr(H), rpw = 256 / lpr;
     const size_t mlp_lds = ((size_t)H * H + (size_t)4 * rpw * H) * sizeof(float);
     for (int i = c.G - 1; i >= 1; --i) {
-        const float* yi = c.point(i);
+        const float* yi = c.point(c.jp(i));
         const float dt = c.dt_host[i - 1];
         if (int e = gn_launch_mlp_any(g, yi, p->odefunc_linear_weight, p->odefunc_linear_bias, c.Z, 2 * rows, H, c.st)) return e;
         hipLaunchKernelGGL(k_bwd_q, dim3(2048), dim3(256), 0, c.st, c.a, c.Z, c.beta, c.q, rows, H);
@@ -1463,11 +1504,13 @@ static int backward_generic(BwdCall& c) {
     return 0;
 }
 
-extern "C" int gnode_backward_dx_f32(gnode_graph_t g, const float* x, const gnode_params* p, const float* dt_host,
-                                     int32_t n_steps, const int32_t* out_rows_host, int32_t n_out, const float* sol,
-                                     const float* keep, size_t keep_bytes, const float* gS, const float* gI, const float* gR,
-                                     const gnode_params* grads, int64_t rows, int32_t H, void* workspace,
-                                     size_t workspace_bytes, void* stream, int32_t flags, int32_t sol_info, float* gx) {
+// exact: the discrete sweep (gnode_backward_discrete_f32; keep is null, flags GNODE_FWD_PER_STEP): the one-launch-per-interval
+// forms of the gx call, each interval's Jacobian at y_{i-1}
+static int backward_euler(gnode_graph_t g, const float* x, const gnode_params* p, const float* dt_host, int32_t n_steps,
+                          const int32_t* out_rows_host, int32_t n_out, const float* sol, const float* keep, size_t keep_bytes,
+                          const float* gS, const float* gI, const float* gR, const gnode_params* grads, int64_t rows, int32_t H,
+                          void* workspace, size_t workspace_bytes, void* stream, int32_t flags, int32_t sol_info, float* gx,
+                          bool exact) {
     GN_CHECK_ARG(g && x && p && sol && gS && gI && gR && workspace, "gnode_backward_f32: null pointer");
     GN_CHECK_ARG(grads || gx, "gnode_backward_dx_f32: neither grads nor gx requested");
     GN_CHECK_ARG(!(gx && keep), "gnode_backward_dx_f32: a keep buffer cannot serve an input gradient (pass keep = NULL)");
@@ -1486,12 +1529,14 @@ extern "C" int gnode_backward_dx_f32(gnode_graph_t g, const float* x, const gnod
     const int G = n_steps + 1, n_emit = out_rows_host ? n_out : G;
     if (int e = gn_check_out_rows("gnode_backward_f32", out_rows_host, n_out, G)) return e;
     const std::vector<int> slot = gn_out_slots(out_rows_host, n_out, G);
-    const BwdPlan pl = backward_plan(g, rows, H, n_steps, n_emit, slot.data(), keep, sol_info, flags, gx != nullptr);
+    BwdPlan pl = backward_plan(g, rows, H, n_steps, n_emit, slot.data(), keep, sol_info, flags, gx != nullptr || exact);
+    // the discrete sweep reads A Z_I from the 4th slabs only when the forward said it left it there (unchecked: gathers it)
+    if (exact) pl.fwd_tiny = !(sol_info >= 0 && (sol_info & GNODE_SOL_AI));
     const BwdLayout L = backward_layout(rows, H);
     char* ws = (char*)workspace;
     BwdCall c{g, p, dt_host, G, H, (long)rows, (size_t)rows * H, L.slab, sol, gS, gI, gR, slot.data(),
               (float*)(ws + L.a), (float*)(ws + L.Z), (float*)(ws + L.q), (float*)(ws + L.dpre), (float*)(ws + L.beta),
-              (float*)(ws + L.gamma), (float*)(ws + L.part), ws + L.ctl, ws + L.fixed, (hipStream_t)stream, 1, gx};
+              (float*)(ws + L.gamma), (float*)(ws + L.part), ws + L.ctl, ws + L.fixed, (hipStream_t)stream, 1, gx, exact};
     int e = 0;
     // the interval kernels accumulate columns 3, 4 in place and the encoder writes 0-2: the rest stays 0
     if (gx) e = gn_zero_async(gx, (size_t)rows * (3 + H) * sizeof(float), c.st);
@@ -1507,6 +1552,31 @@ extern "C" int gnode_backward_dx_f32(gnode_graph_t g, const float* x, const gnod
     }
     if (e || !grads) return e;
     return gn_launch_reduce_all(c.part, c.slots_used, H, grads, c.st);
+}
+
+extern "C" int gnode_backward_dx_f32(gnode_graph_t g, const float* x, const gnode_params* p, const float* dt_host,
+                                     int32_t n_steps, const int32_t* out_rows_host, int32_t n_out, const float* sol,
+                                     const float* keep, size_t keep_bytes, const float* gS, const float* gI, const float* gR,
+                                     const gnode_params* grads, int64_t rows, int32_t H, void* workspace,
+                                     size_t workspace_bytes, void* stream, int32_t flags, int32_t sol_info, float* gx) {
+    return backward_euler(g, x, p, dt_host, n_steps, out_rows_host, n_out, sol, keep, keep_bytes, gS, gI, gR, grads, rows, H,
+                          workspace, workspace_bytes, stream, flags, sol_info, gx, false);
+}
+
+extern "C" size_t gnode_backward_discrete_workspace_bytes(gnode_graph_t g, int64_t rows, int32_t H) {
+    return gnode_backward_workspace_bytes(g, rows, H);
+}
+
+extern "C" int gnode_backward_discrete_f32(gnode_graph_t g, const float* x, const gnode_params* p, const float* dt_host,
+                                           int32_t n_steps, const int32_t* out_rows_host, int32_t n_out, const float* sol,
+                                           int32_t sol_info, const float* gS, const float* gI, const float* gR,
+                                           const gnode_params* grads, float* gx, int64_t rows, int32_t H, void* workspace,
+                                           size_t workspace_bytes, void* stream) {
+    GN_CHECK_ARG(grads || gx, "gnode_backward_discrete_f32: neither grads nor gx requested");
+    GN_CHECK_ARG(sol_info < 0 || !(sol_info & GNODE_SOL_KEEP), "gnode_backward_discrete_f32: this trajectory was produced WITH a "
+                 "keep buffer (its 4th slabs are unwritten): run the forward without one (sol_info %d)", sol_info);
+    return backward_euler(g, x, p, dt_host, n_steps, out_rows_host, n_out, sol, nullptr, 0, gS, gI, gR, grads, rows, H, workspace,
+                          workspace_bytes, stream, GNODE_FWD_PER_STEP, sol_info, gx, true);
 }
 
 extern "C" int gnode_backward_f32(gnode_graph_t g, const float* x, const gnode_params* p, const float* dt_host,

@@ -21,6 +21,7 @@ EXPORTS = [
     "gnode_backward_workspace_bytes", "gnode_backward_f32",
     "gnode_rhs_vjp_workspace_bytes", "gnode_rhs_vjp_f32", "gnode_backward_rk4_workspace_bytes", "gnode_backward_rk4_f32",
     "gnode_backward_dx_f32", "gnode_backward_rk4_dx_f32",
+    "gnode_backward_discrete_workspace_bytes", "gnode_backward_discrete_f32",
     "gnode_sir_workspace_bytes", "gnode_sir_coins_workspace_bytes",
     "gnode_sir_mc_philox", "gnode_sir_mc_philox_scan", "gnode_sir_mc_philox_counted", "gnode_sir_mc_coins",
     "gnode_dmp_workspace_bytes", "gnode_dmp_f32",
@@ -111,6 +112,11 @@ def load():
     lib.gnode_backward_rk4_f32.restype = C.c_int
     lib.gnode_backward_rk4_dx_f32.argtypes = lib.gnode_backward_rk4_f32.argtypes + [vp]
     lib.gnode_backward_rk4_dx_f32.restype = C.c_int
+    lib.gnode_backward_discrete_workspace_bytes.argtypes = [vp, i64, i32]
+    lib.gnode_backward_discrete_workspace_bytes.restype = sz
+    lib.gnode_backward_discrete_f32.argtypes = [vp, vp, C.POINTER(Params), vp, i32, vp, i32, vp, i32, vp, vp, vp,
+                                                C.POINTER(Params), vp, i64, i32, vp, sz, vp]
+    lib.gnode_backward_discrete_f32.restype = C.c_int
     lib.gnode_sir_workspace_bytes.argtypes = [vp, i32]
     lib.gnode_sir_workspace_bytes.restype = sz
     lib.gnode_sir_coins_workspace_bytes.restype = sz
@@ -127,8 +133,8 @@ def load():
     for fn in ("gnode_graph_create", "gnode_graph_destroy", "gnode_graph_info", "gnode_rhs_f32", "gnode_forward_f32",
                "gnode_sir_mc_philox", "gnode_sir_mc_coins"):
         getattr(lib, fn).restype = C.c_int
-    if lib.gnode_version() < 223:
-        raise GnodeError(f"{LIB_PATH} is stale (ABI {lib.gnode_version()} < 223): rebuild it (gnode.build.build_lib)")
+    if lib.gnode_version() < 224:
+        raise GnodeError(f"{LIB_PATH} is stale (ABI {lib.gnode_version()} < 224): rebuild it (gnode.build.build_lib)")
     _lib = lib
     return lib
 

@@ -4,7 +4,8 @@ Inference (no_grad, or nothing requires grad) calls the fused forward and never
 materialises the trajectory.  Training saves `sol` as torchdiffeq's
 odeint_adjoint does and runs its adjoint backward in libgnode_hip.so: the
 adjoint-Euler sweep (method='euler') or the RK4 (3/8 rule)
-adjoint (method='rk4').  `rhs` is ODEfunc.forward as an
+adjoint (method='rk4'), or with adjoint=False the exact gradient
+of the Euler solve.  `rhs` is ODEfunc.forward as an
 autograd node over the RHS and its vector-Jacobian product.
 """
 from __future__ import annotations
@@ -21,12 +22,13 @@ def _needs_grad(params: dict, x2d=None) -> bool:
 
 class _GNODEForward(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, graph, x2d, dts, method, out_rows, keys, *tensors):
+    def forward(ctx, graph, x2d, dts, method, out_rows, adjoint, keys, *tensors):
         params = dict(zip(keys, tensors))
-        # an input gradient needs the recomputing backward: no kept activations, the trajectory carries A Z_I instead
-        want_keep = False if ctx.needs_input_grad[1] else None
+        # an input gradient, and the exact (adjoint=False) gradient, need the recomputing backward: no kept activations, the
+        # trajectory carries A Z_I instead
+        want_keep = False if (ctx.needs_input_grad[1] or not adjoint) else None
         S, I, R, sol = ops.forward(graph, x2d.detach(), params, dts, method, out_rows, want_sol=True, want_keep=want_keep)
-        ctx.graph, ctx.dts, ctx.method, ctx.out_rows, ctx.keys = graph, dts, method, out_rows, keys
+        ctx.graph, ctx.dts, ctx.method, ctx.out_rows, ctx.adjoint, ctx.keys = graph, dts, method, out_rows, adjoint, keys
         ctx.keep = sol.gnode_keep            # kept activations (a plain buffer nothing else references), or None
         ctx.save_for_backward(x2d, sol, *tensors)
         return S, I, R
@@ -38,24 +40,27 @@ class _GNODEForward(torch.autograd.Function):
         ref = next(g for g in (gS, gI, gR) if g is not None)          # an output the loss did not use has no gradient
         gS, gI, gR = (torch.zeros_like(ref) if g is None else g for g in (gS, gI, gR))
         want_x = ctx.needs_input_grad[1]
-        want_params = any(ctx.needs_input_grad[6:])
+        want_params = any(ctx.needs_input_grad[7:])
         grads = ops.backward(ctx.graph, x2d.detach(), params, ctx.dts, ctx.method, ctx.out_rows, sol,
                              gS.contiguous(), gI.contiguous(), gR.contiguous(), keep=ctx.keep, want_x=want_x,
-                             want_params=want_params)
+                             want_params=want_params, adjoint=ctx.adjoint)
         # (ctx.keep stays: a second backward through this node -- retain_graph=True, two losses on one forward --
         #  needs it again; it is freed with ctx and sol)
         gx = grads["x"].to(x2d.dtype) if want_x else None
-        return (None, gx, None, None, None, None,
-                *[grads[k] if need else None for k, need in zip(ctx.keys, ctx.needs_input_grad[6:])])
+        return (None, gx, None, None, None, None, None,
+                *[grads[k] if need else None for k, need in zip(ctx.keys, ctx.needs_input_grad[7:])])
 
 
-def forward_with_grad(graph, x2d, params, dts, method="euler", out_rows=None):
+def forward_with_grad(graph, x2d, params, dts, method="euler", out_rows=None, adjoint=True):
+    """adjoint=False: the backward is the exact gradient of the Euler solve (ops.backward(adjoint=False)); it raises for rk4."""
+    if not adjoint and method != "euler":
+        raise ops._lib.GnodeError(f"adjoint=False is Euler only (method {method!r}): DESIGN section 7.3")
     if not _needs_grad(params, x2d):
         with torch.no_grad():
             S, I, R, _ = ops.forward(graph, x2d, {k: v.detach() for k, v in params.items()}, dts, method, out_rows)
         return S, I, R
     keys = tuple(params.keys())
-    return _GNODEForward.apply(graph, x2d, dts, method, out_rows, keys, *[params[k] for k in keys])
+    return _GNODEForward.apply(graph, x2d, dts, method, out_rows, bool(adjoint), keys, *[params[k] for k in keys])
 
 
 class _RHSFunction(torch.autograd.Function):

@@ -5,6 +5,7 @@ in libgnode_hip.so on the MI355X.
 
     ODEfunc(A, beta, gamma, hidden1, device)            reference :37-96
     ODEBlock(maxTime, deltaT, n_nodes, indices, hidden1, odefunc, device)   :99-188
+        (+ method="euler" | "rk4", adjoint=True | False: extensions)
 """
 from __future__ import annotations
 
@@ -15,6 +16,14 @@ import torch.nn as nn
 from . import autograd as _autograd
 from . import ops
 from .graph import DeviceGraph
+
+
+def _check_adjoint(adjoint, method) -> bool:
+    """ODEBlock's `adjoint` flag: False (the exact gradient of the solve) exists for Euler only."""
+    if not adjoint and method != "euler":
+        raise ops._lib.GnodeError(f"ODEBlock(adjoint=False) is Euler only (method {method!r}): for RK4 the adjoint gradient is "
+                                  "within 3.4e-5 of the exact one, below fp32 noise (DESIGN section 7.3)")
+    return bool(adjoint)
 
 
 class ODEfunc(nn.Module):
@@ -43,12 +52,15 @@ class ODEfunc(nn.Module):
 
 
 class ODEBlock(nn.Module):
-    def __init__(self, maxTime, deltaT, n_nodes, indices, hidden1, odefunc, device, method="euler"):
+    def __init__(self, maxTime, deltaT, n_nodes, indices, hidden1, odefunc, device, method="euler", adjoint=True):
         super().__init__()
         self.maxTime = maxTime
         self.deltaT = deltaT
         self.device = device
         self.method = method                        # the reference hard-codes 'euler' (:168)
+        # extension: adjoint=False trains with the exact gradient of the Euler solve (torchdiffeq's odeint in place of
+        # odeint_adjoint); the default is the reference's adjoint gradient
+        self.adjoint = _check_adjoint(adjoint, method)
         self.integration_time = torch.from_numpy(ops.time_grid(maxTime, deltaT))
         self._dts = ops.step_sizes(ops.time_grid(maxTime, deltaT))
         self.odefunc = odefunc
@@ -80,5 +92,6 @@ class ODEBlock(nn.Module):
         """
         x2d = x.reshape(-1, x.size(-1))
         from .autograd import forward_with_grad
-        S, I, R = forward_with_grad(self.odefunc.graph, x2d, self._params(), self._dts, self.method, out_rows)
+        S, I, R = forward_with_grad(self.odefunc.graph, x2d, self._params(), self._dts, self.method, out_rows,
+                                    self.adjoint)
         return S.unsqueeze(-1), I.unsqueeze(-1), R.unsqueeze(-1)

@@ -23,6 +23,7 @@ import torch.nn as nn
 from . import autograd as _autograd
 from . import ops
 from .graph import DeviceGraph, concat_csr, csr_arrays
+from .ode_nn_ngraph_sim import _check_adjoint
 
 
 class ODEfunc(nn.Module):
@@ -74,12 +75,13 @@ class ODEfunc(nn.Module):
 
 
 class ODEBlock(nn.Module):
-    def __init__(self, maxTime, deltaT, hidden1, odefunc, device, method="euler"):
+    def __init__(self, maxTime, deltaT, hidden1, odefunc, device, method="euler", adjoint=True):
         super().__init__()
         self.maxTime = maxTime
         self.deltaT = deltaT
         self.device = device
         self.method = method
+        self.adjoint = _check_adjoint(adjoint, method)     # extension: see gnode.ode_nn_ngraph_sim.ODEBlock
         self.integration_time = torch.from_numpy(ops.time_grid(maxTime, deltaT))
         self._dts = ops.step_sizes(ops.time_grid(maxTime, deltaT))
         self.odefunc = odefunc
@@ -106,5 +108,5 @@ class ODEBlock(nn.Module):
         if g.n != x.size(0):
             raise ValueError(f"markers describe {g.n} nodes but the batch has {x.size(0)}")
         from .autograd import forward_with_grad
-        S, I, R = forward_with_grad(g, x, self._params(), self._dts, self.method, out_rows)
+        S, I, R = forward_with_grad(g, x, self._params(), self._dts, self.method, out_rows, self.adjoint)
         return S.unsqueeze(-1), I.unsqueeze(-1), R.unsqueeze(-1)

@@ -192,14 +192,24 @@ def _grad_buffers(params: dict, want_params: bool, want_x: bool, x2d: torch.Tens
 
 def backward(graph: DeviceGraph, x2d: torch.Tensor, params: dict, dts: np.ndarray, method: str, out_rows, sol: torch.Tensor,
              gS: torch.Tensor, gI: torch.Tensor, gR: torch.Tensor, keep="auto", persist: bool | None = None,
-             want_x: bool = False, want_params: bool = True) -> dict:
+             want_x: bool = False, want_params: bool = True, adjoint: bool = True) -> dict:
     """Adjoint parameter gradients (torchdiffeq odeint_adjoint semantics: Euler; rk4)
     given the saved trajectory `sol` and the upstream gradients of S, I, R ([n_out, rows]).
     keep: the forward's kept activations ("auto": ``sol.gnode_keep`` when `forward` attached it; None: recompute; Euler only).
     want_x: also dL/dx2d as key "x" ([rows, 3+H]; include/gnode.h gnode_backward_dx_f32; needs a trajectory produced
-    without keep); want_params=False: no parameter gradients (then want_x must be set)."""
+    without keep); want_params=False: no parameter gradients (then want_x must be set).
+    adjoint=False: the exact gradient of the Euler solve instead (backpropagation through the solver, include/gnode.h
+    gnode_backward_discrete_f32); `sol` must come from a forward without keep, `keep` and `persist`
+    are not used."""
     if not (want_x or want_params):
         raise _lib.GnodeError("backward: neither parameter nor input gradients requested")
+    if not adjoint:
+        if method == "rk4":
+            raise _lib.GnodeError("backward(adjoint=False) is Euler only: for RK4 the adjoint gradient is within 3.4e-5 of the "
+                                  "exact one (DESIGN section 7.3), below fp32 noise, so use adjoint=True")
+        if method != "euler":
+            raise _lib.GnodeError(f"unknown method {method!r} (euler | rk4)")
+        return _backward_discrete(graph, x2d, params, dts, out_rows, sol, gS, gI, gR, want_x=want_x, want_params=want_params)
     if method == "rk4":
         return _backward_rk4(graph, x2d, params, dts, out_rows, sol, gS, gI, gR, want_x=want_x, want_params=want_params)
     if method != "euler":
@@ -266,6 +276,34 @@ def _backward_rk4(graph: DeviceGraph, x2d, params: dict, dts, out_rows, sol, gS,
     else:
         _lib.check(lib.gnode_backward_rk4_f32(*args))
     backward.last_workspace = None               # (no persistent sweep on this path: nothing for backward_status to read)
+    return grads
+
+
+def _backward_discrete(graph: DeviceGraph, x2d, params: dict, dts, out_rows, sol, gS, gI, gR, want_x: bool = False,
+                       want_params: bool = True) -> dict:
+    """The exact gradient of a method='euler' forward: gnode_backward_discrete_f32."""
+    lib = _lib.load()
+    x2d = _f32c(x2d)
+    rows, H = x2d.shape[0], x2d.shape[1] - 3
+    dts = np.ascontiguousarray(dts, dtype=np.float32)
+    n_steps = int(dts.shape[0])
+    if out_rows is not None:
+        out_rows = np.ascontiguousarray(out_rows, dtype=np.int32)
+        n_out = int(out_rows.shape[0])
+    else:
+        n_out = n_steps + 1
+    for t in (gS, gI, gR):
+        if tuple(t.shape) != (n_out, rows):
+            raise _lib.GnodeError(f"upstream gradient shape {tuple(t.shape)} != {(n_out, rows)}")
+    grads, gp, gx = _grad_buffers(params, want_params, want_x, x2d)
+    ws = _workspace(lib.gnode_backward_discrete_workspace_bytes(graph.handle, rows, H), x2d.device)
+    p = pack_params({k: v.detach() for k, v in params.items()})
+    _lib.check(lib.gnode_backward_discrete_f32(
+        graph.handle, _lib.ptr(x2d), C.byref(p), _lib.host_ptr(dts), n_steps,
+        _lib.host_ptr(out_rows) if out_rows is not None else None, n_out, _lib.ptr(_f32c(sol)),
+        int(getattr(sol, "gnode_info", -1)), _lib.ptr(_f32c(gS)), _lib.ptr(_f32c(gI)), _lib.ptr(_f32c(gR)),
+        C.byref(gp) if gp is not None else None, _lib.ptr(gx), rows, H, _lib.ptr(ws), ws.numel(), _lib.stream_ptr()))
+    backward.last_workspace = (rows, H, ws)      # (its control block is zeroed by the call: backward_status reads 0)
     return grads
 
 

@@ -27,6 +27,10 @@ import torch.nn as nn
 from . import ops, sharding
 from .ode_nn import create_graph, sir_torch
 
+# GNODE_ADJOINT=0 (read ONCE at import): the drop-in scripts build their ODEBlock with adjoint=False and train with the exact
+# gradient of the Euler solve instead of the reference's adjoint gradient; argv is untouched.
+ADJOINT_DEFAULT = os.environ.get("GNODE_ADJOINT", "1") != "0"
+
 
 # --------------------------------------------------------------------------- CSV (ode_nn.py:374-392)
 def csv_trials(path_to_csv, columns, list_to_csv):
@@ -380,7 +384,8 @@ def main_single(argv=None):
     torch.set_default_dtype(torch.float32)
     print(device)
     odefunc = ODEfunc(A, args.beta[0], args.gamma[0], args.hidden, device)
-    model = ODEBlock(args.maxTime, args.deltaT, n_nodes, args.I_indices[0], args.hidden, odefunc, device).to(device)
+    model = ODEBlock(args.maxTime, args.deltaT, n_nodes, args.I_indices[0], args.hidden, odefunc, device,
+                     adjoint=ADJOINT_DEFAULT).to(device)
     run = Runner(model, args.lr, args.maxTime, args.deltaT, device, stack=True)
     xs, ys = run.place(xs, ys)
     pick = lambda ids: ([xs[i] for i in ids], [ys[i] for i in ids])
@@ -592,7 +597,7 @@ def main_multi(argv=None):
     torch.set_default_dtype(torch.float32)
     print(device)
     odefunc = ODEfunc(A_list, args.hidden, device)
-    model = ODEBlock(args.maxTime, args.deltaT, args.hidden, odefunc, device).to(device)
+    model = ODEBlock(args.maxTime, args.deltaT, args.hidden, odefunc, device, adjoint=ADJOINT_DEFAULT).to(device)
     run = Runner(model, args.lr, args.maxTime, args.deltaT, device, stack=False)
     tr, va, te = (run.place(*d) for d in (tr, va, te))
     best_loss, best_epoch, test_loss, t_test = np.inf, -1, float("nan"), 0.0

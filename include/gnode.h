@@ -14,7 +14,7 @@
  *     past the call.  "host" pointers are ordinary memory, read before return.
  *   - `stream` is a hipStream_t passed as void* (NULL = the default stream).
  *     All work is enqueued on it.  gnode_rhs_f32, gnode_forward_f32,
- *     gnode_backward_f32, gnode_rhs_vjp_f32, gnode_backward_rk4_f32, their _dx forms and gnode_l1_loss_f32 allocate nothing, synchronise nothing and keep nothing in
+ *     gnode_backward_f32, gnode_rhs_vjp_f32, gnode_backward_rk4_f32, their _dx forms, gnode_backward_discrete_f32 and gnode_l1_loss_f32 allocate nothing, synchronise nothing and keep nothing in
  *     the graph handle: every byte of scratch (including the partial sums of long
  *     "hub" rows) is carved from the caller's workspace, so they can be captured
  *     into a hipGraph on first use and one handle may serve several streams (each
@@ -256,6 +256,31 @@ int gnode_backward_rk4_dx_f32(gnode_graph_t g, const float* x, const gnode_param
                               int32_t n_steps, const int32_t* out_rows_host, int32_t n_out, const float* sol,
                               const float* gS, const float* gI, const float* gR, const gnode_params* grads,
                               int64_t rows, int32_t H, void* workspace, size_t workspace_bytes, void* stream, float* gx);
+
+/* ---- exact gradient of the Euler solve (backpropagation through the solver) -----------
+ * What torch autograd returns through a plain Euler loop y_i = y_{i-1} + dt_{i-1} f(y_{i-1}) (torchdiffeq's odeint instead
+ * of odeint_adjoint at ode_nn_ngraph_sim.py:168): the adjoint sweep of gnode_backward_f32 with every interval's Jacobian
+ * and parameter VJP evaluated at its LEFT endpoint y_{i-1}, where the forward took its slope, instead of at y_i.  With
+ * a = dL/dsol[G-1], for i = G-1 .. 1:
+ *     gtheta += dt_{i-1} (df/dtheta (y_{i-1}))^T a        a += dt_{i-1} (df/dy (y_{i-1}))^T a + dL/dsol[i-1]
+ * then the encoder on a.  DESIGN.md section 7.3 has the rule, the launch structure and how far the adjoint is from it.
+ *   sol        device [n_steps+1, 4*rows, H]: the trajectory of a gnode_forward_f32 call with method = 0 on THIS graph, same
+ *              n_steps / out_rows, produced WITHOUT a keep buffer
+ *   sol_info   what that forward reported through sol_info_host (A*Z_I(y_k) is then read back from the 4th slabs that
+ *              carry it), or -1 = unchecked (A*Z_I is gathered at every interval).  A keep-produced trajectory
+ *              (GNODE_SOL_KEEP): GNODE_ERR_ARG.
+ *   grads, gx  as gnode_backward_dx_f32 (gx columns 3, 4 sum the same terms at y_{i-1}); either may be NULL, not both.
+ * Other arguments as gnode_backward_f32.  Runs the recomputing one-launch-per-interval forms (H = 64: the fused interval
+ * kernel; H <= 32: the small-H interval kernel; other H: five launches per interval), never the kept, persistent or
+ * one-launch sweeps.  Deterministic (fixed-order reduction, no float atomics); enqueue-only (capturable).
+ *   workspace  device, >= gnode_backward_discrete_workspace_bytes(g, rows, H) */
+size_t gnode_backward_discrete_workspace_bytes(gnode_graph_t g, int64_t rows, int32_t H);
+int gnode_backward_discrete_f32(gnode_graph_t g, const float* x, const gnode_params* p, const float* dt_host,
+                                int32_t n_steps, const int32_t* out_rows_host, int32_t n_out,
+                                const float* sol, int32_t sol_info,
+                                const float* gS, const float* gI, const float* gR,
+                                const gnode_params* grads, float* gx,
+                                int64_t rows, int32_t H, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- Monte-Carlo SIR labels ------------------------------------------------
  * sir_torch(G, seed_set, beta, gamma, sims, T): ode_nn.py:30-88.
