@@ -122,13 +122,13 @@ def main():
 
     A_list = create_graphs()
     ns = [a.shape[0] for a in A_list]
-    import real_graph_cases as RC
-    gs = RC.graphs()
+    import fixture_cases as FC
+    gs = FC.graphs()
     # fb-social: the inputs of input_grad_fbsocial_B1_H64_T30
     H, maxTime, deltaT = 64, 30, 0.5
     d0 = dict(graph=np.int32(2), B=np.int32(1), H=np.int32(H), maxTime=np.int32(maxTime), deltaT=np.float64(deltaT),
               param_seed=np.int32(61), sample_seed=np.int32(6100), beta_scale=np.float64(0.1), method=np.asarray("euler"))
-    x, P, y = RC.inputs(d0, gs)
+    x, P, y = FC.inputs(d0, gs)
     A, n = A_list[2], ns[2]
     make = lambda: single.ODEBlock(maxTime, deltaT, n, [0], H, single.ODEfunc(A, 0.2, 0.1, H, dev), dev)
     yt = torch.from_numpy(y.reshape(1, n, maxTime, 3)).to(torch.float64)
@@ -141,7 +141,7 @@ def main():
     d0 = dict(picks=np.asarray([1, 0, 2, 1, 0, 3, 0, 1], dtype=np.int32), H=np.int32(H), maxTime=np.int32(maxTime),
               deltaT=np.float64(deltaT), param_seed=np.int32(62), sample_seed=np.int32(6200), beta_scale=np.float64(0.03),
               method=np.asarray("euler"))
-    x, P, y = RC.inputs(d0, gs)
+    x, P, y = FC.inputs(d0, gs)
     make = lambda: multi.ODEBlock(maxTime, deltaT, H, multi.ODEfunc(A_list, H, dev), dev)
     yt = torch.from_numpy(y).to(torch.float64)
     d = _run(make, x, P, lambda S, I, R: multi_loss(helpers, S, I, R, yt, maxTime, deltaT))

@@ -18,7 +18,7 @@ returns the adjoint at t0 for the WHOLE state, beta-gamma slab included -- what 
   input_grad_rk4_karate_B2_H64_T20    karate club under the RK4 (3/8 rule) adjoint, B = 2, H = 64
 
 Each stores the inputs by seed (gnode/synth.py; real graphs by index into real_graphs.npz, the multi-graph batch as
-real_graph_cases.inputs rebuilds it), "GX": x.grad[..., :5] as [rows, 5] of the float64 run, "yard32": how far the same
+fixture_cases.inputs rebuilds it), "GX": x.grad[..., :5] as [rows, 5] of the float64 run, "yard32": how far the same
 classes and rule run under float32 land from it -- max |GX32 - GX| / max |GX| over columns {S0, I0, R0} and over {beta,
 gamma}: the yardstick --, "rest_max": max |x.grad[..., 5:]| of the float64 run, and both losses.
 """
@@ -115,13 +115,13 @@ def main():
     _use("euler", single, multi)
     A_list = create_graphs()
     ns = [a.shape[0] for a in A_list]
-    import real_graph_cases as RC
-    gs = RC.graphs()
+    import fixture_cases as FC
+    gs = FC.graphs()
     # fb-social, configs[1]'s shape, the seeds and beta scale of real_single_fbsocial_H64_T30
     H, maxTime, deltaT = 64, 30, 0.5
     d0 = dict(graph=np.int32(2), B=np.int32(1), H=np.int32(H), maxTime=np.int32(maxTime), deltaT=np.float64(deltaT),
               param_seed=np.int32(61), sample_seed=np.int32(6100), beta_scale=np.float64(0.1), method=np.asarray("euler"))
-    x, P, y = RC.inputs(d0, gs)
+    x, P, y = FC.inputs(d0, gs)
     A, n = A_list[2], ns[2]
     make = lambda: single.ODEBlock(maxTime, deltaT, n, [0], H, single.ODEfunc(A, 0.2, 0.1, H, dev), dev)
     yt = torch.from_numpy(y.reshape(1, n, maxTime, 3)).to(torch.float64)
@@ -134,7 +134,7 @@ def main():
     d0 = dict(picks=np.asarray([4, 2, 3, 1, 0, 4, 2, 3], dtype=np.int32), H=np.int32(H), maxTime=np.int32(maxTime),
               deltaT=np.float64(deltaT), param_seed=np.int32(62), sample_seed=np.int32(6200), beta_scale=np.float64(0.03),
               method=np.asarray("euler"))
-    x, P, y = RC.inputs(d0, gs)
+    x, P, y = FC.inputs(d0, gs)
     make = lambda: multi.ODEBlock(maxTime, deltaT, H, multi.ODEfunc(A_list, H, dev), dev)
     yt = torch.from_numpy(y).to(torch.float64)
     d = _run(make, x, P, lambda S, I, R: multi_loss(helpers, S, I, R, yt, maxTime, deltaT))

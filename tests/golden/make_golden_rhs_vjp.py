@@ -11,7 +11,7 @@ torch.float64.
   rhs_vjp_heavy_B1_H64.npz       synth.heavy_tail_csr(1500, 6000, seed=4): rows longer than the hub threshold (96)
   rhs_vjp_karate_B1_H128.npz     karate club, B = 1, H = 128
   rhs_vjp_multi_0-2-1_H8.npz     multi-graph batch of karate, er200, loops40 (picks 0, 2, 1), H = 8
-Each holds the seeds of its inputs (tests/rhs_vjp_restate.py rebuilds them), the edge list (or the generator's arguments),
+Each holds the seeds of its inputs (tests/fixture_cases.py rebuilds them), the edge list (or the generator's arguments),
 dx at the rows listed in "rows_kept" (indices into the [4*rows, H] state; all rows for the small cases), dW and db in full.
 """
 import os
@@ -30,7 +30,7 @@ sys.path.insert(0, os.path.join(ROOT, "oracle"))
 sys.path.insert(0, os.path.join(ROOT, "gn-ode-sir_amd", "gnode"))
 import make_golden as MG  # noqa: E402
 import synth  # noqa: E402
-import rhs_vjp_restate as RV  # noqa: E402
+import fixture_cases as FC  # noqa: E402
 
 
 def _grads(f, x, v):
@@ -75,7 +75,7 @@ def main():
         P = synth.linear_params(H, seed=seed)
         f = single.ODEfunc(A, 0.2, 0.1, H, dev)
         _set_linear(f, P)
-        y, v = RV.vjp_inputs(B * n, H, seed + 100, n)
+        y, v = FC.vjp_inputs(B * n, H, seed + 100, n)
         gx, gW, gb = _grads(f, y, v)
         rows = 4 * B * n
         kept = np.arange(rows) if rows <= 2000 else np.sort(np.random.default_rng(seed).choice(rows, 1000, replace=False))
@@ -92,7 +92,7 @@ def main():
     P = synth.linear_params(H, seed=seed)
     _set_linear(f, P)
     ns = [a.shape[0] for a in A_list]
-    y, v = RV.multi_inputs(ns, picks, H, seed + 100)
+    y, v = FC.multi_inputs(ns, picks, H, seed + 100)
     gx, gW, gb = _grads(f, y, v)
     d = dict(H=np.int32(H), param_seed=np.int32(seed), input_seed=np.int32(seed + 100), picks=np.asarray(picks, dtype=np.int32),
              gx=gx, gW=gW, gb=gb)

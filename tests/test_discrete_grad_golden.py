@@ -1,15 +1,13 @@
-"""CPU: the float64 restatement of the exact Euler gradient (discrete_grad_restate.py) against the gradients of the reference's
+"""CPU: the float64 restatement of the exact Euler gradient (oracle/gnode_restate.py exact_grads) against the gradients of the reference's
 own classes under a differentiable Euler loop (tests/golden/discrete_*.npz, make_golden_discrete.py) -- one and many samples,
 H = 8 .. 128, hub rows of real fb-social, the eight-graph batch -- to float64 rounding; against central finite differences;
 and against the adjoint rule, which it must NOT be."""
 import numpy as np
 import pytest
-import torch
 
-import real_graph_cases as RC
-from discrete_grad_restate import KEYS, discrete_grads, linear_loss, reference_loss_grads
-from rhs_vjp_restate import adjoint_grads, l1_loss_of
-from test_input_grad_golden import _inputs
+import fixture_cases as FC
+import gnode_restate as RS
+from gnode_restate import KEYS
 
 CASES = ["discrete_karate_B2_H64_T20", "discrete_loops40_B3_H8_T5", "discrete_er200_B2_H48_T6",
          "discrete_er200_B2_H128_T4", "discrete_fbsocial_B1_H64_T30", "discrete_multi8_H8_T20"]
@@ -17,9 +15,9 @@ CASES = ["discrete_karate_B2_H64_T20", "discrete_loops40_B3_H8_T5", "discrete_er
 
 @pytest.mark.parametrize("name", CASES)
 def test_restated_discrete_gradient_matches_reference(name):
-    d = RC.load(name)
-    x2d, P, rp, ci, n, y = _inputs(d)
-    got = reference_loss_grads(x2d, P, rp, ci, n, int(d["maxTime"]), float(d["deltaT"]), y)
+    d = FC.load(name)
+    args = FC.restate_args(d)
+    x2d, got = args[0], RS.exact_grads(*args)
     scale = max(float(np.abs(d["G:" + k]).max()) for k in KEYS)
     for k in KEYS:
         want = d["G:" + k]
@@ -42,7 +40,7 @@ def test_restated_discrete_gradient_matches_reference(name):
 def test_restatement_matches_finite_differences():
     """central differences of the float64 loss through the same Euler loop, on a tiny graph, for a few entries of every
     parameter and of x's first five columns"""
-    sy = RC.synth()
+    sy = FC.synth()
     n, B, H = 9, 2, 8
     rp, ci = sy.er_csr(n, 14, seed=4)
     P = sy.linear_params(H, seed=9)
@@ -51,27 +49,9 @@ def test_restatement_matches_finite_differences():
     dts = np.full(5, 0.5, dtype=np.float32)
     rng = np.random.default_rng(2)
     gS, gI, gR = (rng.normal(size=(6, B * n)) for _ in range(3))
-    L = linear_loss(gS, gI, gR)
-    g = discrete_grads(x2d, P, rp, ci, n, dts, L)
-
-    def loss_at(P2, x2):
-        with torch.no_grad():
-            t = lambda a: torch.tensor(np.asarray(a), dtype=torch.float64)
-            from rhs_vjp_restate import _index, rhs
-            Pt = {k: t(v) for k, v in P2.items()}
-            xx = t(x2)
-            ridx, cidx = _index(rp, ci, n, xx.shape[0])
-            enc = lambda s: torch.relu(torch.nn.functional.linear(s.unsqueeze(-1), Pt["linearS1.weight"], Pt["linearS1.bias"]))
-            y = torch.cat((enc(xx[:, 0]), enc(xx[:, 1]), enc(xx[:, 2]), xx[:, 3:]))
-            sol = [y]
-            for dt in dts.astype(np.float64):
-                sol.append(sol[-1] + float(dt) * rhs(sol[-1], Pt["odefunc.linear.weight"], Pt["odefunc.linear.bias"], ridx, cidx))
-            sol = torch.stack(sol)
-            q = xx.shape[0]
-            ro = lambda Y: torch.nn.functional.linear(torch.relu(torch.nn.functional.linear(Y, Pt["linear3.weight"], Pt["linear3.bias"])),
-                                                      Pt["linearS2.weight"], Pt["linearS2.bias"])
-            out = torch.softmax(torch.cat((ro(sol[:, :q]), ro(sol[:, q:2 * q]), ro(sol[:, 2 * q:3 * q])), -1), 2)
-            return float(L(out[..., 0], out[..., 1], out[..., 2]))
+    L = RS.linear_loss(gS, gI, gR)
+    g = RS.exact_grads(x2d, P, (rp, ci), dts, L)
+    loss_at = lambda P2, x2: RS.forward_loss(x2, P2, (rp, ci), dts, L)
 
     h = 1e-6
     checked = 0
@@ -99,11 +79,8 @@ def test_restatement_matches_finite_differences():
 def test_exact_gradient_is_not_the_adjoint():
     """karate, B = 2, H = 64, maxTime 20: the adjoint rule (Jacobians at the right endpoints) misses the exact gradient of
     odefunc.linear.weight by more than 1 % of its largest entry -- the new gradient is a different one."""
-    d = RC.load("discrete_karate_B2_H64_T20")
-    x2d, P, rp, ci, n, y = _inputs(d)
-    maxTime, deltaT = int(d["maxTime"]), float(d["deltaT"])
-    out_rows = [int(i / deltaT) for i in range(maxTime)]
-    adj = adjoint_grads(x2d.reshape(int(d["B"]), n, -1), P, rp, ci, maxTime, deltaT, l1_loss_of(y, out_rows), method="euler")
+    d = FC.load("discrete_karate_B2_H64_T20")
+    adj = RS.adjoint(*FC.restate_args(d))
     k = "odefunc.linear.weight"
     want = d["G:" + k]
     gap = float(np.abs(adj[k] - want).max()) / float(np.abs(want).max())

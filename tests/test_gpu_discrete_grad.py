@@ -1,6 +1,6 @@
 """GPU: the exact gradient of the Euler solve, ODEBlock(adjoint=False) (include/gnode.h gnode_backward_discrete_f32; DESIGN
 section 7.3).  Held to float64 vectors of the reference's own classes under a differentiable Euler loop (tests/golden/
-discrete_*.npz), to the float64 restatement (discrete_grad_restate.py) over H = 4 .. 128, hub graphs, 75k x 4 and 2- / 3-point
+discrete_*.npz), to the float64 restatement (oracle/gnode_restate.py exact_grads) over H = 4 .. 128, hub graphs, 75k x 4 and 2- / 3-point
 grids, and to autograd through a Python Euler loop of ODEfunc(differentiable=True) on the GPU.  Then the call-level contract:
 deterministic, capturable, parameter gradients unchanged by gx, keep-produced trajectories refused, RK4 refused, and training
 with it (Adam, the drop-in script under GNODE_ADJOINT=0) works."""
@@ -9,10 +9,10 @@ import os
 import numpy as np
 import pytest
 
+import fixture_cases as FC
 import gnode_oracle as O
-import real_graph_cases as RC
-from discrete_grad_restate import KEYS, discrete_grads, linear_loss
-from test_gpu_input_grad import _adj, _case, _loss
+import gnode_restate as RS
+from gnode_restate import KEYS
 
 pytestmark = pytest.mark.gpu
 
@@ -30,7 +30,7 @@ def dev():
 
 def _exact_case(name, dev):
     """_case of the input-gradient tests (the same inputs) with the model switched to adjoint=False"""
-    d, model, xt, y = _case(name, dev)
+    d, model, xt, y = FC.gpu_case(name, dev)
     model.adjoint = False
     return d, model, xt, y
 
@@ -54,7 +54,7 @@ def _check(got, want, label, tol=TOL):
 def test_exact_gradient_matches_reference(name, fused, dev):
     d, model, xt, y = _exact_case(name, dev)
     xt.requires_grad_(True)
-    loss = _loss(d, model, xt, y, fused)
+    loss = FC.gpu_loss(d, model, xt, y, fused)
     assert abs(float(loss.detach()) - float(d["loss"])) <= 1e-6
     loss.backward()
     named = dict(model.named_parameters())
@@ -82,7 +82,7 @@ def _setup(rp, ci, B, H, dts, out_rows, dev, seed=0):
     import torch
     from gnode import ops
     from gnode.graph import DeviceGraph
-    sy = RC.synth()
+    sy = FC.synth()
     n = rp.shape[0] - 1
     P = sy.linear_params(H, seed=seed)
     x = sy.samples(n, B, H, seed=seed + 1).reshape(B * n, -1)
@@ -112,7 +112,7 @@ def test_exact_gradient_matches_restatement(H, graph, grid, dev):
         assert int(np.diff(rp).max()) > 96                     # rows above the hub threshold (GN_HUB_T)
     g, x2d, params, sol, (gS, gI, gR), P, x, gn = _setup(rp, ci, 2, H, dts, out_rows, dev, seed=H)
     got = _ops(g, x2d, params, dts, out_rows, gS, gI, gR, sol=sol, want_x=True)
-    want = discrete_grads(x, P, rp, ci, rp.shape[0] - 1, dts, linear_loss(*gn, out_rows))
+    want = RS.exact_grads(x, P, (rp, ci), dts, RS.linear_loss(*gn, out_rows))
     wx = want.pop("x")
     _check(got, want, (H, graph, grid))
     err = float(np.abs(got["x"].double().cpu().numpy()[:, :5] - wx[:, :5]).max()) / float(np.abs(wx[:, :5]).max())
@@ -121,12 +121,12 @@ def test_exact_gradient_matches_restatement(H, graph, grid, dev):
 
 def test_exact_gradient_75k_by_4(dev):
     """the large-graph H = 64 shape (many workgroups, XCD-affine tile queues), 3-point grid"""
-    sy = RC.synth()
+    sy = FC.synth()
     rp, ci = sy.er_csr(75000, 300000, seed=1)
     dts, out_rows = GRIDS["3pt"]
     g, x2d, params, sol, (gS, gI, gR), P, x, gn = _setup(rp, ci, 4, 64, dts, out_rows, dev, seed=7)
     got = _ops(g, x2d, params, dts, out_rows, gS, gI, gR, sol=sol, want_x=True)
-    want = discrete_grads(x, P, rp, ci, rp.shape[0] - 1, dts, linear_loss(*gn, out_rows))
+    want = RS.exact_grads(x, P, (rp, ci), dts, RS.linear_loss(*gn, out_rows))
     wx = want.pop("x")
     _check(got, want, "75k x 4")
     err = float(np.abs(got["x"].double().cpu().numpy()[:, :5] - wx[:, :5]).max()) / float(np.abs(wx[:, :5]).max())
@@ -141,9 +141,9 @@ def test_matches_autograd_through_a_python_euler_loop(H, dev):
     from gnode.ode_nn_ngraph_sim import ODEBlock, ODEfunc
     rp, ci, _ = O.er_graph(200, 700, seed=3)
     n, B, maxTime, deltaT = 200, 2, 6, 0.5
-    sy = RC.synth()
+    sy = FC.synth()
     P = sy.linear_params(H, seed=11)
-    f = ODEfunc(_adj(rp, ci), 0.2, 0.1, H, dev, differentiable=True)
+    f = ODEfunc(FC.adj(rp, ci), 0.2, 0.1, H, dev, differentiable=True)
     model = ODEBlock(maxTime, deltaT, n, [0], H, f, dev, adjoint=False).to(dev)
     model.load_state_dict({**model.state_dict(), **{k: torch.from_numpy(v) for k, v in P.items()}})
     x = torch.from_numpy(sy.samples(n, B, H, seed=12)).to(dev)
@@ -184,7 +184,7 @@ def test_repeatable_capturable_and_gx_free(case, dev):
     on whether gx is asked for"""
     import torch
     H = {"h64": 64, "h8": 8, "h48": 48}[case]
-    rp, ci = RC.synth().heavy_tail_csr(900, 5000, seed=2)
+    rp, ci = FC.synth().heavy_tail_csr(900, 5000, seed=2)
     dts, out_rows = np.full(11, 0.5, np.float32), np.arange(0, 12, 2, dtype=np.int32)
     g, x2d, params, sol, (gS, gI, gR), *_ = _setup(rp, ci, 3, H, dts, out_rows, dev, seed=21)
     run = lambda **kw: _ops(g, x2d, params, dts, out_rows, gS, gI, gR, sol=sol, **kw)
@@ -211,7 +211,7 @@ def test_keep_trajectory_and_rk4_are_refused(dev):
     from gnode.ode_nn_ngraph_sim import ODEBlock, ODEfunc
     rp, ci, _ = O.er_graph(300, 1200, seed=5)
     dts = np.full(11, 0.5, np.float32)
-    sy = RC.synth()
+    sy = FC.synth()
     P = sy.linear_params(64, seed=1)
     from gnode.graph import DeviceGraph
     g = DeviceGraph(rp, ci)
@@ -225,19 +225,19 @@ def test_keep_trajectory_and_rk4_are_refused(dev):
     with pytest.raises(_lib.GnodeError, match="Euler only"):
         ops.backward(g, x2d, params, dts, "rk4", None, sol, one, one, one, adjoint=False)
     with pytest.raises(_lib.GnodeError, match="Euler only"):
-        ODEBlock(6, 0.5, 300, [0], 64, ODEfunc(_adj(rp, ci), 0.2, 0.1, 64, dev), dev, method="rk4", adjoint=False)
+        ODEBlock(6, 0.5, 300, [0], 64, ODEfunc(FC.adj(rp, ci), 0.2, 0.1, 64, dev), dev, method="rk4", adjoint=False)
 
 
 def test_default_is_the_adjoint(dev):
     """ODEBlock() keeps the adjoint gradient bit for bit; adjoint=False gives a different one"""
     import torch
-    d, model, xt, y = _case("input_grad_fbsocial_B1_H64_T30", dev)
+    d, model, xt, y = FC.gpu_case("input_grad_fbsocial_B1_H64_T30", dev)
     assert model.adjoint is True
     grads = []
     for adjoint in (True, True, False):
         model.adjoint = adjoint
         model.zero_grad(set_to_none=True)
-        _loss(d, model, xt, y, True).backward()
+        FC.gpu_loss(d, model, xt, y, True).backward()
         grads.append(model.odefunc.linear.weight.grad.clone())
     assert torch.equal(grads[0], grads[1]) and not torch.equal(grads[0], grads[2])
 
@@ -249,7 +249,7 @@ def test_adam_lowers_the_loss(dev):
     losses = []
     for _ in range(30):
         opt.zero_grad(set_to_none=True)
-        loss = _loss(d, model, xt, y, True)
+        loss = FC.gpu_loss(d, model, xt, y, True)
         loss.backward()
         opt.step()
         losses.append(float(loss.detach()))
@@ -262,14 +262,13 @@ def test_drop_in_script_trains_with_exact_gradients(tmp_path, monkeypatch, dev):
     HIP-graph replay: the exact backward runs and the CSV row is written"""
     import pandas as pd
     from gnode import ops, trainer
-    from test_gpu_trainer import _mk_graph
     monkeypatch.setattr(trainer, "ADJOINT_DEFAULT", False)
     calls = []
     real = ops._backward_discrete
     monkeypatch.setattr(ops, "_backward_discrete", lambda *a, **k: (calls.append(1), real(*a, **k))[1])
     monkeypatch.chdir(tmp_path)
     os.makedirs("real_graphs"); os.makedirs("multi-graph-1/Experiments-seed2-toy")
-    G = _mk_graph("real_graphs/toy.pkl", 80, 240, 1)
+    G = FC.mk_graph("real_graphs/toy.pkl", 80, 240, 1)
     n = G.number_of_nodes()
     rng = np.random.default_rng(0)
     seeds = [sorted(rng.choice(n, 2, replace=False).tolist()) for _ in range(10)]

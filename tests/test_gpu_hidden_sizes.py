@@ -17,7 +17,8 @@ same oracles sits within 2e-5 of float64, ten times inside the backward bar."""
 import numpy as np
 import pytest
 
-import rhs_vjp_restate as RV
+import fixture_cases as FC
+import gnode_restate as RS
 
 pytestmark = pytest.mark.gpu
 
@@ -115,11 +116,11 @@ def euler_oracle(rp, ci, P, x, maxTime, deltaT, gs, out_rows):
 
 
 def rk4_oracle(rp, ci, P, x, maxTime, deltaT, gs, out_rows):
-    import torch
-    G = len(np.arange(0, maxTime, deltaT))
-    it = torch.as_tensor(np.arange(G) if out_rows is None else np.asarray(out_rows), dtype=torch.int64)
-    L = lambda S, I, R: sum((o[it] * torch.from_numpy(g).to(o.dtype)).sum() for o, g in zip((S, I, R), gs))
-    return RV.adjoint_grads(x, P, rp, ci, maxTime, deltaT, L, "rk4")
+    import gnode_oracle as O
+    grads = RS.adjoint(x.reshape(-1, x.shape[-1]), P, (rp, ci), O.step_sizes(O.time_grid(maxTime, deltaT)),
+                       RS.linear_loss(*gs, out_rows), "rk4")
+    del grads["x"]
+    return grads
 
 
 def check_grads(got, want, tag):
@@ -225,11 +226,11 @@ def _rhs_vjp_case(dev, rp, ci, n, B, H, tag, w_scale=1.0):
     import torch
     from gnode import ops, synth
     from gnode.graph import DeviceGraph
-    y, v = RV.vjp_inputs(B * n, H, seed=H, sample_rows=n)
+    y, v = FC.vjp_inputs(B * n, H, seed=H, sample_rows=n)
     P = synth.linear_params(H, seed=H + 7)
     W = (P["odefunc.linear.weight"] * w_scale).astype(np.float32)
     b = P["odefunc.linear.bias"]
-    wf, wy, wW, wb = RV.rhs_vjp_np(y, W, b, v, rp, ci, n)
+    wf, wy, wW, wb = RS.rhs_vjp_np(y, W, b, v, rp, ci)
     for name, w in (("dW", wW), ("db", wb)):                    # sensitivity: dpre is not ~0 everywhere
         assert float(np.abs(w).max()) > 1e-3 * float(np.abs(wy).max()), f"{tag}: {name} degenerate"
     g = DeviceGraph(rp, ci)

@@ -1,13 +1,13 @@
 """GPU: the ODEBlock input gradient x.grad (include/gnode.h gnode_backward_dx_f32 / gnode_backward_rk4_dx_f32) against
 float64 vectors the reference classes produced (tests/golden/input_grad_*.npz, make_golden_input_grad.py; the spec they
-pin: input_grad_restate.py, test_input_grad_golden.py), through the drop-in ODEBlocks, loss.backward() as the reference
+pin: oracle/gnode_restate.py, test_input_grad_golden.py), through the drop-in ODEBlocks, loss.backward() as the reference
 takes it.  Per column group ({S0, I0, R0} and {beta, gamma}) the max-abs error over the group's max-abs is held to
 max(2e-4, 4 x the reference's own fp32 distance).  Then the call-level contract: parameter gradients unchanged bit for bit,
 gx = NULL is the old call, two calls agree bitwise, keep + gx is refused, and one descent step on beta / gamma helps."""
 import numpy as np
 import pytest
 
-import real_graph_cases as RC
+import fixture_cases as FC
 
 pytestmark = pytest.mark.gpu
 
@@ -21,56 +21,6 @@ def dev():
     import torch
     assert torch.cuda.is_available(), "GPU tests need a GPU"
     return torch.device("cuda:0")
-
-
-def _adj(rp, ci):
-    import scipy.sparse as sp
-    n = rp.shape[0] - 1
-    return sp.csr_matrix((np.ones(ci.shape[0]), ci, rp), shape=(n, n))
-
-
-def _case(name, dev):
-    """(fixture, model, x as the model takes it, labels [rows, T, 3]) of one fixture"""
-    import torch
-    import gnode_oracle as O
-    from golden.labels import closed_form_labels
-    from gnode import ode_nn_ngraph_sim as single, ode_nn_ngraphs as multi
-    d = RC.load(name)
-    H, maxTime, deltaT, method = int(d["H"]), int(d["maxTime"]), float(d["deltaT"]), str(d["method"])
-    if "picks" in d:
-        gs = RC.graphs()
-        x, P, y = RC.inputs(d, gs)
-        model = multi.ODEBlock(maxTime, deltaT, H, multi.ODEfunc([_adj(*rc) for rc in gs], H, dev), dev)
-    else:
-        if "graph" in d:
-            gs = RC.graphs()
-            x, P, y = RC.inputs(d, gs)
-            rp, ci = gs[int(d["graph"])]
-        else:
-            n, B = int(d["n"]), int(d["B"])
-            rp, ci = O.csr_from_edges(n, d["edges"])
-            P = RC.synth().linear_params(H, seed=int(d["param_seed"]))
-            x = RC.synth().samples(n, B, H, seed=int(d["sample_seed"]))
-            y = closed_form_labels(B, n, maxTime).reshape(B * n, maxTime, 3)
-        model = single.ODEBlock(maxTime, deltaT, rp.shape[0] - 1, [0], H, single.ODEfunc(_adj(rp, ci), 0.2, 0.1, H, dev), dev,
-                                method=method)
-    model = model.to(dev)
-    model.load_state_dict({**model.state_dict(), **{k: torch.from_numpy(v) for k, v in P.items()}})
-    return d, model, torch.from_numpy(x).to(dev), y
-
-
-def _loss(d, model, xt, y, fused):
-    import torch
-    from gnode import ops
-    from gnode.autograd import l1_loss_sum
-    maxTime, deltaT = int(d["maxTime"]), float(d["deltaT"])
-    rows_out = ops.subsample_rows(maxTime, deltaT)
-    if fused:
-        S, I, R = model(xt, out_rows=rows_out)
-    else:
-        S, I, R = (a[torch.from_numpy(rows_out.astype(np.int64)).to(xt.device)] for a in model(xt))
-    rows = y.shape[0]
-    return l1_loss_sum(S, I, R, torch.from_numpy(y).to(xt.device), 1) / (rows * (maxTime - 1) * 3)
 
 
 def _group_errors(d, gx):
@@ -87,10 +37,10 @@ def _group_errors(d, gx):
 def test_input_grad_matches_reference(name, trainable, fused, persist, dev, monkeypatch):
     from gnode import ops
     monkeypatch.setattr(ops, "PERSIST_DEFAULT", persist)
-    d, model, xt, y = _case(name, dev)
+    d, model, xt, y = FC.gpu_case(name, dev)
     model.requires_grad_(trainable)
     xt.requires_grad_(True)
-    loss = _loss(d, model, xt, y, fused)
+    loss = FC.gpu_loss(d, model, xt, y, fused)
     assert abs(float(loss.detach()) - float(d["loss"])) <= 1e-6, (float(loss.detach()), float(d["loss"]))
     loss.backward()
     assert xt.grad is not None
@@ -108,7 +58,7 @@ def _ops_call(name, dev, persist=False):
     """(run) for the call-level tests: run(**kw) -> ops.backward's dict on one forward's trajectory (want_keep=False)"""
     import torch
     from gnode import ops
-    d, model, xt, y = _case(name, dev)
+    d, model, xt, y = FC.gpu_case(name, dev)
     params = {k: v.detach().contiguous() for k, v in model.state_dict().items() if k in ops.PARAM_KEYS}
     x2d = xt.reshape(-1, xt.shape[-1]).contiguous()
     dts = ops.step_sizes(ops.time_grid(int(d["maxTime"]), float(d["deltaT"])))
@@ -174,7 +124,7 @@ def test_null_gx_is_the_old_call(name, dev, monkeypatch):
 def test_keep_with_gx_is_refused(dev):
     import torch
     from gnode import _lib, ops
-    d, model, xt, y = _case("input_grad_fbsocial_B1_H64_T30", dev)
+    d, model, xt, y = FC.gpu_case("input_grad_fbsocial_B1_H64_T30", dev)
     params = {k: v.detach().contiguous() for k, v in model.state_dict().items() if k in ops.PARAM_KEYS}
     x2d = xt.reshape(-1, xt.shape[-1]).contiguous()
     dts = ops.step_sizes(ops.time_grid(int(d["maxTime"]), float(d["deltaT"])))
@@ -193,17 +143,17 @@ def test_descent_on_beta_gamma_lowers_the_loss(dev):
     from golden.labels import closed_form_labels
     from gnode import ops
     from gnode.ode_nn_ngraph_sim import ODEBlock, ODEfunc
-    sy = RC.synth()
+    sy = FC.synth()
     n, H, maxTime, deltaT = 1893, 64, 30, 0.5
     rp, ci = sy.er_csr(n, 13835, seed=0)
-    model = ODEBlock(maxTime, deltaT, n, [0], H, ODEfunc(_adj(rp, ci), 0.2, 0.1, H, dev), dev).to(dev)
+    model = ODEBlock(maxTime, deltaT, n, [0], H, ODEfunc(FC.adj(rp, ci), 0.2, 0.1, H, dev), dev).to(dev)
     model.load_state_dict({**model.state_dict(), **{k: torch.from_numpy(v) for k, v in sy.linear_params(H, seed=3).items()}})
     model.requires_grad_(False)
     x = torch.from_numpy(sy.samples(n, 1, H, seed=7)).to(dev)
     y = closed_form_labels(1, n, maxTime).reshape(n, maxTime, 3)
     d = {"maxTime": maxTime, "deltaT": deltaT}
     xt = x.clone().requires_grad_(True)
-    loss0 = _loss(d, model, xt, y, True)
+    loss0 = FC.gpu_loss(d, model, xt, y, True)
     loss0.backward()
     g = xt.grad[..., 3:5]
     assert float(g.abs().max()) > 0
@@ -211,6 +161,6 @@ def test_descent_on_beta_gamma_lowers_the_loss(dev):
     x1 = x.clone()
     x1[..., 3:5] -= step * g
     with torch.no_grad():
-        loss1 = _loss(d, model, x1, y, True)
+        loss1 = FC.gpu_loss(d, model, x1, y, True)
     print(f"descent: loss {float(loss0):.9f} -> {float(loss1):.9f}")
     assert float(loss1) < float(loss0)

@@ -15,7 +15,7 @@ rule ("G32:") is printed beside each GPU distance."""
 import numpy as np
 import pytest
 
-import real_graph_cases as RC
+import fixture_cases as FC
 
 pytestmark = pytest.mark.gpu
 
@@ -30,13 +30,6 @@ def dev():
 def _rel(a, b):
     a = np.asarray(a, np.float64); b = np.asarray(b, np.float64)
     return np.max(np.abs(a - b)) / (np.max(np.abs(b)) + 1e-12)
-
-
-def _adj(rc):
-    import scipy.sparse as sp
-    rp, ci = rc
-    n = rp.shape[0] - 1
-    return sp.csr_matrix((np.ones(ci.shape[0]), ci, rp), shape=(n, n))
 
 
 def _check(tag, d, model, S, I, R, y, rows):
@@ -65,7 +58,7 @@ def _check(tag, d, model, S, I, R, y, rows):
 
 
 @pytest.mark.parametrize("persist", [True, False], ids=["default", "per_step"])
-@pytest.mark.parametrize("name,kind", [(RC.MULTI[0], 3), (RC.MULTI[1], 0)], ids=["A", "B"])
+@pytest.mark.parametrize("name,kind", [(FC.MULTI[0], 3), (FC.MULTI[1], 0)], ids=["A", "B"])
 def test_multi_graph_training_gradient_on_real_graphs(name, kind, persist, dev, monkeypatch):
     """configs[4] through gnode.ode_nn_ngraphs: the default path (A: small-hidden persistent, kind 3; B: per step, kind 0)
     and the per-step kernels (ops.PERSIST_DEFAULT off) against the reference's float64 run."""
@@ -73,12 +66,12 @@ def test_multi_graph_training_gradient_on_real_graphs(name, kind, persist, dev, 
     from gnode import ops
     from gnode import ode_nn_ngraphs as multi
     monkeypatch.setattr(ops, "PERSIST_DEFAULT", persist)
-    gs = RC.graphs()
-    d = RC.load(name)
-    x, P, y = RC.inputs(d, gs)
+    gs = FC.graphs()
+    d = FC.load(name)
+    x, P, y = FC.inputs(d, gs)
     H, maxTime, deltaT = int(d["H"]), int(d["maxTime"]), float(d["deltaT"])
     rows = x.shape[0]
-    model = multi.ODEBlock(maxTime, deltaT, H, multi.ODEfunc([_adj(rc) for rc in gs], H, dev), dev).to(dev)
+    model = multi.ODEBlock(maxTime, deltaT, H, multi.ODEfunc([FC.adj(*rc) for rc in gs], H, dev), dev).to(dev)
     model.load_state_dict({**model.state_dict(), **{k: torch.from_numpy(v) for k, v in P.items()}})
     xt = torch.from_numpy(x).to(dev)
     rows_out = ops.subsample_rows(maxTime, deltaT)
@@ -96,7 +89,7 @@ def test_multi_graph_training_gradient_on_real_graphs(name, kind, persist, dev, 
 
 
 @pytest.mark.parametrize("keep", [True, False], ids=["kept", "recompute"])
-@pytest.mark.parametrize("name", RC.SINGLE)
+@pytest.mark.parametrize("name", FC.SINGLE)
 def test_single_graph_training_gradient_on_real_graphs(name, keep, dev, monkeypatch):
     """configs[1] / [2] through gnode.ode_nn_ngraph_sim at B = 1, H = 64, the full 59-interval adjoint on the real
     topology: the persistent launch (kind 2) with hub rows, over kept activations and recomputing them."""
@@ -104,13 +97,13 @@ def test_single_graph_training_gradient_on_real_graphs(name, keep, dev, monkeypa
     from gnode import ops
     from gnode.ode_nn_ngraph_sim import ODEBlock, ODEfunc
     monkeypatch.setattr(ops, "KEEP_DEFAULT", keep)
-    gs = RC.graphs()
-    d = RC.load(name)
-    x, P, y = RC.inputs(d, gs)
+    gs = FC.graphs()
+    d = FC.load(name)
+    x, P, y = FC.inputs(d, gs)
     rp, ci = gs[int(d["graph"])]
     n, H, maxTime, deltaT = rp.shape[0] - 1, int(d["H"]), int(d["maxTime"]), float(d["deltaT"])
     assert int((np.diff(rp) > 96).sum()) > 0                                 # hub rows (GN_HUB_T = 96)
-    model = ODEBlock(maxTime, deltaT, n, [0], H, ODEfunc(_adj((rp, ci)), 0.2, 0.1, H, dev), dev).to(dev)
+    model = ODEBlock(maxTime, deltaT, n, [0], H, ODEfunc(FC.adj(rp, ci), 0.2, 0.1, H, dev), dev).to(dev)
     model.load_state_dict({**model.state_dict(), **{k: torch.from_numpy(v) for k, v in P.items()}})
     rows_out = ops.subsample_rows(maxTime, deltaT)
     path = ops.forward_path(model.odefunc.graph, n, H, len(ops.time_grid(maxTime, deltaT)) - 1, len(rows_out), want_sol=True)[0]
@@ -128,7 +121,7 @@ def test_sir_philox_on_wikivote_bit_exact_vs_oracle(dev):
     import gnode_oracle as O
     from gnode.graph import DeviceGraph
     from gnode.ode_nn import sir_counts
-    rp, ci = RC.graphs()[RC.WIKI]
+    rp, ci = FC.graphs()[FC.WIKI]
     n, deg = rp.shape[0] - 1, np.diff(rp)
     hub = int(np.argmax(deg))
     assert deg[hub] == 1065

@@ -5,8 +5,9 @@ import ctypes as C
 import numpy as np
 import pytest
 
-import rhs_vjp_restate as RV
-from test_rhs_vjp_golden import VJP_CASES, load_multi_case, load_vjp_case
+import fixture_cases as FC
+import gnode_restate as RS
+from fixture_cases import VJP_CASES, load_multi_case, load_vjp_case
 
 pytestmark = pytest.mark.gpu
 
@@ -40,7 +41,7 @@ def _run(dev, rp, ci, y, v, P, want_f=True):
 def test_rhs_vjp_vs_reference_classes(name, dev):
     import torch
     from gnode import ops
-    rp, ci, n, y, v, P, d = load_vjp_case(name)
+    rp, ci, y, v, P, d = load_vjp_case(name)
     g, yt, W, b, vt, (f, gy, gW, gb) = _run(dev, rp, ci, y, v, P)
     assert _rel(gy.cpu().numpy()[d["rows_kept"]], d["gx"]) <= 1e-5
     assert _rel(gW.cpu().numpy(), d["gW"]) <= 1e-4
@@ -75,10 +76,10 @@ def test_rhs_vjp_vs_restatement(kind, n, m, B, H, dev):
     import gnode_oracle as O
     from gnode import synth
     rp, ci = synth.er_csr(n, m, seed=n + H) if kind == "er" else O.chung_lu_graph(n, m, seed=n + H)[:2]
-    y, v = RV.vjp_inputs(B * n, H, seed=H, sample_rows=n)
+    y, v = FC.vjp_inputs(B * n, H, seed=H, sample_rows=n)
     P = synth.linear_params(H, seed=H + 7)
     _, _, _, _, _, (f, gy, gW, gb) = _run(dev, rp, ci, y, v, P)
-    wf, wy, wW, wb = RV.rhs_vjp_np(y, P["odefunc.linear.weight"], P["odefunc.linear.bias"], v, rp, ci, n)
+    wf, wy, wW, wb = RS.rhs_vjp_np(y, P["odefunc.linear.weight"], P["odefunc.linear.bias"], v, rp, ci)
     assert _rel(f.cpu().numpy(), wf) <= 1e-5
     assert _rel(gy.cpu().numpy(), wy) <= 1e-5
     assert _rel(gW.cpu().numpy(), wW) <= 1e-4 and _rel(gb.cpu().numpy(), wb) <= 1e-4
@@ -111,7 +112,7 @@ def _integrate(f, y0, dts, method):
         if method == "euler":
             y = y + dt * f(0.0, y)
         else:
-            y = y + RV.rk4_step(lambda s: f(0.0, s), y, dt)
+            y = y + RS.rk4_step(lambda s: f(0.0, s), y, dt)
     return y
 
 
@@ -132,18 +133,18 @@ def test_differentiable_odefunc_single(method, H, dev):
     with torch.no_grad():
         f.linear.weight.copy_(torch.from_numpy(P["odefunc.linear.weight"]))
         f.linear.bias.copy_(torch.from_numpy(P["odefunc.linear.bias"]))
-    y0, w = RV.vjp_inputs(B * n, H, seed=9, sample_rows=n)
+    y0, w = FC.vjp_inputs(B * n, H, seed=9, sample_rows=n)
     y0[:3 * B * n] *= 0.5
     dts = [0.5, 0.5, 0.25]
     yt = torch.from_numpy(y0).to(dev).requires_grad_(True)
     loss = (_integrate(f, yt, dts, method) * torch.from_numpy(w).to(dev)).sum()
     loss.backward()
     # float64 restatement through autograd
-    ridx, cidx = RV._index(rp, ci, n, B * n)
+    ridx, cidx = RS.index(rp, ci, B * n)
     W64 = torch.from_numpy(P["odefunc.linear.weight"]).double().requires_grad_(True)
     b64 = torch.from_numpy(P["odefunc.linear.bias"]).double().requires_grad_(True)
     y64 = torch.from_numpy(y0).double().requires_grad_(True)
-    f64 = lambda t, y: RV.rhs(y, W64, b64, ridx, cidx)
+    f64 = lambda t, y: RS.rhs(y, W64, b64, ridx, cidx)
     L64 = (_integrate(f64, y64, dts, method) * torch.from_numpy(w).double()).sum()
     L64.backward()
     assert abs(float(loss) - float(L64)) <= 1e-4 * max(1.0, abs(float(L64)))
@@ -172,11 +173,11 @@ def test_differentiable_odefunc_multi(method, dev):
     loss.backward()
     rp, ci, _ = O.concat_csr(graphs, picks)
     tot = y.shape[1]
-    ridx, cidx = RV._index(rp, ci, tot, tot)
+    ridx, cidx = RS.index(rp, ci, tot)
     W64 = torch.from_numpy(P["odefunc.linear.weight"]).double().requires_grad_(True)
     b64 = torch.from_numpy(P["odefunc.linear.bias"]).double().requires_grad_(True)
     y64 = torch.from_numpy(y).double().requires_grad_(True)
-    f64 = lambda t, s: RV.rhs(s.reshape(4 * tot, H), W64, b64, ridx, cidx).view_as(s)
+    f64 = lambda t, s: RS.rhs(s.reshape(4 * tot, H), W64, b64, ridx, cidx).view_as(s)
     L64 = (_integrate(f64, y64, dts, method) * torch.from_numpy(w).double()).sum()
     L64.backward()
     assert _rel(yt.grad.cpu().numpy(), y64.grad.numpy()) <= 1e-4
@@ -194,7 +195,7 @@ def test_default_odefunc_is_unchanged(dev):
     rp, ci = synth.er_csr(n, 300, seed=2)
     A = sp.csr_matrix((np.ones(ci.shape[0]), ci, rp), shape=(n, n))
     f = ODEfunc(A, 0.2, 0.1, H, dev).to(dev)
-    y, _ = RV.vjp_inputs(2 * n, H, seed=1, sample_rows=n)
+    y, _ = FC.vjp_inputs(2 * n, H, seed=1, sample_rows=n)
     yt = torch.from_numpy(y).to(dev).requires_grad_(True)
     out = f(0.0, yt)
     assert not out.requires_grad

@@ -1,11 +1,11 @@
 """GPU: ODEBlock(method='rk4') trains -- the RK4 (3/8 rule) adjoint backward (gnode_backward_rk4_f32) against the
 reference's classes under the restated torchdiffeq rule (tests/golden/make_golden_rk4_adjoint.py) and against the float64
-restatement of tests/rhs_vjp_restate.py."""
+restatement of oracle/gnode_restate.py."""
 import numpy as np
 import pytest
 
-import rhs_vjp_restate as RV
-from test_rhs_vjp_golden import rk4_case
+import gnode_restate as RS
+from fixture_cases import rk4_case
 
 pytestmark = pytest.mark.gpu
 
@@ -86,9 +86,8 @@ def test_rk4_param_grads_vs_restatement(kind, n, m, B, H, maxTime, deltaT, sub, 
     idx = out_rows if sub else np.arange(len(grid))
     rng = np.random.default_rng(0)
     gs = [rng.normal(size=(len(idx), B * n)).astype(np.float32) for _ in range(3)]
-    it = torch.as_tensor(np.asarray(idx), dtype=torch.int64)
-    L = lambda S, I, R: sum((o[it] * torch.from_numpy(gg).to(o.dtype)).sum() for o, gg in zip((S, I, R), gs))
-    want = RV.adjoint_grads(x, P, rp, ci, maxTime, deltaT, L, "rk4")
+    want = RS.adjoint(x.reshape(B * n, 3 + H), P, (rp, ci), O.step_sizes(grid), RS.linear_loss(*gs, idx), "rk4")
+    del want["x"]
     g = DeviceGraph(rp, ci)
     params = {k: torch.from_numpy(v).to(dev) for k, v in P.items()}
     x2d = torch.from_numpy(x).to(dev).reshape(B * n, 3 + H)

@@ -7,6 +7,8 @@ import pickle
 import numpy as np
 import pytest
 
+import fixture_cases as FC
+
 pytestmark = pytest.mark.gpu
 
 
@@ -18,20 +20,12 @@ def dev():
     return torch.device("cuda:0")
 
 
-def _mk_graph(path, n, m, seed):
-    import networkx as nx
-    G = nx.gnm_random_graph(n, m, seed=seed)
-    G = nx.convert_node_labels_to_integers(G.subgraph(max(nx.connected_components(G), key=len)).copy(), ordering="sorted")
-    pickle.dump(G, open(path, "wb"))
-    return G
-
-
 def test_single_graph_entry_point(tmp_path, monkeypatch, dev):
     import pandas as pd
     from gnode.trainer import main_single
     monkeypatch.chdir(tmp_path)
     os.makedirs("real_graphs"); os.makedirs("multi-graph-1/Experiments-seed2-toy")
-    G = _mk_graph("real_graphs/toy.pkl", 80, 240, 1)
+    G = FC.mk_graph("real_graphs/toy.pkl", 80, 240, 1)
     n = G.number_of_nodes()
     rng = np.random.default_rng(0)
     seeds = [sorted(rng.choice(n, 2, replace=False).tolist()) for _ in range(10)]
@@ -82,7 +76,7 @@ def test_multi_graph_entry_point(tmp_path, monkeypatch, dev):
     ipg = [3, 3, 4]                                   # train: ga, gb ; val 2 + test 2 from gc
     rng = np.random.default_rng(3)
     for (name, (n, m)) in zip(names, sizes):
-        G = _mk_graph(f"real_graphs/{name}.pkl", n, m, 5)
+        G = FC.mk_graph(f"real_graphs/{name}.pkl", n, m, 5)
         d = f"multi-graph-1/Experiments-seed2-{name}"
         os.makedirs(d)
         k = max(ipg)
@@ -115,8 +109,8 @@ def test_multi_graph_entry_point_from_empty_directory(tmp_path, monkeypatch, dev
     from gnode.trainer import main_multi
     monkeypatch.chdir(tmp_path)
     os.makedirs("real_graphs")
-    G1 = _mk_graph("real_graphs/ga.pkl", 40, 100, 5)
-    G2 = _mk_graph("real_graphs/wiki-vote.pkl", 60, 200, 6)           # the name selects the raw-count convention
+    G1 = FC.mk_graph("real_graphs/ga.pkl", 40, 100, 5)
+    G2 = FC.mk_graph("real_graphs/wiki-vote.pkl", 60, 200, 6)           # the name selects the raw-count convention
     ipg, sim, T = [2, 3, 4], 50, 5                                    # train: ga, wiki-vote ; val 2 + test 2 from epinions
     save = "./multi-graph-1/Experiments-seed2-ga+wiki-vote+epinions"
     os.makedirs(save)
@@ -189,7 +183,7 @@ def test_two_rank_entry_point(tmp_path, dev):
     import pandas as pd
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     os.makedirs(tmp_path / "real_graphs"); os.makedirs(tmp_path / "multi-graph-1" / "Experiments-seed2-toy")
-    G = _mk_graph(str(tmp_path / "real_graphs" / "toy.pkl"), 60, 180, 4)
+    G = FC.mk_graph(str(tmp_path / "real_graphs" / "toy.pkl"), 60, 180, 4)
     n = G.number_of_nodes()
     rng = np.random.default_rng(1)
     seeds = [sorted(rng.choice(n, 2, replace=False).tolist()) for _ in range(8)]

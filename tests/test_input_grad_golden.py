@@ -1,44 +1,23 @@
-"""CPU: the float64 restatement of the ODEBlock input gradient (input_grad_restate.py) against x.grad of the reference's own
-classes (tests/golden/input_grad_*.npz, make_golden_input_grad.py) -- Euler and RK4, one and many samples, H = 8 .. 128, hub
-rows of real fb-social, the eight-graph batch with its marker column -- to float64 rounding; the columns past gamma are 0."""
+"""CPU: the float64 restatement of the ODEBlock input gradient (oracle/gnode_restate.py adjoint's "x") against x.grad of the
+reference's own classes (tests/golden/input_grad_*.npz, make_golden_input_grad.py) -- Euler and RK4, one and many samples,
+H = 8 .. 128, hub rows of real fb-social, the eight-graph batch with its marker column -- to float64 rounding; the columns
+past gamma are 0."""
 import numpy as np
 import pytest
 
-import gnode_oracle as O
-import real_graph_cases as RC
-from input_grad_restate import input_grad
+import fixture_cases as FC
+import gnode_restate as RS
 
 CASES = ["input_grad_karate_B2_H64_T20", "input_grad_loops40_B3_H8_T5", "input_grad_er200_B2_H48_T6",
          "input_grad_er200_B2_H128_T4", "input_grad_fbsocial_B1_H64_T30", "input_grad_multi8_H8_T20",
          "input_grad_rk4_karate_B2_H64_T20"]
 
 
-def _inputs(d):
-    """(x2d, P, rowptr, col, n, y) of a fixture"""
-    from golden.labels import closed_form_labels
-    if "picks" in d:
-        gs = RC.graphs()
-        x, P, y = RC.inputs(d, gs)
-        rp, ci, _ = O.concat_csr(gs, [int(p) for p in d["picks"]])
-        return x, P, rp, ci, x.shape[0], y
-    if "graph" in d:
-        gs = RC.graphs()
-        x, P, y = RC.inputs(d, gs)
-        rp, ci = gs[int(d["graph"])]
-        return x.reshape(-1, x.shape[-1]), P, rp, ci, rp.shape[0] - 1, y
-    n, B, H = int(d["n"]), int(d["B"]), int(d["H"])
-    rp, ci = O.csr_from_edges(n, d["edges"])
-    P = RC.synth().linear_params(H, seed=int(d["param_seed"]))
-    x = RC.synth().samples(n, B, H, seed=int(d["sample_seed"]))
-    y = closed_form_labels(B, n, int(d["maxTime"])).reshape(B * n, int(d["maxTime"]), 3)
-    return x.reshape(B * n, -1), P, rp, ci, n, y
-
-
 @pytest.mark.parametrize("name", CASES)
 def test_restated_input_gradient_matches_reference(name):
-    d = RC.load(name)
-    x2d, P, rp, ci, n, y = _inputs(d)
-    gx = input_grad(x2d, P, rp, ci, n, int(d["maxTime"]), float(d["deltaT"]), y, method=str(d["method"]))
+    d = FC.load(name)
+    args = FC.restate_args(d)
+    x2d, gx = args[0], RS.adjoint(*args, method=str(d["method"]))["x"]
     assert gx.shape == x2d.shape
     for c in (slice(0, 3), slice(3, 5)):
         want = d["GX"][:, c]
@@ -52,8 +31,7 @@ def test_restated_input_gradient_matches_reference(name):
 def test_restatement_is_sensitive_to_the_beta_gamma_rule():
     """Dropping the stage weights' middle terms (the Euler rule on an RK4 trajectory) misses the RK4 fixture by far more
     than the GPU tolerance: the fixtures do tell the rules apart."""
-    d = RC.load("input_grad_rk4_karate_B2_H64_T20")
-    x2d, P, rp, ci, n, y = _inputs(d)
-    gx = input_grad(x2d, P, rp, ci, n, int(d["maxTime"]), float(d["deltaT"]), y, method="euler")
+    d = FC.load("input_grad_rk4_karate_B2_H64_T20")
+    gx = RS.adjoint(*FC.restate_args(d), method="euler")["x"]
     err = np.abs(gx[:, 3:5] - d["GX"][:, 3:5]).max() / np.abs(d["GX"][:, 3:5]).max()
     assert err > 1e-2, err

@@ -209,7 +209,7 @@ def test_full_horizon_matches_reference(path):
 
 @pytest.mark.parametrize("path", _cases("adjoint_"), ids=os.path.basename)
 def test_adjoint_restatement_matches_reference_classes(path):
-    """The oracle's adjoint-Euler gradient (autograd over the oracle's OWN restatement of the RHS, head and encoder)
+    """The oracle's adjoint-Euler gradient (the OWN restatement of the RHS, its VJP, head and encoder, oracle/gnode_restate.py)
     against the gradients the REFERENCE classes produced under the same integrator rule
     (tests/golden/make_golden_adjoint.py: reference ODEBlock / ODEfunc / loss expression, float64): pins every
     derivative on the training path except torchdiffeq's adjoint rule itself, which both sides restate."""

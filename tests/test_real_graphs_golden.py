@@ -10,7 +10,7 @@ import pytest
 import scipy.sparse as sp
 
 import gnode_oracle as O
-import real_graph_cases as RC
+import fixture_cases as FC
 
 GPU_OUT, GPU_LOSS, GPU_GRAD = 2e-5, 1e-6, 2e-4          # test_gpu_real_graphs.py's tolerances
 
@@ -22,13 +22,13 @@ def _rel(a, b):
 
 @functools.lru_cache(maxsize=None)
 def _graphs():
-    return RC.graphs()
+    return FC.graphs()
 
 
 def _forward64(d, x, gs):
     """float64 oracle forward -> pred [maxTime, rows, 3] at the rows the loss sees (get_sir_t_nodes)"""
     maxTime, deltaT = int(d["maxTime"]), float(d["deltaT"])
-    P = {k: v.astype(np.float64) for k, v in RC.inputs(d, _graphs())[1].items()}
+    P = {k: v.astype(np.float64) for k, v in FC.inputs(d, _graphs())[1].items()}
     with O.precision(np.float64):
         if x.ndim == 2:
             out = O.odeblock_forward_multi(x.astype(np.float64), P, gs, maxTime, deltaT)
@@ -48,7 +48,7 @@ def _loss_and_cotangent(pred, y):
 def _adjoint64(d, x, pred, y, gs, stop_at=1):
     maxTime, deltaT = int(d["maxTime"]), float(d["deltaT"])
     _, g = _loss_and_cotangent(pred, y)
-    P = RC.inputs(d, _graphs())[1]
+    P = FC.inputs(d, _graphs())[1]
     rows = np.asarray([int(i / deltaT) for i in range(maxTime)])
     if x.ndim == 2:
         return O.adjoint_grads_multi(x, P, gs, maxTime, deltaT, g[..., 0], g[..., 1], g[..., 2], out_rows=rows, dtype="float64",
@@ -61,8 +61,8 @@ def _adjoint64(d, x, pred, y, gs, stop_at=1):
 @functools.lru_cache(maxsize=None)
 def _oracle(name):
     """(fixture, x, y, pred, grads) of the oracle's float64 run on a fixture's inputs"""
-    d = RC.load(name)
-    x, _, y = RC.inputs(d, _graphs())
+    d = FC.load(name)
+    x, _, y = FC.inputs(d, _graphs())
     pred = _forward64(d, x, _graphs())
     return d, x, y, pred, _adjoint64(d, x, pred, y, _graphs())
 
@@ -87,7 +87,7 @@ def test_real_graphs_are_create_graphs_output():
         assert (n, A.nnz, int(np.diff(rp).max()), int(A.diagonal().sum())) == want[j]
 
 
-@pytest.mark.parametrize("name", RC.MULTI + RC.SINGLE)
+@pytest.mark.parametrize("name", FC.MULTI + FC.SINGLE)
 def test_oracle_matches_reference_on_real_graphs(name):
     """float64 oracle forward: the reference's float64 outputs at the kept rows to 1e-12 beyond their float32 rounding
     (half an ulp, 2^-25 on values below 1), its loss to 1e-9; the oracle's adjoint: the reference's gradients to 1e-9 relative."""
@@ -108,8 +108,8 @@ def test_concatenated_csr_is_the_references_block_diag():
     """ode_nn_ngraphs.py:65-71 rebuilds scipy.sparse.block_diag of the picked graphs on every RHS call; the concatenated
     CSR (oracle concat_csr, the product's graph.concat_csr) is that matrix, for both compositions."""
     gs = _graphs()
-    for name in RC.MULTI:
-        picks = [int(p) for p in RC.load(name)["picks"]]
+    for name in FC.MULTI:
+        picks = [int(p) for p in FC.load(name)["picks"]]
         rp, ci, off = O.concat_csr(gs, picks)
         mats = [sp.csr_matrix((np.ones(c.shape[0]), c, r), shape=(r.shape[0] - 1,) * 2) for r, c in gs]
         bd = sp.block_diag([mats[p] for p in picks]).tocsr()
@@ -122,13 +122,13 @@ def test_multi_adjoint_equals_batched_single_graph():
     """Composition B (eight wiki-vote samples): the multi-graph adjoint over the concatenated CSR with B = 1 is the
     single-graph adjoint over B = 8 copies of the graph (the block-diagonal replication of ode_nn_ngraph_sim.py)."""
     gs = _graphs()
-    d, x, y, pred, want = _oracle(RC.MULTI[1])
-    _, P, _ = RC.inputs(d, gs)
+    d, x, y, pred, want = _oracle(FC.MULTI[1])
+    _, P, _ = FC.inputs(d, gs)
     maxTime, deltaT = int(d["maxTime"]), float(d["deltaT"])
-    n = gs[RC.WIKI][0].shape[0] - 1
+    n = gs[FC.WIKI][0].shape[0] - 1
     _, g = _loss_and_cotangent(pred, y)
     rows = np.asarray([int(i / deltaT) for i in range(maxTime)])
-    got = O.adjoint_grads_torch(x.reshape(8, n, x.shape[1]), P, *gs[RC.WIKI], maxTime, deltaT, g[..., 0], g[..., 1], g[..., 2],
+    got = O.adjoint_grads_torch(x.reshape(8, n, x.shape[1]), P, *gs[FC.WIKI], maxTime, deltaT, g[..., 0], g[..., 1], g[..., 2],
                                 out_rows=rows, dtype="float64")
     for k in want:
         assert np.max(np.abs(got[k] - want[k])) <= 1e-12 * (np.max(np.abs(want[k])) + 1e-12), k
@@ -141,9 +141,9 @@ def test_dropped_hub_segment_is_caught():
     The kept outputs catch it by orders of magnitude; the summed parameter gradients alone move by about half their
     tolerance (one row of 7 066), so the outputs are the check that holds this fault."""
     gs = _graphs()
-    name = RC.SINGLE[1]
+    name = FC.SINGLE[1]
     d, x, y, _, _ = _oracle(name)
-    rp, ci = gs[RC.WIKI]
+    rp, ci = gs[FC.WIKI]
     deg = np.diff(rp)
     hub = int(np.argmax(deg))
     assert deg[hub] == 1065
@@ -153,7 +153,7 @@ def test_dropped_hub_segment_is_caught():
     rp2 = rp.copy()
     rp2[hub + 1:] -= 32
     bad = list(gs)
-    bad[RC.WIKI] = (rp2, ci[keep])
+    bad[FC.WIKI] = (rp2, ci[keep])
     pred = _forward64(d, x, bad)
     out_err = _out_err(d, pred)
     grad_err = _grad_err(d, _adjoint64(d, x, pred, y, bad))
@@ -165,13 +165,13 @@ def test_swapped_composition_is_caught():
     """Composition A's first two picks (wiki-vote, fb-social) swapped: the concatenated CSR still has the batch's row count,
     but the gather runs over the wrong graphs' blocks -- what a cached graph of the wrong composition would do."""
     gs = _graphs()
-    d, x, y, _, _ = _oracle(RC.MULTI[0])
+    d, x, y, _, _ = _oracle(FC.MULTI[0])
     picks = [int(p) for p in d["picks"]]
     assert picks[0] != picks[1]
     picks[0], picks[1] = picks[1], picks[0]
     rp, ci, off = O.concat_csr(gs, picks)
     assert off[-1] == x.shape[0]
-    P = {k: v.astype(np.float64) for k, v in RC.inputs(d, gs)[1].items()}
+    P = {k: v.astype(np.float64) for k, v in FC.inputs(d, gs)[1].items()}
     maxTime, deltaT = int(d["maxTime"]), float(d["deltaT"])
     with O.precision(np.float64):
         out = O.odeblock_forward_single(x[None].astype(np.float64), P, rp, ci, maxTime, deltaT)
@@ -181,7 +181,7 @@ def test_swapped_composition_is_caught():
     assert out_err > GPU_OUT
 
 
-@pytest.mark.parametrize("name", [RC.MULTI[0], RC.SINGLE[0]])
+@pytest.mark.parametrize("name", [FC.MULTI[0], FC.SINGLE[0]])
 def test_missing_interval_is_caught(name):
     """The adjoint sweep stops one interval early (interval 1 -> 0 is never taken): gradients miss by more than 2e-4."""
     d, x, y, pred, _ = _oracle(name)

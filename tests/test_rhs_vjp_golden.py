@@ -1,17 +1,14 @@
-"""CPU: the float64 restatements of the RHS vector-Jacobian product and of the RK4 adjoint (tests/rhs_vjp_restate.py)
+"""CPU: the float64 restatements of the RHS vector-Jacobian product and of the RK4 adjoint (oracle/gnode_restate.py)
 against what the REFERENCE's classes produced through torch autograd (tests/golden/make_golden_rhs_vjp.py,
 make_golden_rk4_adjoint.py), and the argument checks of the two new C entries (no GPU: every call is refused before
 anything is launched)."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 
-import rhs_vjp_restate as RV
-
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-VJP_CASES = ["rhs_vjp_karate_B2_H64", "rhs_vjp_loops40_B3_H8", "rhs_vjp_heavy_B1_H64", "rhs_vjp_karate_B1_H128"]
+import gnode_restate as RS
+from fixture_cases import VJP_CASES, load_multi_case, load_vjp_case, rk4_case
 
 
 def _rel(a, b):
@@ -19,40 +16,12 @@ def _rel(a, b):
     return np.max(np.abs(a - b)) / (np.max(np.abs(b)) + 1e-30)
 
 
-def load_vjp_case(name):
-    """(rowptr, col, n, y, v, P, fixture dict) of a single-graph VJP fixture."""
-    import gnode_oracle as O
-    from gnode import synth
-    d = dict(np.load(os.path.join(GOLDEN, name + ".npz")))
-    n, B, H = int(d["n"]), int(d["B"]), int(d["H"])
-    if "graph_seed" in d:
-        rp, ci = synth.heavy_tail_csr(n, int(d["m"]), seed=int(d["graph_seed"]))
-    else:
-        rp, ci = O.csr_from_edges(n, d["edges"])
-    y, v = RV.vjp_inputs(B * n, H, int(d["input_seed"]), n)
-    P = synth.linear_params(H, seed=int(d["param_seed"]))
-    return rp, ci, n, y, v, P, d
-
-
-def load_multi_case(name="rhs_vjp_multi_0-2-1_H8"):
-    """(graphs [(rowptr, col)], picks, y [4, sumN, H], v, P, fixture dict)."""
-    import gnode_oracle as O
-    from gnode import synth
-    d = dict(np.load(os.path.join(GOLDEN, name + ".npz")))
-    H = int(d["H"])
-    graphs = [O.csr_from_edges(int(d[f"n{j}"]), d[f"edges{j}"]) for j in range(3)]
-    ns = [int(d[f"n{j}"]) for j in range(3)]
-    picks = [int(p) for p in d["picks"]]
-    y, v = RV.multi_inputs(ns, picks, H, int(d["input_seed"]))
-    return graphs, picks, y, v, synth.linear_params(H, seed=int(d["param_seed"])), d
-
-
 @pytest.mark.parametrize("name", VJP_CASES)
 def test_vjp_restatement_vs_reference(name):
-    rp, ci, n, y, v, P, d = load_vjp_case(name)
+    rp, ci, y, v, P, d = load_vjp_case(name)
     if name == "rhs_vjp_heavy_B1_H64":
         assert int(np.diff(rp).max()) > 96                      # hub rows (GN_HUB_T) in the graph
-    _, gy, gW, gb = RV.rhs_vjp_np(y, P["odefunc.linear.weight"], P["odefunc.linear.bias"], v, rp, ci, n)
+    _, gy, gW, gb = RS.rhs_vjp_np(y, P["odefunc.linear.weight"], P["odefunc.linear.bias"], v, rp, ci)
     assert _rel(gy[d["rows_kept"]], d["gx"]) <= 1e-9
     assert _rel(gW, d["gW"]) <= 1e-9
     assert _rel(gb, d["gb"]) <= 1e-9
@@ -63,33 +32,27 @@ def test_vjp_restatement_vs_reference_multi():
     graphs, picks, y, v, P, d = load_multi_case()
     rp, ci, off = O.concat_csr(graphs, picks)
     tot, H = y.shape[1], y.shape[2]
-    _, gy, gW, gb = RV.rhs_vjp_np(y.reshape(4 * tot, H), P["odefunc.linear.weight"], P["odefunc.linear.bias"],
-                                  v.reshape(4 * tot, H), rp, ci, tot)
+    _, gy, gW, gb = RS.rhs_vjp_np(y.reshape(4 * tot, H), P["odefunc.linear.weight"], P["odefunc.linear.bias"],
+                                 v.reshape(4 * tot, H), rp, ci)
     assert _rel(gy.reshape(4, tot, H), d["gx"]) <= 1e-9
     assert _rel(gW, d["gW"]) <= 1e-9 and _rel(gb, d["gb"]) <= 1e-9
 
 
-def rk4_case(name):
-    """(rowptr, col, x [B, n, 3+H], P, labels [rows, T, 3], fixture dict) of an RK4-adjoint fixture."""
+def _rk4_fixture_adjoint(name, method):
+    """(the restated adjoint of `method` on an RK4-adjoint fixture's inputs for the reference's L1 loss, fixture dict)"""
     import gnode_oracle as O
-    from gnode import synth
-    from golden.labels import closed_form_labels
-    d = dict(np.load(os.path.join(GOLDEN, name + ".npz")))
-    n, B, H, maxTime = int(d["n"]), int(d["B"]), int(d["H"]), int(d["maxTime"])
-    rp, ci = O.csr_from_edges(n, d["edges"])
-    x = synth.samples(n, B, H, seed=int(d["sample_seed"]))
-    P = synth.linear_params(H, seed=int(d["param_seed"]))
-    y = closed_form_labels(B, n, maxTime).reshape(B * n, maxTime, 3)
-    return rp, ci, x, P, y, d
+    from gnode import ops
+    rp, ci, x, P, y, d = rk4_case(name)
+    maxTime, deltaT = int(d["maxTime"]), float(d["deltaT"])
+    return RS.adjoint(x.reshape(-1, x.shape[-1]), P, (rp, ci), O.step_sizes(O.time_grid(maxTime, deltaT)),
+                     RS.l1_loss_of(y, ops.subsample_rows(maxTime, deltaT)), method), d
 
 
 @pytest.mark.parametrize("name", ["rk4_adjoint_karate_H64_T20", "rk4_adjoint_loops40_H8_T5"])
 def test_rk4_adjoint_restatement_vs_reference(name):
-    from gnode import ops
-    rp, ci, x, P, y, d = rk4_case(name)
-    maxTime, deltaT = int(d["maxTime"]), float(d["deltaT"])
-    got = RV.adjoint_grads(x, P, rp, ci, maxTime, deltaT, RV.l1_loss_of(y, ops.subsample_rows(maxTime, deltaT)), "rk4")
-    for k, g in got.items():
+    got, d = _rk4_fixture_adjoint(name, "rk4")
+    for k in RS.KEYS:
+        g = got[k]
         if k == "linearS2.bias":                                 # exact gradient 0 (softmax shift invariance)
             assert abs(float(g[0])) <= 1e-12 and abs(float(d["G:" + k][0])) <= 1e-12
             continue
@@ -98,10 +61,7 @@ def test_rk4_adjoint_restatement_vs_reference(name):
 
 def test_rk4_and_euler_adjoints_differ():
     """The RK4 fixtures are not the Euler rule in disguise: the Euler restatement on the same inputs is far off."""
-    from gnode import ops
-    rp, ci, x, P, y, d = rk4_case("rk4_adjoint_karate_H64_T20")
-    maxTime, deltaT = int(d["maxTime"]), float(d["deltaT"])
-    eu = RV.adjoint_grads(x, P, rp, ci, maxTime, deltaT, RV.l1_loss_of(y, ops.subsample_rows(maxTime, deltaT)), "euler")
+    eu, d = _rk4_fixture_adjoint("rk4_adjoint_karate_H64_T20", "euler")
     assert _rel(eu["odefunc.linear.weight"], d["G:odefunc.linear.weight"]) > 1e-3
 
 

@@ -62,13 +62,13 @@ def single(tag, rp, ci, B, H, maxTime):
 
 
 def main():
-    import real_graph_cases as RC
-    gs = RC.graphs()
+    import fixture_cases as FC
+    gs = FC.graphs()
     single("er75k_B4_H64_T30", *synth.er_csr(75000, 1000000 // 2, seed=0), 4, 64, 30)
     single("fbsocial_B1_H64_T30", *gs[2], 1, 64, 30)
     single("fbsocial_B1_H128_T30", *gs[2], 1, 128, 30)
     from gnode import ode_nn_ngraphs as multi
-    x, _, _ = RC.inputs(RC.load("input_grad_multi8_H8_T20"), gs)         # the eight-graph training batch, 24 410 nodes
+    x, _, _ = FC.inputs(FC.load("input_grad_multi8_H8_T20"), gs)         # the eight-graph training batch, 24 410 nodes
     x2d = torch.from_numpy(x).to(dev).contiguous()
     import scipy.sparse as sp
     adj = [sp.csr_matrix((np.ones(c.shape[0]), c, r), shape=(r.shape[0] - 1,) * 2) for r, c in gs]

@@ -63,10 +63,10 @@ def main():
     single("karate_B1_H64_T20", *O.csr_from_edges(int(d["n"]), d["edges"]), 1, 64, 20)
     single("fbsize_B8_H64_T30", *synth.er_csr(1893, 13835, seed=0), 8, 64, 30)
     single("er75k_B4_H64_T30", *synth.er_csr(75000, 1000000 // 2, seed=0), 4, 64, 30)
-    import real_graph_cases as RC
+    import fixture_cases as FC
     from gnode import ode_nn_ngraphs as multi
-    gs = RC.graphs()
-    x, _, _ = RC.inputs(RC.load("input_grad_multi8_H8_T20"), gs)
+    gs = FC.graphs()
+    x, _, _ = FC.inputs(FC.load("input_grad_multi8_H8_T20"), gs)
     x2d = torch.from_numpy(x).to(dev).contiguous()
     import scipy.sparse as sp
     adj = [sp.csr_matrix((np.ones(c.shape[0]), c, r), shape=(r.shape[0] - 1,) * 2) for r, c in gs]
