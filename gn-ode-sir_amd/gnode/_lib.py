@@ -13,23 +13,6 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgnode_hip.so")
 
-EXPORTS = [
-    "gnode_last_error", "gnode_version",
-    "gnode_graph_create", "gnode_graph_destroy", "gnode_graph_info",
-    "gnode_rhs_workspace_bytes", "gnode_rhs_f32",
-    "gnode_forward_workspace_bytes", "gnode_forward_f32", "gnode_forward_status", "gnode_backward_status", "gnode_forward_path", "gnode_sol_carries_neighbour_sums", "gnode_forward_keep_bytes",
-    "gnode_backward_workspace_bytes", "gnode_backward_f32",
-    "gnode_rhs_vjp_workspace_bytes", "gnode_rhs_vjp_f32", "gnode_backward_rk4_workspace_bytes", "gnode_backward_rk4_f32",
-    "gnode_backward_dx_f32", "gnode_backward_rk4_dx_f32",
-    "gnode_backward_discrete_workspace_bytes", "gnode_backward_discrete_f32",
-    "gnode_sir_workspace_bytes", "gnode_sir_coins_workspace_bytes",
-    "gnode_sir_mc_philox", "gnode_sir_mc_philox_scan", "gnode_sir_mc_philox_counted", "gnode_sir_mc_coins",
-    "gnode_dmp_workspace_bytes", "gnode_dmp_f32",
-    "gnode_meanfield_workspace_bytes", "gnode_meanfield_f64",
-    "gnode_l1_loss_workspace_bytes", "gnode_l1_loss_f32", "gnode_l1_loss_scaled_f32",
-    "gnode_profile_enable", "gnode_profile_read", "gnode_profile_read_kind",
-]
-
 
 class GnodeError(RuntimeError):
     pass
@@ -45,6 +28,61 @@ class Grads(C.Structure):
     _fields_ = Params._fields_
 
 
+_vp, _i32, _i64, _sz, _f64, _int, _u64 = C.c_void_p, C.c_int32, C.c_int64, C.c_size_t, C.c_double, C.c_int, C.c_uint64
+_P, _pi32, _pi64, _pf64 = C.POINTER(Params), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_double)
+_BWD = [_vp, _vp, _P, _vp, _i32, _vp, _i32, _vp, _vp, _sz, _vp, _vp, _vp, _P, _i64, _i32, _vp, _sz, _vp, _i32, _i32]
+_BWD_RK4 = [_vp, _vp, _P, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _P, _i64, _i32, _vp, _sz, _vp]
+_SIR = [_vp, _vp, _i32, _f64, _f64, _i64, _i64, _i32, _u64, _vp, _vp, _sz, _vp]
+_L1 = [_vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _vp, _vp]
+
+# The C ABI of include/gnode.h, once: name -> (restype, argtypes).  `load` applies it; tests/test_abi.py holds it against the
+# header's prototypes.  (The _dx / _scan / _counted entries take their base entry's arguments, the extra one last.)
+ABI = {
+    "gnode_last_error": (C.c_char_p, []),
+    "gnode_version": (_int, []),
+    "gnode_graph_create": (_int, [_vp, _vp, _i32, _i64, C.POINTER(_vp)]),
+    "gnode_graph_destroy": (_int, [_vp]),
+    "gnode_graph_info": (_int, [_vp, _pi32, _pi64, _pi32]),
+    "gnode_rhs_workspace_bytes": (_sz, [_vp, _i64, _i32]),
+    "gnode_rhs_f32": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _sz, _vp]),
+    "gnode_forward_workspace_bytes": (_sz, [_vp, _i64, _i32, _i32]),
+    "gnode_forward_f32": (_int, [_vp, _vp, _P, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _i64, _i32, _vp, _sz,
+                                 _vp, _i32, _pi32]),
+    "gnode_forward_status": (_int, [_i64, _i32, _i32, _vp, _vp, _pi32]),
+    "gnode_backward_status": (_int, [_i64, _i32, _vp, _vp, _pi32]),
+    "gnode_forward_path": (_int, [_vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _pi32]),
+    "gnode_sol_carries_neighbour_sums": (_int, [_vp, _i64, _i32, _i32, _i32, _i32]),
+    "gnode_forward_keep_bytes": (_sz, [_vp, _i64, _i32, _i32, _i32]),
+    "gnode_backward_workspace_bytes": (_sz, [_vp, _i64, _i32]),
+    "gnode_backward_f32": (_int, _BWD),
+    "gnode_backward_dx_f32": (_int, _BWD + [_vp]),
+    "gnode_rhs_vjp_workspace_bytes": (_sz, [_vp, _i64, _i32]),
+    "gnode_rhs_vjp_f32": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _sz, _vp]),
+    "gnode_backward_rk4_workspace_bytes": (_sz, [_vp, _i64, _i32]),
+    "gnode_backward_rk4_f32": (_int, _BWD_RK4),
+    "gnode_backward_rk4_dx_f32": (_int, _BWD_RK4 + [_vp]),
+    "gnode_backward_discrete_workspace_bytes": (_sz, [_vp, _i64, _i32]),
+    "gnode_backward_discrete_f32": (_int, [_vp, _vp, _P, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _P, _vp, _i64, _i32,
+                                           _vp, _sz, _vp]),
+    "gnode_sir_workspace_bytes": (_sz, [_vp, _i32]),
+    "gnode_sir_coins_workspace_bytes": (_sz, []),
+    "gnode_sir_mc_philox": (_int, _SIR),
+    "gnode_sir_mc_philox_scan": (_int, _SIR),
+    "gnode_sir_mc_philox_counted": (_int, _SIR + [C.POINTER(_u64)]),
+    "gnode_sir_mc_coins": (_int, [_vp, _vp, _i64, _i32, _vp, _i32, _f64, _f64, _i64, _i32, _vp, _i64, _vp, _pi64, _vp, _sz, _vp]),
+    "gnode_dmp_workspace_bytes": (_sz, [_vp]),
+    "gnode_dmp_f32": (_int, [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _sz, _vp]),
+    "gnode_meanfield_workspace_bytes": (_sz, [_vp]),
+    "gnode_meanfield_f64": (_int, [_vp, _vp, _i32, _f64, _vp, _vp, _i32, _f64, _f64, _vp, _vp, _vp, _pi64, _vp, _sz, _vp]),
+    "gnode_l1_loss_workspace_bytes": (_sz, []),
+    "gnode_l1_loss_f32": (_int, _L1 + [_vp, _sz, _vp]),
+    "gnode_l1_loss_scaled_f32": (_int, _L1 + [C.c_float, _vp, _sz, _vp]),
+    "gnode_profile_enable": (_int, [_int]),
+    "gnode_profile_read": (_int, [_pf64, _pi64, _pf64, _pi64]),
+    "gnode_profile_read_kind": (_int, [_i32, _pf64, _pi64]),
+}
+EXPORTS = list(ABI)
+
 _lib = None
 
 
@@ -59,80 +97,9 @@ def load():
             "(hipcc --offload-arch=gfx950).  There is no CPU fallback for the GN-ODE path.")
     import torch  # noqa: F401  -- first, so that one HIP runtime (torch's libamdhip64.so.7) serves both
     lib = C.CDLL(LIB_PATH)
-    vp, i32, i64, sz, f32p = C.c_void_p, C.c_int32, C.c_int64, C.c_size_t, C.POINTER(C.c_float)
-    lib.gnode_last_error.restype = C.c_char_p
-    lib.gnode_version.restype = C.c_int
-    lib.gnode_graph_create.argtypes = [vp, vp, i32, i64, C.POINTER(vp)]
-    lib.gnode_graph_destroy.argtypes = [vp]
-    lib.gnode_graph_info.argtypes = [vp, C.POINTER(i32), C.POINTER(i64), C.POINTER(i32)]
-    lib.gnode_rhs_workspace_bytes.argtypes = [vp, i64, i32]
-    lib.gnode_rhs_workspace_bytes.restype = sz
-    lib.gnode_rhs_f32.argtypes = [vp, vp, vp, vp, vp, i64, i32, vp, sz, vp]
-    lib.gnode_forward_workspace_bytes.argtypes = [vp, i64, i32, i32]
-    lib.gnode_forward_workspace_bytes.restype = sz
-    lib.gnode_sol_carries_neighbour_sums.argtypes = [vp, i64, i32, i32, i32, i32]
-    lib.gnode_sol_carries_neighbour_sums.restype = C.c_int
-    lib.gnode_forward_keep_bytes.argtypes = [vp, i64, i32, i32, i32]
-    lib.gnode_forward_keep_bytes.restype = sz
-    lib.gnode_forward_f32.argtypes = [vp, vp, C.POINTER(Params), vp, i32, i32, vp, i32, vp, vp, vp, vp, vp, sz, i64, i32, vp, sz, vp, i32, C.POINTER(i32)]
-    lib.gnode_forward_status.argtypes = [i64, i32, i32, vp, vp, C.POINTER(i32)]
-    lib.gnode_forward_status.restype = C.c_int
-    lib.gnode_backward_status.argtypes = [i64, i32, vp, vp, C.POINTER(i32)]
-    lib.gnode_backward_status.restype = C.c_int
-    lib.gnode_forward_path.argtypes = [vp, i64, i32, i32, i32, i32, i32, i32, C.POINTER(i32)]
-    lib.gnode_forward_path.restype = C.c_int
-    lib.gnode_meanfield_workspace_bytes.argtypes = [vp]
-    lib.gnode_meanfield_workspace_bytes.restype = sz
-    lib.gnode_meanfield_f64.argtypes = [vp, vp, i32, C.c_double, vp, vp, i32, C.c_double, C.c_double, vp, vp, vp,
-                                        C.POINTER(C.c_int64), vp, sz, vp]
-    lib.gnode_dmp_workspace_bytes.argtypes = [vp]
-    lib.gnode_dmp_workspace_bytes.restype = sz
-    lib.gnode_dmp_f32.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, sz, vp]
-    lib.gnode_l1_loss_workspace_bytes.argtypes = []
-    lib.gnode_l1_loss_workspace_bytes.restype = sz
-    lib.gnode_l1_loss_f32.argtypes = [vp, vp, vp, vp, i32, i64, i32, i32, vp, vp, vp, sz, vp]
-    lib.gnode_l1_loss_f32.restype = C.c_int
-    lib.gnode_l1_loss_scaled_f32.argtypes = [vp, vp, vp, vp, i32, i64, i32, i32, vp, vp, C.c_float, vp, sz, vp]
-    lib.gnode_l1_loss_scaled_f32.restype = C.c_int
-    lib.gnode_backward_workspace_bytes.argtypes = [vp, i64, i32]
-    lib.gnode_backward_workspace_bytes.restype = sz
-    lib.gnode_backward_f32.argtypes = [vp, vp, C.POINTER(Params), vp, i32, vp, i32, vp, vp, sz, vp, vp, vp,
-                                       C.POINTER(Params), i64, i32, vp, sz, vp, i32, i32]
-    lib.gnode_backward_f32.restype = C.c_int
-    lib.gnode_backward_dx_f32.argtypes = lib.gnode_backward_f32.argtypes + [vp]
-    lib.gnode_backward_dx_f32.restype = C.c_int
-    lib.gnode_rhs_vjp_workspace_bytes.argtypes = [vp, i64, i32]
-    lib.gnode_rhs_vjp_workspace_bytes.restype = sz
-    lib.gnode_rhs_vjp_f32.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, vp, sz, vp]
-    lib.gnode_rhs_vjp_f32.restype = C.c_int
-    lib.gnode_backward_rk4_workspace_bytes.argtypes = [vp, i64, i32]
-    lib.gnode_backward_rk4_workspace_bytes.restype = sz
-    lib.gnode_backward_rk4_f32.argtypes = [vp, vp, C.POINTER(Params), vp, i32, vp, i32, vp, vp, vp, vp,
-                                           C.POINTER(Params), i64, i32, vp, sz, vp]
-    lib.gnode_backward_rk4_f32.restype = C.c_int
-    lib.gnode_backward_rk4_dx_f32.argtypes = lib.gnode_backward_rk4_f32.argtypes + [vp]
-    lib.gnode_backward_rk4_dx_f32.restype = C.c_int
-    lib.gnode_backward_discrete_workspace_bytes.argtypes = [vp, i64, i32]
-    lib.gnode_backward_discrete_workspace_bytes.restype = sz
-    lib.gnode_backward_discrete_f32.argtypes = [vp, vp, C.POINTER(Params), vp, i32, vp, i32, vp, i32, vp, vp, vp,
-                                                C.POINTER(Params), vp, i64, i32, vp, sz, vp]
-    lib.gnode_backward_discrete_f32.restype = C.c_int
-    lib.gnode_sir_workspace_bytes.argtypes = [vp, i32]
-    lib.gnode_sir_workspace_bytes.restype = sz
-    lib.gnode_sir_coins_workspace_bytes.restype = sz
-    lib.gnode_sir_mc_philox.argtypes = [vp, vp, i32, C.c_double, C.c_double, i64, i64, i32, C.c_uint64, vp, vp, sz, vp]
-    lib.gnode_sir_mc_philox_scan.argtypes = lib.gnode_sir_mc_philox.argtypes
-    lib.gnode_sir_mc_philox_scan.restype = C.c_int
-    lib.gnode_sir_mc_philox_counted.argtypes = lib.gnode_sir_mc_philox.argtypes + [C.POINTER(C.c_uint64)]
-    lib.gnode_sir_mc_philox_counted.restype = C.c_int
-    lib.gnode_sir_mc_coins.argtypes = [vp, vp, i64, i32, vp, i32, C.c_double, C.c_double, i64, i32, vp, i64, vp,
-                                       C.POINTER(i64), vp, sz, vp]
-    lib.gnode_profile_enable.argtypes = [C.c_int]
-    lib.gnode_profile_read.argtypes = [C.POINTER(C.c_double), C.POINTER(i64), C.POINTER(C.c_double), C.POINTER(i64)]
-    lib.gnode_profile_read_kind.argtypes = [i32, C.POINTER(C.c_double), C.POINTER(i64)]
-    for fn in ("gnode_graph_create", "gnode_graph_destroy", "gnode_graph_info", "gnode_rhs_f32", "gnode_forward_f32",
-               "gnode_sir_mc_philox", "gnode_sir_mc_coins"):
-        getattr(lib, fn).restype = C.c_int
+    for name, (restype, argtypes) in ABI.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
     if lib.gnode_version() < 224:
         raise GnodeError(f"{LIB_PATH} is stale (ABI {lib.gnode_version()} < 224): rebuild it (gnode.build.build_lib)")
     _lib = lib

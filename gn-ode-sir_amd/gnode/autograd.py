@@ -53,14 +53,13 @@ class _GNODEForward(torch.autograd.Function):
 
 def forward_with_grad(graph, x2d, params, dts, method="euler", out_rows=None, adjoint=True):
     """adjoint=False: the backward is the exact gradient of the Euler solve (ops.backward(adjoint=False)); it raises for rk4."""
-    if not adjoint and method != "euler":
-        raise ops._lib.GnodeError(f"adjoint=False is Euler only (method {method!r}): DESIGN section 7.3")
+    adjoint = ops._check_adjoint(adjoint, method)
     if not _needs_grad(params, x2d):
         with torch.no_grad():
             S, I, R, _ = ops.forward(graph, x2d, {k: v.detach() for k, v in params.items()}, dts, method, out_rows)
         return S, I, R
     keys = tuple(params.keys())
-    return _GNODEForward.apply(graph, x2d, dts, method, out_rows, bool(adjoint), keys, *[params[k] for k in keys])
+    return _GNODEForward.apply(graph, x2d, dts, method, out_rows, adjoint, keys, *[params[k] for k in keys])
 
 
 class _RHSFunction(torch.autograd.Function):

@@ -56,37 +56,41 @@ def _device_graph_for(G):
     return dg
 
 
+def _philox_launch(entry: str, graph: DeviceGraph, seed_set, beta, gamma, sims, T, rng_seed, sim_offset, device, counts, *extra):
+    """One launch of a gnode_sir_mc_philox* entry into `counts` (zeros [3, T, n] on `device` when None); returns counts."""
+    lib = _lib.load()
+    seeds = np.ascontiguousarray(list(seed_set), dtype=np.int32)
+    if counts is None:
+        counts = torch.zeros((3, T, graph.n), dtype=torch.int32, device=device)
+    ws = torch.empty(lib.gnode_sir_workspace_bytes(graph.handle, T), dtype=torch.uint8, device=counts.device)
+    _lib.check(getattr(lib, entry)(graph.handle, _lib.host_ptr(seeds), int(seeds.shape[0]), float(beta), float(gamma),
+                                   int(sims), int(sim_offset), int(T), C.c_uint64(int(rng_seed) & (2**64 - 1)),
+                                   _lib.ptr(counts), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(), *extra))
+    return counts
+
+
 def sir_counts(graph: DeviceGraph, seed_set, beta, gamma, sims, T, rng_seed, sim_offset=0, device="cuda",
                counts: torch.Tensor | None = None, edge_scan: bool = False) -> torch.Tensor:
     """Production Monte-Carlo on the GPU: uint32 (stored as int32 tensor) counts [3, T, n].
 
     `counts` may be passed to accumulate several shards of the sims range into one array.  edge_scan=True runs the
     edge-parallel statement of the same model (`gnode_sir_mc_philox_scan`: identical counts, O(nnz) per step)."""
-    lib = _lib.load()
-    seeds = np.ascontiguousarray(list(seed_set), dtype=np.int32)
-    if counts is None:
-        counts = torch.zeros((3, T, graph.n), dtype=torch.int32, device=device)
-    ws_bytes = lib.gnode_sir_workspace_bytes(graph.handle, T)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=counts.device)
-    fn = lib.gnode_sir_mc_philox_scan if edge_scan else lib.gnode_sir_mc_philox
-    _lib.check(fn(graph.handle, _lib.host_ptr(seeds), int(seeds.shape[0]), float(beta), float(gamma),
-                  int(sims), int(sim_offset), int(T), C.c_uint64(int(rng_seed) & (2**64 - 1)),
-                  _lib.ptr(counts), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()))
-    return counts
+    return _philox_launch("gnode_sir_mc_philox_scan" if edge_scan else "gnode_sir_mc_philox", graph, seed_set, beta, gamma,
+                          sims, T, rng_seed, sim_offset, device, counts)
 
 
 def sir_counts_counted(graph: DeviceGraph, seed_set, beta, gamma, sims, T, rng_seed, sim_offset=0, device="cuda"):
     """`sir_counts` through the kernel's profiling instantiation: (counts, stats) with stats = what the launch did --
     Philox blocks computed, infection coins drawn, recovery coins drawn, CSR entries read (bench.py's `sir` roofline)."""
-    lib = _lib.load()
-    seeds = np.ascontiguousarray(list(seed_set), dtype=np.int32)
-    counts = torch.zeros((3, T, graph.n), dtype=torch.int32, device=device)
-    ws = torch.empty(lib.gnode_sir_workspace_bytes(graph.handle, T), dtype=torch.uint8, device=counts.device)
     st = (C.c_uint64 * 4)()
-    _lib.check(lib.gnode_sir_mc_philox_counted(graph.handle, _lib.host_ptr(seeds), int(seeds.shape[0]), float(beta), float(gamma),
-                                               int(sims), int(sim_offset), int(T), C.c_uint64(int(rng_seed) & (2**64 - 1)),
-                                               _lib.ptr(counts), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(), st))
+    counts = _philox_launch("gnode_sir_mc_philox_counted", graph, seed_set, beta, gamma, sims, T, rng_seed, sim_offset, device,
+                            None, st)
     return counts, {"philox_blocks": int(st[0]), "infection_coins": int(st[1]), "recovery_coins": int(st[2]), "csr_entries_read": int(st[3])}
+
+
+def _counts_f64(counts: torch.Tensor) -> np.ndarray:
+    """The kernels' uint32 counts (held in an int32 tensor) as float64 on the host."""
+    return (counts.cpu().numpy().astype(np.int64) & 0xFFFFFFFF).astype(np.float64)
 
 
 def sir_counts_coins(n, table: np.ndarray, seed_set, beta, gamma, sims, T, coins: np.ndarray, device="cuda"):
@@ -135,8 +139,7 @@ def sir_torch(G, seed_set, beta, gamma, sims=10000, T=20, rng_seed=None, coins=N
         if rng_seed is None:
             rng_seed = int(torch.randint(0, 2**62, (1,), dtype=torch.int64).item())
         counts = sir_counts(_device_graph_for(G), seed_set, beta, gamma, sims, T, rng_seed)
-    c = counts.cpu().numpy().astype(np.int64) & 0xFFFFFFFF
-    c = c.astype(np.float64)
+    c = _counts_f64(counts)
     if normalize_t0:
         c[:, 0] *= float(sims)
     return c[0][None], c[1][None], c[2][None]

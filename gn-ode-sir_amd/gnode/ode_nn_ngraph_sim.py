@@ -9,21 +9,21 @@ in libgnode_hip.so on the MI355X.
 """
 from __future__ import annotations
 
-import numpy as np
 import torch
 import torch.nn as nn
 
 from . import autograd as _autograd
 from . import ops
 from .graph import DeviceGraph
+from .ops import _check_adjoint  # noqa: F401  (the method / adjoint rule; imported from here by ode_nn_ngraphs and the tests)
 
 
-def _check_adjoint(adjoint, method) -> bool:
-    """ODEBlock's `adjoint` flag: False (the exact gradient of the solve) exists for Euler only."""
-    if not adjoint and method != "euler":
-        raise ops._lib.GnodeError(f"ODEBlock(adjoint=False) is Euler only (method {method!r}): for RK4 the adjoint gradient is "
-                                  "within 3.4e-5 of the exact one, below fp32 noise (DESIGN section 7.3)")
-    return bool(adjoint)
+def _rhs(func, graph, flat):
+    """Both ODEfunc.forwards on flat [4*rows, H]: an autograd node when `func.differentiable` and grad is on, else the no_grad RHS."""
+    if func.differentiable and torch.is_grad_enabled():
+        return _autograd.rhs(graph, flat, func.linear.weight, func.linear.bias)
+    with torch.no_grad():
+        return ops.rhs(graph, flat, func.linear.weight, func.linear.bias)
 
 
 class ODEfunc(nn.Module):
@@ -45,14 +45,14 @@ class ODEfunc(nn.Module):
 
     def forward(self, t, x):
         """x [4*B*n, H] -> dx (reference :58-96).  t is unused there too."""
-        if self.differentiable and torch.is_grad_enabled():
-            return _autograd.rhs(self.graph, x, self.linear.weight, self.linear.bias)
-        with torch.no_grad():
-            return ops.rhs(self.graph, x, self.linear.weight, self.linear.bias)
+        return _rhs(self, self.graph, x)
 
 
-class ODEBlock(nn.Module):
-    def __init__(self, maxTime, deltaT, n_nodes, indices, hidden1, odefunc, device, method="euler", adjoint=True):
+class _ODEBlock(nn.Module):
+    """What the single-graph ODEBlock and gnode.ode_nn_ngraphs.ODEBlock share: the time grid, the sub-modules (created in the
+    reference's order -- nn.Linear draws from the global RNG -- under the reference's state_dict keys) and the solve."""
+
+    def __init__(self, maxTime, deltaT, hidden1, odefunc, device, method, adjoint):
         super().__init__()
         self.maxTime = maxTime
         self.deltaT = deltaT
@@ -64,19 +64,11 @@ class ODEBlock(nn.Module):
         self.integration_time = torch.from_numpy(ops.time_grid(maxTime, deltaT))
         self._dts = ops.step_sizes(ops.time_grid(maxTime, deltaT))
         self.odefunc = odefunc
-        self.n_nodes = n_nodes
-        self.indices = torch.tensor(indices, requires_grad=False)
         self.hidden1 = hidden1
         self.linearS1 = nn.Linear(1, hidden1)
         self.ln = nn.LayerNorm(hidden1)             # unused in the reference forward
         self.linear3 = nn.Linear(hidden1, 4)
         self.linearS2 = nn.Linear(4, 1)
-
-    def init_weights(self):
-        """reference :139-146 (defined, never called)."""
-        nn.init.kaiming_normal_(self.linearS1.weight, mode="fan_in", nonlinearity="relu")
-        nn.init.kaiming_normal_(self.linear3.weight, mode="fan_in", nonlinearity="relu")
-        self.linearS2.weight.data.normal_(0, 1)
 
     def _params(self):
         return {"odefunc.linear.weight": self.odefunc.linear.weight, "odefunc.linear.bias": self.odefunc.linear.bias,
@@ -84,14 +76,28 @@ class ODEBlock(nn.Module):
                 "linear3.weight": self.linear3.weight, "linear3.bias": self.linear3.bias,
                 "linearS2.weight": self.linearS2.weight, "linearS2.bias": self.linearS2.bias}
 
+    def _solve(self, graph, x2d, out_rows):
+        """x2d [rows, 3+H] on `graph` -> (S, I, R), each [G, rows, 1]."""
+        S, I, R = _autograd.forward_with_grad(graph, x2d, self._params(), self._dts, self.method, out_rows, self.adjoint)
+        return S.unsqueeze(-1), I.unsqueeze(-1), R.unsqueeze(-1)
+
+
+class ODEBlock(_ODEBlock):
+    def __init__(self, maxTime, deltaT, n_nodes, indices, hidden1, odefunc, device, method="euler", adjoint=True):
+        super().__init__(maxTime, deltaT, hidden1, odefunc, device, method, adjoint)
+        self.n_nodes = n_nodes
+        self.indices = torch.tensor(indices, requires_grad=False)
+
+    def init_weights(self):
+        """reference :139-146 (defined, never called)."""
+        nn.init.kaiming_normal_(self.linearS1.weight, mode="fan_in", nonlinearity="relu")
+        nn.init.kaiming_normal_(self.linear3.weight, mode="fan_in", nonlinearity="relu")
+        self.linearS2.weight.data.normal_(0, 1)
+
     def forward(self, x, out_rows=None):
         """x [B, n, 3+H] -> (S, I, R), each [G, B*n, 1] (reference :148-188).
 
         out_rows (extension): ascending grid indices to emit instead of all G points;
         `ops.subsample_rows(maxTime, deltaT)` fuses get_sir_t_nodes_torch (ode_nn.py:249-261).
         """
-        x2d = x.reshape(-1, x.size(-1))
-        from .autograd import forward_with_grad
-        S, I, R = forward_with_grad(self.odefunc.graph, x2d, self._params(), self._dts, self.method, out_rows,
-                                    self.adjoint)
-        return S.unsqueeze(-1), I.unsqueeze(-1), R.unsqueeze(-1)
+        return self._solve(self.odefunc.graph, x.reshape(-1, x.size(-1)), out_rows)

@@ -20,10 +20,8 @@ import collections
 import torch
 import torch.nn as nn
 
-from . import autograd as _autograd
-from . import ops
 from .graph import DeviceGraph, concat_csr, csr_arrays
-from .ode_nn_ngraph_sim import _check_adjoint
+from .ode_nn_ngraph_sim import _ODEBlock, _rhs
 
 
 class ODEfunc(nn.Module):
@@ -66,40 +64,16 @@ class ODEfunc(nn.Module):
         g = self.graph_for(x[3, :, 2])
         if g.n != x.size(1):
             raise ValueError(f"markers describe {g.n} nodes but the state has {x.size(1)}")
-        if self.differentiable and torch.is_grad_enabled():
-            flat = x.reshape(4 * x.size(1), x.size(2))
-            return _autograd.rhs(g, flat, self.linear.weight, self.linear.bias).view_as(x)
-        with torch.no_grad():
-            flat = x.reshape(4 * x.size(1), x.size(2))
-            return ops.rhs(g, flat, self.linear.weight, self.linear.bias).view_as(x)
+        return _rhs(self, g, x.reshape(4 * x.size(1), x.size(2))).view_as(x)
 
 
-class ODEBlock(nn.Module):
+class ODEBlock(_ODEBlock):
     def __init__(self, maxTime, deltaT, hidden1, odefunc, device, method="euler", adjoint=True):
-        super().__init__()
-        self.maxTime = maxTime
-        self.deltaT = deltaT
-        self.device = device
-        self.method = method
-        self.adjoint = _check_adjoint(adjoint, method)     # extension: see gnode.ode_nn_ngraph_sim.ODEBlock
-        self.integration_time = torch.from_numpy(ops.time_grid(maxTime, deltaT))
-        self._dts = ops.step_sizes(ops.time_grid(maxTime, deltaT))
-        self.odefunc = odefunc
-        self.hidden1 = hidden1
-        self.linearS1 = nn.Linear(1, hidden1)
-        self.ln = nn.LayerNorm(hidden1)
-        self.linear3 = nn.Linear(hidden1, 4)
-        self.linearS2 = nn.Linear(4, 1)
+        super().__init__(maxTime, deltaT, hidden1, odefunc, device, method, adjoint)
 
     def init_weights(self):
         """reference :121-122 (defined, never called)."""
         self.linearS1.weight.data.normal_(0, 1)
-
-    def _params(self):
-        return {"odefunc.linear.weight": self.odefunc.linear.weight, "odefunc.linear.bias": self.odefunc.linear.bias,
-                "linearS1.weight": self.linearS1.weight, "linearS1.bias": self.linearS1.bias,
-                "linear3.weight": self.linear3.weight, "linear3.bias": self.linear3.bias,
-                "linearS2.weight": self.linearS2.weight, "linearS2.bias": self.linearS2.bias}
 
     def forward(self, x, out_rows=None, picks=None):
         """x [sumN, 3+H] -> (S, I, R), each [G, sumN, 1] (reference :124-152).  picks: the batch's graph indices when the
@@ -107,6 +81,4 @@ class ODEBlock(nn.Module):
         g = self.odefunc.graph_for_picks(picks) if picks is not None else self.odefunc.graph_for(x[:, 3 + 2])
         if g.n != x.size(0):
             raise ValueError(f"markers describe {g.n} nodes but the batch has {x.size(0)}")
-        from .autograd import forward_with_grad
-        S, I, R = forward_with_grad(g, x, self._params(), self._dts, self.method, out_rows, self.adjoint)
-        return S.unsqueeze(-1), I.unsqueeze(-1), R.unsqueeze(-1)
+        return self._solve(g, x, out_rows)

@@ -57,6 +57,35 @@ def _workspace(nbytes: int, device) -> torch.Tensor:
     return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
 
 
+def _check_adjoint(adjoint, method) -> bool:
+    """The solver rule, worded here alone: method is euler | rk4, and adjoint=False (the exact gradient of the solve, DESIGN
+    section 7.3) exists for Euler.  Returns `adjoint` as a bool."""
+    if method not in METHODS:
+        raise _lib.GnodeError(f"unknown method {method!r} (euler | rk4)")
+    if not adjoint and method != "euler":
+        raise _lib.GnodeError(f"adjoint=False is Euler only (method {method!r}): for RK4 the adjoint gradient is within 3.4e-5 of "
+                              "the exact one (DESIGN section 7.3), below fp32 noise, so use adjoint=True")
+    return bool(adjoint)
+
+
+def _solve_call(x2d: torch.Tensor, dts, out_rows, upstream=()):
+    """What every solve entry is told about its call: (x2d, dts, out_rows) as the contiguous fp32 / fp32 / int32-or-None the C
+    ABI reads, and rows, H, n_steps, n_out.  `upstream` (the backwards' gS, gI, gR) must each be [n_out, rows]."""
+    x2d = _f32c(x2d)
+    rows, H = x2d.shape[0], x2d.shape[1] - 3
+    dts = np.ascontiguousarray(dts, dtype=np.float32)
+    n_steps = int(dts.shape[0])
+    if out_rows is not None:
+        out_rows = np.ascontiguousarray(out_rows, dtype=np.int32)
+        n_out = int(out_rows.shape[0])
+    else:
+        n_out = n_steps + 1
+    for t in upstream:
+        if tuple(t.shape) != (n_out, rows):
+            raise _lib.GnodeError(f"upstream gradient shape {tuple(t.shape)} != {(n_out, rows)}")
+    return x2d, dts, out_rows, rows, H, n_steps, n_out
+
+
 def pack_params(tensors: dict) -> _lib.Params:
     p = _lib.Params()
     for k in PARAM_KEYS:
@@ -115,17 +144,9 @@ def forward(graph: DeviceGraph, x2d: torch.Tensor, params: dict, dts: np.ndarray
     With want_sol (training) and want_keep, the kept activations the adjoint backward reads back (include/gnode.h: `keep`)
     ride along as ``sol.gnode_keep`` (None on paths that keep nothing); `backward` picks them up from there."""
     lib = _lib.load()
-    x2d = _f32c(x2d)
+    x2d, dts, out_rows, rows, H, n_steps, n_out = _solve_call(x2d, dts, out_rows)
     graph.check_device(x2d)
-    rows, H = x2d.shape[0], x2d.shape[1] - 3
-    dts = np.ascontiguousarray(dts, dtype=np.float32)
-    n_steps = int(dts.shape[0])
     m = METHODS[method]
-    if out_rows is not None:
-        out_rows = np.ascontiguousarray(out_rows, dtype=np.int32)
-        n_out = int(out_rows.shape[0])
-    else:
-        n_out = n_steps + 1
     dev = x2d.device
     out = torch.empty((3, n_out, rows), dtype=torch.float32, device=dev)
     sol = torch.empty((n_steps + 1, 4 * rows, H), dtype=torch.float32, device=dev) if want_sol else None
@@ -190,12 +211,35 @@ def _grad_buffers(params: dict, want_params: bool, want_x: bool, x2d: torch.Tens
     return grads, (pack_params({k: grads[k] for k in PARAM_KEYS}) if want_params else None), gx
 
 
+def _run_backward(size_fn: str, entry: str, dx_entry, arrange, graph: DeviceGraph, x2d, params: dict, dts, out_rows, sol,
+                  gS, gI, gR, want_x: bool, want_params: bool):
+    """One backward call of the library, whichever gradient it is: size_fn sizes its workspace, `entry` is called with
+    arrange(head, ups, tail, gx) -- head = (graph, x, params, dts, n_steps, out_rows, n_out, sol), ups = (gS, gI, gR, gradient
+    pointers), tail = (rows, H, workspace, its bytes, stream), in the order that entry declares them -- and with want_x
+    `dx_entry` is called instead, gx appended (None: `entry` places gx itself).  Returns (grads, (rows, H, workspace))."""
+    lib = _lib.load()
+    x2d, dts, out_rows, rows, H, n_steps, n_out = _solve_call(x2d, dts, out_rows, (gS, gI, gR))
+    grads, gp, gx = _grad_buffers(params, want_params, want_x, x2d)
+    ws = _workspace(getattr(lib, size_fn)(graph.handle, rows, H), x2d.device)
+    p = pack_params({k: v.detach() for k, v in params.items()})
+    args = arrange((graph.handle, _lib.ptr(x2d), C.byref(p), _lib.host_ptr(dts), n_steps,
+                    _lib.host_ptr(out_rows) if out_rows is not None else None, n_out, _lib.ptr(_f32c(sol))),
+                   (_lib.ptr(_f32c(gS)), _lib.ptr(_f32c(gI)), _lib.ptr(_f32c(gR)), C.byref(gp) if gp is not None else None),
+                   (rows, H, _lib.ptr(ws), ws.numel(), _lib.stream_ptr()), _lib.ptr(gx))
+    if want_x and dx_entry is not None:
+        _lib.check(getattr(lib, dx_entry)(*args, _lib.ptr(gx)))
+    else:
+        _lib.check(getattr(lib, entry)(*args))
+    return grads, (rows, H, ws)
+
+
 def backward(graph: DeviceGraph, x2d: torch.Tensor, params: dict, dts: np.ndarray, method: str, out_rows, sol: torch.Tensor,
              gS: torch.Tensor, gI: torch.Tensor, gR: torch.Tensor, keep="auto", persist: bool | None = None,
              want_x: bool = False, want_params: bool = True, adjoint: bool = True) -> dict:
     """Adjoint parameter gradients (torchdiffeq odeint_adjoint semantics: Euler; rk4)
     given the saved trajectory `sol` and the upstream gradients of S, I, R ([n_out, rows]).
-    keep: the forward's kept activations ("auto": ``sol.gnode_keep`` when `forward` attached it; None: recompute; Euler only).
+    keep: the forward's kept activations ("auto": ``sol.gnode_keep`` when `forward` attached it; None: recompute; method
+    'euler' alone keeps any).
     want_x: also dL/dx2d as key "x" ([rows, 3+H]; include/gnode.h gnode_backward_dx_f32; needs a trajectory produced
     without keep); want_params=False: no parameter gradients (then want_x must be set).
     adjoint=False: the exact gradient of the Euler solve instead (backpropagation through the solver, include/gnode.h
@@ -203,107 +247,43 @@ def backward(graph: DeviceGraph, x2d: torch.Tensor, params: dict, dts: np.ndarra
     are not used."""
     if not (want_x or want_params):
         raise _lib.GnodeError("backward: neither parameter nor input gradients requested")
-    if not adjoint:
-        if method == "rk4":
-            raise _lib.GnodeError("backward(adjoint=False) is Euler only: for RK4 the adjoint gradient is within 3.4e-5 of the "
-                                  "exact one (DESIGN section 7.3), below fp32 noise, so use adjoint=True")
-        if method != "euler":
-            raise _lib.GnodeError(f"unknown method {method!r} (euler | rk4)")
-        return _backward_discrete(graph, x2d, params, dts, out_rows, sol, gS, gI, gR, want_x=want_x, want_params=want_params)
+    solve = (graph, x2d, params, dts, out_rows, sol, gS, gI, gR)
+    if not _check_adjoint(adjoint, method):
+        return _backward_discrete(*solve, want_x=want_x, want_params=want_params)
     if method == "rk4":
-        return _backward_rk4(graph, x2d, params, dts, out_rows, sol, gS, gI, gR, want_x=want_x, want_params=want_params)
-    if method != "euler":
-        raise _lib.GnodeError(f"unknown method {method!r} (euler | rk4)")
-    lib = _lib.load()
-    x2d = _f32c(x2d)
-    rows, H = x2d.shape[0], x2d.shape[1] - 3
-    dts = np.ascontiguousarray(dts, dtype=np.float32)
-    n_steps = int(dts.shape[0])
-    if out_rows is not None:
-        out_rows = np.ascontiguousarray(out_rows, dtype=np.int32)
-        n_out = int(out_rows.shape[0])
-    else:
-        n_out = n_steps + 1
-    for t in (gS, gI, gR):
-        if tuple(t.shape) != (n_out, rows):
-            raise _lib.GnodeError(f"upstream gradient shape {tuple(t.shape)} != {(n_out, rows)}")
-    grads, gp, gx = _grad_buffers(params, want_params, want_x, x2d)
-    ws = _workspace(lib.gnode_backward_workspace_bytes(graph.handle, rows, H), x2d.device)
-    p = pack_params({k: v.detach() for k, v in params.items()})
+        return _backward_rk4(*solve, want_x=want_x, want_params=want_params)
     if isinstance(keep, str):
         keep = getattr(sol, "gnode_keep", None)
-    elif keep is None and getattr(sol, "gnode_keep", None) is not None and H == 64:
+    elif keep is None and getattr(sol, "gnode_keep", None) is not None and x2d.shape[1] - 3 == 64:
         # (a trajectory produced WITH kept activations does not carry A Z_I in its 4th slabs: include/gnode.h)
         raise _lib.GnodeError("this trajectory was produced with a keep buffer: pass it (keep='auto'), or run the forward with want_keep=False")
-    args = (graph.handle, _lib.ptr(x2d), C.byref(p), _lib.host_ptr(dts), n_steps,
-            _lib.host_ptr(out_rows) if out_rows is not None else None, n_out, _lib.ptr(_f32c(sol)),
-            _lib.ptr(keep) if keep is not None else None, keep.numel() * 4 if keep is not None else 0,
-            _lib.ptr(_f32c(gS)), _lib.ptr(_f32c(gI)), _lib.ptr(_f32c(gR)), C.byref(gp) if gp is not None else None, rows, H,
-            _lib.ptr(ws), ws.numel(), _lib.stream_ptr(), _fwd_flags(persist), int(getattr(sol, "gnode_info", -1)))
-    if want_x:
-        _lib.check(lib.gnode_backward_dx_f32(*args, _lib.ptr(gx)))
-    else:
-        _lib.check(lib.gnode_backward_f32(*args))
-    backward.last_workspace = (rows, H, ws)
+    kept = (_lib.ptr(keep), keep.numel() * 4) if keep is not None else (None, 0)
+    last = (_fwd_flags(persist), int(getattr(sol, "gnode_info", -1)))
+    grads, backward.last_workspace = _run_backward(
+        "gnode_backward_workspace_bytes", "gnode_backward_f32", "gnode_backward_dx_f32",
+        lambda head, ups, tail, gx: head + kept + ups + tail + last, *solve, want_x, want_params)
     return grads
 
 
 def _backward_rk4(graph: DeviceGraph, x2d, params: dict, dts, out_rows, sol, gS, gI, gR, want_x: bool = False,
                   want_params: bool = True) -> dict:
     """The RK4 (3/8 rule) adjoint of a method='rk4' forward: gnode_backward_rk4_f32 (want_x: gnode_backward_rk4_dx_f32)."""
-    lib = _lib.load()
-    x2d = _f32c(x2d)
-    rows, H = x2d.shape[0], x2d.shape[1] - 3
-    dts = np.ascontiguousarray(dts, dtype=np.float32)
-    n_steps = int(dts.shape[0])
-    if out_rows is not None:
-        out_rows = np.ascontiguousarray(out_rows, dtype=np.int32)
-        n_out = int(out_rows.shape[0])
-    else:
-        n_out = n_steps + 1
-    for t in (gS, gI, gR):
-        if tuple(t.shape) != (n_out, rows):
-            raise _lib.GnodeError(f"upstream gradient shape {tuple(t.shape)} != {(n_out, rows)}")
-    grads, gp, gx = _grad_buffers(params, want_params, want_x, x2d)
-    ws = _workspace(lib.gnode_backward_rk4_workspace_bytes(graph.handle, rows, H), x2d.device)
-    p = pack_params({k: v.detach() for k, v in params.items()})
-    args = (graph.handle, _lib.ptr(x2d), C.byref(p), _lib.host_ptr(dts), n_steps,
-            _lib.host_ptr(out_rows) if out_rows is not None else None, n_out, _lib.ptr(_f32c(sol)),
-            _lib.ptr(_f32c(gS)), _lib.ptr(_f32c(gI)), _lib.ptr(_f32c(gR)), C.byref(gp) if gp is not None else None, rows, H,
-            _lib.ptr(ws), ws.numel(), _lib.stream_ptr())
-    if want_x:
-        _lib.check(lib.gnode_backward_rk4_dx_f32(*args, _lib.ptr(gx)))
-    else:
-        _lib.check(lib.gnode_backward_rk4_f32(*args))
+    grads, _ = _run_backward("gnode_backward_rk4_workspace_bytes", "gnode_backward_rk4_f32", "gnode_backward_rk4_dx_f32",
+                             lambda head, ups, tail, gx: head + ups + tail,
+                             graph, x2d, params, dts, out_rows, sol, gS, gI, gR, want_x, want_params)
     backward.last_workspace = None               # (no persistent sweep on this path: nothing for backward_status to read)
     return grads
 
 
 def _backward_discrete(graph: DeviceGraph, x2d, params: dict, dts, out_rows, sol, gS, gI, gR, want_x: bool = False,
                        want_params: bool = True) -> dict:
-    """The exact gradient of a method='euler' forward: gnode_backward_discrete_f32."""
-    lib = _lib.load()
-    x2d = _f32c(x2d)
-    rows, H = x2d.shape[0], x2d.shape[1] - 3
-    dts = np.ascontiguousarray(dts, dtype=np.float32)
-    n_steps = int(dts.shape[0])
-    if out_rows is not None:
-        out_rows = np.ascontiguousarray(out_rows, dtype=np.int32)
-        n_out = int(out_rows.shape[0])
-    else:
-        n_out = n_steps + 1
-    for t in (gS, gI, gR):
-        if tuple(t.shape) != (n_out, rows):
-            raise _lib.GnodeError(f"upstream gradient shape {tuple(t.shape)} != {(n_out, rows)}")
-    grads, gp, gx = _grad_buffers(params, want_params, want_x, x2d)
-    ws = _workspace(lib.gnode_backward_discrete_workspace_bytes(graph.handle, rows, H), x2d.device)
-    p = pack_params({k: v.detach() for k, v in params.items()})
-    _lib.check(lib.gnode_backward_discrete_f32(
-        graph.handle, _lib.ptr(x2d), C.byref(p), _lib.host_ptr(dts), n_steps,
-        _lib.host_ptr(out_rows) if out_rows is not None else None, n_out, _lib.ptr(_f32c(sol)),
-        int(getattr(sol, "gnode_info", -1)), _lib.ptr(_f32c(gS)), _lib.ptr(_f32c(gI)), _lib.ptr(_f32c(gR)),
-        C.byref(gp) if gp is not None else None, _lib.ptr(gx), rows, H, _lib.ptr(ws), ws.numel(), _lib.stream_ptr()))
-    backward.last_workspace = (rows, H, ws)      # (its control block is zeroed by the call: backward_status reads 0)
+    """The exact gradient of a method='euler' forward: gnode_backward_discrete_f32 (one entry, gx in its own place)."""
+    info = int(getattr(sol, "gnode_info", -1))
+    # (the call zeroes its control block: backward_status reads 0)
+    grads, backward.last_workspace = _run_backward(
+        "gnode_backward_discrete_workspace_bytes", "gnode_backward_discrete_f32", None,
+        lambda head, ups, tail, gx: head + (info,) + ups + (gx,) + tail,
+        graph, x2d, params, dts, out_rows, sol, gS, gI, gR, want_x, want_params)
     return grads
 
 

@@ -25,7 +25,8 @@ import torch
 import torch.nn as nn
 
 from . import ops, sharding
-from .ode_nn import create_graph, sir_torch
+from .autograd import l1_loss_mean_backward, l1_loss_sum
+from .ode_nn import _counts_f64, _device_graph_for, create_graph, sir_counts, sir_torch
 
 # GNODE_ADJOINT=0 (read ONCE at import): the drop-in scripts build their ODEBlock with adjoint=False and train with the exact
 # gradient of the Euler solve instead of the reference's adjoint gradient; argv is untouched.
@@ -87,21 +88,47 @@ def _label_store(ps, G, I_indices, beta, gamma, sim, maxTime, raw_counts):
         S, I, R = sir_torch(G, I_indices, beta, gamma, sim, maxTime)
         cnt = (S[0], I[0], R[0])
     else:
-        from .ode_nn import _device_graph_for, sir_counts
         seed = torch.randint(0, 2**62, (1,), dtype=torch.int64).to(dev)
         torch.distributed.broadcast(seed, src=0)
         graph = _device_graph_for(G)
         lo, hi = sharding.shard_range(sim, rank, world)
         counts = sir_counts(graph, I_indices, beta, gamma, hi - lo, maxTime, int(seed.item()), sim_offset=lo)
         sharding.allreduce_counts(counts)
-        c = (counts.cpu().numpy().astype(np.int64) & 0xFFFFFFFF).astype(np.float64)
-        cnt = (c[0], c[1], c[2])
+        cnt = tuple(_counts_f64(counts))
     out = tuple(a / sim for a in cnt)
     if rank == 0:
         for p, a in zip(ps, cnt if raw_counts else out):
             pickle.dump(a, open(p, "wb"))
     sharding.barrier()
     return out
+
+
+def label_tensor(S, I, R) -> torch.Tensor:
+    """Three [T, n] label arrays -> the sample's y [n, T, 3] float64, contiguous."""
+    return torch.from_numpy(np.stack([np.asarray(S), np.asarray(I), np.asarray(R)], -1)).transpose(0, 1).contiguous()
+
+
+def _graph_cache() -> bool:
+    """GNODE_GRAPH_CACHE=1: create_graph keeps a CSR file next to each graph pickle."""
+    return os.environ.get("GNODE_GRAPH_CACHE", "0") == "1"
+
+
+def _decode_seeds(args):
+    """--I_indices "[25, 18]" "[3, 7]" -> [[25, 18], [3, 7]], in place."""
+    args.I_indices = [list(map(int, str(i)[1:-1].split(", "))) for i in args.I_indices]
+
+
+def _save_initial(args):
+    """The experiment's initial-{seed,beta,gamma}.pkl, unless they are there already."""
+    if not os.path.exists(args.path_to_save + "/initial-seed.pkl"):
+        for name, val in (("seed", args.I_indices), ("beta", args.beta), ("gamma", args.gamma)):
+            pickle.dump(val, open(args.path_to_save + f"/initial-{name}.pkl", "wb"))
+
+
+def _labels_of(args, G):
+    """(S, I, R) of every sample of a single-graph experiment, loaded or generated in sample order."""
+    return [load_SIR_labels(args.dataset, args.path_to_save, G, seeds, args.beta[i], args.gamma[i], args.sim, args.maxTime)
+            for i, seeds in enumerate(args.I_indices)]
 
 
 # --------------------------------------------------------------------------- dataset assembly
@@ -149,12 +176,12 @@ class Runner:
         # Single-graph batches only (the multi-graph forward reads its markers on the host).
         if use_graphs is None:
             use_graphs = os.environ.get("GNODE_TRAIN_GRAPHS", "1") != "0"
-        self.use_graphs = bool(use_graphs) and stack and torch.cuda.is_available() and str(device).startswith("cuda")
+        self.on_gpu = torch.cuda.is_available() and str(device).startswith("cuda")
+        self.use_graphs = bool(use_graphs) and stack and self.on_gpu
         self._graphs = {}
         self._marks, self._picks = {}, None
-        on_gpu = torch.cuda.is_available() and str(device).startswith("cuda")
         # same Adam as the reference (:442); on the GPU the whole update is ONE kernel instead of ~16 tiny ones
-        self.opt = torch.optim.Adam(model.parameters(), lr=lr, fused=True) if on_gpu else torch.optim.Adam(model.parameters(), lr=lr)
+        self.opt = torch.optim.Adam(model.parameters(), lr=lr, fused=True) if self.on_gpu else torch.optim.Adam(model.parameters(), lr=lr)
         self.rows = ops.subsample_rows(maxTime, deltaT)
         self.rank, self.world = sharding.world_info()
         self.collective = sharding.collectives_on()      # world > 1, or a forced single-rank rehearsal of the RCCL calls
@@ -170,7 +197,7 @@ class Runner:
         """Keep the dataset resident in HBM when it fits (a 75k-node sample is 20 MB of x + 54 MB of float64
         labels; 288 GB holds thousands): the per-batch `.to(device)` of the reference's loop (:221-222) then
         moves nothing.  Falls back to host tensors (pageable H2D per batch) when it does not fit."""
-        if not (torch.cuda.is_available() and str(self.device).startswith("cuda")):
+        if not self.on_gpu:
             return lists
         need = sum(t.numel() * t.element_size() for l in lists for t in l)
         free, _ = torch.cuda.mem_get_info(self.device)
@@ -210,24 +237,20 @@ class Runner:
             self._marks[id(xj)] = m
         return m[1]
 
-    def _loss_sum(self, x, y):
+    def _model_out(self, x):
+        """(S, I, R) at the label rows for the batch `_local` built last"""
         if not self.stack and self._picks:
-            S, I, R = self.model(x, out_rows=self.rows, picks=self._picks)
-        else:
-            S, I, R = self.model(x, out_rows=self.rows)
+            return self.model(x, out_rows=self.rows, picks=self._picks)
+        return self.model(x, out_rows=self.rows)
+
+    def _loss_sum(self, x, y):
         # L1 over cat(S, I, R)[rows, T, 3][:, 1:, :] (t = 0 excluded, :234) and its gradient: one kernel instead of the
         # cat / transpose / convert / subtract / abs / sum chain and its six backward launches
-        from .autograd import l1_loss_sum
-        return l1_loss_sum(S, I, R, y, 1)
+        return l1_loss_sum(*self._model_out(x), y, 1)
 
     def _loss_backward(self, x, y, gcount):
         """forward + loss + backward of one batch (gradients of the element-mean L1 over `gcount` elements); returns the loss sum"""
-        if not self.stack and self._picks:
-            S, I, R = self.model(x, out_rows=self.rows, picks=self._picks)
-        else:
-            S, I, R = self.model(x, out_rows=self.rows)
-        from .autograd import l1_loss_mean_backward
-        return l1_loss_mean_backward(S, I, R, y, gcount, 1)
+        return l1_loss_mean_backward(*self._model_out(x), y, gcount, 1)
 
     def _graphed_backward(self, x_list, y_list, gcount):
         """Replay (capturing on first use) forward + L1 + backward for this batch shape; returns the loss sum.  x_list / y_list:
@@ -307,7 +330,7 @@ class Runner:
     def _check_launches(self):
         """Once per epoch (there is a host sync here anyway): did a persistent launch give up waiting for its group?  Its spins
         are bounded so that a lost workgroup becomes this error instead of a hang (csrc/gnode_pers64.hip, gnode_persg.hip)."""
-        if not (torch.cuda.is_available() and str(self.device).startswith("cuda")):
+        if not self.on_gpu:
             return
         f, b = ops.forward_status(), ops.backward_status()
         if f or b:
@@ -334,6 +357,24 @@ class Runner:
         self._check_launches()
         per_batch = [v / max(c, 1) for v, c in zip(vals, counts)]
         return sum(vals) / max(sum(counts), 1), per_batch
+
+    def fit(self, train, val, test, epochs, batch_size, test_batch_size):
+        """The reference's epoch loop (ode_nn_ngraph_sim.py:444-470, ode_nn_ngraphs.py:380-402) over (xs, ys) pairs: train, validate,
+        and on every best validation loss evaluate the test set.  Returns (best_epoch, best val loss, test loss, per-batch test
+        losses, seconds of that test pass)."""
+        best_loss, best_epoch, test_loss, test_all, t_test = np.inf, -1, float("nan"), [], 0.0
+        print("training...")
+        for epoch in range(epochs):
+            loss, t_fwd = self.train_epoch(*train, batch_size, epoch)
+            val_loss, _ = self.evaluate(*val, batch_size)
+            print("Time: ", t_fwd)
+            print("Epoch: {:03d}, Train Loss: {:.10f}, Val Loss: {:.10f}".format(epoch, loss, val_loss))
+            if val_loss < best_loss:
+                best_loss, best_epoch = val_loss, epoch
+                t0 = time.time()
+                test_loss, test_all = self.evaluate(*test, test_batch_size)
+                t_test = time.time() - t0
+        return best_epoch, best_loss, test_loss, test_all, t_test
 
 
 # --------------------------------------------------------------------------- single-graph entry (ode_nn_ngraph_sim.py:323-486)
@@ -364,20 +405,14 @@ def main_single(argv=None):
     if args.model != "ode_nn":
         raise SystemExit(f"this entry point serves model='ode_nn' only (got {args.model!r})")
     rank, world = sharding.init_from_env()        # torchrun: one process per GPU; plain run: (0, 1)
-    G, A, _ = create_graph(50, args.dataset, cache=os.environ.get("GNODE_GRAPH_CACHE", "0") == "1")
+    G, A, _ = create_graph(50, args.dataset, cache=_graph_cache())
     n_nodes = A.shape[0]
     print(n_nodes)
-    args.I_indices = [list(map(int, str(i)[1:-1].split(", "))) for i in args.I_indices]      # "[25, 18]" -> [25, 18]
-    if rank == 0 and not os.path.exists(args.path_to_save + "/initial-seed.pkl"):
-        pickle.dump(args.I_indices, open(args.path_to_save + "/initial-seed.pkl", "wb"))
-        pickle.dump(args.beta, open(args.path_to_save + "/initial-beta.pkl", "wb"))
-        pickle.dump(args.gamma, open(args.path_to_save + "/initial-gamma.pkl", "wb"))
-    xs, ys = [], []
-    for i, seeds in enumerate(args.I_indices):
-        S, I, R = load_SIR_labels(args.dataset, args.path_to_save, G, seeds, args.beta[i], args.gamma[i], args.sim, args.maxTime)
-        y = torch.from_numpy(np.stack([np.asarray(S), np.asarray(I), np.asarray(R)], -1)).transpose(0, 1)   # [n, T, 3] float64
-        xs.append(sample_tensor(n_nodes, args.hidden, seeds, args.beta[i], args.gamma[i]))
-        ys.append(y.contiguous())
+    _decode_seeds(args)
+    if rank == 0:
+        _save_initial(args)
+    xs = [sample_tensor(n_nodes, args.hidden, seeds, args.beta[i], args.gamma[i]) for i, seeds in enumerate(args.I_indices)]
+    ys = [label_tensor(*lab) for lab in _labels_of(args, G)]
     ood = pickle.load(open(args.path_to_save + "/out-of-dist-gamma.pkl", "rb")) if args.out_of_dist else None
     tr, va, te = split_indices(len(xs), args.train_val_test_ratio, ood)
     device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
@@ -389,18 +424,7 @@ def main_single(argv=None):
     run = Runner(model, args.lr, args.maxTime, args.deltaT, device, stack=True)
     xs, ys = run.place(xs, ys)
     pick = lambda ids: ([xs[i] for i in ids], [ys[i] for i in ids])
-    best_loss, best_epoch, test_loss, test_all, t_test = np.inf, -1, float("nan"), [], 0.0
-    print("training...")
-    for epoch in range(args.epochs):
-        loss, t_fwd = run.train_epoch(*pick(tr), args.batch_size, epoch)
-        val_loss, _ = run.evaluate(*pick(va), args.batch_size)
-        print("Time: ", t_fwd)
-        print("Epoch: {:03d}, Train Loss: {:.10f}, Val Loss: {:.10f}".format(epoch, loss, val_loss))
-        if val_loss < best_loss:
-            best_loss, best_epoch = val_loss, epoch
-            t0 = time.time()
-            test_loss, test_all = run.evaluate(*pick(te), 1)
-            t_test = time.time() - t0
+    best_epoch, best_loss, test_loss, test_all, t_test = run.fit(pick(tr), pick(va), pick(te), args.epochs, args.batch_size, 1)
     if rank != 0:
         return 0
     if not args.out_of_dist:
@@ -444,18 +468,12 @@ def main_dmp(argv=None):
     prints the element-weighted L1 against the Monte-Carlo labels (dmp.py:345-364; the reference saves nothing)."""
     from .dmp import DMP_SIR
     args = parser_single().parse_args(argv)
-    G, A, _ = create_graph(50, args.dataset, cache=os.environ.get("GNODE_GRAPH_CACHE", "0") == "1")
+    G, A, _ = create_graph(50, args.dataset, cache=_graph_cache())
     n_nodes = A.shape[0]
     print(n_nodes)
-    args.I_indices = [list(map(int, str(i)[1:-1].split(", "))) for i in args.I_indices]
-    if not os.path.exists(args.path_to_save + "/initial-seed.pkl"):
-        pickle.dump(args.I_indices, open(args.path_to_save + "/initial-seed.pkl", "wb"))
-        pickle.dump(args.beta, open(args.path_to_save + "/initial-beta.pkl", "wb"))
-        pickle.dump(args.gamma, open(args.path_to_save + "/initial-gamma.pkl", "wb"))
-    ys = []
-    for i, seeds in enumerate(args.I_indices):
-        S, I, R = load_SIR_labels(args.dataset, args.path_to_save, G, seeds, args.beta[i], args.gamma[i], args.sim, args.maxTime)
-        ys.append(np.stack([np.asarray(S), np.asarray(I), np.asarray(R)], -1))       # [T, n, 3]
+    _decode_seeds(args)
+    _save_initial(args)                                           # (this script runs on its own: no ranks)
+    ys = [np.stack([np.asarray(a) for a in lab], -1) for lab in _labels_of(args, G)]        # [T, n, 3]
     ood = pickle.load(open(args.path_to_save + "/out-of-dist-gamma.pkl", "rb")) if args.out_of_dist else None
     _, _, te = split_indices(len(ys), args.train_val_test_ratio, ood)
     import scipy.sparse as sp
@@ -553,7 +571,7 @@ def main_multi(argv=None):
     for gname in names:                                             # create_graphs, ode_nn_ngraphs.py:154-165
         label = args.dataset[:14] + gname
         if os.path.exists(label + ".pkl"):
-            G, A, _ = create_graph(0, label, cache=os.environ.get("GNODE_GRAPH_CACHE", "0") == "1")
+            G, A, _ = create_graph(0, label, cache=_graph_cache())
         else:
             G, A, _ = standin_graph(gname, args.standin[0], args.standin[1])
         A_list.append(A)
@@ -581,7 +599,7 @@ def main_multi(argv=None):
         gammas = pickle.load(open(d + "/initial-gamma.pkl", "rb"))[:ipg[gi]]
         for i, indices in enumerate(I_all):
             S, I, R = load_multi_labels(gname, d, indices, args.sim, G_list[gi], betas[i], gammas[i], args.maxTime)
-            y = torch.from_numpy(np.stack([np.asarray(S), np.asarray(I), np.asarray(R)], -1)).transpose(0, 1).contiguous()
+            y = label_tensor(S, I, R)
             seeds = indices if args.per_sample_seeds else [s for grp in I_all for s in (grp if isinstance(grp, (list, tuple)) else [grp])]
             x = sample_tensor(n_nodes, args.hidden, seeds, betas[i], gammas[i], marker=gi + 1)
             if gi <= n_train_graphs:
@@ -600,18 +618,7 @@ def main_multi(argv=None):
     model = ODEBlock(args.maxTime, args.deltaT, args.hidden, odefunc, device, adjoint=ADJOINT_DEFAULT).to(device)
     run = Runner(model, args.lr, args.maxTime, args.deltaT, device, stack=False)
     tr, va, te = (run.place(*d) for d in (tr, va, te))
-    best_loss, best_epoch, test_loss, t_test = np.inf, -1, float("nan"), 0.0
-    print("training...")
-    for epoch in range(args.epochs):
-        loss, t_fwd = run.train_epoch(tr[0], tr[1], args.batch_size, epoch)
-        val_loss, _ = run.evaluate(va[0], va[1], args.batch_size)
-        print("Time: ", t_fwd)
-        print("Epoch: {:03d}, Train Loss: {:.10f}, Val Loss: {:.10f}".format(epoch, loss, val_loss))
-        if val_loss < best_loss:
-            best_loss, best_epoch = val_loss, epoch
-            t0 = time.time()
-            test_loss, _ = run.evaluate(te[0], te[1], args.batch_size)
-            t_test = time.time() - t0
+    best_epoch, best_loss, test_loss, _, t_test = run.fit(tr, va, te, args.epochs, args.batch_size, args.batch_size)
     if rank != 0:
         return 0
     csv_trials(args.path_to_save + "/Metrics-trials-" + os.path.relpath(args.dataset, "./real_graphs/"),

@@ -34,6 +34,21 @@ def test_binding_table_matches_header(lib):
     assert sorted(_lib.EXPORTS) == _declared()
 
 
+def test_binding_signatures_match_header(lib):
+    """Every prototype of include/gnode.h is bound with its own parameter count and return type: a ctypes call of the wrong
+    arity, or an unset argtypes, goes unnoticed until it corrupts a call on the GPU."""
+    import ctypes as C
+    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "gnode.h")).read(), flags=re.S)
+    protos = re.findall(r"^(size_t|const char\s*\*|int)\s*(gnode_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", src, flags=re.M)
+    assert sorted(name for _, name, _ in protos) == _declared()
+    restypes = {"size_t": C.c_size_t, "constchar*": C.c_char_p, "int": C.c_int}
+    for ret, name, params in protos:
+        fn = getattr(lib, name)
+        n_params = 0 if params.strip() in ("", "void") else params.count(",") + 1
+        assert fn.argtypes is not None and len(fn.argtypes) == n_params, name
+        assert fn.restype is restypes[re.sub(r"\s", "", ret)], name
+
+
 def test_version_and_sizes(lib):
     assert lib.gnode_version() >= 210
     # workspace sizes depend on the graph (hub scratch): without a handle they answer 0 instead of guessing
