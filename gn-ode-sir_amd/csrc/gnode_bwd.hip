@@ -15,6 +15,11 @@
 // system from t_i to t_{i-1}), which is what the reference's training gradients are.
 // gnode_backward_discrete_f32 runs the same sweep with every interval's Jacobian, parameter VJP and beta-gamma sums at the
 // LEFT endpoint y_{i-1} (BwdCall::jp, the kernels' EXACT flag): the exact gradient of the Euler loop.
+// gnode_backward_discrete_keep_f32 is that sweep on the forms of the training backward: at H = 64 over the forward's kept
+// activations -- P_S, Z_I of grid point i-1 and Z_S of i-2 are kept for intervals G-1 .. 2, which run as one launch each
+// (k_bwd_kept64) or as ONE persistent launch (k_pers_bwd64<.., EXACT>); interval 1, whose P_S(y_0) the forward never had, takes
+// the two-table recomputing launch -- and at H <= 32 as one persistent launch (k_persg_bwd<.., EXACT>).  gnode_backward_discrete_path
+// says which.
 //
 // Launch structure: H = 64 and H <= 32 take ONE launch per interval (k_bwd_fused64 / k_bwd_fused_generic: the
 // interval's VJPs, the head's VJP at grid point i-1 and the NEXT interval's Z / q gather tables, double-buffered);
@@ -1183,6 +1188,7 @@ struct BwdPlan {
     bool persist;         // intervals G-2 .. 1 (or G-1 .. 1 with `fold`) in ONE persistent launch (gnode_pers64_bwd.hip)
     bool fold;            // ... starting at interval G-1, whose adjoint is zero
     bool skip_last;       // one launch per interval over kept activations, interval G-1 (zero adjoint) skipped
+                          // (the discrete sweep, `exact`: fold / skip_last shift down by one grid point, see backward_h64_discrete)
     PersPlan pers;
     // small_h
     bool gpersist;
@@ -1192,21 +1198,34 @@ struct BwdPlan {
 // want_x (an input gradient is asked for, keep is then null): only the recomputing one-launch-per-interval forms, which
 // have a, A Z_I and Z of every row at hand -- k_bwd_fused64 (H = 64), k_bwd_fused_generic (H <= 32), the generic path
 // (k_bwd_gather) -- never the one-launch sweeps (k_tiny_bwd64, k_persg_bwd) nor the kept / persistent H = 64 sweeps.
+// exact (the discrete sweep): never the one-workgroup sweep, and graphs of its size (karate) stay on the recomputing form whatever
+// forward ran; over kept activations only when every kept interval (G-1 .. 2) can take the kept or the persistent launch,
+// otherwise -- 2-point grids, tables beyond 32-bit offsets -- the recomputing form throughout.
 static BwdPlan backward_plan(gnode_graph_s* g, long rows, int H, int n_steps, int n_emit, const int* slot, const float* keep,
-                             int sol_info, int flags, bool want_x = false) {
+                             int sol_info, int flags, bool want_x = false, bool exact = false) {
     const int G = n_steps + 1;
     const bool persist_ok = !(flags & GNODE_FWD_PER_STEP) && !want_x;
     BwdPlan pl{};
     // what the forward that produced `sol` / `keep` was (its sol_info says so; unchecked callers: the same question, same flags)
     pl.fwd_tiny = sol_info >= 0 ? (sol_info & GNODE_SOL_TINY) != 0
                                 : gn_forward_plan(g, rows, H, 0, n_steps, n_emit, true, flags).path == FwdPath::tiny;
-    if (pl.fwd_tiny && !want_x && gn_tiny_bwd64_ok(g, rows, H, n_steps)) {
+    if (pl.fwd_tiny && !want_x && !exact && gn_tiny_bwd64_ok(g, rows, H, n_steps)) {
         pl.path = BwdPath::tiny;
     } else if (H == 64 && n_steps >= 1) {
         pl.path = BwdPath::h64;
         // the 4th slabs (or the keep buffer's P_S) carry A Z_I unless the one-workgroup forward ran; the intervals below the
         // last read Z_S(y_k), Z_I(y_k) back when the forward kept them as well
         pl.keep = !pl.fwd_tiny && gnode_forward_keep_bytes(g, rows, H, n_steps, n_emit) > 0 ? keep : nullptr;
+        if (exact) {
+            const bool fits32 = rows < (1L << 24) && (long)(rows / g->n) * g->n_seg < (1L << 24);    // k_bwd_kept64's byte offsets
+            if (G < 3 || !fits32 || want_x || gn_tiny_bwd64_ok(g, rows, H, n_steps)) pl.keep = nullptr;
+            const bool last_zero = slot[G - 1] < 0;
+            // with a zero adjoint through interval G-1 the persistent launch needs an interval of its own below it: G-2 >= 2
+            pl.persist = pl.keep && G >= (last_zero ? 4 : 3) && persist_ok && gn_pers_bwd64_plan(g, rows / g->n, n_steps, &pl.pers);
+            pl.fold = pl.persist && last_zero;
+            pl.skip_last = !pl.persist && pl.keep && last_zero;
+            return pl;
+        }
         pl.persist = pl.keep && G >= 3 && persist_ok && gn_pers_bwd64_plan(g, rows / g->n, n_steps, &pl.pers);
         // The last grid point emits nothing in the reference's use (get_sir_t_nodes_torch keeps the integer times, the grid ends
         // half a step later): the adjoint is still ZERO through interval G-1 -- every product of that interval is zero -- and all
@@ -1331,9 +1350,11 @@ static int backward64_interval(BwdCall& c, const BwdPlan& pl, int i) {
     auto two_at = [&](int j) { const int k = c.jp(j); return !ai_saved || k < 1 || k > c.G - 2; };
     const bool two = two_at(i);
     const float *AIhub = nullptr, *GQhub = nullptr;
+    // the discrete sweep over kept activations gathers A Z_I(y_0) for interval 1 from the kept table (nothing left one in ZIb)
+    const float* ZIc = (c.exact && keep) ? gn_keep_zi(keep, rows, c.jp(i)) : T.ZIb[cur];
     const bool kept_launch = keep && !two && rows < (1L << 24) && (long)(rows / g->n) * g->n_seg < (1L << 24);   // 32-bit byte offsets of rows and hub partials
     const float* HubP = nullptr;               // kept kernel: segment partials only, it adds them up itself
-    if (two) { if (int e = gn_hub_gather(g, rows / g->n, 64, T.ZIb[cur], T.Qb[cur], c.hub_scratch, &AIhub, &GQhub, c.st)) return e; }
+    if (two) { if (int e = gn_hub_gather(g, rows / g->n, 64, ZIc, T.Qb[cur], c.hub_scratch, &AIhub, &GQhub, c.st)) return e; }
     else if (kept_launch) { if (int e = gn_hub_segments(g, rows / g->n, 64, T.Qb[cur], c.hub_scratch, &HubP, c.st)) return e; }
     else if (int e = gn_hub_gather(g, rows / g->n, 64, T.Qb[cur], nullptr, c.hub_scratch, &GQhub, nullptr, c.st)) return e;
     const float* gSs = c.up(c.gS, i - 1);
@@ -1345,11 +1366,14 @@ static int backward64_interval(BwdCall& c, const BwdPlan& pl, int i) {
         auto kept_kernel = gSs ? (hubs ? k_bwd_kept64<HOCC, true, true> : k_bwd_kept64<HOCC, true, false>)
                                : (hubs ? k_bwd_kept64<GN_BWD_RPG1_OCC, false, true> : k_bwd_kept64<GN_BWD_RPG1_OCC, false, false>);
         const int kgrid = gSs ? (int)std::min<long>((long)HOCC * g->num_cu, grid) : grid;
+        // j: the Jacobian's grid point.  The discrete sweep (j = i-1 >= 1) reads P_S, Z_I and the gW rows there, has the head at
+        // the same rows, forms the next q row from Z_S(y_{i-2}) and always leaves one: interval 1 follows on the two-table launch
+        const int j = c.jp(i);
         hipLaunchKernelGGL(kept_kernel, dim3(kgrid), dim3(256), 0, c.st, g->rowhdr, g->col, g->n, rows, tps, total, T.Qb[cur],
-                           T.Qb[cur ^ 1], c.point(i), c.point(i - 1), gn_keep_ps(keep, rows, i), gn_keep_zi(keep, rows, i),
-                           gn_keep_zs(keep, rows, i - 1), p->odefunc_linear_weight, c.beta, c.gamma, c.dt_host[i - 1], c.a, c.part,
+                           T.Qb[cur ^ 1], c.point(j), c.point(i - 1), gn_keep_ps(keep, rows, j), gn_keep_zi(keep, rows, j),
+                           gn_keep_zs(keep, rows, j - 1), p->odefunc_linear_weight, c.beta, c.gamma, c.dt_host[i - 1], c.a, c.part,
                            gSs, c.up(c.gI, i - 1), c.up(c.gR, i - 1), p->linear3_weight, p->linear3_bias, p->linearS2_weight,
-                           p->linearS2_bias, g->hubidx, HubP, g->hub_seg_ptr, g->n_seg, i > 1 ? 1 : 0);
+                           p->linearS2_bias, g->hubidx, HubP, g->hub_seg_ptr, g->n_seg, (c.exact || i > 1) ? 1 : 0);
     } else {
         constexpr int O = GN_BWD_RPG1_OCC;
         auto fused_kernel = c.exact ? (c.gx ? (two ? k_bwd_fused64<O, 1, true, true, true> : k_bwd_fused64<O, 1, false, true, true>)
@@ -1358,7 +1382,7 @@ static int backward64_interval(BwdCall& c, const BwdPlan& pl, int i) {
                                             : (two ? k_bwd_fused64<O, 1, true> : k_bwd_fused64<O, 1, false>));
         // the next interval gathers A Z_I itself when its grid point's 4th slab does not carry it
         float* ZIn = c.exact ? (two_at(i - 1) ? T.ZIb[cur ^ 1] : nullptr) : (ai_saved ? nullptr : T.ZIb[cur ^ 1]);
-        hipLaunchKernelGGL(fused_kernel, dim3(grid), dim3(256), 0, c.st, g->rowptr, g->col, g->n, rows, tps, total, T.ZIb[cur],
+        hipLaunchKernelGGL(fused_kernel, dim3(grid), dim3(256), 0, c.st, g->rowptr, g->col, g->n, rows, tps, total, ZIc,
                            T.Qb[cur], ZIn, T.Qb[cur ^ 1], c.point(c.jp(i)), c.before(i),
                            p->odefunc_linear_weight, p->odefunc_linear_bias, c.beta, c.gamma, c.dt_host[i - 1], c.a, c.part, gSs,
                            c.up(c.gI, i - 1), c.up(c.gR, i - 1), p->linear3_weight, p->linear3_bias, p->linearS2_weight,
@@ -1367,6 +1391,40 @@ static int backward64_interval(BwdCall& c, const BwdPlan& pl, int i) {
     if (sampled) gn_prof_end(2, c.st);
     GN_LAUNCH_CHECK();
     return 0;
+}
+
+// The discrete sweep over kept activations (G >= 3).  Interval i reads grid point i-1, so the top needs no recomputing launch:
+// the first q table is beta (a_I - a_S) Z_S(y_{G-2}) from the kept table, intervals G-1 .. 2 run over kept activations (one
+// launch each, or the persistent sweep), and only interval 1 (no kept P_S(y_0)) takes the two-table launch, which gathers
+// A Z_I(y_0) from the kept Z_I table and the q table the sweep left: Qb[(G-2) & 1] either way.  A last grid point that emits
+// nothing leaves the adjoint zero through interval G-1: the head's VJP at G-2 and q from Z_S(y_{G-3}) start the sweep at G-2
+// (skip_last here, `fold` inside the persistent launch).
+static int backward_h64_discrete(BwdCall& c, const BwdPlan& pl) {
+    const int G = c.G;
+    const Tables64 T = tables64(c);
+    const int top = (pl.fold || pl.skip_last) ? G - 2 : G - 1;          // the first interval with a non-zero adjoint
+    if (!pl.fold) {
+        if (pl.skip_last)
+            if (int e = c.head(G - 2)) return e;
+        hipLaunchKernelGGL(k_bwd_q, dim3(2048), dim3(256), 0, c.st, c.a, gn_keep_zs(pl.keep, c.rows, top - 1), c.beta,
+                           T.Qb[(G - 1 - top) & 1], c.rows, 64);
+        GN_LAUNCH_CHECK();
+    }
+    if (pl.persist) {
+        const std::vector<int> prev = c.slot_prev();
+        int pslots = 0;
+        const bool sampled = gn_prof_begin(2, c.st);
+        if (int e = gn_launch_pers_bwd64(c.g, pl.pers, c.rows, G, T.Qb[0], T.Qb[1], c.sol, pl.keep, c.p->odefunc_linear_weight, c.beta,
+                                         c.gamma, c.a, c.part, c.gS, c.gI, c.gR, c.p, c.dt_host, prev.data(), c.ctl, true, pl.fold,
+                                         true, &pslots, c.st))
+            return e;
+        if (sampled) gn_prof_end(2, c.st);
+        c.slots_used = std::max(c.slots_used, pslots);
+    } else {
+        for (int i = top; i >= 2; --i)
+            if (int e = backward64_interval(c, pl, i)) return e;
+    }
+    return backward64_interval(c, pl, 1);
 }
 
 static int backward_h64(BwdCall& c, const BwdPlan& pl, const float* keep, size_t keep_bytes, int n_emit, int sol_info) {
@@ -1386,6 +1444,7 @@ static int backward_h64(BwdCall& c, const BwdPlan& pl, const float* keep, size_t
         return GNODE_ERR_WORKSPACE;
     }
     c.slots_used = std::max(c.slots_used, grid64(c));
+    if (c.exact && pl.keep) return backward_h64_discrete(c, pl);
     if (pl.skip_last) {
         if (int e = c.head(G - 2)) return e;
         hipLaunchKernelGGL(k_bwd_q, dim3(2048), dim3(256), 0, c.st, c.a, gn_keep_zs(pl.keep, c.rows, G - 2), c.beta, T.Qb[1], c.rows, 64);
@@ -1405,8 +1464,8 @@ static int backward_h64(BwdCall& c, const BwdPlan& pl, const float* keep, size_t
     int pslots = 0;
     const bool sampled = gn_prof_begin(2, c.st);
     if (int e = gn_launch_pers_bwd64(c.g, pl.pers, c.rows, G, T.Qb[0], T.Qb[1], c.sol, pl.keep, p->odefunc_linear_weight, c.beta,
-                                     c.gamma, c.a, c.part, c.gS, c.gI, c.gR, p, c.dt_host, prev.data(), c.ctl, true, pl.fold, &pslots,
-                                     c.st))
+                                     c.gamma, c.a, c.part, c.gS, c.gI, c.gR, p, c.dt_host, prev.data(), c.ctl, true, pl.fold, false,
+                                     &pslots, c.st))
         return e;
     if (sampled) gn_prof_end(2, c.st);
     c.slots_used = std::max(c.slots_used, pslots);
@@ -1426,7 +1485,7 @@ static int backward_small_h(BwdCall& c, const BwdPlan& pl) {
         const std::vector<int> prev = c.slot_prev();
         const bool sampled = gn_prof_begin(2, c.st);
         if (int e = gn_launch_persg_bwd(g, pl.persg, rows, H, G, ZIb[0], ZIb[1], Qb[0], Qb[1], c.Z, c.sol, c.beta, c.gamma, c.a,
-                                        c.part, c.gS, c.gI, c.gR, p, c.dt_host, prev.data(), c.ctl, true, c.st))
+                                        c.part, c.gS, c.gI, c.gR, p, c.dt_host, prev.data(), c.ctl, true, c.exact, c.st))
             return e;
         if (sampled) gn_prof_end(2, c.st);
         c.slots_used = std::max(c.slots_used, pl.persg.wgs);
@@ -1504,8 +1563,8 @@ static int backward_generic(BwdCall& c) {
     return 0;
 }
 
-// exact: the discrete sweep (gnode_backward_discrete_f32; keep is null, flags GNODE_FWD_PER_STEP): the one-launch-per-interval
-// forms of the gx call, each interval's Jacobian at y_{i-1}
+// exact: the discrete sweep, each interval's Jacobian at y_{i-1}.  gnode_backward_discrete_f32 (keep null, flags
+// GNODE_FWD_PER_STEP) runs the one-launch-per-interval forms of the gx call; gnode_backward_discrete_keep_f32 what the plan says
 static int backward_euler(gnode_graph_t g, const float* x, const gnode_params* p, const float* dt_host, int32_t n_steps,
                           const int32_t* out_rows_host, int32_t n_out, const float* sol, const float* keep, size_t keep_bytes,
                           const float* gS, const float* gI, const float* gR, const gnode_params* grads, int64_t rows, int32_t H,
@@ -1529,9 +1588,10 @@ static int backward_euler(gnode_graph_t g, const float* x, const gnode_params* p
     const int G = n_steps + 1, n_emit = out_rows_host ? n_out : G;
     if (int e = gn_check_out_rows("gnode_backward_f32", out_rows_host, n_out, G)) return e;
     const std::vector<int> slot = gn_out_slots(out_rows_host, n_out, G);
-    BwdPlan pl = backward_plan(g, rows, H, n_steps, n_emit, slot.data(), keep, sol_info, flags, gx != nullptr || exact);
-    // the discrete sweep reads A Z_I from the 4th slabs only when the forward said it left it there (unchecked: gathers it)
-    if (exact) pl.fwd_tiny = !(sol_info >= 0 && (sol_info & GNODE_SOL_AI));
+    BwdPlan pl = backward_plan(g, rows, H, n_steps, n_emit, slot.data(), keep, sol_info, flags, gx != nullptr, exact);
+    // the recomputing discrete sweep reads A Z_I from the 4th slabs only when the forward said it left it there (unchecked, or a
+    // trajectory whose keep buffer the plan does not use: gathers it); over kept activations P_S stands in for it
+    if (exact) pl.fwd_tiny = pl.keep ? false : !(sol_info >= 0 && (sol_info & GNODE_SOL_AI));
     const BwdLayout L = backward_layout(rows, H);
     char* ws = (char*)workspace;
     BwdCall c{g, p, dt_host, G, H, (long)rows, (size_t)rows * H, L.slab, sol, gS, gI, gR, slot.data(),
@@ -1577,6 +1637,38 @@ extern "C" int gnode_backward_discrete_f32(gnode_graph_t g, const float* x, cons
                  "keep buffer (its 4th slabs are unwritten): run the forward without one (sol_info %d)", sol_info);
     return backward_euler(g, x, p, dt_host, n_steps, out_rows_host, n_out, sol, nullptr, 0, gS, gI, gR, grads, rows, H, workspace,
                           workspace_bytes, stream, GNODE_FWD_PER_STEP, sol_info, gx, true);
+}
+
+extern "C" int gnode_backward_discrete_keep_f32(gnode_graph_t g, const float* x, const gnode_params* p, const float* dt_host,
+                                                int32_t n_steps, const int32_t* out_rows_host, int32_t n_out, const float* sol,
+                                                const float* keep, size_t keep_bytes, const float* gS, const float* gI,
+                                                const float* gR, const gnode_params* grads, int64_t rows, int32_t H, void* workspace,
+                                                size_t workspace_bytes, void* stream, int32_t flags, int32_t sol_info, float* gx) {
+    GN_CHECK_ARG(grads || gx, "gnode_backward_discrete_keep_f32: neither grads nor gx requested");
+    GN_CHECK_ARG(!(gx && keep), "gnode_backward_discrete_keep_f32: a keep buffer cannot serve an input gradient (pass keep = NULL)");
+    if (sol_info >= 0) {
+        // a trajectory and a keep buffer belong together, as for gnode_backward_f32
+        if (keep) GN_CHECK_ARG(sol_info & GNODE_SOL_KEEP, "gnode_backward_discrete_keep_f32: a keep buffer was passed with a trajectory "
+                               "whose forward call filled none (sol_info %d)", sol_info);
+        else GN_CHECK_ARG(!(sol_info & GNODE_SOL_KEEP) || (sol_info & GNODE_SOL_TINY), "gnode_backward_discrete_keep_f32: this trajectory "
+                          "was produced WITH a keep buffer (its 4th slabs are unwritten): pass that buffer (sol_info %d)", sol_info);
+    }
+    return backward_euler(g, x, p, dt_host, n_steps, out_rows_host, n_out, sol, keep, keep_bytes, gS, gI, gR, grads, rows, H, workspace,
+                          workspace_bytes, stream, flags, sol_info, gx, true);
+}
+
+extern "C" int gnode_backward_discrete_path(gnode_graph_t g, int64_t rows, int32_t H, int32_t n_steps, const int32_t* out_rows_host,
+                                            int32_t n_out, int32_t with_keep, int32_t flags, int32_t sol_info, int32_t with_gx) {
+    if (!g || rows <= 0 || rows % g->n || n_steps < 0 || H < 4 || H > 128 || H % 4) return -1;
+    const int G = n_steps + 1;
+    if (gn_check_out_rows("gnode_backward_discrete_path", out_rows_host, n_out, G)) return -1;
+    const std::vector<int> slot = gn_out_slots(out_rows_host, n_out, G);
+    static const float some_keep = 0.f;                       // the plan only asks whether there is one
+    const BwdPlan pl = backward_plan(g, rows, H, n_steps, out_rows_host ? n_out : G, slot.data(), (with_keep && !with_gx) ? &some_keep : nullptr,
+                                     sol_info, flags, with_gx != 0, true);
+    if (pl.path == BwdPath::h64) return pl.persist ? 2 : pl.keep ? 1 : 0;
+    if (pl.path == BwdPath::small_h) return pl.gpersist ? 3 : 0;
+    return 0;
 }
 
 extern "C" int gnode_backward_f32(gnode_graph_t g, const float* x, const gnode_params* p, const float* dt_host,

@@ -51,7 +51,7 @@ int gn_launch_pers64(const gnode_graph_s* g, const PersPlan& pl, long rows, cons
                      const int* slot_host, int n_steps, const gnode_params* p, float* S, float* I, float* R, float* sol, float* keep,
                      void* ctl, bool ctl_is_zero /* the caller's previous launch on this stream zero-filled it */, hipStream_t st);
 
-// adjoint sweep, intervals G-2 .. 1, in one persistent launch (gnode_pers64_bwd.hip)
+// adjoint sweep, intervals G-2 .. 1 (the discrete sweep: G-1 .. 2), in one persistent launch (gnode_pers64_bwd.hip)
 int gn_pers_bwd64_set_attributes();
 bool gn_pers_bwd64_plan(const gnode_graph_s* g, long B, int n_steps, PersPlan* p);
 int gn_launch_pers_bwd64(const gnode_graph_s* g, const PersPlan& pl, long rows, int G, float* Q0, float* Q1, const float* sol,
@@ -59,4 +59,5 @@ int gn_launch_pers_bwd64(const gnode_graph_s* g, const PersPlan& pl, long rows, 
                          const float* gS, const float* gI, const float* gR, const gnode_params* p, const float* dt_host,
                          const int* slot_of_prev, void* ctl, bool ctl_is_zero,
                          bool fold /* the adjoint is zero through interval G-1 (last grid point not emitted): start there */,
+                         bool exact /* the discrete sweep: intervals G-1 .. 2, Jacobians at the left endpoints */,
                          int* slots, hipStream_t st);

@@ -15,6 +15,12 @@
 // the per-interval kernels do) at the end; the final fixed-order reduction is unchanged -> bitwise reproducible run to run.
 // Numerics: the same VJPs in the same per-row order as k_bwd_kept64; only the order in which rows enter the parameter
 // sums differs (tests hold it to the per-interval path at 1e-5 and to the reference-class gradients at 2e-4).
+//
+// EXACT: the discrete sweep (gnode_backward_discrete_keep_f32), whose interval i+1 evaluates its Jacobian,
+// its parameter VJP AND the head at the LEFT endpoint y_i.  The loop index i is then that grid point: the launch covers
+// intervals G-1 .. 2 (i = G-2 .. 1), everything it reads was kept (P_S(y_i), Z_I(y_i), and Z_S(y_{i-1}) for the q row of the
+// interval below), the head reuses the y_i rows staged for gW, and the q row is stored at i = 1 too: interval 1, whose P_S(y_0)
+// the forward never had, follows on the recomputing launch and gathers it.
 #include "gnode_bwd.h"
 #include "gnode_h64.h"
 #include "gnode_mfma64.h"
@@ -27,7 +33,7 @@ struct PersBwdArgs {
     const int* hubslot; const int* segptr; const int* segitem;
     int n, B, b0, lds_slots; unsigned rows;
     PersPlace pp;
-    int G;                               // grid points; intervals i = G-2 .. 1 are run here
+    int G;                               // grid points; intervals i = G-2 .. 1 are run here (EXACT: intervals i+1 = G-1 .. 2)
     float* Q[2];                         // q tables [rows + 1][64]; interval i gathers Q[(G-1-i) & 1]
     const float* sol; const float* keep;
     const float* W; const float* beta; const float* gamma;
@@ -37,11 +43,11 @@ struct PersBwdArgs {
     const float* w3; const float* b3; const float* w2; const float* b2;
     PersCtl* ctl;
     int fold;                            // 1: the sweep also covers interval G-1, whose adjoint is zero (last grid point not emitted)
-    float dt[128];                       // dt[i]: step size of interval i (grid point i-1 -> i)
-    short slot[128];                     // slot[i]: output row of grid point i-1, or -1
+    float dt[128];                       // dt[i]: step size of interval i (grid point i-1 -> i); EXACT: of interval i+1
+    short slot[128];                     // slot[i]: output row of grid point i-1, or -1; EXACT: of grid point i
 };
 
-template <int NT, bool SC1ST, bool HUBS>
+template <int NT, bool SC1ST, bool HUBS, bool EXACT = false>
 __global__ __launch_bounds__(256 * NT) void k_pers_bwd64(const PersBwdArgs a) {
     constexpr int STAUX = SC1ST ? 16 : 0;
     constexpr int NM = 6;                                  // neighbour-id registers (16 ids each): every row up to the hub threshold (96)
@@ -127,21 +133,26 @@ __global__ __launch_bounds__(256 * NT) void k_pers_bwd64(const PersBwdArgs a) {
         q.zi = ld4so<true>(gn_keep_zi(a.keep, rows, i), off);
         q.ys = ld4so<true>(si, off); q.yi = ld4so<true>(si + slab, off);
         q.zsp = zero4();
-        if (i > 1) q.zsp = ld4so<true>(gn_keep_zs(a.keep, rows, i - 1), off);
+        if (EXACT || i > 1) q.zsp = ld4so<true>(gn_keep_zs(a.keep, rows, i - 1), off);
         const int s = a.slot[i];
         q.y[0] = q.y[1] = q.y[2] = zero4(); q.gout[0] = q.gout[1] = q.gout[2] = 0.f;
         if (s >= 0) {
-            const float* sp = a.sol + (size_t)(i - 1) * 4 * slab;
-            q.y[0] = ld4so<true>(sp, off); q.y[1] = ld4so<true>(sp + slab, off); q.y[2] = ld4so<true>(sp + 2 * slab, off);
+            if constexpr (EXACT) {
+                q.y[2] = ld4so<true>(si + 2 * slab, off);              // the head is at grid point i: y_S, y_I are q.ys, q.yi
+            } else {
+                const float* sp = a.sol + (size_t)(i - 1) * 4 * slab;
+                q.y[0] = ld4so<true>(sp, off); q.y[1] = ld4so<true>(sp + slab, off); q.y[2] = ld4so<true>(sp + 2 * slab, off);
+            }
             if (valid) { q.gout[0] = a.gS[(size_t)s * rows + row]; q.gout[1] = a.gI[(size_t)s * rows + row]; q.gout[2] = a.gR[(size_t)s * rows + row]; }
         }
     };
     Pre pre;
-    prefetch(G - 2, pre);
     const int fold = a.fold;                               // 1: the sweep starts one interval early (see gnode_backward_f32), every epoch is one later
+    const int top = EXACT ? G - 2 - fold : G - 2;          // the first loop index (EXACT: interval G-1, or G-2 behind the fold)
+    prefetch(top, pre);
     if (fold) {
         // interval G-1 with a zero adjoint: only the head's VJP at grid point G-2 and the q row interval G-2 gathers remain
-        const int s = a.slot[G - 1];
+        const int s = a.slot[EXACT ? G - 2 : G - 1];
         if (s >= 0) {
             float4 y[3];
             float gout[3] = {0.f, 0.f, 0.f};
@@ -153,16 +164,16 @@ __global__ __launch_bounds__(256 * NT) void k_pers_bwd64(const PersBwdArgs a) {
             for (int q = 0; q < 4; ++q) w3v[q] = ld4(a.w3 + q * 64 + 4 * sub);
             gn_head_vjp<DppSum16>(y, gout, w3v, a.b3, a.w2, a.b2, aS, aI, aR, hacc);
         }
-        const float4 zsp = ld4so<true>(gn_keep_zs(a.keep, rows, G - 2), off);
+        const float4 zsp = ld4so<true>(gn_keep_zs(a.keep, rows, EXACT ? G - 3 : G - 2), off);
         if (valid) pers_st<STAUX>(pers_rsrc(a.Q[1], tbytes), off,
                                   gn_q4(bt, aI, aS, zsp));
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         if (threadIdx.x == 0) __hip_atomic_store(flags + idx, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-    for (int i = G - 2; i >= 1; --i) {
-        const int k = G - 2 - i + fold;                    // epochs published so far
-        const int cur = (G - 1 - i) & 1;
+    for (int i = top; i >= 1; --i) {
+        const int k = top - i + fold;                      // epochs published so far
+        const int cur = (G - 1 - i - (EXACT ? 1 : 0)) & 1;
         const float dt = a.dt[i];
         if (k > 0) {
             bool ok = true;
@@ -201,15 +212,20 @@ __global__ __launch_bounds__(256 * NT) void k_pers_bwd64(const PersBwdArgs a) {
             float4 w3v[4];
 #pragma unroll
             for (int q = 0; q < 4; ++q) w3v[q] = ld4(a.w3 + q * 64 + 4 * sub);
-            gn_head_vjp<DppSum16>(p.y, p.gout, w3v, a.b3, a.w2, a.b2, aS, aI, aR, hacc);   // padding rows: gout = 0 adds nothing
+            if constexpr (EXACT) {
+                const float4 yh[3] = {p.ys, p.yi, p.y[2]};
+                gn_head_vjp<DppSum16>(yh, p.gout, w3v, a.b3, a.w2, a.b2, aS, aI, aR, hacc);
+            } else {
+                gn_head_vjp<DppSum16>(p.y, p.gout, w3v, a.b3, a.w2, a.b2, aS, aI, aR, hacc);   // padding rows: gout = 0 adds nothing
+            }
         }
-        if (i > 1) {
+        if (EXACT || i > 1) {
             if (valid) pers_st<STAUX>(pers_rsrc(a.Q[cur ^ 1], tbytes), off,
                                       gn_q4(bt, aI, aS, p.zsp));
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __syncthreads();
             if (threadIdx.x == 0) __hip_atomic_store(flags + idx, (unsigned)k + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            prefetch(i - 1, pre);                                      // the next interval's own rows, under the barrier
+            if (!EXACT || i > 1) prefetch(i - 1, pre);                 // the next interval's own rows, under the barrier
         }
         // ---- behind the flag: gW += dt dpre^T y (contraction over the team's 16 rows)
         {
@@ -277,9 +293,10 @@ static size_t pers_bwd_lds_bytes(int nt, int partial_slots = 128) {
 }
 
 int gn_pers_bwd64_set_attributes() {
-#define PB_ATTR(N, S) GN_HIP(hipFuncSetAttribute((const void*)k_pers_bwd64<N, S, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pers_bwd_lds_bytes(N))); \
-                      GN_HIP(hipFuncSetAttribute((const void*)k_pers_bwd64<N, S, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pers_bwd_lds_bytes(N)));
+#define PB_ATTR1(N, S, HB, EX) GN_HIP(hipFuncSetAttribute((const void*)k_pers_bwd64<N, S, HB, EX>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pers_bwd_lds_bytes(N)));
+#define PB_ATTR(N, S) PB_ATTR1(N, S, false, false) PB_ATTR1(N, S, true, false) PB_ATTR1(N, S, false, true) PB_ATTR1(N, S, true, true)
     PB_ATTR(1, false) PB_ATTR(1, true) PB_ATTR(2, false) PB_ATTR(2, true)
+#undef PB_ATTR1
 #undef PB_ATTR
     return 0;
 }
@@ -287,11 +304,14 @@ int gn_pers_bwd64_set_attributes() {
 // intervals G-2 .. 1 over the forward's kept activations; `a` holds the adjoint at grid point G-2 (the head's VJP there
 // included), Q[(G-1-(G-2)) & 1] = Q[1] the q table the recomputing launch of interval G-1 left.  Returns the number of
 // partial slots it wrote through *slots.
+// exact (the discrete sweep): intervals G-1 .. 2; `a` holds the adjoint at grid point G-1 and Q[0] = beta (a_I - a_S) Z_S(y_{G-2})
+// from the kept table (with `fold` the launch forms its first q row itself, as above); its last q table, Q[(G-2) & 1], is the
+// one interval 1 gathers.
 int gn_launch_pers_bwd64(const gnode_graph_s* g, const PersPlan& pl, long rows, int G, float* Q0, float* Q1, const float* sol,
                          const float* keep, const float* W, const float* beta, const float* gamma, float* a, float* part,
                          const float* gS, const float* gI, const float* gR, const gnode_params* p, const float* dt_host,
                          const int* slot_of_prev /* [G]: output row of grid point i-1 for interval i, or -1 */, void* ctl,
-                         bool ctl_is_zero, bool fold, int* slots, hipStream_t st) {
+                         bool ctl_is_zero, bool fold, bool exact, int* slots, hipStream_t st) {
     PersBwdArgs x;
     const int vi = pl.nt == 1 ? 0 : 1;
     const bool hubs = g->n_hub > 0;
@@ -304,9 +324,12 @@ int gn_launch_pers_bwd64(const gnode_graph_s* g, const PersPlan& pl, long rows, 
     x.w3 = p->linear3_weight; x.b3 = p->linear3_bias; x.w2 = p->linearS2_weight; x.b2 = p->linearS2_bias;
     x.ctl = (PersCtl*)ctl;
     for (int i = 0; i < 128; ++i) { x.dt[i] = 0.f; x.slot[i] = -1; }
-    for (int i = 1; i <= G - 2; ++i) { x.dt[i] = dt_host[i - 1]; x.slot[i] = (short)slot_of_prev[i]; }
+    for (int i = 1; i <= G - 2; ++i) {
+        x.dt[i] = dt_host[exact ? i : i - 1];
+        x.slot[i] = (short)slot_of_prev[exact ? i + 1 : i];
+    }
     x.fold = fold ? 1 : 0;
-    if (fold && G - 1 < 128) x.slot[G - 1] = (short)slot_of_prev[G - 1];      // the head's VJP at grid point G-2 belongs to interval G-1
+    if (fold && !exact && G - 1 < 128) x.slot[G - 1] = (short)slot_of_prev[G - 1];      // the head's VJP at grid point G-2 belongs to interval G-1
     const bool sc1 = pl.span > 1;
     const dim3 grid((unsigned)(pl.n_xcc * pl.slots));
     // samples are independent: batches beyond what one resident grid holds run as consecutive launches of `concurrent` samples
@@ -314,11 +337,13 @@ int gn_launch_pers_bwd64(const gnode_graph_s* g, const PersPlan& pl, long rows, 
         x.b0 = b0;
         if (!(ctl_is_zero && b0 == 0))
             if (int e = gn_pers64_zero_ctl(ctl, st)) return e;
-#define PB_GO(N, S) { if (hubs) hipLaunchKernelGGL((k_pers_bwd64<N, S, true>), grid, dim3(256 * N), pers_bwd_lds_bytes(N, g->perslds[vi]), st, x); \
-                      else hipLaunchKernelGGL((k_pers_bwd64<N, S, false>), grid, dim3(256 * N), pers_bwd_lds_bytes(N, 0), st, x); }
+#define PB_GO1(N, S, EX) { if (hubs) hipLaunchKernelGGL((k_pers_bwd64<N, S, true, EX>), grid, dim3(256 * N), pers_bwd_lds_bytes(N, g->perslds[vi]), st, x); \
+                           else hipLaunchKernelGGL((k_pers_bwd64<N, S, false, EX>), grid, dim3(256 * N), pers_bwd_lds_bytes(N, 0), st, x); }
+#define PB_GO(N, S) { if (exact) PB_GO1(N, S, true) else PB_GO1(N, S, false) }
         if (pl.nt == 1) { if (sc1) PB_GO(1, true) else PB_GO(1, false) }
         else { if (sc1) PB_GO(2, true) else PB_GO(2, false) }
 #undef PB_GO
+#undef PB_GO1
         GN_LAUNCH_CHECK();
     }
     *slots = (int)std::min<long>((long)std::min<long>(x.B, BWD_NWG / pl.wgs) * pl.wgs, BWD_NWG);

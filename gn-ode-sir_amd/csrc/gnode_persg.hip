@@ -290,7 +290,10 @@ __device__ __forceinline__ float4 pg_lin(float4 x, const float* __restrict__ M, 
     return acc;
 }
 
-template <int LPR>
+// EXACT: the discrete sweep (gnode_backward_discrete_keep_f32): interval i evaluates its Jacobian, its
+// parameter VJP and the head at y_{i-1}.  The rows a lane group holds (zs0, zi0, yS, yI) are then those of y_{i-1}: the
+// start-up builds the first tables from y_{G-2}, the head reuses yS, yI, and the next tables and q come from y_{i-2}.
+template <int LPR, bool EXACT = false>
 __global__ __launch_bounds__(256) void k_persg_bwd(const PersgArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     constexpr int H = 4 * LPR;
@@ -328,7 +331,7 @@ __global__ __launch_bounds__(256) void k_persg_bwd(const PersgArgs a) {
             const float4 bg = ld4(a.sol + 3 * slab + (size_t)row.r * H);          // sol[0]'s 4th slab: beta, gamma, ... (ode_nn_ngraph_sim.py:149-168)
             bt = bg.x; gm = bg.y;
             const float* Yl = a.sol + (size_t)(G - 1) * 4 * slab;
-            y[0] = ld4(Yl + off); y[1] = ld4(Yl + slab + off);
+            if (!EXACT || slot_last >= 0) { y[0] = ld4(Yl + off); y[1] = ld4(Yl + slab + off); }
             if (slot_last >= 0) {
                 y[2] = ld4(Yl + 2 * slab + off);
                 const size_t o = (size_t)slot_last * a.rows + row.r;
@@ -336,6 +339,13 @@ __global__ __launch_bounds__(256) void k_persg_bwd(const PersgArgs a) {
             }
         }
         if (slot_last >= 0) gn_head_vjp<XorSum<LPR>>(y, gout, w3v, a.b3, a.w2, a.b2, aS, aI, aR, hacc);
+        if constexpr (EXACT) {                                                     // the first Jacobian is at y_{G-2}
+            y[0] = z0; y[1] = z0;
+            if (row.inrow) {
+                const float* Yp = a.sol + (size_t)(G - 2) * 4 * slab;
+                y[0] = ld4(Yp + off); y[1] = ld4(Yp + slab + off);
+            }
+        }
         yS = y[0]; yI = y[1];
         zs0 = group_mlp<LPR>(yS, L.Wt, bias4, sub, true, H);                       // (the start-up launch's arithmetic: bias first)
         zi0 = group_mlp<LPR>(yI, L.Wt, bias4, sub, true, H);
@@ -363,7 +373,11 @@ __global__ __launch_bounds__(256) void k_persg_bwd(const PersgArgs a) {
         float gout[3] = {0.f, 0.f, 0.f};
         if (row.inrow) {
             const float* Yp = a.sol + (size_t)(i - 1) * 4 * slab;
-            y[0] = ld4(Yp + off); y[1] = ld4(Yp + slab + off);
+            if constexpr (EXACT) {                          // the next tables' rows are y_{i-2}; y_S, y_I of y_{i-1} are held
+                if (i > 1) { y[0] = ld4(Yp - 4 * slab + off); y[1] = ld4(Yp - 3 * slab + off); }
+            } else {
+                y[0] = ld4(Yp + off); y[1] = ld4(Yp + slab + off);
+            }
             if (slot >= 0) {
                 y[2] = ld4(Yp + 2 * slab + off);
                 const size_t o = (size_t)slot * a.rows + row.r;
@@ -396,8 +410,15 @@ __global__ __launch_bounds__(256) void k_persg_bwd(const PersgArgs a) {
         aS.x += dt * uS.x; aS.y += dt * uS.y; aS.z += dt * uS.z; aS.w += dt * uS.w;
         aI.x += dt * uI.x; aI.y += dt * uI.y; aI.z += dt * uI.z; aI.w += dt * uI.w;
         // dL/dsol[i-1] through the head
-        if (slot >= 0) gn_head_vjp<XorSum<LPR>>(y, gout, w3v, a.b3, a.w2, a.b2, aS, aI, aR, hacc);
-        // Z(y_{i-1}) and q: the tables the next interval gathers
+        if (slot >= 0) {
+            if constexpr (EXACT) {
+                const float4 yh[3] = {yS, yI, y[2]};
+                gn_head_vjp<XorSum<LPR>>(yh, gout, w3v, a.b3, a.w2, a.b2, aS, aI, aR, hacc);
+            } else {
+                gn_head_vjp<XorSum<LPR>>(y, gout, w3v, a.b3, a.w2, a.b2, aS, aI, aR, hacc);
+            }
+        }
+        // Z(y_{i-1}) and q: the tables the next interval gathers (EXACT: Z(y_{i-2}))
         float4 zs = z0, zi = z0;
         if (i > 1) {
             zs = pg_lin<LPR>(y[0], L.Wt, sub); zi = pg_lin<LPR>(y[1], L.Wt, sub);
@@ -568,6 +589,9 @@ int gn_persg_set_attributes() {
     GN_HIP(hipFuncSetAttribute((const void*)k_persg_bwd<2>, hipFuncAttributeMaxDynamicSharedMemorySize, mx));
     GN_HIP(hipFuncSetAttribute((const void*)k_persg_bwd<4>, hipFuncAttributeMaxDynamicSharedMemorySize, mx));
     GN_HIP(hipFuncSetAttribute((const void*)k_persg_bwd<8>, hipFuncAttributeMaxDynamicSharedMemorySize, mx));
+    GN_HIP(hipFuncSetAttribute((const void*)k_persg_bwd<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, mx));
+    GN_HIP(hipFuncSetAttribute((const void*)k_persg_bwd<4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, mx));
+    GN_HIP(hipFuncSetAttribute((const void*)k_persg_bwd<8, true>, hipFuncAttributeMaxDynamicSharedMemorySize, mx));
     return 0;
 }
 
@@ -605,7 +629,7 @@ int gn_launch_persg(const gnode_graph_s* g, const PersgPlan& pl, long rows, int 
 int gn_launch_persg_bwd(const gnode_graph_s* g, const PersgPlan& pl, long rows, int H, int G, float* ZI0, float* ZI1, float* Q0, float* Q1,
                         const float* ZS0, const float* sol, const float* beta, const float* gamma, float* a_state, float* part,
                         const float* gS, const float* gI, const float* gR, const gnode_params* p, const float* dt_host,
-                        const int* slot_of_prev, void* ctl, bool ctl_is_zero, hipStream_t st) {
+                        const int* slot_of_prev, void* ctl, bool ctl_is_zero, bool exact, hipStream_t st) {
     PersgArgs a;
     persg_common(a, g, pl, rows, H, p, ctl);
     a.T0 = ZI0; a.T1 = ZI1; a.Q0 = Q0; a.Q1 = Q1; a.ZS0 = ZS0; a.sol = const_cast<float*>(sol); a.beta = beta; a.gamma = gamma;
@@ -616,7 +640,11 @@ int gn_launch_persg_bwd(const gnode_graph_s* g, const PersgPlan& pl, long rows, 
     if (!ctl_is_zero)
         if (int e = gn_pers64_zero_ctl(ctl, st)) return e;
     const dim3 grid((unsigned)pl.wgs);
-    if (H == 8) hipLaunchKernelGGL(k_persg_bwd<2>, grid, dim3(64 * pl.nw), pl.lds, st, a);
+    if (exact) {
+        if (H == 8) hipLaunchKernelGGL((k_persg_bwd<2, true>), grid, dim3(64 * pl.nw), pl.lds, st, a);
+        else if (H == 16) hipLaunchKernelGGL((k_persg_bwd<4, true>), grid, dim3(64 * pl.nw), pl.lds, st, a);
+        else hipLaunchKernelGGL((k_persg_bwd<8, true>), grid, dim3(64 * pl.nw), pl.lds, st, a);
+    } else if (H == 8) hipLaunchKernelGGL(k_persg_bwd<2>, grid, dim3(64 * pl.nw), pl.lds, st, a);
     else if (H == 16) hipLaunchKernelGGL(k_persg_bwd<4>, grid, dim3(64 * pl.nw), pl.lds, st, a);
     else hipLaunchKernelGGL(k_persg_bwd<8>, grid, dim3(64 * pl.nw), pl.lds, st, a);
     GN_LAUNCH_CHECK();

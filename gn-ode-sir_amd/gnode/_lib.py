@@ -64,6 +64,8 @@ ABI = {
     "gnode_backward_discrete_workspace_bytes": (_sz, [_vp, _i64, _i32]),
     "gnode_backward_discrete_f32": (_int, [_vp, _vp, _P, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _P, _vp, _i64, _i32,
                                            _vp, _sz, _vp]),
+    "gnode_backward_discrete_keep_f32": (_int, _BWD + [_vp]),
+    "gnode_backward_discrete_path": (_int, [_vp, _i64, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _i32]),
     "gnode_sir_workspace_bytes": (_sz, [_vp, _i32]),
     "gnode_sir_coins_workspace_bytes": (_sz, []),
     "gnode_sir_mc_philox": (_int, _SIR),
@@ -100,8 +102,8 @@ def load():
     for name, (restype, argtypes) in ABI.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
-    if lib.gnode_version() < 224:
-        raise GnodeError(f"{LIB_PATH} is stale (ABI {lib.gnode_version()} < 224): rebuild it (gnode.build.build_lib)")
+    if lib.gnode_version() < 225:
+        raise GnodeError(f"{LIB_PATH} is stale (ABI {lib.gnode_version()} < 225): rebuild it (gnode.build.build_lib)")
     _lib = lib
     return lib
 

@@ -24,9 +24,13 @@ class _GNODEForward(torch.autograd.Function):
     @staticmethod
     def forward(ctx, graph, x2d, dts, method, out_rows, adjoint, keys, *tensors):
         params = dict(zip(keys, tensors))
-        # an input gradient, and the exact (adjoint=False) gradient, need the recomputing backward: no kept activations, the
-        # trajectory carries A Z_I instead
-        want_keep = False if (ctx.needs_input_grad[1] or not adjoint) else None
+        # an input gradient needs the recomputing backward: no kept activations, the trajectory carries A Z_I instead.  The
+        # exact (adjoint=False) gradient runs over the kept activations like the adjoint (backward passes ctx.keep explicitly),
+        # except where its plan stays recomputing whatever is kept (one-workgroup-size graphs, 2-point grids)
+        want_keep = False if ctx.needs_input_grad[1] else None
+        if want_keep is None and not adjoint and x2d.shape[1] - 3 == 64 and \
+                ops.discrete_path(graph, x2d.shape[0], 64, len(dts), out_rows, keep=True) == 0:
+            want_keep = False
         S, I, R, sol = ops.forward(graph, x2d.detach(), params, dts, method, out_rows, want_sol=True, want_keep=want_keep)
         ctx.graph, ctx.dts, ctx.method, ctx.out_rows, ctx.adjoint, ctx.keys = graph, dts, method, out_rows, adjoint, keys
         ctx.keep = sol.gnode_keep            # kept activations (a plain buffer nothing else references), or None

@@ -243,13 +243,19 @@ def backward(graph: DeviceGraph, x2d: torch.Tensor, params: dict, dts: np.ndarra
     want_x: also dL/dx2d as key "x" ([rows, 3+H]; include/gnode.h gnode_backward_dx_f32; needs a trajectory produced
     without keep); want_params=False: no parameter gradients (then want_x must be set).
     adjoint=False: the exact gradient of the Euler solve instead (backpropagation through the solver, include/gnode.h
-    gnode_backward_discrete_f32); `sol` must come from a forward without keep, `keep` and `persist`
-    are not used."""
+    gnode_backward_discrete_keep_f32).  An EXPLICIT keep=<tensor> (the forward's ``sol.gnode_keep``)
+    selects the kept / persistent sweep at H = 64; "auto" and None pass no buffer, so a keep-produced trajectory is refused;
+    `persist` is honoured as for the adjoint (H <= 32: the one-launch sweep).  With NEITHER keep nor persist given the call is
+    the recomputing one it always was, bit for bit (so its parameter gradients still equal a want_x call's).  `discrete_path`
+    says which form runs."""
     if not (want_x or want_params):
         raise _lib.GnodeError("backward: neither parameter nor input gradients requested")
     solve = (graph, x2d, params, dts, out_rows, sol, gS, gI, gR)
     if not _check_adjoint(adjoint, method):
-        return _backward_discrete(*solve, want_x=want_x, want_params=want_params)
+        if isinstance(keep, str):
+            # no buffer is picked up from `sol`; with persist left alone too this is the recomputing call of ABI 224, bit for bit
+            keep, persist = None, (False if persist is None else persist)
+        return _backward_discrete(*solve, want_x=want_x, want_params=want_params, keep=keep, persist=persist)
     if method == "rk4":
         return _backward_rk4(*solve, want_x=want_x, want_params=want_params)
     if isinstance(keep, str):
@@ -276,15 +282,34 @@ def _backward_rk4(graph: DeviceGraph, x2d, params: dict, dts, out_rows, sol, gS,
 
 
 def _backward_discrete(graph: DeviceGraph, x2d, params: dict, dts, out_rows, sol, gS, gI, gR, want_x: bool = False,
-                       want_params: bool = True) -> dict:
-    """The exact gradient of a method='euler' forward: gnode_backward_discrete_f32 (one entry, gx in its own place)."""
-    info = int(getattr(sol, "gnode_info", -1))
-    # (the call zeroes its control block: backward_status reads 0)
+                       want_params: bool = True, keep=None, persist: bool | None = None) -> dict:
+    """The exact gradient of a method='euler' forward: gnode_backward_discrete_keep_f32 (one entry, gx last; the arguments of
+    gnode_backward_dx_f32).  keep: the forward's kept activations or None; persist: as `backward`."""
+    kept = (_lib.ptr(keep), keep.numel() * 4) if keep is not None else (None, 0)
+    last = (_fwd_flags(persist), int(getattr(sol, "gnode_info", -1)))
+    # (the call zeroes its control block: backward_status reads 0 unless a persistent sweep gave up)
     grads, backward.last_workspace = _run_backward(
-        "gnode_backward_discrete_workspace_bytes", "gnode_backward_discrete_f32", None,
-        lambda head, ups, tail, gx: head + (info,) + ups + (gx,) + tail,
+        "gnode_backward_discrete_workspace_bytes", "gnode_backward_discrete_keep_f32", None,
+        lambda head, ups, tail, gx: head + kept + ups + tail + last + (gx,),
         graph, x2d, params, dts, out_rows, sol, gS, gI, gR, want_x, want_params)
     return grads
+
+
+def discrete_path(graph: DeviceGraph, rows: int, H: int, n_steps: int, out_rows=None, sol=None, keep=None,
+                  persist: bool | None = None, want_x: bool = False) -> int:
+    """The form `backward(adjoint=False, keep=keep, persist=persist, want_x=want_x)` takes on `sol` (include/gnode.h
+    gnode_backward_discrete_path): 0 = recomputing, one launch per interval; 1 = kept activations, one launch per interval;
+    2 = persistent H = 64 sweep; 3 = persistent H <= 32 sweep."""
+    if out_rows is not None:
+        out_rows = np.ascontiguousarray(out_rows, dtype=np.int32)
+    n_out = int(out_rows.shape[0]) if out_rows is not None else n_steps + 1
+    path = _lib.load().gnode_backward_discrete_path(graph.handle, rows, H, n_steps,
+                                                    _lib.host_ptr(out_rows) if out_rows is not None else None, n_out,
+                                                    int(keep is not None), _fwd_flags(persist),
+                                                    int(getattr(sol, "gnode_info", -1)), int(want_x))
+    if path < 0:
+        raise _lib.GnodeError("discrete_path: bad arguments")
+    return int(path)
 
 
 def backward_status() -> int:

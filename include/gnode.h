@@ -14,7 +14,7 @@
  *     past the call.  "host" pointers are ordinary memory, read before return.
  *   - `stream` is a hipStream_t passed as void* (NULL = the default stream).
  *     All work is enqueued on it.  gnode_rhs_f32, gnode_forward_f32,
- *     gnode_backward_f32, gnode_rhs_vjp_f32, gnode_backward_rk4_f32, their _dx forms, gnode_backward_discrete_f32 and gnode_l1_loss_f32 allocate nothing, synchronise nothing and keep nothing in
+ *     gnode_backward_f32, gnode_rhs_vjp_f32, gnode_backward_rk4_f32, their _dx forms, gnode_backward_discrete_f32, gnode_backward_discrete_keep_f32 and gnode_l1_loss_f32 allocate nothing, synchronise nothing and keep nothing in
  *     the graph handle: every byte of scratch (including the partial sums of long
  *     "hub" rows) is carved from the caller's workspace, so they can be captured
  *     into a hipGraph on first use and one handle may serve several streams (each
@@ -270,7 +270,7 @@ int gnode_backward_rk4_dx_f32(gnode_graph_t g, const float* x, const gnode_param
  *              carry it), or -1 = unchecked (A*Z_I is gathered at every interval).  A keep-produced trajectory
  *              (GNODE_SOL_KEEP): GNODE_ERR_ARG.
  *   grads, gx  as gnode_backward_dx_f32 (gx columns 3, 4 sum the same terms at y_{i-1}); either may be NULL, not both.
- * Other arguments as gnode_backward_f32.  Runs the recomputing one-launch-per-interval forms (H = 64: the fused interval
+ * Other arguments as gnode_backward_f32.  ALWAYS runs the recomputing one-launch-per-interval forms (H = 64: the fused interval
  * kernel; H <= 32: the small-H interval kernel; other H: five launches per interval), never the kept, persistent or
  * one-launch sweeps.  Deterministic (fixed-order reduction, no float atomics); enqueue-only (capturable).
  *   workspace  device, >= gnode_backward_discrete_workspace_bytes(g, rows, H) */
@@ -281,6 +281,36 @@ int gnode_backward_discrete_f32(gnode_graph_t g, const float* x, const gnode_par
                                 const float* gS, const float* gI, const float* gR,
                                 const gnode_params* grads, float* gx,
                                 int64_t rows, int32_t H, void* workspace, size_t workspace_bytes, void* stream);
+
+/* The same gradient on the forms of the training backward (ABI 225): the arguments of gnode_backward_dx_f32.
+ *   keep, keep_bytes  the kept activations of the forward that produced `sol` (H = 64), or NULL.  With a checked sol_info the
+ *              pairing rule of gnode_backward_f32 holds: keep with a trajectory lacking GNODE_SOL_KEEP, or a keep-produced
+ *              trajectory without its buffer, is GNODE_ERR_ARG; keep together with gx is GNODE_ERR_ARG; a keep buffer smaller
+ *              than gnode_forward_keep_bytes is GNODE_ERR_WORKSPACE.
+ *   flags      as gnode_backward_f32 (GNODE_FWD_PER_STEP: no persistent launch)
+ * Interval i reads grid point i-1, all of which the forward kept for i = G-1 .. 2: P_S(y_{i-1}), Z_I(y_{i-1}), and
+ * Z_S(y_{i-2}) for the next q row; the head's VJP at grid point i-1 reuses the rows staged for gW.  Forms
+ * (gnode_backward_discrete_path):
+ *   0  recomputing, one launch per interval: what gnode_backward_discrete_f32 runs.  Any gx call, H = 64 without keep, graphs
+ *      of the one-workgroup sweep's size (n <= 64: karate) or behind a one-workgroup forward (GNODE_SOL_TINY), 2-point grids, H > 32 other than 64, batches beyond one resident grid at H <= 32
+ *   1  H = 64 with keep: intervals G-1 .. 2 one launch each over the kept activations, interval 1 (P_S(y_0) is not kept) on
+ *      the two-table recomputing launch, which gathers A Z_I(y_0) from the kept Z_I table
+ *   2  H = 64 with keep, mid-size graphs: intervals G-1 .. 2 in ONE persistent launch (up to two per batch), then interval 1
+ *   3  H = 8, 16, 32: the whole sweep in one persistent launch
+ * Forms 2 and 3 write the give-up word gnode_backward_status reads.  Gradients agree with form 0 to rounding (rows enter
+ * the parameter sums in another order).  Deterministic (fixed-slot reduction, no float atomics, bitwise repeatable); allocates
+ * nothing, synchronises nothing, reads no environment variable; enqueue-only (capturable).
+ *   workspace  device, >= gnode_backward_discrete_workspace_bytes(g, rows, H) */
+int gnode_backward_discrete_keep_f32(gnode_graph_t g, const float* x, const gnode_params* p, const float* dt_host,
+                                     int32_t n_steps, const int32_t* out_rows_host, int32_t n_out, const float* sol,
+                                     const float* keep, size_t keep_bytes,
+                                     const float* gS, const float* gI, const float* gR, const gnode_params* grads,
+                                     int64_t rows, int32_t H, void* workspace, size_t workspace_bytes, void* stream,
+                                     int32_t flags, int32_t sol_info, float* gx);
+/* Which form (0 .. 3 above) a gnode_backward_discrete_keep_f32 call with these arguments takes; -1 on a bad argument.
+ * with_keep / with_gx: whether the call passes keep / gx.  Host only, touches no device memory. */
+int gnode_backward_discrete_path(gnode_graph_t g, int64_t rows, int32_t H, int32_t n_steps, const int32_t* out_rows_host,
+                                 int32_t n_out, int32_t with_keep, int32_t flags, int32_t sol_info, int32_t with_gx);
 
 /* ---- Monte-Carlo SIR labels ------------------------------------------------
  * sir_torch(G, seed_set, beta, gamma, sims, T): ode_nn.py:30-88.

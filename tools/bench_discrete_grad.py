@@ -1,11 +1,14 @@
 #!/usr/bin/env python3
-"""The exact gradient of the Euler solve (ops.backward adjoint=False; include/gnode.h gnode_backward_discrete_f32) against the
-adjoint backward, device-event timings after warm-up, one JSON line per shape:
+"""The exact gradient of the Euler solve (ops.backward adjoint=False; include/gnode.h gnode_backward_discrete_keep_f32) against
+the adjoint backward, device-event timings after warm-up, one JSON line per shape:
   adjoint_ms     the adjoint's one-launch-per-interval form on a trajectory without keep (GNODE_FWD_PER_STEP): its twin
-  exact_ms       the exact gradient, parameters only
+  exact_ms       the exact gradient on the recomputing form (a trajectory without keep, persist off), parameters only
   exact_dx_ms    parameters and x
-  train_ms       today's default training backward (kept activations / persistent sweeps where they apply)
-  *_per_iv_us    the same per interval; exact_over_adjoint, exact_over_train: the ratios DESIGN.md section 7.3 records
+  train_ms       the adjoint's default training backward (kept activations / persistent sweeps where they apply)
+  exact_fast_ms  the exact gradient's default (ODEBlock(adjoint=False)): over the kept activations / one persistent launch,
+                 exact_path = the form it takes (ops.discrete_path)
+  *_per_iv_us    the same per interval; exact_over_adjoint, exact_over_train, exact_fast_over_train, exact_fast_over_exact:
+                 the ratios DESIGN.md section 7.3 records
 Run on the GPU:  python tools/bench_discrete_grad.py"""
 import json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -42,16 +45,21 @@ def case(tag, graph, x2d, H, maxTime, deltaT=0.5):
     out = {"case": tag, "rows": rows, "H": H, "intervals": nint}
     _, _, _, sol_k = ops.forward(graph, x2d, P, dts, "euler", rows_out, want_sol=True)
     out["train_ms"] = ev_ms(lambda: ops.backward(graph, x2d, P, dts, "euler", rows_out, sol_k, gS, gI, gR))
-    del sol_k
+    keep = sol_k.gnode_keep
+    out["exact_path"] = ops.discrete_path(graph, rows, H, nint, rows_out, sol_k, keep)
+    out["exact_fast_ms"] = ev_ms(lambda: ops.backward(graph, x2d, P, dts, "euler", rows_out, sol_k, gS, gI, gR, keep=keep, adjoint=False))
+    del sol_k, keep
     _, _, _, sol = ops.forward(graph, x2d, P, dts, "euler", rows_out, want_sol=True, want_keep=False)
     bw = lambda **kw: ops.backward(graph, x2d, P, dts, "euler", rows_out, sol, gS, gI, gR, **kw)
     out["adjoint_ms"] = ev_ms(lambda: bw(keep=None, persist=False))
-    out["exact_ms"] = ev_ms(lambda: bw(adjoint=False))
+    out["exact_ms"] = ev_ms(lambda: bw(adjoint=False, persist=False))
     out["exact_dx_ms"] = ev_ms(lambda: bw(adjoint=False, want_x=True))
     for k in ("adjoint", "exact", "exact_dx"):
         out[k + "_per_iv_us"] = 1e3 * out[k + "_ms"] / nint
     out["exact_over_adjoint"] = out["exact_ms"] / out["adjoint_ms"]
     out["exact_over_train"] = out["exact_ms"] / out["train_ms"]
+    out["exact_fast_over_train"] = out["exact_fast_ms"] / out["train_ms"]
+    out["exact_fast_over_exact"] = out["exact_fast_ms"] / out["exact_ms"]
     print(json.dumps({k: round(v, 4) if isinstance(v, float) else v for k, v in out.items()}), flush=True)
 
 
