@@ -2,7 +2,7 @@
 #pragma once
 #include "gnode_common.h"
 
-#define BWD_NWG 768     // 3 workgroups per CU (52 KB of LDS each) on 256 CUs
+// BWD_NWG, the partial-gradient slots of a call: gnode_graph_plan.h (the adjoint sweep's plan is bound by it)
 
 // partial-buffer layout per workgroup (floats)
 struct PartLayout {

@@ -1164,7 +1164,7 @@ static BwdLayout backward_layout(int64_t rows, int32_t H) {
 
 extern "C" size_t gnode_backward_workspace_bytes(gnode_graph_t g, int64_t rows, int32_t H) {
     if (!g || rows <= 0 || H <= 0) return 0;
-    return backward_layout(rows, H).fixed + gn_hub_scratch_bytes(g, rows / g->n, H, 2);     // two tables per hub pass
+    return backward_layout(rows, H).fixed + gn_hub_scratch_bytes(g, rows / g->info.n, H, 2);     // two tables per hub pass
 }
 
 // dynamic LDS above 64 KB (the five-launch generic path at H > 100) needs the attribute once per device
@@ -1217,16 +1217,16 @@ static BwdPlan backward_plan(gnode_graph_s* g, long rows, int H, int n_steps, in
         // last read Z_S(y_k), Z_I(y_k) back when the forward kept them as well
         pl.keep = !pl.fwd_tiny && gnode_forward_keep_bytes(g, rows, H, n_steps, n_emit) > 0 ? keep : nullptr;
         if (exact) {
-            const bool fits32 = rows < (1L << 24) && (long)(rows / g->n) * g->n_seg < (1L << 24);    // k_bwd_kept64's byte offsets
+            const bool fits32 = rows < (1L << 24) && (long)(rows / g->info.n) * g->n_seg < (1L << 24);    // k_bwd_kept64's byte offsets
             if (G < 3 || !fits32 || want_x || gn_tiny_bwd64_ok(g, rows, H, n_steps)) pl.keep = nullptr;
             const bool last_zero = slot[G - 1] < 0;
             // with a zero adjoint through interval G-1 the persistent launch needs an interval of its own below it: G-2 >= 2
-            pl.persist = pl.keep && G >= (last_zero ? 4 : 3) && persist_ok && gn_pers_bwd64_plan(g, rows / g->n, n_steps, &pl.pers);
+            pl.persist = pl.keep && G >= (last_zero ? 4 : 3) && persist_ok && gn_pers_bwd64_plan(g->info, rows / g->info.n, n_steps, &pl.pers);
             pl.fold = pl.persist && last_zero;
             pl.skip_last = !pl.persist && pl.keep && last_zero;
             return pl;
         }
-        pl.persist = pl.keep && G >= 3 && persist_ok && gn_pers_bwd64_plan(g, rows / g->n, n_steps, &pl.pers);
+        pl.persist = pl.keep && G >= 3 && persist_ok && gn_pers_bwd64_plan(g->info, rows / g->info.n, n_steps, &pl.pers);
         // The last grid point emits nothing in the reference's use (get_sir_t_nodes_torch keeps the integer times, the grid ends
         // half a step later): the adjoint is still ZERO through interval G-1 -- every product of that interval is zero -- and all
         // it leaves is the head's VJP at grid point G-2 and the first q table.  The persistent sweep does that at its start
@@ -1236,11 +1236,11 @@ static BwdPlan backward_plan(gnode_graph_s* g, long rows, int H, int n_steps, in
         // on a zero adjoint (451 us at 75k x 4 against 282 for a kept interval) only the head's VJP at grid point G-2 and
         // q = beta (a_I - a_S) Z_S(y_{G-2}) from the kept table run
         pl.skip_last = !pl.persist && pl.keep && G >= 3 && slot[G - 1] < 0 && rows < (1L << 24) &&
-                       (long)(rows / g->n) * g->n_seg < (1L << 24);
+                       (long)(rows / g->info.n) * g->n_seg < (1L << 24);
     } else if (H <= 32 && n_steps >= 1) {
         pl.path = BwdPath::small_h;
         // batches that fit one resident grid: the whole sweep INCLUDING its start-up is one persistent launch
-        pl.gpersist = persist_ok && gn_persg_plan(g, rows, H, n_steps, &pl.persg);
+        pl.gpersist = persist_ok && gn_persg_plan(g->info, rows, H, n_steps, &pl.persg);
     } else {
         pl.path = BwdPath::generic;
     }
@@ -1319,7 +1319,7 @@ static int backward_tiny(BwdCall& c, const float* x, const int32_t* out_rows_hos
     if (int e = gn_launch_tiny_bwd64(c.g, c.rows, x, c.p, c.dt_host, n_steps, out_rows_host, n_out, c.sol, c.gS, c.gI, c.gR, c.part,
                                      keep_need > 0 ? keep : nullptr, c.st))
         return e;
-    c.slots_used = (int)(c.rows / c.g->n);
+    c.slots_used = (int)(c.rows / c.g->info.n);
     PersCtl* ctl = (PersCtl*)c.ctl;       // (gnode_backward_status reads a defined word after this path too)
     return gn_zero_async(ctl->error, sizeof(ctl->error), c.st);
 }
@@ -1331,8 +1331,8 @@ static int backward_tiny(BwdCall& c, const float* x, const int32_t* out_rows_hos
 struct Tables64 { float* ZIb[2]; float* Qb[2]; };
 static Tables64 tables64(const BwdCall& c) { return {{c.Z + c.slab, c.dpre}, {c.q, c.dpre + c.slab_b / sizeof(float)}}; }
 static int grid64(const BwdCall& c) {
-    const long total = (long)(c.rows / c.g->n) * ((c.g->n + 15) / 16);
-    return (int)std::min<long>(std::min<long>((long)GN_BWD_RPG1_OCC * c.g->num_cu, BWD_NWG), total);
+    const long total = (long)(c.rows / c.g->info.n) * ((c.g->info.n + 15) / 16);
+    return (int)std::min<long>(std::min<long>((long)GN_BWD_RPG1_OCC * c.g->info.num_cu, BWD_NWG), total);
 }
 
 // interval i (y_i -> y_{i-1}) in one launch: over the kept activations, or gathering one or (`two`) both tables
@@ -1342,8 +1342,8 @@ static int backward64_interval(BwdCall& c, const BwdPlan& pl, int i) {
     const Tables64 T = tables64(c);
     const float* keep = pl.keep;
     const long rows = c.rows;
-    const int tps = (g->n + 15) / 16, grid = grid64(c);
-    const long total = (long)(rows / g->n) * tps;
+    const int tps = (g->info.n + 15) / 16, grid = grid64(c);
+    const long total = (long)(rows / g->info.n) * tps;
     const int cur = (c.G - 1 - i) & 1;
     const bool ai_saved = !pl.fwd_tiny;
     // the forward left A Z_I(y_k) in the 4th slab of grid points 1 .. G-2 (A Z_I(y_{G-1}) was never needed by it)
@@ -1352,24 +1352,24 @@ static int backward64_interval(BwdCall& c, const BwdPlan& pl, int i) {
     const float *AIhub = nullptr, *GQhub = nullptr;
     // the discrete sweep over kept activations gathers A Z_I(y_0) for interval 1 from the kept table (nothing left one in ZIb)
     const float* ZIc = (c.exact && keep) ? gn_keep_zi(keep, rows, c.jp(i)) : T.ZIb[cur];
-    const bool kept_launch = keep && !two && rows < (1L << 24) && (long)(rows / g->n) * g->n_seg < (1L << 24);   // 32-bit byte offsets of rows and hub partials
+    const bool kept_launch = keep && !two && rows < (1L << 24) && (long)(rows / g->info.n) * g->n_seg < (1L << 24);   // 32-bit byte offsets of rows and hub partials
     const float* HubP = nullptr;               // kept kernel: segment partials only, it adds them up itself
-    if (two) { if (int e = gn_hub_gather(g, rows / g->n, 64, ZIc, T.Qb[cur], c.hub_scratch, &AIhub, &GQhub, c.st)) return e; }
-    else if (kept_launch) { if (int e = gn_hub_segments(g, rows / g->n, 64, T.Qb[cur], c.hub_scratch, &HubP, c.st)) return e; }
-    else if (int e = gn_hub_gather(g, rows / g->n, 64, T.Qb[cur], nullptr, c.hub_scratch, &GQhub, nullptr, c.st)) return e;
+    if (two) { if (int e = gn_hub_gather(g, rows / g->info.n, 64, ZIc, T.Qb[cur], c.hub_scratch, &AIhub, &GQhub, c.st)) return e; }
+    else if (kept_launch) { if (int e = gn_hub_segments(g, rows / g->info.n, 64, T.Qb[cur], c.hub_scratch, &HubP, c.st)) return e; }
+    else if (int e = gn_hub_gather(g, rows / g->info.n, 64, T.Qb[cur], nullptr, c.hub_scratch, &GQhub, nullptr, c.st)) return e;
     const float* gSs = c.up(c.gS, i - 1);
     const bool sampled = gn_prof_begin(2, c.st);
     if (kept_launch) {
         // the head instance carries 25 more accumulators and the head's temporaries: two workgroups per CU there
         constexpr int HOCC = GN_BWD_KEPT_HEAD_OCC;
-        const bool hubs = g->n_hub > 0;
+        const bool hubs = g->info.n_hub > 0;
         auto kept_kernel = gSs ? (hubs ? k_bwd_kept64<HOCC, true, true> : k_bwd_kept64<HOCC, true, false>)
                                : (hubs ? k_bwd_kept64<GN_BWD_RPG1_OCC, false, true> : k_bwd_kept64<GN_BWD_RPG1_OCC, false, false>);
-        const int kgrid = gSs ? (int)std::min<long>((long)HOCC * g->num_cu, grid) : grid;
+        const int kgrid = gSs ? (int)std::min<long>((long)HOCC * g->info.num_cu, grid) : grid;
         // j: the Jacobian's grid point.  The discrete sweep (j = i-1 >= 1) reads P_S, Z_I and the gW rows there, has the head at
         // the same rows, forms the next q row from Z_S(y_{i-2}) and always leaves one: interval 1 follows on the two-table launch
         const int j = c.jp(i);
-        hipLaunchKernelGGL(kept_kernel, dim3(kgrid), dim3(256), 0, c.st, g->rowhdr, g->col, g->n, rows, tps, total, T.Qb[cur],
+        hipLaunchKernelGGL(kept_kernel, dim3(kgrid), dim3(256), 0, c.st, g->rowhdr, g->col, g->info.n, rows, tps, total, T.Qb[cur],
                            T.Qb[cur ^ 1], c.point(j), c.point(i - 1), gn_keep_ps(keep, rows, j), gn_keep_zi(keep, rows, j),
                            gn_keep_zs(keep, rows, j - 1), p->odefunc_linear_weight, c.beta, c.gamma, c.dt_host[i - 1], c.a, c.part,
                            gSs, c.up(c.gI, i - 1), c.up(c.gR, i - 1), p->linear3_weight, p->linear3_bias, p->linearS2_weight,
@@ -1382,11 +1382,11 @@ static int backward64_interval(BwdCall& c, const BwdPlan& pl, int i) {
                                             : (two ? k_bwd_fused64<O, 1, true> : k_bwd_fused64<O, 1, false>));
         // the next interval gathers A Z_I itself when its grid point's 4th slab does not carry it
         float* ZIn = c.exact ? (two_at(i - 1) ? T.ZIb[cur ^ 1] : nullptr) : (ai_saved ? nullptr : T.ZIb[cur ^ 1]);
-        hipLaunchKernelGGL(fused_kernel, dim3(grid), dim3(256), 0, c.st, g->rowptr, g->col, g->n, rows, tps, total, ZIc,
+        hipLaunchKernelGGL(fused_kernel, dim3(grid), dim3(256), 0, c.st, g->rowptr, g->col, g->info.n, rows, tps, total, ZIc,
                            T.Qb[cur], ZIn, T.Qb[cur ^ 1], c.point(c.jp(i)), c.before(i),
                            p->odefunc_linear_weight, p->odefunc_linear_bias, c.beta, c.gamma, c.dt_host[i - 1], c.a, c.part, gSs,
                            c.up(c.gI, i - 1), c.up(c.gR, i - 1), p->linear3_weight, p->linear3_bias, p->linearS2_weight,
-                           p->linearS2_bias, g->hubidx, AIhub, GQhub, g->n_hub, i > 1 ? 1 : 0, c.point(c.jp(i)) + 3 * c.slab, c.gx);
+                           p->linearS2_bias, g->hubidx, AIhub, GQhub, g->info.n_hub, i > 1 ? 1 : 0, c.point(c.jp(i)) + 3 * c.slab, c.gx);
     }
     if (sampled) gn_prof_end(2, c.st);
     GN_LAUNCH_CHECK();
@@ -1501,11 +1501,11 @@ static int backward_small_h(BwdCall& c, const BwdPlan& pl) {
     for (int i = G - 1; i >= 1; --i) {
         const int cur = (G - 1 - i) & 1;
         const float *HubP0 = nullptr, *HubP1 = nullptr;        // segment partials; the interval kernel adds them up itself
-        if (int e = gn_hub_segments2(g, rows / g->n, H, ZIb[cur], Qb[cur], c.hub_scratch, &HubP0, &HubP1, c.st)) return e;
+        if (int e = gn_hub_segments2(g, rows / g->info.n, H, ZIb[cur], Qb[cur], c.hub_scratch, &HubP0, &HubP1, c.st)) return e;
         const bool sampled = gn_prof_begin(2, c.st);
 #define GN_FUSED_GENERIC(BG, EX)                                                                                                    \
         GN_LPR_DISPATCH(32, lpr, hipLaunchKernelGGL((k_bwd_fused_generic<LPR, BG, EX>), dim3(grid), dim3(256), fl * sizeof(float), c.st, \
-                                                    g->rowptr, g->col, g->n, rows, H, c.Z, ZIb[cur], Qb[cur], ZIb[cur ^ 1], Qb[cur ^ 1], \
+                                                    g->rowptr, g->col, g->info.n, rows, H, c.Z, ZIb[cur], Qb[cur], ZIb[cur ^ 1], Qb[cur ^ 1], \
                                                     c.point(c.jp(i)), c.before(i), p->odefunc_linear_weight, p->odefunc_linear_bias,    \
                                                     c.beta, c.gamma, c.dt_host[i - 1], c.a, c.part, c.up(c.gS, i - 1),                 \
                                                     c.up(c.gI, i - 1), c.up(c.gR, i - 1), p->linear3_weight, p->linear3_bias,          \
@@ -1538,16 +1538,16 @@ static int backward_generic(BwdCall& c) {
         if (int e = gn_launch_mlp_any(g, yi, p->odefunc_linear_weight, p->odefunc_linear_bias, c.Z, 2 * rows, H, c.st)) return e;
         hipLaunchKernelGGL(k_bwd_q, dim3(2048), dim3(256), 0, c.st, c.a, c.Z, c.beta, c.q, rows, H);
         GN_LAUNCH_CHECK();
-        dim3 ggrid((unsigned)((g->n + rpw - 1) / rpw), (unsigned)(rows / g->n));
+        dim3 ggrid((unsigned)((g->info.n + rpw - 1) / rpw), (unsigned)(rows / g->info.n));
         const float *AIhub = nullptr, *GQhub = nullptr;
-        if (int e = gn_hub_gather(g, rows / g->n, H, c.Z + c.slab, c.q, c.hub_scratch, &AIhub, &GQhub, c.st)) return e;
+        if (int e = gn_hub_gather(g, rows / g->info.n, H, c.Z + c.slab, c.q, c.hub_scratch, &AIhub, &GQhub, c.st)) return e;
         if (c.gx)
-            GN_LPR_DISPATCH(32, lpr, hipLaunchKernelGGL((k_bwd_gather<LPR, true>), ggrid, dim3(256), 0, c.st, g->rowptr, g->col, g->n, rows,
-                                                        H, c.a, c.Z, c.q, c.beta, c.gamma, c.dpre, g->hubidx, AIhub, GQhub, g->n_hub,
+            GN_LPR_DISPATCH(32, lpr, hipLaunchKernelGGL((k_bwd_gather<LPR, true>), ggrid, dim3(256), 0, c.st, g->rowptr, g->col, g->info.n, rows,
+                                                        H, c.a, c.Z, c.q, c.beta, c.gamma, c.dpre, g->hubidx, AIhub, GQhub, g->info.n_hub,
                                                         c.gx, dt))
         else
-            GN_LPR_DISPATCH(32, lpr, hipLaunchKernelGGL((k_bwd_gather<LPR, false>), ggrid, dim3(256), 0, c.st, g->rowptr, g->col, g->n, rows,
-                                                        H, c.a, c.Z, c.q, c.beta, c.gamma, c.dpre, g->hubidx, AIhub, GQhub, g->n_hub,
+            GN_LPR_DISPATCH(32, lpr, hipLaunchKernelGGL((k_bwd_gather<LPR, false>), ggrid, dim3(256), 0, c.st, g->rowptr, g->col, g->info.n, rows,
+                                                        H, c.a, c.Z, c.q, c.beta, c.gamma, c.dpre, g->hubidx, AIhub, GQhub, g->info.n_hub,
                                                         nullptr, 0.f))
         GN_LAUNCH_CHECK();
         if (H == 128) {
@@ -1576,8 +1576,8 @@ static int backward_euler(gnode_graph_t g, const float* x, const gnode_params* p
     GN_CHECK_ARG(!gx || p->linearS1_weight, "gnode_backward_dx_f32: null linearS1.weight");
     GN_CHECK_ARG(n_steps >= 0 && (n_steps == 0 || dt_host), "gnode_backward_f32: bad n_steps/dt");
     GN_CHECK_ARG(H >= 4 && H <= 128 && H % 4 == 0, "gnode_backward_f32: need 4 <= H <= 128, H %% 4 == 0 (got %d)", H);
-    GN_CHECK_ARG(rows > 0 && rows % g->n == 0, "gnode_backward_f32: rows=%lld is not a multiple of graph n=%d",
-                 (long long)rows, g->n);
+    GN_CHECK_ARG(rows > 0 && rows % g->info.n == 0, "gnode_backward_f32: rows=%lld is not a multiple of graph n=%d",
+                 (long long)rows, g->info.n);
     GN_CHECK_ARG(!grads || (grads->odefunc_linear_weight && grads->odefunc_linear_bias && grads->linearS1_weight &&
                      grads->linearS1_bias && grads->linear3_weight && grads->linear3_bias && grads->linearS2_weight &&
                      grads->linearS2_bias), "gnode_backward_f32: null gradient pointer");
@@ -1659,7 +1659,7 @@ extern "C" int gnode_backward_discrete_keep_f32(gnode_graph_t g, const float* x,
 
 extern "C" int gnode_backward_discrete_path(gnode_graph_t g, int64_t rows, int32_t H, int32_t n_steps, const int32_t* out_rows_host,
                                             int32_t n_out, int32_t with_keep, int32_t flags, int32_t sol_info, int32_t with_gx) {
-    if (!g || rows <= 0 || rows % g->n || n_steps < 0 || H < 4 || H > 128 || H % 4) return -1;
+    if (!g || rows <= 0 || rows % g->info.n || n_steps < 0 || H < 4 || H > 128 || H % 4) return -1;
     const int G = n_steps + 1;
     if (gn_check_out_rows("gnode_backward_discrete_path", out_rows_host, n_out, G)) return -1;
     const std::vector<int> slot = gn_out_slots(out_rows_host, n_out, G);

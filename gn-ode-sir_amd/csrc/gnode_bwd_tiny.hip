@@ -328,8 +328,8 @@ static size_t tiny_bwd_lds_bytes(int n) {
 #endif
 bool gn_tiny_bwd64_ok(const gnode_graph_s* g, long rows, int H, int n_steps) {
     if (!GN_TINY_TRAIN) return false;
-    return H == 64 && g->n <= 2 * TILE_ROWS && n_steps >= 0 && n_steps <= 128 && rows / g->n <= BWD_NWG &&
-           tiny_bwd_lds_bytes(g->n) <= 160 * 1024;
+    return H == 64 && g->info.n <= 2 * TILE_ROWS && n_steps >= 0 && n_steps <= 128 && rows / g->info.n <= BWD_NWG &&
+           tiny_bwd_lds_bytes(g->info.n) <= 160 * 1024;
 }
 
 int gn_bwd_tiny_set_attributes() {      // once per device, from gnode_graph_create
@@ -349,10 +349,10 @@ int gn_launch_tiny_bwd64(const gnode_graph_s* g, long rows, const float* x, cons
         GN_CHECK_ARG(n_out < 32768, "gnode_backward_f32: too many output rows (%d)", n_out);
         for (int i = 0; i < n_out; ++i) sched.slot[out_rows_host[i]] = (short)i;
     }
-    const unsigned B = (unsigned)(rows / g->n);
-    const unsigned threads = 256u * (unsigned)((g->n + TILE_ROWS - 1) / TILE_ROWS);
+    const unsigned B = (unsigned)(rows / g->info.n);
+    const unsigned threads = 256u * (unsigned)((g->info.n + TILE_ROWS - 1) / TILE_ROWS);
     auto kern = keep ? k_tiny_bwd64<true> : k_tiny_bwd64<false>;
-    hipLaunchKernelGGL(kern, dim3(B), dim3(threads), tiny_bwd_lds_bytes(g->n), st, g->rowptr, g->col, g->n, rows, sol, x,
+    hipLaunchKernelGGL(kern, dim3(B), dim3(threads), tiny_bwd_lds_bytes(g->info.n), st, g->rowptr, g->col, g->info.n, rows, sol, x,
                        gS, gI, gR, p->odefunc_linear_weight, p->odefunc_linear_bias, p->linear3_weight, p->linear3_bias,
                        p->linearS2_weight, p->linearS2_bias, sched, part, keep);
     GN_LAUNCH_CHECK();

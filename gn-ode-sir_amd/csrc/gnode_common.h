@@ -6,55 +6,24 @@
 #include <cstdint>
 #include <vector>
 #include "gnode.h"
+#include "gnode_graph_plan.h"
 
+// The device copy of a graph's plan (gnode_graph_plan.h defines and documents every array; gnode_graph_create uploads them).
 struct gnode_graph_s {
-    int32_t n;
+    GnGraphInfo info;   // n, num_cu, n_hub and the other host scalars the per-call planners read
     int64_t nnz;
-    int32_t max_degree;
-    int32_t n_bigrow; // rows longer than GN_SIR_BIGROW (the Monte-Carlo kernel walks those with the whole workgroup; their list's capacity)
-    int32_t device;   // the HIP device the CSR lives on (current device at gnode_graph_create)
-    int32_t num_cu;   // its compute-unit count: persistent grids are sized from the handle, not from process globals
-    int32_t* rowptr;  // device [n+1]
-    int32_t* rowhdr;  // device [n][20]: {start, end, 0, 0, first 16 column ids (0-padded)} -- the H = 64 step kernel gets a
-                      // row's extent AND its first 16 neighbour ids in ONE round trip instead of two dependent ones
-    int32_t* col;     // device [nnz]
-    // hub rows (gnode_hub.hip): rows longer than the hub threshold, cut into <= 32-edge segments
-    int32_t n_hub, n_seg;
-    int32_t* hubidx;        // device [n]: hub index of a row, -1 for ordinary rows (null when n_hub == 0)
-    int32_t* seg_lo;        // device [n_seg]: first CSR position of a segment
-    int32_t* seg_hi;        // device [n_seg]: one past its last
-    int32_t* hub_seg_ptr;   // device [n_hub+1]: segments of hub h are [ptr[h], ptr[h+1])
-    // persistent one-launch integration (gnode_pers64.hip): for 1 / 2 / 4 tiles per workgroup the node each lane-group slot
-    // owns, -1 for padding slots; null when the graph never takes that path
-    int32_t* persmap[3];
-    // ... and its hub rows (graphs with rows longer than GN_HUB_T): per lane-group slot {first partial slot in the workgroup's
-    // LDS, segments} of the hub row it owns (-1, 0 otherwise); per lane-group slot {first item, items} of the segment sums it
-    // computes each step; the items {first CSR position, one past the last, partial slot, 0}; partial slots per workgroup
-    int32_t* pershub[3];
-    int32_t* perssegptr[3];
-    int32_t* perssegitem[3];
+    int32_t max_degree, n_bigrow, n_seg;
+    int32_t device;     // the HIP device the arrays live on (current device at gnode_graph_create)
+    int32_t* rowptr;    // [n+1]
+    int32_t* col;       // [nnz]
+    int32_t* rowhdr;
+    int32_t *hubidx, *seg_lo, *seg_hi, *hub_seg_ptr;     // null when n_hub == 0
+    int32_t *persmap[3], *pershub[3], *perssegptr[3], *perssegitem[3];   // GnPers64Maps, null for an absent variant
     int32_t perslds[3];
-    int32_t persitems[3];
-    // small hidden sizes (gnode_persg.hip; H = 8 / 16 / 32 x workgroups of 1 .. 4 waves): lane-group slot -> node (-1 padding),
-    // hub rows dealt round-robin, all variants in one allocation at pgoff[][] (-1: variant absent); per variant the most
-    // neighbour ids of ordinary rows and the most hub segments one workgroup has to stage in LDS
-    int32_t* pgmap;
-    int32_t pgoff[3][4], pgids[3][4], pgsegs[3][4];
+    int32_t* pgmap;     // null when no k_persg variant exists
+    std::vector<void*> owned;   // every device allocation of the handle: the pointers above point into these
 };
 
-#ifndef GN_SIR_BIGROW
-#define GN_SIR_BIGROW 512     // Monte-Carlo frontier kernel: rows longer than this are walked by the whole workgroup
-#endif
-#define HUB_SEG 32           // a hub row's neighbour list is cut into segments of this many edges
-#ifndef GN_HUB_T
-#define GN_HUB_T 96          // rows longer than this are hubs (measured break-even against the two extra launches per step)
-#endif
-int gn_hub_build(gnode_graph_s* g, const int32_t* rowptr_host);
-int gn_pers64_build(gnode_graph_s* g, const int32_t* rowptr_host);     // the row maps above (gnode_pers64.hip)
-void gn_pers64_free(gnode_graph_s* g);
-int gn_persg_build(gnode_graph_s* g, const int32_t* rowptr_host);      // row maps above (gnode_persg.hip)
-void gn_persg_free(gnode_graph_s* g);
-void gn_hub_free(gnode_graph_s* g);
 // Hub sums of `ntables` (1 or 2) tables for a batch of B samples need this much of the CALLER's workspace (0 for a graph
 // without hub rows); gn_hub_gather carves its segment partials and hub sums from it: no allocation, no
 // synchronisation, nothing retained in the handle.

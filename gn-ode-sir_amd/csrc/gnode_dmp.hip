@@ -89,7 +89,7 @@ __global__ __launch_bounds__(256) void k_dmp_out0(const float* __restrict__ seed
 
 extern "C" size_t gnode_dmp_workspace_bytes(gnode_graph_t g) {
     if (!g) return 0;
-    const size_t eb = gn_align((size_t)std::max<int64_t>(g->nnz, 1) * 4), nb = gn_align((size_t)g->n * 4);
+    const size_t eb = gn_align((size_t)std::max<int64_t>(g->nnz, 1) * 4), nb = gn_align((size_t)g->info.n * 4);
     return 6 * eb + 4 * nb + 256;          // src, rev, theta x2, phi, ps | seed, P, Pr, Pi | status
 }
 
@@ -99,14 +99,14 @@ extern "C" int gnode_dmp_f32(gnode_graph_t g, const float* weights, const float*
     GN_CHECK_ARG(g && weights && gamma && out && workspace && (seeds_host || n_seeds == 0), "gnode_dmp_f32: null pointer");
     GN_CHECK_ARG(maxTime >= 2, "gnode_dmp_f32: maxTime must be >= 2 (got %d)", maxTime);
     for (int i = 0; i < n_seeds; ++i)
-        GN_CHECK_ARG(seeds_host[i] >= 0 && seeds_host[i] < g->n, "gnode_dmp_f32: seed %d out of range", seeds_host[i]);
+        GN_CHECK_ARG(seeds_host[i] >= 0 && seeds_host[i] < g->info.n, "gnode_dmp_f32: seed %d out of range", seeds_host[i]);
     if (workspace_bytes < gnode_dmp_workspace_bytes(g)) {
         gnode_set_error("gnode_dmp_f32: workspace %zu < %zu", workspace_bytes, gnode_dmp_workspace_bytes(g));
         return GNODE_ERR_WORKSPACE;
     }
     hipStream_t st = (hipStream_t)stream;
     const long nnz = g->nnz;
-    const int n = g->n;
+    const int n = g->info.n;
     const size_t eb = gn_align((size_t)std::max<int64_t>(nnz, 1) * 4), nb = gn_align((size_t)n * 4);
     char* ws = (char*)workspace;
     int* src = (int*)ws; int* rev = (int*)(ws + eb);

@@ -84,7 +84,7 @@ int gn_h128_set_attributes();   // defined below both kernels
 int gn_launch_mlp128(const gnode_graph_s* g, const float* X, const float* W, const float* b, float* Z, long nrows, hipStream_t st) {
     const size_t lds = kMlp128Lds;
     const long ntiles = (nrows + 15) / 16;
-    hipLaunchKernelGGL(k_mlp128, dim3((unsigned)std::min<long>(ntiles, 2L * g->num_cu)), dim3(256), lds, st, X, W, b, Z, nrows);
+    hipLaunchKernelGGL(k_mlp128, dim3((unsigned)std::min<long>(ntiles, 2L * g->info.num_cu)), dim3(256), lds, st, X, W, b, Z, nrows);
     GN_LAUNCH_CHECK();
     return 0;
 }
@@ -199,7 +199,7 @@ int gn_launch_bwd_mlp128(const gnode_graph_s* g, const float* dpre, const float*
                          float* part, int* slots_used, hipStream_t st) {
     const size_t lds = kBwdMlp128Lds;
     const long ntiles = (rows + 15) / 16;
-    const int grid = (int)std::min<long>(std::min<long>(ntiles, g->num_cu), BWD_NWG);     // one slot of the partial buffer per workgroup
+    const int grid = (int)std::min<long>(std::min<long>(ntiles, g->info.num_cu), BWD_NWG);     // one slot of the partial buffer per workgroup
     *slots_used = std::max(*slots_used, grid);
     hipLaunchKernelGGL(k_bwd_mlp128, dim3(grid), dim3(512), lds, st, dpre, Ysol, W, dt, a, rows, part);
     GN_LAUNCH_CHECK();

@@ -574,14 +574,14 @@ int gn_launch_tiny64(const gnode_graph_s* g, long rows, const float* Y0, const f
     sched.n_steps = n_steps;
     for (int k = 0; k < n_steps; ++k) { sched.dt[k] = dt_host[k]; sched.slot[k] = (short)slot_host[k]; }
     const bool prj = PR0 != nullptr;
-    const size_t lds = gn_tiny64_lds_bytes(g->n, prj);
-    const unsigned B = (unsigned)(rows / g->n);
-    const unsigned threads = 256u * (unsigned)((g->n + TILE_ROWS - 1) / TILE_ROWS);
+    const size_t lds = gn_tiny64_lds_bytes(g->info.n, prj);
+    const unsigned B = (unsigned)(rows / g->info.n);
+    const unsigned threads = 256u * (unsigned)((g->info.n + TILE_ROWS - 1) / TILE_ROWS);
     if (prj) {
-        hipLaunchKernelGGL(k_tiny64<true>, dim3(B), dim3(threads), lds, st, g->rowptr, g->col, g->n, rows, Y0, ZI0, PR0, W, bias, beta,
+        hipLaunchKernelGGL(k_tiny64<true>, dim3(B), dim3(threads), lds, st, g->rowptr, g->col, g->info.n, rows, Y0, ZI0, PR0, W, bias, beta,
                            gamma, sched, p->linear3_weight, p->linear3_bias, p->linearS2_weight, p->linearS2_bias, S, I, R, sol, keep);
     } else {
-        hipLaunchKernelGGL(k_tiny64<false>, dim3(B), dim3(threads), lds, st, g->rowptr, g->col, g->n, rows, Y0, ZI0, PR0, W, bias, beta,
+        hipLaunchKernelGGL(k_tiny64<false>, dim3(B), dim3(threads), lds, st, g->rowptr, g->col, g->info.n, rows, Y0, ZI0, PR0, W, bias, beta,
                            gamma, sched, p->linear3_weight, p->linear3_bias, p->linearS2_weight, p->linearS2_bias, S, I, R, sol, keep);
     }
     GN_LAUNCH_CHECK();
@@ -691,7 +691,7 @@ int gn_h64_set_attributes() {
 int gn_launch_mlp64(const gnode_graph_s* g, const float* X, const float* W, const float* b, float* Z, long nrows, hipStream_t st) {
     if (nrows <= 0) return 0;
     const long ntiles = (nrows + TILE_ROWS - 1) / TILE_ROWS;
-    const int grid = (int)std::min<long>(ntiles, (long)g->num_cu * 4);
+    const int grid = (int)std::min<long>(ntiles, (long)g->info.num_cu * 4);
     hipLaunchKernelGGL(k_mlp64, dim3(grid), dim3(256), 0, st, X, W, b, Z, nrows);
     GN_LAUNCH_CHECK();
     return 0;
@@ -703,21 +703,21 @@ int gn_launch_step64(gnode_graph_s* g, long rows, float* Y, const float* ZI, flo
     GN_CHECK_ARG(rows < (1L << 24), "H=64 step kernel addresses rows with 32-bit byte offsets: rows=%ld >= 2^24 per launch "
                  "(split the batch)", rows);
     // (the hub segment partials are addressed the same way: (sample * n_seg + segment) * 256 bytes)
-    GN_CHECK_ARG((long)(rows / g->n) * g->n_seg < (1L << 24), "H=64 step kernel addresses hub segment partials with 32-bit byte offsets: "
-                 "%ld samples x %d segments >= 2^24 per launch (split the batch)", (long)(rows / g->n), g->n_seg);
-    const int tps = (g->n + 15) / 16;
-    const long total = (long)(rows / g->n) * tps;
+    GN_CHECK_ARG((long)(rows / g->info.n) * g->n_seg < (1L << 24), "H=64 step kernel addresses hub segment partials with 32-bit byte offsets: "
+                 "%ld samples x %d segments >= 2^24 per launch (split the batch)", (long)(rows / g->info.n), g->n_seg);
+    const int tps = (g->info.n + 15) / 16;
+    const long total = (long)(rows / g->info.n) * tps;
     const float* HubP = nullptr;               // per-segment partial sums of the hub rows; the step kernel adds them up itself
-    if (int e = gn_hub_segments(g, rows / g->n, 64, ZI, hub_scratch, &HubP, st)) return e;
+    if (int e = gn_hub_segments(g, rows / g->info.n, 64, ZI, hub_scratch, &HubP, st)) return e;
     // persistent grid: GN_STEP_OCC workgroups per CU (measured: 3 / 4 / 5 per CU -> 363 / 360 / 400 us per launch on the
     // 75k graph x 8; shrinking the grid so that every workgroup gets the same number of tiles is slower than filling
     // every slot and accepting a +-1 tile imbalance)
-    const int grid = (int)std::min<long>(total, (long)g->num_cu * (PR ? StepOcc<true>::value : StepOcc<false>::value));
+    const int grid = (int)std::min<long>(total, (long)g->info.num_cu * (PR ? StepOcc<true>::value : StepOcc<false>::value));
     const bool lat = total <= grid;            // one tile per workgroup: the latency-mode instantiation
-#define GN_STEP1(P, L, HB) hipLaunchKernelGGL((k_step64<P, L, HB>), dim3(grid), dim3(256), 0, st, g->rowhdr, g->col, g->n, rows, tps, total, Y, ZI, \
+#define GN_STEP1(P, L, HB) hipLaunchKernelGGL((k_step64<P, L, HB>), dim3(grid), dim3(256), 0, st, g->rowhdr, g->col, g->info.n, rows, tps, total, Y, ZI, \
                                          ZI_next, W, bias, beta, gamma, dt, p->linear3_weight, p->linear3_bias, p->linearS2_weight,     \
                                          p->linearS2_bias, PR, out, g->hubidx, HubP, g->hub_seg_ptr, g->n_seg)
-#define GN_STEP(P, L) { if (g->n_hub > 0) GN_STEP1(P, L, true); else GN_STEP1(P, L, false); }
+#define GN_STEP(P, L) { if (g->info.n_hub > 0) GN_STEP1(P, L, true); else GN_STEP1(P, L, false); }
     if (PR) { if (lat) GN_STEP(true, true) else GN_STEP(true, false) }
     else { if (lat) GN_STEP(false, true) else GN_STEP(false, false) }
 #undef GN_STEP

@@ -31,7 +31,7 @@
 #include <algorithm>
 #include <vector>
 
-// HUB_SEG, GN_HUB_T: gnode_common.h (the persistent kernels cut the same segments)
+// HUB_SEG, GN_HUB_T: gnode_graph_plan.h (the persistent kernels cut the same segments)
 
 __device__ __forceinline__ float4 hld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 __device__ __forceinline__ void hst4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
@@ -159,47 +159,10 @@ __global__ __launch_bounds__(256) void k_hub_reduce(const int* __restrict__ hub_
     if (p1) hst4(A1 + o, a1);
 }
 
-// --------------------------------------------------------------------------- host: build + launch
-int gn_hub_build(gnode_graph_s* g, const int32_t* rowptr_host) {
-    const int T = GN_HUB_T;
-    std::vector<int32_t> hubidx((size_t)g->n, -1), seg_lo, seg_hi, hub_seg_ptr(1, 0);
-    int n_hub = 0;
-    for (int32_t r = 0; r < g->n; ++r) {
-        const int32_t lo = rowptr_host[r], hi = rowptr_host[r + 1];
-        if (hi - lo <= T) continue;
-        hubidx[r] = n_hub++;
-        for (int32_t e = lo; e < hi; e += HUB_SEG) {
-            seg_lo.push_back(e);
-            seg_hi.push_back(std::min(hi, e + HUB_SEG));
-        }
-        hub_seg_ptr.push_back((int32_t)seg_lo.size());
-    }
-    g->n_hub = n_hub;
-    g->n_seg = (int32_t)seg_lo.size();
-    g->hubidx = g->seg_lo = g->seg_hi = g->hub_seg_ptr = nullptr;
-    if (n_hub == 0) return 0;
-    auto up = [](int32_t** dst, const std::vector<int32_t>& v) -> hipError_t {
-        hipError_t e = hipMalloc(dst, sizeof(int32_t) * v.size());
-        if (e != hipSuccess) return e;
-        return hipMemcpy(*dst, v.data(), sizeof(int32_t) * v.size(), hipMemcpyHostToDevice);
-    };
-    GN_HIP(up(&g->hubidx, hubidx));
-    GN_HIP(up(&g->seg_lo, seg_lo));
-    GN_HIP(up(&g->seg_hi, seg_hi));
-    GN_HIP(up(&g->hub_seg_ptr, hub_seg_ptr));
-    return 0;
-}
-
-void gn_hub_free(gnode_graph_s* g) {
-    if (g->hubidx) (void)hipFree(g->hubidx);
-    if (g->seg_lo) (void)hipFree(g->seg_lo);
-    if (g->seg_hi) (void)hipFree(g->seg_hi);
-    if (g->hub_seg_ptr) (void)hipFree(g->hub_seg_ptr);
-}
-
+// --------------------------------------------------------------------------- host: launch (the segment lists: gnode_graph_plan.cpp)
 size_t gn_hub_scratch_bytes(const gnode_graph_s* g, long B, int H, int ntables) {
-    if (g->n_hub == 0) return 0;
-    const size_t part_f = (size_t)B * g->n_seg * H, hub_f = (size_t)B * g->n_hub * H;
+    if (g->info.n_hub == 0) return 0;
+    const size_t part_f = (size_t)B * g->n_seg * H, hub_f = (size_t)B * g->info.n_hub * H;
     return (size_t)ntables * (gn_align(sizeof(float) * part_f) + gn_align(sizeof(float) * hub_f));
 }
 
@@ -214,7 +177,7 @@ int gn_hub_segments2(const gnode_graph_s* g, long B, int H, const float* T0, con
                      const float** P1out, hipStream_t st) {
     *P0out = nullptr;
     if (P1out) *P1out = nullptr;
-    if (g->n_hub == 0) return 0;
+    if (g->info.n_hub == 0) return 0;
     GN_CHECK_ARG(scratch, "hub rows present but no hub scratch was carved from the workspace");
     const size_t part_b = gn_align(sizeof(float) * (size_t)B * g->n_seg * H);
     float* P0 = (float*)scratch;
@@ -223,7 +186,7 @@ int gn_hub_segments2(const gnode_graph_s* g, long B, int H, const float* T0, con
     for (long b0 = 0; b0 < B; b0 += 65535) {
         const unsigned nb = (unsigned)std::min<long>(65535, B - b0);
         GN_LPR_DISPATCH(64, lpr, hipLaunchKernelGGL(k_hub_seg<LPR>, dim3((unsigned)((g->n_seg + gpw - 1) / gpw), nb), dim3(256), 0, st,
-                                                    g->seg_lo, g->seg_hi, g->col, g->n, g->n_seg, H, T0, T1, P0, P1, b0));
+                                                    g->seg_lo, g->seg_hi, g->col, g->info.n, g->n_seg, H, T0, T1, P0, P1, b0));
     }
     GN_LAUNCH_CHECK();
     *P0out = P0;
@@ -237,10 +200,10 @@ int gn_hub_gather(const gnode_graph_s* g, long B, int H, const float* T0, const 
                   const float** A1, hipStream_t st) {
     *A0 = nullptr;
     if (A1) *A1 = nullptr;
-    if (g->n_hub == 0) return 0;
+    if (g->info.n_hub == 0) return 0;
     GN_CHECK_ARG(scratch, "hub rows present but no hub scratch was carved from the workspace");
     const int nt = T1 ? 2 : 1;
-    const size_t part_b = gn_align(sizeof(float) * (size_t)B * g->n_seg * H), hub_b = gn_align(sizeof(float) * (size_t)B * g->n_hub * H);
+    const size_t part_b = gn_align(sizeof(float) * (size_t)B * g->n_seg * H), hub_b = gn_align(sizeof(float) * (size_t)B * g->info.n_hub * H);
     char* base = (char*)scratch;
     float* P0 = (float*)base;
     float* a0 = (float*)(base + part_b);
@@ -249,10 +212,10 @@ int gn_hub_gather(const gnode_graph_s* g, long B, int H, const float* T0, const 
     const int lpr = gn_lpr(H), gpw = 256 / lpr;
     GN_CHECK_ARG(B <= 65535, "hub sums: %ld samples per launch exceed the grid's y extent (split the batch)", B);
     GN_LPR_DISPATCH(64, lpr, hipLaunchKernelGGL(k_hub_seg<LPR>, dim3((unsigned)((g->n_seg + gpw - 1) / gpw), (unsigned)B), dim3(256), 0, st,
-                                                g->seg_lo, g->seg_hi, g->col, g->n, g->n_seg, H, T0, T1, P0, P1, 0L));
+                                                g->seg_lo, g->seg_hi, g->col, g->info.n, g->n_seg, H, T0, T1, P0, P1, 0L));
     GN_LAUNCH_CHECK();
-    GN_LPR_DISPATCH(64, lpr, hipLaunchKernelGGL(k_hub_reduce<LPR>, dim3((unsigned)((g->n_hub + gpw - 1) / gpw), (unsigned)B), dim3(256), 0,
-                                                st, g->hub_seg_ptr, g->n_hub, g->n_seg, H, P0, nt == 2 ? P1 : nullptr, a0, a1));
+    GN_LPR_DISPATCH(64, lpr, hipLaunchKernelGGL(k_hub_reduce<LPR>, dim3((unsigned)((g->info.n_hub + gpw - 1) / gpw), (unsigned)B), dim3(256), 0,
+                                                st, g->hub_seg_ptr, g->info.n_hub, g->n_seg, H, P0, nt == 2 ? P1 : nullptr, a0, a1));
     GN_LAUNCH_CHECK();
     *A0 = a0;
     if (A1) *A1 = nt == 2 ? a1 : nullptr;

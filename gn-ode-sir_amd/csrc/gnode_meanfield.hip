@@ -73,8 +73,8 @@ __global__ __launch_bounds__(256) void k_mf_emit(const double* __restrict__ y, i
 
 extern "C" size_t gnode_meanfield_workspace_bytes(gnode_graph_t g) {
     if (!g) return 0;
-    const size_t v = gn_align((size_t)3 * g->n * sizeof(double));
-    return 10 * v + gn_align((size_t)g->n * sizeof(double)) + 256;      // y, ynew, ytmp, K[7] | seed | err
+    const size_t v = gn_align((size_t)3 * g->info.n * sizeof(double));
+    return 10 * v + gn_align((size_t)g->info.n * sizeof(double)) + 256;      // y, ynew, ytmp, K[7] | seed | err
 }
 
 extern "C" int gnode_meanfield_f64(gnode_graph_t g, const int32_t* seeds_host, int32_t n_seeds, double beta,
@@ -87,13 +87,13 @@ extern "C" int gnode_meanfield_f64(gnode_graph_t g, const int32_t* seeds_host, i
         GN_CHECK_ARG(t_out_host[i] >= t_out_host[i - 1], "gnode_meanfield_f64: output times must be ascending");
     GN_CHECK_ARG(rtol > 0 && atol > 0, "gnode_meanfield_f64: tolerances must be positive");
     for (int i = 0; i < n_seeds; ++i)
-        GN_CHECK_ARG(seeds_host[i] >= 0 && seeds_host[i] < g->n, "gnode_meanfield_f64: seed %d out of range", seeds_host[i]);
+        GN_CHECK_ARG(seeds_host[i] >= 0 && seeds_host[i] < g->info.n, "gnode_meanfield_f64: seed %d out of range", seeds_host[i]);
     if (workspace_bytes < gnode_meanfield_workspace_bytes(g)) {
         gnode_set_error("gnode_meanfield_f64: workspace %zu < %zu", workspace_bytes, gnode_meanfield_workspace_bytes(g));
         return GNODE_ERR_WORKSPACE;
     }
     hipStream_t st = (hipStream_t)stream;
-    const int n = g->n;
+    const int n = g->info.n;
     const long len = 3L * n;
     const size_t v = gn_align((size_t)len * sizeof(double));
     char* ws = (char*)workspace;

@@ -484,19 +484,19 @@ static int launch_gather(gnode_graph_t g, int mode, long rows, int H, float* Y, 
                          const float* gamma, int bg_stride, float dt, float* dY, const gnode_params* p, StepOut out,
                          void* hub_scratch, hipStream_t st) {
     const int lpr = gn_lpr(H), rpw = 256 / lpr;
-    const long B = rows / g->n;
-    dim3 grid((unsigned)((g->n + rpw - 1) / rpw), (unsigned)B);
+    const long B = rows / g->info.n;
+    dim3 grid((unsigned)((g->info.n + rpw - 1) / rpw), (unsigned)B);
     const float *w3 = p ? p->linear3_weight : nullptr, *b3 = p ? p->linear3_bias : nullptr;
     const float *w2 = p ? p->linearS2_weight : nullptr, *b2 = p ? p->linearS2_bias : nullptr;
     const float* AIhub = nullptr;
     if (int e = gn_hub_gather(g, B, H, Z + (size_t)rows * H, nullptr, hub_scratch, &AIhub, nullptr, st)) return e;
     const bool sampled = mode == 1 && prof_begin(0, st);
     if (mode == 0) {
-        GN_LPR_DISPATCH(64, lpr, hipLaunchKernelGGL((k_gather<LPR, 0>), grid, dim3(256), 0, st, g->rowptr, g->col, g->n, rows, H,
-                                                    Y, Z, beta, gamma, bg_stride, dt, dY, w3, b3, w2, b2, out, g->hubidx, AIhub, g->n_hub));
+        GN_LPR_DISPATCH(64, lpr, hipLaunchKernelGGL((k_gather<LPR, 0>), grid, dim3(256), 0, st, g->rowptr, g->col, g->info.n, rows, H,
+                                                    Y, Z, beta, gamma, bg_stride, dt, dY, w3, b3, w2, b2, out, g->hubidx, AIhub, g->info.n_hub));
     } else {
-        GN_LPR_DISPATCH(64, lpr, hipLaunchKernelGGL((k_gather<LPR, 1>), grid, dim3(256), 0, st, g->rowptr, g->col, g->n, rows, H,
-                                                    Y, Z, beta, gamma, bg_stride, dt, dY, w3, b3, w2, b2, out, g->hubidx, AIhub, g->n_hub));
+        GN_LPR_DISPATCH(64, lpr, hipLaunchKernelGGL((k_gather<LPR, 1>), grid, dim3(256), 0, st, g->rowptr, g->col, g->info.n, rows, H,
+                                                    Y, Z, beta, gamma, bg_stride, dt, dY, w3, b3, w2, b2, out, g->hubidx, AIhub, g->info.n_hub));
     }
     if (sampled) prof_mark(0, st);
     GN_LAUNCH_CHECK();
@@ -542,99 +542,78 @@ int gn_device_setup_once(int dev) {
     return 0;
 }
 
+// One device allocation of the handle (at least min_words words), filled with `v` and recorded in g->owned.
+static hipError_t graph_upload(gnode_graph_s* g, int32_t** dst, const int32_t* v, size_t words, size_t min_words = 0) {
+    void* p = nullptr;
+    hipError_t e = hipMalloc(&p, sizeof(int32_t) * std::max(words, min_words));
+    if (e != hipSuccess) return e;
+    g->owned.push_back(p);
+    *dst = (int32_t*)p;
+    return words ? hipMemcpy(p, v, sizeof(int32_t) * words, hipMemcpyHostToDevice) : hipSuccess;
+}
+static hipError_t graph_upload(gnode_graph_s* g, int32_t** dst, const std::vector<int32_t>& v, size_t min_words = 0) {
+    return graph_upload(g, dst, v.data(), v.size(), min_words);
+}
+
+// Every array of the plan that some kernel reads, one allocation each (gnode_graph_plan.h says what they hold).
+static hipError_t graph_upload_plan(gnode_graph_s* g, const GnGraphPlan& P, const int32_t* rowptr_host, const int32_t* col_host) {
+#define UP(...) do { const hipError_t e_ = graph_upload(g, __VA_ARGS__); if (e_ != hipSuccess) return e_; } while (0)
+    UP(&g->rowptr, rowptr_host, (size_t)g->info.n + 1);
+    UP(&g->col, col_host, (size_t)g->nnz, 1);
+    UP(&g->rowhdr, P.rowhdr);
+    if (P.n_hub > 0) {
+        UP(&g->hubidx, P.hubidx);
+        UP(&g->seg_lo, P.seg_lo);
+        UP(&g->seg_hi, P.seg_hi);
+        UP(&g->hub_seg_ptr, P.hub_seg_ptr);
+    }
+    for (int i = 0; i < 3; ++i) {
+        const GnPers64Maps& M = P.pers[i];
+        if (!M.present) continue;
+        UP(&g->persmap[i], M.map, 4);
+        UP(&g->pershub[i], M.hub, 4);
+        UP(&g->perssegptr[i], M.segptr, 4);
+        UP(&g->perssegitem[i], M.items, 4);
+        g->perslds[i] = M.lds;
+    }
+    if (!P.pgmap.empty()) UP(&g->pgmap, P.pgmap);
+#undef UP
+    return hipSuccess;
+}
+
+extern "C" int gnode_graph_destroy(gnode_graph_t g) {
+    if (!g) return 0;
+    for (void* p : g->owned) (void)hipFree(p);
+    delete g;
+    return 0;
+}
+
 extern "C" int gnode_graph_create(const int32_t* rowptr_host, const int32_t* col_host, int32_t n, int64_t nnz,
                                   gnode_graph_t* out) {
     GN_CHECK_ARG(rowptr_host && out && n > 0 && nnz >= 0, "gnode_graph_create: null pointer or empty graph");
     GN_CHECK_ARG(col_host || nnz == 0, "gnode_graph_create: col is null");
-    GN_CHECK_ARG(rowptr_host[0] == 0 && rowptr_host[n] == nnz, "gnode_graph_create: rowptr[0] != 0 or rowptr[n] != nnz");
-    int32_t maxdeg = 0, n_bigrow = 0;
-    for (int32_t i = 0; i < n; ++i) {
-        const int32_t d = rowptr_host[i + 1] - rowptr_host[i];
-        GN_CHECK_ARG(d >= 0, "gnode_graph_create: rowptr not monotone at %d", i);
-        maxdeg = d > maxdeg ? d : maxdeg;
-        n_bigrow += d > GN_SIR_BIGROW;
-    }
-    for (int64_t e = 0; e < nnz; ++e)
-        GN_CHECK_ARG(col_host[e] >= 0 && col_host[e] < n, "gnode_graph_create: col[%lld]=%d out of range",
-                     (long long)e, col_host[e]);
+    const GnGraphPlan plan = gn_plan_graph(rowptr_host, col_host, n, nnz);
+    GN_CHECK_ARG(plan.error.empty(), "%s", plan.error.c_str());
     int dev = 0;
     GN_HIP(hipGetDevice(&dev));
     if (int e = gn_device_setup_once(dev)) return e;
     gnode_graph_s* g = new gnode_graph_s();
-    g->n = n; g->nnz = nnz; g->max_degree = maxdeg; g->n_bigrow = n_bigrow; g->rowptr = nullptr; g->col = nullptr; g->rowhdr = nullptr;
-    g->n_hub = g->n_seg = 0; g->hubidx = g->seg_lo = g->seg_hi = g->hub_seg_ptr = nullptr;
+    g->info = gn_graph_info(plan, n, g_dev_cu[dev]);
+    g->nnz = nnz; g->max_degree = plan.max_degree; g->n_bigrow = plan.n_bigrow; g->n_seg = plan.n_seg;
     g->device = dev;
-    g->num_cu = g_dev_cu[dev];
-    hipError_t e1 = hipMalloc(&g->rowptr, sizeof(int32_t) * (size_t)(n + 1));
-    hipError_t e2 = hipMalloc(&g->col, sizeof(int32_t) * (size_t)(nnz > 0 ? nnz : 1));
-    if (e1 != hipSuccess || e2 != hipSuccess) {
-        gnode_set_error("gnode_graph_create: hipMalloc failed");
-        if (g->rowptr) (void)hipFree(g->rowptr);
-        if (g->col) (void)hipFree(g->col);
-        delete g;
+    const hipError_t e = graph_upload_plan(g, plan, rowptr_host, col_host);
+    if (e != hipSuccess) {
+        gnode_set_error("gnode_graph_create: uploading the graph failed: %s", hipGetErrorString(e));
+        gnode_graph_destroy(g);
         return GNODE_ERR_HIP;
-    }
-    hipError_t e3 = hipMemcpy(g->rowptr, rowptr_host, sizeof(int32_t) * (size_t)(n + 1), hipMemcpyHostToDevice);
-    hipError_t e4 = nnz ? hipMemcpy(g->col, col_host, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice) : hipSuccess;
-    if (e3 != hipSuccess || e4 != hipSuccess) {
-        gnode_set_error("gnode_graph_create: hipMemcpy failed: %s", hipGetErrorString(e3 != hipSuccess ? e3 : e4));
-        (void)hipFree(g->rowptr);
-        (void)hipFree(g->col);
-        delete g;
-        return GNODE_ERR_HIP;
-    }
-    {   // row headers (see gnode_common.h)
-        std::vector<int32_t> hdr((size_t)n * 20, 0);
-        for (int32_t r = 0; r < n; ++r) {
-            const int32_t lo = rowptr_host[r], hi = rowptr_host[r + 1];
-            hdr[(size_t)r * 20] = lo; hdr[(size_t)r * 20 + 1] = hi;
-            for (int32_t k = 0; k < 16 && lo + k < hi; ++k) hdr[(size_t)r * 20 + 4 + k] = col_host[lo + k];
-        }
-        hipError_t e5 = hipMalloc(&g->rowhdr, sizeof(int32_t) * hdr.size());
-        if (e5 == hipSuccess) e5 = hipMemcpy(g->rowhdr, hdr.data(), sizeof(int32_t) * hdr.size(), hipMemcpyHostToDevice);
-        if (e5 != hipSuccess) {
-            gnode_set_error("gnode_graph_create: row headers: %s", hipGetErrorString(e5));
-            if (g->rowhdr) (void)hipFree(g->rowhdr);
-            (void)hipFree(g->rowptr);
-            (void)hipFree(g->col);
-            delete g;
-            return GNODE_ERR_HIP;
-        }
-    }
-    for (int i = 0; i < 3; ++i) { g->persmap[i] = g->pershub[i] = g->perssegptr[i] = g->perssegitem[i] = nullptr; g->perslds[i] = 0; }
-    int e_build = gn_hub_build(g, rowptr_host);
-    if (!e_build) e_build = gn_pers64_build(g, rowptr_host);
-    g->pgmap = nullptr;
-    if (!e_build) e_build = gn_persg_build(g, rowptr_host);
-    if (int e = e_build) {
-        (void)hipFree(g->rowhdr);
-        gn_pers64_free(g);
-        gn_persg_free(g);
-        gn_hub_free(g);
-        (void)hipFree(g->rowptr);
-        (void)hipFree(g->col);
-        delete g;
-        return e;
     }
     *out = g;
     return 0;
 }
 
-extern "C" int gnode_graph_destroy(gnode_graph_t g) {
-    if (!g) return 0;
-    gn_pers64_free(g);
-    gn_persg_free(g);
-    gn_hub_free(g);
-    (void)hipFree(g->rowptr);
-    (void)hipFree(g->col);
-    if (g->rowhdr) (void)hipFree(g->rowhdr);
-    delete g;
-    return 0;
-}
-
 extern "C" int gnode_graph_info(gnode_graph_t g, int32_t* n, int64_t* nnz, int32_t* max_degree) {
     GN_CHECK_ARG(g, "gnode_graph_info: null graph");
-    if (n) *n = g->n;
+    if (n) *n = g->info.n;
     if (nnz) *nnz = g->nnz;
     if (max_degree) *max_degree = g->max_degree;
     return 0;
@@ -643,7 +622,7 @@ extern "C" int gnode_graph_info(gnode_graph_t g, int32_t* n, int64_t* nnz, int32
 // --------------------------------------------------------------------------- RHS
 extern "C" size_t gnode_rhs_workspace_bytes(gnode_graph_t g, int64_t rows, int32_t H) {
     if (!g || rows <= 0 || H < 4 || H > 128 || H % 4) return 0;
-    return gn_align((size_t)2 * rows * H * sizeof(float)) + gn_hub_scratch_bytes(g, rows / g->n, H, 1);
+    return gn_align((size_t)2 * rows * H * sizeof(float)) + gn_hub_scratch_bytes(g, rows / g->info.n, H, 1);
 }
 
 extern "C" int gnode_rhs_f32(gnode_graph_t g, const float* x, const float* W, const float* b, float* dx, int64_t rows,
@@ -651,8 +630,8 @@ extern "C" int gnode_rhs_f32(gnode_graph_t g, const float* x, const float* W, co
     GN_CHECK_ARG(g && x && W && b && dx && workspace, "gnode_rhs_f32: null pointer");
     if (int e = check_H(H)) return e;
     GN_CHECK_ARG(H >= 2, "gnode_rhs_f32: H >= 2 required (beta, gamma live in columns 0, 1)");
-    GN_CHECK_ARG(rows > 0 && rows % g->n == 0, "gnode_rhs_f32: rows=%lld is not a multiple of graph n=%d",
-                 (long long)rows, g->n);
+    GN_CHECK_ARG(rows > 0 && rows % g->info.n == 0, "gnode_rhs_f32: rows=%lld is not a multiple of graph n=%d",
+                 (long long)rows, g->info.n);
     if (workspace_bytes < gnode_rhs_workspace_bytes(g, rows, H)) {
         gnode_set_error("gnode_rhs_f32: workspace %zu < %zu", workspace_bytes, gnode_rhs_workspace_bytes(g, rows, H));
         return GNODE_ERR_WORKSPACE;
@@ -681,9 +660,9 @@ FwdPlan gn_forward_plan(const gnode_graph_s* g, long rows, int H, int method, in
     pl.h64 = H == 64 && method == 0;
     pl.n_emit = n_emit;
     const bool persist = n_steps >= 1 && !(flags & GNODE_FWD_PER_STEP);
-    if (method == 0 && H <= 32 && persist && gn_persg_plan(g, rows, H, n_steps, &pl.persg)) pl.path = FwdPath::persg;
-    else if (pl.h64 && persist && gn_pers64_plan(g, rows / g->n, n_steps, &pl.pers)) pl.path = FwdPath::pers64;
-    else if (pl.h64 && n_steps >= 1 && gn_tiny64_ok(g->n, n_steps, n_emit, !with_sol)) pl.path = FwdPath::tiny;
+    if (method == 0 && H <= 32 && persist && gn_persg_plan(g->info, rows, H, n_steps, &pl.persg)) pl.path = FwdPath::persg;
+    else if (pl.h64 && persist && gn_pers64_plan(g->info, rows / g->info.n, n_steps, &pl.pers)) pl.path = FwdPath::pers64;
+    else if (pl.h64 && n_steps >= 1 && gn_tiny64_ok(g->info.n, n_steps, n_emit, !with_sol)) pl.path = FwdPath::tiny;
     return pl;
 }
 
@@ -707,7 +686,7 @@ static FwdLayout forward_layout(int64_t rows, int32_t H, int32_t method) {
 
 extern "C" size_t gnode_forward_workspace_bytes(gnode_graph_t g, int64_t rows, int32_t H, int32_t method) {
     if (!g || rows <= 0 || H < 4 || H > 128 || H % 4) return 0;
-    return forward_layout(rows, H, method).fixed + gn_hub_scratch_bytes(g, rows / g->n, H, 1);
+    return forward_layout(rows, H, method).fixed + gn_hub_scratch_bytes(g, rows / g->info.n, H, 1);
 }
 
 // One forward call as the path launchers see it.
@@ -825,14 +804,14 @@ static int forward_euler_steps(FwdCall c, const FwdPlan& pl) {
             // two-launch branch below, whose node MLP runs on the matrix cores (a VALU mat-vec is 12x off the bound there)
             StepOut out = {c.out(c.S, k + 1), c.out(c.I, k + 1), c.out(c.R, k + 1), sol_next};
             const float* HubP = nullptr;          // segment partials of the hub rows; the step kernel adds them up itself
-            if (int e = gn_hub_segments(c.g, rows / c.g->n, H, c.zi_cur, c.hub_scratch, &HubP, c.st)) return e;
-            dim3 grid((unsigned)((c.g->n + rpw - 1) / rpw), (unsigned)(rows / c.g->n));
+            if (int e = gn_hub_segments(c.g, rows / c.g->info.n, H, c.zi_cur, c.hub_scratch, &HubP, c.st)) return e;
+            dim3 grid((unsigned)((c.g->info.n + rpw - 1) / rpw), (unsigned)(rows / c.g->info.n));
             const size_t lds = (size_t)H * H * sizeof(float);
             const bool sampled = prof_begin(0, c.st);
             // (H < 128 here: W^T is at most 61 KB of dynamic LDS, below the 64 KB that would need an attribute)
-            const bool hubs = c.g->n_hub > 0;
+            const bool hubs = c.g->info.n_hub > 0;
             GN_LPR_DISPATCH(64, lpr, hipLaunchKernelGGL((hubs ? k_step_generic<LPR, true> : k_step_generic<LPR, false>), grid, dim3(256), lds,
-                                                        c.st, c.g->rowptr, c.g->col, c.g->n, rows, H, Ycur, c.zi_cur, c.zi_nxt,
+                                                        c.st, c.g->rowptr, c.g->col, c.g->info.n, rows, H, Ycur, c.zi_cur, c.zi_nxt,
                                                         p->odefunc_linear_weight, p->odefunc_linear_bias, c.beta, c.gamma, dt,
                                                         p->linear3_weight, p->linear3_bias, p->linearS2_weight, p->linearS2_bias, out,
                                                         c.g->hubidx, HubP, c.g->hub_seg_ptr, c.g->n_seg));
@@ -892,8 +871,8 @@ extern "C" int gnode_forward_f32(gnode_graph_t g, const float* x, const gnode_pa
     GN_CHECK_ARG(method == 0 || method == 1, "gnode_forward_f32: method must be 0 (euler) or 1 (rk4)");
     if (int e = check_H(H)) return e;
     GN_CHECK_ARG(H >= 2, "gnode_forward_f32: H >= 2 required (beta, gamma live in columns 3, 4 of x)");
-    GN_CHECK_ARG(rows > 0 && rows % g->n == 0, "gnode_forward_f32: rows=%lld is not a multiple of graph n=%d",
-                 (long long)rows, g->n);
+    GN_CHECK_ARG(rows > 0 && rows % g->info.n == 0, "gnode_forward_f32: rows=%lld is not a multiple of graph n=%d",
+                 (long long)rows, g->info.n);
     GN_CHECK_ARG(p->odefunc_linear_weight && p->odefunc_linear_bias && p->linearS1_weight && p->linearS1_bias &&
                      p->linear3_weight && p->linear3_bias && p->linearS2_weight && p->linearS2_bias,
                  "gnode_forward_f32: null parameter pointer");
@@ -938,7 +917,7 @@ extern "C" int gnode_forward_f32(gnode_graph_t g, const float* x, const gnode_pa
 
 extern "C" int gnode_forward_path(gnode_graph_t g, int64_t rows, int32_t H, int32_t method, int32_t n_steps, int32_t n_out,
                                   int32_t with_sol, int32_t flags, int32_t* plan_host) {
-    if (!g || rows <= 0 || rows % g->n) return -1;
+    if (!g || rows <= 0 || rows % g->info.n) return -1;
     const FwdPlan pl = gn_forward_plan(g, rows, H, method, n_steps, n_out, with_sol != 0, flags);
     if (pl.path == FwdPath::pers64 && plan_host) {
         const PersPlan& q = pl.pers;
@@ -982,6 +961,6 @@ bool gn_sol_carries_ai(const gnode_graph_s* g, long rows, int H, int n_steps, in
 }
 
 extern "C" int gnode_sol_carries_neighbour_sums(gnode_graph_t g, int64_t rows, int32_t H, int32_t n_steps, int32_t n_out, int32_t flags) {
-    if (!g || rows <= 0 || rows % g->n) return 0;
+    if (!g || rows <= 0 || rows % g->info.n) return 0;
     return gn_sol_carries_ai(g, rows, H, n_steps, n_out, flags) ? 1 : 0;
 }

@@ -2,15 +2,6 @@
 #pragma once
 #include "gnode_common.h"
 
-#define PERS_FLAG_WORDS 2048
-
-// How the workgroups of one launch are dealt to samples.  A "group" = the workgroups that own one sample's rows:
-//   nt          16-row tiles per workgroup (blockDim = 256 * nt); wgs = ceil(n / (16 nt)) workgroups per group
-//   span == 1   a group sits on ONE XCD, gpx groups side by side on each XCD (tickets [gi * wgs, (gi + 1) * wgs))
-//   span  > 1   a group takes `span` whole XCDs, `per` tickets on each
-//   concurrent  groups alive at once (>= B: one round)
-struct PersPlan { int nt, wgs, span, gpx, per, slots, n_xcc, rounds, concurrent, fstride; };
-
 struct PersCtl {                       // device memory, zeroed (k_pers_zero) in front of every launch
     unsigned ticket[8][32];            // per XCC (a 128-B line each): the next free slot on that XCD
     unsigned error[32];                // [0] != 0: a workgroup gave up waiting (code), [1]: the epoch it waited for
@@ -40,8 +31,6 @@ struct PersArgs {
     PersSched sched;
 };
 
-// false: this (graph, batch, horizon) does not take the persistent path (hub rows, too many rows for one resident grid, ...)
-bool gn_pers64_plan(const gnode_graph_s* g, long B, int n_steps, PersPlan* p);
 size_t gn_pers64_ctl_bytes();
 int gn_pers64_zero_ctl(void* ctl, hipStream_t st);      // in front of every persistent launch (a kernel: see gnode_pers64.hip)
 int gn_pers64_set_attributes();
@@ -53,7 +42,6 @@ int gn_launch_pers64(const gnode_graph_s* g, const PersPlan& pl, long rows, cons
 
 // adjoint sweep, intervals G-2 .. 1 (the discrete sweep: G-1 .. 2), in one persistent launch (gnode_pers64_bwd.hip)
 int gn_pers_bwd64_set_attributes();
-bool gn_pers_bwd64_plan(const gnode_graph_s* g, long B, int n_steps, PersPlan* p);
 int gn_launch_pers_bwd64(const gnode_graph_s* g, const PersPlan& pl, long rows, int G, float* Q0, float* Q1, const float* sol,
                          const float* keep, const float* W, const float* beta, const float* gamma, float* a, float* part,
                          const float* gS, const float* gI, const float* gR, const gnode_params* p, const float* dt_host,

@@ -30,8 +30,6 @@
 #include "gnode_pers64.h"
 #include "gnode_pers64_dev.h"
 #include <algorithm>
-#include <queue>
-#include <vector>
 
 template <bool PRJ, int NT, bool SC1ST, bool HUBS>
 __global__ __launch_bounds__(256 * NT) void k_pers64(const PersArgs a) {
@@ -78,8 +76,8 @@ __global__ __launch_bounds__(256 * NT) void k_pers64(const PersArgs a) {
     const unsigned tbytes = (rows + 1u) * 256u;
     const size_t slab = (size_t)rows * 64;
     const int n_steps = a.sched.n_steps;
-    // which node this lane group owns: the plan's row map deals degree-sorted quads of rows to the waves (a wave's four
-    // rows have similar lengths -- its load count is its longest row's) and the quads round-robin to the workgroups
+    // which node this lane group owns: the plan's row map deals the rows longest first, each to the workgroup with the fewest
+    // edges so far; a workgroup's rows come out in descending length, so a wave's four rows have similar lengths
     const int lgslot = idx * (16 * NT) + team * 16 + lr;
     const int node = a.rowmap[lgslot];
     const bool valid = node >= 0;
@@ -240,135 +238,7 @@ __global__ __launch_bounds__(256 * NT) void k_pers64(const PersArgs a) {
 }
 #undef PS_ACC
 
-// --------------------------------------------------------------------------- host: row maps, plan, launch
-// Slot s of the map for nt tiles per workgroup = lane group (s % (16 nt)) of workgroup s / (16 nt).  Rows are sorted by
-// length (longest first, ties by id); hub rows are dealt singly, the others in quads, round-robin: the four rows of a wave have
-// neighbouring lengths, and every workgroup gets rows from the whole length spectrum (equal bytes per CU).
-static const int kPersMaxRows = 256 * 64;              // one resident grid: 256 workgroups x 64 rows
-#define PERS_MAX_PARTIALS 128                          // partial-sum slots (256 B each) a workgroup may need for its hub rows
-int gn_pers64_build(gnode_graph_s* g, const int32_t* rowptr_host) {
-    for (int i = 0; i < 3; ++i) { g->persmap[i] = g->pershub[i] = g->perssegptr[i] = g->perssegitem[i] = nullptr; g->perslds[i] = 0; g->persitems[i] = 0; }
-    if (g->n > kPersMaxRows) return 0;
-    std::vector<int32_t> order((size_t)g->n);
-    for (int32_t r = 0; r < g->n; ++r) order[r] = r;
-    auto deg = [&](int32_t r) { return rowptr_host[r + 1] - rowptr_host[r]; };
-    std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return deg(x) > deg(y); });
-    auto up = [](int32_t** dst, const std::vector<int32_t>& v) -> hipError_t {
-        hipError_t e = hipMalloc(dst, sizeof(int32_t) * std::max<size_t>(v.size(), 4));
-        if (e != hipSuccess || v.empty()) return e;
-        return hipMemcpy(*dst, v.data(), sizeof(int32_t) * v.size(), hipMemcpyHostToDevice);
-    };
-    for (int i = 0; i < 3; ++i) {
-        const int nt = 1 << i, per_wg = 16 * nt, wgs = (g->n + per_wg - 1) / per_wg, quads_per_wg = 4 * nt;
-        std::vector<int32_t> map((size_t)wgs * per_wg, -1);
-        // Rows go to the workgroups longest first, each to the workgroup with the fewest EDGES so far that still has a slot
-        // (longest-processing-time greedy): a step waits for its busiest workgroup, whose gather time follows the rows it has to
-        // read -- hub rows included, their segments are summed by the owner's workgroup.  The two biggest hubs never share a
-        // workgroup, the workgroup of a big hub gets short ordinary rows, and a workgroup's rows come out in descending
-        // length, so the four rows of a wave are of neighbouring lengths (a wave issues loads as far as its longest row needs).
-        std::vector<int> fill((size_t)wgs, 0);
-        int32_t nh = 0;
-        while (nh < g->n && deg(order[nh]) > GN_HUB_T) ++nh;
-        if ((long)nh > (long)wgs * per_wg / 2) { continue; }   // (half the slots hubs: not a graph for this path)
-        {
-            typedef std::pair<long, int> WL;                   // (edges so far, workgroup)
-            std::priority_queue<WL, std::vector<WL>, std::greater<WL>> heap;
-            for (int wg = 0; wg < wgs; ++wg) heap.push(WL(0, wg));
-            for (int32_t r = 0; r < g->n; ++r) {
-                if (heap.empty()) return GNODE_ERR_ARG;        // cannot happen: wgs * per_wg >= n
-                const WL w = heap.top();
-                heap.pop();
-                map[(size_t)w.second * per_wg + fill[w.second]++] = order[r];
-                if (fill[w.second] < per_wg) heap.push(WL(w.first + std::max(1, deg(order[r])), w.second));
-            }
-        }
-        (void)quads_per_wg;
-        // hub rows: the segments of a workgroup's hubs are summed by that workgroup's own lane groups (partials through LDS),
-        // dealt to the lane groups with the least gather work so far; a hub's partial slots are consecutive, in segment order
-        std::vector<int32_t> hub((size_t)wgs * per_wg * 2, 0), segptr((size_t)wgs * per_wg * 2, 0), items;
-        int max_slots = 0, max_items = 0;
-        bool ok = true;
-        for (int wg = 0; wg < wgs && ok; ++wg) {
-            std::vector<long> load((size_t)per_wg, 0);
-            std::vector<std::vector<int32_t>> mine((size_t)per_wg);
-            int slots = 0;
-            for (int s = 0; s < per_wg; ++s) {
-                const int32_t r = map[(size_t)wg * per_wg + s];
-                hub[((size_t)wg * per_wg + s) * 2] = -1;
-                if (r >= 0 && deg(r) <= GN_HUB_T) load[s] = deg(r);
-            }
-            for (int s = 0; s < per_wg; ++s) {
-                const int32_t r = map[(size_t)wg * per_wg + s];
-                if (r < 0 || deg(r) <= GN_HUB_T) continue;
-                const int32_t lo = rowptr_host[r], hi = rowptr_host[r + 1];
-                hub[((size_t)wg * per_wg + s) * 2] = slots;
-                hub[((size_t)wg * per_wg + s) * 2 + 1] = (hi - lo + HUB_SEG - 1) / HUB_SEG;
-                for (int32_t e = lo; e < hi; e += HUB_SEG) {
-                    int best = 0;
-                    for (int t = 1; t < per_wg; ++t) if (load[t] < load[best]) best = t;
-                    load[best] += HUB_SEG;
-                    mine[best].push_back(e); mine[best].push_back(std::min(hi, e + HUB_SEG)); mine[best].push_back(slots++); mine[best].push_back(0);
-                }
-            }
-            if (slots > PERS_MAX_PARTIALS) ok = false;
-            for (int s = 0; s < per_wg; ++s) { if (mine[s].size() / 4 > PERS_MAX_ITEMS) ok = false; max_items = std::max(max_items, (int)(mine[s].size() / 4)); }
-            max_slots = std::max(max_slots, slots);
-            for (int s = 0; s < per_wg; ++s) {
-                segptr[((size_t)wg * per_wg + s) * 2] = (int32_t)(items.size() / 4);
-                segptr[((size_t)wg * per_wg + s) * 2 + 1] = (int32_t)(mine[s].size() / 4);
-                items.insert(items.end(), mine[s].begin(), mine[s].end());
-            }
-        }
-        if (!ok) continue;                                  // this tile count is not available for this graph (plan skips it)
-        GN_HIP(up(&g->persmap[i], map));
-        GN_HIP(up(&g->pershub[i], hub));
-        GN_HIP(up(&g->perssegptr[i], segptr));
-        GN_HIP(up(&g->perssegitem[i], items));
-        g->perslds[i] = max_slots;
-        g->persitems[i] = max_items;
-    }
-    return 0;
-}
-void gn_pers64_free(gnode_graph_s* g) {
-    for (int i = 0; i < 3; ++i) {
-        for (int32_t** q : {&g->persmap[i], &g->pershub[i], &g->perssegptr[i], &g->perssegitem[i]})
-            if (*q) { (void)hipFree(*q); *q = nullptr; }
-    }
-}
-
-bool gn_pers64_plan(const gnode_graph_s* g, long B, int n_steps, PersPlan* p) {
-    if (n_steps < 1 || n_steps > 128 || B < 1) return false;
-    const int n_xcc = 8;
-    if (g->num_cu < 64 || g->num_cu % n_xcc) return false;
-    const int slots = g->num_cu / n_xcc;
-    if ((long)B * g->n >= (1L << 24)) return false;
-    // the smallest tile count that holds the batch -- except that a graph whose biggest hub would give a lane group TWO segment
-    // sums per step (a second ~2 us round of 32-row gathers every step) takes the next tile count when that halves the rounds
-    // (fb-social size with a 738-edge row, B = 1: 8.7 -> 7.x us per step at 32 instead of 16 rows per workgroup)
-    bool have = false;
-    for (int nt = 1; nt <= 4; nt *= 2) {
-        const int vi = nt == 1 ? 0 : nt == 2 ? 1 : 2;
-        if (!g->persmap[vi]) continue;      // graph too large, or its hub rows need too many partial slots
-        const int wgs = (g->n + 16 * nt - 1) / (16 * nt);
-        PersPlan q;
-        q.nt = nt; q.wgs = wgs; q.n_xcc = n_xcc; q.slots = slots;
-        if (wgs <= slots) { q.span = 1; q.gpx = std::min(slots / wgs, PERS_FLAG_WORDS / 32 / n_xcc); q.per = wgs; q.concurrent = n_xcc * q.gpx; }   // (one 32-word flag line per group)
-        else {
-            int span = 2;
-            while (span < n_xcc && wgs > span * slots) span *= 2;
-            if (wgs > span * slots) continue;
-            q.span = span; q.gpx = 1; q.per = (wgs + span - 1) / span; q.concurrent = n_xcc / span;
-        }
-        if (q.concurrent < B) continue;
-        q.rounds = 1;
-        q.fstride = (wgs + 31) / 32 * 32;
-        if ((long)q.concurrent * q.fstride > PERS_FLAG_WORDS) continue;
-        if (!have) { *p = q; have = true; if (g->persitems[vi] <= 1) return true; continue; }
-        if (nt <= 2 && g->persitems[vi] < g->persitems[p->nt == 1 ? 0 : 1]) { *p = q; if (g->persitems[vi] <= 1) return true; }
-    }
-    return have;
-}
-
+// --------------------------------------------------------------------------- host: launch (row maps and plan: gnode_graph_plan.cpp)
 size_t gn_pers64_ctl_bytes() { return gn_align(sizeof(PersCtl)); }
 
 // Tickets, flags and the give-up word are zeroed in front of EVERY persistent launch -- by a kernel, not by hipMemsetAsync (see
@@ -396,10 +266,10 @@ int gn_launch_pers64(const gnode_graph_s* g, const PersPlan& pl, long rows, cons
                      void* ctl, bool ctl_is_zero, hipStream_t st) {
     PersArgs a;
     const int vi = pl.nt == 1 ? 0 : pl.nt == 2 ? 1 : 2;
-    const bool hubs = g->n_hub > 0;
-    a.rowhdr = g->rowhdr; a.col = g->col; a.rowmap = g->persmap[vi]; a.n = g->n;
+    const bool hubs = g->info.n_hub > 0;
+    a.rowhdr = g->rowhdr; a.col = g->col; a.rowmap = g->persmap[vi]; a.n = g->info.n;
     a.lds_slots = hubs ? g->perslds[vi] : 0;
-    a.hubslot = hubs ? g->pershub[vi] : nullptr; a.segptr = hubs ? g->perssegptr[vi] : nullptr; a.segitem = hubs ? g->perssegitem[vi] : nullptr; a.B = (int)(rows / g->n); a.rows = (unsigned)rows;
+    a.hubslot = hubs ? g->pershub[vi] : nullptr; a.segptr = hubs ? g->perssegptr[vi] : nullptr; a.segitem = hubs ? g->perssegitem[vi] : nullptr; a.B = (int)(rows / g->info.n); a.rows = (unsigned)rows;
     a.pp = pers_place_of(pl);
     a.Y0 = Y0; a.PR0 = PR0; a.beta = beta; a.gamma = gamma; a.Z0 = Z0; a.Z1 = Z1; a.keep = keep;
     a.W = W; a.bias = bias; a.w3 = p->linear3_weight; a.b3 = p->linear3_bias; a.w2 = p->linearS2_weight; a.b2 = p->linearS2_bias;

@@ -287,7 +287,7 @@ __global__ __launch_bounds__(256 * NT) void k_pers_bwd64(const PersBwdArgs a) {
 }
 
 // --------------------------------------------------------------------------- host
-static size_t pers_bwd_lds_bytes(int nt, int partial_slots = 128) {
+static size_t pers_bwd_lds_bytes(int nt, int partial_slots = PERS_MAX_PARTIALS) {
     const size_t need = sizeof(float) * ((size_t)64 * TS + (size_t)nt * 6 * 16 * TS + (size_t)partial_slots * 96 + (size_t)16 * nt * PERS_MAX_ITEMS);
     return std::max<size_t>(need, 84 * 1024);              // > half of the CU's 160 KB: ONE workgroup per CU
 }
@@ -314,11 +314,11 @@ int gn_launch_pers_bwd64(const gnode_graph_s* g, const PersPlan& pl, long rows, 
                          bool ctl_is_zero, bool fold, bool exact, int* slots, hipStream_t st) {
     PersBwdArgs x;
     const int vi = pl.nt == 1 ? 0 : 1;
-    const bool hubs = g->n_hub > 0;
+    const bool hubs = g->info.n_hub > 0;
     x.rowhdr = g->rowhdr; x.col = g->col; x.rowmap = g->persmap[vi];
     x.lds_slots = hubs ? g->perslds[vi] : 0;
     x.hubslot = hubs ? g->pershub[vi] : nullptr; x.segptr = hubs ? g->perssegptr[vi] : nullptr; x.segitem = hubs ? g->perssegitem[vi] : nullptr;
-    x.n = g->n; x.B = (int)(rows / g->n); x.rows = (unsigned)rows; x.pp = pers_place_of(pl); x.G = G;
+    x.n = g->info.n; x.B = (int)(rows / g->info.n); x.rows = (unsigned)rows; x.pp = pers_place_of(pl); x.G = G;
     x.Q[0] = Q0; x.Q[1] = Q1; x.sol = sol; x.keep = keep; x.W = W; x.beta = beta; x.gamma = gamma; x.a = a; x.part = part;
     x.gS = gS; x.gI = gI; x.gR = gR;
     x.w3 = p->linear3_weight; x.b3 = p->linear3_bias; x.w2 = p->linearS2_weight; x.b2 = p->linearS2_bias;
@@ -348,17 +348,4 @@ int gn_launch_pers_bwd64(const gnode_graph_s* g, const PersPlan& pl, long rows, 
     }
     *slots = (int)std::min<long>((long)std::min<long>(x.B, BWD_NWG / pl.wgs) * pl.wgs, BWD_NWG);
     return 0;
-}
-
-// The sweep's plan: 1 or 2 tiles per workgroup only (its per-row state -- adjoint, gradient accumulators, the interval's own
-// rows -- does not fit the 128 registers a 1024-thread workgroup leaves), up to 2 consecutive launches (measured: 4 launches at
-// 600 nodes x 32 samples lose to one launch per interval)
-bool gn_pers_bwd64_plan(const gnode_graph_s* g, long B, int n_steps, PersPlan* p) {
-    if (n_steps < 2 || n_steps > 127 || B < 1) return false;
-    for (long conc = B; conc >= 1; conc = (conc + 1) / 2) {
-        PersPlan q;
-        if (gn_pers64_plan(g, conc, n_steps, &q) && q.nt <= 2 && (B + q.concurrent - 1) / q.concurrent <= 2 && q.wgs <= BWD_NWG) { *p = q; return true; }
-        if (conc == 1) break;
-    }
-    return false;
 }

@@ -154,7 +154,6 @@ __device__ __forceinline__ bool pers_wait(unsigned* flags, int wgs, unsigned epo
 // a hub's <= 32-edge segments are summed by lane groups of ITS OWN workgroup (the plan's work lists), partials through LDS --
 // the same segments, the same ascending sums and the same segment-order total as k_hub_seg + the consumers of the per-step
 // kernels, so the bits agree, and no second group barrier is needed.  This lane group's items: [it0, it0 + itn).
-#define PERS_MAX_ITEMS 8                               // segment sums one lane group may be given (plan-time bound)
 // LDS behind the tiles (S = the plan's partial slots per workgroup): partials [S][64] floats | neighbour ids of every segment
 // as table byte offsets [S][32] | per lane group its items [PERS_MAX_ITEMS] as (slot | edges << 16).  The ids and item lists
 // are loop-invariant: staged once per sample, so a segment sum is ONE round trip per step (32 rows in flight where the

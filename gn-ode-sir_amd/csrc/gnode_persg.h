@@ -2,11 +2,6 @@
 #pragma once
 #include "gnode_common.h"
 
-struct PersgPlan { int wgs, wps, nw, map_off, idcap, segcap; size_t lds; };   // nw: waves per workgroup (64 / LPR rows each)
-
-// false: this (graph, rows, H, horizon) keeps the one-launch-per-step forms (more rows than one resident grid of one workgroup
-// per CU holds, a window of rows whose neighbour ids / hub segments do not fit a workgroup's LDS, other hidden sizes)
-bool gn_persg_plan(const gnode_graph_s* g, long rows, int H, int n_steps, PersgPlan* p);
 int gn_persg_set_attributes();
 // Y0 / beta / gamma / table Z0 = Z_I(y_0) as k_encode and the node-MLP launch left them; slot_host[k]: output row of grid point k+1 or -1
 int gn_launch_persg(const gnode_graph_s* g, const PersgPlan& pl, long rows, int H, const float* Y0, float* Z0, float* Z1,

@@ -8,7 +8,7 @@
 //   * ONE launch, one workgroup per CU (dynamic LDS > half of the CU's 160 KB).  A workgroup is 1 .. 4 waves, a wave holds
 //     64 / LPR rows of one sample (32 at H = 8); the plan takes the FEWEST rows per workgroup that keeps the whole batch resident
 //     (gn_persg_plan: the busiest CU's gather is what a step waits for), the graph's row map deals the rows longest first in
-//     snake order (gn_persg_build).  A row's state stays in REGISTERS for every step / interval;
+//     snake order (gnode_graph_plan.cpp).  A row's state stays in REGISTERS for every step / interval;
 //   * only the gather tables travel: Z_I (forward), Z_I and q (adjoint), double-buffered; the hand-off between steps is the
 //     measured form of MI355X_MICROARCH.md's table for groups that span XCDs -- every storing wave `s_waitcnt vmcnt(0)`,
 //     workgroup barrier, ONE lane publishes the workgroup's epoch flag; the consumers' wave 0 polls all flags, barrier, every
@@ -70,12 +70,6 @@ __device__ __forceinline__ PgLds pg_carve(float* lds, int idcap, int segcap) {
     L.HI = (unsigned*)(L.HP1 + (size_t)segcap * H); L.HS = (int*)(L.HI + (size_t)segcap * 32); L.meta = L.HS + 2 * segcap;
     return L;
 }
-static size_t pg_lds_bytes(int H, int idcap, int segcap) {
-    const size_t need = sizeof(float) * ((size_t)2 * H * H + idcap + (size_t)2 * segcap * H + (size_t)segcap * 34 + 8);
-    // >= 84 KB: one workgroup per CU; the adjoint's final reduction borrows 64 KB behind the two weight copies
-    return std::max<size_t>(need, std::max<size_t>(84 * 1024, sizeof(float) * 2 * H * H + 64 * 1024 + 64));
-}
-
 // What a lane group knows about its row, staged once per launch.
 struct PgRow { bool inrow; unsigned r, off_b; int cnt, hub_n, hub_base; unsigned estart; };
 
@@ -500,87 +494,7 @@ __global__ __launch_bounds__(256) void k_persg_bwd(const PersgArgs a) {
     }
 }
 
-// --------------------------------------------------------------------------- host: graph statistics, plan, launchers
-static int persg_vi(int H) { return H == 8 ? 0 : H == 16 ? 1 : H == 32 ? 2 : -1; }
-
-// Row maps for workgroups of 1 .. 4 waves (a wave holds 64 / LPR rows: 32 at H = 8): rows are dealt longest first, round-robin,
-// to the sample's workgroups -- real node numberings put the big nodes next to each other, and one workgroup owning them all
-// would need their segments' ids in its LDS and set every step's duration.  (Edge-balanced dealing -- each row to the workgroup
-// with the fewest edges so far, what gn_pers64_build does -- measured worse here: heavy-tailed wiki-vote size 0.32 -> 0.37 ms;
-// a hub's segments are spread over the workgroup's lane groups, an ordinary row is one lane group's serial chain, and the
-// snake gives every workgroup the same number of rows from every length class.)  Per variant: the most neighbour ids of ordinary rows and the most hub segments one workgroup
-// has to stage.  All maps of a graph live in ONE device allocation.
-int gn_persg_build(gnode_graph_s* g, const int32_t* rowptr_host) {
-    const int n = g->n;
-    g->pgmap = nullptr;
-    for (int vi = 0; vi < 3; ++vi) for (int nw = 0; nw < 4; ++nw) { g->pgoff[vi][nw] = -1; g->pgids[vi][nw] = g->pgsegs[vi][nw] = 0; }
-    if ((long)n > 256L * 128) return 0;                      // never fits one resident grid
-    // every row, longest first (hub rows lead), dealt in snake order: each workgroup gets its share of the long rows AND of the
-    // neighbour ids -- what a step waits for is the busiest workgroup's gather
-    std::vector<int> order(n);
-    auto deg = [&](int i) { return rowptr_host[i + 1] - rowptr_host[i]; };
-    for (int i = 0; i < n; ++i) order[i] = i;
-    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return deg(x) > deg(y); });
-    std::vector<int32_t> all;
-    for (int vi = 0; vi < 3; ++vi)
-    for (int nw = 1; nw <= 4; ++nw) {
-        const int gpw = (32 >> vi) * nw, wps = (n + gpw - 1) / gpw;
-        if (wps > 256) continue;
-        std::vector<std::vector<int>> own(wps);
-        for (size_t h = 0; h < order.size(); ++h) {            // snake order: 0 .. wps-1, wps-1 .. 0, ...
-            const size_t lap = h / wps, pos = h % wps;
-            own[(lap & 1) ? wps - 1 - pos : pos].push_back(order[h]);
-        }
-        bool ok = true;
-        for (int w = 0; w < wps; ++w) if ((int)own[w].size() > gpw) ok = false;     // (cannot happen: wps * gpw >= n)
-        if (!ok) continue;
-        const size_t off = all.size();
-        all.resize(off + (size_t)wps * gpw, -1);
-        long best_i = 0, best_s = 0;
-        for (int ww = 0; ww < wps; ++ww) {
-            long ci = 0, cs = 0;
-            for (size_t k = 0; k < own[ww].size(); ++k) {
-                const int i = own[ww][k], d = deg(i);
-                all[off + (size_t)ww * gpw + k] = i;
-                if (g->n_hub > 0 && d > GN_HUB_T) cs += (d + HUB_SEG - 1) / HUB_SEG; else ci += d;
-            }
-            best_i = std::max(best_i, ci); best_s = std::max(best_s, cs);
-        }
-        g->pgoff[vi][nw - 1] = (int32_t)off;
-        g->pgids[vi][nw - 1] = (int32_t)std::min<long>(best_i, 1L << 30);
-        g->pgsegs[vi][nw - 1] = (int32_t)std::min<long>(best_s, 1L << 30);
-    }
-    if (all.empty()) return 0;
-    GN_HIP(hipMalloc(&g->pgmap, all.size() * sizeof(int32_t)));
-    GN_HIP(hipMemcpy(g->pgmap, all.data(), all.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    return 0;
-}
-void gn_persg_free(gnode_graph_s* g) {
-    if (g->pgmap) (void)hipFree(g->pgmap);
-    g->pgmap = nullptr;
-}
-
-// The fewest rows per workgroup (most CUs) that still leaves every workgroup of the batch resident, one per CU: what a step
-// waits for is its busiest CU's gather, and that is bound by the CU's rate of cache-line requests (a 32-byte row is a request
-// of its own: ~1.3 ns each measured, 128 rows x 22 neighbours = 3.7 us) -- so spread the rows over as many CUs as there are.
-bool gn_persg_plan(const gnode_graph_s* g, long rows, int H, int n_steps, PersgPlan* p) {
-    const int vi = persg_vi(H);
-    if (vi < 0 || n_steps < 1 || n_steps > 127 || !g->pgmap) return false;
-    if ((long)rows * H * 4 >= (1L << 31) - (1L << 17)) return false;    // 32-bit table offsets below PS_OOB
-    for (int nw = 1; nw <= 4; ++nw) {
-        if (g->pgoff[vi][nw - 1] < 0) continue;
-        const int gpw = (32 >> vi) * nw, wps = (g->n + gpw - 1) / gpw;
-        const long wgs = (rows / g->n) * wps;
-        if (wgs > std::min(g->num_cu, 256)) continue;              // one workgroup per CU, all resident; pers_wait sweeps 256 flags
-        const int idcap = (g->pgids[vi][nw - 1] + 3) & ~3, segcap = std::max(4, (g->pgsegs[vi][nw - 1] + 3) & ~3);
-        const size_t need = sizeof(float) * ((size_t)2 * H * H + idcap + (size_t)2 * segcap * H + (size_t)segcap * 34 + 8);
-        if (need > 150 * 1024) continue;
-        if (p) { p->wgs = (int)wgs; p->wps = wps; p->nw = nw; p->map_off = g->pgoff[vi][nw - 1]; p->idcap = idcap; p->segcap = segcap; p->lds = pg_lds_bytes(H, idcap, segcap); }
-        return true;
-    }
-    return false;
-}
-
+// --------------------------------------------------------------------------- host: launchers (row maps and plan: gnode_graph_plan.cpp)
 int gn_persg_set_attributes() {
     const int mx = 160 * 1024;
     GN_HIP(hipFuncSetAttribute((const void*)k_persg<2>, hipFuncAttributeMaxDynamicSharedMemorySize, mx));
@@ -596,11 +510,10 @@ int gn_persg_set_attributes() {
 }
 
 static void persg_common(PersgArgs& a, const gnode_graph_s* g, const PersgPlan& pl, long rows, int H, const gnode_params* p, void* ctl) {
-    a.rowptr = g->rowptr; a.col = g->col; a.hubidx = g->n_hub > 0 ? g->hubidx : nullptr; a.hub_seg_ptr = g->hub_seg_ptr;
+    a.rowptr = g->rowptr; a.col = g->col; a.hubidx = g->info.n_hub > 0 ? g->hubidx : nullptr; a.hub_seg_ptr = g->hub_seg_ptr;
     a.seg_lo = g->seg_lo; a.seg_hi = g->seg_hi;
-    (void)H;
     a.rowmap = g->pgmap + pl.map_off;
-    a.n = g->n; a.wgs = pl.wgs; a.wps = pl.wps; a.segcap = pl.segcap; a.idcap = pl.idcap; a.rows = (unsigned)rows;
+    a.n = g->info.n; a.wgs = pl.wgs; a.wps = pl.wps; a.segcap = pl.segcap; a.idcap = pl.idcap; a.rows = (unsigned)rows;
     a.W = p->odefunc_linear_weight; a.bias = p->odefunc_linear_bias;
     a.w3 = p->linear3_weight; a.b3 = p->linear3_bias; a.w2 = p->linearS2_weight; a.b2 = p->linearS2_bias;
     a.ctl = (PersCtl*)ctl;

@@ -315,11 +315,11 @@ static int vjp_launch(const gnode_graph_s* g, long rows, int H, const float* y, 
     }
     const float* qt = need_q ? q : Z + slab;          // (without g_y / gW / gb the second table is never used)
     const float *AIhub = nullptr, *GQhub = nullptr;
-    if (int e = gn_hub_gather(g, rows / g->n, H, Z + slab, qt, hub_scratch, &AIhub, &GQhub, st)) return e;
+    if (int e = gn_hub_gather(g, rows / g->info.n, H, Z + slab, qt, hub_scratch, &AIhub, &GQhub, st)) return e;
     VjpArgs A;
-    A.rowptr = g->rowptr; A.col = g->col; A.n = g->n; A.rows = rows; A.H = H;
+    A.rowptr = g->rowptr; A.col = g->col; A.n = g->info.n; A.rows = rows; A.H = H;
     A.y = y; A.bg = bg; A.Z = Z; A.q = qt; A.vSI = vSI; A.vR = vR; A.W = W;
-    A.hubidx = g->hubidx; A.AIhub = AIhub; A.GQhub = GQhub; A.n_hub = g->n_hub;
+    A.hubidx = g->hubidx; A.AIhub = AIhub; A.GQhub = GQhub; A.n_hub = g->info.n_hub;
     A.fSI = o.fSI; A.fR = o.fR; A.f4 = o.f4; A.gySI = o.gySI; A.gyR = o.gyR; A.gybg = o.gybg;
     A.part = o.part; A.part_stride = o.part_stride; A.w = o.w; A.gx = o.gx;
     const int lpr = gn_lpr(H);
@@ -345,8 +345,8 @@ static size_t rhs_vjp_fixed_bytes(int64_t rows, int32_t H) {
 }
 
 extern "C" size_t gnode_rhs_vjp_workspace_bytes(gnode_graph_t g, int64_t rows, int32_t H) {
-    if (!g || rows <= 0 || H < 4 || H > 128 || H % 4 || rows % g->n) return 0;
-    return rhs_vjp_fixed_bytes(rows, H) + gn_hub_scratch_bytes(g, rows / g->n, H, 2);
+    if (!g || rows <= 0 || H < 4 || H > 128 || H % 4 || rows % g->info.n) return 0;
+    return rhs_vjp_fixed_bytes(rows, H) + gn_hub_scratch_bytes(g, rows / g->info.n, H, 2);
 }
 
 extern "C" int gnode_rhs_vjp_f32(gnode_graph_t g, const float* y, const float* W, const float* b, const float* v, float* f_out,
@@ -354,8 +354,8 @@ extern "C" int gnode_rhs_vjp_f32(gnode_graph_t g, const float* y, const float* W
                                  size_t workspace_bytes, void* stream) {
     GN_CHECK_ARG(g && y && W && b && v && workspace, "gnode_rhs_vjp_f32: null pointer");
     GN_CHECK_ARG(H >= 4 && H <= 128 && H % 4 == 0, "gnode_rhs_vjp_f32: need 4 <= H <= 128, H %% 4 == 0 (got %d)", H);
-    GN_CHECK_ARG(rows > 0 && rows % g->n == 0, "gnode_rhs_vjp_f32: rows=%lld is not a multiple of graph n=%d",
-                 (long long)rows, g->n);
+    GN_CHECK_ARG(rows > 0 && rows % g->info.n == 0, "gnode_rhs_vjp_f32: rows=%lld is not a multiple of graph n=%d",
+                 (long long)rows, g->info.n);
     if (workspace_bytes < gnode_rhs_vjp_workspace_bytes(g, rows, H)) {
         gnode_set_error("gnode_rhs_vjp_f32: workspace %zu < %zu", workspace_bytes, gnode_rhs_vjp_workspace_bytes(g, rows, H));
         return GNODE_ERR_WORKSPACE;
@@ -400,8 +400,8 @@ static size_t rk4_fixed_bytes(int64_t rows, int32_t H) {
 }
 
 extern "C" size_t gnode_backward_rk4_workspace_bytes(gnode_graph_t g, int64_t rows, int32_t H) {
-    if (!g || rows <= 0 || H < 4 || H > 128 || H % 4 || rows % g->n) return 0;
-    return rk4_fixed_bytes(rows, H) + gn_hub_scratch_bytes(g, rows / g->n, H, 2);
+    if (!g || rows <= 0 || H < 4 || H > 128 || H % 4 || rows % g->info.n) return 0;
+    return rk4_fixed_bytes(rows, H) + gn_hub_scratch_bytes(g, rows / g->info.n, H, 2);
 }
 
 extern "C" int gnode_backward_rk4_dx_f32(gnode_graph_t g, const float* x, const gnode_params* p, const float* dt_host,
@@ -413,8 +413,8 @@ extern "C" int gnode_backward_rk4_dx_f32(gnode_graph_t g, const float* x, const 
     GN_CHECK_ARG(grads || gx, "gnode_backward_rk4_dx_f32: neither grads nor gx requested");
     GN_CHECK_ARG(n_steps >= 0 && (n_steps == 0 || dt_host), "gnode_backward_rk4_f32: bad n_steps/dt");
     GN_CHECK_ARG(H >= 4 && H <= 128 && H % 4 == 0, "gnode_backward_rk4_f32: need 4 <= H <= 128, H %% 4 == 0 (got %d)", H);
-    GN_CHECK_ARG(rows > 0 && rows % g->n == 0, "gnode_backward_rk4_f32: rows=%lld is not a multiple of graph n=%d",
-                 (long long)rows, g->n);
+    GN_CHECK_ARG(rows > 0 && rows % g->info.n == 0, "gnode_backward_rk4_f32: rows=%lld is not a multiple of graph n=%d",
+                 (long long)rows, g->info.n);
     GN_CHECK_ARG(p->odefunc_linear_weight && p->odefunc_linear_bias && p->linear3_weight && p->linear3_bias &&
                      p->linearS2_weight && p->linearS2_bias && p->linearS1_weight && p->linearS1_bias,
                  "gnode_backward_rk4_f32: null parameter pointer");

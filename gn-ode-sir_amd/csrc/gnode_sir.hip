@@ -495,11 +495,11 @@ extern "C" size_t gnode_sir_coins_workspace_bytes(void) { return gn_align(4096 *
 
 extern "C" size_t gnode_sir_workspace_bytes(gnode_graph_t g, int32_t T) {
     if (!g) return 0;
-    size_t b = gn_align((size_t)2 * T * g->n * sizeof(uint32_t)) + gn_align(4096 * sizeof(int32_t)) +
+    size_t b = gn_align((size_t)2 * T * g->info.n * sizeof(uint32_t)) + gn_align(4096 * sizeof(int32_t)) +
                gn_align((size_t)std::max<int64_t>(g->nnz, 1) * sizeof(int32_t));
     size_t tail = 0;                                       // one region, two users that never run together
-    if ((size_t)2 * g->n > kLdsStateLimit) tail = (size_t)2048 * 2 * g->n;                                   // scan kernel, state in memory
-    if (!frontier_lists_in_lds(g->n, g->n_bigrow)) tail = std::max(tail, (size_t)kFrontierGlobalGrid * 3 * g->n * sizeof(int32_t));   // frontier lists
+    if ((size_t)2 * g->info.n > kLdsStateLimit) tail = (size_t)2048 * 2 * g->info.n;                                   // scan kernel, state in memory
+    if (!frontier_lists_in_lds(g->info.n, g->n_bigrow)) tail = std::max(tail, (size_t)kFrontierGlobalGrid * 3 * g->info.n * sizeof(int32_t));   // frontier lists
     return b + gn_align(tail);
 }
 
@@ -513,14 +513,14 @@ static int sir_mc_philox_impl(gnode_graph_t g, const int32_t* seeds_host, int32_
                  "gnode_sir_mc_philox: bad T/sims/sim_offset");
     GN_CHECK_ARG(beta >= 0.0 && beta <= 1.0 && gamma >= 0.0 && gamma <= 1.0, "gnode_sir_mc_philox: beta, gamma in [0,1]");
     for (int i = 0; i < n_seeds; ++i)
-        GN_CHECK_ARG(seeds_host[i] >= 0 && seeds_host[i] < g->n, "gnode_sir_mc_philox: seed %d out of range", seeds_host[i]);
+        GN_CHECK_ARG(seeds_host[i] >= 0 && seeds_host[i] < g->info.n, "gnode_sir_mc_philox: seed %d out of range", seeds_host[i]);
     if (workspace_bytes < gnode_sir_workspace_bytes(g, T)) {
         gnode_set_error("gnode_sir_mc_philox: workspace %zu < %zu", workspace_bytes, gnode_sir_workspace_bytes(g, T));
         return GNODE_ERR_WORKSPACE;
     }
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace;
-    const size_t hist_b = gn_align((size_t)2 * T * g->n * sizeof(uint32_t));
+    const size_t hist_b = gn_align((size_t)2 * T * g->info.n * sizeof(uint32_t));
     uint32_t* hist = (uint32_t*)ws;
     int32_t* seeds = (int32_t*)(ws + hist_b);
     int32_t* src = (int32_t*)(ws + hist_b + gn_align(4096 * sizeof(int32_t)));
@@ -545,43 +545,43 @@ static int sir_mc_philox_impl(gnode_graph_t g, const int32_t* seeds_host, int32_
     if (sims > 0) {
         const bool sampled = gn_prof_begin(3, st);
         int per_cu_f = 1;
-        const int threads_f = frontier_threads(g->n, g->n_bigrow, &per_cu_f);
-        const size_t fl = frontier_lds_bytes(g->n, g->n_bigrow, threads_f);
-        const size_t lds = (size_t)2 * g->n;
+        const int threads_f = frontier_threads(g->info.n, g->n_bigrow, &per_cu_f);
+        const size_t fl = frontier_lds_bytes(g->info.n, g->n_bigrow, threads_f);
+        const size_t lds = (size_t)2 * g->info.n;
         if (fl <= kLdsStateLimit && !edge_scan) {
             // frontier-driven walk.  Workgroups per CU by LDS, at least 16 waves per CU
             const int per_cu = per_cu_f, threads = threads_f;
-            if (frontier_lists_in_lds(g->n, g->n_bigrow)) {
-                const int grid = (int)std::min<int64_t>(sims, (int64_t)g->num_cu * per_cu);
-                if (stats) hipLaunchKernelGGL((k_sir_frontier<uint16_t, true, true>), dim3(grid), dim3(threads), fl, st, g->rowptr, g->col, g->n, seeds,
+            if (frontier_lists_in_lds(g->info.n, g->n_bigrow)) {
+                const int grid = (int)std::min<int64_t>(sims, (int64_t)g->info.num_cu * per_cu);
+                if (stats) hipLaunchKernelGGL((k_sir_frontier<uint16_t, true, true>), dim3(grid), dim3(threads), fl, st, g->rowptr, g->col, g->info.n, seeds,
                                               n_seeds, tb, tg, (long)sims, (long)sim_offset, T, k0, k1, hist, (int32_t*)nullptr, stats);
-                else hipLaunchKernelGGL((k_sir_frontier<uint16_t, true, false>), dim3(grid), dim3(threads), fl, st, g->rowptr, g->col, g->n, seeds,
+                else hipLaunchKernelGGL((k_sir_frontier<uint16_t, true, false>), dim3(grid), dim3(threads), fl, st, g->rowptr, g->col, g->info.n, seeds,
                                         n_seeds, tb, tg, (long)sims, (long)sim_offset, T, k0, k1, hist, (int32_t*)nullptr, stats);
             } else {
-                const int grid = (int)std::min<int64_t>(std::min<int64_t>(sims, (int64_t)g->num_cu * per_cu), kFrontierGlobalGrid);
-                if (stats) hipLaunchKernelGGL((k_sir_frontier<int32_t, false, true>), dim3(grid), dim3(threads), fl, st, g->rowptr, g->col, g->n, seeds,
+                const int grid = (int)std::min<int64_t>(std::min<int64_t>(sims, (int64_t)g->info.num_cu * per_cu), kFrontierGlobalGrid);
+                if (stats) hipLaunchKernelGGL((k_sir_frontier<int32_t, false, true>), dim3(grid), dim3(threads), fl, st, g->rowptr, g->col, g->info.n, seeds,
                                               n_seeds, tb, tg, (long)sims, (long)sim_offset, T, k0, k1, hist, (int32_t*)gstate, stats);
-                else hipLaunchKernelGGL((k_sir_frontier<int32_t, false, false>), dim3(grid), dim3(threads), fl, st, g->rowptr, g->col, g->n, seeds,
+                else hipLaunchKernelGGL((k_sir_frontier<int32_t, false, false>), dim3(grid), dim3(threads), fl, st, g->rowptr, g->col, g->info.n, seeds,
                                         n_seeds, tb, tg, (long)sims, (long)sim_offset, T, k0, k1, hist, (int32_t*)gstate, stats);
             }
         } else if (lds <= kLdsStateLimit) {
             // edge-parallel scan, node state in LDS: graphs whose frontier lists do not fit (n > ~25k with 32-bit ids)
-            hipLaunchKernelGGL(k_expand_rows, dim3((g->n + 255) / 256), dim3(256), 0, st, g->rowptr, g->n, src);
+            hipLaunchKernelGGL(k_expand_rows, dim3((g->info.n + 255) / 256), dim3(256), 0, st, g->rowptr, g->info.n, src);
             const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / std::max<size_t>(lds, 1)));
             const int threads = per_cu >= 4 ? 256 : (per_cu >= 2 ? 512 : 1024);
-            const int grid = (int)std::min<int64_t>(sims, (int64_t)g->num_cu * per_cu);
-            hipLaunchKernelGGL(k_sir_philox<true>, dim3(grid), dim3(threads), lds, st, src, g->col, (long)g->nnz, g->n, seeds,
+            const int grid = (int)std::min<int64_t>(sims, (int64_t)g->info.num_cu * per_cu);
+            hipLaunchKernelGGL(k_sir_philox<true>, dim3(grid), dim3(threads), lds, st, src, g->col, (long)g->nnz, g->info.n, seeds,
                                n_seeds, tb, tg, (long)sims, (long)sim_offset, T, k0, k1, hist, (uint8_t*)nullptr);
         } else {
-            hipLaunchKernelGGL(k_expand_rows, dim3((g->n + 255) / 256), dim3(256), 0, st, g->rowptr, g->n, src);
+            hipLaunchKernelGGL(k_expand_rows, dim3((g->info.n + 255) / 256), dim3(256), 0, st, g->rowptr, g->info.n, src);
             const int grid = (int)std::min<int64_t>(sims, 2048);
-            hipLaunchKernelGGL(k_sir_philox<false>, dim3(grid), dim3(256), 0, st, src, g->col, (long)g->nnz, g->n, seeds,
+            hipLaunchKernelGGL(k_sir_philox<false>, dim3(grid), dim3(256), 0, st, src, g->col, (long)g->nnz, g->info.n, seeds,
                                n_seeds, tb, tg, (long)sims, (long)sim_offset, T, k0, k1, hist, gstate);
         }
         if (sampled) gn_prof_end(3, st);
         GN_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(k_sir_finalize, dim3((g->n + 255) / 256), dim3(256), 0, st, hist, g->n, T, (uint32_t)sims, counts);
+    hipLaunchKernelGGL(k_sir_finalize, dim3((g->info.n + 255) / 256), dim3(256), 0, st, hist, g->info.n, T, (uint32_t)sims, counts);
     GN_LAUNCH_CHECK();
     return 0;
 }
@@ -603,7 +603,7 @@ extern "C" int gnode_sir_mc_philox_counted(gnode_graph_t g, const int32_t* seeds
     GN_CHECK_ARG(workspace_bytes >= gnode_sir_workspace_bytes(g, T), "gnode_sir_mc_philox_counted: workspace too small");
     // the tally lives in the (otherwise unused by the frontier walk) row-expansion region of the workspace
     char* ws = (char*)workspace;
-    unsigned long long* stats = (unsigned long long*)(ws + gn_align((size_t)2 * T * g->n * sizeof(uint32_t)) + gn_align(4096 * sizeof(int32_t)));
+    unsigned long long* stats = (unsigned long long*)(ws + gn_align((size_t)2 * T * g->info.n * sizeof(uint32_t)) + gn_align(4096 * sizeof(int32_t)));
     GN_CHECK_ARG(g->nnz >= 8, "gnode_sir_mc_philox_counted: graph too small");
     GN_HIP(hipMemsetAsync(stats, 0, 4 * sizeof(unsigned long long), (hipStream_t)stream));
     if (int e = sir_mc_philox_impl(g, seeds_host, n_seeds, beta, gamma, sims, sim_offset, T, rng_seed, counts, workspace,

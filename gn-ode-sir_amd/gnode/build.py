@@ -11,7 +11,7 @@ CSRC = os.path.join(os.path.dirname(PKG), "csrc")
 ROOT = os.path.dirname(os.path.dirname(PKG))
 INCLUDE = os.path.join(ROOT, "include")
 LIB = os.path.join(PKG, "libgnode_hip.so")
-SOURCES = ["gnode_ode.hip", "gnode_h64.hip", "gnode_pers64.hip", "gnode_pers64_bwd.hip", "gnode_persg.hip", "gnode_h128.hip", "gnode_bwd.hip", "gnode_bwd_tiny.hip", "gnode_hub.hip", "gnode_sir.hip", "gnode_dmp.hip", "gnode_meanfield.hip", "gnode_loss.hip", "gnode_rhs_vjp.hip"]
+SOURCES = ["gnode_graph_plan.cpp", "gnode_ode.hip", "gnode_h64.hip", "gnode_pers64.hip", "gnode_pers64_bwd.hip", "gnode_persg.hip", "gnode_h128.hip", "gnode_bwd.hip", "gnode_bwd_tiny.hip", "gnode_hub.hip", "gnode_sir.hip", "gnode_dmp.hip", "gnode_meanfield.hip", "gnode_loss.hip", "gnode_rhs_vjp.hip"]
 # -ffp-contract=off: the SIR update must round like the reference's separate torch ops
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-I" + INCLUDE, "-I" + CSRC]
 
@@ -38,7 +38,7 @@ def build_lib(force: bool = False, verbose: bool = False) -> str:
     from concurrent.futures import ThreadPoolExecutor
 
     def compile_one(src):
-        obj = os.path.join(CSRC, src.replace(".hip", ".o"))
+        obj = os.path.join(CSRC, os.path.splitext(src)[0] + ".o")
         cmd = [hipcc, *FLAGS, *os.environ.get("GNODE_EXTRA_FLAGS", "").split(), "-c", os.path.join(CSRC, src), "-o", obj]
         if verbose:
             print(" ".join(cmd), file=sys.stderr)

@@ -137,7 +137,7 @@ def test_multi_adjoint_equals_batched_single_graph():
 # ---- sensitivity: each fault must move the oracle outside the GPU tolerance
 def test_dropped_hub_segment_is_caught():
     """wiki-vote's 1 065-edge row loses its last 32-edge segment (the kernels cut hub rows into segments of <= 32 edges,
-    in order: gnode_hub.hip gn_hub_build) -- what a lost segment in k_hub_seg or a persistent kernel's hub path would do.
+    in order: csrc/gnode_graph_plan.cpp) -- what a lost segment in k_hub_seg or a persistent kernel's hub path would do.
     The kept outputs catch it by orders of magnitude; the summed parameter gradients alone move by about half their
     tolerance (one row of 7 066), so the outputs are the check that holds this fault."""
     gs = _graphs()

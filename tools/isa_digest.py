@@ -44,7 +44,8 @@ def digests(text):
     return [(n, hashlib.sha256("\n".join(bodies[n] + ["--"] + desc.get(n, [])).encode()).hexdigest()[:16]) for n in order]
 
 
-with ThreadPoolExecutor(max_workers=min(16, len(build.SOURCES))) as pool:
-    for src, text in zip(build.SOURCES, pool.map(assembly, build.SOURCES)):
+HIP_SOURCES = [s for s in build.SOURCES if s.endswith(".hip")]      # (the .cpp units are host code: no device assembly)
+with ThreadPoolExecutor(max_workers=min(16, len(HIP_SOURCES))) as pool:
+    for src, text in zip(HIP_SOURCES, pool.map(assembly, HIP_SOURCES)):
         for name, d in digests(text):
             print(f"{src} {name} {d}")
