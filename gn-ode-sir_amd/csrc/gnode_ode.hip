@@ -65,7 +65,7 @@ int gn_zero_regions_async(const GnZeroRegions& r, hipStream_t st) {
     GN_LAUNCH_CHECK();
     return 0;
 }
-extern "C" int gnode_version(void) { return 225; }   // 225: gnode_backward_discrete_keep_f32, gnode_backward_discrete_path; 224: gnode_backward_discrete_f32; 223: gnode_backward_dx_f32, gnode_backward_rk4_dx_f32; 222: gnode_rhs_vjp_f32, gnode_backward_rk4_f32; 221: gnode_backward_status, persistent launches for hidden 8 / 16 / 32 (gnode_forward_path kind 3); 220: forward takes flags + reports what sol / keep carry (sol_info), backward checks it; persistent one-launch path for mid-size graphs; 200: workspace sizes take the graph handle (hub scratch is carved from the caller's workspace); 210: forward / backward take the optional kept-activation buffer
+extern "C" int gnode_version(void) { return 226; }   // 226: gnode_sir_mc_philox_nodes, gnode_sir_nodes_workspace_bytes; 225: gnode_backward_discrete_keep_f32, gnode_backward_discrete_path; 224: gnode_backward_discrete_f32; 223: gnode_backward_dx_f32, gnode_backward_rk4_dx_f32; 222: gnode_rhs_vjp_f32, gnode_backward_rk4_f32; 221: gnode_backward_status, persistent launches for hidden 8 / 16 / 32 (gnode_forward_path kind 3); 220: forward takes flags + reports what sol / keep carry (sol_info), backward checks it; persistent one-launch path for mid-size graphs; 200: workspace sizes take the graph handle (hub scratch is carved from the caller's workspace); 210: forward / backward take the optional kept-activation buffer
 
 // --------------------------------------------------------------------------- instrumentation
 // HIP-event pairs around every launch of the two step kernels while enabled

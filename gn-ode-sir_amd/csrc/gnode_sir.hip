@@ -18,8 +18,14 @@
 // is integer, results are bit-exact against the edge-scan statement of the same model (oracle: sir_philox; the
 // edge-parallel kernel k_sir_philox below remains for graphs whose lists do not fit and as the in-library
 // cross-check of the tests).
+//
+// Per-node rates (gnode_sir_mc_philox_nodes, the NODES instances): the entry (u -> v) fires against the threshold of
+// its TARGET v (the GN-ODE's convention: row v's dS_v = -beta_v (A Z_I)_v Z_S,v) and node u recovers against its own.
+// Same coins, same 64-bit compare: constant arrays give the scalar call's counts.
 #include "gnode_common.h"
 #include <algorithm>
+#include <type_traits>
+#include <vector>
 
 enum : uint8_t { ST_S = 0, ST_I = 1, ST_R = 2 };
 
@@ -44,15 +50,24 @@ __device__ __forceinline__ uint32_t philox_coin(uint32_t pos, uint32_t it, uint3
     return j == 0 ? w[0] : j == 1 ? w[1] : j == 2 ? w[2] : w[3];
 }
 
+// --------------------------------------------------------------------------- coin thresholds
+// A coin fires iff (64-bit) word < thr, thr = floor(p * 2^32) in [0, 2^32].  Scalar instances carry the two thresholds
+// as kernel arguments; the NODES instances read thr[v] from two uint64 [n] arrays in memory (staged by the host, L2
+// resident).  uint64 because 2^32 + 1 thresholds do not fit 32 bits and p = 1 must always fire: stored whole, the test
+// is the scalar one, with nothing to decode.
+template <bool NODES> using SirThr = std::conditional_t<NODES, const unsigned long long*, unsigned long long>;
+__device__ __forceinline__ unsigned long long sir_thr(unsigned long long t, int) { return t; }
+__device__ __forceinline__ unsigned long long sir_thr(const unsigned long long* t, int v) { return t[v]; }
+
 // --------------------------------------------------------------------------- production kernel
 // hist: uint32 [2][T][n]: [0] = infection events (t = 0 for seeds), [1] = recovery events.
 #ifndef GN_SIR_UNROLL
 #define GN_SIR_UNROLL 8
 #endif
-template <bool STATE_IN_LDS>
+template <bool STATE_IN_LDS, bool NODES>
 __global__ __launch_bounds__(1024) void k_sir_philox(const int* __restrict__ src, const int* __restrict__ dst, long nnz,
                                                     int n, const int* __restrict__ seeds, int n_seeds,
-                                                    unsigned long long thr_beta, unsigned long long thr_gamma,
+                                                    SirThr<NODES> thr_beta, SirThr<NODES> thr_gamma,
                                                     long sims, long sim_offset, int T, uint32_t k0, uint32_t k1,
                                                     uint32_t* __restrict__ hist, uint8_t* __restrict__ gstate) {
     extern __shared__ uint8_t smem[];
@@ -84,7 +99,7 @@ __global__ __launch_bounds__(1024) void k_sir_philox(const int* __restrict__ src
                 if (ON) {                                                                                     \
                     const int v = dst[E];                                                                     \
                     if (state[v] == ST_S &&                                                                   \
-                        (unsigned long long)philox_coin((uint32_t)(E), (uint32_t)it, sim, 0u, k0, k1) < thr_beta) \
+                        (unsigned long long)philox_coin((uint32_t)(E), (uint32_t)it, sim, 0u, k0, k1) < sir_thr(thr_beta, v)) \
                         flag[v] = 1;                                                                          \
                 }
             long e = threadIdx.x;
@@ -104,7 +119,7 @@ __global__ __launch_bounds__(1024) void k_sir_philox(const int* __restrict__ src
 #undef GN_EDGE
             for (int u = threadIdx.x; u < n; u += nthr)
                 if (state[u] == ST_I &&
-                    (unsigned long long)philox_coin((uint32_t)u, (uint32_t)it, sim, 1u, k0, k1) < thr_gamma)
+                    (unsigned long long)philox_coin((uint32_t)u, (uint32_t)it, sim, 1u, k0, k1) < sir_thr(thr_gamma, u))
                     flag[u] = 2;
             __syncthreads();
             int any = 0;
@@ -127,10 +142,12 @@ __global__ __launch_bounds__(1024) void k_sir_philox(const int* __restrict__ src
 // one lane group.  Larger graphs keep the three lists in the caller's workspace (int32 ids, one set per workgroup).
 // GN_SIR_BIGROW (gnode_common.h): rows longer than this are walked by the whole workgroup
 // COUNT: the profiling instantiation (gnode_sir_mc_philox_counted) also tallies Philox blocks, coins and CSR entries read.
-template <typename IdT, bool LISTS_IN_LDS, bool COUNT>
+// NODES: per-node thresholds.  A target's threshold is read only where a coin is drawn -- in `drain`, for the (position,
+// target) pairs that passed the ever-infected test -- and the read is issued ahead of the coin's Philox rounds.
+template <typename IdT, bool LISTS_IN_LDS, bool COUNT, bool NODES>
 __global__ __launch_bounds__(1024) void k_sir_frontier(const int* __restrict__ rowptr, const int* __restrict__ col, int n,
                                                       const int* __restrict__ seeds, int n_seeds,
-                                                      unsigned long long thr_beta, unsigned long long thr_gamma,
+                                                      SirThr<NODES> thr_beta, SirThr<NODES> thr_gamma,
                                                       long sims, long sim_offset, int T, uint32_t k0, uint32_t k1,
                                                       uint32_t* __restrict__ hist, int32_t* __restrict__ glists,
                                                       unsigned long long* __restrict__ stats) {
@@ -192,7 +209,7 @@ __global__ __launch_bounds__(1024) void k_sir_frontier(const int* __restrict__ r
 #pragma unroll
                     for (int j = 0; j < 4; ++j)
                         if ((nib >> j) & 1u) {
-                            if ((unsigned long long)w[j] < thr_gamma) { gone |= 1u << j; atomicAdd(&hrec[(size_t)it * n + u0 + j], 1u); }
+                            if ((unsigned long long)w[j] < sir_thr(thr_gamma, u0 + j)) { gone |= 1u << j; atomicAdd(&hrec[(size_t)it * n + u0 + j], 1u); }
                             else ++alive;
                         }
                     if (gone) atomicOr(&recb[u0 >> 5], gone << (u0 & 31));
@@ -226,7 +243,8 @@ __global__ __launch_bounds__(1024) void k_sir_frontier(const int* __restrict__ r
                 if (lane_in_wave < take) {
                     const int e = cq[slot], v = cq[128 + slot];
                     if (COUNT) { ++st_blocks; ++st_ecoins; }
-                    if ((unsigned long long)philox_coin((uint32_t)e, (uint32_t)it, sim, 0u, k0, k1) < thr_beta) infect(v);
+                    const unsigned long long tb = sir_thr(thr_beta, v);
+                    if ((unsigned long long)philox_coin((uint32_t)e, (uint32_t)it, sim, 0u, k0, k1) < tb) infect(v);
                 }
                 qn -= take;
             };
@@ -296,7 +314,8 @@ __global__ __launch_bounds__(1024) void k_sir_frontier(const int* __restrict__ r
             for (int idx = tid; idx < n_inf; idx += nthr) {
                 const int u = (int)cur[idx];
                 if (COUNT) { ++st_blocks; ++st_rcoins; }
-                const bool gone = (unsigned long long)philox_coin((uint32_t)u, (uint32_t)it, sim, 1u, k0, k1) < thr_gamma;
+                const unsigned long long tg = sir_thr(thr_gamma, u);
+                const bool gone = (unsigned long long)philox_coin((uint32_t)u, (uint32_t)it, sim, 1u, k0, k1) < tg;
                 if (gone) {
                     atomicAdd(&hrec[(size_t)it * n + u], 1u);
                     atomicOr(&recb[u >> 5], 1u << (u & 31));
@@ -482,11 +501,14 @@ static int frontier_threads(int n, int n_big, int* per_cu_out) {
 static const int kFrontierGlobalGrid = 1024;       // workgroups that own a set of global lists (graphs past the LDS form)
 
 int gn_sir_set_attributes() {       // once per device, from gnode_graph_create
-    GN_HIP(hipFuncSetAttribute((const void*)k_sir_frontier<uint16_t, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
-    GN_HIP(hipFuncSetAttribute((const void*)k_sir_frontier<int32_t, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
-    GN_HIP(hipFuncSetAttribute((const void*)k_sir_frontier<uint16_t, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
-    GN_HIP(hipFuncSetAttribute((const void*)k_sir_frontier<int32_t, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
-    GN_HIP(hipFuncSetAttribute((const void*)k_sir_philox<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
+    GN_HIP(hipFuncSetAttribute((const void*)k_sir_frontier<uint16_t, true, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
+    GN_HIP(hipFuncSetAttribute((const void*)k_sir_frontier<int32_t, false, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
+    GN_HIP(hipFuncSetAttribute((const void*)k_sir_frontier<uint16_t, true, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
+    GN_HIP(hipFuncSetAttribute((const void*)k_sir_frontier<int32_t, false, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
+    GN_HIP(hipFuncSetAttribute((const void*)k_sir_frontier<uint16_t, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
+    GN_HIP(hipFuncSetAttribute((const void*)k_sir_frontier<int32_t, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
+    GN_HIP(hipFuncSetAttribute((const void*)k_sir_philox<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
+    GN_HIP(hipFuncSetAttribute((const void*)k_sir_philox<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
     GN_HIP(hipFuncSetAttribute((const void*)k_sir_coins, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
     return 0;
 }
@@ -503,23 +525,51 @@ extern "C" size_t gnode_sir_workspace_bytes(gnode_graph_t g, int32_t T) {
     return b + gn_align(tail);
 }
 
+// per-node form: the layout above, then the thresholds -- uint64 [n] for beta, uint64 [n] for gamma
+static size_t sir_thr_bytes(int n) { return gn_align((size_t)2 * n * sizeof(unsigned long long)); }
+extern "C" size_t gnode_sir_nodes_workspace_bytes(gnode_graph_t g, int32_t T) {
+    return g ? gnode_sir_workspace_bytes(g, T) + sir_thr_bytes(g->info.n) : 0;
+}
+
+static unsigned long long coin_threshold(double p) {
+    return (unsigned long long)std::min(4294967296.0, std::max(0.0, std::floor(p * 4294967296.0)));
+}
+
+// beta_nodes / gamma_nodes: host fp64 [n] each, or both null (then the scalars beta / gamma hold for every node)
 static int sir_mc_philox_impl(gnode_graph_t g, const int32_t* seeds_host, int32_t n_seeds, double beta,
                               double gamma, int64_t sims, int64_t sim_offset, int32_t T, uint64_t rng_seed,
                               uint32_t* counts, void* workspace, size_t workspace_bytes, void* stream, bool edge_scan,
-                              unsigned long long* stats = nullptr /* device [4]: the counting instantiation, or null */) {
+                              unsigned long long* stats = nullptr /* device [4]: the counting instantiation, or null */,
+                              const double* beta_nodes = nullptr, const double* gamma_nodes = nullptr) {
     GN_CHECK_ARG(g && counts && workspace, "gnode_sir_mc_philox: null pointer");
+    const bool nodes = beta_nodes || gamma_nodes;
+    GN_CHECK_ARG(!nodes || (beta_nodes && gamma_nodes && !stats), "gnode_sir_mc_philox_nodes: null rate array");
     GN_CHECK_ARG(n_seeds >= 0 && n_seeds <= 4096 && (seeds_host || n_seeds == 0), "gnode_sir_mc_philox: 0..4096 seeds");
     GN_CHECK_ARG(T >= 1 && sims >= 0 && sims <= 0xFFFFFFFFll && sim_offset >= 0 && sim_offset + sims <= 0xFFFFFFFFll,
                  "gnode_sir_mc_philox: bad T/sims/sim_offset");
     GN_CHECK_ARG(beta >= 0.0 && beta <= 1.0 && gamma >= 0.0 && gamma <= 1.0, "gnode_sir_mc_philox: beta, gamma in [0,1]");
     for (int i = 0; i < n_seeds; ++i)
         GN_CHECK_ARG(seeds_host[i] >= 0 && seeds_host[i] < g->info.n, "gnode_sir_mc_philox: seed %d out of range", seeds_host[i]);
-    if (workspace_bytes < gnode_sir_workspace_bytes(g, T)) {
-        gnode_set_error("gnode_sir_mc_philox: workspace %zu < %zu", workspace_bytes, gnode_sir_workspace_bytes(g, T));
+    const size_t ws_need = nodes ? gnode_sir_nodes_workspace_bytes(g, T) : gnode_sir_workspace_bytes(g, T);
+    if (workspace_bytes < ws_need) {
+        gnode_set_error("gnode_sir_mc_philox: workspace %zu < %zu", workspace_bytes, ws_need);
         return GNODE_ERR_WORKSPACE;
+    }
+    std::vector<unsigned long long> thr_host;              // [beta thresholds | gamma thresholds]
+    if (nodes) {
+        const int n = g->info.n;
+        thr_host.resize((size_t)2 * n);
+        for (int v = 0; v < n; ++v) {                      // (a NaN fails both comparisons)
+            GN_CHECK_ARG(beta_nodes[v] >= 0.0 && beta_nodes[v] <= 1.0, "gnode_sir_mc_philox_nodes: beta[%d] = %g is not in [0,1]", v, beta_nodes[v]);
+            GN_CHECK_ARG(gamma_nodes[v] >= 0.0 && gamma_nodes[v] <= 1.0, "gnode_sir_mc_philox_nodes: gamma[%d] = %g is not in [0,1]", v, gamma_nodes[v]);
+            thr_host[v] = coin_threshold(beta_nodes[v]);
+            thr_host[(size_t)n + v] = coin_threshold(gamma_nodes[v]);
+        }
     }
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace;
+    const unsigned long long* thr_b = (const unsigned long long*)(ws + gnode_sir_workspace_bytes(g, T));   // used when `nodes`
+    const unsigned long long* thr_g = thr_b + g->info.n;
     const size_t hist_b = gn_align((size_t)2 * T * g->info.n * sizeof(uint32_t));
     uint32_t* hist = (uint32_t*)ws;
     int32_t* seeds = (int32_t*)(ws + hist_b);
@@ -537,10 +587,10 @@ static int sir_mc_philox_impl(gnode_graph_t g, const int32_t* seeds_host, int32_
         GN_LAUNCH_CHECK();
     } else {
         GN_HIP(hipMemcpyAsync(seeds, seeds_host, sizeof(int32_t) * n_seeds, hipMemcpyHostToDevice, st));
-        GN_HIP(hipStreamSynchronize(st));
     }
-    const unsigned long long tb = (unsigned long long)std::min(4294967296.0, std::max(0.0, std::floor(beta * 4294967296.0)));
-    const unsigned long long tg = (unsigned long long)std::min(4294967296.0, std::max(0.0, std::floor(gamma * 4294967296.0)));
+    if (nodes) GN_HIP(hipMemcpyAsync((void*)thr_b, thr_host.data(), thr_host.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, st));
+    if (n_seeds > 32 || nodes) GN_HIP(hipStreamSynchronize(st));     // the host arrays are done with
+    const unsigned long long tb = coin_threshold(beta), tg = coin_threshold(gamma);
     const uint32_t k0 = (uint32_t)(rng_seed & 0xFFFFFFFFull), k1 = (uint32_t)(rng_seed >> 32);
     if (sims > 0) {
         const bool sampled = gn_prof_begin(3, st);
@@ -548,36 +598,49 @@ static int sir_mc_philox_impl(gnode_graph_t g, const int32_t* seeds_host, int32_
         const int threads_f = frontier_threads(g->info.n, g->n_bigrow, &per_cu_f);
         const size_t fl = frontier_lds_bytes(g->info.n, g->n_bigrow, threads_f);
         const size_t lds = (size_t)2 * g->info.n;
-        if (fl <= kLdsStateLimit && !edge_scan) {
-            // frontier-driven walk.  Workgroups per CU by LDS, at least 16 waves per CU
-            const int per_cu = per_cu_f, threads = threads_f;
-            if (frontier_lists_in_lds(g->info.n, g->n_bigrow)) {
+        // one path selection and launch geometry for both forms: `nodes_tag` picks the kernels' NODES instances, whose
+        // thresholds tb_ / tg_ are the staged arrays instead of the two numbers
+        auto launch = [&](auto nodes_tag, auto tb_, auto tg_) {
+            constexpr bool NODES = decltype(nodes_tag)::value;
+            if (fl <= kLdsStateLimit && !edge_scan) {
+                // frontier-driven walk.  Workgroups per CU by LDS, at least 16 waves per CU
+                const int per_cu = per_cu_f, threads = threads_f;
+                if (frontier_lists_in_lds(g->info.n, g->n_bigrow)) {
+                    const int grid = (int)std::min<int64_t>(sims, (int64_t)g->info.num_cu * per_cu);
+                    if constexpr (!NODES) if (stats) {
+                        hipLaunchKernelGGL((k_sir_frontier<uint16_t, true, true, false>), dim3(grid), dim3(threads), fl, st, g->rowptr, g->col, g->info.n, seeds,
+                                           n_seeds, tb_, tg_, (long)sims, (long)sim_offset, T, k0, k1, hist, (int32_t*)nullptr, stats);
+                        return;
+                    }
+                    hipLaunchKernelGGL((k_sir_frontier<uint16_t, true, false, NODES>), dim3(grid), dim3(threads), fl, st, g->rowptr, g->col, g->info.n, seeds,
+                                       n_seeds, tb_, tg_, (long)sims, (long)sim_offset, T, k0, k1, hist, (int32_t*)nullptr, stats);
+                } else {
+                    const int grid = (int)std::min<int64_t>(std::min<int64_t>(sims, (int64_t)g->info.num_cu * per_cu), kFrontierGlobalGrid);
+                    if constexpr (!NODES) if (stats) {
+                        hipLaunchKernelGGL((k_sir_frontier<int32_t, false, true, false>), dim3(grid), dim3(threads), fl, st, g->rowptr, g->col, g->info.n, seeds,
+                                           n_seeds, tb_, tg_, (long)sims, (long)sim_offset, T, k0, k1, hist, (int32_t*)gstate, stats);
+                        return;
+                    }
+                    hipLaunchKernelGGL((k_sir_frontier<int32_t, false, false, NODES>), dim3(grid), dim3(threads), fl, st, g->rowptr, g->col, g->info.n, seeds,
+                                       n_seeds, tb_, tg_, (long)sims, (long)sim_offset, T, k0, k1, hist, (int32_t*)gstate, stats);
+                }
+            } else if (lds <= kLdsStateLimit) {
+                // edge-parallel scan, node state in LDS: graphs whose frontier lists do not fit (n > ~25k with 32-bit ids)
+                hipLaunchKernelGGL(k_expand_rows, dim3((g->info.n + 255) / 256), dim3(256), 0, st, g->rowptr, g->info.n, src);
+                const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / std::max<size_t>(lds, 1)));
+                const int threads = per_cu >= 4 ? 256 : (per_cu >= 2 ? 512 : 1024);
                 const int grid = (int)std::min<int64_t>(sims, (int64_t)g->info.num_cu * per_cu);
-                if (stats) hipLaunchKernelGGL((k_sir_frontier<uint16_t, true, true>), dim3(grid), dim3(threads), fl, st, g->rowptr, g->col, g->info.n, seeds,
-                                              n_seeds, tb, tg, (long)sims, (long)sim_offset, T, k0, k1, hist, (int32_t*)nullptr, stats);
-                else hipLaunchKernelGGL((k_sir_frontier<uint16_t, true, false>), dim3(grid), dim3(threads), fl, st, g->rowptr, g->col, g->info.n, seeds,
-                                        n_seeds, tb, tg, (long)sims, (long)sim_offset, T, k0, k1, hist, (int32_t*)nullptr, stats);
+                hipLaunchKernelGGL((k_sir_philox<true, NODES>), dim3(grid), dim3(threads), lds, st, src, g->col, (long)g->nnz, g->info.n, seeds,
+                                   n_seeds, tb_, tg_, (long)sims, (long)sim_offset, T, k0, k1, hist, (uint8_t*)nullptr);
             } else {
-                const int grid = (int)std::min<int64_t>(std::min<int64_t>(sims, (int64_t)g->info.num_cu * per_cu), kFrontierGlobalGrid);
-                if (stats) hipLaunchKernelGGL((k_sir_frontier<int32_t, false, true>), dim3(grid), dim3(threads), fl, st, g->rowptr, g->col, g->info.n, seeds,
-                                              n_seeds, tb, tg, (long)sims, (long)sim_offset, T, k0, k1, hist, (int32_t*)gstate, stats);
-                else hipLaunchKernelGGL((k_sir_frontier<int32_t, false, false>), dim3(grid), dim3(threads), fl, st, g->rowptr, g->col, g->info.n, seeds,
-                                        n_seeds, tb, tg, (long)sims, (long)sim_offset, T, k0, k1, hist, (int32_t*)gstate, stats);
+                hipLaunchKernelGGL(k_expand_rows, dim3((g->info.n + 255) / 256), dim3(256), 0, st, g->rowptr, g->info.n, src);
+                const int grid = (int)std::min<int64_t>(sims, 2048);
+                hipLaunchKernelGGL((k_sir_philox<false, NODES>), dim3(grid), dim3(256), 0, st, src, g->col, (long)g->nnz, g->info.n, seeds,
+                                   n_seeds, tb_, tg_, (long)sims, (long)sim_offset, T, k0, k1, hist, gstate);
             }
-        } else if (lds <= kLdsStateLimit) {
-            // edge-parallel scan, node state in LDS: graphs whose frontier lists do not fit (n > ~25k with 32-bit ids)
-            hipLaunchKernelGGL(k_expand_rows, dim3((g->info.n + 255) / 256), dim3(256), 0, st, g->rowptr, g->info.n, src);
-            const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / std::max<size_t>(lds, 1)));
-            const int threads = per_cu >= 4 ? 256 : (per_cu >= 2 ? 512 : 1024);
-            const int grid = (int)std::min<int64_t>(sims, (int64_t)g->info.num_cu * per_cu);
-            hipLaunchKernelGGL(k_sir_philox<true>, dim3(grid), dim3(threads), lds, st, src, g->col, (long)g->nnz, g->info.n, seeds,
-                               n_seeds, tb, tg, (long)sims, (long)sim_offset, T, k0, k1, hist, (uint8_t*)nullptr);
-        } else {
-            hipLaunchKernelGGL(k_expand_rows, dim3((g->info.n + 255) / 256), dim3(256), 0, st, g->rowptr, g->info.n, src);
-            const int grid = (int)std::min<int64_t>(sims, 2048);
-            hipLaunchKernelGGL(k_sir_philox<false>, dim3(grid), dim3(256), 0, st, src, g->col, (long)g->nnz, g->info.n, seeds,
-                               n_seeds, tb, tg, (long)sims, (long)sim_offset, T, k0, k1, hist, gstate);
-        }
+        };
+        if (nodes) launch(std::true_type{}, thr_b, thr_g);
+        else launch(std::false_type{}, tb, tg);
         if (sampled) gn_prof_end(3, st);
         GN_LAUNCH_CHECK();
     }
@@ -619,6 +682,17 @@ extern "C" int gnode_sir_mc_philox_scan(gnode_graph_t g, const int32_t* seeds_ho
                                         uint32_t* counts, void* workspace, size_t workspace_bytes, void* stream) {
     return sir_mc_philox_impl(g, seeds_host, n_seeds, beta, gamma, sims, sim_offset, T, rng_seed, counts, workspace,
                               workspace_bytes, stream, true);
+}
+
+// Per-node rates: beta_host[v] is the probability that an entry (u -> v) with u infected infects the susceptible v,
+// gamma_host[u] that the infected u recovers.  Validated here, turned into thresholds by the scalar path's expression and
+// staged through the workspace; synchronises `stream`.  edge_scan != 0: the scan kernel (the cross-check).
+extern "C" int gnode_sir_mc_philox_nodes(gnode_graph_t g, const int32_t* seeds_host, int32_t n_seeds, const double* beta_host,
+                                         const double* gamma_host, int64_t sims, int64_t sim_offset, int32_t T, uint64_t rng_seed,
+                                         uint32_t* counts, void* workspace, size_t workspace_bytes, void* stream, int32_t edge_scan) {
+    GN_CHECK_ARG(beta_host && gamma_host, "gnode_sir_mc_philox_nodes: null rate array");
+    return sir_mc_philox_impl(g, seeds_host, n_seeds, 0.0, 0.0, sims, sim_offset, T, rng_seed, counts, workspace,
+                              workspace_bytes, stream, edge_scan != 0, nullptr, beta_host, gamma_host);
 }
 
 extern "C" int gnode_sir_mc_coins(const int32_t* table_src, const int32_t* table_dst, int64_t n_table, int32_t n,

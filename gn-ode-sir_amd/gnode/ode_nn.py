@@ -56,14 +56,35 @@ def _device_graph_for(G):
     return dg
 
 
-def _philox_launch(entry: str, graph: DeviceGraph, seed_set, beta, gamma, sims, T, rng_seed, sim_offset, device, counts, *extra):
-    """One launch of a gnode_sir_mc_philox* entry into `counts` (zeros [3, T, n] on `device` when None); returns counts."""
+def _node_rates(name: str, value, n: int):
+    """None when `value` is a scalar rate; else the validated per-node rates as a contiguous float64 [n] host array
+    (from a numpy array, a list or a torch tensor on any device).  Raises ValueError before any library call."""
+    if isinstance(value, torch.Tensor):
+        if value.ndim == 0:
+            return None
+        value = value.detach().cpu().numpy()
+    a = np.asarray(value, dtype=np.float64)
+    if a.ndim == 0:
+        return None
+    if a.shape != (n,):
+        raise ValueError(f"{name}: per-node rates must have shape ({n},), got {tuple(a.shape)}")
+    bad = np.flatnonzero(~((a >= 0.0) & (a <= 1.0)))            # a NaN fails both comparisons
+    if bad.size:
+        raise ValueError(f"{name}[{int(bad[0])}] = {a[bad[0]]} is not a probability in [0, 1]")
+    return np.ascontiguousarray(a)
+
+
+def _philox_launch(entry: str, graph: DeviceGraph, seed_set, beta, gamma, sims, T, rng_seed, sim_offset, device, counts, *extra,
+                   ws_entry: str = "gnode_sir_workspace_bytes"):
+    """One launch of a gnode_sir_mc_philox* entry into `counts` (zeros [3, T, n] on `device` when None); returns counts.
+    beta / gamma: numbers, or (gnode_sir_mc_philox_nodes) float64 [n] host arrays."""
     lib = _lib.load()
     seeds = np.ascontiguousarray(list(seed_set), dtype=np.int32)
     if counts is None:
         counts = torch.zeros((3, T, graph.n), dtype=torch.int32, device=device)
-    ws = torch.empty(lib.gnode_sir_workspace_bytes(graph.handle, T), dtype=torch.uint8, device=counts.device)
-    _lib.check(getattr(lib, entry)(graph.handle, _lib.host_ptr(seeds), int(seeds.shape[0]), float(beta), float(gamma),
+    ws = torch.empty(getattr(lib, ws_entry)(graph.handle, T), dtype=torch.uint8, device=counts.device)
+    rate = lambda r: _lib.host_ptr(r) if isinstance(r, np.ndarray) and r.ndim == 1 else float(r)
+    _lib.check(getattr(lib, entry)(graph.handle, _lib.host_ptr(seeds), int(seeds.shape[0]), rate(beta), rate(gamma),
                                    int(sims), int(sim_offset), int(T), C.c_uint64(int(rng_seed) & (2**64 - 1)),
                                    _lib.ptr(counts), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(), *extra))
     return counts
@@ -74,7 +95,19 @@ def sir_counts(graph: DeviceGraph, seed_set, beta, gamma, sims, T, rng_seed, sim
     """Production Monte-Carlo on the GPU: uint32 (stored as int32 tensor) counts [3, T, n].
 
     `counts` may be passed to accumulate several shards of the sims range into one array.  edge_scan=True runs the
-    edge-parallel statement of the same model (`gnode_sir_mc_philox_scan`: identical counts, O(nnz) per step)."""
+    edge-parallel statement of the same model (`gnode_sir_mc_philox_scan`: identical counts, O(nnz) per step).
+
+    beta and gamma are, independently, one number for the graph or per-node rates of length graph.n (numpy array, list,
+    torch tensor): beta[v] is the probability that an infected neighbour infects the susceptible v in a step (indexed by
+    the target, as x[:, 3] of the GN-ODE), gamma[u] that the infected u recovers.  Two numbers take the scalar entry as
+    before; anything else goes through `gnode_sir_mc_philox_nodes` (same coins: constant arrays give the scalar counts),
+    which synchronises the stream.  A wrong length, a NaN or a value outside [0, 1] raises ValueError."""
+    b, g = _node_rates("beta", beta, graph.n), _node_rates("gamma", gamma, graph.n)
+    if b is not None or g is not None:
+        b = _node_rates("beta", np.full(graph.n, float(beta)), graph.n) if b is None else b
+        g = _node_rates("gamma", np.full(graph.n, float(gamma)), graph.n) if g is None else g
+        return _philox_launch("gnode_sir_mc_philox_nodes", graph, seed_set, b, g, sims, T, rng_seed, sim_offset, device, counts,
+                              int(bool(edge_scan)), ws_entry="gnode_sir_nodes_workspace_bytes")
     return _philox_launch("gnode_sir_mc_philox_scan" if edge_scan else "gnode_sir_mc_philox", graph, seed_set, beta, gamma,
                           sims, T, rng_seed, sim_offset, device, counts)
 
@@ -127,9 +160,14 @@ def sir_torch(G, seed_set, beta, gamma, sims=10000, T=20, rng_seed=None, coins=N
     (:55-56) instead of accumulating it, so after the caller's `/sims` that row reads 1/sims, not 1 (the loss
     skips t = 0, so it is invisible there).  False (default) reproduces the reference's counts exactly;
     True scales row 0 by `sims` so that counts/sims is the initial state itself.
+
+    Per-node rates (extension): in production mode beta and gamma may each be an array of length n indexed by node id
+    (see `sir_counts`).  The recorded-stream parity mode takes numbers only.
     """
     n = G.number_of_nodes()
     if coins is not None:
+        if _node_rates("beta", beta, n) is not None or _node_rates("gamma", gamma, n) is not None:
+            raise ValueError("sir_torch(coins=...): the parity mode takes scalar beta and gamma, not per-node arrays")
         e = _edge_arrays(G)
         table = np.empty((2 * e.shape[0], 2), dtype=np.int64)     # reference :32-38
         table[0::2, 0], table[0::2, 1] = e[:, 0], e[:, 1]

@@ -20,7 +20,7 @@
  *     into a hipGraph on first use and one handle may serve several streams (each
  *     with its own workspace).  Functions that DO synchronise `stream` say so below
  *     (gnode_graph_create, gnode_sir_mc_philox with more than 32 seeds,
- *     gnode_sir_mc_coins, gnode_dmp_f32, gnode_meanfield_f64).
+ *     gnode_sir_mc_philox_nodes, gnode_sir_mc_coins, gnode_dmp_f32, gnode_meanfield_f64).
  *   - process-wide state: (1) a per-device "set up once" table (compute-unit count,
  *     dynamic-LDS kernel attributes), written under a lock by the first
  *     gnode_graph_create on a device and read-only afterwards; (2) the opt-in
@@ -352,6 +352,21 @@ int gnode_sir_mc_philox_scan(gnode_graph_t g, const int32_t* seeds_host, int32_t
 int gnode_sir_mc_philox_counted(gnode_graph_t g, const int32_t* seeds_host, int32_t n_seeds, double beta, double gamma,
                                 int64_t sims, int64_t sim_offset, int32_t T, uint64_t rng_seed, uint32_t* counts,
                                 void* workspace, size_t workspace_bytes, void* stream, uint64_t* stats_host);
+/* Per-node rates (ABI 226): the same model, coins and counts with a rate per node instead of one for the graph.
+ *   beta_host   host fp64 [n]   a directed CSR entry (u -> v), u infected and v susceptible in the pre-step state, fires iff
+ *                               coin(entry) < thr(beta_host[v]): indexed by the TARGET, the GN-ODE's convention for x[:, 3]
+ *                               (row v's dS_v = -beta_v (A Z_I)_v Z_S,v)
+ *   gamma_host  host fp64 [n]   the infected node u recovers iff coin(u) < thr(gamma_host[u])
+ * thr(p) = floor(p * 2^32) in [0, 2^32], compared in 64 bits: p = 0 never fires, p = 1 always does.  Arrays that hold one
+ * constant each give gnode_sir_mc_philox's counts exactly.  Every entry is validated on the host (a NaN or a value
+ * outside [0, 1]: GNODE_ERR_ARG, the message names the index); the thresholds are staged through the workspace, whose
+ * layout is gnode_sir_mc_philox's followed by them.  Synchronises `stream`.  edge_scan != 0 runs the edge-parallel
+ * statement where the frontier walk would apply (what gnode_sir_mc_philox_scan is to gnode_sir_mc_philox). */
+size_t gnode_sir_nodes_workspace_bytes(gnode_graph_t g, int32_t T);
+int gnode_sir_mc_philox_nodes(gnode_graph_t g, const int32_t* seeds_host, int32_t n_seeds,
+                              const double* beta_host, const double* gamma_host,   /* host fp64 [n] each */
+                              int64_t sims, int64_t sim_offset, int32_t T, uint64_t rng_seed, uint32_t* counts,
+                              void* workspace, size_t workspace_bytes, void* stream, int32_t edge_scan);
 int gnode_sir_mc_coins(const int32_t* table_src, const int32_t* table_dst, int64_t n_table, int32_t n,
                        const int32_t* seeds_host, int32_t n_seeds, double beta, double gamma, int64_t sims,
                        int32_t T, const double* coins, int64_t n_coins, uint32_t* counts,
