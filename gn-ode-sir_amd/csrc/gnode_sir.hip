@@ -59,26 +59,63 @@ template <bool NODES> using SirThr = std::conditional_t<NODES, const unsigned lo
 __device__ __forceinline__ unsigned long long sir_thr(unsigned long long t, int) { return t; }
 __device__ __forceinline__ unsigned long long sir_thr(const unsigned long long* t, int v) { return t[v]; }
 
+// --------------------------------------------------------------------------- per-trajectory output
+// TRAJ instances (gnode_sir_mc_philox_traj) also keep what the histograms fold away.  events: int16 [2][sims][n], the step
+// at which node v of the call's s-th trajectory was infected (plane 0; 0 for seeds) and recovered (plane 1), over a -1
+// background laid by k_fill_i16: one 2-byte store next to every histogram atomic.  curves: uint32 [sims][T][3], the
+// trajectory's totals (S_t, I_t, R_t); row 0 is the true initial state, and the rows after an early end of the epidemic
+// repeat the final state.  Either pointer may be null (a kernel argument: tested wave-uniformly).  The other instances
+// take an empty struct and compile to what they were.
+template <bool TRAJ> struct SirTraj {};
+template <> struct SirTraj<true> { int16_t* events; uint32_t* curves; };
+
+__device__ __forceinline__ void sir_curve_row(uint32_t* __restrict__ curves, long s, int T, int row, int n, int n_ever, int n_rec) {
+    uint32_t* r = curves + ((size_t)s * T + row) * 3;
+    r[0] = (uint32_t)(n - n_ever); r[1] = (uint32_t)(n_ever - n_rec); r[2] = (uint32_t)n_rec;
+}
+
+// p[0 .. count) = val.  p is 2-byte aligned only (a caller's view): 16-byte stores over the aligned body, the < 8 elements
+// in front of it and behind it by the first workgroup.
+__global__ __launch_bounds__(256) void k_fill_i16(int16_t* __restrict__ p, size_t count, int16_t val) {
+    const size_t to_align = ((16u - (unsigned)((uintptr_t)p & 15u)) & 15u) >> 1;
+    const size_t head = to_align < count ? to_align : count;
+    const size_t nvec = (count - head) >> 3;
+    uint4* pv = reinterpret_cast<uint4*>(p + head);
+    const uint32_t w = (uint32_t)(uint16_t)val * 0x10001u;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (size_t)gridDim.x * 256) pv[i] = make_uint4(w, w, w, w);
+    if (blockIdx.x == 0 && threadIdx.x < 8) {
+        const size_t t0 = head + nvec * 8;
+        if (threadIdx.x < head) p[threadIdx.x] = val;
+        if (t0 + threadIdx.x < count) p[t0 + threadIdx.x] = val;
+    }
+}
+
 // --------------------------------------------------------------------------- production kernel
 // hist: uint32 [2][T][n]: [0] = infection events (t = 0 for seeds), [1] = recovery events.
 #ifndef GN_SIR_UNROLL
 #define GN_SIR_UNROLL 8
 #endif
-template <bool STATE_IN_LDS, bool NODES>
+template <bool STATE_IN_LDS, bool NODES, bool TRAJ>
 __global__ __launch_bounds__(1024) void k_sir_philox(const int* __restrict__ src, const int* __restrict__ dst, long nnz,
                                                     int n, const int* __restrict__ seeds, int n_seeds,
                                                     SirThr<NODES> thr_beta, SirThr<NODES> thr_gamma,
                                                     long sims, long sim_offset, int T, uint32_t k0, uint32_t k1,
-                                                    uint32_t* __restrict__ hist, uint8_t* __restrict__ gstate) {
+                                                    uint32_t* __restrict__ hist, uint8_t* __restrict__ gstate, SirTraj<TRAJ> tr) {
     extern __shared__ uint8_t smem[];
     uint8_t* state = STATE_IN_LDS ? smem : gstate + (size_t)blockIdx.x * 2 * n;
     uint8_t* flag = state + n;
     uint32_t* hinf = hist;
     uint32_t* hrec = hist + (size_t)T * n;
     const int nthr = blockDim.x;                  // 256 for small graphs, 1024 when the LDS state allows one workgroup per CU
+    // TRAJ: the scan has no counters of its own -- [0] ever infected, [1] recovered, of the trajectory in hand (static LDS:
+    // the dynamic size is what the host's occupancy choice is computed from)
+    __shared__ int tcnt[2];
+    int16_t* ev_inf = nullptr; int16_t* ev_rec = nullptr; uint32_t* curves = nullptr;
+    if constexpr (TRAJ) { ev_inf = tr.events; if (tr.events) ev_rec = tr.events + (size_t)sims * n; curves = tr.curves; }
     for (long s = blockIdx.x; s < sims; s += gridDim.x) {
         const uint32_t sim = (uint32_t)(sim_offset + s);
         for (int v = threadIdx.x; v < n; v += nthr) { state[v] = ST_S; flag[v] = 0; }
+        if (TRAJ && threadIdx.x < 2) tcnt[threadIdx.x] = 0;
         __syncthreads();
         for (int j = threadIdx.x; j < n_seeds; j += nthr) state[seeds[j]] = ST_I;   // duplicates: same value
         __syncthreads();
@@ -87,7 +124,16 @@ __global__ __launch_bounds__(1024) void k_sir_philox(const int* __restrict__ src
             const int v = seeds[j];
             bool first = true;
             for (int q = 0; q < j; ++q) first = first && (seeds[q] != v);
-            if (first) atomicAdd(&hinf[v], 1u);
+            if (first) {
+                atomicAdd(&hinf[v], 1u);
+                if (TRAJ) atomicAdd(&tcnt[0], 1);
+                if (TRAJ && ev_inf) ev_inf[(size_t)s * n + v] = 0;
+            }
+        }
+        int rows_done = 1;                          // (TRAJ) rows of `curves` written so far
+        if (TRAJ && curves) {
+            __syncthreads();
+            if (threadIdx.x == 0) sir_curve_row(curves, s, T, 0, n, tcnt[0], 0);
         }
         for (int it = 1; it < T; ++it) {
             // GN_SIR_UNROLL source ids in flight per thread: the scan is a chain of (global id load -> LDS state read)
@@ -122,15 +168,33 @@ __global__ __launch_bounds__(1024) void k_sir_philox(const int* __restrict__ src
                     (unsigned long long)philox_coin((uint32_t)u, (uint32_t)it, sim, 1u, k0, k1) < sir_thr(thr_gamma, u))
                     flag[u] = 2;
             __syncthreads();
-            int any = 0;
+            int any = 0, n_new = 0, n_gone = 0;
             for (int v = threadIdx.x; v < n; v += nthr) {
                 const uint8_t f = flag[v];
-                if (f == 1) { state[v] = ST_I; atomicAdd(&hinf[(size_t)it * n + v], 1u); }
-                else if (f == 2) { state[v] = ST_R; atomicAdd(&hrec[(size_t)it * n + v], 1u); }
+                if (f == 1) {
+                    state[v] = ST_I; atomicAdd(&hinf[(size_t)it * n + v], 1u);
+                    if (TRAJ) ++n_new;
+                    if (TRAJ && ev_inf) ev_inf[(size_t)s * n + v] = (int16_t)it;
+                } else if (f == 2) {
+                    state[v] = ST_R; atomicAdd(&hrec[(size_t)it * n + v], 1u);
+                    if (TRAJ) ++n_gone;
+                    if (TRAJ && ev_inf) ev_rec[(size_t)s * n + v] = (int16_t)it;
+                }
                 flag[v] = 0;
                 any |= (state[v] == ST_I);
             }
-            if (!__syncthreads_or(any)) break;      // epidemic over: no further events in this trajectory
+            if (TRAJ && n_new) atomicAdd(&tcnt[0], n_new);
+            if (TRAJ && n_gone) atomicAdd(&tcnt[1], n_gone);
+            const int alive = __syncthreads_or(any);
+            if (TRAJ && curves) {                   // (the counters rest until the next step's barrier)
+                if (threadIdx.x == 0) sir_curve_row(curves, s, T, it, n, tcnt[0], tcnt[1]);
+                rows_done = it + 1;
+            }
+            if (!alive) break;                      // epidemic over: no further events in this trajectory
+        }
+        if (TRAJ && curves) {                       // the rows after an early end repeat the final state
+            const int n_ever = tcnt[0], n_rec = tcnt[1];
+            for (int r = rows_done + threadIdx.x; r < T; r += nthr) sir_curve_row(curves, s, T, r, n, n_ever, n_rec);
         }
         __syncthreads();
     }
@@ -144,13 +208,15 @@ __global__ __launch_bounds__(1024) void k_sir_philox(const int* __restrict__ src
 // COUNT: the profiling instantiation (gnode_sir_mc_philox_counted) also tallies Philox blocks, coins and CSR entries read.
 // NODES: per-node thresholds.  A target's threshold is read only where a coin is drawn -- in `drain`, for the (position,
 // target) pairs that passed the ever-infected test -- and the read is issued ahead of the coin's Philox rounds.
-template <typename IdT, bool LISTS_IN_LDS, bool COUNT, bool NODES>
+// TRAJ: per-trajectory events and curves (SirTraj above); there is no COUNT && TRAJ instance.
+template <typename IdT, bool LISTS_IN_LDS, bool COUNT, bool NODES, bool TRAJ>
 __global__ __launch_bounds__(1024) void k_sir_frontier(const int* __restrict__ rowptr, const int* __restrict__ col, int n,
                                                       const int* __restrict__ seeds, int n_seeds,
                                                       SirThr<NODES> thr_beta, SirThr<NODES> thr_gamma,
                                                       long sims, long sim_offset, int T, uint32_t k0, uint32_t k1,
                                                       uint32_t* __restrict__ hist, int32_t* __restrict__ glists,
-                                                      unsigned long long* __restrict__ stats) {
+                                                      unsigned long long* __restrict__ stats, SirTraj<TRAJ> tr) {
+    static_assert(!(COUNT && TRAJ), "the counting instantiation has no per-trajectory output");
     extern __shared__ uint32_t smem_w[];
     const int nwords = (n + 31) >> 5;
     const int nw4 = (nwords + 3) & ~3;
@@ -172,6 +238,8 @@ __global__ __launch_bounds__(1024) void k_sir_frontier(const int* __restrict__ r
     const int nthr = blockDim.x, tid = threadIdx.x;
     const int sub = tid & 15, gid = tid >> 4, ngroups = nthr >> 4, lane_in_wave = tid & 63;
     unsigned long long st_blocks = 0, st_ecoins = 0, st_rcoins = 0, st_entries = 0;
+    int16_t* ev_inf = nullptr; int16_t* ev_rec = nullptr; uint32_t* curves = nullptr;
+    if constexpr (TRAJ) { ev_inf = tr.events; if (tr.events) ev_rec = tr.events + (size_t)sims * n; curves = tr.curves; }
     for (long s = blockIdx.x; s < sims; s += gridDim.x) {
         const uint32_t sim = (uint32_t)(sim_offset + s);
         for (int w = tid; w < nwords; w += nthr) { bits[w] = 0u; spent[w] = 0u; recb[w] = 0u; }
@@ -180,13 +248,18 @@ __global__ __launch_bounds__(1024) void k_sir_frontier(const int* __restrict__ r
         for (int j = tid; j < n_seeds; j += nthr) {            // distinct seeds: one infection event at t = 0 each
             const int v = seeds[j];
             const uint32_t m = 1u << (v & 31);
-            if (!(atomicOr(&bits[v >> 5], m) & m)) { cur[atomicAdd(&cnt[0], 1)] = (IdT)v; atomicAdd(&hinf[v], 1u); }
+            if (!(atomicOr(&bits[v >> 5], m) & m)) {
+                cur[atomicAdd(&cnt[0], 1)] = (IdT)v; atomicAdd(&hinf[v], 1u);
+                if (TRAJ && ev_inf) ev_inf[(size_t)s * n + v] = 0;
+            }
         }
         __syncthreads();
         int n_inf = cnt[0];
         int n_ever = n_inf;                                    // once it reaches n nobody is left to infect: recovery coins only
         __syncthreads();
         if (tid == 0) cnt[2] = n_ever;
+        int rows_done = 1;                                     // (TRAJ) rows of `curves` written so far
+        if (TRAJ && curves && tid == 0) sir_curve_row(curves, s, T, 0, n, n_ever, 0);
         for (int it = 1; it < T && n_inf > 0; ++it) {
             if (tid == 0) { cnt[0] = 0; cnt[1] = 0; }
             __syncthreads();
@@ -209,14 +282,21 @@ __global__ __launch_bounds__(1024) void k_sir_frontier(const int* __restrict__ r
 #pragma unroll
                     for (int j = 0; j < 4; ++j)
                         if ((nib >> j) & 1u) {
-                            if ((unsigned long long)w[j] < sir_thr(thr_gamma, u0 + j)) { gone |= 1u << j; atomicAdd(&hrec[(size_t)it * n + u0 + j], 1u); }
-                            else ++alive;
+                            if ((unsigned long long)w[j] < sir_thr(thr_gamma, u0 + j)) {
+                                gone |= 1u << j; atomicAdd(&hrec[(size_t)it * n + u0 + j], 1u);
+                                if (TRAJ && ev_inf) ev_rec[(size_t)s * n + u0 + j] = (int16_t)it;
+                            } else ++alive;
                         }
                     if (gone) atomicOr(&recb[u0 >> 5], gone << (u0 & 31));
                 }
                 if (alive) atomicAdd(&cnt[0], alive);
                 __syncthreads();
                 n_inf = cnt[0];
+                if (TRAJ && curves) {
+                    n_ever = n;
+                    if (tid == 0) sir_curve_row(curves, s, T, it, n, n_ever, n_ever - n_inf);
+                    rows_done = it + 1;
+                }
                 __syncthreads();
                 continue;
             }
@@ -228,6 +308,7 @@ __global__ __launch_bounds__(1024) void k_sir_frontier(const int* __restrict__ r
                     nxt[atomicAdd(&cnt[0], 1)] = (IdT)v;
                     atomicAdd(&cnt[2], 1);
                     atomicAdd(&hinf[(size_t)it * n + v], 1u);
+                    if (TRAJ && ev_inf) ev_inf[(size_t)s * n + v] = (int16_t)it;
                 }
             };
             // Counted on the wiki-vote-size workload (beta 0.3): 2.6e9 CSR entries read, 0.24e9 of them with a susceptible target.
@@ -318,6 +399,7 @@ __global__ __launch_bounds__(1024) void k_sir_frontier(const int* __restrict__ r
                 const bool gone = (unsigned long long)philox_coin((uint32_t)u, (uint32_t)it, sim, 1u, k0, k1) < tg;
                 if (gone) {
                     atomicAdd(&hrec[(size_t)it * n + u], 1u);
+                    if (TRAJ && ev_inf) ev_rec[(size_t)s * n + u] = (int16_t)it;
                     atomicOr(&recb[u >> 5], 1u << (u & 31));
                 }
                 // survivors go on the next list: ONE LDS atomic per wave (64 lanes adding to the same word serialise)
@@ -338,9 +420,15 @@ __global__ __launch_bounds__(1024) void k_sir_frontier(const int* __restrict__ r
             __syncthreads();
             n_inf = cnt[0];
             n_ever = cnt[2];
+            if (TRAJ && curves) {
+                if (tid == 0) sir_curve_row(curves, s, T, it, n, n_ever, n_ever - n_inf);
+                rows_done = it + 1;
+            }
             IdT* t = cur; cur = nxt; nxt = t;
             __syncthreads();
         }
+        if (TRAJ && curves)                                    // the rows after an early end repeat the final state
+            for (int r = rows_done + tid; r < T; r += nthr) sir_curve_row(curves, s, T, r, n, n_ever, n_ever - n_inf);
     }
     if (COUNT) {
         atomicAdd(&stats[0], st_blocks); atomicAdd(&stats[1], st_ecoins); atomicAdd(&stats[2], st_rcoins); atomicAdd(&stats[3], st_entries);
@@ -501,14 +589,20 @@ static int frontier_threads(int n, int n_big, int* per_cu_out) {
 static const int kFrontierGlobalGrid = 1024;       // workgroups that own a set of global lists (graphs past the LDS form)
 
 int gn_sir_set_attributes() {       // once per device, from gnode_graph_create
-    GN_HIP(hipFuncSetAttribute((const void*)k_sir_frontier<uint16_t, true, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
-    GN_HIP(hipFuncSetAttribute((const void*)k_sir_frontier<int32_t, false, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
-    GN_HIP(hipFuncSetAttribute((const void*)k_sir_frontier<uint16_t, true, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
-    GN_HIP(hipFuncSetAttribute((const void*)k_sir_frontier<int32_t, false, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
-    GN_HIP(hipFuncSetAttribute((const void*)k_sir_frontier<uint16_t, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
-    GN_HIP(hipFuncSetAttribute((const void*)k_sir_frontier<int32_t, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
-    GN_HIP(hipFuncSetAttribute((const void*)k_sir_philox<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
-    GN_HIP(hipFuncSetAttribute((const void*)k_sir_philox<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
+    GN_HIP(hipFuncSetAttribute((const void*)k_sir_frontier<uint16_t, true, false, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
+    GN_HIP(hipFuncSetAttribute((const void*)k_sir_frontier<int32_t, false, false, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
+    GN_HIP(hipFuncSetAttribute((const void*)k_sir_frontier<uint16_t, true, true, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
+    GN_HIP(hipFuncSetAttribute((const void*)k_sir_frontier<int32_t, false, true, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
+    GN_HIP(hipFuncSetAttribute((const void*)k_sir_frontier<uint16_t, true, false, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
+    GN_HIP(hipFuncSetAttribute((const void*)k_sir_frontier<int32_t, false, false, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
+    GN_HIP(hipFuncSetAttribute((const void*)k_sir_frontier<uint16_t, true, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
+    GN_HIP(hipFuncSetAttribute((const void*)k_sir_frontier<int32_t, false, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
+    GN_HIP(hipFuncSetAttribute((const void*)k_sir_frontier<uint16_t, true, false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
+    GN_HIP(hipFuncSetAttribute((const void*)k_sir_frontier<int32_t, false, false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
+    GN_HIP(hipFuncSetAttribute((const void*)k_sir_philox<true, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
+    GN_HIP(hipFuncSetAttribute((const void*)k_sir_philox<true, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
+    GN_HIP(hipFuncSetAttribute((const void*)k_sir_philox<true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
+    GN_HIP(hipFuncSetAttribute((const void*)k_sir_philox<true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
     GN_HIP(hipFuncSetAttribute((const void*)k_sir_coins, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
     return 0;
 }
@@ -540,8 +634,12 @@ static int sir_mc_philox_impl(gnode_graph_t g, const int32_t* seeds_host, int32_
                               double gamma, int64_t sims, int64_t sim_offset, int32_t T, uint64_t rng_seed,
                               uint32_t* counts, void* workspace, size_t workspace_bytes, void* stream, bool edge_scan,
                               unsigned long long* stats = nullptr /* device [4]: the counting instantiation, or null */,
-                              const double* beta_nodes = nullptr, const double* gamma_nodes = nullptr) {
-    GN_CHECK_ARG(g && counts && workspace, "gnode_sir_mc_philox: null pointer");
+                              const double* beta_nodes = nullptr, const double* gamma_nodes = nullptr,
+                              bool traj = false /* gnode_sir_mc_philox_traj: counts may be null, events / curves are written */,
+                              int16_t* events = nullptr, uint32_t* curves = nullptr) {
+    GN_CHECK_ARG(g && (counts || traj) && workspace, "gnode_sir_mc_philox: null pointer");
+    GN_CHECK_ARG(!traj || ((events || curves) && !stats), "gnode_sir_mc_philox_traj: neither events nor curves given");
+    GN_CHECK_ARG(!events || (T <= 32767 && ((uintptr_t)events & 1u) == 0), "gnode_sir_mc_philox_traj: events hold int16 steps (T <= 32767)");
     const bool nodes = beta_nodes || gamma_nodes;
     GN_CHECK_ARG(!nodes || (beta_nodes && gamma_nodes && !stats), "gnode_sir_mc_philox_nodes: null rate array");
     GN_CHECK_ARG(n_seeds >= 0 && n_seeds <= 4096 && (seeds_host || n_seeds == 0), "gnode_sir_mc_philox: 0..4096 seeds");
@@ -577,6 +675,12 @@ static int sir_mc_philox_impl(gnode_graph_t g, const int32_t* seeds_host, int32_
     uint8_t* gstate = (uint8_t*)(ws + hist_b + gn_align(4096 * sizeof(int32_t)) +
                                  gn_align((size_t)std::max<int64_t>(g->nnz, 1) * sizeof(int32_t)));
     if (int e = gn_zero_async(hist, hist_b, st)) return e;
+    if (events && sims > 0) {                              // the "never" background, by a kernel like the zero fill above
+        const size_t count = (size_t)2 * (size_t)sims * (size_t)g->info.n;
+        const int grid = (int)std::min<size_t>((count / 8 + 255) / 256 + 1, (size_t)g->info.num_cu * 8);
+        hipLaunchKernelGGL(k_fill_i16, dim3(grid), dim3(256), 0, st, events, count, (int16_t)-1);
+        GN_LAUNCH_CHECK();
+    }
     // seed ids: up to 32 travel as a kernel argument (no copy, no synchronisation -- the reference's experiments use 2);
     // longer lists are copied from the caller's host array, which may be a temporary, so the stream is synchronised
     // before returning control (documented in gnode.h)
@@ -600,29 +704,32 @@ static int sir_mc_philox_impl(gnode_graph_t g, const int32_t* seeds_host, int32_
         const size_t lds = (size_t)2 * g->info.n;
         // one path selection and launch geometry for both forms: `nodes_tag` picks the kernels' NODES instances, whose
         // thresholds tb_ / tg_ are the staged arrays instead of the two numbers
-        auto launch = [&](auto nodes_tag, auto tb_, auto tg_) {
+        auto launch = [&](auto nodes_tag, auto traj_tag, auto tb_, auto tg_) {
             constexpr bool NODES = decltype(nodes_tag)::value;
+            constexpr bool TRAJ = decltype(traj_tag)::value;
+            SirTraj<TRAJ> tr;
+            if constexpr (TRAJ) { tr.events = events; tr.curves = curves; }
             if (fl <= kLdsStateLimit && !edge_scan) {
                 // frontier-driven walk.  Workgroups per CU by LDS, at least 16 waves per CU
                 const int per_cu = per_cu_f, threads = threads_f;
                 if (frontier_lists_in_lds(g->info.n, g->n_bigrow)) {
                     const int grid = (int)std::min<int64_t>(sims, (int64_t)g->info.num_cu * per_cu);
-                    if constexpr (!NODES) if (stats) {
-                        hipLaunchKernelGGL((k_sir_frontier<uint16_t, true, true, false>), dim3(grid), dim3(threads), fl, st, g->rowptr, g->col, g->info.n, seeds,
-                                           n_seeds, tb_, tg_, (long)sims, (long)sim_offset, T, k0, k1, hist, (int32_t*)nullptr, stats);
+                    if constexpr (!NODES && !TRAJ) if (stats) {
+                        hipLaunchKernelGGL((k_sir_frontier<uint16_t, true, true, false, false>), dim3(grid), dim3(threads), fl, st, g->rowptr, g->col, g->info.n, seeds,
+                                           n_seeds, tb_, tg_, (long)sims, (long)sim_offset, T, k0, k1, hist, (int32_t*)nullptr, stats, tr);
                         return;
                     }
-                    hipLaunchKernelGGL((k_sir_frontier<uint16_t, true, false, NODES>), dim3(grid), dim3(threads), fl, st, g->rowptr, g->col, g->info.n, seeds,
-                                       n_seeds, tb_, tg_, (long)sims, (long)sim_offset, T, k0, k1, hist, (int32_t*)nullptr, stats);
+                    hipLaunchKernelGGL((k_sir_frontier<uint16_t, true, false, NODES, TRAJ>), dim3(grid), dim3(threads), fl, st, g->rowptr, g->col, g->info.n, seeds,
+                                       n_seeds, tb_, tg_, (long)sims, (long)sim_offset, T, k0, k1, hist, (int32_t*)nullptr, stats, tr);
                 } else {
                     const int grid = (int)std::min<int64_t>(std::min<int64_t>(sims, (int64_t)g->info.num_cu * per_cu), kFrontierGlobalGrid);
-                    if constexpr (!NODES) if (stats) {
-                        hipLaunchKernelGGL((k_sir_frontier<int32_t, false, true, false>), dim3(grid), dim3(threads), fl, st, g->rowptr, g->col, g->info.n, seeds,
-                                           n_seeds, tb_, tg_, (long)sims, (long)sim_offset, T, k0, k1, hist, (int32_t*)gstate, stats);
+                    if constexpr (!NODES && !TRAJ) if (stats) {
+                        hipLaunchKernelGGL((k_sir_frontier<int32_t, false, true, false, false>), dim3(grid), dim3(threads), fl, st, g->rowptr, g->col, g->info.n, seeds,
+                                           n_seeds, tb_, tg_, (long)sims, (long)sim_offset, T, k0, k1, hist, (int32_t*)gstate, stats, tr);
                         return;
                     }
-                    hipLaunchKernelGGL((k_sir_frontier<int32_t, false, false, NODES>), dim3(grid), dim3(threads), fl, st, g->rowptr, g->col, g->info.n, seeds,
-                                       n_seeds, tb_, tg_, (long)sims, (long)sim_offset, T, k0, k1, hist, (int32_t*)gstate, stats);
+                    hipLaunchKernelGGL((k_sir_frontier<int32_t, false, false, NODES, TRAJ>), dim3(grid), dim3(threads), fl, st, g->rowptr, g->col, g->info.n, seeds,
+                                       n_seeds, tb_, tg_, (long)sims, (long)sim_offset, T, k0, k1, hist, (int32_t*)gstate, stats, tr);
                 }
             } else if (lds <= kLdsStateLimit) {
                 // edge-parallel scan, node state in LDS: graphs whose frontier lists do not fit (n > ~25k with 32-bit ids)
@@ -630,20 +737,23 @@ static int sir_mc_philox_impl(gnode_graph_t g, const int32_t* seeds_host, int32_
                 const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / std::max<size_t>(lds, 1)));
                 const int threads = per_cu >= 4 ? 256 : (per_cu >= 2 ? 512 : 1024);
                 const int grid = (int)std::min<int64_t>(sims, (int64_t)g->info.num_cu * per_cu);
-                hipLaunchKernelGGL((k_sir_philox<true, NODES>), dim3(grid), dim3(threads), lds, st, src, g->col, (long)g->nnz, g->info.n, seeds,
-                                   n_seeds, tb_, tg_, (long)sims, (long)sim_offset, T, k0, k1, hist, (uint8_t*)nullptr);
+                hipLaunchKernelGGL((k_sir_philox<true, NODES, TRAJ>), dim3(grid), dim3(threads), lds, st, src, g->col, (long)g->nnz, g->info.n, seeds,
+                                   n_seeds, tb_, tg_, (long)sims, (long)sim_offset, T, k0, k1, hist, (uint8_t*)nullptr, tr);
             } else {
                 hipLaunchKernelGGL(k_expand_rows, dim3((g->info.n + 255) / 256), dim3(256), 0, st, g->rowptr, g->info.n, src);
                 const int grid = (int)std::min<int64_t>(sims, 2048);
-                hipLaunchKernelGGL((k_sir_philox<false, NODES>), dim3(grid), dim3(256), 0, st, src, g->col, (long)g->nnz, g->info.n, seeds,
-                                   n_seeds, tb_, tg_, (long)sims, (long)sim_offset, T, k0, k1, hist, gstate);
+                hipLaunchKernelGGL((k_sir_philox<false, NODES, TRAJ>), dim3(grid), dim3(256), 0, st, src, g->col, (long)g->nnz, g->info.n, seeds,
+                                   n_seeds, tb_, tg_, (long)sims, (long)sim_offset, T, k0, k1, hist, gstate, tr);
             }
         };
-        if (nodes) launch(std::true_type{}, thr_b, thr_g);
-        else launch(std::false_type{}, tb, tg);
+        if (nodes && traj) launch(std::true_type{}, std::true_type{}, thr_b, thr_g);
+        else if (nodes) launch(std::true_type{}, std::false_type{}, thr_b, thr_g);
+        else if (traj) launch(std::false_type{}, std::true_type{}, tb, tg);
+        else launch(std::false_type{}, std::false_type{}, tb, tg);
         if (sampled) gn_prof_end(3, st);
         GN_LAUNCH_CHECK();
     }
+    if (!counts) return 0;                                 // (gnode_sir_mc_philox_traj without counts)
     hipLaunchKernelGGL(k_sir_finalize, dim3((g->info.n + 255) / 256), dim3(256), 0, st, hist, g->info.n, T, (uint32_t)sims, counts);
     GN_LAUNCH_CHECK();
     return 0;
@@ -693,6 +803,26 @@ extern "C" int gnode_sir_mc_philox_nodes(gnode_graph_t g, const int32_t* seeds_h
     GN_CHECK_ARG(beta_host && gamma_host, "gnode_sir_mc_philox_nodes: null rate array");
     return sir_mc_philox_impl(g, seeds_host, n_seeds, 0.0, 0.0, sims, sim_offset, T, rng_seed, counts, workspace,
                               workspace_bytes, stream, edge_scan != 0, nullptr, beta_host, gamma_host);
+}
+
+// Per-trajectory output (include/gnode.h): the call above with the kernels' TRAJ instances -- same validation, path selection,
+// geometry and coins; scalar rates when both arrays are null.  The workspace is the per-node form's in either case.
+extern "C" size_t gnode_sir_traj_workspace_bytes(gnode_graph_t g, int32_t T) { return gnode_sir_nodes_workspace_bytes(g, T); }
+extern "C" int gnode_sir_mc_philox_traj(gnode_graph_t g, const int32_t* seeds_host, int32_t n_seeds, double beta, double gamma,
+                                        const double* beta_host, const double* gamma_host, int64_t sims, int64_t sim_offset,
+                                        int32_t T, uint64_t rng_seed, int16_t* events, uint32_t* curves, uint32_t* counts,
+                                        void* workspace, size_t workspace_bytes, void* stream, int32_t edge_scan) {
+    GN_CHECK_ARG(events || curves, "gnode_sir_mc_philox_traj: neither events nor curves given");
+    GN_CHECK_ARG(!beta_host == !gamma_host, "gnode_sir_mc_philox_traj: one rate array without the other");
+    GN_CHECK_ARG(!events || T <= 32767, "gnode_sir_mc_philox_traj: events hold int16 steps, T = %d > 32767", T);
+    GN_CHECK_ARG(g && workspace, "gnode_sir_mc_philox_traj: null pointer");
+    if (workspace_bytes < gnode_sir_traj_workspace_bytes(g, T)) {
+        gnode_set_error("gnode_sir_mc_philox_traj: workspace %zu < %zu", workspace_bytes, gnode_sir_traj_workspace_bytes(g, T));
+        return GNODE_ERR_WORKSPACE;
+    }
+    const bool nodes = beta_host != nullptr;
+    return sir_mc_philox_impl(g, seeds_host, n_seeds, nodes ? 0.0 : beta, nodes ? 0.0 : gamma, sims, sim_offset, T, rng_seed, counts,
+                              workspace, workspace_bytes, stream, edge_scan != 0, nullptr, beta_host, gamma_host, true, events, curves);
 }
 
 extern "C" int gnode_sir_mc_coins(const int32_t* table_src, const int32_t* table_dst, int64_t n_table, int32_t n,

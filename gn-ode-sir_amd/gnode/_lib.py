@@ -73,6 +73,8 @@ ABI = {
     "gnode_sir_mc_philox_counted": (_int, _SIR + [C.POINTER(_u64)]),
     "gnode_sir_nodes_workspace_bytes": (_sz, [_vp, _i32]),
     "gnode_sir_mc_philox_nodes": (_int, [_vp, _vp, _i32, _vp, _vp, _i64, _i64, _i32, _u64, _vp, _vp, _sz, _vp, _i32]),
+    "gnode_sir_traj_workspace_bytes": (_sz, [_vp, _i32]),
+    "gnode_sir_mc_philox_traj": (_int, [_vp, _vp, _i32, _f64, _f64, _vp, _vp, _i64, _i64, _i32, _u64, _vp, _vp, _vp, _vp, _sz, _vp, _i32]),
     "gnode_sir_mc_coins": (_int, [_vp, _vp, _i64, _i32, _vp, _i32, _f64, _f64, _i64, _i32, _vp, _i64, _vp, _pi64, _vp, _sz, _vp]),
     "gnode_dmp_workspace_bytes": (_sz, [_vp]),
     "gnode_dmp_f32": (_int, [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _sz, _vp]),
@@ -102,7 +104,9 @@ def load():
     import torch  # noqa: F401  -- first, so that one HIP runtime (torch's libamdhip64.so.7) serves both
     lib = C.CDLL(LIB_PATH)
     for name, (restype, argtypes) in ABI.items():
-        fn = getattr(lib, name)
+        fn = getattr(lib, name, None)
+        if fn is None:                     # an entry added without a version step: the missing symbol is the sign
+            raise GnodeError(f"{LIB_PATH} is stale (no {name}): rebuild it (gnode.build.build_lib)")
         fn.restype, fn.argtypes = restype, argtypes
     if lib.gnode_version() < 226:
         raise GnodeError(f"{LIB_PATH} is stale (ABI {lib.gnode_version()} < 226): rebuild it (gnode.build.build_lib)")

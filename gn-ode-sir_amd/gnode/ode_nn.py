@@ -10,6 +10,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 import pickle
+from typing import NamedTuple
 
 import numpy as np
 import scipy.sparse as sp
@@ -110,6 +111,101 @@ def sir_counts(graph: DeviceGraph, seed_set, beta, gamma, sims, T, rng_seed, sim
                               int(bool(edge_scan)), ws_entry="gnode_sir_nodes_workspace_bytes")
     return _philox_launch("gnode_sir_mc_philox_scan" if edge_scan else "gnode_sir_mc_philox", graph, seed_set, beta, gamma,
                           sims, T, rng_seed, sim_offset, device, counts)
+
+
+class SirTrajectories(NamedTuple):
+    """What `sir_trajectories` returns; a field is None where it was not requested."""
+    t_inf: torch.Tensor | None      # int16 [sims, n]: step at which the node was infected (0: a seed), -1 never within T
+    t_rec: torch.Tensor | None      # int16 [sims, n]: step at which it recovered, -1 never within T
+    curves: torch.Tensor | None     # int32 [sims, T, 3]: (S_t, I_t, R_t) of each trajectory
+
+
+def _traj_launch(graph: DeviceGraph, seed_set, b, g, sims, T, rng_seed, sim_offset, ev, cv, counts, edge_scan):
+    """One gnode_sir_mc_philox_traj launch into ev (int16 [2, sims, n] or None), cv (int32 [sims, T, 3] or None) and counts
+    (int32 [3, T, n], accumulated, or None).  b / g: two numbers, or two float64 [n] host arrays (`_node_rates`)."""
+    lib = _lib.load()
+    seeds = np.ascontiguousarray(list(seed_set), dtype=np.int32)
+    dev = (ev if ev is not None else cv).device
+    ws = torch.empty(lib.gnode_sir_traj_workspace_bytes(graph.handle, T), dtype=torch.uint8, device=dev)
+    arrays = isinstance(b, np.ndarray)
+    _lib.check(lib.gnode_sir_mc_philox_traj(graph.handle, _lib.host_ptr(seeds), int(seeds.shape[0]),
+                                            0.0 if arrays else float(b), 0.0 if arrays else float(g),
+                                            _lib.host_ptr(b) if arrays else None, _lib.host_ptr(g) if arrays else None,
+                                            int(sims), int(sim_offset), int(T), C.c_uint64(int(rng_seed) & (2**64 - 1)),
+                                            _lib.ptr(ev), _lib.ptr(cv), _lib.ptr(counts), _lib.ptr(ws), ws.numel(),
+                                            _lib.stream_ptr(), int(bool(edge_scan))))
+
+
+def sir_trajectories(graph_or_G, seed_set, beta, gamma, sims, T, rng_seed=None, sim_offset=0, events=True, curves=True,
+                     counts: torch.Tensor | None = None, edge_scan: bool = False, device="cuda") -> SirTrajectories:
+    """The Monte-Carlo of `sir_counts`, trajectory by trajectory: `SirTrajectories(t_inf, t_rec, curves)` on the GPU.
+
+    Each of the `sims` trajectories is described by two steps per node -- t_inf[s, v], when v was infected (0 for a seed),
+    and t_rec[s, v], when it recovered; -1 = never within T; t_rec > t_inf wherever both are set -- and by its population
+    totals curves[s, t] = (S_t, I_t, R_t), whose row 0 is the true initial state.  s counts inside the call: trajectory s
+    draws the coins of sim_offset + s, so trajectories [a, b) of a large run are the call with sims = b - a, sim_offset = a
+    (events take 4 * sims * n bytes: shard large runs).  `sir_state_at`, `sir_counts_from_events` and
+    `sir_curves_from_events` read the events; the second returns what `sir_counts` of the same arguments returns.
+
+    graph_or_G: a DeviceGraph or a networkx graph.  beta / gamma: as in `sir_counts`.  rng_seed=None draws the seed from
+    torch's CPU generator, as `sir_torch` does.  events=False / curves=False leave that output out (None in the result);
+    `counts` (int32 [3, T, n]) is accumulated into as by `sir_counts`.  edge_scan=True runs the edge-parallel kernel.
+    Raises ValueError for bad rates, for T > 32767 with events, and when neither output is requested."""
+    graph = _device_graph_for(graph_or_G) if hasattr(graph_or_G, "number_of_nodes") else graph_or_G
+    n = graph.n
+    b, g = _node_rates("beta", beta, n), _node_rates("gamma", gamma, n)
+    if b is not None or g is not None:
+        b = _node_rates("beta", np.full(n, float(beta)), n) if b is None else b
+        g = _node_rates("gamma", np.full(n, float(gamma)), n) if g is None else g
+    else:
+        b, g = float(beta), float(gamma)
+    if not events and not curves:
+        raise ValueError("sir_trajectories: neither events nor curves requested")
+    if events and T > 32767:
+        raise ValueError(f"sir_trajectories: events hold int16 steps, T = {T} > 32767")
+    if rng_seed is None:
+        rng_seed = int(torch.randint(0, 2**62, (1,), dtype=torch.int64).item())
+    dev = counts.device if counts is not None else device
+    ev = torch.empty((2, sims, n), dtype=torch.int16, device=dev) if events else None
+    cv = torch.empty((sims, T, 3), dtype=torch.int32, device=dev) if curves else None
+    if sims > 0:
+        _traj_launch(graph, seed_set, b, g, sims, T, rng_seed, sim_offset, ev, cv, counts, edge_scan)
+    return SirTrajectories(ev[0] if events else None, ev[1] if events else None, cv)
+
+
+def sir_state_at(t_inf: torch.Tensor, t_rec: torch.Tensor, t: int) -> torch.Tensor:
+    """int8 [sims, n]: 0 S, 1 I, 2 R at step t -- infected means 0 <= t_inf <= t, recovered 0 <= t_rec <= t."""
+    inf = (t_inf >= 0) & (t_inf <= t)
+    rec = (t_rec >= 0) & (t_rec <= t)
+    return inf.to(torch.int8) + rec.to(torch.int8)
+
+
+def _events_up_to(t_ev: torch.Tensor, T: int, dim: int) -> torch.Tensor:
+    """int32 cumulative event counts: along the other dimension of the [sims, n] event steps, how many are in [0, t], for
+    t = 0 .. T - 1 (dim = 0: [T, n], summed over trajectories; dim = 1: [sims, T], summed over nodes)."""
+    idx = torch.where(t_ev < 0, T, t_ev.to(torch.int64))                       # "never" goes to a row that is dropped
+    shape = (T + 1, t_ev.shape[1]) if dim == 0 else (t_ev.shape[0], T + 1)
+    hist = torch.zeros(shape, dtype=torch.int32, device=t_ev.device)
+    hist.scatter_add_(dim, idx, torch.ones_like(idx, dtype=torch.int32))
+    return hist.narrow(dim, 0, T).cumsum(dim, dtype=torch.int32)
+
+
+def sir_counts_from_events(t_inf: torch.Tensor, t_rec: torch.Tensor, T: int) -> torch.Tensor:
+    """int32 [3, T, n]: the counts `sir_counts` accumulates for these trajectories -- rows t >= 1 the number of
+    trajectories in which the node is S / I / R at step t, row 0 the initial state ONCE (the reference's quirk)."""
+    sims = t_inf.shape[0]
+    ci, cr = _events_up_to(t_inf, T, 0), _events_up_to(t_rec, T, 0)
+    out = torch.stack([sims - ci, ci - cr, cr])
+    seeded = (t_inf == 0).any(dim=0).to(torch.int32)                           # every trajectory starts from the same seeds
+    out[0, 0], out[1, 0], out[2, 0] = 1 - seeded, seeded, 0
+    return out
+
+
+def sir_curves_from_events(t_inf: torch.Tensor, t_rec: torch.Tensor, T: int) -> torch.Tensor:
+    """int32 [sims, T, 3]: (S_t, I_t, R_t) of each trajectory, row 0 the true initial state."""
+    n = t_inf.shape[1]
+    ci, cr = _events_up_to(t_inf, T, 1), _events_up_to(t_rec, T, 1)
+    return torch.stack([n - ci, ci - cr, cr], dim=2)
 
 
 def sir_counts_counted(graph: DeviceGraph, seed_set, beta, gamma, sims, T, rng_seed, sim_offset=0, device="cuda"):

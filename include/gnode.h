@@ -20,7 +20,7 @@
  *     into a hipGraph on first use and one handle may serve several streams (each
  *     with its own workspace).  Functions that DO synchronise `stream` say so below
  *     (gnode_graph_create, gnode_sir_mc_philox with more than 32 seeds,
- *     gnode_sir_mc_philox_nodes, gnode_sir_mc_coins, gnode_dmp_f32, gnode_meanfield_f64).
+ *     gnode_sir_mc_philox_nodes, gnode_sir_mc_philox_traj with more than 32 seeds or rate arrays, gnode_sir_mc_coins, gnode_dmp_f32, gnode_meanfield_f64).
  *   - process-wide state: (1) a per-device "set up once" table (compute-unit count,
  *     dynamic-LDS kernel attributes), written under a lock by the first
  *     gnode_graph_create on a device and read-only afterwards; (2) the opt-in
@@ -367,6 +367,32 @@ int gnode_sir_mc_philox_nodes(gnode_graph_t g, const int32_t* seeds_host, int32_
                               const double* beta_host, const double* gamma_host,   /* host fp64 [n] each */
                               int64_t sims, int64_t sim_offset, int32_t T, uint64_t rng_seed, uint32_t* counts,
                               void* workspace, size_t workspace_bytes, void* stream, int32_t edge_scan);
+/* Per-trajectory output: what the counts have averaged away.  The call is gnode_sir_mc_philox (both rate arrays NULL: the
+ * scalars beta / gamma hold) or gnode_sir_mc_philox_nodes (both given; exactly one is GNODE_ERR_ARG) -- same validation, path
+ * selection, launch geometry and coins -- through the kernels' TRAJ instances, which also keep
+ *   events  device int16 [2, sims, n], OVERWRITTEN   [0, s, v] the step at which node v of the call's s-th trajectory became
+ *                                                    infected (0 for a seed), [1, s, v] the step at which it recovered; -1 =
+ *                                                    never within T.  s counts inside the call (the trajectory's coins are
+ *                                                    those of sim_offset + s).  Recovery is decided on the pre-step state, so
+ *                                                    [1, s, v] > [0, s, v] wherever both are set.  T <= 32767 (GNODE_ERR_ARG).
+ *   curves  device uint32 [sims, T, 3], OVERWRITTEN  (S_t, I_t, R_t), the population totals of each trajectory.  Row 0 is the
+ *                                                    true initial state (n - k, k, 0), k distinct seeds: the assigned-once
+ *                                                    row 0 is a property of the accumulated counts, not of a trajectory.
+ *   counts  device uint32 [3, T, n], ACCUMULATED     exactly what gnode_sir_mc_philox / _nodes add, or NULL (nothing is added)
+ * events or curves may be NULL, not both (GNODE_ERR_ARG).  sims == 0 is valid and touches neither.  Memory: events take
+ * 4 * sims * n bytes -- 283 MB for 10 000 trajectories of a 7 066-node graph -- and curves 12 * sims * T, so callers shard a
+ * large run with sim_offset.  The -1 background of events is laid by a fill kernel on `stream` in front of the Monte-Carlo
+ * kernel (2 * sims * n elements, no more).  Enqueue-only with up to 32 seeds and scalar rates; otherwise `stream` is
+ * synchronised as by the entries above.  The workspace is gnode_sir_nodes_workspace_bytes' in either case. */
+size_t gnode_sir_traj_workspace_bytes(gnode_graph_t g, int32_t T);
+int gnode_sir_mc_philox_traj(gnode_graph_t g, const int32_t* seeds_host, int32_t n_seeds,
+                             double beta, double gamma,                          /* used when both arrays are NULL */
+                             const double* beta_host, const double* gamma_host,  /* host fp64 [n] each, or both NULL */
+                             int64_t sims, int64_t sim_offset, int32_t T, uint64_t rng_seed,
+                             int16_t* events,    /* device [2, sims, n], OVERWRITTEN, or NULL */
+                             uint32_t* curves,   /* device [sims, T, 3], OVERWRITTEN, or NULL */
+                             uint32_t* counts,   /* device [3, T, n], ACCUMULATED as gnode_sir_mc_philox does, or NULL */
+                             void* workspace, size_t workspace_bytes, void* stream, int32_t edge_scan);
 int gnode_sir_mc_coins(const int32_t* table_src, const int32_t* table_dst, int64_t n_table, int32_t n,
                        const int32_t* seeds_host, int32_t n_seeds, double beta, double gamma, int64_t sims,
                        int32_t T, const double* coins, int64_t n_coins, uint32_t* counts,
