@@ -96,7 +96,8 @@ extern "C" size_t gnode_dmp_workspace_bytes(gnode_graph_t g) {
 extern "C" int gnode_dmp_f32(gnode_graph_t g, const float* weights, const float* gamma, const int32_t* seeds_host,
                              int32_t n_seeds, int32_t maxTime, float* out, void* workspace, size_t workspace_bytes,
                              void* stream) {
-    GN_CHECK_ARG(g && weights && gamma && out && workspace && (seeds_host || n_seeds == 0), "gnode_dmp_f32: null pointer");
+    GN_CHECK_ARG(g && gamma && out && workspace && (seeds_host || n_seeds == 0), "gnode_dmp_f32: null pointer");
+    GN_CHECK_ARG(weights || g->nnz == 0, "gnode_dmp_f32: weights is null");          // no edge, no weight: an empty tensor has no address
     GN_CHECK_ARG(maxTime >= 2, "gnode_dmp_f32: maxTime must be >= 2 (got %d)", maxTime);
     for (int i = 0; i < n_seeds; ++i)
         GN_CHECK_ARG(seeds_host[i] >= 0 && seeds_host[i] < g->info.n, "gnode_dmp_f32: seed %d out of range", seeds_host[i]);

@@ -404,7 +404,7 @@ int gnode_sir_mc_coins(const int32_t* table_src, const int32_t* table_dst, int64
  * CSR positions of the handle in row-major order (what `sp.coo_matrix(weight_adj)`
  * yields, dmp.py:67-72).
  *   weights   device fp32 [nnz]   transmission probability of each directed edge
- *                                 (the reference passes A*beta, dmp.py:349)
+ *                                 (the reference passes A*beta, dmp.py:349); may be NULL when nnz = 0
  *   gamma     device fp32 [n]     recovery probability of each node (dmp.py:349)
  *   out       device fp32 [maxTime, n, 3] = (Ps, Pi, Pr), row 0 = initial state
  *                                 (`DMP_SIR.output()`, dmp.py:159-162)

@@ -569,13 +569,17 @@ def dmp_reverse_index(rowptr, col):
     return np.array([pos.get((int(t), int(s)), nnz) for s, t in zip(src, col)], dtype=np.int64)
 
 
-def dmp_sir(rowptr, col, weights, gamma, seeds, maxTime):
+def dmp_sir(rowptr, col, weights, gamma, seeds, maxTime, dtype="float32"):
     """Dynamic message passing for SIR, reference dmp.py:74-170 (`DMP_SIR.run`), restated in float32 numpy with the
     reference's operation order.  Directed edges are the CSR positions in row-major order (what
     `sp.coo_matrix(weight_adj)` yields, dmp.py:67-72): src = row, tar = col, `weights` [nnz], `gamma` [n].
     `scatter(..., reduce='mul')` (torch_scatter, ABSENT here: parity unpinned) multiplies in ascending edge order.
-    Returns float32 [maxTime, n, 3] = (Ps, Pi, Pr) per step, step 0 = the initial condition."""
-    f = np.float32
+    Returns float32 [maxTime, n, 3] = (Ps, Pi, Pr) per step, step 0 = the initial condition.
+    dtype="float64" runs the same recurrence (the 1e-10 offset included) in double precision and returns float64: the
+    yardstick that measures the float32 rounding of the recurrence itself."""
+    f = np.dtype(dtype).type
+    if f not in (np.float32, np.float64):
+        raise ValueError(f"dmp_sir: dtype {dtype!r} is neither float32 nor float64")
     n, E = len(rowptr) - 1, len(col)
     src = np.repeat(np.arange(n, dtype=np.int64), np.diff(rowptr))
     tar = np.asarray(col, dtype=np.int64)
@@ -586,8 +590,7 @@ def dmp_sir(rowptr, col, weights, gamma, seeds, maxTime):
 
     def scatter_mul(vals, index, size):
         out = np.ones(size, dtype=f)
-        for e in range(len(vals)):                      # ascending edge order, one float32 product at a time
-            out[index[e]] = f(out[index[e]] * vals[e])
+        np.multiply.at(out, index, np.asarray(vals, dtype=f))      # unbuffered: ascending edge order, one product at a time
         return out
 
     def mulmul(theta):
@@ -620,15 +623,17 @@ def dmp_sir(rowptr, col, weights, gamma, seeds, maxTime):
 
 
 # --------------------------------------------------------------------------- mean-field baseline
-def meanfield_rk(rowptr, col, seeds, beta, gamma, deltaT, maxTime):
+def meanfield_rk(rowptr, col, seeds, beta, gamma, deltaT, maxTime, rtol=None, atol=None):
     """`runge_kutta_order4` of the reference (ode_nn.py:222-233) with its RHS `sir` (:214-220): scipy's LSODA (default
     tolerances) on t = arange(0, maxTime, deltaT), rows int(i/deltaT) kept.  The only restatement is the sparse A I
-    instead of the dense np.dot.  Returns (I, S, R), float64 [maxTime, n]."""
+    instead of the dense np.dot.  Returns (I, S, R), float64 [maxTime, n].
+    `rtol` / `atol` go to odeint as they are (None = its defaults, the reference's call); `gamma` is a scalar, as the
+    reference passes it, or one rate per node."""
     import scipy.sparse as sp
     from scipy.integrate import odeint
     n = len(rowptr) - 1
     A = sp.csr_matrix((np.ones(len(col)), np.asarray(col), np.asarray(rowptr)), shape=(n, n))
-    gam = gamma * np.ones(n)
+    gam = np.asarray(gamma, dtype=np.float64) * np.ones(n)
 
     def rhs(x, t):
         S, I = x[:n], x[n:2 * n]
@@ -637,6 +642,6 @@ def meanfield_rk(rowptr, col, seeds, beta, gamma, deltaT, maxTime):
         return np.hstack([dS, -dS - gam * I, gam * I])
 
     y0 = np.zeros(3 * n); y0[n + np.asarray(list(seeds), dtype=np.int64)] = 1.0; y0[:n] = 1.0 - y0[n:2 * n]
-    sol = odeint(rhs, y0, np.arange(0, maxTime, deltaT))
+    sol = odeint(rhs, y0, np.arange(0, maxTime, deltaT), rtol=rtol, atol=atol)
     rows = [int(i / deltaT) for i in range(int(maxTime))]
     return sol[rows, n:2 * n], sol[rows, :n], sol[rows, 2 * n:]

@@ -156,6 +156,40 @@ def test_meanfield_oracle_matches_reference_vectors(name):
         assert np.max(np.abs(got - want)) <= 1e-9
 
 
+@pytest.mark.parametrize("name", ["karate", "er120", "loops40"])
+def test_dmp_oracle_float64_mode_matches_reference_vectors(name):
+    """dmp_sir(dtype="float64"), the yardstick of tests/test_gpu_baselines.py, against the reference's own float32
+    vectors at the suite's fp32 bar: the double-precision mode is the same recurrence, not another model."""
+    d = np.load(os.path.join(os.path.dirname(__file__), "golden", f"dmp_{name}.npz"))
+    args = (d["rowptr"], d["col"], d["weights"], d["gamma"], d["seeds"].tolist(), int(d["maxTime"]))
+    got = O.dmp_sir(*args, dtype="float64")
+    assert got.shape == d["out"].shape and got.dtype == np.float64
+    _close(got, d["out"])
+    assert np.max(np.abs(got.sum(-1) - 1.0)) <= 1e-12        # Ps + Pi + Pr = 1 by construction (dmp.py:129)
+    same = O.dmp_sir(*args, dtype="float32")                 # the default, spelled out: today's bits
+    assert same.dtype == np.float32 and np.array_equal(same, d["out"])
+    with pytest.raises(ValueError):
+        O.dmp_sir(*args, dtype="float16")
+
+
+@pytest.mark.parametrize("name", ["karate", "er150"])
+def test_meanfield_oracle_tight_tolerances_match_reference_vectors(name):
+    """meanfield_rk(rtol = atol = 1e-11), the reference solution of tests/test_gpu_baselines.py, against the vectors the
+    reference produced at LSODA's default tolerances (1.5e-8 per step): 1e-6 absolute, the project's mean-field bar.
+    A per-node gamma array of equal entries is the scalar case bit for bit."""
+    d = np.load(os.path.join(os.path.dirname(__file__), "golden", f"meanfield_{name}.npz"))
+    n = len(d["rowptr"]) - 1
+    args = (d["rowptr"], d["col"], d["seeds"].tolist(), float(d["beta"]))
+    tail = (float(d["deltaT"]), int(d["maxTime"]))
+    tight = O.meanfield_rk(*args, float(d["gamma"]), *tail, rtol=1e-11, atol=1e-11)
+    for got, want in zip(tight, (d["I"], d["S"], d["R"])):
+        assert got.shape == want.shape
+        assert np.max(np.abs(got - want)) <= 1e-6
+    assert np.max(np.abs(sum(tight) - 1.0)) <= 1e-9
+    per_node = O.meanfield_rk(*args, np.full(n, float(d["gamma"])), *tail, rtol=1e-11, atol=1e-11)
+    assert all(np.array_equal(a, b) for a, b in zip(per_node, tight))
+
+
 # ---- full horizon at the BASELINE graph sizes (tests/golden/make_golden_fullsize.py): the reference's own fp32
 # output over 59 Euler steps on fb-social- and wiki-vote-sized graphs pins both CPU restatements there.
 def _synth():
