@@ -22,6 +22,11 @@
 // Per-node rates (gnode_sir_mc_philox_nodes, the NODES instances): the entry (u -> v) fires against the threshold of
 // its TARGET v (the GN-ODE's convention: row v's dS_v = -beta_v (A Z_I)_v Z_S,v) and node u recovers against its own.
 // Same coins, same 64-bit compare: constant arrays give the scalar call's counts.
+//
+// Per-edge probabilities (gnode_sir_mc_philox_edges, the EDGES instances): the entry at CSR position p, in row u with
+// col[p] = v, fires against the threshold of w[p], the probability that u infects v (source = row, target = column:
+// gnode_dmp_f32's convention for its weights).  The pattern stays symmetric; a directed contact is a zero on the reverse
+// entry.  Recovery is per node.  w[p] = beta[col[p]] gives the per-node call's counts, one constant the scalar call's.
 #include "gnode_common.h"
 #include <algorithm>
 #include <type_traits>
@@ -54,7 +59,8 @@ __device__ __forceinline__ uint32_t philox_coin(uint32_t pos, uint32_t it, uint3
 // A coin fires iff (64-bit) word < thr, thr = floor(p * 2^32) in [0, 2^32].  Scalar instances carry the two thresholds
 // as kernel arguments; the NODES instances read thr[v] from two uint64 [n] arrays in memory (staged by the host, L2
 // resident).  uint64 because 2^32 + 1 thresholds do not fit 32 bits and p = 1 must always fire: stored whole, the test
-// is the scalar one, with nothing to decode.
+// is the scalar one, with nothing to decode.  The EDGES instances (which are NODES instances: recovery stays per node) read
+// the infection threshold at the entry's CSR position instead, thr[e], from a uint64 [nnz] array staged the same way.
 template <bool NODES> using SirThr = std::conditional_t<NODES, const unsigned long long*, unsigned long long>;
 __device__ __forceinline__ unsigned long long sir_thr(unsigned long long t, int) { return t; }
 __device__ __forceinline__ unsigned long long sir_thr(const unsigned long long* t, int v) { return t[v]; }
@@ -95,12 +101,13 @@ __global__ __launch_bounds__(256) void k_fill_i16(int16_t* __restrict__ p, size_
 #ifndef GN_SIR_UNROLL
 #define GN_SIR_UNROLL 8
 #endif
-template <bool STATE_IN_LDS, bool NODES, bool TRAJ>
+template <bool STATE_IN_LDS, bool NODES, bool TRAJ, bool EDGES = false>
 __global__ __launch_bounds__(1024) void k_sir_philox(const int* __restrict__ src, const int* __restrict__ dst, long nnz,
                                                     int n, const int* __restrict__ seeds, int n_seeds,
                                                     SirThr<NODES> thr_beta, SirThr<NODES> thr_gamma,
                                                     long sims, long sim_offset, int T, uint32_t k0, uint32_t k1,
                                                     uint32_t* __restrict__ hist, uint8_t* __restrict__ gstate, SirTraj<TRAJ> tr) {
+    static_assert(NODES || !EDGES, "per-edge infection thresholds come with per-node recovery thresholds");
     extern __shared__ uint8_t smem[];
     uint8_t* state = STATE_IN_LDS ? smem : gstate + (size_t)blockIdx.x * 2 * n;
     uint8_t* flag = state + n;
@@ -145,7 +152,7 @@ __global__ __launch_bounds__(1024) void k_sir_philox(const int* __restrict__ src
                 if (ON) {                                                                                     \
                     const int v = dst[E];                                                                     \
                     if (state[v] == ST_S &&                                                                   \
-                        (unsigned long long)philox_coin((uint32_t)(E), (uint32_t)it, sim, 0u, k0, k1) < sir_thr(thr_beta, v)) \
+                        (unsigned long long)philox_coin((uint32_t)(E), (uint32_t)it, sim, 0u, k0, k1) < sir_thr(thr_beta, EDGES ? (int)(E) : v)) \
                         flag[v] = 1;                                                                          \
                 }
             long e = threadIdx.x;
@@ -208,8 +215,12 @@ __global__ __launch_bounds__(1024) void k_sir_philox(const int* __restrict__ src
 // COUNT: the profiling instantiation (gnode_sir_mc_philox_counted) also tallies Philox blocks, coins and CSR entries read.
 // NODES: per-node thresholds.  A target's threshold is read only where a coin is drawn -- in `drain`, for the (position,
 // target) pairs that passed the ever-infected test -- and the read is issued ahead of the coin's Philox rounds.
+// EDGES (with NODES): the infection threshold is read at the queued CSR position instead of the queued target -- the queue
+// already carries both, for every path into it (lane-group rows and the whole-workgroup walk of hub rows alike).  `spent`
+// and the recovery-only phase ask only whether a target is susceptible, so both stay sufficient next to w = 0 entries: a row
+// whose susceptible targets all sit behind zeros keeps being walked.  There is no COUNT && EDGES instance.
 // TRAJ: per-trajectory events and curves (SirTraj above); there is no COUNT && TRAJ instance.
-template <typename IdT, bool LISTS_IN_LDS, bool COUNT, bool NODES, bool TRAJ>
+template <typename IdT, bool LISTS_IN_LDS, bool COUNT, bool NODES, bool TRAJ, bool EDGES = false>
 __global__ __launch_bounds__(1024) void k_sir_frontier(const int* __restrict__ rowptr, const int* __restrict__ col, int n,
                                                       const int* __restrict__ seeds, int n_seeds,
                                                       SirThr<NODES> thr_beta, SirThr<NODES> thr_gamma,
@@ -217,6 +228,7 @@ __global__ __launch_bounds__(1024) void k_sir_frontier(const int* __restrict__ r
                                                       uint32_t* __restrict__ hist, int32_t* __restrict__ glists,
                                                       unsigned long long* __restrict__ stats, SirTraj<TRAJ> tr) {
     static_assert(!(COUNT && TRAJ), "the counting instantiation has no per-trajectory output");
+    static_assert(!(COUNT && EDGES) && (NODES || !EDGES), "per-edge thresholds: with per-node recovery, never counted");
     extern __shared__ uint32_t smem_w[];
     const int nwords = (n + 31) >> 5;
     const int nw4 = (nwords + 3) & ~3;
@@ -324,7 +336,7 @@ __global__ __launch_bounds__(1024) void k_sir_frontier(const int* __restrict__ r
                 if (lane_in_wave < take) {
                     const int e = cq[slot], v = cq[128 + slot];
                     if (COUNT) { ++st_blocks; ++st_ecoins; }
-                    const unsigned long long tb = sir_thr(thr_beta, v);
+                    const unsigned long long tb = sir_thr(thr_beta, EDGES ? e : v);
                     if ((unsigned long long)philox_coin((uint32_t)e, (uint32_t)it, sim, 0u, k0, k1) < tb) infect(v);
                 }
                 qn -= take;
@@ -599,10 +611,16 @@ int gn_sir_set_attributes() {       // once per device, from gnode_graph_create
     GN_HIP(hipFuncSetAttribute((const void*)k_sir_frontier<int32_t, false, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
     GN_HIP(hipFuncSetAttribute((const void*)k_sir_frontier<uint16_t, true, false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
     GN_HIP(hipFuncSetAttribute((const void*)k_sir_frontier<int32_t, false, false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
+    GN_HIP(hipFuncSetAttribute((const void*)k_sir_frontier<uint16_t, true, false, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
+    GN_HIP(hipFuncSetAttribute((const void*)k_sir_frontier<int32_t, false, false, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
+    GN_HIP(hipFuncSetAttribute((const void*)k_sir_frontier<uint16_t, true, false, true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
+    GN_HIP(hipFuncSetAttribute((const void*)k_sir_frontier<int32_t, false, false, true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
     GN_HIP(hipFuncSetAttribute((const void*)k_sir_philox<true, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
     GN_HIP(hipFuncSetAttribute((const void*)k_sir_philox<true, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
     GN_HIP(hipFuncSetAttribute((const void*)k_sir_philox<true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
     GN_HIP(hipFuncSetAttribute((const void*)k_sir_philox<true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
+    GN_HIP(hipFuncSetAttribute((const void*)k_sir_philox<true, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
+    GN_HIP(hipFuncSetAttribute((const void*)k_sir_philox<true, true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
     GN_HIP(hipFuncSetAttribute((const void*)k_sir_coins, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
     return 0;
 }
@@ -625,30 +643,42 @@ extern "C" size_t gnode_sir_nodes_workspace_bytes(gnode_graph_t g, int32_t T) {
     return g ? gnode_sir_workspace_bytes(g, T) + sir_thr_bytes(g->info.n) : 0;
 }
 
+// per-edge form: the scalar layout, then the thresholds -- uint64 [nnz] for the entries, uint64 [n] for gamma
+static size_t sir_edge_thr_bytes(gnode_graph_t g) {
+    return gn_align(((size_t)std::max<int64_t>(g->nnz, 0) + (size_t)g->info.n) * sizeof(unsigned long long));
+}
+extern "C" size_t gnode_sir_edges_workspace_bytes(gnode_graph_t g, int32_t T) {
+    return g ? gnode_sir_workspace_bytes(g, T) + sir_edge_thr_bytes(g) : 0;
+}
+
 static unsigned long long coin_threshold(double p) {
     return (unsigned long long)std::min(4294967296.0, std::max(0.0, std::floor(p * 4294967296.0)));
 }
 
-// beta_nodes / gamma_nodes: host fp64 [n] each, or both null (then the scalars beta / gamma hold for every node)
+// beta_nodes / gamma_nodes: host fp64 [n] each, or both null (then the scalars beta / gamma hold for every node).
+// edges (gnode_sir_mc_philox_edges): w_edges is host fp64 [nnz] (null only when nnz = 0), beta and beta_nodes are unused,
+// gamma_nodes may be null (then the scalar gamma holds for every node).
 static int sir_mc_philox_impl(gnode_graph_t g, const int32_t* seeds_host, int32_t n_seeds, double beta,
                               double gamma, int64_t sims, int64_t sim_offset, int32_t T, uint64_t rng_seed,
                               uint32_t* counts, void* workspace, size_t workspace_bytes, void* stream, bool edge_scan,
                               unsigned long long* stats = nullptr /* device [4]: the counting instantiation, or null */,
                               const double* beta_nodes = nullptr, const double* gamma_nodes = nullptr,
                               bool traj = false /* gnode_sir_mc_philox_traj: counts may be null, events / curves are written */,
-                              int16_t* events = nullptr, uint32_t* curves = nullptr) {
+                              int16_t* events = nullptr, uint32_t* curves = nullptr,
+                              bool edges = false, const double* w_edges = nullptr) {
     GN_CHECK_ARG(g && (counts || traj) && workspace, "gnode_sir_mc_philox: null pointer");
     GN_CHECK_ARG(!traj || ((events || curves) && !stats), "gnode_sir_mc_philox_traj: neither events nor curves given");
     GN_CHECK_ARG(!events || (T <= 32767 && ((uintptr_t)events & 1u) == 0), "gnode_sir_mc_philox_traj: events hold int16 steps (T <= 32767)");
-    const bool nodes = beta_nodes || gamma_nodes;
+    const bool nodes = !edges && (beta_nodes || gamma_nodes);
     GN_CHECK_ARG(!nodes || (beta_nodes && gamma_nodes && !stats), "gnode_sir_mc_philox_nodes: null rate array");
+    GN_CHECK_ARG(!edges || ((w_edges || g->nnz == 0) && !beta_nodes && !stats), "gnode_sir_mc_philox_edges: null weight array");
     GN_CHECK_ARG(n_seeds >= 0 && n_seeds <= 4096 && (seeds_host || n_seeds == 0), "gnode_sir_mc_philox: 0..4096 seeds");
     GN_CHECK_ARG(T >= 1 && sims >= 0 && sims <= 0xFFFFFFFFll && sim_offset >= 0 && sim_offset + sims <= 0xFFFFFFFFll,
                  "gnode_sir_mc_philox: bad T/sims/sim_offset");
     GN_CHECK_ARG(beta >= 0.0 && beta <= 1.0 && gamma >= 0.0 && gamma <= 1.0, "gnode_sir_mc_philox: beta, gamma in [0,1]");
     for (int i = 0; i < n_seeds; ++i)
         GN_CHECK_ARG(seeds_host[i] >= 0 && seeds_host[i] < g->info.n, "gnode_sir_mc_philox: seed %d out of range", seeds_host[i]);
-    const size_t ws_need = nodes ? gnode_sir_nodes_workspace_bytes(g, T) : gnode_sir_workspace_bytes(g, T);
+    const size_t ws_need = edges ? gnode_sir_edges_workspace_bytes(g, T) : nodes ? gnode_sir_nodes_workspace_bytes(g, T) : gnode_sir_workspace_bytes(g, T);
     if (workspace_bytes < ws_need) {
         gnode_set_error("gnode_sir_mc_philox: workspace %zu < %zu", workspace_bytes, ws_need);
         return GNODE_ERR_WORKSPACE;
@@ -664,10 +694,24 @@ static int sir_mc_philox_impl(gnode_graph_t g, const int32_t* seeds_host, int32_
             thr_host[(size_t)n + v] = coin_threshold(gamma_nodes[v]);
         }
     }
+    const size_t n_thr_b = edges ? (size_t)g->nnz : (size_t)g->info.n;   // infection thresholds in front of the recovery ones
+    if (edges) {
+        const int n = g->info.n;
+        thr_host.resize(n_thr_b + n);
+        for (size_t p = 0; p < n_thr_b; ++p) {
+            GN_CHECK_ARG(w_edges[p] >= 0.0 && w_edges[p] <= 1.0, "gnode_sir_mc_philox_edges: the weight at CSR position %zu, %g, is not in [0,1]", p, w_edges[p]);
+            thr_host[p] = coin_threshold(w_edges[p]);
+        }
+        for (int v = 0; v < n; ++v) {
+            const double gv = gamma_nodes ? gamma_nodes[v] : gamma;
+            GN_CHECK_ARG(gv >= 0.0 && gv <= 1.0, "gnode_sir_mc_philox_edges: gamma[%d] = %g is not in [0,1]", v, gv);
+            thr_host[n_thr_b + v] = coin_threshold(gv);
+        }
+    }
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace;
-    const unsigned long long* thr_b = (const unsigned long long*)(ws + gnode_sir_workspace_bytes(g, T));   // used when `nodes`
-    const unsigned long long* thr_g = thr_b + g->info.n;
+    const unsigned long long* thr_b = (const unsigned long long*)(ws + gnode_sir_workspace_bytes(g, T));   // used when `nodes` or `edges`
+    const unsigned long long* thr_g = thr_b + n_thr_b;
     const size_t hist_b = gn_align((size_t)2 * T * g->info.n * sizeof(uint32_t));
     uint32_t* hist = (uint32_t*)ws;
     int32_t* seeds = (int32_t*)(ws + hist_b);
@@ -692,8 +736,8 @@ static int sir_mc_philox_impl(gnode_graph_t g, const int32_t* seeds_host, int32_
     } else {
         GN_HIP(hipMemcpyAsync(seeds, seeds_host, sizeof(int32_t) * n_seeds, hipMemcpyHostToDevice, st));
     }
-    if (nodes) GN_HIP(hipMemcpyAsync((void*)thr_b, thr_host.data(), thr_host.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, st));
-    if (n_seeds > 32 || nodes) GN_HIP(hipStreamSynchronize(st));     // the host arrays are done with
+    if (nodes || edges) GN_HIP(hipMemcpyAsync((void*)thr_b, thr_host.data(), thr_host.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, st));
+    if (n_seeds > 32 || nodes || edges) GN_HIP(hipStreamSynchronize(st));     // the host arrays are done with
     const unsigned long long tb = coin_threshold(beta), tg = coin_threshold(gamma);
     const uint32_t k0 = (uint32_t)(rng_seed & 0xFFFFFFFFull), k1 = (uint32_t)(rng_seed >> 32);
     if (sims > 0) {
@@ -702,10 +746,11 @@ static int sir_mc_philox_impl(gnode_graph_t g, const int32_t* seeds_host, int32_
         const int threads_f = frontier_threads(g->info.n, g->n_bigrow, &per_cu_f);
         const size_t fl = frontier_lds_bytes(g->info.n, g->n_bigrow, threads_f);
         const size_t lds = (size_t)2 * g->info.n;
-        // one path selection and launch geometry for both forms: `nodes_tag` picks the kernels' NODES instances, whose
-        // thresholds tb_ / tg_ are the staged arrays instead of the two numbers
-        auto launch = [&](auto nodes_tag, auto traj_tag, auto tb_, auto tg_) {
-            constexpr bool NODES = decltype(nodes_tag)::value;
+        // one path selection and launch geometry for all forms: `rates_tag` (0 scalar, 1 per node, 2 per edge) picks the
+        // kernels' NODES / EDGES instances, whose thresholds tb_ / tg_ are the staged arrays instead of the two numbers
+        auto launch = [&](auto rates_tag, auto traj_tag, auto tb_, auto tg_) {
+            constexpr bool NODES = decltype(rates_tag)::value >= 1;
+            constexpr bool EDGES = decltype(rates_tag)::value == 2;
             constexpr bool TRAJ = decltype(traj_tag)::value;
             SirTraj<TRAJ> tr;
             if constexpr (TRAJ) { tr.events = events; tr.curves = curves; }
@@ -719,7 +764,7 @@ static int sir_mc_philox_impl(gnode_graph_t g, const int32_t* seeds_host, int32_
                                            n_seeds, tb_, tg_, (long)sims, (long)sim_offset, T, k0, k1, hist, (int32_t*)nullptr, stats, tr);
                         return;
                     }
-                    hipLaunchKernelGGL((k_sir_frontier<uint16_t, true, false, NODES, TRAJ>), dim3(grid), dim3(threads), fl, st, g->rowptr, g->col, g->info.n, seeds,
+                    hipLaunchKernelGGL((k_sir_frontier<uint16_t, true, false, NODES, TRAJ, EDGES>), dim3(grid), dim3(threads), fl, st, g->rowptr, g->col, g->info.n, seeds,
                                        n_seeds, tb_, tg_, (long)sims, (long)sim_offset, T, k0, k1, hist, (int32_t*)nullptr, stats, tr);
                 } else {
                     const int grid = (int)std::min<int64_t>(std::min<int64_t>(sims, (int64_t)g->info.num_cu * per_cu), kFrontierGlobalGrid);
@@ -728,7 +773,7 @@ static int sir_mc_philox_impl(gnode_graph_t g, const int32_t* seeds_host, int32_
                                            n_seeds, tb_, tg_, (long)sims, (long)sim_offset, T, k0, k1, hist, (int32_t*)gstate, stats, tr);
                         return;
                     }
-                    hipLaunchKernelGGL((k_sir_frontier<int32_t, false, false, NODES, TRAJ>), dim3(grid), dim3(threads), fl, st, g->rowptr, g->col, g->info.n, seeds,
+                    hipLaunchKernelGGL((k_sir_frontier<int32_t, false, false, NODES, TRAJ, EDGES>), dim3(grid), dim3(threads), fl, st, g->rowptr, g->col, g->info.n, seeds,
                                        n_seeds, tb_, tg_, (long)sims, (long)sim_offset, T, k0, k1, hist, (int32_t*)gstate, stats, tr);
                 }
             } else if (lds <= kLdsStateLimit) {
@@ -737,19 +782,22 @@ static int sir_mc_philox_impl(gnode_graph_t g, const int32_t* seeds_host, int32_
                 const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / std::max<size_t>(lds, 1)));
                 const int threads = per_cu >= 4 ? 256 : (per_cu >= 2 ? 512 : 1024);
                 const int grid = (int)std::min<int64_t>(sims, (int64_t)g->info.num_cu * per_cu);
-                hipLaunchKernelGGL((k_sir_philox<true, NODES, TRAJ>), dim3(grid), dim3(threads), lds, st, src, g->col, (long)g->nnz, g->info.n, seeds,
+                hipLaunchKernelGGL((k_sir_philox<true, NODES, TRAJ, EDGES>), dim3(grid), dim3(threads), lds, st, src, g->col, (long)g->nnz, g->info.n, seeds,
                                    n_seeds, tb_, tg_, (long)sims, (long)sim_offset, T, k0, k1, hist, (uint8_t*)nullptr, tr);
             } else {
                 hipLaunchKernelGGL(k_expand_rows, dim3((g->info.n + 255) / 256), dim3(256), 0, st, g->rowptr, g->info.n, src);
                 const int grid = (int)std::min<int64_t>(sims, 2048);
-                hipLaunchKernelGGL((k_sir_philox<false, NODES, TRAJ>), dim3(grid), dim3(256), 0, st, src, g->col, (long)g->nnz, g->info.n, seeds,
+                hipLaunchKernelGGL((k_sir_philox<false, NODES, TRAJ, EDGES>), dim3(grid), dim3(256), 0, st, src, g->col, (long)g->nnz, g->info.n, seeds,
                                    n_seeds, tb_, tg_, (long)sims, (long)sim_offset, T, k0, k1, hist, gstate, tr);
             }
         };
-        if (nodes && traj) launch(std::true_type{}, std::true_type{}, thr_b, thr_g);
-        else if (nodes) launch(std::true_type{}, std::false_type{}, thr_b, thr_g);
-        else if (traj) launch(std::false_type{}, std::true_type{}, tb, tg);
-        else launch(std::false_type{}, std::false_type{}, tb, tg);
+        using Scalar = std::integral_constant<int, 0>; using Nodes = std::integral_constant<int, 1>; using Edges = std::integral_constant<int, 2>;
+        if (edges && traj) launch(Edges{}, std::true_type{}, thr_b, thr_g);
+        else if (edges) launch(Edges{}, std::false_type{}, thr_b, thr_g);
+        else if (nodes && traj) launch(Nodes{}, std::true_type{}, thr_b, thr_g);
+        else if (nodes) launch(Nodes{}, std::false_type{}, thr_b, thr_g);
+        else if (traj) launch(Scalar{}, std::true_type{}, tb, tg);
+        else launch(Scalar{}, std::false_type{}, tb, tg);
         if (sampled) gn_prof_end(3, st);
         GN_LAUNCH_CHECK();
     }
@@ -823,6 +871,25 @@ extern "C" int gnode_sir_mc_philox_traj(gnode_graph_t g, const int32_t* seeds_ho
     const bool nodes = beta_host != nullptr;
     return sir_mc_philox_impl(g, seeds_host, n_seeds, nodes ? 0.0 : beta, nodes ? 0.0 : gamma, sims, sim_offset, T, rng_seed, counts,
                               workspace, workspace_bytes, stream, edge_scan != 0, nullptr, beta_host, gamma_host, true, events, curves);
+}
+
+// Per-edge transmission probabilities (include/gnode.h): w_host[p] is the probability that the row of CSR position p infects
+// col[p].  The same impl -- validation, path selection, geometry, coins -- through the kernels' EDGES instances.
+extern "C" int gnode_sir_mc_philox_edges(gnode_graph_t g, const int32_t* seeds_host, int32_t n_seeds, const double* w_host,
+                                         double gamma, const double* gamma_host, int64_t sims, int64_t sim_offset, int32_t T,
+                                         uint64_t rng_seed, uint32_t* counts, void* workspace, size_t workspace_bytes, void* stream,
+                                         int32_t edge_scan) {
+    return sir_mc_philox_impl(g, seeds_host, n_seeds, 0.0, gamma_host ? 0.0 : gamma, sims, sim_offset, T, rng_seed, counts, workspace,
+                              workspace_bytes, stream, edge_scan != 0, nullptr, nullptr, gamma_host, false, nullptr, nullptr, true, w_host);
+}
+extern "C" int gnode_sir_mc_philox_traj_edges(gnode_graph_t g, const int32_t* seeds_host, int32_t n_seeds, const double* w_host,
+                                              double gamma, const double* gamma_host, int64_t sims, int64_t sim_offset, int32_t T,
+                                              uint64_t rng_seed, int16_t* events, uint32_t* curves, uint32_t* counts, void* workspace,
+                                              size_t workspace_bytes, void* stream, int32_t edge_scan) {
+    GN_CHECK_ARG(events || curves, "gnode_sir_mc_philox_traj_edges: neither events nor curves given");
+    GN_CHECK_ARG(!events || T <= 32767, "gnode_sir_mc_philox_traj_edges: events hold int16 steps, T = %d > 32767", T);
+    return sir_mc_philox_impl(g, seeds_host, n_seeds, 0.0, gamma_host ? 0.0 : gamma, sims, sim_offset, T, rng_seed, counts, workspace,
+                              workspace_bytes, stream, edge_scan != 0, nullptr, nullptr, gamma_host, true, events, curves, true, w_host);
 }
 
 extern "C" int gnode_sir_mc_coins(const int32_t* table_src, const int32_t* table_dst, int64_t n_table, int32_t n,

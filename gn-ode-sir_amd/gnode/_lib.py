@@ -75,6 +75,9 @@ ABI = {
     "gnode_sir_mc_philox_nodes": (_int, [_vp, _vp, _i32, _vp, _vp, _i64, _i64, _i32, _u64, _vp, _vp, _sz, _vp, _i32]),
     "gnode_sir_traj_workspace_bytes": (_sz, [_vp, _i32]),
     "gnode_sir_mc_philox_traj": (_int, [_vp, _vp, _i32, _f64, _f64, _vp, _vp, _i64, _i64, _i32, _u64, _vp, _vp, _vp, _vp, _sz, _vp, _i32]),
+    "gnode_sir_edges_workspace_bytes": (_sz, [_vp, _i32]),
+    "gnode_sir_mc_philox_edges": (_int, [_vp, _vp, _i32, _vp, _f64, _vp, _i64, _i64, _i32, _u64, _vp, _vp, _sz, _vp, _i32]),
+    "gnode_sir_mc_philox_traj_edges": (_int, [_vp, _vp, _i32, _vp, _f64, _vp, _i64, _i64, _i32, _u64, _vp, _vp, _vp, _vp, _sz, _vp, _i32]),
     "gnode_sir_mc_coins": (_int, [_vp, _vp, _i64, _i32, _vp, _i32, _f64, _f64, _i64, _i32, _vp, _i64, _vp, _pi64, _vp, _sz, _vp]),
     "gnode_dmp_workspace_bytes": (_sz, [_vp]),
     "gnode_dmp_f32": (_int, [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _sz, _vp]),

@@ -75,17 +75,92 @@ def _node_rates(name: str, value, n: int):
     return np.ascontiguousarray(a)
 
 
+class EdgeRates:
+    """Per-edge transmission probabilities for `sir_counts` / `sir_trajectories` / `sir_torch` (pass it as `beta`): `w`, a
+    validated contiguous float64 [nnz] host array in the CSR position order of the graph it was made for (n nodes).  w[p] is
+    the probability per step that the row of position p infects col[p].  Made by `edge_rates`."""
+
+    def __init__(self, w: np.ndarray, n: int):
+        self.w, self.n, self.nnz = w, int(n), int(w.shape[0])
+
+
+def _host_csr(graph):
+    """(n, rowptr, col) on the host of a DeviceGraph, a networkx graph (the CSR sir_torch builds for it) or a (rowptr, col) pair."""
+    if hasattr(graph, "number_of_nodes"):
+        rp, ci = _csr_from_edges(graph.number_of_nodes(), _edge_arrays(graph))
+    elif isinstance(graph, (tuple, list)):
+        rp, ci = graph
+    else:
+        rp, ci = graph.rowptr, graph.col
+    rp, ci = np.asarray(rp, dtype=np.int64), np.asarray(ci, dtype=np.int64)
+    return int(rp.shape[0] - 1), rp, ci
+
+
+def edge_rates(graph, M) -> EdgeRates:
+    """Per-edge transmission probabilities in the graph's CSR position order, for `beta` of the Monte-Carlo calls.
+
+    graph: a DeviceGraph, a networkx graph, or a (rowptr, col) pair.  M: an array of length nnz already in CSR position
+    order, or a scipy sparse [n, n] matrix with M[u, v] = the probability per step that the infected u infects the
+    susceptible v (source = row, target = column: what `DMP_SIR` takes as `weight_adj`, so one matrix serves both).
+    Entries of the pattern that M does not store are 0: the graph's pattern is symmetric, and a directed contact u -> v is
+    M[u, v] > 0 with M[v, u] absent or 0.  Raises ValueError for a wrong shape, a NaN, a value outside [0, 1] and a
+    non-zero entry of M outside the pattern."""
+    n, rp, ci = _host_csr(graph)
+    nnz = int(ci.shape[0])
+    if sp.issparse(M):
+        if M.shape != (n, n):
+            raise ValueError(f"edge_rates: the matrix must have shape ({n}, {n}), got {tuple(M.shape)}")
+        m = sp.coo_matrix(M, dtype=np.float64)
+        m.sum_duplicates()
+        keep = m.data != 0.0                                        # (a NaN is kept: it is not an absent entry)
+        mr, mc, mv = m.row[keep].astype(np.int64), m.col[keep].astype(np.int64), m.data[keep]
+        key = np.repeat(np.arange(n, dtype=np.int64), np.diff(rp)) * n + ci        # of every CSR position
+        order = np.argsort(key, kind="stable")
+        at = np.searchsorted(key[order], mr * n + mc)
+        hit = at < nnz
+        hit[hit] = key[order][at[hit]] == (mr * n + mc)[hit]
+        if not hit.all():
+            k = int(np.flatnonzero(~hit)[0])
+            raise ValueError(f"edge_rates: M[{int(mr[k])}, {int(mc[k])}] = {mv[k]} lies outside the graph's pattern")
+        w = np.zeros(nnz, dtype=np.float64)
+        w[order[at]] = mv
+    else:
+        if isinstance(M, torch.Tensor):
+            M = M.detach().cpu().numpy()
+        w = np.array(M, dtype=np.float64)
+        if w.shape != (nnz,):
+            raise ValueError(f"edge_rates: per-edge rates must have shape ({nnz},), got {tuple(w.shape)}")
+    bad = np.flatnonzero(~((w >= 0.0) & (w <= 1.0)))                # a NaN fails both comparisons
+    if bad.size:
+        raise ValueError(f"edge_rates: the rate at CSR position {int(bad[0])}, {w[bad[0]]}, is not a probability in [0, 1]")
+    return EdgeRates(np.ascontiguousarray(w), n)
+
+
+def _edge_rate_args(er: EdgeRates, gamma, graph):
+    """The rate arguments of the gnode_sir_mc_philox*_edges entries -- (w, gamma, gamma_host) -- and the host array to keep
+    alive; raises ValueError when `er` was made for another graph or gamma is not a rate."""
+    if (er.n, er.nnz) != (graph.n, graph.nnz):
+        raise ValueError(f"EdgeRates of a graph with {er.n} nodes / {er.nnz} entries given for one with {graph.n} / {graph.nnz}")
+    g = _node_rates("gamma", gamma, graph.n)
+    if g is None:
+        _node_rates("gamma", np.full(1, float(gamma)), 1)           # the scalar, through the same check
+        return (_lib.host_ptr(er.w), float(gamma), None), g
+    return (_lib.host_ptr(er.w), 0.0, _lib.host_ptr(g)), g
+
+
 def _philox_launch(entry: str, graph: DeviceGraph, seed_set, beta, gamma, sims, T, rng_seed, sim_offset, device, counts, *extra,
                    ws_entry: str = "gnode_sir_workspace_bytes"):
     """One launch of a gnode_sir_mc_philox* entry into `counts` (zeros [3, T, n] on `device` when None); returns counts.
-    beta / gamma: numbers, or (gnode_sir_mc_philox_nodes) float64 [n] host arrays."""
+    beta / gamma: numbers, or (gnode_sir_mc_philox_nodes) float64 [n] host arrays; or (gnode_sir_mc_philox_edges) an
+    EdgeRates and a number or array."""
     lib = _lib.load()
     seeds = np.ascontiguousarray(list(seed_set), dtype=np.int32)
     if counts is None:
         counts = torch.zeros((3, T, graph.n), dtype=torch.int32, device=device)
     ws = torch.empty(getattr(lib, ws_entry)(graph.handle, T), dtype=torch.uint8, device=counts.device)
     rate = lambda r: _lib.host_ptr(r) if isinstance(r, np.ndarray) and r.ndim == 1 else float(r)
-    _lib.check(getattr(lib, entry)(graph.handle, _lib.host_ptr(seeds), int(seeds.shape[0]), rate(beta), rate(gamma),
+    rates, _alive = _edge_rate_args(beta, gamma, graph) if isinstance(beta, EdgeRates) else ((rate(beta), rate(gamma)), None)
+    _lib.check(getattr(lib, entry)(graph.handle, _lib.host_ptr(seeds), int(seeds.shape[0]), *rates,
                                    int(sims), int(sim_offset), int(T), C.c_uint64(int(rng_seed) & (2**64 - 1)),
                                    _lib.ptr(counts), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(), *extra))
     return counts
@@ -102,7 +177,14 @@ def sir_counts(graph: DeviceGraph, seed_set, beta, gamma, sims, T, rng_seed, sim
     torch tensor): beta[v] is the probability that an infected neighbour infects the susceptible v in a step (indexed by
     the target, as x[:, 3] of the GN-ODE), gamma[u] that the infected u recovers.  Two numbers take the scalar entry as
     before; anything else goes through `gnode_sir_mc_philox_nodes` (same coins: constant arrays give the scalar counts),
-    which synchronises the stream.  A wrong length, a NaN or a value outside [0, 1] raises ValueError."""
+    which synchronises the stream.  A wrong length, a NaN or a value outside [0, 1] raises ValueError.
+
+    beta may also be an `EdgeRates` (from `edge_rates`): one transmission probability per directed CSR entry, source = row,
+    target = column, through `gnode_sir_mc_philox_edges`; gamma stays a number or per-node rates."""
+    if isinstance(beta, EdgeRates):
+        _edge_rate_args(beta, gamma, graph)                         # (ValueError before the library is entered)
+        return _philox_launch("gnode_sir_mc_philox_edges", graph, seed_set, beta, gamma, sims, T, rng_seed, sim_offset, device, counts,
+                              int(bool(edge_scan)), ws_entry="gnode_sir_edges_workspace_bytes")
     b, g = _node_rates("beta", beta, graph.n), _node_rates("gamma", gamma, graph.n)
     if b is not None or g is not None:
         b = _node_rates("beta", np.full(graph.n, float(beta)), graph.n) if b is None else b
@@ -122,10 +204,19 @@ class SirTrajectories(NamedTuple):
 
 def _traj_launch(graph: DeviceGraph, seed_set, b, g, sims, T, rng_seed, sim_offset, ev, cv, counts, edge_scan):
     """One gnode_sir_mc_philox_traj launch into ev (int16 [2, sims, n] or None), cv (int32 [sims, T, 3] or None) and counts
-    (int32 [3, T, n], accumulated, or None).  b / g: two numbers, or two float64 [n] host arrays (`_node_rates`)."""
+    (int32 [3, T, n], accumulated, or None).  b / g: two numbers, or two float64 [n] host arrays (`_node_rates`); or an
+    EdgeRates and a number or array (gnode_sir_mc_philox_traj_edges)."""
     lib = _lib.load()
     seeds = np.ascontiguousarray(list(seed_set), dtype=np.int32)
     dev = (ev if ev is not None else cv).device
+    if isinstance(b, EdgeRates):
+        rates, _alive = _edge_rate_args(b, g, graph)
+        ws = torch.empty(lib.gnode_sir_edges_workspace_bytes(graph.handle, T), dtype=torch.uint8, device=dev)
+        _lib.check(lib.gnode_sir_mc_philox_traj_edges(graph.handle, _lib.host_ptr(seeds), int(seeds.shape[0]), *rates,
+                                                      int(sims), int(sim_offset), int(T), C.c_uint64(int(rng_seed) & (2**64 - 1)),
+                                                      _lib.ptr(ev), _lib.ptr(cv), _lib.ptr(counts), _lib.ptr(ws), ws.numel(),
+                                                      _lib.stream_ptr(), int(bool(edge_scan))))
+        return
     ws = torch.empty(lib.gnode_sir_traj_workspace_bytes(graph.handle, T), dtype=torch.uint8, device=dev)
     arrays = isinstance(b, np.ndarray)
     _lib.check(lib.gnode_sir_mc_philox_traj(graph.handle, _lib.host_ptr(seeds), int(seeds.shape[0]),
@@ -147,18 +238,22 @@ def sir_trajectories(graph_or_G, seed_set, beta, gamma, sims, T, rng_seed=None, 
     (events take 4 * sims * n bytes: shard large runs).  `sir_state_at`, `sir_counts_from_events` and
     `sir_curves_from_events` read the events; the second returns what `sir_counts` of the same arguments returns.
 
-    graph_or_G: a DeviceGraph or a networkx graph.  beta / gamma: as in `sir_counts`.  rng_seed=None draws the seed from
+    graph_or_G: a DeviceGraph or a networkx graph.  beta / gamma: as in `sir_counts` (an `EdgeRates` for beta included).  rng_seed=None draws the seed from
     torch's CPU generator, as `sir_torch` does.  events=False / curves=False leave that output out (None in the result);
     `counts` (int32 [3, T, n]) is accumulated into as by `sir_counts`.  edge_scan=True runs the edge-parallel kernel.
     Raises ValueError for bad rates, for T > 32767 with events, and when neither output is requested."""
     graph = _device_graph_for(graph_or_G) if hasattr(graph_or_G, "number_of_nodes") else graph_or_G
     n = graph.n
-    b, g = _node_rates("beta", beta, n), _node_rates("gamma", gamma, n)
-    if b is not None or g is not None:
-        b = _node_rates("beta", np.full(n, float(beta)), n) if b is None else b
-        g = _node_rates("gamma", np.full(n, float(gamma)), n) if g is None else g
+    if isinstance(beta, EdgeRates):
+        _edge_rate_args(beta, gamma, graph)                         # (ValueError before anything is allocated)
+        b, g = beta, gamma
     else:
-        b, g = float(beta), float(gamma)
+        b, g = _node_rates("beta", beta, n), _node_rates("gamma", gamma, n)
+        if b is not None or g is not None:
+            b = _node_rates("beta", np.full(n, float(beta)), n) if b is None else b
+            g = _node_rates("gamma", np.full(n, float(gamma)), n) if g is None else g
+        else:
+            b, g = float(beta), float(gamma)
     if not events and not curves:
         raise ValueError("sir_trajectories: neither events nor curves requested")
     if events and T > 32767:
@@ -258,12 +353,13 @@ def sir_torch(G, seed_set, beta, gamma, sims=10000, T=20, rng_seed=None, coins=N
     True scales row 0 by `sims` so that counts/sims is the initial state itself.
 
     Per-node rates (extension): in production mode beta and gamma may each be an array of length n indexed by node id
-    (see `sir_counts`).  The recorded-stream parity mode takes numbers only.
+    (see `sir_counts`), and beta an `EdgeRates` made by `edge_rates(G, M)`: one probability per directed contact.  The
+    recorded-stream parity mode takes numbers only.
     """
     n = G.number_of_nodes()
     if coins is not None:
-        if _node_rates("beta", beta, n) is not None or _node_rates("gamma", gamma, n) is not None:
-            raise ValueError("sir_torch(coins=...): the parity mode takes scalar beta and gamma, not per-node arrays")
+        if isinstance(beta, EdgeRates) or _node_rates("beta", beta, n) is not None or _node_rates("gamma", gamma, n) is not None:
+            raise ValueError("sir_torch(coins=...): the parity mode takes scalar beta and gamma, not per-node arrays or EdgeRates")
         e = _edge_arrays(G)
         table = np.empty((2 * e.shape[0], 2), dtype=np.int64)     # reference :32-38
         table[0::2, 0], table[0::2, 1] = e[:, 0], e[:, 1]

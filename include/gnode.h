@@ -20,7 +20,7 @@
  *     into a hipGraph on first use and one handle may serve several streams (each
  *     with its own workspace).  Functions that DO synchronise `stream` say so below
  *     (gnode_graph_create, gnode_sir_mc_philox with more than 32 seeds,
- *     gnode_sir_mc_philox_nodes, gnode_sir_mc_philox_traj with more than 32 seeds or rate arrays, gnode_sir_mc_coins, gnode_dmp_f32, gnode_meanfield_f64).
+ *     gnode_sir_mc_philox_nodes, gnode_sir_mc_philox_edges, gnode_sir_mc_philox_traj_edges, gnode_sir_mc_philox_traj with more than 32 seeds or rate arrays, gnode_sir_mc_coins, gnode_dmp_f32, gnode_meanfield_f64).
  *   - process-wide state: (1) a per-device "set up once" table (compute-unit count,
  *     dynamic-LDS kernel attributes), written under a lock by the first
  *     gnode_graph_create on a device and read-only afterwards; (2) the opt-in
@@ -393,6 +393,34 @@ int gnode_sir_mc_philox_traj(gnode_graph_t g, const int32_t* seeds_host, int32_t
                              uint32_t* curves,   /* device [sims, T, 3], OVERWRITTEN, or NULL */
                              uint32_t* counts,   /* device [3, T, n], ACCUMULATED as gnode_sir_mc_philox does, or NULL */
                              void* workspace, size_t workspace_bytes, void* stream, int32_t edge_scan);
+/* Per-edge transmission probabilities (no version step: a stale library is known by the missing symbol): the same model,
+ * coins and counts with one probability per directed CSR entry.
+ *   w_host      host fp64 [nnz], in CSR position order.  The entry at position p, in row u with col[p] = v, u infected and v
+ *               susceptible in the pre-step state, fires iff coin(p) < thr(w_host[p]): w_host[p] is the probability that u
+ *               infects v -- the SOURCE is the row, the TARGET the column, the convention of gnode_dmp_f32's `weights`, so one
+ *               array serves both.  The handle's pattern stays symmetric; a directed contact u -> v is a zero on the reverse
+ *               entry (v -> u).  May be NULL when nnz = 0.
+ *   gamma       the recovery probability of every node, used when gamma_host is NULL
+ *   gamma_host  host fp64 [n] or NULL: the infected node u recovers iff coin(u) < thr(gamma_host[u])
+ * thr as above, compared in 64 bits: an array that holds one constant gives gnode_sir_mc_philox's counts exactly, w_host[p] =
+ * beta[col[p]] gives gnode_sir_mc_philox_nodes' exactly, 0 never fires, 1 always does.  Every weight and rate is validated on
+ * the host (a NaN or a value outside [0, 1]: GNODE_ERR_ARG, the message names the CSR position); the thresholds -- uint64
+ * [nnz], then uint64 [n] -- are staged through the workspace behind gnode_sir_mc_philox's layout.  Both calls SYNCHRONISE
+ * `stream`, because host arrays are staged.  edge_scan as in gnode_sir_mc_philox_nodes.  gnode_sir_mc_philox_traj_edges takes
+ * events / curves / counts under the rules of gnode_sir_mc_philox_traj; both calls use gnode_sir_edges_workspace_bytes. */
+size_t gnode_sir_edges_workspace_bytes(gnode_graph_t g, int32_t T);
+int gnode_sir_mc_philox_edges(gnode_graph_t g, const int32_t* seeds_host, int32_t n_seeds,
+                              const double* w_host,                       /* host fp64 [nnz], CSR position order */
+                              double gamma, const double* gamma_host,     /* host fp64 [n], or NULL: then the scalar */
+                              int64_t sims, int64_t sim_offset, int32_t T, uint64_t rng_seed, uint32_t* counts,
+                              void* workspace, size_t workspace_bytes, void* stream, int32_t edge_scan);
+int gnode_sir_mc_philox_traj_edges(gnode_graph_t g, const int32_t* seeds_host, int32_t n_seeds,
+                                   const double* w_host, double gamma, const double* gamma_host,
+                                   int64_t sims, int64_t sim_offset, int32_t T, uint64_t rng_seed,
+                                   int16_t* events,    /* device [2, sims, n], OVERWRITTEN, or NULL */
+                                   uint32_t* curves,   /* device [sims, T, 3], OVERWRITTEN, or NULL */
+                                   uint32_t* counts,   /* device [3, T, n], ACCUMULATED, or NULL */
+                                   void* workspace, size_t workspace_bytes, void* stream, int32_t edge_scan);
 int gnode_sir_mc_coins(const int32_t* table_src, const int32_t* table_dst, int64_t n_table, int32_t n,
                        const int32_t* seeds_host, int32_t n_seeds, double beta, double gamma, int64_t sims,
                        int32_t T, const double* coins, int64_t n_coins, uint32_t* counts,
