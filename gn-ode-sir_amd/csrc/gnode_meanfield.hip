@@ -63,6 +63,13 @@ __global__ __launch_bounds__(256) void k_mf_init(const double* __restrict__ seed
     y[u] = 1.0 - seed[u]; y[n + u] = seed[u]; y[2 * (size_t)n + u] = 0.0;
 }
 
+// gnode_meanfield_init_f64: y(0) = the caller's [n][3] = (pS, pI, pR)
+__global__ __launch_bounds__(256) void k_mf_init_state(const double* __restrict__ init, int n, double* __restrict__ y) {
+    const int u = blockIdx.x * 256 + threadIdx.x;
+    if (u >= n) return;
+    y[u] = init[(size_t)u * 3]; y[n + u] = init[(size_t)u * 3 + 1]; y[2 * (size_t)n + u] = init[(size_t)u * 3 + 2];
+}
+
 // out rows (I, S, R order of the reference's return value, ode_nn.py:233): out[c][t][u]
 __global__ __launch_bounds__(256) void k_mf_emit(const double* __restrict__ y, int n, int t, int T, double* __restrict__ outI,
                                                 double* __restrict__ outS, double* __restrict__ outR) {
@@ -77,19 +84,20 @@ extern "C" size_t gnode_meanfield_workspace_bytes(gnode_graph_t g) {
     return 10 * v + gn_align((size_t)g->info.n * sizeof(double)) + 256;      // y, ynew, ytmp, K[7] | seed | err
 }
 
-extern "C" int gnode_meanfield_f64(gnode_graph_t g, const int32_t* seeds_host, int32_t n_seeds, double beta,
-                                   const double* gamma, const double* t_out_host, int32_t n_out, double rtol, double atol,
-                                   double* outI, double* outS,
-                                   double* outR, int64_t* steps_host, void* workspace, size_t workspace_bytes, void* stream) {
-    GN_CHECK_ARG(g && gamma && outI && outS && outR && workspace && (seeds_host || n_seeds == 0), "gnode_meanfield_f64: null pointer");
-    GN_CHECK_ARG(t_out_host && n_out >= 1 && t_out_host[0] == 0.0, "gnode_meanfield_f64: need output times starting at 0");
+// `who`: the entry's name for the messages.  init: device fp64 [n][3] (gnode_meanfield_init_f64), or null: then the seed list holds
+static int meanfield_impl(const char* who, gnode_graph_t g, const int32_t* seeds_host, int32_t n_seeds, const double* init, double beta,
+                          const double* gamma, const double* t_out_host, int32_t n_out, double rtol, double atol,
+                          double* outI, double* outS,
+                          double* outR, int64_t* steps_host, void* workspace, size_t workspace_bytes, void* stream) {
+    GN_CHECK_ARG(g && gamma && outI && outS && outR && workspace && (init || seeds_host || n_seeds == 0), "%s: null pointer", who);
+    GN_CHECK_ARG(t_out_host && n_out >= 1 && t_out_host[0] == 0.0, "%s: need output times starting at 0", who);
     for (int i = 1; i < n_out; ++i)
-        GN_CHECK_ARG(t_out_host[i] >= t_out_host[i - 1], "gnode_meanfield_f64: output times must be ascending");
-    GN_CHECK_ARG(rtol > 0 && atol > 0, "gnode_meanfield_f64: tolerances must be positive");
+        GN_CHECK_ARG(t_out_host[i] >= t_out_host[i - 1], "%s: output times must be ascending", who);
+    GN_CHECK_ARG(rtol > 0 && atol > 0, "%s: tolerances must be positive", who);
     for (int i = 0; i < n_seeds; ++i)
-        GN_CHECK_ARG(seeds_host[i] >= 0 && seeds_host[i] < g->info.n, "gnode_meanfield_f64: seed %d out of range", seeds_host[i]);
+        GN_CHECK_ARG(seeds_host[i] >= 0 && seeds_host[i] < g->info.n, "%s: seed %d out of range", who, seeds_host[i]);
     if (workspace_bytes < gnode_meanfield_workspace_bytes(g)) {
-        gnode_set_error("gnode_meanfield_f64: workspace %zu < %zu", workspace_bytes, gnode_meanfield_workspace_bytes(g));
+        gnode_set_error("%s: workspace %zu < %zu", who, workspace_bytes, gnode_meanfield_workspace_bytes(g));
         return GNODE_ERR_WORKSPACE;
     }
     hipStream_t st = (hipStream_t)stream;
@@ -102,11 +110,15 @@ extern "C" int gnode_meanfield_f64(gnode_graph_t g, const int32_t* seeds_host, i
     double* seed = (double*)(ws + 10 * v);
     unsigned long long* err = (unsigned long long*)(ws + 10 * v + gn_align((size_t)n * sizeof(double)));
     // K is indexed K[j * len + i]: lay the 7 stages out back to back in elements (7 * len doubles fit in 7 aligned slots)
-    GN_HIP(hipMemsetAsync(seed, 0, (size_t)n * sizeof(double), st));
-    const double one = 1.0;
-    for (int i = 0; i < n_seeds; ++i) GN_HIP(hipMemcpyAsync(seed + seeds_host[i], &one, sizeof(double), hipMemcpyHostToDevice, st));
     const unsigned ng = (unsigned)((n + 255) / 256), lg = (unsigned)((len + 255) / 256);
-    hipLaunchKernelGGL(k_mf_init, dim3(ng), dim3(256), 0, st, seed, n, y);
+    const double one = 1.0;
+    if (init) {
+        hipLaunchKernelGGL(k_mf_init_state, dim3(ng), dim3(256), 0, st, init, n, y);
+    } else {
+        GN_HIP(hipMemsetAsync(seed, 0, (size_t)n * sizeof(double), st));
+        for (int i = 0; i < n_seeds; ++i) GN_HIP(hipMemcpyAsync(seed + seeds_host[i], &one, sizeof(double), hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_mf_init, dim3(ng), dim3(256), 0, st, seed, n, y);
+    }
     hipLaunchKernelGGL(k_mf_emit, dim3(ng), dim3(256), 0, st, y, n, 0, n_out, outI, outS, outR);
     GN_LAUNCH_CHECK();
     GN_HIP(hipStreamSynchronize(st));                                 // `one` / seeds_host are done with
@@ -149,9 +161,9 @@ extern "C" int gnode_meanfield_f64(gnode_graph_t g, const int32_t* seeds_host, i
             GN_HIP(hipStreamSynchronize(st));
             double e;
             memcpy(&e, &eb, sizeof(e));
-            GN_CHECK_ARG(std::isfinite(e), "gnode_meanfield_f64: non-finite state at t=%g", t);
+            GN_CHECK_ARG(std::isfinite(e), "%s: non-finite state at t=%g", who, t);
             ++steps;
-            GN_CHECK_ARG(steps < 2000000, "gnode_meanfield_f64: step count exploded (h=%g at t=%g)", hh, t);
+            GN_CHECK_ARG(steps < 2000000, "%s: step count exploded (h=%g at t=%g)", who, hh, t);
             if (e <= 1.0) {                                           // accept
                 t = (hh == t_end - t) ? t_end : t + hh;
                 std::swap(y, ynew);
@@ -165,4 +177,22 @@ extern "C" int gnode_meanfield_f64(gnode_graph_t g, const int32_t* seeds_host, i
     }
     if (steps_host) *steps_host = steps;
     return 0;
+}
+
+extern "C" int gnode_meanfield_f64(gnode_graph_t g, const int32_t* seeds_host, int32_t n_seeds, double beta,
+                                   const double* gamma, const double* t_out_host, int32_t n_out, double rtol, double atol,
+                                   double* outI, double* outS,
+                                   double* outR, int64_t* steps_host, void* workspace, size_t workspace_bytes, void* stream) {
+    return meanfield_impl("gnode_meanfield_f64", g, seeds_host, n_seeds, nullptr, beta, gamma, t_out_host, n_out, rtol, atol, outI, outS, outR, steps_host,
+                          workspace, workspace_bytes, stream);
+}
+
+// The same integration from y(0) = init (device fp64 [n][3]); the workspace is gnode_meanfield_workspace_bytes'.
+extern "C" int gnode_meanfield_init_f64(gnode_graph_t g, const double* init, double beta, const double* gamma,
+                                        const double* t_out_host, int32_t n_out, double rtol, double atol, double* outI,
+                                        double* outS, double* outR, int64_t* steps_host, void* workspace, size_t workspace_bytes,
+                                        void* stream) {
+    GN_CHECK_ARG(init, "gnode_meanfield_init_f64: null pointer");
+    return meanfield_impl("gnode_meanfield_init_f64", g, nullptr, 0, init, beta, gamma, t_out_host, n_out, rtol, atol, outI, outS, outR, steps_host, workspace,
+                          workspace_bytes, stream);
 }

@@ -27,8 +27,15 @@
 // col[p] = v, fires against the threshold of w[p], the probability that u infects v (source = row, target = column:
 // gnode_dmp_f32's convention for its weights).  The pattern stays symmetric; a directed contact is a zero on the reverse
 // entry.  Recovery is per node.  w[p] = beta[col[p]] gives the per-node call's counts, one constant the scalar call's.
+//
+// Initial-state distributions (gnode_sir_mc_philox_init, the INIT instances): they take uint64 [2][n] -- thr(pS) and thr(pR)
+// per node -- and each trajectory DRAWS its start, one coin per node (kind 2, step 0; sir_init_draw below), in place of the
+// seed phase; the step loops do not know which form ran.  Row 0 of the counts is then accumulated like every other row
+// (k_sir_finalize<ACC0>).  Separate instances, not a run-time test in the shared ones: that form was measured and cost the
+// seed-list call 2 % at fb-social size, so the seed-list instances are the code they were before.
 #include "gnode_common.h"
 #include <algorithm>
+#include <cmath>
 #include <type_traits>
 #include <vector>
 
@@ -65,6 +72,28 @@ template <bool NODES> using SirThr = std::conditional_t<NODES, const unsigned lo
 __device__ __forceinline__ unsigned long long sir_thr(unsigned long long t, int) { return t; }
 __device__ __forceinline__ unsigned long long sir_thr(const unsigned long long* t, int v) { return t[v]; }
 
+// --------------------------------------------------------------------------- drawn initial state
+// Node v of trajectory `sim` starts in S iff coin < thr(pS), else in R iff coin >= 2^32 - thr(pR), else in I; coin = word
+// (v & 3) of philox(ctr = (v >> 2, step 0, sim, kind 2)): four consecutive nodes share a block, as the recovery coins do.
+// A one-hot row never depends on the coin (thresholds 0 and 2^32).  A thread takes the block of nodes 4q .. 4q + 3: two
+// nibbles, bit j = node 4q + j -- `inf` (starts in I) and `rec` (starts in R).
+__device__ __forceinline__ void sir_init_draw(const unsigned long long* __restrict__ init_thr, int n, int q, uint32_t sim,
+                                              uint32_t k0, uint32_t k1, uint32_t& inf, uint32_t& rec) {
+    uint32_t w[4];
+    philox_block((uint32_t)q, 0u, sim, 2u, k0, k1, w);
+    inf = 0; rec = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int v = 4 * q + j;
+        if (v < n) {
+            const unsigned long long c = w[j];
+            if (c >= init_thr[v]) {
+                if (c >= 4294967296ull - init_thr[(size_t)n + v]) rec |= 1u << j; else inf |= 1u << j;
+            }
+        }
+    }
+}
+
 // --------------------------------------------------------------------------- per-trajectory output
 // TRAJ instances (gnode_sir_mc_philox_traj) also keep what the histograms fold away.  events: int16 [2][sims][n], the step
 // at which node v of the call's s-th trajectory was infected (plane 0; 0 for seeds) and recovered (plane 1), over a -1
@@ -74,6 +103,11 @@ __device__ __forceinline__ unsigned long long sir_thr(const unsigned long long* 
 // take an empty struct and compile to what they were.
 template <bool TRAJ> struct SirTraj {};
 template <> struct SirTraj<true> { int16_t* events; uint32_t* curves; };
+
+// INIT instances (gnode_sir_mc_philox_init) take the start thresholds, uint64 [2][n]; the others take an empty struct, as
+// with SirTraj, and compile to what they were: the drawn start is no part of a seed-list instance.
+template <bool INIT> struct SirInit {};
+template <> struct SirInit<true> { const unsigned long long* thr; };
 
 __device__ __forceinline__ void sir_curve_row(uint32_t* __restrict__ curves, long s, int T, int row, int n, int n_ever, int n_rec) {
     uint32_t* r = curves + ((size_t)s * T + row) * 3;
@@ -101,12 +135,13 @@ __global__ __launch_bounds__(256) void k_fill_i16(int16_t* __restrict__ p, size_
 #ifndef GN_SIR_UNROLL
 #define GN_SIR_UNROLL 8
 #endif
-template <bool STATE_IN_LDS, bool NODES, bool TRAJ, bool EDGES = false>
+template <bool STATE_IN_LDS, bool NODES, bool TRAJ, bool EDGES = false, bool INIT = false>
 __global__ __launch_bounds__(1024) void k_sir_philox(const int* __restrict__ src, const int* __restrict__ dst, long nnz,
                                                     int n, const int* __restrict__ seeds, int n_seeds,
                                                     SirThr<NODES> thr_beta, SirThr<NODES> thr_gamma,
                                                     long sims, long sim_offset, int T, uint32_t k0, uint32_t k1,
-                                                    uint32_t* __restrict__ hist, uint8_t* __restrict__ gstate, SirTraj<TRAJ> tr) {
+                                                    uint32_t* __restrict__ hist, uint8_t* __restrict__ gstate, SirTraj<TRAJ> tr,
+                                                    SirInit<INIT> in) {
     static_assert(NODES || !EDGES, "per-edge infection thresholds come with per-node recovery thresholds");
     extern __shared__ uint8_t smem[];
     uint8_t* state = STATE_IN_LDS ? smem : gstate + (size_t)blockIdx.x * 2 * n;
@@ -124,7 +159,30 @@ __global__ __launch_bounds__(1024) void k_sir_philox(const int* __restrict__ src
         for (int v = threadIdx.x; v < n; v += nthr) { state[v] = ST_S; flag[v] = 0; }
         if (TRAJ && threadIdx.x < 2) tcnt[threadIdx.x] = 0;
         __syncthreads();
-        for (int j = threadIdx.x; j < n_seeds; j += nthr) state[seeds[j]] = ST_I;   // duplicates: same value
+        if constexpr (INIT) {
+            // drawn start: a node that starts in I or R has left S at step 0 (one infection event), one that starts in R
+            // has recovered at step 0 as well
+            int n_out = 0, n_gone = 0;
+            for (int q = threadIdx.x; 4 * q < n; q += nthr) {
+                uint32_t inf, rec;
+                sir_init_draw(in.thr, n, q, sim, k0, k1, inf, rec);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int v = 4 * q + j;
+                    if (!(((inf | rec) >> j) & 1u)) continue;
+                    const bool r = (rec >> j) & 1u;
+                    state[v] = r ? ST_R : ST_I;
+                    atomicAdd(&hinf[v], 1u);
+                    if (r) atomicAdd(&hrec[v], 1u);
+                    if (TRAJ && ev_inf) { ev_inf[(size_t)s * n + v] = 0; if (r) ev_rec[(size_t)s * n + v] = 0; }
+                }
+                n_out += __popc(inf | rec); n_gone += __popc(rec);
+            }
+            if (TRAJ && n_out) atomicAdd(&tcnt[0], n_out);
+            if (TRAJ && n_gone) atomicAdd(&tcnt[1], n_gone);
+        } else {
+            for (int j = threadIdx.x; j < n_seeds; j += nthr) state[seeds[j]] = ST_I;   // duplicates: same value
+        }
         __syncthreads();
         for (int j = threadIdx.x; j < n_seeds; j += nthr) {
             // one infection event at t=0 per distinct seed node
@@ -140,7 +198,7 @@ __global__ __launch_bounds__(1024) void k_sir_philox(const int* __restrict__ src
         int rows_done = 1;                          // (TRAJ) rows of `curves` written so far
         if (TRAJ && curves) {
             __syncthreads();
-            if (threadIdx.x == 0) sir_curve_row(curves, s, T, 0, n, tcnt[0], 0);
+            if (threadIdx.x == 0) sir_curve_row(curves, s, T, 0, n, tcnt[0], INIT ? tcnt[1] : 0);
         }
         for (int it = 1; it < T; ++it) {
             // GN_SIR_UNROLL source ids in flight per thread: the scan is a chain of (global id load -> LDS state read)
@@ -220,13 +278,14 @@ __global__ __launch_bounds__(1024) void k_sir_philox(const int* __restrict__ src
 // and the recovery-only phase ask only whether a target is susceptible, so both stay sufficient next to w = 0 entries: a row
 // whose susceptible targets all sit behind zeros keeps being walked.  There is no COUNT && EDGES instance.
 // TRAJ: per-trajectory events and curves (SirTraj above); there is no COUNT && TRAJ instance.
-template <typename IdT, bool LISTS_IN_LDS, bool COUNT, bool NODES, bool TRAJ, bool EDGES = false>
+template <typename IdT, bool LISTS_IN_LDS, bool COUNT, bool NODES, bool TRAJ, bool EDGES = false, bool INIT = false>
 __global__ __launch_bounds__(1024) void k_sir_frontier(const int* __restrict__ rowptr, const int* __restrict__ col, int n,
                                                       const int* __restrict__ seeds, int n_seeds,
                                                       SirThr<NODES> thr_beta, SirThr<NODES> thr_gamma,
                                                       long sims, long sim_offset, int T, uint32_t k0, uint32_t k1,
                                                       uint32_t* __restrict__ hist, int32_t* __restrict__ glists,
-                                                      unsigned long long* __restrict__ stats, SirTraj<TRAJ> tr) {
+                                                      unsigned long long* __restrict__ stats, SirTraj<TRAJ> tr, SirInit<INIT> in) {
+    static_assert(!(COUNT && INIT), "the counting instantiation starts from a seed list");
     static_assert(!(COUNT && TRAJ), "the counting instantiation has no per-trajectory output");
     static_assert(!(COUNT && EDGES) && (NODES || !EDGES), "per-edge thresholds: with per-node recovery, never counted");
     extern __shared__ uint32_t smem_w[];
@@ -257,21 +316,60 @@ __global__ __launch_bounds__(1024) void k_sir_frontier(const int* __restrict__ r
         for (int w = tid; w < nwords; w += nthr) { bits[w] = 0u; spent[w] = 0u; recb[w] = 0u; }
         if (tid < 3) cnt[tid] = 0;
         __syncthreads();
-        for (int j = tid; j < n_seeds; j += nthr) {            // distinct seeds: one infection event at t = 0 each
-            const int v = seeds[j];
-            const uint32_t m = 1u << (v & 31);
-            if (!(atomicOr(&bits[v >> 5], m) & m)) {
-                cur[atomicAdd(&cnt[0], 1)] = (IdT)v; atomicAdd(&hinf[v], 1u);
-                if (TRAJ && ev_inf) ev_inf[(size_t)s * n + v] = 0;
+        if constexpr (INIT) {
+            // drawn start (sir_init_draw): I and R starts have left S (ever-infected bit, one infection event at t = 0), R
+            // starts have recovered too (recb, one recovery event at t = 0), I starts make the first frontier -- which may be a
+            // large share of n, so the list grows by ONE LDS atomic per wave, as the survivors' append does.  Every lane of the
+            // workgroup runs every iteration: the ballots need whole waves.
+            const int nq = (n + 3) >> 2;
+            for (int q0 = 0; q0 < nq; q0 += nthr) {
+                const int q = q0 + tid, u0 = 4 * q;
+                uint32_t inf = 0, rec = 0;
+                if (q < nq) sir_init_draw(in.thr, n, q, sim, k0, k1, inf, rec);
+                const uint32_t out = inf | rec;
+                if (out) atomicOr(&bits[u0 >> 5], out << (u0 & 31));
+                if (rec) atomicOr(&recb[u0 >> 5], rec << (u0 & 31));
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if ((out >> j) & 1u) {
+                        const bool r = (rec >> j) & 1u;
+                        atomicAdd(&hinf[u0 + j], 1u);
+                        if (r) atomicAdd(&hrec[u0 + j], 1u);
+                        if (TRAJ && ev_inf) { ev_inf[(size_t)s * n + u0 + j] = 0; if (r) ev_rec[(size_t)s * n + u0 + j] = 0; }
+                    }
+                // this wave's I starts: slot = wave base + the I starts of the lanes below + this lane's own in front
+                const unsigned long long below = (1ull << lane_in_wave) - 1ull;
+                int before = 0, n_i = 0, n_out = 0;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const unsigned long long mi = __ballot((inf >> j) & 1u);
+                    before += __popcll(mi & below); n_i += __popcll(mi);
+                    n_out += __popcll(__ballot((out >> j) & 1u));
+                }
+                int basep = 0;
+                if (lane_in_wave == 0 && n_out) { basep = atomicAdd(&cnt[0], n_i); atomicAdd(&cnt[2], n_out); }
+                basep = __shfl(basep, 0, 64) + before;
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if ((inf >> j) & 1u) cur[basep++] = (IdT)(u0 + j);
+            }
+        } else {
+            for (int j = tid; j < n_seeds; j += nthr) {        // distinct seeds: one infection event at t = 0 each
+                const int v = seeds[j];
+                const uint32_t m = 1u << (v & 31);
+                if (!(atomicOr(&bits[v >> 5], m) & m)) {
+                    cur[atomicAdd(&cnt[0], 1)] = (IdT)v; atomicAdd(&hinf[v], 1u);
+                    if (TRAJ && ev_inf) ev_inf[(size_t)s * n + v] = 0;
+                }
             }
         }
         __syncthreads();
         int n_inf = cnt[0];
-        int n_ever = n_inf;                                    // once it reaches n nobody is left to infect: recovery coins only
+        int n_ever = INIT ? cnt[2] : n_inf;                // once it reaches n nobody is left to infect: recovery coins only
         __syncthreads();
         if (tid == 0) cnt[2] = n_ever;
         int rows_done = 1;                                     // (TRAJ) rows of `curves` written so far
-        if (TRAJ && curves && tid == 0) sir_curve_row(curves, s, T, 0, n, n_ever, 0);
+        if (TRAJ && curves && tid == 0) sir_curve_row(curves, s, T, 0, n, n_ever, INIT ? n_ever - n_inf : 0);
         for (int it = 1; it < T && n_inf > 0; ++it) {
             if (tid == 0) { cnt[0] = 0; cnt[1] = 0; }
             __syncthreads();
@@ -447,7 +545,9 @@ __global__ __launch_bounds__(1024) void k_sir_frontier(const int* __restrict__ r
     }
 }
 
-// counts[0..2][t][v] += (sims - cumInf, cumInf - cumRec, cumRec) for t >= 1; row 0 assigned.
+// counts[0..2][t][v] += (sims - cumInf, cumInf - cumRec, cumRec) for t >= 1; row 0 assigned -- or, ACC0 (a drawn start:
+// the trajectories do not share one initial state), accumulated like the others from the events of step 0.
+template <bool ACC0>
 __global__ __launch_bounds__(256) void k_sir_finalize(const uint32_t* __restrict__ hist, int n, int T, uint32_t sims,
                                                       uint32_t* __restrict__ counts) {
     const int v = blockIdx.x * 256 + threadIdx.x;
@@ -456,10 +556,15 @@ __global__ __launch_bounds__(256) void k_sir_finalize(const uint32_t* __restrict
     const uint32_t* hrec = hist + (size_t)T * n;
     const size_t plane = (size_t)T * n;
     uint32_t ci = hinf[v], cr = 0;
-    const uint32_t seeded = ci ? 1u : 0u;            // every trajectory starts from the same seed set
-    counts[v] = 1u - seeded;                         // S row 0: assigned, ode_nn.py:56
-    counts[plane + v] = seeded;                      // I row 0: assigned, ode_nn.py:55
-    ci = seeded * sims;
+    if constexpr (ACC0) {
+        cr = hrec[v];
+        counts[v] += sims - ci; counts[plane + v] += ci - cr; counts[2 * plane + v] += cr;
+    } else {
+        const uint32_t seeded = ci ? 1u : 0u;        // every trajectory starts from the same seed set
+        counts[v] = 1u - seeded;                     // S row 0: assigned, ode_nn.py:56
+        counts[plane + v] = seeded;                  // I row 0: assigned, ode_nn.py:55
+        ci = seeded * sims;
+    }
     for (int t = 1; t < T; ++t) {
         ci += hinf[(size_t)t * n + v];
         cr += hrec[(size_t)t * n + v];
@@ -621,6 +726,25 @@ int gn_sir_set_attributes() {       // once per device, from gnode_graph_create
     GN_HIP(hipFuncSetAttribute((const void*)k_sir_philox<true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
     GN_HIP(hipFuncSetAttribute((const void*)k_sir_philox<true, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
     GN_HIP(hipFuncSetAttribute((const void*)k_sir_philox<true, true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
+    // the INIT instances (drawn start): every rate form, with and without per-trajectory output
+    GN_HIP(hipFuncSetAttribute((const void*)k_sir_frontier<uint16_t, true, false, false, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
+    GN_HIP(hipFuncSetAttribute((const void*)k_sir_frontier<uint16_t, true, false, false, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
+    GN_HIP(hipFuncSetAttribute((const void*)k_sir_frontier<uint16_t, true, false, true, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
+    GN_HIP(hipFuncSetAttribute((const void*)k_sir_frontier<uint16_t, true, false, true, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
+    GN_HIP(hipFuncSetAttribute((const void*)k_sir_frontier<uint16_t, true, false, true, false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
+    GN_HIP(hipFuncSetAttribute((const void*)k_sir_frontier<uint16_t, true, false, true, true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
+    GN_HIP(hipFuncSetAttribute((const void*)k_sir_frontier<int32_t, false, false, false, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
+    GN_HIP(hipFuncSetAttribute((const void*)k_sir_frontier<int32_t, false, false, false, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
+    GN_HIP(hipFuncSetAttribute((const void*)k_sir_frontier<int32_t, false, false, true, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
+    GN_HIP(hipFuncSetAttribute((const void*)k_sir_frontier<int32_t, false, false, true, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
+    GN_HIP(hipFuncSetAttribute((const void*)k_sir_frontier<int32_t, false, false, true, false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
+    GN_HIP(hipFuncSetAttribute((const void*)k_sir_frontier<int32_t, false, false, true, true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
+    GN_HIP(hipFuncSetAttribute((const void*)k_sir_philox<true, false, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
+    GN_HIP(hipFuncSetAttribute((const void*)k_sir_philox<true, false, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
+    GN_HIP(hipFuncSetAttribute((const void*)k_sir_philox<true, true, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
+    GN_HIP(hipFuncSetAttribute((const void*)k_sir_philox<true, true, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
+    GN_HIP(hipFuncSetAttribute((const void*)k_sir_philox<true, true, false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
+    GN_HIP(hipFuncSetAttribute((const void*)k_sir_philox<true, true, true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
     GN_HIP(hipFuncSetAttribute((const void*)k_sir_coins, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
     return 0;
 }
@@ -651,6 +775,12 @@ extern "C" size_t gnode_sir_edges_workspace_bytes(gnode_graph_t g, int32_t T) {
     return g ? gnode_sir_workspace_bytes(g, T) + sir_edge_thr_bytes(g) : 0;
 }
 
+// drawn-start form: the per-edge layout (the largest of the rate forms'), then the start thresholds -- uint64 [n] for pS,
+// uint64 [n] for pR
+extern "C" size_t gnode_sir_init_workspace_bytes(gnode_graph_t g, int32_t T) {
+    return g ? gnode_sir_edges_workspace_bytes(g, T) + sir_thr_bytes(g->info.n) : 0;
+}
+
 static unsigned long long coin_threshold(double p) {
     return (unsigned long long)std::min(4294967296.0, std::max(0.0, std::floor(p * 4294967296.0)));
 }
@@ -665,22 +795,29 @@ static int sir_mc_philox_impl(gnode_graph_t g, const int32_t* seeds_host, int32_
                               const double* beta_nodes = nullptr, const double* gamma_nodes = nullptr,
                               bool traj = false /* gnode_sir_mc_philox_traj: counts may be null, events / curves are written */,
                               int16_t* events = nullptr, uint32_t* curves = nullptr,
-                              bool edges = false, const double* w_edges = nullptr) {
-    GN_CHECK_ARG(g && (counts || traj) && workspace, "gnode_sir_mc_philox: null pointer");
-    GN_CHECK_ARG(!traj || ((events || curves) && !stats), "gnode_sir_mc_philox_traj: neither events nor curves given");
-    GN_CHECK_ARG(!events || (T <= 32767 && ((uintptr_t)events & 1u) == 0), "gnode_sir_mc_philox_traj: events hold int16 steps (T <= 32767)");
+                              bool edges = false, const double* w_edges = nullptr,
+                              const double* init = nullptr /* gnode_sir_mc_philox_init: host fp64 [n][3], in place of the seeds */) {
+    // the entry's name for the messages, by the argument group a check belongs to: the init entry is one for all of them
+    const char* const who = init ? "gnode_sir_mc_philox_init" : "gnode_sir_mc_philox";
+    const char* const who_t = init ? who : "gnode_sir_mc_philox_traj";
+    const char* const who_n = init ? who : "gnode_sir_mc_philox_nodes";
+    const char* const who_e = init ? who : "gnode_sir_mc_philox_edges";
+    GN_CHECK_ARG(g && (counts || traj) && workspace, "%s: null pointer", who);
+    GN_CHECK_ARG(!traj || ((events || curves) && !stats), "%s: neither events nor curves given", who_t);
+    GN_CHECK_ARG(!events || (T <= 32767 && ((uintptr_t)events & 1u) == 0), "%s: events hold int16 steps (T <= 32767)", who_t);
     const bool nodes = !edges && (beta_nodes || gamma_nodes);
-    GN_CHECK_ARG(!nodes || (beta_nodes && gamma_nodes && !stats), "gnode_sir_mc_philox_nodes: null rate array");
-    GN_CHECK_ARG(!edges || ((w_edges || g->nnz == 0) && !beta_nodes && !stats), "gnode_sir_mc_philox_edges: null weight array");
-    GN_CHECK_ARG(n_seeds >= 0 && n_seeds <= 4096 && (seeds_host || n_seeds == 0), "gnode_sir_mc_philox: 0..4096 seeds");
+    GN_CHECK_ARG(!nodes || (beta_nodes && gamma_nodes && !stats), "%s: null rate array", who_n);
+    GN_CHECK_ARG(!edges || ((w_edges || g->nnz == 0) && !beta_nodes && !stats), "%s: null weight array", who_e);
+    GN_CHECK_ARG(n_seeds >= 0 && n_seeds <= 4096 && (seeds_host || n_seeds == 0), "%s: 0..4096 seeds", who);
     GN_CHECK_ARG(T >= 1 && sims >= 0 && sims <= 0xFFFFFFFFll && sim_offset >= 0 && sim_offset + sims <= 0xFFFFFFFFll,
-                 "gnode_sir_mc_philox: bad T/sims/sim_offset");
-    GN_CHECK_ARG(beta >= 0.0 && beta <= 1.0 && gamma >= 0.0 && gamma <= 1.0, "gnode_sir_mc_philox: beta, gamma in [0,1]");
+                 "%s: bad T/sims/sim_offset", who);
+    GN_CHECK_ARG(beta >= 0.0 && beta <= 1.0 && gamma >= 0.0 && gamma <= 1.0, "%s: beta, gamma in [0,1]", who);
     for (int i = 0; i < n_seeds; ++i)
-        GN_CHECK_ARG(seeds_host[i] >= 0 && seeds_host[i] < g->info.n, "gnode_sir_mc_philox: seed %d out of range", seeds_host[i]);
-    const size_t ws_need = edges ? gnode_sir_edges_workspace_bytes(g, T) : nodes ? gnode_sir_nodes_workspace_bytes(g, T) : gnode_sir_workspace_bytes(g, T);
+        GN_CHECK_ARG(seeds_host[i] >= 0 && seeds_host[i] < g->info.n, "%s: seed %d out of range", who, seeds_host[i]);
+    const size_t ws_need = init ? gnode_sir_init_workspace_bytes(g, T) : edges ? gnode_sir_edges_workspace_bytes(g, T)
+                                : nodes ? gnode_sir_nodes_workspace_bytes(g, T) : gnode_sir_workspace_bytes(g, T);
     if (workspace_bytes < ws_need) {
-        gnode_set_error("gnode_sir_mc_philox: workspace %zu < %zu", workspace_bytes, ws_need);
+        gnode_set_error("%s: workspace %zu < %zu", who, workspace_bytes, ws_need);
         return GNODE_ERR_WORKSPACE;
     }
     std::vector<unsigned long long> thr_host;              // [beta thresholds | gamma thresholds]
@@ -688,8 +825,8 @@ static int sir_mc_philox_impl(gnode_graph_t g, const int32_t* seeds_host, int32_
         const int n = g->info.n;
         thr_host.resize((size_t)2 * n);
         for (int v = 0; v < n; ++v) {                      // (a NaN fails both comparisons)
-            GN_CHECK_ARG(beta_nodes[v] >= 0.0 && beta_nodes[v] <= 1.0, "gnode_sir_mc_philox_nodes: beta[%d] = %g is not in [0,1]", v, beta_nodes[v]);
-            GN_CHECK_ARG(gamma_nodes[v] >= 0.0 && gamma_nodes[v] <= 1.0, "gnode_sir_mc_philox_nodes: gamma[%d] = %g is not in [0,1]", v, gamma_nodes[v]);
+            GN_CHECK_ARG(beta_nodes[v] >= 0.0 && beta_nodes[v] <= 1.0, "%s: beta[%d] = %g is not in [0,1]", who_n, v, beta_nodes[v]);
+            GN_CHECK_ARG(gamma_nodes[v] >= 0.0 && gamma_nodes[v] <= 1.0, "%s: gamma[%d] = %g is not in [0,1]", who_n, v, gamma_nodes[v]);
             thr_host[v] = coin_threshold(beta_nodes[v]);
             thr_host[(size_t)n + v] = coin_threshold(gamma_nodes[v]);
         }
@@ -699,17 +836,31 @@ static int sir_mc_philox_impl(gnode_graph_t g, const int32_t* seeds_host, int32_
         const int n = g->info.n;
         thr_host.resize(n_thr_b + n);
         for (size_t p = 0; p < n_thr_b; ++p) {
-            GN_CHECK_ARG(w_edges[p] >= 0.0 && w_edges[p] <= 1.0, "gnode_sir_mc_philox_edges: the weight at CSR position %zu, %g, is not in [0,1]", p, w_edges[p]);
+            GN_CHECK_ARG(w_edges[p] >= 0.0 && w_edges[p] <= 1.0, "%s: the weight at CSR position %zu, %g, is not in [0,1]", who_e, p, w_edges[p]);
             thr_host[p] = coin_threshold(w_edges[p]);
         }
         for (int v = 0; v < n; ++v) {
             const double gv = gamma_nodes ? gamma_nodes[v] : gamma;
-            GN_CHECK_ARG(gv >= 0.0 && gv <= 1.0, "gnode_sir_mc_philox_edges: gamma[%d] = %g is not in [0,1]", v, gv);
+            GN_CHECK_ARG(gv >= 0.0 && gv <= 1.0, "%s: gamma[%d] = %g is not in [0,1]", who_e, v, gv);
             thr_host[n_thr_b + v] = coin_threshold(gv);
+        }
+    }
+    std::vector<unsigned long long> init_host;             // [thr(pS) | thr(pR)]
+    if (init) {
+        const int n = g->info.n;
+        init_host.resize((size_t)2 * n);
+        for (int v = 0; v < n; ++v) {
+            const double* p = init + (size_t)3 * v;
+            for (int c = 0; c < 3; ++c)                    // (a NaN fails both comparisons)
+                GN_CHECK_ARG(p[c] >= 0.0 && p[c] <= 1.0, "gnode_sir_mc_philox_init: init[%d][%d] = %g is not in [0,1]", v, c, p[c]);
+            GN_CHECK_ARG(std::fabs(p[0] + p[1] + p[2] - 1.0) <= 1e-6, "gnode_sir_mc_philox_init: the row of node %d sums to %.9g, not 1", v, p[0] + p[1] + p[2]);
+            init_host[v] = coin_threshold(p[0]);
+            init_host[(size_t)n + v] = coin_threshold(p[2]);
         }
     }
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace;
+    const unsigned long long* thr_init = init ? (const unsigned long long*)(ws + gnode_sir_edges_workspace_bytes(g, T)) : nullptr;
     const unsigned long long* thr_b = (const unsigned long long*)(ws + gnode_sir_workspace_bytes(g, T));   // used when `nodes` or `edges`
     const unsigned long long* thr_g = thr_b + n_thr_b;
     const size_t hist_b = gn_align((size_t)2 * T * g->info.n * sizeof(uint32_t));
@@ -737,7 +888,8 @@ static int sir_mc_philox_impl(gnode_graph_t g, const int32_t* seeds_host, int32_
         GN_HIP(hipMemcpyAsync(seeds, seeds_host, sizeof(int32_t) * n_seeds, hipMemcpyHostToDevice, st));
     }
     if (nodes || edges) GN_HIP(hipMemcpyAsync((void*)thr_b, thr_host.data(), thr_host.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, st));
-    if (n_seeds > 32 || nodes || edges) GN_HIP(hipStreamSynchronize(st));     // the host arrays are done with
+    if (init) GN_HIP(hipMemcpyAsync((void*)thr_init, init_host.data(), init_host.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, st));
+    if (n_seeds > 32 || nodes || edges || init) GN_HIP(hipStreamSynchronize(st));     // the host arrays are done with
     const unsigned long long tb = coin_threshold(beta), tg = coin_threshold(gamma);
     const uint32_t k0 = (uint32_t)(rng_seed & 0xFFFFFFFFull), k1 = (uint32_t)(rng_seed >> 32);
     if (sims > 0) {
@@ -748,33 +900,36 @@ static int sir_mc_philox_impl(gnode_graph_t g, const int32_t* seeds_host, int32_
         const size_t lds = (size_t)2 * g->info.n;
         // one path selection and launch geometry for all forms: `rates_tag` (0 scalar, 1 per node, 2 per edge) picks the
         // kernels' NODES / EDGES instances, whose thresholds tb_ / tg_ are the staged arrays instead of the two numbers
-        auto launch = [&](auto rates_tag, auto traj_tag, auto tb_, auto tg_) {
+        auto launch = [&](auto rates_tag, auto traj_tag, auto init_tag, auto tb_, auto tg_) {
             constexpr bool NODES = decltype(rates_tag)::value >= 1;
             constexpr bool EDGES = decltype(rates_tag)::value == 2;
             constexpr bool TRAJ = decltype(traj_tag)::value;
+            constexpr bool INIT = decltype(init_tag)::value;
             SirTraj<TRAJ> tr;
             if constexpr (TRAJ) { tr.events = events; tr.curves = curves; }
+            SirInit<INIT> in;
+            if constexpr (INIT) in.thr = thr_init;
             if (fl <= kLdsStateLimit && !edge_scan) {
                 // frontier-driven walk.  Workgroups per CU by LDS, at least 16 waves per CU
                 const int per_cu = per_cu_f, threads = threads_f;
                 if (frontier_lists_in_lds(g->info.n, g->n_bigrow)) {
                     const int grid = (int)std::min<int64_t>(sims, (int64_t)g->info.num_cu * per_cu);
-                    if constexpr (!NODES && !TRAJ) if (stats) {
+                    if constexpr (!NODES && !TRAJ && !INIT) if (stats) {
                         hipLaunchKernelGGL((k_sir_frontier<uint16_t, true, true, false, false>), dim3(grid), dim3(threads), fl, st, g->rowptr, g->col, g->info.n, seeds,
-                                           n_seeds, tb_, tg_, (long)sims, (long)sim_offset, T, k0, k1, hist, (int32_t*)nullptr, stats, tr);
+                                           n_seeds, tb_, tg_, (long)sims, (long)sim_offset, T, k0, k1, hist, (int32_t*)nullptr, stats, tr, in);
                         return;
                     }
-                    hipLaunchKernelGGL((k_sir_frontier<uint16_t, true, false, NODES, TRAJ, EDGES>), dim3(grid), dim3(threads), fl, st, g->rowptr, g->col, g->info.n, seeds,
-                                       n_seeds, tb_, tg_, (long)sims, (long)sim_offset, T, k0, k1, hist, (int32_t*)nullptr, stats, tr);
+                    hipLaunchKernelGGL((k_sir_frontier<uint16_t, true, false, NODES, TRAJ, EDGES, INIT>), dim3(grid), dim3(threads), fl, st, g->rowptr, g->col, g->info.n, seeds,
+                                       n_seeds, tb_, tg_, (long)sims, (long)sim_offset, T, k0, k1, hist, (int32_t*)nullptr, stats, tr, in);
                 } else {
                     const int grid = (int)std::min<int64_t>(std::min<int64_t>(sims, (int64_t)g->info.num_cu * per_cu), kFrontierGlobalGrid);
-                    if constexpr (!NODES && !TRAJ) if (stats) {
+                    if constexpr (!NODES && !TRAJ && !INIT) if (stats) {
                         hipLaunchKernelGGL((k_sir_frontier<int32_t, false, true, false, false>), dim3(grid), dim3(threads), fl, st, g->rowptr, g->col, g->info.n, seeds,
-                                           n_seeds, tb_, tg_, (long)sims, (long)sim_offset, T, k0, k1, hist, (int32_t*)gstate, stats, tr);
+                                           n_seeds, tb_, tg_, (long)sims, (long)sim_offset, T, k0, k1, hist, (int32_t*)gstate, stats, tr, in);
                         return;
                     }
-                    hipLaunchKernelGGL((k_sir_frontier<int32_t, false, false, NODES, TRAJ, EDGES>), dim3(grid), dim3(threads), fl, st, g->rowptr, g->col, g->info.n, seeds,
-                                       n_seeds, tb_, tg_, (long)sims, (long)sim_offset, T, k0, k1, hist, (int32_t*)gstate, stats, tr);
+                    hipLaunchKernelGGL((k_sir_frontier<int32_t, false, false, NODES, TRAJ, EDGES, INIT>), dim3(grid), dim3(threads), fl, st, g->rowptr, g->col, g->info.n, seeds,
+                                       n_seeds, tb_, tg_, (long)sims, (long)sim_offset, T, k0, k1, hist, (int32_t*)gstate, stats, tr, in);
                 }
             } else if (lds <= kLdsStateLimit) {
                 // edge-parallel scan, node state in LDS: graphs whose frontier lists do not fit (n > ~25k with 32-bit ids)
@@ -782,27 +937,33 @@ static int sir_mc_philox_impl(gnode_graph_t g, const int32_t* seeds_host, int32_
                 const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / std::max<size_t>(lds, 1)));
                 const int threads = per_cu >= 4 ? 256 : (per_cu >= 2 ? 512 : 1024);
                 const int grid = (int)std::min<int64_t>(sims, (int64_t)g->info.num_cu * per_cu);
-                hipLaunchKernelGGL((k_sir_philox<true, NODES, TRAJ, EDGES>), dim3(grid), dim3(threads), lds, st, src, g->col, (long)g->nnz, g->info.n, seeds,
-                                   n_seeds, tb_, tg_, (long)sims, (long)sim_offset, T, k0, k1, hist, (uint8_t*)nullptr, tr);
+                hipLaunchKernelGGL((k_sir_philox<true, NODES, TRAJ, EDGES, INIT>), dim3(grid), dim3(threads), lds, st, src, g->col, (long)g->nnz, g->info.n, seeds,
+                                   n_seeds, tb_, tg_, (long)sims, (long)sim_offset, T, k0, k1, hist, (uint8_t*)nullptr, tr, in);
             } else {
                 hipLaunchKernelGGL(k_expand_rows, dim3((g->info.n + 255) / 256), dim3(256), 0, st, g->rowptr, g->info.n, src);
                 const int grid = (int)std::min<int64_t>(sims, 2048);
-                hipLaunchKernelGGL((k_sir_philox<false, NODES, TRAJ, EDGES>), dim3(grid), dim3(256), 0, st, src, g->col, (long)g->nnz, g->info.n, seeds,
-                                   n_seeds, tb_, tg_, (long)sims, (long)sim_offset, T, k0, k1, hist, gstate, tr);
+                hipLaunchKernelGGL((k_sir_philox<false, NODES, TRAJ, EDGES, INIT>), dim3(grid), dim3(256), 0, st, src, g->col, (long)g->nnz, g->info.n, seeds,
+                                   n_seeds, tb_, tg_, (long)sims, (long)sim_offset, T, k0, k1, hist, gstate, tr, in);
             }
         };
         using Scalar = std::integral_constant<int, 0>; using Nodes = std::integral_constant<int, 1>; using Edges = std::integral_constant<int, 2>;
-        if (edges && traj) launch(Edges{}, std::true_type{}, thr_b, thr_g);
-        else if (edges) launch(Edges{}, std::false_type{}, thr_b, thr_g);
-        else if (nodes && traj) launch(Nodes{}, std::true_type{}, thr_b, thr_g);
-        else if (nodes) launch(Nodes{}, std::false_type{}, thr_b, thr_g);
-        else if (traj) launch(Scalar{}, std::true_type{}, tb, tg);
-        else launch(Scalar{}, std::false_type{}, tb, tg);
+        // the drawn start is a set of instances of its own (INIT): the seed-list instances do not carry it
+        auto with_start = [&](auto rates_tag, auto traj_tag, auto tb_, auto tg_) {
+            if (init) launch(rates_tag, traj_tag, std::true_type{}, tb_, tg_);
+            else launch(rates_tag, traj_tag, std::false_type{}, tb_, tg_);
+        };
+        if (edges && traj) with_start(Edges{}, std::true_type{}, thr_b, thr_g);
+        else if (edges) with_start(Edges{}, std::false_type{}, thr_b, thr_g);
+        else if (nodes && traj) with_start(Nodes{}, std::true_type{}, thr_b, thr_g);
+        else if (nodes) with_start(Nodes{}, std::false_type{}, thr_b, thr_g);
+        else if (traj) with_start(Scalar{}, std::true_type{}, tb, tg);
+        else with_start(Scalar{}, std::false_type{}, tb, tg);
         if (sampled) gn_prof_end(3, st);
         GN_LAUNCH_CHECK();
     }
     if (!counts) return 0;                                 // (gnode_sir_mc_philox_traj without counts)
-    hipLaunchKernelGGL(k_sir_finalize, dim3((g->info.n + 255) / 256), dim3(256), 0, st, hist, g->info.n, T, (uint32_t)sims, counts);
+    if (init) hipLaunchKernelGGL(k_sir_finalize<true>, dim3((g->info.n + 255) / 256), dim3(256), 0, st, hist, g->info.n, T, (uint32_t)sims, counts);
+    else hipLaunchKernelGGL(k_sir_finalize<false>, dim3((g->info.n + 255) / 256), dim3(256), 0, st, hist, g->info.n, T, (uint32_t)sims, counts);
     GN_LAUNCH_CHECK();
     return 0;
 }
@@ -890,6 +1051,41 @@ extern "C" int gnode_sir_mc_philox_traj_edges(gnode_graph_t g, const int32_t* se
     GN_CHECK_ARG(!events || T <= 32767, "gnode_sir_mc_philox_traj_edges: events hold int16 steps, T = %d > 32767", T);
     return sir_mc_philox_impl(g, seeds_host, n_seeds, 0.0, gamma_host ? 0.0 : gamma, sims, sim_offset, T, rng_seed, counts, workspace,
                               workspace_bytes, stream, edge_scan != 0, nullptr, nullptr, gamma_host, true, events, curves, true, w_host);
+}
+
+// Initial-state distributions (include/gnode.h): one entry for the three rate forms and every output.  The same impl; the
+// kernels draw each trajectory's start from the staged thresholds of `init_host` instead of reading a seed list.
+extern "C" int gnode_sir_mc_philox_init(gnode_graph_t g, const double* init_host, double beta, const double* beta_host,
+                                        const double* w_host, double gamma, const double* gamma_host, int64_t sims,
+                                        int64_t sim_offset, int32_t T, uint64_t rng_seed, int16_t* events, uint32_t* curves,
+                                        uint32_t* counts, void* workspace, size_t workspace_bytes, void* stream, int32_t edge_scan) {
+    GN_CHECK_ARG(g && init_host && workspace, "gnode_sir_mc_philox_init: null pointer");
+    GN_CHECK_ARG(events || curves || counts, "gnode_sir_mc_philox_init: none of events, curves and counts given");
+    GN_CHECK_ARG(!events || T <= 32767, "gnode_sir_mc_philox_init: events hold int16 steps, T = %d > 32767", T);
+    const bool edges = w_host != nullptr, nodes = !edges && beta_host && gamma_host;
+    GN_CHECK_ARG(!edges || !beta_host, "gnode_sir_mc_philox_init: per-edge rates and per-node beta together");
+    GN_CHECK_ARG(edges || nodes || (!beta_host && !gamma_host), "gnode_sir_mc_philox_init: one per-node rate array without the other");
+    const bool traj = events || curves;
+    if (nodes && sir_thr_bytes(g->info.n) > sir_edge_thr_bytes(g)) {
+        // fewer entries than nodes: two per-node arrays would reach into the start thresholds.  The per-node form is the
+        // per-edge one with w[p] = beta[col[p]] (same coins, same counts), and that one fits: restate it.  (beta is checked
+        // here so that the message names the node; the impl then sees weights that are all in range.)  The column ids come
+        // back on the caller's stream, which the entry synchronises anyway
+        for (int v = 0; v < g->info.n; ++v)
+            GN_CHECK_ARG(beta_host[v] >= 0.0 && beta_host[v] <= 1.0, "gnode_sir_mc_philox_init: beta[%d] = %g is not in [0,1]", v, beta_host[v]);
+        std::vector<int32_t> col((size_t)g->nnz);
+        if (g->nnz) {
+            GN_HIP(hipMemcpyAsync(col.data(), g->col, sizeof(int32_t) * (size_t)g->nnz, hipMemcpyDeviceToHost, (hipStream_t)stream));
+            GN_HIP(hipStreamSynchronize((hipStream_t)stream));
+        }
+        std::vector<double> w((size_t)std::max<int64_t>(g->nnz, 1), 0.0);
+        for (size_t p = 0; p < (size_t)g->nnz; ++p) w[p] = beta_host[col[p]];
+        return sir_mc_philox_impl(g, nullptr, 0, 0.0, 0.0, sims, sim_offset, T, rng_seed, counts, workspace, workspace_bytes, stream,
+                                  edge_scan != 0, nullptr, nullptr, gamma_host, traj, events, curves, true, w.data(), init_host);
+    }
+    return sir_mc_philox_impl(g, nullptr, 0, (edges || nodes) ? 0.0 : beta, (nodes || (edges && gamma_host)) ? 0.0 : gamma, sims, sim_offset,
+                              T, rng_seed, counts, workspace, workspace_bytes, stream, edge_scan != 0, nullptr, nodes ? beta_host : nullptr,
+                              (nodes || edges) ? gamma_host : nullptr, traj, events, curves, edges, w_host, init_host);
 }
 
 extern "C" int gnode_sir_mc_coins(const int32_t* table_src, const int32_t* table_dst, int64_t n_table, int32_t n,

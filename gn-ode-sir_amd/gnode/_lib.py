@@ -78,11 +78,16 @@ ABI = {
     "gnode_sir_edges_workspace_bytes": (_sz, [_vp, _i32]),
     "gnode_sir_mc_philox_edges": (_int, [_vp, _vp, _i32, _vp, _f64, _vp, _i64, _i64, _i32, _u64, _vp, _vp, _sz, _vp, _i32]),
     "gnode_sir_mc_philox_traj_edges": (_int, [_vp, _vp, _i32, _vp, _f64, _vp, _i64, _i64, _i32, _u64, _vp, _vp, _vp, _vp, _sz, _vp, _i32]),
+    "gnode_sir_init_workspace_bytes": (_sz, [_vp, _i32]),
+    "gnode_sir_mc_philox_init": (_int, [_vp, _vp, _f64, _vp, _vp, _f64, _vp, _i64, _i64, _i32, _u64, _vp, _vp, _vp, _vp, _sz, _vp, _i32]),
     "gnode_sir_mc_coins": (_int, [_vp, _vp, _i64, _i32, _vp, _i32, _f64, _f64, _i64, _i32, _vp, _i64, _vp, _pi64, _vp, _sz, _vp]),
     "gnode_dmp_workspace_bytes": (_sz, [_vp]),
     "gnode_dmp_f32": (_int, [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _sz, _vp]),
+    "gnode_dmp_init_workspace_bytes": (_sz, [_vp]),
+    "gnode_dmp_init_f32": (_int, [_vp, _vp, _vp, _vp, _i32, _vp, _vp, _sz, _vp]),
     "gnode_meanfield_workspace_bytes": (_sz, [_vp]),
     "gnode_meanfield_f64": (_int, [_vp, _vp, _i32, _f64, _vp, _vp, _i32, _f64, _f64, _vp, _vp, _vp, _pi64, _vp, _sz, _vp]),
+    "gnode_meanfield_init_f64": (_int, [_vp, _vp, _f64, _vp, _vp, _i32, _f64, _f64, _vp, _vp, _vp, _pi64, _vp, _sz, _vp]),
     "gnode_l1_loss_workspace_bytes": (_sz, []),
     "gnode_l1_loss_f32": (_int, _L1 + [_vp, _sz, _vp]),
     "gnode_l1_loss_scaled_f32": (_int, _L1 + [C.c_float, _vp, _sz, _vp]),

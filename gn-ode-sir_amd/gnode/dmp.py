@@ -3,6 +3,7 @@ same constructor and `run(seed_list, maxTime)`, the message passing runs in libg
 
     DMP_SIR(weight_adj, nodes_gamma)        weight_adj: scipy sparse / dense [n, n] (the reference passes A*beta)
         .run(seed_list, maxTime) -> float32 tensor [maxTime, n, 3] = (Ps, Pi, Pr) on the GPU
+                                                seed_list: seed ids, or an `InitialState` (an extension)
 """
 from __future__ import annotations
 
@@ -28,9 +29,21 @@ class DMP_SIR:
         self.marginals = None
 
     def run(self, seed_list, maxTime):
+        """seed_list: the seed ids, or (extension) a `gnode.ode_nn.InitialState`: Ps_0, Pi_0, Pr_0 are then its columns and
+        the messages start from Phi_0 = Pi_0[src] (gnode_dmp_init_f32)."""
+        from .ode_nn import InitialState
+        if isinstance(seed_list, InitialState) and seed_list.n != self.N:
+            raise ValueError(f"InitialState of {seed_list.n} nodes given for a graph of {self.N}")
         lib = _lib.load()
-        seeds = np.ascontiguousarray(list(seed_list), dtype=np.int32)
         out = torch.empty((int(maxTime), self.N, 3), dtype=torch.float32, device=self.weights.device)
+        if isinstance(seed_list, InitialState):
+            init = torch.from_numpy(seed_list.p.astype(np.float32)).to(out.device)
+            ws = torch.empty(lib.gnode_dmp_init_workspace_bytes(self.graph.handle), dtype=torch.uint8, device=out.device)
+            _lib.check(lib.gnode_dmp_init_f32(self.graph.handle, _lib.ptr(self.weights), _lib.ptr(self.nodes_gamma), _lib.ptr(init),
+                                              int(maxTime), _lib.ptr(out), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()))
+            self.marginals = out
+            return out
+        seeds = np.ascontiguousarray(list(seed_list), dtype=np.int32)
         ws = torch.empty(lib.gnode_dmp_workspace_bytes(self.graph.handle), dtype=torch.uint8, device=out.device)
         _lib.check(lib.gnode_dmp_f32(self.graph.handle, _lib.ptr(self.weights), _lib.ptr(self.nodes_gamma), _lib.host_ptr(seeds),
                                      int(seeds.shape[0]), int(maxTime), _lib.ptr(out), _lib.ptr(ws), ws.numel(),

@@ -148,6 +148,96 @@ def _edge_rate_args(er: EdgeRates, gamma, graph):
     return (_lib.host_ptr(er.w), 0.0, _lib.host_ptr(g)), g
 
 
+class InitialState:
+    """An initial-state distribution for the label generators and baselines, passed wherever a seed set goes (`sir_counts`,
+    `sir_trajectories`, `sir_torch`, `DMP_SIR.run`, `runge_kutta_order4`): `p`, a validated contiguous float64 [n, 3] host
+    array of (pS, pI, pR) per node -- the GN-ODE's own x[:, 0:3].  The Monte-Carlo draws every trajectory's start from it,
+    independently per node; DMP and the mean-field start from it as it is.  Made by `initial_state` or `from_sets`."""
+
+    def __init__(self, p: np.ndarray):
+        self.p, self.n = p, int(p.shape[0])
+
+    @classmethod
+    def from_sets(cls, n: int, infected, immune=()) -> "InitialState":
+        """The crisp state: `infected` nodes start in I, `immune` nodes in R (vaccinated), everybody else in S."""
+        p = np.zeros((int(n), 3), dtype=np.float64)
+        p[:, 0] = 1.0
+        for ids, c in ((infected, 1), (immune, 2)):
+            ids = np.asarray(list(ids), dtype=np.int64)
+            if ids.size and (ids.min() < 0 or ids.max() >= n):
+                raise ValueError(f"InitialState.from_sets: node {int(ids[(ids < 0) | (ids >= n)][0])} is not in [0, {n})")
+            if ids.size and p[ids, 0].min() == 0.0:
+                raise ValueError("InitialState.from_sets: a node is both infected and immune")
+            p[ids, 0], p[ids, c] = 0.0, 1.0
+        return initial_state(p)
+
+    def x(self, hidden: int, beta, gamma) -> torch.Tensor:
+        """The float32 [n, 3 + hidden] sample `trainer.sample_tensor` would build, columns 0..2 taken from `p`."""
+        x = torch.zeros(self.n, 3 + int(hidden), dtype=torch.float32)
+        x[:, :3] = torch.from_numpy(self.p).to(torch.float32)
+        x[:, 3] = torch.as_tensor(beta, dtype=torch.float32)
+        x[:, 4] = torch.as_tensor(gamma, dtype=torch.float32)
+        return x
+
+
+def initial_state(p) -> InitialState:
+    """An `InitialState` from an [n, 3] array-like of (pS, pI, pR) per node (numpy, list or torch tensor on any device;
+    x[:, :3] of a sample works).  The checks of gnode_sir_mc_philox_init, raised as ValueError before the library is
+    entered: the shape, a NaN, an entry outside [0, 1], a row whose sum is off 1 by more than 1e-6.  Nothing is renormalised."""
+    if isinstance(p, torch.Tensor):
+        p = p.detach().cpu().numpy()
+    a = np.array(p, dtype=np.float64)
+    if a.ndim != 2 or a.shape[1] != 3:
+        raise ValueError(f"initial_state: need (pS, pI, pR) per node, shape [n, 3], got {tuple(a.shape)}")
+    bad = np.argwhere(~((a >= 0.0) & (a <= 1.0)))                   # a NaN fails both comparisons
+    if bad.size:
+        v, c = int(bad[0][0]), int(bad[0][1])
+        raise ValueError(f"initial_state: p[{v}][{c}] = {a[v, c]} is not a probability in [0, 1]")
+    off = np.flatnonzero(~(np.abs(a[:, 0] + a[:, 1] + a[:, 2] - 1.0) <= 1e-6))
+    if off.size:
+        raise ValueError(f"initial_state: the row of node {int(off[0])} sums to {a[off[0]].sum()!r}, not 1")
+    return InitialState(np.ascontiguousarray(a))
+
+
+def _resolved_rates(beta, gamma, graph):
+    """(b, g) for one launch: an EdgeRates and gamma as given (checked), two float64 [n] host arrays when either rate is per
+    node, else two numbers.  Raises ValueError before anything is allocated."""
+    n = graph.n
+    if isinstance(beta, EdgeRates):
+        _edge_rate_args(beta, gamma, graph)
+        return beta, gamma
+    b, g = _node_rates("beta", beta, n), _node_rates("gamma", gamma, n)
+    if b is not None or g is not None:
+        b = _node_rates("beta", np.full(n, float(beta)), n) if b is None else b
+        g = _node_rates("gamma", np.full(n, float(gamma)), n) if g is None else g
+        return b, g
+    return float(beta), float(gamma)
+
+
+def _init_launch(graph: DeviceGraph, init: InitialState, b, g, sims, T, rng_seed, sim_offset, ev, cv, counts, edge_scan):
+    """One gnode_sir_mc_philox_init launch into ev / cv / counts (each may be None, not all); b / g as `_resolved_rates`
+    returns them."""
+    lib = _lib.load()
+    if isinstance(b, EdgeRates):
+        (w, gam, gam_host), _alive = _edge_rate_args(b, g, graph)
+        rates = (0.0, None, w, gam, gam_host)
+    elif isinstance(b, np.ndarray):
+        rates = (0.0, _lib.host_ptr(b), None, 0.0, _lib.host_ptr(g))
+    else:
+        rates = (float(b), None, None, float(g), None)
+    dev = next(t for t in (counts, ev, cv) if t is not None).device
+    ws = torch.empty(lib.gnode_sir_init_workspace_bytes(graph.handle, T), dtype=torch.uint8, device=dev)
+    _lib.check(lib.gnode_sir_mc_philox_init(graph.handle, _lib.host_ptr(init.p), *rates, int(sims), int(sim_offset), int(T),
+                                            C.c_uint64(int(rng_seed) & (2**64 - 1)), _lib.ptr(ev), _lib.ptr(cv), _lib.ptr(counts),
+                                            _lib.ptr(ws), ws.numel(), _lib.stream_ptr(), int(bool(edge_scan))))
+
+
+def _init_for(init: InitialState, n: int) -> InitialState:
+    if init.n != n:
+        raise ValueError(f"InitialState of {init.n} nodes given for a graph of {n}")
+    return init
+
+
 def _philox_launch(entry: str, graph: DeviceGraph, seed_set, beta, gamma, sims, T, rng_seed, sim_offset, device, counts, *extra,
                    ws_entry: str = "gnode_sir_workspace_bytes"):
     """One launch of a gnode_sir_mc_philox* entry into `counts` (zeros [3, T, n] on `device` when None); returns counts.
@@ -180,7 +270,19 @@ def sir_counts(graph: DeviceGraph, seed_set, beta, gamma, sims, T, rng_seed, sim
     which synchronises the stream.  A wrong length, a NaN or a value outside [0, 1] raises ValueError.
 
     beta may also be an `EdgeRates` (from `edge_rates`): one transmission probability per directed CSR entry, source = row,
-    target = column, through `gnode_sir_mc_philox_edges`; gamma stays a number or per-node rates."""
+    target = column, through `gnode_sir_mc_philox_edges`; gamma stays a number or per-node rates.
+
+    seed_set may be an `InitialState` (from `initial_state` / `InitialState.from_sets`): every trajectory then draws its
+    start from the per-node (pS, pI, pR), through `gnode_sir_mc_philox_init`, with any of the rate forms above.  Row 0 of
+    the counts is then ACCUMULATED like the other rows (how many trajectories start in S / I / R); a state that is one-hot
+    I on a seed set and S elsewhere gives the seed-list call's rows t >= 1 exactly.  A wrong n raises ValueError."""
+    if isinstance(seed_set, InitialState):
+        _init_for(seed_set, graph.n)
+        b, g = _resolved_rates(beta, gamma, graph)                  # (ValueError before the library is entered)
+        if counts is None:
+            counts = torch.zeros((3, T, graph.n), dtype=torch.int32, device=device)
+        _init_launch(graph, seed_set, b, g, sims, T, rng_seed, sim_offset, None, None, counts, edge_scan)
+        return counts
     if isinstance(beta, EdgeRates):
         _edge_rate_args(beta, gamma, graph)                         # (ValueError before the library is entered)
         return _philox_launch("gnode_sir_mc_philox_edges", graph, seed_set, beta, gamma, sims, T, rng_seed, sim_offset, device, counts,
@@ -241,19 +343,14 @@ def sir_trajectories(graph_or_G, seed_set, beta, gamma, sims, T, rng_seed=None, 
     graph_or_G: a DeviceGraph or a networkx graph.  beta / gamma: as in `sir_counts` (an `EdgeRates` for beta included).  rng_seed=None draws the seed from
     torch's CPU generator, as `sir_torch` does.  events=False / curves=False leave that output out (None in the result);
     `counts` (int32 [3, T, n]) is accumulated into as by `sir_counts`.  edge_scan=True runs the edge-parallel kernel.
+    seed_set may be an `InitialState`, as in `sir_counts`: a node that starts in I has t_inf = 0, one that starts in R has
+    t_inf = 0 and t_rec = 0 (the one case of t_rec == t_inf), and curves row 0 is the trajectory's drawn state.
     Raises ValueError for bad rates, for T > 32767 with events, and when neither output is requested."""
     graph = _device_graph_for(graph_or_G) if hasattr(graph_or_G, "number_of_nodes") else graph_or_G
     n = graph.n
-    if isinstance(beta, EdgeRates):
-        _edge_rate_args(beta, gamma, graph)                         # (ValueError before anything is allocated)
-        b, g = beta, gamma
-    else:
-        b, g = _node_rates("beta", beta, n), _node_rates("gamma", gamma, n)
-        if b is not None or g is not None:
-            b = _node_rates("beta", np.full(n, float(beta)), n) if b is None else b
-            g = _node_rates("gamma", np.full(n, float(gamma)), n) if g is None else g
-        else:
-            b, g = float(beta), float(gamma)
+    if isinstance(seed_set, InitialState):
+        _init_for(seed_set, n)
+    b, g = _resolved_rates(beta, gamma, graph)                      # (ValueError before anything is allocated)
     if not events and not curves:
         raise ValueError("sir_trajectories: neither events nor curves requested")
     if events and T > 32767:
@@ -264,7 +361,8 @@ def sir_trajectories(graph_or_G, seed_set, beta, gamma, sims, T, rng_seed=None, 
     ev = torch.empty((2, sims, n), dtype=torch.int16, device=dev) if events else None
     cv = torch.empty((sims, T, 3), dtype=torch.int32, device=dev) if curves else None
     if sims > 0:
-        _traj_launch(graph, seed_set, b, g, sims, T, rng_seed, sim_offset, ev, cv, counts, edge_scan)
+        launch = _init_launch if isinstance(seed_set, InitialState) else _traj_launch
+        launch(graph, seed_set, b, g, sims, T, rng_seed, sim_offset, ev, cv, counts, edge_scan)
     return SirTrajectories(ev[0] if events else None, ev[1] if events else None, cv)
 
 
@@ -285,12 +383,15 @@ def _events_up_to(t_ev: torch.Tensor, T: int, dim: int) -> torch.Tensor:
     return hist.narrow(dim, 0, T).cumsum(dim, dtype=torch.int32)
 
 
-def sir_counts_from_events(t_inf: torch.Tensor, t_rec: torch.Tensor, T: int) -> torch.Tensor:
+def sir_counts_from_events(t_inf: torch.Tensor, t_rec: torch.Tensor, T: int, accumulate_t0: bool = False) -> torch.Tensor:
     """int32 [3, T, n]: the counts `sir_counts` accumulates for these trajectories -- rows t >= 1 the number of
-    trajectories in which the node is S / I / R at step t, row 0 the initial state ONCE (the reference's quirk)."""
+    trajectories in which the node is S / I / R at step t, row 0 the initial state ONCE (the reference's quirk).
+    accumulate_t0=True counts row 0 like the other rows: what `sir_counts` of an `InitialState` returns."""
     sims = t_inf.shape[0]
     ci, cr = _events_up_to(t_inf, T, 0), _events_up_to(t_rec, T, 0)
     out = torch.stack([sims - ci, ci - cr, cr])
+    if accumulate_t0:
+        return out
     seeded = (t_inf == 0).any(dim=0).to(torch.int32)                           # every trajectory starts from the same seeds
     out[0, 0], out[1, 0], out[2, 0] = 1 - seeded, seeded, 0
     return out
@@ -355,9 +456,14 @@ def sir_torch(G, seed_set, beta, gamma, sims=10000, T=20, rng_seed=None, coins=N
     Per-node rates (extension): in production mode beta and gamma may each be an array of length n indexed by node id
     (see `sir_counts`), and beta an `EdgeRates` made by `edge_rates(G, M)`: one probability per directed contact.  The
     recorded-stream parity mode takes numbers only.
+
+    Initial-state distributions (extension): in production mode seed_set may be an `InitialState` (see `sir_counts`); row 0
+    is then accumulated over the trajectories and normalize_t0 has nothing to do.
     """
     n = G.number_of_nodes()
     if coins is not None:
+        if isinstance(seed_set, InitialState):
+            raise ValueError("sir_torch(coins=...): the parity mode takes a seed list, not an InitialState")
         if isinstance(beta, EdgeRates) or _node_rates("beta", beta, n) is not None or _node_rates("gamma", gamma, n) is not None:
             raise ValueError("sir_torch(coins=...): the parity mode takes scalar beta and gamma, not per-node arrays or EdgeRates")
         e = _edge_arrays(G)
@@ -370,7 +476,7 @@ def sir_torch(G, seed_set, beta, gamma, sims=10000, T=20, rng_seed=None, coins=N
             rng_seed = int(torch.randint(0, 2**62, (1,), dtype=torch.int64).item())
         counts = sir_counts(_device_graph_for(G), seed_set, beta, gamma, sims, T, rng_seed)
     c = _counts_f64(counts)
-    if normalize_t0:
+    if normalize_t0 and not isinstance(seed_set, InitialState):     # (a drawn start: row 0 already holds counts)
         c[:, 0] *= float(sims)
     return c[0][None], c[1][None], c[2][None]
 
@@ -399,24 +505,30 @@ def runge_kutta_order4(sir, A, n_nodes, indices, beta_factor, gamma_factor, delt
     """Mean-field baseline, reference ode_nn.py:222-233 (despite its name the reference runs scipy's LSODA):
     returns (I_sampled_t, S_sampled_t, R_sampled_t), float64 [maxTime, n] at the times int(i/deltaT)*deltaT.
     `sir` (the RHS callable) is accepted for signature compatibility; the integration runs in libgnode_hip.so
-    (adaptive Dormand-Prince 5(4), sparse A I) -- SURVEY 8f rank 4, not on the `ode_nn` path."""
-    lib = _lib.load()
+    (adaptive Dormand-Prince 5(4), sparse A I) -- SURVEY 8f rank 4, not on the `ode_nn` path.
+    `indices` is the seed list, or (extension) an `InitialState`: y(0) = (pS, pI, pR)."""
     Ac = sp.csr_matrix(A)
     Ac.sort_indices()
-    g = DeviceGraph(Ac.indptr.astype(np.int32), Ac.indices.astype(np.int32))
     n = Ac.shape[0]
+    if isinstance(indices, InitialState):
+        _init_for(indices, n)
+    lib = _lib.load()
+    g = DeviceGraph(Ac.indptr.astype(np.int32), Ac.indices.astype(np.int32))
     grid = np.arange(0, maxTime, deltaT)
     t_out = np.ascontiguousarray([grid[int(i / deltaT)] for i in range(int(maxTime))], dtype=np.float64)
-    seeds = np.ascontiguousarray(list(indices), dtype=np.int32)
     dev = torch.device("cuda", torch.cuda.current_device())
     gam = torch.full((n,), float(gamma_factor), dtype=torch.float64, device=dev)
     out = torch.empty((3, len(t_out), n), dtype=torch.float64, device=dev)
     ws = torch.empty(lib.gnode_meanfield_workspace_bytes(g.handle), dtype=torch.uint8, device=dev)
     steps = C.c_int64(0)
-    _lib.check(lib.gnode_meanfield_f64(g.handle, _lib.host_ptr(seeds), int(seeds.shape[0]), float(beta_factor), _lib.ptr(gam),
-                                       _lib.host_ptr(t_out), int(len(t_out)), float(rtol), float(atol), _lib.ptr(out[0]),
-                                       _lib.ptr(out[1]), _lib.ptr(out[2]), C.byref(steps), _lib.ptr(ws), ws.numel(),
-                                       _lib.stream_ptr()))
+    tail = (float(beta_factor), _lib.ptr(gam), _lib.host_ptr(t_out), int(len(t_out)), float(rtol), float(atol), _lib.ptr(out[0]),
+            _lib.ptr(out[1]), _lib.ptr(out[2]), C.byref(steps), _lib.ptr(ws), ws.numel(), _lib.stream_ptr())
+    if isinstance(indices, InitialState):                           # y(0) = (pS, pI, pR)
+        y0 = torch.from_numpy(indices.p).to(dev)
+        _lib.check(lib.gnode_meanfield_init_f64(g.handle, _lib.ptr(y0), *tail))
+    else:
+        seeds = np.ascontiguousarray(list(indices), dtype=np.int32)
+        _lib.check(lib.gnode_meanfield_f64(g.handle, _lib.host_ptr(seeds), int(seeds.shape[0]), *tail))
     o = out.cpu().numpy()
     return o[0], o[1], o[2]
 

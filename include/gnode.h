@@ -20,7 +20,7 @@
  *     into a hipGraph on first use and one handle may serve several streams (each
  *     with its own workspace).  Functions that DO synchronise `stream` say so below
  *     (gnode_graph_create, gnode_sir_mc_philox with more than 32 seeds,
- *     gnode_sir_mc_philox_nodes, gnode_sir_mc_philox_edges, gnode_sir_mc_philox_traj_edges, gnode_sir_mc_philox_traj with more than 32 seeds or rate arrays, gnode_sir_mc_coins, gnode_dmp_f32, gnode_meanfield_f64).
+ *     gnode_sir_mc_philox_nodes, gnode_sir_mc_philox_edges, gnode_sir_mc_philox_traj_edges, gnode_sir_mc_philox_traj with more than 32 seeds or rate arrays, gnode_sir_mc_philox_init, gnode_sir_mc_coins, gnode_dmp_f32, gnode_dmp_init_f32, gnode_meanfield_f64, gnode_meanfield_init_f64).
  *   - process-wide state: (1) a per-device "set up once" table (compute-unit count,
  *     dynamic-LDS kernel attributes), written under a lock by the first
  *     gnode_graph_create on a device and read-only afterwards; (2) the opt-in
@@ -421,6 +421,34 @@ int gnode_sir_mc_philox_traj_edges(gnode_graph_t g, const int32_t* seeds_host, i
                                    uint32_t* curves,   /* device [sims, T, 3], OVERWRITTEN, or NULL */
                                    uint32_t* counts,   /* device [3, T, n], ACCUMULATED, or NULL */
                                    void* workspace, size_t workspace_bytes, void* stream, int32_t edge_scan);
+/* Initial-state distributions (no version step: a stale library is known by the missing symbol): the same model with every
+ * trajectory drawing its own start from one probability triple per node, the GN-ODE's own x[:, 0:3], instead of sharing a
+ * seed set.  One entry for the three rate forms and every output.
+ *   init_host   host fp64 [n][3] = (pS, pI, pR) per node.  Validated here -- a NaN, an entry outside [0, 1] or a row whose sum
+ *               is off 1 by more than 1e-6 is GNODE_ERR_ARG, the message names the node -- and never renormalised.  Node v of
+ *               trajectory s starts in S iff c < thr(pS), else in R iff c >= 2^32 - thr(pR), else in I, compared in 64 bits,
+ *               thr(p) = floor(p * 2^32), c = word (v & 3) of philox(ctr = (v >> 2, step 0, sim_offset + s, kind 2)): four
+ *               consecutive nodes share a block, as the recovery coins do, and a one-hot row never depends on c.
+ *   rates       w_host non-NULL: per-edge rates as in gnode_sir_mc_philox_edges (beta_host must be NULL; gamma_host or the
+ *               scalar gamma).  Else beta_host and gamma_host both non-NULL: per-node rates as in gnode_sir_mc_philox_nodes.
+ *               Else both NULL: the scalars beta / gamma.  Any other combination is GNODE_ERR_ARG.
+ *   events / curves / counts   as in gnode_sir_mc_philox_traj, each may be NULL but not all three.  A node that starts in I
+ *               has t_inf = 0, as a seed has; one that starts in R has t_inf = 0 AND t_rec = 0 (the one case of t_rec ==
+ *               t_inf).  curves row 0 is the trajectory's drawn state.  counts row 0 is ACCUMULATED like every other row --
+ *               the number of trajectories that start in S / I / R -- so shards of the sims range add up on it too.
+ * Steps 1 .. T-1 are the other entries', with the same coins (kinds 0 and 1): a node that starts in R is never infected and
+ * never infects, and an init that is one-hot I on a seed set and S elsewhere gives the seed-list call's counts exactly on rows
+ * t >= 1 and `sims` times its row 0.  The workspace is gnode_sir_edges_workspace_bytes' followed by the two uint64 [n] start
+ * thresholds.  A refused call writes nothing.  SYNCHRONISES `stream`, because host arrays are staged.  edge_scan as above. */
+size_t gnode_sir_init_workspace_bytes(gnode_graph_t g, int32_t T);
+int gnode_sir_mc_philox_init(gnode_graph_t g, const double* init_host,
+                             double beta, const double* beta_host, const double* w_host,
+                             double gamma, const double* gamma_host,
+                             int64_t sims, int64_t sim_offset, int32_t T, uint64_t rng_seed,
+                             int16_t* events,    /* device [2, sims, n], OVERWRITTEN, or NULL */
+                             uint32_t* curves,   /* device [sims, T, 3], OVERWRITTEN, or NULL */
+                             uint32_t* counts,   /* device [3, T, n], ACCUMULATED (row 0 included), or NULL */
+                             void* workspace, size_t workspace_bytes, void* stream, int32_t edge_scan);
 int gnode_sir_mc_coins(const int32_t* table_src, const int32_t* table_dst, int64_t n_table, int32_t n,
                        const int32_t* seeds_host, int32_t n_seeds, double beta, double gamma, int64_t sims,
                        int32_t T, const double* coins, int64_t n_coins, uint32_t* counts,
@@ -442,6 +470,14 @@ size_t gnode_dmp_workspace_bytes(gnode_graph_t g);
 int gnode_dmp_f32(gnode_graph_t g, const float* weights, const float* gamma, const int32_t* seeds_host,
                   int32_t n_seeds, int32_t maxTime, float* out, void* workspace, size_t workspace_bytes,
                   void* stream);
+/* gnode_dmp_f32 from an initial-state distribution instead of a seed list: init is device fp32 [n][3] = (pS, pI, pR) per
+ * node (not validated here: it lives on the device).  Ps_0 = pS, Pi_0 = pI, Pr_0 = pR, the message of edge (i -> j) starts from
+ * Phi_0 = Pi_0[i] (the reference's 1 - Ps_0[i] is the same number when pR = 0), Pr_1 = Pr_0 + gamma Pi_0, everything after
+ * that as gnode_dmp_f32, the 1e-10 offset included: a one-hot seed state returns gnode_dmp_f32's output bit for bit. */
+size_t gnode_dmp_init_workspace_bytes(gnode_graph_t g);
+int gnode_dmp_init_f32(gnode_graph_t g, const float* weights, const float* gamma,
+                       const float* init /* device fp32 [n][3] */, int32_t maxTime, float* out,
+                       void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- mean-field baseline (reference ode_nn.py:214-233) ----
  * `runge_kutta_order4(sir, A, ...)`: dS = -beta (A I) S, dI = beta (A I) S - gamma I,
@@ -458,6 +494,11 @@ size_t gnode_meanfield_workspace_bytes(gnode_graph_t g);
 int gnode_meanfield_f64(gnode_graph_t g, const int32_t* seeds_host, int32_t n_seeds, double beta, const double* gamma,
                         const double* t_out_host, int32_t n_out, double rtol, double atol, double* outI, double* outS,
                         double* outR, int64_t* steps_host, void* workspace, size_t workspace_bytes, void* stream);
+/* gnode_meanfield_f64 from y(0) = init, device fp64 [n][3] = (pS, pI, pR) per node, in place of the seed list; the rest,
+ * gnode_meanfield_workspace_bytes included, is the same. */
+int gnode_meanfield_init_f64(gnode_graph_t g, const double* init, double beta, const double* gamma,
+                             const double* t_out_host, int32_t n_out, double rtol, double atol, double* outI, double* outS,
+                             double* outR, int64_t* steps_host, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- loss ------------------------------------------------------------------
  * The training loss of ode_nn_ngraph_sim.py:230-234 (multi-graph: ode_nn_ngraphs.py:199-203) and its gradient in one
