@@ -34,6 +34,7 @@
 // (k_sir_finalize<ACC0>).  Separate instances, not a run-time test in the shared ones: that form was measured and cost the
 // seed-list call 2 % at fb-social size, so the seed-list instances are the code they were before.
 #include "gnode_common.h"
+#include "gnode_sir_plan.h"
 #include <algorithm>
 #include <cmath>
 #include <type_traits>
@@ -266,8 +267,8 @@ __global__ __launch_bounds__(1024) void k_sir_philox(const int* __restrict__ src
 }
 
 // --------------------------------------------------------------------------- frontier-driven kernel
-// LDS: ever-infected bitmap (n bits) and, when they fit (uint16 ids: n up to ~25 000 -- every graph of the reference's
-// multi-graph experiment but enron and epinions), the node lists: current / next frontier and the rows too long for
+// LDS: ever-infected bitmap (n bits) and, when they fit (uint16 ids: n up to 11 232 for a graph without rows longer than
+// GN_SIR_BIGROW, frontier_lists_in_lds), the node lists: current / next frontier and the rows too long for
 // one lane group.  Larger graphs keep the three lists in the caller's workspace (int32 ids, one set per workgroup).
 // GN_SIR_BIGROW (gnode_common.h): rows longer than this are walked by the whole workgroup
 // COUNT: the profiling instantiation (gnode_sir_mc_philox_counted) also tallies Philox blocks, coins and CSR entries read.
@@ -664,428 +665,255 @@ __global__ __launch_bounds__(256) void k_sir_coins(const int* __restrict__ tsrc,
 }
 
 // --------------------------------------------------------------------------- host side
-static const size_t kLdsStateLimit = 150 * 1024;   // of the CU's 160 KiB
-
+// Layout, path selection, geometry and staging are gnode_sir_plan.{h,cpp}; here: the kernel instances and the calls.
 struct SeedArg { int32_t v[32]; };
 __global__ void k_put_seeds(SeedArg sa, int n_seeds, int32_t* __restrict__ seeds) {
     if ((int)threadIdx.x < n_seeds) seeds[threadIdx.x] = sa.v[threadIdx.x];
 }
 
-// LDS of the frontier kernel: bitmap (+ three uint16 node lists -- current, next, long rows -- when they fit)
-static size_t frontier_bitmap_bytes(int n) { return 3 * ((((size_t)n + 31) / 32 + 3) & ~(size_t)3) * 4; }   // ever-infected + spent + recovered
-// list elements in LDS: current + next frontier [n] each, long rows [as many as the graph has, padded to 8]
-static size_t frontier_list_bytes(int n, int n_big) { return 2 * (2 * (size_t)n + (((size_t)n_big + 7) & ~(size_t)7)); }
-static bool frontier_lists_in_lds(int n, int n_big) { return n <= 65536 && frontier_bitmap_bytes(n) + frontier_list_bytes(n, n_big) <= 48 * 1024; }
-// + 1 KB of coin queue per wave
-static size_t frontier_lds_bytes(int n, int n_big, int threads) {
-    return frontier_bitmap_bytes(n) + (size_t)(threads / 64) * 1024 + (frontier_lists_in_lds(n, n_big) ? frontier_list_bytes(n, n_big) : 0);
+// The kernels one form of call can launch, by path (SirPath): RATES is SIR_SCALAR / SIR_NODES / SIR_EDGES.  The launch and the
+// registration below both go through sir_dispatch, so an instance cannot be launched without being registered.
+template <int RATES, bool TRAJ_, bool INIT_> struct SirKernels {
+    static constexpr bool NODES = RATES >= SIR_NODES, EDGES = RATES == SIR_EDGES, TRAJ = TRAJ_, INIT = INIT_;
+    static constexpr auto frontier_lds = &k_sir_frontier<uint16_t, true, false, NODES, TRAJ, EDGES, INIT>;
+    static constexpr auto frontier_mem = &k_sir_frontier<int32_t, false, false, NODES, TRAJ, EDGES, INIT>;
+    static constexpr auto scan_lds = &k_sir_philox<true, NODES, TRAJ, EDGES, INIT>;
+    static constexpr auto scan_mem = &k_sir_philox<false, NODES, TRAJ, EDGES, INIT>;
+};
+// the counting instances (gnode_sir_mc_philox_counted): the frontier walk of SirKernels<SIR_SCALAR, false, false>
+static constexpr auto kSirCountedLds = &k_sir_frontier<uint16_t, true, true, false, false>;
+static constexpr auto kSirCountedMem = &k_sir_frontier<int32_t, false, true, false, false>;
+
+template <int RATES, class F> static void sir_dispatch_rates(bool traj, bool init, F&& f) {
+    if (traj) { if (init) f(SirKernels<RATES, true, true>{}); else f(SirKernels<RATES, true, false>{}); }
+    else { if (init) f(SirKernels<RATES, false, true>{}); else f(SirKernels<RATES, false, false>{}); }
 }
-// Workgroup size and workgroups per CU (the LDS decides how many fit).  Measured, 10 000 x 20 (2 000 x 30 at epinions size),
-// beta 0.3 / 0.05, ms:            16 waves per CU    24 waves      32 waves
-//   fb-social size (256 threads)        --           2.90 / 4.12   3.26 / 4.14
-//   wiki-vote size (512 threads)    9.8 / 28.0       8.2 / 22.5    9.3 / 25.1
-//   epinions size  (512 threads)        --          29.5 / 36.8   35.7 / 41.9     (256 threads x 5: 37.1 / 46.8)
-// -- past 24 waves the resident trajectories thrash each other's rows in the L2, below it the waits are exposed.  So: 256
-// threads for small graphs, 512 otherwise (1 024 when the LDS leaves fewer than 16 waves), at most GN_SIR_WAVES waves per CU.
-#ifndef GN_SIR_WAVES
-#define GN_SIR_WAVES 24
-#endif
-#ifndef GN_SIR_THREADS
-#define GN_SIR_THREADS 0
-#endif
-static int frontier_threads(int n, int n_big, int* per_cu_out) {
-    for (int threads = GN_SIR_THREADS ? GN_SIR_THREADS : (n < 4096 ? 256 : 512); ; threads *= 2) {
-        int per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / (frontier_lds_bytes(n, n_big, threads) + 64)));
-        if (per_cu * (threads / 64) >= 16 || threads == 1024 || GN_SIR_THREADS) {
-            per_cu = std::max(1, std::min(per_cu, GN_SIR_WAVES / (threads / 64)));
-            *per_cu_out = per_cu;
-            return threads;
-        }
-    }
+template <class F> static void sir_dispatch(int rates, bool traj, bool init, F&& f) {   // f(SirKernels<...>{}) of the 3 x 2 x 2 forms
+    if (rates == SIR_EDGES) sir_dispatch_rates<SIR_EDGES>(traj, init, f);
+    else if (rates == SIR_NODES) sir_dispatch_rates<SIR_NODES>(traj, init, f);
+    else sir_dispatch_rates<SIR_SCALAR>(traj, init, f);
 }
-static const int kFrontierGlobalGrid = 1024;       // workgroups that own a set of global lists (graphs past the LDS form)
 
 int gn_sir_set_attributes() {       // once per device, from gnode_graph_create
-    GN_HIP(hipFuncSetAttribute((const void*)k_sir_frontier<uint16_t, true, false, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
-    GN_HIP(hipFuncSetAttribute((const void*)k_sir_frontier<int32_t, false, false, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
-    GN_HIP(hipFuncSetAttribute((const void*)k_sir_frontier<uint16_t, true, true, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
-    GN_HIP(hipFuncSetAttribute((const void*)k_sir_frontier<int32_t, false, true, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
-    GN_HIP(hipFuncSetAttribute((const void*)k_sir_frontier<uint16_t, true, false, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
-    GN_HIP(hipFuncSetAttribute((const void*)k_sir_frontier<int32_t, false, false, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
-    GN_HIP(hipFuncSetAttribute((const void*)k_sir_frontier<uint16_t, true, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
-    GN_HIP(hipFuncSetAttribute((const void*)k_sir_frontier<int32_t, false, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
-    GN_HIP(hipFuncSetAttribute((const void*)k_sir_frontier<uint16_t, true, false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
-    GN_HIP(hipFuncSetAttribute((const void*)k_sir_frontier<int32_t, false, false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
-    GN_HIP(hipFuncSetAttribute((const void*)k_sir_frontier<uint16_t, true, false, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
-    GN_HIP(hipFuncSetAttribute((const void*)k_sir_frontier<int32_t, false, false, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
-    GN_HIP(hipFuncSetAttribute((const void*)k_sir_frontier<uint16_t, true, false, true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
-    GN_HIP(hipFuncSetAttribute((const void*)k_sir_frontier<int32_t, false, false, true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
-    GN_HIP(hipFuncSetAttribute((const void*)k_sir_philox<true, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
-    GN_HIP(hipFuncSetAttribute((const void*)k_sir_philox<true, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
-    GN_HIP(hipFuncSetAttribute((const void*)k_sir_philox<true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
-    GN_HIP(hipFuncSetAttribute((const void*)k_sir_philox<true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
-    GN_HIP(hipFuncSetAttribute((const void*)k_sir_philox<true, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
-    GN_HIP(hipFuncSetAttribute((const void*)k_sir_philox<true, true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
-    // the INIT instances (drawn start): every rate form, with and without per-trajectory output
-    GN_HIP(hipFuncSetAttribute((const void*)k_sir_frontier<uint16_t, true, false, false, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
-    GN_HIP(hipFuncSetAttribute((const void*)k_sir_frontier<uint16_t, true, false, false, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
-    GN_HIP(hipFuncSetAttribute((const void*)k_sir_frontier<uint16_t, true, false, true, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
-    GN_HIP(hipFuncSetAttribute((const void*)k_sir_frontier<uint16_t, true, false, true, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
-    GN_HIP(hipFuncSetAttribute((const void*)k_sir_frontier<uint16_t, true, false, true, false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
-    GN_HIP(hipFuncSetAttribute((const void*)k_sir_frontier<uint16_t, true, false, true, true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
-    GN_HIP(hipFuncSetAttribute((const void*)k_sir_frontier<int32_t, false, false, false, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
-    GN_HIP(hipFuncSetAttribute((const void*)k_sir_frontier<int32_t, false, false, false, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
-    GN_HIP(hipFuncSetAttribute((const void*)k_sir_frontier<int32_t, false, false, true, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
-    GN_HIP(hipFuncSetAttribute((const void*)k_sir_frontier<int32_t, false, false, true, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
-    GN_HIP(hipFuncSetAttribute((const void*)k_sir_frontier<int32_t, false, false, true, false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
-    GN_HIP(hipFuncSetAttribute((const void*)k_sir_frontier<int32_t, false, false, true, true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
-    GN_HIP(hipFuncSetAttribute((const void*)k_sir_philox<true, false, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
-    GN_HIP(hipFuncSetAttribute((const void*)k_sir_philox<true, false, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
-    GN_HIP(hipFuncSetAttribute((const void*)k_sir_philox<true, true, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
-    GN_HIP(hipFuncSetAttribute((const void*)k_sir_philox<true, true, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
-    GN_HIP(hipFuncSetAttribute((const void*)k_sir_philox<true, true, false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
-    GN_HIP(hipFuncSetAttribute((const void*)k_sir_philox<true, true, true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
-    GN_HIP(hipFuncSetAttribute((const void*)k_sir_coins, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit));
+    hipError_t err = hipSuccess;
+    auto lift = [&](auto kernel) {   // dynamic LDS up to kLdsStateLimit (scan_mem takes none)
+        const hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit);
+        if (err == hipSuccess) err = e;
+    };
+    for (int form = 0; form < 12; ++form)
+        sir_dispatch(form >> 2, form & 2, form & 1, [&](auto K) { lift(K.frontier_lds); lift(K.frontier_mem); lift(K.scan_lds); });
+    lift(kSirCountedLds); lift(kSirCountedMem); lift(&k_sir_coins);
+    GN_HIP(err);
     return 0;
 }
 
 extern "C" size_t gnode_sir_coins_workspace_bytes(void) { return gn_align(4096 * sizeof(int32_t)) + gn_align(64); }
+static size_t sir_ws_bytes(gnode_graph_t g, int32_t T, int form) { return g ? sir_layout(g->info.n, g->nnz, g->n_bigrow, T).bytes[form] : 0; }
+extern "C" size_t gnode_sir_workspace_bytes(gnode_graph_t g, int32_t T) { return sir_ws_bytes(g, T, SIR_SCALAR); }
+extern "C" size_t gnode_sir_nodes_workspace_bytes(gnode_graph_t g, int32_t T) { return sir_ws_bytes(g, T, SIR_NODES); }
+extern "C" size_t gnode_sir_traj_workspace_bytes(gnode_graph_t g, int32_t T) { return sir_ws_bytes(g, T, SIR_NODES); }   // scalar rates too
+extern "C" size_t gnode_sir_edges_workspace_bytes(gnode_graph_t g, int32_t T) { return sir_ws_bytes(g, T, SIR_EDGES); }
+extern "C" size_t gnode_sir_init_workspace_bytes(gnode_graph_t g, int32_t T) { return sir_ws_bytes(g, T, SIR_INIT); }
 
-extern "C" size_t gnode_sir_workspace_bytes(gnode_graph_t g, int32_t T) {
-    if (!g) return 0;
-    size_t b = gn_align((size_t)2 * T * g->info.n * sizeof(uint32_t)) + gn_align(4096 * sizeof(int32_t)) +
-               gn_align((size_t)std::max<int64_t>(g->nnz, 1) * sizeof(int32_t));
-    size_t tail = 0;                                       // one region, two users that never run together
-    if ((size_t)2 * g->info.n > kLdsStateLimit) tail = (size_t)2048 * 2 * g->info.n;                                   // scan kernel, state in memory
-    if (!frontier_lists_in_lds(g->info.n, g->n_bigrow)) tail = std::max(tail, (size_t)kFrontierGlobalGrid * 3 * g->info.n * sizeof(int32_t));   // frontier lists
-    return b + gn_align(tail);
-}
+// One Monte-Carlo call, as its entry states it (include/gnode.h documents the arrays).
+struct SirCall {
+    const char* who = "";                    // the entry's name, for the messages
+    gnode_graph_t g = nullptr;
+    // the start: a seed list on the host, or (drawn) host fp64 [n][3], each trajectory's start drawn from (pS, pI, pR)
+    const int32_t* seeds = nullptr; int32_t n_seeds = 0; bool drawn = false; const double* init = nullptr;
+    SirRates rates;
+    // the outputs.  need_traj: the entry is for per-trajectory output (counts alone will not do)
+    uint32_t* counts = nullptr; int16_t* events = nullptr; uint32_t* curves = nullptr; bool need_traj = false;
+    int64_t sims = 0, sim_offset = 0; int32_t T = 0; uint64_t rng_seed = 0;
+    void *workspace = nullptr, *stream = nullptr; size_t workspace_bytes = 0; int ws_form = SIR_SCALAR;   // which of SirLayout::bytes the entry asks for
+    bool edge_scan = false;                  // the scan kernel (the cross-check) instead of the frontier walk
+    uint64_t* stats_host = nullptr;          // gnode_sir_mc_philox_counted: the counting instances, their tally [4] copied here
+};
+// the arguments every entry has, under the names every entry gives them
+#define SIR_CALL(c, name)                                                                                                         \
+    SirCall c; c.who = name; c.g = g; c.counts = counts; c.sims = sims; c.sim_offset = sim_offset; c.T = T; c.rng_seed = rng_seed; \
+    c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = stream
 
-// per-node form: the layout above, then the thresholds -- uint64 [n] for beta, uint64 [n] for gamma
-static size_t sir_thr_bytes(int n) { return gn_align((size_t)2 * n * sizeof(unsigned long long)); }
-extern "C" size_t gnode_sir_nodes_workspace_bytes(gnode_graph_t g, int32_t T) {
-    return g ? gnode_sir_workspace_bytes(g, T) + sir_thr_bytes(g->info.n) : 0;
-}
-
-// per-edge form: the scalar layout, then the thresholds -- uint64 [nnz] for the entries, uint64 [n] for gamma
-static size_t sir_edge_thr_bytes(gnode_graph_t g) {
-    return gn_align(((size_t)std::max<int64_t>(g->nnz, 0) + (size_t)g->info.n) * sizeof(unsigned long long));
-}
-extern "C" size_t gnode_sir_edges_workspace_bytes(gnode_graph_t g, int32_t T) {
-    return g ? gnode_sir_workspace_bytes(g, T) + sir_edge_thr_bytes(g) : 0;
-}
-
-// drawn-start form: the per-edge layout (the largest of the rate forms'), then the start thresholds -- uint64 [n] for pS,
-// uint64 [n] for pR
-extern "C" size_t gnode_sir_init_workspace_bytes(gnode_graph_t g, int32_t T) {
-    return g ? gnode_sir_edges_workspace_bytes(g, T) + sir_thr_bytes(g->info.n) : 0;
-}
-
-static unsigned long long coin_threshold(double p) {
-    return (unsigned long long)std::min(4294967296.0, std::max(0.0, std::floor(p * 4294967296.0)));
-}
-
-// beta_nodes / gamma_nodes: host fp64 [n] each, or both null (then the scalars beta / gamma hold for every node).
-// edges (gnode_sir_mc_philox_edges): w_edges is host fp64 [nnz] (null only when nnz = 0), beta and beta_nodes are unused,
-// gamma_nodes may be null (then the scalar gamma holds for every node).
-static int sir_mc_philox_impl(gnode_graph_t g, const int32_t* seeds_host, int32_t n_seeds, double beta,
-                              double gamma, int64_t sims, int64_t sim_offset, int32_t T, uint64_t rng_seed,
-                              uint32_t* counts, void* workspace, size_t workspace_bytes, void* stream, bool edge_scan,
-                              unsigned long long* stats = nullptr /* device [4]: the counting instantiation, or null */,
-                              const double* beta_nodes = nullptr, const double* gamma_nodes = nullptr,
-                              bool traj = false /* gnode_sir_mc_philox_traj: counts may be null, events / curves are written */,
-                              int16_t* events = nullptr, uint32_t* curves = nullptr,
-                              bool edges = false, const double* w_edges = nullptr,
-                              const double* init = nullptr /* gnode_sir_mc_philox_init: host fp64 [n][3], in place of the seeds */) {
-    // the entry's name for the messages, by the argument group a check belongs to: the init entry is one for all of them
-    const char* const who = init ? "gnode_sir_mc_philox_init" : "gnode_sir_mc_philox";
-    const char* const who_t = init ? who : "gnode_sir_mc_philox_traj";
-    const char* const who_n = init ? who : "gnode_sir_mc_philox_nodes";
-    const char* const who_e = init ? who : "gnode_sir_mc_philox_edges";
-    GN_CHECK_ARG(g && (counts || traj) && workspace, "%s: null pointer", who);
-    GN_CHECK_ARG(!traj || ((events || curves) && !stats), "%s: neither events nor curves given", who_t);
-    GN_CHECK_ARG(!events || (T <= 32767 && ((uintptr_t)events & 1u) == 0), "%s: events hold int16 steps (T <= 32767)", who_t);
-    const bool nodes = !edges && (beta_nodes || gamma_nodes);
-    GN_CHECK_ARG(!nodes || (beta_nodes && gamma_nodes && !stats), "%s: null rate array", who_n);
-    GN_CHECK_ARG(!edges || ((w_edges || g->nnz == 0) && !beta_nodes && !stats), "%s: null weight array", who_e);
-    GN_CHECK_ARG(n_seeds >= 0 && n_seeds <= 4096 && (seeds_host || n_seeds == 0), "%s: 0..4096 seeds", who);
-    GN_CHECK_ARG(T >= 1 && sims >= 0 && sims <= 0xFFFFFFFFll && sim_offset >= 0 && sim_offset + sims <= 0xFFFFFFFFll,
-                 "%s: bad T/sims/sim_offset", who);
-    GN_CHECK_ARG(beta >= 0.0 && beta <= 1.0 && gamma >= 0.0 && gamma <= 1.0, "%s: beta, gamma in [0,1]", who);
-    for (int i = 0; i < n_seeds; ++i)
-        GN_CHECK_ARG(seeds_host[i] >= 0 && seeds_host[i] < g->info.n, "%s: seed %d out of range", who, seeds_host[i]);
-    const size_t ws_need = init ? gnode_sir_init_workspace_bytes(g, T) : edges ? gnode_sir_edges_workspace_bytes(g, T)
-                                : nodes ? gnode_sir_nodes_workspace_bytes(g, T) : gnode_sir_workspace_bytes(g, T);
-    if (workspace_bytes < ws_need) {
-        gnode_set_error("%s: workspace %zu < %zu", who, workspace_bytes, ws_need);
-        return GNODE_ERR_WORKSPACE;
+static int sir_mc_philox_impl(const SirCall& c) {
+    const gnode_graph_t g = c.g;
+    const SirRates& r = c.rates;
+    const bool traj = c.events || c.curves;
+    const hipStream_t st = (hipStream_t)c.stream;
+    GN_CHECK_ARG(g && c.workspace && (!c.drawn || c.init), "%s: null pointer", c.who);
+    GN_CHECK_ARG(c.need_traj ? traj : (traj || c.counts), "%s: no output array given", c.who);
+    GN_CHECK_ARG(!c.events || (c.T <= 32767 && ((uintptr_t)c.events & 1u) == 0), "%s: events hold int16 steps (T = %d, at most 32767) at an even address", c.who, c.T);
+    GN_CHECK_ARG(r.form != SIR_NODES || (r.beta_nodes && r.gamma_nodes), "%s: one per-node rate array without the other", c.who);
+    GN_CHECK_ARG(r.form != SIR_EDGES || ((r.w_edges || g->nnz == 0) && !r.beta_nodes), "%s: per-edge rates take a weight array and no per-node beta", c.who);
+    GN_CHECK_ARG(c.n_seeds >= 0 && c.n_seeds <= 4096 && (c.seeds || c.n_seeds == 0), "%s: 0..4096 seeds", c.who);
+    GN_CHECK_ARG(c.T >= 1 && c.sims >= 0 && c.sims <= 0xFFFFFFFFll && c.sim_offset >= 0 && c.sim_offset + c.sims <= 0xFFFFFFFFll, "%s: bad T/sims/sim_offset", c.who);
+    const int n = g->info.n, T = c.T;
+    for (int i = 0; i < c.n_seeds; ++i)
+        GN_CHECK_ARG(c.seeds[i] >= 0 && c.seeds[i] < n, "%s: seed %d out of range", c.who, c.seeds[i]);
+    const SirLayout L = sir_layout(n, g->nnz, g->n_bigrow, T);
+    if (c.workspace_bytes < L.bytes[c.ws_form]) {
+        gnode_set_error("%s: workspace %zu < %zu", c.who, c.workspace_bytes, L.bytes[c.ws_form]);
+        return c.stats_host ? GNODE_ERR_ARG : GNODE_ERR_WORKSPACE;   // (the counted entry has always called it an argument)
     }
-    std::vector<unsigned long long> thr_host;              // [beta thresholds | gamma thresholds]
-    if (nodes) {
-        const int n = g->info.n;
-        thr_host.resize((size_t)2 * n);
-        for (int v = 0; v < n; ++v) {                      // (a NaN fails both comparisons)
-            GN_CHECK_ARG(beta_nodes[v] >= 0.0 && beta_nodes[v] <= 1.0, "%s: beta[%d] = %g is not in [0,1]", who_n, v, beta_nodes[v]);
-            GN_CHECK_ARG(gamma_nodes[v] >= 0.0 && gamma_nodes[v] <= 1.0, "%s: gamma[%d] = %g is not in [0,1]", who_n, v, gamma_nodes[v]);
-            thr_host[v] = coin_threshold(beta_nodes[v]);
-            thr_host[(size_t)n + v] = coin_threshold(gamma_nodes[v]);
-        }
+    // A drawn start with per-node rates on a graph of fewer entries than nodes: two per-node arrays would reach into the start
+    // thresholds.  The per-node form is the per-edge one with w[p] = beta[col[p]] (same coins, same counts), and that one fits:
+    // sir_stage restates it.  The column ids come back on the caller's stream, which the call synchronises anyway
+    const bool restate = c.drawn && r.form == SIR_NODES && L.bytes[SIR_NODES] > L.bytes[SIR_EDGES];
+    std::vector<int32_t> col(restate ? (size_t)std::max<int64_t>(g->nnz, 1) : 0);
+    if (restate && g->nnz) {
+        GN_HIP(hipMemcpyAsync(col.data(), g->col, sizeof(int32_t) * (size_t)g->nnz, hipMemcpyDeviceToHost, st));
+        GN_HIP(hipStreamSynchronize(st));
     }
-    const size_t n_thr_b = edges ? (size_t)g->nnz : (size_t)g->info.n;   // infection thresholds in front of the recovery ones
-    if (edges) {
-        const int n = g->info.n;
-        thr_host.resize(n_thr_b + n);
-        for (size_t p = 0; p < n_thr_b; ++p) {
-            GN_CHECK_ARG(w_edges[p] >= 0.0 && w_edges[p] <= 1.0, "%s: the weight at CSR position %zu, %g, is not in [0,1]", who_e, p, w_edges[p]);
-            thr_host[p] = coin_threshold(w_edges[p]);
-        }
-        for (int v = 0; v < n; ++v) {
-            const double gv = gamma_nodes ? gamma_nodes[v] : gamma;
-            GN_CHECK_ARG(gv >= 0.0 && gv <= 1.0, "%s: gamma[%d] = %g is not in [0,1]", who_e, v, gv);
-            thr_host[n_thr_b + v] = coin_threshold(gv);
-        }
-    }
-    std::vector<unsigned long long> init_host;             // [thr(pS) | thr(pR)]
-    if (init) {
-        const int n = g->info.n;
-        init_host.resize((size_t)2 * n);
-        for (int v = 0; v < n; ++v) {
-            const double* p = init + (size_t)3 * v;
-            for (int c = 0; c < 3; ++c)                    // (a NaN fails both comparisons)
-                GN_CHECK_ARG(p[c] >= 0.0 && p[c] <= 1.0, "gnode_sir_mc_philox_init: init[%d][%d] = %g is not in [0,1]", v, c, p[c]);
-            GN_CHECK_ARG(std::fabs(p[0] + p[1] + p[2] - 1.0) <= 1e-6, "gnode_sir_mc_philox_init: the row of node %d sums to %.9g, not 1", v, p[0] + p[1] + p[2]);
-            init_host[v] = coin_threshold(p[0]);
-            init_host[(size_t)n + v] = coin_threshold(p[2]);
-        }
-    }
-    hipStream_t st = (hipStream_t)stream;
-    char* ws = (char*)workspace;
-    const unsigned long long* thr_init = init ? (const unsigned long long*)(ws + gnode_sir_edges_workspace_bytes(g, T)) : nullptr;
-    const unsigned long long* thr_b = (const unsigned long long*)(ws + gnode_sir_workspace_bytes(g, T));   // used when `nodes` or `edges`
-    const unsigned long long* thr_g = thr_b + n_thr_b;
-    const size_t hist_b = gn_align((size_t)2 * T * g->info.n * sizeof(uint32_t));
-    uint32_t* hist = (uint32_t*)ws;
-    int32_t* seeds = (int32_t*)(ws + hist_b);
-    int32_t* src = (int32_t*)(ws + hist_b + gn_align(4096 * sizeof(int32_t)));
-    uint8_t* gstate = (uint8_t*)(ws + hist_b + gn_align(4096 * sizeof(int32_t)) +
-                                 gn_align((size_t)std::max<int64_t>(g->nnz, 1) * sizeof(int32_t)));
-    if (int e = gn_zero_async(hist, hist_b, st)) return e;
-    if (events && sims > 0) {                              // the "never" background, by a kernel like the zero fill above
-        const size_t count = (size_t)2 * (size_t)sims * (size_t)g->info.n;
+    const SirThresholds thr = sir_stage(c.who, n, g->nnz, r, restate ? col.data() : nullptr, c.init);
+    GN_CHECK_ARG(thr.error.empty(), "%s", thr.error.c_str());
+    const int form = restate ? SIR_EDGES : r.form;
+    char* ws = (char*)c.workspace;
+    uint32_t* hist = (uint32_t*)(ws + L.hist);
+    int32_t *seeds = (int32_t*)(ws + L.seeds), *src = (int32_t*)(ws + L.rows);
+    unsigned long long* stats = c.stats_host ? (unsigned long long*)(ws + L.rows) : nullptr;   // the frontier walk leaves the region unused
+    const unsigned long long *thr_b = (const unsigned long long*)(ws + L.thr), *thr_g = thr_b + (thr.rates.size() - (form ? n : 0));
+    const unsigned long long* thr_start = (const unsigned long long*)(ws + L.start);
+    if (stats) GN_HIP(hipMemsetAsync(stats, 0, 4 * sizeof(unsigned long long), st));
+    if (int e = gn_zero_async(hist, L.seeds - L.hist, st)) return e;
+    if (c.events && c.sims > 0) {                          // the "never" background, by a kernel like the zero fill above
+        const size_t count = (size_t)2 * (size_t)c.sims * (size_t)n;
         const int grid = (int)std::min<size_t>((count / 8 + 255) / 256 + 1, (size_t)g->info.num_cu * 8);
-        hipLaunchKernelGGL(k_fill_i16, dim3(grid), dim3(256), 0, st, events, count, (int16_t)-1);
+        hipLaunchKernelGGL(k_fill_i16, dim3(grid), dim3(256), 0, st, c.events, count, (int16_t)-1);
         GN_LAUNCH_CHECK();
     }
     // seed ids: up to 32 travel as a kernel argument (no copy, no synchronisation -- the reference's experiments use 2);
     // longer lists are copied from the caller's host array, which may be a temporary, so the stream is synchronised
     // before returning control (documented in gnode.h)
     SeedArg sa;
-    for (int i = 0; i < 32; ++i) sa.v[i] = i < n_seeds ? seeds_host[i] : 0;
-    if (n_seeds <= 32) {
-        hipLaunchKernelGGL(k_put_seeds, dim3(1), dim3(32), 0, st, sa, n_seeds, seeds);
+    for (int i = 0; i < 32; ++i) sa.v[i] = i < c.n_seeds ? c.seeds[i] : 0;
+    if (c.n_seeds <= 32) {
+        hipLaunchKernelGGL(k_put_seeds, dim3(1), dim3(32), 0, st, sa, c.n_seeds, seeds);
         GN_LAUNCH_CHECK();
     } else {
-        GN_HIP(hipMemcpyAsync(seeds, seeds_host, sizeof(int32_t) * n_seeds, hipMemcpyHostToDevice, st));
+        GN_HIP(hipMemcpyAsync(seeds, c.seeds, sizeof(int32_t) * c.n_seeds, hipMemcpyHostToDevice, st));
     }
-    if (nodes || edges) GN_HIP(hipMemcpyAsync((void*)thr_b, thr_host.data(), thr_host.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, st));
-    if (init) GN_HIP(hipMemcpyAsync((void*)thr_init, init_host.data(), init_host.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, st));
-    if (n_seeds > 32 || nodes || edges || init) GN_HIP(hipStreamSynchronize(st));     // the host arrays are done with
-    const unsigned long long tb = coin_threshold(beta), tg = coin_threshold(gamma);
-    const uint32_t k0 = (uint32_t)(rng_seed & 0xFFFFFFFFull), k1 = (uint32_t)(rng_seed >> 32);
-    if (sims > 0) {
+    if (form) GN_HIP(hipMemcpyAsync((void*)thr_b, thr.rates.data(), thr.rates.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, st));
+    if (c.init) GN_HIP(hipMemcpyAsync((void*)thr_start, thr.start.data(), thr.start.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, st));
+    if (c.n_seeds > 32 || form || c.init) GN_HIP(hipStreamSynchronize(st));     // the host arrays are done with
+    const uint32_t k0 = (uint32_t)(c.rng_seed & 0xFFFFFFFFull), k1 = (uint32_t)(c.rng_seed >> 32);
+    if (c.sims > 0) {
         const bool sampled = gn_prof_begin(3, st);
-        int per_cu_f = 1;
-        const int threads_f = frontier_threads(g->info.n, g->n_bigrow, &per_cu_f);
-        const size_t fl = frontier_lds_bytes(g->info.n, g->n_bigrow, threads_f);
-        const size_t lds = (size_t)2 * g->info.n;
-        // one path selection and launch geometry for all forms: `rates_tag` (0 scalar, 1 per node, 2 per edge) picks the
-        // kernels' NODES / EDGES instances, whose thresholds tb_ / tg_ are the staged arrays instead of the two numbers
-        auto launch = [&](auto rates_tag, auto traj_tag, auto init_tag, auto tb_, auto tg_) {
-            constexpr bool NODES = decltype(rates_tag)::value >= 1;
-            constexpr bool EDGES = decltype(rates_tag)::value == 2;
-            constexpr bool TRAJ = decltype(traj_tag)::value;
-            constexpr bool INIT = decltype(init_tag)::value;
-            SirTraj<TRAJ> tr;
-            if constexpr (TRAJ) { tr.events = events; tr.curves = curves; }
-            SirInit<INIT> in;
-            if constexpr (INIT) in.thr = thr_init;
-            if (fl <= kLdsStateLimit && !edge_scan) {
-                // frontier-driven walk.  Workgroups per CU by LDS, at least 16 waves per CU
-                const int per_cu = per_cu_f, threads = threads_f;
-                if (frontier_lists_in_lds(g->info.n, g->n_bigrow)) {
-                    const int grid = (int)std::min<int64_t>(sims, (int64_t)g->info.num_cu * per_cu);
-                    if constexpr (!NODES && !TRAJ && !INIT) if (stats) {
-                        hipLaunchKernelGGL((k_sir_frontier<uint16_t, true, true, false, false>), dim3(grid), dim3(threads), fl, st, g->rowptr, g->col, g->info.n, seeds,
-                                           n_seeds, tb_, tg_, (long)sims, (long)sim_offset, T, k0, k1, hist, (int32_t*)nullptr, stats, tr, in);
-                        return;
-                    }
-                    hipLaunchKernelGGL((k_sir_frontier<uint16_t, true, false, NODES, TRAJ, EDGES, INIT>), dim3(grid), dim3(threads), fl, st, g->rowptr, g->col, g->info.n, seeds,
-                                       n_seeds, tb_, tg_, (long)sims, (long)sim_offset, T, k0, k1, hist, (int32_t*)nullptr, stats, tr, in);
-                } else {
-                    const int grid = (int)std::min<int64_t>(std::min<int64_t>(sims, (int64_t)g->info.num_cu * per_cu), kFrontierGlobalGrid);
-                    if constexpr (!NODES && !TRAJ && !INIT) if (stats) {
-                        hipLaunchKernelGGL((k_sir_frontier<int32_t, false, true, false, false>), dim3(grid), dim3(threads), fl, st, g->rowptr, g->col, g->info.n, seeds,
-                                           n_seeds, tb_, tg_, (long)sims, (long)sim_offset, T, k0, k1, hist, (int32_t*)gstate, stats, tr, in);
-                        return;
-                    }
-                    hipLaunchKernelGGL((k_sir_frontier<int32_t, false, false, NODES, TRAJ, EDGES, INIT>), dim3(grid), dim3(threads), fl, st, g->rowptr, g->col, g->info.n, seeds,
-                                       n_seeds, tb_, tg_, (long)sims, (long)sim_offset, T, k0, k1, hist, (int32_t*)gstate, stats, tr, in);
-                }
-            } else if (lds <= kLdsStateLimit) {
-                // edge-parallel scan, node state in LDS: graphs whose frontier lists do not fit (n > ~25k with 32-bit ids)
-                hipLaunchKernelGGL(k_expand_rows, dim3((g->info.n + 255) / 256), dim3(256), 0, st, g->rowptr, g->info.n, src);
-                const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / std::max<size_t>(lds, 1)));
-                const int threads = per_cu >= 4 ? 256 : (per_cu >= 2 ? 512 : 1024);
-                const int grid = (int)std::min<int64_t>(sims, (int64_t)g->info.num_cu * per_cu);
-                hipLaunchKernelGGL((k_sir_philox<true, NODES, TRAJ, EDGES, INIT>), dim3(grid), dim3(threads), lds, st, src, g->col, (long)g->nnz, g->info.n, seeds,
-                                   n_seeds, tb_, tg_, (long)sims, (long)sim_offset, T, k0, k1, hist, (uint8_t*)nullptr, tr, in);
-            } else {
-                hipLaunchKernelGGL(k_expand_rows, dim3((g->info.n + 255) / 256), dim3(256), 0, st, g->rowptr, g->info.n, src);
-                const int grid = (int)std::min<int64_t>(sims, 2048);
-                hipLaunchKernelGGL((k_sir_philox<false, NODES, TRAJ, EDGES, INIT>), dim3(grid), dim3(256), 0, st, src, g->col, (long)g->nnz, g->info.n, seeds,
-                                   n_seeds, tb_, tg_, (long)sims, (long)sim_offset, T, k0, k1, hist, gstate, tr, in);
-            }
-        };
-        using Scalar = std::integral_constant<int, 0>; using Nodes = std::integral_constant<int, 1>; using Edges = std::integral_constant<int, 2>;
+        const SirLaunch P = sir_launch_plan(n, g->n_bigrow, g->info.num_cu, c.sims, c.edge_scan);
+        const bool frontier = P.path == SIR_FRONTIER_LDS || P.path == SIR_FRONTIER_MEM;
+        void* tail = P.path == SIR_FRONTIER_MEM || P.path == SIR_SCAN_MEM ? ws + L.tail : nullptr;   // the lists / the state, when not in LDS
+        if (!frontier) hipLaunchKernelGGL(k_expand_rows, dim3((n + 255) / 256), dim3(256), 0, st, g->rowptr, n, src);
         // the drawn start is a set of instances of its own (INIT): the seed-list instances do not carry it
-        auto with_start = [&](auto rates_tag, auto traj_tag, auto tb_, auto tg_) {
-            if (init) launch(rates_tag, traj_tag, std::true_type{}, tb_, tg_);
-            else launch(rates_tag, traj_tag, std::false_type{}, tb_, tg_);
-        };
-        if (edges && traj) with_start(Edges{}, std::true_type{}, thr_b, thr_g);
-        else if (edges) with_start(Edges{}, std::false_type{}, thr_b, thr_g);
-        else if (nodes && traj) with_start(Nodes{}, std::true_type{}, thr_b, thr_g);
-        else if (nodes) with_start(Nodes{}, std::false_type{}, thr_b, thr_g);
-        else if (traj) with_start(Scalar{}, std::true_type{}, tb, tg);
-        else with_start(Scalar{}, std::false_type{}, tb, tg);
+        sir_dispatch(form, traj, c.init != nullptr, [&](auto K) {
+            using Kt = decltype(K);
+            SirTraj<Kt::TRAJ> tr;
+            SirInit<Kt::INIT> in;
+            SirThr<Kt::NODES> tb, tg;                      // the staged arrays, or the two numbers
+            if constexpr (Kt::TRAJ) { tr.events = c.events; tr.curves = c.curves; }
+            if constexpr (Kt::INIT) in.thr = thr_start;
+            if constexpr (Kt::NODES) { tb = thr_b; tg = thr_g; } else { tb = thr.tb; tg = thr.tg; }
+            if (frontier) {
+                auto kernel = P.path == SIR_FRONTIER_LDS ? Kt::frontier_lds : Kt::frontier_mem;
+                if constexpr (!Kt::NODES && !Kt::TRAJ && !Kt::INIT) if (stats) kernel = P.path == SIR_FRONTIER_LDS ? kSirCountedLds : kSirCountedMem;
+                hipLaunchKernelGGL(kernel, dim3(P.grid), dim3(P.threads), P.lds, st, g->rowptr, g->col, n, seeds, c.n_seeds, tb, tg, (long)c.sims,
+                                   (long)c.sim_offset, T, k0, k1, hist, (int32_t*)tail, stats, tr, in);
+            } else {
+                auto kernel = P.path == SIR_SCAN_LDS ? Kt::scan_lds : Kt::scan_mem;
+                hipLaunchKernelGGL(kernel, dim3(P.grid), dim3(P.threads), P.lds, st, src, g->col, (long)g->nnz, n, seeds, c.n_seeds, tb, tg, (long)c.sims,
+                                   (long)c.sim_offset, T, k0, k1, hist, (uint8_t*)tail, tr, in);
+            }
+        });
         if (sampled) gn_prof_end(3, st);
         GN_LAUNCH_CHECK();
     }
-    if (!counts) return 0;                                 // (gnode_sir_mc_philox_traj without counts)
-    if (init) hipLaunchKernelGGL(k_sir_finalize<true>, dim3((g->info.n + 255) / 256), dim3(256), 0, st, hist, g->info.n, T, (uint32_t)sims, counts);
-    else hipLaunchKernelGGL(k_sir_finalize<false>, dim3((g->info.n + 255) / 256), dim3(256), 0, st, hist, g->info.n, T, (uint32_t)sims, counts);
-    GN_LAUNCH_CHECK();
+    if (c.counts) {                                        // (per-trajectory output alone: no counts)
+        hipLaunchKernelGGL(c.init ? k_sir_finalize<true> : k_sir_finalize<false>, dim3((n + 255) / 256), dim3(256), 0, st, hist, n, T, (uint32_t)c.sims, c.counts);
+        GN_LAUNCH_CHECK();
+    }
+    if (stats) {
+        GN_HIP(hipMemcpyAsync(c.stats_host, stats, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+        GN_HIP(hipStreamSynchronize(st));
+    }
     return 0;
 }
 
-extern "C" int gnode_sir_mc_philox(gnode_graph_t g, const int32_t* seeds_host, int32_t n_seeds, double beta,
-                                   double gamma, int64_t sims, int64_t sim_offset, int32_t T, uint64_t rng_seed,
-                                   uint32_t* counts, void* workspace, size_t workspace_bytes, void* stream) {
-    return sir_mc_philox_impl(g, seeds_host, n_seeds, beta, gamma, sims, sim_offset, T, rng_seed, counts, workspace,
-                              workspace_bytes, stream, false);
+extern "C" int gnode_sir_mc_philox(gnode_graph_t g, const int32_t* seeds_host, int32_t n_seeds, double beta, double gamma, int64_t sims,
+                                   int64_t sim_offset, int32_t T, uint64_t rng_seed, uint32_t* counts, void* workspace, size_t workspace_bytes,
+                                   void* stream) {
+    SIR_CALL(c, "gnode_sir_mc_philox");
+    c.seeds = seeds_host; c.n_seeds = n_seeds; c.rates.beta = beta; c.rates.gamma = gamma;
+    return sir_mc_philox_impl(c);
 }
 
-// The production kernel's profiling instantiation: the same counts, plus what the launch did -- stats_host[0] Philox blocks
-// computed, [1] infection coins drawn, [2] recovery coins drawn, [3] CSR entries read.  Synchronises `stream`.
-extern "C" int gnode_sir_mc_philox_counted(gnode_graph_t g, const int32_t* seeds_host, int32_t n_seeds, double beta,
-                                           double gamma, int64_t sims, int64_t sim_offset, int32_t T, uint64_t rng_seed,
-                                           uint32_t* counts, void* workspace, size_t workspace_bytes, void* stream,
-                                           uint64_t* stats_host) {
-    GN_CHECK_ARG(stats_host && workspace, "gnode_sir_mc_philox_counted: null pointer");
-    GN_CHECK_ARG(workspace_bytes >= gnode_sir_workspace_bytes(g, T), "gnode_sir_mc_philox_counted: workspace too small");
-    // the tally lives in the (otherwise unused by the frontier walk) row-expansion region of the workspace
-    char* ws = (char*)workspace;
-    unsigned long long* stats = (unsigned long long*)(ws + gn_align((size_t)2 * T * g->info.n * sizeof(uint32_t)) + gn_align(4096 * sizeof(int32_t)));
-    GN_CHECK_ARG(g->nnz >= 8, "gnode_sir_mc_philox_counted: graph too small");
-    GN_HIP(hipMemsetAsync(stats, 0, 4 * sizeof(unsigned long long), (hipStream_t)stream));
-    if (int e = sir_mc_philox_impl(g, seeds_host, n_seeds, beta, gamma, sims, sim_offset, T, rng_seed, counts, workspace,
-                                   workspace_bytes, stream, false, stats))
-        return e;
-    GN_HIP(hipMemcpyAsync(stats_host, stats, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, (hipStream_t)stream));
-    GN_HIP(hipStreamSynchronize((hipStream_t)stream));
-    return 0;
+// The profiling instantiation: the same counts, plus stats_host[0] Philox blocks computed, [1] infection coins drawn, [2] recovery
+// coins drawn, [3] CSR entries read.  Synchronises `stream`.
+extern "C" int gnode_sir_mc_philox_counted(gnode_graph_t g, const int32_t* seeds_host, int32_t n_seeds, double beta, double gamma, int64_t sims,
+                                           int64_t sim_offset, int32_t T, uint64_t rng_seed, uint32_t* counts, void* workspace,
+                                           size_t workspace_bytes, void* stream, uint64_t* stats_host) {
+    GN_CHECK_ARG(stats_host && g && g->nnz >= 8, "gnode_sir_mc_philox_counted: null pointer, or a graph too small to hold the tally");
+    SIR_CALL(c, "gnode_sir_mc_philox_counted");
+    c.seeds = seeds_host; c.n_seeds = n_seeds; c.rates.beta = beta; c.rates.gamma = gamma; c.stats_host = stats_host;
+    return sir_mc_philox_impl(c);
 }
 
-extern "C" int gnode_sir_mc_philox_scan(gnode_graph_t g, const int32_t* seeds_host, int32_t n_seeds, double beta,
-                                        double gamma, int64_t sims, int64_t sim_offset, int32_t T, uint64_t rng_seed,
-                                        uint32_t* counts, void* workspace, size_t workspace_bytes, void* stream) {
-    return sir_mc_philox_impl(g, seeds_host, n_seeds, beta, gamma, sims, sim_offset, T, rng_seed, counts, workspace,
-                              workspace_bytes, stream, true);
+extern "C" int gnode_sir_mc_philox_scan(gnode_graph_t g, const int32_t* seeds_host, int32_t n_seeds, double beta, double gamma, int64_t sims,
+                                        int64_t sim_offset, int32_t T, uint64_t rng_seed, uint32_t* counts, void* workspace, size_t workspace_bytes,
+                                        void* stream) {
+    SIR_CALL(c, "gnode_sir_mc_philox_scan");
+    c.seeds = seeds_host; c.n_seeds = n_seeds; c.rates.beta = beta; c.rates.gamma = gamma; c.edge_scan = true;
+    return sir_mc_philox_impl(c);
 }
 
-// Per-node rates: beta_host[v] is the probability that an entry (u -> v) with u infected infects the susceptible v,
-// gamma_host[u] that the infected u recovers.  Validated here, turned into thresholds by the scalar path's expression and
-// staged through the workspace; synchronises `stream`.  edge_scan != 0: the scan kernel (the cross-check).
+// Per-node rates: beta_host[v] is the probability that an entry (u -> v) with u infected infects the susceptible v, gamma_host[u]
+// that the infected u recovers.  Staged through the workspace (sir_stage); synchronises `stream`.
 extern "C" int gnode_sir_mc_philox_nodes(gnode_graph_t g, const int32_t* seeds_host, int32_t n_seeds, const double* beta_host,
-                                         const double* gamma_host, int64_t sims, int64_t sim_offset, int32_t T, uint64_t rng_seed,
-                                         uint32_t* counts, void* workspace, size_t workspace_bytes, void* stream, int32_t edge_scan) {
-    GN_CHECK_ARG(beta_host && gamma_host, "gnode_sir_mc_philox_nodes: null rate array");
-    return sir_mc_philox_impl(g, seeds_host, n_seeds, 0.0, 0.0, sims, sim_offset, T, rng_seed, counts, workspace,
-                              workspace_bytes, stream, edge_scan != 0, nullptr, beta_host, gamma_host);
+                                         const double* gamma_host, int64_t sims, int64_t sim_offset, int32_t T, uint64_t rng_seed, uint32_t* counts,
+                                         void* workspace, size_t workspace_bytes, void* stream, int32_t edge_scan) {
+    SIR_CALL(c, "gnode_sir_mc_philox_nodes");
+    c.seeds = seeds_host; c.n_seeds = n_seeds; c.ws_form = SIR_NODES; c.edge_scan = edge_scan != 0;
+    c.rates.form = SIR_NODES; c.rates.beta_nodes = beta_host; c.rates.gamma_nodes = gamma_host;
+    return sir_mc_philox_impl(c);
 }
 
-// Per-trajectory output (include/gnode.h): the call above with the kernels' TRAJ instances -- same validation, path selection,
-// geometry and coins; scalar rates when both arrays are null.  The workspace is the per-node form's in either case.
-extern "C" size_t gnode_sir_traj_workspace_bytes(gnode_graph_t g, int32_t T) { return gnode_sir_nodes_workspace_bytes(g, T); }
+// Per-trajectory output: the kernels' TRAJ instances; scalar rates when both arrays are null, the per-node form's workspace either way.
 extern "C" int gnode_sir_mc_philox_traj(gnode_graph_t g, const int32_t* seeds_host, int32_t n_seeds, double beta, double gamma,
-                                        const double* beta_host, const double* gamma_host, int64_t sims, int64_t sim_offset,
-                                        int32_t T, uint64_t rng_seed, int16_t* events, uint32_t* curves, uint32_t* counts,
-                                        void* workspace, size_t workspace_bytes, void* stream, int32_t edge_scan) {
-    GN_CHECK_ARG(events || curves, "gnode_sir_mc_philox_traj: neither events nor curves given");
-    GN_CHECK_ARG(!beta_host == !gamma_host, "gnode_sir_mc_philox_traj: one rate array without the other");
-    GN_CHECK_ARG(!events || T <= 32767, "gnode_sir_mc_philox_traj: events hold int16 steps, T = %d > 32767", T);
-    GN_CHECK_ARG(g && workspace, "gnode_sir_mc_philox_traj: null pointer");
-    if (workspace_bytes < gnode_sir_traj_workspace_bytes(g, T)) {
-        gnode_set_error("gnode_sir_mc_philox_traj: workspace %zu < %zu", workspace_bytes, gnode_sir_traj_workspace_bytes(g, T));
-        return GNODE_ERR_WORKSPACE;
-    }
-    const bool nodes = beta_host != nullptr;
-    return sir_mc_philox_impl(g, seeds_host, n_seeds, nodes ? 0.0 : beta, nodes ? 0.0 : gamma, sims, sim_offset, T, rng_seed, counts,
-                              workspace, workspace_bytes, stream, edge_scan != 0, nullptr, beta_host, gamma_host, true, events, curves);
+                                        const double* beta_host, const double* gamma_host, int64_t sims, int64_t sim_offset, int32_t T,
+                                        uint64_t rng_seed, int16_t* events, uint32_t* curves, uint32_t* counts, void* workspace,
+                                        size_t workspace_bytes, void* stream, int32_t edge_scan) {
+    SIR_CALL(c, "gnode_sir_mc_philox_traj");
+    c.seeds = seeds_host; c.n_seeds = n_seeds; c.ws_form = SIR_NODES; c.edge_scan = edge_scan != 0; c.events = events; c.curves = curves; c.need_traj = true;
+    c.rates.form = (beta_host || gamma_host) ? SIR_NODES : SIR_SCALAR; c.rates.beta = beta; c.rates.gamma = gamma; c.rates.beta_nodes = beta_host; c.rates.gamma_nodes = gamma_host;
+    return sir_mc_philox_impl(c);
 }
 
-// Per-edge transmission probabilities (include/gnode.h): w_host[p] is the probability that the row of CSR position p infects
-// col[p].  The same impl -- validation, path selection, geometry, coins -- through the kernels' EDGES instances.
-extern "C" int gnode_sir_mc_philox_edges(gnode_graph_t g, const int32_t* seeds_host, int32_t n_seeds, const double* w_host,
-                                         double gamma, const double* gamma_host, int64_t sims, int64_t sim_offset, int32_t T,
-                                         uint64_t rng_seed, uint32_t* counts, void* workspace, size_t workspace_bytes, void* stream,
-                                         int32_t edge_scan) {
-    return sir_mc_philox_impl(g, seeds_host, n_seeds, 0.0, gamma_host ? 0.0 : gamma, sims, sim_offset, T, rng_seed, counts, workspace,
-                              workspace_bytes, stream, edge_scan != 0, nullptr, nullptr, gamma_host, false, nullptr, nullptr, true, w_host);
+// Per-edge transmission probabilities: w_host[p] is the probability that the row of CSR position p infects col[p] (EDGES instances).
+extern "C" int gnode_sir_mc_philox_edges(gnode_graph_t g, const int32_t* seeds_host, int32_t n_seeds, const double* w_host, double gamma,
+                                         const double* gamma_host, int64_t sims, int64_t sim_offset, int32_t T, uint64_t rng_seed, uint32_t* counts,
+                                         void* workspace, size_t workspace_bytes, void* stream, int32_t edge_scan) {
+    SIR_CALL(c, "gnode_sir_mc_philox_edges");
+    c.seeds = seeds_host; c.n_seeds = n_seeds; c.ws_form = SIR_EDGES; c.edge_scan = edge_scan != 0;
+    c.rates.form = SIR_EDGES; c.rates.w_edges = w_host; c.rates.gamma = gamma; c.rates.gamma_nodes = gamma_host;
+    return sir_mc_philox_impl(c);
 }
-extern "C" int gnode_sir_mc_philox_traj_edges(gnode_graph_t g, const int32_t* seeds_host, int32_t n_seeds, const double* w_host,
-                                              double gamma, const double* gamma_host, int64_t sims, int64_t sim_offset, int32_t T,
-                                              uint64_t rng_seed, int16_t* events, uint32_t* curves, uint32_t* counts, void* workspace,
-                                              size_t workspace_bytes, void* stream, int32_t edge_scan) {
-    GN_CHECK_ARG(events || curves, "gnode_sir_mc_philox_traj_edges: neither events nor curves given");
-    GN_CHECK_ARG(!events || T <= 32767, "gnode_sir_mc_philox_traj_edges: events hold int16 steps, T = %d > 32767", T);
-    return sir_mc_philox_impl(g, seeds_host, n_seeds, 0.0, gamma_host ? 0.0 : gamma, sims, sim_offset, T, rng_seed, counts, workspace,
-                              workspace_bytes, stream, edge_scan != 0, nullptr, nullptr, gamma_host, true, events, curves, true, w_host);
+extern "C" int gnode_sir_mc_philox_traj_edges(gnode_graph_t g, const int32_t* seeds_host, int32_t n_seeds, const double* w_host, double gamma,
+                                              const double* gamma_host, int64_t sims, int64_t sim_offset, int32_t T, uint64_t rng_seed,
+                                              int16_t* events, uint32_t* curves, uint32_t* counts, void* workspace, size_t workspace_bytes,
+                                              void* stream, int32_t edge_scan) {
+    SIR_CALL(c, "gnode_sir_mc_philox_traj_edges");
+    c.seeds = seeds_host; c.n_seeds = n_seeds; c.ws_form = SIR_EDGES; c.edge_scan = edge_scan != 0; c.events = events; c.curves = curves; c.need_traj = true;
+    c.rates.form = SIR_EDGES; c.rates.w_edges = w_host; c.rates.gamma = gamma; c.rates.gamma_nodes = gamma_host;
+    return sir_mc_philox_impl(c);
 }
 
-// Initial-state distributions (include/gnode.h): one entry for the three rate forms and every output.  The same impl; the
-// kernels draw each trajectory's start from the staged thresholds of `init_host` instead of reading a seed list.
-extern "C" int gnode_sir_mc_philox_init(gnode_graph_t g, const double* init_host, double beta, const double* beta_host,
-                                        const double* w_host, double gamma, const double* gamma_host, int64_t sims,
-                                        int64_t sim_offset, int32_t T, uint64_t rng_seed, int16_t* events, uint32_t* curves,
-                                        uint32_t* counts, void* workspace, size_t workspace_bytes, void* stream, int32_t edge_scan) {
-    GN_CHECK_ARG(g && init_host && workspace, "gnode_sir_mc_philox_init: null pointer");
-    GN_CHECK_ARG(events || curves || counts, "gnode_sir_mc_philox_init: none of events, curves and counts given");
-    GN_CHECK_ARG(!events || T <= 32767, "gnode_sir_mc_philox_init: events hold int16 steps, T = %d > 32767", T);
-    const bool edges = w_host != nullptr, nodes = !edges && beta_host && gamma_host;
-    GN_CHECK_ARG(!edges || !beta_host, "gnode_sir_mc_philox_init: per-edge rates and per-node beta together");
-    GN_CHECK_ARG(edges || nodes || (!beta_host && !gamma_host), "gnode_sir_mc_philox_init: one per-node rate array without the other");
-    const bool traj = events || curves;
-    if (nodes && sir_thr_bytes(g->info.n) > sir_edge_thr_bytes(g)) {
-        // fewer entries than nodes: two per-node arrays would reach into the start thresholds.  The per-node form is the
-        // per-edge one with w[p] = beta[col[p]] (same coins, same counts), and that one fits: restate it.  (beta is checked
-        // here so that the message names the node; the impl then sees weights that are all in range.)  The column ids come
-        // back on the caller's stream, which the entry synchronises anyway
-        for (int v = 0; v < g->info.n; ++v)
-            GN_CHECK_ARG(beta_host[v] >= 0.0 && beta_host[v] <= 1.0, "gnode_sir_mc_philox_init: beta[%d] = %g is not in [0,1]", v, beta_host[v]);
-        std::vector<int32_t> col((size_t)g->nnz);
-        if (g->nnz) {
-            GN_HIP(hipMemcpyAsync(col.data(), g->col, sizeof(int32_t) * (size_t)g->nnz, hipMemcpyDeviceToHost, (hipStream_t)stream));
-            GN_HIP(hipStreamSynchronize((hipStream_t)stream));
-        }
-        std::vector<double> w((size_t)std::max<int64_t>(g->nnz, 1), 0.0);
-        for (size_t p = 0; p < (size_t)g->nnz; ++p) w[p] = beta_host[col[p]];
-        return sir_mc_philox_impl(g, nullptr, 0, 0.0, 0.0, sims, sim_offset, T, rng_seed, counts, workspace, workspace_bytes, stream,
-                                  edge_scan != 0, nullptr, nullptr, gamma_host, traj, events, curves, true, w.data(), init_host);
-    }
-    return sir_mc_philox_impl(g, nullptr, 0, (edges || nodes) ? 0.0 : beta, (nodes || (edges && gamma_host)) ? 0.0 : gamma, sims, sim_offset,
-                              T, rng_seed, counts, workspace, workspace_bytes, stream, edge_scan != 0, nullptr, nodes ? beta_host : nullptr,
-                              (nodes || edges) ? gamma_host : nullptr, traj, events, curves, edges, w_host, init_host);
+// Initial-state distributions: one entry for the three rate forms and every output; each trajectory's start is drawn from the
+// staged thresholds of `init_host` instead of a seed list (INIT instances).
+extern "C" int gnode_sir_mc_philox_init(gnode_graph_t g, const double* init_host, double beta, const double* beta_host, const double* w_host,
+                                        double gamma, const double* gamma_host, int64_t sims, int64_t sim_offset, int32_t T, uint64_t rng_seed,
+                                        int16_t* events, uint32_t* curves, uint32_t* counts, void* workspace, size_t workspace_bytes, void* stream,
+                                        int32_t edge_scan) {
+    SIR_CALL(c, "gnode_sir_mc_philox_init");
+    c.drawn = true; c.init = init_host; c.ws_form = SIR_INIT; c.edge_scan = edge_scan != 0; c.events = events; c.curves = curves;
+    c.rates.form = w_host ? SIR_EDGES : (beta_host || gamma_host) ? SIR_NODES : SIR_SCALAR; c.rates.beta = beta; c.rates.gamma = gamma;
+    c.rates.beta_nodes = beta_host; c.rates.gamma_nodes = gamma_host; c.rates.w_edges = w_host;
+    return sir_mc_philox_impl(c);
 }
 
 extern "C" int gnode_sir_mc_coins(const int32_t* table_src, const int32_t* table_dst, int64_t n_table, int32_t n,

@@ -1,0 +1,122 @@
+// Layout, launch plan and staging of the Monte-Carlo SIR calls (gnode_sir_plan.h); gnode_sir.hip holds the kernels and the calls.
+#include "gnode_sir_plan.h"
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+
+static size_t al(size_t x) { return (x + 255) / 256 * 256; }
+
+static size_t frontier_bitmap_bytes(int n) { return 3 * ((((size_t)n + 31) / 32 + 3) & ~(size_t)3) * 4; }   // ever-infected + spent + recovered
+// list elements in LDS: current + next frontier [n] each, long rows [as many as the graph has, padded to 8]
+static size_t frontier_list_bytes(int n, int n_big) { return 2 * (2 * (size_t)n + (((size_t)n_big + 7) & ~(size_t)7)); }
+bool frontier_lists_in_lds(int n, int n_big) { return n <= 65536 && frontier_bitmap_bytes(n) + frontier_list_bytes(n, n_big) <= 48 * 1024; }
+// + 1 KB of coin queue per wave
+size_t frontier_lds_bytes(int n, int n_big, int threads) {
+    return frontier_bitmap_bytes(n) + (size_t)(threads / 64) * 1024 + (frontier_lists_in_lds(n, n_big) ? frontier_list_bytes(n, n_big) : 0);
+}
+// Workgroup size and workgroups per CU (the LDS decides how many fit).  Measured, 10 000 x 20 (2 000 x 30 at epinions size),
+// beta 0.3 / 0.05, ms:            16 waves per CU    24 waves      32 waves
+//   fb-social size (256 threads)        --           2.90 / 4.12   3.26 / 4.14
+//   wiki-vote size (512 threads)    9.8 / 28.0       8.2 / 22.5    9.3 / 25.1
+//   epinions size  (512 threads)        --          29.5 / 36.8   35.7 / 41.9     (256 threads x 5: 37.1 / 46.8)
+// -- past 24 waves the resident trajectories thrash each other's rows in the L2, below it the waits are exposed.  So: 256
+// threads for small graphs, 512 otherwise (1 024 when the LDS leaves fewer than 16 waves), at most GN_SIR_WAVES waves per CU.
+#ifndef GN_SIR_WAVES
+#define GN_SIR_WAVES 24
+#endif
+#ifndef GN_SIR_THREADS
+#define GN_SIR_THREADS 0
+#endif
+int frontier_threads(int n, int n_big, int* per_cu_out) {
+    for (int threads = GN_SIR_THREADS ? GN_SIR_THREADS : (n < 4096 ? 256 : 512); ; threads *= 2) {
+        int per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / (frontier_lds_bytes(n, n_big, threads) + 64)));
+        if (per_cu * (threads / 64) >= 16 || threads == 1024 || GN_SIR_THREADS) {
+            per_cu = std::max(1, std::min(per_cu, GN_SIR_WAVES / (threads / 64)));
+            *per_cu_out = per_cu;
+            return threads;
+        }
+    }
+}
+
+SirLaunch sir_launch_plan(int n, int n_bigrow, int num_cu, int64_t sims, bool edge_scan) {
+    int per_cu = 1;
+    const int threads = frontier_threads(n, n_bigrow, &per_cu);
+    const size_t fl = frontier_lds_bytes(n, n_bigrow, threads), lds = (size_t)2 * n;
+    if (fl <= kLdsStateLimit && !edge_scan) {
+        // frontier-driven walk.  Workgroups per CU by LDS, at least 16 waves per CU
+        const int64_t grid = std::min<int64_t>(sims, (int64_t)num_cu * per_cu);
+        if (frontier_lists_in_lds(n, n_bigrow)) return {SIR_FRONTIER_LDS, threads, (int)grid, fl};
+        return {SIR_FRONTIER_MEM, threads, (int)std::min<int64_t>(grid, kFrontierGlobalGrid), fl};
+    }
+    if (lds <= kLdsStateLimit) {
+        // edge-parallel scan, node state in LDS: 256 threads for small graphs, 1024 when the state allows one workgroup per CU
+        per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / std::max<size_t>(lds, 1)));
+        return {SIR_SCAN_LDS, per_cu >= 4 ? 256 : (per_cu >= 2 ? 512 : 1024), (int)std::min<int64_t>(sims, (int64_t)num_cu * per_cu), lds};
+    }
+    return {SIR_SCAN_MEM, 256, (int)std::min<int64_t>(sims, 2048), 0};
+}
+
+SirLayout sir_layout(int n, int64_t nnz, int n_bigrow, int T) {
+    SirLayout L;
+    L.hist = 0;
+    L.seeds = L.hist + al((size_t)2 * T * n * sizeof(uint32_t));
+    L.rows = L.seeds + al(4096 * sizeof(int32_t));
+    L.tail = L.rows + al((size_t)std::max<int64_t>(nnz, 1) * sizeof(int32_t));
+    size_t tail = 0;
+    if ((size_t)2 * n > kLdsStateLimit) tail = (size_t)2048 * 2 * n;
+    if (!frontier_lists_in_lds(n, n_bigrow)) tail = std::max(tail, (size_t)kFrontierGlobalGrid * 3 * n * sizeof(int32_t));
+    L.thr = L.bytes[SIR_SCALAR] = L.tail + al(tail);
+    const size_t per_node = al((size_t)2 * n * sizeof(unsigned long long));
+    L.bytes[SIR_NODES] = L.thr + per_node;
+    L.start = L.bytes[SIR_EDGES] = L.thr + al(((size_t)std::max<int64_t>(nnz, 0) + (size_t)n) * sizeof(unsigned long long));
+    L.bytes[SIR_INIT] = L.start + per_node;
+    return L;
+}
+
+unsigned long long coin_threshold(double p) {
+    return (unsigned long long)std::min(4294967296.0, std::max(0.0, std::floor(p * 4294967296.0)));
+}
+
+static SirThresholds refused(const char* msg) { SirThresholds t; t.error = msg; return t; }   // nothing staged, only the message
+#define refuse(...) (snprintf(buf, sizeof buf, __VA_ARGS__), refused(buf))
+
+SirThresholds sir_stage(const char* who, int n, int64_t nnz, const SirRates& r, const int32_t* restate_col, const double* init) {
+    SirThresholds t;
+    char buf[256];
+    const int32_t* col = r.form == SIR_NODES ? restate_col : nullptr;
+    const auto prob = [](double p) { return p >= 0.0 && p <= 1.0; };   // (a NaN fails both comparisons)
+    if (r.form == SIR_SCALAR) {
+        if (!prob(r.beta) || !prob(r.gamma)) return refuse("%s: beta = %g, gamma = %g are not both in [0,1]", who, r.beta, r.gamma);
+        t.tb = coin_threshold(r.beta); t.tg = coin_threshold(r.gamma);
+    } else {
+        const size_t nb = (r.form == SIR_EDGES || col) ? (size_t)nnz : (size_t)n;   // infection thresholds in front of the recovery ones
+        t.rates.resize(nb + n);
+        if (r.form == SIR_EDGES) {
+            for (size_t p = 0; p < nb; ++p) {
+                if (!prob(r.w_edges[p])) return refuse("%s: the weight at CSR position %zu, %g, is not in [0,1]", who, p, r.w_edges[p]);
+                t.rates[p] = coin_threshold(r.w_edges[p]);
+            }
+        } else {
+            for (int v = 0; v < n; ++v)
+                if (!prob(r.beta_nodes[v])) return refuse("%s: beta[%d] = %g is not in [0,1]", who, v, r.beta_nodes[v]);
+            for (size_t p = 0; p < nb; ++p) t.rates[p] = coin_threshold(r.beta_nodes[col ? col[p] : (int)p]);
+        }
+        for (int v = 0; v < n; ++v) {
+            const double gv = r.gamma_nodes ? r.gamma_nodes[v] : r.gamma;
+            if (!prob(gv)) return refuse("%s: gamma[%d] = %g is not in [0,1]", who, v, gv);
+            t.rates[nb + v] = coin_threshold(gv);
+        }
+    }
+    if (init) {
+        t.start.resize((size_t)2 * n);
+        for (int v = 0; v < n; ++v) {
+            const double* p = init + (size_t)3 * v;
+            for (int c = 0; c < 3; ++c)
+                if (!prob(p[c])) return refuse("%s: init[%d][%d] = %g is not in [0,1]", who, v, c, p[c]);
+            if (!(std::fabs(p[0] + p[1] + p[2] - 1.0) <= 1e-6)) return refuse("%s: the row of node %d sums to %.9g, not 1", who, v, p[0] + p[1] + p[2]);
+            t.start[v] = coin_threshold(p[0]);
+            t.start[(size_t)n + v] = coin_threshold(p[2]);
+        }
+    }
+    return t;
+}

@@ -1,0 +1,50 @@
+// The host side of the Monte-Carlo SIR calls that never touches the device, each stated once: where every array of a call sits
+// in the caller's workspace (sir_layout), which kernel path a call takes with what geometry (sir_launch_plan), and the coin
+// thresholds staged from the caller's rates and start distribution (sir_stage).  Plain C++, like gnode_graph_plan.h:
+// tests/test_sir_plan.py compiles this unit with the system compiler and pins it to the commit before it existed.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+#include <string>
+#include <vector>
+
+static const size_t kLdsStateLimit = 150 * 1024;   // of the CU's 160 KiB
+static const int kFrontierGlobalGrid = 1024;       // workgroups that own a set of global lists (graphs past the LDS form)
+
+enum { SIR_SCALAR = 0, SIR_NODES = 1, SIR_EDGES = 2, SIR_INIT = 3 };   // rate forms (the kernels' NODES / EDGES instances); SIR_INIT only indexes SirLayout::bytes
+
+// Byte offsets into a call's workspace (each 256-byte aligned), and what each form needs of it.
+struct SirLayout {
+    size_t hist, seeds;   // uint32 [2][T][n] event histograms (up to `seeds`), int32 [4096] seed ids
+    size_t rows;       // int32 [max(nnz, 1)]: the scan's row expansion; the counted call's tally (the frontier walk leaves it unused)
+    size_t tail;       // one region, two users that never run together: the scan's state in memory (2048 x 2n bytes, n past the
+                       // LDS state) and the frontier's global lists (kFrontierGlobalGrid x 3n int32, lists past the LDS form)
+    size_t thr;        // uint64 rate thresholds: [n beta | n gamma] per node, [nnz entries | n gamma] per edge
+    size_t start;      // uint64 [2][n] start thresholds thr(pS) | thr(pR): behind the per-edge form, the largest of the rate forms'
+    size_t bytes[4];   // the workspace of SIR_SCALAR (= thr), SIR_NODES, SIR_EDGES (= start) and SIR_INIT
+};
+SirLayout sir_layout(int n, int64_t nnz, int n_bigrow, int T);
+
+// LDS of the frontier kernel: bitmaps + 1 KB of coin queue per wave (+ three uint16 node lists when they fit: n <= 11 232 without long rows)
+bool frontier_lists_in_lds(int n, int n_big);
+size_t frontier_lds_bytes(int n, int n_big, int threads);
+int frontier_threads(int n, int n_big, int* per_cu_out);   // workgroup size, and workgroups per CU
+
+enum SirPath { SIR_FRONTIER_LDS, SIR_FRONTIER_MEM /* lists in the workspace */, SIR_SCAN_LDS, SIR_SCAN_MEM /* state in the workspace */ };
+struct SirLaunch { SirPath path; int threads, grid; size_t lds; };
+SirLaunch sir_launch_plan(int n, int n_bigrow, int num_cu, int64_t sims, bool edge_scan);
+unsigned long long coin_threshold(double p);   // a coin fires iff (64-bit) word < thr, thr = floor(p * 2^32) in [0, 2^32]
+
+// The rates of a call, on the host.  SIR_SCALAR: beta, gamma.  SIR_NODES: beta_nodes, gamma_nodes, fp64 [n] each.  SIR_EDGES:
+// w_edges, fp64 [nnz] in CSR position order, with gamma_nodes or (when that is null) the scalar gamma for every node.
+struct SirRates { int form = SIR_SCALAR; double beta = 0.0, gamma = 0.0; const double *beta_nodes = nullptr, *gamma_nodes = nullptr, *w_edges = nullptr; };
+struct SirThresholds {
+    std::string error;                         // non-empty: an input was refused; names `who` and the first offending index
+    unsigned long long tb = 0, tg = 0;         // SIR_SCALAR
+    std::vector<unsigned long long> rates;     // [infection thresholds: n or nnz | n recovery thresholds]; empty for SIR_SCALAR
+    std::vector<unsigned long long> start;     // [n thr(pS) | n thr(pR)]; empty without `init`
+};
+// Every range, NaN and row-sum check of the host arrays is here.  restate_col (non-null, with SIR_NODES): the column ids of the
+// CSR; the per-node rates are then staged as the per-edge form's, thr[p] = thr(beta[col[p]]) -- same coins, same counts.
+// init: null, or fp64 [n][3], (pS, pI, pR) per node.
+SirThresholds sir_stage(const char* who, int n, int64_t nnz, const SirRates& r, const int32_t* restate_col, const double* init);

@@ -214,46 +214,53 @@ def _resolved_rates(beta, gamma, graph):
     return float(beta), float(gamma)
 
 
-def _init_launch(graph: DeviceGraph, init: InitialState, b, g, sims, T, rng_seed, sim_offset, ev, cv, counts, edge_scan):
-    """One gnode_sir_mc_philox_init launch into ev / cv / counts (each may be None, not all); b / g as `_resolved_rates`
-    returns them."""
-    lib = _lib.load()
-    if isinstance(b, EdgeRates):
-        (w, gam, gam_host), _alive = _edge_rate_args(b, g, graph)
-        rates = (0.0, None, w, gam, gam_host)
-    elif isinstance(b, np.ndarray):
-        rates = (0.0, _lib.host_ptr(b), None, 0.0, _lib.host_ptr(g))
-    else:
-        rates = (float(b), None, None, float(g), None)
-    dev = next(t for t in (counts, ev, cv) if t is not None).device
-    ws = torch.empty(lib.gnode_sir_init_workspace_bytes(graph.handle, T), dtype=torch.uint8, device=dev)
-    _lib.check(lib.gnode_sir_mc_philox_init(graph.handle, _lib.host_ptr(init.p), *rates, int(sims), int(sim_offset), int(T),
-                                            C.c_uint64(int(rng_seed) & (2**64 - 1)), _lib.ptr(ev), _lib.ptr(cv), _lib.ptr(counts),
-                                            _lib.ptr(ws), ws.numel(), _lib.stream_ptr(), int(bool(edge_scan))))
-
-
 def _init_for(init: InitialState, n: int) -> InitialState:
     if init.n != n:
         raise ValueError(f"InitialState of {init.n} nodes given for a graph of {n}")
     return init
 
 
-def _philox_launch(entry: str, graph: DeviceGraph, seed_set, beta, gamma, sims, T, rng_seed, sim_offset, device, counts, *extra,
-                   ws_entry: str = "gnode_sir_workspace_bytes"):
-    """One launch of a gnode_sir_mc_philox* entry into `counts` (zeros [3, T, n] on `device` when None); returns counts.
-    beta / gamma: numbers, or (gnode_sir_mc_philox_nodes) float64 [n] host arrays; or (gnode_sir_mc_philox_edges) an
-    EdgeRates and a number or array."""
+# (rate form 0 scalar / 1 per node / 2 per edge, per-trajectory output) -> the seed-list C entry, its workspace-size entry and
+# which of the rate arguments (beta, beta_host, w_host, gamma, gamma_host) it takes, in its order
+_SIR_ENTRIES = {
+    (0, False): ("gnode_sir_mc_philox", "gnode_sir_workspace_bytes", (0, 3)),
+    (1, False): ("gnode_sir_mc_philox_nodes", "gnode_sir_nodes_workspace_bytes", (1, 4)),
+    (2, False): ("gnode_sir_mc_philox_edges", "gnode_sir_edges_workspace_bytes", (2, 3, 4)),
+    (0, True): ("gnode_sir_mc_philox_traj", "gnode_sir_traj_workspace_bytes", (0, 3, 1, 4)),
+    (1, True): ("gnode_sir_mc_philox_traj", "gnode_sir_traj_workspace_bytes", (0, 3, 1, 4)),
+    (2, True): ("gnode_sir_mc_philox_traj_edges", "gnode_sir_edges_workspace_bytes", (2, 3, 4)),
+}
+_SIR_INIT_ENTRY = ("gnode_sir_mc_philox_init", "gnode_sir_init_workspace_bytes", (0, 1, 2, 3, 4))
+
+
+def _sir_launch(graph: DeviceGraph, start, b, g, sims, T, rng_seed, sim_offset, ev, cv, counts, edge_scan, entry=None, extra=()):
+    """One Monte-Carlo launch into ev (int16 [2, sims, n]), cv (int32 [sims, T, 3]) and counts (int32 [3, T, n], accumulated);
+    each may be None, not all.  start: a seed list or an `InitialState`; b / g: as `_resolved_rates` returns them.  `entry`
+    names a C entry that takes the scalar seed-list entry's arguments (then `extra` behind them) in its place."""
     lib = _lib.load()
-    seeds = np.ascontiguousarray(list(seed_set), dtype=np.int32)
-    if counts is None:
-        counts = torch.zeros((3, T, graph.n), dtype=torch.int32, device=device)
-    ws = torch.empty(getattr(lib, ws_entry)(graph.handle, T), dtype=torch.uint8, device=counts.device)
-    rate = lambda r: _lib.host_ptr(r) if isinstance(r, np.ndarray) and r.ndim == 1 else float(r)
-    rates, _alive = _edge_rate_args(beta, gamma, graph) if isinstance(beta, EdgeRates) else ((rate(beta), rate(gamma)), None)
-    _lib.check(getattr(lib, entry)(graph.handle, _lib.host_ptr(seeds), int(seeds.shape[0]), *rates,
-                                   int(sims), int(sim_offset), int(T), C.c_uint64(int(rng_seed) & (2**64 - 1)),
-                                   _lib.ptr(counts), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(), *extra))
-    return counts
+    drawn, traj = isinstance(start, InitialState), ev is not None or cv is not None
+    if isinstance(b, EdgeRates):
+        (w, gam, gam_host), _alive = _edge_rate_args(b, g, graph)
+        form, rates = 2, (0.0, None, w, gam, gam_host)
+    elif isinstance(b, np.ndarray):
+        form, rates = 1, (0.0, _lib.host_ptr(b), None, 0.0, _lib.host_ptr(g))
+    else:
+        form, rates = 0, (float(b), None, None, float(g), None)
+    name, ws_name, takes = _SIR_INIT_ENTRY if drawn else _SIR_ENTRIES[(form, traj)]
+    if drawn:
+        start_args = (_lib.host_ptr(start.p),)
+    else:
+        seeds = np.ascontiguousarray(list(start), dtype=np.int32)
+        start_args = (_lib.host_ptr(seeds), int(seeds.shape[0]))
+    scalar_entry = not drawn and form == 0 and not traj             # ... and its _scan / _counted siblings: no edge_scan argument
+    if scalar_entry and edge_scan:
+        name = "gnode_sir_mc_philox_scan"
+    dev = next(t for t in (counts, ev, cv) if t is not None).device
+    ws = torch.empty(getattr(lib, ws_name)(graph.handle, T), dtype=torch.uint8, device=dev)
+    outputs = (_lib.ptr(ev), _lib.ptr(cv)) if drawn or traj else ()
+    _lib.check(getattr(lib, entry or name)(graph.handle, *start_args, *(rates[i] for i in takes), int(sims), int(sim_offset), int(T),
+                                           C.c_uint64(int(rng_seed) & (2**64 - 1)), *outputs, _lib.ptr(counts), _lib.ptr(ws), ws.numel(),
+                                           _lib.stream_ptr(), *(() if scalar_entry else (int(bool(edge_scan)),)), *extra))
 
 
 def sir_counts(graph: DeviceGraph, seed_set, beta, gamma, sims, T, rng_seed, sim_offset=0, device="cuda",
@@ -278,23 +285,11 @@ def sir_counts(graph: DeviceGraph, seed_set, beta, gamma, sims, T, rng_seed, sim
     I on a seed set and S elsewhere gives the seed-list call's rows t >= 1 exactly.  A wrong n raises ValueError."""
     if isinstance(seed_set, InitialState):
         _init_for(seed_set, graph.n)
-        b, g = _resolved_rates(beta, gamma, graph)                  # (ValueError before the library is entered)
-        if counts is None:
-            counts = torch.zeros((3, T, graph.n), dtype=torch.int32, device=device)
-        _init_launch(graph, seed_set, b, g, sims, T, rng_seed, sim_offset, None, None, counts, edge_scan)
-        return counts
-    if isinstance(beta, EdgeRates):
-        _edge_rate_args(beta, gamma, graph)                         # (ValueError before the library is entered)
-        return _philox_launch("gnode_sir_mc_philox_edges", graph, seed_set, beta, gamma, sims, T, rng_seed, sim_offset, device, counts,
-                              int(bool(edge_scan)), ws_entry="gnode_sir_edges_workspace_bytes")
-    b, g = _node_rates("beta", beta, graph.n), _node_rates("gamma", gamma, graph.n)
-    if b is not None or g is not None:
-        b = _node_rates("beta", np.full(graph.n, float(beta)), graph.n) if b is None else b
-        g = _node_rates("gamma", np.full(graph.n, float(gamma)), graph.n) if g is None else g
-        return _philox_launch("gnode_sir_mc_philox_nodes", graph, seed_set, b, g, sims, T, rng_seed, sim_offset, device, counts,
-                              int(bool(edge_scan)), ws_entry="gnode_sir_nodes_workspace_bytes")
-    return _philox_launch("gnode_sir_mc_philox_scan" if edge_scan else "gnode_sir_mc_philox", graph, seed_set, beta, gamma,
-                          sims, T, rng_seed, sim_offset, device, counts)
+    b, g = _resolved_rates(beta, gamma, graph)                      # (ValueError before the library is entered)
+    if counts is None:
+        counts = torch.zeros((3, T, graph.n), dtype=torch.int32, device=device)
+    _sir_launch(graph, seed_set, b, g, sims, T, rng_seed, sim_offset, None, None, counts, edge_scan)
+    return counts
 
 
 class SirTrajectories(NamedTuple):
@@ -302,31 +297,6 @@ class SirTrajectories(NamedTuple):
     t_inf: torch.Tensor | None      # int16 [sims, n]: step at which the node was infected (0: a seed), -1 never within T
     t_rec: torch.Tensor | None      # int16 [sims, n]: step at which it recovered, -1 never within T
     curves: torch.Tensor | None     # int32 [sims, T, 3]: (S_t, I_t, R_t) of each trajectory
-
-
-def _traj_launch(graph: DeviceGraph, seed_set, b, g, sims, T, rng_seed, sim_offset, ev, cv, counts, edge_scan):
-    """One gnode_sir_mc_philox_traj launch into ev (int16 [2, sims, n] or None), cv (int32 [sims, T, 3] or None) and counts
-    (int32 [3, T, n], accumulated, or None).  b / g: two numbers, or two float64 [n] host arrays (`_node_rates`); or an
-    EdgeRates and a number or array (gnode_sir_mc_philox_traj_edges)."""
-    lib = _lib.load()
-    seeds = np.ascontiguousarray(list(seed_set), dtype=np.int32)
-    dev = (ev if ev is not None else cv).device
-    if isinstance(b, EdgeRates):
-        rates, _alive = _edge_rate_args(b, g, graph)
-        ws = torch.empty(lib.gnode_sir_edges_workspace_bytes(graph.handle, T), dtype=torch.uint8, device=dev)
-        _lib.check(lib.gnode_sir_mc_philox_traj_edges(graph.handle, _lib.host_ptr(seeds), int(seeds.shape[0]), *rates,
-                                                      int(sims), int(sim_offset), int(T), C.c_uint64(int(rng_seed) & (2**64 - 1)),
-                                                      _lib.ptr(ev), _lib.ptr(cv), _lib.ptr(counts), _lib.ptr(ws), ws.numel(),
-                                                      _lib.stream_ptr(), int(bool(edge_scan))))
-        return
-    ws = torch.empty(lib.gnode_sir_traj_workspace_bytes(graph.handle, T), dtype=torch.uint8, device=dev)
-    arrays = isinstance(b, np.ndarray)
-    _lib.check(lib.gnode_sir_mc_philox_traj(graph.handle, _lib.host_ptr(seeds), int(seeds.shape[0]),
-                                            0.0 if arrays else float(b), 0.0 if arrays else float(g),
-                                            _lib.host_ptr(b) if arrays else None, _lib.host_ptr(g) if arrays else None,
-                                            int(sims), int(sim_offset), int(T), C.c_uint64(int(rng_seed) & (2**64 - 1)),
-                                            _lib.ptr(ev), _lib.ptr(cv), _lib.ptr(counts), _lib.ptr(ws), ws.numel(),
-                                            _lib.stream_ptr(), int(bool(edge_scan))))
 
 
 def sir_trajectories(graph_or_G, seed_set, beta, gamma, sims, T, rng_seed=None, sim_offset=0, events=True, curves=True,
@@ -361,8 +331,7 @@ def sir_trajectories(graph_or_G, seed_set, beta, gamma, sims, T, rng_seed=None, 
     ev = torch.empty((2, sims, n), dtype=torch.int16, device=dev) if events else None
     cv = torch.empty((sims, T, 3), dtype=torch.int32, device=dev) if curves else None
     if sims > 0:
-        launch = _init_launch if isinstance(seed_set, InitialState) else _traj_launch
-        launch(graph, seed_set, b, g, sims, T, rng_seed, sim_offset, ev, cv, counts, edge_scan)
+        _sir_launch(graph, seed_set, b, g, sims, T, rng_seed, sim_offset, ev, cv, counts, edge_scan)
     return SirTrajectories(ev[0] if events else None, ev[1] if events else None, cv)
 
 
@@ -408,8 +377,8 @@ def sir_counts_counted(graph: DeviceGraph, seed_set, beta, gamma, sims, T, rng_s
     """`sir_counts` through the kernel's profiling instantiation: (counts, stats) with stats = what the launch did --
     Philox blocks computed, infection coins drawn, recovery coins drawn, CSR entries read (bench.py's `sir` roofline)."""
     st = (C.c_uint64 * 4)()
-    counts = _philox_launch("gnode_sir_mc_philox_counted", graph, seed_set, beta, gamma, sims, T, rng_seed, sim_offset, device,
-                            None, st)
+    counts = torch.zeros((3, T, graph.n), dtype=torch.int32, device=device)
+    _sir_launch(graph, seed_set, beta, gamma, sims, T, rng_seed, sim_offset, None, None, counts, False, "gnode_sir_mc_philox_counted", (st,))
     return counts, {"philox_blocks": int(st[0]), "infection_coins": int(st[1]), "recovery_coins": int(st[2]), "csr_entries_read": int(st[3])}
 
 

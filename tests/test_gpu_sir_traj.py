@@ -280,7 +280,7 @@ def test_writes_stay_inside_the_outputs(case, scan, dev):
     import gnode_oracle as O
     import torch
     from gnode.graph import DeviceGraph
-    from gnode.ode_nn import _traj_launch
+    from gnode.ode_nn import _sir_launch
     if case == "odd-n-3-sims":
         n, seeds, sims, T = 301, [4, 300], 3, 7
         rp, ci, _ = O.er_graph(n, 900, seed=301)
@@ -295,7 +295,7 @@ def test_writes_stay_inside_the_outputs(case, scan, dev):
     ebuf = torch.full((ge + ne + 2 * ge,), 0x5A5A, dtype=torch.int16, device=dev)
     cbuf = torch.full((gc + nc + gc,), 0x5A5A5A5A, dtype=torch.int32, device=dev)
     ev, cv = ebuf[ge:ge + ne].view(2, sims, n), cbuf[gc:gc + nc].view(sims, T, 3)
-    _traj_launch(g, seeds, beta, gamma, sims, T, 21, 0, ev, cv, None, scan)
+    _sir_launch(g, seeds, beta, gamma, sims, T, 21, 0, ev, cv, None, scan)
     torch.cuda.synchronize()
     assert bool((ebuf[:ge] == 0x5A5A).all()) and bool((ebuf[ge + ne:] == 0x5A5A).all()), "events: a guard was written"
     assert bool((cbuf[:gc] == 0x5A5A5A5A).all()) and bool((cbuf[gc + nc:] == 0x5A5A5A5A).all()), "curves: a guard was written"
