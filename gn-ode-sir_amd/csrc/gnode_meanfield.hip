@@ -36,6 +36,43 @@ __global__ __launch_bounds__(256) void k_mf_rhs(const int* __restrict__ rowptr, 
     k[u] = -inf; k[n + u] = inf - rec; k[2 * (size_t)n + u] = rec;
 }
 
+// gnode_meanfield_rates_f64: k = f(y) for B samples on one graph, one thread per row r = b * n + v of the [3][B * n] state.
+// Row r gathers from its own sample's I; w_in[p] is the weight of the contact col[p] -> v, beta and gamma are [B][n].  With
+// W = false and one constant beta this is k_mf_rhs's arithmetic, operation for operation (beta * (ai * S)).
+template <bool W, bool BETA>
+__global__ __launch_bounds__(256) void k_mf_rhs_rates(const int* __restrict__ rowptr, const int* __restrict__ col, int n, int rows,
+                                                     const double* __restrict__ beta, const double* __restrict__ w_in,
+                                                     const double* __restrict__ gamma, const double* __restrict__ y,
+                                                     double* __restrict__ k) {
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= rows) return;
+    const int v = r % n;
+    const double* I = y + rows + (r - v);                             // sample b's I: y[rows + b * n + .]
+    double ai = 0.0;
+    for (int e = rowptr[v]; e < rowptr[v + 1]; ++e) ai += W ? w_in[e] * I[col[e]] : I[col[e]];
+    const double inf = BETA ? beta[r] * (ai * y[r]) : ai * y[r], rec = gamma[r] * I[v];
+    k[r] = -inf; k[rows + r] = inf - rec; k[2 * (size_t)rows + r] = rec;
+}
+
+// w_in[p] = w[rev(p)]: the weight of the contact col[p] -> v for position p of row v (w is source = row, target = column).
+// The reverse-position search of k_dmp_setup; a self-loop is its own reverse.
+__global__ __launch_bounds__(256) void k_mf_w_in(const int* __restrict__ rowptr, const int* __restrict__ col, int n,
+                                                const double* __restrict__ w, double* __restrict__ w_in, int* __restrict__ bad) {
+    const int v = blockIdx.x * 256 + threadIdx.x;
+    if (v >= n) return;
+    for (int p = rowptr[v]; p < rowptr[v + 1]; ++p) {
+        const int u = col[p];
+        int lo = rowptr[u], hi = rowptr[u + 1] - 1, found = -1;       // position of v in row u (sorted columns)
+        while (lo <= hi) {
+            const int mid = (lo + hi) >> 1, c = col[mid];
+            if (c == v) { found = mid; break; }
+            if (c < v) lo = mid + 1; else hi = mid - 1;
+        }
+        w_in[p] = found < 0 ? 0.0 : w[found];
+        if (found < 0) atomicExch(bad, 1);
+    }
+}
+
 // err = max_i |h sum_j e_j k_j| / (atol + rtol max(|y_i|, |ynew_i|))   (non-negative doubles order like their bits)
 __global__ __launch_bounds__(256) void k_mf_err(const double* __restrict__ y, const double* __restrict__ ynew,
                                                const double* __restrict__ K, MfCoef ef, double h, double rtol, double atol,
@@ -78,30 +115,47 @@ __global__ __launch_bounds__(256) void k_mf_emit(const double* __restrict__ y, i
     outS[(size_t)t * n + u] = y[u]; outI[(size_t)t * n + u] = y[n + u]; outR[(size_t)t * n + u] = y[2 * (size_t)n + u];
 }
 
-extern "C" size_t gnode_meanfield_workspace_bytes(gnode_graph_t g) {
-    if (!g) return 0;
-    const size_t v = gn_align((size_t)3 * g->info.n * sizeof(double));
-    return 10 * v + gn_align((size_t)g->info.n * sizeof(double)) + 256;      // y, ynew, ytmp, K[7] | seed | err
+// rows = the state's rows: n, or B * n of the rates entry
+static size_t mf_workspace_bytes(size_t rows) {
+    const size_t v = gn_align(3 * rows * sizeof(double));
+    return 10 * v + gn_align(rows * sizeof(double)) + 256;                   // y, ynew, ytmp, K[7] | seed | err, bad
 }
 
-// `who`: the entry's name for the messages.  init: device fp64 [n][3] (gnode_meanfield_init_f64), or null: then the seed list holds
+extern "C" size_t gnode_meanfield_workspace_bytes(gnode_graph_t g) {
+    if (!g) return 0;
+    return mf_workspace_bytes((size_t)g->info.n);
+}
+
+extern "C" size_t gnode_meanfield_rates_workspace_bytes(gnode_graph_t g, int32_t B) {
+    if (!g || B < 1) return 0;
+    return mf_workspace_bytes((size_t)B * g->info.n) + gn_align((size_t)std::max<int64_t>(g->nnz, 1) * sizeof(double));   // ... | w_in
+}
+
+// gnode_meanfield_rates_f64's part of a call: B samples, beta device [B][n] or null = 1, w device [nnz] or null = 1
+struct MfRates { int B; const double* beta; const double* w; };
+
+// `who`: the entry's name for the messages.  init: device fp64 [n][3] (gnode_meanfield_init_f64), or null: then the seed list holds.
+// rates: null for the scalar entries; else init is [B][n][3], gamma [B][n], the scalar beta rests and the state has B * n rows.
 static int meanfield_impl(const char* who, gnode_graph_t g, const int32_t* seeds_host, int32_t n_seeds, const double* init, double beta,
                           const double* gamma, const double* t_out_host, int32_t n_out, double rtol, double atol,
                           double* outI, double* outS,
-                          double* outR, int64_t* steps_host, void* workspace, size_t workspace_bytes, void* stream) {
+                          double* outR, int64_t* steps_host, void* workspace, size_t workspace_bytes, void* stream,
+                          const MfRates* rates = nullptr) {
     GN_CHECK_ARG(g && gamma && outI && outS && outR && workspace && (init || seeds_host || n_seeds == 0), "%s: null pointer", who);
+    GN_CHECK_ARG(!rates || (rates->B >= 1 && (int64_t)rates->B * g->info.n <= INT32_MAX / 3), "%s: need 1 <= B and 3 * B * n < 2^31", who);
     GN_CHECK_ARG(t_out_host && n_out >= 1 && t_out_host[0] == 0.0, "%s: need output times starting at 0", who);
     for (int i = 1; i < n_out; ++i)
         GN_CHECK_ARG(t_out_host[i] >= t_out_host[i - 1], "%s: output times must be ascending", who);
     GN_CHECK_ARG(rtol > 0 && atol > 0, "%s: tolerances must be positive", who);
     for (int i = 0; i < n_seeds; ++i)
         GN_CHECK_ARG(seeds_host[i] >= 0 && seeds_host[i] < g->info.n, "%s: seed %d out of range", who, seeds_host[i]);
-    if (workspace_bytes < gnode_meanfield_workspace_bytes(g)) {
-        gnode_set_error("%s: workspace %zu < %zu", who, workspace_bytes, gnode_meanfield_workspace_bytes(g));
+    const size_t need = rates ? gnode_meanfield_rates_workspace_bytes(g, rates->B) : gnode_meanfield_workspace_bytes(g);
+    if (workspace_bytes < need) {
+        gnode_set_error("%s: workspace %zu < %zu", who, workspace_bytes, need);
         return GNODE_ERR_WORKSPACE;
     }
     hipStream_t st = (hipStream_t)stream;
-    const int n = g->info.n;
+    const int n = (rates ? rates->B : 1) * g->info.n;                 // rows of the state
     const long len = 3L * n;
     const size_t v = gn_align((size_t)len * sizeof(double));
     char* ws = (char*)workspace;
@@ -111,6 +165,20 @@ static int meanfield_impl(const char* who, gnode_graph_t g, const int32_t* seeds
     unsigned long long* err = (unsigned long long*)(ws + 10 * v + gn_align((size_t)n * sizeof(double)));
     // K is indexed K[j * len + i]: lay the 7 stages out back to back in elements (7 * len doubles fit in 7 aligned slots)
     const unsigned ng = (unsigned)((n + 255) / 256), lg = (unsigned)((len + 255) / 256);
+    const double* w_in = nullptr;
+    if (rates && rates->w && g->nnz > 0) {                            // before anything is written to the outputs
+        int* bad = (int*)(err + 1);
+        double* tab = (double*)(ws + mf_workspace_bytes((size_t)n));
+        GN_HIP(hipMemsetAsync(bad, 0, sizeof(int), st));
+        hipLaunchKernelGGL(k_mf_w_in, dim3((unsigned)((g->info.n + 255) / 256)), dim3(256), 0, st, g->rowptr, g->col, g->info.n,
+                           rates->w, tab, bad);
+        GN_LAUNCH_CHECK();
+        int bad_h = 0;
+        GN_HIP(hipMemcpyAsync(&bad_h, bad, sizeof(int), hipMemcpyDeviceToHost, st));
+        GN_HIP(hipStreamSynchronize(st));
+        GN_CHECK_ARG(!bad_h, "%s: the sparsity pattern is not symmetric (a directed contact is a zero weight on the reverse entry)", who);
+        w_in = tab;
+    }
     const double one = 1.0;
     if (init) {
         hipLaunchKernelGGL(k_mf_init_state, dim3(ng), dim3(256), 0, st, init, n, y);
@@ -134,7 +202,13 @@ static int meanfield_impl(const char* who, gnode_graph_t g, const int32_t* seeds
         {35.0 / 384, 0, 500.0 / 1113, 125.0 / 192, -2187.0 / 6784, 11.0 / 84}};
     static const double B4[7] = {5179.0 / 57600, 0, 7571.0 / 16695, 393.0 / 640, -92097.0 / 339200, 187.0 / 2100, 1.0 / 40};
     auto rhs = [&](const double* yy, double* kk) {
-        hipLaunchKernelGGL(k_mf_rhs, dim3(ng), dim3(256), 0, st, g->rowptr, g->col, n, beta, gamma, yy, kk);
+        if (!rates) {
+            hipLaunchKernelGGL(k_mf_rhs, dim3(ng), dim3(256), 0, st, g->rowptr, g->col, n, beta, gamma, yy, kk);
+            return;
+        }
+        auto kern = w_in ? (rates->beta ? k_mf_rhs_rates<true, true> : k_mf_rhs_rates<true, false>)
+                         : (rates->beta ? k_mf_rhs_rates<false, true> : k_mf_rhs_rates<false, false>);
+        hipLaunchKernelGGL(kern, dim3(ng), dim3(256), 0, st, g->rowptr, g->col, g->info.n, n, rates->beta, w_in, gamma, yy, kk);
     };
     rhs(y, K);                                                        // k1 (FSAL: later steps reuse k7)
     double t = 0.0, h = 1e-3;
@@ -195,4 +269,15 @@ extern "C" int gnode_meanfield_init_f64(gnode_graph_t g, const double* init, dou
     GN_CHECK_ARG(init, "gnode_meanfield_init_f64: null pointer");
     return meanfield_impl("gnode_meanfield_init_f64", g, nullptr, 0, init, beta, gamma, t_out_host, n_out, rtol, atol, outI, outS, outR, steps_host, workspace,
                           workspace_bytes, stream);
+}
+
+// B samples on one graph with per-sample, per-node beta and gamma and per-contact weights: see include/gnode.h.
+extern "C" int gnode_meanfield_rates_f64(gnode_graph_t g, int32_t B, const double* init, const double* beta, const double* w,
+                                         const double* gamma, const double* t_out_host, int32_t n_out, double rtol, double atol,
+                                         double* outI, double* outS, double* outR, int64_t* steps_host, void* workspace,
+                                         size_t workspace_bytes, void* stream) {
+    GN_CHECK_ARG(init, "gnode_meanfield_rates_f64: null pointer");
+    const MfRates rates = {B, beta, w};
+    return meanfield_impl("gnode_meanfield_rates_f64", g, nullptr, 0, init, 0.0, gamma, t_out_host, n_out, rtol, atol, outI, outS, outR,
+                          steps_host, workspace, workspace_bytes, stream, &rates);
 }

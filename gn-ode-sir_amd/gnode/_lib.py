@@ -88,6 +88,8 @@ ABI = {
     "gnode_meanfield_workspace_bytes": (_sz, [_vp]),
     "gnode_meanfield_f64": (_int, [_vp, _vp, _i32, _f64, _vp, _vp, _i32, _f64, _f64, _vp, _vp, _vp, _pi64, _vp, _sz, _vp]),
     "gnode_meanfield_init_f64": (_int, [_vp, _vp, _f64, _vp, _vp, _i32, _f64, _f64, _vp, _vp, _vp, _pi64, _vp, _sz, _vp]),
+    "gnode_meanfield_rates_workspace_bytes": (_sz, [_vp, _i32]),
+    "gnode_meanfield_rates_f64": (_int, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _f64, _f64, _vp, _vp, _vp, _pi64, _vp, _sz, _vp]),
     "gnode_l1_loss_workspace_bytes": (_sz, []),
     "gnode_l1_loss_f32": (_int, _L1 + [_vp, _sz, _vp]),
     "gnode_l1_loss_scaled_f32": (_int, _L1 + [C.c_float, _vp, _sz, _vp]),

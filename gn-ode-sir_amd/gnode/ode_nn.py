@@ -4,6 +4,7 @@
     get_sir_t_nodes_torch(x_rk, maxTime, deltaT, count=True)     reference :249-261
     create_graph(n_nodes, graph_label='none')                    reference :394-414
     sir(x, y, A, beta, gamma), runge_kutta_order4(sir, A, ...)   reference :214-233 (mean-field comparison column)
+    meanfield_batch(graph, starts, beta, gamma, ...)             extension: that column for a batch of samples
 """
 from __future__ import annotations
 
@@ -470,21 +471,100 @@ def sir(x, y, A, beta, gamma):
     return np.hstack([dS, -dS - gamma * I, gamma * I])
 
 
+def _is_number(v) -> bool:
+    return (v.ndim == 0) if isinstance(v, torch.Tensor) else (not isinstance(v, EdgeRates) and np.ndim(v) == 0)
+
+
+def _mf_rate_rows(name: str, value, n: int, B: int, batch: bool):
+    """`value` as float64 [B, n] host rows of mean-field RATES: finite and >= 0, not probabilities (the mean-field takes
+    rates, and beta * degree > 1 is ordinary).  A number, per-node rates [n], and with `batch` also [B, n] or B numbers, one
+    per sample (a 1-D value of length n is per node, also where B == n).  Raises ValueError before any library call."""
+    if isinstance(value, torch.Tensor):
+        value = value.detach().cpu().numpy()
+    a = np.asarray(value, dtype=np.float64)
+    if a.ndim == 0 or a.shape == (n,) or (batch and a.shape == (B, n)):
+        rows = np.broadcast_to(a, (B, n))
+    elif batch and a.shape == (B,):
+        rows = np.broadcast_to(a[:, None], (B, n))
+    else:
+        forms = f"({n},), ({B}, {n}) or ({B},)" if batch else f"({n},)"
+        raise ValueError(f"{name}: rates must be a number or have shape {forms}, got {tuple(a.shape)}")
+    bad = np.argwhere(~((rows >= 0.0) & np.isfinite(rows)))         # a NaN fails the comparison
+    if bad.size:
+        b, v = int(bad[0][0]), int(bad[0][1])
+        raise ValueError(f"{name}: the rate of sample {b}, node {v}, {rows[b, v]}, is not a finite rate >= 0")
+    return np.array(rows, dtype=np.float64)                         # a writable, contiguous copy of the broadcast
+
+
+def _mf_times(deltaT, maxTime):
+    grid = np.arange(0, maxTime, deltaT)
+    return np.ascontiguousarray([grid[int(i / deltaT)] for i in range(int(maxTime))], dtype=np.float64)
+
+
+def _mf_checked(n: int, nnz: int, starts, beta, gamma, batch: bool):
+    """The host side of one gnode_meanfield_rates_f64 call, checked before the library is entered: (init [B, n, 3], beta
+    [B, n] or None, w [nnz] or None, gamma [B, n]).  With an `EdgeRates` the contact rate is w alone and beta is None."""
+    B = len(starts)
+    if B < 1:
+        raise ValueError("meanfield: need at least one start")
+    init = np.empty((B, n, 3), dtype=np.float64)
+    for b, start in enumerate(starts):
+        init[b] = (_init_for(start, n) if isinstance(start, InitialState) else InitialState.from_sets(n, list(start))).p
+    if isinstance(beta, EdgeRates):
+        if (beta.n, beta.nnz) != (n, nnz):
+            raise ValueError(f"EdgeRates of a graph with {beta.n} nodes / {beta.nnz} entries given for one with {n} / {nnz}")
+        b_rows, w = None, beta.w
+    else:
+        b_rows, w = _mf_rate_rows("beta", beta, n, B, batch), None
+    return init, b_rows, w, _mf_rate_rows("gamma", gamma, n, B, batch)
+
+
+def _meanfield_rates(graph: DeviceGraph, args, t_out, rtol, atol):
+    """One gnode_meanfield_rates_f64 call for what `_mf_checked` returned: (out, steps), out a float64 device tensor
+    [3 = (I, S, R), len(t_out), B * n] with row b * n + node."""
+    init, b_rows, w, g_rows = args
+    B, n = init.shape[0], init.shape[1]
+    lib, handle = _lib.load(), graph.handle
+    dev = torch.device("cuda", torch.cuda.current_device())
+    up = lambda a: None if a is None or a.size == 0 else torch.from_numpy(a).to(dev)      # noqa: E731  (no edge, no table)
+    y0, bet, wd, gam = up(init), up(b_rows), up(w), up(g_rows)
+    out = torch.empty((3, len(t_out), B * n), dtype=torch.float64, device=dev)
+    ws = torch.empty(lib.gnode_meanfield_rates_workspace_bytes(handle, B), dtype=torch.uint8, device=dev)
+    steps = C.c_int64(0)
+    _lib.check(lib.gnode_meanfield_rates_f64(handle, B, _lib.ptr(y0), _lib.ptr(bet), _lib.ptr(wd), _lib.ptr(gam),
+                                             _lib.host_ptr(t_out), int(len(t_out)), float(rtol), float(atol), _lib.ptr(out[0]),
+                                             _lib.ptr(out[1]), _lib.ptr(out[2]), C.byref(steps), _lib.ptr(ws), ws.numel(),
+                                             _lib.stream_ptr()))
+    return out, int(steps.value)
+
+
 def runge_kutta_order4(sir, A, n_nodes, indices, beta_factor, gamma_factor, deltaT=1, maxTime=70, rtol=1e-10, atol=1e-12):
     """Mean-field baseline, reference ode_nn.py:222-233 (despite its name the reference runs scipy's LSODA):
     returns (I_sampled_t, S_sampled_t, R_sampled_t), float64 [maxTime, n] at the times int(i/deltaT)*deltaT.
     `sir` (the RHS callable) is accepted for signature compatibility; the integration runs in libgnode_hip.so
     (adaptive Dormand-Prince 5(4), sparse A I) -- SURVEY 8f rank 4, not on the `ode_nn` path.
-    `indices` is the seed list, or (extension) an `InitialState`: y(0) = (pS, pI, pR)."""
+    `indices` is the seed list, or (extension) an `InitialState`: y(0) = (pS, pI, pR).
+
+    Heterogeneous rates (extension, `gnode_meanfield_rates_f64`): beta_factor may be per-node rates of length n, indexed by
+    the target node as x[:, 3], or an `EdgeRates` made for A's sorted CSR -- w[p], in row u with col[p] = v, is the rate at
+    which u infects v, the contact rate is then w alone, and A's pattern must be symmetric (a directed contact is a zero on
+    the reverse entry).  gamma_factor may be per-node rates of length n.  These are RATES, finite and >= 0, not
+    probabilities: the mean-field takes rates, and the reference's own configurations have beta * degree > 1.  A wrong
+    length, a NaN, a negative value or an `EdgeRates` of another graph raises ValueError before the library is loaded.  Two
+    numbers take the scalar entries as before.  A's stored values are ignored in every form."""
     Ac = sp.csr_matrix(A)
     Ac.sort_indices()
     n = Ac.shape[0]
     if isinstance(indices, InitialState):
         _init_for(indices, n)
+    if not (_is_number(beta_factor) and _is_number(gamma_factor)):
+        args = _mf_checked(n, int(Ac.nnz), [indices], beta_factor, gamma_factor, batch=False)
+        g = DeviceGraph(Ac.indptr.astype(np.int32), Ac.indices.astype(np.int32))
+        o = _meanfield_rates(g, args, _mf_times(deltaT, maxTime), rtol, atol)[0].cpu().numpy()
+        return o[0], o[1], o[2]
     lib = _lib.load()
     g = DeviceGraph(Ac.indptr.astype(np.int32), Ac.indices.astype(np.int32))
-    grid = np.arange(0, maxTime, deltaT)
-    t_out = np.ascontiguousarray([grid[int(i / deltaT)] for i in range(int(maxTime))], dtype=np.float64)
+    t_out = _mf_times(deltaT, maxTime)
     dev = torch.device("cuda", torch.cuda.current_device())
     gam = torch.full((n,), float(gamma_factor), dtype=torch.float64, device=dev)
     out = torch.empty((3, len(t_out), n), dtype=torch.float64, device=dev)
@@ -500,6 +580,32 @@ def runge_kutta_order4(sir, A, n_nodes, indices, beta_factor, gamma_factor, delt
         _lib.check(lib.gnode_meanfield_f64(g.handle, _lib.host_ptr(seeds), int(seeds.shape[0]), *tail))
     o = out.cpu().numpy()
     return o[0], o[1], o[2]
+
+
+class MeanfieldBatch(NamedTuple):
+    I: torch.Tensor
+    S: torch.Tensor
+    R: torch.Tensor
+
+
+def meanfield_batch(graph: DeviceGraph, starts, beta, gamma, deltaT=1, maxTime=70, rtol=1e-10, atol=1e-12) -> MeanfieldBatch:
+    """The mean-field baseline for B samples on one graph in ONE integration (`gnode_meanfield_rates_f64`): (I, S, R),
+    float64 device tensors [B, maxTime, n] at `runge_kutta_order4`'s times.
+
+    starts: B seed lists and / or `InitialState`s.  beta: a number, per-node rates [n] (indexed by the target node),
+    [B, n], B numbers (one per sample; a 1-D value of length n is per node), or an `EdgeRates` of `graph` (the contact
+    rate is then w alone).  gamma: a number, [n], [B, n] or B numbers.  Rates are finite and >= 0, not probabilities; what
+    is wrong raises ValueError before the library is entered.
+
+    The B samples share the launches, the host round trip per step and the step size: the error norm is the maximum over
+    every sample, so a sample's numbers differ from its solo `runge_kutta_order4` run at the level of rtol / atol, not bit
+    for bit."""
+    starts = list(starts)
+    n, B = int(graph.n), len(starts)
+    out, _ = _meanfield_rates(graph, _mf_checked(n, int(graph.nnz), starts, beta, gamma, batch=True), _mf_times(deltaT, maxTime),
+                              rtol, atol)
+    I, S, R = (out[c].view(-1, B, n).permute(1, 0, 2).contiguous() for c in range(3))
+    return MeanfieldBatch(I, S, R)
 
 
 class CsrGraph:

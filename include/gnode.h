@@ -20,7 +20,7 @@
  *     into a hipGraph on first use and one handle may serve several streams (each
  *     with its own workspace).  Functions that DO synchronise `stream` say so below
  *     (gnode_graph_create, gnode_sir_mc_philox with more than 32 seeds,
- *     gnode_sir_mc_philox_nodes, gnode_sir_mc_philox_edges, gnode_sir_mc_philox_traj_edges, gnode_sir_mc_philox_traj with more than 32 seeds or rate arrays, gnode_sir_mc_philox_init, gnode_sir_mc_coins, gnode_dmp_f32, gnode_dmp_init_f32, gnode_meanfield_f64, gnode_meanfield_init_f64).
+ *     gnode_sir_mc_philox_nodes, gnode_sir_mc_philox_edges, gnode_sir_mc_philox_traj_edges, gnode_sir_mc_philox_traj with more than 32 seeds or rate arrays, gnode_sir_mc_philox_init, gnode_sir_mc_coins, gnode_dmp_f32, gnode_dmp_init_f32, gnode_meanfield_f64, gnode_meanfield_init_f64, gnode_meanfield_rates_f64).
  *   - process-wide state: (1) a per-device "set up once" table (compute-unit count,
  *     dynamic-LDS kernel attributes), written under a lock by the first
  *     gnode_graph_create on a device and read-only afterwards; (2) the opt-in
@@ -499,6 +499,28 @@ int gnode_meanfield_f64(gnode_graph_t g, const int32_t* seeds_host, int32_t n_se
 int gnode_meanfield_init_f64(gnode_graph_t g, const double* init, double beta, const double* gamma,
                              const double* t_out_host, int32_t n_out, double rtol, double atol, double* outI, double* outS,
                              double* outR, int64_t* steps_host, void* workspace, size_t workspace_bytes, void* stream);
+/* The mean-field with per-node and per-contact rates, for B samples on one graph in one integration.  For sample b, node v:
+ *     dS_v = -beta[b][v] S_v sum_{p in row v} w_in[p] I[b][col[p]],  dI_v = -dS_v - gamma[b][v] I_v,  dR_v = gamma[b][v] I_v
+ * where w_in[p] = w[rev(p)] is the weight of the contact col[p] -> v.  `w` comes in the convention of
+ * gnode_sir_mc_philox_edges and gnode_dmp_f32 (w[p], in row u with col[p] = v, is the rate at which u infects v); the entry
+ * transposes it into the workspace once per call.  With `w` given the sparsity pattern must be symmetric (GNODE_ERR_ARG
+ * otherwise); a directed contact is a zero on the reverse entry; a self-loop is its own reverse and counts once.
+ *   init    device fp64 [B][n][3] = (pS, pI, pR) per sample and node
+ *   beta    device fp64 [B][n], indexed by the TARGET node (x[:, 3]'s convention), or NULL = 1
+ *   w       device fp64 [nnz], CSR position order, source = row, target = column, or NULL = 1 (no table is built)
+ *   gamma   device fp64 [B][n]
+ *   outI/outS/outR  device fp64 [n_out][B * n], row r = b * n + node
+ * The same Dormand-Prince 5(4) as gnode_meanfield_f64 over the 3 * B * n state with ONE shared step size: the error norm is
+ * the maximum over every sample, so a sample's numbers inside a batch differ from its solo run at the level of the
+ * tolerances, not bit for bit; *steps_host counts the shared steps.  B = 1, w NULL or all ones and one constant beta return
+ * gnode_meanfield_init_f64's outputs and step count bit for bit.  Host arguments are validated as there, plus B >= 1 and
+ * 3 * B * n < 2^31; device arrays are not.  Synchronises `stream`.  A short workspace is GNODE_ERR_WORKSPACE with nothing
+ * written. */
+size_t gnode_meanfield_rates_workspace_bytes(gnode_graph_t g, int32_t B);
+int gnode_meanfield_rates_f64(gnode_graph_t g, int32_t B, const double* init, const double* beta, const double* w,
+                              const double* gamma, const double* t_out_host, int32_t n_out, double rtol, double atol,
+                              double* outI, double* outS, double* outR, int64_t* steps_host, void* workspace,
+                              size_t workspace_bytes, void* stream);
 
 /* ---- loss ------------------------------------------------------------------
  * The training loss of ode_nn_ngraph_sim.py:230-234 (multi-graph: ode_nn_ngraphs.py:199-203) and its gradient in one
