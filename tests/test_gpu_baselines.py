@@ -40,100 +40,13 @@ import functools
 import numpy as np
 import pytest
 
+from baseline_cases import DMP_CASES, MF_ATOL, RTOL, dmp_model as _dmp_model, er as _er, gammas as _gammas, rel as _rel, weights as _weights
+from sir_cases import dev  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
-RTOL = 1e-5                     # test_gpu_parity.py's fp32 bar
 YARD_MAX = 2.5e-5
-MF_ATOL = 1e-6                  # the project's mean-field bar
 MF_GIVE_UP = 2000000            # gnode_meanfield_f64's step bound
-
-
-@pytest.fixture(scope="module")
-def dev():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from gnode import _lib
-    _lib.load()                       # fails loudly if libgnode_hip.so is missing
-    return torch.device("cuda:0")
-
-
-def _rel(a, b):
-    a = np.asarray(a, np.float64); b = np.asarray(b, np.float64)
-    return np.max(np.abs(a - b)) / (np.max(np.abs(b)) + 1e-30)
-
-
-# ------------------------------------------------------------------ DMP: cases (numpy only) and their two references
-def _weights(nnz, lo, hi, seed):
-    return np.random.default_rng(seed).uniform(lo, hi, size=nnz).astype(np.float32)   # per directed edge: w_uv != w_vu
-
-
-def _gammas(n, seed):
-    return np.random.default_rng(seed).uniform(0.1, 0.5, size=n).astype(np.float32)
-
-
-def _er(n, m, seed):
-    import gnode_oracle as O
-    rp, ci, e = O.er_graph(n, m, seed=seed)
-    return rp, ci, e
-
-
-def _case(rp, ci, w, gam, seeds, T):
-    return dict(rp=rp, ci=ci, w=w, gam=gam, seeds=[int(s) for s in seeds], T=int(T))
-
-
-def _case_hub():
-    import gnode_oracle as O
-    rp, ci, _ = O.chung_lu_graph(3001, 40000, seed=2)
-    return _case(rp, ci, _weights(len(ci), 0.02, 0.3, 5), _gammas(3001, 6), [0, 17, 2500], 10)
-
-
-def _case_isolated():
-    rp, ci, _ = _er(513, 40, 6)
-    deg = np.diff(rp)
-    iso, con = int(np.flatnonzero(deg == 0)[0]), int(np.flatnonzero(deg > 0)[0])
-    return _case(rp, ci, _weights(len(ci), 0.05, 0.5, 7), _gammas(513, 8), [iso, con], 7)
-
-
-def _case_horizon(T):
-    rp, ci, _ = _er(300, 900, 7)
-    return _case(rp, ci, _weights(len(ci), 0.05, 0.4, 9), _gammas(300, 10), [5, 250], T)
-
-
-def _case_nnz0():
-    return _case(np.zeros(6, np.int32), np.zeros(0, np.int32), np.zeros(0, np.float32), _gammas(5, 11), [1, 3], 6)
-
-
-def _case_seeds(seeds):
-    rp, ci, _ = _er(400, 1200, 8)
-    return _case(rp, ci, _weights(len(ci), 0.05, 0.4, 12), _gammas(400, 13), seeds, 8)
-
-
-def _case_w_one():
-    rp, ci, e = _er(34, 78, 3)
-    return _case(rp, ci, np.ones(len(ci), np.float32), _gammas(34, 14), e[0], 3)       # e[0]: two adjacent seeds
-
-
-def _case_w_zero():
-    rp, ci, _ = _er(34, 78, 3)
-    w = _weights(len(ci), 0.05, 0.6, 15)
-    w[::3] = 0.0                                                    # a third of the directed edges never transmit
-    return _case(rp, ci, w, _gammas(34, 16), [0, 20], 12)
-
-
-def _case_gamma_01():
-    rp, ci, _ = _er(34, 78, 3)
-    gam = _gammas(34, 17)
-    gam[0::3] = 0.0                                                 # never recover (seed 0 among them)
-    gam[1::3] = 1.0                                                 # recover within the step (seed 1 among them)
-    return _case(rp, ci, _weights(len(ci), 0.05, 0.6, 18), gam, [0, 1, 20], 12)
-
-
-DMP_CASES = {
-    "hub": _case_hub, "isolated": _case_isolated, "T2": lambda: _case_horizon(2), "T3": lambda: _case_horizon(3),
-    "nnz0": _case_nnz0, "seeds_none": lambda: _case_seeds([]), "seeds_all": lambda: _case_seeds(range(400)),
-    "w_one": _case_w_one, "w_zero": _case_w_zero, "gamma_01": _case_gamma_01,
-}
 
 
 def _oracle(c, dtype):
@@ -150,13 +63,6 @@ def dmp_refs(name):
     for o in (o32, o64):
         o.setflags(write=False)
     return c, o32, o64, _rel(o32, o64)
-
-
-def _dmp_model(c):
-    import scipy.sparse as sp
-    from gnode.dmp import DMP_SIR
-    n = len(c["rp"]) - 1
-    return DMP_SIR(sp.csr_matrix((c["w"], c["ci"], c["rp"]), shape=(n, n)), c["gam"])
 
 
 def _dmp_gpu(c, seeds=None, T=None):

@@ -1,12 +1,14 @@
 """GPU: the DMP and mean-field baselines from an initial-state distribution (gnode_dmp_init_f32, gnode_meanfield_init_f64
 through DMP_SIR.run / runge_kutta_order4 with an InitialState), at the graphs and bars of tests/test_gpu_baselines.py against
-the references of tests/sir_init_model.py, and the Monte-Carlo's marginals against DMP's on a tree, where those are exact."""
+the references of tests/sir_init_model.py on the cases of tests/baseline_cases.py, and the Monte-Carlo's marginals against
+DMP's on a tree, where those are exact."""
 import functools
 
 import numpy as np
 import pytest
 
-from test_gpu_baselines import DMP_CASES, MF_ATOL, RTOL, _dmp_model, _er, _rel
+from baseline_cases import DMP_CASES, MF_ATOL, RTOL, dmp_model as _dmp_model, er as _er, rel as _rel
+from sir_cases import dev, state as _state, tree_case, u32 as _u32  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -14,25 +16,11 @@ CASES = ["hub", "isolated", "T2", "T3", "nnz0", "seeds_none", "w_one", "w_zero",
 INIT_SEED = {name: 401 + i for i, name in enumerate(CASES)}
 
 
-@pytest.fixture(scope="module")
-def dev():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from gnode import _lib
-    _lib.load()                       # fails loudly if libgnode_hip.so is missing
-    return torch.device("cuda:0")
-
-
-def _state(p):
-    from gnode.ode_nn import initial_state
-    return initial_state(p)
-
-
 @functools.lru_cache(maxsize=None)
 def init_refs(name):
     """(case, p, float32 restatement, float64 yardstick, yard), computed once; nothing here touches the GPU."""
-    from sir_init_model import dmp_sir_init, mixed_init
+    from sir_init_model import dmp_sir_init
+    from sir_model import mixed_init
     c = DMP_CASES[name]()
     p, _ = mixed_init(len(c["rp"]) - 1, INIT_SEED[name])
     with np.errstate(all="ignore"):     # w = 1: the float32 recurrence divides 0 by 0 in its last edge pass (test_gpu_baselines.py)
@@ -101,7 +89,6 @@ def test_counts_agree_with_dmp_on_a_tree(dev):
     from gnode.graph import DeviceGraph
     from gnode.ode_nn import edge_rates, sir_counts
     from sir_init_model import dmp_sir_init, sigma_ratio, tree_init
-    from test_gpu_sir_edges import _u32, tree_case
     n, rp, ci, w, gamma = tree_case()
     p, sims, T = tree_init(), 20000, 12
     P = dmp_sir_init(rp, ci, w, gamma, p, T, "float64")
@@ -144,7 +131,8 @@ def test_meanfield_one_hot_state_is_the_seed_list_run(n, m, gseed, dev):
 @pytest.mark.parametrize("n,m,gseed,beta", [(700, 3000, 11, 0.05), (257, 30, 12, 0.4), (2001, 25000, 2, 0.002)], ids=["er700", "ragged-isolated", "hub"])
 def test_meanfield_mixed_state(n, m, gseed, beta, dev):
     import gnode_oracle as O
-    from sir_init_model import meanfield_init, mixed_init
+    from sir_init_model import meanfield_init
+    from sir_model import mixed_init
     rp, ci = O.chung_lu_graph(n, m, seed=gseed)[:2] if n == 2001 else _er(n, m, gseed)[:2]
     p, _ = mixed_init(n, 500 + n)
     got = _meanfield(rp, ci, _state(p), beta, 0.2, 8)

@@ -163,7 +163,7 @@ def test_b1_constant_beta_is_the_seed_entry_bit_for_bit(dev):
 
 
 def test_b1_constant_beta_is_the_init_entry_bit_for_bit(dev):
-    from sir_init_model import mixed_init
+    from sir_model import mixed_init
     rp, ci = _er150()
     n, t_out = 150, np.arange(9.0)
     p, _ = mixed_init(n, 5)

@@ -1,185 +1,78 @@
 """GPU: Monte-Carlo SIR labels with per-edge transmission probabilities (gnode_sir_mc_philox_edges / _traj_edges through
 sir_counts / sir_trajectories / sir_torch with an EdgeRates).  Every comparison but the last is np.array_equal on uint32
 counts: against the scalar call where the weights are one constant, against the per-node call where w[p] = beta[col[p]],
-against the CPU model of tests/sir_edges_model.py (held to the oracle by tests/test_sir_edges_model.py) where they are
-neither.  The last holds the counts to DMP's marginals on a tree, where those are exact: the direction convention."""
+against the CPU model of tests/sir_model.py on the cases of tests/sir_cases.py (held to the oracle by
+tests/test_sir_model.py) where they are neither.  The last holds the counts to DMP's marginals on a tree, where those are
+exact: the direction convention."""
 import numpy as np
 import pytest
 
+from baseline_cases import rel as _rel
+from sir_cases import (EDGE_RATE_SEED, IDS, SHAPES, bfs_depth, case, dev, dmp_ratio, edge_weights, er_of, expected, graph,  # noqa: F401
+                       live_edges, tree_case, u32)
+from sir_model import one_way_path
+
 pytestmark = pytest.mark.gpu
 
-# the shapes of test_gpu_sir_nodes.py
-SHAPES = [
-    ("er-small", 500, 2500, [3, 499], 200, 15),                 # lists in LDS (uint16 ids)
-    ("wiki-vote-size", 7066, 100736, [1, 3533], 96, 20),        # lists in LDS, three workgroups per CU
-    ("hubs", 3000, 40000, [0, 1, 2999], 64, 12),                # rows longer than 512 edges: walked by the whole workgroup
-    ("global-lists", 12000, 60000, [5, 6, 5, 11999], 48, 10),   # lists in the workspace (int32 ids); a duplicated seed
-    ("isolated", 300, 40, [7], 64, 6),                          # mostly isolated nodes: the frontier dies out
-]
-# seeds of the rate draw, one per kind (the liveness checks of the heterogeneous test are on the CPU model's output: a seed
-# that fails them is changed, not the check)
-RATE_SEED = {"er-small": 201, "wiki-vote-size": 202, "hubs": 203, "global-lists": 204, "isolated": 205, "large": 206}
 
-
-@pytest.fixture(scope="module")
-def dev():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from gnode import _lib
-    _lib.load()                       # fails loudly if libgnode_hip.so is missing
-    return torch.device("cuda:0")
-
-
-_GRAPHS: dict = {}
-
-
-def _csr(kind, n, m):
-    import gnode_oracle as O
-    if kind == "hubs":
-        rp, ci, _ = O.chung_lu_graph(n, m, exponent=0.95, seed=3)
-        assert int(np.max(np.diff(rp))) > 512
-    elif kind == "large":
-        rp, ci, _ = O.er_graph(n, m, seed=8)
-    else:
-        rp, ci, _ = O.er_graph(n, m, seed=n)
-    return rp, ci
-
-
-def _graph(kind, n, m):
-    """(rowptr, col, DeviceGraph), built once per module."""
-    if kind not in _GRAPHS:
-        from gnode.graph import DeviceGraph
-        rp, ci = _csr(kind, n, m)
-        _GRAPHS[kind] = (rp, ci, DeviceGraph(rp, ci))
-    return _GRAPHS[kind]
-
-
-def _rates(kind, n, nnz, seeds):
-    """w ~ U(0.05, 0.9) independently per directed entry (so w[u -> v] != w[v -> u]), then at fixed pseudo-random positions
-    20 % of the entries 0 and 5 % of them 1; gamma_u ~ U(0.05, 0.6) with 5 % of the nodes 0 and 5 % 1, as in the per-node
-    tests (the seeds keep their drawn gamma).  Returns (w, gamma)."""
-    rng = np.random.default_rng(RATE_SEED[kind])
-    w, gamma = rng.uniform(0.05, 0.9, nnz), rng.uniform(0.05, 0.6, n)
-    epos = rng.permutation(nnz)
-    w[epos[:nnz // 5]], w[epos[nnz // 5:nnz // 5 + nnz // 20]] = 0.0, 1.0
-    npos = rng.permutation(np.setdiff1d(np.arange(n), seeds))
-    gamma[npos[:n // 20]], gamma[npos[n // 20:2 * (n // 20)]] = 0.0, 1.0
-    return w, gamma
-
-
-_MODEL: dict = {}
-
-
-def _model(key, n, rp, ci, seeds, w, gamma, sims, T, rng_seed, sim_offset=0):
-    """The CPU model's (counts, t_inf, t_rec), computed once per case and shared (never modified)."""
-    if key not in _MODEL:
-        from sir_edges_model import sir_philox_edges
-        out = sir_philox_edges(n, rp, ci, seeds, w, gamma, sims, T, rng_seed, sim_offset, return_events=True)
-        for a in out:
-            a.setflags(write=False)
-        _MODEL[key] = out
-    return _MODEL[key]
-
-
-def _u32(t):
-    return t.cpu().numpy().astype(np.uint32)
-
-
-def _er_of(g, w):
-    from gnode.ode_nn import edge_rates
-    return edge_rates(g, w)
-
-
-@pytest.mark.parametrize("kind,n,m,seeds,sims,T", SHAPES, ids=[s[0] for s in SHAPES])
+@pytest.mark.parametrize("kind,n,m,seeds,sims,T", SHAPES, ids=IDS)
 def test_constant_weights_equal_scalar_call(kind, n, m, seeds, sims, T, dev):
     """One constant on every entry returns the scalar call's counts, bit for bit: frontier walk and edge scan, scalar and
     per-node gamma, sim_offset != 0."""
     from gnode.ode_nn import sir_counts
-    rp, ci, g = _graph(kind, n, m)
+    rp, ci, g = graph(kind, n, m)
     for beta, gamma, rs in ((0.45, 0.15, 11), (0.05, 0.6, 12)):
-        want = _u32(sir_counts(g, seeds, beta, gamma, sims, T, rng_seed=rs, sim_offset=5))
+        want = u32(sir_counts(g, seeds, beta, gamma, sims, T, rng_seed=rs, sim_offset=5))
         assert want[1, 1:].any()
-        er = _er_of(g, np.full(len(ci), beta))
+        er = er_of(g, np.full(len(ci), beta))
         for scan in (False, True):
             for gm in (gamma, np.full(n, gamma)):
-                got = _u32(sir_counts(g, seeds, er, gm, sims, T, rng_seed=rs, sim_offset=5, edge_scan=scan))
+                got = u32(sir_counts(g, seeds, er, gm, sims, T, rng_seed=rs, sim_offset=5, edge_scan=scan))
                 assert np.array_equal(got, want), f"{kind}: per-edge call with a constant != scalar call (beta={beta}, scan={scan})"
 
 
-@pytest.mark.parametrize("kind,n,m,seeds,sims,T", SHAPES, ids=[s[0] for s in SHAPES])
+@pytest.mark.parametrize("kind,n,m,seeds,sims,T", SHAPES, ids=IDS)
 def test_target_weights_equal_per_node_call(kind, n, m, seeds, sims, T, dev):
     """w[p] = beta[col[p]] with per-node gamma returns the per-node call's counts."""
     from gnode.ode_nn import sir_counts
-    rp, ci, g = _graph(kind, n, m)
-    rng = np.random.default_rng(RATE_SEED[kind] + 50)
+    rp, ci, g = graph(kind, n, m)
+    rng = np.random.default_rng(EDGE_RATE_SEED[kind] + 50)
     beta, gamma = rng.uniform(0.05, 0.6, n), rng.uniform(0.05, 0.6, n)
     beta[rng.permutation(n)[:n // 10]] = 0.0
-    want = _u32(sir_counts(g, seeds, beta, gamma, sims, T, rng_seed=13, sim_offset=2))
+    want = u32(sir_counts(g, seeds, beta, gamma, sims, T, rng_seed=13, sim_offset=2))
     assert want[1, 1:].any()
-    er = _er_of(g, beta[ci])
+    er = er_of(g, beta[ci])
     for scan in (False, True):
-        got = _u32(sir_counts(g, seeds, er, gamma, sims, T, rng_seed=13, sim_offset=2, edge_scan=scan))
+        got = u32(sir_counts(g, seeds, er, gamma, sims, T, rng_seed=13, sim_offset=2, edge_scan=scan))
         assert np.array_equal(got, want), f"{kind}: w = beta[col] != per-node call (scan={scan})"
 
 
-def _hetero_seeds(kind, rp, seeds):
-    """The seed set of the heterogeneous case.  `isolated` (40 edges on 300 nodes: components of two or three nodes) cannot
-    carry an epidemic to a quarter of its connected nodes from one seed, whatever the coins: it is seeded in every third
-    connected node as well, as in the per-node tests."""
-    if kind != "isolated":
-        return seeds
-    return seeds + np.flatnonzero(np.diff(rp) > 0)[::3].tolist()
-
-
-def _assert_live(kind, n, rp, ci, w, sims, T, model):
-    """On the model's own output: (1) at least a quarter of the (connected node, trajectory) pairs left S; (2) a w = 1
-    entry fired; (3) some w = 0 entry had an infected source next to a susceptible target in a pre-step state."""
-    cnt, t_inf, t_rec = model
-    connected = np.diff(rp) > 0
-    left = float((t_inf[:, connected] >= 0).sum()) / (sims * int(connected.sum()))
-    print(f"{kind}: {left:.3f} of the (connected node, trajectory) pairs left S")
-    assert left >= 0.25
-    src = np.repeat(np.arange(n), np.diff(rp))
-    one, zero = np.flatnonzero(w == 1.0), np.flatnonzero(w == 0.0)
-    tu, tv, ru = t_inf[:, src[one]].astype(np.int32), t_inf[:, ci[one]].astype(np.int32), t_rec[:, src[one]].astype(np.int32)
-    # u in I and v in S before step t = t_inf[v]: the entry's coin was drawn at t, and a w = 1 coin fires
-    fired = (tu >= 0) & (tv > tu) & ((ru < 0) | (ru >= tv))
-    assert fired.any(), f"{kind}: no w = 1 entry fired"
-    tu, tv = t_inf[:, src[zero]].astype(np.int32), t_inf[:, ci[zero]].astype(np.int32)
-    blocked = (tu >= 0) & (tu + 1 <= T - 1) & ((tv < 0) | (tv > tu))
-    assert blocked.any(), f"{kind}: no w = 0 entry was ever tried"
-
-
-@pytest.mark.parametrize("kind,n,m,seeds,sims,T", SHAPES, ids=[s[0] for s in SHAPES])
+@pytest.mark.parametrize("kind,n,m,seeds,sims,T", SHAPES, ids=IDS)
 def test_heterogeneous_weights_equal_cpu_model(kind, n, m, seeds, sims, T, dev):
     """Frontier walk and edge scan with a different, asymmetric weight on every directed entry, closed (w = 0) and certain
     (w = 1) entries among them, per-node gamma, against the CPU model.  The model's output is first checked for a live
     epidemic, so that two dead ones cannot pass for agreement."""
     from gnode.ode_nn import sir_counts
-    rp, ci, g = _graph(kind, n, m)
-    seeds = _hetero_seeds(kind, rp, seeds)
-    w, gamma = _rates(kind, n, len(ci), seeds)
-    model = _model(kind, n, rp, ci, seeds, w, gamma, sims, T, 21)
-    _assert_live(kind, n, rp, ci, w, sims, T, model)
-    er = _er_of(g, w)
-    a = _u32(sir_counts(g, seeds, er, gamma, sims, T, rng_seed=21))
-    assert np.array_equal(a, model[0]), f"{kind}: frontier walk != CPU model"
-    b = _u32(sir_counts(g, seeds, er, gamma, sims, T, rng_seed=21, edge_scan=True))
-    assert np.array_equal(b, model[0]), f"{kind}: edge scan != CPU model"
+    g = graph(kind, n, m)[2]
+    c, model = case(f"edges/{kind}"), expected(f"edges/{kind}")
+    seeds, w, gamma = c.start, c.w, c.gamma
+    live_edges(c, model)
+    er = er_of(g, w)
+    a = u32(sir_counts(g, seeds, er, gamma, sims, T, rng_seed=21))
+    assert np.array_equal(a, model.counts), f"{kind}: frontier walk != CPU model"
+    b = u32(sir_counts(g, seeds, er, gamma, sims, T, rng_seed=21, edge_scan=True))
+    assert np.array_equal(b, model.counts), f"{kind}: edge scan != CPU model"
 
 
 def test_large_state_paths(dev):
     """n = 100 000: the scan kernel keeps the trajectory state in memory, the frontier walk its lists (int32 ids)."""
     from gnode.ode_nn import sir_counts
-    n, seeds = 100_000, [5, 77, 4242]
-    rp, ci, g = _graph("large", n, 300_000)
-    w, gamma = _rates("large", n, len(ci), seeds)
-    want = _model("large", n, rp, ci, seeds, w, gamma, 24, 8, 99)[0]
+    c, want = case("edges/large"), expected("edges/large").counts
+    g, seeds, w, gamma = graph("large", c.n, c.m)[2], c.start, c.w, c.gamma
     assert (want[0, -1] < 24).sum() > 1000
-    er = _er_of(g, w)
-    assert np.array_equal(_u32(sir_counts(g, seeds, er, gamma, 24, 8, rng_seed=99)), want)
-    assert np.array_equal(_u32(sir_counts(g, seeds, er, gamma, 24, 8, rng_seed=99, edge_scan=True)), want)
+    er = er_of(g, w)
+    assert np.array_equal(u32(sir_counts(g, seeds, er, gamma, 24, 8, rng_seed=99)), want)
+    assert np.array_equal(u32(sir_counts(g, seeds, er, gamma, 24, 8, rng_seed=99, edge_scan=True)), want)
 
 
 def test_one_way_path(dev):
@@ -188,7 +81,6 @@ def test_one_way_path(dev):
     by the target node, is used."""
     from gnode.graph import DeviceGraph
     from gnode.ode_nn import sir_trajectories
-    from sir_edges_model import one_way_path
     k, m, sims = 40, 17, 33
     n, rp, ci, w = one_way_path(k)
     g = DeviceGraph(rp, ci)
@@ -196,7 +88,7 @@ def test_one_way_path(dev):
     want = np.full(n, -1)
     want[m:] = np.arange(n - m)
     for scan in (False, True):
-        tr = sir_trajectories(g, [m], _er_of(g, w), 0.0, sims, T, rng_seed=9, edge_scan=scan)
+        tr = sir_trajectories(g, [m], er_of(g, w), 0.0, sims, T, rng_seed=9, edge_scan=scan)
         assert np.array_equal(tr.t_inf.cpu().numpy(), np.broadcast_to(want, (sims, n))), f"scan={scan}"
         assert bool((tr.t_rec == -1).all())
 
@@ -204,15 +96,12 @@ def test_one_way_path(dev):
 def test_more_than_32_seeds(dev):
     """40 seeds: the list is copied from the host instead of travelling as a kernel argument."""
     from gnode.ode_nn import sir_counts
-    n = 500
-    rp, ci, g = _graph("er-small", n, 2500)
-    seeds = list(range(3, 3 + 12 * 40, 12))
-    assert len(seeds) == 40 and max(seeds) < n
-    w, gamma = _rates("er-small", n, len(ci), seeds)
-    want = _model("seeds40", n, rp, ci, seeds, w, gamma, 50, 8, 31)[0]
-    er = _er_of(g, w)
-    assert np.array_equal(_u32(sir_counts(g, seeds, er, gamma, 50, 8, rng_seed=31)), want)
-    assert np.array_equal(_u32(sir_counts(g, seeds, er, gamma, 50, 8, rng_seed=31, edge_scan=True)), want)
+    c, want = case("edges/seeds40"), expected("edges/seeds40").counts
+    g, seeds, w, gamma = graph("er-small", c.n, c.m)[2], c.start, c.w, c.gamma
+    assert len(seeds) == 40 and max(seeds) < c.n
+    er = er_of(g, w)
+    assert np.array_equal(u32(sir_counts(g, seeds, er, gamma, 50, 8, rng_seed=31)), want)
+    assert np.array_equal(u32(sir_counts(g, seeds, er, gamma, 50, 8, rng_seed=31, edge_scan=True)), want)
 
 
 def test_sharded_equals_whole(dev):
@@ -220,70 +109,53 @@ def test_sharded_equals_whole(dev):
     import torch
     from gnode.ode_nn import sir_counts
     n, seeds = 500, [3, 499]
-    rp, ci, g = _graph("er-small", n, 2500)
-    w, gamma = _rates("er-small", n, len(ci), seeds)
-    er = _er_of(g, w)
+    rp, ci, g = graph("er-small", n, 2500)
+    w, gamma = edge_weights("er-small", n, len(ci), seeds)
+    er = er_of(g, w)
     whole = sir_counts(g, seeds, er, gamma, 1000, 12, rng_seed=5)
     acc = sir_counts(g, seeds, er, gamma, 600, 12, rng_seed=5, sim_offset=0)
     acc = sir_counts(g, seeds, er, gamma, 400, 12, rng_seed=5, sim_offset=600, counts=acc)
     assert torch.equal(whole, acc)
     assert whole[2, -1].sum().item() > 0
     # the second shard alone is the model's trajectories 600..639
-    part = _u32(sir_counts(g, seeds, er, gamma, 40, 12, rng_seed=5, sim_offset=600))
-    assert np.array_equal(part, _model("shard", n, rp, ci, seeds, w, gamma, 40, 12, 5, 600)[0])
-
-
-def _bfs_depth(rp, ci, root, n):
-    depth = np.full(n, -1)
-    depth[root] = 0
-    frontier = [root]
-    while frontier:
-        nxt = []
-        for u in frontier:
-            for v in ci[rp[u]:rp[u + 1]]:
-                if depth[v] < 0:
-                    depth[v] = depth[u] + 1
-                    nxt.append(int(v))
-        frontier = nxt
-    return depth
+    part = u32(sir_counts(g, seeds, er, gamma, 40, 12, rng_seed=5, sim_offset=600))
+    assert np.array_equal(part, expected("edges/shard").counts)
 
 
 def test_extreme_weights(dev):
     """w = 0 everywhere leaves only the seed infected; w = 1 everywhere with gamma = 0 infects exactly the BFS ball of
     radius t (the threshold 2^32 of p = 1 does not fit 32 bits)."""
-    import gnode_oracle as O
-    from gnode.graph import DeviceGraph
     from gnode.ode_nn import sir_counts
     n, seed, sims = 300, 11, 32
-    rp, ci, _ = O.er_graph(n, 600, seed=300)
-    g = DeviceGraph(rp, ci)
-    depth = _bfs_depth(rp, ci, seed, n)
+    rp, ci, g = graph("er300", n, 600)
+    depth = bfs_depth(rp, ci, seed, n)
     comp, ecc = depth >= 0, int(depth.max())
     assert comp.sum() > 200 and ecc >= 4
     T = ecc + 2
-    ones, zeros = _er_of(g, np.ones(len(ci))), _er_of(g, np.zeros(len(ci)))
+    ones, zeros = er_of(g, np.ones(len(ci))), er_of(g, np.zeros(len(ci)))
     for scan in (False, True):
-        got = _u32(sir_counts(g, [seed], ones, 0.0, sims, T, rng_seed=3, edge_scan=scan))
+        got = u32(sir_counts(g, [seed], ones, 0.0, sims, T, rng_seed=3, edge_scan=scan))
         for t in range(1, T):
             assert np.array_equal(got[1, t], np.where(comp & (depth <= t), sims, 0)), t
         assert np.all(got[1, ecc][comp] == sims) and not got[2].any()
-        got0 = _u32(sir_counts(g, [seed], zeros, np.full(n, 0.3), sims, T, rng_seed=3, edge_scan=scan))
+        got0 = u32(sir_counts(g, [seed], zeros, np.full(n, 0.3), sims, T, rng_seed=3, edge_scan=scan))
         others = np.arange(n) != seed
         assert np.all(got0[0, 1:][:, others] == sims) and np.all(got0[0, 1:, seed] == 0)
         assert got0[2, -1, seed] > 0
 
 
-@pytest.mark.parametrize("kind,n,m,seeds,sims,T", [SHAPES[0], SHAPES[2], SHAPES[3]], ids=[SHAPES[i][0] for i in (0, 2, 3)])
+@pytest.mark.parametrize("kind,n,m,seeds,sims,T", [SHAPES[0], SHAPES[2], SHAPES[3]], ids=[IDS[i] for i in (0, 2, 3)])
 def test_trajectories_consistent_with_counts(kind, n, m, seeds, sims, T, dev):
     """sir_counts_from_events of the per-edge trajectory call equals the per-edge counts call, the events equal the CPU
     model's, the curves are the events' sums and `counts=` accumulates what sir_counts adds."""
     import torch
     from gnode.ode_nn import sir_counts, sir_counts_from_events, sir_curves_from_events, sir_trajectories
-    rp, ci, g = _graph(kind, n, m)
-    w, gamma = _rates(kind, n, len(ci), seeds)
-    er = _er_of(g, w)
+    g = graph(kind, n, m)[2]
+    c, model = case(f"edges/{kind}"), expected(f"edges/{kind}")       # (these kinds' heterogeneous case starts from the shape's seeds)
+    assert c.start == seeds
+    w, gamma, t_inf, t_rec = c.w, c.gamma, model.t_inf, model.t_rec
+    er = er_of(g, w)
     want = sir_counts(g, seeds, er, gamma, sims, T, rng_seed=21)
-    _, t_inf, t_rec = _model(kind, n, rp, ci, seeds, w, gamma, sims, T, 21)
     for scan in (False, True):
         acc = torch.zeros_like(want)
         tr = sir_trajectories(g, seeds, er, gamma, sims, T, rng_seed=21, counts=acc, edge_scan=scan)
@@ -296,19 +168,13 @@ def test_trajectories_consistent_with_counts(kind, n, m, seeds, sims, T, dev):
 
 def test_sir_torch_surface(dev):
     """An EdgeRates made from a networkx graph and a scipy matrix, through the reference-shaped surface."""
-    import networkx as nx
     import scipy.sparse as sp
-    from gnode.ode_nn import _csr_from_edges, _edge_arrays, edge_rates, sir_torch
-    G = nx.karate_club_graph()
-    n, sims, T, seeds = 34, 300, 12, [0, 33]
-    rp, ci = _csr_from_edges(n, _edge_arrays(G))
-    rng = np.random.default_rng(34)
-    w, gamma = rng.uniform(0.05, 0.9, len(ci)), rng.uniform(0.05, 0.6, n)
-    w[rng.permutation(len(ci))[:30]] = 0.0
+    from gnode.ode_nn import edge_rates, sir_torch
+    c = case("edges/karate")
+    G, n, rp, ci, sims, T, seeds, w, gamma, keep = c.G, c.n, c.rp, c.ci, c.sims, c.T, c.start, c.w, c.gamma, c.keep
     src = np.repeat(np.arange(n), np.diff(rp))
-    keep = rng.permutation(np.flatnonzero(w != 0.0))                 # the zeros are absent from the matrix, the rest shuffled
-    M = sp.coo_matrix((w[keep], (src[keep], ci[keep])), shape=(n, n))
-    want = _model("karate", n, rp, ci, seeds, w, gamma, sims, T, 77)[0].astype(np.float64)
+    M = sp.coo_matrix((w[keep], (src[keep], ci[keep])), shape=(n, n))   # the zeros are absent from the matrix, the rest shuffled
+    want = expected("edges/karate").counts.astype(np.float64)
     assert want[2, -1].sum() > 0
     S, I, R = sir_torch(G, seeds, edge_rates(G, M), gamma, sims, T, rng_seed=77)
     assert S.shape == (1, T, n) and S.dtype == np.float64
@@ -324,48 +190,17 @@ def test_other_forms_untouched_after_per_edge_calls(dev):
     import oracle_c as OC
     from gnode.ode_nn import sir_counts
     n, seeds = 500, [3, 499]
-    rp, ci, g = _graph("er-small", n, 2500)
-    w, gamma = _rates("er-small", n, len(ci), seeds)
+    rp, ci, g = graph("er-small", n, 2500)
+    w, gamma = edge_weights("er-small", n, len(ci), seeds)
     beta = np.random.default_rng(1).uniform(0.05, 0.6, n)
-    before = {scan: _u32(sir_counts(g, seeds, beta, gamma, 64, 10, rng_seed=9, edge_scan=scan)) for scan in (False, True)}
-    er = _er_of(g, w)
+    before = {scan: u32(sir_counts(g, seeds, beta, gamma, 64, 10, rng_seed=9, edge_scan=scan)) for scan in (False, True)}
+    er = er_of(g, w)
     sir_counts(g, seeds, er, gamma, 64, 10, rng_seed=9)
     sir_counts(g, seeds, er, 0.2, 64, 10, rng_seed=9, edge_scan=True)
     for scan in (False, True):
-        got = _u32(sir_counts(g, seeds, 0.3, 0.2, 64, 10, rng_seed=9, edge_scan=scan))
+        got = u32(sir_counts(g, seeds, 0.3, 0.2, 64, 10, rng_seed=9, edge_scan=scan))
         assert np.array_equal(got, OC.sir_philox(n, rp, ci, seeds, 0.3, 0.2, 64, 10, rng_seed=9))
-        assert np.array_equal(_u32(sir_counts(g, seeds, beta, gamma, 64, 10, rng_seed=9, edge_scan=scan)), before[scan])
-
-
-def _rel(a, b):
-    a = np.asarray(a, np.float64); b = np.asarray(b, np.float64)
-    return np.max(np.abs(a - b)) / (np.max(np.abs(b)) + 1e-30)
-
-
-def tree_case():
-    """The DMP comparison's inputs (numpy only): a random recursive tree of 120 nodes, asymmetric weights with closed and
-    certain entries, per-node gamma."""
-    import gnode_oracle as O
-    n = 120
-    rng = np.random.default_rng(5)
-    edges = [(int(rng.integers(0, i)), i) for i in range(1, n)]
-    rp, ci = O.csr_from_edges(n, edges)
-    nnz = len(ci)
-    assert nnz == 2 * (n - 1)
-    rng = np.random.default_rng(7)
-    w = rng.uniform(0.3, 0.95, nnz)
-    pos = rng.permutation(nnz)
-    w[pos[:nnz // 10]], w[pos[nnz // 10:nnz // 10 + nnz // 20]] = 0.0, 1.0
-    gamma = rng.uniform(0.05, 0.3, n)
-    return n, rp, ci, w, gamma
-
-
-def dmp_ratio(counts, sims, P):
-    """max over the cells of rows t >= 1 of |count / sims - P| / (sqrt(P (1 - P) / sims) + 1 / sims); counts uint32
-    [3, T, n], P float64 [T, n, 3]."""
-    f = counts[:, 1:].astype(np.float64).transpose(1, 2, 0) / sims
-    p = np.clip(P[1:], 0.0, 1.0)
-    return float(np.max(np.abs(f - P[1:]) / (np.sqrt(p * (1.0 - p) / sims) + 1.0 / sims)))
+        assert np.array_equal(u32(sir_counts(g, seeds, beta, gamma, 64, 10, rng_seed=9, edge_scan=scan)), before[scan])
 
 
 def test_counts_agree_with_dmp_on_a_tree(dev):
@@ -384,7 +219,7 @@ def test_counts_agree_with_dmp_on_a_tree(dev):
     P = O.dmp_sir(rp, ci, w, gamma, [0], T, dtype="float64")
     g = DeviceGraph(rp, ci)
     M = sp.csr_matrix((w, ci, rp), shape=(n, n))
-    counts = _u32(sir_counts(g, [0], edge_rates(g, M), gamma, sims, T, rng_seed=1234))
+    counts = u32(sir_counts(g, [0], edge_rates(g, M), gamma, sims, T, rng_seed=1234))
     left = 1.0 - counts[0, -1].sum() / (sims * n)
     ratio = dmp_ratio(counts, sims, P)
     print(f"tree: {left:.3f} of the (node, trajectory) pairs left S, largest |f - P| / bound unit = {ratio:.2f}")
@@ -409,7 +244,7 @@ def test_library_validates_weights_and_takes_an_empty_graph(dev):
     from gnode.graph import DeviceGraph
     lib = _lib.load()
     n = 500
-    rp, ci, g = _graph("er-small", n, 2500)
+    rp, ci, g = graph("er-small", n, 2500)
     T, seeds = 6, np.array([3], np.int32)
     counts = torch.zeros((3, T, n), dtype=torch.int32, device=dev)
     ws = torch.empty(lib.gnode_sir_edges_workspace_bytes(g.handle, T), dtype=torch.uint8, device=dev)
@@ -437,5 +272,5 @@ def test_library_validates_weights_and_takes_an_empty_graph(dev):
     g0 = DeviceGraph(np.zeros(6, np.int32), np.zeros(0, np.int32))
     status, c0 = call(g0, None, None, ws.numel(), 5)
     assert status == 0, lib.gnode_last_error().decode()
-    c0 = _u32(c0)
+    c0 = u32(c0)
     assert np.all(c0[0, 1:, [0, 1, 2, 4]] == 8) and np.all(c0[0, 1:, 3] == 0) and np.all(c0[1, 1:, 3] + c0[2, 1:, 3] == 8)

@@ -1,91 +1,23 @@
 """GPU: Monte-Carlo SIR labels from an initial-state distribution (gnode_sir_mc_philox_init through sir_counts /
 sir_trajectories / sir_torch with an InitialState).  Every count comparison is np.array_equal on uint32 and runs for the
 frontier walk and for edge_scan=True: against the seed-list calls where the state is one-hot, against the CPU model of
-tests/sir_init_model.py (held to the oracle by tests/test_sir_init_model.py) where it is not."""
+tests/sir_model.py on the cases of tests/sir_cases.py (held to the oracle by tests/test_sir_model.py) where it is not."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
-from test_gpu_sir_edges import _csr, _rates, _u32
+from sir_cases import (IDS, INIT_SEED, INIT_SHAPES as SHAPES, case, dev, edge_weights, er_of, expected, graph, live_init, mixed_start,  # noqa: F401
+                       state, u32)
+from sir_model import one_way_path
 
 pytestmark = pytest.mark.gpu
 
-# the shapes of test_gpu_sir_edges.py, n ragged where the generator allows it: the last Philox block of node coins is partial
-SHAPES = [
-    ("er-small", 503, 2500, [3, 499], 200, 15),                 # lists in LDS (uint16 ids)
-    ("wiki-vote-size", 7066, 100736, [1, 3533], 96, 20),        # lists in LDS, three workgroups per CU
-    ("hubs", 3000, 40000, [0, 1, 2999], 64, 12),                # rows longer than 512 edges: walked by the whole workgroup
-    ("global-lists", 12001, 60000, [5, 6, 5, 11999], 48, 10),   # lists in the workspace (int32 ids); a duplicated seed
-    ("isolated", 300, 40, [7], 64, 6),                          # mostly isolated nodes: the frontier dies out
-]
-IDS = [s[0] for s in SHAPES]
-# seeds of the initial-state draw, one per kind (the liveness check is on the CPU model's output: a seed that fails it is
-# changed, not the check)
-INIT_SEED = {"er-small": 301, "wiki-vote-size": 302, "hubs": 303, "global-lists": 304, "isolated": 305, "large": 306}
 
-
-@pytest.fixture(scope="module")
-def dev():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from gnode import _lib
-    _lib.load()                       # fails loudly if libgnode_hip.so is missing
-    return torch.device("cuda:0")
-
-
-_GRAPHS: dict = {}
-_MODEL: dict = {}
-
-
-def _graph(kind, n, m):
-    """(rowptr, col, DeviceGraph), built once per module."""
-    if kind not in _GRAPHS:
-        from gnode.graph import DeviceGraph
-        rp, ci = _csr(kind, n, m)
-        if kind == "hubs":
-            assert int(np.max(np.diff(rp))) > 512
-        _GRAPHS[kind] = (rp, ci, DeviceGraph(rp, ci))
-    return _GRAPHS[kind]
-
-
-def _mixed(kind, n, rp):
-    """55 % S, 5 % I, 10 % R and 30 % Dirichlet(4, 1, 1) rows under the kind's seed.  `isolated` (40 edges on 300 nodes:
-    components of two or three nodes) cannot lose a quarter of its susceptible connected nodes from that, whatever the
-    coins: every third connected node starts infected as well, as in the per-edge tests."""
-    from sir_init_model import mixed_init
-    p, _ = mixed_init(n, INIT_SEED[kind])
-    if kind == "isolated":
-        p[np.flatnonzero(np.diff(rp) > 0)[::3]] = (0.0, 1.0, 0.0)
-    return p
-
-
-def _model(key, n, rp, ci, p, w, gamma, sims, T, rng_seed, sim_offset=0):
-    """The CPU model's (counts, t_inf, t_rec), computed once per case and shared (never modified)."""
-    if key not in _MODEL:
-        from sir_init_model import sir_philox_init
-        out = sir_philox_init(n, rp, ci, p, w, gamma, sims, T, rng_seed, sim_offset, return_events=True)
-        for a in out:
-            a.setflags(write=False)
-        _MODEL[key] = out
-    return _MODEL[key]
-
-
-def _state(p):
-    from gnode.ode_nn import initial_state
-    return initial_state(p)
-
-
-def _er_of(g, w):
-    from gnode.ode_nn import edge_rates
-    return edge_rates(g, w)
-
-
-def _mixed_case(kind, n, m, seeds):
-    rp, ci, g = _graph(kind, n, m)
-    w, gamma = _rates(kind, n, len(ci), seeds)
-    return rp, ci, g, _mixed(kind, n, rp), w, gamma
+def _mixed_case(kind):
+    """(rowptr, col, DeviceGraph, p, w, gamma) of the kind's mixed case: the inputs of `expected("init/<kind>")`."""
+    c = case(f"init/{kind}")
+    return c.rp, c.ci, graph(kind, c.n, c.m)[2], c.start, c.w, c.gamma
 
 
 @pytest.mark.parametrize("kind,n,m,seeds,sims,T", SHAPES, ids=IDS)
@@ -93,26 +25,17 @@ def test_one_hot_state_equals_seed_list_call(kind, n, m, seeds, sims, T, dev):
     """One-hot I on the seed set, S elsewhere: the seed-list call's counts on rows t >= 1 and `sims` times its row 0, for
     the scalar, per-node and per-edge rate forms, sim_offset != 0."""
     from gnode.ode_nn import InitialState, sir_counts
-    rp, ci, g = _graph(kind, n, m)
+    rp, ci, g = graph(kind, n, m)
     st = InitialState.from_sets(n, seeds)
-    w, gamma = _rates(kind, n, len(ci), seeds)
+    w, gamma = edge_weights(kind, n, len(ci), seeds)
     beta = np.random.default_rng(INIT_SEED[kind] + 50).uniform(0.05, 0.6, n)
-    for name, b, gm in (("scalar", 0.45, 0.15), ("per-node", beta, gamma), ("per-edge", _er_of(g, w), gamma), ("per-edge, scalar gamma", _er_of(g, w), 0.2)):
-        want = _u32(sir_counts(g, seeds, b, gm, sims, T, rng_seed=11, sim_offset=5))
+    for name, b, gm in (("scalar", 0.45, 0.15), ("per-node", beta, gamma), ("per-edge", er_of(g, w), gamma), ("per-edge, scalar gamma", er_of(g, w), 0.2)):
+        want = u32(sir_counts(g, seeds, b, gm, sims, T, rng_seed=11, sim_offset=5))
         assert want[1, 1:].any()
         for scan in (False, True):
-            got = _u32(sir_counts(g, st, b, gm, sims, T, rng_seed=11, sim_offset=5, edge_scan=scan))
+            got = u32(sir_counts(g, st, b, gm, sims, T, rng_seed=11, sim_offset=5, edge_scan=scan))
             assert np.array_equal(got[:, 1:], want[:, 1:]), f"{kind}: {name}, scan={scan}: rows t >= 1"
             assert np.array_equal(got[:, 0], sims * want[:, 0]), f"{kind}: {name}, scan={scan}: row 0"
-
-
-def _assert_live(kind, rp, sims, model):
-    """On the model's own output: at least a quarter of the initially susceptible (connected node, trajectory) pairs left S."""
-    _, t_inf, _ = model
-    connected = np.diff(rp) > 0
-    sus, left = (t_inf != 0)[:, connected], (t_inf > 0)[:, connected]
-    print(f"{kind}: {left.sum() / sus.sum():.3f} of the initially susceptible (connected node, trajectory) pairs left S")
-    assert left.sum() >= 0.25 * sus.sum()
 
 
 @pytest.mark.parametrize("kind,n,m,seeds,sims,T", SHAPES, ids=IDS)
@@ -121,13 +44,14 @@ def test_mixed_state_equals_cpu_model(kind, n, m, seeds, sims, T, dev):
     counts, events, curves, the events' counts and `counts=`."""
     import torch
     from gnode.ode_nn import sir_counts, sir_counts_from_events, sir_curves_from_events, sir_trajectories
-    rp, ci, g, p, w, gamma = _mixed_case(kind, n, m, seeds)
-    model = _model(kind, n, rp, ci, p, w, gamma, sims, T, 21)
-    _assert_live(kind, rp, sims, model)
-    st, er = _state(p), _er_of(g, w)
+    rp, ci, g, p, w, gamma = _mixed_case(kind)
+    c, e = case(f"init/{kind}"), expected(f"init/{kind}")
+    model = (e.counts, e.t_inf, e.t_rec)
+    live_init(c, e)
+    st, er = state(p), er_of(g, w)
     for scan in (False, True):
         counts = sir_counts(g, st, er, gamma, sims, T, rng_seed=21, edge_scan=scan)
-        assert np.array_equal(_u32(counts), model[0]), f"{kind}: counts != CPU model (scan={scan})"
+        assert np.array_equal(u32(counts), model[0]), f"{kind}: counts != CPU model (scan={scan})"
         acc = torch.zeros_like(counts)
         tr = sir_trajectories(g, st, er, gamma, sims, T, rng_seed=21, counts=acc, edge_scan=scan)
         assert np.array_equal(tr.t_inf.cpu().numpy(), model[1]) and np.array_equal(tr.t_rec.cpu().numpy(), model[2]), f"{kind}: events (scan={scan})"
@@ -136,22 +60,21 @@ def test_mixed_state_equals_cpu_model(kind, n, m, seeds, sims, T, dev):
         assert torch.equal(sir_counts_from_events(tr.t_inf, tr.t_rec, T, accumulate_t0=True), counts), f"{kind}: events -> counts (scan={scan})"
         assert torch.equal(acc, counts), f"{kind}: counts= of the trajectory call (scan={scan})"
         acc = sir_counts(g, st, er, gamma, sims, T, rng_seed=21, edge_scan=scan, counts=acc)
-        assert np.array_equal(_u32(acc), 2 * model[0]), f"{kind}: counts= accumulates (scan={scan})"
+        assert np.array_equal(u32(acc), 2 * model[0]), f"{kind}: counts= accumulates (scan={scan})"
 
 
 def test_other_rate_forms_with_a_mixed_state(dev):
     """The scalar and per-node forms of the init call (a constant and beta[col] in the model's per-position weights)."""
     from gnode.ode_nn import sir_counts
     n, sims, T = 503, 100, 10
-    rp, ci, g = _graph("er-small", n, 2500)
-    p = _mixed("er-small", n, rp)
-    rng = np.random.default_rng(8)
-    beta, gamma = rng.uniform(0.05, 0.6, n), rng.uniform(0.05, 0.6, n)
-    for name, b, gm, w in (("scalar", 0.3, 0.2, 0.3), ("per-node", beta, gamma, beta[ci]), ("per-node beta only", beta, 0.2, beta[ci])):
-        want = _model("forms-" + name, n, rp, ci, p, w, gm, sims, T, 33, 4)[0]
+    rp, ci, g = graph("er-small", n, 2500)
+    p = mixed_start("er-small", n, rp)
+    for name in ("scalar", "per-node", "per-node beta only"):
+        c, want = case("init/forms-" + name), expected("init/forms-" + name).counts
+        b, gm = c.beta, c.gamma
         assert want[1, -1].any() and want[2, -1].any()
         for scan in (False, True):
-            assert np.array_equal(_u32(sir_counts(g, _state(p), b, gm, sims, T, rng_seed=33, sim_offset=4, edge_scan=scan)), want), f"{name}, scan={scan}"
+            assert np.array_equal(u32(sir_counts(g, state(p), b, gm, sims, T, rng_seed=33, sim_offset=4, edge_scan=scan)), want), f"{name}, scan={scan}"
 
 
 def test_more_initially_infected_than_a_seed_list_carries(dev):
@@ -159,17 +82,12 @@ def test_more_initially_infected_than_a_seed_list_carries(dev):
     with probability 0.3: a first frontier that fills a large share of the uint16 lists."""
     from gnode.ode_nn import sir_counts
     n, sims, T = 7066, 32, 8
-    rp, ci, g = _graph("wiki-vote-size", n, 100736)
-    rng = np.random.default_rng(41)
-    kind = rng.choice(3, size=n, p=[0.5, 0.4, 0.1])
-    p = np.zeros((n, 3))
-    p[kind == 0, 0], p[kind == 1, 1] = 1.0, 1.0
-    p[kind == 2] = (0.5, 0.3, 0.2)
-    assert (kind == 1).sum() > 0.39 * n
-    want = _model("many", n, rp, ci, p, 0.05, 0.1, sims, T, 42)[0]
+    rp, ci, g = graph("wiki-vote-size", n, 100736)
+    p, want = case("init/many").start, expected("init/many").counts
+    assert (p[:, 1] == 1.0).sum() > 0.39 * n
     assert want[1, 0].sum() > 0.39 * n * sims and want[0, -1].sum() < want[0, 0].sum()
     for scan in (False, True):
-        assert np.array_equal(_u32(sir_counts(g, _state(p), 0.05, 0.1, sims, T, rng_seed=42, edge_scan=scan)), want), f"scan={scan}"
+        assert np.array_equal(u32(sir_counts(g, state(p), 0.05, 0.1, sims, T, rng_seed=42, edge_scan=scan)), want), f"scan={scan}"
 
 
 def test_nobody_susceptible(dev):
@@ -177,16 +95,14 @@ def test_nobody_susceptible(dev):
     counts are 0."""
     from gnode.ode_nn import sir_counts, sir_trajectories
     n, sims, T = 503, 100, 10
-    rp, ci, g = _graph("er-small", n, 2500)
-    p = np.zeros((n, 3))
-    p[0::3], p[1::3], p[2::3] = (0.0, 1.0, 0.0), (0.0, 0.0, 1.0), (0.0, 0.6, 0.4)
-    gamma = np.random.default_rng(9).uniform(0.05, 0.6, n)
-    want = _model("no-S", n, rp, ci, p, 0.4, gamma, sims, T, 51)
+    rp, ci, g = graph("er-small", n, 2500)
+    c, e = case("init/no-S"), expected("init/no-S")
+    p, gamma, want = c.start, c.gamma, (e.counts, e.t_inf, e.t_rec)
     assert not want[0][0].any() and want[0][2, -1].sum() > want[0][2, 0].sum() and want[0][1, -1].any()
     for scan in (False, True):
-        got = _u32(sir_counts(g, _state(p), np.full(n, 0.4), gamma, sims, T, rng_seed=51, edge_scan=scan))
+        got = u32(sir_counts(g, state(p), np.full(n, 0.4), gamma, sims, T, rng_seed=51, edge_scan=scan))
         assert np.array_equal(got, want[0]), f"scan={scan}"
-        tr = sir_trajectories(g, _state(p), np.full(n, 0.4), gamma, sims, T, rng_seed=51, edge_scan=scan)
+        tr = sir_trajectories(g, state(p), np.full(n, 0.4), gamma, sims, T, rng_seed=51, edge_scan=scan)
         assert bool((tr.t_inf == 0).all()) and np.array_equal(tr.t_rec.cpu().numpy(), want[2])
         assert bool((tr.curves[:, :, 0] == 0).all()) and bool((tr.curves.sum(dim=2) == n).all())
 
@@ -195,16 +111,14 @@ def test_nobody_infected(dev):
     """Every row S or R: nothing ever happens, all rows equal row 0 and the events are `never` or (0, 0)."""
     from gnode.ode_nn import sir_counts, sir_trajectories
     n, sims, T = 503, 100, 10
-    rp, ci, g = _graph("er-small", n, 2500)
-    p = np.zeros((n, 3))
-    p[0::3], p[1::3], p[2::3] = (1.0, 0.0, 0.0), (0.0, 0.0, 1.0), (0.7, 0.0, 0.3)
-    want = _model("no-I", n, rp, ci, p, 0.4, 0.2, sims, T, 52)[0]
+    rp, ci, g = graph("er-small", n, 2500)
+    p, want = case("init/no-I").start, expected("init/no-I").counts
     for scan in (False, True):
-        got = _u32(sir_counts(g, _state(p), 0.4, 0.2, sims, T, rng_seed=52, edge_scan=scan))
+        got = u32(sir_counts(g, state(p), 0.4, 0.2, sims, T, rng_seed=52, edge_scan=scan))
         assert np.array_equal(got, want), f"scan={scan}"
         assert np.array_equal(got, np.broadcast_to(got[:, :1], got.shape)) and not got[1].any()
         assert 0 < got[2, 0, 2::3].sum() < sims * len(got[2, 0, 2::3])
-        tr = sir_trajectories(g, _state(p), 0.4, 0.2, sims, T, rng_seed=52, edge_scan=scan)
+        tr = sir_trajectories(g, state(p), 0.4, 0.2, sims, T, rng_seed=52, edge_scan=scan)
         ti, trc = tr.t_inf.cpu().numpy(), tr.t_rec.cpu().numpy()
         assert np.array_equal(ti, trc) and set(np.unique(ti).tolist()) == {-1, 0}
         cv = tr.curves.cpu().numpy()
@@ -216,13 +130,14 @@ def test_single_row(dev):
     from gnode.ode_nn import sir_trajectories
     import torch
     n, sims = 503, 100
-    rp, ci, g = _graph("er-small", n, 2500)
-    p = _mixed("er-small", n, rp)
-    want = _model("T1", n, rp, ci, p, 0.3, 0.2, sims, 1, 53)
+    rp, ci, g = graph("er-small", n, 2500)
+    p = mixed_start("er-small", n, rp)
+    e = expected("init/T1")
+    want = (e.counts, e.t_inf, e.t_rec)
     for scan in (False, True):
         acc = torch.zeros((3, 1, n), dtype=torch.int32, device=dev)
-        tr = sir_trajectories(g, _state(p), 0.3, 0.2, sims, 1, rng_seed=53, counts=acc, edge_scan=scan)
-        assert np.array_equal(_u32(acc), want[0]) and np.array_equal(tr.t_inf.cpu().numpy(), want[1])
+        tr = sir_trajectories(g, state(p), 0.3, 0.2, sims, 1, rng_seed=53, counts=acc, edge_scan=scan)
+        assert np.array_equal(u32(acc), want[0]) and np.array_equal(tr.t_inf.cpu().numpy(), want[1])
         assert tr.curves.shape == (sims, 1, 3)
         assert np.array_equal(tr.curves[:, 0].cpu().numpy(), np.stack([(want[1] < 0).sum(1), ((want[1] == 0) & (want[2] < 0)).sum(1), (want[2] == 0).sum(1)], 1))
 
@@ -232,7 +147,6 @@ def test_immune_barrier(dev):
     nodes 18 .. 24 are infected at steps 1 .. 7, nobody at or beyond the barrier ever is, and the barrier is R throughout."""
     from gnode.graph import DeviceGraph
     from gnode.ode_nn import InitialState, sir_state_at, sir_trajectories
-    from sir_edges_model import one_way_path
     n, rp, ci, w = one_way_path(40)
     g = DeviceGraph(rp, ci)
     sims, T = 33, 14
@@ -242,7 +156,7 @@ def test_immune_barrier(dev):
     want_rec = np.full(n, -1)
     want_rec[25] = 0
     for scan in (False, True):
-        tr = sir_trajectories(g, InitialState.from_sets(n, [17], immune=[25]), _er_of(g, w), 0.0, sims, T, rng_seed=9, edge_scan=scan)
+        tr = sir_trajectories(g, InitialState.from_sets(n, [17], immune=[25]), er_of(g, w), 0.0, sims, T, rng_seed=9, edge_scan=scan)
         assert np.array_equal(tr.t_inf.cpu().numpy(), np.broadcast_to(want_inf, (sims, n))), f"scan={scan}"
         assert np.array_equal(tr.t_rec.cpu().numpy(), np.broadcast_to(want_rec, (sims, n))), f"scan={scan}"
         for t in range(T):
@@ -255,28 +169,28 @@ def test_sharded_equals_whole(dev):
     import torch
     from gnode.ode_nn import sir_counts
     n, seeds = 503, [3, 499]
-    rp, ci, g, p, w, gamma = _mixed_case("er-small", n, 2500, seeds)
-    st, er = _state(p), _er_of(g, w)
+    rp, ci, g, p, w, gamma = _mixed_case("er-small")
+    st, er = state(p), er_of(g, w)
     for scan in (False, True):
         whole = sir_counts(g, st, er, gamma, 1000, 12, rng_seed=5, edge_scan=scan)
         acc = sir_counts(g, st, er, gamma, 600, 12, rng_seed=5, sim_offset=0, edge_scan=scan)
         acc = sir_counts(g, st, er, gamma, 400, 12, rng_seed=5, sim_offset=600, counts=acc, edge_scan=scan)
         assert torch.equal(whole, acc)
         assert bool((whole.sum(dim=0) == 1000).all()) and whole[2, -1].sum().item() > whole[2, 0].sum().item()
-    part = _u32(sir_counts(g, st, er, gamma, 40, 12, rng_seed=5, sim_offset=600))
-    assert np.array_equal(part, _model("shard", n, rp, ci, p, w, gamma, 40, 12, 5, 600)[0])
+    part = u32(sir_counts(g, st, er, gamma, 40, 12, rng_seed=5, sim_offset=600))
+    assert np.array_equal(part, expected("init/shard").counts)
 
 
 def test_large_state_paths(dev):
     """n = 100 000: the scan kernel keeps the trajectory state in memory, the frontier walk its lists (int32 ids)."""
     from gnode.ode_nn import sir_counts
     n, seeds = 100_000, [5, 77, 4242]
-    rp, ci, g, p, w, gamma = _mixed_case("large", n, 300_000, seeds)
-    want = _model("large", n, rp, ci, p, w, gamma, 24, 8, 99)[0]
+    rp, ci, g, p, w, gamma = _mixed_case("large")
+    want = expected("init/large").counts
     assert (want[0, -1] < want[0, 0]).sum() > 1000
-    st, er = _state(p), _er_of(g, w)
-    assert np.array_equal(_u32(sir_counts(g, st, er, gamma, 24, 8, rng_seed=99)), want)
-    assert np.array_equal(_u32(sir_counts(g, st, er, gamma, 24, 8, rng_seed=99, edge_scan=True)), want)
+    st, er = state(p), er_of(g, w)
+    assert np.array_equal(u32(sir_counts(g, st, er, gamma, 24, 8, rng_seed=99)), want)
+    assert np.array_equal(u32(sir_counts(g, st, er, gamma, 24, 8, rng_seed=99, edge_scan=True)), want)
 
 
 def test_fewer_entries_than_nodes_with_per_node_rates(dev):
@@ -284,15 +198,13 @@ def test_fewer_entries_than_nodes_with_per_node_rates(dev):
     thresholds, and the entry restates it per edge.  Same counts as the model's w = beta[col]."""
     from gnode.ode_nn import sir_counts
     n, sims, T = 300, 64, 6
-    rp, ci, g = _graph("isolated", n, 40)
+    rp, ci, g = graph("isolated", n, 40)
     assert len(ci) < n
-    p = _mixed("isolated", n, rp)
-    rng = np.random.default_rng(12)
-    beta, gamma = rng.uniform(0.3, 0.9, n), rng.uniform(0.05, 0.6, n)
-    want = _model("isolated-nodes", n, rp, ci, p, beta[ci], gamma, sims, T, 61)[0]
+    c, want = case("init/isolated-nodes"), expected("init/isolated-nodes").counts
+    p, beta, gamma = c.start, c.beta, c.gamma
     assert (want[0, -1] < want[0, 0]).any()
     for scan in (False, True):
-        assert np.array_equal(_u32(sir_counts(g, _state(p), beta, gamma, sims, T, rng_seed=61, edge_scan=scan)), want), f"scan={scan}"
+        assert np.array_equal(u32(sir_counts(g, state(p), beta, gamma, sims, T, rng_seed=61, edge_scan=scan)), want), f"scan={scan}"
 
 
 def test_seed_list_calls_untouched_after_init_calls(dev):
@@ -301,33 +213,28 @@ def test_seed_list_calls_untouched_after_init_calls(dev):
     import oracle_c as OC
     from gnode.ode_nn import sir_counts
     n, seeds = 503, [3, 499]
-    rp, ci, g, p, w, gamma = _mixed_case("er-small", n, 2500, seeds)
+    rp, ci, g, p, w, gamma = _mixed_case("er-small")
     beta = np.random.default_rng(1).uniform(0.05, 0.6, n)
-    forms = {"scalar": (0.3, 0.2), "per-node": (beta, gamma), "per-edge": (_er_of(g, w), gamma)}
-    before = {(k, scan): _u32(sir_counts(g, seeds, b, gm, 64, 10, rng_seed=9, edge_scan=scan)) for k, (b, gm) in forms.items() for scan in (False, True)}
+    forms = {"scalar": (0.3, 0.2), "per-node": (beta, gamma), "per-edge": (er_of(g, w), gamma)}
+    before = {(k, scan): u32(sir_counts(g, seeds, b, gm, 64, 10, rng_seed=9, edge_scan=scan)) for k, (b, gm) in forms.items() for scan in (False, True)}
     for b, gm in forms.values():
         for scan in (False, True):
-            sir_counts(g, _state(p), b, gm, 64, 10, rng_seed=9, edge_scan=scan)
+            sir_counts(g, state(p), b, gm, 64, 10, rng_seed=9, edge_scan=scan)
     for (k, scan), want in before.items():
         b, gm = forms[k]
-        assert np.array_equal(_u32(sir_counts(g, seeds, b, gm, 64, 10, rng_seed=9, edge_scan=scan)), want), f"{k}, scan={scan}"
+        assert np.array_equal(u32(sir_counts(g, seeds, b, gm, 64, 10, rng_seed=9, edge_scan=scan)), want), f"{k}, scan={scan}"
     assert np.array_equal(before[("scalar", False)], OC.sir_philox(n, rp, ci, seeds, 0.3, 0.2, 64, 10, rng_seed=9))
 
 
 def test_sir_torch_surface(dev):
     """An InitialState through the reference-shaped surface: row 0 holds counts and normalize_t0 has nothing to do."""
-    import networkx as nx
-    from gnode.ode_nn import _csr_from_edges, _edge_arrays, sir_torch
-    from sir_init_model import mixed_init
-    G = nx.karate_club_graph()
-    n, sims, T = 34, 300, 12
-    rp, ci = _csr_from_edges(n, _edge_arrays(G))
-    p, _ = mixed_init(n, 34)
-    gamma = np.random.default_rng(35).uniform(0.05, 0.6, n)
-    want = _model("karate", n, rp, ci, p, 0.3, gamma, sims, T, 77)[0].astype(np.float64)
+    from gnode.ode_nn import sir_torch
+    c = case("init/karate")
+    G, n, sims, T, p, gamma = c.G, c.n, c.sims, c.T, c.start, c.gamma
+    want = expected("init/karate").counts.astype(np.float64)
     assert want[2, -1].sum() > want[2, 0].sum()
     for norm in (False, True):
-        S, I, R = sir_torch(G, _state(p), 0.3, gamma, sims, T, rng_seed=77, normalize_t0=norm)
+        S, I, R = sir_torch(G, state(p), 0.3, gamma, sims, T, rng_seed=77, normalize_t0=norm)
         assert S.shape == (1, T, n) and S.dtype == np.float64
         assert np.array_equal(S[0], want[0]) and np.array_equal(I[0], want[1]) and np.array_equal(R[0], want[2])
 
@@ -339,8 +246,8 @@ def test_library_validates_the_state_and_the_rate_forms(dev):
     from gnode import _lib
     lib = _lib.load()
     n, T, sims = 503, 6, 8
-    rp, ci, g = _graph("er-small", n, 2500)
-    good = _mixed("er-small", n, rp)
+    rp, ci, g = graph("er-small", n, 2500)
+    good = mixed_start("er-small", n, rp)
     counts = torch.zeros((3, T, n), dtype=torch.int32, device=dev)
     events = torch.full((2, sims, n), 7, dtype=torch.int16, device=dev)
     curves = torch.full((sims, T, 3), 7, dtype=torch.int32, device=dev)

@@ -6,43 +6,20 @@ Two graphs (tests/test_sir_plan.py pins their plans: "lds64k" in its GRAPHS):
   * n = 153 000 without rows longer than 512: the frontier walk takes 65 600 B; the scan with its state in memory is the
     cross-check, and the workspace is 1.9 GB.
 On each, all twelve (rate form x output x start) instances run on the large-LDS path and are compared bit for bit with the other
-path; one call per graph is held to a CPU statement of the model (tests/sir_init_model.py, the C oracle's sir_philox)."""
+path; one call per graph is held to a CPU statement of the model (tests/sir_model.py, the C oracle's sir_philox)."""
 import numpy as np
 import pytest
 
-from test_gpu_sir_edges import _u32
+from sir_cases import LDS64K_FRONTIER as FRONTIER, LDS64K_RNG as RNG, LDS64K_SCAN as SCAN_STATE, LDS64K_SIMS as SIMS, LDS64K_T as T  # noqa: F401
+from sir_cases import dev, expected, graph, lds64k_case, u32  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-SIMS, T, RNG = 8, 6, 41
-SCAN_STATE, FRONTIER = ("scan-state-in-lds", 33000, 100000, True), ("frontier", 153000, 460000, False)
-
-_CASE: dict = {}
-
-
-@pytest.fixture(scope="module")
-def dev():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from gnode import _lib
-    _lib.load()                       # fails loudly if libgnode_hip.so is missing
-    return torch.device("cuda:0")
-
 
 def _case(kind, n, m):
-    """graph, start and rates of a shape, built once: (rowptr, col, DeviceGraph, seeds, p, beta, w, gamma)"""
-    if kind not in _CASE:
-        import gnode_oracle as O
-        from gnode.graph import DeviceGraph
-        from sir_init_model import mixed_init
-        rp, ci, _ = O.er_graph(n, m, seed=n)
-        rng = np.random.default_rng(n)
-        beta, w, gamma = rng.uniform(0.2, 0.8, n), rng.uniform(0.05, 0.9, len(ci)), rng.uniform(0.05, 0.6, n)
-        w[rng.permutation(len(ci))[:len(ci) // 5]] = 0.0                # directed contacts
-        w[::17], gamma[::19], gamma[5::23] = 1.0, 0.0, 1.0
-        _CASE[kind] = (rp, ci, DeviceGraph(rp, ci), [7, n // 2, n - 1], mixed_init(n, n + 1)[0], beta, w, gamma)
-    return _CASE[kind]
+    """graph, start and rates of a shape: (rowptr, col, DeviceGraph, seeds, p, beta, w, gamma)"""
+    rp, ci, *rest = lds64k_case(kind, n, m)
+    return (rp, ci, graph(kind, n, m)[2], *rest)
 
 
 def _twelve(g, seeds, p, beta, w, gamma, edge_scan):
@@ -52,19 +29,11 @@ def _twelve(g, seeds, p, beta, w, gamma, edge_scan):
     out = {}
     for rname, b, gm in (("scalar", 0.45, 0.15), ("per-node", beta, gamma), ("per-edge", edge_rates(g, w), gamma)):
         for sname, start in (("seeds", seeds), ("drawn", initial_state(p))):
-            out[(rname, "counts", sname)] = (_u32(sir_counts(g, start, b, gm, SIMS, T, rng_seed=RNG, sim_offset=3, edge_scan=edge_scan)),)
+            out[(rname, "counts", sname)] = (u32(sir_counts(g, start, b, gm, SIMS, T, rng_seed=RNG, sim_offset=3, edge_scan=edge_scan)),)
             acc = torch.zeros((3, T, g.n), dtype=torch.int32, device="cuda")
             tr = sir_trajectories(g, start, b, gm, SIMS, T, rng_seed=RNG, sim_offset=3, counts=acc, edge_scan=edge_scan)
-            out[(rname, "events", sname)] = (_u32(acc), tr.t_inf.cpu().numpy(), tr.t_rec.cpu().numpy(), tr.curves.cpu().numpy())
+            out[(rname, "events", sname)] = (u32(acc), tr.t_inf.cpu().numpy(), tr.t_rec.cpu().numpy(), tr.curves.cpu().numpy())
     return out
-
-
-def _curves_of(t_inf, t_rec, n):
-    """int [sims, T, 3] from the events, on the CPU"""
-    steps = np.arange(T)[None, :, None]
-    ci = ((t_inf[:, None, :] >= 0) & (t_inf[:, None, :] <= steps)).sum(2)
-    cr = ((t_rec[:, None, :] >= 0) & (t_rec[:, None, :] <= steps)).sum(2)
-    return np.stack([n - ci, ci - cr, cr], axis=2)
 
 
 @pytest.mark.parametrize("kind,n,m,large_is_scan", [SCAN_STATE, FRONTIER], ids=[SCAN_STATE[0], FRONTIER[0]])
@@ -84,18 +53,18 @@ def test_scan_with_lds_state_equals_cpu_model(dev):
     """drawn start, per-edge rates, per-node gamma, with events: counts, events, and curves rebuilt from the events"""
     import torch
     from gnode.ode_nn import edge_rates, initial_state, sir_trajectories
-    from sir_init_model import sir_philox_init
     kind, n, m, _ = SCAN_STATE
     rp, ci, g, seeds, p, beta, w, gamma = _case(kind, n, m)
-    want, t_inf, t_rec = sir_philox_init(n, rp, ci, p, w, gamma, SIMS, T, RNG, 3, return_events=True)
+    e = expected("init/lds64k")
+    want, t_inf, t_rec = e.counts, e.t_inf, e.t_rec
     moved = int((want[0, -1] < want[0, 0]).sum())
     print(f"{kind}: the model's S row fell on {moved} nodes")
     assert moved > 100
     acc = torch.zeros((3, T, n), dtype=torch.int32, device=dev)
     tr = sir_trajectories(g, initial_state(p), edge_rates(g, w), gamma, SIMS, T, rng_seed=RNG, sim_offset=3, counts=acc, edge_scan=True)
-    assert np.array_equal(_u32(acc), want)
+    assert np.array_equal(u32(acc), want)
     assert np.array_equal(tr.t_inf.cpu().numpy(), t_inf) and np.array_equal(tr.t_rec.cpu().numpy(), t_rec)
-    assert np.array_equal(tr.curves.cpu().numpy(), _curves_of(t_inf, t_rec, n))
+    assert np.array_equal(tr.curves.cpu().numpy(), e.curves)
 
 
 def test_frontier_past_64k_equals_c_oracle(dev):
@@ -110,4 +79,4 @@ def test_frontier_past_64k_equals_c_oracle(dev):
     moved = int((want[0, -1] < SIMS * want[0, 0]).sum())                                 # (row 0 holds the start once)
     print(f"{kind}: the oracle's S row fell on {moved} nodes")
     assert moved > 100
-    assert np.array_equal(_u32(sir_counts(g, seeds, 0.45, 0.15, SIMS, T, rng_seed=RNG, sim_offset=3)), want)
+    assert np.array_equal(u32(sir_counts(g, seeds, 0.45, 0.15, SIMS, T, rng_seed=RNG, sim_offset=3)), want)

@@ -1,40 +1,15 @@
 """GPU: per-trajectory Monte-Carlo SIR output (gnode_sir_mc_philox_traj through gnode.ode_nn.sir_trajectories): the step at
 which every node of every trajectory was infected and recovered, and each trajectory's population totals.  Every
-comparison is array_equal on integers: against the CPU model of tests/sir_events_model.py (held to the oracle by
-tests/test_sir_events_model.py), against the production call `sir_counts`, and between the two kernels.  Shapes, graphs
-and rates are those of tests/test_gpu_sir_nodes.py: the smallest that reach each storage form."""
+comparison is array_equal on integers: against the CPU model of tests/sir_model.py on the cases of tests/sir_cases.py (held
+to the oracle by tests/test_sir_model.py), against the production call `sir_counts`, and between the two kernels.  Shapes,
+graphs and rates are those of tests/test_gpu_sir_nodes.py: the smallest that reach each storage form."""
 import numpy as np
 import pytest
 
-from test_gpu_sir_nodes import SHAPES, _bfs_depth, _graph, _hetero_seeds, _rates
+from sir_cases import IDS, SHAPE, SHAPES, bfs_depth, case, dev, expected, graph, live_events, node_rates  # noqa: F401
+from sir_model import states_at
 
 pytestmark = pytest.mark.gpu
-IDS = [s[0] for s in SHAPES]
-SHAPE = {s[0]: s for s in SHAPES}
-
-
-@pytest.fixture(scope="module")
-def dev():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from gnode import _lib
-    _lib.load()                       # fails loudly if libgnode_hip.so is missing
-    return torch.device("cuda:0")
-
-
-_MODEL: dict = {}
-
-
-def _model(key, n, rp, ci, seeds, beta, gamma, sims, T, rng_seed, sim_offset=0):
-    """The CPU model's (t_inf, t_rec, curves), computed once per case and shared (never modified)."""
-    if key not in _MODEL:
-        from sir_events_model import sir_philox_events
-        out = sir_philox_events(n, rp, ci, seeds, beta, gamma, sims, T, rng_seed, sim_offset)
-        for a in out:
-            a.setflags(write=False)
-        _MODEL[key] = out
-    return _MODEL[key]
 
 
 def _np(tr):
@@ -42,18 +17,16 @@ def _np(tr):
     return tr.t_inf.cpu().numpy(), tr.t_rec.cpu().numpy(), tr.curves.cpu().numpy().astype(np.uint32)
 
 
+def _want(key):
+    """(t_inf, t_rec, curves) of the model on a case of sir_cases."""
+    e = expected(key)
+    return e.t_inf, e.t_rec, e.curves
+
+
 def _same(got, want, what, rows=None):
     for name, a, b in zip(("t_inf", "t_rec", "curves"), got, want):
         a = a if rows is None else a[:rows]
         assert a.dtype == b.dtype and np.array_equal(a, b), f"{what}: {name} differs"
-
-
-def _assert_live(t_inf, t_rec, curves, what):
-    """On the MODEL's output: the case exercises every kind of entry (a seed that fails this is changed, not the check)."""
-    assert (t_inf == -1).any(), f"{what}: every node is infected in every trajectory"
-    assert ((t_inf >= 0) & (t_rec == -1)).any(), f"{what}: nobody stays infected to the end"
-    assert (t_rec >= 0).any(), f"{what}: nobody recovers"
-    assert any(not np.array_equal(curves[0], c) for c in curves[1:]), f"{what}: all curves are the same"
 
 
 # -------------------------------------------------------------------------------------------------- 1. against the CPU model
@@ -63,12 +36,12 @@ MODEL_SIMS = {"wiki-vote-size": 24}       # the model runs the first 24 trajecto
 @pytest.mark.parametrize("kind,n,m,seeds,sims,T", SHAPES, ids=IDS)
 def test_events_and_curves_equal_cpu_model(kind, n, m, seeds, sims, T, dev):
     from gnode.ode_nn import sir_trajectories
-    rp, ci, g = _graph(kind, n, m)
-    seeds = _hetero_seeds(kind, rp, seeds)
-    beta, gamma, _ = _rates(kind, n, seeds)
+    g = graph(kind, n, m)[2]
     msims = MODEL_SIMS.get(kind, sims)
-    want = _model(kind, n, rp, ci, seeds, beta, gamma, msims, T, 21)
-    _assert_live(*want, kind)
+    key = f"nodes/{kind}" + (f"/{msims}" if msims != sims else "")
+    c, want = case(key), _want(key)
+    seeds, beta, gamma = c.start, c.beta, c.gamma
+    live_events(c, expected(key))
     for scan in (False, True):
         tr = sir_trajectories(g, seeds, beta, gamma, sims, T, rng_seed=21, edge_scan=scan)
         assert tr.t_inf.shape == (sims, n) and tr.t_rec.shape == (sims, n) and tr.curves.shape == (sims, T, 3)
@@ -79,7 +52,7 @@ def test_events_and_curves_equal_cpu_model(kind, n, m, seeds, sims, T, dev):
 @pytest.mark.parametrize("kind,n,m,seeds,sims,T", SHAPES, ids=IDS)
 def test_scalar_rates_equal_constant_arrays(kind, n, m, seeds, sims, T, dev):
     from gnode.ode_nn import sir_trajectories
-    rp, ci, g = _graph(kind, n, m)
+    rp, ci, g = graph(kind, n, m)
     for beta, gamma, rs in ((0.45, 0.15, 11), (0.05, 0.6, 12)):
         a = _np(sir_trajectories(g, seeds, beta, gamma, sims, T, rng_seed=rs, sim_offset=5))
         b = _np(sir_trajectories(g, seeds, np.full(n, beta), np.full(n, gamma), sims, T, rng_seed=rs, sim_offset=5))
@@ -108,8 +81,8 @@ def _check_identities(g, seeds, beta, gamma, sims, T, rs, what, edge_scan=False)
 
 @pytest.mark.parametrize("kind,n,m,seeds,sims,T", SHAPES, ids=IDS)
 def test_consistent_with_production_call(kind, n, m, seeds, sims, T, dev):
-    rp, ci, g = _graph(kind, n, m)
-    beta, gamma, _ = _rates(kind, n, seeds)
+    rp, ci, g = graph(kind, n, m)
+    beta, gamma, _ = node_rates(kind, n, seeds)
     _check_identities(g, seeds, 0.3, 0.2, sims, T, 9, f"{kind}, scalar rates")
     _check_identities(g, seeds, beta, gamma, sims, T, 9, f"{kind}, per-node rates")
 
@@ -118,8 +91,8 @@ def test_scalar_production_call_untouched_after_traj_calls(dev):
     import oracle_c as OC
     from gnode.ode_nn import sir_counts, sir_trajectories
     kind, n, m, seeds, sims, T = SHAPE["er-small"]
-    rp, ci, g = _graph(kind, n, m)
-    beta, gamma, _ = _rates(kind, n, seeds)
+    rp, ci, g = graph(kind, n, m)
+    beta, gamma, _ = node_rates(kind, n, seeds)
     sir_trajectories(g, seeds, beta, gamma, 64, 10, rng_seed=9)
     sir_trajectories(g, seeds, 0.3, 0.2, 64, 10, rng_seed=9, edge_scan=True)
     for scan in (False, True):
@@ -134,8 +107,8 @@ def test_one_output_at_a_time(kind, scan, dev):
     import torch
     from gnode.ode_nn import sir_trajectories
     _, n, m, seeds, sims, T = SHAPE[kind]
-    rp, ci, g = _graph(kind, n, m)
-    beta, gamma, _ = _rates(kind, n, seeds)
+    rp, ci, g = graph(kind, n, m)
+    beta, gamma, _ = node_rates(kind, n, seeds)
     both = sir_trajectories(g, seeds, beta, gamma, sims, T, rng_seed=21, edge_scan=scan)
     ev = sir_trajectories(g, seeds, beta, gamma, sims, T, rng_seed=21, edge_scan=scan, curves=False)
     cv = sir_trajectories(g, seeds, beta, gamma, sims, T, rng_seed=21, edge_scan=scan, events=False)
@@ -148,8 +121,8 @@ def test_shard_equals_slice_of_whole(dev):
     import torch
     from gnode.ode_nn import sir_trajectories
     kind, n, m, seeds, _, _ = SHAPE["er-small"]
-    rp, ci, g = _graph(kind, n, m)
-    beta, gamma, _ = _rates(kind, n, seeds)
+    rp, ci, g = graph(kind, n, m)
+    beta, gamma, _ = node_rates(kind, n, seeds)
     whole = sir_trajectories(g, seeds, beta, gamma, 1000, 12, rng_seed=5)
     part = sir_trajectories(g, seeds, beta, gamma, 40, 12, rng_seed=5, sim_offset=600)
     assert (whole.t_rec[600:640] >= 0).any()
@@ -158,24 +131,12 @@ def test_shard_equals_slice_of_whole(dev):
 
 
 # -------------------------------------------------------------------------------------------------- 6. sims > workgroups
-def _er300():
-    import gnode_oracle as O
-    from gnode.graph import DeviceGraph
-    if "er300" not in _MODEL:
-        rp, ci, _ = O.er_graph(300, 600, seed=300)           # the graph of test_gpu_sir_nodes.py::test_extreme_thresholds
-        _MODEL["er300"] = (rp, ci, DeviceGraph(rp, ci))
-    return _MODEL["er300"]
-
-
 def test_more_trajectories_than_workgroups_lds(dev):
     """5 000 trajectories: every workgroup of the LDS forms takes several, one after the other."""
     from gnode.ode_nn import sir_trajectories
-    n, seeds, sims, T = 300, [11, 200], 5000, 8
-    rp, ci, g = _er300()
-    rng = np.random.default_rng(300)
-    beta, gamma = rng.uniform(0.05, 0.6, n), rng.uniform(0.05, 0.6, n)
-    want = _model("many", n, rp, ci, seeds, beta, gamma, sims, T, 13)
-    _assert_live(*want, "er300 x 5000")
+    c, want = case("nodes/many"), _want("nodes/many")
+    g, seeds, beta, gamma, sims, T = graph("er300", 300, 600)[2], c.start, c.beta, c.gamma, c.sims, c.T
+    live_events(c, expected("nodes/many"))
     for scan in (False, True):
         _same(_np(sir_trajectories(g, seeds, beta, gamma, sims, T, rng_seed=13, edge_scan=scan)), want, f"edge_scan={scan}")
 
@@ -185,8 +146,8 @@ def test_more_trajectories_than_workgroups_workspace_lists(dev):
     identities with the production call, and frontier == scan)."""
     import torch
     kind, n, m, seeds, _, _ = SHAPE["global-lists"]
-    rp, ci, g = _graph(kind, n, m)
-    beta, gamma, _ = _rates(kind, n, seeds)
+    rp, ci, g = graph(kind, n, m)
+    beta, gamma, _ = node_rates(kind, n, seeds)
     a = _check_identities(g, seeds, beta, gamma, 1100, 6, 17, "global-lists x 1100")
     b = _check_identities(g, seeds, beta, gamma, 1100, 6, 17, "global-lists x 1100, scan", edge_scan=True)
     assert (a.t_inf[1024:] > 0).any() and (a.t_rec[1024:] > 0).any()
@@ -198,11 +159,9 @@ def test_more_trajectories_than_workgroups_workspace_lists(dev):
 def test_large_state_paths(dev):
     """n = 100 000: the scan kernel keeps the trajectory state in memory, the frontier walk its lists (int32 ids)."""
     from gnode.ode_nn import sir_trajectories
-    n, seeds = 100_000, [5, 77, 4242]
-    rp, ci, g = _graph("large", n, 300_000)
-    beta, gamma, _ = _rates("large", n, seeds)
-    want = _model("large", n, rp, ci, seeds, beta, gamma, 24, 8, 99)
-    _assert_live(*want, "large")
+    c, want = case("nodes/large"), _want("nodes/large")
+    g, seeds, beta, gamma = graph("large", c.n, c.m)[2], c.start, c.beta, c.gamma
+    live_events(c, expected("nodes/large"))
     for scan in (False, True):
         _same(_np(sir_trajectories(g, seeds, beta, gamma, 24, 8, rng_seed=99, edge_scan=scan)), want, f"large, edge_scan={scan}")
 
@@ -211,9 +170,9 @@ def test_large_state_paths(dev):
 def test_early_extinction_fills_the_tail(dev):
     from gnode.ode_nn import sir_trajectories
     kind, n, m, seeds, sims, T = SHAPE["isolated"]
-    rp, ci, g = _graph(kind, n, m)
-    beta, gamma, _ = _rates(kind, n, seeds)
-    want = _model("isolated-1", n, rp, ci, seeds, beta, gamma, sims, T, 21)
+    rp, ci, g = graph(kind, n, m)
+    beta, gamma, _ = node_rates(kind, n, seeds)
+    want = _want("nodes/isolated-1")
     cv = want[2].astype(np.int64)
     dead = cv[:, :, 1] == 0
     assert dead[:, :T - 2].any(), "no trajectory of the model is extinct before T - 2"
@@ -229,8 +188,8 @@ def test_certain_infection_follows_bfs_depth(dev):
     """beta = 1, gamma = 0: t_inf is the BFS depth on the seed's component, nobody recovers, and the epidemic stops."""
     from gnode.ode_nn import sir_trajectories
     n, seed, sims = 300, 11, 32
-    rp, ci, g = _er300()
-    depth = _bfs_depth(rp, ci, seed, n)
+    rp, ci, g = graph("er300", n, 600)
+    depth = bfs_depth(rp, ci, seed, n)
     ecc = int(depth.max())
     T = ecc + 2
     for scan in (False, True):
@@ -248,22 +207,8 @@ def test_everybody_infected_branch(dev):
     take the frontier kernel's recovery-only branch."""
     from gnode.graph import DeviceGraph
     from gnode.ode_nn import sir_trajectories
-    rp0, ci0, _ = _er300()
-    depth0 = _bfs_depth(rp0, ci0, 11, 300)
-    keep = np.flatnonzero(depth0 >= 0)
-    new_id = np.full(300, -1)
-    new_id[keep] = np.arange(keep.size)
-    n = int(keep.size)
-    rp = np.concatenate([[0], np.cumsum(np.diff(rp0)[keep])]).astype(np.int32)      # a component keeps whole rows
-    ci = np.concatenate([new_id[ci0[rp0[u]:rp0[u + 1]]] for u in keep]).astype(np.int32)
-    assert ci.min() >= 0 and rp[-1] == ci.size
-    seed = int(new_id[11])
-    ecc = int(_bfs_depth(rp, ci, seed, n).max())
-    sims, T = 32, ecc + 8
-    gamma = np.random.default_rng(9).uniform(0.05, 0.6, n)
-    gamma[seed] = 0.0
-    beta = np.ones(n)
-    want = _model("everybody", n, rp, ci, [seed], beta, gamma, sims, T, 4)
+    c, want = case("nodes/everybody"), _want("nodes/everybody")
+    rp, ci, (seed,), beta, gamma, sims, T = c.rp, c.ci, c.start, c.beta, c.gamma, c.sims, c.T
     full = want[2][:, :, 0] == 0                                     # S_t = 0: n_ever == n
     assert full[:, T - 6].all(), "the model has not infected everybody 5 steps before the end"
     assert (want[1] >= T - 5).any(), "nobody recovers in the model's last five steps"
@@ -287,7 +232,7 @@ def test_writes_stay_inside_the_outputs(case, scan, dev):
         g = DeviceGraph(rp, ci)
     else:
         _, n, m, seeds, sims, T = SHAPE[case]
-        rp, ci, g = _graph(case, n, m)
+        rp, ci, g = graph(case, n, m)
     rng = np.random.default_rng(55)
     beta, gamma = rng.uniform(0.05, 0.6, n), rng.uniform(0.05, 0.6, n)
     ge, gc = 3, 5                                                     # guards; 3 int16: the view is 2-byte aligned only
@@ -309,11 +254,10 @@ def test_writes_stay_inside_the_outputs(case, scan, dev):
 def test_sir_state_at(dev):
     import torch
     from gnode.ode_nn import sir_state_at, sir_trajectories
-    from sir_events_model import states_at
     kind, n, m, seeds, sims, T = SHAPE["er-small"]
-    rp, ci, g = _graph(kind, n, m)
-    beta, gamma, _ = _rates(kind, n, seeds)
-    want = _model(kind, n, rp, ci, seeds, beta, gamma, sims, T, 21)
+    rp, ci, g = graph(kind, n, m)
+    beta, gamma, _ = node_rates(kind, n, seeds)
+    want = _want(f"nodes/{kind}")
     tr = sir_trajectories(g, seeds, beta, gamma, sims, T, rng_seed=21)
     for t in (0, T // 2, T - 1):
         st = sir_state_at(tr.t_inf, tr.t_rec, t)
@@ -332,7 +276,7 @@ def test_no_trajectories(dev):
     from gnode import _lib
     from gnode.ode_nn import sir_counts_from_events, sir_curves_from_events, sir_trajectories
     kind, n, m, seeds, _, T = SHAPE["er-small"]
-    rp, ci, g = _graph(kind, n, m)
+    rp, ci, g = graph(kind, n, m)
     tr = sir_trajectories(g, seeds, 0.3, 0.2, 0, T, rng_seed=1)
     assert tr.t_inf.shape == (0, n) and tr.t_rec.shape == (0, n) and tr.curves.shape == (0, T, 3)
     assert tr.t_inf.dtype == torch.int16 and tr.curves.dtype == torch.int32 and tr.t_inf.is_cuda

@@ -3,6 +3,8 @@ must before the library is entered (no GPU here: a stub graph is all these calls
 import numpy as np
 import pytest
 
+from sir_cases import StubGraph as _StubGraph
+
 
 @pytest.fixture(scope="module")
 def lib():
@@ -23,17 +25,6 @@ def test_edges_entries_exported(lib):
     assert len(lib.gnode_sir_mc_philox_traj_edges.argtypes) == 17
     assert len(lib.gnode_sir_mc_philox_traj.argtypes) == 18              # untouched
     assert lib.gnode_sir_edges_workspace_bytes(None, 20) == 0            # no handle: no guess
-
-
-class _StubGraph:
-    """What the Monte-Carlo calls read before they enter the library.  `handle` raises: reaching it means a check came too late."""
-    n, nnz = 10, 18
-    rowptr = np.concatenate([[0], np.cumsum([1] + [2] * 8 + [1])])
-    col = np.asarray([j for i in range(10) for j in (i - 1, i + 1) if 0 <= j < 10])
-
-    @property
-    def handle(self):
-        raise AssertionError("the library was entered before the rates were checked")
 
 
 def test_surface_refuses_bad_gamma_and_foreign_rates():

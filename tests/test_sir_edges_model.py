@@ -1,71 +1,23 @@
-"""CPU: the per-edge model of tests/sir_edges_model.py held to the oracle (`sir_philox`), to the per-node model and to
-what a direction means, and `gnode.ode_nn.edge_rates`, which puts a matrix into CSR position order
-(tests/test_gpu_sir_edges.py compares the GPU with the model and feeds it through edge_rates)."""
+"""CPU: what a direction means to the model of tests/sir_model.py -- the one-way path, a closed form -- and
+`gnode.ode_nn.edge_rates`, which puts a matrix into CSR position order (tests/test_gpu_sir_edges.py feeds the GPU through it).
+The model itself is held to the oracle by tests/test_sir_model.py."""
 import numpy as np
 import pytest
 
-
-def _karate():
-    import networkx as nx
-    import gnode_oracle as O
-    G = nx.karate_club_graph()
-    return (34, *O.csr_from_edges(34, [(int(a), int(b)) for a, b in G.edges()]))
-
-
-def _er200():
-    import gnode_oracle as O
-    rp, ci, _ = O.er_graph(200, 800, seed=200)
-    return 200, rp, ci
-
-
-@pytest.mark.parametrize("graph,seeds,beta,gamma,sims,T,off", [
-    (_karate, [0, 33], 0.3, 0.2, 40, 12, 0),
-    (_er200, [3, 150], 0.45, 0.15, 24, 10, 0),
-    (_er200, [3, 150], 0.05, 0.6, 24, 10, 1000),
-    (_karate, [5], 1.0, 0.0, 6, 6, 7),
-])
-def test_constant_weights_equal_scalar_oracle(graph, seeds, beta, gamma, sims, T, off):
-    import gnode_oracle as O
-    from sir_edges_model import sir_philox_edges
-    n, rp, ci = graph()
-    want = O.sir_philox(n, rp, ci, seeds, beta, gamma, sims, T, rng_seed=0xABCDEF0123, sim_offset=off)
-    assert want[2, -1].sum() > 0 or gamma == 0.0
-    for g in (gamma, np.full(n, gamma)):
-        got = sir_philox_edges(n, rp, ci, seeds, np.full(len(ci), beta), g, sims, T, rng_seed=0xABCDEF0123, sim_offset=off)
-        assert np.array_equal(got, want)
-
-
-@pytest.mark.parametrize("graph", [_karate, _er200])
-def test_target_weights_equal_per_node_model(graph):
-    """w[p] = beta[col[p]] is the per-node form."""
-    from sir_edges_model import sir_philox_edges
-    from sir_nodes_model import sir_philox_nodes
-    n, rp, ci = graph()
-    rng = np.random.default_rng(17)
-    beta, gamma = rng.uniform(0.05, 0.7, n), rng.uniform(0.05, 0.5, n)
-    beta[rng.permutation(n)[:n // 8]] = 0.0
-    want = sir_philox_nodes(n, rp, ci, [1, n - 2], beta, gamma, 20, 10, rng_seed=41, sim_offset=3)
-    assert want[2, -1].sum() > 0
-    assert np.array_equal(sir_philox_edges(n, rp, ci, [1, n - 2], beta[ci], gamma, 20, 10, rng_seed=41, sim_offset=3), want)
-    # ... and not the source's: rates indexed by the row give other counts
-    src = np.repeat(np.arange(n), np.diff(rp))
-    assert not np.array_equal(sir_philox_edges(n, rp, ci, [1, n - 2], beta[src], gamma, 20, 10, rng_seed=41, sim_offset=3), want)
+from sir_cases import case, er200 as _er200, expected, karate
 
 
 def test_one_way_path_is_deterministic():
     """w = 1 along i -> i + 1, 0 along i + 1 -> i, nobody recovers: node m + j leaves S at step j in every trajectory,
     nobody below m ever does."""
-    from sir_edges_model import one_way_path, sir_philox_edges
-    k, m, sims = 12, 5, 7
-    n, rp, ci, w = one_way_path(k)
-    T = k - m + 3
-    cnt, t_inf, t_rec = sir_philox_edges(n, rp, ci, [m], w, 0.0, sims, T, rng_seed=9, return_events=True)
+    c, got = case("cpu/path12"), expected("cpu/path12")
+    n, m, sims, T = c.n, 5, c.sims, c.T
     want = np.full(n, -1)
     want[m:] = np.arange(n - m)
-    assert np.array_equal(t_inf, np.broadcast_to(want, (sims, n)))
+    assert np.array_equal(got.t_inf, np.broadcast_to(want, (sims, n)))
     for t in range(1, T):
-        assert np.array_equal(cnt[1, t], np.where((np.arange(n) >= m) & (np.arange(n) - m <= t), sims, 0))
-    assert not cnt[2].any() and np.all(t_rec == -1)
+        assert np.array_equal(got.counts[1, t], np.where((np.arange(n) >= m) & (np.arange(n) - m <= t), sims, 0))
+    assert not got.counts[2].any() and np.all(got.t_rec == -1)
 
 
 def _shuffled_matrix(n, rp, ci, w, seed):
@@ -102,11 +54,9 @@ def test_edge_rates_aligns_a_matrix_with_the_csr():
 
 
 def test_edge_rates_from_a_networkx_graph():
-    import networkx as nx
     import scipy.sparse as sp
-    from gnode.ode_nn import _csr_from_edges, _edge_arrays, edge_rates
-    G = nx.karate_club_graph()
-    rp, ci = _csr_from_edges(34, _edge_arrays(G))
+    from gnode.ode_nn import edge_rates
+    G, n, rp, ci = karate()
     w = np.random.default_rng(5).uniform(0.0, 1.0, len(ci))
     assert np.array_equal(edge_rates(G, sp.csr_matrix((w, ci, rp), shape=(34, 34))).w, w)
 

@@ -3,7 +3,7 @@ before the library is entered (no GPU here: a stub graph is all these calls may 
 import numpy as np
 import pytest
 
-from test_sir_edges_abi import _StubGraph
+from sir_cases import StubGraph as _StubGraph
 
 
 @pytest.fixture(scope="module")
