@@ -4,6 +4,8 @@ same constructor and `run(seed_list, maxTime)`, the message passing runs in libg
     DMP_SIR(weight_adj, nodes_gamma)        weight_adj: scipy sparse / dense [n, n] (the reference passes A*beta)
         .run(seed_list, maxTime) -> float32 tensor [maxTime, n, 3] = (Ps, Pi, Pr) on the GPU
                                                 seed_list: seed ids, or an `InitialState` (an extension)
+    dmp_batch(weight_adj, starts, gamma, maxTime, scale=None) -> float32 tensor [B, maxTime, n, 3] (an extension): B
+                                                samples on one graph in one library call, each its solo run's bits
 """
 from __future__ import annotations
 
@@ -53,3 +55,82 @@ class DMP_SIR:
 
     def output(self):
         return self.marginals
+
+
+class DmpGraph:
+    """One weighted adjacency prepared for several `dmp_batch` calls: the sorted CSR on the host, and the graph handle, made
+    on first use and kept.  `dmp_batch` takes it wherever it takes a matrix."""
+
+    def __init__(self, weight_adj):
+        A = sp.csr_matrix(weight_adj)
+        A.sort_indices()
+        self.N, self.E = int(A.shape[0]), int(A.nnz)
+        self.indptr, self.indices = A.indptr.astype(np.int32), A.indices.astype(np.int32)
+        self.data = np.ascontiguousarray(A.data, dtype=np.float64)
+        self._graph = None
+
+    @property
+    def graph(self):
+        if self._graph is None:
+            self._graph = DeviceGraph(self.indptr, self.indices)
+        return self._graph
+
+
+def _batch_numbers(name, value, shapes):
+    """`value` as a float64 host array of one of `shapes`, every entry finite and >= 0; ValueError otherwise."""
+    if isinstance(value, torch.Tensor):
+        value = value.detach().cpu().numpy()
+    try:
+        a = np.asarray(value, dtype=np.float64)
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"dmp_batch: {name} is not an array of numbers ({e})") from None
+    if a.shape not in shapes:
+        raise ValueError(f"dmp_batch: {name} must have one of the shapes {shapes}, got {tuple(a.shape)}")
+    if not ((a >= 0.0) & np.isfinite(a)).all():                     # a NaN fails the comparison
+        raise ValueError(f"dmp_batch: {name} holds an entry that is not a finite number >= 0")
+    return a
+
+
+def dmp_batch(weight_adj, starts, gamma, maxTime, scale=None, device="cuda"):
+    """`DMP_SIR.run` for B samples on one graph in ONE library call (`gnode_dmp_batch_f32`): a float32 device tensor
+    [B, maxTime, n, 3] = (Ps, Pi, Pr).  DMP is a fixed recurrence and no sample reads another's numbers, so row b is bit for bit
+    what `DMP_SIR(weight_adj * scale[b], gamma_b).run(starts[b], maxTime)` returns.
+
+    weight_adj: one matrix, as `DMP_SIR` takes, or a `DmpGraph` made from one (its graph handle then serves every call).
+    starts: B seed lists and / or `InitialState`s.  scale: None -- the B samples share the matrix's weights -- or B numbers:
+    sample b's weights are float32(float64(data) * scale[b]).  gamma: a number, per-node values [n], [B, n], or B numbers, one
+    per sample (a 1-D value of length n is per node, also where B == n).  gamma and scale are finite and >= 0.  What is wrong
+    raises ValueError before the library is loaded or a graph handle is made."""
+    from .ode_nn import InitialState
+    G = weight_adj if isinstance(weight_adj, DmpGraph) else DmpGraph(weight_adj)
+    starts = list(starts)
+    n, nnz, B, T = G.N, G.E, len(starts), int(maxTime)
+    if B < 1:
+        raise ValueError("dmp_batch: need at least one start")
+    if T < 2:
+        raise ValueError(f"dmp_batch: maxTime must be >= 2 (got {maxTime})")
+    init = np.empty((B, n, 3), dtype=np.float32)
+    for b, start in enumerate(starts):
+        if isinstance(start, InitialState):
+            if start.n != n:
+                raise ValueError(f"InitialState of {start.n} nodes given for a graph of {n}")
+        else:
+            start = InitialState.from_sets(n, list(start))          # (a seed outside the graph: ValueError)
+        init[b] = start.p.astype(np.float32)
+    g = _batch_numbers("gamma", gamma, [(), (n,), (B, n), (B,)])
+    if g.shape == (B,) and g.shape != (n,):
+        g = np.repeat(g[:, None], n, axis=1)
+    gam = np.ascontiguousarray(np.broadcast_to(g, (n,)) if g.ndim < 2 else g, dtype=np.float32)
+    if scale is None:
+        w = G.data.astype(np.float32)
+    else:
+        sc = _batch_numbers("scale", scale, [(B,)])
+        w = (G.data[None, :] * sc[:, None]).astype(np.float32)
+    lib, handle = _lib.load(), G.graph.handle
+    up = lambda a: None if a.size == 0 else torch.from_numpy(np.ascontiguousarray(a)).to(device)      # noqa: E731  (no edge, no table)
+    wd, gd, y0 = up(w), up(gam), up(init)
+    out = torch.empty((B, T, n, 3), dtype=torch.float32, device=y0.device)
+    ws = torch.empty(lib.gnode_dmp_batch_workspace_bytes(handle, B), dtype=torch.uint8, device=y0.device)
+    _lib.check(lib.gnode_dmp_batch_f32(handle, _lib.ptr(wd), nnz if w.ndim == 2 else 0, _lib.ptr(gd), n if gam.ndim == 2 else 0,
+                                       _lib.ptr(y0), B, T, _lib.ptr(out), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()))
+    return out

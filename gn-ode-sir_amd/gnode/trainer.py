@@ -465,8 +465,10 @@ def runge_kutta_baseline(A, args, test_ids, ys):
 def main_dmp(argv=None):
     """What monitorer-sim.py spawns for model='dmp' (monitorer-sim.py:30-31): same argv and label / initial-* files
     as the single-graph script; runs `DMP_SIR(A*beta, [gamma]*n).run(seeds, maxTime)` on every test sample and
-    prints the element-weighted L1 against the Monte-Carlo labels (dmp.py:345-364; the reference saves nothing)."""
-    from .dmp import DMP_SIR
+    prints the element-weighted L1 against the Monte-Carlo labels (dmp.py:345-364; the reference saves nothing).
+    The samples go through `dmp_batch` in chunks of at most 64 on one graph handle: each sample's bits, and so every
+    printed loss, are its solo `DMP_SIR` run's."""
+    from .dmp import DmpGraph, dmp_batch
     args = parser_single().parse_args(argv)
     G, A, _ = create_graph(50, args.dataset, cache=_graph_cache())
     n_nodes = A.shape[0]
@@ -479,15 +481,21 @@ def main_dmp(argv=None):
     import scipy.sparse as sp
     A1 = sp.csr_matrix(A).astype(np.float64)
     A1.data[:] = 1.0                                              # the reference multiplies the 0/1 adjacency by beta (:349)
+    graph = DmpGraph(A1)
+    te = list(te)
     t0, loss_all, items = time.time(), 0.0, 0
-    for i in te:
-        print("dmp")
-        out = DMP_SIR(A1 * args.beta[i], [args.gamma[i]] * n_nodes).run(args.I_indices[i], args.maxTime).cpu().numpy()
-        loss = float(np.abs(out[1:].astype(np.float64) - ys[i][1:]).mean())
-        cnt = 3 * n_nodes * (args.maxTime - 1)
-        loss_all += loss * cnt
-        items += cnt
-        print(loss)
+    for c0 in range(0, len(te), 64):
+        chunk = te[c0:c0 + 64]
+        gam = np.repeat(np.asarray([args.gamma[i] for i in chunk], dtype=np.float64)[:, None], n_nodes, axis=1)
+        outs = dmp_batch(graph, [args.I_indices[i] for i in chunk], gam, args.maxTime,
+                         scale=[args.beta[i] for i in chunk]).cpu().numpy()
+        for i, out in zip(chunk, outs):
+            print("dmp")
+            loss = float(np.abs(out[1:].astype(np.float64) - ys[i][1:]).mean())
+            cnt = 3 * n_nodes * (args.maxTime - 1)
+            loss_all += loss * cnt
+            items += cnt
+            print(loss)
     test_loss = loss_all / max(items, 1)
     print("DMP baseline Loss: {:.5f}".format(test_loss))
     print("Time inference baseline: {:.5f}".format(time.time() - t0))

@@ -20,7 +20,7 @@
  *     into a hipGraph on first use and one handle may serve several streams (each
  *     with its own workspace).  Functions that DO synchronise `stream` say so below
  *     (gnode_graph_create, gnode_sir_mc_philox with more than 32 seeds,
- *     gnode_sir_mc_philox_nodes, gnode_sir_mc_philox_edges, gnode_sir_mc_philox_traj_edges, gnode_sir_mc_philox_traj with more than 32 seeds or rate arrays, gnode_sir_mc_philox_init, gnode_sir_mc_coins, gnode_dmp_f32, gnode_dmp_init_f32, gnode_meanfield_f64, gnode_meanfield_init_f64, gnode_meanfield_rates_f64).
+ *     gnode_sir_mc_philox_nodes, gnode_sir_mc_philox_edges, gnode_sir_mc_philox_traj_edges, gnode_sir_mc_philox_traj with more than 32 seeds or rate arrays, gnode_sir_mc_philox_init, gnode_sir_mc_coins, gnode_dmp_f32, gnode_dmp_init_f32, gnode_dmp_batch_f32, gnode_meanfield_f64, gnode_meanfield_init_f64, gnode_meanfield_rates_f64).
  *   - process-wide state: (1) a per-device "set up once" table (compute-unit count,
  *     dynamic-LDS kernel attributes), written under a lock by the first
  *     gnode_graph_create on a device and read-only afterwards; (2) the opt-in
@@ -478,6 +478,28 @@ size_t gnode_dmp_init_workspace_bytes(gnode_graph_t g);
 int gnode_dmp_init_f32(gnode_graph_t g, const float* weights, const float* gamma,
                        const float* init /* device fp32 [n][3] */, int32_t maxTime, float* out,
                        void* workspace, size_t workspace_bytes, void* stream);
+/* gnode_dmp_init_f32 for B samples on one graph in one call.  Sample b starts from init[b], with the weights at
+ * weights + b * w_stride and the recovery probabilities at gamma + b * gamma_stride: a stride of 0 shares one table among
+ * the samples, the other legal value is the table's length (nnz, n).  Every sample's arithmetic is gnode_dmp_init_f32's, in
+ * the same per-element order (P_k multiplies over row k in ascending position from 1.0f), and no sample reads another's
+ * numbers: out[b] is bit for bit what gnode_dmp_init_f32 returns for sample b's weights, gamma and state.
+ *   weights   device fp32 [nnz] (w_stride 0) or [B][nnz] (w_stride nnz); may be NULL when nnz = 0
+ *   gamma     device fp32 [n] (gamma_stride 0) or [B][n] (gamma_stride n)
+ *   init      device fp32 [B][n][3] = (pS, pI, pR), not validated here
+ *   out       device fp32 [B][maxTime][n][3], out[b][0] = init[b]
+ * The source / reverse-edge tables are built once per call.  Two forms, chosen from the graph alone: when
+ * gnode_dmp_batch_lds_bytes(g) -- 5 edge arrays (theta twice, phi, Ps_e, rev) and 3 node arrays (P, Pi, Pr) of 4 bytes,
+ * each rounded up to 16 -- fits the 160 KiB of LDS of a gfx950 workgroup, one workgroup integrates one sample over the whole
+ * horizon from LDS, in ONE launch for the batch; otherwise the node and edge passes run over B * n rows and B * nnz edge slots
+ * of the workspace, two launches per time step whatever B is.  gnode_dmp_batch_lds_bytes and
+ * gnode_dmp_batch_workspace_bytes return 0 without a handle (the latter also for B < 1).
+ * GNODE_ERR_ARG: a null pointer, B < 1, maxTime < 2, a stride that is neither 0 nor the table's length, an asymmetric
+ * pattern; GNODE_ERR_WORKSPACE: a short workspace; nothing is written to `out` in either case.  Synchronises `stream`. */
+size_t gnode_dmp_batch_workspace_bytes(gnode_graph_t g, int32_t B);
+size_t gnode_dmp_batch_lds_bytes(gnode_graph_t g);
+int gnode_dmp_batch_f32(gnode_graph_t g, const float* weights, int64_t w_stride, const float* gamma,
+                        int64_t gamma_stride, const float* init /* device fp32 [B][n][3] */, int32_t B,
+                        int32_t maxTime, float* out, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- mean-field baseline (reference ode_nn.py:214-233) ----
  * `runge_kutta_order4(sir, A, ...)`: dS = -beta (A I) S, dI = beta (A I) S - gamma I,
