@@ -93,6 +93,17 @@ void gn_prof_end(int kind, hipStream_t st);
 
 static inline size_t gn_align(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
 
+// position of column c in row r of a CSR whose rows hold ascending columns, or -1 when (r, c) is no entry
+__device__ __forceinline__ int gn_csr_position(const int* __restrict__ rowptr, const int* __restrict__ col, int r, int c) {
+    int lo = rowptr[r], hi = rowptr[r + 1] - 1;
+    while (lo <= hi) {
+        const int mid = (lo + hi) >> 1, x = col[mid];
+        if (x == c) return mid;
+        if (x < c) lo = mid + 1; else hi = mid - 1;
+    }
+    return -1;
+}
+
 // lanes per row of the lane-group kernels: H/4 rounded up to a power of two
 static inline int gn_lpr(int H) {
     int need = H / 4, l = 1;

@@ -9,8 +9,16 @@
 //   marginals  Ps_k = Ps0_k P_k,  Pr_k += gamma_k Pi_k,  Pi_k = 1 - Ps_k - Pr_k       (:124-129, :141-145)
 // Undirected graphs only (every shipped graph is `.to_undirected()`, ode_nn.py:402): the edges INTO k are then the
 // reverses of row k's edges, so one CSR serves both directions and P_k multiplies theta_{rev(e)} over row k in
-// ascending order -- the order the reference's CPU scatter uses.  fp32 like the reference's FloatTensors; two
-// launches per time step (node pass, edge pass), theta ping-pongs because the edge pass reads its neighbours'.
+// ascending order -- the order the reference's CPU scatter uses.  fp32 like the reference's FloatTensors.
+//
+// One statement serves the three entries: B samples on one graph, sample b starting from init[b] = (pS, pI, pR) per node with
+// weights + b * w_stride and gamma + b * gamma_stride (a stride of 0 shares the table); gnode_dmp_f32 and gnode_dmp_init_f32
+// are B = 1.  The recurrence is the four dmp_* functions below and nothing else; the kernels are loops and indexing around
+// them, in two forms chosen by dmp_run:
+//   general                    four kernels over rows b * n + k and edge slots b * nnz + e of the workspace: two launches per
+//                              time step (node pass, edge pass); theta ping-pongs because the edge pass reads its neighbours'
+//   one workgroup per sample   the messages and marginals of a sample live in LDS for the whole horizon: one launch
+// A sample's numbers do not depend on the form or on B: same expressions, same per-element order.
 #include "gnode_common.h"
 #include <algorithm>
 
@@ -19,163 +27,51 @@ __global__ __launch_bounds__(256) void k_dmp_setup(const int* __restrict__ rowpt
     const int u = blockIdx.x * 256 + threadIdx.x;
     if (u >= n) return;
     for (int e = rowptr[u]; e < rowptr[u + 1]; ++e) {
-        const int v = col[e];
         src[e] = u;
-        int lo = rowptr[v], hi = rowptr[v + 1] - 1, found = -1;       // position of u in row v (sorted columns)
-        while (lo <= hi) {
-            const int mid = (lo + hi) >> 1, c = col[mid];
-            if (c == u) { found = mid; break; }
-            if (c < u) lo = mid + 1; else hi = mid - 1;
-        }
+        const int found = gn_csr_position(rowptr, col, col[e], u);
         rev[e] = found;
         if (found < 0) atomicExch(bad, 1);
     }
 }
 
-// The initial marginals of node k.  INIT = false: from the 0/1 seed vector (Ps0 = 1 - seed, Pi0 = seed, Pr0 = 0: dmp.py's
-// _set_seeds).  INIT = true (gnode_dmp_init_f32): the caller's fp32 [n][3] = (pS, pI, pR), and the message of an edge starts
-// from Phi_0 = Pi0[src] -- what 1 - Ps0 is when Pr0 = 0.  The seed instances compile to what they were.
-template <bool INIT> __device__ __forceinline__ float dmp_ps0(const float* __restrict__ s0, int k) { return INIT ? s0[(size_t)k * 3] : 1.0f - s0[k]; }
-template <bool INIT> __device__ __forceinline__ float dmp_pi0(const float* __restrict__ s0, int k) { return INIT ? s0[(size_t)k * 3 + 1] : s0[k]; }
-template <bool INIT> __device__ __forceinline__ float dmp_pr0(const float* __restrict__ s0, int k) { return INIT ? s0[(size_t)k * 3 + 2] : 0.0f; }
+// ------------------------------------------------------------------------------------------------ the recurrence, once
+// On values and on pointers that are already the sample's own, in global memory or in LDS.  The library is built with
+// -ffp-contract=off, so these round as written wherever they are inlined; their operand order is the reference's.
 
-// t = 1 (dmp.py:104-121): theta_1 = 1 - w phi_0 + 1e-10, Ps_e^{prev} = Ps0[src]
-template <bool INIT>
-__global__ __launch_bounds__(256) void k_dmp_init(const int* __restrict__ src, const float* __restrict__ w,
-                                                 const float* __restrict__ seed, long nnz, float* __restrict__ theta,
-                                                 float* __restrict__ phi, float* __restrict__ ps) {
-    const long e = (long)blockIdx.x * 256 + threadIdx.x;
-    if (e >= nnz) return;
-    const float ps0 = dmp_ps0<INIT>(seed, src[e]);
-    const float ph = INIT ? dmp_pi0<INIT>(seed, src[e]) : 1.0f - ps0;
-    theta[e] = (1.0f - w[e] * ph) + 1e-10f;
-    phi[e] = ph;
-    ps[e] = ps0;
+// t = 1 (dmp.py:104-121): theta_1 = 1 - w phi_0 + 1e-10, phi_0 = Pi0[src] (what 1 - Ps0 is when Pr0 = 0), Ps_e^{prev} = Ps0[src]
+__device__ __forceinline__ void dmp_edge_start(float ps0_u, float pi0_u, float w_e, float& theta, float& phi, float& ps) {
+    theta = (1.0f - w_e * pi0_u) + 1e-10f;
+    phi = pi0_u;
+    ps = ps0_u;
 }
 
-// node pass: P_k and the marginals of time step t
-template <bool INIT>
-__global__ __launch_bounds__(256) void k_dmp_node(const int* __restrict__ rowptr, const int* __restrict__ rev,
-                                                 const float* __restrict__ theta, const float* __restrict__ seed,
-                                                 const float* __restrict__ gamma, int n, int first, float* __restrict__ P,
-                                                 float* __restrict__ Pr, float* __restrict__ Pi, float* __restrict__ out_t) {
-    const int k = blockIdx.x * 256 + threadIdx.x;
-    if (k >= n) return;
+// P_k: theta of the reverses of row k's edges [lo, hi), in ascending position from 1
+__device__ __forceinline__ float dmp_row_product(const int* rev, const float* theta, int lo, int hi) {
     float p = 1.0f;
-    for (int e = rowptr[k]; e < rowptr[k + 1]; ++e) p = p * theta[rev[e]];
-    P[k] = p;
-    const float ps0 = dmp_ps0<INIT>(seed, k);
-    const float ps = ps0 * p;
-    const float pi_prev = first ? dmp_pi0<INIT>(seed, k) : Pi[k];
-    const float pr = (first ? dmp_pr0<INIT>(seed, k) : Pr[k]) + gamma[k] * pi_prev;
-    const float pi = 1.0f - ps - pr;
-    Pr[k] = pr; Pi[k] = pi;
-    out_t[(size_t)k * 3 + 0] = ps; out_t[(size_t)k * 3 + 1] = pi; out_t[(size_t)k * 3 + 2] = pr;
+    for (int e = lo; e < hi; ++e) p = p * theta[rev[e]];
+    return p;
 }
 
-// edge pass: Ps_e, phi_e of this step, theta of the NEXT step into the other buffer
-template <bool INIT>
-__global__ __launch_bounds__(256) void k_dmp_edge(const int* __restrict__ src, const int* __restrict__ rev,
-                                                 const float* __restrict__ w, const float* __restrict__ gamma,
-                                                 const float* __restrict__ seed, const float* __restrict__ P,
-                                                 const float* __restrict__ theta, long nnz, float* __restrict__ phi,
-                                                 float* __restrict__ ps, float* __restrict__ theta_next) {
-    const long e = (long)blockIdx.x * 256 + threadIdx.x;
-    if (e >= nnz) return;
-    const int u = src[e];
-    const float mul = P[u] / theta[rev[e]];
-    const float ps_new = dmp_ps0<INIT>(seed, u) * mul;
-    const float ph = (1.0f - w[e]) * (1.0f - gamma[u]) * phi[e] - (ps_new - ps[e]);
-    phi[e] = ph;
-    ps[e] = ps_new;
-    theta_next[e] = theta[e] - w[e] * ph;
+// the marginals of node k at this step from P_k and the previous step's Pi_k, Pr_k
+__device__ __forceinline__ void dmp_node_update(float P_k, float ps0_k, float pi_prev, float pr_prev, float gamma_k, float& ps,
+                                                float& pi, float& pr) {
+    ps = ps0_k * P_k;
+    pr = pr_prev + gamma_k * pi_prev;
+    pi = 1.0f - ps - pr;
 }
 
-template <bool INIT>
-__global__ __launch_bounds__(256) void k_dmp_out0(const float* __restrict__ seed, int n, float* __restrict__ out0) {
-    const int k = blockIdx.x * 256 + threadIdx.x;
-    if (k >= n) return;
-    out0[(size_t)k * 3 + 0] = dmp_ps0<INIT>(seed, k); out0[(size_t)k * 3 + 1] = dmp_pi0<INIT>(seed, k); out0[(size_t)k * 3 + 2] = dmp_pr0<INIT>(seed, k);
+// Ps_e and phi_e of this step (in place), theta_e of the NEXT step; `theta` is a reference so that it is loaded where it is used
+__device__ __forceinline__ void dmp_edge_update(float P_u, float theta_rev, float ps0_u, float w_e, float gamma_u, float& phi,
+                                                float& ps, const float& theta, float& theta_next) {
+    const float mul = P_u / theta_rev;
+    const float ps_new = ps0_u * mul;
+    const float ph = (1.0f - w_e) * (1.0f - gamma_u) * phi - (ps_new - ps);
+    phi = ph;
+    ps = ps_new;
+    theta_next = theta - w_e * ph;
 }
 
-extern "C" size_t gnode_dmp_workspace_bytes(gnode_graph_t g) {
-    if (!g) return 0;
-    const size_t eb = gn_align((size_t)std::max<int64_t>(g->nnz, 1) * 4), nb = gn_align((size_t)g->info.n * 4);
-    return 6 * eb + 4 * nb + 256;          // src, rev, theta x2, phi, ps | seed, P, Pr, Pi | status
-}
-extern "C" size_t gnode_dmp_init_workspace_bytes(gnode_graph_t g) { return gnode_dmp_workspace_bytes(g); }   // (the seed vector rests)
-
-// INIT = false: the seed list is staged as a 0/1 vector in the workspace.  INIT = true: `init` is the caller's device fp32
-// [n][3], read where the seed vector is.  `who`: the entry's name for the messages.
-template <bool INIT>
-static int dmp_impl(const char* who, gnode_graph_t g, const float* weights, const float* gamma, const int32_t* seeds_host,
-                    int32_t n_seeds, const float* init, int32_t maxTime, float* out, void* workspace, size_t workspace_bytes,
-                    void* stream) {
-    GN_CHECK_ARG(g && gamma && out && workspace && (INIT ? init != nullptr : (seeds_host || n_seeds == 0)), "%s: null pointer", who);
-    GN_CHECK_ARG(weights || g->nnz == 0, "%s: weights is null", who);          // no edge, no weight: an empty tensor has no address
-    GN_CHECK_ARG(maxTime >= 2, "%s: maxTime must be >= 2 (got %d)", who, maxTime);
-    for (int i = 0; i < n_seeds; ++i)
-        GN_CHECK_ARG(seeds_host[i] >= 0 && seeds_host[i] < g->info.n, "%s: seed %d out of range", who, seeds_host[i]);
-    if (workspace_bytes < gnode_dmp_workspace_bytes(g)) {
-        gnode_set_error("%s: workspace %zu < %zu", who, workspace_bytes, gnode_dmp_workspace_bytes(g));
-        return GNODE_ERR_WORKSPACE;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    const long nnz = g->nnz;
-    const int n = g->info.n;
-    const size_t eb = gn_align((size_t)std::max<int64_t>(nnz, 1) * 4), nb = gn_align((size_t)n * 4);
-    char* ws = (char*)workspace;
-    int* src = (int*)ws; int* rev = (int*)(ws + eb);
-    float* theta[2] = {(float*)(ws + 2 * eb), (float*)(ws + 3 * eb)};
-    float* phi = (float*)(ws + 4 * eb); float* ps = (float*)(ws + 5 * eb);
-    float* seed_ws = (float*)(ws + 6 * eb); float* P = (float*)(ws + 6 * eb + nb);
-    float* Pr = (float*)(ws + 6 * eb + 2 * nb); float* Pi = (float*)(ws + 6 * eb + 3 * nb);
-    int* bad = (int*)(ws + 6 * eb + 4 * nb);
-    const float* seed = INIT ? init : seed_ws;
-    if (!INIT) GN_HIP(hipMemsetAsync(seed_ws, 0, (size_t)n * 4, st));
-    GN_HIP(hipMemsetAsync(bad, 0, 4, st));
-    const float one = 1.0f;
-    for (int i = 0; i < n_seeds; ++i) GN_HIP(hipMemcpyAsync(seed_ws + seeds_host[i], &one, 4, hipMemcpyHostToDevice, st));
-    const unsigned ng = (unsigned)((n + 255) / 256), eg = (unsigned)std::max<long>(1, (nnz + 255) / 256);
-    hipLaunchKernelGGL(k_dmp_setup, dim3(ng), dim3(256), 0, st, g->rowptr, g->col, n, src, rev, bad);
-    GN_LAUNCH_CHECK();
-    int bad_h = 0;
-    GN_HIP(hipMemcpyAsync(&bad_h, bad, 4, hipMemcpyDeviceToHost, st));
-    GN_HIP(hipStreamSynchronize(st));          // also: `one` and seeds_host are done with
-    GN_CHECK_ARG(!bad_h, "%s: the sparsity pattern is not symmetric (DMP here serves undirected graphs)", who);
-    const size_t plane = (size_t)n * 3;
-    hipLaunchKernelGGL(k_dmp_out0<INIT>, dim3(ng), dim3(256), 0, st, seed, n, out);
-    hipLaunchKernelGGL(k_dmp_init<INIT>, dim3(eg), dim3(256), 0, st, src, weights, seed, nnz, theta[0], phi, ps);
-    GN_LAUNCH_CHECK();
-    for (int t = 1; t < maxTime; ++t) {
-        const int cur = (t - 1) & 1;
-        hipLaunchKernelGGL(k_dmp_node<INIT>, dim3(ng), dim3(256), 0, st, g->rowptr, rev, theta[cur], seed, gamma, n, t == 1 ? 1 : 0, P, Pr,
-                           Pi, out + (size_t)t * plane);
-        hipLaunchKernelGGL(k_dmp_edge<INIT>, dim3(eg), dim3(256), 0, st, src, rev, weights, gamma, seed, P, theta[cur], nnz, phi, ps,
-                           theta[cur ^ 1]);
-        GN_LAUNCH_CHECK();
-    }
-    return 0;
-}
-
-extern "C" int gnode_dmp_f32(gnode_graph_t g, const float* weights, const float* gamma, const int32_t* seeds_host,
-                             int32_t n_seeds, int32_t maxTime, float* out, void* workspace, size_t workspace_bytes,
-                             void* stream) {
-    return dmp_impl<false>("gnode_dmp_f32", g, weights, gamma, seeds_host, n_seeds, nullptr, maxTime, out, workspace, workspace_bytes, stream);
-}
-
-extern "C" int gnode_dmp_init_f32(gnode_graph_t g, const float* weights, const float* gamma, const float* init, int32_t maxTime,
-                                  float* out, void* workspace, size_t workspace_bytes, void* stream) {
-    return dmp_impl<true>("gnode_dmp_init_f32", g, weights, gamma, nullptr, 0, init, maxTime, out, workspace, workspace_bytes, stream);
-}
-
-// ------------------------------------------------------------------------------------------------ B samples in one call
-// gnode_dmp_batch_f32: sample b starts from init[b] with weights + b * w_stride and gamma + b * gamma_stride (a stride of 0
-// shares the table).  Every sample's arithmetic is the INIT instances' above, expression for expression, in the same
-// per-element order, so sample b's output is gnode_dmp_init_f32's for its inputs bit for bit; `src` / `rev` are built once.
-// Two forms, chosen from the graph alone (dmp_batch_one_workgroup):
-//   one workgroup per sample   the messages and marginals of a sample live in LDS for the whole horizon: one launch
-//   general                    the four kernels over rows r = b * n + k and edge slots b * nnz + e: two launches per step
+// ------------------------------------------------------------------------------------------------ the kernels
 struct DmpBatchArgs {
     const float* w; long w_stride;
     const float* gamma; long gamma_stride;
@@ -183,6 +79,15 @@ struct DmpBatchArgs {
     float* out;                         // [B][maxTime][n][3]
     int n, maxTime; long nnz;
 };
+struct DmpSample {                      // sample b's own tables: w[nnz], gamma[n], the start s0[n][3], out[maxTime][n][3]
+    const float* __restrict__ w; const float* __restrict__ gamma; const float* __restrict__ s0; float* __restrict__ out;
+};
+__device__ __forceinline__ DmpSample dmp_sample(const DmpBatchArgs& a, size_t b) {
+    return {a.w + b * a.w_stride, a.gamma + b * a.gamma_stride, a.init + b * (size_t)a.n * 3, a.out + b * (size_t)a.maxTime * a.n * 3};
+}
+__device__ __forceinline__ void dmp_store3(float* __restrict__ row, int k, float ps, float pi, float pr) {
+    row[(size_t)k * 3 + 0] = ps; row[(size_t)k * 3 + 1] = pi; row[(size_t)k * 3 + 2] = pr;
+}
 
 __host__ __device__ static inline size_t dmp_align16(size_t x) { return (x + 15) / 16 * 16; }
 static constexpr size_t kDmpLdsLimit = 160 * 1024;      // what a gfx950 workgroup may declare
@@ -205,53 +110,39 @@ __global__ __launch_bounds__(1024) void k_dmp_batch_wg(const int* __restrict__ r
                                                       const int* __restrict__ rev_g, DmpBatchArgs a) {
     extern __shared__ __attribute__((aligned(16))) char dmp_smem[];
     const int n = a.n, nnz = (int)a.nnz, tid = threadIdx.x, nt = blockDim.x;
-    const size_t b = blockIdx.x, eb = dmp_align16((size_t)nnz * 4), nb = dmp_align16((size_t)n * 4);
+    const size_t eb = dmp_align16((size_t)nnz * 4), nb = dmp_align16((size_t)n * 4);
     float* theta[2] = {(float*)dmp_smem, (float*)(dmp_smem + eb)};
     float* phi = (float*)(dmp_smem + 2 * eb); float* ps = (float*)(dmp_smem + 3 * eb);
     int* rev = (int*)(dmp_smem + 4 * eb);
     float* P = (float*)(dmp_smem + 5 * eb); float* Pi = (float*)(dmp_smem + 5 * eb + nb); float* Pr = (float*)(dmp_smem + 5 * eb + 2 * nb);
-    const float* __restrict__ w = a.w + b * a.w_stride;
-    const float* __restrict__ gamma = a.gamma + b * a.gamma_stride;
-    const float* __restrict__ s0 = a.init + b * (size_t)n * 3;
-    float* __restrict__ out = a.out + b * (size_t)a.maxTime * n * 3;
-    for (int k = tid; k < n; k += nt) {                                   // k_dmp_out0; Pi, Pr hold what `first` selects
-        const float ps0 = dmp_ps0<true>(s0, k), pi0 = dmp_pi0<true>(s0, k), pr0 = dmp_pr0<true>(s0, k);
-        out[(size_t)k * 3 + 0] = ps0; out[(size_t)k * 3 + 1] = pi0; out[(size_t)k * 3 + 2] = pr0;
+    const DmpSample s = dmp_sample(a, blockIdx.x);
+    for (int k = tid; k < n; k += nt) {                                   // output row 0; Pi, Pr hold the start for step 1
+        const float ps0 = s.s0[(size_t)k * 3], pi0 = s.s0[(size_t)k * 3 + 1], pr0 = s.s0[(size_t)k * 3 + 2];
+        dmp_store3(s.out, k, ps0, pi0, pr0);
         Pi[k] = pi0; Pr[k] = pr0;
     }
-    for (int e = tid; e < nnz; e += nt) {                                 // k_dmp_init
+    for (int e = tid; e < nnz; e += nt) {
         const int u = src[e];
-        const float ps0 = dmp_ps0<true>(s0, u), ph = dmp_pi0<true>(s0, u);
-        theta[0][e] = (1.0f - w[e] * ph) + 1e-10f;
-        phi[e] = ph;
-        ps[e] = ps0;
+        dmp_edge_start(s.s0[(size_t)u * 3], s.s0[(size_t)u * 3 + 1], s.w[e], theta[0][e], phi[e], ps[e]);
         rev[e] = rev_g[e];
     }
     __syncthreads();
     for (int t = 1; t < a.maxTime; ++t) {
         const float* th = theta[(t - 1) & 1];
         float* th_next = theta[t & 1];
-        float* __restrict__ out_t = out + (size_t)t * n * 3;
-        for (int k = tid; k < n; k += nt) {                               // k_dmp_node
-            float p = 1.0f;
-            for (int e = rowptr[k]; e < rowptr[k + 1]; ++e) p = p * th[rev[e]];
+        for (int k = tid; k < n; k += nt) {                               // node pass
+            const float p = dmp_row_product(rev, th, rowptr[k], rowptr[k + 1]);
             P[k] = p;
-            const float s = dmp_ps0<true>(s0, k) * p;
-            const float pr = Pr[k] + gamma[k] * Pi[k];
-            const float pi = 1.0f - s - pr;
+            float sk, pi, pr;
+            dmp_node_update(p, s.s0[(size_t)k * 3], Pi[k], Pr[k], s.gamma[k], sk, pi, pr);
             Pr[k] = pr; Pi[k] = pi;
-            out_t[(size_t)k * 3 + 0] = s; out_t[(size_t)k * 3 + 1] = pi; out_t[(size_t)k * 3 + 2] = pr;
+            dmp_store3(s.out + (size_t)t * n * 3, k, sk, pi, pr);
         }
         __syncthreads();                                                  // P is complete; theta[cur] is still this step's
         if (t + 1 < a.maxTime)                                            // (the last step's messages have no reader)
-            for (int e = tid; e < nnz; e += nt) {                         // k_dmp_edge
+            for (int e = tid; e < nnz; e += nt) {                         // edge pass
                 const int u = src[e];
-                const float mul = P[u] / th[rev[e]];
-                const float ps_new = dmp_ps0<true>(s0, u) * mul;
-                const float ph = (1.0f - w[e]) * (1.0f - gamma[u]) * phi[e] - (ps_new - ps[e]);
-                phi[e] = ph;
-                ps[e] = ps_new;
-                th_next[e] = th[e] - w[e] * ph;
+                dmp_edge_update(P[u], th[rev[e]], s.s0[(size_t)u * 3], s.w[e], s.gamma[u], phi[e], ps[e], th[e], th_next[e]);
             }
         __syncthreads();                                                  // theta[next] is complete before its node pass
     }
@@ -260,12 +151,17 @@ __global__ __launch_bounds__(1024) void k_dmp_batch_wg(const int* __restrict__ r
 // The general form: `per` blocks of 256 per sample, sample b = blockIdx.x / per.  Per-sample state is at row b * n + k and
 // edge slot b * nnz + e of the workspace arrays.
 __global__ __launch_bounds__(256) void k_dmp_batch_out0(DmpBatchArgs a, unsigned per) {
-    const size_t b = blockIdx.x / per;
     const int k = (int)(blockIdx.x % per) * 256 + threadIdx.x;
     if (k >= a.n) return;
-    const float* __restrict__ s0 = a.init + b * (size_t)a.n * 3;
-    float* __restrict__ out0 = a.out + b * (size_t)a.maxTime * a.n * 3;
-    out0[(size_t)k * 3 + 0] = dmp_ps0<true>(s0, k); out0[(size_t)k * 3 + 1] = dmp_pi0<true>(s0, k); out0[(size_t)k * 3 + 2] = dmp_pr0<true>(s0, k);
+    const DmpSample s = dmp_sample(a, blockIdx.x / per);
+    dmp_store3(s.out, k, s.s0[(size_t)k * 3], s.s0[(size_t)k * 3 + 1], s.s0[(size_t)k * 3 + 2]);
+}
+
+// gnode_dmp_f32's start: the state of a 0/1 seed vector is (1 - seed, seed, 0) (dmp.py's _set_seeds), exact in fp32.  It IS
+// output row 0, and the run reads it back from there as its `init`.
+__global__ __launch_bounds__(256) void k_dmp_seed_out0(const float* __restrict__ seed, int n, float* __restrict__ out0) {
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    if (k < n) dmp_store3(out0, k, 1.0f - seed[k], seed[k], 0.0f);
 }
 
 __global__ __launch_bounds__(256) void k_dmp_batch_init(const int* __restrict__ src, DmpBatchArgs a, unsigned per,
@@ -273,13 +169,9 @@ __global__ __launch_bounds__(256) void k_dmp_batch_init(const int* __restrict__ 
     const size_t b = blockIdx.x / per;
     const long e = (long)(blockIdx.x % per) * 256 + threadIdx.x;
     if (e >= a.nnz) return;
-    const float* __restrict__ s0 = a.init + b * (size_t)a.n * 3;
-    const size_t slot = b * (size_t)a.nnz + e;
-    const float ps0 = dmp_ps0<true>(s0, src[e]);
-    const float ph = dmp_pi0<true>(s0, src[e]);
-    theta[slot] = (1.0f - a.w[b * a.w_stride + e] * ph) + 1e-10f;
-    phi[slot] = ph;
-    ps[slot] = ps0;
+    const DmpSample s = dmp_sample(a, b);
+    const size_t slot = b * (size_t)a.nnz + e, u = src[e];
+    dmp_edge_start(s.s0[u * 3], s.s0[u * 3 + 1], s.w[e], theta[slot], phi[slot], ps[slot]);
 }
 
 __global__ __launch_bounds__(256) void k_dmp_batch_node(const int* __restrict__ rowptr, const int* __restrict__ rev,
@@ -288,20 +180,15 @@ __global__ __launch_bounds__(256) void k_dmp_batch_node(const int* __restrict__ 
     const size_t b = blockIdx.x / per;
     const int k = (int)(blockIdx.x % per) * 256 + threadIdx.x;
     if (k >= a.n) return;
-    const float* __restrict__ s0 = a.init + b * (size_t)a.n * 3;
-    const float* __restrict__ th = theta + b * (size_t)a.nnz;
+    const DmpSample s = dmp_sample(a, b);
     const size_t r = b * (size_t)a.n + k;
-    float p = 1.0f;
-    for (int e = rowptr[k]; e < rowptr[k + 1]; ++e) p = p * th[rev[e]];
+    const float p = dmp_row_product(rev, theta + b * (size_t)a.nnz, rowptr[k], rowptr[k + 1]);
     P[r] = p;
-    const float ps0 = dmp_ps0<true>(s0, k);
-    const float s = ps0 * p;
-    const float pi_prev = t == 1 ? dmp_pi0<true>(s0, k) : Pi[r];
-    const float pr = (t == 1 ? dmp_pr0<true>(s0, k) : Pr[r]) + a.gamma[b * a.gamma_stride + k] * pi_prev;
-    const float pi = 1.0f - s - pr;
+    float sk, pi, pr;                                                     // step 1 starts from the state itself
+    dmp_node_update(p, s.s0[(size_t)k * 3], t == 1 ? s.s0[(size_t)k * 3 + 1] : Pi[r], t == 1 ? s.s0[(size_t)k * 3 + 2] : Pr[r], s.gamma[k],
+                    sk, pi, pr);
     Pr[r] = pr; Pi[r] = pi;
-    float* __restrict__ out_t = a.out + (b * (size_t)a.maxTime + t) * a.n * 3;
-    out_t[(size_t)k * 3 + 0] = s; out_t[(size_t)k * 3 + 1] = pi; out_t[(size_t)k * 3 + 2] = pr;
+    dmp_store3(s.out + (size_t)t * a.n * 3, k, sk, pi, pr);
 }
 
 __global__ __launch_bounds__(256) void k_dmp_batch_edge(const int* __restrict__ src, const int* __restrict__ rev,
@@ -311,16 +198,12 @@ __global__ __launch_bounds__(256) void k_dmp_batch_edge(const int* __restrict__ 
     const size_t b = blockIdx.x / per;
     const long e = (long)(blockIdx.x % per) * 256 + threadIdx.x;
     if (e >= a.nnz) return;
-    const float* __restrict__ s0 = a.init + b * (size_t)a.n * 3;
+    const DmpSample s = dmp_sample(a, b);
     const size_t base = b * (size_t)a.nnz, slot = base + e;
     const int u = src[e];
-    const float we = a.w[b * a.w_stride + e];
-    const float mul = P[b * (size_t)a.n + u] / theta[base + rev[e]];
-    const float ps_new = dmp_ps0<true>(s0, u) * mul;
-    const float ph = (1.0f - we) * (1.0f - a.gamma[b * a.gamma_stride + u]) * phi[slot] - (ps_new - ps[slot]);
-    phi[slot] = ph;
-    ps[slot] = ps_new;
-    theta_next[slot] = theta[slot] - we * ph;
+    const float w_e = s.w[e];
+    dmp_edge_update(P[b * (size_t)a.n + u], theta[base + rev[e]], s.s0[(size_t)u * 3], w_e, s.gamma[u], phi[slot], ps[slot],
+                    theta[slot], theta_next[slot]);
 }
 
 int gn_dmp_set_attributes() {       // once per device, from gnode_graph_create
@@ -328,67 +211,120 @@ int gn_dmp_set_attributes() {       // once per device, from gnode_graph_create
     return 0;
 }
 
-// src, rev | status, and for the general form theta x2, phi, ps over B * nnz slots and P, Pr, Pi over B * n rows
+// ------------------------------------------------------------------------------------------------ the host side, once
+// The workspace of a call: src, rev | status; for the general form theta x2, phi, ps over B * nnz edge slots and P, Pr, Pi over
+// B * n rows; for the solo entries the 0/1 seed vector after them.  With `base` null only `bytes` means anything.
+struct DmpWorkspace {
+    int *src, *rev, *bad;
+    float *theta[2], *phi, *ps, *P, *Pr, *Pi, *seed;
+    size_t bytes;
+};
+static DmpWorkspace dmp_carve(gnode_graph_t g, size_t B, bool general, bool seed_vector, void* base) {
+    const size_t edges = (size_t)std::max<int64_t>(g->nnz, 1), eb = gn_align(edges * 4);
+    const size_t EB = general ? gn_align(B * edges * 4) : 0, NB = general ? gn_align(B * (size_t)g->info.n * 4) : 0;
+    size_t at = 0;
+    auto take = [&](size_t bytes) { char* p = base ? (char*)base + at : nullptr; at += bytes; return p; };
+    DmpWorkspace w;
+    w.src = (int*)take(eb); w.rev = (int*)take(eb); w.bad = (int*)take(256);
+    w.theta[0] = (float*)take(EB); w.theta[1] = (float*)take(EB); w.phi = (float*)take(EB); w.ps = (float*)take(EB);
+    w.P = (float*)take(NB); w.Pr = (float*)take(NB); w.Pi = (float*)take(NB);
+    w.seed = (float*)take(seed_vector ? gn_align((size_t)g->info.n * 4) : 0);
+    w.bytes = at;
+    return w;
+}
+// A solo call is always the general form (dmp_run), and both solo entries ask for the seed vector's room: 6 eb + 4 nb + 256.
+extern "C" size_t gnode_dmp_workspace_bytes(gnode_graph_t g) { return g ? dmp_carve(g, 1, true, true, nullptr).bytes : 0; }
+extern "C" size_t gnode_dmp_init_workspace_bytes(gnode_graph_t g) { return gnode_dmp_workspace_bytes(g); }   // (the seed vector rests)
 extern "C" size_t gnode_dmp_batch_workspace_bytes(gnode_graph_t g, int32_t B) {
-    if (!g || B < 1) return 0;
-    const size_t eb = gn_align((size_t)std::max<int64_t>(g->nnz, 1) * 4);
-    if (dmp_batch_one_workgroup(g)) return 2 * eb + 256;
-    return 2 * eb + 256 + 4 * gn_align((size_t)B * (size_t)std::max<int64_t>(g->nnz, 1) * 4) + 3 * gn_align((size_t)B * (size_t)g->info.n * 4);
+    return g && B >= 1 ? dmp_carve(g, (size_t)B, !dmp_batch_one_workgroup(g), false, nullptr).bytes : 0;
+}
+
+// what every entry checks first; `who`: the entry's name for the messages, `start`: whether its start state is there
+static int dmp_check_args(const char* who, gnode_graph_t g, const float* weights, const float* gamma, bool start, int32_t maxTime,
+                          const float* out, const void* workspace) {
+    GN_CHECK_ARG(g && gamma && start && out && workspace, "%s: null pointer", who);
+    GN_CHECK_ARG(weights || g->nnz == 0, "%s: weights is null", who);          // no edge, no weight: an empty tensor has no address
+    GN_CHECK_ARG(maxTime >= 2, "%s: maxTime must be >= 2 (got %d)", who, maxTime);
+    return 0;
+}
+
+// B samples (arguments checked by the entry).  `solo`: one of the two solo entries, which take the general form at every
+// size and carve the solo workspace.  init == nullptr: gnode_dmp_f32, whose n_seeds seeds become output row 0, the run's init.
+static int dmp_run(const char* who, gnode_graph_t g, const float* weights, long w_stride, const float* gamma, long gamma_stride,
+                   const float* init, const int32_t* seeds_host, int32_t n_seeds, int32_t B, int32_t maxTime, float* out, bool solo,
+                   void* workspace, size_t workspace_bytes, void* stream) {
+    const long nnz = g->nnz;
+    const int n = g->info.n;
+    const unsigned ng = (unsigned)((n + 255) / 256), eg = (unsigned)std::max<long>(1, (nnz + 255) / 256);
+    const bool one_wg = !solo && dmp_batch_one_workgroup(g);
+    GN_CHECK_ARG(one_wg || (size_t)B * std::max(ng, eg) < ((size_t)1 << 31), "%s: B = %d is too many samples for this graph", who, B);
+    const DmpWorkspace ws = dmp_carve(g, (size_t)B, !one_wg, solo, workspace);
+    if (workspace_bytes < ws.bytes) {
+        gnode_set_error("%s: workspace %zu < %zu", who, workspace_bytes, ws.bytes);
+        return GNODE_ERR_WORKSPACE;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const float one = 1.0f;
+    if (!init) {
+        GN_HIP(hipMemsetAsync(ws.seed, 0, (size_t)n * 4, st));
+        for (int i = 0; i < n_seeds; ++i) GN_HIP(hipMemcpyAsync(ws.seed + seeds_host[i], &one, 4, hipMemcpyHostToDevice, st));
+    }
+    GN_HIP(hipMemsetAsync(ws.bad, 0, 4, st));
+    hipLaunchKernelGGL(k_dmp_setup, dim3(ng), dim3(256), 0, st, g->rowptr, g->col, n, ws.src, ws.rev, ws.bad);
+    GN_LAUNCH_CHECK();
+    int bad_h = 0;
+    GN_HIP(hipMemcpyAsync(&bad_h, ws.bad, 4, hipMemcpyDeviceToHost, st));
+    GN_HIP(hipStreamSynchronize(st));          // also: `one` and seeds_host are done with
+    GN_CHECK_ARG(!bad_h, "%s: the sparsity pattern is not symmetric (DMP here serves undirected graphs)", who);
+    const DmpBatchArgs a = {weights, w_stride, gamma, gamma_stride, init ? init : out, out, n, maxTime, nnz};
+    if (one_wg) {
+        const long most = std::max<long>(n, nnz);
+        const unsigned threads = (unsigned)std::min<long>(1024, std::max<long>(64, (most + 63) / 64 * 64));
+        hipLaunchKernelGGL(k_dmp_batch_wg, dim3((unsigned)B), dim3(threads), gnode_dmp_batch_lds_bytes(g), st, g->rowptr, ws.src, ws.rev, a);
+        GN_LAUNCH_CHECK();
+        return 0;
+    }
+    const dim3 gn((unsigned)B * ng), ge((unsigned)B * eg);
+    if (init) hipLaunchKernelGGL(k_dmp_batch_out0, gn, dim3(256), 0, st, a, ng);
+    else hipLaunchKernelGGL(k_dmp_seed_out0, gn, dim3(256), 0, st, ws.seed, n, out);
+    hipLaunchKernelGGL(k_dmp_batch_init, ge, dim3(256), 0, st, ws.src, a, eg, ws.theta[0], ws.phi, ws.ps);
+    GN_LAUNCH_CHECK();
+    for (int t = 1; t < maxTime; ++t) {
+        const int cur = (t - 1) & 1;
+        hipLaunchKernelGGL(k_dmp_batch_node, gn, dim3(256), 0, st, g->rowptr, ws.rev, ws.theta[cur], a, ng, t, ws.P, ws.Pr, ws.Pi);
+        if (t + 1 < maxTime)                 // (the last step's messages have no reader)
+            hipLaunchKernelGGL(k_dmp_batch_edge, ge, dim3(256), 0, st, ws.src, ws.rev, ws.P, ws.theta[cur], a, eg, ws.phi, ws.ps, ws.theta[cur ^ 1]);
+        GN_LAUNCH_CHECK();
+    }
+    return 0;
+}
+
+extern "C" int gnode_dmp_f32(gnode_graph_t g, const float* weights, const float* gamma, const int32_t* seeds_host,
+                             int32_t n_seeds, int32_t maxTime, float* out, void* workspace, size_t workspace_bytes,
+                             void* stream) {
+    const char* who = "gnode_dmp_f32";
+    if (int rc = dmp_check_args(who, g, weights, gamma, seeds_host || n_seeds == 0, maxTime, out, workspace)) return rc;
+    for (int i = 0; i < n_seeds; ++i)
+        GN_CHECK_ARG(seeds_host[i] >= 0 && seeds_host[i] < g->info.n, "%s: seed %d out of range", who, seeds_host[i]);
+    return dmp_run(who, g, weights, 0, gamma, 0, nullptr, seeds_host, n_seeds, 1, maxTime, out, true, workspace, workspace_bytes, stream);
+}
+
+extern "C" int gnode_dmp_init_f32(gnode_graph_t g, const float* weights, const float* gamma, const float* init, int32_t maxTime,
+                                  float* out, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* who = "gnode_dmp_init_f32";
+    if (int rc = dmp_check_args(who, g, weights, gamma, init != nullptr, maxTime, out, workspace)) return rc;
+    return dmp_run(who, g, weights, 0, gamma, 0, init, nullptr, 0, 1, maxTime, out, true, workspace, workspace_bytes, stream);
 }
 
 extern "C" int gnode_dmp_batch_f32(gnode_graph_t g, const float* weights, int64_t w_stride, const float* gamma, int64_t gamma_stride,
                                    const float* init, int32_t B, int32_t maxTime, float* out, void* workspace,
                                    size_t workspace_bytes, void* stream) {
     const char* who = "gnode_dmp_batch_f32";
-    GN_CHECK_ARG(g && gamma && init && out && workspace, "%s: null pointer", who);
-    GN_CHECK_ARG(weights || g->nnz == 0, "%s: weights is null", who);
+    if (int rc = dmp_check_args(who, g, weights, gamma, init != nullptr, maxTime, out, workspace)) return rc;
     GN_CHECK_ARG(B >= 1, "%s: B must be >= 1 (got %d)", who, B);
-    GN_CHECK_ARG(maxTime >= 2, "%s: maxTime must be >= 2 (got %d)", who, maxTime);
-    const long nnz = g->nnz;
-    const int n = g->info.n;
-    GN_CHECK_ARG(w_stride == 0 || w_stride == nnz, "%s: w_stride must be 0 or nnz = %ld (got %lld)", who, nnz, (long long)w_stride);
-    GN_CHECK_ARG(gamma_stride == 0 || gamma_stride == n, "%s: gamma_stride must be 0 or n = %d (got %lld)", who, n, (long long)gamma_stride);
-    const unsigned ng = (unsigned)((n + 255) / 256), eg = (unsigned)std::max<long>(1, (nnz + 255) / 256);
-    const bool one_wg = dmp_batch_one_workgroup(g);
-    GN_CHECK_ARG(one_wg || (size_t)B * std::max(ng, eg) < ((size_t)1 << 31), "%s: B = %d is too many samples for this graph", who, B);
-    if (workspace_bytes < gnode_dmp_batch_workspace_bytes(g, B)) {
-        gnode_set_error("%s: workspace %zu < %zu", who, workspace_bytes, gnode_dmp_batch_workspace_bytes(g, B));
-        return GNODE_ERR_WORKSPACE;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    const size_t eb = gn_align((size_t)std::max<long>(nnz, 1) * 4);
-    char* ws = (char*)workspace;
-    int* src = (int*)ws; int* rev = (int*)(ws + eb); int* bad = (int*)(ws + 2 * eb);
-    GN_HIP(hipMemsetAsync(bad, 0, 4, st));
-    hipLaunchKernelGGL(k_dmp_setup, dim3(ng), dim3(256), 0, st, g->rowptr, g->col, n, src, rev, bad);
-    GN_LAUNCH_CHECK();
-    int bad_h = 0;
-    GN_HIP(hipMemcpyAsync(&bad_h, bad, 4, hipMemcpyDeviceToHost, st));
-    GN_HIP(hipStreamSynchronize(st));
-    GN_CHECK_ARG(!bad_h, "%s: the sparsity pattern is not symmetric (DMP here serves undirected graphs)", who);
-    const DmpBatchArgs a = {weights, (long)w_stride, gamma, (long)gamma_stride, init, out, n, maxTime, nnz};
-    if (one_wg) {
-        const long most = std::max<long>(n, nnz);
-        const unsigned threads = (unsigned)std::min<long>(1024, std::max<long>(64, (most + 63) / 64 * 64));
-        hipLaunchKernelGGL(k_dmp_batch_wg, dim3((unsigned)B), dim3(threads), gnode_dmp_batch_lds_bytes(g), st, g->rowptr, src, rev, a);
-        GN_LAUNCH_CHECK();
-    } else {
-        const size_t EB = gn_align((size_t)B * (size_t)std::max<long>(nnz, 1) * 4), NB = gn_align((size_t)B * (size_t)n * 4);
-        char* per_sample = ws + 2 * eb + 256;
-        float* theta[2] = {(float*)per_sample, (float*)(per_sample + EB)};
-        float* phi = (float*)(per_sample + 2 * EB); float* ps = (float*)(per_sample + 3 * EB);
-        float* P = (float*)(per_sample + 4 * EB); float* Pr = (float*)(per_sample + 4 * EB + NB); float* Pi = (float*)(per_sample + 4 * EB + 2 * NB);
-        const dim3 gn((unsigned)B * ng), ge((unsigned)B * eg);
-        hipLaunchKernelGGL(k_dmp_batch_out0, gn, dim3(256), 0, st, a, ng);
-        hipLaunchKernelGGL(k_dmp_batch_init, ge, dim3(256), 0, st, src, a, eg, theta[0], phi, ps);
-        GN_LAUNCH_CHECK();
-        for (int t = 1; t < maxTime; ++t) {
-            const int cur = (t - 1) & 1;
-            hipLaunchKernelGGL(k_dmp_batch_node, gn, dim3(256), 0, st, g->rowptr, rev, theta[cur], a, ng, t, P, Pr, Pi);
-            if (t + 1 < maxTime)                 // (the last step's messages have no reader)
-                hipLaunchKernelGGL(k_dmp_batch_edge, ge, dim3(256), 0, st, src, rev, P, theta[cur], a, eg, phi, ps, theta[cur ^ 1]);
-            GN_LAUNCH_CHECK();
-        }
-    }
-    return 0;
+    GN_CHECK_ARG(w_stride == 0 || w_stride == g->nnz, "%s: w_stride must be 0 or nnz = %ld (got %lld)", who, (long)g->nnz, (long long)w_stride);
+    GN_CHECK_ARG(gamma_stride == 0 || gamma_stride == g->info.n, "%s: gamma_stride must be 0 or n = %d (got %lld)", who, g->info.n,
+                 (long long)gamma_stride);
+    return dmp_run(who, g, weights, (long)w_stride, gamma, (long)gamma_stride, init, nullptr, 0, B, maxTime, out, false, workspace,
+                   workspace_bytes, stream);
 }

@@ -55,19 +55,13 @@ __global__ __launch_bounds__(256) void k_mf_rhs_rates(const int* __restrict__ ro
 }
 
 // w_in[p] = w[rev(p)]: the weight of the contact col[p] -> v for position p of row v (w is source = row, target = column).
-// The reverse-position search of k_dmp_setup; a self-loop is its own reverse.
+// The reverse position is k_dmp_setup's (gn_csr_position); a self-loop is its own reverse.
 __global__ __launch_bounds__(256) void k_mf_w_in(const int* __restrict__ rowptr, const int* __restrict__ col, int n,
                                                 const double* __restrict__ w, double* __restrict__ w_in, int* __restrict__ bad) {
     const int v = blockIdx.x * 256 + threadIdx.x;
     if (v >= n) return;
     for (int p = rowptr[v]; p < rowptr[v + 1]; ++p) {
-        const int u = col[p];
-        int lo = rowptr[u], hi = rowptr[u + 1] - 1, found = -1;       // position of v in row u (sorted columns)
-        while (lo <= hi) {
-            const int mid = (lo + hi) >> 1, c = col[mid];
-            if (c == v) { found = mid; break; }
-            if (c < v) lo = mid + 1; else hi = mid - 1;
-        }
+        const int found = gn_csr_position(rowptr, col, col[p], v);
         w_in[p] = found < 0 ? 0.0 : w[found];
         if (found < 0) atomicExch(bad, 1);
     }

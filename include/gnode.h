@@ -464,6 +464,8 @@ int gnode_sir_mc_coins(const int32_t* table_src, const int32_t* table_dst, int64
  *   gamma     device fp32 [n]     recovery probability of each node (dmp.py:349)
  *   out       device fp32 [maxTime, n, 3] = (Ps, Pi, Pr), row 0 = initial state
  *                                 (`DMP_SIR.output()`, dmp.py:159-162)
+ * The seed list is the state (1 - seed, seed, 0) per node: it is written to out row 0, and the call is
+ * gnode_dmp_batch_f32's general form with B = 1 reading its start from there.
  * Synchronises `stream` (host arrays are staged through the workspace).
  * Not on the `model='ode_nn'` path: a comparison column of the paper. */
 size_t gnode_dmp_workspace_bytes(gnode_graph_t g);
@@ -473,16 +475,19 @@ int gnode_dmp_f32(gnode_graph_t g, const float* weights, const float* gamma, con
 /* gnode_dmp_f32 from an initial-state distribution instead of a seed list: init is device fp32 [n][3] = (pS, pI, pR) per
  * node (not validated here: it lives on the device).  Ps_0 = pS, Pi_0 = pI, Pr_0 = pR, the message of edge (i -> j) starts from
  * Phi_0 = Pi_0[i] (the reference's 1 - Ps_0[i] is the same number when pR = 0), Pr_1 = Pr_0 + gamma Pi_0, everything after
- * that as gnode_dmp_f32, the 1e-10 offset included: a one-hot seed state returns gnode_dmp_f32's output bit for bit. */
+ * that as gnode_dmp_f32, the 1e-10 offset included: a one-hot seed state returns gnode_dmp_f32's output bit for bit.  It is
+ * gnode_dmp_batch_f32's general form with B = 1, at every graph size. */
 size_t gnode_dmp_init_workspace_bytes(gnode_graph_t g);
 int gnode_dmp_init_f32(gnode_graph_t g, const float* weights, const float* gamma,
                        const float* init /* device fp32 [n][3] */, int32_t maxTime, float* out,
                        void* workspace, size_t workspace_bytes, void* stream);
-/* gnode_dmp_init_f32 for B samples on one graph in one call.  Sample b starts from init[b], with the weights at
+/* The recurrence for B samples on one graph in one call.  Sample b starts from init[b], with the weights at
  * weights + b * w_stride and the recovery probabilities at gamma + b * gamma_stride: a stride of 0 shares one table among
- * the samples, the other legal value is the table's length (nnz, n).  Every sample's arithmetic is gnode_dmp_init_f32's, in
- * the same per-element order (P_k multiplies over row k in ascending position from 1.0f), and no sample reads another's
- * numbers: out[b] is bit for bit what gnode_dmp_init_f32 returns for sample b's weights, gamma and state.
+ * the samples, the other legal value is the table's length (nnz, n).  The library states the recurrence once, for every entry
+ * and both forms below, in one per-element order (P_k multiplies over row k in ascending position from 1.0f), and no sample
+ * reads another's numbers: out[b] is bit for bit what gnode_dmp_init_f32 returns for sample b's weights, gamma and state.  In
+ * the general form that holds by construction -- the solo entries ARE that form with B = 1 -- and in the one-workgroup form
+ * because it calls the same arithmetic on values held in LDS.
  *   weights   device fp32 [nnz] (w_stride 0) or [B][nnz] (w_stride nnz); may be NULL when nnz = 0
  *   gamma     device fp32 [n] (gamma_stride 0) or [B][n] (gamma_stride n)
  *   init      device fp32 [B][n][3] = (pS, pI, pR), not validated here

@@ -1,6 +1,11 @@
 """The DMP baseline's cases for the GPU tests (a helper, not a test): graphs, per-edge weights that are not symmetric in value,
 per-node gamma, seeds and horizons (numpy only), the bars they are held to, and the model under test built from a case.
 tests/test_gpu_baselines.py says what each case is for."""
+import functools
+import hashlib
+import json
+import os
+
 import numpy as np
 
 RTOL = 1e-5                     # test_gpu_parity.py's fp32 bar
@@ -10,6 +15,26 @@ MF_ATOL = 1e-6                  # the project's mean-field bar
 def rel(a, b):
     a = np.asarray(a, np.float64); b = np.asarray(b, np.float64)
     return np.max(np.abs(a - b)) / (np.max(np.abs(b)) + 1e-30)
+
+
+def f32_digest(a):
+    """SHA-256 of the contiguous bytes of a float32 array or tensor: what tests/golden/dmp_parent.json holds per output."""
+    a = np.ascontiguousarray(a.cpu().numpy() if hasattr(a, "cpu") else a)
+    assert a.dtype == np.float32
+    return hashlib.sha256(a.tobytes()).hexdigest()
+
+
+@functools.lru_cache(maxsize=None)
+def dmp_parent():
+    """{key: entry} of tests/golden/dmp_parent.json (make_golden_dmp_parent.py says what the keys are)."""
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "dmp_parent.json")) as f:
+        return {e["key"]: e for e in json.load(f)["entries"]}
+
+
+def is_parents(key, out):
+    """`out` has the shape and the bits that the parent library returned for the call `key`."""
+    e = dmp_parent()[key]
+    return list(out.shape) == e["shape"] and f32_digest(out) == e["sha256"]
 
 
 def weights(nnz, lo, hi, seed):

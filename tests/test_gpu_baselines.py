@@ -40,7 +40,7 @@ import functools
 import numpy as np
 import pytest
 
-from baseline_cases import DMP_CASES, MF_ATOL, RTOL, dmp_model as _dmp_model, er as _er, gammas as _gammas, rel as _rel, weights as _weights
+from baseline_cases import DMP_CASES, MF_ATOL, RTOL, dmp_model as _dmp_model, dmp_parent, is_parents, er as _er, gammas as _gammas, rel as _rel, weights as _weights
 from sir_cases import dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
@@ -137,6 +137,18 @@ def test_dmp_boundary_weights_and_rates(name, dev):
         assert c["gam"][0] == 0 and c["gam"][1] == 1
         assert not out[:, 0, 2].any()                               # gamma = 0: never recovered
         assert out[1, 1, 2] == 1 and out[1, 1, 1] == 0              # gamma = 1: recovered after one step
+
+
+@pytest.mark.parametrize("name", list(DMP_CASES))
+def test_dmp_seed_entry_is_the_parents_bits(name, dev):
+    """tests/golden/dmp_parent.json: the output of gnode_dmp_f32 at commit 893d874 on an MI355X, by digest and with no
+    tolerance, and the workspace that the seed entry and the initial-state entry asked for there."""
+    from gnode import _lib
+    c = DMP_CASES[name]()
+    m = _dmp_model(c)
+    assert is_parents(f"dmp_f32/{name}", m.run(c["seeds"], c["T"]))
+    lib, want = _lib.load(), dmp_parent()[f"dmp_f32/{name}"]["workspace_bytes"]
+    assert lib.gnode_dmp_workspace_bytes(m.graph.handle) == want and lib.gnode_dmp_init_workspace_bytes(m.graph.handle) == want
 
 
 def test_dmp_workspace_carries_nothing_between_runs(dev):

@@ -9,7 +9,7 @@ import pickle
 import numpy as np
 import pytest
 
-from baseline_cases import DMP_CASES, RTOL, er as _er, gammas as _gammas, rel as _rel, weights as _weights
+from baseline_cases import DMP_CASES, RTOL, dmp_parent, er as _er, gammas as _gammas, is_parents, rel as _rel, weights as _weights
 from sir_cases import dev, state as _state  # noqa: F401
 
 pytestmark = pytest.mark.gpu
@@ -19,6 +19,8 @@ CASE_SEED = {name: 700 + 10 * i for i, name in enumerate(CASES)}
 SCALE = [1.0, 0.5, 0.8125]
 LDS_WORKGROUP = 160 * 1024          # what a gfx950 workgroup may declare
 T_FORMS = 6
+FORM_TAGS = ["small", "mid", "last_fit", "first_unfit"]
+FORM_SCALE = [1.0, 0.75]
 
 
 def _matrix(rp, ci, w):
@@ -150,17 +152,55 @@ def _form_inputs(tag, B, seed):
     return M, _states(N_FORMS, seed + 1, B), np.stack([_gammas(N_FORMS, seed + 10 + b) for b in range(B)])
 
 
-@pytest.mark.parametrize("tag", ["small", "mid", "last_fit", "first_unfit"])
-def test_each_form_and_boundary_is_the_solo_run(tag, dev):
-    import torch
+def form_out(tag):
+    """(inputs, the batch of two samples on a form graph through dmp_batch)"""
     from gnode.dmp import dmp_batch
     M, ps, gam = _form_inputs(tag, 2, 50)
-    scale = [1.0, 0.75]
-    got = dmp_batch(M, [_state(p) for p in ps], gam, T_FORMS, scale=scale)
+    return (M, ps, gam), dmp_batch(M, [_state(p) for p in ps], gam, T_FORMS, scale=FORM_SCALE)
+
+
+def form_solo(inputs, b):
+    M, ps, gam = inputs
+    return _solo(M * FORM_SCALE[b], gam[b], _state(ps[b]), T_FORMS)
+
+
+@pytest.mark.parametrize("tag", FORM_TAGS)
+def test_each_form_and_boundary_is_the_solo_run(tag, dev):
+    import torch
+    inputs, got = form_out(tag)
     for b in range(2):
-        want = _solo(M * scale[b], gam[b], _state(ps[b]), T_FORMS)
+        want = form_solo(inputs, b)
         assert torch.isfinite(want).all() and float((want[0, :, 0] - want[-1, :, 0]).max()) > 0.05       # something spread
         assert torch.equal(got[b], want), f"{tag}: sample {b}"
+
+
+# ------------------------------------------------------------------ the parent's bits
+def _batch_need(M, B):
+    from gnode import _lib
+    from gnode.dmp import DmpGraph
+    G = DmpGraph(M)                                                 # (kept: the handle dies with it)
+    return int(_lib.load().gnode_dmp_batch_workspace_bytes(G.graph.handle, B))
+
+
+@pytest.mark.parametrize("name", CASES)
+def test_batch_and_solo_runs_are_the_parents_bits(name, dev):
+    """tests/golden/dmp_parent.json: what the library of commit 893d874 returned on an MI355X, when the solo entries had kernels
+    of their own.  Equality of digests; since then a solo call is the general form with one sample, so for the graphs that
+    the general form serves this, not the comparison with the solo run, is what holds the arithmetic."""
+    c, M, ps, gam = batch_case(name)
+    assert is_parents(f"dmp_batch/{name}", batch_out(name))
+    assert _batch_need(M, 3) == dmp_parent()[f"dmp_batch/{name}"]["batch_workspace_bytes"]
+    for b in range(3):
+        assert is_parents(f"dmp_init_f32/{name}/{b}", _solo(M * SCALE[b], gam[b], _state(ps[b]), c["T"])), f"sample {b}"
+
+
+@pytest.mark.parametrize("tag", FORM_TAGS)
+def test_each_form_and_boundary_is_the_parents_bits(tag, dev):
+    inputs, got = form_out(tag)
+    assert is_parents(f"dmp_batch/form/{tag}", got)
+    assert _batch_need(inputs[0], 2) == dmp_parent()[f"dmp_batch/form/{tag}"]["batch_workspace_bytes"]
+    for b in range(2):
+        assert is_parents(f"dmp_init_f32/form/{tag}/{b}", form_solo(inputs, b)), f"sample {b}"
 
 
 def test_which_form_serves_which_case(dev):
