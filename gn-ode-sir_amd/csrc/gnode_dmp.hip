@@ -19,6 +19,10 @@
 //                              time step (node pass, edge pass); theta ping-pongs because the edge pass reads its neighbours'
 //   one workgroup per sample   the messages and marginals of a sample live in LDS for the whole horizon: one launch
 // A sample's numbers do not depend on the form or on B: same expressions, same per-element order.
+//
+// The second half of the file is the reverse sweep of the same recurrence (gnode_dmp_batch_backward_f32, gnode_dmp_backward_f32):
+// the gradients of the marginals with respect to w, gamma and the start, stated once as dmp_rev_* functions and served in the
+// same two forms.
 #include "gnode_common.h"
 #include <algorithm>
 
@@ -206,8 +210,250 @@ __global__ __launch_bounds__(256) void k_dmp_batch_edge(const int* __restrict__ 
                     theta[slot], theta_next[slot]);
 }
 
+// ------------------------------------------------------------------------------------------------ the reverse sweep, once
+// The gradient of sum(grad_out * out) with respect to w, gamma and the start (gnode_dmp_batch_backward_f32).  Adjoints carried
+// from step t + 1 to step t: per edge theta_bar, phi_bar, q_bar (of Ps_e), per node pi_bar, pr_bar; all start at 0.  A step is
+// an edge pass (the reverse of dmp_edge_update, absent at t = maxTime - 1, whose messages had no reader) and a node pass (the
+// reverse of dmp_node_update and of both products: P_u and the cavity product P_u / theta[rev e], which does not depend on
+// theta[rev e]).  The edge pass leaves two numbers per edge for the node pass of its source's row, which sums them in
+// ascending position from 0; the node pass writes theta_bar of the reverses of its row's edges into the OTHER theta_bar
+// buffer: rev is a permutation, so every slot is written once per step and nothing here is atomic.  Like the recurrence these
+// round as written, and the two forms below call them on the sample's own pointers, in global memory or in LDS.
+
+// the reverse of dmp_edge_update at step t for one edge: theta_bar is that of theta_{t+1}; phi_bar, q_bar come in as step
+// t + 1 left them and go out for step t - 1.  q_tot (the adjoint of Ps_e of this step) and gamma_part (this edge's share of
+// gamma_bar[src]) are for the node pass.
+__device__ __forceinline__ void dmp_rev_edge(float w_e, float gamma_u, float phi_t, float phi_prev, float theta_bar, float& phi_bar,
+                                             float& q_bar, float& w_bar, float& q_tot, float& gamma_part) {
+    const float pb = phi_bar - w_e * theta_bar;                 // the adjoint of phi_t: theta_{t+1} = theta_t - w phi_t
+    w_bar = w_bar - phi_t * theta_bar;
+    w_bar = w_bar - ((1.0f - gamma_u) * phi_prev) * pb;         // phi_t = (1 - w)(1 - gamma) phi_{t-1} - (Ps_e - Ps_e^{prev})
+    gamma_part = -(((1.0f - w_e) * phi_prev) * pb);
+    q_tot = q_bar - pb;
+    q_bar = pb;
+    phi_bar = ((1.0f - w_e) * (1.0f - gamma_u)) * pb;
+}
+
+// what row u's edges [lo, hi) hand to their source: S = sum c_bar c, the shares of ps0_bar[u] and of gamma_bar[u]
+struct DmpRowSums { float S, ps0, gamma; };
+__device__ __forceinline__ DmpRowSums dmp_rev_row_sums(const int* rev, const float* theta, const float* q_tot, const float* gamma_part,
+                                                       int lo, int hi, float P_u, float ps0_u) {
+    DmpRowSums s = {0.0f, 0.0f, 0.0f};
+    for (int e = lo; e < hi; ++e) {
+        const float c = P_u / theta[rev[e]];                    // the cavity product, as dmp_edge_update divides
+        s.ps0 = s.ps0 + c * q_tot[e];
+        s.S = s.S + (ps0_u * q_tot[e]) * c;
+        s.gamma = s.gamma + gamma_part[e];
+    }
+    return s;
+}
+
+// the reverse of dmp_node_update for node k at step t: (gS, gI, gR) is grad_out's row, pi_prev the forward's Pi_{t-1}[k]
+__device__ __forceinline__ void dmp_rev_node(float gS, float gI, float gR, float P_k, float ps0_k, float pi_prev, float gamma_k,
+                                             float& pi_bar, float& pr_bar, float& gamma_bar, float& ps0_bar, float& P_bar) {
+    const float aI = gI + pi_bar;
+    const float aR = (gR + pr_bar) - aI;                        // pi = 1 - ps - pr
+    const float aS = gS - aI;
+    gamma_bar = gamma_bar + pi_prev * aR;                       // pr = pr_prev + gamma pi_prev
+    pr_bar = aR;
+    pi_bar = gamma_k * aR;
+    ps0_bar = ps0_bar + P_k * aS;                               // ps = ps0 P
+    P_bar = ps0_k * aS;
+}
+
+// theta_bar of step t for the reverses of row u's edges: the carried theta_bar plus the derivative of P_u and of the other
+// edges' cavity products.  q_tot == nullptr: there was no edge pass (t = maxTime - 1, S = 0).
+__device__ __forceinline__ void dmp_rev_theta(const int* rev, const float* theta, const float* q_tot, int lo, int hi, float P_u,
+                                              float ps0_u, float PbarP, float S, const float* tb_cur, float* tb_next) {
+    for (int f = lo; f < hi; ++f) {
+        const int r = rev[f];
+        const float th = theta[r];
+        const float own = q_tot ? (ps0_u * q_tot[f]) * (P_u / th) : 0.0f;
+        tb_next[r] = tb_cur[r] + ((PbarP + S) - own) / th;
+    }
+}
+
+struct DmpGradArgs {
+    const float* w; long w_stride;
+    const float* gamma; long gamma_stride;
+    const float* init;                  // [B][n][3]
+    const float* out;                   // [B][maxTime][n][3], the forward's
+    const float* gout;                  // the same shape
+    float *gw, *gg, *gi;                // [B][nnz], [B][n], [B][n][3]; null: not wanted
+    float *th_tape, *ph_tape;           // [B][maxTime - 1][nnz]: theta_1 .. theta_{T-1} and phi_0 .. phi_{T-2}
+    int n, maxTime; long nnz;
+};
+struct DmpGradSample {                  // sample b's own tables (the tapes are not __restrict__: written and read in one launch)
+    const float* __restrict__ w; const float* __restrict__ gamma; const float* __restrict__ s0; const float* __restrict__ out;
+    const float* __restrict__ gout;
+    float *gw, *gg, *gi, *th_tape, *ph_tape;
+    int n, maxTime; long nnz;
+    __device__ __forceinline__ float* theta(int t) const { return th_tape + (size_t)(t - 1) * nnz; }    // theta_t, t >= 1
+    __device__ __forceinline__ float* phi(int t) const { return ph_tape + (size_t)t * nnz; }            // phi_t, t >= 0
+};
+__device__ __forceinline__ DmpGradSample dmp_grad_sample(const DmpGradArgs& a, size_t b) {
+    const size_t nn = (size_t)a.n, ne = (size_t)a.nnz, tape = b * (size_t)(a.maxTime - 1) * ne;
+    return {a.w + b * a.w_stride, a.gamma + b * a.gamma_stride, a.init + b * nn * 3, a.out + b * (size_t)a.maxTime * nn * 3,
+            a.gout + b * (size_t)a.maxTime * nn * 3, a.gw ? a.gw + b * ne : nullptr, a.gg ? a.gg + b * nn : nullptr,
+            a.gi ? a.gi + b * nn * 3 : nullptr, a.th_tape + tape, a.ph_tape + tape, a.n, a.maxTime, a.nnz};
+}
+struct DmpAdjoint {                     // sample b's own adjoint state, in the workspace or in LDS
+    float *tb, *tb_next, *phb, *qb, *q_tot, *gamma_part, *pib, *prb;      // tb: theta_bar as the step finds it, tb_next: as it leaves it
+};
+__host__ __device__ static inline void dmp_adjoint_swap(DmpAdjoint& A) { float* t = A.tb; A.tb = A.tb_next; A.tb_next = t; }
+
+// The work of one thread on one element, for both forms.  The tape first: the forward's own functions, theta and phi kept.
+__device__ __forceinline__ void dmp_tape_start(const DmpGradSample& s, const int* src, float* ps, long e) {
+    const size_t u = src[e];
+    dmp_edge_start(s.s0[u * 3], s.s0[u * 3 + 1], s.w[e], s.theta(1)[e], s.phi(0)[e], ps[e]);
+}
+__device__ __forceinline__ void dmp_tape_edge(const DmpGradSample& s, const int* src, const int* rev, const float* P, float* ps, int t,
+                                              long e) {
+    const size_t u = src[e];
+    float ph = s.phi(t - 1)[e];
+    dmp_edge_update(P[u], s.theta(t)[rev[e]], s.s0[u * 3], s.w[e], s.gamma[u], ph, ps[e], s.theta(t)[e], s.theta(t + 1)[e]);
+    s.phi(t)[e] = ph;
+}
+__device__ __forceinline__ void dmp_grad_edge(const DmpGradSample& s, const DmpAdjoint& A, const int* src, int t, long e) {
+    const int u = src[e];
+    float w_bar = s.gw ? s.gw[e] : 0.0f;
+    dmp_rev_edge(s.w[e], s.gamma[u], s.phi(t)[e], s.phi(t - 1)[e], A.tb[e], A.phb[e], A.qb[e], w_bar, A.q_tot[e], A.gamma_part[e]);
+    if (s.gw) s.gw[e] = w_bar;
+}
+__device__ __forceinline__ void dmp_grad_node(const DmpGradSample& s, const DmpAdjoint& A, const int* rowptr, const int* rev, int t,
+                                              int k) {
+    const int lo = rowptr[k], hi = rowptr[k + 1];
+    const bool edge_pass = t + 1 < s.maxTime;                   // (the last step's messages had no reader)
+    const float* theta = s.theta(t);
+    const float ps0 = s.s0[(size_t)k * 3];
+    const float P = dmp_row_product(rev, theta, lo, hi);
+    float gamma_bar = s.gg ? s.gg[k] : 0.0f, ps0_bar = s.gi ? s.gi[(size_t)k * 3] : 0.0f, S = 0.0f, P_bar;
+    if (edge_pass) {
+        const DmpRowSums sums = dmp_rev_row_sums(rev, theta, A.q_tot, A.gamma_part, lo, hi, P, ps0);
+        gamma_bar = gamma_bar + sums.gamma;
+        ps0_bar = ps0_bar + sums.ps0;
+        S = sums.S;
+    }
+    const float* g = s.gout + ((size_t)t * s.n + k) * 3;
+    dmp_rev_node(g[0], g[1], g[2], P, ps0, s.out[((size_t)(t - 1) * s.n + k) * 3 + 1], s.gamma[k], A.pib[k], A.prb[k], gamma_bar, ps0_bar,
+                 P_bar);
+    if (s.gg) s.gg[k] = gamma_bar;
+    if (s.gi) s.gi[(size_t)k * 3] = ps0_bar;
+    dmp_rev_theta(rev, theta, edge_pass ? A.q_tot : nullptr, lo, hi, P, ps0, P_bar * P, S, A.tb, A.tb_next);
+}
+// after step 1: theta_1 = (1 - w Pi_0[src]) + 1e-10, phi_0 = Pi_0[src], Ps_e^{prev} = Ps_0[src], and row 0 of `out` is the start
+__device__ __forceinline__ void dmp_grad_start_edge(const DmpGradSample& s, const DmpAdjoint& A, const int* src, long e) {
+    if (s.gw) s.gw[e] = s.gw[e] - s.s0[(size_t)src[e] * 3 + 1] * A.tb[e];
+}
+__device__ __forceinline__ void dmp_grad_start_node(const DmpGradSample& s, const DmpAdjoint& A, const int* rowptr, int k) {
+    if (!s.gi) return;
+    float pi0_bar = 0.0f, ps0_bar = s.gi[(size_t)k * 3];
+    float q_sum = 0.0f;
+    for (int e = rowptr[k]; e < rowptr[k + 1]; ++e) {
+        pi0_bar = pi0_bar + (A.phb[e] - s.w[e] * A.tb[e]);
+        q_sum = q_sum + A.qb[e];
+    }
+    ps0_bar = ps0_bar + q_sum;
+    const float* g = s.gout + (size_t)k * 3;
+    s.gi[(size_t)k * 3] = ps0_bar + g[0];
+    s.gi[(size_t)k * 3 + 1] = pi0_bar + (A.pib[k] + g[1]);
+    s.gi[(size_t)k * 3 + 2] = A.prb[k] + g[2];
+}
+
+extern "C" size_t gnode_dmp_batch_backward_lds_bytes(gnode_graph_t g) {
+    if (!g) return 0;                   // theta_bar x2, phi_bar, q_bar, q_tot, gamma_part, rev | pi_bar, pr_bar
+    return 7 * dmp_align16((size_t)g->nnz * 4) + 2 * dmp_align16((size_t)g->info.n * 4);
+}
+static bool dmp_grad_one_workgroup(gnode_graph_t g) { return gnode_dmp_batch_backward_lds_bytes(g) <= kDmpLdsLimit; }
+
+// One workgroup = one sample: the forward again with theta and phi kept on the tape (in the workspace; Ps_e and P use the
+// room of q_tot and pi_bar meanwhile), then the sweep with the adjoint state in LDS.  Thread `tid` owns nodes and edges tid,
+// tid + blockDim.x, ... in every pass, so a gradient slot has one writer; the barriers sit in uniform control flow (the loops'
+// bounds are kernel arguments).  What one thread writes to the tape another reads only after a barrier.
+__global__ __launch_bounds__(1024) void k_dmp_grad_wg(const int* __restrict__ rowptr, const int* __restrict__ src,
+                                                     const int* __restrict__ rev_g, DmpGradArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char dmp_smem[];
+    const int n = a.n, nnz = (int)a.nnz, T = a.maxTime, tid = threadIdx.x, nt = blockDim.x;
+    const size_t eb = dmp_align16((size_t)nnz * 4), nb = dmp_align16((size_t)n * 4);
+    auto edges = [&](int i) { return (float*)(dmp_smem + i * eb); };
+    DmpAdjoint A = {edges(0), edges(1), edges(2), edges(3), edges(4), edges(5), (float*)(dmp_smem + 7 * eb),
+                          (float*)(dmp_smem + 7 * eb + nb)};
+    int* rev = (int*)(dmp_smem + 6 * eb);
+    float* ps = A.q_tot; float* P = A.pib;
+    const DmpGradSample s = dmp_grad_sample(a, blockIdx.x);
+    for (int e = tid; e < nnz; e += nt) {
+        rev[e] = rev_g[e];
+        dmp_tape_start(s, src, ps, e);
+    }
+    __syncthreads();
+    for (int t = 1; t + 1 < T; ++t) {
+        for (int k = tid; k < n; k += nt) P[k] = dmp_row_product(rev, s.theta(t), rowptr[k], rowptr[k + 1]);
+        __syncthreads();
+        for (int e = tid; e < nnz; e += nt) dmp_tape_edge(s, src, rev, P, ps, t, e);
+        __syncthreads();
+    }
+    for (int e = tid; e < nnz; e += nt) { A.tb[e] = 0.0f; A.phb[e] = 0.0f; A.qb[e] = 0.0f; }
+    for (int k = tid; k < n; k += nt) { A.pib[k] = 0.0f; A.prb[k] = 0.0f; }
+    __syncthreads();
+    for (int t = T - 1; t >= 1; --t, dmp_adjoint_swap(A)) {
+        if (t + 1 < T)
+            for (int e = tid; e < nnz; e += nt) dmp_grad_edge(s, A, src, t, e);
+        __syncthreads();
+        for (int k = tid; k < n; k += nt) dmp_grad_node(s, A, rowptr, rev, t, k);
+        __syncthreads();
+    }
+    for (int e = tid; e < nnz; e += nt) dmp_grad_start_edge(s, A, src, e);
+    for (int k = tid; k < n; k += nt) dmp_grad_start_node(s, A, rowptr, k);
+}
+
+// The general form: `per` blocks of 256 per sample; the adjoint state of sample b is at row b * n and edge slot b * nnz of
+// the workspace arrays.
+__device__ __forceinline__ DmpAdjoint dmp_adjoint_of(const DmpAdjoint& A, size_t b, int n, long nnz) {
+    const size_t e = b * (size_t)nnz, k = b * (size_t)n;
+    return {A.tb + e, A.tb_next + e, A.phb + e, A.qb + e, A.q_tot + e, A.gamma_part + e, A.pib + k, A.prb + k};
+}
+__global__ __launch_bounds__(256) void k_dmp_tape_start(const int* __restrict__ src, DmpGradArgs a, unsigned per, float* ps) {
+    const size_t b = blockIdx.x / per;
+    const long e = (long)(blockIdx.x % per) * 256 + threadIdx.x;
+    if (e < a.nnz) dmp_tape_start(dmp_grad_sample(a, b), src, ps + b * (size_t)a.nnz, e);
+}
+__global__ __launch_bounds__(256) void k_dmp_tape_node(const int* __restrict__ rowptr, const int* __restrict__ rev, DmpGradArgs a,
+                                                      unsigned per, int t, float* __restrict__ P) {
+    const size_t b = blockIdx.x / per;
+    const int k = (int)(blockIdx.x % per) * 256 + threadIdx.x;
+    if (k < a.n) P[b * (size_t)a.n + k] = dmp_row_product(rev, dmp_grad_sample(a, b).theta(t), rowptr[k], rowptr[k + 1]);
+}
+__global__ __launch_bounds__(256) void k_dmp_tape_edge(const int* __restrict__ src, const int* __restrict__ rev, const float* __restrict__ P,
+                                                      DmpGradArgs a, unsigned per, int t, float* ps) {
+    const size_t b = blockIdx.x / per;
+    const long e = (long)(blockIdx.x % per) * 256 + threadIdx.x;
+    if (e < a.nnz) dmp_tape_edge(dmp_grad_sample(a, b), src, rev, P + b * (size_t)a.n, ps + b * (size_t)a.nnz, t, e);
+}
+__global__ __launch_bounds__(256) void k_dmp_grad_edge(const int* __restrict__ src, DmpGradArgs a, DmpAdjoint A, unsigned per, int t) {
+    const size_t b = blockIdx.x / per;
+    const long e = (long)(blockIdx.x % per) * 256 + threadIdx.x;
+    if (e < a.nnz) dmp_grad_edge(dmp_grad_sample(a, b), dmp_adjoint_of(A, b, a.n, a.nnz), src, t, e);
+}
+__global__ __launch_bounds__(256) void k_dmp_grad_node(const int* __restrict__ rowptr, const int* __restrict__ rev, DmpGradArgs a,
+                                                      DmpAdjoint A, unsigned per, int t) {
+    const size_t b = blockIdx.x / per;
+    const int k = (int)(blockIdx.x % per) * 256 + threadIdx.x;
+    if (k < a.n) dmp_grad_node(dmp_grad_sample(a, b), dmp_adjoint_of(A, b, a.n, a.nnz), rowptr, rev, t, k);
+}
+__global__ __launch_bounds__(256) void k_dmp_grad_start_edge(const int* __restrict__ src, DmpGradArgs a, DmpAdjoint A, unsigned per) {
+    const size_t b = blockIdx.x / per;
+    const long e = (long)(blockIdx.x % per) * 256 + threadIdx.x;
+    if (e < a.nnz) dmp_grad_start_edge(dmp_grad_sample(a, b), dmp_adjoint_of(A, b, a.n, a.nnz), src, e);
+}
+__global__ __launch_bounds__(256) void k_dmp_grad_start_node(const int* __restrict__ rowptr, DmpGradArgs a, DmpAdjoint A, unsigned per) {
+    const size_t b = blockIdx.x / per;
+    const int k = (int)(blockIdx.x % per) * 256 + threadIdx.x;
+    if (k < a.n) dmp_grad_start_node(dmp_grad_sample(a, b), dmp_adjoint_of(A, b, a.n, a.nnz), rowptr, k);
+}
+
 int gn_dmp_set_attributes() {       // once per device, from gnode_graph_create
     GN_HIP(hipFuncSetAttribute((const void*)k_dmp_batch_wg, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kDmpLdsLimit));
+    GN_HIP(hipFuncSetAttribute((const void*)k_dmp_grad_wg, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kDmpLdsLimit));
     return 0;
 }
 
@@ -327,4 +573,112 @@ extern "C" int gnode_dmp_batch_f32(gnode_graph_t g, const float* weights, int64_
                  (long long)gamma_stride);
     return dmp_run(who, g, weights, (long)w_stride, gamma, (long)gamma_stride, init, nullptr, 0, B, maxTime, out, false, workspace,
                    workspace_bytes, stream);
+}
+
+// ------------------------------------------------------------------------------------------------ the reverse sweep's host side
+// The workspace of a backward call: src, rev | status | the tapes of theta and phi, B * (maxTime - 1) * nnz each; for the general
+// form Ps_e, theta_bar x2, phi_bar, q_bar, q_tot, gamma_part over B * nnz edge slots and P, pi_bar, pr_bar over B * n rows.
+struct DmpGradWorkspace {
+    int *src, *rev, *bad;
+    float *th_tape, *ph_tape, *ps, *P;
+    DmpAdjoint adj;
+    size_t bytes;
+};
+static DmpGradWorkspace dmp_grad_carve(gnode_graph_t g, size_t B, size_t maxTime, bool general, void* base) {
+    const size_t edges = (size_t)std::max<int64_t>(g->nnz, 1), eb = gn_align(edges * 4), tape = gn_align(B * (maxTime - 1) * edges * 4);
+    const size_t EB = general ? gn_align(B * edges * 4) : 0, NB = general ? gn_align(B * (size_t)g->info.n * 4) : 0;
+    size_t at = 0;
+    auto take = [&](size_t bytes) { char* p = base ? (char*)base + at : nullptr; at += bytes; return (float*)p; };
+    DmpGradWorkspace w;
+    w.src = (int*)take(eb); w.rev = (int*)take(eb); w.bad = (int*)take(256);
+    w.th_tape = take(tape); w.ph_tape = take(tape);
+    w.ps = take(EB); w.P = take(NB);
+    w.adj.tb = take(EB); w.adj.tb_next = take(EB); w.adj.phb = take(EB); w.adj.qb = take(EB); w.adj.q_tot = take(EB);
+    w.adj.gamma_part = take(EB); w.adj.pib = take(NB); w.adj.prb = take(NB);
+    w.bytes = at;
+    return w;
+}
+extern "C" size_t gnode_dmp_batch_backward_workspace_bytes(gnode_graph_t g, int32_t B, int32_t maxTime) {
+    return g && B >= 1 && maxTime >= 2 ? dmp_grad_carve(g, (size_t)B, (size_t)maxTime, !dmp_grad_one_workgroup(g), nullptr).bytes : 0;
+}
+extern "C" size_t gnode_dmp_backward_workspace_bytes(gnode_graph_t g, int32_t maxTime) {      // a solo call is the general form
+    return g && maxTime >= 2 ? dmp_grad_carve(g, 1, (size_t)maxTime, true, nullptr).bytes : 0;
+}
+
+// B samples; `solo`: gnode_dmp_backward_f32, the general form at every size
+static int dmp_grad_run(const char* who, gnode_graph_t g, const float* weights, long w_stride, const float* gamma, long gamma_stride,
+                        const float* init, int32_t B, int32_t maxTime, const float* out, const float* grad_out, float* grad_w,
+                        float* grad_gamma, float* grad_init, bool solo, void* workspace, size_t workspace_bytes, void* stream) {
+    GN_CHECK_ARG(g && gamma && init && out && grad_out && workspace, "%s: null pointer", who);
+    GN_CHECK_ARG(weights || g->nnz == 0, "%s: weights is null", who);
+    GN_CHECK_ARG(B >= 1, "%s: B must be >= 1 (got %d)", who, B);
+    GN_CHECK_ARG(maxTime >= 2, "%s: maxTime must be >= 2 (got %d)", who, maxTime);
+    GN_CHECK_ARG(w_stride == 0 || w_stride == g->nnz, "%s: w_stride must be 0 or nnz = %ld (got %ld)", who, (long)g->nnz, w_stride);
+    GN_CHECK_ARG(gamma_stride == 0 || gamma_stride == g->info.n, "%s: gamma_stride must be 0 or n = %d (got %ld)", who, g->info.n, gamma_stride);
+    GN_CHECK_ARG(grad_w || grad_gamma || grad_init, "%s: no gradient is asked for", who);
+    const long nnz = g->nnz;
+    const int n = g->info.n;
+    const unsigned ng = (unsigned)((n + 255) / 256), eg = (unsigned)std::max<long>(1, (nnz + 255) / 256);
+    const bool one_wg = !solo && dmp_grad_one_workgroup(g);
+    GN_CHECK_ARG(one_wg || (size_t)B * std::max(ng, eg) < ((size_t)1 << 31), "%s: B = %d is too many samples for this graph", who, B);
+    const DmpGradWorkspace ws = dmp_grad_carve(g, (size_t)B, (size_t)maxTime, !one_wg, workspace);
+    if (workspace_bytes < ws.bytes) {
+        gnode_set_error("%s: workspace %zu < %zu", who, workspace_bytes, ws.bytes);
+        return GNODE_ERR_WORKSPACE;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    GN_HIP(hipMemsetAsync(ws.bad, 0, 4, st));
+    hipLaunchKernelGGL(k_dmp_setup, dim3(ng), dim3(256), 0, st, g->rowptr, g->col, n, ws.src, ws.rev, ws.bad);
+    GN_LAUNCH_CHECK();
+    int bad_h = 0;
+    GN_HIP(hipMemcpyAsync(&bad_h, ws.bad, 4, hipMemcpyDeviceToHost, st));
+    GN_HIP(hipStreamSynchronize(st));
+    GN_CHECK_ARG(!bad_h, "%s: the sparsity pattern is not symmetric (DMP here serves undirected graphs)", who);
+    if (grad_w && nnz) GN_HIP(hipMemsetAsync(grad_w, 0, (size_t)B * nnz * 4, st));         // the sweep accumulates into them
+    if (grad_gamma) GN_HIP(hipMemsetAsync(grad_gamma, 0, (size_t)B * n * 4, st));
+    if (grad_init) GN_HIP(hipMemsetAsync(grad_init, 0, (size_t)B * n * 12, st));
+    const DmpGradArgs a = {weights, w_stride, gamma, gamma_stride, init, out, grad_out, grad_w, grad_gamma, grad_init, ws.th_tape, ws.ph_tape,
+                           n, maxTime, nnz};
+    if (one_wg) {
+        const long most = std::max<long>(n, nnz);
+        const unsigned threads = (unsigned)std::min<long>(1024, std::max<long>(64, (most + 63) / 64 * 64));
+        hipLaunchKernelGGL(k_dmp_grad_wg, dim3((unsigned)B), dim3(threads), gnode_dmp_batch_backward_lds_bytes(g), st, g->rowptr, ws.src,
+                           ws.rev, a);
+        GN_LAUNCH_CHECK();
+        return 0;
+    }
+    const dim3 gn((unsigned)B * ng), ge((unsigned)B * eg);
+    hipLaunchKernelGGL(k_dmp_tape_start, ge, dim3(256), 0, st, ws.src, a, eg, ws.ps);
+    for (int t = 1; t + 1 < maxTime; ++t) {
+        hipLaunchKernelGGL(k_dmp_tape_node, gn, dim3(256), 0, st, g->rowptr, ws.rev, a, ng, t, ws.P);
+        hipLaunchKernelGGL(k_dmp_tape_edge, ge, dim3(256), 0, st, ws.src, ws.rev, ws.P, a, eg, t, ws.ps);
+    }
+    GN_LAUNCH_CHECK();
+    for (float* zero : {ws.adj.tb, ws.adj.phb, ws.adj.qb}) GN_HIP(hipMemsetAsync(zero, 0, (size_t)B * std::max<long>(nnz, 1) * 4, st));
+    for (float* zero : {ws.adj.pib, ws.adj.prb}) GN_HIP(hipMemsetAsync(zero, 0, (size_t)B * n * 4, st));
+    DmpAdjoint A = ws.adj;
+    for (int t = maxTime - 1; t >= 1; --t, dmp_adjoint_swap(A)) {
+        if (t + 1 < maxTime) hipLaunchKernelGGL(k_dmp_grad_edge, ge, dim3(256), 0, st, ws.src, a, A, eg, t);
+        hipLaunchKernelGGL(k_dmp_grad_node, gn, dim3(256), 0, st, g->rowptr, ws.rev, a, A, ng, t);
+        GN_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(k_dmp_grad_start_edge, ge, dim3(256), 0, st, ws.src, a, A, eg);
+    hipLaunchKernelGGL(k_dmp_grad_start_node, gn, dim3(256), 0, st, g->rowptr, a, A, ng);
+    GN_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int gnode_dmp_batch_backward_f32(gnode_graph_t g, const float* weights, int64_t w_stride, const float* gamma, int64_t gamma_stride,
+                                            const float* init, int32_t B, int32_t maxTime, const float* out, const float* grad_out,
+                                            float* grad_w, float* grad_gamma, float* grad_init, void* workspace, size_t workspace_bytes,
+                                            void* stream) {
+    return dmp_grad_run("gnode_dmp_batch_backward_f32", g, weights, (long)w_stride, gamma, (long)gamma_stride, init, B, maxTime, out, grad_out,
+                        grad_w, grad_gamma, grad_init, false, workspace, workspace_bytes, stream);
+}
+
+extern "C" int gnode_dmp_backward_f32(gnode_graph_t g, const float* weights, const float* gamma, const float* init, int32_t maxTime,
+                                      const float* out, const float* grad_out, float* grad_w, float* grad_gamma, float* grad_init,
+                                      void* workspace, size_t workspace_bytes, void* stream) {
+    return dmp_grad_run("gnode_dmp_backward_f32", g, weights, 0, gamma, 0, init, 1, maxTime, out, grad_out, grad_w, grad_gamma, grad_init, true,
+                        workspace, workspace_bytes, stream);
 }

@@ -6,6 +6,8 @@ same constructor and `run(seed_list, maxTime)`, the message passing runs in libg
                                                 seed_list: seed ids, or an `InitialState` (an extension)
     dmp_batch(weight_adj, starts, gamma, maxTime, scale=None) -> float32 tensor [B, maxTime, n, 3] (an extension): B
                                                 samples on one graph in one library call, each its solo run's bits
+    dmp_marginals(DmpGraph, weights, gamma, init, maxTime) -> the same tensor as a torch.autograd.Function of device tensors (an
+                                                extension): gradients with respect to weights, gamma and the start
 """
 from __future__ import annotations
 
@@ -74,6 +76,78 @@ class DmpGraph:
         if self._graph is None:
             self._graph = DeviceGraph(self.indptr, self.indices)
         return self._graph
+
+
+class _DmpMarginals(torch.autograd.Function):
+    """gnode_dmp_batch_f32 forward, gnode_dmp_batch_backward_f32 backward; the arguments are `dmp_marginals`', already checked."""
+
+    @staticmethod
+    def forward(ctx, graph, weights, gamma, init, maxTime):
+        lib, handle = _lib.load(), graph.graph.handle
+        w, g, y0 = weights.detach().contiguous(), gamma.detach().contiguous(), init.detach().contiguous()
+        B, n, nnz = y0.shape[0], graph.N, graph.E
+        out = torch.empty((B, maxTime, n, 3), dtype=torch.float32, device=y0.device)
+        ws = torch.empty(lib.gnode_dmp_batch_workspace_bytes(handle, B), dtype=torch.uint8, device=y0.device)
+        ctx.strides = (nnz if w.dim() == 2 else 0, n if g.dim() == 2 else 0)
+        _lib.check(lib.gnode_dmp_batch_f32(handle, _lib.ptr(w) if nnz else None, ctx.strides[0], _lib.ptr(g), ctx.strides[1], _lib.ptr(y0),
+                                           B, maxTime, _lib.ptr(out), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()))
+        ctx.graph, ctx.maxTime = graph, maxTime
+        ctx.save_for_backward(w, g, y0, out)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        w, g, y0, out = ctx.saved_tensors
+        graph, T, grad_out = ctx.graph, ctx.maxTime, grad_out.contiguous()
+        B, n, nnz = y0.shape[0], graph.N, graph.E
+        want_w, want_g, want_i = ctx.needs_input_grad[1:4]
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=y0.device)      # noqa: E731
+        gw = new(B, nnz) if want_w and nnz else None                 # (no edge, no table: an empty tensor has no address)
+        gg, gi = new(B, n) if want_g else None, new(B, n, 3) if want_i else None
+        if gw is not None or gg is not None or gi is not None:
+            lib, handle = _lib.load(), graph.graph.handle
+            ws = torch.empty(lib.gnode_dmp_batch_backward_workspace_bytes(handle, B, T), dtype=torch.uint8, device=y0.device)
+            _lib.check(lib.gnode_dmp_batch_backward_f32(
+                handle, _lib.ptr(w) if nnz else None, ctx.strides[0], _lib.ptr(g), ctx.strides[1], _lib.ptr(y0), B, T, _lib.ptr(out),
+                _lib.ptr(grad_out), _lib.ptr(gw), _lib.ptr(gg), _lib.ptr(gi), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()))
+        if want_w:                                                  # the library returns one row per sample: a shared table sums them
+            gw = torch.zeros_like(w) if gw is None else gw if w.dim() == 2 else gw.sum(0)
+        if want_g and g.dim() == 1:
+            gg = gg.sum(0)
+        return None, gw, gg, gi, None
+
+
+def dmp_marginals(graph, weights, gamma, init, maxTime):
+    """The DMP marginals of B samples on one graph as a differentiable function of device tensors: float32 [B, maxTime, n, 3] =
+    (Ps, Pi, Pr), bit for bit what `dmp_batch` returns for the same numbers, with `.backward()` through the library's reverse
+    sweep (gnode_dmp_batch_backward_f32) -- fitting per-contact transmission probabilities and recovery rates to observed
+    curves, scoring source nodes by the gradient with respect to the start.
+
+    graph: a `DmpGraph` (only its pattern is read).  weights: float32 [nnz], shared by the samples, or [B, nnz], in the
+    graph's CSR position order (`DmpGraph.data`'s).  gamma: float32 [n] or [B, n].  init: float32 [B, n, 3] = (pS, pI, pR) per
+    node.  Gradients are computed for the inputs that require one; a shared table gets the sum over the samples.  Where the
+    forward is not finite (a weight of 1 next to a seed) the gradient is unspecified.  What is wrong raises ValueError
+    before the library is loaded; a tensor that is not on a GPU raises GnodeError."""
+    if not isinstance(graph, DmpGraph):
+        raise ValueError(f"dmp_marginals: graph must be a DmpGraph, got {type(graph).__name__}")
+    T, n, nnz = int(maxTime), graph.N, graph.E
+    if T < 2:
+        raise ValueError(f"dmp_marginals: maxTime must be >= 2 (got {maxTime})")
+    for name, t in (("weights", weights), ("gamma", gamma), ("init", init)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+            raise ValueError(f"dmp_marginals: {name} must be a float32 tensor")
+    if init.dim() != 3 or init.shape[0] < 1 or tuple(init.shape[1:]) != (n, 3):
+        raise ValueError(f"dmp_marginals: init must have the shape [B >= 1, {n}, 3], got {tuple(init.shape)}")
+    B = init.shape[0]
+    if tuple(weights.shape) not in ((nnz,), (B, nnz)):
+        raise ValueError(f"dmp_marginals: weights must have the shape [{nnz}] or [{B}, {nnz}], got {tuple(weights.shape)}")
+    if tuple(gamma.shape) not in ((n,), (B, n)):
+        raise ValueError(f"dmp_marginals: gamma must have the shape [{n}] or [{B}, {n}], got {tuple(gamma.shape)}")
+    for t in (weights, gamma, init):
+        if not t.is_cuda:
+            raise _lib.GnodeError("GN-ODE path: tensor is not on a GPU (no CPU fallback exists)")
+    return _DmpMarginals.apply(graph, weights, gamma, init, T)
 
 
 def _batch_numbers(name, value, shapes):

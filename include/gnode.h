@@ -20,7 +20,7 @@
  *     into a hipGraph on first use and one handle may serve several streams (each
  *     with its own workspace).  Functions that DO synchronise `stream` say so below
  *     (gnode_graph_create, gnode_sir_mc_philox with more than 32 seeds,
- *     gnode_sir_mc_philox_nodes, gnode_sir_mc_philox_edges, gnode_sir_mc_philox_traj_edges, gnode_sir_mc_philox_traj with more than 32 seeds or rate arrays, gnode_sir_mc_philox_init, gnode_sir_mc_coins, gnode_dmp_f32, gnode_dmp_init_f32, gnode_dmp_batch_f32, gnode_meanfield_f64, gnode_meanfield_init_f64, gnode_meanfield_rates_f64).
+ *     gnode_sir_mc_philox_nodes, gnode_sir_mc_philox_edges, gnode_sir_mc_philox_traj_edges, gnode_sir_mc_philox_traj with more than 32 seeds or rate arrays, gnode_sir_mc_philox_init, gnode_sir_mc_coins, gnode_dmp_f32, gnode_dmp_init_f32, gnode_dmp_batch_f32, gnode_dmp_batch_backward_f32, gnode_dmp_backward_f32, gnode_meanfield_f64, gnode_meanfield_init_f64, gnode_meanfield_rates_f64).
  *   - process-wide state: (1) a per-device "set up once" table (compute-unit count,
  *     dynamic-LDS kernel attributes), written under a lock by the first
  *     gnode_graph_create on a device and read-only afterwards; (2) the opt-in
@@ -505,6 +505,43 @@ size_t gnode_dmp_batch_lds_bytes(gnode_graph_t g);
 int gnode_dmp_batch_f32(gnode_graph_t g, const float* weights, int64_t w_stride, const float* gamma,
                         int64_t gamma_stride, const float* init /* device fp32 [B][n][3] */, int32_t B,
                         int32_t maxTime, float* out, void* workspace, size_t workspace_bytes, void* stream);
+/* The reverse sweep of that recurrence: the gradient of sum(grad_out * out) with respect to the weights, the recovery
+ * probabilities and the start, for B samples on one graph, fp32.  weights, gamma, init, the strides, B and maxTime are the
+ * forward call's; `out` is what it returned (the sweep reads Pi_{t-1} from it) and grad_out has its shape.
+ *   grad_w      device fp32 [B][nnz], in CSR position order     grad_gamma  device fp32 [B][n]     grad_init  device fp32 [B][n][3]
+ * One row per sample even where the forward's table is shared (stride 0): the caller sums the rows of a shared table.  A
+ * NULL gradient pointer means "not wanted"; grad_w may also be NULL when nnz = 0.  The entry runs the forward again into the
+ * workspace with the forward's own arithmetic, keeping theta_t and phi_t of every step (2 * nnz * 4 bytes per step and sample);
+ * P_t is recomputed from theta_t.  Then, from t = maxTime - 1 down to 1, an edge pass (absent at maxTime - 1) and a node pass
+ * carry the adjoints of theta, phi, Ps_e per edge and of Pi, Pr per node; every sum runs over the rows of one node in
+ * ascending position and every scattered value goes to the reverse edge's slot, written once per step, so there are no
+ * atomics and the result is deterministic.  Two forms, chosen from the graph alone: when
+ * gnode_dmp_batch_backward_lds_bytes(g) -- 7 edge arrays (theta_bar twice, phi_bar, q_bar, two hand-overs, rev) and 2 node
+ * arrays (pi_bar, pr_bar) of 4 bytes, each rounded up to 16 -- fits the 160 KiB of LDS of a gfx950 workgroup, one workgroup
+ * sweeps one sample with its adjoint state in LDS, in ONE launch for the batch; otherwise the passes run over B * n rows and
+ * B * nnz edge slots of the workspace.  Both call the same arithmetic in the same per-element order: a sample's gradient does
+ * not depend on the form or on B.  gnode_dmp_backward_f32 is one sample without strides, in the general form at every graph
+ * size (as the forward's solo entries are), so it returns row b of the batch entry bit for bit.
+ * Where the forward is not finite (theta = 0: a weight of 1 next to a seed) the gradient is unspecified.
+ * The size queries return 0 without a handle, for B < 1 and for maxTime < 2.
+ * GNODE_ERR_ARG: a null out, grad_out, init, gamma or workspace, weights null with nnz > 0, B < 1, maxTime < 2, a stride that
+ * is neither 0 nor the table's length, all three gradient pointers null, an asymmetric pattern; GNODE_ERR_WORKSPACE: a short
+ * workspace; nothing is written to the gradients in either case.  Synchronises `stream` (the reverse-edge table is built per
+ * call). */
+size_t gnode_dmp_batch_backward_lds_bytes(gnode_graph_t g);
+size_t gnode_dmp_batch_backward_workspace_bytes(gnode_graph_t g, int32_t B, int32_t maxTime);
+int gnode_dmp_batch_backward_f32(gnode_graph_t g, const float* weights, int64_t w_stride, const float* gamma,
+                                 int64_t gamma_stride, const float* init /* device fp32 [B][n][3] */, int32_t B,
+                                 int32_t maxTime, const float* out /* the forward's [B][maxTime][n][3] */,
+                                 const float* grad_out /* the same shape */, float* grad_w /* [B][nnz] or NULL */,
+                                 float* grad_gamma /* [B][n] or NULL */, float* grad_init /* [B][n][3] or NULL */,
+                                 void* workspace, size_t workspace_bytes, void* stream);
+size_t gnode_dmp_backward_workspace_bytes(gnode_graph_t g, int32_t maxTime);
+int gnode_dmp_backward_f32(gnode_graph_t g, const float* weights, const float* gamma, const float* init /* device fp32 [n][3] */,
+                           int32_t maxTime, const float* out /* the forward's [maxTime][n][3] */,
+                           const float* grad_out /* the same shape */, float* grad_w /* [nnz] or NULL */,
+                           float* grad_gamma /* [n] or NULL */, float* grad_init /* [n][3] or NULL */,
+                           void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- mean-field baseline (reference ode_nn.py:214-233) ----
  * `runge_kutta_order4(sir, A, ...)`: dS = -beta (A I) S, dI = beta (A I) S - gamma I,
