@@ -16,6 +16,8 @@ struct gnode_graph_s {
     int32_t device;     // the HIP device the arrays live on (current device at gnode_graph_create)
     int32_t* rowptr;    // [n+1]
     int32_t* col;       // [nnz]
+    int32_t *src, *rev; // [nnz] each: the row of a CSR position and the position of its opposite entry
+    bool symmetric;     // every entry has its opposite: DMP and the weighted mean-field serve such graphs only
     int32_t* rowhdr;
     int32_t *hubidx, *seg_lo, *seg_hi, *hub_seg_ptr;     // null when n_hub == 0
     int32_t *persmap[3], *pershub[3], *perssegptr[3], *perssegitem[3];   // GnPers64Maps, null for an absent variant
@@ -92,17 +94,6 @@ void gn_prof_end(int kind, hipStream_t st);
 #define GN_LAUNCH_CHECK() GN_HIP(hipGetLastError())
 
 static inline size_t gn_align(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
-
-// position of column c in row r of a CSR whose rows hold ascending columns, or -1 when (r, c) is no entry
-__device__ __forceinline__ int gn_csr_position(const int* __restrict__ rowptr, const int* __restrict__ col, int r, int c) {
-    int lo = rowptr[r], hi = rowptr[r + 1] - 1;
-    while (lo <= hi) {
-        const int mid = (lo + hi) >> 1, x = col[mid];
-        if (x == c) return mid;
-        if (x < c) lo = mid + 1; else hi = mid - 1;
-    }
-    return -1;
-}
 
 // lanes per row of the lane-group kernels: H/4 rounded up to a power of two
 static inline int gn_lpr(int H) {

@@ -26,18 +26,6 @@
 #include "gnode_common.h"
 #include <algorithm>
 
-__global__ __launch_bounds__(256) void k_dmp_setup(const int* __restrict__ rowptr, const int* __restrict__ col, int n,
-                                                  int* __restrict__ src, int* __restrict__ rev, int* __restrict__ bad) {
-    const int u = blockIdx.x * 256 + threadIdx.x;
-    if (u >= n) return;
-    for (int e = rowptr[u]; e < rowptr[u + 1]; ++e) {
-        src[e] = u;
-        const int found = gn_csr_position(rowptr, col, col[e], u);
-        rev[e] = found;
-        if (found < 0) atomicExch(bad, 1);
-    }
-}
-
 // ------------------------------------------------------------------------------------------------ the recurrence, once
 // On values and on pointers that are already the sample's own, in global memory or in LDS.  The library is built with
 // -ffp-contract=off, so these round as written wherever they are inlined; their operand order is the reference's.
@@ -458,10 +446,11 @@ int gn_dmp_set_attributes() {       // once per device, from gnode_graph_create
 }
 
 // ------------------------------------------------------------------------------------------------ the host side, once
-// The workspace of a call: src, rev | status; for the general form theta x2, phi, ps over B * nnz edge slots and P, Pr, Pi over
-// B * n rows; for the solo entries the 0/1 seed vector after them.  With `base` null only `bytes` means anything.
+// The workspace of a call: room no kernel uses any more (src, rev and a status word lay there while every call built them; the
+// handle holds them now) -- the size queries are pinned by tests/golden/dmp_parent.json -- then for the general form theta x2,
+// phi, ps over B * nnz edge slots and P, Pr, Pi over B * n rows; for the solo entries the 0/1 seed vector after them.  With
+// `base` null only `bytes` means anything.
 struct DmpWorkspace {
-    int *src, *rev, *bad;
     float *theta[2], *phi, *ps, *P, *Pr, *Pi, *seed;
     size_t bytes;
 };
@@ -469,12 +458,12 @@ static DmpWorkspace dmp_carve(gnode_graph_t g, size_t B, bool general, bool seed
     const size_t edges = (size_t)std::max<int64_t>(g->nnz, 1), eb = gn_align(edges * 4);
     const size_t EB = general ? gn_align(B * edges * 4) : 0, NB = general ? gn_align(B * (size_t)g->info.n * 4) : 0;
     size_t at = 0;
-    auto take = [&](size_t bytes) { char* p = base ? (char*)base + at : nullptr; at += bytes; return p; };
+    auto take = [&](size_t bytes) { char* p = base ? (char*)base + at : nullptr; at += bytes; return (float*)p; };
     DmpWorkspace w;
-    w.src = (int*)take(eb); w.rev = (int*)take(eb); w.bad = (int*)take(256);
-    w.theta[0] = (float*)take(EB); w.theta[1] = (float*)take(EB); w.phi = (float*)take(EB); w.ps = (float*)take(EB);
-    w.P = (float*)take(NB); w.Pr = (float*)take(NB); w.Pi = (float*)take(NB);
-    w.seed = (float*)take(seed_vector ? gn_align((size_t)g->info.n * 4) : 0);
+    take(2 * eb + 256);
+    w.theta[0] = take(EB); w.theta[1] = take(EB); w.phi = take(EB); w.ps = take(EB);
+    w.P = take(NB); w.Pr = take(NB); w.Pi = take(NB);
+    w.seed = take(seed_vector ? gn_align((size_t)g->info.n * 4) : 0);
     w.bytes = at;
     return w;
 }
@@ -485,61 +474,82 @@ extern "C" size_t gnode_dmp_batch_workspace_bytes(gnode_graph_t g, int32_t B) {
     return g && B >= 1 ? dmp_carve(g, (size_t)B, !dmp_batch_one_workgroup(g), false, nullptr).bytes : 0;
 }
 
-// what every entry checks first; `who`: the entry's name for the messages, `start`: whether its start state is there
-static int dmp_check_args(const char* who, gnode_graph_t g, const float* weights, const float* gamma, bool start, int32_t maxTime,
-                          const float* out, const void* workspace) {
-    GN_CHECK_ARG(g && gamma && start && out && workspace, "%s: null pointer", who);
+// What a forward or a backward call settles before it writes anything, in this order: its arguments, the form and its launch
+// shape, the workspace's size, the pattern's symmetry.
+//   who       the entry's name for the messages        pointers   whether the entry's own pointers are all there
+//   wanted    whether some output is asked for         solo       a solo entry: the general form at every size
+//   fits      whether the direction's one-workgroup form serves this graph; need(general): its workspace bytes
+struct DmpShape {
+    int n; long nnz;
+    bool one_wg;
+    unsigned ng, eg;                    // blocks of 256 per sample over the nodes and over the edges (the general form)
+    unsigned threads;                   // of the one workgroup per sample
+};
+template <class Need>
+static int dmp_preamble(const char* who, gnode_graph_t g, const float* weights, long w_stride, const float* gamma, long gamma_stride,
+                        bool pointers, const int32_t* seeds_host, int32_t n_seeds, bool wanted, int32_t B, int32_t maxTime, bool solo,
+                        bool (*fits)(gnode_graph_t), Need need, size_t workspace_bytes, DmpShape* s) {
+    GN_CHECK_ARG(g && gamma && pointers, "%s: null pointer", who);
     GN_CHECK_ARG(weights || g->nnz == 0, "%s: weights is null", who);          // no edge, no weight: an empty tensor has no address
     GN_CHECK_ARG(maxTime >= 2, "%s: maxTime must be >= 2 (got %d)", who, maxTime);
+    GN_CHECK_ARG(B >= 1, "%s: B must be >= 1 (got %d)", who, B);
+    GN_CHECK_ARG(w_stride == 0 || w_stride == g->nnz, "%s: w_stride must be 0 or nnz = %ld (got %ld)", who, (long)g->nnz, w_stride);
+    GN_CHECK_ARG(gamma_stride == 0 || gamma_stride == g->info.n, "%s: gamma_stride must be 0 or n = %d (got %ld)", who, g->info.n, gamma_stride);
+    for (int i = 0; i < n_seeds; ++i)
+        GN_CHECK_ARG(seeds_host[i] >= 0 && seeds_host[i] < g->info.n, "%s: seed %d out of range", who, seeds_host[i]);
+    GN_CHECK_ARG(wanted, "%s: no gradient is asked for", who);
+    s->n = g->info.n; s->nnz = g->nnz;
+    s->ng = (unsigned)((s->n + 255) / 256); s->eg = (unsigned)std::max<long>(1, (s->nnz + 255) / 256);
+    s->one_wg = !solo && fits(g);
+    s->threads = (unsigned)std::min<long>(1024, std::max<long>(64, (std::max<long>(s->n, s->nnz) + 63) / 64 * 64));
+    GN_CHECK_ARG(s->one_wg || (size_t)B * std::max(s->ng, s->eg) < ((size_t)1 << 31), "%s: B = %d is too many samples for this graph", who, B);
+    const size_t bytes = need(!s->one_wg);
+    if (workspace_bytes < bytes) {
+        gnode_set_error("%s: workspace %zu < %zu", who, workspace_bytes, bytes);
+        return GNODE_ERR_WORKSPACE;
+    }
+    GN_CHECK_ARG(g->symmetric, "%s: the sparsity pattern is not symmetric (DMP here serves undirected graphs)", who);
     return 0;
 }
 
-// B samples (arguments checked by the entry).  `solo`: one of the two solo entries, which take the general form at every
-// size and carve the solo workspace.  init == nullptr: gnode_dmp_f32, whose n_seeds seeds become output row 0, the run's init.
+// B samples.  `solo`: one of the two solo entries, which take the general form at every size and carve the solo workspace.
+// init == nullptr: gnode_dmp_f32, whose n_seeds seeds become output row 0, the run's init.
 static int dmp_run(const char* who, gnode_graph_t g, const float* weights, long w_stride, const float* gamma, long gamma_stride,
                    const float* init, const int32_t* seeds_host, int32_t n_seeds, int32_t B, int32_t maxTime, float* out, bool solo,
                    void* workspace, size_t workspace_bytes, void* stream) {
-    const long nnz = g->nnz;
-    const int n = g->info.n;
-    const unsigned ng = (unsigned)((n + 255) / 256), eg = (unsigned)std::max<long>(1, (nnz + 255) / 256);
-    const bool one_wg = !solo && dmp_batch_one_workgroup(g);
-    GN_CHECK_ARG(one_wg || (size_t)B * std::max(ng, eg) < ((size_t)1 << 31), "%s: B = %d is too many samples for this graph", who, B);
-    const DmpWorkspace ws = dmp_carve(g, (size_t)B, !one_wg, solo, workspace);
-    if (workspace_bytes < ws.bytes) {
-        gnode_set_error("%s: workspace %zu < %zu", who, workspace_bytes, ws.bytes);
-        return GNODE_ERR_WORKSPACE;
-    }
+    DmpShape s;
+    if (int rc = dmp_preamble(who, g, weights, w_stride, gamma, gamma_stride, (init || seeds_host || n_seeds == 0) && out && workspace,
+                              seeds_host, n_seeds, true, B, maxTime, solo, dmp_batch_one_workgroup,
+                              [&](bool general) { return dmp_carve(g, (size_t)B, general, solo, nullptr).bytes; }, workspace_bytes, &s))
+        return rc;
+    const int n = s.n;
+    const unsigned ng = s.ng, eg = s.eg;
+    const DmpWorkspace ws = dmp_carve(g, (size_t)B, !s.one_wg, solo, workspace);
     hipStream_t st = (hipStream_t)stream;
     const float one = 1.0f;
     if (!init) {
         GN_HIP(hipMemsetAsync(ws.seed, 0, (size_t)n * 4, st));
         for (int i = 0; i < n_seeds; ++i) GN_HIP(hipMemcpyAsync(ws.seed + seeds_host[i], &one, 4, hipMemcpyHostToDevice, st));
     }
-    GN_HIP(hipMemsetAsync(ws.bad, 0, 4, st));
-    hipLaunchKernelGGL(k_dmp_setup, dim3(ng), dim3(256), 0, st, g->rowptr, g->col, n, ws.src, ws.rev, ws.bad);
-    GN_LAUNCH_CHECK();
-    int bad_h = 0;
-    GN_HIP(hipMemcpyAsync(&bad_h, ws.bad, 4, hipMemcpyDeviceToHost, st));
-    GN_HIP(hipStreamSynchronize(st));          // also: `one` and seeds_host are done with
-    GN_CHECK_ARG(!bad_h, "%s: the sparsity pattern is not symmetric (DMP here serves undirected graphs)", who);
-    const DmpBatchArgs a = {weights, w_stride, gamma, gamma_stride, init ? init : out, out, n, maxTime, nnz};
-    if (one_wg) {
-        const long most = std::max<long>(n, nnz);
-        const unsigned threads = (unsigned)std::min<long>(1024, std::max<long>(64, (most + 63) / 64 * 64));
-        hipLaunchKernelGGL(k_dmp_batch_wg, dim3((unsigned)B), dim3(threads), gnode_dmp_batch_lds_bytes(g), st, g->rowptr, ws.src, ws.rev, a);
+    // `one` and seeds_host are done with.  For the entries without a seed list nothing waits on the host any more: only the
+    // documented contract ("Synchronises `stream`", include/gnode.h) keeps the call there
+    GN_HIP(hipStreamSynchronize(st));
+    const DmpBatchArgs a = {weights, w_stride, gamma, gamma_stride, init ? init : out, out, n, maxTime, s.nnz};
+    if (s.one_wg) {
+        hipLaunchKernelGGL(k_dmp_batch_wg, dim3((unsigned)B), dim3(s.threads), gnode_dmp_batch_lds_bytes(g), st, g->rowptr, g->src, g->rev, a);
         GN_LAUNCH_CHECK();
         return 0;
     }
     const dim3 gn((unsigned)B * ng), ge((unsigned)B * eg);
     if (init) hipLaunchKernelGGL(k_dmp_batch_out0, gn, dim3(256), 0, st, a, ng);
     else hipLaunchKernelGGL(k_dmp_seed_out0, gn, dim3(256), 0, st, ws.seed, n, out);
-    hipLaunchKernelGGL(k_dmp_batch_init, ge, dim3(256), 0, st, ws.src, a, eg, ws.theta[0], ws.phi, ws.ps);
+    hipLaunchKernelGGL(k_dmp_batch_init, ge, dim3(256), 0, st, g->src, a, eg, ws.theta[0], ws.phi, ws.ps);
     GN_LAUNCH_CHECK();
     for (int t = 1; t < maxTime; ++t) {
         const int cur = (t - 1) & 1;
-        hipLaunchKernelGGL(k_dmp_batch_node, gn, dim3(256), 0, st, g->rowptr, ws.rev, ws.theta[cur], a, ng, t, ws.P, ws.Pr, ws.Pi);
+        hipLaunchKernelGGL(k_dmp_batch_node, gn, dim3(256), 0, st, g->rowptr, g->rev, ws.theta[cur], a, ng, t, ws.P, ws.Pr, ws.Pi);
         if (t + 1 < maxTime)                 // (the last step's messages have no reader)
-            hipLaunchKernelGGL(k_dmp_batch_edge, ge, dim3(256), 0, st, ws.src, ws.rev, ws.P, ws.theta[cur], a, eg, ws.phi, ws.ps, ws.theta[cur ^ 1]);
+            hipLaunchKernelGGL(k_dmp_batch_edge, ge, dim3(256), 0, st, g->src, g->rev, ws.P, ws.theta[cur], a, eg, ws.phi, ws.ps, ws.theta[cur ^ 1]);
         GN_LAUNCH_CHECK();
     }
     return 0;
@@ -548,38 +558,29 @@ static int dmp_run(const char* who, gnode_graph_t g, const float* weights, long 
 extern "C" int gnode_dmp_f32(gnode_graph_t g, const float* weights, const float* gamma, const int32_t* seeds_host,
                              int32_t n_seeds, int32_t maxTime, float* out, void* workspace, size_t workspace_bytes,
                              void* stream) {
-    const char* who = "gnode_dmp_f32";
-    if (int rc = dmp_check_args(who, g, weights, gamma, seeds_host || n_seeds == 0, maxTime, out, workspace)) return rc;
-    for (int i = 0; i < n_seeds; ++i)
-        GN_CHECK_ARG(seeds_host[i] >= 0 && seeds_host[i] < g->info.n, "%s: seed %d out of range", who, seeds_host[i]);
-    return dmp_run(who, g, weights, 0, gamma, 0, nullptr, seeds_host, n_seeds, 1, maxTime, out, true, workspace, workspace_bytes, stream);
+    return dmp_run("gnode_dmp_f32", g, weights, 0, gamma, 0, nullptr, seeds_host, n_seeds, 1, maxTime, out, true, workspace, workspace_bytes,
+                   stream);
 }
 
 extern "C" int gnode_dmp_init_f32(gnode_graph_t g, const float* weights, const float* gamma, const float* init, int32_t maxTime,
                                   float* out, void* workspace, size_t workspace_bytes, void* stream) {
-    const char* who = "gnode_dmp_init_f32";
-    if (int rc = dmp_check_args(who, g, weights, gamma, init != nullptr, maxTime, out, workspace)) return rc;
-    return dmp_run(who, g, weights, 0, gamma, 0, init, nullptr, 0, 1, maxTime, out, true, workspace, workspace_bytes, stream);
+    GN_CHECK_ARG(init, "gnode_dmp_init_f32: null pointer");
+    return dmp_run("gnode_dmp_init_f32", g, weights, 0, gamma, 0, init, nullptr, 0, 1, maxTime, out, true, workspace, workspace_bytes, stream);
 }
 
 extern "C" int gnode_dmp_batch_f32(gnode_graph_t g, const float* weights, int64_t w_stride, const float* gamma, int64_t gamma_stride,
                                    const float* init, int32_t B, int32_t maxTime, float* out, void* workspace,
                                    size_t workspace_bytes, void* stream) {
-    const char* who = "gnode_dmp_batch_f32";
-    if (int rc = dmp_check_args(who, g, weights, gamma, init != nullptr, maxTime, out, workspace)) return rc;
-    GN_CHECK_ARG(B >= 1, "%s: B must be >= 1 (got %d)", who, B);
-    GN_CHECK_ARG(w_stride == 0 || w_stride == g->nnz, "%s: w_stride must be 0 or nnz = %ld (got %lld)", who, (long)g->nnz, (long long)w_stride);
-    GN_CHECK_ARG(gamma_stride == 0 || gamma_stride == g->info.n, "%s: gamma_stride must be 0 or n = %d (got %lld)", who, g->info.n,
-                 (long long)gamma_stride);
-    return dmp_run(who, g, weights, (long)w_stride, gamma, (long)gamma_stride, init, nullptr, 0, B, maxTime, out, false, workspace,
-                   workspace_bytes, stream);
+    GN_CHECK_ARG(init, "gnode_dmp_batch_f32: null pointer");
+    return dmp_run("gnode_dmp_batch_f32", g, weights, (long)w_stride, gamma, (long)gamma_stride, init, nullptr, 0, B, maxTime, out, false,
+                   workspace, workspace_bytes, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ the reverse sweep's host side
-// The workspace of a backward call: src, rev | status | the tapes of theta and phi, B * (maxTime - 1) * nnz each; for the general
-// form Ps_e, theta_bar x2, phi_bar, q_bar, q_tot, gamma_part over B * nnz edge slots and P, pi_bar, pr_bar over B * n rows.
+// The workspace of a backward call: the same unused room as dmp_carve's (sizes pinned by tests/golden/edge_tables_parent.json) | the
+// tapes of theta and phi, B * (maxTime - 1) * nnz each; for the general form Ps_e, theta_bar x2, phi_bar, q_bar, q_tot, gamma_part
+// over B * nnz edge slots and P, pi_bar, pr_bar over B * n rows.
 struct DmpGradWorkspace {
-    int *src, *rev, *bad;
     float *th_tape, *ph_tape, *ps, *P;
     DmpAdjoint adj;
     size_t bytes;
@@ -590,7 +591,7 @@ static DmpGradWorkspace dmp_grad_carve(gnode_graph_t g, size_t B, size_t maxTime
     size_t at = 0;
     auto take = [&](size_t bytes) { char* p = base ? (char*)base + at : nullptr; at += bytes; return (float*)p; };
     DmpGradWorkspace w;
-    w.src = (int*)take(eb); w.rev = (int*)take(eb); w.bad = (int*)take(256);
+    take(2 * eb + 256);
     w.th_tape = take(tape); w.ph_tape = take(tape);
     w.ps = take(EB); w.P = take(NB);
     w.adj.tb = take(EB); w.adj.tb_next = take(EB); w.adj.phb = take(EB); w.adj.qb = take(EB); w.adj.q_tot = take(EB);
@@ -609,60 +610,45 @@ extern "C" size_t gnode_dmp_backward_workspace_bytes(gnode_graph_t g, int32_t ma
 static int dmp_grad_run(const char* who, gnode_graph_t g, const float* weights, long w_stride, const float* gamma, long gamma_stride,
                         const float* init, int32_t B, int32_t maxTime, const float* out, const float* grad_out, float* grad_w,
                         float* grad_gamma, float* grad_init, bool solo, void* workspace, size_t workspace_bytes, void* stream) {
-    GN_CHECK_ARG(g && gamma && init && out && grad_out && workspace, "%s: null pointer", who);
-    GN_CHECK_ARG(weights || g->nnz == 0, "%s: weights is null", who);
-    GN_CHECK_ARG(B >= 1, "%s: B must be >= 1 (got %d)", who, B);
-    GN_CHECK_ARG(maxTime >= 2, "%s: maxTime must be >= 2 (got %d)", who, maxTime);
-    GN_CHECK_ARG(w_stride == 0 || w_stride == g->nnz, "%s: w_stride must be 0 or nnz = %ld (got %ld)", who, (long)g->nnz, w_stride);
-    GN_CHECK_ARG(gamma_stride == 0 || gamma_stride == g->info.n, "%s: gamma_stride must be 0 or n = %d (got %ld)", who, g->info.n, gamma_stride);
-    GN_CHECK_ARG(grad_w || grad_gamma || grad_init, "%s: no gradient is asked for", who);
-    const long nnz = g->nnz;
-    const int n = g->info.n;
-    const unsigned ng = (unsigned)((n + 255) / 256), eg = (unsigned)std::max<long>(1, (nnz + 255) / 256);
-    const bool one_wg = !solo && dmp_grad_one_workgroup(g);
-    GN_CHECK_ARG(one_wg || (size_t)B * std::max(ng, eg) < ((size_t)1 << 31), "%s: B = %d is too many samples for this graph", who, B);
-    const DmpGradWorkspace ws = dmp_grad_carve(g, (size_t)B, (size_t)maxTime, !one_wg, workspace);
-    if (workspace_bytes < ws.bytes) {
-        gnode_set_error("%s: workspace %zu < %zu", who, workspace_bytes, ws.bytes);
-        return GNODE_ERR_WORKSPACE;
-    }
+    DmpShape s;
+    if (int rc = dmp_preamble(who, g, weights, w_stride, gamma, gamma_stride, init && out && grad_out && workspace, nullptr, 0,
+                              grad_w || grad_gamma || grad_init, B, maxTime, solo, dmp_grad_one_workgroup,
+                              [&](bool general) { return dmp_grad_carve(g, (size_t)B, (size_t)maxTime, general, nullptr).bytes; },
+                              workspace_bytes, &s))
+        return rc;
+    const long nnz = s.nnz;
+    const int n = s.n;
+    const unsigned ng = s.ng, eg = s.eg;
+    const DmpGradWorkspace ws = dmp_grad_carve(g, (size_t)B, (size_t)maxTime, !s.one_wg, workspace);
     hipStream_t st = (hipStream_t)stream;
-    GN_HIP(hipMemsetAsync(ws.bad, 0, 4, st));
-    hipLaunchKernelGGL(k_dmp_setup, dim3(ng), dim3(256), 0, st, g->rowptr, g->col, n, ws.src, ws.rev, ws.bad);
-    GN_LAUNCH_CHECK();
-    int bad_h = 0;
-    GN_HIP(hipMemcpyAsync(&bad_h, ws.bad, 4, hipMemcpyDeviceToHost, st));
-    GN_HIP(hipStreamSynchronize(st));
-    GN_CHECK_ARG(!bad_h, "%s: the sparsity pattern is not symmetric (DMP here serves undirected graphs)", who);
+    GN_HIP(hipStreamSynchronize(st));          // nothing waits on the host here: only the documented contract (include/gnode.h) keeps it
     if (grad_w && nnz) GN_HIP(hipMemsetAsync(grad_w, 0, (size_t)B * nnz * 4, st));         // the sweep accumulates into them
     if (grad_gamma) GN_HIP(hipMemsetAsync(grad_gamma, 0, (size_t)B * n * 4, st));
     if (grad_init) GN_HIP(hipMemsetAsync(grad_init, 0, (size_t)B * n * 12, st));
     const DmpGradArgs a = {weights, w_stride, gamma, gamma_stride, init, out, grad_out, grad_w, grad_gamma, grad_init, ws.th_tape, ws.ph_tape,
                            n, maxTime, nnz};
-    if (one_wg) {
-        const long most = std::max<long>(n, nnz);
-        const unsigned threads = (unsigned)std::min<long>(1024, std::max<long>(64, (most + 63) / 64 * 64));
-        hipLaunchKernelGGL(k_dmp_grad_wg, dim3((unsigned)B), dim3(threads), gnode_dmp_batch_backward_lds_bytes(g), st, g->rowptr, ws.src,
-                           ws.rev, a);
+    if (s.one_wg) {
+        hipLaunchKernelGGL(k_dmp_grad_wg, dim3((unsigned)B), dim3(s.threads), gnode_dmp_batch_backward_lds_bytes(g), st, g->rowptr, g->src,
+                           g->rev, a);
         GN_LAUNCH_CHECK();
         return 0;
     }
     const dim3 gn((unsigned)B * ng), ge((unsigned)B * eg);
-    hipLaunchKernelGGL(k_dmp_tape_start, ge, dim3(256), 0, st, ws.src, a, eg, ws.ps);
+    hipLaunchKernelGGL(k_dmp_tape_start, ge, dim3(256), 0, st, g->src, a, eg, ws.ps);
     for (int t = 1; t + 1 < maxTime; ++t) {
-        hipLaunchKernelGGL(k_dmp_tape_node, gn, dim3(256), 0, st, g->rowptr, ws.rev, a, ng, t, ws.P);
-        hipLaunchKernelGGL(k_dmp_tape_edge, ge, dim3(256), 0, st, ws.src, ws.rev, ws.P, a, eg, t, ws.ps);
+        hipLaunchKernelGGL(k_dmp_tape_node, gn, dim3(256), 0, st, g->rowptr, g->rev, a, ng, t, ws.P);
+        hipLaunchKernelGGL(k_dmp_tape_edge, ge, dim3(256), 0, st, g->src, g->rev, ws.P, a, eg, t, ws.ps);
     }
     GN_LAUNCH_CHECK();
     for (float* zero : {ws.adj.tb, ws.adj.phb, ws.adj.qb}) GN_HIP(hipMemsetAsync(zero, 0, (size_t)B * std::max<long>(nnz, 1) * 4, st));
     for (float* zero : {ws.adj.pib, ws.adj.prb}) GN_HIP(hipMemsetAsync(zero, 0, (size_t)B * n * 4, st));
     DmpAdjoint A = ws.adj;
     for (int t = maxTime - 1; t >= 1; --t, dmp_adjoint_swap(A)) {
-        if (t + 1 < maxTime) hipLaunchKernelGGL(k_dmp_grad_edge, ge, dim3(256), 0, st, ws.src, a, A, eg, t);
-        hipLaunchKernelGGL(k_dmp_grad_node, gn, dim3(256), 0, st, g->rowptr, ws.rev, a, A, ng, t);
+        if (t + 1 < maxTime) hipLaunchKernelGGL(k_dmp_grad_edge, ge, dim3(256), 0, st, g->src, a, A, eg, t);
+        hipLaunchKernelGGL(k_dmp_grad_node, gn, dim3(256), 0, st, g->rowptr, g->rev, a, A, ng, t);
         GN_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(k_dmp_grad_start_edge, ge, dim3(256), 0, st, ws.src, a, A, eg);
+    hipLaunchKernelGGL(k_dmp_grad_start_edge, ge, dim3(256), 0, st, g->src, a, A, eg);
     hipLaunchKernelGGL(k_dmp_grad_start_node, gn, dim3(256), 0, st, g->rowptr, a, A, ng);
     GN_LAUNCH_CHECK();
     return 0;

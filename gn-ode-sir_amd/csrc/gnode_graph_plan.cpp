@@ -154,6 +154,48 @@ static void plan_persg(GnGraphPlan& P, const int32_t* rowptr, int32_t n) {
     }
 }
 
+// position of column c in row r of a CSR whose rows hold ascending columns, or -1 when (r, c) is no entry
+static int32_t csr_position(const int32_t* rowptr, const int32_t* col, int32_t r, int32_t c) {
+    int32_t lo = rowptr[r], hi = rowptr[r + 1] - 1;
+    while (lo <= hi) {
+        const int32_t mid = (lo + hi) >> 1, x = col[mid];
+        if (x == c) return mid;
+        if (x < c) lo = mid + 1; else hi = mid - 1;
+    }
+    return -1;
+}
+
+// src and rev of every CSR position (gnode_graph_plan.h); `symmetric` follows from rev.  rev[p] is csr_position's answer for
+// (col[p], src[p]).  Where every row's columns ascend strictly -- every graph the project makes -- a merge gives that answer
+// without searching: the questions put to row v come with ascending u (rows are visited in order, and v stands once in each),
+// so `next[v]` only ever moves forward over row v.  One pass over the entries then, which is what keeps gnode_graph_create's
+// cost near what it was (a search per entry: 14 ns each measured, 2.5 ms more per handle at fb-social size).
+static void plan_edge_tables(GnGraphPlan& P, const int32_t* rowptr, const int32_t* col, int32_t n) {
+    const size_t nnz = (size_t)rowptr[n];
+    P.src.resize(nnz);
+    P.rev.resize(nnz);
+    bool ascending = true;
+    for (int32_t u = 0; u < n; ++u)
+        for (int32_t p = rowptr[u]; p < rowptr[u + 1]; ++p) {
+            P.src[p] = u;
+            if (p > rowptr[u] && col[p] <= col[p - 1]) ascending = false;
+        }
+    std::vector<int32_t> next;
+    if (ascending) next.assign(rowptr, rowptr + n);
+    for (int32_t u = 0; u < n; ++u)
+        for (int32_t p = rowptr[u]; p < rowptr[u + 1]; ++p) {
+            const int32_t v = col[p];
+            int32_t r;
+            if (ascending) {
+                int32_t& c = next[v];
+                while (c < rowptr[v + 1] && col[c] < u) ++c;
+                r = c < rowptr[v + 1] && col[c] == u ? c : -1;
+            } else r = csr_position(rowptr, col, v, u);
+            P.rev[p] = r;
+            if (r < 0) P.symmetric = false;
+        }
+}
+
 GnGraphPlan gn_plan_graph(const int32_t* rowptr, const int32_t* col, int32_t n, int64_t nnz) {
     GnGraphPlan P;
     if (!(rowptr[0] == 0 && rowptr[n] == nnz)) { P.error = "gnode_graph_create: rowptr[0] != 0 or rowptr[n] != nnz"; return P; }
@@ -174,6 +216,7 @@ GnGraphPlan gn_plan_graph(const int32_t* rowptr, const int32_t* col, int32_t n, 
     plan_hubs(P, rowptr, n);
     plan_pers64(P, rowptr, n);
     plan_persg(P, rowptr, n);
+    plan_edge_tables(P, rowptr, col, n);
     return P;
 }
 

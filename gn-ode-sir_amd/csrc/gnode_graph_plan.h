@@ -50,6 +50,12 @@ struct GnGraphPlan {
     // segments one workgroup has to stage in LDS
     std::vector<int32_t> pgmap;
     int32_t pgoff[3][4], pgids[3][4], pgsegs[3][4];
+    // edge tables of the DMP, mean-field and Monte-Carlo scan kernels, per CSR position p
+    std::vector<int32_t> src;      // [nnz]: the row p lies in
+    std::vector<int32_t> rev;      // [nnz]: the position of the opposite entry (col[p], src[p]), -1 where the pattern has none;
+                                   // a self-loop is its own reverse.  Defined by a binary search that takes a row's columns
+                                   // to ascend; in a row that does not it is whatever that search finds, as it always was
+    bool symmetric = true;         // no rev entry is -1 (true for nnz == 0)
 };
 
 // Checks the CSR (monotone rowptr from 0 to nnz, col in [0, n)) and plans it.  rowptr [n+1], col [nnz], n >= 1.

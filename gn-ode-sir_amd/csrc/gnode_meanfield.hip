@@ -23,25 +23,13 @@ __global__ __launch_bounds__(256) void k_mf_comb(const double* __restrict__ y, c
     out[i] = y[i] + h * s;
 }
 
-// k = f(y)
-__global__ __launch_bounds__(256) void k_mf_rhs(const int* __restrict__ rowptr, const int* __restrict__ col, int n, double beta,
-                                               const double* __restrict__ gamma, const double* __restrict__ y,
-                                               double* __restrict__ k) {
-    const int u = blockIdx.x * 256 + threadIdx.x;
-    if (u >= n) return;
-    const double* I = y + n;
-    double ai = 0.0;
-    for (int e = rowptr[u]; e < rowptr[u + 1]; ++e) ai += I[col[e]];
-    const double inf = beta * (ai * y[u]), rec = gamma[u] * I[u];
-    k[u] = -inf; k[n + u] = inf - rec; k[2 * (size_t)n + u] = rec;
-}
-
-// gnode_meanfield_rates_f64: k = f(y) for B samples on one graph, one thread per row r = b * n + v of the [3][B * n] state.
-// Row r gathers from its own sample's I; w_in[p] is the weight of the contact col[p] -> v, beta and gamma are [B][n].  With
-// W = false and one constant beta this is k_mf_rhs's arithmetic, operation for operation (beta * (ai * S)).
+// k = f(y) for B samples on one graph, one thread per row r = b * n + v of the [3][B * n] state (the scalar entries: B = 1,
+// rows = n).  Row r gathers from its own sample's I; w_in[p] is the weight of the contact col[p] -> v, gamma is [B][n].  The
+// infection rate is beta[r] with BETA, else the one number beta_s: the scalar entries' beta, and 1.0 (an exact factor) for
+// gnode_meanfield_rates_f64 without a beta array.
 template <bool W, bool BETA>
 __global__ __launch_bounds__(256) void k_mf_rhs_rates(const int* __restrict__ rowptr, const int* __restrict__ col, int n, int rows,
-                                                     const double* __restrict__ beta, const double* __restrict__ w_in,
+                                                     const double* __restrict__ beta, double beta_s, const double* __restrict__ w_in,
                                                      const double* __restrict__ gamma, const double* __restrict__ y,
                                                      double* __restrict__ k) {
     const int r = blockIdx.x * 256 + threadIdx.x;
@@ -50,21 +38,16 @@ __global__ __launch_bounds__(256) void k_mf_rhs_rates(const int* __restrict__ ro
     const double* I = y + rows + (r - v);                             // sample b's I: y[rows + b * n + .]
     double ai = 0.0;
     for (int e = rowptr[v]; e < rowptr[v + 1]; ++e) ai += W ? w_in[e] * I[col[e]] : I[col[e]];
-    const double inf = BETA ? beta[r] * (ai * y[r]) : ai * y[r], rec = gamma[r] * I[v];
+    const double inf = (BETA ? beta[r] : beta_s) * (ai * y[r]), rec = gamma[r] * I[v];
     k[r] = -inf; k[rows + r] = inf - rec; k[2 * (size_t)rows + r] = rec;
 }
 
-// w_in[p] = w[rev(p)]: the weight of the contact col[p] -> v for position p of row v (w is source = row, target = column).
-// The reverse position is k_dmp_setup's (gn_csr_position); a self-loop is its own reverse.
-__global__ __launch_bounds__(256) void k_mf_w_in(const int* __restrict__ rowptr, const int* __restrict__ col, int n,
-                                                const double* __restrict__ w, double* __restrict__ w_in, int* __restrict__ bad) {
-    const int v = blockIdx.x * 256 + threadIdx.x;
-    if (v >= n) return;
-    for (int p = rowptr[v]; p < rowptr[v + 1]; ++p) {
-        const int found = gn_csr_position(rowptr, col, col[p], v);
-        w_in[p] = found < 0 ? 0.0 : w[found];
-        if (found < 0) atomicExch(bad, 1);
-    }
+// w_in[p] = w[rev[p]]: the weight of the contact col[p] -> v for position p of row v (w is source = row, target = column).
+// rev is the handle's table of a symmetric pattern (every entry >= 0); a self-loop is its own reverse.
+__global__ __launch_bounds__(256) void k_mf_w_in(const int* __restrict__ rev, long nnz, const double* __restrict__ w,
+                                                double* __restrict__ w_in) {
+    const long p = (long)blockIdx.x * 256 + threadIdx.x;
+    if (p < nnz) w_in[p] = w[rev[p]];
 }
 
 // err = max_i |h sum_j e_j k_j| / (atol + rtol max(|y_i|, |ynew_i|))   (non-negative doubles order like their bits)
@@ -112,7 +95,7 @@ __global__ __launch_bounds__(256) void k_mf_emit(const double* __restrict__ y, i
 // rows = the state's rows: n, or B * n of the rates entry
 static size_t mf_workspace_bytes(size_t rows) {
     const size_t v = gn_align(3 * rows * sizeof(double));
-    return 10 * v + gn_align(rows * sizeof(double)) + 256;                   // y, ynew, ytmp, K[7] | seed | err, bad
+    return 10 * v + gn_align(rows * sizeof(double)) + 256;                   // y, ynew, ytmp, K[7] | seed | err
 }
 
 extern "C" size_t gnode_meanfield_workspace_bytes(gnode_graph_t g) {
@@ -159,18 +142,13 @@ static int meanfield_impl(const char* who, gnode_graph_t g, const int32_t* seeds
     unsigned long long* err = (unsigned long long*)(ws + 10 * v + gn_align((size_t)n * sizeof(double)));
     // K is indexed K[j * len + i]: lay the 7 stages out back to back in elements (7 * len doubles fit in 7 aligned slots)
     const unsigned ng = (unsigned)((n + 255) / 256), lg = (unsigned)((len + 255) / 256);
+    const double* beta_rows = rates ? rates->beta : nullptr;          // [B][n], or null: the scalar beta (1 for the rates entry)
     const double* w_in = nullptr;
     if (rates && rates->w && g->nnz > 0) {                            // before anything is written to the outputs
-        int* bad = (int*)(err + 1);
+        GN_CHECK_ARG(g->symmetric, "%s: the sparsity pattern is not symmetric (a directed contact is a zero weight on the reverse entry)", who);
         double* tab = (double*)(ws + mf_workspace_bytes((size_t)n));
-        GN_HIP(hipMemsetAsync(bad, 0, sizeof(int), st));
-        hipLaunchKernelGGL(k_mf_w_in, dim3((unsigned)((g->info.n + 255) / 256)), dim3(256), 0, st, g->rowptr, g->col, g->info.n,
-                           rates->w, tab, bad);
+        hipLaunchKernelGGL(k_mf_w_in, dim3((unsigned)((g->nnz + 255) / 256)), dim3(256), 0, st, g->rev, (long)g->nnz, rates->w, tab);
         GN_LAUNCH_CHECK();
-        int bad_h = 0;
-        GN_HIP(hipMemcpyAsync(&bad_h, bad, sizeof(int), hipMemcpyDeviceToHost, st));
-        GN_HIP(hipStreamSynchronize(st));
-        GN_CHECK_ARG(!bad_h, "%s: the sparsity pattern is not symmetric (a directed contact is a zero weight on the reverse entry)", who);
         w_in = tab;
     }
     const double one = 1.0;
@@ -196,13 +174,9 @@ static int meanfield_impl(const char* who, gnode_graph_t g, const int32_t* seeds
         {35.0 / 384, 0, 500.0 / 1113, 125.0 / 192, -2187.0 / 6784, 11.0 / 84}};
     static const double B4[7] = {5179.0 / 57600, 0, 7571.0 / 16695, 393.0 / 640, -92097.0 / 339200, 187.0 / 2100, 1.0 / 40};
     auto rhs = [&](const double* yy, double* kk) {
-        if (!rates) {
-            hipLaunchKernelGGL(k_mf_rhs, dim3(ng), dim3(256), 0, st, g->rowptr, g->col, n, beta, gamma, yy, kk);
-            return;
-        }
-        auto kern = w_in ? (rates->beta ? k_mf_rhs_rates<true, true> : k_mf_rhs_rates<true, false>)
-                         : (rates->beta ? k_mf_rhs_rates<false, true> : k_mf_rhs_rates<false, false>);
-        hipLaunchKernelGGL(kern, dim3(ng), dim3(256), 0, st, g->rowptr, g->col, g->info.n, n, rates->beta, w_in, gamma, yy, kk);
+        auto kern = w_in ? (beta_rows ? k_mf_rhs_rates<true, true> : k_mf_rhs_rates<true, false>)
+                         : (beta_rows ? k_mf_rhs_rates<false, true> : k_mf_rhs_rates<false, false>);
+        hipLaunchKernelGGL(kern, dim3(ng), dim3(256), 0, st, g->rowptr, g->col, g->info.n, n, beta_rows, rates ? 1.0 : beta, w_in, gamma, yy, kk);
     };
     rhs(y, K);                                                        // k1 (FSAL: later steps reuse k7)
     double t = 0.0, h = 1e-3;

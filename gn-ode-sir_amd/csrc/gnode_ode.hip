@@ -561,6 +561,8 @@ static hipError_t graph_upload_plan(gnode_graph_s* g, const GnGraphPlan& P, cons
 #define UP(...) do { const hipError_t e_ = graph_upload(g, __VA_ARGS__); if (e_ != hipSuccess) return e_; } while (0)
     UP(&g->rowptr, rowptr_host, (size_t)g->info.n + 1);
     UP(&g->col, col_host, (size_t)g->nnz, 1);
+    UP(&g->src, P.src, 1);
+    UP(&g->rev, P.rev, 1);
     UP(&g->rowhdr, P.rowhdr);
     if (P.n_hub > 0) {
         UP(&g->hubidx, P.hubidx);
@@ -601,6 +603,7 @@ extern "C" int gnode_graph_create(const int32_t* rowptr_host, const int32_t* col
     gnode_graph_s* g = new gnode_graph_s();
     g->info = gn_graph_info(plan, n, g_dev_cu[dev]);
     g->nnz = nnz; g->max_degree = plan.max_degree; g->n_bigrow = plan.n_bigrow; g->n_seg = plan.n_seg;
+    g->symmetric = plan.symmetric;
     g->device = dev;
     const hipError_t e = graph_upload_plan(g, plan, rowptr_host, col_host);
     if (e != hipSuccess) {

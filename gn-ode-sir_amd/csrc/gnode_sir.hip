@@ -575,13 +575,6 @@ __global__ __launch_bounds__(256) void k_sir_finalize(const uint32_t* __restrict
     }
 }
 
-// src[e] for every CSR position (row expansion), once per call
-__global__ void k_expand_rows(const int* __restrict__ rowptr, int n, int* __restrict__ src) {
-    const int u = blockIdx.x * blockDim.x + threadIdx.x;
-    if (u >= n) return;
-    for (int e = rowptr[u]; e < rowptr[u + 1]; ++e) src[e] = u;
-}
-
 // --------------------------------------------------------------------------- parity kernel (recorded coin stream)
 __device__ __forceinline__ int block_rank(bool pred, int* wave_tot, int& total) {
     // stable exclusive rank of `pred` lanes over the 256-thread block
@@ -768,8 +761,8 @@ static int sir_mc_philox_impl(const SirCall& c) {
     const int form = restate ? SIR_EDGES : r.form;
     char* ws = (char*)c.workspace;
     uint32_t* hist = (uint32_t*)(ws + L.hist);
-    int32_t *seeds = (int32_t*)(ws + L.seeds), *src = (int32_t*)(ws + L.rows);
-    unsigned long long* stats = c.stats_host ? (unsigned long long*)(ws + L.rows) : nullptr;   // the frontier walk leaves the region unused
+    int32_t* seeds = (int32_t*)(ws + L.seeds);
+    unsigned long long* stats = c.stats_host ? (unsigned long long*)(ws + L.rows) : nullptr;
     const unsigned long long *thr_b = (const unsigned long long*)(ws + L.thr), *thr_g = thr_b + (thr.rates.size() - (form ? n : 0));
     const unsigned long long* thr_start = (const unsigned long long*)(ws + L.start);
     if (stats) GN_HIP(hipMemsetAsync(stats, 0, 4 * sizeof(unsigned long long), st));
@@ -800,7 +793,6 @@ static int sir_mc_philox_impl(const SirCall& c) {
         const SirLaunch P = sir_launch_plan(n, g->n_bigrow, g->info.num_cu, c.sims, c.edge_scan);
         const bool frontier = P.path == SIR_FRONTIER_LDS || P.path == SIR_FRONTIER_MEM;
         void* tail = P.path == SIR_FRONTIER_MEM || P.path == SIR_SCAN_MEM ? ws + L.tail : nullptr;   // the lists / the state, when not in LDS
-        if (!frontier) hipLaunchKernelGGL(k_expand_rows, dim3((n + 255) / 256), dim3(256), 0, st, g->rowptr, n, src);
         // the drawn start is a set of instances of its own (INIT): the seed-list instances do not carry it
         sir_dispatch(form, traj, c.init != nullptr, [&](auto K) {
             using Kt = decltype(K);
@@ -817,7 +809,7 @@ static int sir_mc_philox_impl(const SirCall& c) {
                                    (long)c.sim_offset, T, k0, k1, hist, (int32_t*)tail, stats, tr, in);
             } else {
                 auto kernel = P.path == SIR_SCAN_LDS ? Kt::scan_lds : Kt::scan_mem;
-                hipLaunchKernelGGL(kernel, dim3(P.grid), dim3(P.threads), P.lds, st, src, g->col, (long)g->nnz, n, seeds, c.n_seeds, tb, tg, (long)c.sims,
+                hipLaunchKernelGGL(kernel, dim3(P.grid), dim3(P.threads), P.lds, st, g->src, g->col, (long)g->nnz, n, seeds, c.n_seeds, tb, tg, (long)c.sims,
                                    (long)c.sim_offset, T, k0, k1, hist, (uint8_t*)tail, tr, in);
             }
         });

@@ -16,7 +16,8 @@ enum { SIR_SCALAR = 0, SIR_NODES = 1, SIR_EDGES = 2, SIR_INIT = 3 };   // rate f
 // Byte offsets into a call's workspace (each 256-byte aligned), and what each form needs of it.
 struct SirLayout {
     size_t hist, seeds;   // uint32 [2][T][n] event histograms (up to `seeds`), int32 [4096] seed ids
-    size_t rows;       // int32 [max(nnz, 1)]: the scan's row expansion; the counted call's tally (the frontier walk leaves it unused)
+    size_t rows;       // int32 [max(nnz, 1)]: the counted call's tally; the rest is unused (the scan's row expansion lay here, it is
+                       // the handle's src now) and stays because the workspace sizes are pinned
     size_t tail;       // one region, two users that never run together: the scan's state in memory (2048 x 2n bytes, n past the
                        // LDS state) and the frontier's global lists (kFrontierGlobalGrid x 3n int32, lists past the LDS form)
     size_t thr;        // uint64 rate thresholds: [n beta | n gamma] per node, [nnz entries | n gamma] per edge

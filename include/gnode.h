@@ -492,7 +492,7 @@ int gnode_dmp_init_f32(gnode_graph_t g, const float* weights, const float* gamma
  *   gamma     device fp32 [n] (gamma_stride 0) or [B][n] (gamma_stride n)
  *   init      device fp32 [B][n][3] = (pS, pI, pR), not validated here
  *   out       device fp32 [B][maxTime][n][3], out[b][0] = init[b]
- * The source / reverse-edge tables are built once per call.  Two forms, chosen from the graph alone: when
+ * The source / reverse-edge tables are the handle's.  Two forms, chosen from the graph alone: when
  * gnode_dmp_batch_lds_bytes(g) -- 5 edge arrays (theta twice, phi, Ps_e, rev) and 3 node arrays (P, Pi, Pr) of 4 bytes,
  * each rounded up to 16 -- fits the 160 KiB of LDS of a gfx950 workgroup, one workgroup integrates one sample over the whole
  * horizon from LDS, in ONE launch for the batch; otherwise the node and edge passes run over B * n rows and B * nnz edge slots
@@ -526,8 +526,7 @@ int gnode_dmp_batch_f32(gnode_graph_t g, const float* weights, int64_t w_stride,
  * The size queries return 0 without a handle, for B < 1 and for maxTime < 2.
  * GNODE_ERR_ARG: a null out, grad_out, init, gamma or workspace, weights null with nnz > 0, B < 1, maxTime < 2, a stride that
  * is neither 0 nor the table's length, all three gradient pointers null, an asymmetric pattern; GNODE_ERR_WORKSPACE: a short
- * workspace; nothing is written to the gradients in either case.  Synchronises `stream` (the reverse-edge table is built per
- * call). */
+ * workspace; nothing is written to the gradients in either case.  Synchronises `stream`. */
 size_t gnode_dmp_batch_backward_lds_bytes(gnode_graph_t g);
 size_t gnode_dmp_batch_backward_workspace_bytes(gnode_graph_t g, int32_t B, int32_t maxTime);
 int gnode_dmp_batch_backward_f32(gnode_graph_t g, const float* weights, int64_t w_stride, const float* gamma,
@@ -567,7 +566,7 @@ int gnode_meanfield_init_f64(gnode_graph_t g, const double* init, double beta, c
  *     dS_v = -beta[b][v] S_v sum_{p in row v} w_in[p] I[b][col[p]],  dI_v = -dS_v - gamma[b][v] I_v,  dR_v = gamma[b][v] I_v
  * where w_in[p] = w[rev(p)] is the weight of the contact col[p] -> v.  `w` comes in the convention of
  * gnode_sir_mc_philox_edges and gnode_dmp_f32 (w[p], in row u with col[p] = v, is the rate at which u infects v); the entry
- * transposes it into the workspace once per call.  With `w` given the sparsity pattern must be symmetric (GNODE_ERR_ARG
+ * gathers w_in into the workspace through the handle's reverse-edge table.  With `w` given the sparsity pattern must be symmetric (GNODE_ERR_ARG
  * otherwise); a directed contact is a zero on the reverse entry; a self-loop is its own reverse and counts once.
  *   init    device fp64 [B][n][3] = (pS, pI, pR) per sample and node
  *   beta    device fp64 [B][n], indexed by the TARGET node (x[:, 3]'s convention), or NULL = 1

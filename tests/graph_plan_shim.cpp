@@ -36,6 +36,15 @@ const int32_t* gp_array(void* h, int which, int64_t* len) {
     return v->data();
 }
 
+// the edge tables, apart from gp_array (tests/golden/graph_plan_parent.json has no entry for them): 0 src, 1 rev
+const int32_t* gp_edge_table(void* h, int which, int64_t* len) {
+    const GnGraphPlan& P = *(GnGraphPlan*)h;
+    const std::vector<int32_t>& v = which == 0 ? P.src : P.rev;
+    *len = (int64_t)v.size();
+    return v.data();
+}
+int gp_symmetric(void* h) { return ((GnGraphPlan*)h)->symmetric; }
+
 static int put(bool ok, const PersPlan& q, int32_t* o) {
     if (!ok) return 0;
     const int f[10] = {q.nt, q.wgs, q.span, q.gpx, q.per, q.slots, q.n_xcc, q.rounds, q.concurrent, q.fstride};

@@ -5,7 +5,10 @@ object with ctypes and checks
   * that every array the handle uploads, every scalar it keeps and every per-call plan (k_pers64, its adjoint sweep, k_persg)
     is the one tests/golden/graph_plan_parent.json recorded from the commit before the plan unit existed (SHA-256 of the
     arrays' little-endian bytes; the recipe is in the fixture's "recipe" entry), and
-  * the invariants the kernels rely on, recomputed in numpy from the CSR alone.
+  * the invariants the kernels rely on, recomputed in numpy from the CSR alone, and
+  * the edge tables src, rev and `symmetric` (younger than that fixture, so read through shim functions of their own): the
+    identities that define them, tests/dmp_grad_model.py's restatement, the small graphs at which a search or an expansion goes
+    wrong, an asymmetric pattern; the unit runs once under AddressSanitizer and UBSan in a program of its own.
 The argument checks of gnode_graph_create (which sit in front of any HIP call) go through the hipcc-built library."""
 import ctypes as C
 import hashlib
@@ -87,6 +90,8 @@ def load_shim(so):
     lib.gp_free.restype, lib.gp_free.argtypes = None, [vp]
     lib.gp_scalars.restype, lib.gp_scalars.argtypes = None, [vp, vp]
     lib.gp_array.restype, lib.gp_array.argtypes = vp, [vp, C.c_int, C.POINTER(i64)]
+    lib.gp_edge_table.restype, lib.gp_edge_table.argtypes = vp, [vp, C.c_int, C.POINTER(i64)]
+    lib.gp_symmetric.restype, lib.gp_symmetric.argtypes = C.c_int, [vp]
     lib.gp_pers64_plan.restype, lib.gp_pers64_plan.argtypes = C.c_int, [vp, C.c_int, lng, C.c_int, vp]
     lib.gp_pers_bwd64_plan.restype, lib.gp_pers_bwd64_plan.argtypes = C.c_int, [vp, C.c_int, lng, C.c_int, vp]
     lib.gp_persg_plan.restype, lib.gp_persg_plan.argtypes = C.c_int, [vp, C.c_int, lng, C.c_int, C.c_int, vp]
@@ -113,6 +118,13 @@ class Plan:
             ln = C.c_int64(0)
             p = lib.gp_array(self.h, k, C.byref(ln))
             self.arrays[name] = None if ln.value < 0 else np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_int32)), (ln.value,)).copy() if ln.value else np.zeros(0, np.int32)
+        self.src, self.rev = (self._edge_table(k) for k in range(2))   # apart from ARRAYS: the parent's fixture has no entry for them
+        self.symmetric = bool(lib.gp_symmetric(self.h))
+
+    def _edge_table(self, which):
+        ln = C.c_int64(0)
+        p = self.lib.gp_edge_table(self.h, which, C.byref(ln))
+        return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_int32)), (ln.value,)).copy() if ln.value else np.zeros(0, np.int32)
 
     def close(self):
         self.lib.gp_free(self.h)
@@ -291,6 +303,118 @@ def test_plan_invariants(lib, graphs):
             assert p.scalars["pers_present"] == [0, 0, 0], name
         _check_persg(p, hub_t, seg)
         p.close()
+
+
+# --------------------------------------------------------------------------- the edge tables: src, rev, symmetric
+def _edge_tables_hold(p, name):
+    """the tables of a symmetric pattern, against the CSR itself and against tests/dmp_grad_model.py's restatement"""
+    from dmp_grad_model import tables
+    src, rev = p.src.astype(np.int64), p.rev.astype(np.int64)
+    assert p.src.dtype == p.rev.dtype == np.int32 and src.shape == rev.shape == p.ci.shape, name
+    assert np.array_equal(src, np.repeat(np.arange(p.n), np.diff(p.rp))), name
+    assert p.symmetric, name
+    assert np.array_equal(p.ci[rev], src) and np.array_equal(src[rev], p.ci) and np.array_equal(rev[rev], np.arange(rev.shape[0])), name
+    want_src, want_rev = tables(p.rp, p.ci)
+    assert np.array_equal(src, want_src) and np.array_equal(rev, want_rev), name
+
+
+def _rows(*rows):
+    """CSR of explicit rows of ascending columns"""
+    return np.cumsum([0] + [len(r) for r in rows]).astype(np.int32), np.array([c for r in rows for c in r], np.int32)
+
+
+SMALL = {"isolated_middle": _rows([1], [0], [], [4], [3]),                      # node 2 has no entry
+         "path5_loop2": _rows([1], [0, 2], [1, 2, 3], [2, 4], [3]),             # a self-loop on node 2
+         "rows_1_2_3": _rows([1], [0, 2], [1, 3, 4], [2], [2])}                 # both ends of the search
+
+
+def test_edge_tables(lib, graphs):
+    for name, (rp, ci) in {**graphs, **SMALL}.items():
+        p = Plan(lib, rp, ci)
+        _edge_tables_hold(p, name)
+        p.close()
+    p = Plan(lib, *graphs["single_node"])
+    assert p.src.shape == p.rev.shape == (0,) and p.symmetric
+    p.close()
+    p = Plan(lib, *SMALL["path5_loop2"])
+    assert p.ci[4] == 2 and p.src[4] == 2 and p.rev[4] == 4                     # the diagonal entry is its own reverse
+    p.close()
+
+
+def _karate_less_one(graphs):
+    """(rowptr, col, u, v): karate without the directed entry (u, v), taken from the middle of a row"""
+    rp, ci = graphs["karate"]
+    row = int(np.argmax(np.diff(rp) >= 3))
+    k = int(rp[row]) + 1                                                        # neither end of the row
+    rp2 = rp.copy()
+    rp2[row + 1:] -= 1
+    return rp2, np.delete(ci, k), row, int(ci[k])
+
+
+def test_edge_tables_of_an_asymmetric_pattern(lib, graphs):
+    """karate with one directed entry taken out of the middle of a row: its opposite has no reverse, every other entry does"""
+    rp2, ci2, u, v = _karate_less_one(graphs)
+    p = Plan(lib, rp2, ci2)
+    assert not p.error and not p.symmetric
+    src, rev = p.src.astype(np.int64), p.rev.astype(np.int64)
+    assert np.array_equal(src, np.repeat(np.arange(p.n), np.diff(p.rp)))
+    lost = np.flatnonzero(rev == -1)
+    assert lost.shape == (1,) and (src[lost[0]], p.ci[lost[0]]) == (v, u)      # the entry (v, u), whose reverse (u, v) is gone
+    ok = rev >= 0
+    assert np.all(rev[ok] < rev.shape[0])
+    assert np.array_equal(p.ci[rev[ok]], src[ok]) and np.array_equal(src[rev[ok]], p.ci[ok]) and np.array_equal(rev[rev[ok]], np.flatnonzero(ok))
+    p.close()
+
+
+def _searched_rev(rp, ci):
+    """rev by the binary search every handle has used (lo / hi / mid over the row of col[p], for the column src[p]), whatever
+    the row's order: what the plan has to return for a CSR whose rows do not ascend, which gnode_graph_create accepts"""
+    rev = np.full(len(ci), -1, np.int32)
+    for u in range(len(rp) - 1):
+        for p in range(rp[u], rp[u + 1]):
+            lo, hi = int(rp[ci[p]]), int(rp[ci[p] + 1]) - 1
+            while lo <= hi:
+                mid = (lo + hi) >> 1
+                if ci[mid] == u:
+                    rev[p] = mid
+                    break
+                lo, hi = (mid + 1, hi) if ci[mid] < u else (lo, mid - 1)
+    return rev
+
+
+UNORDERED = {"descending_row": _rows([1, 2, 3], [0], [0], [0, 4, 2], [3]),     # row 3 does not ascend: the search misses (3, 0)
+             "duplicate_column": _rows([1, 1, 2], [0, 2], [0, 1]),              # (0, 1) twice: the search settles on one of them
+             "equal_neighbours_late": _rows([1], [0, 2], [1, 3, 3], [2])}
+
+
+def test_edge_tables_of_rows_that_do_not_ascend(lib, graphs):
+    """the search's answer, entry for entry, where the plan cannot take the one-pass merge -- and on the ordered graphs too"""
+    for name, (rp, ci) in {**UNORDERED, **SMALL, "karate": graphs["karate"], "karate_less_one": _karate_less_one(graphs)[:2]}.items():
+        p = Plan(lib, rp, ci)
+        assert not p.error, name
+        want = _searched_rev(p.rp, p.ci)
+        assert np.array_equal(p.rev, want) and p.symmetric == bool((want >= 0).all()), name
+        assert np.array_equal(p.src, np.repeat(np.arange(p.n), np.diff(p.rp))), name
+        p.close()
+    assert (_searched_rev(*UNORDERED["descending_row"]) == -1).any()
+
+
+def test_plan_unit_under_sanitizers(tmp_path, graphs):
+    """the plan unit and tests/graph_plan_sanitized_main.cpp, a program of its own, built with AddressSanitizer and
+    UndefinedBehaviorSanitizer and run once over every graph above: no report, and the tables' summary is the expected one"""
+    small = {**SMALL, **UNORDERED, "karate_less_one": _karate_less_one(graphs)[:2]}
+    cases = {**graphs, **small}
+    with open(tmp_path / "graphs.txt", "w") as f:
+        for rp, ci in cases.values():
+            f.write(f"{len(rp) - 1} {len(ci)}\n{' '.join(map(str, rp))}\n{' '.join(map(str, ci))}\n")
+    exe = str(tmp_path / "plan_sanitized")
+    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I" + CSRC, "-o", exe,
+                    os.path.join(CSRC, "gnode_graph_plan.cpp"), os.path.join(HERE, "graph_plan_sanitized_main.cpp")], check=True)
+    run = subprocess.run([exe, str(tmp_path / "graphs.txt")], capture_output=True, text=True)
+    assert run.returncode == 0 and not run.stderr, run.stderr[-2000:]
+    lost = {name: int((_searched_rev(rp, ci) < 0).sum()) if name in small else 0 for name, (rp, ci) in cases.items()}
+    assert lost["karate_less_one"] == 1 and lost["descending_row"] > 0
+    assert run.stdout.split("\n")[:-1] == [f"{len(cases[name][1])} {int(k == 0)} {k}" for name, k in lost.items()]
 
 
 # --------------------------------------------------------------------------- argument checks, through the library

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""The DMP baseline for 16 test samples on one graph: 16 solo `DMP_SIR(...).run(...)` calls (one graph handle, one setup pass
+"""The DMP baseline for 16 test samples on one graph: 16 solo `DMP_SIR(...).run(...)` calls (one graph handle
 and 2 (maxTime - 1) launches each) against one `dmp_batch` of the same 16 samples.  Both sides include building the graph
 handle and copying the result to the host.  One JSON line per graph; no threshold.
 

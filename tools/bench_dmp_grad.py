@@ -11,11 +11,14 @@ for p in (os.path.join(ROOT, "gn-ode-sir_amd"), os.path.join(ROOT, "oracle")):
 import numpy as np, scipy.sparse as sp, torch
 import gnode_oracle as O
 from gnode import _lib
-from gnode.dmp import DmpGraph, dmp_marginals
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--out", default=None, help="append the lines to this file as well")
+ap.add_argument("--lib", default=None, help="load this build of libgnode_hip.so instead of the package's (as tools/bench_dmp_batch.py)")
 opt = ap.parse_args()
+if opt.lib:
+    _lib.LIB_PATH = os.path.abspath(opt.lib)
+from gnode.dmp import DmpGraph, dmp_marginals
 
 SAMPLES, T = 16, 30
 
