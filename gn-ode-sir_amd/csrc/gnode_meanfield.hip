@@ -6,21 +6,17 @@
 // pair whose steps are clipped to land exactly on the output times.  The step-size control runs on the host (one
 // 8-byte error norm per step comes back); tolerances default far below LSODA's own (rtol = atol = 1.5e-8), so the
 // two agree to ~1e-7 -- the test tolerance is 1e-6 absolute on probabilities.
-#include "gnode_common.h"
+#include "gnode_meanfield.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-
-struct MfCoef { double c[7]; int n; };
 
 // ytmp = y + h * sum_j c_j k_j        (3n doubles; k_j = K + j * 3n)
 __global__ __launch_bounds__(256) void k_mf_comb(const double* __restrict__ y, const double* __restrict__ K, MfCoef cf, double h,
                                                 long len, double* __restrict__ out) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i >= len) return;
-    double s = 0.0;
-    for (int j = 0; j < cf.n; ++j) s += cf.c[j] * K[(size_t)j * len + i];
-    out[i] = y[i] + h * s;
+    out[i] = mf_comb_at(y, K, cf, h, len, i);
 }
 
 // k = f(y) for B samples on one graph, one thread per row r = b * n + v of the [3][B * n] state (the scalar entries: B = 1,
@@ -34,11 +30,8 @@ __global__ __launch_bounds__(256) void k_mf_rhs_rates(const int* __restrict__ ro
                                                      double* __restrict__ k) {
     const int r = blockIdx.x * 256 + threadIdx.x;
     if (r >= rows) return;
-    const int v = r % n;
-    const double* I = y + rows + (r - v);                             // sample b's I: y[rows + b * n + .]
-    double ai = 0.0;
-    for (int e = rowptr[v]; e < rowptr[v + 1]; ++e) ai += W ? w_in[e] * I[col[e]] : I[col[e]];
-    const double inf = (BETA ? beta[r] : beta_s) * (ai * y[r]), rec = gamma[r] * I[v];
+    double inf, rec;
+    mf_rhs_row<W, BETA>(rowptr, col, n, rows, r, beta, beta_s, w_in, gamma, y, &inf, &rec);
     k[r] = -inf; k[rows + r] = inf - rec; k[2 * (size_t)rows + r] = rec;
 }
 
@@ -48,6 +41,12 @@ __global__ __launch_bounds__(256) void k_mf_w_in(const int* __restrict__ rev, lo
                                                 double* __restrict__ w_in) {
     const long p = (long)blockIdx.x * 256 + threadIdx.x;
     if (p < nnz) w_in[p] = w[rev[p]];
+}
+
+int gn_mf_stage_w_in(const gnode_graph_s* g, const double* w, double* w_in, hipStream_t st) {
+    hipLaunchKernelGGL(k_mf_w_in, dim3((unsigned)((g->nnz + 255) / 256)), dim3(256), 0, st, g->rev, (long)g->nnz, w, w_in);
+    GN_LAUNCH_CHECK();
+    return 0;
 }
 
 // err = max_i |h sum_j e_j k_j| / (atol + rtol max(|y_i|, |ynew_i|))   (non-negative doubles order like their bits)
@@ -110,6 +109,9 @@ extern "C" size_t gnode_meanfield_rates_workspace_bytes(gnode_graph_t g, int32_t
 
 // gnode_meanfield_rates_f64's part of a call: B samples, beta device [B][n] or null = 1, w device [nnz] or null = 1
 struct MfRates { int B; const double* beta; const double* w; };
+// gnode_meanfield_rates_steps_f64's record of the accepted steps: their sizes in order (the first `cap` of them), how many there
+// were, and how many carried t_out[to - 1] to t_out[to]
+struct MfRecord { double* h; int64_t cap; int64_t n; int32_t* n_acc; };
 
 // `who`: the entry's name for the messages.  init: device fp64 [n][3] (gnode_meanfield_init_f64), or null: then the seed list holds.
 // rates: null for the scalar entries; else init is [B][n][3], gamma [B][n], the scalar beta rests and the state has B * n rows.
@@ -117,7 +119,7 @@ static int meanfield_impl(const char* who, gnode_graph_t g, const int32_t* seeds
                           const double* gamma, const double* t_out_host, int32_t n_out, double rtol, double atol,
                           double* outI, double* outS,
                           double* outR, int64_t* steps_host, void* workspace, size_t workspace_bytes, void* stream,
-                          const MfRates* rates = nullptr) {
+                          const MfRates* rates = nullptr, MfRecord* rec = nullptr) {
     GN_CHECK_ARG(g && gamma && outI && outS && outR && workspace && (init || seeds_host || n_seeds == 0), "%s: null pointer", who);
     GN_CHECK_ARG(!rates || (rates->B >= 1 && (int64_t)rates->B * g->info.n <= INT32_MAX / 3), "%s: need 1 <= B and 3 * B * n < 2^31", who);
     GN_CHECK_ARG(t_out_host && n_out >= 1 && t_out_host[0] == 0.0, "%s: need output times starting at 0", who);
@@ -147,8 +149,7 @@ static int meanfield_impl(const char* who, gnode_graph_t g, const int32_t* seeds
     if (rates && rates->w && g->nnz > 0) {                            // before anything is written to the outputs
         GN_CHECK_ARG(g->symmetric, "%s: the sparsity pattern is not symmetric (a directed contact is a zero weight on the reverse entry)", who);
         double* tab = (double*)(ws + mf_workspace_bytes((size_t)n));
-        hipLaunchKernelGGL(k_mf_w_in, dim3((unsigned)((g->nnz + 255) / 256)), dim3(256), 0, st, g->rev, (long)g->nnz, rates->w, tab);
-        GN_LAUNCH_CHECK();
+        if (int rc = gn_mf_stage_w_in(g, rates->w, tab, st)) return rc;
         w_in = tab;
     }
     const double one = 1.0;
@@ -163,16 +164,6 @@ static int meanfield_impl(const char* who, gnode_graph_t g, const int32_t* seeds
     GN_LAUNCH_CHECK();
     GN_HIP(hipStreamSynchronize(st));                                 // `one` / seeds_host are done with
 
-    // Dormand-Prince 5(4)
-    static const double A[7][6] = {
-        {0, 0, 0, 0, 0, 0},
-        {1.0 / 5, 0, 0, 0, 0, 0},
-        {3.0 / 40, 9.0 / 40, 0, 0, 0, 0},
-        {44.0 / 45, -56.0 / 15, 32.0 / 9, 0, 0, 0},
-        {19372.0 / 6561, -25360.0 / 2187, 64448.0 / 6561, -212.0 / 729, 0, 0},
-        {9017.0 / 3168, -355.0 / 33, 46732.0 / 5247, 49.0 / 176, -5103.0 / 18656, 0},
-        {35.0 / 384, 0, 500.0 / 1113, 125.0 / 192, -2187.0 / 6784, 11.0 / 84}};
-    static const double B4[7] = {5179.0 / 57600, 0, 7571.0 / 16695, 393.0 / 640, -92097.0 / 339200, 187.0 / 2100, 1.0 / 40};
     auto rhs = [&](const double* yy, double* kk) {
         auto kern = w_in ? (beta_rows ? k_mf_rhs_rates<true, true> : k_mf_rhs_rates<true, false>)
                          : (beta_rows ? k_mf_rhs_rates<false, true> : k_mf_rhs_rates<false, false>);
@@ -181,19 +172,19 @@ static int meanfield_impl(const char* who, gnode_graph_t g, const int32_t* seeds
     rhs(y, K);                                                        // k1 (FSAL: later steps reuse k7)
     double t = 0.0, h = 1e-3;
     long steps = 0;
+    if (rec) std::fill(rec->n_acc, rec->n_acc + n_out, 0);
     for (int to = 1; to < n_out; ++to) {
         const double t_end = t_out_host[to];
         while (t < t_end) {
             const double hh = std::min(h, t_end - t);
             for (int s = 1; s < 7; ++s) {
-                MfCoef cf; cf.n = s;
-                for (int j = 0; j < s; ++j) cf.c[j] = A[s][j];
+                const MfCoef cf = mf_stage_coef(s);
                 double* dst = (s == 6) ? ynew : ytmp;                 // stage 7's argument IS the 5th-order solution
                 hipLaunchKernelGGL(k_mf_comb, dim3(lg), dim3(256), 0, st, y, K, cf, hh, len, dst);
                 rhs(dst, K + (size_t)s * len);
             }
             MfCoef ef; ef.n = 7;
-            for (int j = 0; j < 7; ++j) ef.c[j] = (j < 6 ? A[6][j] : 0.0) - B4[j];
+            for (int j = 0; j < 7; ++j) ef.c[j] = (j < 6 ? kMfA[6][j] : 0.0) - kMfB4[j];
             GN_HIP(hipMemsetAsync(err, 0, sizeof(unsigned long long), st));
             hipLaunchKernelGGL(k_mf_err, dim3((unsigned)std::min<long>(lg, 1024)), dim3(256), 0, st, y, ynew, K, ef, hh, rtol, atol,
                                len, err);
@@ -207,6 +198,10 @@ static int meanfield_impl(const char* who, gnode_graph_t g, const int32_t* seeds
             ++steps;
             GN_CHECK_ARG(steps < 2000000, "%s: step count exploded (h=%g at t=%g)", who, hh, t);
             if (e <= 1.0) {                                           // accept
+                if (rec) {
+                    if (rec->n < rec->cap) rec->h[rec->n] = hh;
+                    ++rec->n; ++rec->n_acc[to];
+                }
                 t = (hh == t_end - t) ? t_end : t + hh;
                 std::swap(y, ynew);
                 GN_HIP(hipMemcpyAsync(K, K + (size_t)6 * len, (size_t)len * sizeof(double), hipMemcpyDeviceToDevice, st));   // FSAL
@@ -248,4 +243,19 @@ extern "C" int gnode_meanfield_rates_f64(gnode_graph_t g, int32_t B, const doubl
     const MfRates rates = {B, beta, w};
     return meanfield_impl("gnode_meanfield_rates_f64", g, nullptr, 0, init, 0.0, gamma, t_out_host, n_out, rtol, atol, outI, outS, outR,
                           steps_host, workspace, workspace_bytes, stream, &rates);
+}
+
+// The same integration, and the accepted steps: what gnode_meanfield_rates_backward_f64 sweeps back over (include/gnode.h).
+extern "C" int gnode_meanfield_rates_steps_f64(gnode_graph_t g, int32_t B, const double* init, const double* beta, const double* w,
+                                               const double* gamma, const double* t_out_host, int32_t n_out, double rtol, double atol,
+                                               double* outI, double* outS, double* outR, int64_t* steps_host, void* workspace,
+                                               size_t workspace_bytes, void* stream, double* h_host, int64_t h_cap,
+                                               int64_t* n_h_host, int32_t* n_acc_host) {
+    GN_CHECK_ARG(init && n_h_host && n_acc_host && h_cap >= 0 && (h_host || h_cap == 0), "gnode_meanfield_rates_steps_f64: null pointer");
+    const MfRates rates = {B, beta, w};
+    MfRecord rec = {h_host, h_cap, 0, n_acc_host};
+    const int rc = meanfield_impl("gnode_meanfield_rates_steps_f64", g, nullptr, 0, init, 0.0, gamma, t_out_host, n_out, rtol, atol, outI, outS,
+                                  outR, steps_host, workspace, workspace_bytes, stream, &rates, &rec);
+    if (rc == 0) *n_h_host = rec.n;
+    return rc;
 }

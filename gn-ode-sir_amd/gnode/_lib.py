@@ -98,6 +98,11 @@ ABI = {
     "gnode_meanfield_init_f64": (_int, [_vp, _vp, _f64, _vp, _vp, _i32, _f64, _f64, _vp, _vp, _vp, _pi64, _vp, _sz, _vp]),
     "gnode_meanfield_rates_workspace_bytes": (_sz, [_vp, _i32]),
     "gnode_meanfield_rates_f64": (_int, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _f64, _f64, _vp, _vp, _vp, _pi64, _vp, _sz, _vp]),
+    "gnode_meanfield_rates_steps_f64": (_int, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _f64, _f64, _vp, _vp, _vp, _pi64, _vp, _sz, _vp,
+                                               _vp, _i64, _pi64, _vp]),
+    "gnode_meanfield_rates_backward_workspace_bytes": (_sz, [_vp, _i32, _i32]),
+    "gnode_meanfield_rates_backward_f64": (_int, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                  _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "gnode_l1_loss_workspace_bytes": (_sz, []),
     "gnode_l1_loss_f32": (_int, _L1 + [_vp, _sz, _vp]),
     "gnode_l1_loss_scaled_f32": (_int, _L1 + [C.c_float, _vp, _sz, _vp]),

@@ -5,6 +5,7 @@
     create_graph(n_nodes, graph_label='none')                    reference :394-414
     sir(x, y, A, beta, gamma), runge_kutta_order4(sir, A, ...)   reference :214-233 (mean-field comparison column)
     meanfield_batch(graph, starts, beta, gamma, ...)             extension: that column for a batch of samples
+    meanfield_marginals(graph, init, beta, gamma, w, ...)        extension: the same numbers as a differentiable function
 """
 from __future__ import annotations
 
@@ -606,6 +607,111 @@ def meanfield_batch(graph: DeviceGraph, starts, beta, gamma, deltaT=1, maxTime=7
                               rtol, atol)
     I, S, R = (out[c].view(-1, B, n).permute(1, 0, 2).contiguous() for c in range(3))
     return MeanfieldBatch(I, S, R)
+
+
+class _MeanfieldMarginals(torch.autograd.Function):
+    """gnode_meanfield_rates_steps_f64 forward, gnode_meanfield_rates_backward_f64 backward; the arguments are
+    `meanfield_marginals`', already checked and expanded to the library's shapes (beta and w may be None)."""
+
+    @staticmethod
+    def forward(ctx, graph, init, beta, gamma, w, t_out, rtol, atol):
+        lib, handle = _lib.load(), graph.handle
+        det = lambda t: None if t is None else t.detach().contiguous()      # noqa: E731
+        y0, bet, gam, wd = det(init), det(beta), det(gamma), det(w)
+        B, n, T = y0.shape[0], y0.shape[1], len(t_out)
+        out = torch.empty((3, T, B * n), dtype=torch.float64, device=y0.device)
+        ws = torch.empty(lib.gnode_meanfield_rates_workspace_bytes(handle, B), dtype=torch.uint8, device=y0.device)
+        steps, n_h, n_acc, cap = C.c_int64(0), C.c_int64(0), np.zeros(T, dtype=np.int32), 4096
+        while True:                                                 # once more, with room, if the record did not fit
+            h = np.empty(cap, dtype=np.float64)
+            _lib.check(lib.gnode_meanfield_rates_steps_f64(
+                handle, B, _lib.ptr(y0), _lib.ptr(bet), _lib.ptr(wd), _lib.ptr(gam), _lib.host_ptr(t_out), T, float(rtol), float(atol),
+                _lib.ptr(out[0]), _lib.ptr(out[1]), _lib.ptr(out[2]), C.byref(steps), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(),
+                _lib.host_ptr(h), cap, C.byref(n_h), _lib.host_ptr(n_acc)))
+            if n_h.value <= cap:
+                break
+            cap = int(n_h.value)
+        ctx.graph, ctx.t_out, ctx.h, ctx.n_acc = graph, t_out, np.ascontiguousarray(h[:n_h.value]), n_acc
+        ctx.has = (bet is not None, wd is not None)
+        ctx.save_for_backward(*(t for t in (y0, gam, out, bet, wd) if t is not None))
+        I, S, R = (out[c].view(T, B, n).permute(1, 0, 2).contiguous() for c in range(3))
+        return I, S, R
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gI, gS, gR):
+        saved = list(ctx.saved_tensors)
+        y0, gam, out = saved[:3]
+        bet = saved[3] if ctx.has[0] else None
+        wd = saved[-1] if ctx.has[1] else None
+        graph, t_out = ctx.graph, ctx.t_out
+        B, n, T, nnz = y0.shape[0], y0.shape[1], len(t_out), int(graph.nnz)
+        gout = torch.zeros((3, T, B * n), dtype=torch.float64, device=y0.device)      # the outputs' layout: [T][B * n]
+        for c, g in enumerate((gI, gS, gR)):
+            if g is not None:
+                gout[c].view(T, B, n).copy_(g.permute(1, 0, 2))
+        want_i, want_b, want_g, want_w = (ctx.needs_input_grad[k] for k in (1, 2, 3, 4))
+        new = lambda *shape: torch.empty(shape, dtype=torch.float64, device=y0.device)      # noqa: E731
+        gi, gb = new(B, n, 3) if want_i else None, new(B, n) if want_b and bet is not None else None
+        gg = new(B, n) if want_g else None
+        gw = new(B, nnz) if want_w and wd is not None and nnz else None      # (no edge, no table: an empty tensor has no address)
+        if gi is not None or gb is not None or gg is not None or gw is not None:
+            lib, handle = _lib.load(), graph.handle
+            m = int(ctx.n_acc.max(initial=0))
+            ws = torch.empty(lib.gnode_meanfield_rates_backward_workspace_bytes(handle, B, m), dtype=torch.uint8, device=y0.device)
+            _lib.check(lib.gnode_meanfield_rates_backward_f64(
+                handle, B, _lib.ptr(y0), _lib.ptr(bet), _lib.ptr(wd), _lib.ptr(gam), _lib.host_ptr(t_out), T, _lib.host_ptr(ctx.h),
+                int(ctx.h.shape[0]), _lib.host_ptr(ctx.n_acc), _lib.ptr(out[0]), _lib.ptr(out[1]), _lib.ptr(out[2]), _lib.ptr(gout[0]),
+                _lib.ptr(gout[1]), _lib.ptr(gout[2]), _lib.ptr(gi), _lib.ptr(gb), _lib.ptr(gw), _lib.ptr(gg), _lib.ptr(ws), ws.numel(),
+                _lib.stream_ptr()))
+        if want_w and wd is not None:                               # the library returns one row per sample: the shared table sums them
+            gw = torch.zeros_like(wd) if gw is None else gw.sum(0)
+        return None, gi, gb, gg, gw, None, None, None
+
+
+def meanfield_marginals(graph: DeviceGraph, init, beta, gamma, w=None, deltaT=1, maxTime=70, rtol=1e-10, atol=1e-12) -> MeanfieldBatch:
+    """The mean-field marginals of B samples on one graph as a differentiable function of float64 device tensors: (I, S, R),
+    [B, maxTime, n] each, bit for bit what `meanfield_batch` returns for the same numbers, with `.backward()` through the
+    library's reverse sweep of the Dormand-Prince solve (gnode_meanfield_rates_backward_f64) -- fitting beta and gamma to
+    observed curves, per-contact rates, scoring source nodes by the gradient with respect to the start.  The gradient is
+    the exact derivative of the returned numbers with the accepted step sizes held fixed (what backpropagating through an
+    explicit dopri5 loop gives), not a continuous adjoint.
+
+    init: [B, n, 3] = (pS, pI, pR) per node.  beta: [B, n], [n] (indexed by the target node) or None = 1.  gamma: [B, n] or
+    [n].  w: [nnz] in the graph's CSR position order (source = row, target = column; the pattern must then be symmetric) or
+    None = 1.  The [n] forms are expanded in front of the library call, so their gradient is the sum over the samples, as w's
+    is.  What is wrong raises ValueError before the library is loaded; a tensor that is not on a GPU raises GnodeError."""
+    n, nnz, T = int(graph.n), int(graph.nnz), int(maxTime)
+    if T < 1:
+        raise ValueError(f"meanfield_marginals: maxTime must be >= 1 (got {maxTime})")
+    if not deltaT > 0:
+        raise ValueError(f"meanfield_marginals: deltaT must be > 0 (got {deltaT})")
+    for name, t in (("init", init), ("beta", beta), ("gamma", gamma), ("w", w)):
+        if t is None and name in ("beta", "w"):
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float64:
+            raise ValueError(f"meanfield_marginals: {name} must be a float64 tensor")
+    if init.dim() != 3 or init.shape[0] < 1 or tuple(init.shape[1:]) != (n, 3):
+        raise ValueError(f"meanfield_marginals: init must have the shape [B >= 1, {n}, 3], got {tuple(init.shape)}")
+    B = init.shape[0]
+    if beta is not None and tuple(beta.shape) not in ((n,), (B, n)):
+        raise ValueError(f"meanfield_marginals: beta must have the shape [{n}] or [{B}, {n}], got {tuple(beta.shape)}")
+    if tuple(gamma.shape) not in ((n,), (B, n)):
+        raise ValueError(f"meanfield_marginals: gamma must have the shape [{n}] or [{B}, {n}], got {tuple(gamma.shape)}")
+    if w is not None and tuple(w.shape) != (nnz,):
+        raise ValueError(f"meanfield_marginals: w must have the shape [{nnz}], got {tuple(w.shape)}")
+    if 3 * B * n >= 2**31:
+        raise ValueError(f"meanfield_marginals: 3 * B * n = {3 * B * n} does not fit 31 bits")
+    for t in (init, beta, gamma, w):
+        if t is not None and not t.is_cuda:
+            raise _lib.GnodeError("GN-ODE path: tensor is not on a GPU (no CPU fallback exists)")
+    if beta is not None and beta.dim() == 1:
+        beta = beta.unsqueeze(0).expand(B, n)                       # autograd sums the samples' rows
+    if gamma.dim() == 1:
+        gamma = gamma.unsqueeze(0).expand(B, n)
+    if w is not None and nnz == 0:
+        w = None                                                    # (no edge, no table)
+    return MeanfieldBatch(*_MeanfieldMarginals.apply(graph, init, beta, gamma, w, _mf_times(deltaT, T), rtol, atol))
 
 
 class CsrGraph:

@@ -20,7 +20,7 @@
  *     into a hipGraph on first use and one handle may serve several streams (each
  *     with its own workspace).  Functions that DO synchronise `stream` say so below
  *     (gnode_graph_create, gnode_sir_mc_philox with more than 32 seeds,
- *     gnode_sir_mc_philox_nodes, gnode_sir_mc_philox_edges, gnode_sir_mc_philox_traj_edges, gnode_sir_mc_philox_traj with more than 32 seeds or rate arrays, gnode_sir_mc_philox_init, gnode_sir_mc_coins, gnode_dmp_f32, gnode_dmp_init_f32, gnode_dmp_batch_f32, gnode_dmp_batch_backward_f32, gnode_dmp_backward_f32, gnode_meanfield_f64, gnode_meanfield_init_f64, gnode_meanfield_rates_f64).
+ *     gnode_sir_mc_philox_nodes, gnode_sir_mc_philox_edges, gnode_sir_mc_philox_traj_edges, gnode_sir_mc_philox_traj with more than 32 seeds or rate arrays, gnode_sir_mc_philox_init, gnode_sir_mc_coins, gnode_dmp_f32, gnode_dmp_init_f32, gnode_dmp_batch_f32, gnode_dmp_batch_backward_f32, gnode_dmp_backward_f32, gnode_meanfield_f64, gnode_meanfield_init_f64, gnode_meanfield_rates_f64, gnode_meanfield_rates_steps_f64).
  *   - process-wide state: (1) a per-device "set up once" table (compute-unit count,
  *     dynamic-LDS kernel attributes), written under a lock by the first
  *     gnode_graph_create on a device and read-only afterwards; (2) the opt-in
@@ -584,6 +584,54 @@ int gnode_meanfield_rates_f64(gnode_graph_t g, int32_t B, const double* init, co
                               const double* gamma, const double* t_out_host, int32_t n_out, double rtol, double atol,
                               double* outI, double* outS, double* outR, int64_t* steps_host, void* workspace,
                               size_t workspace_bytes, void* stream);
+/* gnode_meanfield_rates_f64, and the record of its accepted steps: the same integration through the same code, so the outputs
+ * and *steps_host are that entry's bit for bit, and gnode_meanfield_rates_workspace_bytes is its workspace too.
+ *   h_host      host fp64 [h_cap]: the accepted step sizes in order; those past h_cap are dropped (h_host may be NULL with
+ *               h_cap = 0: a first call that only counts)
+ *   n_h_host    host: the number of accepted steps, whatever h_cap is
+ *   n_acc_host  host int32 [n_out]: n_acc[to] accepted steps carried t_out[to - 1] to t_out[to]; n_acc[0] = 0, and an interval
+ *               between equal output times has none
+ * GNODE_ERR_ARG for a null n_h_host or n_acc_host, h_cap < 0, or h_host null with h_cap > 0; otherwise as that entry. */
+int gnode_meanfield_rates_steps_f64(gnode_graph_t g, int32_t B, const double* init, const double* beta, const double* w,
+                                    const double* gamma, const double* t_out_host, int32_t n_out, double rtol, double atol,
+                                    double* outI, double* outS, double* outR, int64_t* steps_host, void* workspace,
+                                    size_t workspace_bytes, void* stream, double* h_host, int64_t h_cap, int64_t* n_h_host,
+                                    int32_t* n_acc_host);
+/* The reverse sweep of that solve: the gradient of  sum(gI * outI) + sum(gS * outS) + sum(gR * outR)  with respect to the
+ * start, beta, the contact weights and gamma, for B samples on one graph, fp64.  It is the exact derivative of the numbers
+ * the forward returned WITH THE ACCEPTED STEP SIZES HELD FIXED (what backpropagating through an explicit Dormand-Prince loop
+ * gives), not a second adaptive solve of the continuous adjoint: an accepted step is the 6-stage map
+ *     Y_1 = y,  Y_s = y + h sum_{j<s} a_sj k_j,  k_s = f(Y_s),  y' = Y_7
+ * (stage 7 feeds only the error estimate) and the sweep applies its transpose step by step, from the last output time down,
+ * adding gI / gS / gR row `to` to the adjoint of y when it passes t_out[to] (rows at equal times both add).
+ *   g, B, init, beta, w, gamma, t_out_host, n_out   the forward call's (beta and w may be NULL as there)
+ *   h_host, n_h, n_acc_host   gnode_meanfield_rates_steps_f64's record, complete (n_h = its *n_h_host <= its h_cap)
+ *   outI/outS/outR            what the forward returned, device fp64 [n_out][B * n]
+ *   gI/gS/gR                  device fp64, the outputs' layout
+ *   grad_init   device fp64 [B][n][3]      grad_beta, grad_gamma   device fp64 [B][n]
+ *   grad_w      device fp64 [B][nnz], CSR position order: one row per sample, which the caller sums (w is shared)
+ * A NULL gradient pointer means "not wanted"; the others' bits do not depend on it.  With beta or w NULL the gradient asked
+ * for is the one at beta = 1, w = 1.  Per interval the entry integrates again from the forward's own output row with the
+ * recorded steps and the forward's arithmetic, keeping y at every step (3 * B * n * 8 bytes each), then walks the steps
+ * backwards: 5 launches recompute Y_2..Y_6 and 7 launches carry the adjoint through the six stages -- each completes one
+ * stage's neighbour gather and does the next stage's row-local part, so there is one grid-wide dependency per stage.  No
+ * atomics; every accumulator has one writer per launch and every row sum runs in ascending CSR position: two calls return
+ * the same bits.  Enqueue-only: the host arrays are read before the call returns and `stream` is not synchronised.
+ * gnode_meanfield_rates_backward_workspace_bytes(g, B, m) is the workspace for a record whose largest n_acc is m; it returns
+ * 0 without a handle, for B < 1 and for m < 0.
+ * GNODE_ERR_ARG, before any launch and with no gradient written: a null required pointer, all four gradient pointers null,
+ * B < 1 or 3 * B * n >= 2^31, output times that do not start at 0 or ascend, an asymmetric pattern (also with w NULL: the
+ * transpose gather needs every contact's reverse entry), a step list that the forward cannot have walked -- a step that is not
+ * finite and > 0, counts that do not add up to n_h, an interval whose last step is not t_end - t bit for bit, an interval
+ * of positive length without a step; the message names the interval.  GNODE_ERR_WORKSPACE: a short workspace.
+ * n_out = 1 is valid: grad_init is row 0 of gS / gI / gR and the other gradients are 0. */
+size_t gnode_meanfield_rates_backward_workspace_bytes(gnode_graph_t g, int32_t B, int32_t max_interval_steps);
+int gnode_meanfield_rates_backward_f64(gnode_graph_t g, int32_t B, const double* init, const double* beta, const double* w,
+                                       const double* gamma, const double* t_out_host, int32_t n_out, const double* h_host,
+                                       int64_t n_h, const int32_t* n_acc_host, const double* outI, const double* outS,
+                                       const double* outR, const double* gI, const double* gS, const double* gR,
+                                       double* grad_init, double* grad_beta, double* grad_w, double* grad_gamma,
+                                       void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- loss ------------------------------------------------------------------
  * The training loss of ode_nn_ngraph_sim.py:230-234 (multi-graph: ode_nn_ngraphs.py:199-203) and its gradient in one
