@@ -13,8 +13,8 @@
 //
 // One statement serves the three entries: B samples on one graph, sample b starting from init[b] = (pS, pI, pR) per node with
 // weights + b * w_stride and gamma + b * gamma_stride (a stride of 0 shares the table); gnode_dmp_f32 and gnode_dmp_init_f32
-// are B = 1.  The recurrence is the four dmp_* functions below and nothing else; the kernels are loops and indexing around
-// them, in two forms chosen by dmp_run:
+// are B = 1.  The recurrence is the four dmp_* functions of gnode_dmp.h and nothing else; the kernels are loops and indexing
+// around them, in two forms chosen by dmp_run:
 //   general                    four kernels over rows b * n + k and edge slots b * nnz + e of the workspace: two launches per
 //                              time step (node pass, edge pass); theta ping-pongs because the edge pass reads its neighbours'
 //   one workgroup per sample   the messages and marginals of a sample live in LDS for the whole horizon: one launch
@@ -23,45 +23,8 @@
 // The second half of the file is the reverse sweep of the same recurrence (gnode_dmp_batch_backward_f32, gnode_dmp_backward_f32):
 // the gradients of the marginals with respect to w, gamma and the start, stated once as dmp_rev_* functions and served in the
 // same two forms.
-#include "gnode_common.h"
+#include "gnode_dmp.h"
 #include <algorithm>
-
-// ------------------------------------------------------------------------------------------------ the recurrence, once
-// On values and on pointers that are already the sample's own, in global memory or in LDS.  The library is built with
-// -ffp-contract=off, so these round as written wherever they are inlined; their operand order is the reference's.
-
-// t = 1 (dmp.py:104-121): theta_1 = 1 - w phi_0 + 1e-10, phi_0 = Pi0[src] (what 1 - Ps0 is when Pr0 = 0), Ps_e^{prev} = Ps0[src]
-__device__ __forceinline__ void dmp_edge_start(float ps0_u, float pi0_u, float w_e, float& theta, float& phi, float& ps) {
-    theta = (1.0f - w_e * pi0_u) + 1e-10f;
-    phi = pi0_u;
-    ps = ps0_u;
-}
-
-// P_k: theta of the reverses of row k's edges [lo, hi), in ascending position from 1
-__device__ __forceinline__ float dmp_row_product(const int* rev, const float* theta, int lo, int hi) {
-    float p = 1.0f;
-    for (int e = lo; e < hi; ++e) p = p * theta[rev[e]];
-    return p;
-}
-
-// the marginals of node k at this step from P_k and the previous step's Pi_k, Pr_k
-__device__ __forceinline__ void dmp_node_update(float P_k, float ps0_k, float pi_prev, float pr_prev, float gamma_k, float& ps,
-                                                float& pi, float& pr) {
-    ps = ps0_k * P_k;
-    pr = pr_prev + gamma_k * pi_prev;
-    pi = 1.0f - ps - pr;
-}
-
-// Ps_e and phi_e of this step (in place), theta_e of the NEXT step; `theta` is a reference so that it is loaded where it is used
-__device__ __forceinline__ void dmp_edge_update(float P_u, float theta_rev, float ps0_u, float w_e, float gamma_u, float& phi,
-                                                float& ps, const float& theta, float& theta_next) {
-    const float mul = P_u / theta_rev;
-    const float ps_new = ps0_u * mul;
-    const float ph = (1.0f - w_e) * (1.0f - gamma_u) * phi - (ps_new - ps);
-    phi = ph;
-    ps = ps_new;
-    theta_next = theta - w_e * ph;
-}
 
 // ------------------------------------------------------------------------------------------------ the kernels
 struct DmpBatchArgs {
@@ -80,9 +43,6 @@ __device__ __forceinline__ DmpSample dmp_sample(const DmpBatchArgs& a, size_t b)
 __device__ __forceinline__ void dmp_store3(float* __restrict__ row, int k, float ps, float pi, float pr) {
     row[(size_t)k * 3 + 0] = ps; row[(size_t)k * 3 + 1] = pi; row[(size_t)k * 3 + 2] = pr;
 }
-
-__host__ __device__ static inline size_t dmp_align16(size_t x) { return (x + 15) / 16 * 16; }
-static constexpr size_t kDmpLdsLimit = 160 * 1024;      // what a gfx950 workgroup may declare
 
 extern "C" size_t gnode_dmp_batch_lds_bytes(gnode_graph_t g) {
     if (!g) return 0;

@@ -8,6 +8,10 @@ same constructor and `run(seed_list, maxTime)`, the message passing runs in libg
                                                 samples on one graph in one library call, each its solo run's bits
     dmp_marginals(DmpGraph, weights, gamma, init, maxTime) -> the same tensor as a torch.autograd.Function of device tensors (an
                                                 extension): gradients with respect to weights, gamma and the start
+    source_scores(graph, obs, gamma, maxTime, candidates=None, floor=1e-30, budget_bytes=1 << 30) -> float64 tensor
+                                                [C, maxTime] on the GPU (an extension): the log-likelihood of one observed
+                                                snapshot for every candidate source and time, fused into the node pass
+    rank_sources(scores, candidates)         -> the candidates by their best score, with the time at which each attains it
 """
 from __future__ import annotations
 
@@ -150,18 +154,18 @@ def dmp_marginals(graph, weights, gamma, init, maxTime):
     return _DmpMarginals.apply(graph, weights, gamma, init, T)
 
 
-def _batch_numbers(name, value, shapes):
+def _batch_numbers(name, value, shapes, who="dmp_batch"):
     """`value` as a float64 host array of one of `shapes`, every entry finite and >= 0; ValueError otherwise."""
     if isinstance(value, torch.Tensor):
         value = value.detach().cpu().numpy()
     try:
         a = np.asarray(value, dtype=np.float64)
     except (TypeError, ValueError) as e:
-        raise ValueError(f"dmp_batch: {name} is not an array of numbers ({e})") from None
+        raise ValueError(f"{who}: {name} is not an array of numbers ({e})") from None
     if a.shape not in shapes:
-        raise ValueError(f"dmp_batch: {name} must have one of the shapes {shapes}, got {tuple(a.shape)}")
+        raise ValueError(f"{who}: {name} must have one of the shapes {shapes}, got {tuple(a.shape)}")
     if not ((a >= 0.0) & np.isfinite(a)).all():                     # a NaN fails the comparison
-        raise ValueError(f"dmp_batch: {name} holds an entry that is not a finite number >= 0")
+        raise ValueError(f"{who}: {name} holds an entry that is not a finite number >= 0")
     return a
 
 
@@ -208,3 +212,101 @@ def dmp_batch(weight_adj, starts, gamma, maxTime, scale=None, device="cuda"):
     _lib.check(lib.gnode_dmp_batch_f32(handle, _lib.ptr(wd), nnz if w.ndim == 2 else 0, _lib.ptr(gd), n if gam.ndim == 2 else 0,
                                        _lib.ptr(y0), B, T, _lib.ptr(out), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()))
     return out
+
+
+def _source_ints(name, value, n_expected=None):
+    """`value` as a 1-D int64 host array of whole numbers (of length n_expected, where given); ValueError otherwise."""
+    if isinstance(value, torch.Tensor):
+        value = value.detach().cpu().numpy()
+    try:
+        a = np.asarray(value)
+        if a.dtype.kind not in "iub" and not (a.dtype.kind == "f" and (np.isfinite(a) & (a == np.floor(a))).all()):
+            raise ValueError("not whole numbers")
+        whole = a.astype(np.int64)
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"source_scores: {name} is not an array of integers ({e})") from None
+    if whole.ndim != 1 or (n_expected is not None and whole.shape[0] != n_expected):
+        want = "1-D" if n_expected is None else f"[{n_expected}]"
+        raise ValueError(f"source_scores: {name} must have the shape {want}, got {tuple(whole.shape)}")
+    return whole
+
+
+def source_scores(graph, obs, gamma, maxTime, candidates=None, floor=1e-30, budget_bytes=1 << 30, device="cuda"):
+    """Which node started the outbreak?  Given ONE observed snapshot `obs` of the SIR states, taken at an unknown time, score
+    every candidate source c and time t by the mean-field likelihood of the snapshot under DMP started from c alone (Lokhov,
+    Mezard, Ohta, Zdeborova 2014):  scores[c, t] = sum over the observed nodes k of log P^k_{obs[k]}(t | c),  t = 0 .. maxTime - 1,
+    a float64 device tensor [C, maxTime].  The probabilities are `dmp_batch`'s float32 marginals from the seed list [c], bit for
+    bit, clamped to [floor, 1] in float32 before the float64 logarithm -- a node further than t from c has probability exactly
+    0 -- but they never reach global memory: the sums are taken in the node pass that holds them in registers
+    (`gnode_dmp_source_scores_f32`), in a fixed order, so a candidate's row does not depend on the other candidates or on the
+    chunking.
+
+    graph: one matrix, as `DMP_SIR` takes, or a `DmpGraph` made from one; its `data` gives the weights.  obs: n integers,
+    0 / 1 / 2 = observed susceptible / infected / recovered, -1 = not observed.  gamma: a number or per-node values [n], finite
+    and >= 0.  candidates: node ids (repeats allowed); by default the nodes observed infected or recovered, ascending -- a source
+    cannot be susceptible -- and every node if there is none.  The candidates go to the library in chunks of the largest C
+    whose `gnode_dmp_source_workspace_bytes` fits `budget_bytes` (the one-workgroup form needs no room per candidate: one
+    chunk); a budget too small for one candidate raises ValueError.  What is wrong raises ValueError before the library is
+    loaded or a graph handle is made."""
+    G = graph if isinstance(graph, DmpGraph) else DmpGraph(graph)
+    n, T = G.N, int(maxTime)
+    if T < 2:
+        raise ValueError(f"source_scores: maxTime must be >= 2 (got {maxTime})")
+    floor = float(floor)
+    if not 0.0 < floor <= 1.0 or not 0.0 < float(np.float32(floor)) <= 1.0:        # (a NaN fails it; so does a float32 zero)
+        raise ValueError(f"source_scores: floor must be in (0, 1] as a float32 (got {floor})")
+    o = _source_ints("obs", obs, n)
+    if o.size and (o.min() < -1 or o.max() > 2):
+        raise ValueError("source_scores: obs holds a value outside -1 (not observed), 0, 1, 2")
+    if candidates is None:
+        cand = source_candidates(o)
+    else:
+        cand = _source_ints("candidates", candidates)
+    if cand.size < 1:
+        raise ValueError("source_scores: need at least one candidate")
+    if cand.min() < 0 or cand.max() >= n:
+        raise ValueError(f"source_scores: candidate {int(cand[(cand < 0) | (cand >= n)][0])} is not in [0, {n})")
+    g = _batch_numbers("gamma", gamma, [(), (n,)], "source_scores")
+    budget = int(budget_bytes)
+    lib, handle = _lib.load(), G.graph.handle
+    need = lambda c: int(lib.gnode_dmp_source_workspace_bytes(handle, c, T))       # noqa: E731  (grows with c, or is constant)
+    if need(1) > budget:
+        raise ValueError(f"source_scores: budget_bytes = {budget} is too small for one candidate ({need(1)} bytes)")
+    lo, hi = 1, int(cand.size)                                      # the largest chunk that fits: need(lo) <= budget throughout
+    if need(hi) <= budget:
+        lo = hi
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        lo, hi = (mid, hi) if need(mid) <= budget else (lo, mid)
+    chunk = lo
+    up = lambda a, dt: None if a.size == 0 else torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(device)      # noqa: E731
+    wd, gd = up(G.data, np.float32), up(np.broadcast_to(g, (n,)), np.float32)
+    od, cd = up(o, np.int32), up(cand, np.int32)
+    scores = torch.empty((cand.size, T), dtype=torch.float64, device=cd.device)
+    ws = torch.empty(need(chunk), dtype=torch.uint8, device=cd.device)
+    for at in range(0, cand.size, chunk):
+        c = min(chunk, cand.size - at)
+        _lib.check(lib.gnode_dmp_source_scores_f32(handle, _lib.ptr(wd), _lib.ptr(gd), _lib.ptr(cd[at:at + c]), c, _lib.ptr(od), floor, T,
+                                                   _lib.ptr(scores[at:at + c]), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()))
+    return scores
+
+
+def source_candidates(obs):
+    """The candidates `source_scores` takes by default for `obs`: the nodes observed infected or recovered, ascending; every
+    node if there is none."""
+    o = np.asarray(obs).astype(np.int64)
+    cand = np.flatnonzero(o >= 1)
+    return cand if cand.size else np.arange(o.shape[0])
+
+
+def rank_sources(scores, candidates):
+    """The candidates of a `source_scores` table, most likely first: a list of (candidate, t, score) sorted by the candidate's
+    best score over time, descending (ties keep the table's order), with the t at which it is attained."""
+    s = scores.detach().cpu().numpy() if isinstance(scores, torch.Tensor) else np.asarray(scores, dtype=np.float64)
+    cand = np.asarray(candidates).astype(np.int64).reshape(-1)
+    if s.ndim != 2 or s.shape[0] != cand.shape[0] or s.shape[1] < 1:
+        raise ValueError(f"rank_sources: scores {tuple(s.shape)} is not one row per candidate ({cand.shape[0]})")
+    best_t = s.argmax(1)
+    best = s[np.arange(s.shape[0]), best_t]
+    order = np.argsort(-best, kind="stable")
+    return [(int(cand[i]), int(best_t[i]), float(best[i])) for i in order]

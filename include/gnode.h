@@ -20,7 +20,7 @@
  *     into a hipGraph on first use and one handle may serve several streams (each
  *     with its own workspace).  Functions that DO synchronise `stream` say so below
  *     (gnode_graph_create, gnode_sir_mc_philox with more than 32 seeds,
- *     gnode_sir_mc_philox_nodes, gnode_sir_mc_philox_edges, gnode_sir_mc_philox_traj_edges, gnode_sir_mc_philox_traj with more than 32 seeds or rate arrays, gnode_sir_mc_philox_init, gnode_sir_mc_coins, gnode_dmp_f32, gnode_dmp_init_f32, gnode_dmp_batch_f32, gnode_dmp_batch_backward_f32, gnode_dmp_backward_f32, gnode_meanfield_f64, gnode_meanfield_init_f64, gnode_meanfield_rates_f64, gnode_meanfield_rates_steps_f64).
+ *     gnode_sir_mc_philox_nodes, gnode_sir_mc_philox_edges, gnode_sir_mc_philox_traj_edges, gnode_sir_mc_philox_traj with more than 32 seeds or rate arrays, gnode_sir_mc_philox_init, gnode_sir_mc_coins, gnode_dmp_f32, gnode_dmp_init_f32, gnode_dmp_batch_f32, gnode_dmp_batch_backward_f32, gnode_dmp_backward_f32, gnode_dmp_source_scores_f32, gnode_meanfield_f64, gnode_meanfield_init_f64, gnode_meanfield_rates_f64, gnode_meanfield_rates_steps_f64).
  *   - process-wide state: (1) a per-device "set up once" table (compute-unit count,
  *     dynamic-LDS kernel attributes), written under a lock by the first
  *     gnode_graph_create on a device and read-only afterwards; (2) the opt-in
@@ -541,6 +541,36 @@ int gnode_dmp_backward_f32(gnode_graph_t g, const float* weights, const float* g
                            const float* grad_out /* the same shape */, float* grad_w /* [nnz] or NULL */,
                            float* grad_gamma /* [n] or NULL */, float* grad_init /* [n][3] or NULL */,
                            void* workspace, size_t workspace_bytes, void* stream);
+/* Source inference from one snapshot (Lokhov, Mezard, Ohta, Zdeborova 2014): the recurrence from each of C candidate sources,
+ * scored against the observed states, without a marginal ever reaching global memory.  Candidate c's sample is
+ * gnode_dmp_batch_f32's from the one-hot seed state (1 - [k == candidates[c]], [k == candidates[c]], 0) with the shared
+ * weights and gamma -- the same fp32 marginals, bit for bit -- and the kernels make that state from the id: no [C][n][3]
+ * start exists.  With p = Ps / Pi / Pr of node k at step t for obs[k] = 0 / 1 / 2,
+ *   scores[c][t] = sum over the observed k of log((double)min(max(p, floor), 1.0f)),     t = 0 .. maxTime - 1, row 0 = the start;
+ * any other obs[k] means "not observed" and contributes nothing, and a candidate id outside [0, n) matches no node (an
+ * all-susceptible start), so the device arrays are not validated and cannot cause an access out of bounds.  The clamp is fp32:
+ * Pi = 1 - Ps - Pr can round below 0, Ps can exceed 1 by the 1e-10 offset, and a node further than t from the candidate has
+ * probability exactly 0.  The sum is fp64, in a fixed order, without atomics: a thread adds its own nodes in ascending k, a
+ * wave of 64 adds its lanes in a fixed tree, the waves' sums are added in ascending wave order.
+ *   weights     device fp32 [nnz], may be NULL when nnz = 0        gamma   device fp32 [n]
+ *   candidates  device int32 [C]                                   obs     device int32 [n]
+ *   floor       in (0, 1]                                          scores  device fp64 [C][maxTime]
+ * Two forms, chosen from the graph alone: when gnode_dmp_source_lds_bytes(g) -- gnode_dmp_batch_lds_bytes(g) plus 256 bytes
+ * of fp64 reduction scratch -- fits the 160 KiB of LDS of a gfx950 workgroup, one workgroup integrates and scores one
+ * candidate from LDS, in ONE launch for the call, and the workspace is one unused unit of 256 bytes; otherwise the node and
+ * edge passes run over C * n rows and C * nnz edge slots of the workspace, two launches per time step, each block of 256 nodes
+ * leaves one partial at [c][t][block], and a last kernel adds them in ascending block order.  A candidate's row does not
+ * depend on C or on its position in the call; within a form the bits are reproducible from call to call (the forms differ in
+ * the order of the sum, not in the marginals).  The size queries return 0 without a handle, for C < 1 and for maxTime < 2.
+ * GNODE_ERR_ARG: a null pointer (weights may be null when nnz = 0), C < 1, maxTime < 2, floor not in (0, 1], in the general
+ * form C * max(blocks of 256 over the nodes, over the edges) >= 2^31, an asymmetric pattern; GNODE_ERR_WORKSPACE: a short
+ * workspace; nothing is written to `scores` in either case.  Synchronises `stream`. */
+size_t gnode_dmp_source_lds_bytes(gnode_graph_t g);
+size_t gnode_dmp_source_workspace_bytes(gnode_graph_t g, int32_t C, int32_t maxTime);
+int gnode_dmp_source_scores_f32(gnode_graph_t g, const float* weights, const float* gamma,
+                                const int32_t* candidates /* device [C] */, int32_t C, const int32_t* obs /* device [n] */,
+                                float floor, int32_t maxTime, double* scores /* device fp64 [C][maxTime] */,
+                                void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- mean-field baseline (reference ode_nn.py:214-233) ----
  * `runge_kutta_order4(sir, A, ...)`: dS = -beta (A I) S, dI = beta (A I) S - gamma I,
