@@ -1,5 +1,5 @@
-// The DMP recurrence, stated once for the marginals and their reverse sweep (gnode_dmp.hip) and for the source scores
-// (gnode_dmp_source.hip): the four dmp_* functions below and nothing else.  They work on values and on pointers that are
+// The DMP recurrence, stated once for the marginals and their reverse sweep (gnode_dmp.hip), for the source scores
+// (gnode_dmp_source.hip) and for the outbreak sizes (gnode_dmp_outbreak.hip): the four dmp_* functions below and nothing else.  They work on values and on pointers that are
 // already the sample's own, in global memory or in LDS.  The library is built with -ffp-contract=off, so they round as
 // written wherever they are inlined; their operand order is the reference's.
 #pragma once
@@ -36,6 +36,18 @@ __device__ __forceinline__ void dmp_edge_update(float P_u, float theta_rev, floa
     phi = ph;
     ps = ps_new;
     theta_next = theta - w_e * ph;
+}
+
+// The fp64 sums of gnode_dmp_source.hip and gnode_dmp_outbreak.hip, in a fixed order.  The sum of the 64 lanes' values in lane 0:
+// a fixed tree, 32 16 8 4 2 1 (every lane of the wave is active where this is called)
+__device__ __forceinline__ double dmp_wave_sum(double v) {
+    for (int off = 32; off >= 1; off >>= 1) v = v + __shfl_down(v, off, 64);
+    return v;
+}
+__device__ __forceinline__ double dmp_sum_in_order(const double* v, int count) {
+    double s = 0.0;
+    for (int i = 0; i < count; ++i) s = s + v[i];
+    return s;
 }
 
 __host__ __device__ static inline size_t dmp_align16(size_t x) { return (x + 15) / 16 * 16; }

@@ -44,17 +44,6 @@ __device__ __forceinline__ double dmp_source_term(int o, float ps, float pi, flo
     return log((double)fminf(fmaxf(p, floor), 1.0f));
 }
 
-// the sum of the 64 lanes' values in lane 0: a fixed tree, 32 16 8 4 2 1 (every lane of the wave is active where this is called)
-__device__ __forceinline__ double dmp_source_wave_sum(double v) {
-    for (int off = 32; off >= 1; off >>= 1) v = v + __shfl_down(v, off, 64);
-    return v;
-}
-__device__ __forceinline__ double dmp_source_sum_in_order(const double* v, int count) {
-    double s = 0.0;
-    for (int i = 0; i < count; ++i) s = s + v[i];
-    return s;
-}
-
 static constexpr size_t kDmpSourceRedBytes = 2 * 16 * sizeof(double);       // the waves' sums of a step, two steps' worth
 
 extern "C" size_t gnode_dmp_source_lds_bytes(gnode_graph_t g) {
@@ -86,7 +75,7 @@ __global__ __launch_bounds__(1024) void k_dmp_source_wg(const int* __restrict__ 
         Pi[k] = pi0; Pr[k] = 0.0f;
         acc = acc + dmp_source_term(a.obs[k], ps0, pi0, 0.0f, a.floor);
     }
-    acc = dmp_source_wave_sum(acc);
+    acc = dmp_wave_sum(acc);
     if (lane == 0) red[wave] = acc;
     for (int e = tid; e < nnz; e += nt) {
         float ps0, pi0;
@@ -95,7 +84,7 @@ __global__ __launch_bounds__(1024) void k_dmp_source_wg(const int* __restrict__ 
         rev[e] = rev_g[e];
     }
     __syncthreads();
-    if (tid == 0) score[0] = dmp_source_sum_in_order(red, waves);
+    if (tid == 0) score[0] = dmp_sum_in_order(red, waves);
     for (int t = 1; t < a.maxTime; ++t) {
         const float* th = theta[(t - 1) & 1];
         float* th_next = theta[t & 1];
@@ -110,10 +99,10 @@ __global__ __launch_bounds__(1024) void k_dmp_source_wg(const int* __restrict__ 
             Pr[k] = pr; Pi[k] = pi;
             acc = acc + dmp_source_term(a.obs[k], sk, pi, pr, a.floor);
         }
-        acc = dmp_source_wave_sum(acc);
+        acc = dmp_wave_sum(acc);
         if (lane == 0) red_t[wave] = acc;
         __syncthreads();                                                  // P and the wave sums are complete; theta[cur] is still this step's
-        if (tid == 0) score[t] = dmp_source_sum_in_order(red_t, waves);
+        if (tid == 0) score[t] = dmp_sum_in_order(red_t, waves);
         if (t + 1 < a.maxTime)                                            // (the last step's messages have no reader)
             for (int e = tid; e < nnz; e += nt) {                         // edge pass
                 const int u = src[e];
@@ -163,10 +152,10 @@ __global__ __launch_bounds__(256) void k_dmp_source_node(const int* __restrict__
         }
         term = dmp_source_term(a.obs[k], sk, pi, pr, a.floor);
     }
-    term = dmp_source_wave_sum(term);
+    term = dmp_wave_sum(term);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = term;
     __syncthreads();
-    if (threadIdx.x == 0) partial[(c * (size_t)a.maxTime + t) * per + blk] = dmp_source_sum_in_order(red, 4);
+    if (threadIdx.x == 0) partial[(c * (size_t)a.maxTime + t) * per + blk] = dmp_sum_in_order(red, 4);
 }
 
 __global__ __launch_bounds__(256) void k_dmp_source_edge(const int* __restrict__ src, const int* __restrict__ rev,
@@ -188,7 +177,7 @@ __global__ __launch_bounds__(256) void k_dmp_source_edge(const int* __restrict__
 __global__ __launch_bounds__(256) void k_dmp_source_add(const double* __restrict__ partial, unsigned per, size_t rows,
                                                        double* __restrict__ scores) {
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < rows; i += (size_t)gridDim.x * 256)
-        scores[i] = dmp_source_sum_in_order(partial + i * per, (int)per);
+        scores[i] = dmp_sum_in_order(partial + i * per, (int)per);
 }
 
 int gn_dmp_source_set_attributes() {        // once per device, from gnode_graph_create

@@ -12,6 +12,12 @@ same constructor and `run(seed_list, maxTime)`, the message passing runs in libg
                                                 [C, maxTime] on the GPU (an extension): the log-likelihood of one observed
                                                 snapshot for every candidate source and time, fused into the node pass
     rank_sources(scores, candidates)         -> the candidates by their best score, with the time at which each attains it
+    outbreak_sizes(graph, gamma, maxTime, candidates=None, action="seed", start=None, value=None, budget_bytes=1 << 30)
+                                             -> float64 tensor [C, maxTime, 3] on the GPU (an extension): the expected size of
+                                                S / I / R over time when candidate c alone is seeded or immunised in `start`,
+                                                summed in the node pass; infections(sizes) -> the number ever infected, [C]
+    greedy_immunisation(graph, start, gamma, maxTime, k), greedy_seeds(graph, gamma, maxTime, k, start=None)
+                                             -> [(node, infections_after), ...]: k greedy rounds of outbreak_sizes
 """
 from __future__ import annotations
 
@@ -214,7 +220,20 @@ def dmp_batch(weight_adj, starts, gamma, maxTime, scale=None, device="cuda"):
     return out
 
 
-def _source_ints(name, value, n_expected=None):
+def _largest_chunk(need, total, budget, who):
+    """The largest C <= total whose workspace `need(C)` fits `budget` bytes; ValueError if one candidate does not."""
+    if need(1) > budget:
+        raise ValueError(f"{who}: budget_bytes = {budget} is too small for one candidate ({need(1)} bytes)")
+    lo, hi = 1, total                                               # need(lo) <= budget throughout
+    if need(hi) <= budget:
+        lo = hi
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        lo, hi = (mid, hi) if need(mid) <= budget else (lo, mid)
+    return lo
+
+
+def _source_ints(name, value, n_expected=None, who="source_scores"):
     """`value` as a 1-D int64 host array of whole numbers (of length n_expected, where given); ValueError otherwise."""
     if isinstance(value, torch.Tensor):
         value = value.detach().cpu().numpy()
@@ -224,10 +243,10 @@ def _source_ints(name, value, n_expected=None):
             raise ValueError("not whole numbers")
         whole = a.astype(np.int64)
     except (TypeError, ValueError) as e:
-        raise ValueError(f"source_scores: {name} is not an array of integers ({e})") from None
+        raise ValueError(f"{who}: {name} is not an array of integers ({e})") from None
     if whole.ndim != 1 or (n_expected is not None and whole.shape[0] != n_expected):
         want = "1-D" if n_expected is None else f"[{n_expected}]"
-        raise ValueError(f"source_scores: {name} must have the shape {want}, got {tuple(whole.shape)}")
+        raise ValueError(f"{who}: {name} must have the shape {want}, got {tuple(whole.shape)}")
     return whole
 
 
@@ -270,15 +289,7 @@ def source_scores(graph, obs, gamma, maxTime, candidates=None, floor=1e-30, budg
     budget = int(budget_bytes)
     lib, handle = _lib.load(), G.graph.handle
     need = lambda c: int(lib.gnode_dmp_source_workspace_bytes(handle, c, T))       # noqa: E731  (grows with c, or is constant)
-    if need(1) > budget:
-        raise ValueError(f"source_scores: budget_bytes = {budget} is too small for one candidate ({need(1)} bytes)")
-    lo, hi = 1, int(cand.size)                                      # the largest chunk that fits: need(lo) <= budget throughout
-    if need(hi) <= budget:
-        lo = hi
-    while hi - lo > 1:
-        mid = (lo + hi) // 2
-        lo, hi = (mid, hi) if need(mid) <= budget else (lo, mid)
-    chunk = lo
+    chunk = _largest_chunk(need, int(cand.size), budget, "source_scores")
     up = lambda a, dt: None if a.size == 0 else torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(device)      # noqa: E731
     wd, gd = up(G.data, np.float32), up(np.broadcast_to(g, (n,)), np.float32)
     od, cd = up(o, np.int32), up(cand, np.int32)
@@ -310,3 +321,154 @@ def rank_sources(scores, candidates):
     best = s[np.arange(s.shape[0]), best_t]
     order = np.argsort(-best, kind="stable")
     return [(int(cand[i]), int(best_t[i]), float(best[i])) for i in order]
+
+
+_OUTBREAK_ACTIONS = {"seed": 0, "immunise": 1}
+
+
+class _Outbreak:
+    """The checked, host-side half of an `outbreak_sizes` call -- graph, gamma, value, horizon -- and, from `device_tables` on,
+    the device tables and the library: made once, then `sizes` serves any start, candidate list and action on them (the rounds
+    of the greedy helpers).  Everything in __init__ raises ValueError and touches neither the library nor a graph handle."""
+
+    def __init__(self, who, graph, gamma, maxTime, value, budget_bytes):
+        self.who = who
+        self.G = graph if isinstance(graph, DmpGraph) else DmpGraph(graph)
+        self.n, self.T = self.G.N, int(maxTime)
+        if self.T < 2:
+            raise ValueError(f"{who}: maxTime must be >= 2 (got {maxTime})")
+        self.gamma = _batch_numbers("gamma", gamma, [(), (self.n,)], who)
+        self.value = None if value is None else _batch_numbers("value", value, [(self.n,)], who)
+        self.budget = int(budget_bytes)
+        self.tables = None
+
+    def start(self, start):
+        """`start` -- None, a seed list or an `InitialState` -- as an InitialState of this graph's size."""
+        from .ode_nn import InitialState
+        if isinstance(start, InitialState):
+            if start.n != self.n:
+                raise ValueError(f"{self.who}: InitialState of {start.n} nodes given for a graph of {self.n}")
+            return start
+        seeds = [] if start is None else _source_ints("start", start, who=self.who)
+        return InitialState.from_sets(self.n, seeds)                 # (a seed outside the graph: ValueError)
+
+    def candidates(self, candidates, lowest):
+        """The candidate ids, every node by default, as an int64 array with at least one entry, each in [lowest, n)."""
+        cand = np.arange(self.n, dtype=np.int64) if candidates is None else _source_ints("candidates", candidates, who=self.who)
+        if cand.size < 1:
+            raise ValueError(f"{self.who}: need at least one candidate")
+        if cand.min() < lowest or cand.max() >= self.n:
+            raise ValueError(f"{self.who}: candidate {int(cand[(cand < lowest) | (cand >= self.n)][0])} is not in [{lowest}, {self.n})")
+        return cand
+
+    def device_tables(self, device):
+        if self.tables is None:
+            lib, handle = _lib.load(), self.G.graph.handle
+            up = lambda a: None if a is None or a.size == 0 else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(device)  # noqa: E731
+            self.tables = (lib, handle, up(self.G.data), up(np.broadcast_to(self.gamma, (self.n,))), up(self.value))
+        return self.tables
+
+    def sizes(self, start, cand, action, device):
+        """float64 device tensor [C, maxTime, 3]: the candidates in chunks of the largest C whose workspace fits the budget."""
+        lib, handle, wd, gd, vd = self.device_tables(device)
+        T = self.T
+        need = lambda c: int(lib.gnode_dmp_outbreak_workspace_bytes(handle, c, T))       # noqa: E731  (grows with c, or is constant)
+        chunk = _largest_chunk(need, int(cand.size), self.budget, self.who)
+        y0 = torch.from_numpy(start.p.astype(np.float32)).to(device)
+        cd = torch.from_numpy(cand.astype(np.int32)).to(device)
+        out = torch.empty((cand.size, T, 3), dtype=torch.float64, device=cd.device)
+        ws = torch.empty(need(chunk), dtype=torch.uint8, device=cd.device)
+        for at in range(0, cand.size, chunk):
+            c = min(chunk, cand.size - at)
+            _lib.check(lib.gnode_dmp_outbreak_sizes_f32(handle, _lib.ptr(wd), _lib.ptr(gd), _lib.ptr(y0), _lib.ptr(cd[at:at + c]), c,
+                                                        _OUTBREAK_ACTIONS[action], _lib.ptr(vd), T, _lib.ptr(out[at:at + c]), _lib.ptr(ws),
+                                                        ws.numel(), _lib.stream_ptr()))
+        return out
+
+
+def _outbreak_action(who, action, start):
+    if action not in _OUTBREAK_ACTIONS:
+        raise ValueError(f"{who}: action must be one of {sorted(_OUTBREAK_ACTIONS)}, got {action!r}")
+    if action == "immunise" and not (start.p[:, 1] > 0.0).any():
+        raise ValueError(f"{who}: nothing to immunise against: the start holds no infected mass")
+
+
+def outbreak_sizes(graph, gamma, maxTime, candidates=None, action="seed", start=None, value=None, budget_bytes=1 << 30, device="cuda"):
+    """Whom to immunise, or where to seed?  For every candidate node c, the expected size of each compartment over time under
+    DMP when c alone is changed in the outbreak `start`: a float64 device tensor [C, maxTime, 3],
+    sizes[c, t, j] = sum over the nodes k of value[k] * P^k_j(t),  j = 0 / 1 / 2 for S / I / R,  t = 0 .. maxTime - 1 (row 0 is the
+    start itself).  action="seed": c starts infected, (0, 1, 0); action="immunise": c starts removed, (0, 0, 1).  The
+    probabilities are `dmp_batch`'s float32 marginals from that start, bit for bit, but they never reach global memory: the sums
+    are taken in float64, in a fixed order, in the node pass that holds them in registers (`gnode_dmp_outbreak_sizes_f32`), so a
+    candidate's rows do not depend on the other candidates or on the chunking.  `infections(sizes)` reads the number ever
+    infected off the table.
+
+    graph: one matrix, as `DMP_SIR` takes, or a `DmpGraph` made from one; its `data` gives the weights.  gamma: a number or
+    per-node values [n], finite and >= 0.  start: an `InitialState`, a seed list, or None -- everybody susceptible; "immunise"
+    needs some infected mass in it.  candidates: node ids (repeats allowed), every node by default; -1 means "no change" and
+    gives the row of `start` as it is.  value: None -- every node counts 1 -- or n finite numbers >= 0, taken as float32.  The
+    candidates go to the library in chunks of the largest C whose `gnode_dmp_outbreak_workspace_bytes` fits `budget_bytes` (the
+    one-workgroup form needs no room per candidate: one chunk); a budget too small for one candidate raises ValueError.  What
+    is wrong raises ValueError before the library is loaded or a graph handle is made."""
+    who = "outbreak_sizes"
+    plan = _Outbreak(who, graph, gamma, maxTime, value, budget_bytes)
+    base = plan.start(start)
+    _outbreak_action(who, action, base)
+    return plan.sizes(base, plan.candidates(candidates, -1), action, device)
+
+
+def infections(sizes):
+    """The expected value-weighted number ever infected by the horizon for every candidate of an `outbreak_sizes` table: the
+    float64 [C] quantity sizes[:, -1, 1] + sizes[:, -1, 2] - sizes[:, 0, 2] -- infected or removed at the end, less those removed
+    at the start (the immunised among them), who never were infected.  A tensor gives a tensor, anything else a numpy array."""
+    s = sizes if isinstance(sizes, torch.Tensor) else np.asarray(sizes, dtype=np.float64)
+    if s.ndim != 3 or s.shape[1] < 1 or s.shape[2] != 3:
+        raise ValueError(f"infections: sizes must have the shape [C, maxTime, 3], got {tuple(s.shape)}")
+    if isinstance(s, torch.Tensor):
+        s = s.double()
+    return s[:, -1, 1] + s[:, -1, 2] - s[:, 0, 2]
+
+
+def _greedy(who, action, graph, start, gamma, maxTime, k, candidates, value, budget_bytes, device):
+    """k rounds of one `outbreak_sizes` call each over the pool -- the distinct candidates that are not yet chosen and not
+    already fully infected or removed in the start -- on one `_Outbreak`: the round's best node (lowest id among equals) gets
+    the action's triple in the start of the next round."""
+    from .ode_nn import initial_state
+    plan = _Outbreak(who, graph, gamma, maxTime, value, budget_bytes)
+    cur = plan.start(start)
+    _outbreak_action(who, action, cur)
+    pool = np.unique(plan.candidates(candidates, 0))                 # ascending: argmin / argmax take the lowest id among equals
+    pool = pool[cur.p[pool, 0] > 0.0]
+    try:
+        rounds = int(k)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: k must be a whole number (got {k!r})") from None
+    if rounds != k or rounds < 1 or rounds > pool.size:
+        raise ValueError(f"{who}: k must be a whole number in [1, {pool.size}], the candidates still susceptible (got {k!r})")
+    triple = (0.0, 1.0, 0.0) if action == "seed" else (0.0, 0.0, 1.0)
+    chosen = []
+    for _ in range(rounds):
+        inf = infections(plan.sizes(cur, pool, action, device)).cpu().numpy()
+        i = int(inf.argmax() if action == "seed" else inf.argmin())
+        p = cur.p.copy()
+        p[pool[i]] = triple
+        cur = initial_state(p)
+        chosen.append((int(pool[i]), float(inf[i])))
+        pool = np.delete(pool, i)
+    return chosen
+
+
+def greedy_immunisation(graph, start, gamma, maxTime, k, candidates=None, value=None, budget_bytes=1 << 30, device="cuda"):
+    """k nodes to immunise against the outbreak `start` (an `InitialState` or a seed list, with some infected mass), chosen
+    greedily: each round makes one `outbreak_sizes(..., action="immunise")` call over the candidates not yet chosen and not
+    already fully infected or removed, and the node with the fewest `infections` (the lowest id among equals) joins the
+    start's removed.  Returns [(node, infections_after), ...] in the order chosen.  The graph handle and the device tables are
+    made once for all rounds.  candidates: node ids in [0, n), every node by default; k must not exceed what is left of them.
+    What is wrong raises ValueError before the library is loaded or a graph handle is made."""
+    return _greedy("greedy_immunisation", "immunise", graph, start, gamma, maxTime, k, candidates, value, budget_bytes, device)
+
+
+def greedy_seeds(graph, gamma, maxTime, k, start=None, candidates=None, value=None, budget_bytes=1 << 30, device="cuda"):
+    """k nodes whose seeding spreads furthest, chosen greedily on top of `start` (None: everybody susceptible): `greedy_immunisation`
+    with action="seed" and the node with the MOST `infections` each round, which then starts infected in the next."""
+    return _greedy("greedy_seeds", "seed", graph, start, gamma, maxTime, k, candidates, value, budget_bytes, device)

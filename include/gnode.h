@@ -571,6 +571,40 @@ int gnode_dmp_source_scores_f32(gnode_graph_t g, const float* weights, const flo
                                 const int32_t* candidates /* device [C] */, int32_t C, const int32_t* obs /* device [n] */,
                                 float floor, int32_t maxTime, double* scores /* device fp64 [C][maxTime] */,
                                 void* workspace, size_t workspace_bytes, void* stream);
+/* Whom to immunise and where to seed (Lokhov, Saad 2017): the recurrence from each of C candidate interventions on one
+ * outbreak, kept only as the expected size of each compartment over time.  Candidate c's sample is gnode_dmp_batch_f32's from
+ * the shared base start init[n][3] = (pS, pI, pR) with the triple of node candidates[c] replaced -- action 0 (seed): (0, 1, 0),
+ * action 1 (immunise): (0, 0, 1) -- with the shared weights and gamma: the same fp32 marginals, bit for bit (Pr_0 from the
+ * triple, phi_0 = Pi_0, as gnode_dmp_init_f32 starts).  The kernels make that start from the id wherever one is read: no
+ * [C][n][3] start exists, and an id outside [0, n) (-1 is the documented spelling) matches no node and gives the base start
+ * itself, the "do nothing" row; so the candidates are not validated and cannot cause an access out of bounds.  No marginal
+ * reaches global memory: with P^k_j(t) = Ps / Pi / Pr of node k at step t for j = 0 / 1 / 2,
+ *   sizes[c][t][j] = sum over k of (double)value[k] * (double)P^k_j(t),     t = 0 .. maxTime - 1, row 0 = the start;
+ * value == NULL means 1 for every node.  The product of two floats is exact in a double; the sum is fp64, in a fixed order,
+ * without atomics: a thread adds its own nodes in ascending k, a wave of 64 adds its lanes in a fixed tree (32 16 8 4 2 1), the
+ * waves' sums are added in ascending wave order.
+ *   weights     device fp32 [nnz], may be NULL when nnz = 0        gamma   device fp32 [n]
+ *   init        device fp32 [n][3]                                 candidates  device int32 [C]
+ *   value       device fp32 [n] or NULL                            sizes   device fp64 [C][maxTime][3]
+ * Two forms, chosen from the graph alone: when gnode_dmp_outbreak_lds_bytes(g) -- gnode_dmp_batch_lds_bytes(g) plus 768 bytes
+ * of fp64 reduction scratch (16 waves' three sums, two steps' worth) -- fits the 160 KiB of LDS of a gfx950 workgroup, one
+ * workgroup integrates and sums one candidate from LDS, in ONE launch for the call, and the workspace is one unused unit of 256
+ * bytes; otherwise the node and edge passes run over C * n rows and C * nnz edge slots of the workspace, two launches per time
+ * step, each block of 256 nodes leaves one partial at [c][t][j][block], and a last kernel adds them in ascending block order.
+ * A candidate's rows do not depend on C or on its position in the call; within a form the bits are reproducible from call to
+ * call (the forms differ in the order of the sum, not in the marginals).  The size queries return 0 without a handle, for
+ * C < 1 and for maxTime < 2.
+ * GNODE_ERR_ARG: a null pointer (weights may be null when nnz = 0, value always), maxTime < 2, C < 1, an action other than 0
+ * or 1, in the general form C * max(blocks of 256 over the nodes, over the edges) >= 2^31, an asymmetric pattern;
+ * GNODE_ERR_WORKSPACE: a short workspace; nothing is written to `sizes` in either case.  Does NOT wait on the host: the call
+ * enqueues its kernels on `stream` and returns, allocates nothing and keeps nothing in the handle. */
+size_t gnode_dmp_outbreak_lds_bytes(gnode_graph_t g);
+size_t gnode_dmp_outbreak_workspace_bytes(gnode_graph_t g, int32_t C, int32_t maxTime);
+int gnode_dmp_outbreak_sizes_f32(gnode_graph_t g, const float* weights, const float* gamma, const float* init /* device [n][3] */,
+                                 const int32_t* candidates /* device [C] */, int32_t C, int32_t action,
+                                 const float* value /* device [n] or NULL */, int32_t maxTime,
+                                 double* sizes /* device fp64 [C][maxTime][3] */, void* workspace, size_t workspace_bytes,
+                                 void* stream);
 
 /* ---- mean-field baseline (reference ode_nn.py:214-233) ----
  * `runge_kutta_order4(sir, A, ...)`: dS = -beta (A I) S, dI = beta (A I) S - gamma I,
