@@ -1,7 +1,8 @@
 // The DMP recurrence, stated once for the marginals and their reverse sweep (gnode_dmp.hip), for the source scores
-// (gnode_dmp_source.hip) and for the outbreak sizes (gnode_dmp_outbreak.hip): the four dmp_* functions below and nothing else.  They work on values and on pointers that are
+// (gnode_dmp_source.hip, gnode_dmp_source_batch.hip) and for the outbreak sizes (gnode_dmp_outbreak.hip): the four dmp_* functions below and nothing else.  They work on values and on pointers that are
 // already the sample's own, in global memory or in LDS.  The library is built with -ffp-contract=off, so they round as
-// written wherever they are inlined; their operand order is the reference's.
+// written wherever they are inlined; their operand order is the reference's.  Behind them: the fixed-order fp64 sums, and what
+// the two source units share -- the synthesised start, the likelihood terms and the two kernels that read no observation.
 #pragma once
 #include "gnode_common.h"
 
@@ -48,6 +49,62 @@ __device__ __forceinline__ double dmp_sum_in_order(const double* v, int count) {
     double s = 0.0;
     for (int i = 0; i < count; ++i) s = s + v[i];
     return s;
+}
+
+// Source inference (gnode_dmp_source.hip, gnode_dmp_source_batch.hip).  The start of node k in the sample of candidate `cand`:
+// (1 - seed, seed, 0) like k_dmp_seed_out0; Pr_0 = 0
+__device__ __forceinline__ void dmp_source_state(int k, int cand, float& ps0, float& pi0) {
+    const float seed = k == cand ? 1.0f : 0.0f;
+    ps0 = 1.0f - seed;
+    pi0 = seed;
+}
+
+// the log-likelihood term of a node observed in state o; anything but 0 / 1 / 2 is "not observed"
+__device__ __forceinline__ double dmp_source_term(int o, float ps, float pi, float pr, float floor) {
+    if ((unsigned)o > 2u) return 0.0;
+    const float p = o == 0 ? ps : o == 1 ? pi : pr;
+    return log((double)fminf(fmaxf(p, floor), 1.0f));
+}
+
+// The same term for many observations of one node: its three possible values, once, and the choice among them by an
+// observation's code -- the double dmp_source_term(o, ...) returns, selected and never indexed.
+struct DmpSourceLogs { double s, i, r; };
+__device__ __forceinline__ DmpSourceLogs dmp_source_logs(float ps, float pi, float pr, float floor) {
+    return {log((double)fminf(fmaxf(ps, floor), 1.0f)), log((double)fminf(fmaxf(pi, floor), 1.0f)),
+            log((double)fminf(fmaxf(pr, floor), 1.0f))};
+}
+__device__ __forceinline__ double dmp_source_pick(int o, const DmpSourceLogs& l) {
+    return o == 0 ? l.s : o == 1 ? l.i : o == 2 ? l.r : 0.0;
+}
+
+// The two kernels of the source entries' general form that read no observation, for the argument struct of either unit (its
+// w, gamma, cand, n, nnz).  `per` blocks of 256 per candidate, candidate c = blockIdx.x / per; per-candidate state is at row
+// c * n + k and edge slot c * nnz + e of the workspace arrays.
+template <class Args>
+__global__ __launch_bounds__(256) void k_dmp_source_init(const int* __restrict__ src, Args a, unsigned per, float* __restrict__ theta,
+                                                        float* __restrict__ phi, float* __restrict__ ps) {
+    const size_t c = blockIdx.x / per;
+    const long e = (long)(blockIdx.x % per) * 256 + threadIdx.x;
+    if (e >= a.nnz) return;
+    const size_t slot = c * (size_t)a.nnz + e;
+    float ps0, pi0;
+    dmp_source_state(src[e], a.cand[c], ps0, pi0);
+    dmp_edge_start(ps0, pi0, a.w[e], theta[slot], phi[slot], ps[slot]);
+}
+template <class Args>
+__global__ __launch_bounds__(256) void k_dmp_source_edge(const int* __restrict__ src, const int* __restrict__ rev,
+                                                        const float* __restrict__ P, const float* __restrict__ theta, Args a,
+                                                        unsigned per, float* __restrict__ phi, float* __restrict__ ps,
+                                                        float* __restrict__ theta_next) {
+    const size_t c = blockIdx.x / per;
+    const long e = (long)(blockIdx.x % per) * 256 + threadIdx.x;
+    if (e >= a.nnz) return;
+    const size_t base = c * (size_t)a.nnz, slot = base + e;
+    const int u = src[e];
+    float ps0, pi0;
+    dmp_source_state(u, a.cand[c], ps0, pi0);
+    dmp_edge_update(P[c * (size_t)a.n + u], theta[base + rev[e]], ps0, a.w[e], a.gamma[u], phi[slot], ps[slot], theta[slot],
+                    theta_next[slot]);
 }
 
 __host__ __device__ static inline size_t dmp_align16(size_t x) { return (x + 15) / 16 * 16; }

@@ -30,20 +30,7 @@ struct DmpSourceArgs {
     int n, maxTime; long nnz;
 };
 
-// the start of node k in the sample of candidate `cand`: (1 - seed, seed, 0) like k_dmp_seed_out0; Pr_0 = 0
-__device__ __forceinline__ void dmp_source_state(int k, int cand, float& ps0, float& pi0) {
-    const float seed = k == cand ? 1.0f : 0.0f;
-    ps0 = 1.0f - seed;
-    pi0 = seed;
-}
-
-// the log-likelihood term of a node observed in state o; anything but 0 / 1 / 2 is "not observed"
-__device__ __forceinline__ double dmp_source_term(int o, float ps, float pi, float pr, float floor) {
-    if ((unsigned)o > 2u) return 0.0;
-    const float p = o == 0 ? ps : o == 1 ? pi : pr;
-    return log((double)fminf(fmaxf(p, floor), 1.0f));
-}
-
+// (dmp_source_state and dmp_source_term, which gnode_dmp_source_batch.hip shares, are in gnode_dmp.h)
 static constexpr size_t kDmpSourceRedBytes = 2 * 16 * sizeof(double);       // the waves' sums of a step, two steps' worth
 
 extern "C" size_t gnode_dmp_source_lds_bytes(gnode_graph_t g) {
@@ -115,18 +102,9 @@ __global__ __launch_bounds__(1024) void k_dmp_source_wg(const int* __restrict__ 
 }
 
 // The general form: `per` blocks of 256 per candidate, candidate c = blockIdx.x / per.  Per-candidate state is at row c * n + k
-// and edge slot c * nnz + e of the workspace arrays.
-__global__ __launch_bounds__(256) void k_dmp_source_init(const int* __restrict__ src, DmpSourceArgs a, unsigned per,
-                                                        float* __restrict__ theta, float* __restrict__ phi, float* __restrict__ ps) {
-    const size_t c = blockIdx.x / per;
-    const long e = (long)(blockIdx.x % per) * 256 + threadIdx.x;
-    if (e >= a.nnz) return;
-    const size_t slot = c * (size_t)a.nnz + e;
-    float ps0, pi0;
-    dmp_source_state(src[e], a.cand[c], ps0, pi0);
-    dmp_edge_start(ps0, pi0, a.w[e], theta[slot], phi[slot], ps[slot]);
-}
-
+// and edge slot c * nnz + e of the workspace arrays.  The messages' start and the edge pass, which read no observation, are
+// k_dmp_source_init and k_dmp_source_edge of gnode_dmp.h, shared with gnode_dmp_source_batch.hip.
+//
 // Step t of every candidate's nodes and the block's partial of scores[c][t]; t = 0 is the start itself (theta is not read).  No
 // thread leaves before the barrier: one past the last node contributes 0.
 __global__ __launch_bounds__(256) void k_dmp_source_node(const int* __restrict__ rowptr, const int* __restrict__ rev,
@@ -156,21 +134,6 @@ __global__ __launch_bounds__(256) void k_dmp_source_node(const int* __restrict__
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = term;
     __syncthreads();
     if (threadIdx.x == 0) partial[(c * (size_t)a.maxTime + t) * per + blk] = dmp_sum_in_order(red, 4);
-}
-
-__global__ __launch_bounds__(256) void k_dmp_source_edge(const int* __restrict__ src, const int* __restrict__ rev,
-                                                        const float* __restrict__ P, const float* __restrict__ theta, DmpSourceArgs a,
-                                                        unsigned per, float* __restrict__ phi, float* __restrict__ ps,
-                                                        float* __restrict__ theta_next) {
-    const size_t c = blockIdx.x / per;
-    const long e = (long)(blockIdx.x % per) * 256 + threadIdx.x;
-    if (e >= a.nnz) return;
-    const size_t base = c * (size_t)a.nnz, slot = base + e;
-    const int u = src[e];
-    float ps0, pi0;
-    dmp_source_state(u, a.cand[c], ps0, pi0);
-    dmp_edge_update(P[c * (size_t)a.n + u], theta[base + rev[e]], ps0, a.w[e], a.gamma[u], phi[slot], ps[slot], theta[slot],
-                    theta_next[slot]);
 }
 
 // scores[i] = the `per` partials of row i = c * maxTime + t, in ascending block order
@@ -244,13 +207,14 @@ extern "C" int gnode_dmp_source_scores_f32(gnode_graph_t g, const float* weights
     }
     const dim3 gn((unsigned)C * ng), ge((unsigned)C * eg);
     hipLaunchKernelGGL(k_dmp_source_node, gn, dim3(256), 0, st, g->rowptr, g->rev, ws.theta[0], a, ng, 0, ws.P, ws.Pr, ws.Pi, ws.partial);
-    hipLaunchKernelGGL(k_dmp_source_init, ge, dim3(256), 0, st, g->src, a, eg, ws.theta[0], ws.phi, ws.ps);
+    hipLaunchKernelGGL(k_dmp_source_init<DmpSourceArgs>, ge, dim3(256), 0, st, g->src, a, eg, ws.theta[0], ws.phi, ws.ps);
     GN_LAUNCH_CHECK();
     for (int t = 1; t < maxTime; ++t) {
         const int cur = (t - 1) & 1;
         hipLaunchKernelGGL(k_dmp_source_node, gn, dim3(256), 0, st, g->rowptr, g->rev, ws.theta[cur], a, ng, t, ws.P, ws.Pr, ws.Pi, ws.partial);
         if (t + 1 < maxTime)                 // (the last step's messages have no reader)
-            hipLaunchKernelGGL(k_dmp_source_edge, ge, dim3(256), 0, st, g->src, g->rev, ws.P, ws.theta[cur], a, eg, ws.phi, ws.ps, ws.theta[cur ^ 1]);
+            hipLaunchKernelGGL(k_dmp_source_edge<DmpSourceArgs>, ge, dim3(256), 0, st, g->src, g->rev, ws.P, ws.theta[cur], a, eg, ws.phi, ws.ps,
+                               ws.theta[cur ^ 1]);
         GN_LAUNCH_CHECK();
     }
     const size_t rows = (size_t)C * maxTime;

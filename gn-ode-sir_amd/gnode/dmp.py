@@ -12,6 +12,12 @@ same constructor and `run(seed_list, maxTime)`, the message passing runs in libg
                                                 [C, maxTime] on the GPU (an extension): the log-likelihood of one observed
                                                 snapshot for every candidate source and time, fused into the node pass
     rank_sources(scores, candidates)         -> the candidates by their best score, with the time at which each attains it
+    source_scores_batch(graph, obs, gamma, maxTime, candidates=None, floor=1e-30, budget_bytes=1 << 30) -> float64 tensor
+                                                [O, C, maxTime] on the GPU (an extension): `source_scores` for O snapshots
+                                                [O, n] (a device tensor of `sir_state_at` is used where it lies) in one pass of
+                                                the recurrence, row o bit for bit the solo call's; source_candidates_batch(obs)
+                                                is its default candidate list
+    source_rank_of(scores, candidates, truth) -> int64 tensor [O]: how many candidates beat each snapshot's true source
     outbreak_sizes(graph, gamma, maxTime, candidates=None, action="seed", start=None, value=None, budget_bytes=1 << 30)
                                              -> float64 tensor [C, maxTime, 3] on the GPU (an extension): the expected size of
                                                 S / I / R over time when candidate c alone is seeded or immunised in `start`,
@@ -308,6 +314,114 @@ def source_candidates(obs):
     o = np.asarray(obs).astype(np.int64)
     cand = np.flatnonzero(o >= 1)
     return cand if cand.size else np.arange(o.shape[0])
+
+
+def _is_device_ints(value):
+    return isinstance(value, torch.Tensor) and value.is_cuda and not value.dtype.is_floating_point and not value.dtype.is_complex
+
+
+def _source_obs_rows(obs, n, who):
+    """`obs` as O >= 1 rows of n whole numbers in -1 .. 2: an integer device tensor stays where it is (checked with torch
+    operations), anything else becomes an int64 host array; ValueError otherwise."""
+    if _is_device_ints(obs):
+        if obs.dim() != 2 or obs.shape[0] < 1 or obs.shape[1] != n:
+            raise ValueError(f"{who}: obs must have the shape [O >= 1, {n}], got {tuple(obs.shape)}")
+        if n and (int(obs.min()) < -1 or int(obs.max()) > 2):
+            raise ValueError(f"{who}: obs holds a value outside -1 (not observed), 0, 1, 2")
+        return obs
+    if isinstance(obs, torch.Tensor):
+        obs = obs.detach().cpu().numpy()
+    try:
+        a = np.asarray(obs)
+    except (TypeError, ValueError) as e:                            # (a ragged list)
+        raise ValueError(f"{who}: obs is not an array of integers ({e})") from None
+    if a.ndim != 2 or a.shape[0] < 1 or a.shape[1] != n:
+        raise ValueError(f"{who}: obs must have the shape [O >= 1, {n}], got {tuple(a.shape)}")
+    o = _source_ints("obs", a.reshape(-1), who=who).reshape(a.shape)
+    if o.size and (o.min() < -1 or o.max() > 2):
+        raise ValueError(f"{who}: obs holds a value outside -1 (not observed), 0, 1, 2")
+    return o
+
+
+def source_candidates_batch(obs):
+    """The candidates `source_scores_batch` takes by default for the rows `obs` [O, n]: the nodes observed infected or recovered
+    in at least one of them, ascending; every node if there is none.  A tensor is reduced where it lies; the ids come back as
+    a host array."""
+    if isinstance(obs, torch.Tensor):
+        seen = (obs >= 1).any(0).cpu().numpy()
+    else:
+        seen = (np.asarray(obs).astype(np.int64) >= 1).any(0)
+    cand = np.flatnonzero(seen)
+    return cand if cand.size else np.arange(seen.shape[0])
+
+
+def source_scores_batch(graph, obs, gamma, maxTime, candidates=None, floor=1e-30, budget_bytes=1 << 30, device="cuda"):
+    """`source_scores` for O snapshots of one graph in one pass of the recurrence: a float64 device tensor [O, C, maxTime], and
+    scores[o] equals source_scores(graph, obs[o], gamma, maxTime, candidates=candidates, floor=floor) BIT FOR BIT.  A
+    candidate's marginals do not depend on the observation, so the node pass computes the three possible terms of a node once
+    and every snapshot selects its own (`gnode_dmp_source_batch_scores_f32`): the rank of the true source over many Monte-Carlo
+    realisations (`source_rank_of`), or several hypotheses about one incomplete observation, cost one message passing per
+    candidate (per tile of `gnode_dmp_source_batch_tile` snapshots on a graph small enough for the one-workgroup form).
+
+    obs: O >= 1 rows of n whole numbers, 0 / 1 / 2 = observed susceptible / infected / recovered, -1 = not observed: a list of
+    lists, an array or a tensor.  An integer device tensor -- what `sir_state_at` returns -- is used where it lies and never
+    copied to the host.  candidates: node ids (repeats allowed), shared by the snapshots; by default
+    `source_candidates_batch(obs)`.  graph, gamma, floor and maxTime are `source_scores`'.  The candidates go to the library in
+    chunks of the largest C whose `gnode_dmp_source_batch_workspace_bytes` for these O snapshots fits `budget_bytes`; a budget
+    too small for one candidate raises ValueError.  For host inputs, what is wrong raises ValueError before the library is
+    loaded or a graph handle is made."""
+    who = "source_scores_batch"
+    G = graph if isinstance(graph, DmpGraph) else DmpGraph(graph)
+    n, T = G.N, int(maxTime)
+    if T < 2:
+        raise ValueError(f"{who}: maxTime must be >= 2 (got {maxTime})")
+    floor = float(floor)
+    if not 0.0 < floor <= 1.0 or not 0.0 < float(np.float32(floor)) <= 1.0:        # (a NaN fails it; so does a float32 zero)
+        raise ValueError(f"{who}: floor must be in (0, 1] as a float32 (got {floor})")
+    o = _source_obs_rows(obs, n, who)
+    cand = source_candidates_batch(o) if candidates is None else _source_ints("candidates", candidates, who=who)
+    if cand.size < 1:
+        raise ValueError(f"{who}: need at least one candidate")
+    if cand.min() < 0 or cand.max() >= n:
+        raise ValueError(f"{who}: candidate {int(cand[(cand < 0) | (cand >= n)][0])} is not in [0, {n})")
+    g = _batch_numbers("gamma", gamma, [(), (n,)], who)
+    budget, O, C = int(budget_bytes), int(o.shape[0]), int(cand.size)
+    lib, handle = _lib.load(), G.graph.handle
+    need = lambda c: int(lib.gnode_dmp_source_batch_workspace_bytes(handle, c, O, T))      # noqa: E731  (grows with c, or is constant)
+    chunk = _largest_chunk(need, C, budget, who)
+    up = lambda a, dt: None if a.size == 0 else torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(device)      # noqa: E731
+    wd, gd, cd = up(G.data, np.float32), up(np.broadcast_to(g, (n,)), np.float32), up(cand, np.int32)
+    od = o.to(torch.int8).contiguous() if isinstance(o, torch.Tensor) else up(o, np.int8)
+    scores = torch.empty((O, C, T), dtype=torch.float64, device=cd.device)
+    ws = torch.empty(need(chunk), dtype=torch.uint8, device=cd.device)
+    for at in range(0, C, chunk):
+        c = min(chunk, C - at)
+        _lib.check(lib.gnode_dmp_source_batch_scores_f32(handle, _lib.ptr(wd), _lib.ptr(gd), _lib.ptr(cd[at:at + c]), c, _lib.ptr(od), O,
+                                                         floor, T, _lib.ptr(scores[0, at:at + c]), C * T, _lib.ptr(ws), ws.numel(),
+                                                         _lib.stream_ptr()))
+    return scores
+
+
+def source_rank_of(scores, candidates, truth):
+    """How well was each snapshot's true source found?  For a `source_scores_batch` table [O, C, T] and the true source truth[o]
+    of every snapshot, an int64 tensor [O]: the number of candidates whose best score over time is STRICTLY greater than that
+    of the candidate equal to truth[o] -- 0 means the true source is ranked first, and a tie costs nothing.  A candidate id
+    that is repeated takes its first position; a truth[o] that is not among the candidates raises ValueError.  scores may be a
+    tensor, and is then ranked where it lies, or an array."""
+    s = scores if isinstance(scores, torch.Tensor) else torch.from_numpy(np.asarray(scores, dtype=np.float64))
+    cand = _source_ints("candidates", candidates, who="source_rank_of")
+    true = _source_ints("truth", truth, who="source_rank_of")
+    if s.dim() != 3 or s.shape[0] != true.shape[0] or s.shape[1] != cand.shape[0] or s.shape[2] < 1:
+        raise ValueError(f"source_rank_of: scores {tuple(s.shape)} is not [O = {true.shape[0]}, C = {cand.shape[0]}, T >= 1]")
+    first = {}
+    for i, k in enumerate(cand.tolist()):
+        first.setdefault(k, i)
+    missing = [k for k in true.tolist() if k not in first]
+    if missing:
+        raise ValueError(f"source_rank_of: the true source {missing[0]} is not among the candidates")
+    best = s.detach().max(2).values                                  # [O, C]
+    at = torch.tensor([first[k] for k in true.tolist()], dtype=torch.int64, device=s.device)
+    return (best > best.gather(1, at.view(-1, 1))).sum(1)
 
 
 def rank_sources(scores, candidates):

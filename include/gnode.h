@@ -20,7 +20,7 @@
  *     into a hipGraph on first use and one handle may serve several streams (each
  *     with its own workspace).  Functions that DO synchronise `stream` say so below
  *     (gnode_graph_create, gnode_sir_mc_philox with more than 32 seeds,
- *     gnode_sir_mc_philox_nodes, gnode_sir_mc_philox_edges, gnode_sir_mc_philox_traj_edges, gnode_sir_mc_philox_traj with more than 32 seeds or rate arrays, gnode_sir_mc_philox_init, gnode_sir_mc_coins, gnode_dmp_f32, gnode_dmp_init_f32, gnode_dmp_batch_f32, gnode_dmp_batch_backward_f32, gnode_dmp_backward_f32, gnode_dmp_source_scores_f32, gnode_meanfield_f64, gnode_meanfield_init_f64, gnode_meanfield_rates_f64, gnode_meanfield_rates_steps_f64).
+ *     gnode_sir_mc_philox_nodes, gnode_sir_mc_philox_edges, gnode_sir_mc_philox_traj_edges, gnode_sir_mc_philox_traj with more than 32 seeds or rate arrays, gnode_sir_mc_philox_init, gnode_sir_mc_coins, gnode_dmp_f32, gnode_dmp_init_f32, gnode_dmp_batch_f32, gnode_dmp_batch_backward_f32, gnode_dmp_backward_f32, gnode_dmp_source_scores_f32, gnode_dmp_source_batch_scores_f32, gnode_meanfield_f64, gnode_meanfield_init_f64, gnode_meanfield_rates_f64, gnode_meanfield_rates_steps_f64).
  *   - process-wide state: (1) a per-device "set up once" table (compute-unit count,
  *     dynamic-LDS kernel attributes), written under a lock by the first
  *     gnode_graph_create on a device and read-only afterwards; (2) the opt-in
@@ -571,6 +571,31 @@ int gnode_dmp_source_scores_f32(gnode_graph_t g, const float* weights, const flo
                                 const int32_t* candidates /* device [C] */, int32_t C, const int32_t* obs /* device [n] */,
                                 float floor, int32_t maxTime, double* scores /* device fp64 [C][maxTime] */,
                                 void* workspace, size_t workspace_bytes, void* stream);
+/* gnode_dmp_source_scores_f32 for O snapshots in one pass of the recurrence: a candidate's marginals do not depend on the
+ * observation, so per node and step the three possible terms (p = Ps, Pi, Pr) are computed once and each observation selects
+ * one of them, or nothing.
+ *   obs     device int8 [O][n]: 0 / 1 / 2 observed, anything else not observed
+ *   scores  device fp64: scores[o * score_stride + c * maxTime + t], score_stride >= C * maxTime (so a chunk of candidates can
+ *           write its slice of a [O][C_total][maxTime] table), and that entry is BIT FOR BIT what gnode_dmp_source_scores_f32
+ *           writes at [c][t] for obs[o] alone: the same form (chosen by gnode_dmp_source_lds_bytes as there), the same launch
+ *           shape, the same terms and the same order of every sum.  The other arguments are that entry's.
+ * One-workgroup form: a workgroup serves one candidate and a tile of gnode_dmp_source_batch_tile(g) observations, whose sums it
+ * keeps in registers, so a candidate's recurrence runs ceil(O / tile) times; the tile is at most 16 and narrows, down to 1, on a
+ * graph that leaves less LDS than its wave sums need (256 bytes per observation) -- the form never changes with O.  The
+ * workspace is one unused unit of 256 bytes.  General form: the node pass loops over all O observations after its three
+ * logarithms, in groups of gnode_dmp_source_batch_tile(g) that share a barrier, so the recurrence runs once per candidate; the
+ * workspace holds gnode_dmp_source_scores_f32's arrays and the partials [C][maxTime][O][blocks of 256 nodes] in fp64.
+ * gnode_dmp_source_batch_tile returns 0 without a handle; gnode_dmp_source_batch_workspace_bytes returns 0 without a handle,
+ * for C < 1, for O < 1 and for maxTime < 2.
+ * GNODE_ERR_ARG: a null pointer (weights may be null when nnz = 0), maxTime < 2, C < 1, O < 1, floor not in (0, 1],
+ * score_stride < C * maxTime, C * (tiles of observations | blocks of 256 over the nodes or the edges) >= 2^31, an asymmetric
+ * pattern; GNODE_ERR_WORKSPACE: a short workspace; nothing is written to `scores` in either case.  Synchronises `stream`. */
+int gnode_dmp_source_batch_tile(gnode_graph_t g);
+size_t gnode_dmp_source_batch_workspace_bytes(gnode_graph_t g, int32_t C, int32_t O, int32_t maxTime);
+int gnode_dmp_source_batch_scores_f32(gnode_graph_t g, const float* weights, const float* gamma,
+                                      const int32_t* candidates /* device [C] */, int32_t C, const int8_t* obs /* device [O][n] */,
+                                      int32_t O, float floor, int32_t maxTime, double* scores /* device fp64, see above */,
+                                      int64_t score_stride, void* workspace, size_t workspace_bytes, void* stream);
 /* Whom to immunise and where to seed (Lokhov, Saad 2017): the recurrence from each of C candidate interventions on one
  * outbreak, kept only as the expected size of each compartment over time.  Candidate c's sample is gnode_dmp_batch_f32's from
  * the shared base start init[n][3] = (pS, pI, pR) with the triple of node candidates[c] replaced -- action 0 (seed): (0, 1, 0),
