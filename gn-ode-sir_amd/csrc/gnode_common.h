@@ -46,6 +46,7 @@ int gn_sir_set_attributes();
 int gn_dmp_set_attributes();
 int gn_dmp_source_set_attributes();
 int gn_dmp_source_batch_set_attributes();
+int gn_dmp_source_events_set_attributes();
 int gn_dmp_outbreak_set_attributes();
 int gn_rhs_vjp_set_attributes();
 

@@ -1,5 +1,5 @@
 // The DMP recurrence, stated once for the marginals and their reverse sweep (gnode_dmp.hip), for the source scores
-// (gnode_dmp_source.hip, gnode_dmp_source_batch.hip) and for the outbreak sizes (gnode_dmp_outbreak.hip): the four dmp_* functions below and nothing else.  They work on values and on pointers that are
+// (gnode_dmp_source.hip, gnode_dmp_source_batch.hip, gnode_dmp_source_events.hip) and for the outbreak sizes (gnode_dmp_outbreak.hip): the four dmp_* functions below and nothing else.  They work on values and on pointers that are
 // already the sample's own, in global memory or in LDS.  The library is built with -ffp-contract=off, so they round as
 // written wherever they are inlined; their operand order is the reference's.  Behind them: the fixed-order fp64 sums, and what
 // the two source units share -- the synthesised start, the likelihood terms and the two kernels that read no observation.
@@ -75,6 +75,19 @@ __device__ __forceinline__ DmpSourceLogs dmp_source_logs(float ps, float pi, flo
 }
 __device__ __forceinline__ double dmp_source_pick(int o, const DmpSourceLogs& l) {
     return o == 0 ? l.s : o == 1 ? l.i : o == 2 ? l.r : 0.0;
+}
+
+// With the two event terms (gnode_dmp_source_events.hip): node k became infected AT this step with p = Ps(t-1) - Ps(t), and
+// recovered AT it with p = Pr(t) - Pr(t-1); ps_prev, pr_prev are the previous step's marginals, (1, 0) before the start.  The
+// first three are dmp_source_logs' doubles, so a row of codes 0 / 1 / 2 selects what dmp_source_pick selects.
+struct DmpSourceEventLogs { double s, i, r, on, off; };
+__device__ __forceinline__ DmpSourceEventLogs dmp_source_event_logs(float ps, float pi, float pr, float ps_prev, float pr_prev,
+                                                                    float floor) {
+    const DmpSourceLogs l = dmp_source_logs(ps, pi, pr, floor);
+    return {l.s, l.i, l.r, log((double)fminf(fmaxf(ps_prev - ps, floor), 1.0f)), log((double)fminf(fmaxf(pr - pr_prev, floor), 1.0f))};
+}
+__device__ __forceinline__ double dmp_source_event_pick(int o, const DmpSourceEventLogs& l) {
+    return o == 0 ? l.s : o == 1 ? l.i : o == 2 ? l.r : o == 3 ? l.on : o == 4 ? l.off : 0.0;
 }
 
 // The two kernels of the source entries' general form that read no observation, for the argument struct of either unit (its

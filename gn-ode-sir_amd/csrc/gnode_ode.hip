@@ -540,6 +540,7 @@ int gn_device_setup_once(int dev) {
     if (int e = gn_dmp_set_attributes()) return e;
     if (int e = gn_dmp_source_set_attributes()) return e;
     if (int e = gn_dmp_source_batch_set_attributes()) return e;
+    if (int e = gn_dmp_source_events_set_attributes()) return e;
     if (int e = gn_dmp_outbreak_set_attributes()) return e;
     if (int e = gn_rhs_vjp_set_attributes()) return e;
     g_dev_done[dev] = true;

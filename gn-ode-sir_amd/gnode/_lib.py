@@ -99,6 +99,9 @@ ABI = {
     "gnode_dmp_source_batch_tile": (_int, [_vp]),
     "gnode_dmp_source_batch_workspace_bytes": (_sz, [_vp, _i32, _i32, _i32]),
     "gnode_dmp_source_batch_scores_f32": (_int, [_vp, _vp, _vp, _vp, _i32, _vp, _i32, C.c_float, _i32, _vp, _i64, _vp, _sz, _vp]),
+    "gnode_dmp_source_events_tile": (_int, [_vp]),
+    "gnode_dmp_source_events_workspace_bytes": (_sz, [_vp, _i32, _i32, _i32]),
+    "gnode_dmp_source_events_scores_f32": (_int, [_vp, _vp, _vp, _vp, _i32, _vp, _i32, C.c_float, _i32, _vp, _i64, _vp, _sz, _vp]),
     "gnode_dmp_outbreak_lds_bytes": (_sz, [_vp]),
     "gnode_dmp_outbreak_workspace_bytes": (_sz, [_vp, _i32, _i32]),
     "gnode_dmp_outbreak_sizes_f32": (_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _sz, _vp]),

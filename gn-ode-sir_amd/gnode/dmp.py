@@ -18,6 +18,14 @@ same constructor and `run(seed_list, maxTime)`, the message passing runs in libg
                                                 the recurrence, row o bit for bit the solo call's; source_candidates_batch(obs)
                                                 is its default candidate list
     source_rank_of(scores, candidates, truth) -> int64 tensor [O]: how many candidates beat each snapshot's true source
+    source_scores_events(graph, rows, gamma, maxTime, candidates=None, floor=1e-30, budget_bytes=1 << 30) -> float64 tensor
+                                                [R, C, maxTime] on the GPU (an extension): `source_scores_batch` with the codes
+                                                3 = became infected at the step and 4 = recovered at the step, differences of
+                                                consecutive marginals taken in the node pass
+    timed_observations(n, nodes, offsets, kinds) -> TimedObservations: records taken at different times, packed into such rows;
+                                                observations_from_events(t_inf, t_rec, now, sensors, what) makes the records
+    source_scores_timed(graph, observations, gamma, maxTime, ...) -> float64 tensor [C, maxTime]: the log-likelihood of all
+                                                records when "now" is t steps after c was seeded (`sum_timed_rows` of the rows)
     outbreak_sizes(graph, gamma, maxTime, candidates=None, action="seed", start=None, value=None, budget_bytes=1 << 30)
                                              -> float64 tensor [C, maxTime, 3] on the GPU (an extension): the expected size of
                                                 S / I / R over time when candidate c alone is seeded or immunised in `start`,
@@ -320,26 +328,27 @@ def _is_device_ints(value):
     return isinstance(value, torch.Tensor) and value.is_cuda and not value.dtype.is_floating_point and not value.dtype.is_complex
 
 
-def _source_obs_rows(obs, n, who):
-    """`obs` as O >= 1 rows of n whole numbers in -1 .. 2: an integer device tensor stays where it is (checked with torch
+def _source_obs_rows(obs, n, who, name="obs", top=2):
+    """`obs` as O >= 1 rows of n whole numbers in -1 .. top: an integer device tensor stays where it is (checked with torch
     operations), anything else becomes an int64 host array; ValueError otherwise."""
+    outside = f"{who}: {name} holds a value outside -1 (not observed), 0 .. {top}"
     if _is_device_ints(obs):
         if obs.dim() != 2 or obs.shape[0] < 1 or obs.shape[1] != n:
-            raise ValueError(f"{who}: obs must have the shape [O >= 1, {n}], got {tuple(obs.shape)}")
-        if n and (int(obs.min()) < -1 or int(obs.max()) > 2):
-            raise ValueError(f"{who}: obs holds a value outside -1 (not observed), 0, 1, 2")
+            raise ValueError(f"{who}: {name} must have the shape [O >= 1, {n}], got {tuple(obs.shape)}")
+        if n and (int(obs.min()) < -1 or int(obs.max()) > top):
+            raise ValueError(outside)
         return obs
     if isinstance(obs, torch.Tensor):
         obs = obs.detach().cpu().numpy()
     try:
         a = np.asarray(obs)
     except (TypeError, ValueError) as e:                            # (a ragged list)
-        raise ValueError(f"{who}: obs is not an array of integers ({e})") from None
+        raise ValueError(f"{who}: {name} is not an array of integers ({e})") from None
     if a.ndim != 2 or a.shape[0] < 1 or a.shape[1] != n:
-        raise ValueError(f"{who}: obs must have the shape [O >= 1, {n}], got {tuple(a.shape)}")
-    o = _source_ints("obs", a.reshape(-1), who=who).reshape(a.shape)
-    if o.size and (o.min() < -1 or o.max() > 2):
-        raise ValueError(f"{who}: obs holds a value outside -1 (not observed), 0, 1, 2")
+        raise ValueError(f"{who}: {name} must have the shape [O >= 1, {n}], got {tuple(a.shape)}")
+    o = _source_ints(name, a.reshape(-1), who=who).reshape(a.shape)
+    if o.size and (o.min() < -1 or o.max() > top):
+        raise ValueError(outside)
     return o
 
 
@@ -370,7 +379,13 @@ def source_scores_batch(graph, obs, gamma, maxTime, candidates=None, floor=1e-30
     chunks of the largest C whose `gnode_dmp_source_batch_workspace_bytes` for these O snapshots fits `budget_bytes`; a budget
     too small for one candidate raises ValueError.  For host inputs, what is wrong raises ValueError before the library is
     loaded or a graph handle is made."""
-    who = "source_scores_batch"
+    entries = ("gnode_dmp_source_batch_workspace_bytes", "gnode_dmp_source_batch_scores_f32")
+    return _scores_of_rows("source_scores_batch", "obs", 2, entries, graph, obs, gamma, maxTime, candidates, floor, budget_bytes, device)
+
+
+def _scores_of_rows(who, name, top, entries, graph, obs, gamma, maxTime, candidates, floor, budget_bytes, device):
+    """`source_scores_batch` and `source_scores_events`: the rows `obs` (called `name`) of codes -1 .. top, checked, and the
+    candidates in chunks through the library's `entries` = (workspace query, scoring call), which share one signature."""
     G = graph if isinstance(graph, DmpGraph) else DmpGraph(graph)
     n, T = G.N, int(maxTime)
     if T < 2:
@@ -378,7 +393,7 @@ def source_scores_batch(graph, obs, gamma, maxTime, candidates=None, floor=1e-30
     floor = float(floor)
     if not 0.0 < floor <= 1.0 or not 0.0 < float(np.float32(floor)) <= 1.0:        # (a NaN fails it; so does a float32 zero)
         raise ValueError(f"{who}: floor must be in (0, 1] as a float32 (got {floor})")
-    o = _source_obs_rows(obs, n, who)
+    o = _source_obs_rows(obs, n, who, name, top)
     cand = source_candidates_batch(o) if candidates is None else _source_ints("candidates", candidates, who=who)
     if cand.size < 1:
         raise ValueError(f"{who}: need at least one candidate")
@@ -387,7 +402,8 @@ def source_scores_batch(graph, obs, gamma, maxTime, candidates=None, floor=1e-30
     g = _batch_numbers("gamma", gamma, [(), (n,)], who)
     budget, O, C = int(budget_bytes), int(o.shape[0]), int(cand.size)
     lib, handle = _lib.load(), G.graph.handle
-    need = lambda c: int(lib.gnode_dmp_source_batch_workspace_bytes(handle, c, O, T))      # noqa: E731  (grows with c, or is constant)
+    need_bytes, scores_f32 = (getattr(lib, e) for e in entries)
+    need = lambda c: int(need_bytes(handle, c, O, T))               # noqa: E731  (grows with c, or is constant)
     chunk = _largest_chunk(need, C, budget, who)
     up = lambda a, dt: None if a.size == 0 else torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(device)      # noqa: E731
     wd, gd, cd = up(G.data, np.float32), up(np.broadcast_to(g, (n,)), np.float32), up(cand, np.int32)
@@ -396,10 +412,157 @@ def source_scores_batch(graph, obs, gamma, maxTime, candidates=None, floor=1e-30
     ws = torch.empty(need(chunk), dtype=torch.uint8, device=cd.device)
     for at in range(0, C, chunk):
         c = min(chunk, C - at)
-        _lib.check(lib.gnode_dmp_source_batch_scores_f32(handle, _lib.ptr(wd), _lib.ptr(gd), _lib.ptr(cd[at:at + c]), c, _lib.ptr(od), O,
-                                                         floor, T, _lib.ptr(scores[0, at:at + c]), C * T, _lib.ptr(ws), ws.numel(),
-                                                         _lib.stream_ptr()))
+        _lib.check(scores_f32(handle, _lib.ptr(wd), _lib.ptr(gd), _lib.ptr(cd[at:at + c]), c, _lib.ptr(od), O, floor, T,
+                              _lib.ptr(scores[0, at:at + c]), C * T, _lib.ptr(ws), ws.numel(), _lib.stream_ptr()))
     return scores
+
+
+def source_candidates_events(rows):
+    """The candidates `source_scores_events` takes by default for the rows [R, n]: the nodes with a code >= 1 -- infected,
+    recovered, or seen to become either -- in at least one row, ascending; every node if there is none."""
+    return source_candidates_batch(rows)
+
+
+def source_scores_events(graph, rows, gamma, maxTime, candidates=None, floor=1e-30, budget_bytes=1 << 30, device="cuda"):
+    """`source_scores_batch` for evidence that is an EVENT as well as a state: a float64 device tensor [R, C, maxTime],
+    scores[r, c, t] = the log-likelihood of row r at model step t under DMP started from candidate c alone.  A row holds one code
+    per node: -1 not observed, 0 / 1 / 2 susceptible / infected / recovered at step t (as `source_scores_batch`), 3 = became
+    infected AT step t (`t_inf == t` of `sir_trajectories`), with probability Ps(t-1) - Ps(t), 4 = recovered AT step t
+    (`t_rec == t`), with probability Pr(t) - Pr(t-1); before the start everybody is susceptible, Ps(-1) = 1 and Pr(-1) = 0, so at
+    t = 0 a code 3 is certain at the candidate and at the floor elsewhere.  The differences are float32, of `dmp_batch`'s
+    marginals bit for bit, clamped to [floor, 1] before the float64 logarithm; they are taken in the node pass that holds both
+    steps in registers (`gnode_dmp_source_events_scores_f32`) and no marginal reaches global memory.  A row of codes -1 .. 2
+    equals `source_scores_batch`'s row bit for bit, and no row depends on the others or on the chunking.
+
+    rows: R >= 1 rows of n whole numbers in -1 .. 4; an integer device tensor is used where it lies.  candidates: by default
+    `source_candidates_events(rows)`.  Everything else is `source_scores_batch`'s, the chunking by
+    `gnode_dmp_source_events_workspace_bytes` included.  `timed_observations` packs records taken at different times into such
+    rows and `source_scores_timed` adds their shifted tables."""
+    entries = ("gnode_dmp_source_events_workspace_bytes", "gnode_dmp_source_events_scores_f32")
+    return _scores_of_rows("source_scores_events", "rows", 4, entries, graph, rows, gamma, maxTime, candidates, floor, budget_bytes,
+                           device)
+
+
+class TimedObservations:
+    """Records (node, offset, kind) packed into rows for `source_scores_events`, by `timed_observations`: `rows` int8 [R, n]
+    (-1 where a row has no record of a node), `row_offsets` int64 [R], the offset every record of a row shares (<= 0, steps
+    relative to "now"), and `row_events` int64 [R], how many records of the row have a kind other than 0.  Host arrays."""
+
+    def __init__(self, rows, row_offsets, row_events):
+        self.rows, self.row_offsets, self.row_events = rows, row_offsets, row_events
+        self.n = int(rows.shape[1])
+
+
+def timed_observations(n, nodes, offsets, kinds):
+    """Pack time-stamped records into a `TimedObservations`.  Record i says that node nodes[i] was seen offsets[i] <= 0 steps
+    from "now" in kind kinds[i]: 0 / 1 / 2 susceptible / infected / recovered then, 3 became infected at that step, 4 recovered
+    at that step (`source_scores_events`' codes).  A row holds records of ONE offset and at most one per node, so that the
+    kernel sums a row in its fixed order and the rows are added in a fixed order after it: the distinct offsets are packed in
+    descending order, 0 first, and within an offset a node's j-th record, in input order, goes to that offset's j-th row -- an
+    offset has as many rows as its most-observed node has records.  What is wrong raises ValueError."""
+    who = "timed_observations"
+    try:
+        size = int(n)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: n must be a whole number >= 1 (got {n!r})") from None
+    if size != n or size < 1:
+        raise ValueError(f"{who}: n must be a whole number >= 1 (got {n!r})")
+    node, off, kind = (_source_ints(name, v, who=who) for name, v in (("nodes", nodes), ("offsets", offsets), ("kinds", kinds)))
+    if not node.shape == off.shape == kind.shape or node.size < 1:
+        raise ValueError(f"{who}: nodes, offsets and kinds must be three sequences of one length >= 1, got {node.size}, {off.size}, {kind.size}")
+    if node.min() < 0 or node.max() >= size:
+        raise ValueError(f"{who}: node {int(node[(node < 0) | (node >= size)][0])} is not in [0, {size})")
+    if off.max() > 0:
+        raise ValueError(f"{who}: offset {int(off.max())} is after now: offsets are <= 0")
+    if kind.min() < 0 or kind.max() > 4:
+        raise ValueError(f"{who}: kind {int(kind[(kind < 0) | (kind > 4)][0])} is not in 0 .. 4")
+    rows, row_offsets = [], []
+    for d in sorted(set(off.tolist()), reverse=True):
+        first, seen = len(rows), {}
+        for k, code in zip(node[off == d].tolist(), kind[off == d].tolist()):
+            j = seen.get(k, 0)
+            seen[k] = j + 1
+            if first + j == len(rows):
+                rows.append(np.full(size, -1, dtype=np.int8))
+                row_offsets.append(d)
+            rows[first + j][k] = code
+    rows = np.stack(rows)
+    return TimedObservations(rows, np.asarray(row_offsets, dtype=np.int64), (rows >= 1).sum(1).astype(np.int64))
+
+
+def sum_timed_rows(table, row_offsets, row_events, floor):
+    """The shift-and-add of `source_scores_timed` on a `source_scores_events` table [R, C, T] (a tensor, summed where it lies,
+    or an array): float64 [C, T], out[c, t] = the sum over r, taken with explicit adds in ascending r from 0.0, of
+    table[r, c, t + row_offsets[r]] where t + row_offsets[r] >= 0 and of row_events[r] * log(float64(float32(floor))) where it is
+    not -- before the outbreak everybody is susceptible with probability 1 and every other kind is at the floor (exactly 0.0
+    for a row without such a record)."""
+    s = table if isinstance(table, torch.Tensor) else torch.from_numpy(np.asarray(table, dtype=np.float64))
+    off, events = _source_ints("row_offsets", row_offsets, who="sum_timed_rows"), _source_ints("row_events", row_events, who="sum_timed_rows")
+    if s.dim() != 3 or s.dtype != torch.float64 or off.shape[0] != s.shape[0] or events.shape[0] != s.shape[0] or (off.size and off.max() > 0):
+        raise ValueError(f"sum_timed_rows: need a float64 table [R, C, T] with R offsets <= 0 and R counts, got {tuple(s.shape)}, "
+                         f"{off.shape[0]}, {events.shape[0]}")
+    R, C, T = s.shape
+    before = float(np.log(np.float64(np.float32(floor))))
+    out = torch.zeros((C, T), dtype=torch.float64, device=s.device)
+    for r in range(R):
+        back = min(-int(off[r]), T)                                   # the row's model step is t - back
+        term = torch.full((C, T), int(events[r]) * before if events[r] else 0.0, dtype=torch.float64, device=s.device)
+        term[:, back:] = s[r, :, :T - back]
+        out = out + term
+    return out
+
+
+def source_scores_timed(graph, observations, gamma, maxTime, candidates=None, floor=1e-30, budget_bytes=1 << 30, device="cuda"):
+    """Which node started the outbreak, from records taken at DIFFERENT times -- onset or detection times at a few sensors,
+    recovery dates, tests on different days, twice for one person?  A float64 device tensor [C, maxTime]: scores[c, t] = the
+    log-likelihood of all records of `observations` (a `TimedObservations`) when "now" is t steps after candidate c was seeded.
+    It is `sum_timed_rows` of `source_scores_events(graph, observations.rows, ...)`: row r, whose records lie row_offsets[r]
+    steps before now, is read at model step t + row_offsets[r], and where that is before the outbreak a record of kind 0 is
+    certain and every other at the floor.  candidates: by default the nodes with a record of a kind other than 0, ascending
+    (`source_candidates_events(observations.rows)`).  The other arguments are `source_scores_events`'; `rank_sources` reads the
+    result."""
+    who = "source_scores_timed"
+    if not isinstance(observations, TimedObservations):
+        raise ValueError(f"{who}: observations must be what timed_observations returns, got {type(observations).__name__}")
+    table = source_scores_events(graph, observations.rows, gamma, maxTime, candidates, floor, budget_bytes, device)
+    return sum_timed_rows(table, observations.row_offsets, observations.row_events, floor)
+
+
+_EVENT_SOURCES = ("onset", "removal", "state")
+
+
+def observations_from_events(t_inf, t_rec, now, sensors, what=("onset",)):
+    """What the nodes `sensors` of ONE trajectory report at step `now`, as the (nodes, offsets, kinds) of `timed_observations`.
+    t_inf, t_rec: the trajectory's event steps [n] (a row of `sir_trajectories`' tensors, or arrays; -1 = never).  what: any of
+    "onset" -- kind 3 at offset t_inf - now for a sensor with 0 <= t_inf <= now, kind 0 (still susceptible) at offset 0 for
+    any other; "removal" -- kind 4 at offset t_rec - now for a sensor with 0 <= t_rec <= now, nothing for one not yet
+    recovered; "state" -- `sir_state_at`'s code at offset 0.  The records come in the order of `what`, then of `sensors`.  Runs on
+    the host."""
+    who = "observations_from_events"
+    ti, tr, ids = (_source_ints(name, v, who=who) for name, v in (("t_inf", t_inf), ("t_rec", t_rec), ("sensors", sensors)))
+    if ti.shape != tr.shape or ti.size < 1:
+        raise ValueError(f"{who}: t_inf and t_rec must be two 1-D rows of one length >= 1, got {ti.size} and {tr.size}")
+    if ids.size and (ids.min() < 0 or ids.max() >= ti.size):
+        raise ValueError(f"{who}: sensor {int(ids[(ids < 0) | (ids >= ti.size)][0])} is not in [0, {ti.size})")
+    t = _source_ints("now", [now], who=who)[0]
+    if t < 0:
+        raise ValueError(f"{who}: now must be >= 0 (got {now})")
+    what = (what,) if isinstance(what, str) else tuple(what)
+    if not what or any(w not in _EVENT_SOURCES for w in what):
+        raise ValueError(f"{who}: what must name some of {_EVENT_SOURCES}, got {what!r}")
+    nodes, offsets, kinds = [], [], []
+    for w in what:
+        for k in ids.tolist():
+            infected, recovered = 0 <= ti[k] <= t, 0 <= tr[k] <= t
+            if w == "onset":
+                record = (int(ti[k] - t), 3) if infected else (0, 0)
+            elif w == "removal":
+                record = (int(tr[k] - t), 4) if recovered else None
+            else:
+                record = (0, int(infected) + int(recovered))
+            if record is not None:
+                nodes.append(k); offsets.append(record[0]); kinds.append(record[1])
+    return nodes, offsets, kinds
 
 
 def source_rank_of(scores, candidates, truth):

@@ -20,7 +20,7 @@
  *     into a hipGraph on first use and one handle may serve several streams (each
  *     with its own workspace).  Functions that DO synchronise `stream` say so below
  *     (gnode_graph_create, gnode_sir_mc_philox with more than 32 seeds,
- *     gnode_sir_mc_philox_nodes, gnode_sir_mc_philox_edges, gnode_sir_mc_philox_traj_edges, gnode_sir_mc_philox_traj with more than 32 seeds or rate arrays, gnode_sir_mc_philox_init, gnode_sir_mc_coins, gnode_dmp_f32, gnode_dmp_init_f32, gnode_dmp_batch_f32, gnode_dmp_batch_backward_f32, gnode_dmp_backward_f32, gnode_dmp_source_scores_f32, gnode_dmp_source_batch_scores_f32, gnode_meanfield_f64, gnode_meanfield_init_f64, gnode_meanfield_rates_f64, gnode_meanfield_rates_steps_f64).
+ *     gnode_sir_mc_philox_nodes, gnode_sir_mc_philox_edges, gnode_sir_mc_philox_traj_edges, gnode_sir_mc_philox_traj with more than 32 seeds or rate arrays, gnode_sir_mc_philox_init, gnode_sir_mc_coins, gnode_dmp_f32, gnode_dmp_init_f32, gnode_dmp_batch_f32, gnode_dmp_batch_backward_f32, gnode_dmp_backward_f32, gnode_dmp_source_scores_f32, gnode_dmp_source_batch_scores_f32, gnode_dmp_source_events_scores_f32, gnode_meanfield_f64, gnode_meanfield_init_f64, gnode_meanfield_rates_f64, gnode_meanfield_rates_steps_f64).
  *   - process-wide state: (1) a per-device "set up once" table (compute-unit count,
  *     dynamic-LDS kernel attributes), written under a lock by the first
  *     gnode_graph_create on a device and read-only afterwards; (2) the opt-in
@@ -596,6 +596,28 @@ int gnode_dmp_source_batch_scores_f32(gnode_graph_t g, const float* weights, con
                                       const int32_t* candidates /* device [C] */, int32_t C, const int8_t* obs /* device [O][n] */,
                                       int32_t O, float floor, int32_t maxTime, double* scores /* device fp64, see above */,
                                       int64_t score_stride, void* workspace, size_t workspace_bytes, void* stream);
+/* gnode_dmp_source_batch_scores_f32 for time-stamped evidence: a row code may also say that a node CHANGED state at the model
+ * step, which DMP gives as a difference of two consecutive marginals that the node pass holds in registers.
+ *   rows    device int8 [R][n], code of node k at model step t -> p:
+ *             0 / 1 / 2  susceptible / infected / recovered at t   Ps(t), Pi(t), Pr(t)
+ *             3          became infected at step t                 Ps(t-1) - Ps(t),   Ps(-1) = 1.0f for every node
+ *             4          recovered at step t                       Pr(t) - Pr(t-1),   Pr(-1) = 0.0f
+ *             anything else: not observed, contributes 0.0
+ *           and the term is log((double)min(max(p, floor), 1.0f)) for every code; the differences are fp32, of the bits
+ *           gnode_dmp_batch_f32 writes at [t-1][k] and [t][k].  At t = 0 a code 3 gives log 1 = 0 at the candidate itself and
+ *           log(floor) elsewhere, a code 4 gives log(floor) everywhere.
+ *   scores  device fp64: scores[r * score_stride + c * maxTime + t], score_stride >= C * maxTime.  A row whose codes are all
+ *           outside 3 / 4 is BIT FOR BIT gnode_dmp_source_batch_scores_f32's row: the same form, launch shape, terms and order
+ *           of every sum; a row does not depend on R, C, its position or the other rows.
+ * The other arguments, the two forms, the tile (gnode_dmp_source_events_tile, at most 16), the workspace (its size for R rows),
+ * the error codes and the queries' zeros (no handle; C, R < 1; maxTime < 2) are gnode_dmp_source_batch_scores_f32's with R for
+ * O.  Nothing is written to `scores` when the call is refused.  Synchronises `stream`. */
+int gnode_dmp_source_events_tile(gnode_graph_t g);
+size_t gnode_dmp_source_events_workspace_bytes(gnode_graph_t g, int32_t C, int32_t R, int32_t maxTime);
+int gnode_dmp_source_events_scores_f32(gnode_graph_t g, const float* weights, const float* gamma,
+                                       const int32_t* candidates /* device [C] */, int32_t C, const int8_t* rows /* device [R][n] */,
+                                       int32_t R, float floor, int32_t maxTime, double* scores /* device fp64, see above */,
+                                       int64_t score_stride, void* workspace, size_t workspace_bytes, void* stream);
 /* Whom to immunise and where to seed (Lokhov, Saad 2017): the recurrence from each of C candidate interventions on one
  * outbreak, kept only as the expected size of each compartment over time.  Candidate c's sample is gnode_dmp_batch_f32's from
  * the shared base start init[n][3] = (pS, pI, pR) with the triple of node candidates[c] replaced -- action 0 (seed): (0, 1, 0),
