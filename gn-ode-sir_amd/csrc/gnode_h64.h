@@ -40,7 +40,11 @@ int gn_launch_mlp64(const gnode_graph_s* g, const float* X, const float* W, cons
 int gn_launch_step64(gnode_graph_s* g, long rows, float* Y, const float* ZI, float* ZI_next, const float* W,
                      const float* bias, const float* beta, const float* gamma, float dt, const gnode_params* p,
                      float* PR /* [rows][4] projected R state, or null = carry Y_R */, Step64Out out,
-                     void* hub_scratch /* gn_hub_scratch_bytes(g, B, 64, 1) bytes of the caller's workspace */, hipStream_t st);
+                     void* hub_scratch /* gn_hub_scratch_bytes(g, B, 64, 1) bytes of the caller's workspace */,
+                     unsigned* tickets /* GN_STEP_TICKET_WORDS zero words: the tile counters of this launch */,
+                     unsigned* tickets_next /* as many words, zeroed BY this launch for the next one (the two alternate) */, hipStream_t st);
+// tile counters of k_step64: one 128-B line per tile queue, two sets (even / odd steps) 64 B apart inside each line
+#define GN_STEP_TICKET_WORDS (8 * 32)
 
 // single-launch integration for graphs whose per-sample state fits one workgroup's LDS (gnode_h64.hip: k_tiny64)
 bool gn_tiny64_ok(int n, int n_steps, int n_out, bool prj);

@@ -2,7 +2,8 @@
 //
 // One launch per Euler step (per chunk of samples):
 //   k_step64<PRJ>    persistent 256-thread workgroups (4 per CU) walk 16-node tiles, three tiles in flight per
-//                    workgroup (software pipeline, see the kernel's header comment):
+//                    workgroup (software pipeline, see the kernel's header comment), the tiles behind a workgroup's
+//                    first two drawn from a counter per tile queue:
 //       gather   AI = sum_{c in adj} Z_I[c], one 16-lane group per row, neighbour rows as 256-B coalesced reads,
 //                eight in flight per group rolling through eight registers, column ids broadcast inside the group
 //                by DPP row_newbcast fused into the address add, ascending-column sum (the CPU scatter_add_ order);
@@ -108,7 +109,8 @@ __global__ __launch_bounds__(256, LAT ? 2 : StepOcc<PRJ>::value) void k_step64(c
                                                  const float* __restrict__ w2, const float* __restrict__ b2,
                                                  float* __restrict__ PR, Step64Out out,
                                                  const int* __restrict__ hubidx, const float* __restrict__ HubP /* per-segment partial sums [B][n_seg][64] */,
-                                                 const int* __restrict__ hub_seg_ptr, int n_seg) {
+                                                 const int* __restrict__ hub_seg_ptr, int n_seg, unsigned* tickets /* this launch's tile counters, zero */,
+                                                 unsigned* tickets_next /* the next launch's: zeroed here */) {
     // out.ai (training): the neighbour sums A Z_I(y_k) of this step are kept for the adjoint backward, which then reads a
     // row back instead of gathering the table a second time
     // measured on the 75k-node benchmark and fixed: non-temporal streaming state accesses (the gather table keeps the
@@ -117,7 +119,7 @@ __global__ __launch_bounds__(256, LAT ? 2 : StepOcc<PRJ>::value) void k_step64(c
     constexpr int XQ = 8;
     // one LDS block, sub-arrays at compile-time offsets: every access below is (one per-lane offset) + constant
     constexpr int O_W = 0, O_TA = O_W + 64 * TS, O_TB = O_TA + 16 * TS, O_T2I = O_TB + 16 * TS, O_T2S = O_T2I + 16 * TS,
-                  O_W3 = O_T2S + 16 * TS, O_END = O_W3 + 4 * 64;
+                  O_W3 = O_T2S + 16 * TS, O_TK = O_W3 + 4 * 64, O_END = O_TK + 4;
     __shared__ __attribute__((aligned(16))) float L[O_END];
     //   TA  updated Y_I rows of tile t (MFMA operand)     TB  Y_S rows of tile t+1 (MFMA operand)
     //   T2I Z_I'(t)     T2S Z_S(t+1)     W3 read-out weight rows (re-read every tile: 16 loop-invariant VGPRs otherwise)
@@ -153,6 +155,19 @@ __global__ __launch_bounds__(256, LAT ? 2 : StepOcc<PRJ>::value) void k_step64(c
     const int q_hi = __builtin_amdgcn_readfirstlane((int)(total_tiles * (q + 1) / xq));
     const int t_stride = gridDim.x / xq;
     int t_it = q_lo + blockIdx.x / xq;                     // iterator: the tile the NEXT fetch_head() describes
+    // Which tile comes next.  With a fixed stride (tile, tile + t_stride, ...) the four workgroups of a CU finish far apart,
+    // in the order the CU received them (its oldest waves are served first): on the 75k graph x 8 the first of them was
+    // through its 36-37 tiles after ~300 us and the last after ~385 us, so the CU ran the last quarter of the launch
+    // with one or two workgroups (100 MHz clock stamps per workgroup).  So only a workgroup's first two tiles
+    // are dealt by stride (nothing waits for a counter while the pipeline fills); every further tile is drawn from its
+    // queue's counter: thread 0 asks at the top of an iteration, the answer returns under the gather (whose loads were
+    // issued behind it) and goes round through LDS behind the first barrier.  Each tile is still visited exactly once, by
+    // one workgroup, with the same arithmetic: which workgroup it is changes no bit.  Two sets of counters alternate
+    // between launches; a launch zeroes the set of the next one (the prologue zeroes both).
+    constexpr bool DYN = !LAT;                             // (latency mode: one tile per workgroup, nothing to draw)
+    static_assert(32 * XQ <= GN_STEP_TICKET_WORDS, "a counter line per queue");
+    unsigned* const q_ctr = tickets + 32 * q;              // a 128-B line per queue
+    if (DYN && blockIdx.x == 0 && threadIdx.x < XQ) tickets_next[32 * threadIdx.x] = 0u;
     int b_it = __builtin_amdgcn_readfirstlane(t_it / tiles_per_sample);
     int tile_it = t_it - b_it * tiles_per_sample;
 
@@ -161,7 +176,7 @@ __global__ __launch_bounds__(256, LAT ? 2 : StepOcc<PRJ>::value) void k_step64(c
     const unsigned zoff = (unsigned)rows * 256u;           // byte offset of the table's zero row (one past the last row)
     auto fetch_head = [&](Stage& s) {                      // top of the chain: row id, row header, hub index
         s.ok = t_it < q_hi;
-        while (tile_it >= tiles_per_sample) { tile_it -= tiles_per_sample; ++b_it; }
+        while (s.ok && tile_it >= tiles_per_sample) { tile_it -= tiles_per_sample; ++b_it; }
         const int node = tile_it * 16 + lr;
         s.valid = s.ok && node < n;
         const int nodec = s.valid ? node : 0;
@@ -186,8 +201,9 @@ __global__ __launch_bounds__(256, LAT ? 2 : StepOcc<PRJ>::value) void k_step64(c
         if (!s.valid) s.end = s.start;
         s.base = (unsigned)b_it * (unsigned)n;             // first row of the tile's sample (uniform)
         if (sub < (s.hub ? 0 : s.end - s.start)) s.mine = (s.base + (unsigned)c0) * 256u;
-        t_it += t_stride; tile_it += t_stride;
     };
+    auto next_tile = [&](int t_new) { tile_it += t_new - t_it; t_it = t_new; };     // t_new > t_it
+
     auto fetch_cols = [&](Stage& s) {                      // second link: column ids 16..31 (rows longer than the header's 16)
         s.mine2 = zoff;
         if (s.ok) {
@@ -201,6 +217,7 @@ __global__ __launch_bounds__(256, LAT ? 2 : StepOcc<PRJ>::value) void k_step64(c
     Stage cur, n1, n2;
     cur.ok = false; cur.valid = false; cur.hub = false; cur.row = 0; cur.start = cur.end = 0; cur.mine = cur.mine2 = zoff; cur.hoff = 0; cur.hcnt = 0; cur.base = 0;
     fetch_head(n1);
+    next_tile(t_it + t_stride);
     float4 ys_n1 = zero4();
     if (n1.ok) ys_n1 = ld4so<NT>(YS, n1.row * 256u + lane_b);
     fetch_cols(n1);
@@ -221,6 +238,9 @@ __global__ __launch_bounds__(256, LAT ? 2 : StepOcc<PRJ>::value) void k_step64(c
         const float* const w3s = L + O_W3;
         // ---- top: head of tile t+2's chain
         fetch_head(n2);
+        int tkv = 1 << 24;                                 // (past every queue's end: tiles < 2^20)
+        if (DYN) { if (threadIdx.x == 0 && n2.ok) tkv = (int)__hip_atomic_fetch_add(q_ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+        else next_tile(t_it + t_stride);
         // ---- A: finish the gather of tile t.  v0..v7 hold neighbours 0..7 (requested one matrix phase ago); further
         // neighbours roll through the same eight registers four at a time, as far as the longest row of the WAVE needs
         // (wave-uniform branches), always summed in ascending column order (the CPU scatter_add_ order of the reference).
@@ -338,6 +358,7 @@ __global__ __launch_bounds__(256, LAT ? 2 : StepOcc<PRJ>::value) void k_step64(c
             *reinterpret_cast<float4*>(tA) = yi;                       // Y_I' -> operand of Z_I'(t)
         }
         if (n1.ok) *reinterpret_cast<float4*>(tB) = ys_n1;             // Y_S(t+1) -> operand of Z_S(t+1)
+        if (DYN && threadIdx.x == 0) reinterpret_cast<int*>(L)[O_TK] = tkv;   // (the gather's loads were issued behind it: it is back)
         // ---- C: request tile t+1's first 8 neighbour rows and its own rows (they travel under the matrix phase).
         // Unconditional on purpose (past the queue's end they read row 0 and the zero row): guarding this block and the
         // next load by the uniform `ok` flags cost 9 us per launch on the 75k graph x 8 (368 vs 359)
@@ -377,6 +398,7 @@ __global__ __launch_bounds__(256, LAT ? 2 : StepOcc<PRJ>::value) void k_step64(c
         // ---- D: tile t+2's Y_S row
         const float4 ys_n2 = ld4so<NT>(YS, n2.row * 256u + lane_b);
         __syncthreads();
+        if (DYN) next_tile(q_lo + 2 * t_stride + __builtin_amdgcn_readfirstlane(reinterpret_cast<const int*>(L)[O_TK]));
         // ---- E: Z_I'(t) and Z_S(t+1) in one matrix phase, each W fragment read once for both
 #define GN_DUAL(A, B) mfma_dual16<A, B>(L + O_TA, L + O_TB, L + O_W + 16 * w * TS, L + O_T2I, L + O_T2S, bias_l, fo, oo)
         if (cur.ok && n1.ok) GN_DUAL(true, true);
@@ -699,7 +721,7 @@ int gn_launch_mlp64(const gnode_graph_s* g, const float* X, const float* W, cons
 
 int gn_launch_step64(gnode_graph_s* g, long rows, float* Y, const float* ZI, float* ZI_next, const float* W,
                      const float* bias, const float* beta, const float* gamma, float dt, const gnode_params* p,
-                     float* PR, Step64Out out, void* hub_scratch, hipStream_t st) {
+                     float* PR, Step64Out out, void* hub_scratch, unsigned* tickets, unsigned* tickets_next, hipStream_t st) {
     GN_CHECK_ARG(rows < (1L << 24), "H=64 step kernel addresses rows with 32-bit byte offsets: rows=%ld >= 2^24 per launch "
                  "(split the batch)", rows);
     // (the hub segment partials are addressed the same way: (sample * n_seg + segment) * 256 bytes)
@@ -716,7 +738,7 @@ int gn_launch_step64(gnode_graph_s* g, long rows, float* Y, const float* ZI, flo
     const bool lat = total <= grid;            // one tile per workgroup: the latency-mode instantiation
 #define GN_STEP1(P, L, HB) hipLaunchKernelGGL((k_step64<P, L, HB>), dim3(grid), dim3(256), 0, st, g->rowhdr, g->col, g->info.n, rows, tps, total, Y, ZI, \
                                          ZI_next, W, bias, beta, gamma, dt, p->linear3_weight, p->linear3_bias, p->linearS2_weight,     \
-                                         p->linearS2_bias, PR, out, g->hubidx, HubP, g->hub_seg_ptr, g->n_seg)
+                                         p->linearS2_bias, PR, out, g->hubidx, HubP, g->hub_seg_ptr, g->n_seg, tickets, tickets_next)
 #define GN_STEP(P, L) { if (g->info.n_hub > 0) GN_STEP1(P, L, true); else GN_STEP1(P, L, false); }
     if (PR) { if (lat) GN_STEP(true, true) else GN_STEP(true, false) }
     else { if (lat) GN_STEP(false, true) else GN_STEP(false, false) }

@@ -677,8 +677,10 @@ FwdPlan gn_forward_plan(const gnode_graph_s* g, long rows, int H, int method, in
 // The forward workspace as byte offsets, in order: Y [3 slabs, element-contiguous] | Z [2 slabs; on the H = 64 path
 // [table 0][zero row][table 1][zero row]: rows shorter than the step kernel's gather width read a zero row instead of
 // branching per neighbour] | beta | gamma | projected R [rows][4] | (rk4) k1..k4, ytmp [3 slabs each] | the control block
-// of the persistent launches (tickets, barrier flags, give-up word) | `fixed`: the hub scratch (gn_hub_scratch_bytes).
+// of the persistent launches (tickets, barrier flags, give-up word; with one launch per H = 64 step its first
+// GN_STEP_TICKET_WORDS words are k_step64's tile counters instead) | `fixed`: the hub scratch (gn_hub_scratch_bytes).
 struct FwdLayout { size_t Y, Z, beta, gamma, pr, rk, ctl, fixed; };
+static_assert(sizeof(PersCtl) >= GN_STEP_TICKET_WORDS * sizeof(unsigned), "k_step64's tile counters live in the control block");
 static FwdLayout forward_layout(int64_t rows, int32_t H, int32_t method) {
     const size_t slab = gn_align((size_t)rows * H * sizeof(float)), vec = gn_align((size_t)rows * sizeof(float));
     size_t off = 0;
@@ -731,9 +733,13 @@ static int forward_prologue(const FwdCall& c, const FwdPlan& pl, const float* x,
     const gnode_params* p = c.p;
     const int H = c.H, lpr = gn_lpr(H), rpw = 256 / lpr;
     const dim3 grid((unsigned)((c.rows + rpw - 1) / rpw));
-    if (pl.h64 && c.n_steps > 0)        // encoder, beta/gamma, trajectory point 0, read-out, projected R and Z_I(y_0): one launch
+    if (pl.h64 && c.n_steps > 0) {      // encoder, beta/gamma, trajectory point 0, read-out, projected R and Z_I(y_0): one launch
+        // (one launch per step: the head of the same block holds k_step64's tile counters, and each step zeroes the next one's)
+        const bool steps = pl.path == FwdPath::per_step;
         return gn_launch_prologue64(x, p, c.Y, c.beta, c.gamma, c.sol, c.zi_cur, c.zi_nxt, c.PR, c.out(c.S, 0), c.out(c.I, 0),
-                                    c.out(c.R, 0), c.rows, pl.path == FwdPath::pers64 ? c.ctl : nullptr, gn_pers64_ctl_bytes(), c.st);
+                                    c.out(c.R, 0), c.rows, pl.path == FwdPath::pers64 || steps ? c.ctl : nullptr,
+                                    steps ? GN_STEP_TICKET_WORDS * sizeof(unsigned) : gn_pers64_ctl_bytes(), c.st);
+    }
     if (method == 0 && H < 128 && c.n_steps > 0) {     // generic H: encoder, read-out and Z_I(y_0) in one launch
         uint32_t* ctl = pl.path == FwdPath::persg ? (uint32_t*)c.ctl : nullptr;
         GN_LPR_DISPATCH(64, lpr, hipLaunchKernelGGL(k_prologue_generic<LPR>, grid, dim3(256), (size_t)H * H * sizeof(float), c.st, x,
@@ -802,7 +808,8 @@ static int forward_euler_steps(FwdCall c, const FwdPlan& pl) {
                              c.keep ? gn_keep_zs(c.keep, rows, k) : nullptr};
             const bool sampled = prof_begin(0, c.st);
             if (int e = gn_launch_step64(c.g, rows, Ycur, c.zi_cur, c.zi_nxt, p->odefunc_linear_weight,
-                                         p->odefunc_linear_bias, c.beta, c.gamma, dt, p, c.PR, out, c.hub_scratch, c.st))
+                                         p->odefunc_linear_bias, c.beta, c.gamma, dt, p, c.PR, out, c.hub_scratch,
+                                         (unsigned*)c.ctl + 16 * (k & 1), (unsigned*)c.ctl + 16 * ((k + 1) & 1), c.st))
                 return e;
             if (sampled) prof_mark(0, c.st);
             if (c.keep) { c.zi_cur = c.zi_nxt; c.zi_nxt = gn_keep_zi(c.keep, rows, std::min(k + 2, c.n_steps)); }
