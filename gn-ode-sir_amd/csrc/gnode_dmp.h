@@ -28,15 +28,22 @@ __device__ __forceinline__ void dmp_node_update(float P_k, float ps0_k, float pi
     pi = 1.0f - ps - pr;
 }
 
-// Ps_e and phi_e of this step (in place), theta_e of the NEXT step; `theta` is a reference so that it is loaded where it is used
-__device__ __forceinline__ void dmp_edge_update(float P_u, float theta_rev, float ps0_u, float w_e, float gamma_u, float& phi,
+// Ps_e and phi_e of this step (in place), theta_e of the NEXT step; `theta` is a reference so that it is loaded where it is used.
+// Two weights (gnode_dmp_schedule.hip, rates that change over time): phi_t is what survived THIS step, so it takes this step's
+// w_e and gamma_u; theta_{t+1} - theta_t is what is transmitted DURING the next step, so it takes the next step's w_next.
+__device__ __forceinline__ void dmp_edge_update(float P_u, float theta_rev, float ps0_u, float w_e, float w_next, float gamma_u, float& phi,
                                                 float& ps, const float& theta, float& theta_next) {
     const float mul = P_u / theta_rev;
     const float ps_new = ps0_u * mul;
     const float ph = (1.0f - w_e) * (1.0f - gamma_u) * phi - (ps_new - ps);
     phi = ph;
     ps = ps_new;
-    theta_next = theta - w_e * ph;
+    theta_next = theta - w_next * ph;
+}
+// constant rates: both weights are the edge's one
+__device__ __forceinline__ void dmp_edge_update(float P_u, float theta_rev, float ps0_u, float w_e, float gamma_u, float& phi,
+                                                float& ps, const float& theta, float& theta_next) {
+    dmp_edge_update(P_u, theta_rev, ps0_u, w_e, w_e, gamma_u, phi, ps, theta, theta_next);
 }
 
 // The fp64 sums of gnode_dmp_source.hip and gnode_dmp_outbreak.hip, in a fixed order.  The sum of the 64 lanes' values in lane 0:

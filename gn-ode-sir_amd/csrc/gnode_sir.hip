@@ -33,6 +33,12 @@
 // seed phase; the step loops do not know which form ran.  Row 0 of the counts is then accumulated like every other row
 // (k_sir_finalize<ACC0>).  Separate instances, not a run-time test in the shared ones: that form was measured and cost the
 // seed-list call 2 % at fb-social size, so the seed-list instances are the code they were before.
+//
+// Rates that change over time (gnode_sir_mc_philox_schedule, the SCHED instances, EDGES only): P staged tables of per-edge and
+// per-node thresholds and an int32 [T] phase table; step `it` reads table phase[it], a wave-uniform choice of two pointers at
+// the top of the step (sir_step_thr).  The coins do not know the schedule, so one phase gives the per-edge call's counts.
+// Separate instances again: the other forms' step pointers are their kernel arguments, and they compile to what they were
+// (DESIGN 4.12).
 #include "gnode_common.h"
 #include "gnode_sir_plan.h"
 #include <algorithm>
@@ -110,6 +116,17 @@ template <> struct SirTraj<true> { int16_t* events; uint32_t* curves; };
 template <bool INIT> struct SirInit {};
 template <> struct SirInit<true> { const unsigned long long* thr; };
 
+// SCHED instances (gnode_sir_mc_philox_schedule) take the phase table, int32 [T] in memory: step `it` reads its thresholds from
+// table phase[it] of P staged ones, thr_beta + phase[it] * nnz and thr_gamma + phase[it] * n -- a wave-uniform choice of two
+// pointers at the top of the step, behind which every read of a threshold sees that step's table.  EDGES instances only.  The
+// others take an empty struct, as with SirTraj and SirInit, and their step's pointers ARE the kernel's arguments.
+template <bool SCHED> struct SirSched {};
+template <> struct SirSched<true> { const int32_t* phase; };
+template <bool NODES, bool SCHED>
+__device__ __forceinline__ SirThr<NODES> sir_step_thr(SirThr<NODES> base, const SirSched<SCHED>& sc, int it, size_t len) {
+    if constexpr (SCHED) return base + (size_t)sc.phase[it] * len; else return base;
+}
+
 __device__ __forceinline__ void sir_curve_row(uint32_t* __restrict__ curves, long s, int T, int row, int n, int n_ever, int n_rec) {
     uint32_t* r = curves + ((size_t)s * T + row) * 3;
     r[0] = (uint32_t)(n - n_ever); r[1] = (uint32_t)(n_ever - n_rec); r[2] = (uint32_t)n_rec;
@@ -136,14 +153,15 @@ __global__ __launch_bounds__(256) void k_fill_i16(int16_t* __restrict__ p, size_
 #ifndef GN_SIR_UNROLL
 #define GN_SIR_UNROLL 8
 #endif
-template <bool STATE_IN_LDS, bool NODES, bool TRAJ, bool EDGES = false, bool INIT = false>
+template <bool STATE_IN_LDS, bool NODES, bool TRAJ, bool EDGES = false, bool INIT = false, bool SCHED = false>
 __global__ __launch_bounds__(1024) void k_sir_philox(const int* __restrict__ src, const int* __restrict__ dst, long nnz,
                                                     int n, const int* __restrict__ seeds, int n_seeds,
                                                     SirThr<NODES> thr_beta, SirThr<NODES> thr_gamma,
                                                     long sims, long sim_offset, int T, uint32_t k0, uint32_t k1,
                                                     uint32_t* __restrict__ hist, uint8_t* __restrict__ gstate, SirTraj<TRAJ> tr,
-                                                    SirInit<INIT> in) {
+                                                    SirInit<INIT> in, SirSched<SCHED> sc) {
     static_assert(NODES || !EDGES, "per-edge infection thresholds come with per-node recovery thresholds");
+    static_assert(EDGES || !SCHED, "a schedule switches per-edge tables");
     extern __shared__ uint8_t smem[];
     uint8_t* state = STATE_IN_LDS ? smem : gstate + (size_t)blockIdx.x * 2 * n;
     uint8_t* flag = state + n;
@@ -202,6 +220,7 @@ __global__ __launch_bounds__(1024) void k_sir_philox(const int* __restrict__ src
             if (threadIdx.x == 0) sir_curve_row(curves, s, T, 0, n, tcnt[0], INIT ? tcnt[1] : 0);
         }
         for (int it = 1; it < T; ++it) {
+            const SirThr<NODES> tb_step = sir_step_thr<NODES>(thr_beta, sc, it, (size_t)nnz), tg_step = sir_step_thr<NODES>(thr_gamma, sc, it, (size_t)n);
             // GN_SIR_UNROLL source ids in flight per thread: the scan is a chain of (global id load -> LDS state read)
             // pairs, latency-bound when issued one at a time.  Wiki-vote-size graph, 10 000 sims x T = 20: 38.8 ms at 1,
             // 25.9 ms at 4, 23.6 ms at 8.  Tried on top, no gain: 16-bit ids (23.4 ms: not bound by the id bytes); four
@@ -211,7 +230,7 @@ __global__ __launch_bounds__(1024) void k_sir_philox(const int* __restrict__ src
                 if (ON) {                                                                                     \
                     const int v = dst[E];                                                                     \
                     if (state[v] == ST_S &&                                                                   \
-                        (unsigned long long)philox_coin((uint32_t)(E), (uint32_t)it, sim, 0u, k0, k1) < sir_thr(thr_beta, EDGES ? (int)(E) : v)) \
+                        (unsigned long long)philox_coin((uint32_t)(E), (uint32_t)it, sim, 0u, k0, k1) < sir_thr(tb_step, EDGES ? (int)(E) : v)) \
                         flag[v] = 1;                                                                          \
                 }
             long e = threadIdx.x;
@@ -231,7 +250,7 @@ __global__ __launch_bounds__(1024) void k_sir_philox(const int* __restrict__ src
 #undef GN_EDGE
             for (int u = threadIdx.x; u < n; u += nthr)
                 if (state[u] == ST_I &&
-                    (unsigned long long)philox_coin((uint32_t)u, (uint32_t)it, sim, 1u, k0, k1) < sir_thr(thr_gamma, u))
+                    (unsigned long long)philox_coin((uint32_t)u, (uint32_t)it, sim, 1u, k0, k1) < sir_thr(tg_step, u))
                     flag[u] = 2;
             __syncthreads();
             int any = 0, n_new = 0, n_gone = 0;
@@ -279,14 +298,16 @@ __global__ __launch_bounds__(1024) void k_sir_philox(const int* __restrict__ src
 // and the recovery-only phase ask only whether a target is susceptible, so both stay sufficient next to w = 0 entries: a row
 // whose susceptible targets all sit behind zeros keeps being walked.  There is no COUNT && EDGES instance.
 // TRAJ: per-trajectory events and curves (SirTraj above); there is no COUNT && TRAJ instance.
-template <typename IdT, bool LISTS_IN_LDS, bool COUNT, bool NODES, bool TRAJ, bool EDGES = false, bool INIT = false>
+template <typename IdT, bool LISTS_IN_LDS, bool COUNT, bool NODES, bool TRAJ, bool EDGES = false, bool INIT = false, bool SCHED = false>
 __global__ __launch_bounds__(1024) void k_sir_frontier(const int* __restrict__ rowptr, const int* __restrict__ col, int n,
                                                       const int* __restrict__ seeds, int n_seeds,
                                                       SirThr<NODES> thr_beta, SirThr<NODES> thr_gamma,
                                                       long sims, long sim_offset, int T, uint32_t k0, uint32_t k1,
                                                       uint32_t* __restrict__ hist, int32_t* __restrict__ glists,
-                                                      unsigned long long* __restrict__ stats, SirTraj<TRAJ> tr, SirInit<INIT> in) {
+                                                      unsigned long long* __restrict__ stats, SirTraj<TRAJ> tr, SirInit<INIT> in,
+                                                      SirSched<SCHED> sc) {
     static_assert(!(COUNT && INIT), "the counting instantiation starts from a seed list");
+    static_assert(EDGES || !SCHED, "a schedule switches per-edge tables");
     static_assert(!(COUNT && TRAJ), "the counting instantiation has no per-trajectory output");
     static_assert(!(COUNT && EDGES) && (NODES || !EDGES), "per-edge thresholds: with per-node recovery, never counted");
     extern __shared__ uint32_t smem_w[];
@@ -312,6 +333,8 @@ __global__ __launch_bounds__(1024) void k_sir_frontier(const int* __restrict__ r
     unsigned long long st_blocks = 0, st_ecoins = 0, st_rcoins = 0, st_entries = 0;
     int16_t* ev_inf = nullptr; int16_t* ev_rec = nullptr; uint32_t* curves = nullptr;
     if constexpr (TRAJ) { ev_inf = tr.events; if (tr.events) ev_rec = tr.events + (size_t)sims * n; curves = tr.curves; }
+    size_t sched_nnz = 0;                                      // (SCHED) the length of one infection table
+    if constexpr (SCHED) sched_nnz = (size_t)rowptr[n];
     for (long s = blockIdx.x; s < sims; s += gridDim.x) {
         const uint32_t sim = (uint32_t)(sim_offset + s);
         for (int w = tid; w < nwords; w += nthr) { bits[w] = 0u; spent[w] = 0u; recb[w] = 0u; }
@@ -372,6 +395,8 @@ __global__ __launch_bounds__(1024) void k_sir_frontier(const int* __restrict__ r
         int rows_done = 1;                                     // (TRAJ) rows of `curves` written so far
         if (TRAJ && curves && tid == 0) sir_curve_row(curves, s, T, 0, n, n_ever, INIT ? n_ever - n_inf : 0);
         for (int it = 1; it < T && n_inf > 0; ++it) {
+            // this step's tables: drain, the recovery loop and the recovery-only branch read nothing else
+            const SirThr<NODES> tb_step = sir_step_thr<NODES>(thr_beta, sc, it, sched_nnz), tg_step = sir_step_thr<NODES>(thr_gamma, sc, it, (size_t)n);
             if (tid == 0) { cnt[0] = 0; cnt[1] = 0; }
             __syncthreads();
 #ifndef GN_SIR_MODEB
@@ -393,7 +418,7 @@ __global__ __launch_bounds__(1024) void k_sir_frontier(const int* __restrict__ r
 #pragma unroll
                     for (int j = 0; j < 4; ++j)
                         if ((nib >> j) & 1u) {
-                            if ((unsigned long long)w[j] < sir_thr(thr_gamma, u0 + j)) {
+                            if ((unsigned long long)w[j] < sir_thr(tg_step, u0 + j)) {
                                 gone |= 1u << j; atomicAdd(&hrec[(size_t)it * n + u0 + j], 1u);
                                 if (TRAJ && ev_inf) ev_rec[(size_t)s * n + u0 + j] = (int16_t)it;
                             } else ++alive;
@@ -435,7 +460,7 @@ __global__ __launch_bounds__(1024) void k_sir_frontier(const int* __restrict__ r
                 if (lane_in_wave < take) {
                     const int e = cq[slot], v = cq[128 + slot];
                     if (COUNT) { ++st_blocks; ++st_ecoins; }
-                    const unsigned long long tb = sir_thr(thr_beta, EDGES ? e : v);
+                    const unsigned long long tb = sir_thr(tb_step, EDGES ? e : v);
                     if ((unsigned long long)philox_coin((uint32_t)e, (uint32_t)it, sim, 0u, k0, k1) < tb) infect(v);
                 }
                 qn -= take;
@@ -506,7 +531,7 @@ __global__ __launch_bounds__(1024) void k_sir_frontier(const int* __restrict__ r
             for (int idx = tid; idx < n_inf; idx += nthr) {
                 const int u = (int)cur[idx];
                 if (COUNT) { ++st_blocks; ++st_rcoins; }
-                const unsigned long long tg = sir_thr(thr_gamma, u);
+                const unsigned long long tg = sir_thr(tg_step, u);
                 const bool gone = (unsigned long long)philox_coin((uint32_t)u, (uint32_t)it, sim, 1u, k0, k1) < tg;
                 if (gone) {
                     atomicAdd(&hrec[(size_t)it * n + u], 1u);
@@ -666,12 +691,13 @@ __global__ void k_put_seeds(SeedArg sa, int n_seeds, int32_t* __restrict__ seeds
 
 // The kernels one form of call can launch, by path (SirPath): RATES is SIR_SCALAR / SIR_NODES / SIR_EDGES.  The launch and the
 // registration below both go through sir_dispatch, so an instance cannot be launched without being registered.
-template <int RATES, bool TRAJ_, bool INIT_> struct SirKernels {
-    static constexpr bool NODES = RATES >= SIR_NODES, EDGES = RATES == SIR_EDGES, TRAJ = TRAJ_, INIT = INIT_;
-    static constexpr auto frontier_lds = &k_sir_frontier<uint16_t, true, false, NODES, TRAJ, EDGES, INIT>;
-    static constexpr auto frontier_mem = &k_sir_frontier<int32_t, false, false, NODES, TRAJ, EDGES, INIT>;
-    static constexpr auto scan_lds = &k_sir_philox<true, NODES, TRAJ, EDGES, INIT>;
-    static constexpr auto scan_mem = &k_sir_philox<false, NODES, TRAJ, EDGES, INIT>;
+// SCHED_: the four scheduled forms (per-edge rates only, TRAJ x INIT), reached through sir_dispatch_sched.
+template <int RATES, bool TRAJ_, bool INIT_, bool SCHED_ = false> struct SirKernels {
+    static constexpr bool NODES = RATES >= SIR_NODES, EDGES = RATES == SIR_EDGES, TRAJ = TRAJ_, INIT = INIT_, SCHED = SCHED_;
+    static constexpr auto frontier_lds = &k_sir_frontier<uint16_t, true, false, NODES, TRAJ, EDGES, INIT, SCHED>;
+    static constexpr auto frontier_mem = &k_sir_frontier<int32_t, false, false, NODES, TRAJ, EDGES, INIT, SCHED>;
+    static constexpr auto scan_lds = &k_sir_philox<true, NODES, TRAJ, EDGES, INIT, SCHED>;
+    static constexpr auto scan_mem = &k_sir_philox<false, NODES, TRAJ, EDGES, INIT, SCHED>;
 };
 // the counting instances (gnode_sir_mc_philox_counted): the frontier walk of SirKernels<SIR_SCALAR, false, false>
 static constexpr auto kSirCountedLds = &k_sir_frontier<uint16_t, true, true, false, false>;
@@ -686,6 +712,10 @@ template <class F> static void sir_dispatch(int rates, bool traj, bool init, F&&
     else if (rates == SIR_NODES) sir_dispatch_rates<SIR_NODES>(traj, init, f);
     else sir_dispatch_rates<SIR_SCALAR>(traj, init, f);
 }
+template <class F> static void sir_dispatch_sched(bool traj, bool init, F&& f) {        // f(SirKernels<SIR_EDGES, ..., true>{}) of the 2 x 2 scheduled forms
+    if (traj) { if (init) f(SirKernels<SIR_EDGES, true, true, true>{}); else f(SirKernels<SIR_EDGES, true, false, true>{}); }
+    else { if (init) f(SirKernels<SIR_EDGES, false, true, true>{}); else f(SirKernels<SIR_EDGES, false, false, true>{}); }
+}
 
 int gn_sir_set_attributes() {       // once per device, from gnode_graph_create
     hipError_t err = hipSuccess;
@@ -695,6 +725,8 @@ int gn_sir_set_attributes() {       // once per device, from gnode_graph_create
     };
     for (int form = 0; form < 12; ++form)
         sir_dispatch(form >> 2, form & 2, form & 1, [&](auto K) { lift(K.frontier_lds); lift(K.frontier_mem); lift(K.scan_lds); });
+    for (int form = 0; form < 4; ++form)
+        sir_dispatch_sched(form & 2, form & 1, [&](auto K) { lift(K.frontier_lds); lift(K.frontier_mem); lift(K.scan_lds); });
     lift(kSirCountedLds); lift(kSirCountedMem); lift(&k_sir_coins);
     GN_HIP(err);
     return 0;
@@ -707,6 +739,9 @@ extern "C" size_t gnode_sir_nodes_workspace_bytes(gnode_graph_t g, int32_t T) { 
 extern "C" size_t gnode_sir_traj_workspace_bytes(gnode_graph_t g, int32_t T) { return sir_ws_bytes(g, T, SIR_NODES); }   // scalar rates too
 extern "C" size_t gnode_sir_edges_workspace_bytes(gnode_graph_t g, int32_t T) { return sir_ws_bytes(g, T, SIR_EDGES); }
 extern "C" size_t gnode_sir_init_workspace_bytes(gnode_graph_t g, int32_t T) { return sir_ws_bytes(g, T, SIR_INIT); }
+extern "C" size_t gnode_sir_schedule_workspace_bytes(gnode_graph_t g, int32_t T, int32_t P) {
+    return g && P >= 1 ? sir_schedule_layout(g->info.n, g->nnz, g->n_bigrow, T, P).total : 0;
+}
 
 // One Monte-Carlo call, as its entry states it (include/gnode.h documents the arrays).
 struct SirCall {
@@ -721,6 +756,9 @@ struct SirCall {
     void *workspace = nullptr, *stream = nullptr; size_t workspace_bytes = 0; int ws_form = SIR_SCALAR;   // which of SirLayout::bytes the entry asks for
     bool edge_scan = false;                  // the scan kernel (the cross-check) instead of the frontier walk
     uint64_t* stats_host = nullptr;          // gnode_sir_mc_philox_counted: the counting instances, their tally [4] copied here
+    // gnode_sir_mc_philox_schedule (sched): P phases of per-edge tables, host fp64 w [P][nnz] and gamma [P][n], and the host phase
+    // table [T]; `rates` rests
+    bool sched = false; const int32_t* phase = nullptr; int32_t P = 0; const double *w_sched = nullptr, *gamma_sched = nullptr;
 };
 // the arguments every entry has, under the names every entry gives them
 #define SIR_CALL(c, name)                                                                                                         \
@@ -733,6 +771,7 @@ static int sir_mc_philox_impl(const SirCall& c) {
     const bool traj = c.events || c.curves;
     const hipStream_t st = (hipStream_t)c.stream;
     GN_CHECK_ARG(g && c.workspace && (!c.drawn || c.init), "%s: null pointer", c.who);
+    GN_CHECK_ARG(!c.sched || (c.P >= 1 && c.gamma_sched && (c.w_sched || g->nnz == 0) && (c.phase || c.T <= 1)), "%s: a schedule takes P >= 1 phases (P = %d), the phase table and both rate tables", c.who, c.P);
     GN_CHECK_ARG(c.need_traj ? traj : (traj || c.counts), "%s: no output array given", c.who);
     GN_CHECK_ARG(!c.events || (c.T <= 32767 && ((uintptr_t)c.events & 1u) == 0), "%s: events hold int16 steps (T = %d, at most 32767) at an even address", c.who, c.T);
     GN_CHECK_ARG(r.form != SIR_NODES || (r.beta_nodes && r.gamma_nodes), "%s: one per-node rate array without the other", c.who);
@@ -742,9 +781,11 @@ static int sir_mc_philox_impl(const SirCall& c) {
     const int n = g->info.n, T = c.T;
     for (int i = 0; i < c.n_seeds; ++i)
         GN_CHECK_ARG(c.seeds[i] >= 0 && c.seeds[i] < n, "%s: seed %d out of range", c.who, c.seeds[i]);
-    const SirLayout L = sir_layout(n, g->nnz, g->n_bigrow, T);
-    if (c.workspace_bytes < L.bytes[c.ws_form]) {
-        gnode_set_error("%s: workspace %zu < %zu", c.who, c.workspace_bytes, L.bytes[c.ws_form]);
+    const SirScheduleLayout SL = sir_schedule_layout(n, g->nnz, g->n_bigrow, T, c.sched ? c.P : 1);
+    const SirLayout L = c.sched ? static_cast<const SirLayout&>(SL) : sir_layout(n, g->nnz, g->n_bigrow, T);
+    const size_t need = c.sched ? SL.total : L.bytes[c.ws_form];
+    if (c.workspace_bytes < need) {
+        gnode_set_error("%s: workspace %zu < %zu", c.who, c.workspace_bytes, need);
         return c.stats_host ? GNODE_ERR_ARG : GNODE_ERR_WORKSPACE;   // (the counted entry has always called it an argument)
     }
     // A drawn start with per-node rates on a graph of fewer entries than nodes: two per-node arrays would reach into the start
@@ -756,14 +797,16 @@ static int sir_mc_philox_impl(const SirCall& c) {
         GN_HIP(hipMemcpyAsync(col.data(), g->col, sizeof(int32_t) * (size_t)g->nnz, hipMemcpyDeviceToHost, st));
         GN_HIP(hipStreamSynchronize(st));
     }
-    const SirThresholds thr = sir_stage(c.who, n, g->nnz, r, restate ? col.data() : nullptr, c.init);
+    const SirThresholds thr = c.sched ? sir_stage_schedule(c.who, n, g->nnz, T, c.P, c.phase, c.w_sched, c.gamma_sched, c.init)
+                                      : sir_stage(c.who, n, g->nnz, r, restate ? col.data() : nullptr, c.init);
     GN_CHECK_ARG(thr.error.empty(), "%s", thr.error.c_str());
-    const int form = restate ? SIR_EDGES : r.form;
+    const int form = restate || c.sched ? SIR_EDGES : r.form;
     char* ws = (char*)c.workspace;
     uint32_t* hist = (uint32_t*)(ws + L.hist);
     int32_t* seeds = (int32_t*)(ws + L.seeds);
     unsigned long long* stats = c.stats_host ? (unsigned long long*)(ws + L.rows) : nullptr;
-    const unsigned long long *thr_b = (const unsigned long long*)(ws + L.thr), *thr_g = thr_b + (thr.rates.size() - (form ? n : 0));
+    const unsigned long long *thr_b = (const unsigned long long*)(ws + L.thr), *thr_g = thr_b + (thr.rates.size() - (form ? (size_t)n * (c.sched ? c.P : 1) : 0));
+    const int32_t* phase_dev = (const int32_t*)(ws + SL.phase);                      // (sched)
     const unsigned long long* thr_start = (const unsigned long long*)(ws + L.start);
     if (stats) GN_HIP(hipMemsetAsync(stats, 0, 4 * sizeof(unsigned long long), st));
     if (int e = gn_zero_async(hist, L.seeds - L.hist, st)) return e;
@@ -786,6 +829,7 @@ static int sir_mc_philox_impl(const SirCall& c) {
     }
     if (form) GN_HIP(hipMemcpyAsync((void*)thr_b, thr.rates.data(), thr.rates.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, st));
     if (c.init) GN_HIP(hipMemcpyAsync((void*)thr_start, thr.start.data(), thr.start.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, st));
+    if (c.sched && T > 1) GN_HIP(hipMemcpyAsync((void*)phase_dev, c.phase, sizeof(int32_t) * (size_t)T, hipMemcpyHostToDevice, st));
     if (c.n_seeds > 32 || form || c.init) GN_HIP(hipStreamSynchronize(st));     // the host arrays are done with
     const uint32_t k0 = (uint32_t)(c.rng_seed & 0xFFFFFFFFull), k1 = (uint32_t)(c.rng_seed >> 32);
     if (c.sims > 0) {
@@ -793,11 +837,12 @@ static int sir_mc_philox_impl(const SirCall& c) {
         const SirLaunch P = sir_launch_plan(n, g->n_bigrow, g->info.num_cu, c.sims, c.edge_scan);
         const bool frontier = P.path == SIR_FRONTIER_LDS || P.path == SIR_FRONTIER_MEM;
         void* tail = P.path == SIR_FRONTIER_MEM || P.path == SIR_SCAN_MEM ? ws + L.tail : nullptr;   // the lists / the state, when not in LDS
-        // the drawn start is a set of instances of its own (INIT): the seed-list instances do not carry it
-        sir_dispatch(form, traj, c.init != nullptr, [&](auto K) {
+        auto launch = [&](auto K) {
             using Kt = decltype(K);
             SirTraj<Kt::TRAJ> tr;
             SirInit<Kt::INIT> in;
+            SirSched<Kt::SCHED> sc;
+            if constexpr (Kt::SCHED) sc.phase = phase_dev;
             SirThr<Kt::NODES> tb, tg;                      // the staged arrays, or the two numbers
             if constexpr (Kt::TRAJ) { tr.events = c.events; tr.curves = c.curves; }
             if constexpr (Kt::INIT) in.thr = thr_start;
@@ -806,13 +851,16 @@ static int sir_mc_philox_impl(const SirCall& c) {
                 auto kernel = P.path == SIR_FRONTIER_LDS ? Kt::frontier_lds : Kt::frontier_mem;
                 if constexpr (!Kt::NODES && !Kt::TRAJ && !Kt::INIT) if (stats) kernel = P.path == SIR_FRONTIER_LDS ? kSirCountedLds : kSirCountedMem;
                 hipLaunchKernelGGL(kernel, dim3(P.grid), dim3(P.threads), P.lds, st, g->rowptr, g->col, n, seeds, c.n_seeds, tb, tg, (long)c.sims,
-                                   (long)c.sim_offset, T, k0, k1, hist, (int32_t*)tail, stats, tr, in);
+                                   (long)c.sim_offset, T, k0, k1, hist, (int32_t*)tail, stats, tr, in, sc);
             } else {
                 auto kernel = P.path == SIR_SCAN_LDS ? Kt::scan_lds : Kt::scan_mem;
                 hipLaunchKernelGGL(kernel, dim3(P.grid), dim3(P.threads), P.lds, st, g->src, g->col, (long)g->nnz, n, seeds, c.n_seeds, tb, tg, (long)c.sims,
-                                   (long)c.sim_offset, T, k0, k1, hist, (uint8_t*)tail, tr, in);
+                                   (long)c.sim_offset, T, k0, k1, hist, (uint8_t*)tail, tr, in, sc);
             }
-        });
+        };
+        // the drawn start and the schedule are sets of instances of their own: the others do not carry them
+        if (c.sched) sir_dispatch_sched(traj, c.init != nullptr, launch);
+        else sir_dispatch(form, traj, c.init != nullptr, launch);
         if (sampled) gn_prof_end(3, st);
         GN_LAUNCH_CHECK();
     }
@@ -905,6 +953,21 @@ extern "C" int gnode_sir_mc_philox_init(gnode_graph_t g, const double* init_host
     c.drawn = true; c.init = init_host; c.ws_form = SIR_INIT; c.edge_scan = edge_scan != 0; c.events = events; c.curves = curves;
     c.rates.form = w_host ? SIR_EDGES : (beta_host || gamma_host) ? SIR_NODES : SIR_SCALAR; c.rates.beta = beta; c.rates.gamma = gamma;
     c.rates.beta_nodes = beta_host; c.rates.gamma_nodes = gamma_host; c.rates.w_edges = w_host;
+    return sir_mc_philox_impl(c);
+}
+
+// Rates that change over time: P phases of the per-edge form, chosen per step by the phase table (SCHED instances).  The start
+// is a seed list (rows as gnode_sir_mc_philox_traj_edges) or drawn (rows as gnode_sir_mc_philox_init), exactly one of them.
+extern "C" int gnode_sir_mc_philox_schedule(gnode_graph_t g, const int32_t* seeds_host, int32_t n_seeds, const double* init_host,
+                                            const int32_t* phase_host, int32_t P, const double* w_host, const double* gamma_host, int64_t sims,
+                                            int64_t sim_offset, int32_t T, uint64_t rng_seed, int16_t* events, uint32_t* curves, uint32_t* counts,
+                                            void* workspace, size_t workspace_bytes, void* stream, int32_t edge_scan) {
+    const bool listed = seeds_host != nullptr || n_seeds != 0;
+    GN_CHECK_ARG(listed != (init_host != nullptr), "gnode_sir_mc_philox_schedule: the start is a seed list or init_host, exactly one of them");
+    SIR_CALL(c, "gnode_sir_mc_philox_schedule");
+    c.seeds = seeds_host; c.n_seeds = n_seeds; c.drawn = init_host != nullptr; c.init = init_host; c.edge_scan = edge_scan != 0;
+    c.events = events; c.curves = curves;
+    c.sched = true; c.phase = phase_host; c.P = P; c.w_sched = w_host; c.gamma_sched = gamma_host;
     return sir_mc_philox_impl(c);
 }
 

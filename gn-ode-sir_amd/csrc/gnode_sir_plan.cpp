@@ -120,3 +120,41 @@ SirThresholds sir_stage(const char* who, int n, int64_t nnz, const SirRates& r, 
     }
     return t;
 }
+
+SirScheduleLayout sir_schedule_layout(int n, int64_t nnz, int n_bigrow, int T, int P) {
+    SirScheduleLayout L;
+    static_cast<SirLayout&>(L) = sir_layout(n, nnz, n_bigrow, T);
+    const size_t tables = (size_t)std::max(P, 1) * ((size_t)std::max<int64_t>(nnz, 0) + (size_t)n);
+    L.start = L.thr + al(tables * sizeof(unsigned long long));
+    L.phase = L.start + al((size_t)2 * n * sizeof(unsigned long long));
+    L.total = L.phase + al((size_t)std::max(T, 1) * sizeof(int32_t));
+    return L;
+}
+
+SirThresholds sir_stage_schedule(const char* who, int n, int64_t nnz, int T, int P, const int32_t* phase, const double* w, const double* gamma,
+                                 const double* init) {
+    char buf[256];
+    const auto prob = [](double p) { return p >= 0.0 && p <= 1.0; };   // (a NaN fails both comparisons)
+    if (P < 1) return refuse("%s: a schedule has at least one phase (P = %d)", who, P);
+    for (int t = 1; t < T; ++t)
+        if (phase[t] < 0 || phase[t] >= P) return refuse("%s: phase[%d] = %d is not in [0, %d)", who, t, phase[t], P);
+    SirRates none;                                                     // the start alone, through the one place that checks it
+    SirThresholds t = sir_stage(who, n, nnz, none, nullptr, init);
+    if (!t.error.empty()) return t;
+    const size_t ne = (size_t)std::max<int64_t>(nnz, 0);
+    t.tb = t.tg = 0;
+    t.rates.resize((size_t)P * (ne + n));
+    for (int p = 0; p < P; ++p) {
+        for (size_t q = 0; q < ne; ++q) {
+            const double x = w[(size_t)p * ne + q];
+            if (!prob(x)) return refuse("%s: phase %d: the weight at CSR position %zu, %g, is not in [0,1]", who, p, q, x);
+            t.rates[(size_t)p * ne + q] = coin_threshold(x);
+        }
+        for (int v = 0; v < n; ++v) {
+            const double x = gamma[(size_t)p * n + v];
+            if (!prob(x)) return refuse("%s: phase %d: gamma[%d] = %g is not in [0,1]", who, p, v, x);
+            t.rates[(size_t)P * ne + (size_t)p * n + v] = coin_threshold(x);
+        }
+    }
+    return t;
+}

@@ -49,3 +49,18 @@ struct SirThresholds {
 // CSR; the per-node rates are then staged as the per-edge form's, thr[p] = thr(beta[col[p]]) -- same coins, same counts.
 // init: null, or fp64 [n][3], (pS, pI, pR) per node.
 SirThresholds sir_stage(const char* who, int n, int64_t nnz, const SirRates& r, const int32_t* restate_col, const double* init);
+
+// Rates that change over time (gnode_sir_mc_philox_schedule): P >= 1 phases of the per-edge form, phase[t] in [0, P) naming the
+// tables that govern step t = 1 .. T-1.  The layout is sir_layout's with the threshold region grown to P tables -- uint64
+// [P][nnz] infection thresholds, then uint64 [P][n] recovery thresholds, so that a step's tables are thr + phase * nnz and
+// thr_gamma + phase * n -- the start thresholds behind it, and the int32 [T] phase table last.
+struct SirScheduleLayout : SirLayout {   // hist .. tail are sir_layout's; thr is too; start moves behind the P tables
+    size_t phase;      // int32 [T]
+    size_t total;      // the workspace of the scheduled call
+};
+SirScheduleLayout sir_schedule_layout(int n, int64_t nnz, int n_bigrow, int T, int P);
+// Every check of the schedule is here: P >= 1, phase[1 .. T-1] in [0, P) (entry 0 is never read), every weight of w [P][nnz]
+// and every rate of gamma [P][n] a probability (a NaN fails), the start as sir_stage checks it.  A refusal names `who`, the
+// phase and the position.  rates = [P * nnz infection thresholds | P * n recovery thresholds].
+SirThresholds sir_stage_schedule(const char* who, int n, int64_t nnz, int T, int P, const int32_t* phase, const double* w, const double* gamma,
+                                 const double* init);

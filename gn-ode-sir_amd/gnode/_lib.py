@@ -80,6 +80,8 @@ ABI = {
     "gnode_sir_mc_philox_traj_edges": (_int, [_vp, _vp, _i32, _vp, _f64, _vp, _i64, _i64, _i32, _u64, _vp, _vp, _vp, _vp, _sz, _vp, _i32]),
     "gnode_sir_init_workspace_bytes": (_sz, [_vp, _i32]),
     "gnode_sir_mc_philox_init": (_int, [_vp, _vp, _f64, _vp, _vp, _f64, _vp, _i64, _i64, _i32, _u64, _vp, _vp, _vp, _vp, _sz, _vp, _i32]),
+    "gnode_sir_schedule_workspace_bytes": (_sz, [_vp, _i32, _i32]),
+    "gnode_sir_mc_philox_schedule": (_int, [_vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _i64, _i64, _i32, _u64, _vp, _vp, _vp, _vp, _sz, _vp, _i32]),
     "gnode_sir_mc_coins": (_int, [_vp, _vp, _i64, _i32, _vp, _i32, _f64, _f64, _i64, _i32, _vp, _i64, _vp, _pi64, _vp, _sz, _vp]),
     "gnode_dmp_workspace_bytes": (_sz, [_vp]),
     "gnode_dmp_f32": (_int, [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _sz, _vp]),
@@ -88,6 +90,8 @@ ABI = {
     "gnode_dmp_batch_workspace_bytes": (_sz, [_vp, _i32]),
     "gnode_dmp_batch_lds_bytes": (_sz, [_vp]),
     "gnode_dmp_batch_f32": (_int, [_vp, _vp, _i64, _vp, _i64, _vp, _i32, _i32, _vp, _vp, _sz, _vp]),
+    "gnode_dmp_batch_schedule_workspace_bytes": (_sz, [_vp, _i32, _i32]),
+    "gnode_dmp_batch_schedule_f32": (_int, [_vp, _vp, _i64, _vp, _i64, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _sz, _vp]),
     "gnode_dmp_batch_backward_lds_bytes": (_sz, [_vp]),
     "gnode_dmp_batch_backward_workspace_bytes": (_sz, [_vp, _i32, _i32]),
     "gnode_dmp_batch_backward_f32": (_int, [_vp, _vp, _i64, _vp, _i64, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),

@@ -6,6 +6,8 @@ same constructor and `run(seed_list, maxTime)`, the message passing runs in libg
                                                 seed_list: seed ids, or an `InitialState` (an extension)
     dmp_batch(weight_adj, starts, gamma, maxTime, scale=None) -> float32 tensor [B, maxTime, n, 3] (an extension): B
                                                 samples on one graph in one library call, each its solo run's bits
+                                                weight_adj, scale and gamma may each be a `gnode.ode_nn.RateSchedule`: rates
+                                                that change over time (gnode_dmp_batch_schedule_f32)
     dmp_marginals(DmpGraph, weights, gamma, init, maxTime) -> the same tensor as a torch.autograd.Function of device tensors (an
                                                 extension): gradients with respect to weights, gamma and the start
     source_scores(graph, obs, gamma, maxTime, candidates=None, floor=1e-30, budget_bytes=1 << 30) -> float64 tensor
@@ -43,8 +45,14 @@ from . import _lib
 from .graph import DeviceGraph
 
 
+def _refuse_schedule(who, **args):
+    from .ode_nn import refuse_schedule
+    refuse_schedule(who, **args)
+
+
 class DMP_SIR:
     def __init__(self, weight_adj, nodes_gamma, device="cuda"):
+        _refuse_schedule("DMP_SIR", weight_adj=weight_adj, nodes_gamma=nodes_gamma)
         A = sp.csr_matrix(weight_adj)
         A.sort_indices()
         self.N = A.shape[0]
@@ -88,6 +96,7 @@ class DmpGraph:
     on first use and kept.  `dmp_batch` takes it wherever it takes a matrix."""
 
     def __init__(self, weight_adj):
+        _refuse_schedule("DmpGraph", weight_adj=weight_adj)
         A = sp.csr_matrix(weight_adj)
         A.sort_indices()
         self.N, self.E = int(A.shape[0]), int(A.nnz)
@@ -153,6 +162,7 @@ def dmp_marginals(graph, weights, gamma, init, maxTime):
     node.  Gradients are computed for the inputs that require one; a shared table gets the sum over the samples.  Where the
     forward is not finite (a weight of 1 next to a seed) the gradient is unspecified.  What is wrong raises ValueError
     before the library is loaded; a tensor that is not on a GPU raises GnodeError."""
+    _refuse_schedule("dmp_marginals", graph=graph, weights=weights, gamma=gamma)
     if not isinstance(graph, DmpGraph):
         raise ValueError(f"dmp_marginals: graph must be a DmpGraph, got {type(graph).__name__}")
     T, n, nnz = int(maxTime), graph.N, graph.E
@@ -176,6 +186,7 @@ def dmp_marginals(graph, weights, gamma, init, maxTime):
 
 def _batch_numbers(name, value, shapes, who="dmp_batch"):
     """`value` as a float64 host array of one of `shapes`, every entry finite and >= 0; ValueError otherwise."""
+    _refuse_schedule(who, **{name: value})
     if isinstance(value, torch.Tensor):
         value = value.detach().cpu().numpy()
     try:
@@ -198,8 +209,18 @@ def dmp_batch(weight_adj, starts, gamma, maxTime, scale=None, device="cuda"):
     starts: B seed lists and / or `InitialState`s.  scale: None -- the B samples share the matrix's weights -- or B numbers:
     sample b's weights are float32(float64(data) * scale[b]).  gamma: a number, per-node values [n], [B, n], or B numbers, one
     per sample (a 1-D value of length n is per node, also where B == n).  gamma and scale are finite and >= 0.  What is wrong
-    raises ValueError before the library is loaded or a graph handle is made."""
-    from .ode_nn import InitialState
+    raises ValueError before the library is loaded or a graph handle is made.
+
+    Rates that change over time: weight_adj, scale and / or gamma may be a `gnode.ode_nn.RateSchedule` (from `rate_schedule`);
+    step t of the recurrence then reads the tables that govern step t, and theta_{t+1} the weight of step t + 1
+    (`gnode_dmp_batch_schedule_f32`).  scale's values are each None, a number or B numbers; gamma's are each what gamma
+    accepts; weight_adj's are matrices that share one sparsity pattern after `sp.csr_matrix(...).sort_indices()` (an entry
+    absent in some phases is stored as an explicit zero there), else ValueError.  The schedules need not change at the same
+    steps.  Sample b's weights in a phase are float32(float64(data_p) * scale_p[b]); a schedule of one value returns the
+    constant call's bits."""
+    from .ode_nn import InitialState, RateSchedule
+    if any(isinstance(v, RateSchedule) for v in (weight_adj, scale, gamma)):
+        return _dmp_batch_schedule(weight_adj, starts, gamma, maxTime, scale, device)
     G = weight_adj if isinstance(weight_adj, DmpGraph) else DmpGraph(weight_adj)
     starts = list(starts)
     n, nnz, B, T = G.N, G.E, len(starts), int(maxTime)
@@ -207,18 +228,8 @@ def dmp_batch(weight_adj, starts, gamma, maxTime, scale=None, device="cuda"):
         raise ValueError("dmp_batch: need at least one start")
     if T < 2:
         raise ValueError(f"dmp_batch: maxTime must be >= 2 (got {maxTime})")
-    init = np.empty((B, n, 3), dtype=np.float32)
-    for b, start in enumerate(starts):
-        if isinstance(start, InitialState):
-            if start.n != n:
-                raise ValueError(f"InitialState of {start.n} nodes given for a graph of {n}")
-        else:
-            start = InitialState.from_sets(n, list(start))          # (a seed outside the graph: ValueError)
-        init[b] = start.p.astype(np.float32)
-    g = _batch_numbers("gamma", gamma, [(), (n,), (B, n), (B,)])
-    if g.shape == (B,) and g.shape != (n,):
-        g = np.repeat(g[:, None], n, axis=1)
-    gam = np.ascontiguousarray(np.broadcast_to(g, (n,)) if g.ndim < 2 else g, dtype=np.float32)
+    init = _batch_starts(starts, n)
+    gam = _batch_gamma(gamma, n, B)
     if scale is None:
         w = G.data.astype(np.float32)
     else:
@@ -231,6 +242,90 @@ def dmp_batch(weight_adj, starts, gamma, maxTime, scale=None, device="cuda"):
     ws = torch.empty(lib.gnode_dmp_batch_workspace_bytes(handle, B), dtype=torch.uint8, device=y0.device)
     _lib.check(lib.gnode_dmp_batch_f32(handle, _lib.ptr(wd), nnz if w.ndim == 2 else 0, _lib.ptr(gd), n if gam.ndim == 2 else 0,
                                        _lib.ptr(y0), B, T, _lib.ptr(out), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()))
+    return out
+
+
+def _batch_starts(starts, n):
+    """float32 [B, n, 3] of B seed lists and / or `InitialState`s; ValueError for a wrong n or a seed outside the graph."""
+    from .ode_nn import InitialState
+    init = np.empty((len(starts), n, 3), dtype=np.float32)
+    for b, start in enumerate(starts):
+        if isinstance(start, InitialState):
+            if start.n != n:
+                raise ValueError(f"InitialState of {start.n} nodes given for a graph of {n}")
+        else:
+            start = InitialState.from_sets(n, list(start))          # (a seed outside the graph: ValueError)
+        init[b] = start.p.astype(np.float32)
+    return init
+
+
+def _batch_gamma(gamma, n, B, name="gamma"):
+    """float32 [n] or [B, n] of what `dmp_batch` accepts as gamma."""
+    g = _batch_numbers(name, gamma, [(), (n,), (B, n), (B,)])
+    if g.shape == (B,) and g.shape != (n,):
+        g = np.repeat(g[:, None], n, axis=1)
+    return np.ascontiguousarray(np.broadcast_to(g, (n,)) if g.ndim < 2 else g, dtype=np.float32)
+
+
+def _dmp_batch_schedule(weight_adj, starts, gamma, maxTime, scale, device):
+    """`dmp_batch` where weight_adj, scale and / or gamma is a RateSchedule: the joint phases of the schedules -- the distinct
+    combinations in order of first use -- their tables [P][...] (or [B][P][...] where a phase is per sample), and one
+    gnode_dmp_batch_schedule_f32 call.  Everything is checked before the library is loaded or a graph handle is made."""
+    from .ode_nn import RateSchedule, joint_phases
+    who = "dmp_batch"
+    starts = list(starts)
+    B, T = len(starts), int(maxTime)
+    if B < 1:
+        raise ValueError("dmp_batch: need at least one start")
+    if T < 2:
+        raise ValueError(f"dmp_batch: maxTime must be >= 2 (got {maxTime})")
+    if isinstance(weight_adj, RateSchedule):
+        mats = []
+        for p, M in enumerate(weight_adj.values):
+            if isinstance(M, DmpGraph):
+                raise ValueError(f"{who}: weight_adj phase {p}: a schedule takes matrices, not a DmpGraph")
+            A = sp.csr_matrix(M)
+            A.sort_indices()
+            mats.append(A)
+        for p, A in enumerate(mats[1:], 1):
+            if A.shape != mats[0].shape or not np.array_equal(A.indptr, mats[0].indptr) or not np.array_equal(A.indices, mats[0].indices):
+                raise ValueError(f"{who}: weight_adj phase {p} does not share phase 0's sparsity pattern (store an absent entry as an "
+                                 "explicit zero)")
+        G = DmpGraph(mats[0])
+        datas = [np.ascontiguousarray(A.data, dtype=np.float64) for A in mats]
+    else:
+        G = weight_adj if isinstance(weight_adj, DmpGraph) else DmpGraph(weight_adj)
+        datas = [G.data]
+    n, nnz = G.N, G.E
+    init = _batch_starts(starts, n)
+    s_vals = scale.values if isinstance(scale, RateSchedule) else [scale]
+    scales = [None if v is None else _batch_numbers(f"scale phase {p}", v, [(), (B,)]) for p, v in enumerate(s_vals)]
+    g_vals = gamma.values if isinstance(gamma, RateSchedule) else [gamma]
+    gams = [_batch_gamma(v, n, B, f"gamma phase {p}") for p, v in enumerate(g_vals)]
+    rows = [s.phase_of_step(T) if isinstance(s, RateSchedule) else np.zeros(T, dtype=np.int32) for s in (weight_adj, scale, gamma)]
+    phase, triples = joint_phases(rows)
+    P = len(triples)
+    per_sample_w = any(scales[ps] is not None and scales[ps].ndim == 1 for _, ps, _ in triples)
+    per_sample_g = any(gams[pg].ndim == 2 for _, _, pg in triples)
+    w = np.empty((B, P, nnz) if per_sample_w else (P, nnz), dtype=np.float32)
+    gam = np.empty((B, P, n) if per_sample_g else (P, n), dtype=np.float32)
+    for j, (pw, ps, pg) in enumerate(triples):
+        sc = scales[ps]
+        table = datas[pw] if sc is None else datas[pw][None, :] * sc[:, None] if sc.ndim == 1 else datas[pw] * sc
+        w[..., j, :] = table.astype(np.float32)
+        gam[..., j, :] = gams[pg]
+        for name, a in (("a weight times its scale", w[..., j, :]), ("gamma", gam[..., j, :])):
+            if a.size and a.max() > 1.0:                            # (NaN, infinite and negative values: _batch_numbers)
+                raise ValueError(f"{who}: phase {j} (weight_adj {pw}, scale {ps}, gamma {pg}): {name} exceeds 1; a schedule takes "
+                                 "probabilities")
+    lib, handle = _lib.load(), G.graph.handle
+    up = lambda a: None if a.size == 0 else torch.from_numpy(np.ascontiguousarray(a)).to(device)      # noqa: E731  (no edge, no table)
+    wd, gd, y0 = up(w), up(gam), up(init)
+    out = torch.empty((B, T, n, 3), dtype=torch.float32, device=y0.device)
+    ws = torch.empty(lib.gnode_dmp_batch_schedule_workspace_bytes(handle, B, T), dtype=torch.uint8, device=y0.device)
+    _lib.check(lib.gnode_dmp_batch_schedule_f32(handle, _lib.ptr(wd), P * nnz if per_sample_w else 0, _lib.ptr(gd), P * n if per_sample_g else 0,
+                                                _lib.host_ptr(phase), P, _lib.ptr(y0), B, T, _lib.ptr(out), _lib.ptr(ws), ws.numel(),
+                                                _lib.stream_ptr()))
     return out
 
 

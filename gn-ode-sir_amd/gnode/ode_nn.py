@@ -1,6 +1,8 @@
 """Drop-in for the helpers of reference ode_nn.py that sit on the hot path:
 
     sir_torch(G, seed_set, beta, gamma, sims=10000, T=20)        reference :30-88
+    rate_schedule(values, starts=None, steps=None)               extension: a rate that changes over time, for the
+                                                                 Monte-Carlo calls here and gnode.dmp.dmp_batch
     get_sir_t_nodes_torch(x_rk, maxTime, deltaT, count=True)     reference :249-261
     create_graph(n_nodes, graph_label='none')                    reference :394-414
     sir(x, y, A, beta, gamma), runge_kutta_order4(sir, A, ...)   reference :214-233 (mean-field comparison column)
@@ -201,10 +203,150 @@ def initial_state(p) -> InitialState:
     return InitialState(np.ascontiguousarray(a))
 
 
-def _resolved_rates(beta, gamma, graph):
+class RateSchedule:
+    """A rate that changes over time, piecewise constant: `values`, P >= 1 of whatever the argument it replaces accepts as a
+    constant, and which of them governs each step.  A call over T grid points takes steps t = 1 .. T-1, step t leading from
+    state t-1 to state t.  Made by `rate_schedule`; pass it as `beta` / `gamma` of `sir_counts`, `sir_trajectories` and
+    `sir_torch`, or as `weight_adj` / `scale` / `gamma` of `gnode.dmp.dmp_batch`."""
+
+    def __init__(self, values, starts, steps):
+        self.values, self.P, self.starts, self.steps = values, len(values), starts, steps
+
+    def phase_of_step(self, T) -> np.ndarray:
+        """int32 [T]: entry t is the index of the value that governs step t; entry 0 is 0 and is never read.  ValueError when
+        the schedule was given as `steps` and holds fewer than T entries."""
+        T = int(T)
+        if T < 1:
+            raise ValueError(f"RateSchedule.phase_of_step: T must be >= 1 (got {T})")
+        out = np.zeros(T, dtype=np.int32)
+        if self.steps is not None:
+            if T > self.steps.shape[0]:
+                raise ValueError(f"RateSchedule: the schedule names {self.steps.shape[0]} steps, the call has T = {T}")
+            out[1:] = self.steps[1:T]
+        else:
+            out[1:] = np.searchsorted(self.starts, np.arange(1, T), side="right") - 1
+        return out
+
+
+def _whole_numbers(who, name, value):
+    """`value` as a 1-D int64 array of whole numbers; ValueError otherwise."""
+    try:
+        a = np.asarray(value)
+        if a.ndim != 1 or (a.size and a.dtype.kind not in "iu" and not (a.dtype.kind == "f" and (np.isfinite(a) & (a == np.floor(a))).all())):
+            raise ValueError("not a sequence of whole numbers")
+        return a.astype(np.int64)
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"{who}: {name} is not a sequence of whole numbers ({e})") from None
+
+
+def rate_schedule(values, starts=None, steps=None) -> RateSchedule:
+    """A piecewise-constant schedule of P >= 1 values for a rate argument (see `RateSchedule`).
+
+    values: each one whatever the argument it replaces accepts as a constant (checked by the call that takes the schedule).
+    Give exactly one of
+      starts: P ascending whole numbers with starts[0] == 1; value p holds for steps starts[p] .. starts[p+1] - 1, the last to
+              the end.  Starts at or beyond a call's T are ignored.
+      steps:  a sequence with steps[t] in [0, P) for t >= 1 (entry 0 is ignored): periodic patterns, phases revisited.  A
+              call's T must not exceed its length.
+    What is wrong raises ValueError."""
+    who = "rate_schedule"
+    if isinstance(values, (RateSchedule, EdgeRates, str)) or not hasattr(values, "__len__"):
+        raise ValueError(f"{who}: values must be a sequence of P >= 1 values")
+    values = list(values)
+    P = len(values)
+    if P < 1:
+        raise ValueError(f"{who}: values must hold at least one value")
+    if any(isinstance(v, RateSchedule) for v in values):
+        raise ValueError(f"{who}: a value cannot be a schedule itself")
+    if (starts is None) == (steps is None):
+        raise ValueError(f"{who}: give exactly one of starts and steps")
+    if starts is not None:
+        st = _whole_numbers(who, "starts", starts)
+        if st.shape[0] != P:
+            raise ValueError(f"{who}: {P} values need {P} starts, got {st.shape[0]}")
+        if st[0] != 1 or (np.diff(st) <= 0).any():
+            raise ValueError(f"{who}: starts must ascend from starts[0] == 1, got {st.tolist()}")
+        return RateSchedule(values, st, None)
+    sp_ = _whole_numbers(who, "steps", steps)
+    if sp_.shape[0] < 1:
+        raise ValueError(f"{who}: steps must hold at least one entry")
+    bad = np.flatnonzero((sp_[1:] < 0) | (sp_[1:] >= P))
+    if bad.size:
+        raise ValueError(f"{who}: steps[{int(bad[0]) + 1}] = {int(sp_[bad[0] + 1])} is not in [0, {P})")
+    return RateSchedule(values, None, sp_)
+
+
+def refuse_schedule(who, **args):
+    """ValueError when one of the named arguments is a `RateSchedule`: the calls that take constant rates only."""
+    for name, v in args.items():
+        if isinstance(v, RateSchedule):
+            raise ValueError(f"{who}: {name} is a RateSchedule; this call takes constant rates "
+                             "(schedules: sir_counts, sir_trajectories, sir_torch, dmp_batch)")
+
+
+def joint_phases(phases):
+    """The joint schedule of several per-step phase rows (int [T] each): (phase int32 [T], tuples), tuples[j] = the combination
+    of the rows' phases that joint phase j stands for -- the distinct combinations over steps 1 .. T-1 in order of first use
+    (for T = 1, the one combination of entry 0)."""
+    rows = np.stack([np.asarray(p, dtype=np.int64) for p in phases], axis=1)
+    T = rows.shape[0]
+    index, phase = {}, np.zeros(T, dtype=np.int32)
+    for t in (range(1, T) if T > 1 else range(1)):
+        phase[t] = index.setdefault(tuple(int(x) for x in rows[t]), len(index))
+    return phase, list(index)
+
+
+class _SirSchedule:
+    """The checked host side of a scheduled Monte-Carlo call: phase int32 [T], W float64 [P, nnz], G float64 [P, n]."""
+
+    def __init__(self, phase, W, G):
+        self.phase, self.W, self.G, self.P = phase, W, G, int(W.shape[0])
+
+
+def _scheduled_rates(beta, gamma, graph, T) -> _SirSchedule:
+    """beta and / or gamma is a RateSchedule: every value checked as the constant it stands for and restated as the most
+    general form -- per-edge weights (w[q] = beta[col[q]] for a number or per-node rates) and per-node gamma -- per joint
+    phase.  Raises ValueError before the library is entered."""
+    n, nnz = int(graph.n), int(graph.nnz)
+    if int(T) < 1:
+        raise ValueError(f"a scheduled call needs T >= 1 (got {T})")
+    col = None
+
+    def edge_table(v):
+        nonlocal col
+        if isinstance(v, EdgeRates):
+            if (v.n, v.nnz) != (n, nnz):
+                raise ValueError(f"EdgeRates of a graph with {v.n} nodes / {v.nnz} entries given for one with {n} / {nnz}")
+            return v.w
+        b = _node_rates("beta", v, n)
+        if b is None:
+            b = _node_rates("beta", np.full(n, float(v)), n)        # the scalar, through the same check
+        if col is None:
+            col = _host_csr(graph)[2]
+        return b[col]
+
+    def node_table(v):
+        if isinstance(v, EdgeRates):
+            raise ValueError("gamma: a recovery rate is a number or per-node rates, not EdgeRates")
+        g = _node_rates("gamma", v, n)
+        return _node_rates("gamma", np.full(n, float(v)), n) if g is None else g
+
+    b_vals, g_vals = (s.values if isinstance(s, RateSchedule) else [s] for s in (beta, gamma))
+    b_tabs, g_tabs = [edge_table(v) for v in b_vals], [node_table(v) for v in g_vals]
+    rows = [s.phase_of_step(T) if isinstance(s, RateSchedule) else np.zeros(int(T), dtype=np.int32) for s in (beta, gamma)]
+    phase, pairs = joint_phases(rows)
+    W = np.ascontiguousarray(np.stack([b_tabs[pb] for pb, _ in pairs]).reshape(len(pairs), nnz), dtype=np.float64)
+    G = np.ascontiguousarray(np.stack([g_tabs[pg] for _, pg in pairs]), dtype=np.float64)
+    return _SirSchedule(phase, W, G)
+
+
+def _resolved_rates(beta, gamma, graph, T=None):
     """(b, g) for one launch: an EdgeRates and gamma as given (checked), two float64 [n] host arrays when either rate is per
-    node, else two numbers.  Raises ValueError before anything is allocated."""
+    node, else two numbers; a `_SirSchedule` and None when either is a `RateSchedule` (T is then the call's).  Raises
+    ValueError before anything is allocated."""
     n = graph.n
+    if isinstance(beta, RateSchedule) or isinstance(gamma, RateSchedule):
+        return _scheduled_rates(beta, gamma, graph, T), None
     if isinstance(beta, EdgeRates):
         _edge_rate_args(beta, gamma, graph)
         return beta, gamma
@@ -241,6 +383,16 @@ def _sir_launch(graph: DeviceGraph, start, b, g, sims, T, rng_seed, sim_offset, 
     names a C entry that takes the scalar seed-list entry's arguments (then `extra` behind them) in its place."""
     lib = _lib.load()
     drawn, traj = isinstance(start, InitialState), ev is not None or cv is not None
+    if isinstance(b, _SirSchedule):                                 # one entry for both starts and every output
+        seeds = None if drawn else np.ascontiguousarray(list(start), dtype=np.int32)
+        start_args = (None, 0, _lib.host_ptr(start.p)) if drawn else (_lib.host_ptr(seeds), int(seeds.shape[0]), None)
+        dev = next(t for t in (counts, ev, cv) if t is not None).device
+        ws = torch.empty(lib.gnode_sir_schedule_workspace_bytes(graph.handle, int(T), b.P), dtype=torch.uint8, device=dev)
+        _lib.check(lib.gnode_sir_mc_philox_schedule(graph.handle, *start_args, _lib.host_ptr(b.phase), b.P, _lib.host_ptr(b.W), _lib.host_ptr(b.G),
+                                                    int(sims), int(sim_offset), int(T), C.c_uint64(int(rng_seed) & (2**64 - 1)), _lib.ptr(ev),
+                                                    _lib.ptr(cv), _lib.ptr(counts), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(),
+                                                    int(bool(edge_scan))))
+        return
     if isinstance(b, EdgeRates):
         (w, gam, gam_host), _alive = _edge_rate_args(b, g, graph)
         form, rates = 2, (0.0, None, w, gam, gam_host)
@@ -284,10 +436,16 @@ def sir_counts(graph: DeviceGraph, seed_set, beta, gamma, sims, T, rng_seed, sim
     seed_set may be an `InitialState` (from `initial_state` / `InitialState.from_sets`): every trajectory then draws its
     start from the per-node (pS, pI, pR), through `gnode_sir_mc_philox_init`, with any of the rate forms above.  Row 0 of
     the counts is then ACCUMULATED like the other rows (how many trajectories start in S / I / R); a state that is one-hot
-    I on a seed set and S elsewhere gives the seed-list call's rows t >= 1 exactly.  A wrong n raises ValueError."""
+    I on a seed set and S elsewhere gives the seed-list call's rows t >= 1 exactly.  A wrong n raises ValueError.
+
+    beta and / or gamma may be a `RateSchedule` (from `rate_schedule`): the rate then changes at given steps -- contacts cut
+    to 30 % from day 10, weekends unlike weekdays.  beta's values are numbers, per-node arrays or `EdgeRates`, mixed freely;
+    gamma's are numbers or per-node arrays; the two schedules need not change at the same steps.  Step t draws the coins it
+    always drew and holds them against the thresholds of the values that govern step t (`gnode_sir_mc_philox_schedule`), so
+    a schedule of one value returns the constant call's counts.  Every start, output, shard and edge_scan works as above."""
     if isinstance(seed_set, InitialState):
         _init_for(seed_set, graph.n)
-    b, g = _resolved_rates(beta, gamma, graph)                      # (ValueError before the library is entered)
+    b, g = _resolved_rates(beta, gamma, graph, T)                   # (ValueError before the library is entered)
     if counts is None:
         counts = torch.zeros((3, T, graph.n), dtype=torch.int32, device=device)
     _sir_launch(graph, seed_set, b, g, sims, T, rng_seed, sim_offset, None, None, counts, edge_scan)
@@ -322,7 +480,7 @@ def sir_trajectories(graph_or_G, seed_set, beta, gamma, sims, T, rng_seed=None, 
     n = graph.n
     if isinstance(seed_set, InitialState):
         _init_for(seed_set, n)
-    b, g = _resolved_rates(beta, gamma, graph)                      # (ValueError before anything is allocated)
+    b, g = _resolved_rates(beta, gamma, graph, T)                   # (ValueError before anything is allocated)
     if not events and not curves:
         raise ValueError("sir_trajectories: neither events nor curves requested")
     if events and T > 32767:
@@ -433,6 +591,8 @@ def sir_torch(G, seed_set, beta, gamma, sims=10000, T=20, rng_seed=None, coins=N
     """
     n = G.number_of_nodes()
     if coins is not None:
+        if isinstance(beta, RateSchedule) or isinstance(gamma, RateSchedule):
+            raise ValueError("sir_torch(coins=...): the parity mode takes scalar beta and gamma, not a RateSchedule")
         if isinstance(seed_set, InitialState):
             raise ValueError("sir_torch(coins=...): the parity mode takes a seed list, not an InitialState")
         if isinstance(beta, EdgeRates) or _node_rates("beta", beta, n) is not None or _node_rates("gamma", gamma, n) is not None:
@@ -553,6 +713,7 @@ def runge_kutta_order4(sir, A, n_nodes, indices, beta_factor, gamma_factor, delt
     probabilities: the mean-field takes rates, and the reference's own configurations have beta * degree > 1.  A wrong
     length, a NaN, a negative value or an `EdgeRates` of another graph raises ValueError before the library is loaded.  Two
     numbers take the scalar entries as before.  A's stored values are ignored in every form."""
+    refuse_schedule("runge_kutta_order4", beta_factor=beta_factor, gamma_factor=gamma_factor)
     Ac = sp.csr_matrix(A)
     Ac.sort_indices()
     n = Ac.shape[0]
@@ -601,6 +762,7 @@ def meanfield_batch(graph: DeviceGraph, starts, beta, gamma, deltaT=1, maxTime=7
     The B samples share the launches, the host round trip per step and the step size: the error norm is the maximum over
     every sample, so a sample's numbers differ from its solo `runge_kutta_order4` run at the level of rtol / atol, not bit
     for bit."""
+    refuse_schedule("meanfield_batch", beta=beta, gamma=gamma)
     starts = list(starts)
     n, B = int(graph.n), len(starts)
     out, _ = _meanfield_rates(graph, _mf_checked(n, int(graph.nnz), starts, beta, gamma, batch=True), _mf_times(deltaT, maxTime),
@@ -681,6 +843,7 @@ def meanfield_marginals(graph: DeviceGraph, init, beta, gamma, w=None, deltaT=1,
     [n].  w: [nnz] in the graph's CSR position order (source = row, target = column; the pattern must then be symmetric) or
     None = 1.  The [n] forms are expanded in front of the library call, so their gradient is the sum over the samples, as w's
     is.  What is wrong raises ValueError before the library is loaded; a tensor that is not on a GPU raises GnodeError."""
+    refuse_schedule("meanfield_marginals", beta=beta, gamma=gamma, w=w)
     n, nnz, T = int(graph.n), int(graph.nnz), int(maxTime)
     if T < 1:
         raise ValueError(f"meanfield_marginals: maxTime must be >= 1 (got {maxTime})")

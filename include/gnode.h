@@ -449,6 +449,33 @@ int gnode_sir_mc_philox_init(gnode_graph_t g, const double* init_host,
                              uint32_t* curves,   /* device [sims, T, 3], OVERWRITTEN, or NULL */
                              uint32_t* counts,   /* device [3, T, n], ACCUMULATED (row 0 included), or NULL */
                              void* workspace, size_t workspace_bytes, void* stream, int32_t edge_scan);
+/* Rates that change over time (no version step: a stale library is known by the missing symbol): the same model with a
+ * piecewise-constant SCHEDULE of P >= 1 phases.  A call over T grid points takes steps t = 1 .. T-1, step t leading from state
+ * t-1 to state t; phase_host[t] in [0, P) names the tables that govern step t (entry 0 is never read).  Phase p has per-edge
+ * weights w_host[p][nnz] and per-node recovery probabilities gamma_host[p][n], under gnode_sir_mc_philox_edges' convention
+ * (source = row, target = column).  In step t, on the pre-step state, entry q (row u infected, col[q] = v susceptible) fires
+ * iff coin(q, t, sim, kind 0) < thr(w_host[phase[t]][q]), and the infected u recovers iff coin(u, t, sim, kind 1) <
+ * thr(gamma_host[phase[t]][u]): the coins and thresholds of the other entries, so one phase gives gnode_sir_mc_philox_traj_edges'
+ * / gnode_sir_mc_philox_init's output exactly, as do several phases that hold equal tables.  The one rate form is the most
+ * general; a caller restates scalars and per-node rates as such tables (w[q] = beta[col[q]]).
+ *   start       a seed list (seeds_host, n_seeds; init_host NULL): outputs and the row-0 rule of gnode_sir_mc_philox_traj_edges;
+ *               or drawn (init_host, host fp64 [n][3]; seeds_host NULL, n_seeds 0): those of gnode_sir_mc_philox_init.  Both
+ *               or neither is GNODE_ERR_ARG.
+ *   events / curves / counts   each may be NULL, not all three.  T = 1 is legal (no step, phase_host is not read).
+ * GNODE_ERR_ARG: P < 1, a phase outside [0, P) at a step 1 .. T-1, a NaN or a rate outside [0, 1] (the message names the phase
+ * and the CSR position or node), and what the other entries refuse; GNODE_ERR_WORKSPACE: a workspace shorter than
+ * gnode_sir_schedule_workspace_bytes(g, T, P) -- gnode_sir_workspace_bytes' layout, then uint64 [P][nnz] and [P][n] thresholds,
+ * the two uint64 [n] start thresholds and the int32 [T] phase table.  A refused call writes nothing.  SYNCHRONISES `stream`. */
+size_t gnode_sir_schedule_workspace_bytes(gnode_graph_t g, int32_t T, int32_t P);
+int gnode_sir_mc_philox_schedule(gnode_graph_t g,
+                                 const int32_t* seeds_host, int32_t n_seeds,   /* the start: a seed list ... */
+                                 const double* init_host,                      /* ... or host fp64 [n][3], then seeds NULL / 0 */
+                                 const int32_t* phase_host, int32_t P,         /* host [T], entry 0 ignored, the others in [0, P) */
+                                 const double* w_host,                         /* host fp64 [P][nnz], CSR position order */
+                                 const double* gamma_host,                     /* host fp64 [P][n] */
+                                 int64_t sims, int64_t sim_offset, int32_t T, uint64_t rng_seed,
+                                 int16_t* events, uint32_t* curves, uint32_t* counts,
+                                 void* workspace, size_t workspace_bytes, void* stream, int32_t edge_scan);
 int gnode_sir_mc_coins(const int32_t* table_src, const int32_t* table_dst, int64_t n_table, int32_t n,
                        const int32_t* seeds_host, int32_t n_seeds, double beta, double gamma, int64_t sims,
                        int32_t T, const double* coins, int64_t n_coins, uint32_t* counts,
@@ -505,8 +532,36 @@ size_t gnode_dmp_batch_lds_bytes(gnode_graph_t g);
 int gnode_dmp_batch_f32(gnode_graph_t g, const float* weights, int64_t w_stride, const float* gamma,
                         int64_t gamma_stride, const float* init /* device fp32 [B][n][3] */, int32_t B,
                         int32_t maxTime, float* out, void* workspace, size_t workspace_bytes, void* stream);
-/* The reverse sweep of that recurrence: the gradient of sum(grad_out * out) with respect to the weights, the recovery
- * probabilities and the start, for B samples on one graph, fp32.  weights, gamma, init, the strides, B and maxTime are the
+/* Rates that change over time (no version step: a stale library is known by the missing symbol): gnode_dmp_batch_f32 with a
+ * piecewise-constant schedule of P >= 1 phases.  Step t = 1 .. maxTime-1 leads from state t-1 to state t under the tables of
+ * phase_host[t] in [0, P) (entry 0 is never read):
+ *   theta_1     = (1 - w^{phase[1]} phi_0) + 1e-10
+ *   node pass t   Pr_t = Pr_{t-1} + gamma^{phase[t]} Pi_{t-1}; Ps_t and Pi_t as in gnode_dmp_batch_f32
+ *   edge pass t   (only when t + 1 < maxTime)
+ *                 phi_t = (1 - w^{phase[t]})(1 - gamma^{phase[t]}_src) phi_{t-1} - (Ps_e(t) - Ps_e(t-1))
+ *                 theta_{t+1} = theta_t - w^{phase[t+1]} phi_t
+ * phi_t -- infected, and neither transmitted nor recovered during step t -- reads step t's tables; theta_{t+1} - theta_t is the
+ * transmission DURING step t + 1 and reads that step's weight.  Operand order and rounding are gnode_dmp_batch_f32's, so one
+ * phase, or several that hold equal tables, return its bits; so does sample b of a batch with respect to its B = 1 call.
+ *   weights   device fp32 [P][nnz] (w_stride 0) or [B][P][nnz] (w_stride P * nnz); may be NULL when nnz = 0
+ *   gamma     device fp32 [P][n] (gamma_stride 0) or [B][P][n] (gamma_stride P * n)
+ *   init, out as in gnode_dmp_batch_f32.  The two tables are read back once and validated on the host: a NaN or an entry
+ *             outside [0, 1] is GNODE_ERR_ARG, the message names the sample, the phase and the position
+ * The two forms are gnode_dmp_batch_f32's, chosen by gnode_dmp_batch_lds_bytes (the tables are never held in LDS): the
+ * one-workgroup form reads a device copy of the phase table at every step, the general form's launches get their step's table
+ * offsets from the host loop.  The workspace holds that copy, then the general form's arrays.
+ * GNODE_ERR_ARG: a null pointer, B < 1, maxTime < 2, P < 1, a phase outside [0, P) at a step 1 .. maxTime-1, a stride that is
+ * neither 0 nor the table's length, a NaN or out-of-range rate, an asymmetric pattern; GNODE_ERR_WORKSPACE: a short workspace; nothing is written to `out`
+ * in either case.  Synchronises `stream`. */
+size_t gnode_dmp_batch_schedule_workspace_bytes(gnode_graph_t g, int32_t B, int32_t maxTime);
+int gnode_dmp_batch_schedule_f32(gnode_graph_t g,
+                                 const float* weights, int64_t w_stride,       /* device [P][nnz] (stride 0) or [B][P][nnz] (P * nnz) */
+                                 const float* gamma, int64_t gamma_stride,     /* device [P][n] (stride 0) or [B][P][n] (P * n) */
+                                 const int32_t* phase_host, int32_t P,         /* host [maxTime], entry 0 ignored */
+                                 const float* init, int32_t B, int32_t maxTime, float* out,
+                                 void* workspace, size_t workspace_bytes, void* stream);
+/* The reverse sweep of gnode_dmp_batch_f32's recurrence (constant rates): the gradient of sum(grad_out * out) with respect
+ * to the weights, the recovery probabilities and the start, for B samples on one graph, fp32.  weights, gamma, init, the strides, B and maxTime are the
  * forward call's; `out` is what it returned (the sweep reads Pi_{t-1} from it) and grad_out has its shape.
  *   grad_w      device fp32 [B][nnz], in CSR position order     grad_gamma  device fp32 [B][n]     grad_init  device fp32 [B][n][3]
  * One row per sample even where the forward's table is shared (stride 0): the caller sums the rows of a shared table.  A
