@@ -45,6 +45,7 @@ int gn_bwd_tiny_set_attributes();
 int gn_sir_set_attributes();
 int gn_dmp_set_attributes();
 int gn_dmp_schedule_set_attributes();
+int gn_dmp_schedule_bwd_set_attributes();
 int gn_dmp_source_set_attributes();
 int gn_dmp_source_batch_set_attributes();
 int gn_dmp_source_events_set_attributes();

@@ -166,60 +166,8 @@ __global__ __launch_bounds__(256) void k_dmp_batch_edge(const int* __restrict__ 
 // theta[rev e]).  The edge pass leaves two numbers per edge for the node pass of its source's row, which sums them in
 // ascending position from 0; the node pass writes theta_bar of the reverses of its row's edges into the OTHER theta_bar
 // buffer: rev is a permutation, so every slot is written once per step and nothing here is atomic.  Like the recurrence these
-// round as written, and the two forms below call them on the sample's own pointers, in global memory or in LDS.
-
-// the reverse of dmp_edge_update at step t for one edge: theta_bar is that of theta_{t+1}; phi_bar, q_bar come in as step
-// t + 1 left them and go out for step t - 1.  q_tot (the adjoint of Ps_e of this step) and gamma_part (this edge's share of
-// gamma_bar[src]) are for the node pass.
-__device__ __forceinline__ void dmp_rev_edge(float w_e, float gamma_u, float phi_t, float phi_prev, float theta_bar, float& phi_bar,
-                                             float& q_bar, float& w_bar, float& q_tot, float& gamma_part) {
-    const float pb = phi_bar - w_e * theta_bar;                 // the adjoint of phi_t: theta_{t+1} = theta_t - w phi_t
-    w_bar = w_bar - phi_t * theta_bar;
-    w_bar = w_bar - ((1.0f - gamma_u) * phi_prev) * pb;         // phi_t = (1 - w)(1 - gamma) phi_{t-1} - (Ps_e - Ps_e^{prev})
-    gamma_part = -(((1.0f - w_e) * phi_prev) * pb);
-    q_tot = q_bar - pb;
-    q_bar = pb;
-    phi_bar = ((1.0f - w_e) * (1.0f - gamma_u)) * pb;
-}
-
-// what row u's edges [lo, hi) hand to their source: S = sum c_bar c, the shares of ps0_bar[u] and of gamma_bar[u]
-struct DmpRowSums { float S, ps0, gamma; };
-__device__ __forceinline__ DmpRowSums dmp_rev_row_sums(const int* rev, const float* theta, const float* q_tot, const float* gamma_part,
-                                                       int lo, int hi, float P_u, float ps0_u) {
-    DmpRowSums s = {0.0f, 0.0f, 0.0f};
-    for (int e = lo; e < hi; ++e) {
-        const float c = P_u / theta[rev[e]];                    // the cavity product, as dmp_edge_update divides
-        s.ps0 = s.ps0 + c * q_tot[e];
-        s.S = s.S + (ps0_u * q_tot[e]) * c;
-        s.gamma = s.gamma + gamma_part[e];
-    }
-    return s;
-}
-
-// the reverse of dmp_node_update for node k at step t: (gS, gI, gR) is grad_out's row, pi_prev the forward's Pi_{t-1}[k]
-__device__ __forceinline__ void dmp_rev_node(float gS, float gI, float gR, float P_k, float ps0_k, float pi_prev, float gamma_k,
-                                             float& pi_bar, float& pr_bar, float& gamma_bar, float& ps0_bar, float& P_bar) {
-    const float aI = gI + pi_bar;
-    const float aR = (gR + pr_bar) - aI;                        // pi = 1 - ps - pr
-    const float aS = gS - aI;
-    gamma_bar = gamma_bar + pi_prev * aR;                       // pr = pr_prev + gamma pi_prev
-    pr_bar = aR;
-    pi_bar = gamma_k * aR;
-    ps0_bar = ps0_bar + P_k * aS;                               // ps = ps0 P
-    P_bar = ps0_k * aS;
-}
-
-// theta_bar of step t for the reverses of row u's edges: the carried theta_bar plus the derivative of P_u and of the other
-// edges' cavity products.  q_tot == nullptr: there was no edge pass (t = maxTime - 1, S = 0).
-__device__ __forceinline__ void dmp_rev_theta(const int* rev, const float* theta, const float* q_tot, int lo, int hi, float P_u,
-                                              float ps0_u, float PbarP, float S, const float* tb_cur, float* tb_next) {
-    for (int f = lo; f < hi; ++f) {
-        const int r = rev[f];
-        const float th = theta[r];
-        const float own = q_tot ? (ps0_u * q_tot[f]) * (P_u / th) : 0.0f;
-        tb_next[r] = tb_cur[r] + ((PbarP + S) - own) / th;
-    }
-}
+// round as written, and the two forms below call them on the sample's own pointers, in global memory or in LDS.  The dmp_rev_*
+// functions, DmpRowSums and DmpAdjoint are gnode_dmp.h's: gnode_dmp_schedule_bwd.hip sweeps with them too.
 
 struct DmpGradArgs {
     const float* w; long w_stride;
@@ -245,11 +193,6 @@ __device__ __forceinline__ DmpGradSample dmp_grad_sample(const DmpGradArgs& a, s
             a.gout + b * (size_t)a.maxTime * nn * 3, a.gw ? a.gw + b * ne : nullptr, a.gg ? a.gg + b * nn : nullptr,
             a.gi ? a.gi + b * nn * 3 : nullptr, a.th_tape + tape, a.ph_tape + tape, a.n, a.maxTime, a.nnz};
 }
-struct DmpAdjoint {                     // sample b's own adjoint state, in the workspace or in LDS
-    float *tb, *tb_next, *phb, *qb, *q_tot, *gamma_part, *pib, *prb;      // tb: theta_bar as the step finds it, tb_next: as it leaves it
-};
-__host__ __device__ static inline void dmp_adjoint_swap(DmpAdjoint& A) { float* t = A.tb; A.tb = A.tb_next; A.tb_next = t; }
-
 // The work of one thread on one element, for both forms.  The tape first: the forward's own functions, theta and phi kept.
 __device__ __forceinline__ void dmp_tape_start(const DmpGradSample& s, const int* src, float* ps, long e) {
     const size_t u = src[e];

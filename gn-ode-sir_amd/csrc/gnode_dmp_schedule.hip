@@ -17,7 +17,6 @@
 // launch the offsets of its step's tables.
 #include "gnode_dmp.h"
 #include <algorithm>
-#include <vector>
 
 struct DmpSchedArgs {
     const float* w; long w_stride;      // [P][nnz] per sample, sample b at w + b * w_stride
@@ -176,20 +175,6 @@ extern "C" size_t gnode_dmp_batch_schedule_workspace_bytes(gnode_graph_t g, int3
     return g && B >= 1 && maxTime >= 2 ? dmp_sched_carve(g, (size_t)B, (size_t)maxTime, !dmp_sched_one_workgroup(g), nullptr).bytes : 0;
 }
 
-// The P tables are probabilities, and they live on the device: they come back once, on the caller's stream (which the call
-// synchronises anyway), and the first entry that is a NaN or outside [0, 1] is named by sample, phase and position.  Nothing
-// has been written when this refuses.  `samples`: 1 for a shared table (stride 0), else B.
-static int dmp_sched_check_tables(const char* who, const char* what, const float* dev, size_t samples, size_t P, size_t len, hipStream_t st) {
-    std::vector<float> host(samples * P * len);
-    if (host.empty()) return 0;
-    GN_HIP(hipMemcpyAsync(host.data(), dev, host.size() * sizeof(float), hipMemcpyDeviceToHost, st));
-    GN_HIP(hipStreamSynchronize(st));
-    for (size_t i = 0; i < host.size(); ++i)
-        GN_CHECK_ARG(host[i] >= 0.0f && host[i] <= 1.0f, "%s: sample %zu, phase %zu: %s[%zu] = %g is not in [0,1]", who, i / (P * len),
-                     (i / len) % P, what, i % len, (double)host[i]);          // (a NaN fails both comparisons)
-    return 0;
-}
-
 extern "C" int gnode_dmp_batch_schedule_f32(gnode_graph_t g, const float* weights, int64_t w_stride, const float* gamma, int64_t gamma_stride,
                                             const int32_t* phase_host, int32_t P, const float* init, int32_t B, int32_t maxTime, float* out,
                                             void* workspace, size_t workspace_bytes, void* stream) {
@@ -218,8 +203,8 @@ extern "C" int gnode_dmp_batch_schedule_f32(gnode_graph_t g, const float* weight
     }
     GN_CHECK_ARG(g->symmetric, "%s: the sparsity pattern is not symmetric (DMP here serves undirected graphs)", who);
     hipStream_t st = (hipStream_t)stream;
-    if (int rc = dmp_sched_check_tables(who, "weights", weights, w_stride ? (size_t)B : 1, (size_t)P, (size_t)nnz, st)) return rc;
-    if (int rc = dmp_sched_check_tables(who, "gamma", gamma, gamma_stride ? (size_t)B : 1, (size_t)P, (size_t)n, st)) return rc;
+    if (int rc = dmp_check_rate_tables(who, "weights", weights, w_stride ? (size_t)B : 1, (size_t)P, (size_t)nnz, st)) return rc;
+    if (int rc = dmp_check_rate_tables(who, "gamma", gamma, gamma_stride ? (size_t)B : 1, (size_t)P, (size_t)n, st)) return rc;
     const DmpSchedWorkspace ws = dmp_sched_carve(g, (size_t)B, (size_t)maxTime, !one_wg, workspace);
     // entry 0 is never read; it travels as 0 so that the device copy holds no number out of range
     GN_HIP(hipMemsetAsync(ws.phase, 0, sizeof(int32_t), st));

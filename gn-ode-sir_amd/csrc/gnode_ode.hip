@@ -539,6 +539,7 @@ int gn_device_setup_once(int dev) {
     if (int e = gn_sir_set_attributes()) return e;
     if (int e = gn_dmp_set_attributes()) return e;
     if (int e = gn_dmp_schedule_set_attributes()) return e;
+    if (int e = gn_dmp_schedule_bwd_set_attributes()) return e;
     if (int e = gn_dmp_source_set_attributes()) return e;
     if (int e = gn_dmp_source_batch_set_attributes()) return e;
     if (int e = gn_dmp_source_events_set_attributes()) return e;

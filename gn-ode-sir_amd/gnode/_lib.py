@@ -95,6 +95,9 @@ ABI = {
     "gnode_dmp_batch_backward_lds_bytes": (_sz, [_vp]),
     "gnode_dmp_batch_backward_workspace_bytes": (_sz, [_vp, _i32, _i32]),
     "gnode_dmp_batch_backward_f32": (_int, [_vp, _vp, _i64, _vp, _i64, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "gnode_dmp_batch_schedule_backward_workspace_bytes": (_sz, [_vp, _i32, _i32]),
+    "gnode_dmp_batch_schedule_backward_f32": (_int, [_vp, _vp, _i64, _vp, _i64, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
+                                                     _vp]),
     "gnode_dmp_backward_workspace_bytes": (_sz, [_vp, _i32]),
     "gnode_dmp_backward_f32": (_int, [_vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "gnode_dmp_source_lds_bytes": (_sz, [_vp]),

@@ -10,6 +10,9 @@ same constructor and `run(seed_list, maxTime)`, the message passing runs in libg
                                                 that change over time (gnode_dmp_batch_schedule_f32)
     dmp_marginals(DmpGraph, weights, gamma, init, maxTime) -> the same tensor as a torch.autograd.Function of device tensors (an
                                                 extension): gradients with respect to weights, gamma and the start
+    dmp_marginals_schedule(DmpGraph, weights, gamma, init, maxTime, phase) -> `dmp_batch` under a rate schedule as such a
+                                                function (an extension): weights [P, nnz], gamma [P, n] hold one table per
+                                                phase, phase names each step's, and `.backward()` fills every phase's gradient
     source_scores(graph, obs, gamma, maxTime, candidates=None, floor=1e-30, budget_bytes=1 << 30) -> float64 tensor
                                                 [C, maxTime] on the GPU (an extension): the log-likelihood of one observed
                                                 snapshot for every candidate source and time, fused into the node pass
@@ -182,6 +185,107 @@ def dmp_marginals(graph, weights, gamma, init, maxTime):
         if not t.is_cuda:
             raise _lib.GnodeError("GN-ODE path: tensor is not on a GPU (no CPU fallback exists)")
     return _DmpMarginals.apply(graph, weights, gamma, init, T)
+
+
+class _DmpMarginalsSchedule(torch.autograd.Function):
+    """gnode_dmp_batch_schedule_f32 forward, gnode_dmp_batch_schedule_backward_f32 backward; the arguments are
+    `dmp_marginals_schedule`'s, already checked (phase: int32 host array [maxTime])."""
+
+    @staticmethod
+    def forward(ctx, graph, weights, gamma, init, maxTime, phase):
+        lib, handle = _lib.load(), graph.graph.handle
+        w, g, y0 = weights.detach().contiguous(), gamma.detach().contiguous(), init.detach().contiguous()
+        B, n, nnz, P = y0.shape[0], graph.N, graph.E, g.shape[-2]
+        out = torch.empty((B, maxTime, n, 3), dtype=torch.float32, device=y0.device)
+        ws = torch.empty(lib.gnode_dmp_batch_schedule_workspace_bytes(handle, B, maxTime), dtype=torch.uint8, device=y0.device)
+        ctx.strides = (P * nnz if w.dim() == 3 else 0, P * n if g.dim() == 3 else 0)
+        _lib.check(lib.gnode_dmp_batch_schedule_f32(handle, _lib.ptr(w) if nnz else None, ctx.strides[0], _lib.ptr(g), ctx.strides[1],
+                                                    _lib.host_ptr(phase), P, _lib.ptr(y0), B, maxTime, _lib.ptr(out), _lib.ptr(ws),
+                                                    ws.numel(), _lib.stream_ptr()))
+        ctx.graph, ctx.maxTime, ctx.phase, ctx.P = graph, maxTime, phase, P
+        ctx.save_for_backward(w, g, y0, out)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        w, g, y0, out = ctx.saved_tensors
+        graph, T, P, grad_out = ctx.graph, ctx.maxTime, ctx.P, grad_out.contiguous()
+        B, n, nnz = y0.shape[0], graph.N, graph.E
+        want_w, want_g, want_i = ctx.needs_input_grad[1:4]
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=y0.device)      # noqa: E731
+        gw = new(B, P, nnz) if want_w and nnz else None              # (no edge, no table: an empty tensor has no address)
+        gg, gi = new(B, P, n) if want_g else None, new(B, n, 3) if want_i else None
+        if gw is not None or gg is not None or gi is not None:
+            lib, handle = _lib.load(), graph.graph.handle
+            ws = torch.empty(lib.gnode_dmp_batch_schedule_backward_workspace_bytes(handle, B, T), dtype=torch.uint8, device=y0.device)
+            _lib.check(lib.gnode_dmp_batch_schedule_backward_f32(
+                handle, _lib.ptr(w) if nnz else None, ctx.strides[0], _lib.ptr(g), ctx.strides[1], _lib.host_ptr(ctx.phase), P, _lib.ptr(y0), B, T,
+                _lib.ptr(out), _lib.ptr(grad_out), _lib.ptr(gw), _lib.ptr(gg), _lib.ptr(gi), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()))
+        if want_w:                                                  # the library returns one block per sample: a shared table sums them
+            gw = torch.zeros_like(w) if gw is None else gw if w.dim() == 3 else gw.sum(0)
+        if want_g and g.dim() == 2:
+            gg = gg.sum(0)
+        return None, gw, gg, gi, None, None
+
+
+def dmp_marginals_schedule(graph, weights, gamma, init, maxTime, phase):
+    """`dmp_marginals` with rates that change over time: the DMP marginals of B samples under a piecewise-constant schedule of
+    P phases as a differentiable function of device tensors -- float32 [B, maxTime, n, 3], bit for bit what `dmp_batch` returns
+    for the same schedule -- with `.backward()` through the library's scheduled reverse sweep
+    (gnode_dmp_batch_schedule_backward_f32): how strong was the lockdown, did recovery speed up once testing began.
+
+    graph: a `DmpGraph` (only its pattern is read).  weights: float32 [P, nnz], shared by the samples, or [B, P, nnz]: one
+    table per phase in the graph's CSR position order.  gamma: float32 [P, n] or [B, P, n], with the same P.  init: float32
+    [B, n, 3].  phase: a sequence of whole numbers of length >= maxTime, phase[t] in [0, P) naming the tables of step t = 1 ..
+    maxTime-1 (entry 0 is ignored), or a `gnode.ode_nn.RateSchedule`, of which `phase_of_step(maxTime)` is taken and the values
+    ignored.  The tables are probabilities: the library refuses a NaN or an entry outside [0, 1] (GnodeError).  Gradients are
+    computed for the inputs that require one; a shared table gets the sum over the samples, and a phase no step names gets
+    exact zeros.  Step t's phi reads step t's tables and theta_{t+1} the weight of step t + 1, so phase p's weight gradient
+    collects both kinds of term.
+
+    One scale per phase needs no kernel of its own: write `weights = base[None, :] * s[:, None]` in torch and autograd carries
+    the table's gradient to `s`.  What is wrong raises ValueError before the library is loaded; a tensor that is not on a GPU
+    raises GnodeError."""
+    from .ode_nn import RateSchedule
+    who = "dmp_marginals_schedule"
+    _refuse_schedule(who, graph=graph, weights=weights, gamma=gamma)
+    if not isinstance(graph, DmpGraph):
+        raise ValueError(f"{who}: graph must be a DmpGraph, got {type(graph).__name__}")
+    try:
+        T = int(maxTime)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: maxTime must be a whole number >= 2 (got {maxTime!r})") from None
+    n, nnz = graph.N, graph.E
+    if T < 2:
+        raise ValueError(f"{who}: maxTime must be >= 2 (got {maxTime})")
+    for name, t in (("weights", weights), ("gamma", gamma), ("init", init)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+            raise ValueError(f"{who}: {name} must be a float32 tensor")
+    if init.dim() != 3 or init.shape[0] < 1 or tuple(init.shape[1:]) != (n, 3):
+        raise ValueError(f"{who}: init must have the shape [B >= 1, {n}, 3], got {tuple(init.shape)}")
+    B = init.shape[0]
+    if gamma.dim() not in (2, 3) or gamma.shape[-2] < 1 or gamma.shape[-1] != n or (gamma.dim() == 3 and gamma.shape[0] != B):
+        raise ValueError(f"{who}: gamma must have the shape [P >= 1, {n}] or [{B}, P, {n}], got {tuple(gamma.shape)}")
+    P = int(gamma.shape[-2])
+    if tuple(weights.shape) not in ((P, nnz), (B, P, nnz)):
+        raise ValueError(f"{who}: weights must have the shape [{P}, {nnz}] or [{B}, {P}, {nnz}] -- gamma holds P = {P} phases --, got "
+                         f"{tuple(weights.shape)}")
+    if isinstance(phase, RateSchedule):
+        steps = phase.phase_of_step(T).astype(np.int64)              # (a schedule given as too few `steps`: ValueError)
+    else:
+        steps = _source_ints("phase", phase, who=who)
+        if steps.shape[0] < T:
+            raise ValueError(f"{who}: phase names {steps.shape[0]} steps, the call has maxTime = {T}")
+    steps = steps[:T].copy()
+    steps[0] = 0                                                    # never read
+    if steps.min() < 0 or steps.max() >= P:
+        t_bad = int(np.flatnonzero((steps < 0) | (steps >= P))[0])
+        raise ValueError(f"{who}: phase[{t_bad}] = {int(steps[t_bad])} is not in [0, {P})")
+    for t in (weights, gamma, init):
+        if not t.is_cuda:
+            raise _lib.GnodeError("GN-ODE path: tensor is not on a GPU (no CPU fallback exists)")
+    return _DmpMarginalsSchedule.apply(graph, weights, gamma, init, T, np.ascontiguousarray(steps, dtype=np.int32))
 
 
 def _batch_numbers(name, value, shapes, who="dmp_batch"):

@@ -281,7 +281,7 @@ def refuse_schedule(who, **args):
     for name, v in args.items():
         if isinstance(v, RateSchedule):
             raise ValueError(f"{who}: {name} is a RateSchedule; this call takes constant rates "
-                             "(schedules: sir_counts, sir_trajectories, sir_torch, dmp_batch)")
+                             "(schedules: sir_counts, sir_trajectories, sir_torch, dmp_batch; gradients under one: dmp_marginals_schedule)")
 
 
 def joint_phases(phases):

@@ -596,6 +596,42 @@ int gnode_dmp_backward_f32(gnode_graph_t g, const float* weights, const float* g
                            const float* grad_out /* the same shape */, float* grad_w /* [nnz] or NULL */,
                            float* grad_gamma /* [n] or NULL */, float* grad_init /* [n][3] or NULL */,
                            void* workspace, size_t workspace_bytes, void* stream);
+/* The reverse sweep under a rate schedule (no version step: a stale library is known by the missing symbol): the gradient of
+ * sum(grad_out * out) for gnode_dmp_batch_schedule_f32's recurrence, with respect to every phase's tables and the start.
+ * weights, the strides, gamma, phase_host, P, init, B and maxTime are the scheduled forward's arguments, checked as there (the
+ * tables are read back once: a NaN or an entry outside [0, 1] is named by sample, phase and position); `out` is what it
+ * returned and grad_out has its shape.
+ *   grad_w      device fp32 [B][P][nnz]     grad_gamma  device fp32 [B][P][n]     grad_init  device fp32 [B][n][3]
+ * One block per sample even where the forward's table is shared; NULL means "not wanted", and grad_w may be NULL when nnz = 0.
+ * The entry zeroes the gradients it is given, so a phase that no step names comes back as exact zeros.  The sweep is
+ * gnode_dmp_batch_backward_f32's with each step's adjoint going to its phase, p_t = phase_host[t]:
+ *   edge pass t (t + 1 < maxTime)   pb = phi_bar - w^{p_{t+1}} theta_bar;   w_bar^{p_{t+1}} -= phi_t theta_bar  (theta_{t+1}'s
+ *                                   weight is the NEXT step's);   w_bar^{p_t} -= ((1 - gamma^{p_t}_u) phi_{t-1}) pb;   gamma^{p_t}_u
+ *                                   gets -((1 - w^{p_t}) phi_{t-1}) pb;   phi_bar <- ((1 - w^{p_t})(1 - gamma^{p_t}_u)) pb
+ *   node pass t                     gamma_bar^{p_t}_k += Pi_{t-1}[k] aR and its row's shares;   pi_bar <- gamma^{p_t}_k aR
+ *   after t = 1                     w_bar^{p_1} -= Pi_0[src] theta_bar;   pi0_bar sums phi_bar - w^{p_1} theta_bar over the row
+ * In one pass the thread of edge e writes grad_w[p_t][e] and grad_w[p_{t+1}][e] only, the thread of node k grad_gamma[p_t][k]
+ * only; where the two phases are equal the two updates of the one slot happen in the constant sweep's order.  No atomics, a
+ * deterministic result; with P = 1 the three gradients are gnode_dmp_batch_backward_f32's bit for bit.  The tape is rebuilt
+ * with the scheduled forward's own arithmetic (2 * nnz * 4 bytes per step and sample).  The two forms are the constant
+ * backward's, chosen by gnode_dmp_batch_backward_lds_bytes(g) <= 160 KiB (the tables are never held in LDS): one workgroup per
+ * sample, which reads a device copy of the phase table at every step, or launches per pass over B * n rows and B * nnz edge
+ * slots whose table offsets come from the host loop.  The workspace holds that copy, the tapes, then the general form's arrays;
+ * the size query returns 0 without a handle, for B < 1 and for maxTime < 2.
+ * GNODE_ERR_ARG: a null pointer, weights null with nnz > 0, B < 1, maxTime < 2, P < 1, a phase outside [0, P) at a step
+ * 1 .. maxTime-1, a stride that is neither 0 nor the table's length, all three gradient pointers null, a NaN or out-of-range
+ * rate, an asymmetric pattern; GNODE_ERR_WORKSPACE: a short workspace; nothing is written to the gradients in either case.
+ * Synchronises `stream`. */
+size_t gnode_dmp_batch_schedule_backward_workspace_bytes(gnode_graph_t g, int32_t B, int32_t maxTime);
+int gnode_dmp_batch_schedule_backward_f32(gnode_graph_t g,
+                                          const float* weights, int64_t w_stride,       /* device [P][nnz] (stride 0) or [B][P][nnz] (P * nnz) */
+                                          const float* gamma, int64_t gamma_stride,     /* device [P][n] (stride 0) or [B][P][n] (P * n) */
+                                          const int32_t* phase_host, int32_t P,         /* host [maxTime], entry 0 ignored */
+                                          const float* init, int32_t B, int32_t maxTime,
+                                          const float* out /* the scheduled forward's [B][maxTime][n][3] */,
+                                          const float* grad_out /* the same shape */, float* grad_w /* [B][P][nnz] or NULL */,
+                                          float* grad_gamma /* [B][P][n] or NULL */, float* grad_init /* [B][n][3] or NULL */,
+                                          void* workspace, size_t workspace_bytes, void* stream);
 /* Source inference from one snapshot (Lokhov, Mezard, Ohta, Zdeborova 2014): the recurrence from each of C candidate sources,
  * scored against the observed states, without a marginal ever reaching global memory.  Candidate c's sample is
  * gnode_dmp_batch_f32's from the one-hot seed state (1 - [k == candidates[c]], [k == candidates[c]], 0) with the shared
