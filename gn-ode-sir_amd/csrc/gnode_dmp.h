@@ -1,10 +1,11 @@
 // The DMP recurrence, stated once for the marginals and their reverse sweep (gnode_dmp.hip, and gnode_dmp_schedule.hip,
-// gnode_dmp_schedule_bwd.hip under a rate schedule), for the source scores (gnode_dmp_source.hip, gnode_dmp_source_batch.hip,
-// gnode_dmp_source_events.hip) and for the outbreak sizes (gnode_dmp_outbreak.hip): the four dmp_* functions below and nothing
-// else, and their reverses, the dmp_rev_* functions after them.  They work on values and on pointers that are
-// already the sample's own, in global memory or in LDS.  The library is built with -ffp-contract=off, so they round as
-// written wherever they are inlined; their operand order is the reference's.  Behind them: the fixed-order fp64 sums, and what
-// the two source units share -- the synthesised start, the likelihood terms and the two kernels that read no observation.
+// gnode_dmp_schedule_bwd.hip under a rate schedule) and for the candidate sweeps (gnode_dmp_sweep.h: the source scores of
+// gnode_dmp_source.hip, gnode_dmp_source_batch.hip, gnode_dmp_source_events.hip and the outbreak sizes of gnode_dmp_outbreak.hip):
+// the four dmp_* functions below and nothing else, and their reverses, the dmp_rev_* functions after them.  They work on values
+// and on pointers that are already the sample's own, in global memory or in LDS.  The library is built with -ffp-contract=off, so
+// they round as written wherever they are inlined; their operand order is the reference's.  Behind them: the fixed-order fp64
+// sums, the source units' one-hot start and likelihood terms, and the LDS of a one-workgroup kernel.  The candidate sweep itself
+// -- its kernels, workspace, preamble and launches -- is gnode_dmp_sweep.h's.
 #pragma once
 #include "gnode_common.h"
 #include <vector>
@@ -130,7 +131,7 @@ __device__ __forceinline__ double dmp_sum_in_order(const double* v, int count) {
     return s;
 }
 
-// Source inference (gnode_dmp_source.hip, gnode_dmp_source_batch.hip).  The start of node k in the sample of candidate `cand`:
+// Source inference (the readers of gnode_dmp_source.hip, gnode_dmp_source_batch.hip, gnode_dmp_source_events.hip).  The start of node k in the sample of candidate `cand`:
 // (1 - seed, seed, 0) like k_dmp_seed_out0; Pr_0 = 0
 __device__ __forceinline__ void dmp_source_state(int k, int cand, float& ps0, float& pi0) {
     const float seed = k == cand ? 1.0f : 0.0f;
@@ -169,36 +170,6 @@ __device__ __forceinline__ double dmp_source_event_pick(int o, const DmpSourceEv
     return o == 0 ? l.s : o == 1 ? l.i : o == 2 ? l.r : o == 3 ? l.on : o == 4 ? l.off : 0.0;
 }
 
-// The two kernels of the source entries' general form that read no observation, for the argument struct of either unit (its
-// w, gamma, cand, n, nnz).  `per` blocks of 256 per candidate, candidate c = blockIdx.x / per; per-candidate state is at row
-// c * n + k and edge slot c * nnz + e of the workspace arrays.
-template <class Args>
-__global__ __launch_bounds__(256) void k_dmp_source_init(const int* __restrict__ src, Args a, unsigned per, float* __restrict__ theta,
-                                                        float* __restrict__ phi, float* __restrict__ ps) {
-    const size_t c = blockIdx.x / per;
-    const long e = (long)(blockIdx.x % per) * 256 + threadIdx.x;
-    if (e >= a.nnz) return;
-    const size_t slot = c * (size_t)a.nnz + e;
-    float ps0, pi0;
-    dmp_source_state(src[e], a.cand[c], ps0, pi0);
-    dmp_edge_start(ps0, pi0, a.w[e], theta[slot], phi[slot], ps[slot]);
-}
-template <class Args>
-__global__ __launch_bounds__(256) void k_dmp_source_edge(const int* __restrict__ src, const int* __restrict__ rev,
-                                                        const float* __restrict__ P, const float* __restrict__ theta, Args a,
-                                                        unsigned per, float* __restrict__ phi, float* __restrict__ ps,
-                                                        float* __restrict__ theta_next) {
-    const size_t c = blockIdx.x / per;
-    const long e = (long)(blockIdx.x % per) * 256 + threadIdx.x;
-    if (e >= a.nnz) return;
-    const size_t base = c * (size_t)a.nnz, slot = base + e;
-    const int u = src[e];
-    float ps0, pi0;
-    dmp_source_state(u, a.cand[c], ps0, pi0);
-    dmp_edge_update(P[c * (size_t)a.n + u], theta[base + rev[e]], ps0, a.w[e], a.gamma[u], phi[slot], ps[slot], theta[slot],
-                    theta_next[slot]);
-}
-
 // The P tables of a scheduled call (gnode_dmp_schedule.hip, gnode_dmp_schedule_bwd.hip) are probabilities, and they live on the
 // device: they come back once, on the caller's stream (which the call synchronises anyway), and the first entry that is a NaN
 // or outside [0, 1] is named by sample, phase and position.  Nothing has been written when this refuses.  `samples`: 1 for a
@@ -216,3 +187,19 @@ static inline int dmp_check_rate_tables(const char* who, const char* what, const
 
 __host__ __device__ static inline size_t dmp_align16(size_t x) { return (x + 15) / 16 * 16; }
 static constexpr size_t kDmpLdsLimit = 160 * 1024;      // what a gfx950 workgroup may declare
+
+// The LDS of a one-workgroup kernel's sample, carved from the kernel's dynamic LDS: theta x2, phi, ps, rev over the edges | P,
+// Pi, Pr over the nodes (gnode_dmp_batch_lds_bytes), and `rest`, whatever the kernel declares behind them.  (k_dmp_batch_wg and
+// k_dmp_sched_wg carve the same by hand: through this struct their instruction streams change, and they were to stay.)
+struct DmpLds {
+    float *theta0, *theta1, *phi, *ps;
+    int* rev;
+    float *P, *Pi, *Pr;
+    char* rest;
+    __device__ __forceinline__ float* theta(int i) const { return i ? theta1 : theta0; }       // (selected, not indexed: the struct stays in registers)
+};
+__device__ __forceinline__ DmpLds dmp_lds(char* smem, int n, int nnz) {
+    const size_t eb = dmp_align16((size_t)nnz * 4), nb = dmp_align16((size_t)n * 4);
+    return {(float*)smem, (float*)(smem + eb), (float*)(smem + 2 * eb), (float*)(smem + 3 * eb), (int*)(smem + 4 * eb),
+            (float*)(smem + 5 * eb), (float*)(smem + 5 * eb + nb), (float*)(smem + 5 * eb + 2 * nb), smem + 5 * eb + 3 * nb};
+}

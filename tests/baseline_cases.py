@@ -37,6 +37,27 @@ def is_parents(key, out):
     return list(out.shape) == e["shape"] and f32_digest(out) == e["sha256"]
 
 
+def candidates_entry(out, **sizes):
+    """What tests/golden/dmp_candidates_parent.json holds for one call of a candidate sweep: the shape of its float64 output, the
+    SHA-256 of its bytes, and the sizes and the tile that the library answered for the call's graph.  Finite, or nothing to hash."""
+    a = np.ascontiguousarray(out.cpu().numpy())
+    assert a.dtype == np.float64 and np.isfinite(a).all()
+    return {"shape": list(a.shape), "sha256": hashlib.sha256(a.tobytes()).hexdigest(), **{k: int(v) for k, v in sizes.items()}}
+
+
+@functools.lru_cache(maxsize=None)
+def dmp_candidates_parent():
+    """{key: entry} of tests/golden/dmp_candidates_parent.json (make_golden_dmp_candidates_parent.py says what the keys are)."""
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "dmp_candidates_parent.json")) as f:
+        return json.load(f)["entries"]
+
+
+def assert_candidates_parents(entries):
+    """every (key, entry) that a module's `parent_entries` recomputed is the fixture's: shape, bits, sizes and tile"""
+    for key, got in entries:
+        assert got == dmp_candidates_parent()[key], key
+
+
 def weights(nnz, lo, hi, seed):
     return np.random.default_rng(seed).uniform(lo, hi, size=nnz).astype(np.float32)   # per directed edge: w_uv != w_vu
 

@@ -19,7 +19,7 @@ import numpy as np
 import pytest
 
 import dmp_grad_model
-from baseline_cases import DMP_CASES, er as _er
+from baseline_cases import DMP_CASES, assert_candidates_parents, candidates_entry, er as _er
 from sir_cases import dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
@@ -447,3 +447,26 @@ def test_greedy_seeds_takes_the_hub_then_the_far_path(dev):
     got = greedy_seeds(DmpGraph(_matrix(c)), c["gam"], T, 2)
     assert [k for k, _ in got] == [0, 9], got
     assert abs(got[0][1] - model[0]) < 1e-3 and abs(got[1][1] - model2[pool2.index(9)]) < 1e-3
+
+
+# ------------------------------------------------------------------ the parent's bits
+PARENT_CASES = [(name, T) for name in ONE_WORKGROUP + GENERAL for T in HORIZONS]
+
+
+def parent_entries(name, T, dev):
+    """[(key, entry)] of tests/golden/dmp_candidates_parent.json for one case and horizon: both actions on the mixed start, with
+    and without `value`, on `cand_list`'s candidates (the last of them -1)."""
+    c, n = case(name), _n(name)
+    e = Entry(c["rp"], c["ci"], dev)
+    many = cand_list(n)
+    sizes = dict(workspace_bytes=e.need(len(many), T), lds_bytes=e.lib.gnode_dmp_outbreak_lds_bytes(e.g.handle))
+    return [(f"outbreak/{name}/T{T}/{action}/{'valued' if valued else 'null'}",
+             candidates_entry(e.sizes(c, base_start(name, "mixed"), many, action, values(name) if valued else None, T), **sizes))
+            for action in ACTIONS for valued in (False, True)]
+
+
+@pytest.mark.parametrize("name,T", PARENT_CASES)
+def test_sizes_are_the_parents_bits(name, T, dev):
+    """tests/golden/dmp_candidates_parent.json: what the library of commit 40c1952 returned on an MI355X, when this entry had
+    kernels and a host side of its own.  Equality of digests, of the workspace and of the LDS the library asks for."""
+    assert_candidates_parents(parent_entries(name, T, dev))

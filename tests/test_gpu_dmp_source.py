@@ -16,7 +16,7 @@ import numpy as np
 import pytest
 
 import dmp_grad_model
-from baseline_cases import DMP_CASES, er as _er
+from baseline_cases import DMP_CASES, assert_candidates_parents, candidates_entry, er as _er
 from sir_cases import dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
@@ -356,3 +356,23 @@ def test_the_source_of_a_path_outbreak_is_found(dev):
         ranked = rank_sources(scores, ids)
         assert ranked[0][:2] == (4, 2), ranked
         assert [r[0] for r in ranked] == [ids[i] for i in np.argsort(-scores.max(1).values.cpu().numpy(), kind="stable")]
+
+
+# ------------------------------------------------------------------ the parent's bits
+PARENT_CASES = [(name, T) for name in ONE_WORKGROUP + GENERAL for T in HORIZONS]
+
+
+def parent_entries(name, T, dev):
+    """[(key, entry)] of tests/golden/dmp_candidates_parent.json for one case and horizon: `cand_list`'s candidates on `mixed_obs`."""
+    c, n = case(name), _n(name)
+    e = Entry(c["rp"], c["ci"], dev)
+    many = cand_list(n)
+    sizes = dict(workspace_bytes=e.need(len(many), T), lds_bytes=e.lib.gnode_dmp_source_lds_bytes(e.g.handle))
+    return [(f"source/{name}/T{T}", candidates_entry(e.scores(c, many, mixed_obs(n), T), **sizes))]
+
+
+@pytest.mark.parametrize("name,T", PARENT_CASES)
+def test_scores_are_the_parents_bits(name, T, dev):
+    """tests/golden/dmp_candidates_parent.json: what the library of commit 40c1952 returned on an MI355X, when this entry had
+    kernels and a host side of its own.  Equality of digests, of the workspace and of the LDS the library asks for."""
+    assert_candidates_parents(parent_entries(name, T, dev))

@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 
 import dmp_grad_model
-from baseline_cases import er as _er
+from baseline_cases import assert_candidates_parents, candidates_entry, er as _er
 from sir_cases import dev  # noqa: F401
 from test_gpu_dmp_source import big_er, cand_list, case, mixed_obs
 
@@ -279,3 +279,26 @@ def test_reproducible_on_a_dirty_workspace(form, dev):
     e.scores(many[:3], rows(name, range(50, 52 + O)), T + 1, ws=ws)                      # a larger call, other numbers
     assert torch.equal(e.scores(many, obs, T, ws=ws), first)
     assert torch.equal(first, solo_table(name, T, range(O), many))
+
+
+# ------------------------------------------------------------------ 9. the parent's bits
+PARENT_CASES = [(name, T) for name in ONE_WORKGROUP + GENERAL for T in HORIZONS] + [("edge", 8)]
+
+
+def parent_entries(name, T, dev):
+    """[(key, entry)] of tests/golden/dmp_candidates_parent.json for one case and horizon: O around the tile as test 1 chooses
+    it, and on the graph at the LDS edge test 3's two."""
+    e = BatchEntry(name, dev)
+    W, cands = e.tile(), cand_list(_n(name))
+    out = []
+    for O in (3, W + 1) if name == "edge" else sorted({o for o in (1, W - 1, W, W + 1, 2 * W + 1) if o >= 1}):
+        sizes = dict(workspace_bytes=e.need(len(cands), O, T), tile=W, lds_bytes=e.lib.gnode_dmp_source_lds_bytes(e.g.handle))
+        out.append((f"source_batch/{name}/T{T}/O{O}", candidates_entry(e.scores(cands, rows(name, range(O)), T), **sizes)))
+    return out
+
+
+@pytest.mark.parametrize("name,T", PARENT_CASES)
+def test_scores_are_the_parents_bits(name, T, dev):
+    """tests/golden/dmp_candidates_parent.json: what the library of commit 40c1952 returned on an MI355X, when this entry had
+    kernels and a host side of its own.  Equality of digests, of the workspace, of the tile and of the LDS the library asks for."""
+    assert_candidates_parents(parent_entries(name, T, dev))

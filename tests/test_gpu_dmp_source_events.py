@@ -15,7 +15,7 @@ import numpy as np
 import pytest
 
 import dmp_grad_model
-from baseline_cases import er as _er
+from baseline_cases import assert_candidates_parents, candidates_entry, er as _er
 from sir_cases import dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
@@ -419,3 +419,27 @@ def test_the_source_is_found_from_twelve_onset_times(dev):
     scores = source_scores_timed(A, obs, s["gamma"], s["T"], candidates=np.arange(s["n"]))
     ranked = rank_sources(scores, np.arange(s["n"]))
     assert ranked[0][0] == s["source"], ranked[:3]
+
+
+# ------------------------------------------------------------------ 7. the parent's bits
+PARENT_CASES = [(name, T) for name in NAMES for T in HORIZONS] + [("edge", 12)]
+
+
+def parent_entries(name, T, dev):
+    """[(key, entry)] of tests/golden/dmp_candidates_parent.json for one case and horizon: R and the floor around the tile as
+    test 1 chooses them, and on the graph at the LDS edge that test's two."""
+    e = EventsEntry(name, dev)
+    W, cands = e.tile(), cand_list(_n(name))
+    picks = [(W + 1, FLOORS[0]), (3, FLOORS[0])] if name == "edge" else [(1, FLOORS[0]), (W, FLOORS[0]), (W + 1, FLOORS[0]), (W + 1, FLOORS[1])]
+    out = []
+    for R, floor in picks:
+        sizes = dict(workspace_bytes=e.need(len(cands), R, T), tile=W, lds_bytes=e.lib.gnode_dmp_source_lds_bytes(e.g.handle))
+        out.append((f"source_events/{name}/T{T}/R{R}/floor{floor:g}", candidates_entry(e.scores(cands, coded_rows(name, range(R)), T, floor), **sizes)))
+    return out
+
+
+@pytest.mark.parametrize("name,T", PARENT_CASES)
+def test_scores_are_the_parents_bits(name, T, dev):
+    """tests/golden/dmp_candidates_parent.json: what the library of commit 40c1952 returned on an MI355X, when this entry had
+    kernels and a host side of its own.  Equality of digests, of the workspace, of the tile and of the LDS the library asks for."""
+    assert_candidates_parents(parent_entries(name, T, dev))
