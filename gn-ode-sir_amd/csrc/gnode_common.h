@@ -50,6 +50,8 @@ int gn_dmp_source_set_attributes();
 int gn_dmp_source_batch_set_attributes();
 int gn_dmp_source_events_set_attributes();
 int gn_dmp_outbreak_set_attributes();
+int gn_dmp_source_events_schedule_set_attributes();
+int gn_dmp_outbreak_schedule_set_attributes();
 int gn_rhs_vjp_set_attributes();
 
 // The training forward's KEPT ACTIVATIONS (H = 64): per grid point k three tables of rows + 1 rows of 64 floats --

@@ -18,6 +18,7 @@ struct DmpSourceArgs : DmpSweepArgs {
 };
 struct DmpSourceReader : DmpOneHotStart {
     using Args = DmpSourceArgs;
+    using Rates = DmpConstantRates;
     using Terms = double;
     static constexpr int W = 1;
     static constexpr bool kTiled = false;

@@ -13,14 +13,6 @@
 // the first three of the five are that unit's doubles, and everything else is the same sweep.
 #include "gnode_dmp_sweep.h"
 
-struct DmpEventTerms {
-    using Logs = DmpSourceEventLogs;
-    static __device__ __forceinline__ Logs logs(float ps, float pi, float pr, float ps_prev, float pr_prev, float floor) {
-        return dmp_source_event_logs(ps, pi, pr, ps_prev, pr_prev, floor);
-    }
-    static __device__ __forceinline__ double pick(int o, const Logs& l) { return dmp_source_event_pick(o, l); }
-};
-
 extern "C" int gnode_dmp_source_events_tile(gnode_graph_t g) { return dmp_rows_tile<DmpEventTerms>(g); }
 int gn_dmp_source_events_set_attributes() { return dmp_sweep_set_attributes<DmpRowsReader<DmpEventTerms>>(); }
 extern "C" size_t gnode_dmp_source_events_workspace_bytes(gnode_graph_t g, int32_t C, int32_t R, int32_t maxTime) {

@@ -544,6 +544,8 @@ int gn_device_setup_once(int dev) {
     if (int e = gn_dmp_source_batch_set_attributes()) return e;
     if (int e = gn_dmp_source_events_set_attributes()) return e;
     if (int e = gn_dmp_outbreak_set_attributes()) return e;
+    if (int e = gn_dmp_source_events_schedule_set_attributes()) return e;
+    if (int e = gn_dmp_outbreak_schedule_set_attributes()) return e;
     if (int e = gn_rhs_vjp_set_attributes()) return e;
     g_dev_done[dev] = true;
     return 0;

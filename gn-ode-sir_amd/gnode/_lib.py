@@ -112,6 +112,12 @@ ABI = {
     "gnode_dmp_outbreak_lds_bytes": (_sz, [_vp]),
     "gnode_dmp_outbreak_workspace_bytes": (_sz, [_vp, _i32, _i32]),
     "gnode_dmp_outbreak_sizes_f32": (_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _sz, _vp]),
+    "gnode_dmp_source_events_schedule_workspace_bytes": (_sz, [_vp, _i32, _i32, _i32, _i32]),
+    "gnode_dmp_source_events_scores_schedule_f32": (_int, [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _i32, C.c_float, _i32, _vp,
+                                                           _i64, _vp, _sz, _vp]),
+    "gnode_dmp_outbreak_schedule_workspace_bytes": (_sz, [_vp, _i32, _i32, _i32]),
+    "gnode_dmp_outbreak_sizes_schedule_f32": (_int, [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _sz,
+                                                     _vp]),
     "gnode_meanfield_workspace_bytes": (_sz, [_vp]),
     "gnode_meanfield_f64": (_int, [_vp, _vp, _i32, _f64, _vp, _vp, _i32, _f64, _f64, _vp, _vp, _vp, _pi64, _vp, _sz, _vp]),
     "gnode_meanfield_init_f64": (_int, [_vp, _vp, _f64, _vp, _vp, _i32, _f64, _f64, _vp, _vp, _vp, _pi64, _vp, _sz, _vp]),

@@ -35,6 +35,10 @@ same constructor and `run(seed_list, maxTime)`, the message passing runs in libg
                                              -> float64 tensor [C, maxTime, 3] on the GPU (an extension): the expected size of
                                                 S / I / R over time when candidate c alone is seeded or immunised in `start`,
                                                 summed in the node pass; infections(sizes) -> the number ever infected, [C]
+    source_scores_schedule(weight_adj, rows, gamma, maxTime, observed_at=None, ...), outbreak_sizes_schedule(weight_adj, gamma,
+                                                maxTime, ..., shifts=None) -> `source_scores_events` and `outbreak_sizes` when
+                                                weight_adj, scale and / or gamma is a RateSchedule: per sample a candidate
+                                                and a calendar shift; observed_at=D anchors the snapshot at calendar step D
     greedy_immunisation(graph, start, gamma, maxTime, k), greedy_seeds(graph, gamma, maxTime, k, start=None)
                                              -> [(node, infections_after), ...]: k greedy rounds of outbreak_sizes
 """
@@ -363,50 +367,49 @@ def _batch_starts(starts, n):
     return init
 
 
-def _batch_gamma(gamma, n, B, name="gamma"):
-    """float32 [n] or [B, n] of what `dmp_batch` accepts as gamma."""
-    g = _batch_numbers(name, gamma, [(), (n,), (B, n), (B,)])
-    if g.shape == (B,) and g.shape != (n,):
+def _batch_gamma(gamma, n, B, name="gamma", who="dmp_batch"):
+    """float32 [n] or [B, n] of what `dmp_batch` accepts as gamma; B None: a number or per-node values only, float32 [n]."""
+    g = _batch_numbers(name, gamma, [(), (n,)] if B is None else [(), (n,), (B, n), (B,)], who)
+    if B is not None and g.shape == (B,) and g.shape != (n,):
         g = np.repeat(g[:, None], n, axis=1)
     return np.ascontiguousarray(np.broadcast_to(g, (n,)) if g.ndim < 2 else g, dtype=np.float32)
 
 
-def _dmp_batch_schedule(weight_adj, starts, gamma, maxTime, scale, device):
-    """`dmp_batch` where weight_adj, scale and / or gamma is a RateSchedule: the joint phases of the schedules -- the distinct
-    combinations in order of first use -- their tables [P][...] (or [B][P][...] where a phase is per sample), and one
-    gnode_dmp_batch_schedule_f32 call.  Everything is checked before the library is loaded or a graph handle is made."""
-    from .ode_nn import RateSchedule, joint_phases
-    who = "dmp_batch"
-    starts = list(starts)
-    B, T = len(starts), int(maxTime)
-    if B < 1:
-        raise ValueError("dmp_batch: need at least one start")
-    if T < 2:
-        raise ValueError(f"dmp_batch: maxTime must be >= 2 (got {maxTime})")
-    if isinstance(weight_adj, RateSchedule):
-        mats = []
-        for p, M in enumerate(weight_adj.values):
-            if isinstance(M, DmpGraph):
-                raise ValueError(f"{who}: weight_adj phase {p}: a schedule takes matrices, not a DmpGraph")
-            A = sp.csr_matrix(M)
-            A.sort_indices()
-            mats.append(A)
-        for p, A in enumerate(mats[1:], 1):
-            if A.shape != mats[0].shape or not np.array_equal(A.indptr, mats[0].indptr) or not np.array_equal(A.indices, mats[0].indices):
-                raise ValueError(f"{who}: weight_adj phase {p} does not share phase 0's sparsity pattern (store an absent entry as an "
-                                 "explicit zero)")
-        G = DmpGraph(mats[0])
-        datas = [np.ascontiguousarray(A.data, dtype=np.float64) for A in mats]
-    else:
+def _schedule_graph(who, weight_adj):
+    """(DmpGraph, [float64 data per weight_adj phase]) of a weight_adj that may be a RateSchedule of matrices sharing one sparsity
+    pattern; ValueError otherwise."""
+    from .ode_nn import RateSchedule
+    if not isinstance(weight_adj, RateSchedule):
         G = weight_adj if isinstance(weight_adj, DmpGraph) else DmpGraph(weight_adj)
-        datas = [G.data]
+        return G, [G.data]
+    mats = []
+    for p, M in enumerate(weight_adj.values):
+        if isinstance(M, DmpGraph):
+            raise ValueError(f"{who}: weight_adj phase {p}: a schedule takes matrices, not a DmpGraph")
+        A = sp.csr_matrix(M)
+        A.sort_indices()
+        mats.append(A)
+    for p, A in enumerate(mats[1:], 1):
+        if A.shape != mats[0].shape or not np.array_equal(A.indptr, mats[0].indptr) or not np.array_equal(A.indices, mats[0].indices):
+            raise ValueError(f"{who}: weight_adj phase {p} does not share phase 0's sparsity pattern (store an absent entry as an "
+                             "explicit zero)")
+    return DmpGraph(mats[0]), [np.ascontiguousarray(A.data, dtype=np.float64) for A in mats]
+
+
+def _schedule_tables(who, G, datas, weight_adj, scale, gamma, L, B=None):
+    """The joint phases of the schedules among weight_adj, scale and gamma over a phase row of L entries -- the distinct
+    combinations in order of first use -- and their tables: (phase int32 [L], w float32 [P, nnz], gam float32 [P, n]).  With B
+    samples that may have rates of their own (`dmp_batch`: a scale of B numbers, gamma [B, n] or B numbers) a table is
+    [B, P, ...] where some phase is per sample; B None: the tables are shared, and a scale is None or one number.  Every table
+    holds probabilities: a weight times its scale, or a gamma, above 1 raises ValueError, as does a `steps=` schedule shorter
+    than L."""
+    from .ode_nn import RateSchedule, joint_phases
     n, nnz = G.N, G.E
-    init = _batch_starts(starts, n)
     s_vals = scale.values if isinstance(scale, RateSchedule) else [scale]
-    scales = [None if v is None else _batch_numbers(f"scale phase {p}", v, [(), (B,)]) for p, v in enumerate(s_vals)]
+    scales = [None if v is None else _batch_numbers(f"scale phase {p}", v, [()] if B is None else [(), (B,)], who) for p, v in enumerate(s_vals)]
     g_vals = gamma.values if isinstance(gamma, RateSchedule) else [gamma]
-    gams = [_batch_gamma(v, n, B, f"gamma phase {p}") for p, v in enumerate(g_vals)]
-    rows = [s.phase_of_step(T) if isinstance(s, RateSchedule) else np.zeros(T, dtype=np.int32) for s in (weight_adj, scale, gamma)]
+    gams = [_batch_gamma(v, n, B, f"gamma phase {p}", who) for p, v in enumerate(g_vals)]
+    rows = [s.phase_of_step(L) if isinstance(s, RateSchedule) else np.zeros(L, dtype=np.int32) for s in (weight_adj, scale, gamma)]
     phase, triples = joint_phases(rows)
     P = len(triples)
     per_sample_w = any(scales[ps] is not None and scales[ps].ndim == 1 for _, ps, _ in triples)
@@ -422,6 +425,25 @@ def _dmp_batch_schedule(weight_adj, starts, gamma, maxTime, scale, device):
             if a.size and a.max() > 1.0:                            # (NaN, infinite and negative values: _batch_numbers)
                 raise ValueError(f"{who}: phase {j} (weight_adj {pw}, scale {ps}, gamma {pg}): {name} exceeds 1; a schedule takes "
                                  "probabilities")
+    return phase, w, gam
+
+
+def _dmp_batch_schedule(weight_adj, starts, gamma, maxTime, scale, device):
+    """`dmp_batch` where weight_adj, scale and / or gamma is a RateSchedule: the joint phases of the schedules and their tables
+    [P][...] (or [B][P][...] where a phase is per sample) from `_schedule_tables`, and one gnode_dmp_batch_schedule_f32 call.
+    Everything is checked before the library is loaded or a graph handle is made."""
+    who = "dmp_batch"
+    starts = list(starts)
+    B, T = len(starts), int(maxTime)
+    if B < 1:
+        raise ValueError("dmp_batch: need at least one start")
+    if T < 2:
+        raise ValueError(f"dmp_batch: maxTime must be >= 2 (got {maxTime})")
+    G, datas = _schedule_graph(who, weight_adj)
+    n, nnz = G.N, G.E
+    init = _batch_starts(starts, n)
+    phase, w, gam = _schedule_tables(who, G, datas, weight_adj, scale, gamma, T, B)
+    P, per_sample_w, per_sample_g = int(gam.shape[-2]), w.ndim == 3, gam.ndim == 3
     lib, handle = _lib.load(), G.graph.handle
     up = lambda a: None if a.size == 0 else torch.from_numpy(np.ascontiguousarray(a)).to(device)      # noqa: E731  (no edge, no table)
     wd, gd, y0 = up(w), up(gam), up(init)
@@ -642,6 +664,88 @@ def source_scores_events(graph, rows, gamma, maxTime, candidates=None, floor=1e-
                            device)
 
 
+def _whole_number(who, name, value, lowest):
+    """`value` as an int >= lowest; ValueError otherwise."""
+    try:
+        whole = int(value)
+        ok = whole == value and whole >= lowest
+    except (TypeError, ValueError, OverflowError):
+        ok = False
+    if not ok:
+        raise ValueError(f"{who}: {name} must be a whole number >= {lowest} (got {value!r})")
+    return whole
+
+
+def source_scores_schedule(weight_adj, rows, gamma, maxTime, observed_at=None, candidates=None, scale=None, floor=1e-30,
+                           budget_bytes=1 << 30, device="cuda"):
+    """`source_scores_events` when the rates change over time -- who started this outbreak, given that contacts were cut on day
+    10 and the snapshot was taken on day 17?  A float64 device tensor [R, C, maxTime].
+
+    weight_adj, scale and gamma may each be a `gnode.ode_nn.RateSchedule`, joined exactly as `dmp_batch` joins them (one
+    sparsity pattern, a weight times its scale and every gamma in [0, 1], the schedules need not change at the same steps);
+    a scale is None or one number per phase, gamma a number or per-node values: the tables are shared by the candidates.  rows
+    holds codes -1 .. 4 as in `source_scores_events`; a row of codes -1 .. 2 is a snapshot, so this call serves what
+    `source_scores` and `source_scores_batch` serve under constant rates.  The schedules are stated in CALENDAR steps:
+      observed_at=None   the schedule counts from the outbreak's start: scores[r, c, t] = the log-likelihood of row r, t steps
+                         after c was seeded at calendar step 0, where step t of the run is governed by the schedule's step t.
+      observed_at=D      the rows were taken at calendar step D, a whole number >= maxTime - 1.  "c started tau steps before"
+                         places the run's step t at calendar step D - tau + t, so every tau is a run of its own: the samples
+                         are (c, shift D - tau) for tau = 0 .. maxTime - 1, and scores[r, c, tau] = that run's value at t = tau.
+                         The schedules are read up to calendar step D (`phase_of_step(D + 1)`: a `steps=` schedule shorter
+                         than that raises ValueError).  This costs maxTime full-length runs per candidate, of which about
+                         half the steps are never read: the run of tau continues past calendar step D, under step D's
+                         tables, and is read at t = tau only.
+    A sample's marginals are `dmp_batch`'s under `rate_schedule(values, steps=` the phase row from its shift on `)` from the
+    seed list [c], bit for bit, and the sums are `source_scores_events`' (`gnode_dmp_source_events_scores_schedule_f32`): with
+    schedules that change nothing the table is that call's bit for bit, and no entry depends on the other samples or on the
+    chunking.  The samples -- C, or C * maxTime -- go to the library in chunks of the largest count whose
+    `gnode_dmp_source_events_schedule_workspace_bytes` fits `budget_bytes`.  candidates, floor: `source_scores_events`'.  The
+    result feeds `rank_sources` (a row of it) and `source_rank_of`.  What is wrong raises ValueError before the library is
+    loaded or a graph handle is made."""
+    who = "source_scores_schedule"
+    T = _whole_number(who, "maxTime", maxTime, 2)
+    floor = float(floor)
+    if not 0.0 < floor <= 1.0 or not 0.0 < float(np.float32(floor)) <= 1.0:        # (a NaN fails it; so does a float32 zero)
+        raise ValueError(f"{who}: floor must be in (0, 1] as a float32 (got {floor})")
+    D = None if observed_at is None else _whole_number(who, "observed_at", observed_at, T - 1)
+    G, datas = _schedule_graph(who, weight_adj)
+    n = G.N
+    o = _source_obs_rows(rows, n, who, "rows", 4)
+    cand = source_candidates_events(o) if candidates is None else _source_ints("candidates", candidates, who=who)
+    if cand.size < 1:
+        raise ValueError(f"{who}: need at least one candidate")
+    if cand.min() < 0 or cand.max() >= n:
+        raise ValueError(f"{who}: candidate {int(cand[(cand < 0) | (cand >= n)][0])} is not in [0, {n})")
+    phase, w, gam = _schedule_tables(who, G, datas, weight_adj, scale, gamma, T if D is None else D + 1)
+    R, C, P = int(o.shape[0]), int(cand.size), int(gam.shape[0])
+    if D is None:
+        ids, shifts = cand.astype(np.int32), np.zeros(C, dtype=np.int32)
+    else:                                                           # sample c * T + tau = (c, D - tau)
+        ids, shifts = np.repeat(cand, T).astype(np.int32), np.tile(D - np.arange(T), C).astype(np.int32)
+        # every run is full-length, so the run of tau goes on to calendar step D - tau + T - 1 > D: steps that no entry of the
+        # result reads (entry tau stops at t = tau, calendar step D).  They are run under step D's phase.
+        phase = np.ascontiguousarray(np.concatenate([phase, np.full(T - 1, phase[-1], dtype=np.int32)]))
+    L = int(phase.shape[0])
+    N, budget = int(ids.size), int(budget_bytes)
+    lib, handle = _lib.load(), G.graph.handle
+    need = lambda c: int(lib.gnode_dmp_source_events_schedule_workspace_bytes(handle, c, R, T, L))       # noqa: E731
+    chunk = _largest_chunk(need, N, budget, who)
+    up = lambda a, dt: None if a.size == 0 else torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(device)      # noqa: E731
+    wd, gd, cd = up(w, np.float32), up(gam, np.float32), up(ids, np.int32)
+    od = o.to(torch.int8).contiguous() if isinstance(o, torch.Tensor) else up(o, np.int8)
+    table = torch.empty((R, N, T), dtype=torch.float64, device=cd.device)
+    ws = torch.empty(need(chunk), dtype=torch.uint8, device=cd.device)
+    for at in range(0, N, chunk):
+        c = min(chunk, N - at)
+        part = np.ascontiguousarray(shifts[at:at + c])
+        _lib.check(lib.gnode_dmp_source_events_scores_schedule_f32(
+            handle, _lib.ptr(wd), _lib.ptr(gd), _lib.host_ptr(phase), P, L, _lib.ptr(cd[at:at + c]), _lib.host_ptr(part), c, _lib.ptr(od), R,
+            floor, T, _lib.ptr(table[0, at:at + c]), N * T, _lib.ptr(ws), ws.numel(), _lib.stream_ptr()))
+    if D is None:
+        return table
+    return torch.diagonal(table.view(R, C, T, T), dim1=2, dim2=3).contiguous()       # [r, c, tau] = sample (c, tau) at t = tau
+
+
 class TimedObservations:
     """Records (node, offset, kind) packed into rows for `source_scores_events`, by `timed_observations`: `rows` int8 [R, n]
     (-1 where a row has no record of a node), `row_offsets` int64 [R], the offset every record of a row shares (<= 0, steps
@@ -813,7 +917,7 @@ class _Outbreak:
         self.n, self.T = self.G.N, int(maxTime)
         if self.T < 2:
             raise ValueError(f"{who}: maxTime must be >= 2 (got {maxTime})")
-        self.gamma = _batch_numbers("gamma", gamma, [(), (self.n,)], who)
+        self.gamma = None if gamma is None else _batch_numbers("gamma", gamma, [(), (self.n,)], who)      # (None: the caller's tables)
         self.value = None if value is None else _batch_numbers("value", value, [(self.n,)], who)
         self.budget = int(budget_bytes)
         self.tables = None
@@ -891,6 +995,56 @@ def outbreak_sizes(graph, gamma, maxTime, candidates=None, action="seed", start=
     base = plan.start(start)
     _outbreak_action(who, action, base)
     return plan.sizes(base, plan.candidates(candidates, -1), action, device)
+
+
+def outbreak_sizes_schedule(weight_adj, gamma, maxTime, candidates=None, action="seed", start=None, value=None, scale=None, shifts=None,
+                            budget_bytes=1 << 30, device="cuda"):
+    """`outbreak_sizes` when the rates change over time -- whom do we immunise now, given the reopening planned for day 25?  A
+    float64 device tensor [C, maxTime, 3], sizes[c, t, j] as `outbreak_sizes` defines it.
+
+    weight_adj, scale and gamma may each be a `gnode.ode_nn.RateSchedule`, joined as `source_scores_schedule` joins them; the
+    tables are shared by the candidates.  shifts: None -- the schedule counts from the start of every run -- or one whole
+    number >= 0 per candidate: step t of candidate c's run is governed by the schedule's step shifts[c] + t, a run that starts
+    shifts[c] steps into the calendar.  candidates=[-1] * K with shifts=range(K) gives the outbreak as it is, started at each
+    of K steps: what each step of delay costs.  The schedules are read up to step max(shifts) + maxTime - 1
+    (`phase_of_step(max(shifts) + maxTime)`; a `steps=` schedule shorter than that raises ValueError).  A sample's marginals
+    are `dmp_batch`'s under the phase row from its shift on, bit for bit, and the sums are `outbreak_sizes`'
+    (`gnode_dmp_outbreak_sizes_schedule_f32`): with schedules that change nothing the table is that call's bit for bit.
+    candidates, action, start, value, budget_bytes (by `gnode_dmp_outbreak_schedule_workspace_bytes`): `outbreak_sizes`';
+    `infections(sizes)` reads the result as before.  What is wrong raises ValueError before the library is loaded or a graph
+    handle is made."""
+    who = "outbreak_sizes_schedule"
+    T = _whole_number(who, "maxTime", maxTime, 2)
+    G, datas = _schedule_graph(who, weight_adj)
+    plan = _Outbreak(who, G, None, T, value, budget_bytes)
+    base = plan.start(start)
+    _outbreak_action(who, action, base)
+    cand = plan.candidates(candidates, -1)
+    C = int(cand.size)
+    if shifts is None:
+        sh = np.zeros(C, dtype=np.int64)
+    else:
+        sh = _source_ints("shifts", shifts, C, who=who)
+        if sh.min() < 0:
+            raise ValueError(f"{who}: shift {int(sh.min())} is negative: a run starts at calendar step 0 or later")
+    L = int(sh.max()) + T
+    phase, w, gam = _schedule_tables(who, G, datas, weight_adj, scale, gamma, L)
+    P, sh = int(gam.shape[0]), sh.astype(np.int32)
+    lib, handle = _lib.load(), G.graph.handle
+    need = lambda c: int(lib.gnode_dmp_outbreak_schedule_workspace_bytes(handle, c, T, L))       # noqa: E731
+    chunk = _largest_chunk(need, C, plan.budget, who)
+    up = lambda a, dt: None if a is None or a.size == 0 else torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(device)      # noqa: E731
+    wd, gd, vd = up(w, np.float32), up(gam, np.float32), up(plan.value, np.float32)
+    y0, cd = up(base.p, np.float32), up(cand, np.int32)
+    out = torch.empty((C, T, 3), dtype=torch.float64, device=cd.device)
+    ws = torch.empty(need(chunk), dtype=torch.uint8, device=cd.device)
+    for at in range(0, C, chunk):
+        c = min(chunk, C - at)
+        part = np.ascontiguousarray(sh[at:at + c])
+        _lib.check(lib.gnode_dmp_outbreak_sizes_schedule_f32(
+            handle, _lib.ptr(wd), _lib.ptr(gd), _lib.host_ptr(phase), P, L, _lib.ptr(y0), _lib.ptr(cd[at:at + c]), _lib.host_ptr(part), c,
+            _OUTBREAK_ACTIONS[action], _lib.ptr(vd), T, _lib.ptr(out[at:at + c]), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()))
+    return out
 
 
 def infections(sizes):

@@ -281,7 +281,8 @@ def refuse_schedule(who, **args):
     for name, v in args.items():
         if isinstance(v, RateSchedule):
             raise ValueError(f"{who}: {name} is a RateSchedule; this call takes constant rates "
-                             "(schedules: sir_counts, sir_trajectories, sir_torch, dmp_batch; gradients under one: dmp_marginals_schedule)")
+                             "(schedules: sir_counts, sir_trajectories, sir_torch, dmp_batch; gradients under one: dmp_marginals_schedule; source "
+                             "scores and outbreak sizes under one: source_scores_schedule, outbreak_sizes_schedule)")
 
 
 def joint_phases(phases):

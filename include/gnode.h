@@ -20,7 +20,7 @@
  *     into a hipGraph on first use and one handle may serve several streams (each
  *     with its own workspace).  Functions that DO synchronise `stream` say so below
  *     (gnode_graph_create, gnode_sir_mc_philox with more than 32 seeds,
- *     gnode_sir_mc_philox_nodes, gnode_sir_mc_philox_edges, gnode_sir_mc_philox_traj_edges, gnode_sir_mc_philox_traj with more than 32 seeds or rate arrays, gnode_sir_mc_philox_init, gnode_sir_mc_coins, gnode_dmp_f32, gnode_dmp_init_f32, gnode_dmp_batch_f32, gnode_dmp_batch_backward_f32, gnode_dmp_backward_f32, gnode_dmp_source_scores_f32, gnode_dmp_source_batch_scores_f32, gnode_dmp_source_events_scores_f32, gnode_meanfield_f64, gnode_meanfield_init_f64, gnode_meanfield_rates_f64, gnode_meanfield_rates_steps_f64).
+ *     gnode_sir_mc_philox_nodes, gnode_sir_mc_philox_edges, gnode_sir_mc_philox_traj_edges, gnode_sir_mc_philox_traj with more than 32 seeds or rate arrays, gnode_sir_mc_philox_init, gnode_sir_mc_coins, gnode_dmp_f32, gnode_dmp_init_f32, gnode_dmp_batch_f32, gnode_dmp_batch_backward_f32, gnode_dmp_backward_f32, gnode_dmp_source_scores_f32, gnode_dmp_source_batch_scores_f32, gnode_dmp_source_events_scores_f32, gnode_dmp_source_events_scores_schedule_f32, gnode_dmp_outbreak_sizes_schedule_f32, gnode_meanfield_f64, gnode_meanfield_init_f64, gnode_meanfield_rates_f64, gnode_meanfield_rates_steps_f64).
  *   - process-wide state: (1) a per-device "set up once" table (compute-unit count,
  *     dynamic-LDS kernel attributes), written under a lock by the first
  *     gnode_graph_create on a device and read-only afterwards; (2) the opt-in
@@ -743,6 +743,51 @@ int gnode_dmp_outbreak_sizes_f32(gnode_graph_t g, const float* weights, const fl
                                  const float* value /* device [n] or NULL */, int32_t maxTime,
                                  double* sizes /* device fp64 [C][maxTime][3] */, void* workspace, size_t workspace_bytes,
                                  void* stream);
+/* Source scores and outbreak sizes under rates that change over time (no version step: a stale library is known by the missing
+ * symbol): gnode_dmp_source_events_scores_f32 and gnode_dmp_outbreak_sizes_f32 with the schedule of gnode_dmp_batch_schedule_f32
+ * -- P >= 1 tables of each kind shared by the samples -- a phase row stated in CALENDAR steps, and per sample a candidate id
+ * and a SHIFT: step t = 1 .. maxTime-1 of sample j reads the tables of p_t = phase_host[shifts_host[j] + t],
+ *   theta_1 from w^{p_1};   node pass t: gamma^{p_t};   edge pass t (only when t + 1 < maxTime): w^{p_t}, gamma^{p_t}, and w^{p_{t+1}}
+ *   for theta_{t+1}
+ * exactly as gnode_dmp_batch_schedule_f32 reads them under the row phase_host[shift .. shift + maxTime): sample j's fp32
+ * marginals are that call's bit for bit, and the sums are the constant entries' (same form, same launch shape, same order).  A
+ * source hypothesis "c started tau steps before the snapshot of calendar step D" is the sample (c, D - tau) read at t = tau;
+ * shift 0 for everybody is a schedule that counts from the outbreak's start; candidate -1 of the outbreak entry with shifts
+ * 0 .. K-1 prices each step of delay.  A sample's rows do not depend on C, on its position or on the other samples; (c, shift s)
+ * under a row equals (c, shift 0) under the row moved by s.  With one phase, or several that hold equal tables, every sample is
+ * the constant entry's row bit for bit.
+ *   weights      device fp32 [P][nnz], may be NULL when nnz = 0     gamma        device fp32 [P][n]
+ *   phase_host   host int32 [L], L >= maxTime, entries 1 .. L-1 in [0, P); entry 0 is never read and travels as 0
+ *   candidates   device int32 [C] (a sample's candidate)             shifts_host  host int32 [C], each >= 0 with
+ *                                                                                shift + maxTime <= L, or NULL: all 0
+ *   rows, R, floor, scores, score_stride: gnode_dmp_source_events_scores_f32's (C counts samples);   init, action, value,
+ *   sizes: gnode_dmp_outbreak_sizes_f32's
+ * The two tables are read back once and validated on the host after every other check has passed: a NaN or an entry outside
+ * [0, 1] is GNODE_ERR_ARG, and the message names the phase and the position.  The tables stay in memory, never in LDS, so the
+ * form and the tile are the constant entries' (gnode_dmp_source_events_tile, gnode_dmp_outbreak_lds_bytes).  Both forms read a
+ * device copy of the phase row and of the shifts: the workspace holds the phase copy [L] and the shifts [C], each rounded up to
+ * 256 bytes, then the constant entry's regions; the queries return 0 where the constant entries' do and for L < maxTime.
+ * GNODE_ERR_ARG: whatever the constant entry refuses, a null phase_host, P < 1, L < maxTime, a phase outside [0, P) at an entry
+ * 1 .. L-1, a shift < 0 or with shift + maxTime > L, a NaN or out-of-range rate; GNODE_ERR_WORKSPACE: a short workspace; nothing
+ * is written to `scores` / `sizes` in either case.  Both entries synchronise `stream` once after staging the host arrays (and
+ * while they validate the tables), so phase_host and shifts_host are done with on return; the kernels are enqueued after that
+ * and not waited for. */
+size_t gnode_dmp_source_events_schedule_workspace_bytes(gnode_graph_t g, int32_t C, int32_t R, int32_t maxTime, int32_t L);
+int gnode_dmp_source_events_scores_schedule_f32(gnode_graph_t g, const float* weights /* device [P][nnz] */,
+                                                const float* gamma /* device [P][n] */, const int32_t* phase_host /* int32 [L] */,
+                                                int32_t P, int32_t L, const int32_t* candidates /* device [C] */,
+                                                const int32_t* shifts_host /* int32 [C] or NULL = all 0 */, int32_t C,
+                                                const int8_t* rows /* device [R][n] */, int32_t R, float floor, int32_t maxTime,
+                                                double* scores /* device fp64, see above */, int64_t score_stride, void* workspace,
+                                                size_t workspace_bytes, void* stream);
+size_t gnode_dmp_outbreak_schedule_workspace_bytes(gnode_graph_t g, int32_t C, int32_t maxTime, int32_t L);
+int gnode_dmp_outbreak_sizes_schedule_f32(gnode_graph_t g, const float* weights /* device [P][nnz] */,
+                                          const float* gamma /* device [P][n] */, const int32_t* phase_host /* int32 [L] */, int32_t P,
+                                          int32_t L, const float* init /* device [n][3] */, const int32_t* candidates /* device [C] */,
+                                          const int32_t* shifts_host /* int32 [C] or NULL = all 0 */, int32_t C, int32_t action,
+                                          const float* value /* device [n] or NULL */, int32_t maxTime,
+                                          double* sizes /* device fp64 [C][maxTime][3] */, void* workspace, size_t workspace_bytes,
+                                          void* stream);
 
 /* ---- mean-field baseline (reference ode_nn.py:214-233) ----
  * `runge_kutta_order4(sir, A, ...)`: dS = -beta (A I) S, dI = beta (A I) S - gamma I,
