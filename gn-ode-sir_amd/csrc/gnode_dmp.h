@@ -1,11 +1,12 @@
-// The DMP recurrence, stated once for the marginals and their reverse sweep (gnode_dmp.hip, and gnode_dmp_schedule.hip,
-// gnode_dmp_schedule_bwd.hip under a rate schedule) and for the candidate sweeps (gnode_dmp_sweep.h: the source scores of
-// gnode_dmp_source.hip, gnode_dmp_source_batch.hip, gnode_dmp_source_events.hip and the outbreak sizes of gnode_dmp_outbreak.hip):
-// the four dmp_* functions below and nothing else, and their reverses, the dmp_rev_* functions after them.  They work on values
-// and on pointers that are already the sample's own, in global memory or in LDS.  The library is built with -ffp-contract=off, so
-// they round as written wherever they are inlined; their operand order is the reference's.  Behind them: the fixed-order fp64
-// sums, the source units' one-hot start and likelihood terms, and the LDS of a one-workgroup kernel.  The candidate sweep itself
-// -- its kernels, workspace, preamble and launches -- is gnode_dmp_sweep.h's.
+// The DMP recurrence, stated once for the marginals and their reverse sweep (gnode_dmp_batch.h: gnode_dmp.hip under constant
+// rates, gnode_dmp_schedule.hip and gnode_dmp_schedule_bwd.hip under a rate schedule) and for the candidate sweeps
+// (gnode_dmp_sweep.h: the source scores of gnode_dmp_source.hip, gnode_dmp_source_batch.hip, gnode_dmp_source_events.hip and
+// the outbreak sizes of gnode_dmp_outbreak.hip): the four dmp_* functions below and nothing else, and their reverses, the
+// dmp_rev_* functions after them.  They work on values and on pointers that are already the sample's own, in global memory or
+// in LDS.  The library is built with -ffp-contract=off, so they round as written wherever they are inlined; their operand order
+// is the reference's.  Behind them: the fixed-order fp64 sums, the source units' one-hot start and likelihood terms, and the
+// LDS of a one-workgroup kernel.  The kernels, workspaces, preambles and launches are gnode_dmp_batch.h's (marginals and
+// gradients) and gnode_dmp_sweep.h's (candidate sweeps).
 #pragma once
 #include "gnode_common.h"
 #include <vector>
@@ -32,9 +33,10 @@ __device__ __forceinline__ void dmp_node_update(float P_k, float ps0_k, float pi
     pi = 1.0f - ps - pr;
 }
 
-// Ps_e and phi_e of this step (in place), theta_e of the NEXT step; `theta` is a reference so that it is loaded where it is used.
-// Two weights (gnode_dmp_schedule.hip, rates that change over time): phi_t is what survived THIS step, so it takes this step's
-// w_e and gamma_u; theta_{t+1} - theta_t is what is transmitted DURING the next step, so it takes the next step's w_next.
+// Ps_e and phi_e of this step (in place), theta_e of the NEXT step; `theta` is a reference so that it is loaded where it is
+// used.  Two weights (rates that change over time; under constant rates both are the edge's one): phi_t is what survived THIS
+// step, so it takes this step's w_e and gamma_u; theta_{t+1} - theta_t is what is transmitted DURING the next step, so it takes
+// the next step's w_next.
 __device__ __forceinline__ void dmp_edge_update(float P_u, float theta_rev, float ps0_u, float w_e, float w_next, float gamma_u, float& phi,
                                                 float& ps, const float& theta, float& theta_next) {
     const float mul = P_u / theta_rev;
@@ -50,12 +52,12 @@ __device__ __forceinline__ void dmp_edge_update(float P_u, float theta_rev, floa
     dmp_edge_update(P_u, theta_rev, ps0_u, w_e, w_e, gamma_u, phi, ps, theta, theta_next);
 }
 
-// The reverse of the recurrence, for gnode_dmp.hip's sweep (constant rates) and gnode_dmp_schedule_bwd.hip's (a schedule); what
-// the adjoints are and why nothing is atomic is told where gnode_dmp.hip's sweep begins.
+// The reverse of the recurrence, for gnode_dmp_batch.h's sweep under constant rates and under a schedule; what the adjoints are
+// and why nothing is atomic is told where that sweep begins.
 // the reverse of dmp_edge_update at step t for one edge: theta_bar is that of theta_{t+1}; phi_bar, q_bar come in as step
 // t + 1 left them and go out for step t - 1.  q_tot (the adjoint of Ps_e of this step) and gamma_part (this edge's share of
-// gamma_bar[src]) are for the node pass.  Two weights and two w_bar targets, as dmp_edge_update has two weights
-// (gnode_dmp_schedule_bwd.hip): theta_{t+1} = theta_t - w_next phi_t gives ITS weight's adjoint, w_bar_next, the term
+// gamma_bar[src]) are for the node pass.  Two weights and two w_bar targets, as dmp_edge_update has two weights:
+// theta_{t+1} = theta_t - w_next phi_t gives ITS weight's adjoint, w_bar_next, the term
 // phi_t theta_bar, and phi_t's own weight and gamma are this step's.  The two targets may be one slot (the phases of steps t and
 // t + 1 are equal, or the rates are constant): the two updates then happen in the order written.
 __device__ __forceinline__ void dmp_rev_edge(float w_e, float w_next, float gamma_u, float phi_t, float phi_prev, float theta_bar,
@@ -170,10 +172,10 @@ __device__ __forceinline__ double dmp_source_event_pick(int o, const DmpSourceEv
     return o == 0 ? l.s : o == 1 ? l.i : o == 2 ? l.r : o == 3 ? l.on : o == 4 ? l.off : 0.0;
 }
 
-// The P tables of a scheduled call (gnode_dmp_schedule.hip, gnode_dmp_schedule_bwd.hip) are probabilities, and they live on the
-// device: they come back once, on the caller's stream (which the call synchronises anyway), and the first entry that is a NaN
-// or outside [0, 1] is named by sample, phase and position.  Nothing has been written when this refuses.  `samples`: 1 for a
-// shared table (stride 0), else B.  Host code.
+// The P tables of a scheduled call (gnode_dmp_batch.h's dmp_stage_schedule, gnode_dmp_sweep.h's dmp_sweep_run) are
+// probabilities, and they live on the device: they come back once, on the caller's stream (which the call synchronises anyway),
+// and the first entry that is a NaN or outside [0, 1] is named by sample, phase and position.  Nothing has been written when
+// this refuses.  `samples`: 1 for a shared table (stride 0), else B.  Host code.
 static inline int dmp_check_rate_tables(const char* who, const char* what, const float* dev, size_t samples, size_t P, size_t len, hipStream_t st) {
     std::vector<float> host(samples * P * len);
     if (host.empty()) return 0;
@@ -189,8 +191,10 @@ __host__ __device__ static inline size_t dmp_align16(size_t x) { return (x + 15)
 static constexpr size_t kDmpLdsLimit = 160 * 1024;      // what a gfx950 workgroup may declare
 
 // The LDS of a one-workgroup kernel's sample, carved from the kernel's dynamic LDS: theta x2, phi, ps, rev over the edges | P,
-// Pi, Pr over the nodes (gnode_dmp_batch_lds_bytes), and `rest`, whatever the kernel declares behind them.  (k_dmp_batch_wg and
-// k_dmp_sched_wg carve the same by hand: through this struct their instruction streams change, and they were to stay.)
+// Pi, Pr over the nodes (gnode_dmp_batch_lds_bytes), and `rest`, whatever the kernel declares behind them.
+// (gnode_dmp_batch.h's k_dmp_batch_wg carves the same by hand, with theta[2] indexed: through this struct, which selects theta,
+// its constant instance takes 23 VGPRs and its scheduled one 24 where both have 22 -- tried when they were restated over a
+// rates policy)
 struct DmpLds {
     float *theta0, *theta1, *phi, *ps;
     int* rev;

@@ -119,19 +119,35 @@ class DmpGraph:
 
 
 class _DmpMarginals(torch.autograd.Function):
-    """gnode_dmp_batch_f32 forward, gnode_dmp_batch_backward_f32 backward; the arguments are `dmp_marginals`', already checked."""
+    """gnode_dmp_batch_f32 forward, gnode_dmp_batch_backward_f32 backward; with `phase` (an int32 host array [maxTime]) their
+    scheduled counterparts, gnode_dmp_batch_schedule_f32 and gnode_dmp_batch_schedule_backward_f32, whose tables hold P phases
+    each: [P, nnz] and [P, n] where the constant call has [nnz] and [n].  The arguments are `dmp_marginals`' or
+    `dmp_marginals_schedule`'s, already checked."""
 
     @staticmethod
-    def forward(ctx, graph, weights, gamma, init, maxTime):
+    def _rates(w, g, n, nnz, phase):
+        """The leading arguments of both entries after the handle -- the tables, their per-sample strides and, under a schedule,
+        the phase row and P -- of the tensors at hand (a pointer is only as good as the tensor it was taken from), and the phases
+        of a table as a shape: () or (P,)."""
+        tables = () if phase is None else (int(g.shape[-2]),)       # between a table's sample and its entries
+        P, shared = int(np.prod(tables)), 1 + len(tables)           # a table of `shared` dimensions serves every sample: stride 0
+        rates = (_lib.ptr(w) if nnz else None, 0 if w.dim() == shared else P * nnz, _lib.ptr(g), 0 if g.dim() == shared else P * n)
+        return rates + (() if phase is None else (_lib.host_ptr(phase), P)), tables
+
+    @staticmethod
+    def forward(ctx, graph, weights, gamma, init, maxTime, phase):
         lib, handle = _lib.load(), graph.graph.handle
         w, g, y0 = weights.detach().contiguous(), gamma.detach().contiguous(), init.detach().contiguous()
         B, n, nnz = y0.shape[0], graph.N, graph.E
+        rates, _ = _DmpMarginals._rates(w, g, n, nnz, phase)
         out = torch.empty((B, maxTime, n, 3), dtype=torch.float32, device=y0.device)
-        ws = torch.empty(lib.gnode_dmp_batch_workspace_bytes(handle, B), dtype=torch.uint8, device=y0.device)
-        ctx.strides = (nnz if w.dim() == 2 else 0, n if g.dim() == 2 else 0)
-        _lib.check(lib.gnode_dmp_batch_f32(handle, _lib.ptr(w) if nnz else None, ctx.strides[0], _lib.ptr(g), ctx.strides[1], _lib.ptr(y0),
-                                           B, maxTime, _lib.ptr(out), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()))
-        ctx.graph, ctx.maxTime = graph, maxTime
+        if phase is None:
+            entry, need = lib.gnode_dmp_batch_f32, lib.gnode_dmp_batch_workspace_bytes(handle, B)
+        else:
+            entry, need = lib.gnode_dmp_batch_schedule_f32, lib.gnode_dmp_batch_schedule_workspace_bytes(handle, B, maxTime)
+        ws = torch.empty(need, dtype=torch.uint8, device=y0.device)
+        _lib.check(entry(handle, *rates, _lib.ptr(y0), B, maxTime, _lib.ptr(out), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()))
+        ctx.graph, ctx.maxTime, ctx.phase = graph, maxTime, phase
         ctx.save_for_backward(w, g, y0, out)
         return out
 
@@ -142,20 +158,24 @@ class _DmpMarginals(torch.autograd.Function):
         graph, T, grad_out = ctx.graph, ctx.maxTime, grad_out.contiguous()
         B, n, nnz = y0.shape[0], graph.N, graph.E
         want_w, want_g, want_i = ctx.needs_input_grad[1:4]
+        rates, tables = _DmpMarginals._rates(w, g, n, nnz, ctx.phase)        # of the saved tensors as autograd hands them back
         new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=y0.device)      # noqa: E731
-        gw = new(B, nnz) if want_w and nnz else None                 # (no edge, no table: an empty tensor has no address)
-        gg, gi = new(B, n) if want_g else None, new(B, n, 3) if want_i else None
+        gw = new(B, *tables, nnz) if want_w and nnz else None        # (no edge, no table: an empty tensor has no address)
+        gg, gi = new(B, *tables, n) if want_g else None, new(B, n, 3) if want_i else None
         if gw is not None or gg is not None or gi is not None:
             lib, handle = _lib.load(), graph.graph.handle
-            ws = torch.empty(lib.gnode_dmp_batch_backward_workspace_bytes(handle, B, T), dtype=torch.uint8, device=y0.device)
-            _lib.check(lib.gnode_dmp_batch_backward_f32(
-                handle, _lib.ptr(w) if nnz else None, ctx.strides[0], _lib.ptr(g), ctx.strides[1], _lib.ptr(y0), B, T, _lib.ptr(out),
-                _lib.ptr(grad_out), _lib.ptr(gw), _lib.ptr(gg), _lib.ptr(gi), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()))
-        if want_w:                                                  # the library returns one row per sample: a shared table sums them
-            gw = torch.zeros_like(w) if gw is None else gw if w.dim() == 2 else gw.sum(0)
-        if want_g and g.dim() == 1:
+            if ctx.phase is None:
+                entry, need = lib.gnode_dmp_batch_backward_f32, lib.gnode_dmp_batch_backward_workspace_bytes(handle, B, T)
+            else:
+                entry, need = lib.gnode_dmp_batch_schedule_backward_f32, lib.gnode_dmp_batch_schedule_backward_workspace_bytes(handle, B, T)
+            ws = torch.empty(need, dtype=torch.uint8, device=y0.device)
+            _lib.check(entry(handle, *rates, _lib.ptr(y0), B, T, _lib.ptr(out), _lib.ptr(grad_out), _lib.ptr(gw), _lib.ptr(gg),
+                             _lib.ptr(gi), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()))
+        if want_w:                                                  # the library returns one block per sample: a shared table sums them
+            gw = torch.zeros_like(w) if gw is None else gw.sum(0) if w.dim() == 1 + len(tables) else gw
+        if want_g and g.dim() == 1 + len(tables):
             gg = gg.sum(0)
-        return None, gw, gg, gi, None
+        return None, gw, gg, gi, None, None
 
 
 def dmp_marginals(graph, weights, gamma, init, maxTime):
@@ -188,49 +208,7 @@ def dmp_marginals(graph, weights, gamma, init, maxTime):
     for t in (weights, gamma, init):
         if not t.is_cuda:
             raise _lib.GnodeError("GN-ODE path: tensor is not on a GPU (no CPU fallback exists)")
-    return _DmpMarginals.apply(graph, weights, gamma, init, T)
-
-
-class _DmpMarginalsSchedule(torch.autograd.Function):
-    """gnode_dmp_batch_schedule_f32 forward, gnode_dmp_batch_schedule_backward_f32 backward; the arguments are
-    `dmp_marginals_schedule`'s, already checked (phase: int32 host array [maxTime])."""
-
-    @staticmethod
-    def forward(ctx, graph, weights, gamma, init, maxTime, phase):
-        lib, handle = _lib.load(), graph.graph.handle
-        w, g, y0 = weights.detach().contiguous(), gamma.detach().contiguous(), init.detach().contiguous()
-        B, n, nnz, P = y0.shape[0], graph.N, graph.E, g.shape[-2]
-        out = torch.empty((B, maxTime, n, 3), dtype=torch.float32, device=y0.device)
-        ws = torch.empty(lib.gnode_dmp_batch_schedule_workspace_bytes(handle, B, maxTime), dtype=torch.uint8, device=y0.device)
-        ctx.strides = (P * nnz if w.dim() == 3 else 0, P * n if g.dim() == 3 else 0)
-        _lib.check(lib.gnode_dmp_batch_schedule_f32(handle, _lib.ptr(w) if nnz else None, ctx.strides[0], _lib.ptr(g), ctx.strides[1],
-                                                    _lib.host_ptr(phase), P, _lib.ptr(y0), B, maxTime, _lib.ptr(out), _lib.ptr(ws),
-                                                    ws.numel(), _lib.stream_ptr()))
-        ctx.graph, ctx.maxTime, ctx.phase, ctx.P = graph, maxTime, phase, P
-        ctx.save_for_backward(w, g, y0, out)
-        return out
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, grad_out):
-        w, g, y0, out = ctx.saved_tensors
-        graph, T, P, grad_out = ctx.graph, ctx.maxTime, ctx.P, grad_out.contiguous()
-        B, n, nnz = y0.shape[0], graph.N, graph.E
-        want_w, want_g, want_i = ctx.needs_input_grad[1:4]
-        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=y0.device)      # noqa: E731
-        gw = new(B, P, nnz) if want_w and nnz else None              # (no edge, no table: an empty tensor has no address)
-        gg, gi = new(B, P, n) if want_g else None, new(B, n, 3) if want_i else None
-        if gw is not None or gg is not None or gi is not None:
-            lib, handle = _lib.load(), graph.graph.handle
-            ws = torch.empty(lib.gnode_dmp_batch_schedule_backward_workspace_bytes(handle, B, T), dtype=torch.uint8, device=y0.device)
-            _lib.check(lib.gnode_dmp_batch_schedule_backward_f32(
-                handle, _lib.ptr(w) if nnz else None, ctx.strides[0], _lib.ptr(g), ctx.strides[1], _lib.host_ptr(ctx.phase), P, _lib.ptr(y0), B, T,
-                _lib.ptr(out), _lib.ptr(grad_out), _lib.ptr(gw), _lib.ptr(gg), _lib.ptr(gi), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()))
-        if want_w:                                                  # the library returns one block per sample: a shared table sums them
-            gw = torch.zeros_like(w) if gw is None else gw if w.dim() == 3 else gw.sum(0)
-        if want_g and g.dim() == 2:
-            gg = gg.sum(0)
-        return None, gw, gg, gi, None, None
+    return _DmpMarginals.apply(graph, weights, gamma, init, T, None)
 
 
 def dmp_marginals_schedule(graph, weights, gamma, init, maxTime, phase):
@@ -289,7 +267,7 @@ def dmp_marginals_schedule(graph, weights, gamma, init, maxTime, phase):
     for t in (weights, gamma, init):
         if not t.is_cuda:
             raise _lib.GnodeError("GN-ODE path: tensor is not on a GPU (no CPU fallback exists)")
-    return _DmpMarginalsSchedule.apply(graph, weights, gamma, init, T, np.ascontiguousarray(steps, dtype=np.int32))
+    return _DmpMarginals.apply(graph, weights, gamma, init, T, np.ascontiguousarray(steps, dtype=np.int32))
 
 
 def _batch_numbers(name, value, shapes, who="dmp_batch"):

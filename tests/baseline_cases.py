@@ -58,6 +58,38 @@ def assert_candidates_parents(entries):
         assert got == dmp_candidates_parent()[key], key
 
 
+def schedule_entry(tensors, workspace_bytes, one_workgroup):
+    """What tests/golden/dmp_schedule_parent.json holds for one scheduled call: per float32 output (None: not returned, a table
+    without entries) its shape and the SHA-256 of its bytes, the workspace the library asked for and whether the one-workgroup
+    form served the graph.  Every output is finite and not all zeros, or there is nothing to hash."""
+    shapes, digests = [], []
+    for t in tensors:
+        if t is None:
+            shapes.append(None); digests.append(None)
+            continue
+        a = np.ascontiguousarray(t.cpu().numpy() if hasattr(t, "cpu") else t)
+        assert a.dtype == np.float32 and np.isfinite(a).all() and a.any()
+        shapes.append(list(a.shape)); digests.append(hashlib.sha256(a.tobytes()).hexdigest())
+    return {"shape": shapes, "sha256": digests, "workspace_bytes": int(workspace_bytes), "one_workgroup": bool(one_workgroup)}
+
+
+@functools.lru_cache(maxsize=None)
+def dmp_schedule_parent():
+    """{key: entry} of tests/golden/dmp_schedule_parent.json (make_golden_dmp_schedule_parent.py says what the keys are); each
+    direction holds an entry of each form."""
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "dmp_schedule_parent.json")) as f:
+        entries = json.load(f)["entries"]
+    for direction in ("forward/", "backward/"):
+        assert {e["one_workgroup"] for k, e in entries.items() if k.startswith(direction)} == {True, False}, direction
+    return entries
+
+
+def assert_schedule_parents(entries):
+    """every (key, entry) that a module's `parent_entries` recomputed is the fixture's: shapes, bits, workspace and form"""
+    for key, got in entries:
+        assert got == dmp_schedule_parent()[key], key
+
+
 def weights(nnz, lo, hi, seed):
     return np.random.default_rng(seed).uniform(lo, hi, size=nnz).astype(np.float32)   # per directed edge: w_uv != w_vu
 

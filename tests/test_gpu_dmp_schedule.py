@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 import schedule_cases as K
-from baseline_cases import DMP_CASES, RTOL, gammas as _gammas, rel as _rel, weights as _weights
+from baseline_cases import DMP_CASES, RTOL, assert_schedule_parents, gammas as _gammas, rel as _rel, schedule_entry, weights as _weights
 from dmp_schedule_model import dmp_sir_schedule
 from sir_cases import dev, dmp_ratio, er_of as _er_of, state as _state, u32 as _u32  # noqa: F401
 
@@ -228,6 +228,33 @@ def test_refusals_leave_out_untouched_and_a_good_call_is_served(name, dev):
     for b in range(B):
         o32 = dmp_sir_schedule(c["rp"], c["ci"], list(Wp), list(Gp), phase, ps[b], T, "float32")
         assert _rel(out[b].cpu().numpy(), o32) <= RTOL
+
+
+# ------------------------------------------------------------------------------------------------------- the parent's bits
+PARENT_CASES = [(name, "per_sample") for name in CASES] + [(name, "shared") for name in ("w_zero", "hub")]
+
+
+def parent_entries(name, tables, dev):
+    """[(key, entry)] of tests/golden/dmp_schedule_parent.json for one case: `sched_out` (per-sample weights and phase-0 gammas,
+    three phases), or one matrix and two different gamma tables alternating, shared by the samples (both strides 0)."""
+    from gnode import _lib
+    from gnode.dmp import dmp_batch
+    from gnode.ode_nn import rate_schedule
+    c, phase, W, G, ps = sched_case(name)
+    T, lib, g = c["T"], _lib.load(), _handle_of(c)
+    if tables == "per_sample":
+        out = sched_out(name)
+    else:
+        out = dmp_batch(_matrix(c["rp"], c["ci"], W[0]), [_state(p) for p in ps], rate_schedule([G[1], G[2]], steps=np.arange(T) % 2), T)
+    return [(f"forward/{name}/{tables}", schedule_entry([out], lib.gnode_dmp_batch_schedule_workspace_bytes(g.handle, 3, T),
+                                                        lib.gnode_dmp_batch_lds_bytes(g.handle) <= LDS_WORKGROUP))]
+
+
+@pytest.mark.parametrize("name,tables", PARENT_CASES)
+def test_outputs_are_the_parents_bits(name, tables, dev):
+    """tests/golden/dmp_schedule_parent.json: what the library of commit 8bd479b returned on an MI355X, when the scheduled
+    marginals had kernels and a host side of their own."""
+    assert_schedule_parents(parent_entries(name, tables, dev))
 
 
 # --------------------------------------------------------------------------------------------------------------- the tree

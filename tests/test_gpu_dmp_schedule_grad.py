@@ -38,7 +38,7 @@ import pytest
 
 import dmp_grad_model as M
 import dmp_schedule_grad_model as S
-from baseline_cases import er as _er, gammas as _gammas, rel as _rel, weights as _weights
+from baseline_cases import assert_schedule_parents, er as _er, gammas as _gammas, rel as _rel, schedule_entry, weights as _weights
 from sir_cases import dev, state as _state  # noqa: F401
 
 pytestmark = pytest.mark.gpu
@@ -386,6 +386,42 @@ def test_refusals_write_nothing_and_a_good_call_is_served(form, dev):
         assert np.array_equal(g.cpu().numpy(), f)
 
 
+# ------------------------------------------------------------------ the parent's bits
+PARENT_CASES = [(g, t) for g in ("last_fit", "first_unfit") for t in ("per_sample", "shared", "P4")] + [("er300_T2", "P2"), ("nnz0", "P3")]
+
+
+def parent_entries(name, tables, dev):
+    """[(key, entry)] of tests/golden/dmp_schedule_parent.json for one call: the three gradients of the graph on each side of the
+    LDS boundary with test_each_side_of_the_lds_boundary's inputs -- per-sample tables, shared ones (sample 0's), and P = 4 where
+    no step names phase 3 --, of er300 at T = 2 with two phases (no edge pass) and of the five nodes without an edge.  The block
+    of a phase that no step names is exact zeros."""
+    if name in ("last_fit", "first_unfit"):
+        rp, ci = form_graphs()[name]
+        T, phase = T_FORMS, PHASE_FORMS
+        W, Gam, init, G = _batch_inputs(rp, ci, 2, 50)
+        if tables == "shared":
+            W, Gam = W[0], Gam[0]
+        elif tables == "P4":
+            W = np.concatenate([W, np.full((2, 1, len(ci)), 0.5, np.float32)], axis=1)
+            Gam = np.concatenate([Gam, np.full((2, 1, len(rp) - 1), 0.5, np.float32)], axis=1)
+    else:
+        c = S.case(name)
+        rp, ci, T, phase, P = c["rp"], c["ci"], c["T"], c["phase"], int(tables[1:])
+        W, Gam, init, G = c["W"][:P], c["Gam"][:P], c["init"][None], c["G"][None]
+    e = Entry(rp, ci, dev)
+    got = e.backward(W, Gam, phase, init, T, e.forward(W, Gam, phase, init, T), G)
+    for p in set(range(np.shape(Gam)[-2])) - set(int(p) for p in phase[1:T]):
+        assert all(g is None or not g[:, p].any() for g in got[:2]), (name, tables, p)
+    return [(f"backward/{name}/{tables}", schedule_entry(got, e.need(init.shape[0], T), e.lds_bytes() <= LDS_WORKGROUP))]
+
+
+@pytest.mark.parametrize("name,tables", PARENT_CASES)
+def test_gradients_are_the_parents_bits(name, tables, dev):
+    """tests/golden/dmp_schedule_parent.json: what the library of commit 8bd479b returned on an MI355X, when the scheduled
+    reverse sweep had kernels and a host side of its own."""
+    assert_schedule_parents(parent_entries(name, tables, dev))
+
+
 # ------------------------------------------------------------------ the Python function
 def _tensors(dev, W, Gam, init, requires=(True, True, True)):
     import torch
@@ -436,6 +472,32 @@ def test_backward_fills_the_inputs_that_require_it(requires, dev):
         assert (t.grad is not None) == r
         if r:
             assert t.grad.shape == t.shape and np.array_equal(t.grad.cpu().numpy(), f)
+
+
+def test_backward_reads_the_saved_tensors_autograd_hands_back(dev):
+    """Under saved-tensor hooks (save_on_cpu) backward receives new allocations, and the forward's are free to be reused: the
+    gradients of both functions are the plain call's bits, with the freed memory overwritten in between.  The tables are
+    products made for the call, so nothing else holds them."""
+    import torch
+    from gnode.dmp import dmp_marginals, dmp_marginals_schedule
+    c = M.case("er300_T8")
+    e = Entry(c["rp"], c["ci"], dev)
+    W, Gam, init, _ = _batch_inputs(c["rp"], c["ci"], 3, 650)
+    G = e.up(np.random.default_rng(651).standard_normal((3, c["T"], e.n, 3)).astype(np.float32))
+    phase, graph = S.spread_phases(c["T"]), _graph(c["rp"], c["ci"])
+    calls = {"schedule": lambda ts: dmp_marginals_schedule(graph, ts[0] * 0.5, ts[1] * 0.5, ts[2], c["T"], phase),
+             "constant": lambda ts: dmp_marginals(graph, ts[0][:, 0] * 0.5, ts[1][:, 0] * 0.5, ts[2], c["T"])}
+    for name, call in calls.items():
+        plain = _tensors(dev, W, Gam, init)
+        (call(plain) * G).sum().backward()
+        hooked = _tensors(dev, W, Gam, init)
+        with torch.autograd.graph.save_on_cpu():
+            out = call(hooked)
+        junk = [torch.full_like(t, 0.5) for t in hooked for _ in range(4)]         # lands where the forward's tables lay
+        (out * G).sum().backward()
+        for a, b in zip(plain, hooked):
+            assert torch.isfinite(b.grad).all() and b.grad.abs().max() > 0 and torch.equal(a.grad, b.grad), name
+        del junk
 
 
 def test_shared_tables_get_the_sum_over_the_samples(dev):

@@ -16,7 +16,10 @@ from gnode import _lib
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--out", default=None, help="append the lines to this file as well")
+ap.add_argument("--lib", default=None, help="load this build of libgnode_hip.so instead of the package's (as tools/bench_dmp_batch.py)")
 opt = ap.parse_args()
+if opt.lib:
+    _lib.LIB_PATH = os.path.abspath(opt.lib)
 from gnode.dmp import DmpGraph, dmp_marginals, dmp_marginals_schedule
 
 SAMPLES, T, PHASES = 16, 30, 4

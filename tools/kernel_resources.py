@@ -24,4 +24,4 @@ for line in out.splitlines():
 for r in rows:
     name = subprocess.run(["c++filt", r["name"]], capture_output=True, text=True).stdout.strip().split("(")[0].replace("void ", "")
     flag = "  <-- SCRATCH" if r.get("ScratchSize [bytes/lane]", "0") != "0" else ""
-    print(f"{name:48s} vgpr {r.get('VGPRs'):>4s} sgpr {r.get('TotalSGPRs'):>4s} vspill {r.get('VGPRs Spill'):>3s} sspill {r.get('SGPRs Spill'):>3s} scratch {r.get('ScratchSize [bytes/lane]'):>4s}{flag}")
+    print(f"{name:48s} vgpr {r.get('VGPRs'):>4s} sgpr {r.get('TotalSGPRs'):>4s} vspill {r.get('VGPRs Spill'):>3s} sspill {r.get('SGPRs Spill'):>3s} scratch {r.get('ScratchSize [bytes/lane]'):>4s} lds {r.get('LDS Size [bytes/block]'):>5s}{flag}")
