@@ -39,6 +39,11 @@
 // the top of the step (sir_step_thr).  The coins do not know the schedule, so one phase gives the per-edge call's counts.
 // Separate instances again: the other forms' step pointers are their kernel arguments, and they compile to what they were
 // (DESIGN 4.12).
+//
+// Outbreak sizes for many candidates (gnode_sir_mc_philox_sweep, the SWEEP instances, INIT and SCHED only): one launch runs C x
+// sims trajectories, trajectory (c, s) from the drawn start with candidate c's node overridden and the phase row read from the
+// candidate's shift on, and leaves integer sums per (candidate, step, compartment) where a TRAJ instance writes a curve -- no
+// histogram, no events, no curves.  The coins do not know the candidate.  Separate instances once more.
 #include "gnode_common.h"
 #include "gnode_sir_plan.h"
 #include <algorithm>
@@ -127,9 +132,63 @@ __device__ __forceinline__ SirThr<NODES> sir_step_thr(SirThr<NODES> base, const 
     if constexpr (SCHED) return base + (size_t)sc.phase[it] * len; else return base;
 }
 
+// SWEEP instances (gnode_sir_mc_philox_sweep; INIT and SCHED ones only): the workgroups' loop runs over C * sims jobs, job j
+// being candidate c = j % C and trajectory s = j / C (sir_sweep_job; DESIGN 4.16 on the order).  Trajectory (c, s) draws the
+// start of `sim` like every INIT instance and then overrides the node cand[c] -- action 0: it starts in I, action 1: in R; an id outside
+// [0, n) matches no node -- reads the phase row from shifts[c] on, and leaves (S_t, I_t, R_t) in sums[c][t] by integer
+// atomic adds where a TRAJ instance writes a row of `curves`, and the number of nodes that were ever infected (the I starts
+// included, the R starts not) in ever[c][s] when `ever` is non-null.  The coins do not know c.  No histogram atomic, no
+// event, no curve.  The others take an empty struct, as with SirTraj, and compile to what they were.
+template <bool SWEEP> struct SirSweep {};
+template <> struct SirSweep<true> {
+    const int32_t* cand; const int32_t* shifts; int C; int action;
+    unsigned long long* sums;   // [C][T][3], accumulated
+    uint32_t* ever;             // [C][sims], overwritten, or null
+};
+// The order of (c, s) within the job index.  0, the choice: candidates interleaved, c = j % C -- the workgroups resident at one
+// time add to the sums of as many candidates as there are, and each workgroup's share of the jobs mixes the candidates.  1:
+// candidate-major, c = j / sims, kept as a build option for the measurement of DESIGN 4.16.  No result depends on it.
+#ifndef GN_SIR_SWEEP_MAJOR
+#define GN_SIR_SWEEP_MAJOR 0
+#endif
+__device__ __forceinline__ void sir_sweep_job(long job, int C, long sims, int& c, long& s) {
+    if (GN_SIR_SWEEP_MAJOR) { c = (int)(job / sims); s = job % sims; } else { c = (int)(job % C); s = job / C; }
+}
+// one event of the [2][T][n] histograms: the SWEEP instances have none
+template <bool SWEEP> __device__ __forceinline__ void sir_hist_add(uint32_t* h) { if constexpr (!SWEEP) atomicAdd(h, 1u); }
+// the start of nodes 4q .. 4q + 3 (sir_init_draw), with the candidate's bit overridden in the SWEEP instances; node < 0: nobody
+template <bool SWEEP>
+__device__ __forceinline__ void sir_start_quad(const unsigned long long* __restrict__ init_thr, int n, int q, uint32_t sim, uint32_t k0,
+                                               uint32_t k1, int node, int action, uint32_t& inf, uint32_t& rec) {
+    sir_init_draw(init_thr, n, q, sim, k0, k1, inf, rec);
+    if constexpr (SWEEP) {
+        if ((node >> 2) == q) {                    // (node = -1: quad -1, never a thread's)
+            const uint32_t bit = 1u << (node & 3);
+            if (action == 0) { inf |= bit; rec &= ~bit; } else { rec |= bit; inf &= ~bit; }
+        }
+    }
+}
+
 __device__ __forceinline__ void sir_curve_row(uint32_t* __restrict__ curves, long s, int T, int row, int n, int n_ever, int n_rec) {
     uint32_t* r = curves + ((size_t)s * T + row) * 3;
     r[0] = (uint32_t)(n - n_ever); r[1] = (uint32_t)(n_ever - n_rec); r[2] = (uint32_t)n_rec;
+}
+// the schedule as job (c, s) reads it: from shifts[c] on in the SWEEP instances, as it is in the others
+template <bool SCHED, bool SWEEP>
+__device__ __forceinline__ SirSched<SCHED> sir_job_sched(const SirSched<SCHED>& sc, const SirSweep<SWEEP>& sw, int c) {
+    if constexpr (SWEEP) { SirSched<SCHED> o = sc; o.phase += sw.shifts[c]; return o; } else return sc;
+}
+// the same row, of candidate c, added to the sums (integer adds commute: exact whatever the order of the jobs)
+__device__ __forceinline__ void sir_sums_row(unsigned long long* __restrict__ sums, int c, int T, int row, int n, int n_ever, int n_rec) {
+    unsigned long long* r = sums + ((size_t)c * T + row) * 3;
+    atomicAdd(&r[0], (unsigned long long)(n - n_ever)); atomicAdd(&r[1], (unsigned long long)(n_ever - n_rec));
+    atomicAdd(&r[2], (unsigned long long)n_rec);
+}
+// where a TRAJ instance writes a row of curves, a SWEEP instance adds it to its candidate's sums
+template <bool SWEEP>
+__device__ __forceinline__ void sir_row_out(uint32_t* __restrict__ curves, const SirSweep<SWEEP>& sw, long s, int c, int T, int row, int n,
+                                            int n_ever, int n_rec) {
+    if constexpr (SWEEP) sir_sums_row(sw.sums, c, T, row, n, n_ever, n_rec); else sir_curve_row(curves, s, T, row, n, n_ever, n_rec);
 }
 
 // p[0 .. count) = val.  p is 2-byte aligned only (a caller's view): 16-byte stores over the aligned body, the < 8 elements
@@ -153,15 +212,17 @@ __global__ __launch_bounds__(256) void k_fill_i16(int16_t* __restrict__ p, size_
 #ifndef GN_SIR_UNROLL
 #define GN_SIR_UNROLL 8
 #endif
-template <bool STATE_IN_LDS, bool NODES, bool TRAJ, bool EDGES = false, bool INIT = false, bool SCHED = false>
+template <bool STATE_IN_LDS, bool NODES, bool TRAJ, bool EDGES = false, bool INIT = false, bool SCHED = false, bool SWEEP = false>
 __global__ __launch_bounds__(1024) void k_sir_philox(const int* __restrict__ src, const int* __restrict__ dst, long nnz,
                                                     int n, const int* __restrict__ seeds, int n_seeds,
                                                     SirThr<NODES> thr_beta, SirThr<NODES> thr_gamma,
                                                     long sims, long sim_offset, int T, uint32_t k0, uint32_t k1,
                                                     uint32_t* __restrict__ hist, uint8_t* __restrict__ gstate, SirTraj<TRAJ> tr,
-                                                    SirInit<INIT> in, SirSched<SCHED> sc) {
+                                                    SirInit<INIT> in, SirSched<SCHED> sc_call, SirSweep<SWEEP> sw) {
     static_assert(NODES || !EDGES, "per-edge infection thresholds come with per-node recovery thresholds");
     static_assert(EDGES || !SCHED, "a schedule switches per-edge tables");
+    static_assert(!SWEEP || (INIT && SCHED && !TRAJ), "the sweep overrides a drawn start and shifts a schedule; its output is the sums");
+    constexpr bool TALLY = TRAJ || SWEEP;         // the trajectory's totals are kept in tcnt
     extern __shared__ uint8_t smem[];
     uint8_t* state = STATE_IN_LDS ? smem : gstate + (size_t)blockIdx.x * 2 * n;
     uint8_t* flag = state + n;
@@ -173,10 +234,15 @@ __global__ __launch_bounds__(1024) void k_sir_philox(const int* __restrict__ src
     __shared__ int tcnt[2];
     int16_t* ev_inf = nullptr; int16_t* ev_rec = nullptr; uint32_t* curves = nullptr;
     if constexpr (TRAJ) { ev_inf = tr.events; if (tr.events) ev_rec = tr.events + (size_t)sims * n; curves = tr.curves; }
-    for (long s = blockIdx.x; s < sims; s += gridDim.x) {
+    long jobs = sims;                             // (SWEEP) C * sims of them, the candidates interleaved
+    if constexpr (SWEEP) jobs = sims * sw.C;
+    for (long job = blockIdx.x; job < jobs; job += gridDim.x) {
+        long s = job; int cj = 0, cnode = -1, cact = 0, rec0 = 0;       // (SWEEP) the candidate, its node and action; the R starts
+        if constexpr (SWEEP) { sir_sweep_job(job, sw.C, sims, cj, s); cnode = sw.cand[cj]; if (cnode >= n) cnode = -1; cact = sw.action; }
+        const SirSched<SCHED> sc = sir_job_sched(sc_call, sw, cj);
         const uint32_t sim = (uint32_t)(sim_offset + s);
         for (int v = threadIdx.x; v < n; v += nthr) { state[v] = ST_S; flag[v] = 0; }
-        if (TRAJ && threadIdx.x < 2) tcnt[threadIdx.x] = 0;
+        if (TALLY && threadIdx.x < 2) tcnt[threadIdx.x] = 0;
         __syncthreads();
         if constexpr (INIT) {
             // drawn start: a node that starts in I or R has left S at step 0 (one infection event), one that starts in R
@@ -184,21 +250,21 @@ __global__ __launch_bounds__(1024) void k_sir_philox(const int* __restrict__ src
             int n_out = 0, n_gone = 0;
             for (int q = threadIdx.x; 4 * q < n; q += nthr) {
                 uint32_t inf, rec;
-                sir_init_draw(in.thr, n, q, sim, k0, k1, inf, rec);
+                sir_start_quad<SWEEP>(in.thr, n, q, sim, k0, k1, cnode, cact, inf, rec);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const int v = 4 * q + j;
                     if (!(((inf | rec) >> j) & 1u)) continue;
                     const bool r = (rec >> j) & 1u;
                     state[v] = r ? ST_R : ST_I;
-                    atomicAdd(&hinf[v], 1u);
-                    if (r) atomicAdd(&hrec[v], 1u);
+                    sir_hist_add<SWEEP>(&hinf[v]);
+                    if (r) sir_hist_add<SWEEP>(&hrec[v]);
                     if (TRAJ && ev_inf) { ev_inf[(size_t)s * n + v] = 0; if (r) ev_rec[(size_t)s * n + v] = 0; }
                 }
                 n_out += __popc(inf | rec); n_gone += __popc(rec);
             }
-            if (TRAJ && n_out) atomicAdd(&tcnt[0], n_out);
-            if (TRAJ && n_gone) atomicAdd(&tcnt[1], n_gone);
+            if (TALLY && n_out) atomicAdd(&tcnt[0], n_out);
+            if (TALLY && n_gone) atomicAdd(&tcnt[1], n_gone);
         } else {
             for (int j = threadIdx.x; j < n_seeds; j += nthr) state[seeds[j]] = ST_I;   // duplicates: same value
         }
@@ -209,15 +275,19 @@ __global__ __launch_bounds__(1024) void k_sir_philox(const int* __restrict__ src
             bool first = true;
             for (int q = 0; q < j; ++q) first = first && (seeds[q] != v);
             if (first) {
-                atomicAdd(&hinf[v], 1u);
+                sir_hist_add<SWEEP>(&hinf[v]);
                 if (TRAJ) atomicAdd(&tcnt[0], 1);
                 if (TRAJ && ev_inf) ev_inf[(size_t)s * n + v] = 0;
             }
         }
-        int rows_done = 1;                          // (TRAJ) rows of `curves` written so far
-        if (TRAJ && curves) {
+        int rows_done = 1;                          // (TRAJ, SWEEP) rows of `curves` / of the sums written so far
+        const bool rows = SWEEP || (TRAJ && curves);
+        if (rows) {
             __syncthreads();
-            if (threadIdx.x == 0) sir_curve_row(curves, s, T, 0, n, tcnt[0], INIT ? tcnt[1] : 0);
+            if (threadIdx.x == 0) {
+                if constexpr (SWEEP) rec0 = tcnt[1];
+                sir_row_out(curves, sw, s, cj, T, 0, n, tcnt[0], INIT ? tcnt[1] : 0);
+            }
         }
         for (int it = 1; it < T; ++it) {
             const SirThr<NODES> tb_step = sir_step_thr<NODES>(thr_beta, sc, it, (size_t)nnz), tg_step = sir_step_thr<NODES>(thr_gamma, sc, it, (size_t)n);
@@ -257,29 +327,30 @@ __global__ __launch_bounds__(1024) void k_sir_philox(const int* __restrict__ src
             for (int v = threadIdx.x; v < n; v += nthr) {
                 const uint8_t f = flag[v];
                 if (f == 1) {
-                    state[v] = ST_I; atomicAdd(&hinf[(size_t)it * n + v], 1u);
-                    if (TRAJ) ++n_new;
+                    state[v] = ST_I; sir_hist_add<SWEEP>(&hinf[(size_t)it * n + v]);
+                    if (TALLY) ++n_new;
                     if (TRAJ && ev_inf) ev_inf[(size_t)s * n + v] = (int16_t)it;
                 } else if (f == 2) {
-                    state[v] = ST_R; atomicAdd(&hrec[(size_t)it * n + v], 1u);
-                    if (TRAJ) ++n_gone;
+                    state[v] = ST_R; sir_hist_add<SWEEP>(&hrec[(size_t)it * n + v]);
+                    if (TALLY) ++n_gone;
                     if (TRAJ && ev_inf) ev_rec[(size_t)s * n + v] = (int16_t)it;
                 }
                 flag[v] = 0;
                 any |= (state[v] == ST_I);
             }
-            if (TRAJ && n_new) atomicAdd(&tcnt[0], n_new);
-            if (TRAJ && n_gone) atomicAdd(&tcnt[1], n_gone);
+            if (TALLY && n_new) atomicAdd(&tcnt[0], n_new);
+            if (TALLY && n_gone) atomicAdd(&tcnt[1], n_gone);
             const int alive = __syncthreads_or(any);
-            if (TRAJ && curves) {                   // (the counters rest until the next step's barrier)
-                if (threadIdx.x == 0) sir_curve_row(curves, s, T, it, n, tcnt[0], tcnt[1]);
+            if (rows) {                             // (the counters rest until the next step's barrier)
+                if (threadIdx.x == 0) sir_row_out(curves, sw, s, cj, T, it, n, tcnt[0], tcnt[1]);
                 rows_done = it + 1;
             }
             if (!alive) break;                      // epidemic over: no further events in this trajectory
         }
-        if (TRAJ && curves) {                       // the rows after an early end repeat the final state
+        if (rows) {                                 // the rows after an early end repeat the final state
             const int n_ever = tcnt[0], n_rec = tcnt[1];
-            for (int r = rows_done + threadIdx.x; r < T; r += nthr) sir_curve_row(curves, s, T, r, n, n_ever, n_rec);
+            for (int r = rows_done + threadIdx.x; r < T; r += nthr) sir_row_out(curves, sw, s, cj, T, r, n, n_ever, n_rec);
+            if constexpr (SWEEP) if (sw.ever && threadIdx.x == 0) sw.ever[(size_t)cj * sims + s] = (uint32_t)(n_ever - rec0);
         }
         __syncthreads();
     }
@@ -298,14 +369,17 @@ __global__ __launch_bounds__(1024) void k_sir_philox(const int* __restrict__ src
 // and the recovery-only phase ask only whether a target is susceptible, so both stay sufficient next to w = 0 entries: a row
 // whose susceptible targets all sit behind zeros keeps being walked.  There is no COUNT && EDGES instance.
 // TRAJ: per-trajectory events and curves (SirTraj above); there is no COUNT && TRAJ instance.
-template <typename IdT, bool LISTS_IN_LDS, bool COUNT, bool NODES, bool TRAJ, bool EDGES = false, bool INIT = false, bool SCHED = false>
+// SWEEP: the candidate sweep (SirSweep above): jobs instead of trajectories, sums instead of histograms.
+template <typename IdT, bool LISTS_IN_LDS, bool COUNT, bool NODES, bool TRAJ, bool EDGES = false, bool INIT = false, bool SCHED = false,
+          bool SWEEP = false>
 __global__ __launch_bounds__(1024) void k_sir_frontier(const int* __restrict__ rowptr, const int* __restrict__ col, int n,
                                                       const int* __restrict__ seeds, int n_seeds,
                                                       SirThr<NODES> thr_beta, SirThr<NODES> thr_gamma,
                                                       long sims, long sim_offset, int T, uint32_t k0, uint32_t k1,
                                                       uint32_t* __restrict__ hist, int32_t* __restrict__ glists,
                                                       unsigned long long* __restrict__ stats, SirTraj<TRAJ> tr, SirInit<INIT> in,
-                                                      SirSched<SCHED> sc) {
+                                                      SirSched<SCHED> sc_call, SirSweep<SWEEP> sw) {
+    static_assert(!SWEEP || (INIT && SCHED && !TRAJ), "the sweep overrides a drawn start and shifts a schedule; its output is the sums");
     static_assert(!(COUNT && INIT), "the counting instantiation starts from a seed list");
     static_assert(EDGES || !SCHED, "a schedule switches per-edge tables");
     static_assert(!(COUNT && TRAJ), "the counting instantiation has no per-trajectory output");
@@ -335,7 +409,12 @@ __global__ __launch_bounds__(1024) void k_sir_frontier(const int* __restrict__ r
     if constexpr (TRAJ) { ev_inf = tr.events; if (tr.events) ev_rec = tr.events + (size_t)sims * n; curves = tr.curves; }
     size_t sched_nnz = 0;                                      // (SCHED) the length of one infection table
     if constexpr (SCHED) sched_nnz = (size_t)rowptr[n];
-    for (long s = blockIdx.x; s < sims; s += gridDim.x) {
+    long jobs = sims;                                          // (SWEEP) C * sims of them, the candidates interleaved
+    if constexpr (SWEEP) jobs = sims * sw.C;
+    for (long job = blockIdx.x; job < jobs; job += gridDim.x) {
+        long s = job; int cj = 0, cnode = -1, cact = 0;        // (SWEEP) the candidate, its node and action
+        if constexpr (SWEEP) { sir_sweep_job(job, sw.C, sims, cj, s); cnode = sw.cand[cj]; if (cnode >= n) cnode = -1; cact = sw.action; }
+        const SirSched<SCHED> sc = sir_job_sched(sc_call, sw, cj);
         const uint32_t sim = (uint32_t)(sim_offset + s);
         for (int w = tid; w < nwords; w += nthr) { bits[w] = 0u; spent[w] = 0u; recb[w] = 0u; }
         if (tid < 3) cnt[tid] = 0;
@@ -349,7 +428,7 @@ __global__ __launch_bounds__(1024) void k_sir_frontier(const int* __restrict__ r
             for (int q0 = 0; q0 < nq; q0 += nthr) {
                 const int q = q0 + tid, u0 = 4 * q;
                 uint32_t inf = 0, rec = 0;
-                if (q < nq) sir_init_draw(in.thr, n, q, sim, k0, k1, inf, rec);
+                if (q < nq) sir_start_quad<SWEEP>(in.thr, n, q, sim, k0, k1, cnode, cact, inf, rec);
                 const uint32_t out = inf | rec;
                 if (out) atomicOr(&bits[u0 >> 5], out << (u0 & 31));
                 if (rec) atomicOr(&recb[u0 >> 5], rec << (u0 & 31));
@@ -357,8 +436,8 @@ __global__ __launch_bounds__(1024) void k_sir_frontier(const int* __restrict__ r
                 for (int j = 0; j < 4; ++j)
                     if ((out >> j) & 1u) {
                         const bool r = (rec >> j) & 1u;
-                        atomicAdd(&hinf[u0 + j], 1u);
-                        if (r) atomicAdd(&hrec[u0 + j], 1u);
+                        sir_hist_add<SWEEP>(&hinf[u0 + j]);
+                        if (r) sir_hist_add<SWEEP>(&hrec[u0 + j]);
                         if (TRAJ && ev_inf) { ev_inf[(size_t)s * n + u0 + j] = 0; if (r) ev_rec[(size_t)s * n + u0 + j] = 0; }
                     }
                 // this wave's I starts: slot = wave base + the I starts of the lanes below + this lane's own in front
@@ -392,8 +471,10 @@ __global__ __launch_bounds__(1024) void k_sir_frontier(const int* __restrict__ r
         int n_ever = INIT ? cnt[2] : n_inf;                // once it reaches n nobody is left to infect: recovery coins only
         __syncthreads();
         if (tid == 0) cnt[2] = n_ever;
-        int rows_done = 1;                                     // (TRAJ) rows of `curves` written so far
-        if (TRAJ && curves && tid == 0) sir_curve_row(curves, s, T, 0, n, n_ever, INIT ? n_ever - n_inf : 0);
+        int rows_done = 1;                                     // (TRAJ, SWEEP) rows of `curves` / of the sums written so far
+        const bool rows = SWEEP || (TRAJ && curves);
+        const int rec0 = n_ever - n_inf;                       // (SWEEP) the R starts: they were never infected
+        if (rows && tid == 0) sir_row_out(curves, sw, s, cj, T, 0, n, n_ever, INIT ? n_ever - n_inf : 0);
         for (int it = 1; it < T && n_inf > 0; ++it) {
             // this step's tables: drain, the recovery loop and the recovery-only branch read nothing else
             const SirThr<NODES> tb_step = sir_step_thr<NODES>(thr_beta, sc, it, sched_nnz), tg_step = sir_step_thr<NODES>(thr_gamma, sc, it, (size_t)n);
@@ -419,7 +500,7 @@ __global__ __launch_bounds__(1024) void k_sir_frontier(const int* __restrict__ r
                     for (int j = 0; j < 4; ++j)
                         if ((nib >> j) & 1u) {
                             if ((unsigned long long)w[j] < sir_thr(tg_step, u0 + j)) {
-                                gone |= 1u << j; atomicAdd(&hrec[(size_t)it * n + u0 + j], 1u);
+                                gone |= 1u << j; sir_hist_add<SWEEP>(&hrec[(size_t)it * n + u0 + j]);
                                 if (TRAJ && ev_inf) ev_rec[(size_t)s * n + u0 + j] = (int16_t)it;
                             } else ++alive;
                         }
@@ -428,9 +509,9 @@ __global__ __launch_bounds__(1024) void k_sir_frontier(const int* __restrict__ r
                 if (alive) atomicAdd(&cnt[0], alive);
                 __syncthreads();
                 n_inf = cnt[0];
-                if (TRAJ && curves) {
+                if (rows) {
                     n_ever = n;
-                    if (tid == 0) sir_curve_row(curves, s, T, it, n, n_ever, n_ever - n_inf);
+                    if (tid == 0) sir_row_out(curves, sw, s, cj, T, it, n, n_ever, n_ever - n_inf);
                     rows_done = it + 1;
                 }
                 __syncthreads();
@@ -443,7 +524,7 @@ __global__ __launch_bounds__(1024) void k_sir_frontier(const int* __restrict__ r
                 if (!(atomicOr(&bits[v >> 5], m) & m)) {       // first edge to reach v this step (it was susceptible)
                     nxt[atomicAdd(&cnt[0], 1)] = (IdT)v;
                     atomicAdd(&cnt[2], 1);
-                    atomicAdd(&hinf[(size_t)it * n + v], 1u);
+                    sir_hist_add<SWEEP>(&hinf[(size_t)it * n + v]);
                     if (TRAJ && ev_inf) ev_inf[(size_t)s * n + v] = (int16_t)it;
                 }
             };
@@ -534,7 +615,7 @@ __global__ __launch_bounds__(1024) void k_sir_frontier(const int* __restrict__ r
                 const unsigned long long tg = sir_thr(tg_step, u);
                 const bool gone = (unsigned long long)philox_coin((uint32_t)u, (uint32_t)it, sim, 1u, k0, k1) < tg;
                 if (gone) {
-                    atomicAdd(&hrec[(size_t)it * n + u], 1u);
+                    sir_hist_add<SWEEP>(&hrec[(size_t)it * n + u]);
                     if (TRAJ && ev_inf) ev_rec[(size_t)s * n + u] = (int16_t)it;
                     atomicOr(&recb[u >> 5], 1u << (u & 31));
                 }
@@ -556,15 +637,16 @@ __global__ __launch_bounds__(1024) void k_sir_frontier(const int* __restrict__ r
             __syncthreads();
             n_inf = cnt[0];
             n_ever = cnt[2];
-            if (TRAJ && curves) {
-                if (tid == 0) sir_curve_row(curves, s, T, it, n, n_ever, n_ever - n_inf);
+            if (rows) {
+                if (tid == 0) sir_row_out(curves, sw, s, cj, T, it, n, n_ever, n_ever - n_inf);
                 rows_done = it + 1;
             }
             IdT* t = cur; cur = nxt; nxt = t;
             __syncthreads();
         }
-        if (TRAJ && curves)                                    // the rows after an early end repeat the final state
-            for (int r = rows_done + tid; r < T; r += nthr) sir_curve_row(curves, s, T, r, n, n_ever, n_ever - n_inf);
+        if (rows)                                              // the rows after an early end repeat the final state
+            for (int r = rows_done + tid; r < T; r += nthr) sir_row_out(curves, sw, s, cj, T, r, n, n_ever, n_ever - n_inf);
+        if constexpr (SWEEP) if (sw.ever && tid == 0) sw.ever[(size_t)cj * sims + s] = (uint32_t)(n_ever - rec0);
     }
     if (COUNT) {
         atomicAdd(&stats[0], st_blocks); atomicAdd(&stats[1], st_ecoins); atomicAdd(&stats[2], st_rcoins); atomicAdd(&stats[3], st_entries);
@@ -692,12 +774,13 @@ __global__ void k_put_seeds(SeedArg sa, int n_seeds, int32_t* __restrict__ seeds
 // The kernels one form of call can launch, by path (SirPath): RATES is SIR_SCALAR / SIR_NODES / SIR_EDGES.  The launch and the
 // registration below both go through sir_dispatch, so an instance cannot be launched without being registered.
 // SCHED_: the four scheduled forms (per-edge rates only, TRAJ x INIT), reached through sir_dispatch_sched.
-template <int RATES, bool TRAJ_, bool INIT_, bool SCHED_ = false> struct SirKernels {
-    static constexpr bool NODES = RATES >= SIR_NODES, EDGES = RATES == SIR_EDGES, TRAJ = TRAJ_, INIT = INIT_, SCHED = SCHED_;
-    static constexpr auto frontier_lds = &k_sir_frontier<uint16_t, true, false, NODES, TRAJ, EDGES, INIT, SCHED>;
-    static constexpr auto frontier_mem = &k_sir_frontier<int32_t, false, false, NODES, TRAJ, EDGES, INIT, SCHED>;
-    static constexpr auto scan_lds = &k_sir_philox<true, NODES, TRAJ, EDGES, INIT, SCHED>;
-    static constexpr auto scan_mem = &k_sir_philox<false, NODES, TRAJ, EDGES, INIT, SCHED>;
+// SWEEP_: the candidate sweep, one form (the drawn-start scheduled one without per-trajectory output), through sir_dispatch_sweep.
+template <int RATES, bool TRAJ_, bool INIT_, bool SCHED_ = false, bool SWEEP_ = false> struct SirKernels {
+    static constexpr bool NODES = RATES >= SIR_NODES, EDGES = RATES == SIR_EDGES, TRAJ = TRAJ_, INIT = INIT_, SCHED = SCHED_, SWEEP = SWEEP_;
+    static constexpr auto frontier_lds = &k_sir_frontier<uint16_t, true, false, NODES, TRAJ, EDGES, INIT, SCHED, SWEEP>;
+    static constexpr auto frontier_mem = &k_sir_frontier<int32_t, false, false, NODES, TRAJ, EDGES, INIT, SCHED, SWEEP>;
+    static constexpr auto scan_lds = &k_sir_philox<true, NODES, TRAJ, EDGES, INIT, SCHED, SWEEP>;
+    static constexpr auto scan_mem = &k_sir_philox<false, NODES, TRAJ, EDGES, INIT, SCHED, SWEEP>;
 };
 // the counting instances (gnode_sir_mc_philox_counted): the frontier walk of SirKernels<SIR_SCALAR, false, false>
 static constexpr auto kSirCountedLds = &k_sir_frontier<uint16_t, true, true, false, false>;
@@ -716,6 +799,7 @@ template <class F> static void sir_dispatch_sched(bool traj, bool init, F&& f) {
     if (traj) { if (init) f(SirKernels<SIR_EDGES, true, true, true>{}); else f(SirKernels<SIR_EDGES, true, false, true>{}); }
     else { if (init) f(SirKernels<SIR_EDGES, false, true, true>{}); else f(SirKernels<SIR_EDGES, false, false, true>{}); }
 }
+template <class F> static void sir_dispatch_sweep(F&& f) { f(SirKernels<SIR_EDGES, false, true, true, true>{}); }
 
 int gn_sir_set_attributes() {       // once per device, from gnode_graph_create
     hipError_t err = hipSuccess;
@@ -727,6 +811,7 @@ int gn_sir_set_attributes() {       // once per device, from gnode_graph_create
         sir_dispatch(form >> 2, form & 2, form & 1, [&](auto K) { lift(K.frontier_lds); lift(K.frontier_mem); lift(K.scan_lds); });
     for (int form = 0; form < 4; ++form)
         sir_dispatch_sched(form & 2, form & 1, [&](auto K) { lift(K.frontier_lds); lift(K.frontier_mem); lift(K.scan_lds); });
+    sir_dispatch_sweep([&](auto K) { lift(K.frontier_lds); lift(K.frontier_mem); lift(K.scan_lds); });
     lift(kSirCountedLds); lift(kSirCountedMem); lift(&k_sir_coins);
     GN_HIP(err);
     return 0;
@@ -851,11 +936,11 @@ static int sir_mc_philox_impl(const SirCall& c) {
                 auto kernel = P.path == SIR_FRONTIER_LDS ? Kt::frontier_lds : Kt::frontier_mem;
                 if constexpr (!Kt::NODES && !Kt::TRAJ && !Kt::INIT) if (stats) kernel = P.path == SIR_FRONTIER_LDS ? kSirCountedLds : kSirCountedMem;
                 hipLaunchKernelGGL(kernel, dim3(P.grid), dim3(P.threads), P.lds, st, g->rowptr, g->col, n, seeds, c.n_seeds, tb, tg, (long)c.sims,
-                                   (long)c.sim_offset, T, k0, k1, hist, (int32_t*)tail, stats, tr, in, sc);
+                                   (long)c.sim_offset, T, k0, k1, hist, (int32_t*)tail, stats, tr, in, sc, SirSweep<false>{});
             } else {
                 auto kernel = P.path == SIR_SCAN_LDS ? Kt::scan_lds : Kt::scan_mem;
                 hipLaunchKernelGGL(kernel, dim3(P.grid), dim3(P.threads), P.lds, st, g->src, g->col, (long)g->nnz, n, seeds, c.n_seeds, tb, tg, (long)c.sims,
-                                   (long)c.sim_offset, T, k0, k1, hist, (uint8_t*)tail, tr, in, sc);
+                                   (long)c.sim_offset, T, k0, k1, hist, (uint8_t*)tail, tr, in, sc, SirSweep<false>{});
             }
         };
         // the drawn start and the schedule are sets of instances of their own: the others do not carry them
@@ -969,6 +1054,68 @@ extern "C" int gnode_sir_mc_philox_schedule(gnode_graph_t g, const int32_t* seed
     c.events = events; c.curves = curves;
     c.sched = true; c.phase = phase_host; c.P = P; c.w_sched = w_host; c.gamma_sched = gamma_host;
     return sir_mc_philox_impl(c);
+}
+
+// Outbreak sizes for many candidates in one launch (SWEEP instances): C x sims trajectories of the drawn-start scheduled form,
+// candidate c's node overridden in the start and its phase row read from shifts[c] on; the sums, no histogram.
+extern "C" size_t gnode_sir_sweep_workspace_bytes(gnode_graph_t g, int32_t T, int32_t P, int32_t L, int32_t C) {
+    return g && T >= 1 && P >= 1 && L >= T && C >= 1 ? sir_sweep_layout(g->info.n, g->nnz, g->n_bigrow, T, P, L, C).total : 0;
+}
+extern "C" int gnode_sir_mc_philox_sweep(gnode_graph_t g, const double* init_host, const int32_t* candidates_host, const int32_t* shifts_host,
+                                         int32_t C, int32_t action, const int32_t* phase_host, int32_t P, int32_t L, const double* w_host,
+                                         const double* gamma_host, int64_t sims, int64_t sim_offset, int32_t T, uint64_t rng_seed,
+                                         uint64_t* sums, uint32_t* ever, void* workspace, size_t workspace_bytes, void* stream,
+                                         int32_t edge_scan) {
+    const char* who = "gnode_sir_mc_philox_sweep";
+    const hipStream_t st = (hipStream_t)stream;
+    GN_CHECK_ARG(g && workspace && init_host && candidates_host && sums, "%s: null pointer", who);
+    GN_CHECK_ARG(P >= 1 && gamma_host && (w_host || g->nnz == 0) && (phase_host || L <= 1), "%s: a schedule takes P >= 1 phases (P = %d), the phase row and both rate tables", who, P);
+    GN_CHECK_ARG(C >= 1, "%s: C = %d: at least one candidate", who, C);
+    GN_CHECK_ARG(action == 0 || action == 1, "%s: action %d is neither 0 (seed) nor 1 (immunise)", who, action);
+    GN_CHECK_ARG(T >= 1 && sims >= 0 && sims <= 0xFFFFFFFFll && sim_offset >= 0 && sim_offset + sims <= 0xFFFFFFFFll, "%s: bad T/sims/sim_offset", who);
+    GN_CHECK_ARG(L >= T, "%s: the phase row holds L = %d entries, fewer than T = %d", who, L, T);
+    const int n = g->info.n;
+    const SirSweepLayout W = sir_sweep_layout(n, g->nnz, g->n_bigrow, T, P, L, C);
+    if (workspace_bytes < W.total) {
+        gnode_set_error("%s: workspace %zu < %zu", who, workspace_bytes, W.total);
+        return GNODE_ERR_WORKSPACE;
+    }
+    const SirThresholds thr = sir_stage_sweep(who, n, g->nnz, T, P, L, phase_host, w_host, gamma_host, init_host, C, shifts_host);
+    GN_CHECK_ARG(thr.error.empty(), "%s", thr.error.c_str());
+    char* ws = (char*)workspace;
+    const unsigned long long *thr_b = (const unsigned long long*)(ws + W.thr), *thr_g = thr_b + (size_t)P * (size_t)g->nnz;
+    const unsigned long long* thr_start = (const unsigned long long*)(ws + W.start);
+    int32_t *phase_dev = (int32_t*)(ws + W.phase), *cand_dev = (int32_t*)(ws + W.cand), *shifts_dev = (int32_t*)(ws + W.shifts);
+    const std::vector<int32_t> no_shift(shifts_host ? 0 : (size_t)C, 0);
+    GN_HIP(hipMemcpyAsync((void*)thr_b, thr.rates.data(), thr.rates.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, st));
+    GN_HIP(hipMemcpyAsync((void*)thr_start, thr.start.data(), thr.start.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, st));
+    if (L > 1) GN_HIP(hipMemcpyAsync(phase_dev, phase_host, sizeof(int32_t) * (size_t)L, hipMemcpyHostToDevice, st));
+    GN_HIP(hipMemcpyAsync(cand_dev, candidates_host, sizeof(int32_t) * (size_t)C, hipMemcpyHostToDevice, st));
+    GN_HIP(hipMemcpyAsync(shifts_dev, shifts_host ? shifts_host : no_shift.data(), sizeof(int32_t) * (size_t)C, hipMemcpyHostToDevice, st));
+    GN_HIP(hipStreamSynchronize(st));                          // the host arrays are done with
+    if (sims == 0) return 0;
+    const uint32_t k0 = (uint32_t)(rng_seed & 0xFFFFFFFFull), k1 = (uint32_t)(rng_seed >> 32);
+    const bool sampled = gn_prof_begin(3, st);
+    const SirLaunch Pl = sir_launch_plan(n, g->n_bigrow, g->info.num_cu, (int64_t)C * sims, edge_scan != 0);
+    void* tail = Pl.path == SIR_FRONTIER_MEM || Pl.path == SIR_SCAN_MEM ? ws + W.tail : nullptr;   // the lists / the state, when not in LDS
+    sir_dispatch_sweep([&](auto K) {
+        using Kt = decltype(K);
+        SirInit<true> in; in.thr = thr_start;
+        SirSched<true> sc; sc.phase = phase_dev;
+        SirSweep<true> sw; sw.cand = cand_dev; sw.shifts = shifts_dev; sw.C = C; sw.action = action; sw.sums = (unsigned long long*)sums; sw.ever = ever;
+        if (Pl.path == SIR_FRONTIER_LDS || Pl.path == SIR_FRONTIER_MEM) {
+            auto kernel = Pl.path == SIR_FRONTIER_LDS ? Kt::frontier_lds : Kt::frontier_mem;
+            hipLaunchKernelGGL(kernel, dim3(Pl.grid), dim3(Pl.threads), Pl.lds, st, g->rowptr, g->col, n, (const int*)nullptr, 0, thr_b, thr_g, (long)sims,
+                               (long)sim_offset, T, k0, k1, (uint32_t*)nullptr, (int32_t*)tail, (unsigned long long*)nullptr, SirTraj<false>{}, in, sc, sw);
+        } else {
+            auto kernel = Pl.path == SIR_SCAN_LDS ? Kt::scan_lds : Kt::scan_mem;
+            hipLaunchKernelGGL(kernel, dim3(Pl.grid), dim3(Pl.threads), Pl.lds, st, g->src, g->col, (long)g->nnz, n, (const int*)nullptr, 0, thr_b, thr_g,
+                               (long)sims, (long)sim_offset, T, k0, k1, (uint32_t*)nullptr, (uint8_t*)tail, SirTraj<false>{}, in, sc, sw);
+        }
+    });
+    if (sampled) gn_prof_end(3, st);
+    GN_LAUNCH_CHECK();
+    return 0;
 }
 
 extern "C" int gnode_sir_mc_coins(const int32_t* table_src, const int32_t* table_dst, int64_t n_table, int32_t n,

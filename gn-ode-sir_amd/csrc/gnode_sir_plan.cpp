@@ -158,3 +158,28 @@ SirThresholds sir_stage_schedule(const char* who, int n, int64_t nnz, int T, int
     }
     return t;
 }
+
+SirSweepLayout sir_sweep_layout(int n, int64_t nnz, int n_bigrow, int T, int P, int L, int C) {
+    const SirScheduleLayout S = sir_schedule_layout(n, nnz, n_bigrow, T, P);
+    const size_t ids = al((size_t)std::max(C, 1) * sizeof(int32_t));
+    SirSweepLayout W;
+    W.rows = 0;                                                    // (S.rows is where the histogram and the seed list end)
+    W.tail = S.tail - S.rows;
+    W.thr = S.thr - S.rows;
+    W.start = S.start - S.rows;
+    W.phase = S.phase - S.rows;
+    W.cand = W.phase + al((size_t)std::max(L, 1) * sizeof(int32_t));
+    W.shifts = W.cand + ids;
+    W.total = W.shifts + ids;
+    return W;
+}
+
+SirThresholds sir_stage_sweep(const char* who, int n, int64_t nnz, int T, int P, int L, const int32_t* phase, const double* w,
+                              const double* gamma, const double* init, int C, const int32_t* shifts) {
+    char buf[256];
+    if (L < T) return refuse("%s: the phase row holds L = %d entries, fewer than T = %d", who, L, T);
+    for (int c = 0; shifts && c < C; ++c)
+        if (shifts[c] < 0 || (int64_t)shifts[c] + T > L)
+            return refuse("%s: shifts[%d] = %d: a shift is >= 0 with shift + T <= L (T = %d, L = %d)", who, c, shifts[c], T, L);
+    return sir_stage_schedule(who, n, nnz, L, P, phase, w, gamma, init);
+}

@@ -64,3 +64,19 @@ SirScheduleLayout sir_schedule_layout(int n, int64_t nnz, int n_bigrow, int T, i
 // phase and the position.  rates = [P * nnz infection thresholds | P * n recovery thresholds].
 SirThresholds sir_stage_schedule(const char* who, int n, int64_t nnz, int T, int P, const int32_t* phase, const double* w, const double* gamma,
                                  const double* init);
+
+// Outbreak sizes for many candidates in one launch (gnode_sir_mc_philox_sweep): C x sims trajectories of the drawn-start
+// scheduled form, candidate c reading the phase row from shifts[c] on.  No histogram and no seed list: the layout is
+// sir_schedule_layout's from `rows` on -- rows, tail, the P tables, the start thresholds -- then the int32 [L] phase row, the
+// int32 [C] candidate ids and the int32 [C] shifts.
+struct SirSweepLayout {
+    size_t rows, tail, thr, start;   // as in SirScheduleLayout, moved down by the histogram and the seed list
+    size_t phase;                    // int32 [L]
+    size_t cand, shifts;             // int32 [C] each
+    size_t total;                    // the workspace of the sweep
+};
+SirSweepLayout sir_sweep_layout(int n, int64_t nnz, int n_bigrow, int T, int P, int L, int C);
+// The sweep's checks, then sir_stage_schedule over the whole phase row (T = L there): L >= T; every shift (shifts may be null:
+// all 0) is >= 0 with shift + T <= L; phase[1 .. L-1] in [0, P).  A refusal names `who` and the offending index.
+SirThresholds sir_stage_sweep(const char* who, int n, int64_t nnz, int T, int P, int L, const int32_t* phase, const double* w,
+                              const double* gamma, const double* init, int C, const int32_t* shifts);

@@ -534,6 +534,110 @@ def sir_curves_from_events(t_inf: torch.Tensor, t_rec: torch.Tensor, T: int) -> 
     return torch.stack([n - ci, ci - cr, cr], dim=2)
 
 
+class SirOutbreakSizes(NamedTuple):
+    """What `outbreak_sizes_mc` returns."""
+    sums: torch.Tensor              # int64 [C, T, 3]: (S_t, I_t, R_t) summed over the trajectories of each candidate
+    ever: torch.Tensor | None       # int32 [C, sims]: nodes ever infected in each trajectory; None unless per_trajectory
+    sims: int                       # the trajectories per candidate of THIS call
+
+    def sizes(self) -> torch.Tensor:
+        """float64 [C, T, 3] = sums / sims: the table `gnode.dmp.outbreak_sizes` gives, from the Monte-Carlo; `gnode.dmp.infections`
+        reads it unchanged.  (After accumulating shards into one `sums`, divide by the total yourself.)"""
+        return self.sums.double() / float(self.sims)
+
+
+class _HostGraph:
+    """n, nnz and the host CSR of a graph argument, before any graph handle exists."""
+
+    def __init__(self, graph):
+        self.n, rp, ci = _host_csr(graph)
+        self.rowptr, self.col, self.nnz = rp, ci, int(ci.shape[0])
+
+
+def _whole(who, name, value, lowest):
+    if isinstance(value, (bool, str)) or not isinstance(value, (int, float, np.integer, np.floating)) or value != int(value) or value < lowest:
+        raise ValueError(f"{who}: {name} must be a whole number >= {lowest}, got {value!r}")
+    return int(value)
+
+
+_MC_ACTIONS = {"seed": 0, "immunise": 1}
+
+
+def outbreak_sizes_mc(graph, beta, gamma, sims, maxTime, candidates=None, action="seed", start=None, shifts=None, rng_seed=None,
+                      sim_offset=0, per_trajectory=False, edge_scan=False, device="cuda", sums: torch.Tensor | None = None) -> SirOutbreakSizes:
+    """`gnode.dmp.outbreak_sizes` / `outbreak_sizes_schedule` by Monte-Carlo, every candidate in ONE launch: for each candidate
+    node c, the compartment sizes over time of `sims` trajectories that start from `start` with c alone changed --
+    action="seed": c starts infected; action="immunise": c starts removed.  Returns `SirOutbreakSizes(sums, ever, sims)`:
+    sums int64 [C, maxTime, 3] on the GPU, sums[c, t] = (S_t, I_t, R_t) added over the trajectories (row 0 is the start after
+    the change; exact integers, whatever the launch geometry); ever int32 [C, sims] when per_trajectory=True, the number of nodes
+    of each trajectory that were ever infected (I starts count, R starts do not), else None.  `.sizes()` is sums / sims, the
+    table DMP approximates; `gnode.dmp.infections` reads it.  DMP is exact on trees only: this is the ground truth to hold its
+    ranking against on a graph with loops.
+
+    Trajectory s of every candidate draws the coins of sim_offset + s: the candidates are compared on common random numbers,
+    and a candidate's rows do not depend on the other candidates.  graph: a DeviceGraph, a networkx graph or a (rowptr, col)
+    pair.  beta / gamma: everything `sir_trajectories` takes -- numbers, per-node arrays, `EdgeRates`, a `RateSchedule` of them.
+    start: None (everybody susceptible), a seed list or an `InitialState`; "immunise" needs some infected mass in it.
+    candidates: node ids (repeats allowed), every node by default; -1 means "no change".  shifts: None, or one whole number >= 0
+    per candidate: step t of candidate c's run is governed by the schedules' step shifts[c] + t (they are read up to step
+    max(shifts) + maxTime - 1), while the coins stay those of the run's own step t.  sums=: an int64 [C, maxTime, 3] tensor to
+    ACCUMULATE into, for shards of the sims range (sim_offset).  edge_scan=True runs the edge-parallel kernel (same integers).
+    Through `gnode_sir_mc_philox_sweep`, which synchronises the stream.  What is wrong raises ValueError before the library is
+    loaded or a graph handle is made."""
+    who = "outbreak_sizes_mc"
+    made = hasattr(graph, "handle")                                 # a DeviceGraph: it carries its host CSR
+    host = graph if made else _HostGraph(graph)
+    n = int(host.n)
+    T, sims, sim_offset = _whole(who, "maxTime", maxTime, 1), _whole(who, "sims", sims, 0), _whole(who, "sim_offset", sim_offset, 0)
+    if sim_offset + sims > 0xFFFFFFFF:
+        raise ValueError(f"{who}: sim_offset + sims = {sim_offset + sims} exceeds 2^32 - 1 trajectories")
+    if action not in _MC_ACTIONS:
+        raise ValueError(f"{who}: action must be one of {sorted(_MC_ACTIONS)}, got {action!r}")
+    if isinstance(start, InitialState):
+        base = _init_for(start, n)
+    else:
+        base = InitialState.from_sets(n, [] if start is None else _whole_numbers(who, "start", start))    # (a seed outside the graph: ValueError)
+    if action == "immunise" and not (base.p[:, 1] > 0.0).any():
+        raise ValueError(f"{who}: nothing to immunise against: the start holds no infected mass")
+    cand = np.arange(n, dtype=np.int64) if candidates is None else _whole_numbers(who, "candidates", candidates)
+    if cand.size < 1:
+        raise ValueError(f"{who}: need at least one candidate")
+    if cand.min() < -1 or cand.max() >= n:
+        raise ValueError(f"{who}: candidate {int(cand[(cand < -1) | (cand >= n)][0])} is not in [-1, {n})")
+    C_ = int(cand.size)
+    if shifts is None:
+        sh = np.zeros(C_, dtype=np.int64)
+    else:
+        sh = _whole_numbers(who, "shifts", shifts)
+        if sh.shape[0] != C_:
+            raise ValueError(f"{who}: {C_} candidates need {C_} shifts, got {sh.shape[0]}")
+        if sh.min() < 0:
+            raise ValueError(f"{who}: shift {int(sh.min())} is negative: a run starts at calendar step 0 or later")
+    L = int(sh.max()) + T
+    if L > 2**31 - 1:
+        raise ValueError(f"{who}: max(shifts) + maxTime = {L} does not fit an int32")
+    sched = _scheduled_rates(beta, gamma, host, L)                  # constants become one phase
+    if sums is not None and (not isinstance(sums, torch.Tensor) or sums.dtype != torch.int64 or tuple(sums.shape) != (C_, T, 3)
+                             or not sums.is_contiguous()):
+        raise ValueError(f"{who}: sums must be a contiguous int64 tensor of shape {(C_, T, 3)}")
+    if rng_seed is None:
+        rng_seed = int(torch.randint(0, 2**62, (1,), dtype=torch.int64).item())
+    g = graph if made else _device_graph_for(graph) if hasattr(graph, "number_of_nodes") else DeviceGraph(host.rowptr, host.col)
+    lib = _lib.load()
+    dev = sums.device if sums is not None else device
+    if sums is None:
+        sums = torch.zeros((C_, T, 3), dtype=torch.int64, device=dev)
+    ever = torch.empty((C_, sims), dtype=torch.int32, device=dev) if per_trajectory else None
+    if sims > 0:
+        cand32, sh32 = np.ascontiguousarray(cand, dtype=np.int32), np.ascontiguousarray(sh, dtype=np.int32)
+        ws = torch.empty(lib.gnode_sir_sweep_workspace_bytes(g.handle, T, sched.P, L, C_), dtype=torch.uint8, device=dev)
+        _lib.check(lib.gnode_sir_mc_philox_sweep(g.handle, _lib.host_ptr(base.p), _lib.host_ptr(cand32), _lib.host_ptr(sh32), C_, _MC_ACTIONS[action],
+                                                 _lib.host_ptr(sched.phase), sched.P, L, _lib.host_ptr(sched.W), _lib.host_ptr(sched.G), sims,
+                                                 sim_offset, T, C.c_uint64(int(rng_seed) & (2**64 - 1)), _lib.ptr(sums), _lib.ptr(ever), _lib.ptr(ws),
+                                                 ws.numel(), _lib.stream_ptr(), int(bool(edge_scan))))
+    return SirOutbreakSizes(sums, ever, sims)
+
+
 def sir_counts_counted(graph: DeviceGraph, seed_set, beta, gamma, sims, T, rng_seed, sim_offset=0, device="cuda"):
     """`sir_counts` through the kernel's profiling instantiation: (counts, stats) with stats = what the launch did --
     Philox blocks computed, infection coins drawn, recovery coins drawn, CSR entries read (bench.py's `sir` roofline)."""

@@ -476,6 +476,43 @@ int gnode_sir_mc_philox_schedule(gnode_graph_t g,
                                  int64_t sims, int64_t sim_offset, int32_t T, uint64_t rng_seed,
                                  int16_t* events, uint32_t* curves, uint32_t* counts,
                                  void* workspace, size_t workspace_bytes, void* stream, int32_t edge_scan);
+/* Outbreak sizes for many candidates in one launch (no version step: a stale library is known by the missing symbol): C x sims
+ * trajectories of gnode_sir_mc_philox_schedule's drawn-start form, the Monte-Carlo counterpart of
+ * gnode_dmp_outbreak_sizes_schedule_f32.  Trajectory (c, s) draws the start of trajectory sim_offset + s from init_host, as
+ * gnode_sir_mc_philox_init does, and then node candidates_host[c] alone is changed -- action 0 (seed): it starts in I; action 1
+ * (immunise): it starts in R, t_inf = t_rec = 0, never infected and never infecting, as every R start.  An id outside [0, n)
+ * matches no node and gives the start as drawn; -1 is the documented spelling.  Repeated ids are allowed.  Step t = 1 .. T-1 of
+ * (c, s) reads the tables of phase_host[shifts_host[c] + t], while its coins stay keyed by the run's own t: (c, shift k) under a
+ * phase row equals (c, shift 0) under the row moved by k, integer for integer.  The coin of (position, step, sim, kind) does not
+ * know c, so candidates are compared on common random numbers.
+ *   phase_host  host int32 [L], L >= T; entries 1 .. L-1 in [0, P) (entry 0 is never read); w_host [P][nnz], gamma_host [P][n]
+ *               as in gnode_sir_mc_philox_schedule
+ *   shifts_host host int32 [C], each >= 0 with shift + T <= L, or NULL: all 0
+ *   sums        device uint64 [C][T][3], ACCUMULATED by integer atomic adds: sums[c][t] += (S_t, I_t, R_t) of every trajectory of
+ *               c; row 0 is the start after the override, rows after an early end of the epidemic repeat the final state.
+ *               Integer adds commute: the result is exact and does not depend on the order of the jobs, the grid or the path,
+ *               and shards of the sims range add up.
+ *   ever        device uint32 [C][sims], OVERWRITTEN, or NULL: the number of nodes of trajectory (c, s) that were infected at
+ *               any step 0 .. T-1; nodes that start in I count, nodes that start in R (the immunised candidate included) do
+ *               not.  Hence sum_s ever[c][s] = sums[c][T-1][1] + sums[c][T-1][2] - sums[c][0][2] of the same call.
+ * No histogram, no events and no curves are allocated or written.  GNODE_ERR_ARG: what gnode_sir_mc_philox_schedule refuses,
+ * C < 1, an action other than 0 or 1, L < T, a shift that is negative or reaches past L, a phase outside [0, P) anywhere in
+ * 1 .. L-1; GNODE_ERR_WORKSPACE: a workspace shorter than gnode_sir_sweep_workspace_bytes(g, T, P, L, C) -- the scheduled call's
+ * layout without the histogram and the seed list, with an int32 [L] phase row and the int32 [C] candidates and shifts behind it;
+ * the query answers 0 for a null handle, T < 1, P < 1, L < T or C < 1.  A refused call writes nothing.  sims = 0 is valid and
+ * touches neither output.  SYNCHRONISES `stream`, because host arrays are staged.  edge_scan as above. */
+size_t gnode_sir_sweep_workspace_bytes(gnode_graph_t g, int32_t T, int32_t P, int32_t L, int32_t C);
+int gnode_sir_mc_philox_sweep(gnode_graph_t g, const double* init_host,          /* host fp64 [n][3] */
+                              const int32_t* candidates_host,                    /* host [C] */
+                              const int32_t* shifts_host,                        /* host [C], or NULL: all 0 */
+                              int32_t C, int32_t action,
+                              const int32_t* phase_host, int32_t P, int32_t L,   /* host [L] */
+                              const double* w_host,                              /* host fp64 [P][nnz] */
+                              const double* gamma_host,                          /* host fp64 [P][n] */
+                              int64_t sims, int64_t sim_offset, int32_t T, uint64_t rng_seed,
+                              uint64_t* sums,     /* device [C][T][3], ACCUMULATED */
+                              uint32_t* ever,     /* device [C][sims], OVERWRITTEN, or NULL */
+                              void* workspace, size_t workspace_bytes, void* stream, int32_t edge_scan);
 int gnode_sir_mc_coins(const int32_t* table_src, const int32_t* table_dst, int64_t n_table, int32_t n,
                        const int32_t* seeds_host, int32_t n_seeds, double beta, double gamma, int64_t sims,
                        int32_t T, const double* coins, int64_t n_coins, uint32_t* counts,
