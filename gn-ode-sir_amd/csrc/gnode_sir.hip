@@ -44,6 +44,11 @@
 // sims trajectories, trajectory (c, s) from the drawn start with candidate c's node overridden and the phase row read from the
 // candidate's shift on, and leaves integer sums per (candidate, step, compartment) where a TRAJ instance writes a curve -- no
 // histogram, no events, no curves.  The coins do not know the candidate.  Separate instances once more.
+//
+// Source scores (gnode_sir_mc_philox_sweep_scores, the SCORE instances, SWEEP ones only): the sweep's trajectories, the state at
+// every step compared with up to GN_SIR_SCORE_MAXO observed snapshots by two integer tallies per snapshot in LDS, and where the
+// sweep adds a row to its sums, one count into a histogram of binned similarities per (snapshot, candidate, step).  Separate
+// instances again; the sweep's compile to what they were.
 #include "gnode_common.h"
 #include "gnode_sir_plan.h"
 #include <algorithm>
@@ -184,6 +189,60 @@ __device__ __forceinline__ void sir_sums_row(unsigned long long* __restrict__ su
     atomicAdd(&r[0], (unsigned long long)(n - n_ever)); atomicAdd(&r[1], (unsigned long long)(n_ever - n_rec));
     atomicAdd(&r[2], (unsigned long long)n_rec);
 }
+// SCORE instances (gnode_sir_mc_philox_sweep_scores; SWEEP ones only): the sweep's jobs, each step of each compared with O
+// snapshots of the epidemic (obs, node-major int8 [n][O]: -1 not observed, 0 / 1 / 2 = S / I / R).  Two integer tallies per
+// snapshot live in LDS (`tal`, below) and move at the sites that hold an event -- the sites of sir_hist_add: a node leaves S
+// (sir_score_event<.., 0>), a node recovers (<.., 1>); an R start is both.  Where a SWEEP instance adds a row to the sums, a
+// SCORE instance adds ONE to hist[o][c][row][k], uint64 [O][C][T][bins + 1], k the binned similarity of the state with snapshot o:
+//   measure 0, Jaccard:  tal[o] = inter = |left S & obs in {1, 2}|, tal[MAXO + o] = pos = |left S & observed|;
+//                        k = inter * bins / (marked[o] + pos - inter), marked[o] = |obs in {1, 2}|
+//   measure 1, match:    tal[o] = agree = |observed & obs == state|, from seen[o] - marked[o] (the zeros: everybody in S) on;
+//                        k = agree * bins / seen[o], seen[o] = |observed|
+// in 64-bit integer division, k = bins for a zero denominator: k = bins exactly when state and snapshot agree completely.  No
+// sums, no ever.  The others take an empty struct, as with SirSweep, and compile to what they were.
+template <bool SCORE> struct SirScore {};
+template <> struct SirScore<true> {
+    const int8_t* obs; const int32_t* marked; const int32_t* seen; int O; int measure; int bins;
+    unsigned long long* hist;   // [O][C][T][bins + 1], accumulated
+};
+// the tallies of a job before its start is drawn: threads 0 .. 2 MAXO - 1, in front of the barrier that resets the counters
+template <bool SCORE> __device__ __forceinline__ void sir_score_reset(const SirScore<SCORE>& sr, int* tal, int tid) {
+    if constexpr (SCORE)
+        if (tid < 2 * GN_SIR_SCORE_MAXO) tal[tid] = (sr.measure == 1 && tid < sr.O) ? sr.seen[tid] - sr.marked[tid] : 0;
+}
+// KIND 0: node v leaves S (it enters I); KIND 1: it recovers (I to R)
+template <bool SCORE, int KIND> __device__ __forceinline__ void sir_score_event(const SirScore<SCORE>& sr, int* tal, int v) {
+    if constexpr (SCORE) {
+        if (KIND == 1 && sr.measure == 0) return;               // the Jaccard sets do not know a recovery
+        const int8_t* ob = sr.obs + (size_t)v * sr.O;
+        for (int o = 0; o < sr.O; ++o) {
+            const int x = ob[o];
+            if (sr.measure == 0) {
+                if (x >= 0) { atomicAdd(&tal[GN_SIR_SCORE_MAXO + o], 1); if (x >= 1) atomicAdd(&tal[o], 1); }
+            } else {
+                const int d = KIND == 0 ? (x == 1) - (x == 0) : (x == 2) - (x == 1);
+                if (d) atomicAdd(&tal[o], d);
+            }
+        }
+    }
+}
+// one trajectory's row `row` against snapshot o: its bin, counted (integer adds commute: exact whatever the order of the jobs)
+__device__ __forceinline__ void sir_score_cell(const SirScore<true>& sr, const int* tal, int C, int c, int T, int row, int o) {
+    unsigned long long num = (unsigned long long)tal[o], den;
+    if (sr.measure == 0) den = (unsigned long long)(sr.marked[o] + tal[GN_SIR_SCORE_MAXO + o]) - num; else den = (unsigned long long)sr.seen[o];
+    const unsigned long long k = den ? num * (unsigned long long)sr.bins / den : (unsigned long long)sr.bins;
+    atomicAdd(&sr.hist[(((size_t)o * C + c) * T + row) * ((size_t)sr.bins + 1) + k], 1ull);
+}
+// where the others put out a row between two barriers from thread 0, a SCORE instance counts the row's bin of snapshot o from
+// thread o ...
+__device__ __forceinline__ void sir_score_row(const SirScore<true>& sr, const int* tal, int C, int c, int T, int row, int tid) {
+    if (tid < sr.O) sir_score_cell(sr, tal, C, c, T, row, tid);
+}
+// ... and the rows after an early end, which repeat the final bin, are spread over the threads as the others' are
+__device__ __forceinline__ void sir_score_rows_after(const SirScore<true>& sr, const int* tal, int C, int c, int T, int from, int tid, int nthr) {
+    for (int r = from + tid; r < T; r += nthr)
+        for (int o = 0; o < sr.O; ++o) sir_score_cell(sr, tal, C, c, T, r, o);
+}
 // where a TRAJ instance writes a row of curves, a SWEEP instance adds it to its candidate's sums
 template <bool SWEEP>
 __device__ __forceinline__ void sir_row_out(uint32_t* __restrict__ curves, const SirSweep<SWEEP>& sw, long s, int c, int T, int row, int n,
@@ -212,16 +271,18 @@ __global__ __launch_bounds__(256) void k_fill_i16(int16_t* __restrict__ p, size_
 #ifndef GN_SIR_UNROLL
 #define GN_SIR_UNROLL 8
 #endif
-template <bool STATE_IN_LDS, bool NODES, bool TRAJ, bool EDGES = false, bool INIT = false, bool SCHED = false, bool SWEEP = false>
+template <bool STATE_IN_LDS, bool NODES, bool TRAJ, bool EDGES = false, bool INIT = false, bool SCHED = false, bool SWEEP = false,
+          bool SCORE = false>
 __global__ __launch_bounds__(1024) void k_sir_philox(const int* __restrict__ src, const int* __restrict__ dst, long nnz,
                                                     int n, const int* __restrict__ seeds, int n_seeds,
                                                     SirThr<NODES> thr_beta, SirThr<NODES> thr_gamma,
                                                     long sims, long sim_offset, int T, uint32_t k0, uint32_t k1,
                                                     uint32_t* __restrict__ hist, uint8_t* __restrict__ gstate, SirTraj<TRAJ> tr,
-                                                    SirInit<INIT> in, SirSched<SCHED> sc_call, SirSweep<SWEEP> sw) {
+                                                    SirInit<INIT> in, SirSched<SCHED> sc_call, SirSweep<SWEEP> sw, SirScore<SCORE> sr) {
     static_assert(NODES || !EDGES, "per-edge infection thresholds come with per-node recovery thresholds");
     static_assert(EDGES || !SCHED, "a schedule switches per-edge tables");
     static_assert(!SWEEP || (INIT && SCHED && !TRAJ), "the sweep overrides a drawn start and shifts a schedule; its output is the sums");
+    static_assert(!SCORE || SWEEP, "the scores are tallied over the sweep's jobs");
     constexpr bool TALLY = TRAJ || SWEEP;         // the trajectory's totals are kept in tcnt
     extern __shared__ uint8_t smem[];
     uint8_t* state = STATE_IN_LDS ? smem : gstate + (size_t)blockIdx.x * 2 * n;
@@ -232,6 +293,7 @@ __global__ __launch_bounds__(1024) void k_sir_philox(const int* __restrict__ src
     // TRAJ: the scan has no counters of its own -- [0] ever infected, [1] recovered, of the trajectory in hand (static LDS:
     // the dynamic size is what the host's occupancy choice is computed from)
     __shared__ int tcnt[2];
+    __shared__ int tal[SCORE ? 2 * GN_SIR_SCORE_MAXO : 1];      // (SCORE) the tallies of SirScore; the others never name it
     int16_t* ev_inf = nullptr; int16_t* ev_rec = nullptr; uint32_t* curves = nullptr;
     if constexpr (TRAJ) { ev_inf = tr.events; if (tr.events) ev_rec = tr.events + (size_t)sims * n; curves = tr.curves; }
     long jobs = sims;                             // (SWEEP) C * sims of them, the candidates interleaved
@@ -243,6 +305,7 @@ __global__ __launch_bounds__(1024) void k_sir_philox(const int* __restrict__ src
         const uint32_t sim = (uint32_t)(sim_offset + s);
         for (int v = threadIdx.x; v < n; v += nthr) { state[v] = ST_S; flag[v] = 0; }
         if (TALLY && threadIdx.x < 2) tcnt[threadIdx.x] = 0;
+        sir_score_reset(sr, tal, (int)threadIdx.x);
         __syncthreads();
         if constexpr (INIT) {
             // drawn start: a node that starts in I or R has left S at step 0 (one infection event), one that starts in R
@@ -259,6 +322,8 @@ __global__ __launch_bounds__(1024) void k_sir_philox(const int* __restrict__ src
                     state[v] = r ? ST_R : ST_I;
                     sir_hist_add<SWEEP>(&hinf[v]);
                     if (r) sir_hist_add<SWEEP>(&hrec[v]);
+                    sir_score_event<SCORE, 0>(sr, tal, v);
+                    if (r) sir_score_event<SCORE, 1>(sr, tal, v);
                     if (TRAJ && ev_inf) { ev_inf[(size_t)s * n + v] = 0; if (r) ev_rec[(size_t)s * n + v] = 0; }
                 }
                 n_out += __popc(inf | rec); n_gone += __popc(rec);
@@ -284,6 +349,7 @@ __global__ __launch_bounds__(1024) void k_sir_philox(const int* __restrict__ src
         const bool rows = SWEEP || (TRAJ && curves);
         if (rows) {
             __syncthreads();
+            if constexpr (SCORE) sir_score_row(sr, tal, sw.C, cj, T, 0, (int)threadIdx.x); else
             if (threadIdx.x == 0) {
                 if constexpr (SWEEP) rec0 = tcnt[1];
                 sir_row_out(curves, sw, s, cj, T, 0, n, tcnt[0], INIT ? tcnt[1] : 0);
@@ -328,10 +394,12 @@ __global__ __launch_bounds__(1024) void k_sir_philox(const int* __restrict__ src
                 const uint8_t f = flag[v];
                 if (f == 1) {
                     state[v] = ST_I; sir_hist_add<SWEEP>(&hinf[(size_t)it * n + v]);
+                    sir_score_event<SCORE, 0>(sr, tal, v);
                     if (TALLY) ++n_new;
                     if (TRAJ && ev_inf) ev_inf[(size_t)s * n + v] = (int16_t)it;
                 } else if (f == 2) {
                     state[v] = ST_R; sir_hist_add<SWEEP>(&hrec[(size_t)it * n + v]);
+                    sir_score_event<SCORE, 1>(sr, tal, v);
                     if (TALLY) ++n_gone;
                     if (TRAJ && ev_inf) ev_rec[(size_t)s * n + v] = (int16_t)it;
                 }
@@ -342,6 +410,7 @@ __global__ __launch_bounds__(1024) void k_sir_philox(const int* __restrict__ src
             if (TALLY && n_gone) atomicAdd(&tcnt[1], n_gone);
             const int alive = __syncthreads_or(any);
             if (rows) {                             // (the counters rest until the next step's barrier)
+                if constexpr (SCORE) sir_score_row(sr, tal, sw.C, cj, T, it, (int)threadIdx.x); else
                 if (threadIdx.x == 0) sir_row_out(curves, sw, s, cj, T, it, n, tcnt[0], tcnt[1]);
                 rows_done = it + 1;
             }
@@ -349,8 +418,9 @@ __global__ __launch_bounds__(1024) void k_sir_philox(const int* __restrict__ src
         }
         if (rows) {                                 // the rows after an early end repeat the final state
             const int n_ever = tcnt[0], n_rec = tcnt[1];
+            if constexpr (SCORE) sir_score_rows_after(sr, tal, sw.C, cj, T, rows_done, (int)threadIdx.x, nthr); else
             for (int r = rows_done + threadIdx.x; r < T; r += nthr) sir_row_out(curves, sw, s, cj, T, r, n, n_ever, n_rec);
-            if constexpr (SWEEP) if (sw.ever && threadIdx.x == 0) sw.ever[(size_t)cj * sims + s] = (uint32_t)(n_ever - rec0);
+            if constexpr (SWEEP && !SCORE) if (sw.ever && threadIdx.x == 0) sw.ever[(size_t)cj * sims + s] = (uint32_t)(n_ever - rec0);
         }
         __syncthreads();
     }
@@ -371,15 +441,16 @@ __global__ __launch_bounds__(1024) void k_sir_philox(const int* __restrict__ src
 // TRAJ: per-trajectory events and curves (SirTraj above); there is no COUNT && TRAJ instance.
 // SWEEP: the candidate sweep (SirSweep above): jobs instead of trajectories, sums instead of histograms.
 template <typename IdT, bool LISTS_IN_LDS, bool COUNT, bool NODES, bool TRAJ, bool EDGES = false, bool INIT = false, bool SCHED = false,
-          bool SWEEP = false>
+          bool SWEEP = false, bool SCORE = false>
 __global__ __launch_bounds__(1024) void k_sir_frontier(const int* __restrict__ rowptr, const int* __restrict__ col, int n,
                                                       const int* __restrict__ seeds, int n_seeds,
                                                       SirThr<NODES> thr_beta, SirThr<NODES> thr_gamma,
                                                       long sims, long sim_offset, int T, uint32_t k0, uint32_t k1,
                                                       uint32_t* __restrict__ hist, int32_t* __restrict__ glists,
                                                       unsigned long long* __restrict__ stats, SirTraj<TRAJ> tr, SirInit<INIT> in,
-                                                      SirSched<SCHED> sc_call, SirSweep<SWEEP> sw) {
+                                                      SirSched<SCHED> sc_call, SirSweep<SWEEP> sw, SirScore<SCORE> sr) {
     static_assert(!SWEEP || (INIT && SCHED && !TRAJ), "the sweep overrides a drawn start and shifts a schedule; its output is the sums");
+    static_assert(!SCORE || SWEEP, "the scores are tallied over the sweep's jobs");
     static_assert(!(COUNT && INIT), "the counting instantiation starts from a seed list");
     static_assert(EDGES || !SCHED, "a schedule switches per-edge tables");
     static_assert(!(COUNT && TRAJ), "the counting instantiation has no per-trajectory output");
@@ -400,6 +471,7 @@ __global__ __launch_bounds__(1024) void k_sir_frontier(const int* __restrict__ r
     IdT* nxt = lists + n;
     IdT* big = lists + 2 * (size_t)n;                          // [rows longer than GN_SIR_BIGROW in the graph] (LDS form), [n] (workspace form)
     __shared__ int cnt[3];                                     // [0] next-list length, [1] big-row list length, [2] ever infected
+    __shared__ int tal[SCORE ? 2 * GN_SIR_SCORE_MAXO : 1];     // (SCORE) the tallies of SirScore; the others never name it
     uint32_t* hinf = hist;
     uint32_t* hrec = hist + (size_t)T * n;
     const int nthr = blockDim.x, tid = threadIdx.x;
@@ -418,6 +490,7 @@ __global__ __launch_bounds__(1024) void k_sir_frontier(const int* __restrict__ r
         const uint32_t sim = (uint32_t)(sim_offset + s);
         for (int w = tid; w < nwords; w += nthr) { bits[w] = 0u; spent[w] = 0u; recb[w] = 0u; }
         if (tid < 3) cnt[tid] = 0;
+        sir_score_reset(sr, tal, tid);
         __syncthreads();
         if constexpr (INIT) {
             // drawn start (sir_init_draw): I and R starts have left S (ever-infected bit, one infection event at t = 0), R
@@ -438,6 +511,8 @@ __global__ __launch_bounds__(1024) void k_sir_frontier(const int* __restrict__ r
                         const bool r = (rec >> j) & 1u;
                         sir_hist_add<SWEEP>(&hinf[u0 + j]);
                         if (r) sir_hist_add<SWEEP>(&hrec[u0 + j]);
+                        sir_score_event<SCORE, 0>(sr, tal, u0 + j);
+                        if (r) sir_score_event<SCORE, 1>(sr, tal, u0 + j);
                         if (TRAJ && ev_inf) { ev_inf[(size_t)s * n + u0 + j] = 0; if (r) ev_rec[(size_t)s * n + u0 + j] = 0; }
                     }
                 // this wave's I starts: slot = wave base + the I starts of the lanes below + this lane's own in front
@@ -474,6 +549,7 @@ __global__ __launch_bounds__(1024) void k_sir_frontier(const int* __restrict__ r
         int rows_done = 1;                                     // (TRAJ, SWEEP) rows of `curves` / of the sums written so far
         const bool rows = SWEEP || (TRAJ && curves);
         const int rec0 = n_ever - n_inf;                       // (SWEEP) the R starts: they were never infected
+        if constexpr (SCORE) sir_score_row(sr, tal, sw.C, cj, T, 0, tid); else
         if (rows && tid == 0) sir_row_out(curves, sw, s, cj, T, 0, n, n_ever, INIT ? n_ever - n_inf : 0);
         for (int it = 1; it < T && n_inf > 0; ++it) {
             // this step's tables: drain, the recovery loop and the recovery-only branch read nothing else
@@ -501,6 +577,7 @@ __global__ __launch_bounds__(1024) void k_sir_frontier(const int* __restrict__ r
                         if ((nib >> j) & 1u) {
                             if ((unsigned long long)w[j] < sir_thr(tg_step, u0 + j)) {
                                 gone |= 1u << j; sir_hist_add<SWEEP>(&hrec[(size_t)it * n + u0 + j]);
+                                sir_score_event<SCORE, 1>(sr, tal, u0 + j);
                                 if (TRAJ && ev_inf) ev_rec[(size_t)s * n + u0 + j] = (int16_t)it;
                             } else ++alive;
                         }
@@ -511,6 +588,7 @@ __global__ __launch_bounds__(1024) void k_sir_frontier(const int* __restrict__ r
                 n_inf = cnt[0];
                 if (rows) {
                     n_ever = n;
+                    if constexpr (SCORE) sir_score_row(sr, tal, sw.C, cj, T, it, tid); else
                     if (tid == 0) sir_row_out(curves, sw, s, cj, T, it, n, n_ever, n_ever - n_inf);
                     rows_done = it + 1;
                 }
@@ -525,6 +603,7 @@ __global__ __launch_bounds__(1024) void k_sir_frontier(const int* __restrict__ r
                     nxt[atomicAdd(&cnt[0], 1)] = (IdT)v;
                     atomicAdd(&cnt[2], 1);
                     sir_hist_add<SWEEP>(&hinf[(size_t)it * n + v]);
+                    sir_score_event<SCORE, 0>(sr, tal, v);
                     if (TRAJ && ev_inf) ev_inf[(size_t)s * n + v] = (int16_t)it;
                 }
             };
@@ -616,6 +695,7 @@ __global__ __launch_bounds__(1024) void k_sir_frontier(const int* __restrict__ r
                 const bool gone = (unsigned long long)philox_coin((uint32_t)u, (uint32_t)it, sim, 1u, k0, k1) < tg;
                 if (gone) {
                     sir_hist_add<SWEEP>(&hrec[(size_t)it * n + u]);
+                    sir_score_event<SCORE, 1>(sr, tal, u);
                     if (TRAJ && ev_inf) ev_rec[(size_t)s * n + u] = (int16_t)it;
                     atomicOr(&recb[u >> 5], 1u << (u & 31));
                 }
@@ -638,15 +718,19 @@ __global__ __launch_bounds__(1024) void k_sir_frontier(const int* __restrict__ r
             n_inf = cnt[0];
             n_ever = cnt[2];
             if (rows) {
+                if constexpr (SCORE) sir_score_row(sr, tal, sw.C, cj, T, it, tid); else
                 if (tid == 0) sir_row_out(curves, sw, s, cj, T, it, n, n_ever, n_ever - n_inf);
                 rows_done = it + 1;
             }
             IdT* t = cur; cur = nxt; nxt = t;
             __syncthreads();
         }
-        if (rows)                                              // the rows after an early end repeat the final state
+        if (rows) {                                            // the rows after an early end repeat the final state
+            if constexpr (SCORE) sir_score_rows_after(sr, tal, sw.C, cj, T, rows_done, tid, nthr); else
             for (int r = rows_done + tid; r < T; r += nthr) sir_row_out(curves, sw, s, cj, T, r, n, n_ever, n_ever - n_inf);
-        if constexpr (SWEEP) if (sw.ever && tid == 0) sw.ever[(size_t)cj * sims + s] = (uint32_t)(n_ever - rec0);
+        }
+        if constexpr (SWEEP && !SCORE) if (sw.ever && tid == 0) sw.ever[(size_t)cj * sims + s] = (uint32_t)(n_ever - rec0);
+        if constexpr (SCORE) __syncthreads();                  // those rows read the tallies: the next job resets them behind this
     }
     if (COUNT) {
         atomicAdd(&stats[0], st_blocks); atomicAdd(&stats[1], st_ecoins); atomicAdd(&stats[2], st_rcoins); atomicAdd(&stats[3], st_entries);
@@ -775,12 +859,13 @@ __global__ void k_put_seeds(SeedArg sa, int n_seeds, int32_t* __restrict__ seeds
 // registration below both go through sir_dispatch, so an instance cannot be launched without being registered.
 // SCHED_: the four scheduled forms (per-edge rates only, TRAJ x INIT), reached through sir_dispatch_sched.
 // SWEEP_: the candidate sweep, one form (the drawn-start scheduled one without per-trajectory output), through sir_dispatch_sweep.
-template <int RATES, bool TRAJ_, bool INIT_, bool SCHED_ = false, bool SWEEP_ = false> struct SirKernels {
-    static constexpr bool NODES = RATES >= SIR_NODES, EDGES = RATES == SIR_EDGES, TRAJ = TRAJ_, INIT = INIT_, SCHED = SCHED_, SWEEP = SWEEP_;
-    static constexpr auto frontier_lds = &k_sir_frontier<uint16_t, true, false, NODES, TRAJ, EDGES, INIT, SCHED, SWEEP>;
-    static constexpr auto frontier_mem = &k_sir_frontier<int32_t, false, false, NODES, TRAJ, EDGES, INIT, SCHED, SWEEP>;
-    static constexpr auto scan_lds = &k_sir_philox<true, NODES, TRAJ, EDGES, INIT, SCHED, SWEEP>;
-    static constexpr auto scan_mem = &k_sir_philox<false, NODES, TRAJ, EDGES, INIT, SCHED, SWEEP>;
+// SCORE_: the source scores, the sweep's form with the similarity tallies, through sir_dispatch_score.
+template <int RATES, bool TRAJ_, bool INIT_, bool SCHED_ = false, bool SWEEP_ = false, bool SCORE_ = false> struct SirKernels {
+    static constexpr bool NODES = RATES >= SIR_NODES, EDGES = RATES == SIR_EDGES, TRAJ = TRAJ_, INIT = INIT_, SCHED = SCHED_, SWEEP = SWEEP_, SCORE = SCORE_;
+    static constexpr auto frontier_lds = &k_sir_frontier<uint16_t, true, false, NODES, TRAJ, EDGES, INIT, SCHED, SWEEP, SCORE>;
+    static constexpr auto frontier_mem = &k_sir_frontier<int32_t, false, false, NODES, TRAJ, EDGES, INIT, SCHED, SWEEP, SCORE>;
+    static constexpr auto scan_lds = &k_sir_philox<true, NODES, TRAJ, EDGES, INIT, SCHED, SWEEP, SCORE>;
+    static constexpr auto scan_mem = &k_sir_philox<false, NODES, TRAJ, EDGES, INIT, SCHED, SWEEP, SCORE>;
 };
 // the counting instances (gnode_sir_mc_philox_counted): the frontier walk of SirKernels<SIR_SCALAR, false, false>
 static constexpr auto kSirCountedLds = &k_sir_frontier<uint16_t, true, true, false, false>;
@@ -800,6 +885,7 @@ template <class F> static void sir_dispatch_sched(bool traj, bool init, F&& f) {
     else { if (init) f(SirKernels<SIR_EDGES, false, true, true>{}); else f(SirKernels<SIR_EDGES, false, false, true>{}); }
 }
 template <class F> static void sir_dispatch_sweep(F&& f) { f(SirKernels<SIR_EDGES, false, true, true, true>{}); }
+template <class F> static void sir_dispatch_score(F&& f) { f(SirKernels<SIR_EDGES, false, true, true, true, true>{}); }
 
 int gn_sir_set_attributes() {       // once per device, from gnode_graph_create
     hipError_t err = hipSuccess;
@@ -812,6 +898,8 @@ int gn_sir_set_attributes() {       // once per device, from gnode_graph_create
     for (int form = 0; form < 4; ++form)
         sir_dispatch_sched(form & 2, form & 1, [&](auto K) { lift(K.frontier_lds); lift(K.frontier_mem); lift(K.scan_lds); });
     sir_dispatch_sweep([&](auto K) { lift(K.frontier_lds); lift(K.frontier_mem); lift(K.scan_lds); });
+    // (the SCORE instances' static tallies come on top: sir_launch_plan keeps dynamic + kSirScoreLds within kLdsStateLimit)
+    sir_dispatch_score([&](auto K) { lift(K.frontier_lds); lift(K.frontier_mem); lift(K.scan_lds); });
     lift(kSirCountedLds); lift(kSirCountedMem); lift(&k_sir_coins);
     GN_HIP(err);
     return 0;
@@ -936,11 +1024,11 @@ static int sir_mc_philox_impl(const SirCall& c) {
                 auto kernel = P.path == SIR_FRONTIER_LDS ? Kt::frontier_lds : Kt::frontier_mem;
                 if constexpr (!Kt::NODES && !Kt::TRAJ && !Kt::INIT) if (stats) kernel = P.path == SIR_FRONTIER_LDS ? kSirCountedLds : kSirCountedMem;
                 hipLaunchKernelGGL(kernel, dim3(P.grid), dim3(P.threads), P.lds, st, g->rowptr, g->col, n, seeds, c.n_seeds, tb, tg, (long)c.sims,
-                                   (long)c.sim_offset, T, k0, k1, hist, (int32_t*)tail, stats, tr, in, sc, SirSweep<false>{});
+                                   (long)c.sim_offset, T, k0, k1, hist, (int32_t*)tail, stats, tr, in, sc, SirSweep<false>{}, SirScore<false>{});
             } else {
                 auto kernel = P.path == SIR_SCAN_LDS ? Kt::scan_lds : Kt::scan_mem;
                 hipLaunchKernelGGL(kernel, dim3(P.grid), dim3(P.threads), P.lds, st, g->src, g->col, (long)g->nnz, n, seeds, c.n_seeds, tb, tg, (long)c.sims,
-                                   (long)c.sim_offset, T, k0, k1, hist, (uint8_t*)tail, tr, in, sc, SirSweep<false>{});
+                                   (long)c.sim_offset, T, k0, k1, hist, (uint8_t*)tail, tr, in, sc, SirSweep<false>{}, SirScore<false>{});
             }
         };
         // the drawn start and the schedule are sets of instances of their own: the others do not carry them
@@ -1061,26 +1149,33 @@ extern "C" int gnode_sir_mc_philox_schedule(gnode_graph_t g, const int32_t* seed
 extern "C" size_t gnode_sir_sweep_workspace_bytes(gnode_graph_t g, int32_t T, int32_t P, int32_t L, int32_t C) {
     return g && T >= 1 && P >= 1 && L >= T && C >= 1 ? sir_sweep_layout(g->info.n, g->nnz, g->n_bigrow, T, P, L, C).total : 0;
 }
-extern "C" int gnode_sir_mc_philox_sweep(gnode_graph_t g, const double* init_host, const int32_t* candidates_host, const int32_t* shifts_host,
-                                         int32_t C, int32_t action, const int32_t* phase_host, int32_t P, int32_t L, const double* w_host,
-                                         const double* gamma_host, int64_t sims, int64_t sim_offset, int32_t T, uint64_t rng_seed,
-                                         uint64_t* sums, uint32_t* ever, void* workspace, size_t workspace_bytes, void* stream,
-                                         int32_t edge_scan) {
-    const char* who = "gnode_sir_mc_philox_sweep";
+// The sweep's call and the scores' (score non-null: the snapshots as the caller holds them, int8 [O][n], and the histogram in
+// place of sums and ever): one set of checks, one staging, one launch.
+struct SirScoreCall { const int8_t* obs; int32_t O, measure, bins; uint64_t* hist; };
+static int sir_sweep_impl(const char* who, gnode_graph_t g, const double* init_host, const int32_t* candidates_host, const int32_t* shifts_host,
+                          int32_t C, int32_t action, const int32_t* phase_host, int32_t P, int32_t L, const double* w_host,
+                          const double* gamma_host, int64_t sims, int64_t sim_offset, int32_t T, uint64_t rng_seed, uint64_t* sums,
+                          uint32_t* ever, void* workspace, size_t workspace_bytes, void* stream, int32_t edge_scan, const SirScoreCall* score) {
     const hipStream_t st = (hipStream_t)stream;
-    GN_CHECK_ARG(g && workspace && init_host && candidates_host && sums, "%s: null pointer", who);
+    GN_CHECK_ARG(g && workspace && init_host && candidates_host && (score ? score->obs && score->hist : sums != nullptr), "%s: null pointer", who);
     GN_CHECK_ARG(P >= 1 && gamma_host && (w_host || g->nnz == 0) && (phase_host || L <= 1), "%s: a schedule takes P >= 1 phases (P = %d), the phase row and both rate tables", who, P);
     GN_CHECK_ARG(C >= 1, "%s: C = %d: at least one candidate", who, C);
     GN_CHECK_ARG(action == 0 || action == 1, "%s: action %d is neither 0 (seed) nor 1 (immunise)", who, action);
     GN_CHECK_ARG(T >= 1 && sims >= 0 && sims <= 0xFFFFFFFFll && sim_offset >= 0 && sim_offset + sims <= 0xFFFFFFFFll, "%s: bad T/sims/sim_offset", who);
     GN_CHECK_ARG(L >= T, "%s: the phase row holds L = %d entries, fewer than T = %d", who, L, T);
     const int n = g->info.n;
-    const SirSweepLayout W = sir_sweep_layout(n, g->nnz, g->n_bigrow, T, P, L, C);
+    const size_t static_lds = score ? kSirScoreLds : 0;
+    const SirScoreLayout WS = score ? sir_score_layout(n, g->nnz, g->n_bigrow, T, P, L, C, score->O) : SirScoreLayout{};
+    const SirSweepLayout W = score ? static_cast<const SirSweepLayout&>(WS) : sir_sweep_layout(n, g->nnz, g->n_bigrow, T, P, L, C);
+    SirScoreStaged staged;
+    if (score) staged = sir_stage_score(who, n, g->nnz, T, P, L, phase_host, w_host, gamma_host, init_host, C, shifts_host, score->obs, score->O, score->measure, score->bins);
+    else staged.thr = sir_stage_sweep(who, n, g->nnz, T, P, L, phase_host, w_host, gamma_host, init_host, C, shifts_host);
+    const SirThresholds& thr = staged.thr;
+    if (score) GN_CHECK_ARG(thr.error.empty(), "%s", thr.error.c_str());   // (the scores: an argument is refused before the workspace is asked about)
     if (workspace_bytes < W.total) {
         gnode_set_error("%s: workspace %zu < %zu", who, workspace_bytes, W.total);
         return GNODE_ERR_WORKSPACE;
     }
-    const SirThresholds thr = sir_stage_sweep(who, n, g->nnz, T, P, L, phase_host, w_host, gamma_host, init_host, C, shifts_host);
     GN_CHECK_ARG(thr.error.empty(), "%s", thr.error.c_str());
     char* ws = (char*)workspace;
     const unsigned long long *thr_b = (const unsigned long long*)(ws + W.thr), *thr_g = thr_b + (size_t)P * (size_t)g->nnz;
@@ -1092,30 +1187,64 @@ extern "C" int gnode_sir_mc_philox_sweep(gnode_graph_t g, const double* init_hos
     if (L > 1) GN_HIP(hipMemcpyAsync(phase_dev, phase_host, sizeof(int32_t) * (size_t)L, hipMemcpyHostToDevice, st));
     GN_HIP(hipMemcpyAsync(cand_dev, candidates_host, sizeof(int32_t) * (size_t)C, hipMemcpyHostToDevice, st));
     GN_HIP(hipMemcpyAsync(shifts_dev, shifts_host ? shifts_host : no_shift.data(), sizeof(int32_t) * (size_t)C, hipMemcpyHostToDevice, st));
+    if (score) {
+        GN_HIP(hipMemcpyAsync(ws + WS.obs, staged.obs.data(), staged.obs.size(), hipMemcpyHostToDevice, st));
+        GN_HIP(hipMemcpyAsync(ws + WS.marked, staged.marked.data(), sizeof(int32_t) * staged.marked.size(), hipMemcpyHostToDevice, st));
+        GN_HIP(hipMemcpyAsync(ws + WS.seen, staged.seen.data(), sizeof(int32_t) * staged.seen.size(), hipMemcpyHostToDevice, st));
+    }
     GN_HIP(hipStreamSynchronize(st));                          // the host arrays are done with
     if (sims == 0) return 0;
     const uint32_t k0 = (uint32_t)(rng_seed & 0xFFFFFFFFull), k1 = (uint32_t)(rng_seed >> 32);
     const bool sampled = gn_prof_begin(3, st);
-    const SirLaunch Pl = sir_launch_plan(n, g->n_bigrow, g->info.num_cu, (int64_t)C * sims, edge_scan != 0);
+    const SirLaunch Pl = sir_launch_plan(n, g->n_bigrow, g->info.num_cu, (int64_t)C * sims, edge_scan != 0, static_lds);
     void* tail = Pl.path == SIR_FRONTIER_MEM || Pl.path == SIR_SCAN_MEM ? ws + W.tail : nullptr;   // the lists / the state, when not in LDS
-    sir_dispatch_sweep([&](auto K) {
+    auto launch = [&](auto K) {
         using Kt = decltype(K);
         SirInit<true> in; in.thr = thr_start;
         SirSched<true> sc; sc.phase = phase_dev;
         SirSweep<true> sw; sw.cand = cand_dev; sw.shifts = shifts_dev; sw.C = C; sw.action = action; sw.sums = (unsigned long long*)sums; sw.ever = ever;
+        SirScore<Kt::SCORE> sr;
+        if constexpr (Kt::SCORE) {
+            sr.obs = (const int8_t*)(ws + WS.obs); sr.marked = (const int32_t*)(ws + WS.marked); sr.seen = (const int32_t*)(ws + WS.seen);
+            sr.O = score->O; sr.measure = score->measure; sr.bins = score->bins; sr.hist = (unsigned long long*)score->hist;
+        }
         if (Pl.path == SIR_FRONTIER_LDS || Pl.path == SIR_FRONTIER_MEM) {
             auto kernel = Pl.path == SIR_FRONTIER_LDS ? Kt::frontier_lds : Kt::frontier_mem;
             hipLaunchKernelGGL(kernel, dim3(Pl.grid), dim3(Pl.threads), Pl.lds, st, g->rowptr, g->col, n, (const int*)nullptr, 0, thr_b, thr_g, (long)sims,
-                               (long)sim_offset, T, k0, k1, (uint32_t*)nullptr, (int32_t*)tail, (unsigned long long*)nullptr, SirTraj<false>{}, in, sc, sw);
+                               (long)sim_offset, T, k0, k1, (uint32_t*)nullptr, (int32_t*)tail, (unsigned long long*)nullptr, SirTraj<false>{}, in, sc, sw, sr);
         } else {
             auto kernel = Pl.path == SIR_SCAN_LDS ? Kt::scan_lds : Kt::scan_mem;
             hipLaunchKernelGGL(kernel, dim3(Pl.grid), dim3(Pl.threads), Pl.lds, st, g->src, g->col, (long)g->nnz, n, (const int*)nullptr, 0, thr_b, thr_g,
-                               (long)sims, (long)sim_offset, T, k0, k1, (uint32_t*)nullptr, (uint8_t*)tail, SirTraj<false>{}, in, sc, sw);
+                               (long)sims, (long)sim_offset, T, k0, k1, (uint32_t*)nullptr, (uint8_t*)tail, SirTraj<false>{}, in, sc, sw, sr);
         }
-    });
+    };
+    if (score) sir_dispatch_score(launch); else sir_dispatch_sweep(launch);
     if (sampled) gn_prof_end(3, st);
     GN_LAUNCH_CHECK();
     return 0;
+}
+extern "C" int gnode_sir_mc_philox_sweep(gnode_graph_t g, const double* init_host, const int32_t* candidates_host, const int32_t* shifts_host,
+                                         int32_t C, int32_t action, const int32_t* phase_host, int32_t P, int32_t L, const double* w_host,
+                                         const double* gamma_host, int64_t sims, int64_t sim_offset, int32_t T, uint64_t rng_seed,
+                                         uint64_t* sums, uint32_t* ever, void* workspace, size_t workspace_bytes, void* stream,
+                                         int32_t edge_scan) {
+    return sir_sweep_impl("gnode_sir_mc_philox_sweep", g, init_host, candidates_host, shifts_host, C, action, phase_host, P, L, w_host, gamma_host, sims,
+                          sim_offset, T, rng_seed, sums, ever, workspace, workspace_bytes, stream, edge_scan, nullptr);
+}
+
+// Monte-Carlo source scores (SCORE instances): the sweep's trajectories, every step of every one binned by its similarity with
+// each of O snapshots; the histogram, no sums.
+extern "C" size_t gnode_sir_sweep_scores_workspace_bytes(gnode_graph_t g, int32_t T, int32_t P, int32_t L, int32_t C, int32_t O) {
+    return g && T >= 1 && P >= 1 && L >= T && C >= 1 && O >= 1 && O <= GN_SIR_SCORE_MAXO ? sir_score_layout(g->info.n, g->nnz, g->n_bigrow, T, P, L, C, O).total : 0;
+}
+extern "C" int gnode_sir_mc_philox_sweep_scores(gnode_graph_t g, const double* init_host, const int32_t* candidates_host, const int32_t* shifts_host,
+                                                int32_t C, int32_t action, const int32_t* phase_host, int32_t P, int32_t L, const double* w_host,
+                                                const double* gamma_host, const int8_t* obs_host, int32_t O, int32_t measure, int32_t bins,
+                                                int64_t sims, int64_t sim_offset, int32_t T, uint64_t rng_seed, uint64_t* hist, void* workspace,
+                                                size_t workspace_bytes, void* stream, int32_t edge_scan) {
+    const SirScoreCall score = {obs_host, O, measure, bins, hist};
+    return sir_sweep_impl("gnode_sir_mc_philox_sweep_scores", g, init_host, candidates_host, shifts_host, C, action, phase_host, P, L, w_host, gamma_host,
+                          sims, sim_offset, T, rng_seed, nullptr, nullptr, workspace, workspace_bytes, stream, edge_scan, &score);
 }
 
 extern "C" int gnode_sir_mc_coins(const int32_t* table_src, const int32_t* table_dst, int64_t n_table, int32_t n,

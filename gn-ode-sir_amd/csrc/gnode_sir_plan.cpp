@@ -9,10 +9,14 @@ static size_t al(size_t x) { return (x + 255) / 256 * 256; }
 static size_t frontier_bitmap_bytes(int n) { return 3 * ((((size_t)n + 31) / 32 + 3) & ~(size_t)3) * 4; }   // ever-infected + spent + recovered
 // list elements in LDS: current + next frontier [n] each, long rows [as many as the graph has, padded to 8]
 static size_t frontier_list_bytes(int n, int n_big) { return 2 * (2 * (size_t)n + (((size_t)n_big + 7) & ~(size_t)7)); }
-bool frontier_lists_in_lds(int n, int n_big) { return n <= 65536 && frontier_bitmap_bytes(n) + frontier_list_bytes(n, n_big) <= 48 * 1024; }
-// + 1 KB of coin queue per wave
-size_t frontier_lds_bytes(int n, int n_big, int threads) {
-    return frontier_bitmap_bytes(n) + (size_t)(threads / 64) * 1024 + (frontier_lists_in_lds(n, n_big) ? frontier_list_bytes(n, n_big) : 0);
+// static_lds (here and below): what the instance keeps in static LDS beyond the few counters every instance has -- the SCORE
+// instances' tallies (kSirScoreLds) -- so that the same 48 KiB hold the lists AND the tallies
+bool frontier_lists_in_lds(int n, int n_big, size_t static_lds) {
+    return n <= 65536 && frontier_bitmap_bytes(n) + frontier_list_bytes(n, n_big) + static_lds <= 48 * 1024;
+}
+// + 1 KB of coin queue per wave (the DYNAMIC bytes: static_lds only moves the boundary of the lists)
+size_t frontier_lds_bytes(int n, int n_big, int threads, size_t static_lds) {
+    return frontier_bitmap_bytes(n) + (size_t)(threads / 64) * 1024 + (frontier_lists_in_lds(n, n_big, static_lds) ? frontier_list_bytes(n, n_big) : 0);
 }
 // Workgroup size and workgroups per CU (the LDS decides how many fit).  Measured, 10 000 x 20 (2 000 x 30 at epinions size),
 // beta 0.3 / 0.05, ms:            16 waves per CU    24 waves      32 waves
@@ -27,9 +31,9 @@ size_t frontier_lds_bytes(int n, int n_big, int threads) {
 #ifndef GN_SIR_THREADS
 #define GN_SIR_THREADS 0
 #endif
-int frontier_threads(int n, int n_big, int* per_cu_out) {
+int frontier_threads(int n, int n_big, int* per_cu_out, size_t static_lds) {
     for (int threads = GN_SIR_THREADS ? GN_SIR_THREADS : (n < 4096 ? 256 : 512); ; threads *= 2) {
-        int per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / (frontier_lds_bytes(n, n_big, threads) + 64)));
+        int per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / (frontier_lds_bytes(n, n_big, threads, static_lds) + 64 + static_lds)));
         if (per_cu * (threads / 64) >= 16 || threads == 1024 || GN_SIR_THREADS) {
             per_cu = std::max(1, std::min(per_cu, GN_SIR_WAVES / (threads / 64)));
             *per_cu_out = per_cu;
@@ -38,33 +42,33 @@ int frontier_threads(int n, int n_big, int* per_cu_out) {
     }
 }
 
-SirLaunch sir_launch_plan(int n, int n_bigrow, int num_cu, int64_t sims, bool edge_scan) {
+SirLaunch sir_launch_plan(int n, int n_bigrow, int num_cu, int64_t sims, bool edge_scan, size_t static_lds) {
     int per_cu = 1;
-    const int threads = frontier_threads(n, n_bigrow, &per_cu);
-    const size_t fl = frontier_lds_bytes(n, n_bigrow, threads), lds = (size_t)2 * n;
-    if (fl <= kLdsStateLimit && !edge_scan) {
+    const int threads = frontier_threads(n, n_bigrow, &per_cu, static_lds);
+    const size_t fl = frontier_lds_bytes(n, n_bigrow, threads, static_lds), lds = (size_t)2 * n;
+    if (fl + static_lds <= kLdsStateLimit && !edge_scan) {
         // frontier-driven walk.  Workgroups per CU by LDS, at least 16 waves per CU
         const int64_t grid = std::min<int64_t>(sims, (int64_t)num_cu * per_cu);
-        if (frontier_lists_in_lds(n, n_bigrow)) return {SIR_FRONTIER_LDS, threads, (int)grid, fl};
+        if (frontier_lists_in_lds(n, n_bigrow, static_lds)) return {SIR_FRONTIER_LDS, threads, (int)grid, fl};
         return {SIR_FRONTIER_MEM, threads, (int)std::min<int64_t>(grid, kFrontierGlobalGrid), fl};
     }
-    if (lds <= kLdsStateLimit) {
+    if (lds + static_lds <= kLdsStateLimit) {
         // edge-parallel scan, node state in LDS: 256 threads for small graphs, 1024 when the state allows one workgroup per CU
-        per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / std::max<size_t>(lds, 1)));
+        per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / std::max<size_t>(lds + static_lds, 1)));
         return {SIR_SCAN_LDS, per_cu >= 4 ? 256 : (per_cu >= 2 ? 512 : 1024), (int)std::min<int64_t>(sims, (int64_t)num_cu * per_cu), lds};
     }
     return {SIR_SCAN_MEM, 256, (int)std::min<int64_t>(sims, 2048), 0};
 }
 
-SirLayout sir_layout(int n, int64_t nnz, int n_bigrow, int T) {
+SirLayout sir_layout(int n, int64_t nnz, int n_bigrow, int T, size_t static_lds) {
     SirLayout L;
     L.hist = 0;
     L.seeds = L.hist + al((size_t)2 * T * n * sizeof(uint32_t));
     L.rows = L.seeds + al(4096 * sizeof(int32_t));
     L.tail = L.rows + al((size_t)std::max<int64_t>(nnz, 1) * sizeof(int32_t));
     size_t tail = 0;
-    if ((size_t)2 * n > kLdsStateLimit) tail = (size_t)2048 * 2 * n;
-    if (!frontier_lists_in_lds(n, n_bigrow)) tail = std::max(tail, (size_t)kFrontierGlobalGrid * 3 * n * sizeof(int32_t));
+    if ((size_t)2 * n + static_lds > kLdsStateLimit) tail = (size_t)2048 * 2 * n;
+    if (!frontier_lists_in_lds(n, n_bigrow, static_lds)) tail = std::max(tail, (size_t)kFrontierGlobalGrid * 3 * n * sizeof(int32_t));
     L.thr = L.bytes[SIR_SCALAR] = L.tail + al(tail);
     const size_t per_node = al((size_t)2 * n * sizeof(unsigned long long));
     L.bytes[SIR_NODES] = L.thr + per_node;
@@ -121,9 +125,9 @@ SirThresholds sir_stage(const char* who, int n, int64_t nnz, const SirRates& r, 
     return t;
 }
 
-SirScheduleLayout sir_schedule_layout(int n, int64_t nnz, int n_bigrow, int T, int P) {
+SirScheduleLayout sir_schedule_layout(int n, int64_t nnz, int n_bigrow, int T, int P, size_t static_lds) {
     SirScheduleLayout L;
-    static_cast<SirLayout&>(L) = sir_layout(n, nnz, n_bigrow, T);
+    static_cast<SirLayout&>(L) = sir_layout(n, nnz, n_bigrow, T, static_lds);
     const size_t tables = (size_t)std::max(P, 1) * ((size_t)std::max<int64_t>(nnz, 0) + (size_t)n);
     L.start = L.thr + al(tables * sizeof(unsigned long long));
     L.phase = L.start + al((size_t)2 * n * sizeof(unsigned long long));
@@ -159,8 +163,8 @@ SirThresholds sir_stage_schedule(const char* who, int n, int64_t nnz, int T, int
     return t;
 }
 
-SirSweepLayout sir_sweep_layout(int n, int64_t nnz, int n_bigrow, int T, int P, int L, int C) {
-    const SirScheduleLayout S = sir_schedule_layout(n, nnz, n_bigrow, T, P);
+static SirSweepLayout sweep_layout(int n, int64_t nnz, int n_bigrow, int T, int P, int L, int C, size_t static_lds) {
+    const SirScheduleLayout S = sir_schedule_layout(n, nnz, n_bigrow, T, P, static_lds);
     const size_t ids = al((size_t)std::max(C, 1) * sizeof(int32_t));
     SirSweepLayout W;
     W.rows = 0;                                                    // (S.rows is where the histogram and the seed list end)
@@ -173,6 +177,7 @@ SirSweepLayout sir_sweep_layout(int n, int64_t nnz, int n_bigrow, int T, int P, 
     W.total = W.shifts + ids;
     return W;
 }
+SirSweepLayout sir_sweep_layout(int n, int64_t nnz, int n_bigrow, int T, int P, int L, int C) { return sweep_layout(n, nnz, n_bigrow, T, P, L, C, 0); }
 
 SirThresholds sir_stage_sweep(const char* who, int n, int64_t nnz, int T, int P, int L, const int32_t* phase, const double* w,
                               const double* gamma, const double* init, int C, const int32_t* shifts) {
@@ -182,4 +187,45 @@ SirThresholds sir_stage_sweep(const char* who, int n, int64_t nnz, int T, int P,
         if (shifts[c] < 0 || (int64_t)shifts[c] + T > L)
             return refuse("%s: shifts[%d] = %d: a shift is >= 0 with shift + T <= L (T = %d, L = %d)", who, c, shifts[c], T, L);
     return sir_stage_schedule(who, n, nnz, L, P, phase, w, gamma, init);
+}
+
+SirScoreLayout sir_score_layout(int n, int64_t nnz, int n_bigrow, int T, int P, int L, int C, int O) {
+    SirScoreLayout W;
+    static_cast<SirSweepLayout&>(W) = sweep_layout(n, nnz, n_bigrow, T, P, L, C, kSirScoreLds);
+    const size_t table = al((size_t)std::max(O, 1) * sizeof(int32_t));
+    W.obs = W.total;
+    W.marked = W.obs + al((size_t)std::max(O, 1) * (size_t)n);
+    W.seen = W.marked + table;
+    W.total = W.seen + table;
+    return W;
+}
+
+SirScoreStaged sir_stage_score(const char* who, int n, int64_t nnz, int T, int P, int L, const int32_t* phase, const double* w,
+                               const double* gamma, const double* init, int C, const int32_t* shifts, const int8_t* obs, int O, int measure,
+                               int bins) {
+    char buf[256];
+    SirScoreStaged s;                                                  // (a refusal: nothing staged, only thr.error)
+#define refuse_score(...) (s.thr = refuse(__VA_ARGS__), s)
+    if (O < 1 || O > GN_SIR_SCORE_MAXO) return refuse_score("%s: O = %d snapshots: 1 to %d in one call", who, O, GN_SIR_SCORE_MAXO);
+    if (bins < 1 || bins > 4096) return refuse_score("%s: bins = %d is not in [1, 4096]", who, bins);
+    if (measure != 0 && measure != 1) return refuse_score("%s: measure %d is neither 0 (jaccard) nor 1 (match)", who, measure);
+    if ((double)O * (double)std::max(C, 1) * (double)std::max(T, 1) * (double)(bins + 1) >= 2147483648.0)
+        return refuse_score("%s: the histogram [O = %d][C = %d][T = %d][bins + 1 = %d] has 2^31 cells or more", who, O, C, T, bins + 1);
+    std::vector<int32_t> marked((size_t)O, 0), seen((size_t)O, 0);
+    for (int o = 0; o < O; ++o) {
+        for (int v = 0; v < n; ++v) {
+            const int x = obs[(size_t)o * n + v];
+            if (x < -1 || x > 2) return refuse_score("%s: obs[%d][%d] = %d is not a code in [-1, 2]", who, o, v, x);
+            seen[o] += x >= 0; marked[o] += x >= 1;
+        }
+        if (seen[o] == 0) return refuse_score("%s: snapshot %d observes no node", who, o);
+    }
+#undef refuse_score
+    s.thr = sir_stage_sweep(who, n, nnz, T, P, L, phase, w, gamma, init, C, shifts);
+    if (!s.thr.error.empty()) return s;
+    s.obs.resize((size_t)n * O);                                       // node-major: an event reads its O codes from one place
+    for (int o = 0; o < O; ++o)
+        for (int v = 0; v < n; ++v) s.obs[(size_t)v * O + o] = obs[(size_t)o * n + v];
+    s.marked = std::move(marked); s.seen = std::move(seen);
+    return s;
 }

@@ -24,16 +24,19 @@ struct SirLayout {
     size_t start;      // uint64 [2][n] start thresholds thr(pS) | thr(pR): behind the per-edge form, the largest of the rate forms'
     size_t bytes[4];   // the workspace of SIR_SCALAR (= thr), SIR_NODES, SIR_EDGES (= start) and SIR_INIT
 };
-SirLayout sir_layout(int n, int64_t nnz, int n_bigrow, int T);
+// static_lds, wherever it appears: the static LDS an instance keeps beyond the few counters all of them have (the SCORE
+// instances' tallies, kSirScoreLds; 0 for every other instance).  It moves the boundary of the lists-in-LDS form and of the
+// scan's state in LDS, and with them the size of `tail`, and it counts in the workgroups per CU.
+SirLayout sir_layout(int n, int64_t nnz, int n_bigrow, int T, size_t static_lds = 0);
 
 // LDS of the frontier kernel: bitmaps + 1 KB of coin queue per wave (+ three uint16 node lists when they fit: n <= 11 232 without long rows)
-bool frontier_lists_in_lds(int n, int n_big);
-size_t frontier_lds_bytes(int n, int n_big, int threads);
-int frontier_threads(int n, int n_big, int* per_cu_out);   // workgroup size, and workgroups per CU
+bool frontier_lists_in_lds(int n, int n_big, size_t static_lds = 0);
+size_t frontier_lds_bytes(int n, int n_big, int threads, size_t static_lds = 0);   // the dynamic bytes
+int frontier_threads(int n, int n_big, int* per_cu_out, size_t static_lds = 0);   // workgroup size, and workgroups per CU
 
 enum SirPath { SIR_FRONTIER_LDS, SIR_FRONTIER_MEM /* lists in the workspace */, SIR_SCAN_LDS, SIR_SCAN_MEM /* state in the workspace */ };
 struct SirLaunch { SirPath path; int threads, grid; size_t lds; };
-SirLaunch sir_launch_plan(int n, int n_bigrow, int num_cu, int64_t sims, bool edge_scan);
+SirLaunch sir_launch_plan(int n, int n_bigrow, int num_cu, int64_t sims, bool edge_scan, size_t static_lds = 0);
 unsigned long long coin_threshold(double p);   // a coin fires iff (64-bit) word < thr, thr = floor(p * 2^32) in [0, 2^32]
 
 // The rates of a call, on the host.  SIR_SCALAR: beta, gamma.  SIR_NODES: beta_nodes, gamma_nodes, fp64 [n] each.  SIR_EDGES:
@@ -58,7 +61,7 @@ struct SirScheduleLayout : SirLayout {   // hist .. tail are sir_layout's; thr i
     size_t phase;      // int32 [T]
     size_t total;      // the workspace of the scheduled call
 };
-SirScheduleLayout sir_schedule_layout(int n, int64_t nnz, int n_bigrow, int T, int P);
+SirScheduleLayout sir_schedule_layout(int n, int64_t nnz, int n_bigrow, int T, int P, size_t static_lds = 0);
 // Every check of the schedule is here: P >= 1, phase[1 .. T-1] in [0, P) (entry 0 is never read), every weight of w [P][nnz]
 // and every rate of gamma [P][n] a probability (a NaN fails), the start as sir_stage checks it.  A refusal names `who`, the
 // phase and the position.  rates = [P * nnz infection thresholds | P * n recovery thresholds].
@@ -80,3 +83,30 @@ SirSweepLayout sir_sweep_layout(int n, int64_t nnz, int n_bigrow, int T, int P, 
 // all 0) is >= 0 with shift + T <= L; phase[1 .. L-1] in [0, P).  A refusal names `who` and the offending index.
 SirThresholds sir_stage_sweep(const char* who, int n, int64_t nnz, int T, int P, int L, const int32_t* phase, const double* w,
                               const double* gamma, const double* init, int C, const int32_t* shifts);
+
+// Monte-Carlo source scores (gnode_sir_mc_philox_sweep_scores, the SCORE instances): the sweep's trajectories, each step of each
+// compared with O snapshots.  At most GN_SIR_SCORE_MAXO snapshots per call: the kernels keep two int32 tallies per snapshot in
+// static LDS, kSirScoreLds bytes that the launch plan and the layout below count (static_lds above).
+#ifndef GN_SIR_SCORE_MAXO
+#define GN_SIR_SCORE_MAXO 16
+#endif
+static const size_t kSirScoreLds = (size_t)2 * GN_SIR_SCORE_MAXO * sizeof(int32_t);
+// The sweep's layout (its `tail` sized for the SCORE instances' boundaries), then the snapshots staged node-major, int8 [n][O],
+// and the two int32 [O] denominator tables: marked[o], the nodes of snapshot o with code 1 or 2 (the Jaccard measure's |A_o|),
+// and seen[o], its observed nodes (the match measure's denominator; seen - marked is its number of zeros).
+struct SirScoreLayout : SirSweepLayout {
+    size_t obs;                      // int8 [n][O]
+    size_t marked, seen;             // int32 [O] each
+};
+SirScoreLayout sir_score_layout(int n, int64_t nnz, int n_bigrow, int T, int P, int L, int C, int O);
+// sir_stage_sweep's checks and those of the snapshots (obs: int8 [O][n] as the caller holds them): 1 <= O <= GN_SIR_SCORE_MAXO,
+// bins in [1, 4096], measure 0 or 1, O * C * T * (bins + 1) < 2^31, every code in [-1, 2], every snapshot observing a node.  A
+// refusal (thr.error) names `who` and the offending index, and nothing is staged.
+struct SirScoreStaged {
+    SirThresholds thr;
+    std::vector<int8_t> obs;         // [n][O]
+    std::vector<int32_t> marked, seen;
+};
+SirScoreStaged sir_stage_score(const char* who, int n, int64_t nnz, int T, int P, int L, const int32_t* phase, const double* w,
+                               const double* gamma, const double* init, int C, const int32_t* shifts, const int8_t* obs, int O, int measure,
+                               int bins);

@@ -585,57 +585,172 @@ def outbreak_sizes_mc(graph, beta, gamma, sims, maxTime, candidates=None, action
     Through `gnode_sir_mc_philox_sweep`, which synchronises the stream.  What is wrong raises ValueError before the library is
     loaded or a graph handle is made."""
     who = "outbreak_sizes_mc"
-    made = hasattr(graph, "handle")                                 # a DeviceGraph: it carries its host CSR
-    host = graph if made else _HostGraph(graph)
-    n = int(host.n)
-    T, sims, sim_offset = _whole(who, "maxTime", maxTime, 1), _whole(who, "sims", sims, 0), _whole(who, "sim_offset", sim_offset, 0)
-    if sim_offset + sims > 0xFFFFFFFF:
-        raise ValueError(f"{who}: sim_offset + sims = {sim_offset + sims} exceeds 2^32 - 1 trajectories")
-    if action not in _MC_ACTIONS:
-        raise ValueError(f"{who}: action must be one of {sorted(_MC_ACTIONS)}, got {action!r}")
-    if isinstance(start, InitialState):
-        base = _init_for(start, n)
-    else:
-        base = InitialState.from_sets(n, [] if start is None else _whole_numbers(who, "start", start))    # (a seed outside the graph: ValueError)
-    if action == "immunise" and not (base.p[:, 1] > 0.0).any():
-        raise ValueError(f"{who}: nothing to immunise against: the start holds no infected mass")
-    cand = np.arange(n, dtype=np.int64) if candidates is None else _whole_numbers(who, "candidates", candidates)
-    if cand.size < 1:
-        raise ValueError(f"{who}: need at least one candidate")
-    if cand.min() < -1 or cand.max() >= n:
-        raise ValueError(f"{who}: candidate {int(cand[(cand < -1) | (cand >= n)][0])} is not in [-1, {n})")
-    C_ = int(cand.size)
-    if shifts is None:
-        sh = np.zeros(C_, dtype=np.int64)
-    else:
-        sh = _whole_numbers(who, "shifts", shifts)
-        if sh.shape[0] != C_:
-            raise ValueError(f"{who}: {C_} candidates need {C_} shifts, got {sh.shape[0]}")
-        if sh.min() < 0:
-            raise ValueError(f"{who}: shift {int(sh.min())} is negative: a run starts at calendar step 0 or later")
-    L = int(sh.max()) + T
-    if L > 2**31 - 1:
-        raise ValueError(f"{who}: max(shifts) + maxTime = {L} does not fit an int32")
-    sched = _scheduled_rates(beta, gamma, host, L)                  # constants become one phase
-    if sums is not None and (not isinstance(sums, torch.Tensor) or sums.dtype != torch.int64 or tuple(sums.shape) != (C_, T, 3)
-                             or not sums.is_contiguous()):
-        raise ValueError(f"{who}: sums must be a contiguous int64 tensor of shape {(C_, T, 3)}")
-    if rng_seed is None:
-        rng_seed = int(torch.randint(0, 2**62, (1,), dtype=torch.int64).item())
-    g = graph if made else _device_graph_for(graph) if hasattr(graph, "number_of_nodes") else DeviceGraph(host.rowptr, host.col)
-    lib = _lib.load()
+    a = _McSweep(who, graph, beta, gamma, sims, maxTime, candidates, action, start, shifts, sim_offset)
+    C_, T, sims = a.C, a.T, a.sims
+    _accumulator(who, "sums", sums, (C_, T, 3))
+    g, lib, rng_seed = a.enter(rng_seed)
     dev = sums.device if sums is not None else device
     if sums is None:
         sums = torch.zeros((C_, T, 3), dtype=torch.int64, device=dev)
     ever = torch.empty((C_, sims), dtype=torch.int32, device=dev) if per_trajectory else None
     if sims > 0:
-        cand32, sh32 = np.ascontiguousarray(cand, dtype=np.int32), np.ascontiguousarray(sh, dtype=np.int32)
-        ws = torch.empty(lib.gnode_sir_sweep_workspace_bytes(g.handle, T, sched.P, L, C_), dtype=torch.uint8, device=dev)
-        _lib.check(lib.gnode_sir_mc_philox_sweep(g.handle, _lib.host_ptr(base.p), _lib.host_ptr(cand32), _lib.host_ptr(sh32), C_, _MC_ACTIONS[action],
-                                                 _lib.host_ptr(sched.phase), sched.P, L, _lib.host_ptr(sched.W), _lib.host_ptr(sched.G), sims,
-                                                 sim_offset, T, C.c_uint64(int(rng_seed) & (2**64 - 1)), _lib.ptr(sums), _lib.ptr(ever), _lib.ptr(ws),
-                                                 ws.numel(), _lib.stream_ptr(), int(bool(edge_scan))))
+        ws = torch.empty(lib.gnode_sir_sweep_workspace_bytes(g.handle, T, a.sched.P, a.L, C_), dtype=torch.uint8, device=dev)
+        _lib.check(lib.gnode_sir_mc_philox_sweep(g.handle, *a.sweep_args(), sims, a.sim_offset, T, C.c_uint64(rng_seed), _lib.ptr(sums), _lib.ptr(ever),
+                                                 _lib.ptr(ws), ws.numel(), _lib.stream_ptr(), int(bool(edge_scan))))
     return SirOutbreakSizes(sums, ever, sims)
+
+
+def _accumulator(who, name, t, shape):
+    """ValueError unless t is None or a contiguous int64 tensor of `shape` (an output to accumulate shards into)"""
+    if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or tuple(t.shape) != tuple(shape) or not t.is_contiguous()):
+        raise ValueError(f"{who}: {name} must be a contiguous int64 tensor of shape {tuple(shape)}")
+
+
+class _McSweep:
+    """The arguments `outbreak_sizes_mc` and `source_scores_mc` share, checked on the host (ValueError) before the library is
+    loaded or a graph handle is made: the graph, maxTime / sims / sim_offset, the action, the start, the candidates, the
+    shifts and the rates as one schedule over max(shifts) + maxTime calendar steps."""
+
+    def __init__(self, who, graph, beta, gamma, sims, maxTime, candidates, action, start, shifts, sim_offset):
+        self.graph, self.made = graph, hasattr(graph, "handle")     # a DeviceGraph: it carries its host CSR
+        self.host = host = graph if self.made else _HostGraph(graph)
+        self.n = n = int(host.n)
+        self.T, self.sims, self.sim_offset = _whole(who, "maxTime", maxTime, 1), _whole(who, "sims", sims, 0), _whole(who, "sim_offset", sim_offset, 0)
+        T = self.T
+        if self.sim_offset + self.sims > 0xFFFFFFFF:
+            raise ValueError(f"{who}: sim_offset + sims = {self.sim_offset + self.sims} exceeds 2^32 - 1 trajectories")
+        if action not in _MC_ACTIONS:
+            raise ValueError(f"{who}: action must be one of {sorted(_MC_ACTIONS)}, got {action!r}")
+        self.action = _MC_ACTIONS[action]
+        if isinstance(start, InitialState):
+            self.base = _init_for(start, n)
+        else:
+            self.base = InitialState.from_sets(n, [] if start is None else _whole_numbers(who, "start", start))    # (a seed outside the graph: ValueError)
+        if action == "immunise" and not (self.base.p[:, 1] > 0.0).any():
+            raise ValueError(f"{who}: nothing to immunise against: the start holds no infected mass")
+        cand = np.arange(n, dtype=np.int64) if candidates is None else _whole_numbers(who, "candidates", candidates)
+        if cand.size < 1:
+            raise ValueError(f"{who}: need at least one candidate")
+        if cand.min() < -1 or cand.max() >= n:
+            raise ValueError(f"{who}: candidate {int(cand[(cand < -1) | (cand >= n)][0])} is not in [-1, {n})")
+        self.C = C_ = int(cand.size)
+        if shifts is None:
+            sh = np.zeros(C_, dtype=np.int64)
+        else:
+            sh = _whole_numbers(who, "shifts", shifts)
+            if sh.shape[0] != C_:
+                raise ValueError(f"{who}: {C_} candidates need {C_} shifts, got {sh.shape[0]}")
+            if sh.min() < 0:
+                raise ValueError(f"{who}: shift {int(sh.min())} is negative: a run starts at calendar step 0 or later")
+        self.L = int(sh.max()) + T
+        if self.L > 2**31 - 1:
+            raise ValueError(f"{who}: max(shifts) + maxTime = {self.L} does not fit an int32")
+        self.sched = _scheduled_rates(beta, gamma, host, self.L)    # constants become one phase
+        self.cand32, self.sh32 = np.ascontiguousarray(cand, dtype=np.int32), np.ascontiguousarray(sh, dtype=np.int32)
+
+    def enter(self, rng_seed):
+        """(graph handle's owner, library, rng seed as a uint64): everything was in order"""
+        if rng_seed is None:
+            rng_seed = int(torch.randint(0, 2**62, (1,), dtype=torch.int64).item())
+        graph, host = self.graph, self.host
+        g = graph if self.made else _device_graph_for(graph) if hasattr(graph, "number_of_nodes") else DeviceGraph(host.rowptr, host.col)
+        return g, _lib.load(), int(rng_seed) & (2**64 - 1)
+
+    def sweep_args(self):
+        """the entries' arguments from init_host to gamma_host"""
+        s = self.sched
+        return (_lib.host_ptr(self.base.p), _lib.host_ptr(self.cand32), _lib.host_ptr(self.sh32), self.C, self.action, _lib.host_ptr(s.phase), s.P,
+                self.L, _lib.host_ptr(s.W), _lib.host_ptr(s.G))
+
+
+SIR_SCORE_MAXO = 16                                                 # GN_SIR_SCORE_MAXO of the library as built: snapshots per launch
+_MC_MEASURES = {"jaccard": 0, "match": 1}
+
+
+class SirSourceScores(NamedTuple):
+    """What `source_scores_mc` returns."""
+    hist: torch.Tensor              # int64 [O, C, T, bins + 1]: trajectories of candidate c whose step t fell into bin k of snapshot o
+    sims: int                       # the trajectories per candidate of THIS call
+    bins: int
+    squeezed: bool                  # `obs` was one row: exact() and scores() drop the snapshot axis
+
+    def _table(self, x):
+        return x[0] if self.squeezed else x
+
+    def exact(self) -> torch.Tensor:
+        """float64 [O, C, T] ([C, T] for one snapshot): hist[..., bins] / sims, the share of the trajectories that agree with the
+        snapshot on every observed node -- an unbiased estimate of the true likelihood (the kernel of width -> 0)."""
+        return self._table(self.hist[..., self.bins].double() / float(self.sims))
+
+    def scores(self, width=0.25, floor=1e-30) -> torch.Tensor:
+        """float64 [O, C, T] ([C, T] for one snapshot): log max(floor, sum_k hist[..., k] exp(-(1 - k / bins)^2 / width^2) / sims),
+        the soft-margin estimator's log-likelihood of (source, onset) -- a bin is taken at its lower edge, the top bin is phi = 1
+        exactly.  `gnode.dmp.rank_sources` and `source_rank_of` read it unchanged.  (After accumulating shards into one `hist`,
+        build the result with the total sims.)"""
+        if not width > 0.0:
+            raise ValueError(f"SirSourceScores.scores: width must be > 0, got {width!r}")
+        k = torch.arange(self.bins + 1, dtype=torch.float64, device=self.hist.device)
+        wgt = torch.exp(-(1.0 - k / float(self.bins)) ** 2 / float(width) ** 2)
+        return self._table(torch.log(torch.clamp((self.hist.double() * wgt).sum(-1) / float(self.sims), min=float(floor))))
+
+
+def source_scores_mc(graph, obs, beta, gamma, sims, maxTime, candidates=None, start=None, shifts=None, measure="jaccard", bins=64, rng_seed=None,
+                     sim_offset=0, edge_scan=False, device="cuda", hist: torch.Tensor | None = None) -> SirSourceScores:
+    """`gnode.dmp.source_scores` by Monte-Carlo, the soft-margin estimator of Antulov-Fantulin et al. (PRL 2015): for each
+    candidate source c, `sims` trajectories start from `start` with c infected -- the trajectories of `outbreak_sizes_mc`,
+    action "seed" -- and the state of each at every step t = 0 .. maxTime - 1 is compared with the observed snapshot(s).  All
+    candidates and up to 16 snapshots share ONE launch; nothing per trajectory reaches memory.  Returns
+    `SirSourceScores(hist, sims, bins, squeezed)`: hist int64 [O, C, maxTime, bins + 1] on the GPU, the number of trajectories
+    whose similarity with snapshot o fell into bin k -- exact integers, whatever the launch geometry; `.exact()` is the
+    exact-match frequency, `.scores(width)` the log of the Gaussian kernel's average, which `gnode.dmp.rank_sources` ranks.  DMP's
+    source likelihood is a product of marginals of an approximation that is exact on trees only: this is what to hold it against
+    on a graph with loops.
+
+    obs: int8 codes [n] or [O, n] -- -1 not observed, 0 / 1 / 2 = S / I / R, as `source_scores` takes them and `sir_state_at`
+    gives them -- numpy or a torch tensor on any device (copied to the host: O * n bytes); every snapshot observes some node.
+    More than 16 snapshots run in groups of 16 on one graph handle.  measure: "jaccard" -- |A & B| / |A | B| of A = the nodes
+    observed infected or recovered and B = the observed nodes that have left S -- or "match", the share of the observed nodes
+    whose state equals the code.  bins: 1 .. 4096; bin k = floor(phi * bins) in integers, so the top bin is complete agreement.
+    candidates, -1, start, shifts, beta / gamma (a `RateSchedule` included), sim_offset, edge_scan: as in `outbreak_sizes_mc`.
+    hist=: an int64 [O, C, maxTime, bins + 1] tensor to ACCUMULATE into, for shards of the sims range.  Through
+    `gnode_sir_mc_philox_sweep_scores`, which synchronises the stream.  What is wrong raises ValueError before the library is
+    loaded or a graph handle is made."""
+    who = "source_scores_mc"
+    a = _McSweep(who, graph, beta, gamma, sims, maxTime, candidates, "seed", start, shifts, sim_offset)
+    if measure not in _MC_MEASURES:
+        raise ValueError(f"{who}: measure must be one of {sorted(_MC_MEASURES)}, got {measure!r}")
+    bins = _whole(who, "bins", bins, 1)
+    if bins > 4096:
+        raise ValueError(f"{who}: bins = {bins} exceeds 4096")
+    if isinstance(obs, torch.Tensor):
+        obs = obs.detach().cpu().numpy()
+    ob = np.asarray(obs)
+    if ob.dtype.kind not in "iu" or ob.ndim not in (1, 2) or ob.shape[-1] != a.n or ob.shape[0] < 1:
+        raise ValueError(f"{who}: obs must hold whole-number codes of shape [{a.n}] or [O, {a.n}], got {ob.dtype} {tuple(ob.shape)}")
+    squeezed = ob.ndim == 1
+    ob = np.atleast_2d(ob)
+    if ob.min() < -1 or ob.max() > 2:
+        o, v = (int(i[0]) for i in np.nonzero((ob < -1) | (ob > 2)))
+        raise ValueError(f"{who}: obs[{o}][{v}] = {int(ob[o, v])} is not a code in [-1, 2]")
+    blind = np.flatnonzero((ob >= 0).sum(1) == 0)
+    if blind.size:
+        raise ValueError(f"{who}: snapshot {int(blind[0])} observes no node")
+    ob = np.ascontiguousarray(ob, dtype=np.int8)
+    O, C_, T, sims = int(ob.shape[0]), a.C, a.T, a.sims
+    if min(O, SIR_SCORE_MAXO) * C_ * T * (bins + 1) >= 2**31:
+        raise ValueError(f"{who}: {min(O, SIR_SCORE_MAXO)} x {C_} x {T} x {bins + 1} histogram cells per launch reach 2^31: fewer bins or candidates")
+    _accumulator(who, "hist", hist, (O, C_, T, bins + 1))
+    g, lib, rng_seed = a.enter(rng_seed)
+    dev = hist.device if hist is not None else device
+    if hist is None:
+        hist = torch.zeros((O, C_, T, bins + 1), dtype=torch.int64, device=dev)
+    for o0 in range(0, O if sims > 0 else 0, SIR_SCORE_MAXO):       # a group's slice of hist is contiguous: o is the slowest axis
+        og = min(SIR_SCORE_MAXO, O - o0)
+        ws = torch.empty(lib.gnode_sir_sweep_scores_workspace_bytes(g.handle, T, a.sched.P, a.L, C_, og), dtype=torch.uint8, device=dev)
+        _lib.check(lib.gnode_sir_mc_philox_sweep_scores(g.handle, *a.sweep_args(), _lib.host_ptr(ob[o0:o0 + og]), og, _MC_MEASURES[measure], bins, sims,
+                                                        a.sim_offset, T, C.c_uint64(rng_seed), _lib.ptr(hist[o0:o0 + og]), _lib.ptr(ws), ws.numel(),
+                                                        _lib.stream_ptr(), int(bool(edge_scan))))
+    return SirSourceScores(hist, sims, bins, squeezed)
 
 
 def sir_counts_counted(graph: DeviceGraph, seed_set, beta, gamma, sims, T, rng_seed, sim_offset=0, device="cuda"):

@@ -513,6 +513,40 @@ int gnode_sir_mc_philox_sweep(gnode_graph_t g, const double* init_host,         
                               uint64_t* sums,     /* device [C][T][3], ACCUMULATED */
                               uint32_t* ever,     /* device [C][sims], OVERWRITTEN, or NULL */
                               void* workspace, size_t workspace_bytes, void* stream, int32_t edge_scan);
+/* Monte-Carlo source scores (no version step: a stale library is known by the missing symbol): the trajectories of
+ * gnode_sir_mc_philox_sweep -- same candidates, override, shifts, coins and job order -- with every step of every trajectory
+ * compared with O snapshots of the epidemic, the soft-margin estimator's raw material (Antulov-Fantulin et al., PRL 2015).
+ *   obs_host   host int8 [O][n]: -1 not observed, 0 / 1 / 2 = S / I / R (gnode_dmp_source_scores_f32's codes); 1 <= O <= 16
+ *              (GN_SIR_SCORE_MAXO of the build), every snapshot observing at least one node
+ *   measure    the similarity phi = num / den of a state with snapshot o, over the observed nodes only:
+ *              0 (Jaccard)  num = |A & B|, den = |A | B|, A = the nodes with code 1 or 2, B = the observed nodes that have left S
+ *              1 (match)    num = the observed nodes whose state equals their code, den = the observed nodes
+ *   bins       1 .. 4096: the bin of a state is k = (num * bins) / den in 64-bit integer division, k = bins when den = 0; hence
+ *              k = bins exactly when state and snapshot agree completely, and bin k < bins holds phi in [k / bins, (k + 1) / bins)
+ *   hist       device uint64 [O][C][T][bins + 1], ACCUMULATED by integer atomic adds: hist[o][c][t][k] += 1 for every trajectory
+ *              of candidate c whose step t falls into bin k of snapshot o (row 0 is the start after the override, rows after an
+ *              early end of the epidemic repeat the final bin), so sum_k hist[o][c][t][k] grows by sims.  Exact, whatever the
+ *              order of the jobs, the grid or the path; shards of the sims range add up.  The floating-point kernel of any width
+ *              is applied to these integers by the caller: hist[..][bins] / sims is the exact-match frequency.
+ * No sums, no ever, no events.  GNODE_ERR_ARG, before any launch and with `hist` untouched: what gnode_sir_mc_philox_sweep
+ * refuses, O outside [1, 16], bins outside [1, 4096], a measure other than 0 or 1, a code outside [-1, 2], a snapshot that
+ * observes no node, O * C * T * (bins + 1) >= 2^31; GNODE_ERR_WORKSPACE: a workspace shorter than
+ * gnode_sir_sweep_scores_workspace_bytes(g, T, P, L, C, O) -- the sweep's layout, then the snapshots staged node-major and two
+ * int32 [O] tables; the query answers 0 where the sweep's does and for O outside [1, 16].  sims = 0 is valid and touches
+ * nothing.  SYNCHRONISES `stream`.  edge_scan as above. */
+size_t gnode_sir_sweep_scores_workspace_bytes(gnode_graph_t g, int32_t T, int32_t P, int32_t L, int32_t C, int32_t O);
+int gnode_sir_mc_philox_sweep_scores(gnode_graph_t g, const double* init_host,   /* host fp64 [n][3] */
+                                     const int32_t* candidates_host,             /* host [C] */
+                                     const int32_t* shifts_host,                 /* host [C], or NULL: all 0 */
+                                     int32_t C, int32_t action,
+                                     const int32_t* phase_host, int32_t P, int32_t L,   /* host [L] */
+                                     const double* w_host,                       /* host fp64 [P][nnz] */
+                                     const double* gamma_host,                   /* host fp64 [P][n] */
+                                     const int8_t* obs_host, int32_t O,          /* host int8 [O][n] */
+                                     int32_t measure, int32_t bins,
+                                     int64_t sims, int64_t sim_offset, int32_t T, uint64_t rng_seed,
+                                     uint64_t* hist,     /* device [O][C][T][bins + 1], ACCUMULATED */
+                                     void* workspace, size_t workspace_bytes, void* stream, int32_t edge_scan);
 int gnode_sir_mc_coins(const int32_t* table_src, const int32_t* table_dst, int64_t n_table, int32_t n,
                        const int32_t* seeds_host, int32_t n_seeds, double beta, double gamma, int64_t sims,
                        int32_t T, const double* coins, int64_t n_coins, uint32_t* counts,
