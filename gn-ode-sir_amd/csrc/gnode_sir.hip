@@ -49,6 +49,11 @@
 // every step compared with up to GN_SIR_SCORE_MAXO observed snapshots by two integer tallies per snapshot in LDS, and where the
 // sweep adds a row to its sums, one count into a histogram of binned similarities per (snapshot, candidate, step).  Separate
 // instances again; the sweep's compile to what they were.
+//
+// Source scores from timed evidence (gnode_sir_mc_philox_sweep_timed, the TIMED instances, SWEEP ones only): the sweep's
+// trajectories, each compared at every possible age t with all records (node, offset, kind) of up to GN_SIR_SCORE_MAXO evidence
+// sets jointly.  An event moves a difference array over t in LDS; one prefix sum at the end of the trajectory gives the number
+// of matched records per (set, t), and one count per (set, t) goes into the histogram.  Separate instances once more.
 #include "gnode_common.h"
 #include "gnode_sir_plan.h"
 #include <algorithm>
@@ -243,6 +248,59 @@ __device__ __forceinline__ void sir_score_rows_after(const SirScore<true>& sr, c
     for (int r = from + tid; r < T; r += nthr)
         for (int o = 0; o < sr.O; ++o) sir_score_cell(sr, tal, C, c, T, r, o);
 }
+// TIMED instances (gnode_sir_mc_philox_sweep_timed; SWEEP ones only, never SCORE): the sweep's jobs, each compared with O sets
+// of records (node v, offset d <= 0, kind).  For "now" = t steps after the run began a record is read at model step m = t + d
+// and is matched when: m < 0 and the kind is 0; kind 0 / 1 / 2 and v is S / I / R at step m; kind 3 and v became infected AT
+// step m; kind 4 and it recovered AT step m.  agree[o][t], the matched records of set o, is a sum of steps and pulses in t that
+// begin at (event step + back), back = -d: `dif`, int32 [O][T] in LDS, holds its DIFFERENCES and moves at the sites that hold an
+// event -- the sites of sir_score_event -- by LDS integer atomics; positions >= T are dropped:
+//   v leaves S at step `it`:   kind 0: -1 at it + back;  kind 1: +1 at it + back;  kind 3: +1 at it + back, -1 at it + back + 1
+//   v recovers at step `it`:   kind 1: -1 at it + back;  kind 2: +1 at it + back;  kind 4: +1 at it + back, -1 at it + back + 1
+// from dif[o][0] = zeros[o], the kind-0 records of the set (everybody in S, for ever), and 0 elsewhere.  Nothing is put out per
+// step.  When the trajectory has ended an inclusive prefix sum over t turns dif into agree, and the job adds ONE to
+// hist[o][c][t][k], uint64 [O][C][T][bins + 1], k = agree * bins / records[o] in integers, for every (o, t): k = bins exactly
+// when every record of the set is matched.  The records are staged by node: those of v are rec[rec_ptr[v] .. rec_ptr[v + 1]),
+// one word each -- set | kind << 4 | min(back, T) << 8 -- and an event of a node without a record costs the two reads of
+// rec_ptr (DESIGN 4.18 on why not a bitmap).  No sums, no ever.  The others take an empty struct, as with SirScore, and
+// compile to what they were.
+template <bool TIMED> struct SirTimed {};
+template <> struct SirTimed<true> {
+    const int32_t* rec_ptr; const uint32_t* rec; const int32_t* zeros; const int32_t* records; int O; int bins;
+    unsigned long long* hist;   // [O][C][T][bins + 1], accumulated
+};
+// the difference array of a job before its start is drawn, in front of the barrier that resets the counters
+template <bool TIMED> __device__ __forceinline__ void sir_timed_reset(const SirTimed<TIMED>& tm, int* dif, int T, int tid, int nthr) {
+    if constexpr (TIMED)
+        for (int i = tid, cells = tm.O * T; i < cells; i += nthr) { const int o = i / T; dif[i] = i == o * T ? tm.zeros[o] : 0; }
+}
+// KIND 0: node v leaves S at step `it`; KIND 1: it recovers at step `it`
+template <bool TIMED, int KIND> __device__ __forceinline__ void sir_timed_event(const SirTimed<TIMED>& tm, int* dif, int T, int v, int it) {
+    if constexpr (TIMED) {
+        for (int r = tm.rec_ptr[v], end = tm.rec_ptr[v + 1]; r < end; ++r) {
+            const uint32_t w = tm.rec[r];
+            const int kind = (int)((w >> 4) & 7u), pos = it + (int)(w >> 8);
+            const int d = KIND == 0 ? (kind == 1 || kind == 3) - (kind == 0) : (kind == 2 || kind == 4) - (kind == 1);
+            if (d == 0 || pos >= T) continue;
+            int* row = dif + (int)(w & 15u) * T;
+            atomicAdd(&row[pos], d);
+            if (kind == 3 + KIND && pos + 1 < T) atomicAdd(&row[pos + 1], -1);      // "at that step": a pulse, not a step
+        }
+    }
+}
+// the end of a job, behind the barrier that follows its last event: dif to agree (thread o takes set o: T dependent LDS adds, a
+// step's worth of time at the end of T steps), a barrier, and the O * T counts spread over the threads as sir_score_rows_after
+// spreads its rows (integer adds commute: exact whatever the order of the jobs).  The caller's barrier in front of the next job's
+// reset follows.
+__device__ __forceinline__ void sir_timed_finish(const SirTimed<true>& tm, int* dif, int C, int c, int T, int tid, int nthr) {
+    if (tid < tm.O) { int* row = dif + tid * T; int run = 0; for (int t = 0; t < T; ++t) { run += row[t]; row[t] = run; } }
+    __syncthreads();
+    for (int i = tid, cells = tm.O * T; i < cells; i += nthr) {
+        const int o = i / T, t = i - o * T;
+        unsigned long long k = (unsigned long long)dif[i] * (unsigned long long)tm.bins / (unsigned long long)tm.records[o];
+        if (k > (unsigned long long)tm.bins) k = (unsigned long long)tm.bins;   // (agree is in [0, records]: the count stays inside its row regardless)
+        atomicAdd(&tm.hist[(((size_t)o * C + c) * T + t) * ((size_t)tm.bins + 1) + k], 1ull);
+    }
+}
 // where a TRAJ instance writes a row of curves, a SWEEP instance adds it to its candidate's sums
 template <bool SWEEP>
 __device__ __forceinline__ void sir_row_out(uint32_t* __restrict__ curves, const SirSweep<SWEEP>& sw, long s, int c, int T, int row, int n,
@@ -272,18 +330,20 @@ __global__ __launch_bounds__(256) void k_fill_i16(int16_t* __restrict__ p, size_
 #define GN_SIR_UNROLL 8
 #endif
 template <bool STATE_IN_LDS, bool NODES, bool TRAJ, bool EDGES = false, bool INIT = false, bool SCHED = false, bool SWEEP = false,
-          bool SCORE = false>
+          bool SCORE = false, bool TIMED = false>
 __global__ __launch_bounds__(1024) void k_sir_philox(const int* __restrict__ src, const int* __restrict__ dst, long nnz,
                                                     int n, const int* __restrict__ seeds, int n_seeds,
                                                     SirThr<NODES> thr_beta, SirThr<NODES> thr_gamma,
                                                     long sims, long sim_offset, int T, uint32_t k0, uint32_t k1,
                                                     uint32_t* __restrict__ hist, uint8_t* __restrict__ gstate, SirTraj<TRAJ> tr,
-                                                    SirInit<INIT> in, SirSched<SCHED> sc_call, SirSweep<SWEEP> sw, SirScore<SCORE> sr) {
+                                                    SirInit<INIT> in, SirSched<SCHED> sc_call, SirSweep<SWEEP> sw, SirScore<SCORE> sr,
+                                                    SirTimed<TIMED> tm) {
     static_assert(NODES || !EDGES, "per-edge infection thresholds come with per-node recovery thresholds");
     static_assert(EDGES || !SCHED, "a schedule switches per-edge tables");
     static_assert(!SWEEP || (INIT && SCHED && !TRAJ), "the sweep overrides a drawn start and shifts a schedule; its output is the sums");
     static_assert(!SCORE || SWEEP, "the scores are tallied over the sweep's jobs");
-    constexpr bool TALLY = TRAJ || SWEEP;         // the trajectory's totals are kept in tcnt
+    static_assert(!TIMED || (SWEEP && !SCORE), "the timed evidence is tallied over the sweep's jobs, in place of the snapshots");
+    constexpr bool TALLY = TRAJ || (SWEEP && !TIMED);   // the trajectory's totals are kept in tcnt
     extern __shared__ uint8_t smem[];
     uint8_t* state = STATE_IN_LDS ? smem : gstate + (size_t)blockIdx.x * 2 * n;
     uint8_t* flag = state + n;
@@ -294,6 +354,7 @@ __global__ __launch_bounds__(1024) void k_sir_philox(const int* __restrict__ src
     // the dynamic size is what the host's occupancy choice is computed from)
     __shared__ int tcnt[2];
     __shared__ int tal[SCORE ? 2 * GN_SIR_SCORE_MAXO : 1];      // (SCORE) the tallies of SirScore; the others never name it
+    __shared__ int dif[TIMED ? GN_SIR_TIMED_CELLS : 1];         // (TIMED) the difference array of SirTimed; likewise
     int16_t* ev_inf = nullptr; int16_t* ev_rec = nullptr; uint32_t* curves = nullptr;
     if constexpr (TRAJ) { ev_inf = tr.events; if (tr.events) ev_rec = tr.events + (size_t)sims * n; curves = tr.curves; }
     long jobs = sims;                             // (SWEEP) C * sims of them, the candidates interleaved
@@ -306,6 +367,7 @@ __global__ __launch_bounds__(1024) void k_sir_philox(const int* __restrict__ src
         for (int v = threadIdx.x; v < n; v += nthr) { state[v] = ST_S; flag[v] = 0; }
         if (TALLY && threadIdx.x < 2) tcnt[threadIdx.x] = 0;
         sir_score_reset(sr, tal, (int)threadIdx.x);
+        sir_timed_reset(tm, dif, T, (int)threadIdx.x, nthr);
         __syncthreads();
         if constexpr (INIT) {
             // drawn start: a node that starts in I or R has left S at step 0 (one infection event), one that starts in R
@@ -324,6 +386,8 @@ __global__ __launch_bounds__(1024) void k_sir_philox(const int* __restrict__ src
                     if (r) sir_hist_add<SWEEP>(&hrec[v]);
                     sir_score_event<SCORE, 0>(sr, tal, v);
                     if (r) sir_score_event<SCORE, 1>(sr, tal, v);
+                    sir_timed_event<TIMED, 0>(tm, dif, T, v, 0);
+                    if (r) sir_timed_event<TIMED, 1>(tm, dif, T, v, 0);
                     if (TRAJ && ev_inf) { ev_inf[(size_t)s * n + v] = 0; if (r) ev_rec[(size_t)s * n + v] = 0; }
                 }
                 n_out += __popc(inf | rec); n_gone += __popc(rec);
@@ -346,7 +410,7 @@ __global__ __launch_bounds__(1024) void k_sir_philox(const int* __restrict__ src
             }
         }
         int rows_done = 1;                          // (TRAJ, SWEEP) rows of `curves` / of the sums written so far
-        const bool rows = SWEEP || (TRAJ && curves);
+        const bool rows = (SWEEP && !TIMED) || (TRAJ && curves);       // (TIMED: nothing is put out per step)
         if (rows) {
             __syncthreads();
             if constexpr (SCORE) sir_score_row(sr, tal, sw.C, cj, T, 0, (int)threadIdx.x); else
@@ -395,11 +459,13 @@ __global__ __launch_bounds__(1024) void k_sir_philox(const int* __restrict__ src
                 if (f == 1) {
                     state[v] = ST_I; sir_hist_add<SWEEP>(&hinf[(size_t)it * n + v]);
                     sir_score_event<SCORE, 0>(sr, tal, v);
+                    sir_timed_event<TIMED, 0>(tm, dif, T, v, it);
                     if (TALLY) ++n_new;
                     if (TRAJ && ev_inf) ev_inf[(size_t)s * n + v] = (int16_t)it;
                 } else if (f == 2) {
                     state[v] = ST_R; sir_hist_add<SWEEP>(&hrec[(size_t)it * n + v]);
                     sir_score_event<SCORE, 1>(sr, tal, v);
+                    sir_timed_event<TIMED, 1>(tm, dif, T, v, it);
                     if (TALLY) ++n_gone;
                     if (TRAJ && ev_inf) ev_rec[(size_t)s * n + v] = (int16_t)it;
                 }
@@ -422,6 +488,7 @@ __global__ __launch_bounds__(1024) void k_sir_philox(const int* __restrict__ src
             for (int r = rows_done + threadIdx.x; r < T; r += nthr) sir_row_out(curves, sw, s, cj, T, r, n, n_ever, n_rec);
             if constexpr (SWEEP && !SCORE) if (sw.ever && threadIdx.x == 0) sw.ever[(size_t)cj * sims + s] = (uint32_t)(n_ever - rec0);
         }
+        if constexpr (TIMED) sir_timed_finish(tm, dif, sw.C, cj, T, (int)threadIdx.x, nthr);   // (every event lies behind a barrier)
         __syncthreads();
     }
 }
@@ -441,16 +508,17 @@ __global__ __launch_bounds__(1024) void k_sir_philox(const int* __restrict__ src
 // TRAJ: per-trajectory events and curves (SirTraj above); there is no COUNT && TRAJ instance.
 // SWEEP: the candidate sweep (SirSweep above): jobs instead of trajectories, sums instead of histograms.
 template <typename IdT, bool LISTS_IN_LDS, bool COUNT, bool NODES, bool TRAJ, bool EDGES = false, bool INIT = false, bool SCHED = false,
-          bool SWEEP = false, bool SCORE = false>
+          bool SWEEP = false, bool SCORE = false, bool TIMED = false>
 __global__ __launch_bounds__(1024) void k_sir_frontier(const int* __restrict__ rowptr, const int* __restrict__ col, int n,
                                                       const int* __restrict__ seeds, int n_seeds,
                                                       SirThr<NODES> thr_beta, SirThr<NODES> thr_gamma,
                                                       long sims, long sim_offset, int T, uint32_t k0, uint32_t k1,
                                                       uint32_t* __restrict__ hist, int32_t* __restrict__ glists,
                                                       unsigned long long* __restrict__ stats, SirTraj<TRAJ> tr, SirInit<INIT> in,
-                                                      SirSched<SCHED> sc_call, SirSweep<SWEEP> sw, SirScore<SCORE> sr) {
+                                                      SirSched<SCHED> sc_call, SirSweep<SWEEP> sw, SirScore<SCORE> sr, SirTimed<TIMED> tm) {
     static_assert(!SWEEP || (INIT && SCHED && !TRAJ), "the sweep overrides a drawn start and shifts a schedule; its output is the sums");
     static_assert(!SCORE || SWEEP, "the scores are tallied over the sweep's jobs");
+    static_assert(!TIMED || (SWEEP && !SCORE), "the timed evidence is tallied over the sweep's jobs, in place of the snapshots");
     static_assert(!(COUNT && INIT), "the counting instantiation starts from a seed list");
     static_assert(EDGES || !SCHED, "a schedule switches per-edge tables");
     static_assert(!(COUNT && TRAJ), "the counting instantiation has no per-trajectory output");
@@ -472,6 +540,7 @@ __global__ __launch_bounds__(1024) void k_sir_frontier(const int* __restrict__ r
     IdT* big = lists + 2 * (size_t)n;                          // [rows longer than GN_SIR_BIGROW in the graph] (LDS form), [n] (workspace form)
     __shared__ int cnt[3];                                     // [0] next-list length, [1] big-row list length, [2] ever infected
     __shared__ int tal[SCORE ? 2 * GN_SIR_SCORE_MAXO : 1];     // (SCORE) the tallies of SirScore; the others never name it
+    __shared__ int dif[TIMED ? GN_SIR_TIMED_CELLS : 1];        // (TIMED) the difference array of SirTimed; likewise
     uint32_t* hinf = hist;
     uint32_t* hrec = hist + (size_t)T * n;
     const int nthr = blockDim.x, tid = threadIdx.x;
@@ -491,6 +560,7 @@ __global__ __launch_bounds__(1024) void k_sir_frontier(const int* __restrict__ r
         for (int w = tid; w < nwords; w += nthr) { bits[w] = 0u; spent[w] = 0u; recb[w] = 0u; }
         if (tid < 3) cnt[tid] = 0;
         sir_score_reset(sr, tal, tid);
+        sir_timed_reset(tm, dif, T, tid, nthr);
         __syncthreads();
         if constexpr (INIT) {
             // drawn start (sir_init_draw): I and R starts have left S (ever-infected bit, one infection event at t = 0), R
@@ -513,6 +583,8 @@ __global__ __launch_bounds__(1024) void k_sir_frontier(const int* __restrict__ r
                         if (r) sir_hist_add<SWEEP>(&hrec[u0 + j]);
                         sir_score_event<SCORE, 0>(sr, tal, u0 + j);
                         if (r) sir_score_event<SCORE, 1>(sr, tal, u0 + j);
+                        sir_timed_event<TIMED, 0>(tm, dif, T, u0 + j, 0);
+                        if (r) sir_timed_event<TIMED, 1>(tm, dif, T, u0 + j, 0);
                         if (TRAJ && ev_inf) { ev_inf[(size_t)s * n + u0 + j] = 0; if (r) ev_rec[(size_t)s * n + u0 + j] = 0; }
                     }
                 // this wave's I starts: slot = wave base + the I starts of the lanes below + this lane's own in front
@@ -547,7 +619,7 @@ __global__ __launch_bounds__(1024) void k_sir_frontier(const int* __restrict__ r
         __syncthreads();
         if (tid == 0) cnt[2] = n_ever;
         int rows_done = 1;                                     // (TRAJ, SWEEP) rows of `curves` / of the sums written so far
-        const bool rows = SWEEP || (TRAJ && curves);
+        const bool rows = (SWEEP && !TIMED) || (TRAJ && curves);   // (TIMED: nothing is put out per step)
         const int rec0 = n_ever - n_inf;                       // (SWEEP) the R starts: they were never infected
         if constexpr (SCORE) sir_score_row(sr, tal, sw.C, cj, T, 0, tid); else
         if (rows && tid == 0) sir_row_out(curves, sw, s, cj, T, 0, n, n_ever, INIT ? n_ever - n_inf : 0);
@@ -578,6 +650,7 @@ __global__ __launch_bounds__(1024) void k_sir_frontier(const int* __restrict__ r
                             if ((unsigned long long)w[j] < sir_thr(tg_step, u0 + j)) {
                                 gone |= 1u << j; sir_hist_add<SWEEP>(&hrec[(size_t)it * n + u0 + j]);
                                 sir_score_event<SCORE, 1>(sr, tal, u0 + j);
+                                sir_timed_event<TIMED, 1>(tm, dif, T, u0 + j, it);
                                 if (TRAJ && ev_inf) ev_rec[(size_t)s * n + u0 + j] = (int16_t)it;
                             } else ++alive;
                         }
@@ -604,6 +677,7 @@ __global__ __launch_bounds__(1024) void k_sir_frontier(const int* __restrict__ r
                     atomicAdd(&cnt[2], 1);
                     sir_hist_add<SWEEP>(&hinf[(size_t)it * n + v]);
                     sir_score_event<SCORE, 0>(sr, tal, v);
+                    sir_timed_event<TIMED, 0>(tm, dif, T, v, it);
                     if (TRAJ && ev_inf) ev_inf[(size_t)s * n + v] = (int16_t)it;
                 }
             };
@@ -696,6 +770,7 @@ __global__ __launch_bounds__(1024) void k_sir_frontier(const int* __restrict__ r
                 if (gone) {
                     sir_hist_add<SWEEP>(&hrec[(size_t)it * n + u]);
                     sir_score_event<SCORE, 1>(sr, tal, u);
+                    sir_timed_event<TIMED, 1>(tm, dif, T, u, it);
                     if (TRAJ && ev_inf) ev_rec[(size_t)s * n + u] = (int16_t)it;
                     atomicOr(&recb[u >> 5], 1u << (u & 31));
                 }
@@ -729,8 +804,10 @@ __global__ __launch_bounds__(1024) void k_sir_frontier(const int* __restrict__ r
             if constexpr (SCORE) sir_score_rows_after(sr, tal, sw.C, cj, T, rows_done, tid, nthr); else
             for (int r = rows_done + tid; r < T; r += nthr) sir_row_out(curves, sw, s, cj, T, r, n, n_ever, n_ever - n_inf);
         }
-        if constexpr (SWEEP && !SCORE) if (sw.ever && tid == 0) sw.ever[(size_t)cj * sims + s] = (uint32_t)(n_ever - rec0);
+        if constexpr (SWEEP && !SCORE && !TIMED) if (sw.ever && tid == 0) sw.ever[(size_t)cj * sims + s] = (uint32_t)(n_ever - rec0);
         if constexpr (SCORE) __syncthreads();                  // those rows read the tallies: the next job resets them behind this
+        // (every step ends in a barrier, and so does the start: every event lies behind one)
+        if constexpr (TIMED) { sir_timed_finish(tm, dif, sw.C, cj, T, tid, nthr); __syncthreads(); }
     }
     if (COUNT) {
         atomicAdd(&stats[0], st_blocks); atomicAdd(&stats[1], st_ecoins); atomicAdd(&stats[2], st_rcoins); atomicAdd(&stats[3], st_entries);
@@ -860,12 +937,14 @@ __global__ void k_put_seeds(SeedArg sa, int n_seeds, int32_t* __restrict__ seeds
 // SCHED_: the four scheduled forms (per-edge rates only, TRAJ x INIT), reached through sir_dispatch_sched.
 // SWEEP_: the candidate sweep, one form (the drawn-start scheduled one without per-trajectory output), through sir_dispatch_sweep.
 // SCORE_: the source scores, the sweep's form with the similarity tallies, through sir_dispatch_score.
-template <int RATES, bool TRAJ_, bool INIT_, bool SCHED_ = false, bool SWEEP_ = false, bool SCORE_ = false> struct SirKernels {
+// TIMED_: the scores from timed evidence, the sweep's form with the difference array, through sir_dispatch_timed.
+template <int RATES, bool TRAJ_, bool INIT_, bool SCHED_ = false, bool SWEEP_ = false, bool SCORE_ = false, bool TIMED_ = false> struct SirKernels {
     static constexpr bool NODES = RATES >= SIR_NODES, EDGES = RATES == SIR_EDGES, TRAJ = TRAJ_, INIT = INIT_, SCHED = SCHED_, SWEEP = SWEEP_, SCORE = SCORE_;
-    static constexpr auto frontier_lds = &k_sir_frontier<uint16_t, true, false, NODES, TRAJ, EDGES, INIT, SCHED, SWEEP, SCORE>;
-    static constexpr auto frontier_mem = &k_sir_frontier<int32_t, false, false, NODES, TRAJ, EDGES, INIT, SCHED, SWEEP, SCORE>;
-    static constexpr auto scan_lds = &k_sir_philox<true, NODES, TRAJ, EDGES, INIT, SCHED, SWEEP, SCORE>;
-    static constexpr auto scan_mem = &k_sir_philox<false, NODES, TRAJ, EDGES, INIT, SCHED, SWEEP, SCORE>;
+    static constexpr bool TIMED = TIMED_;
+    static constexpr auto frontier_lds = &k_sir_frontier<uint16_t, true, false, NODES, TRAJ, EDGES, INIT, SCHED, SWEEP, SCORE, TIMED>;
+    static constexpr auto frontier_mem = &k_sir_frontier<int32_t, false, false, NODES, TRAJ, EDGES, INIT, SCHED, SWEEP, SCORE, TIMED>;
+    static constexpr auto scan_lds = &k_sir_philox<true, NODES, TRAJ, EDGES, INIT, SCHED, SWEEP, SCORE, TIMED>;
+    static constexpr auto scan_mem = &k_sir_philox<false, NODES, TRAJ, EDGES, INIT, SCHED, SWEEP, SCORE, TIMED>;
 };
 // the counting instances (gnode_sir_mc_philox_counted): the frontier walk of SirKernels<SIR_SCALAR, false, false>
 static constexpr auto kSirCountedLds = &k_sir_frontier<uint16_t, true, true, false, false>;
@@ -886,6 +965,7 @@ template <class F> static void sir_dispatch_sched(bool traj, bool init, F&& f) {
 }
 template <class F> static void sir_dispatch_sweep(F&& f) { f(SirKernels<SIR_EDGES, false, true, true, true>{}); }
 template <class F> static void sir_dispatch_score(F&& f) { f(SirKernels<SIR_EDGES, false, true, true, true, true>{}); }
+template <class F> static void sir_dispatch_timed(F&& f) { f(SirKernels<SIR_EDGES, false, true, true, true, false, true>{}); }
 
 int gn_sir_set_attributes() {       // once per device, from gnode_graph_create
     hipError_t err = hipSuccess;
@@ -900,6 +980,7 @@ int gn_sir_set_attributes() {       // once per device, from gnode_graph_create
     sir_dispatch_sweep([&](auto K) { lift(K.frontier_lds); lift(K.frontier_mem); lift(K.scan_lds); });
     // (the SCORE instances' static tallies come on top: sir_launch_plan keeps dynamic + kSirScoreLds within kLdsStateLimit)
     sir_dispatch_score([&](auto K) { lift(K.frontier_lds); lift(K.frontier_mem); lift(K.scan_lds); });
+    sir_dispatch_timed([&](auto K) { lift(K.frontier_lds); lift(K.frontier_mem); lift(K.scan_lds); });    // (likewise, kSirTimedLds)
     lift(kSirCountedLds); lift(kSirCountedMem); lift(&k_sir_coins);
     GN_HIP(err);
     return 0;
@@ -1024,11 +1105,11 @@ static int sir_mc_philox_impl(const SirCall& c) {
                 auto kernel = P.path == SIR_FRONTIER_LDS ? Kt::frontier_lds : Kt::frontier_mem;
                 if constexpr (!Kt::NODES && !Kt::TRAJ && !Kt::INIT) if (stats) kernel = P.path == SIR_FRONTIER_LDS ? kSirCountedLds : kSirCountedMem;
                 hipLaunchKernelGGL(kernel, dim3(P.grid), dim3(P.threads), P.lds, st, g->rowptr, g->col, n, seeds, c.n_seeds, tb, tg, (long)c.sims,
-                                   (long)c.sim_offset, T, k0, k1, hist, (int32_t*)tail, stats, tr, in, sc, SirSweep<false>{}, SirScore<false>{});
+                                   (long)c.sim_offset, T, k0, k1, hist, (int32_t*)tail, stats, tr, in, sc, SirSweep<false>{}, SirScore<false>{}, SirTimed<false>{});
             } else {
                 auto kernel = P.path == SIR_SCAN_LDS ? Kt::scan_lds : Kt::scan_mem;
                 hipLaunchKernelGGL(kernel, dim3(P.grid), dim3(P.threads), P.lds, st, g->src, g->col, (long)g->nnz, n, seeds, c.n_seeds, tb, tg, (long)c.sims,
-                                   (long)c.sim_offset, T, k0, k1, hist, (uint8_t*)tail, tr, in, sc, SirSweep<false>{}, SirScore<false>{});
+                                   (long)c.sim_offset, T, k0, k1, hist, (uint8_t*)tail, tr, in, sc, SirSweep<false>{}, SirScore<false>{}, SirTimed<false>{});
             }
         };
         // the drawn start and the schedule are sets of instances of their own: the others do not carry them
@@ -1149,29 +1230,38 @@ extern "C" int gnode_sir_mc_philox_schedule(gnode_graph_t g, const int32_t* seed
 extern "C" size_t gnode_sir_sweep_workspace_bytes(gnode_graph_t g, int32_t T, int32_t P, int32_t L, int32_t C) {
     return g && T >= 1 && P >= 1 && L >= T && C >= 1 ? sir_sweep_layout(g->info.n, g->nnz, g->n_bigrow, T, P, L, C).total : 0;
 }
-// The sweep's call and the scores' (score non-null: the snapshots as the caller holds them, int8 [O][n], and the histogram in
-// place of sums and ever): one set of checks, one staging, one launch.
+// The sweep's call, the scores' (score non-null: the snapshots as the caller holds them, int8 [O][n], and the histogram in
+// place of sums and ever) and the timed scores' (timed non-null: the R records as four host arrays, and the histogram): one
+// set of checks, one staging, one launch.
 struct SirScoreCall { const int8_t* obs; int32_t O, measure, bins; uint64_t* hist; };
+struct SirTimedCall { const int32_t *rec_set, *rec_node, *rec_offset, *rec_kind; int32_t R, O, bins; uint64_t* hist; };
 static int sir_sweep_impl(const char* who, gnode_graph_t g, const double* init_host, const int32_t* candidates_host, const int32_t* shifts_host,
                           int32_t C, int32_t action, const int32_t* phase_host, int32_t P, int32_t L, const double* w_host,
                           const double* gamma_host, int64_t sims, int64_t sim_offset, int32_t T, uint64_t rng_seed, uint64_t* sums,
-                          uint32_t* ever, void* workspace, size_t workspace_bytes, void* stream, int32_t edge_scan, const SirScoreCall* score) {
+                          uint32_t* ever, void* workspace, size_t workspace_bytes, void* stream, int32_t edge_scan, const SirScoreCall* score,
+                          const SirTimedCall* timed = nullptr) {
     const hipStream_t st = (hipStream_t)stream;
-    GN_CHECK_ARG(g && workspace && init_host && candidates_host && (score ? score->obs && score->hist : sums != nullptr), "%s: null pointer", who);
+    GN_CHECK_ARG(g && workspace && init_host && candidates_host && (score ? score->obs && score->hist : timed ? timed->hist != nullptr : sums != nullptr), "%s: null pointer", who);
+    GN_CHECK_ARG(!timed || timed->R < 1 || (timed->rec_set && timed->rec_node && timed->rec_offset && timed->rec_kind), "%s: null pointer", who);
     GN_CHECK_ARG(P >= 1 && gamma_host && (w_host || g->nnz == 0) && (phase_host || L <= 1), "%s: a schedule takes P >= 1 phases (P = %d), the phase row and both rate tables", who, P);
     GN_CHECK_ARG(C >= 1, "%s: C = %d: at least one candidate", who, C);
     GN_CHECK_ARG(action == 0 || action == 1, "%s: action %d is neither 0 (seed) nor 1 (immunise)", who, action);
     GN_CHECK_ARG(T >= 1 && sims >= 0 && sims <= 0xFFFFFFFFll && sim_offset >= 0 && sim_offset + sims <= 0xFFFFFFFFll, "%s: bad T/sims/sim_offset", who);
     GN_CHECK_ARG(L >= T, "%s: the phase row holds L = %d entries, fewer than T = %d", who, L, T);
     const int n = g->info.n;
-    const size_t static_lds = score ? kSirScoreLds : 0;
+    const size_t static_lds = score ? kSirScoreLds : timed ? kSirTimedLds : 0;
     const SirScoreLayout WS = score ? sir_score_layout(n, g->nnz, g->n_bigrow, T, P, L, C, score->O) : SirScoreLayout{};
-    const SirSweepLayout W = score ? static_cast<const SirSweepLayout&>(WS) : sir_sweep_layout(n, g->nnz, g->n_bigrow, T, P, L, C);
+    const SirTimedLayout WT = timed ? sir_timed_layout(n, g->nnz, g->n_bigrow, T, P, L, C, timed->O, timed->R) : SirTimedLayout{};
+    const SirSweepLayout W = score ? static_cast<const SirSweepLayout&>(WS) : timed ? static_cast<const SirSweepLayout&>(WT)
+                                   : sir_sweep_layout(n, g->nnz, g->n_bigrow, T, P, L, C);
     SirScoreStaged staged;
+    SirTimedStaged records;
     if (score) staged = sir_stage_score(who, n, g->nnz, T, P, L, phase_host, w_host, gamma_host, init_host, C, shifts_host, score->obs, score->O, score->measure, score->bins);
+    else if (timed) records = sir_stage_timed(who, n, g->nnz, T, P, L, phase_host, w_host, gamma_host, init_host, C, shifts_host, timed->rec_set, timed->rec_node,
+                                              timed->rec_offset, timed->rec_kind, timed->R, timed->O, timed->bins);
     else staged.thr = sir_stage_sweep(who, n, g->nnz, T, P, L, phase_host, w_host, gamma_host, init_host, C, shifts_host);
-    const SirThresholds& thr = staged.thr;
-    if (score) GN_CHECK_ARG(thr.error.empty(), "%s", thr.error.c_str());   // (the scores: an argument is refused before the workspace is asked about)
+    const SirThresholds& thr = timed ? records.thr : staged.thr;
+    if (score || timed) GN_CHECK_ARG(thr.error.empty(), "%s", thr.error.c_str());   // (the scores: an argument is refused before the workspace is asked about)
     if (workspace_bytes < W.total) {
         gnode_set_error("%s: workspace %zu < %zu", who, workspace_bytes, W.total);
         return GNODE_ERR_WORKSPACE;
@@ -1192,6 +1282,12 @@ static int sir_sweep_impl(const char* who, gnode_graph_t g, const double* init_h
         GN_HIP(hipMemcpyAsync(ws + WS.marked, staged.marked.data(), sizeof(int32_t) * staged.marked.size(), hipMemcpyHostToDevice, st));
         GN_HIP(hipMemcpyAsync(ws + WS.seen, staged.seen.data(), sizeof(int32_t) * staged.seen.size(), hipMemcpyHostToDevice, st));
     }
+    if (timed) {
+        GN_HIP(hipMemcpyAsync(ws + WT.rec_ptr, records.rec_ptr.data(), sizeof(int32_t) * records.rec_ptr.size(), hipMemcpyHostToDevice, st));
+        GN_HIP(hipMemcpyAsync(ws + WT.rec, records.rec.data(), sizeof(uint32_t) * records.rec.size(), hipMemcpyHostToDevice, st));
+        GN_HIP(hipMemcpyAsync(ws + WT.zeros, records.zeros.data(), sizeof(int32_t) * records.zeros.size(), hipMemcpyHostToDevice, st));
+        GN_HIP(hipMemcpyAsync(ws + WT.records, records.records.data(), sizeof(int32_t) * records.records.size(), hipMemcpyHostToDevice, st));
+    }
     GN_HIP(hipStreamSynchronize(st));                          // the host arrays are done with
     if (sims == 0) return 0;
     const uint32_t k0 = (uint32_t)(rng_seed & 0xFFFFFFFFull), k1 = (uint32_t)(rng_seed >> 32);
@@ -1208,17 +1304,22 @@ static int sir_sweep_impl(const char* who, gnode_graph_t g, const double* init_h
             sr.obs = (const int8_t*)(ws + WS.obs); sr.marked = (const int32_t*)(ws + WS.marked); sr.seen = (const int32_t*)(ws + WS.seen);
             sr.O = score->O; sr.measure = score->measure; sr.bins = score->bins; sr.hist = (unsigned long long*)score->hist;
         }
+        SirTimed<Kt::TIMED> tm;
+        if constexpr (Kt::TIMED) {
+            tm.rec_ptr = (const int32_t*)(ws + WT.rec_ptr); tm.rec = (const uint32_t*)(ws + WT.rec); tm.zeros = (const int32_t*)(ws + WT.zeros);
+            tm.records = (const int32_t*)(ws + WT.records); tm.O = timed->O; tm.bins = timed->bins; tm.hist = (unsigned long long*)timed->hist;
+        }
         if (Pl.path == SIR_FRONTIER_LDS || Pl.path == SIR_FRONTIER_MEM) {
             auto kernel = Pl.path == SIR_FRONTIER_LDS ? Kt::frontier_lds : Kt::frontier_mem;
             hipLaunchKernelGGL(kernel, dim3(Pl.grid), dim3(Pl.threads), Pl.lds, st, g->rowptr, g->col, n, (const int*)nullptr, 0, thr_b, thr_g, (long)sims,
-                               (long)sim_offset, T, k0, k1, (uint32_t*)nullptr, (int32_t*)tail, (unsigned long long*)nullptr, SirTraj<false>{}, in, sc, sw, sr);
+                               (long)sim_offset, T, k0, k1, (uint32_t*)nullptr, (int32_t*)tail, (unsigned long long*)nullptr, SirTraj<false>{}, in, sc, sw, sr, tm);
         } else {
             auto kernel = Pl.path == SIR_SCAN_LDS ? Kt::scan_lds : Kt::scan_mem;
             hipLaunchKernelGGL(kernel, dim3(Pl.grid), dim3(Pl.threads), Pl.lds, st, g->src, g->col, (long)g->nnz, n, (const int*)nullptr, 0, thr_b, thr_g,
-                               (long)sims, (long)sim_offset, T, k0, k1, (uint32_t*)nullptr, (uint8_t*)tail, SirTraj<false>{}, in, sc, sw, sr);
+                               (long)sims, (long)sim_offset, T, k0, k1, (uint32_t*)nullptr, (uint8_t*)tail, SirTraj<false>{}, in, sc, sw, sr, tm);
         }
     };
-    if (score) sir_dispatch_score(launch); else sir_dispatch_sweep(launch);
+    if (score) sir_dispatch_score(launch); else if (timed) sir_dispatch_timed(launch); else sir_dispatch_sweep(launch);
     if (sampled) gn_prof_end(3, st);
     GN_LAUNCH_CHECK();
     return 0;
@@ -1245,6 +1346,22 @@ extern "C" int gnode_sir_mc_philox_sweep_scores(gnode_graph_t g, const double* i
     const SirScoreCall score = {obs_host, O, measure, bins, hist};
     return sir_sweep_impl("gnode_sir_mc_philox_sweep_scores", g, init_host, candidates_host, shifts_host, C, action, phase_host, P, L, w_host, gamma_host,
                           sims, sim_offset, T, rng_seed, nullptr, nullptr, workspace, workspace_bytes, stream, edge_scan, &score);
+}
+
+// Monte-Carlo source scores from timed evidence (TIMED instances): the sweep's trajectories, every age t of every one binned by
+// the number of records of each of O evidence sets it agrees with; the histogram, no sums.
+extern "C" size_t gnode_sir_sweep_timed_workspace_bytes(gnode_graph_t g, int32_t T, int32_t P, int32_t L, int32_t C, int32_t O, int32_t R) {
+    return g && T >= 1 && P >= 1 && L >= T && C >= 1 && O >= 1 && O <= GN_SIR_SCORE_MAXO && R >= 1 ? sir_timed_layout(g->info.n, g->nnz, g->n_bigrow, T, P, L, C, O, R).total : 0;
+}
+extern "C" int gnode_sir_mc_philox_sweep_timed(gnode_graph_t g, const double* init_host, const int32_t* candidates_host, const int32_t* shifts_host,
+                                               int32_t C, int32_t action, const int32_t* phase_host, int32_t P, int32_t L, const double* w_host,
+                                               const double* gamma_host, const int32_t* rec_set, const int32_t* rec_node, const int32_t* rec_offset,
+                                               const int32_t* rec_kind, int32_t R, int32_t O, int32_t bins, int64_t sims, int64_t sim_offset, int32_t T,
+                                               uint64_t rng_seed, uint64_t* hist, void* workspace, size_t workspace_bytes, void* stream,
+                                               int32_t edge_scan) {
+    const SirTimedCall timed = {rec_set, rec_node, rec_offset, rec_kind, R, O, bins, hist};
+    return sir_sweep_impl("gnode_sir_mc_philox_sweep_timed", g, init_host, candidates_host, shifts_host, C, action, phase_host, P, L, w_host, gamma_host,
+                          sims, sim_offset, T, rng_seed, nullptr, nullptr, workspace, workspace_bytes, stream, edge_scan, nullptr, &timed);
 }
 
 extern "C" int gnode_sir_mc_coins(const int32_t* table_src, const int32_t* table_dst, int64_t n_table, int32_t n,

@@ -229,3 +229,52 @@ SirScoreStaged sir_stage_score(const char* who, int n, int64_t nnz, int T, int P
     s.marked = std::move(marked); s.seen = std::move(seen);
     return s;
 }
+
+SirTimedLayout sir_timed_layout(int n, int64_t nnz, int n_bigrow, int T, int P, int L, int C, int O, int R) {
+    SirTimedLayout W;
+    static_cast<SirSweepLayout&>(W) = sweep_layout(n, nnz, n_bigrow, T, P, L, C, kSirTimedLds);
+    const size_t table = al((size_t)std::max(O, 1) * sizeof(int32_t));
+    W.rec_ptr = W.total;
+    W.rec = W.rec_ptr + al(((size_t)n + 1) * sizeof(int32_t));
+    W.zeros = W.rec + al((size_t)std::max(R, 1) * sizeof(uint32_t));
+    W.records = W.zeros + table;
+    W.total = W.records + table;
+    return W;
+}
+
+SirTimedStaged sir_stage_timed(const char* who, int n, int64_t nnz, int T, int P, int L, const int32_t* phase, const double* w,
+                               const double* gamma, const double* init, int C, const int32_t* shifts, const int32_t* rec_set,
+                               const int32_t* rec_node, const int32_t* rec_offset, const int32_t* rec_kind, int R, int O, int bins) {
+    char buf[256];
+    SirTimedStaged s;                                                  // (a refusal: nothing staged, only thr.error)
+#define refuse_timed(...) (s.thr = refuse(__VA_ARGS__), s)
+    if (O < 1 || O > GN_SIR_SCORE_MAXO) return refuse_timed("%s: O = %d evidence sets: 1 to %d in one call", who, O, GN_SIR_SCORE_MAXO);
+    if ((int64_t)O * std::max(T, 1) > GN_SIR_TIMED_CELLS)
+        return refuse_timed("%s: O = %d sets x T = %d steps are more than the %d cells of the difference array", who, O, T, GN_SIR_TIMED_CELLS);
+    if (bins < 1 || bins > 4096) return refuse_timed("%s: bins = %d is not in [1, 4096]", who, bins);
+    if ((double)O * (double)std::max(C, 1) * (double)std::max(T, 1) * (double)(bins + 1) >= 2147483648.0)
+        return refuse_timed("%s: the histogram [O = %d][C = %d][T = %d][bins + 1 = %d] has 2^31 cells or more", who, O, C, T, bins + 1);
+    if (R < 1) return refuse_timed("%s: R = %d records: at least one", who, R);
+    std::vector<int32_t> zeros((size_t)O, 0), records((size_t)O, 0), ptr((size_t)n + 1, 0);
+    for (int i = 0; i < R; ++i) {
+        if (rec_set[i] < 0 || rec_set[i] >= O) return refuse_timed("%s: rec_set[%d] = %d is not in [0, %d)", who, i, rec_set[i], O);
+        if (rec_node[i] < 0 || rec_node[i] >= n) return refuse_timed("%s: rec_node[%d] = %d is not in [0, %d)", who, i, rec_node[i], n);
+        if (rec_kind[i] < 0 || rec_kind[i] > 4) return refuse_timed("%s: rec_kind[%d] = %d is not a kind in [0, 4]", who, i, rec_kind[i]);
+        if (rec_offset[i] > 0) return refuse_timed("%s: rec_offset[%d] = %d is after now: offsets are <= 0", who, i, rec_offset[i]);
+        ++records[rec_set[i]]; zeros[rec_set[i]] += rec_kind[i] == 0; ++ptr[(size_t)rec_node[i] + 1];
+    }
+    for (int o = 0; o < O; ++o)
+        if (records[o] == 0) return refuse_timed("%s: evidence set %d holds no record", who, o);
+#undef refuse_timed
+    s.thr = sir_stage_sweep(who, n, nnz, T, P, L, phase, w, gamma, init, C, shifts);
+    if (!s.thr.error.empty()) return s;
+    for (int v = 0; v < n; ++v) ptr[(size_t)v + 1] += ptr[v];
+    std::vector<int32_t> at(ptr.begin(), ptr.end() - 1);               // by node, a node's records in the order given
+    s.rec.resize((size_t)R);
+    for (int i = 0; i < R; ++i) {
+        const int64_t back = std::min<int64_t>(-(int64_t)rec_offset[i], std::max(T, 0));   // (at T or beyond: never reached)
+        s.rec[(size_t)at[rec_node[i]]++] = (uint32_t)rec_set[i] | (uint32_t)rec_kind[i] << 4 | (uint32_t)back << 8;
+    }
+    s.rec_ptr = std::move(ptr); s.zeros = std::move(zeros); s.records = std::move(records);
+    return s;
+}

@@ -110,3 +110,35 @@ struct SirScoreStaged {
 SirScoreStaged sir_stage_score(const char* who, int n, int64_t nnz, int T, int P, int L, const int32_t* phase, const double* w,
                                const double* gamma, const double* init, int C, const int32_t* shifts, const int8_t* obs, int O, int measure,
                                int bins);
+
+// Monte-Carlo source scores from timed evidence (gnode_sir_mc_philox_sweep_timed, the TIMED instances): the sweep's trajectories,
+// each compared at every age t with the records (node, offset <= 0, kind 0 .. 4) of O evidence sets, at most GN_SIR_SCORE_MAXO per
+// call.  The kernels keep a difference array over t, int32 [O][T], in static LDS: GN_SIR_TIMED_CELLS int32 -- 2 048, 8 KiB, so
+// 16 sets up to T = 128 and one set up to T = 2 048 -- which the launch plan and the layout below count as kSirTimedLds
+// (static_lds above: the lists-in-LDS form ends at n = 9 352 instead of 11 232 with it).
+#ifndef GN_SIR_TIMED_CELLS
+#define GN_SIR_TIMED_CELLS 2048
+#endif
+static const size_t kSirTimedLds = (size_t)GN_SIR_TIMED_CELLS * sizeof(int32_t);
+// The sweep's layout (its `tail` sized for the TIMED instances' boundaries), then the records staged by node: rec_ptr, and one
+// word per record -- set | kind << 4 | min(-offset, T) << 8 -- in ascending node order, the records of one node in the order
+// they were given; then zeros[o], the records of kind 0 of set o, and records[o], its size.
+struct SirTimedLayout : SirSweepLayout {
+    size_t rec_ptr;                  // int32 [n + 1]
+    size_t rec;                      // uint32 [R]
+    size_t zeros, records;           // int32 [O] each
+};
+SirTimedLayout sir_timed_layout(int n, int64_t nnz, int n_bigrow, int T, int P, int L, int C, int O, int R);
+// sir_stage_sweep's checks and those of the records (four arrays of length R): 1 <= O <= GN_SIR_SCORE_MAXO, O * T <=
+// GN_SIR_TIMED_CELLS, bins in [1, 4096], O * C * T * (bins + 1) < 2^31, R >= 1, every set in [0, O), node in [0, n), kind in
+// [0, 4] and offset <= 0, every set holding a record.  A refusal (thr.error) names `who` and the offending index, and nothing
+// is staged.
+struct SirTimedStaged {
+    SirThresholds thr;
+    std::vector<int32_t> rec_ptr;    // [n + 1]
+    std::vector<uint32_t> rec;       // [R]
+    std::vector<int32_t> zeros, records;
+};
+SirTimedStaged sir_stage_timed(const char* who, int n, int64_t nnz, int T, int P, int L, const int32_t* phase, const double* w,
+                               const double* gamma, const double* init, int C, const int32_t* shifts, const int32_t* rec_set,
+                               const int32_t* rec_node, const int32_t* rec_offset, const int32_t* rec_kind, int R, int O, int bins);

@@ -753,6 +753,99 @@ def source_scores_mc(graph, obs, beta, gamma, sims, maxTime, candidates=None, st
     return SirSourceScores(hist, sims, bins, squeezed)
 
 
+SIR_TIMED_CELLS = 2048                                              # GN_SIR_TIMED_CELLS of the library as built: sets x maxTime per launch
+
+
+def _timed_records(who, observations, n):
+    """(squeezed, [(nodes, offsets, kinds) int32 [R_o]] per evidence set) of what `gnode.dmp.timed_observations` returns, or a
+    sequence of them, taken by the attributes `.rows`, `.row_offsets` and `.n`; a record is every rows[r, v] >= 0, at offset
+    row_offsets[r], in the order of the rows and then of the nodes.  ValueError for anything else."""
+    squeezed = hasattr(observations, "rows")
+    try:
+        sets = [observations] if squeezed else list(observations)
+    except TypeError:
+        raise ValueError(f"{who}: observations must be what timed_observations returns, or a sequence of them, got {type(observations).__name__}") from None
+    if not sets:
+        raise ValueError(f"{who}: need at least one evidence set")
+    out = []
+    for o, s in enumerate(sets):
+        if not all(hasattr(s, name) for name in ("rows", "row_offsets", "n")):
+            raise ValueError(f"{who}: evidence set {o} has no .rows, .row_offsets and .n: not what timed_observations returns ({type(s).__name__})")
+        rows, off = (x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x) for x in (s.rows, s.row_offsets))
+        if rows.dtype.kind not in "iu" or rows.ndim != 2 or rows.shape[1] != n or s.n != n:
+            raise ValueError(f"{who}: evidence set {o}: rows must hold whole-number codes of shape [R, {n}], got {rows.dtype} {tuple(rows.shape)} (n = {s.n!r})")
+        if off.dtype.kind not in "iu" or off.shape != (rows.shape[0],):
+            raise ValueError(f"{who}: evidence set {o}: {rows.shape[0]} rows need {rows.shape[0]} whole-number row_offsets, got {off.dtype} {tuple(off.shape)}")
+        if rows.size and (rows.min() < -1 or rows.max() > 4):
+            r, v = (int(i[0]) for i in np.nonzero((rows < -1) | (rows > 4)))
+            raise ValueError(f"{who}: evidence set {o}: rows[{r}][{v}] = {int(rows[r, v])} is not a kind in [-1, 4]")
+        if off.size and off.max() > 0:
+            raise ValueError(f"{who}: evidence set {o}: offset {int(off.max())} is after now: offsets are <= 0")
+        r, v = np.nonzero(rows >= 0)
+        if r.size < 1:
+            raise ValueError(f"{who}: evidence set {o} holds no record")
+        back = np.maximum(off.astype(np.int64)[r], -(2**31 - 1))   # (beyond maxTime steps back every offset reads "before the outbreak")
+        out.append((v.astype(np.int32), back.astype(np.int32), rows[r, v].astype(np.int32)))
+    return squeezed, out
+
+
+def source_scores_timed_mc(graph, observations, beta, gamma, sims, maxTime, candidates=None, start=None, shifts=None, bins=None, rng_seed=None,
+                           sim_offset=0, edge_scan=False, device="cuda", hist: torch.Tensor | None = None) -> SirSourceScores:
+    """`gnode.dmp.source_scores_timed` by Monte-Carlo: which node started the outbreak, from records taken at DIFFERENT times --
+    onsets at a few sensors, recovery dates, tests on different days, two records for one person?  For each candidate source c,
+    `sims` trajectories start from `start` with c infected -- the trajectories of `source_scores_mc` -- and each is compared, for
+    every possible age t = 0 .. maxTime - 1 of the outbreak, with ALL records of an evidence set jointly: a record (node v,
+    offset d <= 0, kind) is read at the trajectory's step t + d -- kind 0 / 1 / 2: v was S / I / R then; 3: v became infected at
+    that step; 4: v recovered at that step; before the outbreak (t + d < 0) everybody is susceptible.  Returns
+    `SirSourceScores(hist, sims, bins, squeezed)`: hist int64 [O, C, maxTime, bins + 1] on the GPU, the number of trajectories of
+    candidate c that at age t agree with agree * bins // records of set o's records in bin k -- exact integers, whatever the
+    launch geometry.  `.exact()` = hist[..., bins] / sims is an unbiased estimate of the JOINT likelihood P(all records | source
+    c, age t), which DMP's timed score approximates twice over: by marginals that are exact on trees only, and by treating the
+    records of one cascade as independent.  `.scores(width)`, `gnode.dmp.rank_sources` and `source_rank_of` work as for
+    `source_scores_mc`.
+
+    observations: what `gnode.dmp.timed_observations` returns (taken by its attributes `.rows` int8 [R, n], `.row_offsets` and
+    `.n`), or a sequence of them for O evidence sets; one object gives [C, maxTime] tables.  A node may have several records.
+    bins: 1 .. 4096; by default the largest record count of any set, so that this set is not binned at all (k = the number of
+    matched records).  All candidates and up to min(16, 2048 // maxTime) sets share ONE launch -- the kernels keep sets x maxTime
+    counters on chip -- and more sets run in groups on one graph handle; maxTime above 2048 is refused.  candidates, -1, start,
+    shifts, beta / gamma (a `RateSchedule` included), sim_offset, edge_scan, hist=: as in `source_scores_mc`.  Through
+    `gnode_sir_mc_philox_sweep_timed`, which synchronises the stream.  What is wrong raises ValueError before the library is
+    loaded or a graph handle is made."""
+    who = "source_scores_timed_mc"
+    a = _McSweep(who, graph, beta, gamma, sims, maxTime, candidates, "seed", start, shifts, sim_offset)
+    C_, T, sims = a.C, a.T, a.sims
+    if T > SIR_TIMED_CELLS:
+        raise ValueError(f"{who}: maxTime = {T} exceeds the {SIR_TIMED_CELLS} steps one evidence set can be tallied over")
+    squeezed, sets = _timed_records(who, observations, a.n)
+    O, most = len(sets), max(len(s[0]) for s in sets)
+    if bins is None:
+        if most > 4096:
+            raise ValueError(f"{who}: an evidence set holds {most} records, more than 4096 bins: give bins")
+        bins = most
+    bins = _whole(who, "bins", bins, 1)
+    if bins > 4096:
+        raise ValueError(f"{who}: bins = {bins} exceeds 4096")
+    group = min(SIR_SCORE_MAXO, SIR_TIMED_CELLS // T)
+    if min(O, group) * C_ * T * (bins + 1) >= 2**31:
+        raise ValueError(f"{who}: {min(O, group)} x {C_} x {T} x {bins + 1} histogram cells per launch reach 2^31: fewer bins or candidates")
+    _accumulator(who, "hist", hist, (O, C_, T, bins + 1))
+    g, lib, rng_seed = a.enter(rng_seed)
+    dev = hist.device if hist is not None else device
+    if hist is None:
+        hist = torch.zeros((O, C_, T, bins + 1), dtype=torch.int64, device=dev)
+    for o0 in range(0, O if sims > 0 else 0, group):               # a group's slice of hist is contiguous: o is the slowest axis
+        part = sets[o0:o0 + group]
+        og = len(part)
+        which = np.concatenate([np.full(len(s[0]), i, dtype=np.int32) for i, s in enumerate(part)])
+        node, off, kind = (np.ascontiguousarray(np.concatenate([s[j] for s in part])) for j in range(3))
+        ws = torch.empty(lib.gnode_sir_sweep_timed_workspace_bytes(g.handle, T, a.sched.P, a.L, C_, og, len(which)), dtype=torch.uint8, device=dev)
+        _lib.check(lib.gnode_sir_mc_philox_sweep_timed(g.handle, *a.sweep_args(), _lib.host_ptr(which), _lib.host_ptr(node), _lib.host_ptr(off),
+                                                       _lib.host_ptr(kind), len(which), og, bins, sims, a.sim_offset, T, C.c_uint64(rng_seed),
+                                                       _lib.ptr(hist[o0:o0 + og]), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(), int(bool(edge_scan))))
+    return SirSourceScores(hist, sims, bins, squeezed)
+
+
 def sir_counts_counted(graph: DeviceGraph, seed_set, beta, gamma, sims, T, rng_seed, sim_offset=0, device="cuda"):
     """`sir_counts` through the kernel's profiling instantiation: (counts, stats) with stats = what the launch did --
     Philox blocks computed, infection coins drawn, recovery coins drawn, CSR entries read (bench.py's `sir` roofline)."""

@@ -547,6 +547,46 @@ int gnode_sir_mc_philox_sweep_scores(gnode_graph_t g, const double* init_host,  
                                      int64_t sims, int64_t sim_offset, int32_t T, uint64_t rng_seed,
                                      uint64_t* hist,     /* device [O][C][T][bins + 1], ACCUMULATED */
                                      void* workspace, size_t workspace_bytes, void* stream, int32_t edge_scan);
+/* Monte-Carlo source scores from timed evidence (no version step: a stale library is known by the missing symbol): the
+ * trajectories of gnode_sir_mc_philox_sweep -- same candidates, override, shifts, coins and job order -- each compared, for every
+ * possible age t = 0 .. T-1 of the outbreak, with ALL records of an evidence set jointly, and counted by the number of records it
+ * agrees with.  Record i belongs to set rec_set[i] in [0, O) and says that node rec_node[i] was seen rec_offset[i] <= 0 steps
+ * from "now" in kind rec_kind[i] (gnode.dmp.timed_observations' records):
+ *   0 / 1 / 2  it was S / I / R then;   3  it became infected at that step;   4  it recovered at that step.
+ * With t_inf[v], t_rec[v] the event steps of a trajectory as gnode_sir_mc_philox_traj reports them (-1 never; an I start has
+ * t_inf = 0, an R start t_inf = t_rec = 0) and "now" = t, the record is read at model step m = t + offset and is MATCHED when
+ *   m < 0   (before the outbreak: everybody susceptible)  kind == 0
+ *   m >= 0  kind 0: not 0 <= t_inf[v] <= m;   kind 1: 0 <= t_inf[v] <= m and not 0 <= t_rec[v] <= m;   kind 2: 0 <= t_rec[v] <= m;
+ *           kind 3: t_inf[v] == m;   kind 4: t_rec[v] == m.
+ *   rec_set, rec_node, rec_offset, rec_kind   host int32 [R] each, R >= 1; 1 <= O <= 16 (GN_SIR_SCORE_MAXO of the build) sets,
+ *              every one holding a record, and O * T <= 2048 (GN_SIR_TIMED_CELLS: the kernels' difference array in LDS).  A node
+ *              may have several records, in one set or in several.
+ *   bins       1 .. 4096: the bin of (trajectory, t) in set o is k = (agree * bins) / records in integer division, agree the
+ *              matched records of the set and records >= 1 its size: k = bins exactly when EVERY record is matched
+ *   hist       device uint64 [O][C][T][bins + 1], ACCUMULATED by integer atomic adds: hist[o][c][t][k] += 1 for every trajectory
+ *              of candidate c whose age t falls into bin k of set o, so sum_k hist[o][c][t][k] grows by sims.  Exact, whatever
+ *              the order of the jobs, the grid or the path; shards of the sims range add up.  hist[..][bins] / sims is an
+ *              unbiased estimate of the joint likelihood P(all records | source c, age t).
+ * No sums, no ever, no events.  GNODE_ERR_ARG, before any launch and with `hist` untouched: what gnode_sir_mc_philox_sweep
+ * refuses, O outside [1, 16], O * T > 2048, bins outside [1, 4096], O * C * T * (bins + 1) >= 2^31, R < 1, a set outside [0, O),
+ * a node outside [0, n), a kind outside [0, 4], an offset > 0, a set without a record; GNODE_ERR_WORKSPACE: a workspace shorter
+ * than gnode_sir_sweep_timed_workspace_bytes(g, T, P, L, C, O, R) -- the sweep's layout, then an int32 [n + 1] index of the
+ * records by node, one word per record and two int32 [O] tables; the query answers 0 where the sweep's does, for O outside
+ * [1, 16] and for R < 1.  sims = 0 is valid and touches nothing.  SYNCHRONISES `stream`.  edge_scan as above. */
+size_t gnode_sir_sweep_timed_workspace_bytes(gnode_graph_t g, int32_t T, int32_t P, int32_t L, int32_t C, int32_t O, int32_t R);
+int gnode_sir_mc_philox_sweep_timed(gnode_graph_t g, const double* init_host,    /* host fp64 [n][3] */
+                                    const int32_t* candidates_host,              /* host [C] */
+                                    const int32_t* shifts_host,                  /* host [C], or NULL: all 0 */
+                                    int32_t C, int32_t action,
+                                    const int32_t* phase_host, int32_t P, int32_t L,   /* host [L] */
+                                    const double* w_host,                        /* host fp64 [P][nnz] */
+                                    const double* gamma_host,                    /* host fp64 [P][n] */
+                                    const int32_t* rec_set, const int32_t* rec_node,          /* host [R] each */
+                                    const int32_t* rec_offset, const int32_t* rec_kind, int32_t R, int32_t O,
+                                    int32_t bins,
+                                    int64_t sims, int64_t sim_offset, int32_t T, uint64_t rng_seed,
+                                    uint64_t* hist,     /* device [O][C][T][bins + 1], ACCUMULATED */
+                                    void* workspace, size_t workspace_bytes, void* stream, int32_t edge_scan);
 int gnode_sir_mc_coins(const int32_t* table_src, const int32_t* table_dst, int64_t n_table, int32_t n,
                        const int32_t* seeds_host, int32_t n_seeds, double beta, double gamma, int64_t sims,
                        int32_t T, const double* coins, int64_t n_coins, uint32_t* counts,
