@@ -54,6 +54,11 @@
 // trajectories, each compared at every possible age t with all records (node, offset, kind) of up to GN_SIR_SCORE_MAXO evidence
 // sets jointly.  An event moves a difference array over t in LDS; one prefix sum at the end of the trajectory gives the number
 // of matched records per (set, t), and one count per (set, t) goes into the histogram.  Separate instances once more.
+//
+// Nowcast and forecast from timed evidence (gnode_sir_mc_philox_sweep_posterior, the POST instances, SWEEP ones only): the sweep's
+// trajectories, each held against the records of up to GN_SIR_SCORE_MAXO evidence sets at ONE known age `now`.  A trajectory that
+// matches every record of a set is accepted for it, and the state of every node of an accepted trajectory is counted at the steps
+// now + h; a trajectory no set accepts ends at step `now`.  Separate instances once more.
 #include "gnode_common.h"
 #include "gnode_sir_plan.h"
 #include <algorithm>
@@ -301,6 +306,91 @@ __device__ __forceinline__ void sir_timed_finish(const SirTimed<true>& tm, int* 
         atomicAdd(&tm.hist[(((size_t)o * C + c) * T + t) * ((size_t)tm.bins + 1) + k], 1ull);
     }
 }
+// POST instances (gnode_sir_mc_philox_sweep_posterior; SWEEP ones only, never SCORE or TIMED): the sweep's jobs, each compared
+// with the TIMED instances' records at ONE age, `now`, and counted by state where it agrees with all of a set's.  agr[o], int32
+// in LDS, is SirTimed's `dif` of set o SUMMED UP TO CELL `now` -- agree[o][now] -- kept as one number because the cell is known:
+// from zeros[o] on, an event at step `it` of a node with a record (kind, back), pos = it + back, moves it by
+//   v leaves S:   kind 0: -1 iff pos <= now;  kind 1: +1 iff pos <= now;  kind 3: +1 iff pos == now  (the pulse's two ends)
+//   v recovers:   kind 1: -1 iff pos <= now;  kind 2: +1 iff pos <= now;  kind 4: +1 iff pos == now
+// (back is staged as min(back, T) and now < T: a record at T or beyond never moves it).  No event after step `now` moves it, so
+// behind the barrier that closes step `now` -- or behind the last step of a trajectory that ended before -- thread o < O
+// compares agr[o] with records[o]: on equality the trajectory is ACCEPTED for set o, one is added to accepted[o][c], uint64
+// [O][C], and bit o enters the job's mask in LDS.  An empty mask ends the job.  At every step now + horizons[j] that the job
+// closes, and after its end for the horizons that are left (the final state stays), the workgroup walks the nodes, one lane
+// per node, and adds one to counts[o][j][0][v] (v is I) or counts[o][j][1][v] (v is R), uint64 [O][H][2][n], for every set of
+// the mask: a wave's adds to one plane are contiguous.  The job never steps past now + horizons[H - 1].  No sums, no ever, no
+// histogram.  The others take an empty struct, as with SirTimed, and compile to what they were.
+template <bool POST> struct SirPost {};
+template <> struct SirPost<true> {
+    const int32_t* rec_ptr; const uint32_t* rec; const int32_t* zeros; const int32_t* records; const int32_t* horizons; int O, now, H;
+    unsigned long long* counts;     // [O][H][2][n], accumulated
+    unsigned long long* accepted;   // [O][C], accumulated
+};
+// the steps a job runs: T, or (POST) up to the last horizon
+template <bool POST> __device__ __forceinline__ int sir_post_end(const SirPost<POST>& ps, int T) {
+    if constexpr (POST) return ps.now + ps.horizons[ps.H - 1] + 1; else return T;
+}
+// the counters and the mask of a job before its start is drawn, in front of the barrier that resets the counters
+template <bool POST> __device__ __forceinline__ void sir_post_reset(const SirPost<POST>& ps, int* agr, uint32_t* pmask, int tid) {
+    if constexpr (POST) {
+        if (tid < GN_SIR_SCORE_MAXO) agr[tid] = tid < ps.O ? ps.zeros[tid] : 0;
+        if (tid == 0) *pmask = 0u;
+    }
+}
+// KIND 0: node v leaves S at step `it`; KIND 1: it recovers at step `it`
+template <bool POST, int KIND> __device__ __forceinline__ void sir_post_event(const SirPost<POST>& ps, int* agr, int v, int it) {
+    if constexpr (POST) {
+        for (int r = ps.rec_ptr[v], end = ps.rec_ptr[v + 1]; r < end; ++r) {
+            const uint32_t w = ps.rec[r];
+            const int kind = (int)((w >> 4) & 7u), pos = it + (int)(w >> 8);
+            const int step = KIND == 0 ? (kind == 1) - (kind == 0) : (kind == 2) - (kind == 1);
+            const int d = pos <= ps.now ? step + (pos == ps.now && kind == 3 + KIND) : 0;
+            if (d) atomicAdd(&agr[(int)(w & 15u)], d);
+        }
+    }
+}
+// behind a barrier that follows every event up to step `now`: the sets that accept the job (the same word in every thread)
+__device__ __forceinline__ uint32_t sir_post_accept(const SirPost<true>& ps, const int* agr, uint32_t* pmask, int C, int c, int tid) {
+    if (tid < ps.O && agr[tid] == ps.records[tid]) {
+        atomicOr(pmask, 1u << tid);
+        atomicAdd(&ps.accepted[(size_t)tid * C + c], 1ull);     // (integer adds commute: exact whatever the order of the jobs)
+    }
+    __syncthreads();
+    return *pmask;
+}
+// horizon j of an accepted job: state_of(v) is 0 / 1 / 2 = S / I / R of the state that nobody writes meanwhile
+template <class StateOf>
+__device__ __forceinline__ void sir_post_count(const SirPost<true>& ps, uint32_t mask, int j, int n, int tid, int nthr, StateOf state_of) {
+    for (int v = tid; v < n; v += nthr) {
+        const int st = state_of(v);
+        if (st == 0) continue;
+        for (uint32_t m = mask; m; m &= m - 1u) {
+            const int o = __ffs((int)m) - 1;
+            atomicAdd(&ps.counts[(((size_t)o * ps.H + j) * 2 + (st - 1)) * (size_t)n + v], 1ull);
+        }
+    }
+}
+// step `st` of a job is closed by a barrier and the next step has not written to the state.  False: no set accepts the job
+template <bool POST, class StateOf>
+__device__ __forceinline__ bool sir_post_closed(const SirPost<POST>& ps, const int* agr, uint32_t* pmask, int C, int c, int st, int n, int tid,
+                                                int nthr, uint32_t& pacc, int& hj, StateOf state_of) {
+    if constexpr (POST) {
+        if (st == ps.now) { pacc = sir_post_accept(ps, agr, pmask, C, c, tid); if (!pacc) return false; }
+        if (st >= ps.now && hj < ps.H && ps.now + ps.horizons[hj] == st) { sir_post_count(ps, pacc, hj, n, tid, nthr, state_of); ++hj; }
+    }
+    return true;
+}
+// the end of a job whose last closed step is `last`: one that ended before `now` is judged on its final state, which is its
+// state at `now`, and the horizons that are left take the final state, as sir_row_out's rows after an early end do.  The
+// caller's barrier in front of the next job's reset follows.
+template <bool POST, class StateOf>
+__device__ __forceinline__ void sir_post_finish(const SirPost<POST>& ps, const int* agr, uint32_t* pmask, int C, int c, int last, int n, int tid,
+                                                int nthr, uint32_t pacc, int hj, StateOf state_of) {
+    if constexpr (POST) {
+        if (last < ps.now) pacc = sir_post_accept(ps, agr, pmask, C, c, tid);
+        if (pacc) for (; hj < ps.H; ++hj) sir_post_count(ps, pacc, hj, n, tid, nthr, state_of);
+    }
+}
 // where a TRAJ instance writes a row of curves, a SWEEP instance adds it to its candidate's sums
 template <bool SWEEP>
 __device__ __forceinline__ void sir_row_out(uint32_t* __restrict__ curves, const SirSweep<SWEEP>& sw, long s, int c, int T, int row, int n,
@@ -330,20 +420,21 @@ __global__ __launch_bounds__(256) void k_fill_i16(int16_t* __restrict__ p, size_
 #define GN_SIR_UNROLL 8
 #endif
 template <bool STATE_IN_LDS, bool NODES, bool TRAJ, bool EDGES = false, bool INIT = false, bool SCHED = false, bool SWEEP = false,
-          bool SCORE = false, bool TIMED = false>
+          bool SCORE = false, bool TIMED = false, bool POST = false>
 __global__ __launch_bounds__(1024) void k_sir_philox(const int* __restrict__ src, const int* __restrict__ dst, long nnz,
                                                     int n, const int* __restrict__ seeds, int n_seeds,
                                                     SirThr<NODES> thr_beta, SirThr<NODES> thr_gamma,
                                                     long sims, long sim_offset, int T, uint32_t k0, uint32_t k1,
                                                     uint32_t* __restrict__ hist, uint8_t* __restrict__ gstate, SirTraj<TRAJ> tr,
                                                     SirInit<INIT> in, SirSched<SCHED> sc_call, SirSweep<SWEEP> sw, SirScore<SCORE> sr,
-                                                    SirTimed<TIMED> tm) {
+                                                    SirTimed<TIMED> tm, SirPost<POST> ps) {
     static_assert(NODES || !EDGES, "per-edge infection thresholds come with per-node recovery thresholds");
     static_assert(EDGES || !SCHED, "a schedule switches per-edge tables");
     static_assert(!SWEEP || (INIT && SCHED && !TRAJ), "the sweep overrides a drawn start and shifts a schedule; its output is the sums");
     static_assert(!SCORE || SWEEP, "the scores are tallied over the sweep's jobs");
     static_assert(!TIMED || (SWEEP && !SCORE), "the timed evidence is tallied over the sweep's jobs, in place of the snapshots");
-    constexpr bool TALLY = TRAJ || (SWEEP && !TIMED);   // the trajectory's totals are kept in tcnt
+    static_assert(!POST || (SWEEP && !SCORE && !TIMED), "the posterior counts are taken over the sweep's jobs, in place of the scores");
+    constexpr bool TALLY = TRAJ || (SWEEP && !TIMED && !POST);   // the trajectory's totals are kept in tcnt
     extern __shared__ uint8_t smem[];
     uint8_t* state = STATE_IN_LDS ? smem : gstate + (size_t)blockIdx.x * 2 * n;
     uint8_t* flag = state + n;
@@ -355,6 +446,9 @@ __global__ __launch_bounds__(1024) void k_sir_philox(const int* __restrict__ src
     __shared__ int tcnt[2];
     __shared__ int tal[SCORE ? 2 * GN_SIR_SCORE_MAXO : 1];      // (SCORE) the tallies of SirScore; the others never name it
     __shared__ int dif[TIMED ? GN_SIR_TIMED_CELLS : 1];         // (TIMED) the difference array of SirTimed; likewise
+    __shared__ int agr[POST ? GN_SIR_SCORE_MAXO : 1];           // (POST) the matched records at `now` of SirPost; likewise
+    __shared__ uint32_t pmask[1];                               // (POST) the sets that accept the job in hand
+    const auto post_state = [&](int v) -> int { return (int)state[v]; };
     int16_t* ev_inf = nullptr; int16_t* ev_rec = nullptr; uint32_t* curves = nullptr;
     if constexpr (TRAJ) { ev_inf = tr.events; if (tr.events) ev_rec = tr.events + (size_t)sims * n; curves = tr.curves; }
     long jobs = sims;                             // (SWEEP) C * sims of them, the candidates interleaved
@@ -368,6 +462,7 @@ __global__ __launch_bounds__(1024) void k_sir_philox(const int* __restrict__ src
         if (TALLY && threadIdx.x < 2) tcnt[threadIdx.x] = 0;
         sir_score_reset(sr, tal, (int)threadIdx.x);
         sir_timed_reset(tm, dif, T, (int)threadIdx.x, nthr);
+        sir_post_reset(ps, agr, pmask, (int)threadIdx.x);
         __syncthreads();
         if constexpr (INIT) {
             // drawn start: a node that starts in I or R has left S at step 0 (one infection event), one that starts in R
@@ -388,6 +483,8 @@ __global__ __launch_bounds__(1024) void k_sir_philox(const int* __restrict__ src
                     if (r) sir_score_event<SCORE, 1>(sr, tal, v);
                     sir_timed_event<TIMED, 0>(tm, dif, T, v, 0);
                     if (r) sir_timed_event<TIMED, 1>(tm, dif, T, v, 0);
+                    sir_post_event<POST, 0>(ps, agr, v, 0);
+                    if (r) sir_post_event<POST, 1>(ps, agr, v, 0);
                     if (TRAJ && ev_inf) { ev_inf[(size_t)s * n + v] = 0; if (r) ev_rec[(size_t)s * n + v] = 0; }
                 }
                 n_out += __popc(inf | rec); n_gone += __popc(rec);
@@ -410,7 +507,10 @@ __global__ __launch_bounds__(1024) void k_sir_philox(const int* __restrict__ src
             }
         }
         int rows_done = 1;                          // (TRAJ, SWEEP) rows of `curves` / of the sums written so far
-        const bool rows = (SWEEP && !TIMED) || (TRAJ && curves);       // (TIMED: nothing is put out per step)
+        const bool rows = (SWEEP && !TIMED && !POST) || (TRAJ && curves);       // (TIMED, POST: nothing is put out per step)
+        int t_end = sir_post_end(ps, T), plast = 0, hj = 0; uint32_t pacc = 0;   // (POST) the steps to run, the last closed one, the next horizon, the mask
+        if constexpr (POST)                                     // (the start is step 0, closed by the barrier above)
+            if (!sir_post_closed(ps, agr, pmask, sw.C, cj, 0, n, (int)threadIdx.x, nthr, pacc, hj, post_state)) t_end = 0;
         if (rows) {
             __syncthreads();
             if constexpr (SCORE) sir_score_row(sr, tal, sw.C, cj, T, 0, (int)threadIdx.x); else
@@ -419,7 +519,7 @@ __global__ __launch_bounds__(1024) void k_sir_philox(const int* __restrict__ src
                 sir_row_out(curves, sw, s, cj, T, 0, n, tcnt[0], INIT ? tcnt[1] : 0);
             }
         }
-        for (int it = 1; it < T; ++it) {
+        for (int it = 1; it < t_end; ++it) {
             const SirThr<NODES> tb_step = sir_step_thr<NODES>(thr_beta, sc, it, (size_t)nnz), tg_step = sir_step_thr<NODES>(thr_gamma, sc, it, (size_t)n);
             // GN_SIR_UNROLL source ids in flight per thread: the scan is a chain of (global id load -> LDS state read)
             // pairs, latency-bound when issued one at a time.  Wiki-vote-size graph, 10 000 sims x T = 20: 38.8 ms at 1,
@@ -460,12 +560,14 @@ __global__ __launch_bounds__(1024) void k_sir_philox(const int* __restrict__ src
                     state[v] = ST_I; sir_hist_add<SWEEP>(&hinf[(size_t)it * n + v]);
                     sir_score_event<SCORE, 0>(sr, tal, v);
                     sir_timed_event<TIMED, 0>(tm, dif, T, v, it);
+                    sir_post_event<POST, 0>(ps, agr, v, it);
                     if (TALLY) ++n_new;
                     if (TRAJ && ev_inf) ev_inf[(size_t)s * n + v] = (int16_t)it;
                 } else if (f == 2) {
                     state[v] = ST_R; sir_hist_add<SWEEP>(&hrec[(size_t)it * n + v]);
                     sir_score_event<SCORE, 1>(sr, tal, v);
                     sir_timed_event<TIMED, 1>(tm, dif, T, v, it);
+                    sir_post_event<POST, 1>(ps, agr, v, it);
                     if (TALLY) ++n_gone;
                     if (TRAJ && ev_inf) ev_rec[(size_t)s * n + v] = (int16_t)it;
                 }
@@ -480,6 +582,10 @@ __global__ __launch_bounds__(1024) void k_sir_philox(const int* __restrict__ src
                 if (threadIdx.x == 0) sir_row_out(curves, sw, s, cj, T, it, n, tcnt[0], tcnt[1]);
                 rows_done = it + 1;
             }
+            if constexpr (POST) {                   // (the next step writes flag[] alone until its own barrier: the state rests)
+                plast = it;
+                if (!sir_post_closed(ps, agr, pmask, sw.C, cj, it, n, (int)threadIdx.x, nthr, pacc, hj, post_state)) break;
+            }
             if (!alive) break;                      // epidemic over: no further events in this trajectory
         }
         if (rows) {                                 // the rows after an early end repeat the final state
@@ -489,6 +595,7 @@ __global__ __launch_bounds__(1024) void k_sir_philox(const int* __restrict__ src
             if constexpr (SWEEP && !SCORE) if (sw.ever && threadIdx.x == 0) sw.ever[(size_t)cj * sims + s] = (uint32_t)(n_ever - rec0);
         }
         if constexpr (TIMED) sir_timed_finish(tm, dif, sw.C, cj, T, (int)threadIdx.x, nthr);   // (every event lies behind a barrier)
+        if constexpr (POST) sir_post_finish(ps, agr, pmask, sw.C, cj, plast, n, (int)threadIdx.x, nthr, pacc, hj, post_state);   // (likewise)
         __syncthreads();
     }
 }
@@ -508,17 +615,19 @@ __global__ __launch_bounds__(1024) void k_sir_philox(const int* __restrict__ src
 // TRAJ: per-trajectory events and curves (SirTraj above); there is no COUNT && TRAJ instance.
 // SWEEP: the candidate sweep (SirSweep above): jobs instead of trajectories, sums instead of histograms.
 template <typename IdT, bool LISTS_IN_LDS, bool COUNT, bool NODES, bool TRAJ, bool EDGES = false, bool INIT = false, bool SCHED = false,
-          bool SWEEP = false, bool SCORE = false, bool TIMED = false>
+          bool SWEEP = false, bool SCORE = false, bool TIMED = false, bool POST = false>
 __global__ __launch_bounds__(1024) void k_sir_frontier(const int* __restrict__ rowptr, const int* __restrict__ col, int n,
                                                       const int* __restrict__ seeds, int n_seeds,
                                                       SirThr<NODES> thr_beta, SirThr<NODES> thr_gamma,
                                                       long sims, long sim_offset, int T, uint32_t k0, uint32_t k1,
                                                       uint32_t* __restrict__ hist, int32_t* __restrict__ glists,
                                                       unsigned long long* __restrict__ stats, SirTraj<TRAJ> tr, SirInit<INIT> in,
-                                                      SirSched<SCHED> sc_call, SirSweep<SWEEP> sw, SirScore<SCORE> sr, SirTimed<TIMED> tm) {
+                                                      SirSched<SCHED> sc_call, SirSweep<SWEEP> sw, SirScore<SCORE> sr, SirTimed<TIMED> tm,
+                                                      SirPost<POST> ps) {
     static_assert(!SWEEP || (INIT && SCHED && !TRAJ), "the sweep overrides a drawn start and shifts a schedule; its output is the sums");
     static_assert(!SCORE || SWEEP, "the scores are tallied over the sweep's jobs");
     static_assert(!TIMED || (SWEEP && !SCORE), "the timed evidence is tallied over the sweep's jobs, in place of the snapshots");
+    static_assert(!POST || (SWEEP && !SCORE && !TIMED), "the posterior counts are taken over the sweep's jobs, in place of the scores");
     static_assert(!(COUNT && INIT), "the counting instantiation starts from a seed list");
     static_assert(EDGES || !SCHED, "a schedule switches per-edge tables");
     static_assert(!(COUNT && TRAJ), "the counting instantiation has no per-trajectory output");
@@ -541,6 +650,12 @@ __global__ __launch_bounds__(1024) void k_sir_frontier(const int* __restrict__ r
     __shared__ int cnt[3];                                     // [0] next-list length, [1] big-row list length, [2] ever infected
     __shared__ int tal[SCORE ? 2 * GN_SIR_SCORE_MAXO : 1];     // (SCORE) the tallies of SirScore; the others never name it
     __shared__ int dif[TIMED ? GN_SIR_TIMED_CELLS : 1];        // (TIMED) the difference array of SirTimed; likewise
+    __shared__ int agr[POST ? GN_SIR_SCORE_MAXO : 1];          // (POST) the matched records at `now` of SirPost; likewise
+    __shared__ uint32_t pmask[1];                              // (POST) the sets that accept the job in hand
+    const auto post_state = [&](int v) -> int {                // (POST) S / I / R of node v off the two bitmaps
+        const uint32_t m = 1u << (v & 31);
+        return (bits[v >> 5] & m) ? ((recb[v >> 5] & m) ? 2 : 1) : 0;
+    };
     uint32_t* hinf = hist;
     uint32_t* hrec = hist + (size_t)T * n;
     const int nthr = blockDim.x, tid = threadIdx.x;
@@ -561,6 +676,7 @@ __global__ __launch_bounds__(1024) void k_sir_frontier(const int* __restrict__ r
         if (tid < 3) cnt[tid] = 0;
         sir_score_reset(sr, tal, tid);
         sir_timed_reset(tm, dif, T, tid, nthr);
+        sir_post_reset(ps, agr, pmask, tid);
         __syncthreads();
         if constexpr (INIT) {
             // drawn start (sir_init_draw): I and R starts have left S (ever-infected bit, one infection event at t = 0), R
@@ -585,6 +701,8 @@ __global__ __launch_bounds__(1024) void k_sir_frontier(const int* __restrict__ r
                         if (r) sir_score_event<SCORE, 1>(sr, tal, u0 + j);
                         sir_timed_event<TIMED, 0>(tm, dif, T, u0 + j, 0);
                         if (r) sir_timed_event<TIMED, 1>(tm, dif, T, u0 + j, 0);
+                        sir_post_event<POST, 0>(ps, agr, u0 + j, 0);
+                        if (r) sir_post_event<POST, 1>(ps, agr, u0 + j, 0);
                         if (TRAJ && ev_inf) { ev_inf[(size_t)s * n + u0 + j] = 0; if (r) ev_rec[(size_t)s * n + u0 + j] = 0; }
                     }
                 // this wave's I starts: slot = wave base + the I starts of the lanes below + this lane's own in front
@@ -619,11 +737,14 @@ __global__ __launch_bounds__(1024) void k_sir_frontier(const int* __restrict__ r
         __syncthreads();
         if (tid == 0) cnt[2] = n_ever;
         int rows_done = 1;                                     // (TRAJ, SWEEP) rows of `curves` / of the sums written so far
-        const bool rows = (SWEEP && !TIMED) || (TRAJ && curves);   // (TIMED: nothing is put out per step)
+        const bool rows = (SWEEP && !TIMED && !POST) || (TRAJ && curves);   // (TIMED, POST: nothing is put out per step)
+        int t_end = sir_post_end(ps, T), plast = 0, hj = 0; uint32_t pacc = 0;   // (POST) the steps to run, the last closed one, the next horizon, the mask
+        if constexpr (POST)                                    // (the start is step 0, closed by the barriers above; the first step's writes lie behind its own)
+            if (!sir_post_closed(ps, agr, pmask, sw.C, cj, 0, n, tid, nthr, pacc, hj, post_state)) t_end = 0;
         const int rec0 = n_ever - n_inf;                       // (SWEEP) the R starts: they were never infected
         if constexpr (SCORE) sir_score_row(sr, tal, sw.C, cj, T, 0, tid); else
         if (rows && tid == 0) sir_row_out(curves, sw, s, cj, T, 0, n, n_ever, INIT ? n_ever - n_inf : 0);
-        for (int it = 1; it < T && n_inf > 0; ++it) {
+        for (int it = 1; it < t_end && n_inf > 0; ++it) {
             // this step's tables: drain, the recovery loop and the recovery-only branch read nothing else
             const SirThr<NODES> tb_step = sir_step_thr<NODES>(thr_beta, sc, it, sched_nnz), tg_step = sir_step_thr<NODES>(thr_gamma, sc, it, (size_t)n);
             if (tid == 0) { cnt[0] = 0; cnt[1] = 0; }
@@ -651,6 +772,7 @@ __global__ __launch_bounds__(1024) void k_sir_frontier(const int* __restrict__ r
                                 gone |= 1u << j; sir_hist_add<SWEEP>(&hrec[(size_t)it * n + u0 + j]);
                                 sir_score_event<SCORE, 1>(sr, tal, u0 + j);
                                 sir_timed_event<TIMED, 1>(tm, dif, T, u0 + j, it);
+                                sir_post_event<POST, 1>(ps, agr, u0 + j, it);
                                 if (TRAJ && ev_inf) ev_rec[(size_t)s * n + u0 + j] = (int16_t)it;
                             } else ++alive;
                         }
@@ -666,6 +788,7 @@ __global__ __launch_bounds__(1024) void k_sir_frontier(const int* __restrict__ r
                     rows_done = it + 1;
                 }
                 __syncthreads();
+                if constexpr (POST) { plast = it; if (!sir_post_closed(ps, agr, pmask, sw.C, cj, it, n, tid, nthr, pacc, hj, post_state)) break; }
                 continue;
             }
             // infection attempts along the out-edges of the frontier: one 16-lane group per infected node, a lane takes
@@ -678,6 +801,7 @@ __global__ __launch_bounds__(1024) void k_sir_frontier(const int* __restrict__ r
                     sir_hist_add<SWEEP>(&hinf[(size_t)it * n + v]);
                     sir_score_event<SCORE, 0>(sr, tal, v);
                     sir_timed_event<TIMED, 0>(tm, dif, T, v, it);
+                    sir_post_event<POST, 0>(ps, agr, v, it);
                     if (TRAJ && ev_inf) ev_inf[(size_t)s * n + v] = (int16_t)it;
                 }
             };
@@ -771,6 +895,7 @@ __global__ __launch_bounds__(1024) void k_sir_frontier(const int* __restrict__ r
                     sir_hist_add<SWEEP>(&hrec[(size_t)it * n + u]);
                     sir_score_event<SCORE, 1>(sr, tal, u);
                     sir_timed_event<TIMED, 1>(tm, dif, T, u, it);
+                    sir_post_event<POST, 1>(ps, agr, u, it);
                     if (TRAJ && ev_inf) ev_rec[(size_t)s * n + u] = (int16_t)it;
                     atomicOr(&recb[u >> 5], 1u << (u & 31));
                 }
@@ -799,15 +924,18 @@ __global__ __launch_bounds__(1024) void k_sir_frontier(const int* __restrict__ r
             }
             IdT* t = cur; cur = nxt; nxt = t;
             __syncthreads();
+            // (POST) the next step's first write to a bitmap lies behind its own barrier: the walk reads a state at rest
+            if constexpr (POST) { plast = it; if (!sir_post_closed(ps, agr, pmask, sw.C, cj, it, n, tid, nthr, pacc, hj, post_state)) break; }
         }
         if (rows) {                                            // the rows after an early end repeat the final state
             if constexpr (SCORE) sir_score_rows_after(sr, tal, sw.C, cj, T, rows_done, tid, nthr); else
             for (int r = rows_done + tid; r < T; r += nthr) sir_row_out(curves, sw, s, cj, T, r, n, n_ever, n_ever - n_inf);
         }
-        if constexpr (SWEEP && !SCORE && !TIMED) if (sw.ever && tid == 0) sw.ever[(size_t)cj * sims + s] = (uint32_t)(n_ever - rec0);
+        if constexpr (SWEEP && !SCORE && !TIMED && !POST) if (sw.ever && tid == 0) sw.ever[(size_t)cj * sims + s] = (uint32_t)(n_ever - rec0);
         if constexpr (SCORE) __syncthreads();                  // those rows read the tallies: the next job resets them behind this
         // (every step ends in a barrier, and so does the start: every event lies behind one)
         if constexpr (TIMED) { sir_timed_finish(tm, dif, sw.C, cj, T, tid, nthr); __syncthreads(); }
+        if constexpr (POST) { sir_post_finish(ps, agr, pmask, sw.C, cj, plast, n, tid, nthr, pacc, hj, post_state); __syncthreads(); }
     }
     if (COUNT) {
         atomicAdd(&stats[0], st_blocks); atomicAdd(&stats[1], st_ecoins); atomicAdd(&stats[2], st_rcoins); atomicAdd(&stats[3], st_entries);
@@ -938,13 +1066,15 @@ __global__ void k_put_seeds(SeedArg sa, int n_seeds, int32_t* __restrict__ seeds
 // SWEEP_: the candidate sweep, one form (the drawn-start scheduled one without per-trajectory output), through sir_dispatch_sweep.
 // SCORE_: the source scores, the sweep's form with the similarity tallies, through sir_dispatch_score.
 // TIMED_: the scores from timed evidence, the sweep's form with the difference array, through sir_dispatch_timed.
-template <int RATES, bool TRAJ_, bool INIT_, bool SCHED_ = false, bool SWEEP_ = false, bool SCORE_ = false, bool TIMED_ = false> struct SirKernels {
+// POST_: the posterior counts at one age, the sweep's form with the matched-record counters, through sir_dispatch_post.
+template <int RATES, bool TRAJ_, bool INIT_, bool SCHED_ = false, bool SWEEP_ = false, bool SCORE_ = false, bool TIMED_ = false, bool POST_ = false>
+struct SirKernels {
     static constexpr bool NODES = RATES >= SIR_NODES, EDGES = RATES == SIR_EDGES, TRAJ = TRAJ_, INIT = INIT_, SCHED = SCHED_, SWEEP = SWEEP_, SCORE = SCORE_;
-    static constexpr bool TIMED = TIMED_;
-    static constexpr auto frontier_lds = &k_sir_frontier<uint16_t, true, false, NODES, TRAJ, EDGES, INIT, SCHED, SWEEP, SCORE, TIMED>;
-    static constexpr auto frontier_mem = &k_sir_frontier<int32_t, false, false, NODES, TRAJ, EDGES, INIT, SCHED, SWEEP, SCORE, TIMED>;
-    static constexpr auto scan_lds = &k_sir_philox<true, NODES, TRAJ, EDGES, INIT, SCHED, SWEEP, SCORE, TIMED>;
-    static constexpr auto scan_mem = &k_sir_philox<false, NODES, TRAJ, EDGES, INIT, SCHED, SWEEP, SCORE, TIMED>;
+    static constexpr bool TIMED = TIMED_, POST = POST_;
+    static constexpr auto frontier_lds = &k_sir_frontier<uint16_t, true, false, NODES, TRAJ, EDGES, INIT, SCHED, SWEEP, SCORE, TIMED, POST>;
+    static constexpr auto frontier_mem = &k_sir_frontier<int32_t, false, false, NODES, TRAJ, EDGES, INIT, SCHED, SWEEP, SCORE, TIMED, POST>;
+    static constexpr auto scan_lds = &k_sir_philox<true, NODES, TRAJ, EDGES, INIT, SCHED, SWEEP, SCORE, TIMED, POST>;
+    static constexpr auto scan_mem = &k_sir_philox<false, NODES, TRAJ, EDGES, INIT, SCHED, SWEEP, SCORE, TIMED, POST>;
 };
 // the counting instances (gnode_sir_mc_philox_counted): the frontier walk of SirKernels<SIR_SCALAR, false, false>
 static constexpr auto kSirCountedLds = &k_sir_frontier<uint16_t, true, true, false, false>;
@@ -966,6 +1096,7 @@ template <class F> static void sir_dispatch_sched(bool traj, bool init, F&& f) {
 template <class F> static void sir_dispatch_sweep(F&& f) { f(SirKernels<SIR_EDGES, false, true, true, true>{}); }
 template <class F> static void sir_dispatch_score(F&& f) { f(SirKernels<SIR_EDGES, false, true, true, true, true>{}); }
 template <class F> static void sir_dispatch_timed(F&& f) { f(SirKernels<SIR_EDGES, false, true, true, true, false, true>{}); }
+template <class F> static void sir_dispatch_post(F&& f) { f(SirKernels<SIR_EDGES, false, true, true, true, false, false, true>{}); }
 
 int gn_sir_set_attributes() {       // once per device, from gnode_graph_create
     hipError_t err = hipSuccess;
@@ -981,6 +1112,7 @@ int gn_sir_set_attributes() {       // once per device, from gnode_graph_create
     // (the SCORE instances' static tallies come on top: sir_launch_plan keeps dynamic + kSirScoreLds within kLdsStateLimit)
     sir_dispatch_score([&](auto K) { lift(K.frontier_lds); lift(K.frontier_mem); lift(K.scan_lds); });
     sir_dispatch_timed([&](auto K) { lift(K.frontier_lds); lift(K.frontier_mem); lift(K.scan_lds); });    // (likewise, kSirTimedLds)
+    sir_dispatch_post([&](auto K) { lift(K.frontier_lds); lift(K.frontier_mem); lift(K.scan_lds); });     // (likewise, kSirPostLds)
     lift(kSirCountedLds); lift(kSirCountedMem); lift(&k_sir_coins);
     GN_HIP(err);
     return 0;
@@ -1105,11 +1237,11 @@ static int sir_mc_philox_impl(const SirCall& c) {
                 auto kernel = P.path == SIR_FRONTIER_LDS ? Kt::frontier_lds : Kt::frontier_mem;
                 if constexpr (!Kt::NODES && !Kt::TRAJ && !Kt::INIT) if (stats) kernel = P.path == SIR_FRONTIER_LDS ? kSirCountedLds : kSirCountedMem;
                 hipLaunchKernelGGL(kernel, dim3(P.grid), dim3(P.threads), P.lds, st, g->rowptr, g->col, n, seeds, c.n_seeds, tb, tg, (long)c.sims,
-                                   (long)c.sim_offset, T, k0, k1, hist, (int32_t*)tail, stats, tr, in, sc, SirSweep<false>{}, SirScore<false>{}, SirTimed<false>{});
+                                   (long)c.sim_offset, T, k0, k1, hist, (int32_t*)tail, stats, tr, in, sc, SirSweep<false>{}, SirScore<false>{}, SirTimed<false>{}, SirPost<false>{});
             } else {
                 auto kernel = P.path == SIR_SCAN_LDS ? Kt::scan_lds : Kt::scan_mem;
                 hipLaunchKernelGGL(kernel, dim3(P.grid), dim3(P.threads), P.lds, st, g->src, g->col, (long)g->nnz, n, seeds, c.n_seeds, tb, tg, (long)c.sims,
-                                   (long)c.sim_offset, T, k0, k1, hist, (uint8_t*)tail, tr, in, sc, SirSweep<false>{}, SirScore<false>{}, SirTimed<false>{});
+                                   (long)c.sim_offset, T, k0, k1, hist, (uint8_t*)tail, tr, in, sc, SirSweep<false>{}, SirScore<false>{}, SirTimed<false>{}, SirPost<false>{});
             }
         };
         // the drawn start and the schedule are sets of instances of their own: the others do not carry them
@@ -1231,37 +1363,46 @@ extern "C" size_t gnode_sir_sweep_workspace_bytes(gnode_graph_t g, int32_t T, in
     return g && T >= 1 && P >= 1 && L >= T && C >= 1 ? sir_sweep_layout(g->info.n, g->nnz, g->n_bigrow, T, P, L, C).total : 0;
 }
 // The sweep's call, the scores' (score non-null: the snapshots as the caller holds them, int8 [O][n], and the histogram in
-// place of sums and ever) and the timed scores' (timed non-null: the R records as four host arrays, and the histogram): one
-// set of checks, one staging, one launch.
+// place of sums and ever), the timed scores' (timed non-null: the R records as four host arrays, and the histogram) and the
+// posterior counts' (post non-null: the records, the age, the horizons, and the two count arrays): one set of checks, one
+// staging, one launch.
 struct SirScoreCall { const int8_t* obs; int32_t O, measure, bins; uint64_t* hist; };
 struct SirTimedCall { const int32_t *rec_set, *rec_node, *rec_offset, *rec_kind; int32_t R, O, bins; uint64_t* hist; };
+struct SirPostCall { const int32_t *rec_set, *rec_node, *rec_offset, *rec_kind; int32_t R, O, now; const int32_t* horizons; int32_t H; uint64_t *counts, *accepted; };
 static int sir_sweep_impl(const char* who, gnode_graph_t g, const double* init_host, const int32_t* candidates_host, const int32_t* shifts_host,
                           int32_t C, int32_t action, const int32_t* phase_host, int32_t P, int32_t L, const double* w_host,
                           const double* gamma_host, int64_t sims, int64_t sim_offset, int32_t T, uint64_t rng_seed, uint64_t* sums,
                           uint32_t* ever, void* workspace, size_t workspace_bytes, void* stream, int32_t edge_scan, const SirScoreCall* score,
-                          const SirTimedCall* timed = nullptr) {
+                          const SirTimedCall* timed = nullptr, const SirPostCall* post = nullptr) {
     const hipStream_t st = (hipStream_t)stream;
-    GN_CHECK_ARG(g && workspace && init_host && candidates_host && (score ? score->obs && score->hist : timed ? timed->hist != nullptr : sums != nullptr), "%s: null pointer", who);
+    GN_CHECK_ARG(g && workspace && init_host && candidates_host && (score ? score->obs && score->hist : timed ? timed->hist != nullptr :
+                 post ? post->counts && post->accepted : sums != nullptr), "%s: null pointer", who);
     GN_CHECK_ARG(!timed || timed->R < 1 || (timed->rec_set && timed->rec_node && timed->rec_offset && timed->rec_kind), "%s: null pointer", who);
+    GN_CHECK_ARG(!post || post->R < 1 || (post->rec_set && post->rec_node && post->rec_offset && post->rec_kind), "%s: null pointer", who);
+    GN_CHECK_ARG(!post || post->H < 1 || post->horizons, "%s: null pointer", who);
     GN_CHECK_ARG(P >= 1 && gamma_host && (w_host || g->nnz == 0) && (phase_host || L <= 1), "%s: a schedule takes P >= 1 phases (P = %d), the phase row and both rate tables", who, P);
     GN_CHECK_ARG(C >= 1, "%s: C = %d: at least one candidate", who, C);
     GN_CHECK_ARG(action == 0 || action == 1, "%s: action %d is neither 0 (seed) nor 1 (immunise)", who, action);
     GN_CHECK_ARG(T >= 1 && sims >= 0 && sims <= 0xFFFFFFFFll && sim_offset >= 0 && sim_offset + sims <= 0xFFFFFFFFll, "%s: bad T/sims/sim_offset", who);
     GN_CHECK_ARG(L >= T, "%s: the phase row holds L = %d entries, fewer than T = %d", who, L, T);
     const int n = g->info.n;
-    const size_t static_lds = score ? kSirScoreLds : timed ? kSirTimedLds : 0;
+    const size_t static_lds = score ? kSirScoreLds : timed ? kSirTimedLds : post ? kSirPostLds : 0;
     const SirScoreLayout WS = score ? sir_score_layout(n, g->nnz, g->n_bigrow, T, P, L, C, score->O) : SirScoreLayout{};
     const SirTimedLayout WT = timed ? sir_timed_layout(n, g->nnz, g->n_bigrow, T, P, L, C, timed->O, timed->R) : SirTimedLayout{};
+    const SirPostLayout WP = post ? sir_post_layout(n, g->nnz, g->n_bigrow, T, P, L, C, post->O, post->R, post->H) : SirPostLayout{};
     const SirSweepLayout W = score ? static_cast<const SirSweepLayout&>(WS) : timed ? static_cast<const SirSweepLayout&>(WT)
-                                   : sir_sweep_layout(n, g->nnz, g->n_bigrow, T, P, L, C);
+                           : post ? static_cast<const SirSweepLayout&>(WP) : sir_sweep_layout(n, g->nnz, g->n_bigrow, T, P, L, C);
     SirScoreStaged staged;
     SirTimedStaged records;
+    SirPostStaged posted;
     if (score) staged = sir_stage_score(who, n, g->nnz, T, P, L, phase_host, w_host, gamma_host, init_host, C, shifts_host, score->obs, score->O, score->measure, score->bins);
     else if (timed) records = sir_stage_timed(who, n, g->nnz, T, P, L, phase_host, w_host, gamma_host, init_host, C, shifts_host, timed->rec_set, timed->rec_node,
                                               timed->rec_offset, timed->rec_kind, timed->R, timed->O, timed->bins);
+    else if (post) posted = sir_stage_post(who, n, g->nnz, T, P, L, phase_host, w_host, gamma_host, init_host, C, shifts_host, post->rec_set, post->rec_node,
+                                           post->rec_offset, post->rec_kind, post->R, post->O, post->now, post->horizons, post->H);
     else staged.thr = sir_stage_sweep(who, n, g->nnz, T, P, L, phase_host, w_host, gamma_host, init_host, C, shifts_host);
-    const SirThresholds& thr = timed ? records.thr : staged.thr;
-    if (score || timed) GN_CHECK_ARG(thr.error.empty(), "%s", thr.error.c_str());   // (the scores: an argument is refused before the workspace is asked about)
+    const SirThresholds& thr = timed ? records.thr : post ? posted.thr : staged.thr;
+    if (score || timed || post) GN_CHECK_ARG(thr.error.empty(), "%s", thr.error.c_str());   // (the scores: an argument is refused before the workspace is asked about)
     if (workspace_bytes < W.total) {
         gnode_set_error("%s: workspace %zu < %zu", who, workspace_bytes, W.total);
         return GNODE_ERR_WORKSPACE;
@@ -1288,6 +1429,13 @@ static int sir_sweep_impl(const char* who, gnode_graph_t g, const double* init_h
         GN_HIP(hipMemcpyAsync(ws + WT.zeros, records.zeros.data(), sizeof(int32_t) * records.zeros.size(), hipMemcpyHostToDevice, st));
         GN_HIP(hipMemcpyAsync(ws + WT.records, records.records.data(), sizeof(int32_t) * records.records.size(), hipMemcpyHostToDevice, st));
     }
+    if (post) {
+        GN_HIP(hipMemcpyAsync(ws + WP.rec_ptr, posted.rec_ptr.data(), sizeof(int32_t) * posted.rec_ptr.size(), hipMemcpyHostToDevice, st));
+        GN_HIP(hipMemcpyAsync(ws + WP.rec, posted.rec.data(), sizeof(uint32_t) * posted.rec.size(), hipMemcpyHostToDevice, st));
+        GN_HIP(hipMemcpyAsync(ws + WP.zeros, posted.zeros.data(), sizeof(int32_t) * posted.zeros.size(), hipMemcpyHostToDevice, st));
+        GN_HIP(hipMemcpyAsync(ws + WP.records, posted.records.data(), sizeof(int32_t) * posted.records.size(), hipMemcpyHostToDevice, st));
+        GN_HIP(hipMemcpyAsync(ws + WP.horizons, posted.horizons.data(), sizeof(int32_t) * posted.horizons.size(), hipMemcpyHostToDevice, st));
+    }
     GN_HIP(hipStreamSynchronize(st));                          // the host arrays are done with
     if (sims == 0) return 0;
     const uint32_t k0 = (uint32_t)(rng_seed & 0xFFFFFFFFull), k1 = (uint32_t)(rng_seed >> 32);
@@ -1309,17 +1457,23 @@ static int sir_sweep_impl(const char* who, gnode_graph_t g, const double* init_h
             tm.rec_ptr = (const int32_t*)(ws + WT.rec_ptr); tm.rec = (const uint32_t*)(ws + WT.rec); tm.zeros = (const int32_t*)(ws + WT.zeros);
             tm.records = (const int32_t*)(ws + WT.records); tm.O = timed->O; tm.bins = timed->bins; tm.hist = (unsigned long long*)timed->hist;
         }
+        SirPost<Kt::POST> ps;
+        if constexpr (Kt::POST) {
+            ps.rec_ptr = (const int32_t*)(ws + WP.rec_ptr); ps.rec = (const uint32_t*)(ws + WP.rec); ps.zeros = (const int32_t*)(ws + WP.zeros);
+            ps.records = (const int32_t*)(ws + WP.records); ps.horizons = (const int32_t*)(ws + WP.horizons); ps.O = post->O; ps.now = post->now;
+            ps.H = post->H; ps.counts = (unsigned long long*)post->counts; ps.accepted = (unsigned long long*)post->accepted;
+        }
         if (Pl.path == SIR_FRONTIER_LDS || Pl.path == SIR_FRONTIER_MEM) {
             auto kernel = Pl.path == SIR_FRONTIER_LDS ? Kt::frontier_lds : Kt::frontier_mem;
             hipLaunchKernelGGL(kernel, dim3(Pl.grid), dim3(Pl.threads), Pl.lds, st, g->rowptr, g->col, n, (const int*)nullptr, 0, thr_b, thr_g, (long)sims,
-                               (long)sim_offset, T, k0, k1, (uint32_t*)nullptr, (int32_t*)tail, (unsigned long long*)nullptr, SirTraj<false>{}, in, sc, sw, sr, tm);
+                               (long)sim_offset, T, k0, k1, (uint32_t*)nullptr, (int32_t*)tail, (unsigned long long*)nullptr, SirTraj<false>{}, in, sc, sw, sr, tm, ps);
         } else {
             auto kernel = Pl.path == SIR_SCAN_LDS ? Kt::scan_lds : Kt::scan_mem;
             hipLaunchKernelGGL(kernel, dim3(Pl.grid), dim3(Pl.threads), Pl.lds, st, g->src, g->col, (long)g->nnz, n, (const int*)nullptr, 0, thr_b, thr_g,
-                               (long)sims, (long)sim_offset, T, k0, k1, (uint32_t*)nullptr, (uint8_t*)tail, SirTraj<false>{}, in, sc, sw, sr, tm);
+                               (long)sims, (long)sim_offset, T, k0, k1, (uint32_t*)nullptr, (uint8_t*)tail, SirTraj<false>{}, in, sc, sw, sr, tm, ps);
         }
     };
-    if (score) sir_dispatch_score(launch); else if (timed) sir_dispatch_timed(launch); else sir_dispatch_sweep(launch);
+    if (score) sir_dispatch_score(launch); else if (timed) sir_dispatch_timed(launch); else if (post) sir_dispatch_post(launch); else sir_dispatch_sweep(launch);
     if (sampled) gn_prof_end(3, st);
     GN_LAUNCH_CHECK();
     return 0;
@@ -1362,6 +1516,23 @@ extern "C" int gnode_sir_mc_philox_sweep_timed(gnode_graph_t g, const double* in
     const SirTimedCall timed = {rec_set, rec_node, rec_offset, rec_kind, R, O, bins, hist};
     return sir_sweep_impl("gnode_sir_mc_philox_sweep_timed", g, init_host, candidates_host, shifts_host, C, action, phase_host, P, L, w_host, gamma_host,
                           sims, sim_offset, T, rng_seed, nullptr, nullptr, workspace, workspace_bytes, stream, edge_scan, nullptr, &timed);
+}
+
+// Nowcast and forecast from timed evidence (POST instances): the sweep's trajectories, each accepted for the evidence sets whose
+// records it matches at age `now`, and the states of the accepted ones counted per node at now + horizons[j]; no sums.
+extern "C" size_t gnode_sir_sweep_posterior_workspace_bytes(gnode_graph_t g, int32_t T, int32_t P, int32_t L, int32_t C, int32_t O, int32_t R, int32_t H) {
+    return g && T >= 1 && P >= 1 && L >= T && C >= 1 && O >= 1 && O <= GN_SIR_SCORE_MAXO && R >= 1 && H >= 1 && H <= GN_SIR_POST_MAXH
+               ? sir_post_layout(g->info.n, g->nnz, g->n_bigrow, T, P, L, C, O, R, H).total : 0;
+}
+extern "C" int gnode_sir_mc_philox_sweep_posterior(gnode_graph_t g, const double* init_host, const int32_t* candidates_host, const int32_t* shifts_host,
+                                                   int32_t C, int32_t action, const int32_t* phase_host, int32_t P, int32_t L, const double* w_host,
+                                                   const double* gamma_host, const int32_t* rec_set, const int32_t* rec_node, const int32_t* rec_offset,
+                                                   const int32_t* rec_kind, int32_t R, int32_t O, int32_t now, const int32_t* horizons_host, int32_t H,
+                                                   int64_t sims, int64_t sim_offset, int32_t T, uint64_t rng_seed, uint64_t* counts, uint64_t* accepted,
+                                                   void* workspace, size_t workspace_bytes, void* stream, int32_t edge_scan) {
+    const SirPostCall post = {rec_set, rec_node, rec_offset, rec_kind, R, O, now, horizons_host, H, counts, accepted};
+    return sir_sweep_impl("gnode_sir_mc_philox_sweep_posterior", g, init_host, candidates_host, shifts_host, C, action, phase_host, P, L, w_host,
+                          gamma_host, sims, sim_offset, T, rng_seed, nullptr, nullptr, workspace, workspace_bytes, stream, edge_scan, nullptr, nullptr, &post);
 }
 
 extern "C" int gnode_sir_mc_coins(const int32_t* table_src, const int32_t* table_dst, int64_t n_table, int32_t n,

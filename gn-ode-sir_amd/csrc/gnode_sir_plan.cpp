@@ -242,6 +242,41 @@ SirTimedLayout sir_timed_layout(int n, int64_t nnz, int n_bigrow, int T, int P, 
     return W;
 }
 
+// The records of a timed call (sir_stage_timed, sir_stage_post), in two halves around the sweep's own staging.  The checks: R >= 1,
+// every set in [0, O), node in [0, n), kind in [0, 4] and offset <= 0, every set holding a record; they count zeros[o],
+// records[o] and, in ptr[v + 1], the records of node v.  A refusal (the message; empty: accepted) names the offending index.
+static std::string check_records(const char* who, int n, const int32_t* rec_set, const int32_t* rec_node, const int32_t* rec_offset,
+                                 const int32_t* rec_kind, int R, int O, std::vector<int32_t>& zeros, std::vector<int32_t>& records,
+                                 std::vector<int32_t>& ptr) {
+    char buf[256];
+#define refuse_rec(...) (snprintf(buf, sizeof buf, __VA_ARGS__), std::string(buf))
+    if (R < 1) return refuse_rec("%s: R = %d records: at least one", who, R);
+    zeros.assign((size_t)O, 0); records.assign((size_t)O, 0); ptr.assign((size_t)n + 1, 0);
+    for (int i = 0; i < R; ++i) {
+        if (rec_set[i] < 0 || rec_set[i] >= O) return refuse_rec("%s: rec_set[%d] = %d is not in [0, %d)", who, i, rec_set[i], O);
+        if (rec_node[i] < 0 || rec_node[i] >= n) return refuse_rec("%s: rec_node[%d] = %d is not in [0, %d)", who, i, rec_node[i], n);
+        if (rec_kind[i] < 0 || rec_kind[i] > 4) return refuse_rec("%s: rec_kind[%d] = %d is not a kind in [0, 4]", who, i, rec_kind[i]);
+        if (rec_offset[i] > 0) return refuse_rec("%s: rec_offset[%d] = %d is after now: offsets are <= 0", who, i, rec_offset[i]);
+        ++records[rec_set[i]]; zeros[rec_set[i]] += rec_kind[i] == 0; ++ptr[(size_t)rec_node[i] + 1];
+    }
+    for (int o = 0; o < O; ++o)
+        if (records[o] == 0) return refuse_rec("%s: evidence set %d holds no record", who, o);
+#undef refuse_rec
+    return std::string();
+}
+// The sort: by node, a node's records in the order given, one word each -- set | kind << 4 | min(-offset, T) << 8.
+static void sort_records(int n, int T, const int32_t* rec_set, const int32_t* rec_node, const int32_t* rec_offset, const int32_t* rec_kind, int R,
+                         std::vector<int32_t>& ptr, SirTimedStaged& s) {
+    for (int v = 0; v < n; ++v) ptr[(size_t)v + 1] += ptr[v];
+    std::vector<int32_t> at(ptr.begin(), ptr.end() - 1);
+    s.rec.resize((size_t)R);
+    for (int i = 0; i < R; ++i) {
+        const int64_t back = std::min<int64_t>(-(int64_t)rec_offset[i], std::max(T, 0));   // (at T or beyond: never reached)
+        s.rec[(size_t)at[rec_node[i]]++] = (uint32_t)rec_set[i] | (uint32_t)rec_kind[i] << 4 | (uint32_t)back << 8;
+    }
+    s.rec_ptr = std::move(ptr);
+}
+
 SirTimedStaged sir_stage_timed(const char* who, int n, int64_t nnz, int T, int P, int L, const int32_t* phase, const double* w,
                                const double* gamma, const double* init, int C, const int32_t* shifts, const int32_t* rec_set,
                                const int32_t* rec_node, const int32_t* rec_offset, const int32_t* rec_kind, int R, int O, int bins) {
@@ -254,27 +289,55 @@ SirTimedStaged sir_stage_timed(const char* who, int n, int64_t nnz, int T, int P
     if (bins < 1 || bins > 4096) return refuse_timed("%s: bins = %d is not in [1, 4096]", who, bins);
     if ((double)O * (double)std::max(C, 1) * (double)std::max(T, 1) * (double)(bins + 1) >= 2147483648.0)
         return refuse_timed("%s: the histogram [O = %d][C = %d][T = %d][bins + 1 = %d] has 2^31 cells or more", who, O, C, T, bins + 1);
-    if (R < 1) return refuse_timed("%s: R = %d records: at least one", who, R);
-    std::vector<int32_t> zeros((size_t)O, 0), records((size_t)O, 0), ptr((size_t)n + 1, 0);
-    for (int i = 0; i < R; ++i) {
-        if (rec_set[i] < 0 || rec_set[i] >= O) return refuse_timed("%s: rec_set[%d] = %d is not in [0, %d)", who, i, rec_set[i], O);
-        if (rec_node[i] < 0 || rec_node[i] >= n) return refuse_timed("%s: rec_node[%d] = %d is not in [0, %d)", who, i, rec_node[i], n);
-        if (rec_kind[i] < 0 || rec_kind[i] > 4) return refuse_timed("%s: rec_kind[%d] = %d is not a kind in [0, 4]", who, i, rec_kind[i]);
-        if (rec_offset[i] > 0) return refuse_timed("%s: rec_offset[%d] = %d is after now: offsets are <= 0", who, i, rec_offset[i]);
-        ++records[rec_set[i]]; zeros[rec_set[i]] += rec_kind[i] == 0; ++ptr[(size_t)rec_node[i] + 1];
-    }
-    for (int o = 0; o < O; ++o)
-        if (records[o] == 0) return refuse_timed("%s: evidence set %d holds no record", who, o);
 #undef refuse_timed
+    std::vector<int32_t> zeros, records, ptr;
+    const std::string bad = check_records(who, n, rec_set, rec_node, rec_offset, rec_kind, R, O, zeros, records, ptr);
+    if (!bad.empty()) { s.thr = refused(bad.c_str()); return s; }
     s.thr = sir_stage_sweep(who, n, nnz, T, P, L, phase, w, gamma, init, C, shifts);
     if (!s.thr.error.empty()) return s;
-    for (int v = 0; v < n; ++v) ptr[(size_t)v + 1] += ptr[v];
-    std::vector<int32_t> at(ptr.begin(), ptr.end() - 1);               // by node, a node's records in the order given
-    s.rec.resize((size_t)R);
-    for (int i = 0; i < R; ++i) {
-        const int64_t back = std::min<int64_t>(-(int64_t)rec_offset[i], std::max(T, 0));   // (at T or beyond: never reached)
-        s.rec[(size_t)at[rec_node[i]]++] = (uint32_t)rec_set[i] | (uint32_t)rec_kind[i] << 4 | (uint32_t)back << 8;
+    sort_records(n, T, rec_set, rec_node, rec_offset, rec_kind, R, ptr, s);
+    s.zeros = std::move(zeros); s.records = std::move(records);
+    return s;
+}
+
+SirPostLayout sir_post_layout(int n, int64_t nnz, int n_bigrow, int T, int P, int L, int C, int O, int R, int H) {
+    SirPostLayout W;
+    static_cast<SirSweepLayout&>(W) = sweep_layout(n, nnz, n_bigrow, T, P, L, C, kSirPostLds);
+    const size_t table = al((size_t)std::max(O, 1) * sizeof(int32_t));
+    W.rec_ptr = W.total;
+    W.rec = W.rec_ptr + al(((size_t)n + 1) * sizeof(int32_t));
+    W.zeros = W.rec + al((size_t)std::max(R, 1) * sizeof(uint32_t));
+    W.records = W.zeros + table;
+    W.horizons = W.records + table;
+    W.total = W.horizons + al((size_t)std::max(H, 1) * sizeof(int32_t));
+    return W;
+}
+
+SirPostStaged sir_stage_post(const char* who, int n, int64_t nnz, int T, int P, int L, const int32_t* phase, const double* w,
+                             const double* gamma, const double* init, int C, const int32_t* shifts, const int32_t* rec_set,
+                             const int32_t* rec_node, const int32_t* rec_offset, const int32_t* rec_kind, int R, int O, int now,
+                             const int32_t* horizons, int H) {
+    char buf[256];
+    SirPostStaged s;                                                   // (a refusal: nothing staged, only thr.error)
+#define refuse_post(...) (s.thr = refuse(__VA_ARGS__), s)
+    if (O < 1 || O > GN_SIR_SCORE_MAXO) return refuse_post("%s: O = %d evidence sets: 1 to %d in one call", who, O, GN_SIR_SCORE_MAXO);
+    if (now < 0 || now >= T) return refuse_post("%s: now = %d is not in [0, T = %d)", who, now, T);
+    if (H < 1 || H > GN_SIR_POST_MAXH) return refuse_post("%s: H = %d horizons: 1 to %d in one call", who, H, GN_SIR_POST_MAXH);
+    for (int j = 0; j < H; ++j) {
+        if (horizons[j] < 0) return refuse_post("%s: horizons[%d] = %d is before now: horizons are >= 0", who, j, horizons[j]);
+        if (j > 0 && horizons[j] <= horizons[j - 1]) return refuse_post("%s: horizons[%d] = %d does not ascend from horizons[%d] = %d", who, j, horizons[j], j - 1, horizons[j - 1]);
+        if ((int64_t)now + horizons[j] > (int64_t)T - 1) return refuse_post("%s: horizons[%d] = %d: now + horizon = %lld is past the last step T - 1 = %d", who, j, horizons[j], (long long)now + horizons[j], T - 1);
     }
-    s.rec_ptr = std::move(ptr); s.zeros = std::move(zeros); s.records = std::move(records);
+    if ((double)O * (double)H * 2.0 * (double)std::max(n, 1) >= 2147483648.0)
+        return refuse_post("%s: the counts [O = %d][H = %d][2][n = %d] have 2^31 cells or more", who, O, H, n);
+#undef refuse_post
+    std::vector<int32_t> zeros, records, ptr;
+    const std::string bad = check_records(who, n, rec_set, rec_node, rec_offset, rec_kind, R, O, zeros, records, ptr);
+    if (!bad.empty()) { s.thr = refused(bad.c_str()); return s; }
+    s.thr = sir_stage_sweep(who, n, nnz, T, P, L, phase, w, gamma, init, C, shifts);
+    if (!s.thr.error.empty()) return s;
+    sort_records(n, T, rec_set, rec_node, rec_offset, rec_kind, R, ptr, s);
+    s.zeros = std::move(zeros); s.records = std::move(records);
+    s.horizons.assign(horizons, horizons + H);
     return s;
 }

@@ -142,3 +142,33 @@ struct SirTimedStaged {
 SirTimedStaged sir_stage_timed(const char* who, int n, int64_t nnz, int T, int P, int L, const int32_t* phase, const double* w,
                                const double* gamma, const double* init, int C, const int32_t* shifts, const int32_t* rec_set,
                                const int32_t* rec_node, const int32_t* rec_offset, const int32_t* rec_kind, int R, int O, int bins);
+
+// Nowcast and forecast from timed evidence (gnode_sir_mc_philox_sweep_posterior, the POST instances): the sweep's trajectories,
+// each compared with the records of O evidence sets, at most GN_SIR_SCORE_MAXO per call, at ONE age `now`, and the states of the
+// accepted ones counted at now + horizons[j], at most GN_SIR_POST_MAXH horizons.  The kernels keep one int32 per set in static
+// LDS -- the difference array summed up to cell `now` -- kSirPostLds bytes for the launch plan and the layout below (static_lds
+// above); no O * T limit applies.
+#ifndef GN_SIR_POST_MAXH
+#define GN_SIR_POST_MAXH 32
+#endif
+static const size_t kSirPostLds = (size_t)GN_SIR_SCORE_MAXO * sizeof(int32_t);
+// The sweep's layout (its `tail` sized for the POST instances' boundaries), then the records staged as SirTimedLayout has them,
+// then the horizons.
+struct SirPostLayout : SirSweepLayout {
+    size_t rec_ptr;                  // int32 [n + 1]
+    size_t rec;                      // uint32 [R]
+    size_t zeros, records;           // int32 [O] each
+    size_t horizons;                 // int32 [H]
+};
+SirPostLayout sir_post_layout(int n, int64_t nnz, int n_bigrow, int T, int P, int L, int C, int O, int R, int H);
+// sir_stage_sweep's checks and those of the records as sir_stage_timed makes them (one record sort for both), without the cells
+// of a difference array: 1 <= O <= GN_SIR_SCORE_MAXO, `now` in [0, T), 1 <= H <= GN_SIR_POST_MAXH, horizons[0] >= 0, ascending,
+// now + horizons[j] <= T - 1, O * H * 2 * n < 2^31, R >= 1 and every record as there.  A refusal (thr.error) names `who` and the
+// offending index, and nothing is staged.
+struct SirPostStaged : SirTimedStaged {
+    std::vector<int32_t> horizons;   // [H]
+};
+SirPostStaged sir_stage_post(const char* who, int n, int64_t nnz, int T, int P, int L, const int32_t* phase, const double* w,
+                             const double* gamma, const double* init, int C, const int32_t* shifts, const int32_t* rec_set,
+                             const int32_t* rec_node, const int32_t* rec_offset, const int32_t* rec_kind, int R, int O, int now,
+                             const int32_t* horizons, int H);

@@ -846,6 +846,111 @@ def source_scores_timed_mc(graph, observations, beta, gamma, sims, maxTime, cand
     return SirSourceScores(hist, sims, bins, squeezed)
 
 
+SIR_POST_MAXH = 32                                                  # GN_SIR_POST_MAXH of the library as built: horizons per launch
+
+
+class SirPosterior(NamedTuple):
+    """What `posterior_states_mc` returns."""
+    counts: torch.Tensor            # int64 [O, H, 2, n]: accepted trajectories of all candidates with node v in I (plane 0) / R (plane 1) at now + h
+    accepted: torch.Tensor          # int64 [O, C]: the accepted trajectories per evidence set and candidate
+    sims: int                       # the trajectories per candidate of THIS call
+    now: int
+    horizons: tuple
+    squeezed: bool                  # `observations` was one object: the methods drop the evidence-set axis
+
+    def _table(self, x):
+        return x[0] if self.squeezed else x
+
+    def accepted_total(self) -> torch.Tensor:
+        """int64 [O] (a scalar tensor for one evidence object): the accepted trajectories of all candidates"""
+        return self._table(self.accepted.sum(-1))
+
+    def source(self) -> torch.Tensor:
+        """float64 [O, C] ([C]): accepted / accepted.sum(), the posterior over the candidates under a uniform prior (a repeated
+        candidate carries its multiplicity); NaN where nothing was accepted"""
+        a = self.accepted.double()
+        return self._table(a / a.sum(-1, keepdim=True))
+
+    def marginals(self) -> torch.Tensor:
+        """float64 [O, H, n, 3] ([H, n, 3]): P(v is S, I, R at now + h | evidence) = (total - I - R, I, R) / total over the accepted
+        trajectories, total = accepted.sum(); NaN where nothing was accepted"""
+        tot = self.accepted.sum(-1)[:, None, None]
+        i, r = self.counts[:, :, 0], self.counts[:, :, 1]
+        return self._table(torch.stack([tot - i - r, i, r], dim=-1).double() / tot[..., None].double())
+
+
+def posterior_states_mc(graph, observations, beta, gamma, sims, maxTime, now, horizons=(0,), candidates=None, start=None, shifts=None, rng_seed=None,
+                        sim_offset=0, edge_scan=False, device="cuda", counts: torch.Tensor | None = None,
+                        accepted: torch.Tensor | None = None) -> SirPosterior:
+    """Nowcast and forecast from timed evidence by rejection sampling: given the records `source_scores_timed_mc` scores and the
+    age `now` of the outbreak, who is infected now that nobody has tested, and who will be in h steps?  For each candidate source
+    c, `sims` trajectories start from `start` with c infected -- the trajectories of `source_scores_timed_mc` -- and a trajectory
+    is ACCEPTED for an evidence set when it matches EVERY record of the set at age `now` (a record (node v, offset d <= 0, kind)
+    is read at step now + d, by that function's rule).  Returns `SirPosterior(counts, accepted, sims, now, horizons, squeezed)`:
+    accepted int64 [O, C] on the GPU, the accepted trajectories per set and candidate; counts int64 [O, H, 2, n], over the
+    accepted trajectories of ALL candidates those in which node v is infected (plane 0) or removed (plane 1) at step now +
+    horizons[j] -- exact integers, whatever the launch geometry.  A trajectory that ended early keeps its final state.  Under a
+    uniform prior over the candidates `.marginals()` = (S, I, R) / accepted.sum() is the posterior marginal of every node and
+    `.source()` the posterior over the sources; repeats in `candidates` weigh the prior by their multiplicity, and a prior over
+    starts that is not a single source goes through start=InitialState with candidates=[-1].  DMP cannot answer this: its
+    marginals are unconditional.
+
+    accepted[o, c] == source_scores_timed_mc(...).hist[o, c, now, bins] for the same seed; with an evidence set that is always
+    matched (one kind-0 record further back than maxTime) accepted == sims everywhere and counts[o, j].sum(-1) is
+    `outbreak_sizes_mc`'s sums[:, now + horizons[j], 1:3] summed over the candidates.
+
+    observations: as in `source_scores_timed_mc`; one object drops the evidence-set axis in the methods.  now: a whole number in
+    [0, maxTime).  horizons: 1 to 32 ascending whole numbers >= 0 with now + h <= maxTime - 1.  All candidates and up to 16 sets
+    share ONE launch at any maxTime, more sets run in groups of 16 on one graph handle; a trajectory that no set of its group
+    accepts ends at step `now`, and none runs past now + max(horizons).  candidates, -1, start, shifts, beta / gamma (a
+    `RateSchedule` included), sim_offset, edge_scan: as in `outbreak_sizes_mc`.  counts=, accepted=: int64 tensors of the output
+    shapes to ACCUMULATE into, for shards of the sims range.  Through `gnode_sir_mc_philox_sweep_posterior`, which synchronises
+    the stream.  What is wrong raises ValueError before the library is loaded or a graph handle is made."""
+    who = "posterior_states_mc"
+    a = _McSweep(who, graph, beta, gamma, sims, maxTime, candidates, "seed", start, shifts, sim_offset)
+    C_, T, sims = a.C, a.T, a.sims
+    now = _whole(who, "now", now, 0)
+    if now >= T:
+        raise ValueError(f"{who}: now = {now} is not in [0, maxTime = {T})")
+    if isinstance(horizons, (int, float, np.integer, np.floating)) and not isinstance(horizons, bool):
+        horizons = (horizons,)
+    hz = _whole_numbers(who, "horizons", horizons)
+    if hz.ndim != 1 or not 1 <= hz.size <= SIR_POST_MAXH:
+        raise ValueError(f"{who}: 1 to {SIR_POST_MAXH} horizons, got {hz.size}")
+    if hz[0] < 0 or (np.diff(hz) <= 0).any():
+        j = 0 if hz[0] < 0 else int(np.flatnonzero(np.diff(hz) <= 0)[0]) + 1
+        raise ValueError(f"{who}: horizons[{j}] = {int(hz[j])}: horizons are whole numbers >= 0 in ascending order")
+    if now + int(hz[-1]) > T - 1:
+        j = int(np.flatnonzero(now + hz > T - 1)[0])
+        raise ValueError(f"{who}: horizons[{j}] = {int(hz[j])}: now + horizon = {now + int(hz[j])} is past the last step maxTime - 1 = {T - 1}")
+    squeezed, sets = _timed_records(who, observations, a.n)
+    O, H = len(sets), int(hz.size)
+    if min(O, SIR_SCORE_MAXO) * H * 2 * a.n >= 2**31:
+        raise ValueError(f"{who}: {min(O, SIR_SCORE_MAXO)} x {H} x 2 x {a.n} count cells per launch reach 2^31: fewer horizons")
+    _accumulator(who, "counts", counts, (O, H, 2, a.n))
+    _accumulator(who, "accepted", accepted, (O, C_))
+    if counts is not None and accepted is not None and counts.device != accepted.device:
+        raise ValueError(f"{who}: counts is on {counts.device} and accepted on {accepted.device}")
+    g, lib, rng_seed = a.enter(rng_seed)
+    dev = counts.device if counts is not None else accepted.device if accepted is not None else device
+    if counts is None:
+        counts = torch.zeros((O, H, 2, a.n), dtype=torch.int64, device=dev)
+    if accepted is None:
+        accepted = torch.zeros((O, C_), dtype=torch.int64, device=dev)
+    hz32 = np.ascontiguousarray(hz, dtype=np.int32)
+    for o0 in range(0, O if sims > 0 else 0, SIR_SCORE_MAXO):      # a group's slices are contiguous: o is the slowest axis of both
+        part = sets[o0:o0 + SIR_SCORE_MAXO]
+        og = len(part)
+        which = np.concatenate([np.full(len(s[0]), i, dtype=np.int32) for i, s in enumerate(part)])
+        node, off, kind = (np.ascontiguousarray(np.concatenate([s[j] for s in part])) for j in range(3))
+        ws = torch.empty(lib.gnode_sir_sweep_posterior_workspace_bytes(g.handle, T, a.sched.P, a.L, C_, og, len(which), H), dtype=torch.uint8, device=dev)
+        _lib.check(lib.gnode_sir_mc_philox_sweep_posterior(g.handle, *a.sweep_args(), _lib.host_ptr(which), _lib.host_ptr(node), _lib.host_ptr(off),
+                                                           _lib.host_ptr(kind), len(which), og, now, _lib.host_ptr(hz32), H, sims, a.sim_offset, T,
+                                                           C.c_uint64(rng_seed), _lib.ptr(counts[o0:o0 + og]), _lib.ptr(accepted[o0:o0 + og]),
+                                                           _lib.ptr(ws), ws.numel(), _lib.stream_ptr(), int(bool(edge_scan))))
+    return SirPosterior(counts, accepted, sims, now, tuple(int(h) for h in hz), squeezed)
+
+
 def sir_counts_counted(graph: DeviceGraph, seed_set, beta, gamma, sims, T, rng_seed, sim_offset=0, device="cuda"):
     """`sir_counts` through the kernel's profiling instantiation: (counts, stats) with stats = what the launch did --
     Philox blocks computed, infection coins drawn, recovery coins drawn, CSR entries read (bench.py's `sir` roofline)."""

@@ -587,6 +587,43 @@ int gnode_sir_mc_philox_sweep_timed(gnode_graph_t g, const double* init_host,   
                                     int64_t sims, int64_t sim_offset, int32_t T, uint64_t rng_seed,
                                     uint64_t* hist,     /* device [O][C][T][bins + 1], ACCUMULATED */
                                     void* workspace, size_t workspace_bytes, void* stream, int32_t edge_scan);
+/* Monte-Carlo nowcast and forecast from timed evidence (no version step: a stale library is known by the missing symbol): the
+ * trajectories of gnode_sir_mc_philox_sweep -- same candidates, override, shifts, coins and job order -- each held against the
+ * records of gnode_sir_mc_philox_sweep_timed at ONE age `now` of the outbreak, by rejection sampling.  Trajectory (c, s) is
+ * ACCEPTED for set o when every record of the set is matched at age `now`, by the definition above: agree[o][now] == records[o].
+ *   now        in [0, T): the age of the outbreak at which the records' offsets are anchored
+ *   horizons_host   host int32 [H], 1 <= H <= 32 (GN_SIR_POST_MAXH of the build): whole numbers >= 0, ascending, with
+ *              now + horizons[H - 1] <= T - 1
+ *   accepted   device uint64 [O][C], ACCUMULATED: accepted[o][c] += the accepted trajectories of candidate c for set o.  It is
+ *              what gnode_sir_mc_philox_sweep_timed adds to hist[o][c][now][bins] for the same seed.
+ *   counts     device uint64 [O][H][2][n], ACCUMULATED: over the accepted trajectories of ALL candidates, counts[o][j][0][v] += those
+ *              in which node v is I at model step now + horizons[j], counts[o][j][1][v] += those in which it is R; S is the
+ *              accepted total minus the two.  A trajectory that ended early keeps its final state at every later step.
+ * Both by integer atomic adds: exact, whatever the order of the jobs, the grid or the path; shards of the sims range add up.
+ * With a set that is always matched (one kind-0 record further back than T) accepted grows by sims everywhere and the sum of
+ * counts[o][j][k] over the nodes is what gnode_sir_mc_philox_sweep adds to sums[c][now + horizons[j]][1 + k], summed over c.  A
+ * trajectory that no set accepts ends at step `now`; none runs past step now + horizons[H - 1].  1 <= O <= 16; no O * T limit.
+ * No sums, no ever, no histogram.  GNODE_ERR_ARG, before any launch and with both outputs untouched: what
+ * gnode_sir_mc_philox_sweep refuses, O outside [1, 16], now outside [0, T), H outside [1, 32], a horizon < 0, not ascending or
+ * with now + horizon > T - 1, O * H * 2 * n >= 2^31, and what gnode_sir_mc_philox_sweep_timed refuses of the records;
+ * GNODE_ERR_WORKSPACE: a workspace shorter than gnode_sir_sweep_posterior_workspace_bytes(g, T, P, L, C, O, R, H) -- the timed
+ * call's tables behind the sweep's layout, then the horizons; the query answers 0 where the timed one does and for H outside
+ * [1, 32].  sims = 0 is valid and touches nothing.  SYNCHRONISES `stream`.  edge_scan as above. */
+size_t gnode_sir_sweep_posterior_workspace_bytes(gnode_graph_t g, int32_t T, int32_t P, int32_t L, int32_t C, int32_t O, int32_t R, int32_t H);
+int gnode_sir_mc_philox_sweep_posterior(gnode_graph_t g, const double* init_host,    /* host fp64 [n][3] */
+                                        const int32_t* candidates_host,              /* host [C] */
+                                        const int32_t* shifts_host,                  /* host [C], or NULL: all 0 */
+                                        int32_t C, int32_t action,
+                                        const int32_t* phase_host, int32_t P, int32_t L,   /* host [L] */
+                                        const double* w_host,                        /* host fp64 [P][nnz] */
+                                        const double* gamma_host,                    /* host fp64 [P][n] */
+                                        const int32_t* rec_set, const int32_t* rec_node,          /* host [R] each */
+                                        const int32_t* rec_offset, const int32_t* rec_kind, int32_t R, int32_t O,
+                                        int32_t now, const int32_t* horizons_host, int32_t H,     /* host [H] */
+                                        int64_t sims, int64_t sim_offset, int32_t T, uint64_t rng_seed,
+                                        uint64_t* counts,     /* device [O][H][2][n], ACCUMULATED */
+                                        uint64_t* accepted,   /* device [O][C], ACCUMULATED */
+                                        void* workspace, size_t workspace_bytes, void* stream, int32_t edge_scan);
 int gnode_sir_mc_coins(const int32_t* table_src, const int32_t* table_dst, int64_t n_table, int32_t n,
                        const int32_t* seeds_host, int32_t n_seeds, double beta, double gamma, int64_t sims,
                        int32_t T, const double* coins, int64_t n_coins, uint32_t* counts,
