@@ -40,27 +40,17 @@
 // Separate instances again: the other forms' step pointers are their kernel arguments, and they compile to what they were
 // (DESIGN 4.12).
 //
-// Outbreak sizes for many candidates (gnode_sir_mc_philox_sweep, the SWEEP instances, INIT and SCHED only): one launch runs C x
-// sims trajectories, trajectory (c, s) from the drawn start with candidate c's node overridden and the phase row read from the
-// candidate's shift on, and leaves integer sums per (candidate, step, compartment) where a TRAJ instance writes a curve -- no
-// histogram, no events, no curves.  The coins do not know the candidate.  Separate instances once more.
-//
-// Source scores (gnode_sir_mc_philox_sweep_scores, the SCORE instances, SWEEP ones only): the sweep's trajectories, the state at
-// every step compared with up to GN_SIR_SCORE_MAXO observed snapshots by two integer tallies per snapshot in LDS, and where the
-// sweep adds a row to its sums, one count into a histogram of binned similarities per (snapshot, candidate, step).  Separate
-// instances again; the sweep's compile to what they were.
-//
-// Source scores from timed evidence (gnode_sir_mc_philox_sweep_timed, the TIMED instances, SWEEP ones only): the sweep's
-// trajectories, each compared at every possible age t with all records (node, offset, kind) of up to GN_SIR_SCORE_MAXO evidence
-// sets jointly.  An event moves a difference array over t in LDS; one prefix sum at the end of the trajectory gives the number
-// of matched records per (set, t), and one count per (set, t) goes into the histogram.  Separate instances once more.
-//
-// Nowcast and forecast from timed evidence (gnode_sir_mc_philox_sweep_posterior, the POST instances, SWEEP ones only): the sweep's
-// trajectories, each held against the records of up to GN_SIR_SCORE_MAXO evidence sets at ONE known age `now`.  A trajectory that
-// matches every record of a set is accepted for it, and the state of every node of an accepted trajectory is counted at the steps
-// now + h; a trajectory no set accepts ends at step `now`.  Separate instances once more.
+// The candidate sweep (gnode_sir_mc_philox_sweep and its _scores, _timed and _posterior forms; INIT and SCHED instances only): one
+// launch runs C x sims jobs, job (c, s) being trajectory s from the drawn start with candidate c's node overridden and the phase
+// row read from the candidate's shift on.  What a job puts out -- sums per (candidate, step, compartment), binned similarities
+// with snapshots, binned agreement with timed records, or per-node counts of the trajectories that match them -- is the kernel's
+// output policy, its type parameter OUT and its last two arguments (the jobs, the policy): gnode_sir_sweep.h states the five
+// policies, the hooks the two step kernels call at every event, every closed step and the end of a job, and the host half of
+// each output.  An instance that is not a sweep takes the empty policy and compiles to what it was; a sweep has no histogram,
+// no events and no curves.
 #include "gnode_common.h"
 #include "gnode_sir_plan.h"
+#include "gnode_sir_sweep.h"
 #include <algorithm>
 #include <cmath>
 #include <type_traits>
@@ -147,28 +137,6 @@ __device__ __forceinline__ SirThr<NODES> sir_step_thr(SirThr<NODES> base, const 
     if constexpr (SCHED) return base + (size_t)sc.phase[it] * len; else return base;
 }
 
-// SWEEP instances (gnode_sir_mc_philox_sweep; INIT and SCHED ones only): the workgroups' loop runs over C * sims jobs, job j
-// being candidate c = j % C and trajectory s = j / C (sir_sweep_job; DESIGN 4.16 on the order).  Trajectory (c, s) draws the
-// start of `sim` like every INIT instance and then overrides the node cand[c] -- action 0: it starts in I, action 1: in R; an id outside
-// [0, n) matches no node -- reads the phase row from shifts[c] on, and leaves (S_t, I_t, R_t) in sums[c][t] by integer
-// atomic adds where a TRAJ instance writes a row of `curves`, and the number of nodes that were ever infected (the I starts
-// included, the R starts not) in ever[c][s] when `ever` is non-null.  The coins do not know c.  No histogram atomic, no
-// event, no curve.  The others take an empty struct, as with SirTraj, and compile to what they were.
-template <bool SWEEP> struct SirSweep {};
-template <> struct SirSweep<true> {
-    const int32_t* cand; const int32_t* shifts; int C; int action;
-    unsigned long long* sums;   // [C][T][3], accumulated
-    uint32_t* ever;             // [C][sims], overwritten, or null
-};
-// The order of (c, s) within the job index.  0, the choice: candidates interleaved, c = j % C -- the workgroups resident at one
-// time add to the sums of as many candidates as there are, and each workgroup's share of the jobs mixes the candidates.  1:
-// candidate-major, c = j / sims, kept as a build option for the measurement of DESIGN 4.16.  No result depends on it.
-#ifndef GN_SIR_SWEEP_MAJOR
-#define GN_SIR_SWEEP_MAJOR 0
-#endif
-__device__ __forceinline__ void sir_sweep_job(long job, int C, long sims, int& c, long& s) {
-    if (GN_SIR_SWEEP_MAJOR) { c = (int)(job / sims); s = job % sims; } else { c = (int)(job % C); s = job / C; }
-}
 // one event of the [2][T][n] histograms: the SWEEP instances have none
 template <bool SWEEP> __device__ __forceinline__ void sir_hist_add(uint32_t* h) { if constexpr (!SWEEP) atomicAdd(h, 1u); }
 // the start of nodes 4q .. 4q + 3 (sir_init_draw), with the candidate's bit overridden in the SWEEP instances; node < 0: nobody
@@ -189,213 +157,9 @@ __device__ __forceinline__ void sir_curve_row(uint32_t* __restrict__ curves, lon
     r[0] = (uint32_t)(n - n_ever); r[1] = (uint32_t)(n_ever - n_rec); r[2] = (uint32_t)n_rec;
 }
 // the schedule as job (c, s) reads it: from shifts[c] on in the SWEEP instances, as it is in the others
-template <bool SCHED, bool SWEEP>
-__device__ __forceinline__ SirSched<SCHED> sir_job_sched(const SirSched<SCHED>& sc, const SirSweep<SWEEP>& sw, int c) {
-    if constexpr (SWEEP) { SirSched<SCHED> o = sc; o.phase += sw.shifts[c]; return o; } else return sc;
-}
-// the same row, of candidate c, added to the sums (integer adds commute: exact whatever the order of the jobs)
-__device__ __forceinline__ void sir_sums_row(unsigned long long* __restrict__ sums, int c, int T, int row, int n, int n_ever, int n_rec) {
-    unsigned long long* r = sums + ((size_t)c * T + row) * 3;
-    atomicAdd(&r[0], (unsigned long long)(n - n_ever)); atomicAdd(&r[1], (unsigned long long)(n_ever - n_rec));
-    atomicAdd(&r[2], (unsigned long long)n_rec);
-}
-// SCORE instances (gnode_sir_mc_philox_sweep_scores; SWEEP ones only): the sweep's jobs, each step of each compared with O
-// snapshots of the epidemic (obs, node-major int8 [n][O]: -1 not observed, 0 / 1 / 2 = S / I / R).  Two integer tallies per
-// snapshot live in LDS (`tal`, below) and move at the sites that hold an event -- the sites of sir_hist_add: a node leaves S
-// (sir_score_event<.., 0>), a node recovers (<.., 1>); an R start is both.  Where a SWEEP instance adds a row to the sums, a
-// SCORE instance adds ONE to hist[o][c][row][k], uint64 [O][C][T][bins + 1], k the binned similarity of the state with snapshot o:
-//   measure 0, Jaccard:  tal[o] = inter = |left S & obs in {1, 2}|, tal[MAXO + o] = pos = |left S & observed|;
-//                        k = inter * bins / (marked[o] + pos - inter), marked[o] = |obs in {1, 2}|
-//   measure 1, match:    tal[o] = agree = |observed & obs == state|, from seen[o] - marked[o] (the zeros: everybody in S) on;
-//                        k = agree * bins / seen[o], seen[o] = |observed|
-// in 64-bit integer division, k = bins for a zero denominator: k = bins exactly when state and snapshot agree completely.  No
-// sums, no ever.  The others take an empty struct, as with SirSweep, and compile to what they were.
-template <bool SCORE> struct SirScore {};
-template <> struct SirScore<true> {
-    const int8_t* obs; const int32_t* marked; const int32_t* seen; int O; int measure; int bins;
-    unsigned long long* hist;   // [O][C][T][bins + 1], accumulated
-};
-// the tallies of a job before its start is drawn: threads 0 .. 2 MAXO - 1, in front of the barrier that resets the counters
-template <bool SCORE> __device__ __forceinline__ void sir_score_reset(const SirScore<SCORE>& sr, int* tal, int tid) {
-    if constexpr (SCORE)
-        if (tid < 2 * GN_SIR_SCORE_MAXO) tal[tid] = (sr.measure == 1 && tid < sr.O) ? sr.seen[tid] - sr.marked[tid] : 0;
-}
-// KIND 0: node v leaves S (it enters I); KIND 1: it recovers (I to R)
-template <bool SCORE, int KIND> __device__ __forceinline__ void sir_score_event(const SirScore<SCORE>& sr, int* tal, int v) {
-    if constexpr (SCORE) {
-        if (KIND == 1 && sr.measure == 0) return;               // the Jaccard sets do not know a recovery
-        const int8_t* ob = sr.obs + (size_t)v * sr.O;
-        for (int o = 0; o < sr.O; ++o) {
-            const int x = ob[o];
-            if (sr.measure == 0) {
-                if (x >= 0) { atomicAdd(&tal[GN_SIR_SCORE_MAXO + o], 1); if (x >= 1) atomicAdd(&tal[o], 1); }
-            } else {
-                const int d = KIND == 0 ? (x == 1) - (x == 0) : (x == 2) - (x == 1);
-                if (d) atomicAdd(&tal[o], d);
-            }
-        }
-    }
-}
-// one trajectory's row `row` against snapshot o: its bin, counted (integer adds commute: exact whatever the order of the jobs)
-__device__ __forceinline__ void sir_score_cell(const SirScore<true>& sr, const int* tal, int C, int c, int T, int row, int o) {
-    unsigned long long num = (unsigned long long)tal[o], den;
-    if (sr.measure == 0) den = (unsigned long long)(sr.marked[o] + tal[GN_SIR_SCORE_MAXO + o]) - num; else den = (unsigned long long)sr.seen[o];
-    const unsigned long long k = den ? num * (unsigned long long)sr.bins / den : (unsigned long long)sr.bins;
-    atomicAdd(&sr.hist[(((size_t)o * C + c) * T + row) * ((size_t)sr.bins + 1) + k], 1ull);
-}
-// where the others put out a row between two barriers from thread 0, a SCORE instance counts the row's bin of snapshot o from
-// thread o ...
-__device__ __forceinline__ void sir_score_row(const SirScore<true>& sr, const int* tal, int C, int c, int T, int row, int tid) {
-    if (tid < sr.O) sir_score_cell(sr, tal, C, c, T, row, tid);
-}
-// ... and the rows after an early end, which repeat the final bin, are spread over the threads as the others' are
-__device__ __forceinline__ void sir_score_rows_after(const SirScore<true>& sr, const int* tal, int C, int c, int T, int from, int tid, int nthr) {
-    for (int r = from + tid; r < T; r += nthr)
-        for (int o = 0; o < sr.O; ++o) sir_score_cell(sr, tal, C, c, T, r, o);
-}
-// TIMED instances (gnode_sir_mc_philox_sweep_timed; SWEEP ones only, never SCORE): the sweep's jobs, each compared with O sets
-// of records (node v, offset d <= 0, kind).  For "now" = t steps after the run began a record is read at model step m = t + d
-// and is matched when: m < 0 and the kind is 0; kind 0 / 1 / 2 and v is S / I / R at step m; kind 3 and v became infected AT
-// step m; kind 4 and it recovered AT step m.  agree[o][t], the matched records of set o, is a sum of steps and pulses in t that
-// begin at (event step + back), back = -d: `dif`, int32 [O][T] in LDS, holds its DIFFERENCES and moves at the sites that hold an
-// event -- the sites of sir_score_event -- by LDS integer atomics; positions >= T are dropped:
-//   v leaves S at step `it`:   kind 0: -1 at it + back;  kind 1: +1 at it + back;  kind 3: +1 at it + back, -1 at it + back + 1
-//   v recovers at step `it`:   kind 1: -1 at it + back;  kind 2: +1 at it + back;  kind 4: +1 at it + back, -1 at it + back + 1
-// from dif[o][0] = zeros[o], the kind-0 records of the set (everybody in S, for ever), and 0 elsewhere.  Nothing is put out per
-// step.  When the trajectory has ended an inclusive prefix sum over t turns dif into agree, and the job adds ONE to
-// hist[o][c][t][k], uint64 [O][C][T][bins + 1], k = agree * bins / records[o] in integers, for every (o, t): k = bins exactly
-// when every record of the set is matched.  The records are staged by node: those of v are rec[rec_ptr[v] .. rec_ptr[v + 1]),
-// one word each -- set | kind << 4 | min(back, T) << 8 -- and an event of a node without a record costs the two reads of
-// rec_ptr (DESIGN 4.18 on why not a bitmap).  No sums, no ever.  The others take an empty struct, as with SirScore, and
-// compile to what they were.
-template <bool TIMED> struct SirTimed {};
-template <> struct SirTimed<true> {
-    const int32_t* rec_ptr; const uint32_t* rec; const int32_t* zeros; const int32_t* records; int O; int bins;
-    unsigned long long* hist;   // [O][C][T][bins + 1], accumulated
-};
-// the difference array of a job before its start is drawn, in front of the barrier that resets the counters
-template <bool TIMED> __device__ __forceinline__ void sir_timed_reset(const SirTimed<TIMED>& tm, int* dif, int T, int tid, int nthr) {
-    if constexpr (TIMED)
-        for (int i = tid, cells = tm.O * T; i < cells; i += nthr) { const int o = i / T; dif[i] = i == o * T ? tm.zeros[o] : 0; }
-}
-// KIND 0: node v leaves S at step `it`; KIND 1: it recovers at step `it`
-template <bool TIMED, int KIND> __device__ __forceinline__ void sir_timed_event(const SirTimed<TIMED>& tm, int* dif, int T, int v, int it) {
-    if constexpr (TIMED) {
-        for (int r = tm.rec_ptr[v], end = tm.rec_ptr[v + 1]; r < end; ++r) {
-            const uint32_t w = tm.rec[r];
-            const int kind = (int)((w >> 4) & 7u), pos = it + (int)(w >> 8);
-            const int d = KIND == 0 ? (kind == 1 || kind == 3) - (kind == 0) : (kind == 2 || kind == 4) - (kind == 1);
-            if (d == 0 || pos >= T) continue;
-            int* row = dif + (int)(w & 15u) * T;
-            atomicAdd(&row[pos], d);
-            if (kind == 3 + KIND && pos + 1 < T) atomicAdd(&row[pos + 1], -1);      // "at that step": a pulse, not a step
-        }
-    }
-}
-// the end of a job, behind the barrier that follows its last event: dif to agree (thread o takes set o: T dependent LDS adds, a
-// step's worth of time at the end of T steps), a barrier, and the O * T counts spread over the threads as sir_score_rows_after
-// spreads its rows (integer adds commute: exact whatever the order of the jobs).  The caller's barrier in front of the next job's
-// reset follows.
-__device__ __forceinline__ void sir_timed_finish(const SirTimed<true>& tm, int* dif, int C, int c, int T, int tid, int nthr) {
-    if (tid < tm.O) { int* row = dif + tid * T; int run = 0; for (int t = 0; t < T; ++t) { run += row[t]; row[t] = run; } }
-    __syncthreads();
-    for (int i = tid, cells = tm.O * T; i < cells; i += nthr) {
-        const int o = i / T, t = i - o * T;
-        unsigned long long k = (unsigned long long)dif[i] * (unsigned long long)tm.bins / (unsigned long long)tm.records[o];
-        if (k > (unsigned long long)tm.bins) k = (unsigned long long)tm.bins;   // (agree is in [0, records]: the count stays inside its row regardless)
-        atomicAdd(&tm.hist[(((size_t)o * C + c) * T + t) * ((size_t)tm.bins + 1) + k], 1ull);
-    }
-}
-// POST instances (gnode_sir_mc_philox_sweep_posterior; SWEEP ones only, never SCORE or TIMED): the sweep's jobs, each compared
-// with the TIMED instances' records at ONE age, `now`, and counted by state where it agrees with all of a set's.  agr[o], int32
-// in LDS, is SirTimed's `dif` of set o SUMMED UP TO CELL `now` -- agree[o][now] -- kept as one number because the cell is known:
-// from zeros[o] on, an event at step `it` of a node with a record (kind, back), pos = it + back, moves it by
-//   v leaves S:   kind 0: -1 iff pos <= now;  kind 1: +1 iff pos <= now;  kind 3: +1 iff pos == now  (the pulse's two ends)
-//   v recovers:   kind 1: -1 iff pos <= now;  kind 2: +1 iff pos <= now;  kind 4: +1 iff pos == now
-// (back is staged as min(back, T) and now < T: a record at T or beyond never moves it).  No event after step `now` moves it, so
-// behind the barrier that closes step `now` -- or behind the last step of a trajectory that ended before -- thread o < O
-// compares agr[o] with records[o]: on equality the trajectory is ACCEPTED for set o, one is added to accepted[o][c], uint64
-// [O][C], and bit o enters the job's mask in LDS.  An empty mask ends the job.  At every step now + horizons[j] that the job
-// closes, and after its end for the horizons that are left (the final state stays), the workgroup walks the nodes, one lane
-// per node, and adds one to counts[o][j][0][v] (v is I) or counts[o][j][1][v] (v is R), uint64 [O][H][2][n], for every set of
-// the mask: a wave's adds to one plane are contiguous.  The job never steps past now + horizons[H - 1].  No sums, no ever, no
-// histogram.  The others take an empty struct, as with SirTimed, and compile to what they were.
-template <bool POST> struct SirPost {};
-template <> struct SirPost<true> {
-    const int32_t* rec_ptr; const uint32_t* rec; const int32_t* zeros; const int32_t* records; const int32_t* horizons; int O, now, H;
-    unsigned long long* counts;     // [O][H][2][n], accumulated
-    unsigned long long* accepted;   // [O][C], accumulated
-};
-// the steps a job runs: T, or (POST) up to the last horizon
-template <bool POST> __device__ __forceinline__ int sir_post_end(const SirPost<POST>& ps, int T) {
-    if constexpr (POST) return ps.now + ps.horizons[ps.H - 1] + 1; else return T;
-}
-// the counters and the mask of a job before its start is drawn, in front of the barrier that resets the counters
-template <bool POST> __device__ __forceinline__ void sir_post_reset(const SirPost<POST>& ps, int* agr, uint32_t* pmask, int tid) {
-    if constexpr (POST) {
-        if (tid < GN_SIR_SCORE_MAXO) agr[tid] = tid < ps.O ? ps.zeros[tid] : 0;
-        if (tid == 0) *pmask = 0u;
-    }
-}
-// KIND 0: node v leaves S at step `it`; KIND 1: it recovers at step `it`
-template <bool POST, int KIND> __device__ __forceinline__ void sir_post_event(const SirPost<POST>& ps, int* agr, int v, int it) {
-    if constexpr (POST) {
-        for (int r = ps.rec_ptr[v], end = ps.rec_ptr[v + 1]; r < end; ++r) {
-            const uint32_t w = ps.rec[r];
-            const int kind = (int)((w >> 4) & 7u), pos = it + (int)(w >> 8);
-            const int step = KIND == 0 ? (kind == 1) - (kind == 0) : (kind == 2) - (kind == 1);
-            const int d = pos <= ps.now ? step + (pos == ps.now && kind == 3 + KIND) : 0;
-            if (d) atomicAdd(&agr[(int)(w & 15u)], d);
-        }
-    }
-}
-// behind a barrier that follows every event up to step `now`: the sets that accept the job (the same word in every thread)
-__device__ __forceinline__ uint32_t sir_post_accept(const SirPost<true>& ps, const int* agr, uint32_t* pmask, int C, int c, int tid) {
-    if (tid < ps.O && agr[tid] == ps.records[tid]) {
-        atomicOr(pmask, 1u << tid);
-        atomicAdd(&ps.accepted[(size_t)tid * C + c], 1ull);     // (integer adds commute: exact whatever the order of the jobs)
-    }
-    __syncthreads();
-    return *pmask;
-}
-// horizon j of an accepted job: state_of(v) is 0 / 1 / 2 = S / I / R of the state that nobody writes meanwhile
-template <class StateOf>
-__device__ __forceinline__ void sir_post_count(const SirPost<true>& ps, uint32_t mask, int j, int n, int tid, int nthr, StateOf state_of) {
-    for (int v = tid; v < n; v += nthr) {
-        const int st = state_of(v);
-        if (st == 0) continue;
-        for (uint32_t m = mask; m; m &= m - 1u) {
-            const int o = __ffs((int)m) - 1;
-            atomicAdd(&ps.counts[(((size_t)o * ps.H + j) * 2 + (st - 1)) * (size_t)n + v], 1ull);
-        }
-    }
-}
-// step `st` of a job is closed by a barrier and the next step has not written to the state.  False: no set accepts the job
-template <bool POST, class StateOf>
-__device__ __forceinline__ bool sir_post_closed(const SirPost<POST>& ps, const int* agr, uint32_t* pmask, int C, int c, int st, int n, int tid,
-                                                int nthr, uint32_t& pacc, int& hj, StateOf state_of) {
-    if constexpr (POST) {
-        if (st == ps.now) { pacc = sir_post_accept(ps, agr, pmask, C, c, tid); if (!pacc) return false; }
-        if (st >= ps.now && hj < ps.H && ps.now + ps.horizons[hj] == st) { sir_post_count(ps, pacc, hj, n, tid, nthr, state_of); ++hj; }
-    }
-    return true;
-}
-// the end of a job whose last closed step is `last`: one that ended before `now` is judged on its final state, which is its
-// state at `now`, and the horizons that are left take the final state, as sir_row_out's rows after an early end do.  The
-// caller's barrier in front of the next job's reset follows.
-template <bool POST, class StateOf>
-__device__ __forceinline__ void sir_post_finish(const SirPost<POST>& ps, const int* agr, uint32_t* pmask, int C, int c, int last, int n, int tid,
-                                                int nthr, uint32_t pacc, int hj, StateOf state_of) {
-    if constexpr (POST) {
-        if (last < ps.now) pacc = sir_post_accept(ps, agr, pmask, C, c, tid);
-        if (pacc) for (; hj < ps.H; ++hj) sir_post_count(ps, pacc, hj, n, tid, nthr, state_of);
-    }
-}
-// where a TRAJ instance writes a row of curves, a SWEEP instance adds it to its candidate's sums
-template <bool SWEEP>
-__device__ __forceinline__ void sir_row_out(uint32_t* __restrict__ curves, const SirSweep<SWEEP>& sw, long s, int c, int T, int row, int n,
-                                            int n_ever, int n_rec) {
-    if constexpr (SWEEP) sir_sums_row(sw.sums, c, T, row, n, n_ever, n_rec); else sir_curve_row(curves, s, T, row, n, n_ever, n_rec);
+template <bool SWEEP, bool SCHED, class JOBS>
+__device__ __forceinline__ SirSched<SCHED> sir_job_sched(const SirSched<SCHED>& sc, const JOBS& jobs, int c) {
+    if constexpr (SWEEP) { SirSched<SCHED> o = sc; o.phase += jobs.shifts[c]; return o; } else return sc;
 }
 
 // p[0 .. count) = val.  p is 2-byte aligned only (a caller's view): 16-byte stores over the aligned body, the < 8 elements
@@ -419,22 +183,17 @@ __global__ __launch_bounds__(256) void k_fill_i16(int16_t* __restrict__ p, size_
 #ifndef GN_SIR_UNROLL
 #define GN_SIR_UNROLL 8
 #endif
-template <bool STATE_IN_LDS, bool NODES, bool TRAJ, bool EDGES = false, bool INIT = false, bool SCHED = false, bool SWEEP = false,
-          bool SCORE = false, bool TIMED = false, bool POST = false>
+template <bool STATE_IN_LDS, bool NODES, bool TRAJ, bool EDGES = false, bool INIT = false, bool SCHED = false, class OUT = SirNoSweep>
 __global__ __launch_bounds__(1024) void k_sir_philox(const int* __restrict__ src, const int* __restrict__ dst, long nnz,
                                                     int n, const int* __restrict__ seeds, int n_seeds,
                                                     SirThr<NODES> thr_beta, SirThr<NODES> thr_gamma,
                                                     long sims, long sim_offset, int T, uint32_t k0, uint32_t k1,
                                                     uint32_t* __restrict__ hist, uint8_t* __restrict__ gstate, SirTraj<TRAJ> tr,
-                                                    SirInit<INIT> in, SirSched<SCHED> sc_call, SirSweep<SWEEP> sw, SirScore<SCORE> sr,
-                                                    SirTimed<TIMED> tm, SirPost<POST> ps) {
+                                                    SirInit<INIT> in, SirSched<SCHED> sc_call, typename OUT::Jobs sw, OUT outp) {
     static_assert(NODES || !EDGES, "per-edge infection thresholds come with per-node recovery thresholds");
     static_assert(EDGES || !SCHED, "a schedule switches per-edge tables");
-    static_assert(!SWEEP || (INIT && SCHED && !TRAJ), "the sweep overrides a drawn start and shifts a schedule; its output is the sums");
-    static_assert(!SCORE || SWEEP, "the scores are tallied over the sweep's jobs");
-    static_assert(!TIMED || (SWEEP && !SCORE), "the timed evidence is tallied over the sweep's jobs, in place of the snapshots");
-    static_assert(!POST || (SWEEP && !SCORE && !TIMED), "the posterior counts are taken over the sweep's jobs, in place of the scores");
-    constexpr bool TALLY = TRAJ || (SWEEP && !TIMED && !POST);   // the trajectory's totals are kept in tcnt
+    static_assert(!OUT::SWEEP || (INIT && SCHED && !TRAJ), "the sweep overrides a drawn start and shifts a schedule; its output is its policy's");
+    constexpr bool SWEEP = OUT::SWEEP, TALLY = TRAJ || OUT::ROWS;   // TALLY: the trajectory's totals are kept in tcnt
     extern __shared__ uint8_t smem[];
     uint8_t* state = STATE_IN_LDS ? smem : gstate + (size_t)blockIdx.x * 2 * n;
     uint8_t* flag = state + n;
@@ -444,25 +203,21 @@ __global__ __launch_bounds__(1024) void k_sir_philox(const int* __restrict__ src
     // TRAJ: the scan has no counters of its own -- [0] ever infected, [1] recovered, of the trajectory in hand (static LDS:
     // the dynamic size is what the host's occupancy choice is computed from)
     __shared__ int tcnt[2];
-    __shared__ int tal[SCORE ? 2 * GN_SIR_SCORE_MAXO : 1];      // (SCORE) the tallies of SirScore; the others never name it
-    __shared__ int dif[TIMED ? GN_SIR_TIMED_CELLS : 1];         // (TIMED) the difference array of SirTimed; likewise
-    __shared__ int agr[POST ? GN_SIR_SCORE_MAXO : 1];           // (POST) the matched records at `now` of SirPost; likewise
-    __shared__ uint32_t pmask[1];                               // (POST) the sets that accept the job in hand
-    const auto post_state = [&](int v) -> int { return (int)state[v]; };
+    __shared__ int olds[OUT::LDS_INTS ? OUT::LDS_INTS : 1];      // the output policy's; a policy without LDS never names it
+    const auto state_of = [&](int v) -> int { return (int)state[v]; };
     int16_t* ev_inf = nullptr; int16_t* ev_rec = nullptr; uint32_t* curves = nullptr;
     if constexpr (TRAJ) { ev_inf = tr.events; if (tr.events) ev_rec = tr.events + (size_t)sims * n; curves = tr.curves; }
     long jobs = sims;                             // (SWEEP) C * sims of them, the candidates interleaved
     if constexpr (SWEEP) jobs = sims * sw.C;
     for (long job = blockIdx.x; job < jobs; job += gridDim.x) {
-        long s = job; int cj = 0, cnode = -1, cact = 0, rec0 = 0;       // (SWEEP) the candidate, its node and action; the R starts
+        long s = job; int cj = 0, cnode = -1, cact = 0;                 // (SWEEP) the candidate, its node and action
         if constexpr (SWEEP) { sir_sweep_job(job, sw.C, sims, cj, s); cnode = sw.cand[cj]; if (cnode >= n) cnode = -1; cact = sw.action; }
-        const SirSched<SCHED> sc = sir_job_sched(sc_call, sw, cj);
+        typename OUT::Job jb;
+        const SirSched<SCHED> sc = sir_job_sched<SWEEP>(sc_call, sw, cj);
         const uint32_t sim = (uint32_t)(sim_offset + s);
         for (int v = threadIdx.x; v < n; v += nthr) { state[v] = ST_S; flag[v] = 0; }
         if (TALLY && threadIdx.x < 2) tcnt[threadIdx.x] = 0;
-        sir_score_reset(sr, tal, (int)threadIdx.x);
-        sir_timed_reset(tm, dif, T, (int)threadIdx.x, nthr);
-        sir_post_reset(ps, agr, pmask, (int)threadIdx.x);
+        outp.reset(olds, T, (int)threadIdx.x, nthr);
         __syncthreads();
         if constexpr (INIT) {
             // drawn start: a node that starts in I or R has left S at step 0 (one infection event), one that starts in R
@@ -477,14 +232,8 @@ __global__ __launch_bounds__(1024) void k_sir_philox(const int* __restrict__ src
                     if (!(((inf | rec) >> j) & 1u)) continue;
                     const bool r = (rec >> j) & 1u;
                     state[v] = r ? ST_R : ST_I;
-                    sir_hist_add<SWEEP>(&hinf[v]);
-                    if (r) sir_hist_add<SWEEP>(&hrec[v]);
-                    sir_score_event<SCORE, 0>(sr, tal, v);
-                    if (r) sir_score_event<SCORE, 1>(sr, tal, v);
-                    sir_timed_event<TIMED, 0>(tm, dif, T, v, 0);
-                    if (r) sir_timed_event<TIMED, 1>(tm, dif, T, v, 0);
-                    sir_post_event<POST, 0>(ps, agr, v, 0);
-                    if (r) sir_post_event<POST, 1>(ps, agr, v, 0);
+                    sir_hist_add<SWEEP>(&hinf[v]); outp.template event<0>(olds, T, v, 0);
+                    if (r) { sir_hist_add<SWEEP>(&hrec[v]); outp.template event<1>(olds, T, v, 0); }
                     if (TRAJ && ev_inf) { ev_inf[(size_t)s * n + v] = 0; if (r) ev_rec[(size_t)s * n + v] = 0; }
                 }
                 n_out += __popc(inf | rec); n_gone += __popc(rec);
@@ -507,17 +256,13 @@ __global__ __launch_bounds__(1024) void k_sir_philox(const int* __restrict__ src
             }
         }
         int rows_done = 1;                          // (TRAJ, SWEEP) rows of `curves` / of the sums written so far
-        const bool rows = (SWEEP && !TIMED && !POST) || (TRAJ && curves);       // (TIMED, POST: nothing is put out per step)
-        int t_end = sir_post_end(ps, T), plast = 0, hj = 0; uint32_t pacc = 0;   // (POST) the steps to run, the last closed one, the next horizon, the mask
-        if constexpr (POST)                                     // (the start is step 0, closed by the barrier above)
-            if (!sir_post_closed(ps, agr, pmask, sw.C, cj, 0, n, (int)threadIdx.x, nthr, pacc, hj, post_state)) t_end = 0;
+        const bool rows = OUT::ROWS || (TRAJ && curves);
+        int t_end = outp.steps(T);
+        if constexpr (OUT::CLOSES) if (!outp.closed(jb, olds, sw, cj, 0, n, (int)threadIdx.x, nthr, state_of)) t_end = 0;   // (the start is step 0, closed by the barrier above)
         if (rows) {
             __syncthreads();
-            if constexpr (SCORE) sir_score_row(sr, tal, sw.C, cj, T, 0, (int)threadIdx.x); else
-            if (threadIdx.x == 0) {
-                if constexpr (SWEEP) rec0 = tcnt[1];
-                sir_row_out(curves, sw, s, cj, T, 0, n, tcnt[0], INIT ? tcnt[1] : 0);
-            }
+            if constexpr (SWEEP) outp.row(jb, olds, sw, cj, T, 0, n, tcnt[0], tcnt[1], (int)threadIdx.x); else
+            if (threadIdx.x == 0) sir_curve_row(curves, s, T, 0, n, tcnt[0], INIT ? tcnt[1] : 0);
         }
         for (int it = 1; it < t_end; ++it) {
             const SirThr<NODES> tb_step = sir_step_thr<NODES>(thr_beta, sc, it, (size_t)nnz), tg_step = sir_step_thr<NODES>(thr_gamma, sc, it, (size_t)n);
@@ -557,17 +302,11 @@ __global__ __launch_bounds__(1024) void k_sir_philox(const int* __restrict__ src
             for (int v = threadIdx.x; v < n; v += nthr) {
                 const uint8_t f = flag[v];
                 if (f == 1) {
-                    state[v] = ST_I; sir_hist_add<SWEEP>(&hinf[(size_t)it * n + v]);
-                    sir_score_event<SCORE, 0>(sr, tal, v);
-                    sir_timed_event<TIMED, 0>(tm, dif, T, v, it);
-                    sir_post_event<POST, 0>(ps, agr, v, it);
+                    state[v] = ST_I; sir_hist_add<SWEEP>(&hinf[(size_t)it * n + v]); outp.template event<0>(olds, T, v, it);
                     if (TALLY) ++n_new;
                     if (TRAJ && ev_inf) ev_inf[(size_t)s * n + v] = (int16_t)it;
                 } else if (f == 2) {
-                    state[v] = ST_R; sir_hist_add<SWEEP>(&hrec[(size_t)it * n + v]);
-                    sir_score_event<SCORE, 1>(sr, tal, v);
-                    sir_timed_event<TIMED, 1>(tm, dif, T, v, it);
-                    sir_post_event<POST, 1>(ps, agr, v, it);
+                    state[v] = ST_R; sir_hist_add<SWEEP>(&hrec[(size_t)it * n + v]); outp.template event<1>(olds, T, v, it);
                     if (TALLY) ++n_gone;
                     if (TRAJ && ev_inf) ev_rec[(size_t)s * n + v] = (int16_t)it;
                 }
@@ -578,24 +317,20 @@ __global__ __launch_bounds__(1024) void k_sir_philox(const int* __restrict__ src
             if (TALLY && n_gone) atomicAdd(&tcnt[1], n_gone);
             const int alive = __syncthreads_or(any);
             if (rows) {                             // (the counters rest until the next step's barrier)
-                if constexpr (SCORE) sir_score_row(sr, tal, sw.C, cj, T, it, (int)threadIdx.x); else
-                if (threadIdx.x == 0) sir_row_out(curves, sw, s, cj, T, it, n, tcnt[0], tcnt[1]);
+                if constexpr (SWEEP) outp.row(jb, olds, sw, cj, T, it, n, tcnt[0], tcnt[1], (int)threadIdx.x); else
+                if (threadIdx.x == 0) sir_curve_row(curves, s, T, it, n, tcnt[0], tcnt[1]);
                 rows_done = it + 1;
             }
-            if constexpr (POST) {                   // (the next step writes flag[] alone until its own barrier: the state rests)
-                plast = it;
-                if (!sir_post_closed(ps, agr, pmask, sw.C, cj, it, n, (int)threadIdx.x, nthr, pacc, hj, post_state)) break;
-            }
+            // (the next step writes flag[] alone until its own barrier: the state rests)
+            if constexpr (OUT::CLOSES) if (!outp.closed(jb, olds, sw, cj, it, n, (int)threadIdx.x, nthr, state_of)) break;
             if (!alive) break;                      // epidemic over: no further events in this trajectory
         }
-        if (rows) {                                 // the rows after an early end repeat the final state
+        if constexpr (SWEEP) {                      // (every event lies behind a barrier)
+            outp.finish(jb, olds, sw, cj, s, sims, T, rows_done, n, OUT::ROWS ? tcnt[0] : 0, OUT::ROWS ? tcnt[1] : 0, (int)threadIdx.x, nthr, state_of);
+        } else if (rows) {                          // the rows after an early end repeat the final state
             const int n_ever = tcnt[0], n_rec = tcnt[1];
-            if constexpr (SCORE) sir_score_rows_after(sr, tal, sw.C, cj, T, rows_done, (int)threadIdx.x, nthr); else
-            for (int r = rows_done + threadIdx.x; r < T; r += nthr) sir_row_out(curves, sw, s, cj, T, r, n, n_ever, n_rec);
-            if constexpr (SWEEP && !SCORE) if (sw.ever && threadIdx.x == 0) sw.ever[(size_t)cj * sims + s] = (uint32_t)(n_ever - rec0);
+            for (int r = rows_done + threadIdx.x; r < T; r += nthr) sir_curve_row(curves, s, T, r, n, n_ever, n_rec);
         }
-        if constexpr (TIMED) sir_timed_finish(tm, dif, sw.C, cj, T, (int)threadIdx.x, nthr);   // (every event lies behind a barrier)
-        if constexpr (POST) sir_post_finish(ps, agr, pmask, sw.C, cj, plast, n, (int)threadIdx.x, nthr, pacc, hj, post_state);   // (likewise)
         __syncthreads();
     }
 }
@@ -613,21 +348,18 @@ __global__ __launch_bounds__(1024) void k_sir_philox(const int* __restrict__ src
 // and the recovery-only phase ask only whether a target is susceptible, so both stay sufficient next to w = 0 entries: a row
 // whose susceptible targets all sit behind zeros keeps being walked.  There is no COUNT && EDGES instance.
 // TRAJ: per-trajectory events and curves (SirTraj above); there is no COUNT && TRAJ instance.
-// SWEEP: the candidate sweep (SirSweep above): jobs instead of trajectories, sums instead of histograms.
+// OUT: the candidate sweep's output policy (gnode_sir_sweep.h): jobs instead of trajectories, its output instead of histograms.
 template <typename IdT, bool LISTS_IN_LDS, bool COUNT, bool NODES, bool TRAJ, bool EDGES = false, bool INIT = false, bool SCHED = false,
-          bool SWEEP = false, bool SCORE = false, bool TIMED = false, bool POST = false>
+          class OUT = SirNoSweep>
 __global__ __launch_bounds__(1024) void k_sir_frontier(const int* __restrict__ rowptr, const int* __restrict__ col, int n,
                                                       const int* __restrict__ seeds, int n_seeds,
                                                       SirThr<NODES> thr_beta, SirThr<NODES> thr_gamma,
                                                       long sims, long sim_offset, int T, uint32_t k0, uint32_t k1,
                                                       uint32_t* __restrict__ hist, int32_t* __restrict__ glists,
                                                       unsigned long long* __restrict__ stats, SirTraj<TRAJ> tr, SirInit<INIT> in,
-                                                      SirSched<SCHED> sc_call, SirSweep<SWEEP> sw, SirScore<SCORE> sr, SirTimed<TIMED> tm,
-                                                      SirPost<POST> ps) {
-    static_assert(!SWEEP || (INIT && SCHED && !TRAJ), "the sweep overrides a drawn start and shifts a schedule; its output is the sums");
-    static_assert(!SCORE || SWEEP, "the scores are tallied over the sweep's jobs");
-    static_assert(!TIMED || (SWEEP && !SCORE), "the timed evidence is tallied over the sweep's jobs, in place of the snapshots");
-    static_assert(!POST || (SWEEP && !SCORE && !TIMED), "the posterior counts are taken over the sweep's jobs, in place of the scores");
+                                                      SirSched<SCHED> sc_call, typename OUT::Jobs sw, OUT outp) {
+    constexpr bool SWEEP = OUT::SWEEP;
+    static_assert(!SWEEP || (INIT && SCHED && !TRAJ), "the sweep overrides a drawn start and shifts a schedule; its output is its policy's");
     static_assert(!(COUNT && INIT), "the counting instantiation starts from a seed list");
     static_assert(EDGES || !SCHED, "a schedule switches per-edge tables");
     static_assert(!(COUNT && TRAJ), "the counting instantiation has no per-trajectory output");
@@ -648,11 +380,8 @@ __global__ __launch_bounds__(1024) void k_sir_frontier(const int* __restrict__ r
     IdT* nxt = lists + n;
     IdT* big = lists + 2 * (size_t)n;                          // [rows longer than GN_SIR_BIGROW in the graph] (LDS form), [n] (workspace form)
     __shared__ int cnt[3];                                     // [0] next-list length, [1] big-row list length, [2] ever infected
-    __shared__ int tal[SCORE ? 2 * GN_SIR_SCORE_MAXO : 1];     // (SCORE) the tallies of SirScore; the others never name it
-    __shared__ int dif[TIMED ? GN_SIR_TIMED_CELLS : 1];        // (TIMED) the difference array of SirTimed; likewise
-    __shared__ int agr[POST ? GN_SIR_SCORE_MAXO : 1];          // (POST) the matched records at `now` of SirPost; likewise
-    __shared__ uint32_t pmask[1];                              // (POST) the sets that accept the job in hand
-    const auto post_state = [&](int v) -> int {                // (POST) S / I / R of node v off the two bitmaps
+    __shared__ int olds[OUT::LDS_INTS ? OUT::LDS_INTS : 1];    // the output policy's; a policy without LDS never names it
+    const auto state_of = [&](int v) -> int {                  // S / I / R of node v off the two bitmaps
         const uint32_t m = 1u << (v & 31);
         return (bits[v >> 5] & m) ? ((recb[v >> 5] & m) ? 2 : 1) : 0;
     };
@@ -670,13 +399,12 @@ __global__ __launch_bounds__(1024) void k_sir_frontier(const int* __restrict__ r
     for (long job = blockIdx.x; job < jobs; job += gridDim.x) {
         long s = job; int cj = 0, cnode = -1, cact = 0;        // (SWEEP) the candidate, its node and action
         if constexpr (SWEEP) { sir_sweep_job(job, sw.C, sims, cj, s); cnode = sw.cand[cj]; if (cnode >= n) cnode = -1; cact = sw.action; }
-        const SirSched<SCHED> sc = sir_job_sched(sc_call, sw, cj);
+        typename OUT::Job jb;
+        const SirSched<SCHED> sc = sir_job_sched<SWEEP>(sc_call, sw, cj);
         const uint32_t sim = (uint32_t)(sim_offset + s);
         for (int w = tid; w < nwords; w += nthr) { bits[w] = 0u; spent[w] = 0u; recb[w] = 0u; }
         if (tid < 3) cnt[tid] = 0;
-        sir_score_reset(sr, tal, tid);
-        sir_timed_reset(tm, dif, T, tid, nthr);
-        sir_post_reset(ps, agr, pmask, tid);
+        outp.reset(olds, T, tid, nthr);
         __syncthreads();
         if constexpr (INIT) {
             // drawn start (sir_init_draw): I and R starts have left S (ever-infected bit, one infection event at t = 0), R
@@ -695,14 +423,8 @@ __global__ __launch_bounds__(1024) void k_sir_frontier(const int* __restrict__ r
                 for (int j = 0; j < 4; ++j)
                     if ((out >> j) & 1u) {
                         const bool r = (rec >> j) & 1u;
-                        sir_hist_add<SWEEP>(&hinf[u0 + j]);
-                        if (r) sir_hist_add<SWEEP>(&hrec[u0 + j]);
-                        sir_score_event<SCORE, 0>(sr, tal, u0 + j);
-                        if (r) sir_score_event<SCORE, 1>(sr, tal, u0 + j);
-                        sir_timed_event<TIMED, 0>(tm, dif, T, u0 + j, 0);
-                        if (r) sir_timed_event<TIMED, 1>(tm, dif, T, u0 + j, 0);
-                        sir_post_event<POST, 0>(ps, agr, u0 + j, 0);
-                        if (r) sir_post_event<POST, 1>(ps, agr, u0 + j, 0);
+                        sir_hist_add<SWEEP>(&hinf[u0 + j]); outp.template event<0>(olds, T, u0 + j, 0);
+                        if (r) { sir_hist_add<SWEEP>(&hrec[u0 + j]); outp.template event<1>(olds, T, u0 + j, 0); }
                         if (TRAJ && ev_inf) { ev_inf[(size_t)s * n + u0 + j] = 0; if (r) ev_rec[(size_t)s * n + u0 + j] = 0; }
                     }
                 // this wave's I starts: slot = wave base + the I starts of the lanes below + this lane's own in front
@@ -737,13 +459,12 @@ __global__ __launch_bounds__(1024) void k_sir_frontier(const int* __restrict__ r
         __syncthreads();
         if (tid == 0) cnt[2] = n_ever;
         int rows_done = 1;                                     // (TRAJ, SWEEP) rows of `curves` / of the sums written so far
-        const bool rows = (SWEEP && !TIMED && !POST) || (TRAJ && curves);   // (TIMED, POST: nothing is put out per step)
-        int t_end = sir_post_end(ps, T), plast = 0, hj = 0; uint32_t pacc = 0;   // (POST) the steps to run, the last closed one, the next horizon, the mask
-        if constexpr (POST)                                    // (the start is step 0, closed by the barriers above; the first step's writes lie behind its own)
-            if (!sir_post_closed(ps, agr, pmask, sw.C, cj, 0, n, tid, nthr, pacc, hj, post_state)) t_end = 0;
-        const int rec0 = n_ever - n_inf;                       // (SWEEP) the R starts: they were never infected
-        if constexpr (SCORE) sir_score_row(sr, tal, sw.C, cj, T, 0, tid); else
-        if (rows && tid == 0) sir_row_out(curves, sw, s, cj, T, 0, n, n_ever, INIT ? n_ever - n_inf : 0);
+        const bool rows = OUT::ROWS || (TRAJ && curves);
+        int t_end = outp.steps(T);
+        // (the start is step 0, closed by the barriers above; the first step's writes lie behind its own)
+        if constexpr (OUT::CLOSES) if (!outp.closed(jb, olds, sw, cj, 0, n, tid, nthr, state_of)) t_end = 0;
+        if constexpr (SWEEP) outp.row(jb, olds, sw, cj, T, 0, n, n_ever, n_ever - n_inf, tid); else
+        if (rows && tid == 0) sir_curve_row(curves, s, T, 0, n, n_ever, INIT ? n_ever - n_inf : 0);
         for (int it = 1; it < t_end && n_inf > 0; ++it) {
             // this step's tables: drain, the recovery loop and the recovery-only branch read nothing else
             const SirThr<NODES> tb_step = sir_step_thr<NODES>(thr_beta, sc, it, sched_nnz), tg_step = sir_step_thr<NODES>(thr_gamma, sc, it, (size_t)n);
@@ -769,10 +490,7 @@ __global__ __launch_bounds__(1024) void k_sir_frontier(const int* __restrict__ r
                     for (int j = 0; j < 4; ++j)
                         if ((nib >> j) & 1u) {
                             if ((unsigned long long)w[j] < sir_thr(tg_step, u0 + j)) {
-                                gone |= 1u << j; sir_hist_add<SWEEP>(&hrec[(size_t)it * n + u0 + j]);
-                                sir_score_event<SCORE, 1>(sr, tal, u0 + j);
-                                sir_timed_event<TIMED, 1>(tm, dif, T, u0 + j, it);
-                                sir_post_event<POST, 1>(ps, agr, u0 + j, it);
+                                gone |= 1u << j; sir_hist_add<SWEEP>(&hrec[(size_t)it * n + u0 + j]); outp.template event<1>(olds, T, u0 + j, it);
                                 if (TRAJ && ev_inf) ev_rec[(size_t)s * n + u0 + j] = (int16_t)it;
                             } else ++alive;
                         }
@@ -783,12 +501,12 @@ __global__ __launch_bounds__(1024) void k_sir_frontier(const int* __restrict__ r
                 n_inf = cnt[0];
                 if (rows) {
                     n_ever = n;
-                    if constexpr (SCORE) sir_score_row(sr, tal, sw.C, cj, T, it, tid); else
-                    if (tid == 0) sir_row_out(curves, sw, s, cj, T, it, n, n_ever, n_ever - n_inf);
+                    if constexpr (SWEEP) outp.row(jb, olds, sw, cj, T, it, n, n_ever, n_ever - n_inf, tid); else
+                    if (tid == 0) sir_curve_row(curves, s, T, it, n, n_ever, n_ever - n_inf);
                     rows_done = it + 1;
                 }
                 __syncthreads();
-                if constexpr (POST) { plast = it; if (!sir_post_closed(ps, agr, pmask, sw.C, cj, it, n, tid, nthr, pacc, hj, post_state)) break; }
+                if constexpr (OUT::CLOSES) if (!outp.closed(jb, olds, sw, cj, it, n, tid, nthr, state_of)) break;
                 continue;
             }
             // infection attempts along the out-edges of the frontier: one 16-lane group per infected node, a lane takes
@@ -798,10 +516,7 @@ __global__ __launch_bounds__(1024) void k_sir_frontier(const int* __restrict__ r
                 if (!(atomicOr(&bits[v >> 5], m) & m)) {       // first edge to reach v this step (it was susceptible)
                     nxt[atomicAdd(&cnt[0], 1)] = (IdT)v;
                     atomicAdd(&cnt[2], 1);
-                    sir_hist_add<SWEEP>(&hinf[(size_t)it * n + v]);
-                    sir_score_event<SCORE, 0>(sr, tal, v);
-                    sir_timed_event<TIMED, 0>(tm, dif, T, v, it);
-                    sir_post_event<POST, 0>(ps, agr, v, it);
+                    sir_hist_add<SWEEP>(&hinf[(size_t)it * n + v]); outp.template event<0>(olds, T, v, it);
                     if (TRAJ && ev_inf) ev_inf[(size_t)s * n + v] = (int16_t)it;
                 }
             };
@@ -892,10 +607,7 @@ __global__ __launch_bounds__(1024) void k_sir_frontier(const int* __restrict__ r
                 const unsigned long long tg = sir_thr(tg_step, u);
                 const bool gone = (unsigned long long)philox_coin((uint32_t)u, (uint32_t)it, sim, 1u, k0, k1) < tg;
                 if (gone) {
-                    sir_hist_add<SWEEP>(&hrec[(size_t)it * n + u]);
-                    sir_score_event<SCORE, 1>(sr, tal, u);
-                    sir_timed_event<TIMED, 1>(tm, dif, T, u, it);
-                    sir_post_event<POST, 1>(ps, agr, u, it);
+                    sir_hist_add<SWEEP>(&hrec[(size_t)it * n + u]); outp.template event<1>(olds, T, u, it);
                     if (TRAJ && ev_inf) ev_rec[(size_t)s * n + u] = (int16_t)it;
                     atomicOr(&recb[u >> 5], 1u << (u & 31));
                 }
@@ -918,24 +630,22 @@ __global__ __launch_bounds__(1024) void k_sir_frontier(const int* __restrict__ r
             n_inf = cnt[0];
             n_ever = cnt[2];
             if (rows) {
-                if constexpr (SCORE) sir_score_row(sr, tal, sw.C, cj, T, it, tid); else
-                if (tid == 0) sir_row_out(curves, sw, s, cj, T, it, n, n_ever, n_ever - n_inf);
+                if constexpr (SWEEP) outp.row(jb, olds, sw, cj, T, it, n, n_ever, n_ever - n_inf, tid); else
+                if (tid == 0) sir_curve_row(curves, s, T, it, n, n_ever, n_ever - n_inf);
                 rows_done = it + 1;
             }
             IdT* t = cur; cur = nxt; nxt = t;
             __syncthreads();
-            // (POST) the next step's first write to a bitmap lies behind its own barrier: the walk reads a state at rest
-            if constexpr (POST) { plast = it; if (!sir_post_closed(ps, agr, pmask, sw.C, cj, it, n, tid, nthr, pacc, hj, post_state)) break; }
+            // the next step's first write to a bitmap lies behind its own barrier: a walk of the nodes reads a state at rest
+            if constexpr (OUT::CLOSES) if (!outp.closed(jb, olds, sw, cj, it, n, tid, nthr, state_of)) break;
         }
-        if (rows) {                                            // the rows after an early end repeat the final state
-            if constexpr (SCORE) sir_score_rows_after(sr, tal, sw.C, cj, T, rows_done, tid, nthr); else
-            for (int r = rows_done + tid; r < T; r += nthr) sir_row_out(curves, sw, s, cj, T, r, n, n_ever, n_ever - n_inf);
+        if constexpr (SWEEP) {
+            // (every step ends in a barrier, and so does the start: every event lies behind one)
+            outp.finish(jb, olds, sw, cj, s, sims, T, rows_done, n, n_ever, n_ever - n_inf, tid, nthr, state_of);
+            if constexpr (OUT::LDS_AT_END) __syncthreads();    // the next job resets the policy's LDS behind this
+        } else if (rows) {                                     // the rows after an early end repeat the final state
+            for (int r = rows_done + tid; r < T; r += nthr) sir_curve_row(curves, s, T, r, n, n_ever, n_ever - n_inf);
         }
-        if constexpr (SWEEP && !SCORE && !TIMED && !POST) if (sw.ever && tid == 0) sw.ever[(size_t)cj * sims + s] = (uint32_t)(n_ever - rec0);
-        if constexpr (SCORE) __syncthreads();                  // those rows read the tallies: the next job resets them behind this
-        // (every step ends in a barrier, and so does the start: every event lies behind one)
-        if constexpr (TIMED) { sir_timed_finish(tm, dif, sw.C, cj, T, tid, nthr); __syncthreads(); }
-        if constexpr (POST) { sir_post_finish(ps, agr, pmask, sw.C, cj, plast, n, tid, nthr, pacc, hj, post_state); __syncthreads(); }
     }
     if (COUNT) {
         atomicAdd(&stats[0], st_blocks); atomicAdd(&stats[1], st_ecoins); atomicAdd(&stats[2], st_rcoins); atomicAdd(&stats[3], st_entries);
@@ -1063,18 +773,15 @@ __global__ void k_put_seeds(SeedArg sa, int n_seeds, int32_t* __restrict__ seeds
 // The kernels one form of call can launch, by path (SirPath): RATES is SIR_SCALAR / SIR_NODES / SIR_EDGES.  The launch and the
 // registration below both go through sir_dispatch, so an instance cannot be launched without being registered.
 // SCHED_: the four scheduled forms (per-edge rates only, TRAJ x INIT), reached through sir_dispatch_sched.
-// SWEEP_: the candidate sweep, one form (the drawn-start scheduled one without per-trajectory output), through sir_dispatch_sweep.
-// SCORE_: the source scores, the sweep's form with the similarity tallies, through sir_dispatch_score.
-// TIMED_: the scores from timed evidence, the sweep's form with the difference array, through sir_dispatch_timed.
-// POST_: the posterior counts at one age, the sweep's form with the matched-record counters, through sir_dispatch_post.
-template <int RATES, bool TRAJ_, bool INIT_, bool SCHED_ = false, bool SWEEP_ = false, bool SCORE_ = false, bool TIMED_ = false, bool POST_ = false>
+// OUT: the candidate sweep, one form per output policy (the drawn-start scheduled one without per-trajectory output), through
+// sir_dispatch_sweep<OUT>.
+template <int RATES, bool TRAJ_, bool INIT_, bool SCHED_ = false, class OUT = SirNoSweep>
 struct SirKernels {
-    static constexpr bool NODES = RATES >= SIR_NODES, EDGES = RATES == SIR_EDGES, TRAJ = TRAJ_, INIT = INIT_, SCHED = SCHED_, SWEEP = SWEEP_, SCORE = SCORE_;
-    static constexpr bool TIMED = TIMED_, POST = POST_;
-    static constexpr auto frontier_lds = &k_sir_frontier<uint16_t, true, false, NODES, TRAJ, EDGES, INIT, SCHED, SWEEP, SCORE, TIMED, POST>;
-    static constexpr auto frontier_mem = &k_sir_frontier<int32_t, false, false, NODES, TRAJ, EDGES, INIT, SCHED, SWEEP, SCORE, TIMED, POST>;
-    static constexpr auto scan_lds = &k_sir_philox<true, NODES, TRAJ, EDGES, INIT, SCHED, SWEEP, SCORE, TIMED, POST>;
-    static constexpr auto scan_mem = &k_sir_philox<false, NODES, TRAJ, EDGES, INIT, SCHED, SWEEP, SCORE, TIMED, POST>;
+    static constexpr bool NODES = RATES >= SIR_NODES, EDGES = RATES == SIR_EDGES, TRAJ = TRAJ_, INIT = INIT_, SCHED = SCHED_;
+    static constexpr auto frontier_lds = &k_sir_frontier<uint16_t, true, false, NODES, TRAJ, EDGES, INIT, SCHED, OUT>;
+    static constexpr auto frontier_mem = &k_sir_frontier<int32_t, false, false, NODES, TRAJ, EDGES, INIT, SCHED, OUT>;
+    static constexpr auto scan_lds = &k_sir_philox<true, NODES, TRAJ, EDGES, INIT, SCHED, OUT>;
+    static constexpr auto scan_mem = &k_sir_philox<false, NODES, TRAJ, EDGES, INIT, SCHED, OUT>;
 };
 // the counting instances (gnode_sir_mc_philox_counted): the frontier walk of SirKernels<SIR_SCALAR, false, false>
 static constexpr auto kSirCountedLds = &k_sir_frontier<uint16_t, true, true, false, false>;
@@ -1093,10 +800,7 @@ template <class F> static void sir_dispatch_sched(bool traj, bool init, F&& f) {
     if (traj) { if (init) f(SirKernels<SIR_EDGES, true, true, true>{}); else f(SirKernels<SIR_EDGES, true, false, true>{}); }
     else { if (init) f(SirKernels<SIR_EDGES, false, true, true>{}); else f(SirKernels<SIR_EDGES, false, false, true>{}); }
 }
-template <class F> static void sir_dispatch_sweep(F&& f) { f(SirKernels<SIR_EDGES, false, true, true, true>{}); }
-template <class F> static void sir_dispatch_score(F&& f) { f(SirKernels<SIR_EDGES, false, true, true, true, true>{}); }
-template <class F> static void sir_dispatch_timed(F&& f) { f(SirKernels<SIR_EDGES, false, true, true, true, false, true>{}); }
-template <class F> static void sir_dispatch_post(F&& f) { f(SirKernels<SIR_EDGES, false, true, true, true, false, false, true>{}); }
+template <class OUT, class F> static void sir_dispatch_sweep(F&& f) { f(SirKernels<SIR_EDGES, false, true, true, OUT>{}); }
 
 int gn_sir_set_attributes() {       // once per device, from gnode_graph_create
     hipError_t err = hipSuccess;
@@ -1104,15 +808,11 @@ int gn_sir_set_attributes() {       // once per device, from gnode_graph_create
         const hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsStateLimit);
         if (err == hipSuccess) err = e;
     };
-    for (int form = 0; form < 12; ++form)
-        sir_dispatch(form >> 2, form & 2, form & 1, [&](auto K) { lift(K.frontier_lds); lift(K.frontier_mem); lift(K.scan_lds); });
-    for (int form = 0; form < 4; ++form)
-        sir_dispatch_sched(form & 2, form & 1, [&](auto K) { lift(K.frontier_lds); lift(K.frontier_mem); lift(K.scan_lds); });
-    sir_dispatch_sweep([&](auto K) { lift(K.frontier_lds); lift(K.frontier_mem); lift(K.scan_lds); });
-    // (the SCORE instances' static tallies come on top: sir_launch_plan keeps dynamic + kSirScoreLds within kLdsStateLimit)
-    sir_dispatch_score([&](auto K) { lift(K.frontier_lds); lift(K.frontier_mem); lift(K.scan_lds); });
-    sir_dispatch_timed([&](auto K) { lift(K.frontier_lds); lift(K.frontier_mem); lift(K.scan_lds); });    // (likewise, kSirTimedLds)
-    sir_dispatch_post([&](auto K) { lift(K.frontier_lds); lift(K.frontier_mem); lift(K.scan_lds); });     // (likewise, kSirPostLds)
+    const auto lift_form = [&](auto K) { lift(K.frontier_lds); lift(K.frontier_mem); lift(K.scan_lds); };
+    for (int form = 0; form < 12; ++form) sir_dispatch(form >> 2, form & 2, form & 1, lift_form);
+    for (int form = 0; form < 4; ++form) sir_dispatch_sched(form & 2, form & 1, lift_form);
+    // (an output policy's static LDS comes on top: sir_launch_plan keeps dynamic + static_lds within kLdsStateLimit)
+    sir_each_output([&](auto out) { sir_dispatch_sweep<decltype(out)>(lift_form); });
     lift(kSirCountedLds); lift(kSirCountedMem); lift(&k_sir_coins);
     GN_HIP(err);
     return 0;
@@ -1237,11 +937,11 @@ static int sir_mc_philox_impl(const SirCall& c) {
                 auto kernel = P.path == SIR_FRONTIER_LDS ? Kt::frontier_lds : Kt::frontier_mem;
                 if constexpr (!Kt::NODES && !Kt::TRAJ && !Kt::INIT) if (stats) kernel = P.path == SIR_FRONTIER_LDS ? kSirCountedLds : kSirCountedMem;
                 hipLaunchKernelGGL(kernel, dim3(P.grid), dim3(P.threads), P.lds, st, g->rowptr, g->col, n, seeds, c.n_seeds, tb, tg, (long)c.sims,
-                                   (long)c.sim_offset, T, k0, k1, hist, (int32_t*)tail, stats, tr, in, sc, SirSweep<false>{}, SirScore<false>{}, SirTimed<false>{}, SirPost<false>{});
+                                   (long)c.sim_offset, T, k0, k1, hist, (int32_t*)tail, stats, tr, in, sc, SirNoJobs{}, SirNoSweep{});
             } else {
                 auto kernel = P.path == SIR_SCAN_LDS ? Kt::scan_lds : Kt::scan_mem;
                 hipLaunchKernelGGL(kernel, dim3(P.grid), dim3(P.threads), P.lds, st, g->src, g->col, (long)g->nnz, n, seeds, c.n_seeds, tb, tg, (long)c.sims,
-                                   (long)c.sim_offset, T, k0, k1, hist, (uint8_t*)tail, tr, in, sc, SirSweep<false>{}, SirScore<false>{}, SirTimed<false>{}, SirPost<false>{});
+                                   (long)c.sim_offset, T, k0, k1, hist, (uint8_t*)tail, tr, in, sc, SirNoJobs{}, SirNoSweep{});
             }
         };
         // the drawn start and the schedule are sets of instances of their own: the others do not carry them
@@ -1362,133 +1062,80 @@ extern "C" int gnode_sir_mc_philox_schedule(gnode_graph_t g, const int32_t* seed
 extern "C" size_t gnode_sir_sweep_workspace_bytes(gnode_graph_t g, int32_t T, int32_t P, int32_t L, int32_t C) {
     return g && T >= 1 && P >= 1 && L >= T && C >= 1 ? sir_sweep_layout(g->info.n, g->nnz, g->n_bigrow, T, P, L, C).total : 0;
 }
-// The sweep's call, the scores' (score non-null: the snapshots as the caller holds them, int8 [O][n], and the histogram in
-// place of sums and ever), the timed scores' (timed non-null: the R records as four host arrays, and the histogram) and the
-// posterior counts' (post non-null: the records, the age, the horizons, and the two count arrays): one set of checks, one
-// staging, one launch.
-struct SirScoreCall { const int8_t* obs; int32_t O, measure, bins; uint64_t* hist; };
-struct SirTimedCall { const int32_t *rec_set, *rec_node, *rec_offset, *rec_kind; int32_t R, O, bins; uint64_t* hist; };
-struct SirPostCall { const int32_t *rec_set, *rec_node, *rec_offset, *rec_kind; int32_t R, O, now; const int32_t* horizons; int32_t H; uint64_t *counts, *accepted; };
-static int sir_sweep_impl(const char* who, gnode_graph_t g, const double* init_host, const int32_t* candidates_host, const int32_t* shifts_host,
-                          int32_t C, int32_t action, const int32_t* phase_host, int32_t P, int32_t L, const double* w_host,
-                          const double* gamma_host, int64_t sims, int64_t sim_offset, int32_t T, uint64_t rng_seed, uint64_t* sums,
-                          uint32_t* ever, void* workspace, size_t workspace_bytes, void* stream, int32_t edge_scan, const SirScoreCall* score,
-                          const SirTimedCall* timed = nullptr, const SirPostCall* post = nullptr) {
-    const hipStream_t st = (hipStream_t)stream;
-    GN_CHECK_ARG(g && workspace && init_host && candidates_host && (score ? score->obs && score->hist : timed ? timed->hist != nullptr :
-                 post ? post->counts && post->accepted : sums != nullptr), "%s: null pointer", who);
-    GN_CHECK_ARG(!timed || timed->R < 1 || (timed->rec_set && timed->rec_node && timed->rec_offset && timed->rec_kind), "%s: null pointer", who);
-    GN_CHECK_ARG(!post || post->R < 1 || (post->rec_set && post->rec_node && post->rec_offset && post->rec_kind), "%s: null pointer", who);
-    GN_CHECK_ARG(!post || post->H < 1 || post->horizons, "%s: null pointer", who);
-    GN_CHECK_ARG(P >= 1 && gamma_host && (w_host || g->nnz == 0) && (phase_host || L <= 1), "%s: a schedule takes P >= 1 phases (P = %d), the phase row and both rate tables", who, P);
-    GN_CHECK_ARG(C >= 1, "%s: C = %d: at least one candidate", who, C);
-    GN_CHECK_ARG(action == 0 || action == 1, "%s: action %d is neither 0 (seed) nor 1 (immunise)", who, action);
-    GN_CHECK_ARG(T >= 1 && sims >= 0 && sims <= 0xFFFFFFFFll && sim_offset >= 0 && sim_offset + sims <= 0xFFFFFFFFll, "%s: bad T/sims/sim_offset", who);
-    GN_CHECK_ARG(L >= T, "%s: the phase row holds L = %d entries, fewer than T = %d", who, L, T);
+// A sweep call with output `out` (its description, gnode_sir_sweep.h): check, layout, stage, workspace check, upload, launch.
+template <class OUTPUT> static int sir_sweep_impl(const SirSweepCall& c, const OUTPUT& out) {
+    using OUT = typename OUTPUT::Policy;
+    const gnode_graph_t g = c.g;
+    const hipStream_t st = (hipStream_t)c.stream;
+    const int32_t C = c.C, P = c.P, L = c.L, T = c.T;
+    GN_CHECK_ARG(g && c.workspace && c.init && c.cand && out.complete(), "%s: null pointer", c.who);
+    GN_CHECK_ARG(P >= 1 && c.gamma && (c.w || g->nnz == 0) && (c.phase || L <= 1), "%s: a schedule takes P >= 1 phases (P = %d), the phase row and both rate tables", c.who, P);
+    GN_CHECK_ARG(C >= 1, "%s: C = %d: at least one candidate", c.who, C);
+    GN_CHECK_ARG(c.action == 0 || c.action == 1, "%s: action %d is neither 0 (seed) nor 1 (immunise)", c.who, c.action);
+    GN_CHECK_ARG(T >= 1 && c.sims >= 0 && c.sims <= 0xFFFFFFFFll && c.sim_offset >= 0 && c.sim_offset + c.sims <= 0xFFFFFFFFll, "%s: bad T/sims/sim_offset", c.who);
+    GN_CHECK_ARG(L >= T, "%s: the phase row holds L = %d entries, fewer than T = %d", c.who, L, T);
     const int n = g->info.n;
-    const size_t static_lds = score ? kSirScoreLds : timed ? kSirTimedLds : post ? kSirPostLds : 0;
-    const SirScoreLayout WS = score ? sir_score_layout(n, g->nnz, g->n_bigrow, T, P, L, C, score->O) : SirScoreLayout{};
-    const SirTimedLayout WT = timed ? sir_timed_layout(n, g->nnz, g->n_bigrow, T, P, L, C, timed->O, timed->R) : SirTimedLayout{};
-    const SirPostLayout WP = post ? sir_post_layout(n, g->nnz, g->n_bigrow, T, P, L, C, post->O, post->R, post->H) : SirPostLayout{};
-    const SirSweepLayout W = score ? static_cast<const SirSweepLayout&>(WS) : timed ? static_cast<const SirSweepLayout&>(WT)
-                           : post ? static_cast<const SirSweepLayout&>(WP) : sir_sweep_layout(n, g->nnz, g->n_bigrow, T, P, L, C);
-    SirScoreStaged staged;
-    SirTimedStaged records;
-    SirPostStaged posted;
-    if (score) staged = sir_stage_score(who, n, g->nnz, T, P, L, phase_host, w_host, gamma_host, init_host, C, shifts_host, score->obs, score->O, score->measure, score->bins);
-    else if (timed) records = sir_stage_timed(who, n, g->nnz, T, P, L, phase_host, w_host, gamma_host, init_host, C, shifts_host, timed->rec_set, timed->rec_node,
-                                              timed->rec_offset, timed->rec_kind, timed->R, timed->O, timed->bins);
-    else if (post) posted = sir_stage_post(who, n, g->nnz, T, P, L, phase_host, w_host, gamma_host, init_host, C, shifts_host, post->rec_set, post->rec_node,
-                                           post->rec_offset, post->rec_kind, post->R, post->O, post->now, post->horizons, post->H);
-    else staged.thr = sir_stage_sweep(who, n, g->nnz, T, P, L, phase_host, w_host, gamma_host, init_host, C, shifts_host);
-    const SirThresholds& thr = timed ? records.thr : post ? posted.thr : staged.thr;
-    if (score || timed || post) GN_CHECK_ARG(thr.error.empty(), "%s", thr.error.c_str());   // (the scores: an argument is refused before the workspace is asked about)
-    if (workspace_bytes < W.total) {
-        gnode_set_error("%s: workspace %zu < %zu", who, workspace_bytes, W.total);
+    const typename OUTPUT::Layout W = out.layout(c);
+    const typename OUTPUT::Staged staged = out.stage(c);
+    const SirThresholds& thr = staged.thr;
+    if (OUTPUT::args_first) GN_CHECK_ARG(thr.error.empty(), "%s", thr.error.c_str());
+    if (c.workspace_bytes < W.total) {
+        gnode_set_error("%s: workspace %zu < %zu", c.who, c.workspace_bytes, W.total);
         return GNODE_ERR_WORKSPACE;
     }
     GN_CHECK_ARG(thr.error.empty(), "%s", thr.error.c_str());
-    char* ws = (char*)workspace;
+    char* ws = (char*)c.workspace;
     const unsigned long long *thr_b = (const unsigned long long*)(ws + W.thr), *thr_g = thr_b + (size_t)P * (size_t)g->nnz;
-    const unsigned long long* thr_start = (const unsigned long long*)(ws + W.start);
-    int32_t *phase_dev = (int32_t*)(ws + W.phase), *cand_dev = (int32_t*)(ws + W.cand), *shifts_dev = (int32_t*)(ws + W.shifts);
-    const std::vector<int32_t> no_shift(shifts_host ? 0 : (size_t)C, 0);
-    GN_HIP(hipMemcpyAsync((void*)thr_b, thr.rates.data(), thr.rates.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, st));
-    GN_HIP(hipMemcpyAsync((void*)thr_start, thr.start.data(), thr.start.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, st));
-    if (L > 1) GN_HIP(hipMemcpyAsync(phase_dev, phase_host, sizeof(int32_t) * (size_t)L, hipMemcpyHostToDevice, st));
-    GN_HIP(hipMemcpyAsync(cand_dev, candidates_host, sizeof(int32_t) * (size_t)C, hipMemcpyHostToDevice, st));
-    GN_HIP(hipMemcpyAsync(shifts_dev, shifts_host ? shifts_host : no_shift.data(), sizeof(int32_t) * (size_t)C, hipMemcpyHostToDevice, st));
-    if (score) {
-        GN_HIP(hipMemcpyAsync(ws + WS.obs, staged.obs.data(), staged.obs.size(), hipMemcpyHostToDevice, st));
-        GN_HIP(hipMemcpyAsync(ws + WS.marked, staged.marked.data(), sizeof(int32_t) * staged.marked.size(), hipMemcpyHostToDevice, st));
-        GN_HIP(hipMemcpyAsync(ws + WS.seen, staged.seen.data(), sizeof(int32_t) * staged.seen.size(), hipMemcpyHostToDevice, st));
-    }
-    if (timed) {
-        GN_HIP(hipMemcpyAsync(ws + WT.rec_ptr, records.rec_ptr.data(), sizeof(int32_t) * records.rec_ptr.size(), hipMemcpyHostToDevice, st));
-        GN_HIP(hipMemcpyAsync(ws + WT.rec, records.rec.data(), sizeof(uint32_t) * records.rec.size(), hipMemcpyHostToDevice, st));
-        GN_HIP(hipMemcpyAsync(ws + WT.zeros, records.zeros.data(), sizeof(int32_t) * records.zeros.size(), hipMemcpyHostToDevice, st));
-        GN_HIP(hipMemcpyAsync(ws + WT.records, records.records.data(), sizeof(int32_t) * records.records.size(), hipMemcpyHostToDevice, st));
-    }
-    if (post) {
-        GN_HIP(hipMemcpyAsync(ws + WP.rec_ptr, posted.rec_ptr.data(), sizeof(int32_t) * posted.rec_ptr.size(), hipMemcpyHostToDevice, st));
-        GN_HIP(hipMemcpyAsync(ws + WP.rec, posted.rec.data(), sizeof(uint32_t) * posted.rec.size(), hipMemcpyHostToDevice, st));
-        GN_HIP(hipMemcpyAsync(ws + WP.zeros, posted.zeros.data(), sizeof(int32_t) * posted.zeros.size(), hipMemcpyHostToDevice, st));
-        GN_HIP(hipMemcpyAsync(ws + WP.records, posted.records.data(), sizeof(int32_t) * posted.records.size(), hipMemcpyHostToDevice, st));
-        GN_HIP(hipMemcpyAsync(ws + WP.horizons, posted.horizons.data(), sizeof(int32_t) * posted.horizons.size(), hipMemcpyHostToDevice, st));
-    }
+    const std::vector<int32_t> no_shift(c.shifts ? 0 : (size_t)C, 0);
+    std::vector<SirUpload> up = {{W.thr, thr.rates.data(), thr.rates.size() * sizeof(unsigned long long)},
+                                 {W.start, thr.start.data(), thr.start.size() * sizeof(unsigned long long)},
+                                 {W.phase, c.phase, L > 1 ? sizeof(int32_t) * (size_t)L : 0},
+                                 {W.cand, c.cand, sizeof(int32_t) * (size_t)C},
+                                 {W.shifts, c.shifts ? c.shifts : no_shift.data(), sizeof(int32_t) * (size_t)C}};
+    for (const SirUpload& u : staged.uploads(W)) up.push_back(u);
+    for (const SirUpload& u : up)
+        if (u.bytes) GN_HIP(hipMemcpyAsync(ws + u.at, u.from, u.bytes, hipMemcpyHostToDevice, st));
     GN_HIP(hipStreamSynchronize(st));                          // the host arrays are done with
-    if (sims == 0) return 0;
-    const uint32_t k0 = (uint32_t)(rng_seed & 0xFFFFFFFFull), k1 = (uint32_t)(rng_seed >> 32);
+    if (c.sims == 0) return 0;
+    const uint32_t k0 = (uint32_t)(c.rng_seed & 0xFFFFFFFFull), k1 = (uint32_t)(c.rng_seed >> 32);
     const bool sampled = gn_prof_begin(3, st);
-    const SirLaunch Pl = sir_launch_plan(n, g->n_bigrow, g->info.num_cu, (int64_t)C * sims, edge_scan != 0, static_lds);
+    const SirLaunch Pl = sir_launch_plan(n, g->n_bigrow, g->info.num_cu, (int64_t)C * c.sims, c.edge_scan != 0, OUTPUT::static_lds);
     void* tail = Pl.path == SIR_FRONTIER_MEM || Pl.path == SIR_SCAN_MEM ? ws + W.tail : nullptr;   // the lists / the state, when not in LDS
-    auto launch = [&](auto K) {
+    SirInit<true> in; in.thr = (const unsigned long long*)(ws + W.start);
+    SirSched<true> sc; sc.phase = (const int32_t*)(ws + W.phase);
+    typename OUT::Jobs jobs; jobs.cand = (const int32_t*)(ws + W.cand); jobs.shifts = (const int32_t*)(ws + W.shifts); jobs.C = C; jobs.action = c.action;
+    OUT o;
+    out.fill(jobs, o, ws, W);
+    sir_dispatch_sweep<OUT>([&](auto K) {
         using Kt = decltype(K);
-        SirInit<true> in; in.thr = thr_start;
-        SirSched<true> sc; sc.phase = phase_dev;
-        SirSweep<true> sw; sw.cand = cand_dev; sw.shifts = shifts_dev; sw.C = C; sw.action = action; sw.sums = (unsigned long long*)sums; sw.ever = ever;
-        SirScore<Kt::SCORE> sr;
-        if constexpr (Kt::SCORE) {
-            sr.obs = (const int8_t*)(ws + WS.obs); sr.marked = (const int32_t*)(ws + WS.marked); sr.seen = (const int32_t*)(ws + WS.seen);
-            sr.O = score->O; sr.measure = score->measure; sr.bins = score->bins; sr.hist = (unsigned long long*)score->hist;
-        }
-        SirTimed<Kt::TIMED> tm;
-        if constexpr (Kt::TIMED) {
-            tm.rec_ptr = (const int32_t*)(ws + WT.rec_ptr); tm.rec = (const uint32_t*)(ws + WT.rec); tm.zeros = (const int32_t*)(ws + WT.zeros);
-            tm.records = (const int32_t*)(ws + WT.records); tm.O = timed->O; tm.bins = timed->bins; tm.hist = (unsigned long long*)timed->hist;
-        }
-        SirPost<Kt::POST> ps;
-        if constexpr (Kt::POST) {
-            ps.rec_ptr = (const int32_t*)(ws + WP.rec_ptr); ps.rec = (const uint32_t*)(ws + WP.rec); ps.zeros = (const int32_t*)(ws + WP.zeros);
-            ps.records = (const int32_t*)(ws + WP.records); ps.horizons = (const int32_t*)(ws + WP.horizons); ps.O = post->O; ps.now = post->now;
-            ps.H = post->H; ps.counts = (unsigned long long*)post->counts; ps.accepted = (unsigned long long*)post->accepted;
-        }
         if (Pl.path == SIR_FRONTIER_LDS || Pl.path == SIR_FRONTIER_MEM) {
             auto kernel = Pl.path == SIR_FRONTIER_LDS ? Kt::frontier_lds : Kt::frontier_mem;
-            hipLaunchKernelGGL(kernel, dim3(Pl.grid), dim3(Pl.threads), Pl.lds, st, g->rowptr, g->col, n, (const int*)nullptr, 0, thr_b, thr_g, (long)sims,
-                               (long)sim_offset, T, k0, k1, (uint32_t*)nullptr, (int32_t*)tail, (unsigned long long*)nullptr, SirTraj<false>{}, in, sc, sw, sr, tm, ps);
+            hipLaunchKernelGGL(kernel, dim3(Pl.grid), dim3(Pl.threads), Pl.lds, st, g->rowptr, g->col, n, (const int*)nullptr, 0, thr_b, thr_g, (long)c.sims,
+                               (long)c.sim_offset, T, k0, k1, (uint32_t*)nullptr, (int32_t*)tail, (unsigned long long*)nullptr, SirTraj<false>{}, in, sc, jobs, o);
         } else {
             auto kernel = Pl.path == SIR_SCAN_LDS ? Kt::scan_lds : Kt::scan_mem;
             hipLaunchKernelGGL(kernel, dim3(Pl.grid), dim3(Pl.threads), Pl.lds, st, g->src, g->col, (long)g->nnz, n, (const int*)nullptr, 0, thr_b, thr_g,
-                               (long)sims, (long)sim_offset, T, k0, k1, (uint32_t*)nullptr, (uint8_t*)tail, SirTraj<false>{}, in, sc, sw, sr, tm, ps);
+                               (long)c.sims, (long)c.sim_offset, T, k0, k1, (uint32_t*)nullptr, (uint8_t*)tail, SirTraj<false>{}, in, sc, jobs, o);
         }
-    };
-    if (score) sir_dispatch_score(launch); else if (timed) sir_dispatch_timed(launch); else if (post) sir_dispatch_post(launch); else sir_dispatch_sweep(launch);
+    });
     if (sampled) gn_prof_end(3, st);
     GN_LAUNCH_CHECK();
     return 0;
 }
+// the arguments every sweep entry has, under the names every one gives them
+#define SIR_SWEEP_CALL(name)                                                                                                                   \
+    SirSweepCall{name, g, init_host, candidates_host, shifts_host, C, action, phase_host, P, L, w_host, gamma_host, sims, sim_offset, T, rng_seed, \
+                 workspace, workspace_bytes, stream, edge_scan}
 extern "C" int gnode_sir_mc_philox_sweep(gnode_graph_t g, const double* init_host, const int32_t* candidates_host, const int32_t* shifts_host,
                                          int32_t C, int32_t action, const int32_t* phase_host, int32_t P, int32_t L, const double* w_host,
                                          const double* gamma_host, int64_t sims, int64_t sim_offset, int32_t T, uint64_t rng_seed,
                                          uint64_t* sums, uint32_t* ever, void* workspace, size_t workspace_bytes, void* stream,
                                          int32_t edge_scan) {
-    return sir_sweep_impl("gnode_sir_mc_philox_sweep", g, init_host, candidates_host, shifts_host, C, action, phase_host, P, L, w_host, gamma_host, sims,
-                          sim_offset, T, rng_seed, sums, ever, workspace, workspace_bytes, stream, edge_scan, nullptr);
+    return sir_sweep_impl(SIR_SWEEP_CALL("gnode_sir_mc_philox_sweep"), SirSumsOutput{sums, ever});
 }
 
-// Monte-Carlo source scores (SCORE instances): the sweep's trajectories, every step of every one binned by its similarity with
-// each of O snapshots; the histogram, no sums.
+// Monte-Carlo source scores (SirScores): the sweep's trajectories, every step of every one binned by its similarity with each of
+// O snapshots; the histogram, no sums.
 extern "C" size_t gnode_sir_sweep_scores_workspace_bytes(gnode_graph_t g, int32_t T, int32_t P, int32_t L, int32_t C, int32_t O) {
     return g && T >= 1 && P >= 1 && L >= T && C >= 1 && O >= 1 && O <= GN_SIR_SCORE_MAXO ? sir_score_layout(g->info.n, g->nnz, g->n_bigrow, T, P, L, C, O).total : 0;
 }
@@ -1497,12 +1144,10 @@ extern "C" int gnode_sir_mc_philox_sweep_scores(gnode_graph_t g, const double* i
                                                 const double* gamma_host, const int8_t* obs_host, int32_t O, int32_t measure, int32_t bins,
                                                 int64_t sims, int64_t sim_offset, int32_t T, uint64_t rng_seed, uint64_t* hist, void* workspace,
                                                 size_t workspace_bytes, void* stream, int32_t edge_scan) {
-    const SirScoreCall score = {obs_host, O, measure, bins, hist};
-    return sir_sweep_impl("gnode_sir_mc_philox_sweep_scores", g, init_host, candidates_host, shifts_host, C, action, phase_host, P, L, w_host, gamma_host,
-                          sims, sim_offset, T, rng_seed, nullptr, nullptr, workspace, workspace_bytes, stream, edge_scan, &score);
+    return sir_sweep_impl(SIR_SWEEP_CALL("gnode_sir_mc_philox_sweep_scores"), SirScoresOutput{obs_host, O, measure, bins, hist});
 }
 
-// Monte-Carlo source scores from timed evidence (TIMED instances): the sweep's trajectories, every age t of every one binned by
+// Monte-Carlo source scores from timed evidence (SirTimedScores): the sweep's trajectories, every age t of every one binned by
 // the number of records of each of O evidence sets it agrees with; the histogram, no sums.
 extern "C" size_t gnode_sir_sweep_timed_workspace_bytes(gnode_graph_t g, int32_t T, int32_t P, int32_t L, int32_t C, int32_t O, int32_t R) {
     return g && T >= 1 && P >= 1 && L >= T && C >= 1 && O >= 1 && O <= GN_SIR_SCORE_MAXO && R >= 1 ? sir_timed_layout(g->info.n, g->nnz, g->n_bigrow, T, P, L, C, O, R).total : 0;
@@ -1513,12 +1158,10 @@ extern "C" int gnode_sir_mc_philox_sweep_timed(gnode_graph_t g, const double* in
                                                const int32_t* rec_kind, int32_t R, int32_t O, int32_t bins, int64_t sims, int64_t sim_offset, int32_t T,
                                                uint64_t rng_seed, uint64_t* hist, void* workspace, size_t workspace_bytes, void* stream,
                                                int32_t edge_scan) {
-    const SirTimedCall timed = {rec_set, rec_node, rec_offset, rec_kind, R, O, bins, hist};
-    return sir_sweep_impl("gnode_sir_mc_philox_sweep_timed", g, init_host, candidates_host, shifts_host, C, action, phase_host, P, L, w_host, gamma_host,
-                          sims, sim_offset, T, rng_seed, nullptr, nullptr, workspace, workspace_bytes, stream, edge_scan, nullptr, &timed);
+    return sir_sweep_impl(SIR_SWEEP_CALL("gnode_sir_mc_philox_sweep_timed"), SirTimedOutput{{rec_set, rec_node, rec_offset, rec_kind, R, O}, bins, hist});
 }
 
-// Nowcast and forecast from timed evidence (POST instances): the sweep's trajectories, each accepted for the evidence sets whose
+// Nowcast and forecast from timed evidence (SirPosteriorCounts): the sweep's trajectories, each accepted for the evidence sets whose
 // records it matches at age `now`, and the states of the accepted ones counted per node at now + horizons[j]; no sums.
 extern "C" size_t gnode_sir_sweep_posterior_workspace_bytes(gnode_graph_t g, int32_t T, int32_t P, int32_t L, int32_t C, int32_t O, int32_t R, int32_t H) {
     return g && T >= 1 && P >= 1 && L >= T && C >= 1 && O >= 1 && O <= GN_SIR_SCORE_MAXO && R >= 1 && H >= 1 && H <= GN_SIR_POST_MAXH
@@ -1530,9 +1173,8 @@ extern "C" int gnode_sir_mc_philox_sweep_posterior(gnode_graph_t g, const double
                                                    const int32_t* rec_kind, int32_t R, int32_t O, int32_t now, const int32_t* horizons_host, int32_t H,
                                                    int64_t sims, int64_t sim_offset, int32_t T, uint64_t rng_seed, uint64_t* counts, uint64_t* accepted,
                                                    void* workspace, size_t workspace_bytes, void* stream, int32_t edge_scan) {
-    const SirPostCall post = {rec_set, rec_node, rec_offset, rec_kind, R, O, now, horizons_host, H, counts, accepted};
-    return sir_sweep_impl("gnode_sir_mc_philox_sweep_posterior", g, init_host, candidates_host, shifts_host, C, action, phase_host, P, L, w_host,
-                          gamma_host, sims, sim_offset, T, rng_seed, nullptr, nullptr, workspace, workspace_bytes, stream, edge_scan, nullptr, nullptr, &post);
+    return sir_sweep_impl(SIR_SWEEP_CALL("gnode_sir_mc_philox_sweep_posterior"),
+                          SirPosteriorOutput{{rec_set, rec_node, rec_offset, rec_kind, R, O}, now, horizons_host, H, counts, accepted});
 }
 
 extern "C" int gnode_sir_mc_coins(const int32_t* table_src, const int32_t* table_dst, int64_t n_table, int32_t n,

@@ -9,7 +9,7 @@ static size_t al(size_t x) { return (x + 255) / 256 * 256; }
 static size_t frontier_bitmap_bytes(int n) { return 3 * ((((size_t)n + 31) / 32 + 3) & ~(size_t)3) * 4; }   // ever-infected + spent + recovered
 // list elements in LDS: current + next frontier [n] each, long rows [as many as the graph has, padded to 8]
 static size_t frontier_list_bytes(int n, int n_big) { return 2 * (2 * (size_t)n + (((size_t)n_big + 7) & ~(size_t)7)); }
-// static_lds (here and below): what the instance keeps in static LDS beyond the few counters every instance has -- the SCORE
+// static_lds (here and below): what the instance keeps in static LDS beyond the few counters every instance has -- e.g. the SCORE
 // instances' tallies (kSirScoreLds) -- so that the same 48 KiB hold the lists AND the tallies
 bool frontier_lists_in_lds(int n, int n_big, size_t static_lds) {
     return n <= 65536 && frontier_bitmap_bytes(n) + frontier_list_bytes(n, n_big) + static_lds <= 48 * 1024;
@@ -200,17 +200,36 @@ SirScoreLayout sir_score_layout(int n, int64_t nnz, int n_bigrow, int T, int P, 
     return W;
 }
 
+// The checks the scored sweeps share, each a refusal (the message; empty: accepted).  O things (`what`: snapshots, evidence sets)
+// per call, as many as the kernels' static LDS has room for ...
+static std::string bad_sets(const char* who, int O, const char* what) {
+    char buf[256];
+    if (O >= 1 && O <= GN_SIR_SCORE_MAXO) return std::string();
+    snprintf(buf, sizeof buf, "%s: O = %d %s: 1 to %d in one call", who, O, what, GN_SIR_SCORE_MAXO);
+    return buf;
+}
+// ... and an output array of d0 * d1 * d2 * d3 cells, which the kernels index below 2^31
+static bool cells_fit(int d0, int d1, int d2, int d3) {
+    return (double)d0 * (double)std::max(d1, 1) * (double)std::max(d2, 1) * (double)std::max(d3, 1) < 2147483648.0;
+}
+static std::string bad_hist(const char* who, int O, int C, int T, int bins) {
+    char buf[256];
+    if (cells_fit(O, C, T, bins + 1)) return std::string();
+    snprintf(buf, sizeof buf, "%s: the histogram [O = %d][C = %d][T = %d][bins + 1 = %d] has 2^31 cells or more", who, O, C, T, bins + 1);
+    return buf;
+}
+
 SirScoreStaged sir_stage_score(const char* who, int n, int64_t nnz, int T, int P, int L, const int32_t* phase, const double* w,
                                const double* gamma, const double* init, int C, const int32_t* shifts, const int8_t* obs, int O, int measure,
                                int bins) {
     char buf[256];
+    std::string bad;
     SirScoreStaged s;                                                  // (a refusal: nothing staged, only thr.error)
 #define refuse_score(...) (s.thr = refuse(__VA_ARGS__), s)
-    if (O < 1 || O > GN_SIR_SCORE_MAXO) return refuse_score("%s: O = %d snapshots: 1 to %d in one call", who, O, GN_SIR_SCORE_MAXO);
+    if (!(bad = bad_sets(who, O, "snapshots")).empty()) return refuse_score("%s", bad.c_str());
     if (bins < 1 || bins > 4096) return refuse_score("%s: bins = %d is not in [1, 4096]", who, bins);
     if (measure != 0 && measure != 1) return refuse_score("%s: measure %d is neither 0 (jaccard) nor 1 (match)", who, measure);
-    if ((double)O * (double)std::max(C, 1) * (double)std::max(T, 1) * (double)(bins + 1) >= 2147483648.0)
-        return refuse_score("%s: the histogram [O = %d][C = %d][T = %d][bins + 1 = %d] has 2^31 cells or more", who, O, C, T, bins + 1);
+    if (!(bad = bad_hist(who, O, C, T, bins)).empty()) return refuse_score("%s", bad.c_str());
     std::vector<int32_t> marked((size_t)O, 0), seen((size_t)O, 0);
     for (int o = 0; o < O; ++o) {
         for (int v = 0; v < n; ++v) {
@@ -229,10 +248,13 @@ SirScoreStaged sir_stage_score(const char* who, int n, int64_t nnz, int T, int P
     s.marked = std::move(marked); s.seen = std::move(seen);
     return s;
 }
+template <class V> static SirUpload upload(size_t at, const V& v) { return {at, v.data(), v.size() * sizeof(v[0])}; }
+std::vector<SirUpload> SirScoreStaged::uploads(const SirScoreLayout& W) const { return {upload(W.obs, obs), upload(W.marked, marked), upload(W.seen, seen)}; }
 
-SirTimedLayout sir_timed_layout(int n, int64_t nnz, int n_bigrow, int T, int P, int L, int C, int O, int R) {
+// the sweep's layout under `static_lds`, then the records of a timed call (sir_timed_layout, sir_post_layout)
+static SirTimedLayout record_layout(int n, int64_t nnz, int n_bigrow, int T, int P, int L, int C, int O, int R, size_t static_lds) {
     SirTimedLayout W;
-    static_cast<SirSweepLayout&>(W) = sweep_layout(n, nnz, n_bigrow, T, P, L, C, kSirTimedLds);
+    static_cast<SirSweepLayout&>(W) = sweep_layout(n, nnz, n_bigrow, T, P, L, C, static_lds);
     const size_t table = al((size_t)std::max(O, 1) * sizeof(int32_t));
     W.rec_ptr = W.total;
     W.rec = W.rec_ptr + al(((size_t)n + 1) * sizeof(int32_t));
@@ -240,6 +262,9 @@ SirTimedLayout sir_timed_layout(int n, int64_t nnz, int n_bigrow, int T, int P, 
     W.records = W.zeros + table;
     W.total = W.records + table;
     return W;
+}
+SirTimedLayout sir_timed_layout(int n, int64_t nnz, int n_bigrow, int T, int P, int L, int C, int O, int R) {
+    return record_layout(n, nnz, n_bigrow, T, P, L, C, O, R, kSirTimedLds);
 }
 
 // The records of a timed call (sir_stage_timed, sir_stage_post), in two halves around the sweep's own staging.  The checks: R >= 1,
@@ -276,39 +301,43 @@ static void sort_records(int n, int T, const int32_t* rec_set, const int32_t* re
     }
     s.rec_ptr = std::move(ptr);
 }
+// The sequence both timed calls end in: the records' checks, the sweep's own staging, the sort.
+static void stage_records(const char* who, int n, int64_t nnz, int T, int P, int L, const int32_t* phase, const double* w, const double* gamma,
+                          const double* init, int C, const int32_t* shifts, const int32_t* rec_set, const int32_t* rec_node,
+                          const int32_t* rec_offset, const int32_t* rec_kind, int R, int O, SirTimedStaged& s) {
+    std::vector<int32_t> zeros, records, ptr;
+    const std::string bad = check_records(who, n, rec_set, rec_node, rec_offset, rec_kind, R, O, zeros, records, ptr);
+    if (!bad.empty()) { s.thr = refused(bad.c_str()); return; }
+    s.thr = sir_stage_sweep(who, n, nnz, T, P, L, phase, w, gamma, init, C, shifts);
+    if (!s.thr.error.empty()) return;
+    sort_records(n, T, rec_set, rec_node, rec_offset, rec_kind, R, ptr, s);
+    s.zeros = std::move(zeros); s.records = std::move(records);
+}
+std::vector<SirUpload> SirTimedStaged::uploads(const SirTimedLayout& W) const {
+    return {upload(W.rec_ptr, rec_ptr), upload(W.rec, rec), upload(W.zeros, zeros), upload(W.records, records)};
+}
 
 SirTimedStaged sir_stage_timed(const char* who, int n, int64_t nnz, int T, int P, int L, const int32_t* phase, const double* w,
                                const double* gamma, const double* init, int C, const int32_t* shifts, const int32_t* rec_set,
                                const int32_t* rec_node, const int32_t* rec_offset, const int32_t* rec_kind, int R, int O, int bins) {
     char buf[256];
+    std::string bad;
     SirTimedStaged s;                                                  // (a refusal: nothing staged, only thr.error)
 #define refuse_timed(...) (s.thr = refuse(__VA_ARGS__), s)
-    if (O < 1 || O > GN_SIR_SCORE_MAXO) return refuse_timed("%s: O = %d evidence sets: 1 to %d in one call", who, O, GN_SIR_SCORE_MAXO);
+    if (!(bad = bad_sets(who, O, "evidence sets")).empty()) return refuse_timed("%s", bad.c_str());
     if ((int64_t)O * std::max(T, 1) > GN_SIR_TIMED_CELLS)
         return refuse_timed("%s: O = %d sets x T = %d steps are more than the %d cells of the difference array", who, O, T, GN_SIR_TIMED_CELLS);
     if (bins < 1 || bins > 4096) return refuse_timed("%s: bins = %d is not in [1, 4096]", who, bins);
-    if ((double)O * (double)std::max(C, 1) * (double)std::max(T, 1) * (double)(bins + 1) >= 2147483648.0)
-        return refuse_timed("%s: the histogram [O = %d][C = %d][T = %d][bins + 1 = %d] has 2^31 cells or more", who, O, C, T, bins + 1);
+    if (!(bad = bad_hist(who, O, C, T, bins)).empty()) return refuse_timed("%s", bad.c_str());
 #undef refuse_timed
-    std::vector<int32_t> zeros, records, ptr;
-    const std::string bad = check_records(who, n, rec_set, rec_node, rec_offset, rec_kind, R, O, zeros, records, ptr);
-    if (!bad.empty()) { s.thr = refused(bad.c_str()); return s; }
-    s.thr = sir_stage_sweep(who, n, nnz, T, P, L, phase, w, gamma, init, C, shifts);
-    if (!s.thr.error.empty()) return s;
-    sort_records(n, T, rec_set, rec_node, rec_offset, rec_kind, R, ptr, s);
-    s.zeros = std::move(zeros); s.records = std::move(records);
+    stage_records(who, n, nnz, T, P, L, phase, w, gamma, init, C, shifts, rec_set, rec_node, rec_offset, rec_kind, R, O, s);
     return s;
 }
 
 SirPostLayout sir_post_layout(int n, int64_t nnz, int n_bigrow, int T, int P, int L, int C, int O, int R, int H) {
     SirPostLayout W;
-    static_cast<SirSweepLayout&>(W) = sweep_layout(n, nnz, n_bigrow, T, P, L, C, kSirPostLds);
-    const size_t table = al((size_t)std::max(O, 1) * sizeof(int32_t));
-    W.rec_ptr = W.total;
-    W.rec = W.rec_ptr + al(((size_t)n + 1) * sizeof(int32_t));
-    W.zeros = W.rec + al((size_t)std::max(R, 1) * sizeof(uint32_t));
-    W.records = W.zeros + table;
-    W.horizons = W.records + table;
+    static_cast<SirTimedLayout&>(W) = record_layout(n, nnz, n_bigrow, T, P, L, C, O, R, kSirPostLds);
+    W.horizons = W.total;
     W.total = W.horizons + al((size_t)std::max(H, 1) * sizeof(int32_t));
     return W;
 }
@@ -318,9 +347,10 @@ SirPostStaged sir_stage_post(const char* who, int n, int64_t nnz, int T, int P, 
                              const int32_t* rec_node, const int32_t* rec_offset, const int32_t* rec_kind, int R, int O, int now,
                              const int32_t* horizons, int H) {
     char buf[256];
+    std::string bad;
     SirPostStaged s;                                                   // (a refusal: nothing staged, only thr.error)
 #define refuse_post(...) (s.thr = refuse(__VA_ARGS__), s)
-    if (O < 1 || O > GN_SIR_SCORE_MAXO) return refuse_post("%s: O = %d evidence sets: 1 to %d in one call", who, O, GN_SIR_SCORE_MAXO);
+    if (!(bad = bad_sets(who, O, "evidence sets")).empty()) return refuse_post("%s", bad.c_str());
     if (now < 0 || now >= T) return refuse_post("%s: now = %d is not in [0, T = %d)", who, now, T);
     if (H < 1 || H > GN_SIR_POST_MAXH) return refuse_post("%s: H = %d horizons: 1 to %d in one call", who, H, GN_SIR_POST_MAXH);
     for (int j = 0; j < H; ++j) {
@@ -328,16 +358,14 @@ SirPostStaged sir_stage_post(const char* who, int n, int64_t nnz, int T, int P, 
         if (j > 0 && horizons[j] <= horizons[j - 1]) return refuse_post("%s: horizons[%d] = %d does not ascend from horizons[%d] = %d", who, j, horizons[j], j - 1, horizons[j - 1]);
         if ((int64_t)now + horizons[j] > (int64_t)T - 1) return refuse_post("%s: horizons[%d] = %d: now + horizon = %lld is past the last step T - 1 = %d", who, j, horizons[j], (long long)now + horizons[j], T - 1);
     }
-    if ((double)O * (double)H * 2.0 * (double)std::max(n, 1) >= 2147483648.0)
-        return refuse_post("%s: the counts [O = %d][H = %d][2][n = %d] have 2^31 cells or more", who, O, H, n);
+    if (!cells_fit(O, H, 2, n)) return refuse_post("%s: the counts [O = %d][H = %d][2][n = %d] have 2^31 cells or more", who, O, H, n);
 #undef refuse_post
-    std::vector<int32_t> zeros, records, ptr;
-    const std::string bad = check_records(who, n, rec_set, rec_node, rec_offset, rec_kind, R, O, zeros, records, ptr);
-    if (!bad.empty()) { s.thr = refused(bad.c_str()); return s; }
-    s.thr = sir_stage_sweep(who, n, nnz, T, P, L, phase, w, gamma, init, C, shifts);
-    if (!s.thr.error.empty()) return s;
-    sort_records(n, T, rec_set, rec_node, rec_offset, rec_kind, R, ptr, s);
-    s.zeros = std::move(zeros); s.records = std::move(records);
-    s.horizons.assign(horizons, horizons + H);
+    stage_records(who, n, nnz, T, P, L, phase, w, gamma, init, C, shifts, rec_set, rec_node, rec_offset, rec_kind, R, O, s);
+    if (s.thr.error.empty()) s.horizons.assign(horizons, horizons + H);
     return s;
+}
+std::vector<SirUpload> SirPostStaged::uploads(const SirPostLayout& W) const {
+    std::vector<SirUpload> up = SirTimedStaged::uploads(W);
+    up.push_back(upload(W.horizons, horizons));
+    return up;
 }

@@ -24,9 +24,10 @@ struct SirLayout {
     size_t start;      // uint64 [2][n] start thresholds thr(pS) | thr(pR): behind the per-edge form, the largest of the rate forms'
     size_t bytes[4];   // the workspace of SIR_SCALAR (= thr), SIR_NODES, SIR_EDGES (= start) and SIR_INIT
 };
-// static_lds, wherever it appears: the static LDS an instance keeps beyond the few counters all of them have (the SCORE
-// instances' tallies, kSirScoreLds; 0 for every other instance).  It moves the boundary of the lists-in-LDS form and of the
-// scan's state in LDS, and with them the size of `tail`, and it counts in the workgroups per CU.
+// static_lds, wherever it appears: the static LDS an instance keeps beyond the few counters all of them have -- what the scored
+// sweeps' output policies hold there (kSirScoreLds, kSirTimedLds, kSirPostLds below; 0 for the plain sweep and for every instance
+// that is not a sweep).  It moves the boundary of the lists-in-LDS form and of the scan's state in LDS, and with them the size of
+// `tail`, and it counts in the workgroups per CU.
 SirLayout sir_layout(int n, int64_t nnz, int n_bigrow, int T, size_t static_lds = 0);
 
 // LDS of the frontier kernel: bitmaps + 1 KB of coin queue per wave (+ three uint16 node lists when they fit: n <= 11 232 without long rows)
@@ -83,6 +84,9 @@ SirSweepLayout sir_sweep_layout(int n, int64_t nnz, int n_bigrow, int T, int P, 
 // all 0) is >= 0 with shift + T <= L; phase[1 .. L-1] in [0, P).  A refusal names `who` and the offending index.
 SirThresholds sir_stage_sweep(const char* who, int n, int64_t nnz, int T, int P, int L, const int32_t* phase, const double* w,
                               const double* gamma, const double* init, int C, const int32_t* shifts);
+// One staged array of a call on its way to the device: `bytes` from `from` go to the workspace offset `at`.  What a scored sweep
+// staged beyond the thresholds is a list of these (uploads() below), so that the call copies them without knowing the output.
+struct SirUpload { size_t at; const void* from; size_t bytes; };
 
 // Monte-Carlo source scores (gnode_sir_mc_philox_sweep_scores, the SCORE instances): the sweep's trajectories, each step of each
 // compared with O snapshots.  At most GN_SIR_SCORE_MAXO snapshots per call: the kernels keep two int32 tallies per snapshot in
@@ -106,6 +110,7 @@ struct SirScoreStaged {
     SirThresholds thr;
     std::vector<int8_t> obs;         // [n][O]
     std::vector<int32_t> marked, seen;
+    std::vector<SirUpload> uploads(const SirScoreLayout& W) const;
 };
 SirScoreStaged sir_stage_score(const char* who, int n, int64_t nnz, int T, int P, int L, const int32_t* phase, const double* w,
                                const double* gamma, const double* init, int C, const int32_t* shifts, const int8_t* obs, int O, int measure,
@@ -138,6 +143,7 @@ struct SirTimedStaged {
     std::vector<int32_t> rec_ptr;    // [n + 1]
     std::vector<uint32_t> rec;       // [R]
     std::vector<int32_t> zeros, records;
+    std::vector<SirUpload> uploads(const SirTimedLayout& W) const;
 };
 SirTimedStaged sir_stage_timed(const char* who, int n, int64_t nnz, int T, int P, int L, const int32_t* phase, const double* w,
                                const double* gamma, const double* init, int C, const int32_t* shifts, const int32_t* rec_set,
@@ -152,12 +158,8 @@ SirTimedStaged sir_stage_timed(const char* who, int n, int64_t nnz, int T, int P
 #define GN_SIR_POST_MAXH 32
 #endif
 static const size_t kSirPostLds = (size_t)GN_SIR_SCORE_MAXO * sizeof(int32_t);
-// The sweep's layout (its `tail` sized for the POST instances' boundaries), then the records staged as SirTimedLayout has them,
-// then the horizons.
-struct SirPostLayout : SirSweepLayout {
-    size_t rec_ptr;                  // int32 [n + 1]
-    size_t rec;                      // uint32 [R]
-    size_t zeros, records;           // int32 [O] each
+// SirTimedLayout (its `tail` sized for the POST instances' boundaries), then the horizons.
+struct SirPostLayout : SirTimedLayout {
     size_t horizons;                 // int32 [H]
 };
 SirPostLayout sir_post_layout(int n, int64_t nnz, int n_bigrow, int T, int P, int L, int C, int O, int R, int H);
@@ -167,6 +169,7 @@ SirPostLayout sir_post_layout(int n, int64_t nnz, int n_bigrow, int T, int P, in
 // offending index, and nothing is staged.
 struct SirPostStaged : SirTimedStaged {
     std::vector<int32_t> horizons;   // [H]
+    std::vector<SirUpload> uploads(const SirPostLayout& W) const;
 };
 SirPostStaged sir_stage_post(const char* who, int n, int64_t nnz, int T, int P, int L, const int32_t* phase, const double* w,
                              const double* gamma, const double* init, int C, const int32_t* shifts, const int32_t* rec_set,

@@ -606,10 +606,29 @@ def _accumulator(who, name, t, shape):
         raise ValueError(f"{who}: {name} must be a contiguous int64 tensor of shape {tuple(shape)}")
 
 
+def _mc_bins(who, bins):
+    """The bins of a Monte-Carlo scorer's histogram: a whole number in 1 .. 4096."""
+    bins = _whole(who, "bins", bins, 1)
+    if bins > 4096:
+        raise ValueError(f"{who}: bins = {bins} exceeds 4096")
+    return bins
+
+
+def _record_groups(sets, group):
+    """(o0, which, node, off, kind) per launch of a timed call: the evidence sets o0 .. o0 + group - 1 of `sets` (_timed_records) as
+    four int32 arrays, `which` naming each record's set within the group."""
+    for o0 in range(0, len(sets), group):
+        part = sets[o0:o0 + group]
+        which = np.concatenate([np.full(len(s[0]), i, dtype=np.int32) for i, s in enumerate(part)])
+        node, off, kind = (np.ascontiguousarray(np.concatenate([s[j] for s in part])) for j in range(3))
+        yield o0, which, node, off, kind
+
+
 class _McSweep:
-    """The arguments `outbreak_sizes_mc` and `source_scores_mc` share, checked on the host (ValueError) before the library is
-    loaded or a graph handle is made: the graph, maxTime / sims / sim_offset, the action, the start, the candidates, the
-    shifts and the rates as one schedule over max(shifts) + maxTime calendar steps."""
+    """The arguments `outbreak_sizes_mc`, `source_scores_mc`, `source_scores_timed_mc` and `posterior_states_mc` share,
+    checked on the host (ValueError) before the library is loaded or a graph handle is made: the graph, maxTime / sims /
+    sim_offset, the action, the start, the candidates, the shifts and the rates as one schedule over max(shifts) + maxTime
+    calendar steps."""
 
     def __init__(self, who, graph, beta, gamma, sims, maxTime, candidates, action, start, shifts, sim_offset):
         self.graph, self.made = graph, hasattr(graph, "handle")     # a DeviceGraph: it carries its host CSR
@@ -719,9 +738,7 @@ def source_scores_mc(graph, obs, beta, gamma, sims, maxTime, candidates=None, st
     a = _McSweep(who, graph, beta, gamma, sims, maxTime, candidates, "seed", start, shifts, sim_offset)
     if measure not in _MC_MEASURES:
         raise ValueError(f"{who}: measure must be one of {sorted(_MC_MEASURES)}, got {measure!r}")
-    bins = _whole(who, "bins", bins, 1)
-    if bins > 4096:
-        raise ValueError(f"{who}: bins = {bins} exceeds 4096")
+    bins = _mc_bins(who, bins)
     if isinstance(obs, torch.Tensor):
         obs = obs.detach().cpu().numpy()
     ob = np.asarray(obs)
@@ -823,9 +840,7 @@ def source_scores_timed_mc(graph, observations, beta, gamma, sims, maxTime, cand
         if most > 4096:
             raise ValueError(f"{who}: an evidence set holds {most} records, more than 4096 bins: give bins")
         bins = most
-    bins = _whole(who, "bins", bins, 1)
-    if bins > 4096:
-        raise ValueError(f"{who}: bins = {bins} exceeds 4096")
+    bins = _mc_bins(who, bins)
     group = min(SIR_SCORE_MAXO, SIR_TIMED_CELLS // T)
     if min(O, group) * C_ * T * (bins + 1) >= 2**31:
         raise ValueError(f"{who}: {min(O, group)} x {C_} x {T} x {bins + 1} histogram cells per launch reach 2^31: fewer bins or candidates")
@@ -834,11 +849,8 @@ def source_scores_timed_mc(graph, observations, beta, gamma, sims, maxTime, cand
     dev = hist.device if hist is not None else device
     if hist is None:
         hist = torch.zeros((O, C_, T, bins + 1), dtype=torch.int64, device=dev)
-    for o0 in range(0, O if sims > 0 else 0, group):               # a group's slice of hist is contiguous: o is the slowest axis
-        part = sets[o0:o0 + group]
-        og = len(part)
-        which = np.concatenate([np.full(len(s[0]), i, dtype=np.int32) for i, s in enumerate(part)])
-        node, off, kind = (np.ascontiguousarray(np.concatenate([s[j] for s in part])) for j in range(3))
+    for o0, which, node, off, kind in _record_groups(sets if sims > 0 else [], group):   # a group's slice of hist is contiguous: o is the slowest axis
+        og = min(group, O - o0)
         ws = torch.empty(lib.gnode_sir_sweep_timed_workspace_bytes(g.handle, T, a.sched.P, a.L, C_, og, len(which)), dtype=torch.uint8, device=dev)
         _lib.check(lib.gnode_sir_mc_philox_sweep_timed(g.handle, *a.sweep_args(), _lib.host_ptr(which), _lib.host_ptr(node), _lib.host_ptr(off),
                                                        _lib.host_ptr(kind), len(which), og, bins, sims, a.sim_offset, T, C.c_uint64(rng_seed),
@@ -938,11 +950,8 @@ def posterior_states_mc(graph, observations, beta, gamma, sims, maxTime, now, ho
     if accepted is None:
         accepted = torch.zeros((O, C_), dtype=torch.int64, device=dev)
     hz32 = np.ascontiguousarray(hz, dtype=np.int32)
-    for o0 in range(0, O if sims > 0 else 0, SIR_SCORE_MAXO):      # a group's slices are contiguous: o is the slowest axis of both
-        part = sets[o0:o0 + SIR_SCORE_MAXO]
-        og = len(part)
-        which = np.concatenate([np.full(len(s[0]), i, dtype=np.int32) for i, s in enumerate(part)])
-        node, off, kind = (np.ascontiguousarray(np.concatenate([s[j] for s in part])) for j in range(3))
+    for o0, which, node, off, kind in _record_groups(sets if sims > 0 else [], SIR_SCORE_MAXO):   # a group's slices are contiguous: o is the slowest axis of both
+        og = min(SIR_SCORE_MAXO, O - o0)
         ws = torch.empty(lib.gnode_sir_sweep_posterior_workspace_bytes(g.handle, T, a.sched.P, a.L, C_, og, len(which), H), dtype=torch.uint8, device=dev)
         _lib.check(lib.gnode_sir_mc_philox_sweep_posterior(g.handle, *a.sweep_args(), _lib.host_ptr(which), _lib.host_ptr(node), _lib.host_ptr(off),
                                                            _lib.host_ptr(kind), len(which), og, now, _lib.host_ptr(hz32), H, sims, a.sim_offset, T,
