@@ -43,8 +43,9 @@
 // The candidate sweep (gnode_sir_mc_philox_sweep and its _scores, _timed and _posterior forms; INIT and SCHED instances only): one
 // launch runs C x sims jobs, job (c, s) being trajectory s from the drawn start with candidate c's node overridden and the phase
 // row read from the candidate's shift on.  What a job puts out -- sums per (candidate, step, compartment), binned similarities
-// with snapshots, binned agreement with timed records, or per-node counts of the trajectories that match them -- is the kernel's
-// output policy, its type parameter OUT and its last two arguments (the jobs, the policy): gnode_sir_sweep.h states the five
+// with snapshots, binned agreement with timed records, per-node counts of the trajectories that match them, or those counts by
+// the number of records missed -- is the kernel's
+// output policy, its type parameter OUT and its last two arguments (the jobs, the policy): gnode_sir_sweep.h states the six
 // policies, the hooks the two step kernels call at every event, every closed step and the end of a job, and the host half of
 // each output.  An instance that is not a sweep takes the empty policy and compiles to what it was; a sweep has no histogram,
 // no events and no curves.
@@ -1175,6 +1176,18 @@ extern "C" int gnode_sir_mc_philox_sweep_posterior(gnode_graph_t g, const double
                                                    void* workspace, size_t workspace_bytes, void* stream, int32_t edge_scan) {
     return sir_sweep_impl(SIR_SWEEP_CALL("gnode_sir_mc_philox_sweep_posterior"),
                           SirPosteriorOutput{{rec_set, rec_node, rec_offset, rec_kind, R, O}, now, horizons_host, H, counts, accepted});
+}
+// The posterior by the number of missed records (SirPosteriorStrata): a trajectory that misses d <= mismatches records of a set is
+// counted for it in stratum d; the posterior's workspace.
+extern "C" int gnode_sir_mc_philox_sweep_posterior_strata(gnode_graph_t g, const double* init_host, const int32_t* candidates_host,
+                                                          const int32_t* shifts_host, int32_t C, int32_t action, const int32_t* phase_host, int32_t P,
+                                                          int32_t L, const double* w_host, const double* gamma_host, const int32_t* rec_set,
+                                                          const int32_t* rec_node, const int32_t* rec_offset, const int32_t* rec_kind, int32_t R, int32_t O,
+                                                          int32_t now, const int32_t* horizons_host, int32_t H, int32_t mismatches, int64_t sims,
+                                                          int64_t sim_offset, int32_t T, uint64_t rng_seed, uint64_t* counts, uint64_t* accepted,
+                                                          void* workspace, size_t workspace_bytes, void* stream, int32_t edge_scan) {
+    return sir_sweep_impl(SIR_SWEEP_CALL("gnode_sir_mc_philox_sweep_posterior_strata"),
+                          SirStrataOutput{{{rec_set, rec_node, rec_offset, rec_kind, R, O}, now, horizons_host, H, counts, accepted}, mismatches});
 }
 
 extern "C" int gnode_sir_mc_coins(const int32_t* table_src, const int32_t* table_dst, int64_t n_table, int32_t n,

@@ -364,6 +364,23 @@ SirPostStaged sir_stage_post(const char* who, int n, int64_t nnz, int T, int P, 
     if (s.thr.error.empty()) s.horizons.assign(horizons, horizons + H);
     return s;
 }
+SirPostStaged sir_stage_strata(const char* who, int n, int64_t nnz, int T, int P, int L, const int32_t* phase, const double* w,
+                               const double* gamma, const double* init, int C, const int32_t* shifts, const int32_t* rec_set,
+                               const int32_t* rec_node, const int32_t* rec_offset, const int32_t* rec_kind, int R, int O, int now,
+                               const int32_t* horizons, int H, int mismatches) {
+    char buf[256];
+    SirPostStaged s;                                                   // (a refusal: nothing staged, only thr.error)
+#define refuse_strata(...) (s = SirPostStaged(), s.thr = refuse(__VA_ARGS__), s)
+    if (mismatches < 0 || mismatches > GN_SIR_POST_MAXD - 1)
+        return refuse_strata("%s: mismatches = %d is not in [0, %d]", who, mismatches, GN_SIR_POST_MAXD - 1);
+    s = sir_stage_post(who, n, nnz, T, P, L, phase, w, gamma, init, C, shifts, rec_set, rec_node, rec_offset, rec_kind, R, O, now, horizons, H);
+    if (!s.thr.error.empty()) return s;
+    const int D = mismatches + 1;                                      // (O, H and n have passed the posterior's checks)
+    if (!cells_fit(O * D, H, 2, n))
+        return refuse_strata("%s: the counts [O = %d][D = %d][H = %d][2][n = %d] have 2^31 cells or more", who, O, D, H, n);
+#undef refuse_strata
+    return s;
+}
 std::vector<SirUpload> SirPostStaged::uploads(const SirPostLayout& W) const {
     std::vector<SirUpload> up = SirTimedStaged::uploads(W);
     up.push_back(upload(W.horizons, horizons));

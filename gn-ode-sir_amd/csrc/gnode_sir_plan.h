@@ -157,6 +157,9 @@ SirTimedStaged sir_stage_timed(const char* who, int n, int64_t nnz, int T, int P
 #ifndef GN_SIR_POST_MAXH
 #define GN_SIR_POST_MAXH 32
 #endif
+#ifndef GN_SIR_POST_MAXD
+#define GN_SIR_POST_MAXD 8           // the strata of sir_stage_strata, below
+#endif
 static const size_t kSirPostLds = (size_t)GN_SIR_SCORE_MAXO * sizeof(int32_t);
 // SirTimedLayout (its `tail` sized for the POST instances' boundaries), then the horizons.
 struct SirPostLayout : SirTimedLayout {
@@ -175,3 +178,13 @@ SirPostStaged sir_stage_post(const char* who, int n, int64_t nnz, int T, int P, 
                              const double* gamma, const double* init, int C, const int32_t* shifts, const int32_t* rec_set,
                              const int32_t* rec_node, const int32_t* rec_offset, const int32_t* rec_kind, int R, int O, int now,
                              const int32_t* horizons, int H);
+
+// The posterior by the number of missed records (gnode_sir_mc_philox_sweep_posterior_strata, the STRATA instances): a trajectory
+// that misses d <= mismatches records of a set is accepted for it in stratum d, at most GN_SIR_POST_MAXD strata.  The workspace,
+// the layout and the LDS are the posterior's: the strata size only the caller's outputs, counts [O][D][H][2][n] and accepted
+// [O][C][D], D = mismatches + 1.  sir_stage_post's checks and staging, and two more in front of the records': mismatches in
+// [0, GN_SIR_POST_MAXD - 1] and O * D * H * 2 * n < 2^31.
+SirPostStaged sir_stage_strata(const char* who, int n, int64_t nnz, int T, int P, int L, const int32_t* phase, const double* w,
+                               const double* gamma, const double* init, int C, const int32_t* shifts, const int32_t* rec_set,
+                               const int32_t* rec_node, const int32_t* rec_offset, const int32_t* rec_kind, int R, int O, int now,
+                               const int32_t* horizons, int H, int mismatches);

@@ -17,7 +17,7 @@
 //   finish      the end of a job, every event behind a barrier
 // state_of(v) is 0 / 1 / 2 = S / I / R off the kernel's own state: the scan's byte, the frontier's two bitmaps.  The coins, the
 // order of the jobs and every address below are the kernels' and the entries' (include/gnode.h); integer adds commute, so every
-// output is exact whatever the order of the jobs.  The host half of each output is at the end (SirSumsOutput .. SirPosteriorOutput).
+// output is exact whatever the order of the jobs.  The host half of each output is at the end (SirSumsOutput .. SirStrataOutput).
 #pragma once
 #include "gnode_common.h"
 #include "gnode_sir_plan.h"
@@ -251,9 +251,53 @@ struct SirPosteriorCounts : SirOutputDefaults, SirRecords {
         if (jb.acc) for (; jb.hj < H; ++jb.hj) count(jb.acc, jb.hj, n, tid, nthr, state_of);
     }
 };
+
+// Nowcast and forecast from evidence that may be wrong (gnode_sir_mc_philox_sweep_posterior_strata): SirPosteriorCounts with the
+// accepted jobs kept apart by the number of records they MISS.  The records, the LDS (agree[o][now] per set and the mask word),
+// reset, event, steps and the Job are the base's, unchanged; what is judged at step `now` is d = records[o] - lds[o] instead of
+// equality.  With d <= M, M = mismatches in [0, GN_SIR_POST_MAXD), D = M + 1, the job is accepted for set o in STRATUM d: one is
+// added to accepted[o][c][d], uint64 [O][C][D], and bit o enters the mask.  No event after step `now` moves lds[o] (pos >= it >
+// now), so at every later horizon d is read off it again -- no LDS of its own -- and the walk of the nodes, one lane per node,
+// adds to counts[o][d][j][st - 1][v], uint64 [O][D][H][2][n]: one set after the other, d and the plane's base found once per
+// set in front of the walk, a wave's adds to one plane contiguous.  Stratum 0 is SirPosteriorCounts' output.
+struct SirPosteriorStrata : SirPosteriorCounts {
+    int M, D;                       // `counts` is [O][D][H][2][n] and `accepted` [O][C][D] here
+    __device__ __forceinline__ uint32_t accept(int* agr, int C, int c, int tid) const {
+        uint32_t* mask = reinterpret_cast<uint32_t*>(agr + GN_SIR_SCORE_MAXO);
+        if (tid < O) {
+            const int d = records[tid] - agr[tid];                 // (agree is in [0, records]: d < 0 cannot be, and accepts nothing)
+            if (d >= 0 && d <= M) { atomicOr(mask, 1u << tid); atomicAdd(&accepted[((size_t)tid * C + c) * D + d], 1ull); }
+        }
+        __syncthreads();
+        return *mask;
+    }
+    template <class StateOf> __device__ __forceinline__ void count(const int* agr, uint32_t mask, int j, int n, int tid, int nthr, StateOf state_of) const {
+        for (uint32_t m = mask; m; m &= m - 1u) {
+            const int o = __ffs((int)m) - 1, d = records[o] - agr[o];
+            unsigned long long* plane = counts + (((size_t)o * D + d) * H + j) * 2 * (size_t)n;
+            for (int v = tid; v < n; v += nthr) {
+                const int st = state_of(v);
+                if (st) atomicAdd(&plane[(size_t)(st - 1) * n + v], 1ull);
+            }
+        }
+    }
+    template <class StateOf>
+    __device__ __forceinline__ bool closed(Job& jb, int* agr, const Jobs& sw, int c, int st, int n, int tid, int nthr, StateOf state_of) const {
+        jb.last = st;
+        if (st == now) { jb.acc = accept(agr, sw.C, c, tid); if (!jb.acc) return false; }
+        if (st >= now && jb.hj < H && now + horizons[jb.hj] == st) { count(agr, jb.acc, jb.hj, n, tid, nthr, state_of); ++jb.hj; }
+        return true;
+    }
+    template <class StateOf>
+    __device__ __forceinline__ void finish(Job& jb, int* agr, const Jobs& sw, int c, long, long, int, int, int n, int, int, int tid, int nthr, StateOf state_of) const {
+        if (jb.last < now) jb.acc = accept(agr, sw.C, c, tid);
+        if (jb.acc) for (; jb.hj < H; ++jb.hj) count(agr, jb.acc, jb.hj, n, tid, nthr, state_of);
+    }
+};
 // the launch plan and the workspace layouts count these bytes (gnode_sir_plan.h); the posterior's mask word comes on top, as it always has
 static_assert(SirScores::LDS_INTS * sizeof(int32_t) == kSirScoreLds && SirTimedScores::LDS_INTS * sizeof(int32_t) == kSirTimedLds &&
-              (SirPosteriorCounts::LDS_INTS - 1) * sizeof(int32_t) == kSirPostLds, "the policies' static LDS is the plan's");
+              (SirPosteriorCounts::LDS_INTS - 1) * sizeof(int32_t) == kSirPostLds &&
+              SirPosteriorStrata::LDS_INTS == SirPosteriorCounts::LDS_INTS, "the policies' static LDS is the plan's");
 
 // --------------------------------------------------------------------------- the host half
 // What the four entries share (include/gnode.h documents the arrays) ...
@@ -321,5 +365,17 @@ struct SirPosteriorOutput {
         o.counts = (unsigned long long*)counts; o.accepted = (unsigned long long*)accepted;
     }
 };
+// the posterior's arrays and workspace; `mismatches` sizes only the caller's two outputs
+struct SirStrataOutput {
+    using Policy = SirPosteriorStrata; using Layout = SirPostLayout; using Staged = SirPostStaged;
+    static constexpr size_t static_lds = kSirPostLds; static constexpr bool args_first = true;
+    SirPosteriorOutput post; int32_t mismatches;
+    bool complete() const { return post.complete(); }
+    Layout layout(const SirSweepCall& c) const { return post.layout(c); }
+    Staged stage(const SirSweepCall& c) const {
+        return sir_stage_strata(SIR_SWEEP_INPUT(c), SIR_RECORD_INPUT(post.rec), post.now, post.horizons, post.H, mismatches);
+    }
+    void fill(SirJobs& sw, Policy& o, char* ws, const Layout& W) const { post.fill(sw, o, ws, W); o.M = mismatches; o.D = mismatches + 1; }
+};
 // f(policy) for every output: what registers the instances (gn_sir_set_attributes)
-template <class F> static void sir_each_output(F&& f) { f(SirSums{}); f(SirScores{}); f(SirTimedScores{}); f(SirPosteriorCounts{}); }
+template <class F> static void sir_each_output(F&& f) { f(SirSums{}); f(SirScores{}); f(SirTimedScores{}); f(SirPosteriorCounts{}); f(SirPosteriorStrata{}); }

@@ -94,6 +94,8 @@ ABI = {
     "gnode_sir_sweep_posterior_workspace_bytes": (_sz, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32]),
     "gnode_sir_mc_philox_sweep_posterior": (_int, [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp,
                                                    _i32, _i64, _i64, _i32, _u64, _vp, _vp, _vp, _sz, _vp, _i32]),
+    "gnode_sir_mc_philox_sweep_posterior_strata": (_int, [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32,
+                                                          _vp, _i32, _i32, _i64, _i64, _i32, _u64, _vp, _vp, _vp, _sz, _vp, _i32]),
     "gnode_sir_mc_coins": (_int, [_vp, _vp, _i64, _i32, _vp, _i32, _f64, _f64, _i64, _i32, _vp, _i64, _vp, _pi64, _vp, _sz, _vp]),
     "gnode_dmp_workspace_bytes": (_sz, [_vp]),
     "gnode_dmp_f32": (_int, [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _sz, _vp]),

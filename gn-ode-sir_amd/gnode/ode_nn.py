@@ -960,6 +960,157 @@ def posterior_states_mc(graph, observations, beta, gamma, sims, maxTime, now, ho
     return SirPosterior(counts, accepted, sims, now, tuple(int(h) for h in hz), squeezed)
 
 
+SIR_POST_MAXD = 8                                                   # GN_SIR_POST_MAXD of the library as built: strata per launch
+
+
+class SirPosteriorStrata(NamedTuple):
+    """What `posterior_strata_mc` returns: the accepted trajectories kept apart by the number d of records they miss.  The
+    methods weigh stratum d by w_d -- `error=e`: w_d = (e / (1 - e))^d, the posterior when EACH record independently disagrees
+    with the truth with probability e (a missed test, a date remembered wrongly), whatever it reads instead; a particular wrong
+    reading among several is the caller's to fold into `weights=`, a length-D sequence (flat: "at most M records are wrong").
+    Exactly one of the two is given.  Where `.complete()` is false the strata beyond `mismatches` were dropped at step `now`,
+    and the weighted posterior is that of the noisy records truncated there."""
+    counts: torch.Tensor            # int64 [O, D, H, 2, n]: accepted trajectories of all candidates in stratum d with node v in I (plane 0) / R (plane 1) at now + h
+    accepted: torch.Tensor          # int64 [O, C, D]: the accepted trajectories per evidence set, candidate and stratum
+    sims: int                       # the trajectories per candidate of THIS call
+    now: int
+    horizons: tuple
+    records: tuple                  # the record count of each evidence set
+    squeezed: bool                  # `observations` was one object: the methods drop the evidence-set axis
+
+    def _table(self, x):
+        return x[0] if self.squeezed else x
+
+    @property
+    def mismatches(self) -> int:
+        return int(self.accepted.shape[-1]) - 1
+
+    def weights(self, error) -> torch.Tensor:
+        """float64 [D]: (error / (1 - error)) ** d for 0 <= error < 1; error 0 gives (1, 0, ...), the exact-match posterior"""
+        if isinstance(error, bool) or not isinstance(error, (int, float, np.integer, np.floating)) or not 0.0 <= float(error) < 1.0:
+            raise ValueError(f"SirPosteriorStrata: error must be a number in [0, 1), got {error!r}")
+        d = torch.arange(self.mismatches + 1, dtype=torch.float64, device=self.accepted.device)
+        return torch.full_like(d, float(error) / (1.0 - float(error))) ** d          # (0 ** 0 is 1)
+
+    def _w(self, who, error, weights):
+        if (error is None) == (weights is None):
+            raise ValueError(f"SirPosteriorStrata.{who}: give exactly one of error= and weights=")
+        if weights is None:
+            return self.weights(error)
+        D = self.mismatches + 1
+        try:
+            w = np.asarray(weights, dtype=np.float64)
+        except (TypeError, ValueError):
+            w = None
+        if w is None or w.shape != (D,) or not np.isfinite(w).all() or (w < 0).any() or not (w > 0).any():
+            raise ValueError(f"SirPosteriorStrata.{who}: weights must be {D} finite numbers >= 0, not all zero, got {weights!r}")
+        return torch.as_tensor(w, device=self.accepted.device)
+
+    def by_stratum(self) -> torch.Tensor:
+        """int64 [O, D] ([D]): the accepted trajectories of all candidates per stratum"""
+        return self._table(self.accepted.sum(1))
+
+    def source(self, error=None, weights=None) -> torch.Tensor:
+        """float64 [O, C] ([C]): sum_d w_d accepted[o, c, d] over its sum over c, the posterior over the candidates under a
+        uniform prior; NaN where nothing was accepted"""
+        a = (self.accepted.double() * self._w("source", error, weights)).sum(-1)
+        return self._table(a / a.sum(-1, keepdim=True))
+
+    def marginals(self, error=None, weights=None) -> torch.Tensor:
+        """float64 [O, H, n, 3] ([H, n, 3]): P(v is S, I, R at now + h | evidence) from the weighted counts over the weighted
+        total; NaN where that total is 0"""
+        w = self._w("marginals", error, weights)
+        tot = (self.accepted.sum(1).double() * w).sum(-1)[:, None, None]
+        c = (self.counts.double() * w[:, None, None, None]).sum(1)
+        i, r = c[:, :, 0], c[:, :, 1]
+        return self._table(torch.stack([tot - i - r, i, r], dim=-1) / tot[..., None])
+
+    def ess(self, error=None, weights=None) -> torch.Tensor:
+        """float64 [O] (a scalar tensor): the effective sample size (sum_d w_d A_d)^2 / sum_d w_d^2 A_d, A = `.by_stratum()`;
+        NaN where nothing was accepted"""
+        w = self._w("ess", error, weights)
+        A = self.accepted.sum(1).double()
+        return self._table((A * w).sum(-1) ** 2 / (A * w * w).sum(-1))
+
+    def complete(self) -> torch.Tensor:
+        """bool [O] (a scalar tensor): records[o] <= mismatches -- no stratum is cut off, every trajectory is accepted, and the
+        weighted posterior is the noisy-record posterior exactly"""
+        return self._table(torch.tensor([r <= self.mismatches for r in self.records], dtype=torch.bool))
+
+    def exact(self) -> SirPosterior:
+        """stratum 0 as `posterior_states_mc` returns it (views of the two tensors)"""
+        return SirPosterior(self.counts[:, 0], self.accepted[:, :, 0], self.sims, self.now, self.horizons, self.squeezed)
+
+
+def posterior_strata_mc(graph, observations, beta, gamma, sims, maxTime, now, horizons=(0,), mismatches=1, candidates=None, start=None,
+                        shifts=None, rng_seed=None, sim_offset=0, edge_scan=False, device="cuda", counts: torch.Tensor | None = None,
+                        accepted: torch.Tensor | None = None) -> SirPosteriorStrata:
+    """`posterior_states_mc` from evidence that may be wrong: the same trajectories, records, `now` and horizons, but a
+    trajectory that misses d of an evidence set's records is kept in STRATUM d as long as d <= `mismatches`, instead of being
+    dropped at the first miss.  Returns `SirPosteriorStrata(counts, accepted, sims, now, horizons, records, squeezed)`: accepted
+    int64 [O, C, D] on the GPU, D = mismatches + 1, the trajectories per set, candidate and stratum; counts int64 [O, D, H, 2, n],
+    over the accepted trajectories of ALL candidates in stratum d those in which node v is infected (plane 0) or removed (plane
+    1) at step now + horizons[j] -- exact integers, whatever the launch geometry.  Its methods turn the strata into posteriors:
+    `.marginals(error=e)`, `.source(error=e)` and `.ess(error=e)` weigh stratum d by (e / (1 - e))^d, the posterior when each
+    record INDEPENDENTLY disagrees with the truth with probability e -- for any e, chosen after the launch; `weights=` takes the
+    strata's weights as given (flat: at most `mismatches` records are wrong; a particular wrong reading among several is the
+    caller's to fold in there).  For a set with more records than `mismatches` (`.complete()` is false) the strata beyond
+    `mismatches` are dropped, and the weighted posterior leaves out what they would add: the exact-match posterior's few
+    accepted trajectories (an acceptance of one in a million for 18 records is usual) become the many that miss one or two.
+
+    Stratum 0 is `posterior_states_mc`'s output for the same seed (`.exact()`), a smaller `mismatches` gives the first strata of
+    a larger one, and accepted[o, c, d] == source_scores_timed_mc(set o).hist[c, now, R_o - d] with that function's default bins.
+
+    mismatches: a whole number in [0, 7].  Everything else as in `posterior_states_mc`: all candidates and up to 16 sets share
+    ONE launch, more sets run in groups of 16 on one graph handle; a trajectory that no set of its group accepts ends at step
+    `now`, and none runs past now + max(horizons).  counts=, accepted=: int64 tensors of the output shapes to ACCUMULATE into,
+    for shards of the sims range.  Through `gnode_sir_mc_philox_sweep_posterior_strata`, which synchronises the stream.  What is
+    wrong raises ValueError before the library is loaded or a graph handle is made."""
+    who = "posterior_strata_mc"
+    a = _McSweep(who, graph, beta, gamma, sims, maxTime, candidates, "seed", start, shifts, sim_offset)
+    C_, T, sims = a.C, a.T, a.sims
+    now = _whole(who, "now", now, 0)
+    if now >= T:
+        raise ValueError(f"{who}: now = {now} is not in [0, maxTime = {T})")
+    if isinstance(horizons, (int, float, np.integer, np.floating)) and not isinstance(horizons, bool):
+        horizons = (horizons,)
+    hz = _whole_numbers(who, "horizons", horizons)
+    if hz.ndim != 1 or not 1 <= hz.size <= SIR_POST_MAXH:
+        raise ValueError(f"{who}: 1 to {SIR_POST_MAXH} horizons, got {hz.size}")
+    if hz[0] < 0 or (np.diff(hz) <= 0).any():
+        j = 0 if hz[0] < 0 else int(np.flatnonzero(np.diff(hz) <= 0)[0]) + 1
+        raise ValueError(f"{who}: horizons[{j}] = {int(hz[j])}: horizons are whole numbers >= 0 in ascending order")
+    if now + int(hz[-1]) > T - 1:
+        j = int(np.flatnonzero(now + hz > T - 1)[0])
+        raise ValueError(f"{who}: horizons[{j}] = {int(hz[j])}: now + horizon = {now + int(hz[j])} is past the last step maxTime - 1 = {T - 1}")
+    M = _whole(who, "mismatches", mismatches, 0)
+    if M > SIR_POST_MAXD - 1:
+        raise ValueError(f"{who}: mismatches = {M} is not in [0, {SIR_POST_MAXD - 1}]")
+    squeezed, sets = _timed_records(who, observations, a.n)
+    O, H, D = len(sets), int(hz.size), M + 1
+    if min(O, SIR_SCORE_MAXO) * D * H * 2 * a.n >= 2**31:
+        raise ValueError(f"{who}: {min(O, SIR_SCORE_MAXO)} x {D} x {H} x 2 x {a.n} count cells per launch reach 2^31: fewer horizons or mismatches")
+    _accumulator(who, "counts", counts, (O, D, H, 2, a.n))
+    _accumulator(who, "accepted", accepted, (O, C_, D))
+    if counts is not None and accepted is not None and counts.device != accepted.device:
+        raise ValueError(f"{who}: counts is on {counts.device} and accepted on {accepted.device}")
+    g, lib, rng_seed = a.enter(rng_seed)
+    dev = counts.device if counts is not None else accepted.device if accepted is not None else device
+    if counts is None:
+        counts = torch.zeros((O, D, H, 2, a.n), dtype=torch.int64, device=dev)
+    if accepted is None:
+        accepted = torch.zeros((O, C_, D), dtype=torch.int64, device=dev)
+    hz32 = np.ascontiguousarray(hz, dtype=np.int32)
+    for o0, which, node, off, kind in _record_groups(sets if sims > 0 else [], SIR_SCORE_MAXO):   # a group's slices are contiguous: o is the slowest axis of both
+        og = min(SIR_SCORE_MAXO, O - o0)
+        ws = torch.empty(lib.gnode_sir_sweep_posterior_workspace_bytes(g.handle, T, a.sched.P, a.L, C_, og, len(which), H), dtype=torch.uint8, device=dev)
+        _lib.check(lib.gnode_sir_mc_philox_sweep_posterior_strata(g.handle, *a.sweep_args(), _lib.host_ptr(which), _lib.host_ptr(node), _lib.host_ptr(off),
+                                                                  _lib.host_ptr(kind), len(which), og, now, _lib.host_ptr(hz32), H, M, sims, a.sim_offset, T,
+                                                                  C.c_uint64(rng_seed), _lib.ptr(counts[o0:o0 + og]), _lib.ptr(accepted[o0:o0 + og]),
+                                                                  _lib.ptr(ws), ws.numel(), _lib.stream_ptr(), int(bool(edge_scan))))
+    return SirPosteriorStrata(counts, accepted, sims, now, tuple(int(h) for h in hz), tuple(len(s[0]) for s in sets), squeezed)
+
+
 def sir_counts_counted(graph: DeviceGraph, seed_set, beta, gamma, sims, T, rng_seed, sim_offset=0, device="cuda"):
     """`sir_counts` through the kernel's profiling instantiation: (counts, stats) with stats = what the launch did --
     Philox blocks computed, infection coins drawn, recovery coins drawn, CSR entries read (bench.py's `sir` roofline)."""

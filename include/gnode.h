@@ -624,6 +624,40 @@ int gnode_sir_mc_philox_sweep_posterior(gnode_graph_t g, const double* init_host
                                         uint64_t* counts,     /* device [O][H][2][n], ACCUMULATED */
                                         uint64_t* accepted,   /* device [O][C], ACCUMULATED */
                                         void* workspace, size_t workspace_bytes, void* stream, int32_t edge_scan);
+/* The same nowcast from evidence that may be wrong (no version step: a stale library is known by the missing symbol): the
+ * trajectories, records, `now` and horizons of gnode_sir_mc_philox_sweep_posterior, each trajectory kept by the number of records it
+ * MISSES instead of being dropped at the first.  For trajectory (c, s) and set o, d = records[o] - agree[o][now]; it is ACCEPTED
+ * for set o in STRATUM d when d <= mismatches.
+ *   mismatches  M in [0, 7] (GN_SIR_POST_MAXD - 1 of the build); D = M + 1 strata
+ *   accepted   device uint64 [O][C][D], ACCUMULATED: accepted[o][c][d] += the trajectories of candidate c that miss exactly d
+ *              records of set o.  It is what gnode_sir_mc_philox_sweep_timed adds to hist[o][c][now][records[o] - d] with bins =
+ *              records[o] for the same seed.
+ *   counts     device uint64 [O][D][H][2][n], ACCUMULATED: over the trajectories of ALL candidates accepted for set o in stratum d,
+ *              counts[o][d][j][0][v] += those in which node v is I at model step now + horizons[j], counts[o][d][j][1][v] += those
+ *              in which it is R.  A trajectory that ended early keeps its final state at every later step.
+ * Both by integer atomic adds: exact, whatever the order of the jobs, the grid or the path; shards of the sims range add up.
+ * Stratum 0 is gnode_sir_mc_philox_sweep_posterior's output; the output for a smaller M is the first strata of that for a larger
+ * one; a set with records[o] <= M accepts every trajectory.  Weighted by (e / (1 - e))^d the strata are the posterior when each
+ * record independently contradicts the truth with probability e, exactly where records[o] <= M.  A trajectory that no set
+ * accepts ends at step `now`; none runs past step now + horizons[H - 1].  GNODE_ERR_ARG, before any launch and with both outputs
+ * untouched: what gnode_sir_mc_philox_sweep_posterior refuses, mismatches outside [0, 7] and O * D * H * 2 * n >= 2^31;
+ * GNODE_ERR_WORKSPACE: a workspace shorter than gnode_sir_sweep_posterior_workspace_bytes(g, T, P, L, C, O, R, H) -- the strata
+ * size only the two outputs.  sims = 0 is valid and touches nothing.  SYNCHRONISES `stream`.  edge_scan as above. */
+int gnode_sir_mc_philox_sweep_posterior_strata(gnode_graph_t g, const double* init_host,    /* host fp64 [n][3] */
+                                               const int32_t* candidates_host,              /* host [C] */
+                                               const int32_t* shifts_host,                  /* host [C], or NULL: all 0 */
+                                               int32_t C, int32_t action,
+                                               const int32_t* phase_host, int32_t P, int32_t L,   /* host [L] */
+                                               const double* w_host,                        /* host fp64 [P][nnz] */
+                                               const double* gamma_host,                    /* host fp64 [P][n] */
+                                               const int32_t* rec_set, const int32_t* rec_node,          /* host [R] each */
+                                               const int32_t* rec_offset, const int32_t* rec_kind, int32_t R, int32_t O,
+                                               int32_t now, const int32_t* horizons_host, int32_t H,     /* host [H] */
+                                               int32_t mismatches,
+                                               int64_t sims, int64_t sim_offset, int32_t T, uint64_t rng_seed,
+                                               uint64_t* counts,     /* device [O][D][H][2][n], ACCUMULATED */
+                                               uint64_t* accepted,   /* device [O][C][D], ACCUMULATED */
+                                               void* workspace, size_t workspace_bytes, void* stream, int32_t edge_scan);
 int gnode_sir_mc_coins(const int32_t* table_src, const int32_t* table_dst, int64_t n_table, int32_t n,
                        const int32_t* seeds_host, int32_t n_seeds, double beta, double gamma, int64_t sims,
                        int32_t T, const double* coins, int64_t n_coins, uint32_t* counts,
