@@ -12,6 +12,7 @@
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 import pickle
 from typing import NamedTuple
@@ -584,20 +585,10 @@ def outbreak_sizes_mc(graph, beta, gamma, sims, maxTime, candidates=None, action
     ACCUMULATE into, for shards of the sims range (sim_offset).  edge_scan=True runs the edge-parallel kernel (same integers).
     Through `gnode_sir_mc_philox_sweep`, which synchronises the stream.  What is wrong raises ValueError before the library is
     loaded or a graph handle is made."""
-    who = "outbreak_sizes_mc"
-    a = _McSweep(who, graph, beta, gamma, sims, maxTime, candidates, action, start, shifts, sim_offset)
-    C_, T, sims = a.C, a.T, a.sims
-    _accumulator(who, "sums", sums, (C_, T, 3))
-    g, lib, rng_seed = a.enter(rng_seed)
-    dev = sums.device if sums is not None else device
-    if sums is None:
-        sums = torch.zeros((C_, T, 3), dtype=torch.int64, device=dev)
-    ever = torch.empty((C_, sims), dtype=torch.int32, device=dev) if per_trajectory else None
-    if sims > 0:
-        ws = torch.empty(lib.gnode_sir_sweep_workspace_bytes(g.handle, T, a.sched.P, a.L, C_), dtype=torch.uint8, device=dev)
-        _lib.check(lib.gnode_sir_mc_philox_sweep(g.handle, *a.sweep_args(), sims, a.sim_offset, T, C.c_uint64(rng_seed), _lib.ptr(sums), _lib.ptr(ever),
-                                                 _lib.ptr(ws), ws.numel(), _lib.stream_ptr(), int(bool(edge_scan))))
-    return SirOutbreakSizes(sums, ever, sims)
+    a = _McSweep("outbreak_sizes_mc", graph, beta, gamma, sims, maxTime, candidates, action, start, shifts, sim_offset)
+    sums, ever = a.launch("gnode_sir_mc_philox_sweep", "gnode_sir_sweep_workspace_bytes", [("sums", sums, (a.C, a.T, 3))], rng_seed, edge_scan, device,
+                          written=[(a.C, a.sims) if per_trajectory else None])
+    return SirOutbreakSizes(sums, ever, a.sims)
 
 
 def _accumulator(who, name, t, shape):
@@ -614,24 +605,53 @@ def _mc_bins(who, bins):
     return bins
 
 
-def _record_groups(sets, group):
-    """(o0, which, node, off, kind) per launch of a timed call: the evidence sets o0 .. o0 + group - 1 of `sets` (_timed_records) as
-    four int32 arrays, `which` naming each record's set within the group."""
-    for o0 in range(0, len(sets), group):
-        part = sets[o0:o0 + group]
+def _mc_groups(evidence, group):
+    """(o0, og, evidence arguments, sizes for the workspace query) per launch of a candidate sweep.  `evidence` None: one
+    launch without evidence, its outputs whole (o0 None).  Snapshot rows (int8 [O, n]) or evidence sets (_timed_records): the
+    rows or sets o0 .. o0 + og - 1, `group` at a time -- the rows as they are, the sets' records as four int32 arrays, `which`
+    naming each record's set within the group."""
+    if evidence is None:
+        yield None, None, (), ()
+        return
+    for o0 in range(0, len(evidence), group):
+        part = evidence[o0:o0 + group]
+        og = len(part)
+        if isinstance(part, np.ndarray):
+            yield o0, og, (_lib.host_ptr(part), og), (og,)
+            continue
         which = np.concatenate([np.full(len(s[0]), i, dtype=np.int32) for i, s in enumerate(part)])
         node, off, kind = (np.ascontiguousarray(np.concatenate([s[j] for s in part])) for j in range(3))
-        yield o0, which, node, off, kind
+        yield o0, og, (*(_lib.host_ptr(x) for x in (which, node, off, kind)), len(which), og), (og, len(which))
+
+
+def _mc_horizons(who, now, horizons, T):
+    """(now, the horizons int64 [H], their int32 copy) of a posterior call: now in [0, T), 1 to SIR_POST_MAXH ascending whole
+    numbers >= 0 (one number is one horizon) with now + h <= T - 1; ValueError otherwise."""
+    now = _whole(who, "now", now, 0)
+    if now >= T:
+        raise ValueError(f"{who}: now = {now} is not in [0, maxTime = {T})")
+    if isinstance(horizons, (int, float, np.integer, np.floating)) and not isinstance(horizons, bool):
+        horizons = (horizons,)
+    hz = _whole_numbers(who, "horizons", horizons)
+    if hz.ndim != 1 or not 1 <= hz.size <= SIR_POST_MAXH:
+        raise ValueError(f"{who}: 1 to {SIR_POST_MAXH} horizons, got {hz.size}")
+    if hz[0] < 0 or (np.diff(hz) <= 0).any():
+        j = 0 if hz[0] < 0 else int(np.flatnonzero(np.diff(hz) <= 0)[0]) + 1
+        raise ValueError(f"{who}: horizons[{j}] = {int(hz[j])}: horizons are whole numbers >= 0 in ascending order")
+    if now + int(hz[-1]) > T - 1:
+        j = int(np.flatnonzero(now + hz > T - 1)[0])
+        raise ValueError(f"{who}: horizons[{j}] = {int(hz[j])}: now + horizon = {now + int(hz[j])} is past the last step maxTime - 1 = {T - 1}")
+    return now, hz, np.ascontiguousarray(hz, dtype=np.int32)
 
 
 class _McSweep:
-    """The arguments `outbreak_sizes_mc`, `source_scores_mc`, `source_scores_timed_mc` and `posterior_states_mc` share,
-    checked on the host (ValueError) before the library is loaded or a graph handle is made: the graph, maxTime / sims /
-    sim_offset, the action, the start, the candidates, the shifts and the rates as one schedule over max(shifts) + maxTime
-    calendar steps."""
+    """The arguments `outbreak_sizes_mc`, `source_scores_mc`, `source_scores_timed_mc`, `posterior_states_mc` and
+    `posterior_strata_mc` share, checked on the host (ValueError) before the library is loaded or a graph handle is made: the
+    graph, maxTime / sims / sim_offset, the action, the start, the candidates, the shifts and the rates as one schedule over
+    max(shifts) + maxTime calendar steps.  `launch` is then the one way into the library for all five."""
 
     def __init__(self, who, graph, beta, gamma, sims, maxTime, candidates, action, start, shifts, sim_offset):
-        self.graph, self.made = graph, hasattr(graph, "handle")     # a DeviceGraph: it carries its host CSR
+        self.who, self.graph, self.made = who, graph, hasattr(graph, "handle")      # a DeviceGraph: it carries its host CSR
         self.host = host = graph if self.made else _HostGraph(graph)
         self.n = n = int(host.n)
         self.T, self.sims, self.sim_offset = _whole(who, "maxTime", maxTime, 1), _whole(who, "sims", sims, 0), _whole(who, "sim_offset", sim_offset, 0)
@@ -680,6 +700,38 @@ class _McSweep:
         s = self.sched
         return (_lib.host_ptr(self.base.p), _lib.host_ptr(self.cand32), _lib.host_ptr(self.sh32), self.C, self.action, _lib.host_ptr(s.phase), s.P,
                 self.L, _lib.host_ptr(s.W), _lib.host_ptr(s.G))
+
+    def launch(self, entry, query, outputs, rng_seed, edge_scan, device, evidence=None, group=None, scalars=(), query_scalars=(), cells=None, written=()):
+        """The last checks, then the launches of `entry`; returns the output tensors, `outputs` and then `written`, in order.
+        outputs: (name, the caller's tensor or None, shape) of each int64 accumulator, by _accumulator; two given ones on different
+        devices are refused, the first given one names the device (else `device`), a missing one is allocated as zeros.
+        written: the shape, or None for an output not wanted, of each int32 output that is written and not accumulated.
+        evidence / group: see _mc_groups; a grouped launch gets rows [o0, o0 + og) of every accumulator (contiguous: o is their
+        slowest axis), and cells = (noun, advice) refuses a first accumulator of 2^31 cells or more per launch.  Per launch the
+        workspace is sized by `query`(handle, T, P, L, C, the group's sizes, *query_scalars) and the entry takes (handle,
+        sweep_args, the group's evidence, *scalars, sims, sim_offset, T, seed, the outputs, workspace, its bytes, stream,
+        edge_scan).  sims == 0: the graph handle is made, nothing is queried or launched."""
+        who = self.who
+        if cells is not None:
+            factors = (min(len(evidence), group), *outputs[0][2][1:])
+            if math.prod(factors) >= 2**31:
+                raise ValueError(f"{who}: {' x '.join(str(f) for f in factors)} {cells[0]} cells per launch reach 2^31: {cells[1]}")
+        for name, t, shape in outputs:
+            _accumulator(who, name, t, shape)
+        given = [(name, t) for name, t, _ in outputs if t is not None]
+        for (first, t), (second, u) in zip(given, given[1:]):
+            if t.device != u.device:
+                raise ValueError(f"{who}: {first} is on {t.device} and {second} on {u.device}")
+        g, lib, seed = self.enter(rng_seed)
+        dev = given[0][1].device if given else device
+        outs = [torch.zeros(shape, dtype=torch.int64, device=dev) if t is None else t for _, t, shape in outputs]
+        more = [None if shape is None else torch.empty(shape, dtype=torch.int32, device=dev) for shape in written]
+        for o0, og, ev_args, ev_sizes in _mc_groups(evidence, group) if self.sims > 0 else ():
+            ws = torch.empty(getattr(lib, query)(g.handle, self.T, self.sched.P, self.L, self.C, *ev_sizes, *query_scalars), dtype=torch.uint8, device=dev)
+            part = outs if o0 is None else [t[o0:o0 + og] for t in outs]
+            _lib.check(getattr(lib, entry)(g.handle, *self.sweep_args(), *ev_args, *scalars, self.sims, self.sim_offset, self.T, C.c_uint64(seed),
+                                           *(_lib.ptr(t) for t in part + more), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(), int(bool(edge_scan))))
+        return (*outs, *more)
 
 
 SIR_SCORE_MAXO = 16                                                 # GN_SIR_SCORE_MAXO of the library as built: snapshots per launch
@@ -753,21 +805,10 @@ def source_scores_mc(graph, obs, beta, gamma, sims, maxTime, candidates=None, st
     if blind.size:
         raise ValueError(f"{who}: snapshot {int(blind[0])} observes no node")
     ob = np.ascontiguousarray(ob, dtype=np.int8)
-    O, C_, T, sims = int(ob.shape[0]), a.C, a.T, a.sims
-    if min(O, SIR_SCORE_MAXO) * C_ * T * (bins + 1) >= 2**31:
-        raise ValueError(f"{who}: {min(O, SIR_SCORE_MAXO)} x {C_} x {T} x {bins + 1} histogram cells per launch reach 2^31: fewer bins or candidates")
-    _accumulator(who, "hist", hist, (O, C_, T, bins + 1))
-    g, lib, rng_seed = a.enter(rng_seed)
-    dev = hist.device if hist is not None else device
-    if hist is None:
-        hist = torch.zeros((O, C_, T, bins + 1), dtype=torch.int64, device=dev)
-    for o0 in range(0, O if sims > 0 else 0, SIR_SCORE_MAXO):       # a group's slice of hist is contiguous: o is the slowest axis
-        og = min(SIR_SCORE_MAXO, O - o0)
-        ws = torch.empty(lib.gnode_sir_sweep_scores_workspace_bytes(g.handle, T, a.sched.P, a.L, C_, og), dtype=torch.uint8, device=dev)
-        _lib.check(lib.gnode_sir_mc_philox_sweep_scores(g.handle, *a.sweep_args(), _lib.host_ptr(ob[o0:o0 + og]), og, _MC_MEASURES[measure], bins, sims,
-                                                        a.sim_offset, T, C.c_uint64(rng_seed), _lib.ptr(hist[o0:o0 + og]), _lib.ptr(ws), ws.numel(),
-                                                        _lib.stream_ptr(), int(bool(edge_scan))))
-    return SirSourceScores(hist, sims, bins, squeezed)
+    hist, = a.launch("gnode_sir_mc_philox_sweep_scores", "gnode_sir_sweep_scores_workspace_bytes", [("hist", hist, (int(ob.shape[0]), a.C, a.T, bins + 1))],
+                     rng_seed, edge_scan, device, evidence=ob, group=SIR_SCORE_MAXO, scalars=(_MC_MEASURES[measure], bins),
+                     cells=("histogram", "fewer bins or candidates"))
+    return SirSourceScores(hist, a.sims, bins, squeezed)
 
 
 SIR_TIMED_CELLS = 2048                                              # GN_SIR_TIMED_CELLS of the library as built: sets x maxTime per launch
@@ -831,31 +872,20 @@ def source_scores_timed_mc(graph, observations, beta, gamma, sims, maxTime, cand
     loaded or a graph handle is made."""
     who = "source_scores_timed_mc"
     a = _McSweep(who, graph, beta, gamma, sims, maxTime, candidates, "seed", start, shifts, sim_offset)
-    C_, T, sims = a.C, a.T, a.sims
+    T = a.T
     if T > SIR_TIMED_CELLS:
         raise ValueError(f"{who}: maxTime = {T} exceeds the {SIR_TIMED_CELLS} steps one evidence set can be tallied over")
     squeezed, sets = _timed_records(who, observations, a.n)
-    O, most = len(sets), max(len(s[0]) for s in sets)
+    most = max(len(s[0]) for s in sets)
     if bins is None:
         if most > 4096:
             raise ValueError(f"{who}: an evidence set holds {most} records, more than 4096 bins: give bins")
         bins = most
     bins = _mc_bins(who, bins)
-    group = min(SIR_SCORE_MAXO, SIR_TIMED_CELLS // T)
-    if min(O, group) * C_ * T * (bins + 1) >= 2**31:
-        raise ValueError(f"{who}: {min(O, group)} x {C_} x {T} x {bins + 1} histogram cells per launch reach 2^31: fewer bins or candidates")
-    _accumulator(who, "hist", hist, (O, C_, T, bins + 1))
-    g, lib, rng_seed = a.enter(rng_seed)
-    dev = hist.device if hist is not None else device
-    if hist is None:
-        hist = torch.zeros((O, C_, T, bins + 1), dtype=torch.int64, device=dev)
-    for o0, which, node, off, kind in _record_groups(sets if sims > 0 else [], group):   # a group's slice of hist is contiguous: o is the slowest axis
-        og = min(group, O - o0)
-        ws = torch.empty(lib.gnode_sir_sweep_timed_workspace_bytes(g.handle, T, a.sched.P, a.L, C_, og, len(which)), dtype=torch.uint8, device=dev)
-        _lib.check(lib.gnode_sir_mc_philox_sweep_timed(g.handle, *a.sweep_args(), _lib.host_ptr(which), _lib.host_ptr(node), _lib.host_ptr(off),
-                                                       _lib.host_ptr(kind), len(which), og, bins, sims, a.sim_offset, T, C.c_uint64(rng_seed),
-                                                       _lib.ptr(hist[o0:o0 + og]), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(), int(bool(edge_scan))))
-    return SirSourceScores(hist, sims, bins, squeezed)
+    hist, = a.launch("gnode_sir_mc_philox_sweep_timed", "gnode_sir_sweep_timed_workspace_bytes", [("hist", hist, (len(sets), a.C, T, bins + 1))],
+                     rng_seed, edge_scan, device, evidence=sets, group=min(SIR_SCORE_MAXO, SIR_TIMED_CELLS // T), scalars=(bins,),
+                     cells=("histogram", "fewer bins or candidates"))
+    return SirSourceScores(hist, a.sims, bins, squeezed)
 
 
 SIR_POST_MAXH = 32                                                  # GN_SIR_POST_MAXH of the library as built: horizons per launch
@@ -920,44 +950,14 @@ def posterior_states_mc(graph, observations, beta, gamma, sims, maxTime, now, ho
     the stream.  What is wrong raises ValueError before the library is loaded or a graph handle is made."""
     who = "posterior_states_mc"
     a = _McSweep(who, graph, beta, gamma, sims, maxTime, candidates, "seed", start, shifts, sim_offset)
-    C_, T, sims = a.C, a.T, a.sims
-    now = _whole(who, "now", now, 0)
-    if now >= T:
-        raise ValueError(f"{who}: now = {now} is not in [0, maxTime = {T})")
-    if isinstance(horizons, (int, float, np.integer, np.floating)) and not isinstance(horizons, bool):
-        horizons = (horizons,)
-    hz = _whole_numbers(who, "horizons", horizons)
-    if hz.ndim != 1 or not 1 <= hz.size <= SIR_POST_MAXH:
-        raise ValueError(f"{who}: 1 to {SIR_POST_MAXH} horizons, got {hz.size}")
-    if hz[0] < 0 or (np.diff(hz) <= 0).any():
-        j = 0 if hz[0] < 0 else int(np.flatnonzero(np.diff(hz) <= 0)[0]) + 1
-        raise ValueError(f"{who}: horizons[{j}] = {int(hz[j])}: horizons are whole numbers >= 0 in ascending order")
-    if now + int(hz[-1]) > T - 1:
-        j = int(np.flatnonzero(now + hz > T - 1)[0])
-        raise ValueError(f"{who}: horizons[{j}] = {int(hz[j])}: now + horizon = {now + int(hz[j])} is past the last step maxTime - 1 = {T - 1}")
+    now, hz, hz32 = _mc_horizons(who, now, horizons, a.T)
     squeezed, sets = _timed_records(who, observations, a.n)
     O, H = len(sets), int(hz.size)
-    if min(O, SIR_SCORE_MAXO) * H * 2 * a.n >= 2**31:
-        raise ValueError(f"{who}: {min(O, SIR_SCORE_MAXO)} x {H} x 2 x {a.n} count cells per launch reach 2^31: fewer horizons")
-    _accumulator(who, "counts", counts, (O, H, 2, a.n))
-    _accumulator(who, "accepted", accepted, (O, C_))
-    if counts is not None and accepted is not None and counts.device != accepted.device:
-        raise ValueError(f"{who}: counts is on {counts.device} and accepted on {accepted.device}")
-    g, lib, rng_seed = a.enter(rng_seed)
-    dev = counts.device if counts is not None else accepted.device if accepted is not None else device
-    if counts is None:
-        counts = torch.zeros((O, H, 2, a.n), dtype=torch.int64, device=dev)
-    if accepted is None:
-        accepted = torch.zeros((O, C_), dtype=torch.int64, device=dev)
-    hz32 = np.ascontiguousarray(hz, dtype=np.int32)
-    for o0, which, node, off, kind in _record_groups(sets if sims > 0 else [], SIR_SCORE_MAXO):   # a group's slices are contiguous: o is the slowest axis of both
-        og = min(SIR_SCORE_MAXO, O - o0)
-        ws = torch.empty(lib.gnode_sir_sweep_posterior_workspace_bytes(g.handle, T, a.sched.P, a.L, C_, og, len(which), H), dtype=torch.uint8, device=dev)
-        _lib.check(lib.gnode_sir_mc_philox_sweep_posterior(g.handle, *a.sweep_args(), _lib.host_ptr(which), _lib.host_ptr(node), _lib.host_ptr(off),
-                                                           _lib.host_ptr(kind), len(which), og, now, _lib.host_ptr(hz32), H, sims, a.sim_offset, T,
-                                                           C.c_uint64(rng_seed), _lib.ptr(counts[o0:o0 + og]), _lib.ptr(accepted[o0:o0 + og]),
-                                                           _lib.ptr(ws), ws.numel(), _lib.stream_ptr(), int(bool(edge_scan))))
-    return SirPosterior(counts, accepted, sims, now, tuple(int(h) for h in hz), squeezed)
+    counts, accepted = a.launch("gnode_sir_mc_philox_sweep_posterior", "gnode_sir_sweep_posterior_workspace_bytes",
+                                [("counts", counts, (O, H, 2, a.n)), ("accepted", accepted, (O, a.C))], rng_seed, edge_scan, device,
+                                evidence=sets, group=SIR_SCORE_MAXO, scalars=(now, _lib.host_ptr(hz32), H), query_scalars=(H,),
+                                cells=("count", "fewer horizons"))
+    return SirPosterior(counts, accepted, a.sims, now, tuple(int(h) for h in hz), squeezed)
 
 
 SIR_POST_MAXD = 8                                                   # GN_SIR_POST_MAXD of the library as built: strata per launch
@@ -1068,47 +1068,17 @@ def posterior_strata_mc(graph, observations, beta, gamma, sims, maxTime, now, ho
     wrong raises ValueError before the library is loaded or a graph handle is made."""
     who = "posterior_strata_mc"
     a = _McSweep(who, graph, beta, gamma, sims, maxTime, candidates, "seed", start, shifts, sim_offset)
-    C_, T, sims = a.C, a.T, a.sims
-    now = _whole(who, "now", now, 0)
-    if now >= T:
-        raise ValueError(f"{who}: now = {now} is not in [0, maxTime = {T})")
-    if isinstance(horizons, (int, float, np.integer, np.floating)) and not isinstance(horizons, bool):
-        horizons = (horizons,)
-    hz = _whole_numbers(who, "horizons", horizons)
-    if hz.ndim != 1 or not 1 <= hz.size <= SIR_POST_MAXH:
-        raise ValueError(f"{who}: 1 to {SIR_POST_MAXH} horizons, got {hz.size}")
-    if hz[0] < 0 or (np.diff(hz) <= 0).any():
-        j = 0 if hz[0] < 0 else int(np.flatnonzero(np.diff(hz) <= 0)[0]) + 1
-        raise ValueError(f"{who}: horizons[{j}] = {int(hz[j])}: horizons are whole numbers >= 0 in ascending order")
-    if now + int(hz[-1]) > T - 1:
-        j = int(np.flatnonzero(now + hz > T - 1)[0])
-        raise ValueError(f"{who}: horizons[{j}] = {int(hz[j])}: now + horizon = {now + int(hz[j])} is past the last step maxTime - 1 = {T - 1}")
+    now, hz, hz32 = _mc_horizons(who, now, horizons, a.T)
     M = _whole(who, "mismatches", mismatches, 0)
     if M > SIR_POST_MAXD - 1:
         raise ValueError(f"{who}: mismatches = {M} is not in [0, {SIR_POST_MAXD - 1}]")
     squeezed, sets = _timed_records(who, observations, a.n)
     O, H, D = len(sets), int(hz.size), M + 1
-    if min(O, SIR_SCORE_MAXO) * D * H * 2 * a.n >= 2**31:
-        raise ValueError(f"{who}: {min(O, SIR_SCORE_MAXO)} x {D} x {H} x 2 x {a.n} count cells per launch reach 2^31: fewer horizons or mismatches")
-    _accumulator(who, "counts", counts, (O, D, H, 2, a.n))
-    _accumulator(who, "accepted", accepted, (O, C_, D))
-    if counts is not None and accepted is not None and counts.device != accepted.device:
-        raise ValueError(f"{who}: counts is on {counts.device} and accepted on {accepted.device}")
-    g, lib, rng_seed = a.enter(rng_seed)
-    dev = counts.device if counts is not None else accepted.device if accepted is not None else device
-    if counts is None:
-        counts = torch.zeros((O, D, H, 2, a.n), dtype=torch.int64, device=dev)
-    if accepted is None:
-        accepted = torch.zeros((O, C_, D), dtype=torch.int64, device=dev)
-    hz32 = np.ascontiguousarray(hz, dtype=np.int32)
-    for o0, which, node, off, kind in _record_groups(sets if sims > 0 else [], SIR_SCORE_MAXO):   # a group's slices are contiguous: o is the slowest axis of both
-        og = min(SIR_SCORE_MAXO, O - o0)
-        ws = torch.empty(lib.gnode_sir_sweep_posterior_workspace_bytes(g.handle, T, a.sched.P, a.L, C_, og, len(which), H), dtype=torch.uint8, device=dev)
-        _lib.check(lib.gnode_sir_mc_philox_sweep_posterior_strata(g.handle, *a.sweep_args(), _lib.host_ptr(which), _lib.host_ptr(node), _lib.host_ptr(off),
-                                                                  _lib.host_ptr(kind), len(which), og, now, _lib.host_ptr(hz32), H, M, sims, a.sim_offset, T,
-                                                                  C.c_uint64(rng_seed), _lib.ptr(counts[o0:o0 + og]), _lib.ptr(accepted[o0:o0 + og]),
-                                                                  _lib.ptr(ws), ws.numel(), _lib.stream_ptr(), int(bool(edge_scan))))
-    return SirPosteriorStrata(counts, accepted, sims, now, tuple(int(h) for h in hz), tuple(len(s[0]) for s in sets), squeezed)
+    counts, accepted = a.launch("gnode_sir_mc_philox_sweep_posterior_strata", "gnode_sir_sweep_posterior_workspace_bytes",
+                                [("counts", counts, (O, D, H, 2, a.n)), ("accepted", accepted, (O, a.C, D))], rng_seed, edge_scan, device,
+                                evidence=sets, group=SIR_SCORE_MAXO, scalars=(now, _lib.host_ptr(hz32), H, M), query_scalars=(H,),
+                                cells=("count", "fewer horizons or mismatches"))
+    return SirPosteriorStrata(counts, accepted, a.sims, now, tuple(int(h) for h in hz), tuple(len(s[0]) for s in sets), squeezed)
 
 
 def sir_counts_counted(graph: DeviceGraph, seed_set, beta, gamma, sims, T, rng_seed, sim_offset=0, device="cuda"):

@@ -4,10 +4,11 @@ SirPosterior makes of the integers."""
 import ctypes as C
 import os
 import re
-from types import SimpleNamespace
 
 import numpy as np
 import pytest
+
+from sir_host_cases import N, RING, Reached, _obs, lib, no_library, shared_refusals  # noqa: F401
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ARITY = {"gnode_sir_sweep_posterior_workspace_bytes": 8, "gnode_sir_mc_philox_sweep_posterior": 30}
@@ -27,14 +28,6 @@ def test_the_two_entries_are_bound_with_the_headers_arity():
     assert post[24:26] == [C.c_void_p] * 2 and post[26:] == timed[23:]
 
 
-@pytest.fixture(scope="module")
-def lib():
-    from gnode.build import build_lib
-    from gnode import _lib
-    build_lib()
-    return _lib.load()
-
-
 def test_the_version_stays_and_the_entry_refuses_without_a_handle(lib):
     assert lib.gnode_version() == 226                               # a stale library is known by the missing symbol
     assert lib.gnode_sir_sweep_posterior_workspace_bytes(None, 10, 2, 12, 5, 3, 9, 2) == 0
@@ -48,32 +41,10 @@ def test_the_version_stays_and_the_entry_refuses_without_a_handle(lib):
 
 
 # --------------------------------------------------------------------------------------------------------------- refusals
-class Reached(Exception):
-    pass
-
-
-@pytest.fixture
-def no_library(monkeypatch):
-    from gnode import _lib, ode_nn
-
-    def refuse(*a, **k):
-        raise Reached("the library was loaded, or a DeviceGraph made")
-    monkeypatch.setattr(_lib, "load", refuse)
-    monkeypatch.setattr(ode_nn, "DeviceGraph", refuse)
-
-
-N = 6
-RING = (np.arange(0, 2 * N + 1, 2), np.asarray([j % N for i in range(N) for j in sorted(((i - 1) % N, (i + 1) % N))]))
-
-
-def _obs(rows, offsets, n=N):
-    return SimpleNamespace(rows=np.asarray(rows), row_offsets=np.asarray(offsets), n=n)
-
-
 def test_posterior_states_mc_refuses_before_the_library(no_library):
     import torch
     from gnode.dmp import timed_observations
-    from gnode.ode_nn import InitialState, edge_rates, posterior_states_mc, rate_schedule
+    from gnode.ode_nn import posterior_states_mc, rate_schedule
     short = rate_schedule([0.2, 0.4], steps=[0, 0, 0, 1, 1, 0])     # names 6 entries: calendar steps up to 5
     ev = timed_observations(N, [0, 2, 2, 5], [0, -1, 0, -3], [1, 3, 2, 0])
     row = [0, 1, 4, -1, 3, 0]
@@ -90,12 +61,7 @@ def test_posterior_states_mc_refuses_before_the_library(no_library):
         dict(counts=torch.zeros((1, 1, 2, N), dtype=torch.int32)), dict(counts=i64(1, 2, N)), dict(counts=np.zeros((1, 1, 2, N))), dict(counts=i64(1, 1, 2, N + 1)),
         dict(counts=i64(1, 2, 2, N)), dict(accepted=i64(1, 2)), dict(accepted=i64(3)), dict(accepted=torch.zeros((1, 3), dtype=torch.int32)),
         dict(observations=[ev, ev], counts=i64(1, 1, 2, N)), dict(observations=[ev, ev], accepted=i64(1, 3)),
-        # what outbreak_sizes_mc refuses, through the shared checks
-        dict(shifts=[0, -1, 2]), dict(shifts=[0, 1]), dict(shifts="now"), dict(gamma=short, shifts=[0, 3, 0]), dict(gamma=short, maxTime=7),
-        dict(beta=1.5), dict(beta=float("nan")), dict(gamma=-0.1), dict(beta=[0.3] * (N - 1)), dict(gamma=edge_rates(RING, np.full(2 * N, 0.3))),
-        dict(candidates=[0, N]), dict(candidates=[-2]), dict(candidates=[]), dict(candidates=[0.5]),
-        dict(start=[N]), dict(start=InitialState.from_sets(N + 1, [1])),
-        dict(maxTime=0), dict(maxTime=2.5), dict(sims=-1), dict(sims=2.5), dict(sim_offset=-1), dict(sims=10, sim_offset=2**32),
+        *shared_refusals(),                                         # what outbreak_sizes_mc refuses, through the shared checks
     ]
     for change in bad:
         with pytest.raises(ValueError):

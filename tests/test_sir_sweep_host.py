@@ -11,6 +11,7 @@ import pytest
 
 import schedule_cases as K
 import sir_sweep_model as S
+from sir_host_cases import N, RING, Reached, lib, no_library  # noqa: F401
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ARITY = {"gnode_sir_sweep_workspace_bytes": 5, "gnode_sir_mc_philox_sweep": 21}
@@ -26,14 +27,6 @@ def test_the_two_entries_are_bound_with_the_headers_arity():
     assert len(_lib.ABI["gnode_sir_mc_philox_schedule"][1]) == 19   # the scheduled entry is what it was
 
 
-@pytest.fixture(scope="module")
-def lib():
-    from gnode.build import build_lib
-    from gnode import _lib
-    build_lib()
-    return _lib.load()
-
-
 def test_the_size_query_answers_0_and_the_entry_refuses_without_a_handle(lib):
     assert lib.gnode_sir_sweep_workspace_bytes(None, 10, 2, 12, 5) == 0
     init = np.ascontiguousarray(np.tile([1.0, 0.0, 0.0], (4, 1)))
@@ -46,24 +39,6 @@ def test_the_size_query_answers_0_and_the_entry_refuses_without_a_handle(lib):
 
 
 # --------------------------------------------------------------------------------------------------------------- refusals
-class Reached(Exception):
-    pass
-
-
-@pytest.fixture
-def no_library(monkeypatch):
-    from gnode import _lib, ode_nn
-
-    def refuse(*a, **k):
-        raise Reached("the library was loaded, or a DeviceGraph made")
-    monkeypatch.setattr(_lib, "load", refuse)
-    monkeypatch.setattr(ode_nn, "DeviceGraph", refuse)
-
-
-N = 6
-RING = (np.arange(0, 2 * N + 1, 2), np.asarray([j % N for i in range(N) for j in sorted(((i - 1) % N, (i + 1) % N))]))
-
-
 def test_outbreak_sizes_mc_refuses_before_the_library(no_library):
     import torch
     from gnode.ode_nn import InitialState, edge_rates, outbreak_sizes_mc, rate_schedule
